@@ -24,9 +24,14 @@ on a ncclCommInitAll communicator) -- the arrangement a C# / Go caller of the C 
 of the two produced `value`.
 
 `value` is measured with inputs and outputs RESIDENT IN HBM (device pointers in, device pointers out; `config.io`);
-the PCIe-inclusive rate of the same workload is `value_host_ptrs`.
+the PCIe-inclusive rate of the same workload is `value_host_ptrs` (--full).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run does only what `value` needs: set-up, the warm-up steps, the --steps timed steps and the JSON line
+(`ms_per_step` = wall time of the timed region / --steps).  --dump-outputs DIR then writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs).  Everything else below -- the oracle checks, the instrumentation and roofline,
+the other legs and the CPU baseline -- runs with --full only; the --no-* options switch parts of it off again.
+
+Rank 0 prints ONE JSON line.  Besides the contract fields, with --full it carries
   steps_ms      wall time of every timed step (HIP events on the launch stream, resolved after the region's final
                 synchronisation: no extra sync inside the region)
   roofline.frac_of_peak_at_that_clock / e2e_frac_of_peak_at_that_clock
@@ -593,6 +598,25 @@ def sharded_scan_leg(torch, np, dist, D, dev, rank, world, docs_per_gpu, dry, st
     return out
 
 
+DUMP_BYTES = 60_000_000   # (the files stay under 64 MB, .npy headers included)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes {name: array} as out_dir/<name>.npy, float32 as it is and any other type as float64, at most
+    DUMP_BYTES in all.  An array larger than its equal share keeps a fixed, seeded sample of its rows (ascending), so runs
+    with the same arguments write the same rows and two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        keep = max(1, share // (a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64))))
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def flush_c_stdio():
     """RCCL prints a version banner through C stdio when a communicator is made; on a pipe that buffer is flushed at process
     exit, i.e. AFTER the JSON line.  Flushing it right after the communicator exists keeps the JSON line the last line."""
@@ -738,7 +762,7 @@ def main_in_process(args):
     def say(msg):
         print(f"bench.py --in-process: {msg}", file=sys.stderr, flush=True)
 
-    def run_leg(rerank, n_total, steps, warmup):
+    def run_leg(rerank, n_total, steps, warmup, dump_dir=None):
         say(f"{'rerank' if rerank else 'embed'} leg: {n_total} rows over {n} device(s), {warmup} + {steps} steps")
         cfg, tensors, grp = load(synth.minilm_cross_encoder if rerank else synth.minilm_embedder, 1 if rerank else 0)
         cols = 1 if rerank else grp.hidden_size
@@ -778,6 +802,9 @@ def main_in_process(args):
         assert bool(torch.isfinite(first).all()), "outputs are not finite"
         for i in range(1, n):
             assert bool(torch.equal(outs[i].cpu(), first)), f"device {i}'s buffer differs from device 0's after the all-gather"
+        if dump_dir:
+            dump_outputs(dump_dir, {"scores": first[:, 0].numpy(), "order_index": held["order"][0].numpy(),
+                                    "order_score": held["order"][1].numpy()} if rerank else {"embeddings": first.numpy()})
         if rerank:
             order = held["order"]
             assert bool((order[1][:-1] >= order[1][1:]).all()), "order is not descending"
@@ -807,7 +834,7 @@ def main_in_process(args):
 
     rerank = args.workload == "rerank"
     n_total = args.pairs if rerank else n * args.sentences
-    elapsed, per_step, parity, transport, fps, rows0 = run_leg(rerank, n_total, args.steps, args.warmup)
+    elapsed, per_step, parity, transport, fps, rows0 = run_leg(rerank, n_total, args.steps, args.warmup, args.dump_outputs)
     value = n_total * args.steps / elapsed
     what = ("pairs/sec minilm-l6-v2-cross-encoder rerank (seq=128)", "pairs/s") if rerank else \
         ("sentences/sec minilm-l6-v2 batch encode (seq=128)", "sentences/s")
@@ -872,7 +899,16 @@ def main():
                     help="one process drives all --gpus devices through the library's EncoderGroup (kjarni_hip_group_*_allgather)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="plumbing self-test without a GPU: gloo + a host stub instead of the HIP encoder")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: oracle checks, instrumentation and roofline, the rerank / scan / model legs, "
+                         "the host-pointer and ragged extras and the CPU baseline (the --no-* options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps and the line, nothing else
+        for opt in ("no_cpu_baseline", "no_extras", "no_profile", "no_parity_check", "no_rerank_leg", "no_scan", "no_models",
+                    "no_instrument"):
+            setattr(args, opt, True)
 
     if args.in_process:
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
@@ -1105,18 +1141,27 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:   # what a caller of the step receives: every rank holds all rows after the all-gather
+        if rerank:
+            dump_outputs(args.dump_outputs, {"scores": result_holder["scores"].cpu().numpy(),
+                                             "order_index": result_holder["order"][0].numpy(),
+                                             "order_score": result_holder["order"][1].numpy()})
+        else:
+            dump_outputs(args.dump_outputs, {"embeddings": result_holder["emb"].cpu().numpy()})
+
     # sanity on what the step produced
-    if rerank:
-        sc, order = result_holder["scores"], result_holder["order"]
-        assert sc.shape == (n_total,) and bool(torch.isfinite(sc).all()), "rerank scores are not finite"
-        if rank == 0:
-            assert order[0].shape == (n_total,) and bool((order[1][:-1] >= order[1][1:]).all()), "order is not descending"
-            assert bool(torch.equal(torch.sort(order[0]).values, torch.arange(n_total))), "order is not a permutation"
-    else:
-        emb = result_holder["emb"]
-        assert emb.shape == (n_total, H)
-        norms = torch.linalg.vector_norm(emb[:: max(1, n_total // 4096)], dim=1)
-        assert torch.allclose(norms, torch.ones_like(norms), atol=1e-4), "embeddings are not L2-normalised"
+    if args.full:
+        if rerank:
+            sc, order = result_holder["scores"], result_holder["order"]
+            assert sc.shape == (n_total,) and bool(torch.isfinite(sc).all()), "rerank scores are not finite"
+            if rank == 0:
+                assert order[0].shape == (n_total,) and bool((order[1][:-1] >= order[1][1:]).all()), "order is not descending"
+                assert bool(torch.equal(torch.sort(order[0]).values, torch.arange(n_total))), "order is not a permutation"
+        else:
+            emb = result_holder["emb"]
+            assert emb.shape == (n_total, H)
+            norms = torch.linalg.vector_norm(emb[:: max(1, n_total // 4096)], dim=1)
+            assert torch.allclose(norms, torch.ones_like(norms), atol=1e-4), "embeddings are not L2-normalised"
 
     # Parity of what the timed region produced: 64 sampled rows of the LAST timed step's output (this rank's block; the
     # first and last row of the block and of its first 2 048-sentence chunk included) against the CPU oracle on the same
@@ -1343,7 +1388,7 @@ def main():
             "config": {"workload": workload, "rows_per_step": n_total, "rows_per_gpu": n_local, "seq_len": S,
                        "sharding": shard, "weights": f"tests/synth.py family '{args.weights}', random (no checkpoints offline)",
                        "io": "ids / mask and the output vectors resident in HBM (device pointers); the PCIe-inclusive rate of the "
-                             "same workload is value_host_ptrs",
+                             "same workload is value_host_ptrs (--full)",
                        "arrangement": "one process per GPU (kjarni_amd.distributed over torch.distributed; RCCL when N > 1)"},
         }
         if not dry:
