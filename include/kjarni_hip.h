@@ -508,9 +508,17 @@ uint64_t kjarni_hip_decoder_tile_gemm_calls(const KjarniHipDecoder* decoder);
 /* kjarni_hip_decoder_generate with a repetition penalty / n-gram ban: processors on the device (default) or on a host copy
  * of the logits (0), as kjarni_hip_chat_set_device_sampling. */
 void kjarni_hip_decoder_set_device_sampling(KjarniHipDecoder* decoder, int32_t on);
-/* CpuDecoder::forward + final norm + lm head (llama/cpu_decoder.rs:196-219): appends n tokens to the cache;
- * the prompt is processed 8 rows at a time and hidden_out receives the final-normed rows of the LAST block,
- * f32 [((n-1) mod 8) + 1, hidden]; logits_out f32 [vocab] of the last position.  Either may be NULL. */
+/* Positions held in the KV cache (0 on NULL). */
+int32_t kjarni_hip_decoder_cache_len(const KjarniHipDecoder* decoder);
+/* Cache rows [first, first + rows) of one layer, a read-back for tests: k_out (after RoPE) and v_out each receive f32
+ * [rows, num_key_value_heads * head_dim].  An error, with nothing copied, for a layer out of range or
+ * first + rows > cache_len. */
+KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder* decoder, int32_t layer, int32_t first, int32_t rows, float* k_out,
+                                           float* v_out);
+/* CpuDecoder::forward + final norm + lm head (llama/cpu_decoder.rs:196-219): appends n tokens to the cache.  Fewer
+ * than 24 tokens run 8 rows at a time; longer prompts (when the geometry allows) go through the matrix-core route in
+ * 2 048-row chunks.  hidden_out receives the final-normed rows of the LAST 8-row block, f32 [((n-1) mod 8) + 1, hidden];
+ * logits_out f32 [vocab] of the last position.  Either may be NULL. */
 KjarniErrorCode kjarni_hip_decoder_forward(KjarniHipDecoder* decoder, const uint32_t* ids, int32_t n, float* hidden_out,
                                            float* logits_out);
 /* run_generation_loop with DecodingStrategy::Greedy (crates/kjarni-transformers/src/decoder/generator.rs:228-381):

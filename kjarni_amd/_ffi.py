@@ -393,6 +393,8 @@ SIGNATURES = {
                                           POINTER(c_int32), POINTER(C.c_uint64)]),
     "kjarni_hip_decoder_reset": (c_int32, [c_void_p]),
     "kjarni_hip_decoder_tile_gemm_calls": (c_uint64, [c_void_p]),
+    "kjarni_hip_decoder_cache_len": (c_int32, [c_void_p]),
+    "kjarni_hip_decoder_kv_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_set_device_sampling": (None, [c_void_p, c_int32]),
     "kjarni_hip_decoder_forward": (c_int32, [c_void_p, _u32p, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_generate": (c_int32, [c_void_p, _u32p, c_size_t, c_size_t, c_float, c_int32, KjarniTokenCallbackFn, c_void_p,

@@ -14,7 +14,7 @@ using namespace kjarni;
 
 struct KjarniHipDecoder {
     std::unique_ptr<LlmModel> model;
-    std::mutex mu;
+    mutable std::mutex mu;
 };
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_load(const char* model_dir, int32_t device, int32_t weights_dtype, int32_t max_context,
@@ -48,6 +48,23 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_dims(const KjarniHipDecoder* d,
 }
 
 KJARNI_EXPORT uint64_t kjarni_hip_decoder_tile_gemm_calls(const KjarniHipDecoder* d) { return d ? d->model->tile_gemm_calls() : 0; }
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_cache_len(const KjarniHipDecoder* d)
+{
+    if (!d) return 0;
+    std::lock_guard<std::mutex> lock(d->mu);
+    return d->model->cache_len();
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder* d, int32_t layer, int32_t first, int32_t rows, float* k_out,
+                                                         float* v_out)
+{
+    if (!d || !k_out || !v_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->kv_rows(layer, first, rows, k_out, v_out);  // range checked before anything is copied
+    });
+}
 
 KJARNI_EXPORT void kjarni_hip_decoder_set_device_sampling(KjarniHipDecoder* d, int32_t on)
 {

@@ -473,6 +473,18 @@ void LlmModel::last_hidden(float* out, int rows) const
     hip_check(hipMemcpy(out, last_, (size_t)std::min(rows, last_rows_) * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
 }
 
+void LlmModel::kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const
+{
+    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > cache_len_ || rows > cache_len_ - first)
+        throw std::runtime_error("cache rows out of range");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    const size_t kv = (size_t)cfg_.kv_heads * cfg_.head_dim, off = (size_t)first * kv, bytes = (size_t)rows * kv * sizeof(float);
+    const Layer& L = layers_[(size_t)layer];
+    hip_check(hipMemcpy(k_out, L.k_cache + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+    hip_check(hipMemcpy(v_out, L.v_cache + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+}
+
 void LlmModel::logits_to_host(float* out) const
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");

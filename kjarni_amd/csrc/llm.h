@@ -71,8 +71,11 @@ public:
     uint64_t tokens_from_logits() const { return tokens_from_logits_; }
 
     void reset();  // empty KV cache
-    // Appends n tokens (any n: processed 8 rows at a time); the logits of the last position stay on the device.
+    // Appends n tokens (fewer than 24: 8-row passes; more: the matrix-core route in 2 048-row chunks); the logits of the last
+    // position stay on the device.
     void forward(const uint32_t* ids, int n);
+    // Cache rows [first, first + rows) of one layer, K after RoPE and V, f32 [rows, kv_heads * head_dim] each (a test hook).
+    void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
     void last_hidden(float* out, int rows) const;  // final-normed hidden states of the last (<= 8-row) pass
     void logits_to_host(float* out) const;
     uint32_t argmax();

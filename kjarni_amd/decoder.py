@@ -2,6 +2,8 @@
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -20,6 +22,11 @@ class HipDecoder:
         wb = C.c_uint64()
         check_error(lib().kjarni_hip_decoder_dims(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e), C.byref(wb)))
         self.hidden, self.layers, self.vocab, self.context, self.bf16, self.weight_bytes = a.value, b.value, c.value, d.value, bool(e.value), wb.value
+        with open(os.path.join(model_dir, "config.json")) as f:  # the defaults of LlmConfig::from_json
+            cfg = json.load(f)
+        heads = cfg["num_attention_heads"]
+        self.kv_heads = cfg.get("num_key_value_heads", heads)
+        self.head_dim = cfg.get("head_dim", self.hidden // heads)
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -35,6 +42,23 @@ class HipDecoder:
     def tile_gemm_calls(self) -> int:
         """Prompt projections that took the 128 x 128-tile GEMM route since load."""
         return int(lib().kjarni_hip_decoder_tile_gemm_calls(self._h))
+
+    def cache_len(self) -> int:
+        """Positions held in the KV cache."""
+        return int(lib().kjarni_hip_decoder_cache_len(self._h))
+
+    def kv_rows(self, layer: int, first: int = 0, rows: Optional[int] = None):
+        """Cache rows [first, first + rows) of `layer` (default: to the end of the cache): (K after RoPE, V), each f32
+        [rows, kv_heads * head_dim]."""
+        if rows is None:
+            rows = self.cache_len() - first
+        if rows < 0:
+            raise ValueError("first is past the end of the cache")
+        kv = self.kv_heads * self.head_dim
+        k, v = np.empty((rows, kv), np.float32), np.empty((rows, kv), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_kv_rows(self._h, layer, first, rows, f(k), f(v)))
+        return k, v
 
     def forward(self, ids: Sequence[int], fetch: bool = True):
         a = np.ascontiguousarray(ids, np.uint32)

@@ -38,7 +38,9 @@ def rms_norm(x: np.ndarray, weight: np.ndarray, eps: float) -> np.ndarray:
 def rope_inv_freq(head_dim: int, theta: float, scaling: Optional[dict] = None) -> np.ndarray:
     """rope/mod.rs:62-105."""
     half = head_dim // 2
-    base = np.asarray([F32(1.0) / F32(np.power(F32(theta), F32(F32(2 * i) / F32(head_dim)))) for i in range(half)], F32)
+    # theta^(2i/d) as a correctly rounded f32 powf (the reference's f32::powf, libm's powf): numpy's float32 power is
+    # 1 ulp off for some i, which at position p turns that frequency's angle by p ulps
+    base = np.asarray([F32(1.0) / F32(np.float64(F32(theta)) ** np.float64(F32(F32(2 * i) / F32(head_dim)))) for i in range(half)], F32)
     if not scaling or scaling.get("rope_type") != "llama3":
         return base
     factor, lo, hi = F32(scaling["factor"]), F32(scaling["low_freq_factor"]), F32(scaling["high_freq_factor"])

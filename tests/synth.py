@@ -639,8 +639,9 @@ LLAMA_1B = dict(model_type="llama", hidden_size=2048, num_hidden_layers=16, num_
                                   original_max_position_embeddings=8192))
 
 
-def llm_tensors(cfg: dict, seed: int = 0, std: float = 0.05, bf16: bool = False) -> Dict[str, np.ndarray]:
-    """Random-init tensors with the HF names of llama/config.rs:283-330 (q/k/v biases for qwen2)."""
+def llm_tensors(cfg: dict, seed: int = 0, std: float = 0.05, bf16: bool = False, qk_scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """Random-init tensors with the HF names of llama/config.rs:283-330 (q/k/v biases for qwen2).  qk_scale multiplies the
+    std of the q / k projection weights (the same draws): > 1 makes attention peaked instead of near-uniform."""
     rng = np.random.default_rng(seed)
     H, L, I = cfg["hidden_size"], cfg["num_hidden_layers"], cfg["intermediate_size"]
     d = cfg.get("head_dim") or H // cfg["num_attention_heads"]
@@ -659,7 +660,7 @@ def llm_tensors(cfg: dict, seed: int = 0, std: float = 0.05, bf16: bool = False)
         t["lm_head.weight"] = w(cfg["vocab_size"], H, s=0.1)
     for i in range(L):
         p = f"model.layers.{i}"
-        t[f"{p}.self_attn.q_proj.weight"], t[f"{p}.self_attn.k_proj.weight"] = w(H, H), w(kv, H)
+        t[f"{p}.self_attn.q_proj.weight"], t[f"{p}.self_attn.k_proj.weight"] = w(H, H, s=std * qk_scale), w(kv, H, s=std * qk_scale)
         t[f"{p}.self_attn.v_proj.weight"], t[f"{p}.self_attn.o_proj.weight"] = w(kv, H), w(H, H)
         if cfg["model_type"] == "qwen2":
             t[f"{p}.self_attn.q_proj.bias"], t[f"{p}.self_attn.k_proj.bias"] = w(H, s=0.1).astype(np.float32), w(kv, s=0.1)
@@ -671,11 +672,12 @@ def llm_tensors(cfg: dict, seed: int = 0, std: float = 0.05, bf16: bool = False)
 
 
 def llm_model(path: str, base: dict, seed: int = 0, bf16_values: bool = False, store_bf16: bool = False, std: float = 0.05,
-              **over):
-    """Writes config.json + model.safetensors.  store_bf16: the 2-D weights are stored as BF16 tensors."""
+              qk_scale: float = 1.0, **over):
+    """Writes config.json + model.safetensors.  store_bf16: the 2-D weights are stored as BF16 tensors.  qk_scale: see
+    llm_tensors."""
     cfg = dict(base)
     cfg.update(over)
-    t = llm_tensors(cfg, seed, std=std, bf16=bf16_values or store_bf16)
+    t = llm_tensors(cfg, seed, std=std, bf16=bf16_values or store_bf16, qk_scale=qk_scale)
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "config.json"), "w") as f:
         json.dump(cfg, f, indent=1)

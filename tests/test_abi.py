@@ -101,6 +101,9 @@ def test_null_pointer_handling():
     assert L.kjarni_embedder_encode_batch(None, None, 0, C.byref(f2)) == E.NULL_POINTER
     assert L.kjarni_embedder_dim(None) == 0               # embedder.rs:265-275
     assert L.kjarni_classifier_num_labels(None) == 0
+    f1 = (C.c_float * 1)()
+    assert L.kjarni_hip_decoder_kv_rows(None, 0, 0, 0, f1, f1) == E.NULL_POINTER
+    assert L.kjarni_hip_decoder_cache_len(None) == 0
     # frees tolerate NULL and empty structs (lib.rs:131-174)
     L.kjarni_float_array_free(None)
     L.kjarni_float_2d_array_free(None)
