@@ -515,6 +515,22 @@ int32_t kjarni_hip_decoder_cache_len(const KjarniHipDecoder* decoder);
  * first + rows > cache_len. */
 KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder* decoder, int32_t layer, int32_t first, int32_t rows, float* k_out,
                                            float* v_out);
+/* GGUF checkpoints (model_dir: a `.gguf` file, or a directory without safetensors that holds one; weights_dtype 0 keeps
+ * Q8_0 / Q4_K / Q6_K matrices quantized in HBM, 1 dequantizes everything to f32, 2 to bf16).
+ * config_json: the resolved config (config.json, or the one synthesized from GGUF metadata); free with kjarni_string_free.
+ * weight_bytes_by_type: out[t] = device bytes of weights held in GGML type t (0 F32, 8 Q8_0, 12 Q4_K, 14 Q6_K, 30 BF16), t < n. */
+KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* decoder, char** out);
+KjarniErrorCode kjarni_hip_decoder_weight_bytes_by_type(const KjarniHipDecoder* decoder, uint64_t* out, size_t n);
+/* Host-only GGUF views: the synthesized decoder config, and one tensor by its HF name, dequantized to f32 in HF row order
+ * (*n_out = elements, may exceed capacity; shape_out[0..1] = rows, cols; *ndim_out = 1 or 2). */
+KjarniErrorCode kjarni_gguf_config_json(const char* path, char** out);
+KjarniErrorCode kjarni_gguf_tensor_f32(const char* path, const char* hf_name, float* out, size_t capacity, size_t* n_out, int64_t* shape_out,
+                                       int32_t* ndim_out);
+/* y[m, n] = x[m, k] . W^T with W given as raw GGUF blocks of type ggml_type (8 Q8_0, 12 Q4_K, 14 Q6_K; n rows of k columns) on
+ * host memory, through the decoder's kernels: m < 24 in 8-row GEMV passes (Q6_K on Q8_K activation codes), m >= 24 through the
+ * prompt route (dequantized weights, f32 matrix cores). */
+KjarniErrorCode kjarni_hip_op_linear_ggml(int32_t device, const float* x, int64_t m, const void* blocks, int32_t ggml_type, int32_t n,
+                                          int32_t k, float* y);
 /* CpuDecoder::forward + final norm + lm head (llama/cpu_decoder.rs:196-219): appends n tokens to the cache.  Fewer
  * than 24 tokens run 8 rows at a time; longer prompts (when the geometry allows) go through the matrix-core route in
  * 2 048-row chunks.  hidden_out receives the final-normed rows of the LAST 8-row block, f32 [((n-1) mod 8) + 1, hidden];

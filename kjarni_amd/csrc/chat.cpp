@@ -306,7 +306,7 @@ std::unique_ptr<Chat> Chat::create(const std::string& model_name, const std::str
     if (task == "generation" && !quiet) std::fprintf(stderr, "Warning: [info] Model '%s' is a base model, not instruction-tuned.\n", cli.c_str());
 
     const std::string dir = !model_dir.empty() ? model_dir : model_dir_for(*entry, cache_dir.empty() ? default_cache_dir() : cache_dir);
-    if (!model_files_present(dir))  // DownloadPolicy: this library never downloads
+    if (!decoder_files_present(dir))  // DownloadPolicy: this library never downloads
         throw ModelNotFound("model '" + cli + "' not downloaded. run: kjarni model download " + cli);
 
     auto load_failed = [&](const std::string& why) { return std::runtime_error("failed to load model '" + cli + "': " + why); };

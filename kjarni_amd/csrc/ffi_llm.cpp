@@ -9,6 +9,8 @@
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
 #include "llm.h"
+#include "gguf.h"
+#include "host_util.h"
 
 using namespace kjarni;
 
@@ -114,5 +116,54 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, c
                                                              repetition_penalty, no_repeat_ngram_size, cb);
         *n_out = ids.size();
         if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* d, char** out)
+{
+    if (!d || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = nullptr;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] { *out = dup_cstr(d->model->config_json()); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_weight_bytes_by_type(const KjarniHipDecoder* d, uint64_t* out, size_t n)
+{
+    if (!d || (n && !out)) return KJARNI_ERROR_NULL_POINTER;
+    for (size_t t = 0; t < n; ++t) out[t] = d->model->weight_bytes_of_type((int)t);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_gguf_config_json(const char* path, char** out)
+{
+    if (!path || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = nullptr;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
+        const std::string f = resolve_gguf(path);
+        if (f.empty()) throw ModelNotFound(std::string("no GGUF file at ") + path);
+        GgufFile g;
+        g.open(f);
+        *out = dup_cstr(g.config_json());
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_gguf_tensor_f32(const char* path, const char* hf_name, float* out, size_t capacity, size_t* n_out,
+                                                     int64_t* shape_out, int32_t* ndim_out)
+{
+    if (!path || !hf_name || !n_out || (capacity && !out)) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
+        const std::string f = resolve_gguf(path);
+        if (f.empty()) throw ModelNotFound(std::string("no GGUF file at ") + path);
+        GgufFile g;
+        g.open(f);
+        std::vector<float> v;
+        const std::vector<int64_t> shape = g.read_f32(hf_name, v);
+        *n_out = v.size();
+        if (ndim_out) *ndim_out = (int32_t)shape.size();
+        if (shape_out) {
+            shape_out[0] = shape.size() == 2 ? shape[0] : 1;
+            shape_out[1] = shape.back();
+        }
+        if (capacity) std::memcpy(out, v.data(), std::min(capacity, v.size()) * sizeof(float));
     });
 }

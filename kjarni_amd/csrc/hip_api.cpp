@@ -1,4 +1,5 @@
 // Token-level C ABI (include/kjarni_hip.h).
+#include <memory>
 #include <mutex>
 #include <sys/stat.h>
 
@@ -9,6 +10,9 @@
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
 #include "group.h"
+#include "gguf.h"
+#include "llm_kernels.h"
+#include "quant_kernels.h"
 #include "tuning.h"
 
 using namespace kjarni;
@@ -533,6 +537,59 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_bf16_weights(int32_t device, 
                                                (GemmEpilogue)epilogue, nullptr),
                       "gemm (bf16 weights)");
         });
+        hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_ggml(int32_t device, const float* x, int64_t m, const void* blocks, int32_t ggml_type,
+                                                        int32_t n, int32_t k, float* y)
+{
+    if (!x || !blocks || !y) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        int64_t be = 0, bb = 0;
+        if (!ggml_matrix_type((uint32_t)ggml_type) || !ggml_block_geometry((uint32_t)ggml_type, &be, &bb))
+            throw InvalidConfig(std::string("unsupported GGML matrix type ") + ggml_type_name((uint32_t)ggml_type));
+        if (m < 0 || n <= 0 || k <= 0 || k % 256 != 0) throw InvalidConfig("invalid quantized linear dimensions (k % 256)");
+        use_device(device);
+        if (m == 0) return;
+        const QPlanes planes = repack_ggml((uint32_t)ggml_type, static_cast<const uint8_t*>(blocks), n, k);
+        std::vector<std::unique_ptr<DeviceBuf>> pl;
+        const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < 4; ++i) {
+            if (planes.plane[i].empty()) continue;
+            pl.push_back(std::make_unique<DeviceBuf>(planes.plane[i].size()));
+            hip_check(hipMemcpy(pl.back()->p, planes.plane[i].data(), planes.plane[i].size(), hipMemcpyHostToDevice), "H2D weights");
+            ptr[i] = pl.back()->p;
+        }
+        QMat W;
+        W.type = (uint32_t)ggml_type; W.n = n; W.k = k; W.q = ptr[0]; W.q2 = ptr[1]; W.s = ptr[2]; W.s2 = ptr[3];
+        const size_t xb = (size_t)m * k * 4, yb = (size_t)m * n * 4;
+        DeviceBuf xd(xb), yd(yb);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        const float* X = static_cast<const float*>(xd.p);
+        float* Y = static_cast<float*>(yd.p);
+        if (m < 24) {  // the decoder's 8-row passes
+            DeviceBuf codes((size_t)8 * k), scales((size_t)8 * (k / 256) * 4);
+            for (int64_t r = 0; r < m; r += 8) {
+                QGemvArgs a;
+                a.W = W; a.X = X + r * k; a.ldx = k; a.rows = (int)std::min<int64_t>(8, m - r); a.Y = Y + r * n; a.ldy = n;
+                if (W.type == GGML_Q6_K) {
+                    hip_check(launch_q8k_quantize(a.X, k, a.rows, k, static_cast<int8_t*>(codes.p), static_cast<float*>(scales.p), nullptr, nullptr),
+                              "q8k quantize");
+                    a.Xq = static_cast<const int8_t*>(codes.p);
+                    a.Xd = static_cast<const float*>(scales.p);
+                }
+                hip_check(launch_qgemv(a, nullptr), "quantized gemv");
+            }
+        } else {  // the prompt route: dequantized weights (+ Q8_K round trip of the activations for Q6_K) on the f32 matrix cores
+            DeviceBuf w32((size_t)n * k * 4), xq(W.type == GGML_Q6_K ? xb : 4);
+            hip_check(launch_qdequant(W, static_cast<float*>(w32.p), nullptr), "dequantize");
+            if (W.type == GGML_Q6_K) {
+                hip_check(launch_q8k_quantize(X, k, (int)m, k, nullptr, nullptr, static_cast<float*>(xq.p), nullptr), "q8k quantize");
+                X = static_cast<const float*>(xq.p);
+            }
+            hip_check(launch_prefill_gemm(X, k, w32.p, 0, nullptr, nullptr, n, Y, n, (int)m, n, k, nullptr), "prefill gemm");
+        }
         hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
     });
 }

@@ -8,6 +8,7 @@
 #include <fstream>
 #include <sstream>
 
+#include "gguf.h"
 #include "json.h"
 #include "kernels.h"
 #include "llm_kernels.h"
@@ -88,6 +89,7 @@ float* LlmModel::upload_f32(const std::vector<float>& host)
     float* d = dalloc(host.size());
     if (!host.empty()) hip_check(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(weights)");
     weight_bytes_ += host.size() * sizeof(float);
+    bytes_by_type_[GGML_F32] += host.size() * sizeof(float);
     return d;
 }
 
@@ -99,6 +101,7 @@ void* LlmModel::upload_weight(const std::vector<float>& host)
     void* d = dalloc((host.size() + 1) / 2);
     if (!h.empty()) hip_check(hipMemcpy(d, h.data(), h.size() * 2, hipMemcpyHostToDevice), "hipMemcpy(weights)");
     weight_bytes_ += h.size() * 2;
+    bytes_by_type_[GGML_BF16] += h.size() * 2;
     return d;
 }
 
@@ -119,47 +122,118 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     std::unique_ptr<LlmModel> m(new LlmModel());
     m->device_ = device;
     hip_check(hipSetDevice(device), "hipSetDevice");
-    m->cfg_ = LlmConfig::from_json(slurp(dir + "/config.json"));
+    // a `.gguf` file, or a directory: safetensors win, else its first `*.gguf` (model_weights.rs:45-77)
+    const std::string gguf_path = resolve_gguf(dir);
+    const bool is_gguf = !gguf_path.empty();
+    GgufFile gf;
+    SafeTensors st;
+    if (is_gguf) {
+        gf.open(gguf_path);
+        m->config_json_ = gf.config_json();
+    } else {
+        m->config_json_ = slurp(dir + "/config.json");
+    }
+    m->cfg_ = LlmConfig::from_json(m->config_json_);
     const LlmConfig& c = m->cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d;
     if ((d & 3) || d > 128 || 256 % (d / 4) != 0 || (H & 7) || (c.inter & 7)) throw std::runtime_error("unsupported decoder geometry");
-    SafeTensors st;
-    st.open_dir(dir);
-    m->bf16_ = weights == 2 || (weights == 0 && st.get("model.layers.0.self_attn.q_proj.weight").dtype == "BF16");
+    auto contains = [&](const std::string& name) { return is_gguf ? gf.find_hf(name) != nullptr : st.contains(name); };
+    if (is_gguf) {
+        // every matrix must be Q8_0 / Q4_K / Q6_K (the reference's F16 LinearLayer is unimplemented; F32 is for norms and biases)
+        std::vector<std::string> mats = {"model.embed_tokens.weight"};
+        if (contains("lm_head.weight")) mats.push_back("lm_head.weight");
+        for (int i = 0; i < c.layers; ++i)
+            for (const char* nm : {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                                   "mlp.down_proj"})
+                mats.push_back("model.layers." + std::to_string(i) + "." + nm + ".weight");
+        for (const std::string& nm : mats) {
+            const GgufTensor* t = gf.find_hf(nm);
+            if (t && !ggml_matrix_type(t->type))
+                throw std::runtime_error("GGUF: matrix " + t->name + " has unsupported type " + ggml_type_name(t->type) + " (" +
+                                         std::to_string(t->type) + "); Q8_0, Q4_K and Q6_K are supported");
+        }
+        m->bf16_ = weights == 2;
+        m->quant_ = weights == 0;
+    } else {
+        st.open_dir(dir);
+        m->bf16_ = weights == 2 || (weights == 0 && st.get("model.layers.0.self_attn.q_proj.weight").dtype == "BF16");
+    }
     std::vector<float> buf, tmp;
+    auto read = [&](const std::string& name, std::vector<float>& out) { return is_gguf ? gf.read_f32(name, out) : st.read_f32(name, out); };
     auto get = [&](const std::string& name, std::vector<int64_t> want) {
-        const std::vector<int64_t> shape = st.read_f32(name, buf);
+        const std::vector<int64_t> shape = read(name, buf);
         if (shape != want) throw std::runtime_error("tensor " + name + " has an unexpected shape");
     };
+    // a quantized matrix [n, k]: HF row order, repacked into its device planes (quant_kernels.hip)
+    auto upload_q = [&](const std::string& name, int n, int k) {
+        const GgufTensor& t = gf.get_hf(name);
+        if (t.ne.size() != 2 || t.ne[0] != k || t.ne[1] != n) throw std::runtime_error("tensor " + name + " has an unexpected shape");
+        const std::vector<uint8_t> raw = gf.rows_hf(name);
+        const QPlanes planes = repack_ggml(t.type, raw.data(), n, k);
+        const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < 4; ++i) {
+            const std::vector<uint8_t>& pl = planes.plane[i];
+            if (pl.empty()) continue;
+            void* dp = m->dalloc((pl.size() + 3) / 4);
+            hip_check(hipMemcpy(dp, pl.data(), pl.size(), hipMemcpyHostToDevice), "hipMemcpy(weights)");
+            m->weight_bytes_ += pl.size();
+            m->bytes_by_type_[t.type] += pl.size();
+            ptr[i] = dp;
+        }
+        QMat q;
+        q.type = t.type;
+        q.n = n;
+        q.k = k;
+        q.q = ptr[0];
+        q.q2 = ptr[1];
+        q.s = ptr[2];
+        q.s2 = ptr[3];
+        return q;
+    };
+    if (m->quant_ && (H % 256 || c.inter % 256)) throw std::runtime_error("quantized GGUF decoder needs hidden and intermediate sizes that are multiples of 256");
     m->layers_.resize((size_t)c.layers);
     m->cache_cap_ = std::min(max_context > 0 ? max_context : c.max_pos, c.max_pos);
     for (int i = 0; i < c.layers; ++i) {
         const std::string p = "model.layers." + std::to_string(i);
         Layer& L = m->layers_[(size_t)i];
+        L.wqkv = L.wo = L.gate = L.up = L.down = nullptr;
         std::vector<float> w, b;
         bool any_bias = false;
         for (const auto& nm : {std::make_pair(std::string("q_proj"), H), std::make_pair(std::string("k_proj"), kv),
                                std::make_pair(std::string("v_proj"), kv)}) {
-            get(p + ".self_attn." + nm.first + ".weight", {nm.second, H});
-            w.insert(w.end(), buf.begin(), buf.end());
-            if (st.contains(p + ".self_attn." + nm.first + ".bias")) {  // Qwen2 (qwen/config.rs:228-234)
-                st.read_f32(p + ".self_attn." + nm.first + ".bias", tmp);
+            if (m->quant_) {
+                QMat& q = nm.first == "q_proj" ? L.q : (nm.first == "k_proj" ? L.k : L.v);
+                q = upload_q(p + ".self_attn." + nm.first + ".weight", nm.second, H);
+            } else {
+                get(p + ".self_attn." + nm.first + ".weight", {nm.second, H});
+                w.insert(w.end(), buf.begin(), buf.end());
+            }
+            if (contains(p + ".self_attn." + nm.first + ".bias")) {  // Qwen2 (qwen/config.rs:228-234)
+                read(p + ".self_attn." + nm.first + ".bias", tmp);
+                if ((int)tmp.size() != nm.second) throw std::runtime_error("tensor " + p + ".self_attn." + nm.first + ".bias has an unexpected shape");
                 b.insert(b.end(), tmp.begin(), tmp.end());
                 any_bias = true;
             } else {
                 b.insert(b.end(), (size_t)nm.second, 0.0f);
             }
         }
-        L.wqkv = m->upload_weight(w);
         L.bqkv = any_bias ? m->upload_f32(b) : nullptr;
-        get(p + ".self_attn.o_proj.weight", {H, H});
-        L.wo = m->upload_weight(buf);
-        get(p + ".mlp.gate_proj.weight", {c.inter, H});
-        L.gate = m->upload_weight(buf);
-        get(p + ".mlp.up_proj.weight", {c.inter, H});
-        L.up = m->upload_weight(buf);
-        get(p + ".mlp.down_proj.weight", {H, c.inter});
-        L.down = m->upload_weight(buf);
+        if (m->quant_) {
+            L.o = upload_q(p + ".self_attn.o_proj.weight", H, H);
+            L.gate_q = upload_q(p + ".mlp.gate_proj.weight", c.inter, H);
+            L.up_q = upload_q(p + ".mlp.up_proj.weight", c.inter, H);
+            L.down_q = upload_q(p + ".mlp.down_proj.weight", H, c.inter);
+        } else {
+            L.wqkv = m->upload_weight(w);
+            get(p + ".self_attn.o_proj.weight", {H, H});
+            L.wo = m->upload_weight(buf);
+            get(p + ".mlp.gate_proj.weight", {c.inter, H});
+            L.gate = m->upload_weight(buf);
+            get(p + ".mlp.up_proj.weight", {c.inter, H});
+            L.up = m->upload_weight(buf);
+            get(p + ".mlp.down_proj.weight", {H, c.inter});
+            L.down = m->upload_weight(buf);
+        }
         get(p + ".input_layernorm.weight", {H});
         L.ln1 = m->upload_f32(buf);
         get(p + ".post_attention_layernorm.weight", {H});
@@ -167,23 +241,38 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         L.k_cache = m->dalloc((size_t)m->cache_cap_ * kv);
         L.v_cache = m->dalloc((size_t)m->cache_cap_ * kv);
     }
-    get("model.embed_tokens.weight", {c.vocab, H});
-    m->embed_ = m->upload_weight(buf);
-    if (c.tie_embeddings || !st.contains("lm_head.weight")) {
-        m->lm_head_ = m->embed_;
+    const bool tied = c.tie_embeddings || !contains("lm_head.weight");
+    if (m->quant_) {
+        m->qembed_ = upload_q("model.embed_tokens.weight", c.vocab, H);
+        m->qhead_ = tied ? m->qembed_ : upload_q("lm_head.weight", c.vocab, H);
+        m->head_q8k_ = !tied;  // a tied head is the embedding table: dequantized rows x f32 activations (cpu/embeddings/mod.rs:94-132)
     } else {
-        get("lm_head.weight", {c.vocab, H});
-        m->lm_head_ = m->upload_weight(buf);
+        get("model.embed_tokens.weight", {c.vocab, H});
+        m->embed_ = m->upload_weight(buf);
+        if (tied) {
+            m->lm_head_ = m->embed_;
+        } else {
+            get("lm_head.weight", {c.vocab, H});
+            m->lm_head_ = m->upload_weight(buf);
+        }
     }
     get("model.norm.weight", {H});
     m->final_norm_ = m->upload_f32(buf);
+    // llama.cpp files carry llama3 RoPE scaling as per-frequency divisors (rope_freqs.weight); the reference ignores them
+    std::vector<float> rope_freqs;
+    if (is_gguf && gf.find_hf("rope_freqs.weight")) {
+        read("rope_freqs.weight", rope_freqs);
+        if ((int)rope_freqs.size() != d / 2) throw std::runtime_error("tensor rope_freqs.weight has an unexpected shape");
+    }
 
     // RoPE tables as the reference builds them (rope/mod.rs:62-130), [cache_cap, d/2]
     {
         const int half = d / 2;
         std::vector<float> inv((size_t)half);
         for (int i = 0; i < half; ++i) inv[(size_t)i] = 1.0f / std::pow(c.rope_theta, (float)(2 * i) / (float)d);
-        if (c.has_rope_scaling && c.rope_type == "llama3") {
+        if (!rope_freqs.empty()) {
+            for (int i = 0; i < half; ++i) inv[(size_t)i] = inv[(size_t)i] / rope_freqs[(size_t)i];
+        } else if (c.has_rope_scaling && c.rope_type == "llama3") {
             const float low_wl = (float)c.rope_original_max / c.rope_low, high_wl = (float)c.rope_original_max / c.rope_high;
             for (int i = 0; i < half; ++i) {
                 const float base = inv[(size_t)i];
@@ -219,6 +308,12 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     m->ctx_ = m->dalloc(8 * (size_t)H);
     m->last_ = m->dalloc(8 * (size_t)H);
     m->mid_ = m->dalloc(8 * (size_t)c.inter);
+    if (m->quant_) {
+        const size_t wide = (size_t)std::max(H, c.inter);
+        m->xn_ = m->dalloc(8 * wide);
+        m->xq_ = reinterpret_cast<int8_t*>(m->dalloc(2 * wide));
+        m->xd_ = m->dalloc(8 * wide / 256 + 4);
+    }
     m->logits_ = m->dalloc((size_t)c.vocab);
     m->att_scratch_ = m->dalloc(decode_attention_scratch_floats(8, c.heads, d, m->splits_));
     m->ids_ = reinterpret_cast<uint32_t*>(m->dalloc(8));
@@ -248,6 +343,10 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
     const int* pp = device_pos ? pos_ : nullptr;
+    if (quant_) {
+        pass_quant(ids_dev, n, device_pos);
+        return;
+    }
     // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
     bool embed_in_qkv = n == 1 && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
 #ifdef KJARNI_TUNING
@@ -311,6 +410,73 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
     hip_check(launch_llm_gemv(lm, s), "lm head");
 }
 
+void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what)
+{
+    QGemvArgs a;
+    a.W = W; a.X = X; a.ldx = ldx; a.rows = rows; a.Y = Y; a.ldy = ldy;
+    if (linear && W.type == GGML_Q6_K) {  // Q6_K x Q8_K (matmul.rs:820-875): the activation rows quantized first
+        hip_check(launch_q8k_quantize(X, ldx, rows, W.k, xq_, xd_, nullptr, stream_), what);
+        a.Xq = xq_;
+        a.Xd = xd_;
+    }
+    hip_check(launch_qgemv(a, stream_), what);
+}
+
+// pass() for a checkpoint whose matrices stay quantized: the same stages and formulas, five fused launches per layer
+// (quant_kernels.hip): RMSNorm + Q|K|V (per-segment types) + RoPE + cache write, attention, o-proj + residual, RMSNorm +
+// gate/up + SwiGLU, down + residual.  A stage whose input feeds a Q6_K linear first runs one qprep launch (RMSNorm where the
+// stage has one + the Q8_K codes, shared by every matrix of the stage).
+void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
+    const int* pp = device_pos ? pos_ : nullptr;
+    // the activation source of a stage: rows X (normalised by gamma inside the GEMV), or -- when a Q6_K linear reads them --
+    // one qprep launch writing the normalised rows and their Q8_K codes
+    auto source = [&](QFusedArgs& a, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what) {
+        a.k = k; a.rows = n;
+        if (!q8k) {
+            a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = c.eps;
+            return;
+        }
+        hip_check(launch_qprep(X, ldx, n, k, gamma, c.eps, gamma ? xn_ : nullptr, xq_, xd_, s), what);
+        a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
+    };
+    auto q6 = [](const QMat& m) { return m.type == GGML_Q6_K; };
+    hip_check(launch_qembed(ids_dev, n, qembed_, h_, s), "embed");
+    for (const Layer& L : layers_) {
+        QFusedArgs qkv;
+        qkv.mode = QF_QKV;
+        source(qkv, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
+        qkv.W[0] = L.q; qkv.W[1] = L.k; qkv.W[2] = L.v;
+        qkv.seg_jobs[0] = H / 2; qkv.seg_jobs[1] = kv / 2; qkv.seg_jobs[2] = kv / 2;
+        qkv.jobs = H / 2 + kv;
+        qkv.bias = L.bqkv; qkv.bias_off[1] = H; qkv.bias_off[2] = H + kv;
+        qkv.Y[0] = q_; qkv.ldy[0] = H; qkv.Y[1] = L.k_cache; qkv.Y[2] = L.v_cache; qkv.ldy[1] = qkv.ldy[2] = kv;
+        qkv.row_off = cache_len_; qkv.row_off_ptr = pp;
+        qkv.head_dim = d; qkv.cos_t = cos_; qkv.sin_t = sin_;
+        hip_check(launch_qfused(qkv, s), "norm + qkv + rope");
+        hip_check(launch_decode_attention(q_, H, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
+                                          splits_, att_scratch_, ctx_, H, s, c.heads / c.kv_heads), "attention");
+        QFusedArgs o;
+        source(o, ctx_, H, H, nullptr, q6(L.o), "q8k o");
+        o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
+        hip_check(launch_qfused(o, s), "o proj");
+        QFusedArgs g;
+        g.mode = QF_SWIGLU;
+        source(g, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
+        g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
+        hip_check(launch_qfused(g, s), "norm + gate/up");
+        QFusedArgs dn;
+        source(dn, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
+        dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
+        hip_check(launch_qfused(dn, s), "down proj");
+    }
+    hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
+    qlinear(qhead_, last_ + (size_t)(n - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
+}
+
 // Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer RMSNorm ->
 // Q, K, V projections (K and V rows land in the cache) -> RoPE -> causal attention over the cache -> o-proj + residual
 // -> RMSNorm -> gate, up -> silu(gate) * up -> down-proj + residual; same formulas as pass().  After the last layer the
@@ -341,14 +507,16 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
         pu_ = dalloc(P * I);
         pids_ = reinterpret_cast<uint32_t*>(dalloc(P));
         psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, H)));
-        if (bf16_) pw32_ = dalloc(std::max((size_t)(H + 2 * kv) * H, (size_t)I * H));
+        if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(H + 2 * kv) * H, (size_t)I * H));
+        if (quant_) pact_ = dalloc(P * (size_t)std::max(H, I));
     }
     const size_t wsz = bf16_ ? 2 : 4;
     auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
     for (int done = 0; done < n; done += prefill_cap_) {
         const int m = std::min(prefill_cap_, n - done);
         hip_check(hipMemcpyAsync(pids_, ids_host + done, (size_t)m * 4, hipMemcpyHostToDevice, s), "H2D ids");
-        hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
+        if (quant_) hip_check(launch_qembed(pids_, m, qembed_, ph_, s), "embed");
+        else hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
         // Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T).  Blocks of >= kTileRows rows run the
         // encoder's 128 x 128-tile f32 GEMM (gemm.hip), bf16 weights on an f32 copy made just before (100 MB moved per 69 GFLOP
         // at 2 048 rows).  Measured on the 1B shape: 2 048 rows 46.2 -> 42.6 ms, 1 792 rows 40.4 -> 39.1 ms, 1 536 rows 33.1 -> 36.1 ms
@@ -356,7 +524,22 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
         // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
         const bool tile_shapes = H % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
         auto proj = [&](const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                        float* gate, const char* what) {
+                        float* gate, const char* what, const QMat* qm = nullptr) {
+            // a quantized matrix: dequantized into the f32 scratch first; a Q6_K linear also takes its activation rows through
+            // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
+            int wbu = wb;
+            bool bf = bf16_;
+            if (qm) {
+                hip_check(launch_qdequant(*qm, pw32_, s), what);
+                if (qm->type == GGML_Q6_K) {
+                    hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
+                    Ain = pact_;
+                    lda = K;
+                }
+                W = pw32_;
+                wbu = 0;
+                bf = false;
+            }
 #ifdef KJARNI_TUNING
             static const int min_tiles_env = [] { const char* v = std::getenv("KJARNI_HIP_LLM_MIN_TILES"); return v ? std::atoi(v) : 0; }();
             const int min_tiles = min_tiles_env > 0 ? min_tiles_env : 208;
@@ -368,7 +551,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
 #endif
             const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
             if (!tiles) {
-                hip_check(launch_prefill_gemm(Ain, lda, W, wb, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
+                hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
                 return;
             }
             ++tile_gemm_calls_;
@@ -379,7 +562,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
 #else
             constexpr bool widen = false;
 #endif
-            if (bf16_ && !widen && K % 64 == 0) {
+            if (bf && !widen && K % 64 == 0) {
                 if (gate)
                     hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
                 else
@@ -387,7 +570,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
                 return;
             }
             const float* W32 = static_cast<const float*>(W);
-            if (bf16_) {
+            if (bf) {
                 hip_check(launch_widen_bf16(W, pw32_, (size_t)N * K, s), "widen");
                 W32 = pw32_;
             }
@@ -400,9 +583,11 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
             float* k_rows = L.k_cache + (size_t)cache_len_ * kv;
             float* v_rows = L.v_cache + (size_t)cache_len_ * kv;
             hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-            proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, H, H, H, nullptr, "q proj");
-            proj(pn_, H, at(L.wqkv, (size_t)H * H), L.bqkv ? L.bqkv + H : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj");
-            proj(pn_, H, at(L.wqkv, (size_t)(H + kv) * H), L.bqkv ? L.bqkv + H + kv : nullptr, nullptr, v_rows, kv, kv, H, nullptr, "v proj");
+            proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, H, H, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
+            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)H * H), L.bqkv ? L.bqkv + H : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj",
+                 quant_ ? &L.k : nullptr);
+            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(H + kv) * H), L.bqkv ? L.bqkv + H + kv : nullptr, nullptr, v_rows, kv, kv, H,
+                 nullptr, "v proj", quant_ ? &L.v : nullptr);
             hip_check(launch_rope(pq_, H, m, c.heads, d, cos_, sin_, cache_len_, nullptr, 0, s), "rope q");
             hip_check(launch_rope(L.k_cache, kv, m, c.kv_heads, d, cos_, sin_, cache_len_, nullptr, 1, s), "rope k");
             if (prefill_attention_supported(d)) {
@@ -416,20 +601,24 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
                                                       c.heads / c.kv_heads), "attention");
                 }
             }
-            proj(pctx_, H, L.wo, nullptr, ph_, ph_, H, H, H, nullptr, "o proj");
+            proj(pctx_, H, L.wo, nullptr, ph_, ph_, H, H, H, nullptr, "o proj", quant_ ? &L.o : nullptr);
             hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
-            proj(pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate");
-            proj(pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu");
-            proj(pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj");
+            proj(pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", quant_ ? &L.gate_q : nullptr);
+            proj(pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
+            proj(pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
         }
         cache_len_ += m;
         if (done + m == n) {
             const int rows = (n - 1) % 8 + 1;
             hip_check(launch_rmsnorm(ph_ + (size_t)(m - rows) * H, final_norm_, c.eps, rows, H, last_, s), "final norm");
-            LlmGemvArgs lm;
-            lm.X = last_ + (size_t)(rows - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-            lm.Y0 = logits_; lm.ldy0 = c.vocab;
-            hip_check(launch_llm_gemv(lm, s), "lm head");
+            if (quant_) {
+                qlinear(qhead_, last_ + (size_t)(rows - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
+            } else {
+                LlmGemvArgs lm;
+                lm.X = last_ + (size_t)(rows - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
+                lm.Y0 = logits_; lm.ldy0 = c.vocab;
+                hip_check(launch_llm_gemv(lm, s), "lm head");
+            }
             last_rows_ = rows;
         }
         hip_check(hipStreamSynchronize(s), "sync");  // pids_ and the activations are reused by the next chunk

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "quant_kernels.h"
 #include "sampling.h"
 
 namespace kjarni {
@@ -49,7 +50,9 @@ struct GenerateOptions {
 
 class LlmModel {
 public:
-    // weights: 0 = as stored (BF16 stays bf16, everything else f32), 1 = f32, 2 = bf16 (f32 rounded to nearest even).
+    // dir: a safetensors model directory, a `.gguf` file or a directory that holds one (gguf.h: resolve_gguf).
+    // weights: 0 = as stored (BF16 stays bf16, everything else f32; GGUF Q8_0 / Q4_K / Q6_K matrices stay quantized), 1 = f32,
+    // 2 = bf16 (f32 rounded to nearest even).
     static std::unique_ptr<LlmModel> load(const std::string& dir, int device, int weights, int max_context);
     ~LlmModel();
     LlmModel(const LlmModel&) = delete;
@@ -58,6 +61,10 @@ public:
     const LlmConfig& config() const { return cfg_; }
     bool bf16() const { return bf16_; }
     size_t weight_bytes() const { return weight_bytes_; }
+    // device bytes of the weights held in each GGML type (0 = F32, 30 = BF16, 8 / 12 / 14 = Q8_0 / Q4_K / Q6_K)
+    uint64_t weight_bytes_of_type(int type) const { return type >= 0 && type < 32 ? bytes_by_type_[type] : 0; }
+    bool quantized() const { return quant_; }
+    const std::string& config_json() const { return config_json_; }  // config.json, or the config synthesized from GGUF metadata
     int context() const { return cache_cap_; }
     int cache_len() const { return cache_len_; }
     // Prompt projections that ran the encoder's 128 x 128-tile GEMM since load (the other route is the 64 x 64 prompt kernel):
@@ -93,6 +100,9 @@ private:
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
     void pass(const uint32_t* ids_dev, int n, bool device_pos);
+    void pass_quant(const uint32_t* ids_dev, int n, bool device_pos);  // pass() on quantized matrices (quant_kernels.hip)
+    // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
+    void qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what);
     void prefill_rows(const uint32_t* ids_host, int n);  // n new tokens through the matrix-core GEMMs
     void enqueue_argmax(bool record);
     hipGraphExec_t step_graph();
@@ -101,11 +111,20 @@ private:
         void *wqkv, *wo, *gate, *up, *down;
         float *bqkv, *ln1, *ln2;
         float *k_cache, *v_cache;
+        QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
     };
     LlmConfig cfg_;
     int device_ = 0;
-    bool bf16_ = false;
+    bool bf16_ = false, quant_ = false;
     size_t weight_bytes_ = 0;
+    uint64_t bytes_by_type_[32] = {};
+    std::string config_json_;
+    QMat qembed_, qhead_;       // quantized checkpoints: the table, and the head (== the table when tied)
+    bool head_q8k_ = false;     // the head is a linear layer (untied output.weight), so a Q6_K head takes Q8_K activations
+    float* xn_ = nullptr;       // quantized decode: normalised rows [8, max(H, I)]
+    int8_t* xq_ = nullptr;      // their Q8_K codes
+    float* xd_ = nullptr;       // and scales
+    float* pact_ = nullptr;     // prompt route, Q6_K linears: the activation rows through Q8_K and back
     DeviceArena arena_;   // every device buffer of the model
     std::vector<Layer> layers_;
     void *embed_ = nullptr, *lm_head_ = nullptr;

@@ -1,5 +1,7 @@
 #include "registry.h"
 
+#include "gguf.h"
+
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -172,6 +174,12 @@ bool model_files_present(const std::string& dir)
     // model_weights.rs:51-53: one file or an index over shards
     return is_file(dir + "/config.json") && is_file(dir + "/tokenizer.json") &&
            (is_file(dir + "/model.safetensors") || is_file(dir + "/model.safetensors.index.json"));
+}
+
+bool decoder_files_present(const std::string& dir)
+{
+    // the decoder also loads a GGUF checkpoint (model_weights.rs:45-77): tokenizer.json beside a `*.gguf`
+    return model_files_present(dir) || (is_file(dir + "/tokenizer.json") && !resolve_gguf(dir).empty());
 }
 
 }  // namespace kjarni

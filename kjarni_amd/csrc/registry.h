@@ -30,5 +30,7 @@ std::string default_cache_dir();
 std::string model_dir_for(const RegistryEntry& e, const std::string& cache_dir);
 // config.json + tokenizer.json + model.safetensors present (registry.rs:814-827).
 bool model_files_present(const std::string& dir);
+// A decoder (chat) directory: model_files_present, or tokenizer.json + a GGUF file (gguf.h: resolve_gguf).
+bool decoder_files_present(const std::string& dir);
 
 }  // namespace kjarni

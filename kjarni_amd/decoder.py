@@ -3,7 +3,6 @@ from __future__ import annotations
 
 import ctypes as C
 import json
-import os
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -22,8 +21,8 @@ class HipDecoder:
         wb = C.c_uint64()
         check_error(lib().kjarni_hip_decoder_dims(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e), C.byref(wb)))
         self.hidden, self.layers, self.vocab, self.context, self.bf16, self.weight_bytes = a.value, b.value, c.value, d.value, bool(e.value), wb.value
-        with open(os.path.join(model_dir, "config.json")) as f:  # the defaults of LlmConfig::from_json
-            cfg = json.load(f)
+        cfg = json.loads(self.config_json())  # config.json, or the config synthesized from a GGUF file's metadata
+        self.config = cfg
         heads = cfg["num_attention_heads"]
         self.kv_heads = cfg.get("num_key_value_heads", heads)
         self.head_dim = cfg.get("head_dim", self.hidden // heads)
@@ -32,6 +31,21 @@ class HipDecoder:
         if getattr(self, "_h", None) and self._h.value:
             lib().kjarni_hip_decoder_free(self._h)
             self._h = C.c_void_p()
+
+    def config_json(self) -> str:
+        """The resolved model config as JSON."""
+        p = C.c_void_p()
+        check_error(lib().kjarni_hip_decoder_config_json(self._h, C.byref(p)))
+        s = C.string_at(p).decode("utf-8")
+        lib().kjarni_string_free(p)
+        return s
+
+    def weight_bytes_by_type(self) -> dict:
+        """Device bytes of the weights per GGML type name (F32, BF16, Q8_0, Q4_K, Q6_K), non-zero entries only."""
+        out = (C.c_uint64 * 32)()
+        check_error(lib().kjarni_hip_decoder_weight_bytes_by_type(self._h, out, 32))
+        names = {0: "F32", 8: "Q8_0", 12: "Q4_K", 14: "Q6_K", 30: "BF16"}
+        return {names[t]: int(out[t]) for t in names if out[t]}
 
     def reset(self):
         check_error(lib().kjarni_hip_decoder_reset(self._h))

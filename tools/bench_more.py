@@ -544,6 +544,36 @@ def main():
             res["cpu_baseline"] = {"value": round(1.0 / c_dec, 2), "unit": "tokens/s", "cores": int(cores), "kind": "port",
                                    "sample": f"oracle: 16-token prefill {c_pre:.2f} s, 4 decode steps at {c_dec * 1e3:.0f} ms each (f32 weights)"}
         emit(res)
+        # The same geometry as a GGUF Q4_K_M-style mix (tests/gguf_fixture.py): Q6_K token_embd (the tied head) and Q6_K
+        # attn_v / ffn_down in the even layers (0, 2, ..., 14), Q4_K everywhere else, F32 norms; matrices quantized in HBM.
+        from tests import gguf_fixture
+        gpath = os.path.join(tmp, "llama-1b-q4km.gguf")
+        gcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=cfg_l["vocab_size"] + 1)
+        gguf_fixture.gguf_model(gpath, gcfg, gguf_fixture.q4_k_m_types(gcfg["num_hidden_layers"]), seed=0, rope_freqs=True, keep_hf=False)
+        qdec = kjarni_amd.HipDecoder(gpath, max_context=2048)
+        qdec.generate(prompt, 8)
+        t0 = time.perf_counter()
+        qdec.reset()
+        qdec.forward(prompt, fetch=False)
+        q_prefill = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        qout = qdec.generate(prompt, n_new)
+        q_dec = time.perf_counter() - t0 - q_prefill
+        q_tok = qdec.weight_bytes + kv_bytes
+        emit({"metric": "tokens/sec greedy decode, Llama-3.2-1B shape, GGUF Q4_K_M mix in HBM, batch 1", "value": round(len(qout) / q_dec, 1),
+              "unit": "tokens/s", "n_gpus": 1, "dtype": "Q4_K / Q6_K weights, f32 activations/accumulate/KV", "data": "synthetic",
+              "config": {"workload": "Llama-3.2-1B geometry as GGUF: Q6_K token_embd (tied head) and attn_v / ffn_down of layers 0, 2, ..., 14, "
+                                     f"Q4_K elsewhere, F32 norms; random blocks, 128-token prompt, {len(qout)} generated tokens"},
+              "ms_prefill_128": round(q_prefill * 1e3, 2), "ms_per_token": round(q_dec * 1e3 / len(qout), 4),
+              "weight_bytes": qdec.weight_bytes, "weight_bytes_by_type": qdec.weight_bytes_by_type(),
+              "bf16_same_run": {"tokens_per_s": res["value"], "ms_per_token": res["ms_per_token"], "weight_bytes": dec.weight_bytes},
+              "speedup_vs_bf16": round((len(qout) / q_dec) / res["value"], 3),
+              "weight_bytes_ratio_vs_bf16": round(qdec.weight_bytes / dec.weight_bytes, 3),
+              "roofline": {"kernel": "qfused_kernel (weight stream) + decode_attention_partial", "bound": "hbm",
+                           "achieved": round(q_tok * len(qout) / q_dec / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                           "frac": round(q_tok * len(qout) / q_dec / 1e9 / PEAK_HBM_GBS, 4), "traffic": None,
+                           "algorithmic_bytes_per_token": int(q_tok)}})
+        del qdec
 
     if "llm8b" in which:
         # The same decode path on the Llama-3.1-8B geometry (16 GB of bf16 weights): the per-kernel floor that bounds the 1B
