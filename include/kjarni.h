@@ -411,6 +411,40 @@ void kjarni_chat_conversation_clear(KjarniChatConversation* convo, int32_t keep_
 size_t kjarni_chat_model_name(const KjarniChat* chat, char* buf, size_t buf_len);
 size_t kjarni_chat_context_size(const KjarniChat* chat);                                             /* :747-758 */
 
+/* ---- Generator (raw text completion) -------------------------------------------------------
+ * NOT part of the reference's kjarni-ffi crate: it mirrors the Rust API crates/kjarni/src/generator/{builder,model,
+ * validation,types}.rs.  The prompt is completed as it is: no chat template, no trimming, no stop-sequence stripping; the
+ * result is the concatenation of the generated tokens' single-token decodes (special tokens kept).  model_name: a Llama,
+ * Qwen2, Mistral or GPT registry name ("gpt2", "distilgpt2", "qwen2.5-1.5b", ...); model_path as in KjarniChatConfig.
+ * Defaults: the model's (GPT-2: sampling at temperature 0.7, top_k 50, top_p 0.9, min_p 0.1, 50 new tokens; Llama /
+ * Qwen2 / Mistral as kjarni_generation_resolve with mode < 0); a KjarniGenerationConfig overrides them per call.
+ * Errors of kjarni_generator_new (validation.rs:8-51): unknown name / files not on disk -> MODEL_NOT_FOUND; encoder,
+ * speech or seq2seq model -> INVALID_CONFIG; Phi-3 -> LOAD_FAILED; no GPU -> GPU_UNAVAILABLE; beam search at generation
+ * time -> INFERENCE_FAILED. */
+typedef struct KjarniGeneratorConfig {
+    KjarniDevice device;
+    const char* cache_dir;     /* NULL = default cache */
+    const char* model_name;    /* required */
+    const char* model_path;    /* NULL = <cache_dir>/<org>_<repo> */
+    int32_t quiet;
+} KjarniGeneratorConfig;
+
+typedef struct KjarniGenerator KjarniGenerator;
+
+KjarniGeneratorConfig kjarni_generator_config_default(void);
+KjarniErrorCode kjarni_generator_new(const KjarniGeneratorConfig* config, KjarniGenerator** out);
+void kjarni_generator_free(KjarniGenerator* generator);
+/* Generator::generate_with_config (model.rs:217-250).  Free *out with kjarni_string_free. */
+KjarniErrorCode kjarni_generator_generate(KjarniGenerator* generator, const char* prompt, const KjarniGenerationConfig* gen_config,
+                                          char** out);
+/* One callback per generated token; the cancel token is looked at before each callback. */
+KjarniErrorCode kjarni_generator_stream(KjarniGenerator* generator, const char* prompt, const KjarniGenerationConfig* gen_config,
+                                        KjarniStreamCallbackFn callback, void* user_data, const KjarniCancelToken* cancel_token);
+/* Without a buffer: the name's byte length; with one: bytes copied, NUL excluded. */
+size_t kjarni_generator_model_name(const KjarniGenerator* generator, char* buf, size_t buf_len);
+size_t kjarni_generator_context_size(const KjarniGenerator* generator);  /* the model's n_ctx / max_position_embeddings */
+size_t kjarni_generator_vocab_size(const KjarniGenerator* generator);
+
 /* ---- streamed tokens: kjarni-ffi/src/callback.rs:36-47 -------------------------------- */
 typedef struct KjarniToken {
     const char* text; /* valid for the duration of the callback */

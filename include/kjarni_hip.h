@@ -490,7 +490,7 @@ KjarniErrorCode kjarni_audio_load_wav(const char* path, KjarniFloatArray* out, u
 KjarniErrorCode kjarni_bytelevel_decode(const char* tokenizer_json_path, const uint32_t* ids, size_t n, int32_t skip_special,
                                         char** out);
 
-/* ---- decoder-only generation (Llama / Qwen2 layouts), token level ----------------------------
+/* ---- decoder-only generation (Llama / Qwen2 / Mistral layouts and GPT-2), token level ----------------------------
  * model_dir: config.json (crates/kjarni-models/src/models/llama/config.rs:98-158, qwen/config.rs:80-125) and
  * model.safetensors with the HF tensor names of llama/config.rs:283-330.  weights_dtype: 0 = as stored (BF16 stays
  * bf16 in HBM, other dtypes are widened to f32), 1 = f32, 2 = bf16 (f32 rounded to nearest even).  Arithmetic,
@@ -622,6 +622,14 @@ void kjarni_hip_chat_seed(KjarniChat* chat, uint64_t seed);
  * counters: tokens decided from candidates / tokens that needed the logits after all. */
 void kjarni_hip_chat_set_device_sampling(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_sampling_counters(KjarniChat* chat, uint64_t* from_candidates, uint64_t* from_logits);
+/* The same hooks on a Generator handle: the resolved config of a call, DecoderGenerator::encode of a prompt (BOS rule
+ * included), the sampler's seed, and device (1) or host (0) sampling / logits processors. */
+KjarniErrorCode kjarni_hip_generator_resolve(const KjarniGenerator* generator, const KjarniGenerationConfig* runtime,
+                                             KjarniResolvedGeneration* out);
+KjarniErrorCode kjarni_hip_generator_encode(const KjarniGenerator* generator, const char* prompt, const KjarniGenerationConfig* runtime,
+                                            uint32_t* ids_out, size_t capacity, size_t* n_out);
+void kjarni_hip_generator_seed(KjarniGenerator* generator, uint64_t seed);
+void kjarni_hip_generator_set_device_sampling(KjarniGenerator* generator, int32_t on);
 
 #ifdef __cplusplus
 }

@@ -233,6 +233,11 @@ class KjarniResolvedGeneration(Structure):
 KjarniStreamCallbackFn = C.CFUNCTYPE(C.c_bool, c_char_p, c_void_p)
 
 
+class KjarniGeneratorConfig(Structure):
+    _fields_ = [("device", c_int32), ("cache_dir", c_char_p), ("model_name", c_char_p), ("model_path", c_char_p),
+                ("quiet", c_int32)]
+
+
 class KjarniRerankerConfig(Structure):
     _fields_ = [("device", c_int32), ("cache_dir", c_char_p), ("model_name", c_char_p),
                 ("model_path", c_char_p), ("quiet", c_int32)]
@@ -387,6 +392,19 @@ SIGNATURES = {
     "kjarni_hip_chat_seed": (None, [c_void_p, C.c_uint64]),
     "kjarni_hip_chat_set_device_sampling": (None, [c_void_p, c_int32]),
     "kjarni_hip_chat_sampling_counters": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_generator_config_default": (KjarniGeneratorConfig, []),
+    "kjarni_generator_new": (c_int32, [POINTER(KjarniGeneratorConfig), POINTER(c_void_p)]),
+    "kjarni_generator_free": (None, [c_void_p]),
+    "kjarni_generator_generate": (c_int32, [c_void_p, c_char_p, POINTER(KjarniGenerationConfig), POINTER(c_void_p)]),
+    "kjarni_generator_stream": (c_int32, [c_void_p, c_char_p, POINTER(KjarniGenerationConfig), KjarniStreamCallbackFn, c_void_p,
+                                          c_void_p]),
+    "kjarni_generator_model_name": (c_size_t, [c_void_p, c_char_p, c_size_t]),
+    "kjarni_generator_context_size": (c_size_t, [c_void_p]),
+    "kjarni_generator_vocab_size": (c_size_t, [c_void_p]),
+    "kjarni_hip_generator_resolve": (c_int32, [c_void_p, POINTER(KjarniGenerationConfig), POINTER(KjarniResolvedGeneration)]),
+    "kjarni_hip_generator_encode": (c_int32, [c_void_p, c_char_p, POINTER(KjarniGenerationConfig), _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_generator_seed": (None, [c_void_p, C.c_uint64]),
+    "kjarni_hip_generator_set_device_sampling": (None, [c_void_p, c_int32]),
     "kjarni_hip_decoder_load": (c_int32, [c_char_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
     "kjarni_hip_decoder_free": (None, [c_void_p]),
     "kjarni_hip_decoder_dims": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),

@@ -156,6 +156,21 @@ GenerationConfig resolve_generation_config(GenerationConfig config, const Genera
 GenerationConfig model_default_generation_config(const std::string& model_type, size_t max_pos, const std::string* hf_json)
 {
     GenerationConfig c;
+    if (model_type == "gpt2") {
+        // Gpt2Model keeps the trait's default (decoder/traits.rs:283-285): GenerationConfig::default()
+        // (common/mod.rs:78-96), whatever generation_config.json says
+        c.max_new_tokens = Opt<size_t>(50);
+        c.max_length = 100;
+        c.repetition_penalty = 1.0f;
+        c.no_repeat_ngram_size = 0;
+        c.add_bos_token = true;
+        c.strategy = Strategy::Sample;
+        c.temperature = 0.7f;
+        c.top_k = Opt<size_t>(50);
+        c.top_p = Opt<float>(0.9f);
+        c.min_p = Opt<float>(0.1f);
+        return c;
+    }
     if (hf_json && model_type != "mistral") {  // HFGenerationDefaults (a file that does not deserialize is ignored); Mistral never reads it
         try {
             const Json j = Json::parse(*hf_json);
@@ -277,18 +292,76 @@ bool read_file(const std::string& p, std::string& out)
     return true;
 }
 
+const ChatModelInfo* model_info(const std::string& model_name, const RegistryEntry*& entry)
+{
+    std::string err;
+    entry = resolve_model(model_name, err);
+    if (!entry) throw ModelNotFound(err);  // ChatError::UnknownModel / GeneratorError::UnknownModel
+    for (const ChatModelInfo& m : kChatModels)
+        if (std::strcmp(m.cli_name, entry->cli_name) == 0) return &m;
+    throw ModelNotFound("Unknown model '" + model_name + "'");
+}
+
+// stop_token_ids (models/base.rs:261-271): the first eos id and <|eot_id|> when the tokenizer has it
+std::vector<uint32_t> stop_token_ids(const LlmConfig& cfg, const BpeTokenizer& tok)
+{
+    std::vector<uint32_t> ids;
+    if (!cfg.eos_ids.empty()) ids.push_back(cfg.eos_ids[0]);
+    uint32_t eot = 0;
+    if (tok.token_to_id("<|eot_id|>", eot) && std::find(ids.begin(), ids.end(), eot) == ids.end()) ids.push_back(eot);
+    if (ids.empty()) ids.push_back(UINT32_MAX);  // nothing stops generation but the length
+    return ids;
+}
+
+// DecoderGenerator::encode (generator.rs:141-163): the BOS rule
+std::vector<uint32_t> encode_prompt(const BpeTokenizer& tok, const LlmConfig& cfg, const std::string& prompt, const GenerationConfig& config)
+{
+    std::vector<uint32_t> tokens = tok.encode(prompt);
+    if (config.add_bos_token && cfg.has_bos && (tokens.empty() || tokens[0] != cfg.bos_id)) tokens.insert(tokens.begin(), cfg.bos_id);
+    return tokens;
+}
+
+// The text side of run_generation_loop shared by Chat and Generator: the resolved config becomes the loop's options, and
+// every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
+std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
+                                const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text)
+{
+    if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
+    const size_t context_size = (size_t)model.config().max_pos;
+    GenerateOptions opt;
+    opt.max_new_tokens = config.max_new_tokens.has ? config.max_new_tokens.value
+                                                   : (config.max_length > tokens.size() ? config.max_length - tokens.size() : 0);
+    opt.max_len = config.max_new_tokens.has ? tokens.size() + config.max_new_tokens.value : config.max_length;
+    opt.max_len = std::min(opt.max_len, context_size);
+    opt.repetition_penalty = config.repetition_penalty;
+    opt.no_repeat_ngram = (int)config.no_repeat_ngram_size;
+    opt.stop_ids = stop_ids;
+    if (config.strategy == Strategy::Sample) {
+        opt.sample = true;
+        opt.sampling.temperature = config.temperature;
+        opt.sampling.top_k = config.top_k.has ? (int64_t)config.top_k.value : -1;
+        opt.sampling.top_p = config.top_p.has ? config.top_p.value : -1.0f;
+        opt.sampling.min_p = config.min_p.has ? config.min_p.value : -1.0f;
+        opt.uniform = [&rng] { return rng.next(); };
+    }
+    std::string text;
+    std::vector<uint32_t> prompt_tokens = tokens;
+    if ((int)prompt_tokens.size() > model.context()) prompt_tokens.resize((size_t)model.context());
+    model.generate(prompt_tokens, opt, [&](uint32_t id) {
+        const std::string piece = tok.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
+        text += piece;
+        return on_text ? on_text(piece) : true;
+    });
+    return text;
+}
+
 }  // namespace
 
 std::unique_ptr<Chat> Chat::create(const std::string& model_name, const std::string& model_dir, const std::string& cache_dir,
                                    const std::string* system_prompt, int mode, bool quiet)
 {
-    std::string err;
-    const RegistryEntry* entry = resolve_model(model_name, err);
-    if (!entry) throw ModelNotFound(err);  // ChatError::UnknownModel
-    const ChatModelInfo* info = nullptr;
-    for (const ChatModelInfo& m : kChatModels)
-        if (std::strcmp(m.cli_name, entry->cli_name) == 0) info = &m;
-    if (!info) throw ModelNotFound("Unknown model '" + model_name + "'");
+    const RegistryEntry* entry = nullptr;
+    const ChatModelInfo* info = model_info(model_name, entry);
     const std::string cli = entry->cli_name;
     const std::string family = info->family;
     auto incompatible = [&](const std::string& reason) { return InvalidConfig("model '" + cli + "' is incompatible with chat: " + reason); };
@@ -348,12 +421,7 @@ std::unique_ptr<Chat> Chat::create(const std::string& model_name, const std::str
     chat->mode_overrides_.max_new_tokens = Opt<size_t>(kModeMaxTokens[m]);
     chat->generation_config_ = resolve_generation_config(defaults, chat->mode_overrides_, GenerationOverrides());
 
-    // stop_token_ids (models/base.rs:261-271): the first eos id and <|eot_id|> when the tokenizer has it
-    if (!cfg.eos_ids.empty()) chat->stop_ids_.push_back(cfg.eos_ids[0]);
-    uint32_t eot = 0;
-    if (chat->tokenizer_.token_to_id("<|eot_id|>", eot) && std::find(chat->stop_ids_.begin(), chat->stop_ids_.end(), eot) == chat->stop_ids_.end())
-        chat->stop_ids_.push_back(eot);
-    if (chat->stop_ids_.empty()) chat->stop_ids_.push_back(UINT32_MAX);  // nothing stops generation but the length
+    chat->stop_ids_ = stop_token_ids(cfg, chat->tokenizer_);
     return chat;
 }
 
@@ -395,10 +463,7 @@ GenerationConfig Chat::resolve(const GenerationOverrides& runtime) const
 
 std::vector<uint32_t> Chat::encode(const std::string& prompt, const GenerationConfig& config) const
 {
-    std::vector<uint32_t> tokens = tokenizer_.encode(prompt);
-    const LlmConfig& cfg = model_->config();
-    if (config.add_bos_token && cfg.has_bos && (tokens.empty() || tokens[0] != cfg.bos_id)) tokens.insert(tokens.begin(), cfg.bos_id);
-    return tokens;
+    return encode_prompt(tokenizer_, model_->config(), prompt, config);
 }
 
 std::string Chat::run(const std::string& prompt, const GenerationOverrides& runtime, const std::function<bool(const std::string&)>& on_text)
@@ -406,34 +471,7 @@ std::string Chat::run(const std::string& prompt, const GenerationOverrides& runt
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
-    const std::vector<uint32_t> tokens = encode(prompt, config);
-    if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
-
-    GenerateOptions opt;
-    opt.max_new_tokens = config.max_new_tokens.has ? config.max_new_tokens.value
-                                                   : (config.max_length > tokens.size() ? config.max_length - tokens.size() : 0);
-    opt.max_len = config.max_new_tokens.has ? tokens.size() + config.max_new_tokens.value : config.max_length;
-    opt.max_len = std::min(opt.max_len, context_size());
-    opt.repetition_penalty = config.repetition_penalty;
-    opt.no_repeat_ngram = (int)config.no_repeat_ngram_size;
-    opt.stop_ids = stop_ids_;
-    if (config.strategy == Strategy::Sample) {
-        opt.sample = true;
-        opt.sampling.temperature = config.temperature;
-        opt.sampling.top_k = config.top_k.has ? (int64_t)config.top_k.value : -1;
-        opt.sampling.top_p = config.top_p.has ? config.top_p.value : -1.0f;
-        opt.sampling.min_p = config.min_p.has ? config.min_p.value : -1.0f;
-        opt.uniform = [this] { return rng_.next(); };
-    }
-    std::string text;
-    std::vector<uint32_t> prompt_tokens = tokens;
-    if ((int)prompt_tokens.size() > model_->context()) prompt_tokens.resize((size_t)model_->context());
-    model_->generate(prompt_tokens, opt, [&](uint32_t id) {
-        const std::string piece = tokenizer_.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
-        text += piece;
-        return on_text ? on_text(piece) : true;
-    });
-    return text;
+    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text);
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -449,6 +487,75 @@ std::string Chat::generate_stream(const std::string& prompt, const GenerationOve
                                   const std::function<bool(const std::string&)>& on_text)
 {
     return run(prompt, runtime, on_text);
+}
+
+// ---- Generator ------------------------------------------------------------------------------------
+
+std::unique_ptr<Generator> Generator::create(const std::string& model_name, const std::string& model_dir, const std::string& cache_dir,
+                                             bool quiet)
+{
+    const RegistryEntry* entry = nullptr;
+    const ChatModelInfo* info = model_info(model_name, entry);
+    const std::string cli = entry->cli_name;
+    const std::string family = info->family;
+    // validate_for_generation (generator/validation.rs:8-51)
+    auto invalid = [&](const std::string& reason) { return InvalidConfig("Model '" + cli + "' is not suitable for text generation: " + reason); };
+    if (family == "encoder")
+        throw invalid(std::string("Architecture '") + info->arch + "' is an encoder and cannot generate text. Use Embedder instead.");
+    if (family == "whisper") throw invalid("Whisper is designed for speech-to-text. Use Transcriber instead.");
+    if (family == "seq2seq")
+        throw invalid(std::string("Architecture '") + info->arch +
+                      "' is a seq2seq model. Use Seq2SeqGenerator, Translator, or Summarizer instead.");
+    if (std::string(info->task) == "generation" && !quiet)
+        std::fprintf(stderr, "Warning: [info] Model '%s' is a base model, not instruction-tuned.\n", cli.c_str());
+
+    const std::string dir = !model_dir.empty() ? model_dir : model_dir_for(*entry, cache_dir.empty() ? default_cache_dir() : cache_dir);
+    if (!decoder_files_present(dir))  // GeneratorError::ModelNotDownloaded: this library never downloads
+        throw ModelNotFound("Model '" + cli + "' not downloaded. Run: kjarni model download " + cli);
+    auto load_failed = [&](const std::string& why) { return std::runtime_error("Failed to load model '" + cli + "': " + why); };
+    if (family == "phi3") throw load_failed("Phi3 model loading not yet implemented");  // generator/model.rs:222
+
+    std::unique_ptr<Generator> g(new Generator());
+    g->model_name_ = cli;
+    int device = 0;
+    if (const char* dv = std::getenv("KJARNI_HIP_DEVICE")) device = std::atoi(dv);
+    int context_cap = 32768;
+    if (const char* cv = std::getenv("KJARNI_HIP_CHAT_CONTEXT")) context_cap = std::max(16, std::atoi(cv));
+    try {
+        g->tokenizer_.load(dir + "/tokenizer.json");
+        g->model_ = LlmModel::load(dir, device, 0, context_cap);
+    } catch (const GpuUnavailable&) {
+        throw;
+    } catch (const std::exception& e) {
+        throw load_failed(e.what());
+    }
+    const LlmConfig& cfg = g->model_->config();
+    g->tokenizer_.set_truncation((size_t)cfg.max_pos);  // loader.rs:115-120
+    std::string hf;
+    const bool has_hf = read_file(dir + "/generation_config.json", hf);
+    // model.rs:127-132: the model's defaults, resolved with no builder overrides
+    g->generation_config_ = resolve_generation_config(
+        model_default_generation_config(cfg.model_type, (size_t)cfg.max_pos, has_hf ? &hf : nullptr), GenerationOverrides(), GenerationOverrides());
+    g->stop_ids_ = stop_token_ids(cfg, g->tokenizer_);
+    return g;
+}
+
+GenerationConfig Generator::resolve(const GenerationOverrides& runtime) const
+{
+    return resolve_generation_config(generation_config_, GenerationOverrides(), runtime);
+}
+
+std::vector<uint32_t> Generator::encode(const std::string& prompt, const GenerationConfig& config) const
+{
+    return encode_prompt(tokenizer_, model_->config(), prompt, config);
+}
+
+std::string Generator::run(const std::string& prompt, const GenerationOverrides& runtime, const std::function<bool(const std::string&)>& on_text)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    const GenerationConfig config = resolve(runtime);
+    if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
+    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text);
 }
 
 }  // namespace kjarni

@@ -8,6 +8,7 @@
 //                        crates/kjarni-transformers/src/common/mod.rs:297-349 (generation_config.json)
 //   encode / stop ids    crates/kjarni-transformers/src/decoder/generator.rs:141-163, models/base.rs:261-271
 //   token text, cleanup  decoder/generator.rs:343-360, crates/kjarni/src/chat/model.rs:283-303
+//   Generator            crates/kjarni/src/generator/{model.rs:40-250, validation.rs:8-51} (raw completion, no template)
 #pragma once
 #include <functional>
 #include <memory>
@@ -115,6 +116,44 @@ private:
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
     std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
+};
+
+// Raw text completion (the reference's Generator): validation, model defaults (GenerationConfig::default() for GPT-2) and the
+// same token loop as Chat, with no template, no trimming and no stop-sequence stripping.
+class Generator {
+public:
+    // model_name: registry name (Llama, Qwen2, Mistral, GPT); model_dir overrides the directory.  Checks run in Chat::create's
+    // order: the name, the files on disk, Phi-3, then the load (the first GPU call).
+    static std::unique_ptr<Generator> create(const std::string& model_name, const std::string& model_dir, const std::string& cache_dir,
+                                             bool quiet);
+
+    const std::string& model_name() const { return model_name_; }
+    size_t context_size() const { return (size_t)model_->config().max_pos; }
+    size_t vocab_size() const { return (size_t)model_->config().vocab; }
+    LlmModel& model() { return *model_; }
+    GenerationConfig resolve(const GenerationOverrides& runtime) const;
+    std::vector<uint32_t> encode(const std::string& prompt, const GenerationConfig& config) const;  // DecoderGenerator::encode
+
+    // Generator::generate_with_config: the concatenated single-token decodes of the generated tokens, as they are.
+    std::string generate(const std::string& prompt, const GenerationOverrides& runtime) { return run(prompt, runtime, nullptr); }
+    std::string generate_stream(const std::string& prompt, const GenerationOverrides& runtime,
+                                const std::function<bool(const std::string&)>& on_text)
+    {
+        return run(prompt, runtime, on_text);
+    }
+    void reseed(uint64_t seed) { rng_.reseed(seed); }
+
+private:
+    Generator() = default;
+    std::string run(const std::string& prompt, const GenerationOverrides& runtime, const std::function<bool(const std::string&)>& on_text);
+
+    std::string model_name_;
+    std::unique_ptr<LlmModel> model_;
+    BpeTokenizer tokenizer_;
+    GenerationConfig generation_config_;  // the model's defaults (no builder overrides through the C ABI)
+    std::vector<uint32_t> stop_ids_;
+    UniformRng rng_;
+    std::mutex mutex_;
 };
 
 // str::trim (Unicode White_Space at both ends).

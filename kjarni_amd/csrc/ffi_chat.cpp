@@ -29,6 +29,10 @@ struct KjarniBpeTokenizer {
     BpeTokenizer tok;
 };
 
+struct KjarniGenerator {
+    std::unique_ptr<Generator> inner;
+};
+
 namespace {
 
 // CString::new(response): an interior NUL is an error here, not an empty string (chat.rs:303-313).
@@ -289,6 +293,79 @@ KJARNI_EXPORT size_t kjarni_chat_model_name(const KjarniChat* chat, char* buf, s
 
 KJARNI_EXPORT size_t kjarni_chat_context_size(const KjarniChat* chat) { return chat ? chat->inner->context_size() : 0; }
 
+// ---- Generator (raw completion; mirrors crates/kjarni/src/generator/*, not part of kjarni-ffi) ----------
+
+KJARNI_EXPORT KjarniGeneratorConfig kjarni_generator_config_default(void)
+{
+    KjarniGeneratorConfig c;
+    c.device = KJARNI_DEVICE_CPU;
+    c.cache_dir = nullptr;
+    c.model_name = nullptr;
+    c.model_path = nullptr;
+    c.quiet = 0;
+    return c;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_new(const KjarniGeneratorConfig* config, KjarniGenerator** out)
+{
+    if (!out) return KJARNI_ERROR_NULL_POINTER;
+    const KjarniGeneratorConfig dflt = kjarni_generator_config_default();
+    const KjarniGeneratorConfig& c = config ? *config : dflt;
+    if (!c.model_name) {
+        set_last_error("model_name is required");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!valid_utf8(c.model_name)) return KJARNI_ERROR_INVALID_UTF8;
+    if (c.cache_dir && !valid_utf8(c.cache_dir)) return KJARNI_ERROR_INVALID_UTF8;
+    if (c.model_path && !valid_utf8(c.model_path)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
+        auto h = std::make_unique<KjarniGenerator>();
+        h->inner = Generator::create(c.model_name, c.model_path ? c.model_path : "", c.cache_dir ? c.cache_dir : "", c.quiet != 0);
+        *out = h.release();
+    });
+}
+
+KJARNI_EXPORT void kjarni_generator_free(KjarniGenerator* gen) { delete gen; }
+
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_generate(KjarniGenerator* gen, const char* prompt, const KjarniGenerationConfig* gen_config,
+                                                        char** out)
+{
+    if (!gen || !prompt || !out) return KJARNI_ERROR_NULL_POINTER;
+    if (!valid_utf8(prompt)) return KJARNI_ERROR_INVALID_UTF8;
+    const KjarniErrorCode rc = generation_guarded(
+        [&] { *out = response_cstr(gen->inner->generate(prompt, gen_config ? to_overrides(*gen_config) : GenerationOverrides())); });
+    if (rc != KJARNI_OK) *out = nullptr;
+    return rc;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_stream(KjarniGenerator* gen, const char* prompt, const KjarniGenerationConfig* gen_config,
+                                                      KjarniStreamCallbackFn callback, void* user_data, const KjarniCancelToken* cancel_token)
+{
+    if (!gen || !prompt || !callback) return KJARNI_ERROR_NULL_POINTER;
+    if (!valid_utf8(prompt)) return KJARNI_ERROR_INVALID_UTF8;
+    return generation_guarded([&] {
+        gen->inner->generate_stream(prompt, gen_config ? to_overrides(*gen_config) : GenerationOverrides(), [&](const std::string& text) {
+            if (kjarni_cancel_token_is_cancelled(cancel_token)) return false;  // looked at before each callback
+            if (text.find('\0') != std::string::npos) return true;             // a token with a NUL byte is skipped, as in chat
+            return callback(text.c_str(), user_data);
+        });
+    });
+}
+
+KJARNI_EXPORT size_t kjarni_generator_model_name(const KjarniGenerator* gen, char* buf, size_t buf_len)
+{
+    if (!gen) return 0;
+    const std::string& name = gen->inner->model_name();
+    if (!buf || buf_len == 0) return name.size();
+    const size_t n = std::min(name.size(), buf_len - 1);
+    std::memcpy(buf, name.data(), n);
+    buf[n] = '\0';
+    return n;
+}
+
+KJARNI_EXPORT size_t kjarni_generator_context_size(const KjarniGenerator* gen) { return gen ? gen->inner->context_size() : 0; }
+KJARNI_EXPORT size_t kjarni_generator_vocab_size(const KjarniGenerator* gen) { return gen ? gen->inner->vocab_size() : 0; }
+
 // ---- one stage at a time (kjarni_hip.h) -------------------------------------------------------------
 
 KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_load(const char* tokenizer_json_path, KjarniBpeTokenizer** out)
@@ -535,6 +612,37 @@ KJARNI_EXPORT void kjarni_hip_chat_seed(KjarniChat* chat, uint64_t seed)
 KJARNI_EXPORT void kjarni_hip_chat_set_device_sampling(KjarniChat* chat, int32_t on)
 {
     if (chat) chat->inner->model().set_device_sampling(on != 0);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_resolve(const KjarniGenerator* gen, const KjarniGenerationConfig* runtime,
+                                                           KjarniResolvedGeneration* out)
+{
+    if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN,
+                   [&] { fill_resolved(gen->inner->resolve(runtime ? to_overrides(*runtime) : GenerationOverrides()), out); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_encode(const KjarniGenerator* gen, const char* prompt, const KjarniGenerationConfig* runtime,
+                                                          uint32_t* ids_out, size_t capacity, size_t* n_out)
+{
+    if (!gen || !prompt || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const Generator& g = *gen->inner;
+        const std::vector<uint32_t> ids = g.encode(prompt, g.resolve(runtime ? to_overrides(*runtime) : GenerationOverrides()));
+        *n_out = ids.size();
+        if (ids_out)
+            for (size_t i = 0; i < ids.size() && i < capacity; ++i) ids_out[i] = ids[i];
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_generator_seed(KjarniGenerator* gen, uint64_t seed)
+{
+    if (gen) gen->inner->reseed(seed);
+}
+
+KJARNI_EXPORT void kjarni_hip_generator_set_device_sampling(KjarniGenerator* gen, int32_t on)
+{
+    if (gen) gen->inner->model().set_device_sampling(on != 0);
 }
 
 KJARNI_EXPORT void kjarni_hip_chat_sampling_counters(KjarniChat* chat, uint64_t* from_candidates, uint64_t* from_logits)

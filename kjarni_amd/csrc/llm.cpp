@@ -40,8 +40,45 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         return (int)v->as_int();
     };
     c.model_type = j.get_string("model_type", "llama");
-    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "mistral")
-        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2 and mistral are)");
+    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "mistral" && c.model_type != "gpt2")
+        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2, mistral and gpt2 are)");
+    auto ids = [&] {  // eos / bos as for every type
+        if (const Json* e = j.find("eos_token_id")) {
+            if (e->is_number()) c.eos_ids.push_back((uint32_t)e->as_int());
+            else if (e->is_array())
+                for (const Json& x : e->arr)
+                    if (x.is_number()) c.eos_ids.push_back((uint32_t)x.as_int());
+        }
+        if (const Json* b = j.find("bos_token_id"); b && b->is_number()) {
+            c.has_bos = true;
+            c.bos_id = (uint32_t)b->as_int();
+        }
+    };
+    if (c.gpt2()) {  // gpt2/config.rs:8-105, HF field names
+        c.hidden = req("n_embd");
+        c.layers = req("n_layer");
+        c.heads = c.kv_heads = req("n_head");
+        c.max_pos = req("n_ctx");  // what the reference reads; HF files also carry n_positions, which must agree
+        if (const Json* np = j.find("n_positions"); np && np->is_number() && (int)np->as_int() != c.max_pos)
+            throw std::runtime_error("config.json: n_positions (" + std::to_string(np->as_int()) + ") differs from n_ctx (" +
+                                     std::to_string(c.max_pos) + ")");
+        c.vocab = req("vocab_size");
+        if (c.heads <= 0 || c.hidden % c.heads) throw std::runtime_error("config.json: unsupported head geometry");
+        c.head_dim = c.hidden / c.heads;
+        c.eps = (float)j.get_double("layer_norm_epsilon", 1e-5);
+        c.tie_embeddings = true;  // the head is wte
+        // activations.rs:40-41: gelu, gelu_new and gelu_fast all run the tanh form, as does an absent field
+        if (const Json* a = j.find("activation_function"); a && !a->is_null()) {
+            const std::string act = a->is_string() ? a->str : std::string("?");
+            if (act != "gelu_new" && act != "gelu_fast" && act != "gelu")
+                throw std::runtime_error("config.json: unsupported activation_function '" + act + "' (gelu_new, gelu_fast and gelu are)");
+        }
+        const Json* ni = j.find("n_inner");  // cpu_decoder.rs:194; the loader checks it against the c_fc weight
+        c.inter = ni && ni->is_number() ? (int)ni->as_int() : 4 * c.hidden;
+        c.rope_theta = 0.0f;
+        ids();
+        return c;
+    }
     c.hidden = req("hidden_size");
     c.layers = req("num_hidden_layers");
     c.heads = req("num_attention_heads");
@@ -64,16 +101,7 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         c.rope_high = (float)rs->get_double("high_freq_factor", 4.0);
         c.rope_original_max = (int)rs->get_int("original_max_position_embeddings", 8192);
     }
-    if (const Json* e = j.find("eos_token_id")) {
-        if (e->is_number()) c.eos_ids.push_back((uint32_t)e->as_int());
-        else if (e->is_array())
-            for (const Json& x : e->arr)
-                if (x.is_number()) c.eos_ids.push_back((uint32_t)x.as_int());
-    }
-    if (const Json* b = j.find("bos_token_id"); b && b->is_number()) {
-        c.has_bos = true;
-        c.bos_id = (uint32_t)b->as_int();
-    }
+    ids();
     if (c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.head_dim * c.heads != c.hidden)
         throw std::runtime_error("config.json: unsupported head geometry");
     return c;
@@ -156,6 +184,12 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         m->quant_ = weights == 0;
     } else {
         st.open_dir(dir);
+        if (c.gpt2()) {
+            m->cache_cap_ = std::min(max_context > 0 ? max_context : c.max_pos, c.max_pos);
+            m->load_gpt2(st, weights);
+            m->finish_load();
+            return m;
+        }
         m->bf16_ = weights == 2 || (weights == 0 && st.get("model.layers.0.self_attn.q_proj.weight").dtype == "BF16");
     }
     std::vector<float> buf, tmp;
@@ -296,37 +330,107 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         m->cos_ = m->upload_f32(cs);
         m->sin_ = m->upload_f32(sn);
     }
+    m->finish_load();
+    return m;
+}
+
+void LlmModel::finish_load()
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim;
     // key ranges per head: up to 512 keys each (128 of them are one register-held pass of the attention kernel); few enough
     // that the output projection can merge the slabs itself
-    m->splits_ = std::max(1, std::min(64, (m->cache_cap_ + 511) / 512));
+    splits_ = std::max(1, std::min(64, (cache_cap_ + 511) / 512));
 #ifdef KJARNI_TUNING
-    if (const char* v = std::getenv("KJARNI_HIP_LLM_SPLITS")) m->splits_ = std::max(1, std::atoi(v));  // measurements
+    if (const char* v = std::getenv("KJARNI_HIP_LLM_SPLITS")) splits_ = std::max(1, std::atoi(v));  // measurements
 #endif
-    while ((m->cache_cap_ + m->splits_ - 1) / m->splits_ > 512) ++m->splits_;
-    m->h_ = m->dalloc(8 * (size_t)H);
-    m->q_ = m->dalloc(8 * (size_t)H);
-    m->ctx_ = m->dalloc(8 * (size_t)H);
-    m->last_ = m->dalloc(8 * (size_t)H);
-    m->mid_ = m->dalloc(8 * (size_t)c.inter);
-    if (m->quant_) {
+    while ((cache_cap_ + splits_ - 1) / splits_ > 512) ++splits_;
+    h_ = dalloc(8 * (size_t)H);
+    q_ = dalloc(8 * (size_t)H);
+    ctx_ = dalloc(8 * (size_t)H);
+    last_ = dalloc(8 * (size_t)H);
+    mid_ = dalloc(8 * (size_t)c.inter);
+    if (quant_) {
         const size_t wide = (size_t)std::max(H, c.inter);
-        m->xn_ = m->dalloc(8 * wide);
-        m->xq_ = reinterpret_cast<int8_t*>(m->dalloc(2 * wide));
-        m->xd_ = m->dalloc(8 * wide / 256 + 4);
+        xn_ = dalloc(8 * wide);
+        xq_ = reinterpret_cast<int8_t*>(dalloc(2 * wide));
+        xd_ = dalloc(8 * wide / 256 + 4);
     }
-    m->logits_ = m->dalloc((size_t)c.vocab);
-    m->att_scratch_ = m->dalloc(decode_attention_scratch_floats(8, c.heads, d, m->splits_));
-    m->ids_ = reinterpret_cast<uint32_t*>(m->dalloc(8));
-    m->token_ = reinterpret_cast<int32_t*>(m->dalloc(4));
-    m->hist_cap_ = m->cache_cap_ + 16;
-    m->hist_ = reinterpret_cast<int32_t*>(m->dalloc((size_t)m->hist_cap_));
-    m->pos_ = reinterpret_cast<int*>(m->dalloc(4));
-    m->count_ = reinterpret_cast<int*>(m->dalloc(4));
-    m->best_ = reinterpret_cast<unsigned long long*>(m->dalloc(4));
-    hip_check(hipMemset(m->best_, 0, 8), "memset");
-    hip_check(hipStreamCreateWithFlags(&m->stream_, hipStreamNonBlocking), "hipStreamCreate");
+    logits_ = dalloc((size_t)c.vocab);
+    att_scratch_ = dalloc(decode_attention_scratch_floats(8, c.heads, d, splits_));
+    ids_ = reinterpret_cast<uint32_t*>(dalloc(8));
+    token_ = reinterpret_cast<int32_t*>(dalloc(4));
+    hist_cap_ = cache_cap_ + 16;
+    hist_ = reinterpret_cast<int32_t*>(dalloc((size_t)hist_cap_));
+    pos_ = reinterpret_cast<int*>(dalloc(4));
+    count_ = reinterpret_cast<int*>(dalloc(4));
+    best_ = reinterpret_cast<unsigned long long*>(dalloc(4));
+    hip_check(hipMemset(best_, 0, 8), "memset");
+    hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(load)");
-    return m;
+}
+
+// GPT-2 tensors (gpt2/config.rs:80-125).  gpt2 files name them `wte.weight`, `h.0.attn.c_attn.weight`, ...; distilgpt2 files
+// carry a `transformer.` prefix.  The reference picks the prefix by model name; here the file decides, by which of
+// `wte.weight` / `transformer.wte.weight` it holds.  The causal-mask buffers older files carry (h.N.attn.bias,
+// h.N.attn.masked_bias) and a stored lm_head.weight are never read: the head is wte.  The Conv1D matrices are stored
+// [in, out] and are transposed once, here on the host, into the [out, in] rows the kernels read.
+void LlmModel::load_gpt2(SafeTensors& st, int weights)
+{
+    gpt2_ = true;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, I = c.inter;
+    std::string p;
+    if (st.contains("wte.weight")) p = "";
+    else if (st.contains("transformer.wte.weight")) p = "transformer.";
+    else throw std::runtime_error("GPT-2 checkpoint without wte.weight or transformer.wte.weight");
+    bf16_ = weights == 2 || (weights == 0 && st.get(p + "wte.weight").dtype == "BF16");
+    std::vector<float> buf, t;
+    auto read = [&](const std::string& name, std::vector<int64_t> want) {
+        if (!st.contains(name)) throw std::runtime_error("missing tensor " + name);
+        if (st.read_f32(name, buf) != want) throw std::runtime_error("tensor " + name + " has an unexpected shape");
+    };
+    auto vec = [&](const std::string& name, int n) {
+        read(name, {n});
+        return upload_f32(buf);
+    };
+    auto conv1d = [&](const std::string& name, int in, int out) {  // Conv1D [in, out] -> [out, in]
+        read(name, {in, out});
+        t.resize(buf.size());
+        for (int i = 0; i < in; ++i)
+            for (int o = 0; o < out; ++o) t[(size_t)o * in + i] = buf[(size_t)i * out + o];
+        return upload_weight(t);
+    };
+    layers_.resize((size_t)c.layers);
+    for (int i = 0; i < c.layers; ++i) {
+        const std::string q = p + "h." + std::to_string(i) + ".";
+        Layer& L = layers_[(size_t)i];
+        L.up = nullptr;
+        const TensorView& fc = st.get(q + "mlp.c_fc.weight");  // the intermediate width: n_inner when set, else 4 x n_embd
+        if (fc.shape.size() != 2 || fc.shape[0] != H || fc.shape[1] != I)
+            throw std::runtime_error("tensor " + q + "mlp.c_fc.weight has an unexpected shape (want [" + std::to_string(H) + ", " +
+                                     std::to_string(I) + "] from n_inner / 4 x n_embd)");
+        L.ln1 = vec(q + "ln_1.weight", H);
+        L.ln1_b = vec(q + "ln_1.bias", H);
+        L.wqkv = conv1d(q + "attn.c_attn.weight", H, 3 * H);
+        L.bqkv = vec(q + "attn.c_attn.bias", 3 * H);
+        L.wo = conv1d(q + "attn.c_proj.weight", H, H);
+        L.bo = vec(q + "attn.c_proj.bias", H);
+        L.ln2 = vec(q + "ln_2.weight", H);
+        L.ln2_b = vec(q + "ln_2.bias", H);
+        L.gate = conv1d(q + "mlp.c_fc.weight", H, I);
+        L.bfc = vec(q + "mlp.c_fc.bias", I);
+        L.down = conv1d(q + "mlp.c_proj.weight", I, H);
+        L.bdown = vec(q + "mlp.c_proj.bias", H);
+        L.k_cache = dalloc((size_t)cache_cap_ * H);
+        L.v_cache = dalloc((size_t)cache_cap_ * H);
+    }
+    read(p + "wte.weight", {c.vocab, H});
+    embed_ = lm_head_ = upload_weight(buf);
+    read(p + "wpe.weight", {c.max_pos, H});
+    wpe_ = upload_weight(buf);
+    final_norm_ = vec(p + "ln_f.weight", H);
+    final_norm_b_ = vec(p + "ln_f.bias", H);
 }
 
 void LlmModel::reset()
@@ -345,6 +449,10 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
     const int* pp = device_pos ? pos_ : nullptr;
     if (quant_) {
         pass_quant(ids_dev, n, device_pos);
+        return;
+    }
+    if (gpt2_) {
+        pass_gpt2(ids_dev, n, device_pos);
         return;
     }
     // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
@@ -407,6 +515,47 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
         hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
         lm.X = last_ + (size_t)(n - 1) * H;
     }
+    hip_check(launch_llm_gemv(lm, s), "lm head");
+}
+
+// pass() for GPT-2 (gpt2/cpu_decoder.rs:371-394): the token + position embedding, then per layer the same five launches as
+// the bf16 Llama step -- LayerNorm(ln_1) + Q|K|V + bias (K / V rows into the cache, no rotation), attention, c_proj + bias +
+// residual, LayerNorm(ln_2) + c_fc + bias + GELU-tanh, mlp.c_proj + bias + residual -- and LayerNorm(ln_f) + the tied head.
+void LlmModel::pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, I = c.inter;
+    const int* pp = device_pos ? pos_ : nullptr;
+    hip_check(launch_llm_embed_pos(ids_dev, n, H, c.vocab, embed_, wpe_, c.max_pos, bf16_ ? 1 : 0, cache_len_, pp, h_, s), "embed");
+    for (const Layer& L : layers_) {
+        LlmGemvArgs a;
+        a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = 1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_;
+        a.bias = L.bqkv; a.n_out = 3 * H; a.k = H; a.seg_q = H; a.seg_kv = H; a.Y0 = q_; a.ldy0 = H; a.Y1 = L.k_cache; a.Y2 = L.v_cache;
+        a.ldy12 = H; a.row_off = cache_len_; a.row_off_ptr = pp;
+        hip_check(launch_llm_gemv(a, s), "ln_1 + c_attn");
+        const bool merge_in_proj = n == 1 && llm_gemv_merges_attention(H, splits_, d);
+        hip_check(launch_decode_attention(q_, H, n, L.k_cache, H, L.v_cache, H, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_, splits_,
+                                          att_scratch_, merge_in_proj ? nullptr : ctx_, H, s, 1), "attention");
+        LlmGemvArgs o;
+        o.X = ctx_; o.ldx = H; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = H; o.Y0 = h_; o.ldy0 = H;
+        if (merge_in_proj) {
+            o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
+        }
+        hip_check(launch_llm_gemv(o, s), "attn c_proj");
+        LlmGemvArgs f;
+        f.X = h_; f.ldx = H; f.rows = n; f.gamma = L.ln2; f.beta = L.ln2_b; f.layernorm = 1; f.eps = c.eps; f.W = L.gate; f.bf16 = bf16_;
+        f.bias = L.bfc; f.gelu_tanh = 1; f.n_out = I; f.k = H; f.Y0 = mid_; f.ldy0 = I;
+        hip_check(launch_llm_gemv(f, s), "ln_2 + c_fc + gelu");
+        LlmGemvArgs dn;
+        dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
+        dn.Y0 = h_; dn.ldy0 = H;
+        hip_check(launch_llm_gemv(dn, s), "mlp c_proj");
+    }
+    hip_check(launch_layernorm(h_, final_norm_, final_norm_b_, c.eps, n, H, last_, s), "ln_f");
+    LlmGemvArgs lm;
+    lm.X = last_ + (size_t)(n - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
+    lm.Y0 = logits_; lm.ldy0 = c.vocab;
     hip_check(launch_llm_gemv(lm, s), "lm head");
 }
 
@@ -516,6 +665,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
         const int m = std::min(prefill_cap_, n - done);
         hip_check(hipMemcpyAsync(pids_, ids_host + done, (size_t)m * 4, hipMemcpyHostToDevice, s), "H2D ids");
         if (quant_) hip_check(launch_qembed(pids_, m, qembed_, ph_, s), "embed");
+        else if (gpt2_) hip_check(launch_llm_embed_pos(pids_, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, cache_len_, nullptr, ph_, s), "embed");
         else hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
         // Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T).  Blocks of >= kTileRows rows run the
         // encoder's 128 x 128-tile f32 GEMM (gemm.hip), bf16 weights on an f32 copy made just before (100 MB moved per 69 GFLOP
@@ -523,8 +673,9 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
         // (the 2 048-wide projections are then 192 tiles on 256 CUs): hence kTileRows.
         // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
         const bool tile_shapes = H % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
+        // gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
         auto proj = [&](const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                        float* gate, const char* what, const QMat* qm = nullptr) {
+                        float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false) {
             // a quantized matrix: dequantized into the f32 scratch first; a Q6_K linear also takes its activation rows through
             // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
             int wbu = wb;
@@ -552,6 +703,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
             const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
             if (!tiles) {
                 hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
+                if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
                 return;
             }
             ++tile_gemm_calls_;
@@ -567,6 +719,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
                     hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
                 else
                     hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, R, ldy, Y, ldy, m, N, K, R ? EPI_BIAS_RESIDUAL : EPI_BIAS, s), what);
+                if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
                 return;
             }
             const float* W32 = static_cast<const float*>(W);
@@ -577,19 +730,23 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
             if (gate)
                 hip_check(launch_gemm(Ain, lda, W32, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
             else
-                hip_check(launch_gemm(Ain, lda, W32, bias, R, ldy, Y, ldy, m, N, K, R ? EPI_BIAS_RESIDUAL : EPI_BIAS, s), what);
+                hip_check(launch_gemm(Ain, lda, W32, bias, R, ldy, Y, ldy, m, N, K, gelu ? EPI_BIAS_GELU_NEW : (R ? EPI_BIAS_RESIDUAL : EPI_BIAS), s),
+                          what);
         };
         for (const Layer& L : layers_) {
             float* k_rows = L.k_cache + (size_t)cache_len_ * kv;
             float* v_rows = L.v_cache + (size_t)cache_len_ * kv;
-            hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
+            if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
+            else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
             proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, H, H, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
             proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)H * H), L.bqkv ? L.bqkv + H : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj",
                  quant_ ? &L.k : nullptr);
             proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(H + kv) * H), L.bqkv ? L.bqkv + H + kv : nullptr, nullptr, v_rows, kv, kv, H,
                  nullptr, "v proj", quant_ ? &L.v : nullptr);
-            hip_check(launch_rope(pq_, H, m, c.heads, d, cos_, sin_, cache_len_, nullptr, 0, s), "rope q");
-            hip_check(launch_rope(L.k_cache, kv, m, c.kv_heads, d, cos_, sin_, cache_len_, nullptr, 1, s), "rope k");
+            if (!gpt2_) {  // (GPT-2: learned positions, already in the embedding)
+                hip_check(launch_rope(pq_, H, m, c.heads, d, cos_, sin_, cache_len_, nullptr, 0, s), "rope q");
+                hip_check(launch_rope(L.k_cache, kv, m, c.kv_heads, d, cos_, sin_, cache_len_, nullptr, 1, s), "rope k");
+            }
             if (prefill_attention_supported(d)) {
                 hip_check(launch_prefill_attention(pq_, H, m, L.k_cache, kv, L.v_cache, kv, cache_len_, c.heads, d, c.heads / c.kv_heads, pctx_, H, s),
                           "attention");
@@ -601,7 +758,13 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
                                                       c.heads / c.kv_heads), "attention");
                 }
             }
-            proj(pctx_, H, L.wo, nullptr, ph_, ph_, H, H, H, nullptr, "o proj", quant_ ? &L.o : nullptr);
+            proj(pctx_, H, L.wo, L.bo, ph_, ph_, H, H, H, nullptr, "o proj", quant_ ? &L.o : nullptr);
+            if (gpt2_) {
+                hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
+                proj(pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
+                proj(pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
+                continue;
+            }
             hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
             proj(pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", quant_ ? &L.gate_q : nullptr);
             proj(pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
@@ -610,7 +773,8 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
         cache_len_ += m;
         if (done + m == n) {
             const int rows = (n - 1) % 8 + 1;
-            hip_check(launch_rmsnorm(ph_ + (size_t)(m - rows) * H, final_norm_, c.eps, rows, H, last_, s), "final norm");
+            if (gpt2_) hip_check(launch_layernorm(ph_ + (size_t)(m - rows) * H, final_norm_, final_norm_b_, c.eps, rows, H, last_, s), "ln_f");
+            else hip_check(launch_rmsnorm(ph_ + (size_t)(m - rows) * H, final_norm_, c.eps, rows, H, last_, s), "final norm");
             if (quant_) {
                 qlinear(qhead_, last_ + (size_t)(rows - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
             } else {

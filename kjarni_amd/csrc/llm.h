@@ -1,10 +1,11 @@
-// LlmModel: a decoder-only transformer (Llama / Qwen2 layouts) resident in HBM with an f32 KV cache, and the
-// greedy generation loop.
+// LlmModel: a decoder-only transformer (Llama / Qwen2 / Mistral layouts, and GPT-2) resident in HBM with an f32 KV cache,
+// and the generation loop.
 //
 //   config + tensor names   crates/kjarni-models/src/models/llama/config.rs:98-330, qwen/config.rs:80-275
 //   layer                   crates/kjarni-transformers/src/cpu/decoder/rope_decoder_layer.rs:18-41
 //   model forward           crates/kjarni-models/src/models/llama/cpu_decoder.rs:142-219
 //   generation loop         crates/kjarni-transformers/src/decoder/generator.rs:228-381 (DecodingStrategy::Greedy)
+//   GPT-2                   crates/kjarni-models/src/models/gpt2/{config.rs:8-125, cpu_decoder.rs:180-394}
 #pragma once
 #include "device_arena.h"
 #include <hip/hip_runtime.h>
@@ -21,6 +22,8 @@
 
 namespace kjarni {
 
+class SafeTensors;
+
 struct LlmConfig {
     std::string model_type;
     int hidden = 0, layers = 0, heads = 0, kv_heads = 0, head_dim = 0, inter = 0, vocab = 0, max_pos = 0;
@@ -33,6 +36,7 @@ struct LlmConfig {
     std::vector<uint32_t> eos_ids;
     bool has_bos = false;
     uint32_t bos_id = 0;
+    bool gpt2() const { return model_type == "gpt2"; }  // LayerNorm + biases, GELU MLP, learned positions, head tied to wte
     static LlmConfig from_json(const std::string& text);
 };
 
@@ -101,6 +105,9 @@ private:
     float* dalloc(size_t floats);
     void pass(const uint32_t* ids_dev, int n, bool device_pos);
     void pass_quant(const uint32_t* ids_dev, int n, bool device_pos);  // pass() on quantized matrices (quant_kernels.hip)
+    void pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos);   // pass() for a GPT-2 layer stack
+    void load_gpt2(SafeTensors& st, int weights);                      // GPT-2 tensors (Conv1D matrices transposed on the host)
+    void finish_load();                                                // attention splits, workspace, stream
     // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
     void qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what);
     void prefill_rows(const uint32_t* ids_host, int n);  // n new tokens through the matrix-core GEMMs
@@ -108,14 +115,15 @@ private:
     hipGraphExec_t step_graph();
 
     struct Layer {
-        void *wqkv, *wo, *gate, *up, *down;
+        void *wqkv, *wo, *gate, *up, *down;  // GPT-2: c_attn, attn.c_proj, mlp.c_fc (in `gate`), mlp.c_proj (in `down`), as [out, in]
         float *bqkv, *ln1, *ln2;
+        float *ln1_b = nullptr, *ln2_b = nullptr, *bo = nullptr, *bfc = nullptr, *bdown = nullptr;  // GPT-2's LayerNorm and projection biases
         float *k_cache, *v_cache;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
     };
     LlmConfig cfg_;
     int device_ = 0;
-    bool bf16_ = false, quant_ = false;
+    bool bf16_ = false, quant_ = false, gpt2_ = false;
     size_t weight_bytes_ = 0;
     uint64_t bytes_by_type_[32] = {};
     std::string config_json_;
@@ -129,6 +137,8 @@ private:
     std::vector<Layer> layers_;
     void *embed_ = nullptr, *lm_head_ = nullptr;
     float *final_norm_ = nullptr, *cos_ = nullptr, *sin_ = nullptr;
+    void* wpe_ = nullptr;               // GPT-2: learned position table [n_ctx, hidden], the weights' dtype
+    float* final_norm_b_ = nullptr;     // GPT-2: ln_f bias
     // workspace
     float *h_ = nullptr, *q_ = nullptr, *ctx_ = nullptr, *mid_ = nullptr, *last_ = nullptr, *logits_ = nullptr, *att_scratch_ = nullptr;
     uint32_t* ids_ = nullptr;

@@ -5,13 +5,16 @@
 
 namespace kjarni {
 
-// Y = epi(rmsnorm?(X) W^T + b) for up to 8 rows; W (and W2) are f32 or bf16 [n_out, k] row-major, k % 8 == 0.
+// Y = epi(norm?(X) W^T + b) for up to 8 rows; W (and W2) are f32 or bf16 [n_out, k] row-major, k % 8 == 0.
 struct LlmGemvArgs {
     const float* X = nullptr;
     int64_t ldx = 0;
     int rows = 0;
-    const float* gamma = nullptr;  // non-null: RMS-normalise the rows first
+    const float* gamma = nullptr;  // non-null: RMS-normalise the rows first (LayerNorm when `layernorm` is set)
     float eps = 0.0f;
+    int layernorm = 0;             // GPT-2: (x - mean) / sqrt(var + eps) * gamma + beta instead of RMSNorm
+    const float* beta = nullptr;
+    int gelu_tanh = 0;             // epilogue gelu_tanh(x.W + b) (GPT-2's c_fc; only after LayerNorm, no segments)
     const void* W = nullptr;
     const void* W2 = nullptr;      // SwiGLU `up` matrix
     int bf16 = 0;
@@ -79,6 +82,12 @@ hipError_t launch_touch(const void* p, size_t bytes, unsigned* sink, hipStream_t
 #endif
 hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, const void* table, int bf16, float* out,
                             hipStream_t stream);
+// GPT-2: out[s] = table[ids[s]] + pos_table[p + s] for n rows, p = *pos_ptr when pos_ptr is non-null (graph replay), else pos;
+// both tables in the weights' dtype, pos_table [max_pos, hidden].
+hipError_t launch_llm_embed_pos(const uint32_t* ids, int n, int hidden, int vocab, const void* table, const void* pos_table, int max_pos,
+                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream);
+// In place x = gelu_tanh(x) (activations.rs:62-66) over n floats, n % 4 == 0: the prompt route's c_fc epilogue where the GEMM has none.
+hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream);
 // argmax (last maximum wins); best_scratch: one zero-initialised u64 (re-zeroed by the call); history/count/pos may be null.
 hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* best_scratch, int32_t* out, int32_t* history, int* count,
                          int* pos, hipStream_t stream);

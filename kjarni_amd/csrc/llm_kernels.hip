@@ -1,6 +1,6 @@
-// Kernels of the decoder-only (Llama / Qwen2) path: a weight-streaming GEMV for 1-8 rows over f32 or bf16
-// weights with RMSNorm folded in and the Q|K|V, SwiGLU and residual epilogues; RoPE; embedding gather;
-// a two-stage argmax.  Attention over the KV cache reuses decode_attention_* (whisper_kernels.hip) with a
+// Kernels of the decoder-only (Llama / Qwen2 / GPT-2) path: a weight-streaming GEMV for 1-8 rows over f32 or bf16
+// weights with RMSNorm or LayerNorm folded in and the Q|K|V, SwiGLU, GELU-tanh and residual epilogues; RoPE; embedding
+// gather (with learned positions for GPT-2); a two-stage argmax.  Attention over the KV cache reuses decode_attention_* (whisper_kernels.hip) with a
 // grouped-query head mapping.
 //
 //   RMSNorm   crates/kjarni-transformers/src/cpu/normalization/rms_norm.rs:19-27
@@ -51,31 +51,58 @@ __device__ __forceinline__ F8 load8(const uint16_t* row, int i)
     return r;
 }
 
-enum : int { LE_NONE = 0, LE_RESIDUAL = 1, LE_SWIGLU = 2 };
+enum : int { LE_NONE = 0, LE_RESIDUAL = 1, LE_SWIGLU = 2, LE_GELU_TANH = 3 };
+// Row normalisation in a kernel's prologue: none, RMSNorm (Llama) or LayerNorm with a bias (GPT-2: (x - mean) / sqrt(var + eps)
+// * gamma + beta, the arithmetic of the encoder's layernorm kernels, rowops.hip).
+enum : int { NK_NONE = 0, NK_RMS = 1, NK_LN = 2 };
 
 // Y[r, n] = epi(norm?(X[r, :]) . W[n, :] + bias[n]) for up to 8 rows; one wave per output column.
-//  NORM: rows are RMS-normalised on the fly: (x / sqrt(mean(x^2) + eps)) * gamma, statistics recomputed per wave.
+//  NORM: rows are RMS-normalised on the fly: (x / sqrt(mean(x^2) + eps)) * gamma, statistics recomputed per wave
+//  (NK_LN: LayerNorm, mean and variance in two passes, + beta).
+//  LE_GELU_TANH: gelu_tanh(x.W[n] + bias[n]).
 //  LE_SWIGLU: W2 is the `up` matrix; the output is silu(x.W[n]) * (x.W2[n]).
 //  LE_RESIDUAL: + R[r, n].
 //  seg > 0: columns [0,seg_q) -> Y0, then two segments of seg_kv columns -> Y1 / Y2 at row (*row_off_ptr | row_off) + r
 //  (Q to scratch, K and V straight into the cache).
-template <typename WT, int EPI, bool NORM>
+template <typename WT, int EPI, int NORM>
 __global__ __launch_bounds__(256) void llm_gemv_kernel(const float* __restrict__ X, int64_t ldx, int rows,
                                                        const float* __restrict__ gamma, float eps, const WT* __restrict__ W,
                                                        const WT* __restrict__ W2, const float* __restrict__ bias,
                                                        const float* __restrict__ R, int64_t ldr, int n_out, int k, int seg_q,
                                                        int seg_kv, float* __restrict__ Y0, int64_t ldy0, float* __restrict__ Y1,
                                                        float* __restrict__ Y2, int64_t ldy12, int row_off,
-                                                       const int* __restrict__ row_off_ptr)
+                                                       const int* __restrict__ row_off_ptr, const float* __restrict__ beta)
 {
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (n >= n_out) return;
     const int k8 = k >> 3;
-    float scale[LLM_MAX_ROWS];
+    float scale[LLM_MAX_ROWS], mu[LLM_MAX_ROWS];
 #pragma unroll
-    for (int r = 0; r < LLM_MAX_ROWS; ++r) scale[r] = 1.0f;
-    if (NORM) {
+    for (int r = 0; r < LLM_MAX_ROWS; ++r) scale[r] = 1.0f, mu[r] = 0.0f;
+    if (NORM == NK_LN) {
+#pragma unroll
+        for (int r = 0; r < LLM_MAX_ROWS; ++r) {
+            if (r < rows) {
+                float s = 0.0f;
+                for (int i = lane; i < k8; i += 64) {
+                    const F8 x = load8(X + r * ldx, i);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) s += x.v[c];
+                }
+                const float m = wave_sum(s) / (float)k;
+                float v = 0.0f;
+                for (int i = lane; i < k8; i += 64) {
+                    const F8 x = load8(X + r * ldx, i);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) v = fmaf(x.v[c] - m, x.v[c] - m, v);
+                }
+                mu[r] = m;
+                scale[r] = 1.0f / sqrtf(wave_sum(v) / (float)k + eps);  // the inverse standard deviation
+            }
+        }
+    }
+    if (NORM == NK_RMS) {
 #pragma unroll
         for (int r = 0; r < LLM_MAX_ROWS; ++r) {
             if (r < rows) {
@@ -98,15 +125,20 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(const float* __restrict__
         const F8 w = load8(w_row, i);
         F8 w2;
         if (EPI == LE_SWIGLU) w2 = load8(w2_row, i);
-        F8 g;
+        F8 g, be;
         if (NORM) g = load8(gamma, i);
+        if (NORM == NK_LN) be = load8(beta, i);
 #pragma unroll
         for (int r = 0; r < LLM_MAX_ROWS; ++r) {
             if (r < rows) {
                 F8 x = load8(X + r * ldx, i);
-                if (NORM) {
+                if (NORM == NK_RMS) {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) x.v[c] = (x.v[c] / scale[r]) * g.v[c];
+                }
+                if (NORM == NK_LN) {
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) x.v[c] = (x.v[c] - mu[r]) * scale[r] * g.v[c] + be.v[c];
                 }
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
@@ -134,6 +166,7 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(const float* __restrict__
                 const float u = wave_sum(acc2[r]);
                 v = (v / (1.0f + expf(-v))) * u;  // silu(gate) * up
             }
+            if (EPI == LE_GELU_TANH) v = gelu_tanh(v);
             if (EPI == LE_RESIDUAL) v += R[r * ldr + n];
             if (lane == 0) Y[(r0 + r) * ldy + col] = v;
         }
@@ -147,20 +180,43 @@ __global__ __launch_bounds__(256) void llm_gemv_kernel(const float* __restrict__
 constexpr int G1_OPW = 2;        // outputs per wave
 constexpr int G1_MAX_K = 16384;  // 64 KiB of LDS
 
-template <typename WT, int EPI, bool NORM>
+template <typename WT, int EPI, int NORM>
 __global__ __launch_bounds__(256) void llm_gemv1_kernel(const float* __restrict__ X, const float* __restrict__ gamma, float eps,
                                                         const WT* __restrict__ W, const WT* __restrict__ W2,
                                                         const float* __restrict__ bias, const float* __restrict__ R, int n_out,
                                                         int k, int seg_q, int seg_kv, float* __restrict__ Y0,
                                                         float* __restrict__ Y1, float* __restrict__ Y2, int64_t ldy12, int row_off,
-                                                        const int* __restrict__ row_off_ptr)
+                                                        const int* __restrict__ row_off_ptr, const float* __restrict__ beta)
 {
     extern __shared__ float xs[];  // [k]
     __shared__ float red[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k8 = k >> 3;
-    float rms = 1.0f;
-    if (NORM) {
+    float rms = 1.0f, mu = 0.0f, inv = 1.0f;
+    if (NORM == NK_LN) {  // mean, then the variance around it: two passes over the row (L2-resident)
+        float s = 0.0f;
+        for (int i = tid; i < k8; i += 256) {
+            const F8 x = load8(X, i);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) s += x.v[c];
+        }
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        mu = ((red[0] + red[1]) + (red[2] + red[3])) / (float)k;
+        __syncthreads();
+        float v = 0.0f;
+        for (int i = tid; i < k8; i += 256) {
+            const F8 x = load8(X, i);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v = fmaf(x.v[c] - mu, x.v[c] - mu, v);
+        }
+        v = wave_sum(v);
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        inv = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)k + eps);
+    }
+    if (NORM == NK_RMS) {
         float s = 0.0f;
         for (int i = tid; i < k8; i += 256) {
             const F8 x = load8(X, i);
@@ -174,10 +230,15 @@ __global__ __launch_bounds__(256) void llm_gemv1_kernel(const float* __restrict_
     }
     for (int i = tid; i < k8; i += 256) {
         F8 x = load8(X, i);
-        if (NORM) {
+        if (NORM == NK_RMS) {
             const F8 g = load8(gamma, i);
 #pragma unroll
             for (int c = 0; c < 8; ++c) x.v[c] = (x.v[c] / rms) * g.v[c];
+        }
+        if (NORM == NK_LN) {
+            const F8 g = load8(gamma, i), be = load8(beta, i);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) x.v[c] = (x.v[c] - mu) * inv * g.v[c] + be.v[c];
         }
         *reinterpret_cast<f32x4*>(xs + i * 8) = f32x4{x.v[0], x.v[1], x.v[2], x.v[3]};
         *reinterpret_cast<f32x4*>(xs + i * 8 + 4) = f32x4{x.v[4], x.v[5], x.v[6], x.v[7]};
@@ -248,11 +309,11 @@ __global__ __launch_bounds__(256) void llm_gemv1_kernel(const float* __restrict_
 // input row once per OPW columns instead of once per column.
 constexpr int SK_MAX_CHUNKS = 8;  // k <= 8 * 256 * 8 = 16384 with 4 waves; long rows (k >= 8192) use 16 waves per workgroup
 
-template <typename WT, int EPI, bool NORM, int OPW, int CH, int NW>
+template <typename WT, int EPI, int NORM, int OPW, int CH, int NW>
 __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* __restrict__ X, const float* __restrict__ gamma, float eps,
                                                               const WT* __restrict__ W, const WT* __restrict__ W2,
                                                               const float* __restrict__ bias, const float* __restrict__ R,
-                                                              int n_out, int k, float* __restrict__ Y)
+                                                              int n_out, int k, float* __restrict__ Y, const float* __restrict__ beta)
 {
     constexpr int NM = EPI == LE_SWIGLU ? 2 : 1;
     constexpr int THREADS = 64 * NW;
@@ -285,7 +346,45 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
             }
         }
     }
-    if (NORM) {
+    if (NORM == NK_LN) {  // mean (the zero padding adds nothing), then the variance around it over the row's own chunks
+        float s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += x[c].v[e];
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+        __syncthreads();
+        float total = 0.0f;
+#pragma unroll
+        for (int wv = 0; wv < NW; ++wv) total += red[wv];
+        const float mean = total / (float)k;
+        __syncthreads();
+        float v = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+            if (tid + c * THREADS < k8) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v = fmaf(x[c].v[e] - mean, x[c].v[e] - mean, v);
+            }
+        v = wave_sum(v);
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        float vt = 0.0f;
+#pragma unroll
+        for (int wv = 0; wv < NW; ++wv) vt += red[wv];
+        const float inv = 1.0f / sqrtf(vt / (float)k + eps);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int i = tid + c * THREADS;
+            if (i < k8) {
+                const F8 g = load8(gamma, i), be = load8(beta, i);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[c].v[e] = (x[c].v[e] - mean) * inv * g.v[e] + be.v[e];
+            }
+        }
+    }
+    if (NORM == NK_RMS) {
         float s = 0.0f;
 #pragma unroll
         for (int c = 0; c < CH; ++c)
@@ -342,6 +441,7 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
             for (int wv = 0; wv < NW; ++wv) up += part[wv][OPW + tid];
             v = (v / (1.0f + expf(-v))) * up;
         }
+        if (EPI == LE_GELU_TANH) v = gelu_tanh(v);
         if (EPI == LE_RESIDUAL) v += R[n];
         Y[n] = v;
     }
@@ -1166,7 +1266,7 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
     // Staging the row in LDS pays when it also has to be normalised (otherwise every wave redoes the statistics); plain
     // projections keep the one-wave-per-column kernel, whose 4x larger grid hides latency better.
     // One row, K = 2048 / 4096 / 8192: the weight-streaming kernel.
-    if (a.rows == 1 && a.seg_q == 0 && llm_gemv_streams(a.k, a.W, a.W2)) {
+    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && llm_gemv_streams(a.k, a.W, a.W2)) {
         constexpr bool BF = sizeof(WT) == 2;
         const int ch = a.k / 512;
         const int nm = a.swiglu ? 2 : 1, lpp = BF ? 1 : 2;
@@ -1237,7 +1337,26 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
 #undef KJ_ST_ATT2
         return hipGetLastError();
     }
-    if (a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048 && (g_llm_gemv_variant == 0 || g_llm_gemv_variant >= 3)) {
+    // LayerNorm (GPT-2) takes three kernels, each instantiated for the one combination it serves: one row, k <= 2048, the
+    // c_fc stage (LayerNorm + GELU) -> split-K with two columns per workgroup; one row, the Q|K|V stage (LayerNorm, cache
+    // segments) -> the LDS-staged kernel; everything else -> the multi-row kernel below.
+    if (a.layernorm && a.rows == 1 && a.gelu_tanh && a.seg_q == 0 && a.k <= 2048) {
+        hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, LE_GELU_TANH, NK_LN, 2, 1, 4>), dim3((unsigned)((a.n_out + 1) / 2)), dim3(256), 0,
+                           stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta);
+        return hipGetLastError();
+    }
+    if (a.layernorm && a.rows == 1 && !a.gelu_tanh && a.k <= G1_MAX_K) {
+        const size_t lds = (size_t)a.k * sizeof(float);
+        auto kern = llm_gemv1_kernel<WT, LE_NONE, NK_LN>;
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW))), dim3(256), lds, stream, a.X, a.gamma, a.eps, W,
+                           W2, a.bias, a.R, a.n_out, a.k, a.seg_q, a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);
+        return hipGetLastError();
+    }
+    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048 && (g_llm_gemv_variant == 0 || g_llm_gemv_variant >= 3)) {
         // Long rows (down-proj: k = 8192 .. 14336) are spread over 16 waves per workgroup: a quarter of the loads per lane,
         // four times the waves in flight, at the same two columns per workgroup.
         const bool wide = a.k >= 8192 && g_llm_gemv_variant != 7;
@@ -1257,7 +1376,7 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
         const dim3 gridk((unsigned)((a.n_out + opw - 1) / opw));
 #define KJ_SK4(EPI, NORM, OPW, CH, NW)                                                                                                \
     hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, EPI, NORM, OPW, CH, NW>), gridk, dim3(64 * NW), 0, stream, a.X, a.gamma, a.eps, W, \
-                       W2, a.bias, a.R, a.n_out, a.k, a.Y0)
+                       W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta)
 #define KJ_SK3(EPI, NORM, OPW, CH)                                                                                                    \
     do {                                                                                                                              \
         if (wide) KJ_SK4(EPI, NORM, (OPW > 2 ? 2 : OPW), (CH > 2 ? 2 : CH), 16);                                                      \
@@ -1293,7 +1412,7 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
 #undef KJ_SK3
         return hipGetLastError();
     }
-    if (a.rows == 1 && norm && a.k <= G1_MAX_K && g_llm_gemv_variant != 1) {
+    if (!a.layernorm && a.rows == 1 && norm && a.k <= G1_MAX_K && g_llm_gemv_variant != 1) {
         const dim3 grid1((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW)));
         const size_t lds = (size_t)a.k * sizeof(float);
 #define KJ_LLM1(EPI, NORM)                                                                                                            \
@@ -1305,7 +1424,7 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
             if (e != hipSuccess) return e;                                                                                            \
         }                                                                                                                             \
         hipLaunchKernelGGL(kern, grid1, dim3(256), lds, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.seg_q,       \
-                           a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr);                                            \
+                           a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);                                    \
     } while (0)
         if (a.swiglu) {
             if (norm) KJ_LLM1(LE_SWIGLU, true);
@@ -1324,8 +1443,11 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
 #define KJ_LLM(EPI, NORM)                                                                                                       \
     hipLaunchKernelGGL((llm_gemv_kernel<WT, EPI, NORM>), grid, dim3(256), 0, stream, a.X, a.ldx, a.rows, a.gamma, a.eps, W, W2,  \
                        a.bias, a.R, a.ldr, a.n_out, a.k, a.seg_q, a.seg_kv, a.Y0, a.ldy0, a.Y1, a.Y2, a.ldy12, a.row_off,       \
-                       a.row_off_ptr)
-    if (a.swiglu) {
+                       a.row_off_ptr, a.beta)
+    if (a.layernorm) {  // the GPT-2 stages that reach here: 2-8 rows, or a projection too wide for the kernels above
+        if (a.gelu_tanh) KJ_LLM(LE_GELU_TANH, NK_LN);
+        else KJ_LLM(LE_NONE, NK_LN);
+    } else if (a.swiglu) {
         if (norm) KJ_LLM(LE_SWIGLU, true);
         else KJ_LLM(LE_SWIGLU, false);
     } else if (a.R) {
@@ -1730,6 +1852,9 @@ hipError_t launch_llm_gemv(const LlmGemvArgs& a, hipStream_t stream)
 {
     if (a.att_splits > 0 && (a.rows != 1 || a.seg_q != 0)) return hipErrorInvalidValue;
     if (a.norm_out && !(a.rows == 1 && a.seg_q == 0 && a.gamma && llm_gemv_streams(a.k, a.W, a.W2))) return hipErrorInvalidValue;
+    // LayerNorm needs gamma and beta and takes no residual / SwiGLU epilogue; GELU-tanh comes only after LayerNorm (GPT-2's c_fc)
+    if (a.layernorm && (!a.gamma || !a.beta || a.R || a.swiglu || a.att_splits > 0 || a.norm_out)) return hipErrorInvalidValue;
+    if (a.gelu_tanh && (!a.layernorm || a.seg_q != 0)) return hipErrorInvalidValue;
     if (a.rows <= 0 || a.n_out <= 0) return hipSuccess;
     if (a.rows > LLM_MAX_ROWS || (a.k & 7) || (a.ldx & 3) || (reinterpret_cast<uintptr_t>(a.X) & 15) ||
         (reinterpret_cast<uintptr_t>(a.W) & 15))
@@ -1789,6 +1914,71 @@ hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, c
     else
         hipLaunchKernelGGL(llm_embed_kernel<float>, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,
                            static_cast<const float*>(table), out);
+    return hipGetLastError();
+}
+
+namespace {
+
+// GPT-2 embeddings (gpt2/cpu_decoder.rs:371-376): row s = wte[ids[s]] + wpe[p + s], p = *pos_ptr or pos (an id >= vocab
+// or a position >= max_pos leaves that part zero).
+template <typename WT>
+__global__ __launch_bounds__(256) void llm_embed_pos_kernel(const uint32_t* __restrict__ ids, int hidden, int vocab,
+                                                            const WT* __restrict__ table, const WT* __restrict__ pos_table, int max_pos,
+                                                            int pos, const int* __restrict__ pos_ptr, float* __restrict__ out)
+{
+    const int s = blockIdx.x;
+    const uint32_t id = ids[s];
+    const int p = (pos_ptr ? *pos_ptr : pos) + s;
+    for (int i = threadIdx.x; i < hidden / 8; i += 256) {
+        F8 v, w;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v.v[c] = w.v[c] = 0.0f;
+        if (id < (uint32_t)vocab) v = load8(table + (int64_t)id * hidden, i);
+        if (p >= 0 && p < max_pos) w = load8(pos_table + (int64_t)p * hidden, i);
+        f32x4 a, b;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            a[c] = v.v[c] + w.v[c];
+            b[c] = v.v[4 + c] + w.v[4 + c];
+        }
+        *reinterpret_cast<f32x4*>(out + (int64_t)s * hidden + i * 8) = a;
+        *reinterpret_cast<f32x4*>(out + (int64_t)s * hidden + i * 8 + 4) = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void gelu_tanh_kernel(float* __restrict__ x, size_t n4)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        f32x4 v = reinterpret_cast<f32x4*>(x)[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = gelu_tanh(v[c]);
+        reinterpret_cast<f32x4*>(x)[i] = v;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_llm_embed_pos(const uint32_t* ids, int n, int hidden, int vocab, const void* table, const void* pos_table, int max_pos,
+                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream)
+{
+    if (hidden & 7) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    if (bf16)
+        hipLaunchKernelGGL(llm_embed_pos_kernel<uint16_t>, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,
+                           static_cast<const uint16_t*>(table), static_cast<const uint16_t*>(pos_table), max_pos, pos, pos_ptr, out);
+    else
+        hipLaunchKernelGGL(llm_embed_pos_kernel<float>, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,
+                           static_cast<const float*>(table), static_cast<const float*>(pos_table), max_pos, pos, pos_ptr, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream)
+{
+    if (n % 4 || (reinterpret_cast<uintptr_t>(x) & 15)) return hipErrorInvalidValue;
+    const size_t n4 = n / 4;
+    if (n4 == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((n4 + 255) / 256, 8192);
+    hipLaunchKernelGGL(gelu_tanh_kernel, dim3(grid), dim3(256), 0, stream, x, n4);
     return hipGetLastError();
 }
 

@@ -23,7 +23,7 @@ class HipDecoder:
         self.hidden, self.layers, self.vocab, self.context, self.bf16, self.weight_bytes = a.value, b.value, c.value, d.value, bool(e.value), wb.value
         cfg = json.loads(self.config_json())  # config.json, or the config synthesized from a GGUF file's metadata
         self.config = cfg
-        heads = cfg["num_attention_heads"]
+        heads = cfg["num_attention_heads"] if "num_attention_heads" in cfg else cfg["n_head"]  # (GPT-2's field name)
         self.kv_heads = cfg.get("num_key_value_heads", heads)
         self.head_dim = cfg.get("head_dim", self.hidden // heads)
 

@@ -1,0 +1,77 @@
+"""Raw text completion over the kjarni_generator_* C ABI (the reference's Rust Generator,
+crates/kjarni/src/generator/*): no chat template, the output as generated."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, List, Optional
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import KjarniDevice, check_error, lib
+from .chat import GenerationConfig, ResolvedGeneration, _gen, _resolved, _stream_cb, _take_string
+
+
+class Generator:
+    def __init__(self, model: str, model_path: Optional[str] = None, cache_dir: Optional[str] = None, device: str = "cpu",
+                 quiet: bool = True):
+        cfg = lib().kjarni_generator_config_default()
+        cfg.device = KjarniDevice.GPU if device == "gpu" else KjarniDevice.CPU
+        self._keep = [s.encode("utf-8") if s is not None else None for s in (cache_dir, model, model_path)]
+        cfg.cache_dir, cfg.model_name, cfg.model_path = self._keep
+        cfg.quiet = int(quiet)
+        self._handle = C.c_void_p()
+        check_error(lib().kjarni_generator_new(C.byref(cfg), C.byref(self._handle)))
+
+    def close(self):
+        if getattr(self, "_handle", None) and self._handle.value:
+            lib().kjarni_generator_free(self._handle)
+            self._handle = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def model_name(self) -> str:
+        need = lib().kjarni_generator_model_name(self._handle, None, 0)
+        buf = C.create_string_buffer(need + 1)
+        lib().kjarni_generator_model_name(self._handle, buf, need + 1)
+        return buf.value.decode("utf-8")
+
+    @property
+    def context_size(self) -> int:
+        return int(lib().kjarni_generator_context_size(self._handle))
+
+    @property
+    def vocab_size(self) -> int:
+        return int(lib().kjarni_generator_vocab_size(self._handle))
+
+    def generate(self, prompt: str, config: Optional[GenerationConfig] = None) -> str:
+        out = C.c_void_p()
+        check_error(lib().kjarni_generator_generate(self._handle, prompt.encode("utf-8"), _gen(config), C.byref(out)))
+        return _take_string(out)
+
+    def stream(self, prompt: str, on_token: Callable[[str], bool], config: Optional[GenerationConfig] = None, cancel=None):
+        cb = _stream_cb(on_token)
+        check_error(lib().kjarni_generator_stream(self._handle, prompt.encode("utf-8"), _gen(config), cb, None,
+                                                  cancel._handle if cancel is not None else None))
+
+    # ---- kjarni_hip.h hooks on a live handle ----
+    def resolve(self, config: Optional[GenerationConfig] = None) -> ResolvedGeneration:
+        r = _ffi.KjarniResolvedGeneration()
+        check_error(lib().kjarni_hip_generator_resolve(self._handle, _gen(config), C.byref(r)))
+        return _resolved(r)
+
+    def encode(self, prompt: str, config: Optional[GenerationConfig] = None) -> List[int]:
+        n = C.c_size_t()
+        check_error(lib().kjarni_hip_generator_encode(self._handle, prompt.encode("utf-8"), _gen(config), None, 0, C.byref(n)))
+        ids = np.zeros(max(n.value, 1), np.uint32)
+        check_error(lib().kjarni_hip_generator_encode(self._handle, prompt.encode("utf-8"), _gen(config),
+                                                      ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, C.byref(n)))
+        return ids[: n.value].tolist()
+
+    def seed(self, seed: int):
+        lib().kjarni_hip_generator_seed(self._handle, seed)
+
+    def set_device_sampling(self, on: bool):
+        """Sampling / logits processors with the O(vocab) work on the device (default) or on a host copy of the logits."""
+        lib().kjarni_hip_generator_set_device_sampling(self._handle, 1 if on else 0)

@@ -69,7 +69,7 @@ def timed(fn, sync, steps, warmup):
 
 
 def main():
-    which = set(sys.argv[1:]) or {"rerank", "scan", "ragged", "host", "sweep", "strings", "latency", "families", "indexer", "search", "whisper", "llm", "chat"}  # "llm8b" only on request (writes 16 GB)
+    which = set(sys.argv[1:]) or {"rerank", "scan", "ragged", "host", "sweep", "strings", "latency", "families", "indexer", "search", "whisper", "llm", "chat", "gpt2"}  # "llm8b" only on request (writes 16 GB)
     import numpy as np
     import torch
 
@@ -497,6 +497,48 @@ def main():
               "value": rows["lock_step_8"]["x_real_time"], "unit": "x real time", "n_gpus": 1, "dtype": "f32", "data": "synthetic",
               "config": {"workload": "whisper-base shape, random init, 480 s synthetic audio, 449 generated tokens per chunk"},
               "runs": rows, "same_text": rows["sequential"]["chars"] == rows["lock_step_8"]["chars"]})
+
+    if "gpt2" in which:
+        # gpt2-small shape (768 hidden, 12 layers, 12 heads, 3 072 MLP, vocab 50 257, n_ctx 1 024), random weights: bf16 stored,
+        # then the same weights as f32; 128-token prompt, 256 greedy tokens (no eos: every token is generated)
+        from tests import gpt2_fixture
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        prompt = np.random.default_rng(0).integers(0, 50257, 128).tolist()
+        n_new = 256
+        bf16_row = None
+        for weights in ("auto", "f32"):
+            dec = kjarni_amd.HipDecoder(gd, weights=weights)
+            dec.generate(prompt, 8)                                           # warm-up (graph capture)
+            t0 = time.perf_counter()
+            dec.reset()
+            dec.forward(prompt, fetch=False)
+            t_prefill = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            out = dec.generate(prompt, n_new)
+            t_dec = time.perf_counter() - t0 - t_prefill
+            kv_bytes = 2 * 12 * 768 * 4 * (128 + n_new / 2)                   # average cache read per step
+            per_tok = dec.weight_bytes + kv_bytes
+            row = {"metric": f"tokens/sec greedy decode, gpt2-small shape, {'bf16' if dec.bf16 else 'f32'} weights, batch 1",
+                   "value": round(len(out) / t_dec, 1), "unit": "tokens/s", "n_gpus": 1,
+                   "dtype": f"{'bf16' if dec.bf16 else 'f32'} weights, f32 activations/accumulate/KV", "data": "synthetic",
+                   "config": {"workload": "gpt2-small geometry (768 hidden, 12 layers, 12 heads, 3 072 MLP, vocab 50 257, n_ctx 1 024), "
+                                          f"random init, 128-token prompt, {len(out)} generated tokens"},
+                   "ms_prefill_128": round(t_prefill * 1e3, 2), "ms_per_token": round(t_dec * 1e3 / len(out), 4),
+                   "weight_bytes": dec.weight_bytes,
+                   "roofline": {"kernel": "llm_gemv1 / llm_gemv_splitk (LayerNorm, GELU-tanh, residual) + decode_attention_partial",
+                                "bound": "hbm", "achieved": round(per_tok * len(out) / t_dec / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                "frac": round(per_tok * len(out) / t_dec / 1e9 / PEAK_HBM_GBS, 4), "traffic": None,
+                                "algorithmic_bytes_per_token": int(per_tok)},
+                   "note": "the bf16 weights (about 249 MB) are close to the 256 MiB Infinity Cache, so part of the weight stream "
+                           "may be served on-die and the HBM fraction overstates what HBM delivered"}
+            if bf16_row is not None:
+                row["bf16_same_run"] = {"tokens_per_s": bf16_row["value"], "ms_per_token": bf16_row["ms_per_token"]}
+            else:
+                bf16_row = row
+            emit(row)
+            del dec
 
     if "llm" in which:
         d = os.path.join(tmp, "llama-1b")
