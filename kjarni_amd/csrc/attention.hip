@@ -29,6 +29,7 @@
 #include <atomic>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "kernels.h"
 #include "tuning.h"
 
@@ -804,15 +805,10 @@ hipError_t launch_d(const float* qkv, const uint32_t* mask, int64_t batch, int s
                     float mask_value, float* ctx, hipStream_t stream, const int32_t* cu)
 {
     using SM = AttnSmem<D>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (SM::BYTES > 64 * 1024 && !attr_set[dev & 63]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<D>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
+    hipError_t e = hipSuccess;
+    if (SM::BYTES > 64 * 1024) {
+        e = allow_dynamic_lds(&attention_kernel<D>, SM::BYTES);
         if (e != hipSuccess) return e;
-        attr_set[dev & 63] = true;
     }
     const float scale = 1.0f / sqrtf((float)D);  // encoder_self_attention.rs:43
     if (seq <= KCHUNK && batch * heads <= kSplitMaxItems && !tune::no_split_attention()) {
@@ -830,20 +826,11 @@ hipError_t launch_d(const float* qkv, const uint32_t* mask, int64_t batch, int s
         int64_t max_blocks = 256 * kResident;
         if (tune::attention_two_workgroups_per_cu()) max_blocks = 256 * 2;
         const unsigned grid = (unsigned)(n_items < max_blocks ? n_items : max_blocks);
-        if (SM::BYTES > 64 * 1024) {  // the dynamic-LDS opt-in, once per device and kernel
-            static bool pipe_attr_set[64] = {};
-            if (!pipe_attr_set[dev & 63]) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_pipe_kernel<D, 0, 1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_pipe_kernel<D, 0, 0>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_pipe_kernel<D, 0, 2>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, SM::BYTES);
-                if (e != hipSuccess) return e;
-                pipe_attr_set[dev & 63] = true;
-            }
+        if (SM::BYTES > 64 * 1024) {  // the dynamic-LDS opt-in of the three kernels below
+            e = allow_dynamic_lds(&attention_pipe_kernel<D, 0, 1>, SM::BYTES);
+            if (e == hipSuccess) e = allow_dynamic_lds(&attention_pipe_kernel<D, 0, 0>, SM::BYTES);
+            if (e == hipSuccess) e = allow_dynamic_lds(&attention_pipe_kernel<D, 0, 2>, SM::BYTES);
+            if (e != hipSuccess) return e;
         }
 #ifdef KJARNI_TUNING
         switch (D == 32 ? tune::attention_knockout() + 10 : 0) {  // (the knock-outs are measured on the headline shape)

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "kernels.h"
 #include "tuning.h"
 
@@ -1741,8 +1742,7 @@ hipError_t filter_launch(const FilterPlan& p, const float* queries, int m, const
     do {                                                                                                                         \
         auto kern = cosine_filter_bf16_kernel<NK_, KIND, PARTS_, WAVES_>;                                                        \
         if (p.lds > 48 * 1024) {                                                                                                 \
-            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                      (int)p.lds);                                                               \
+            const hipError_t ea = allow_dynamic_lds(kern, p.lds);                                                                \
             if (ea != hipSuccess) return ea;                                                                                     \
         }                                                                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES_), p.lds, stream, queries, m, corpus, n_docs, qn2, thr_score, thr_idx, thr_k, \

@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 #include "tuning.h"
@@ -941,20 +942,13 @@ hipError_t launch_ln_tiled(const float* A, int64_t lda, const float* W, const fl
                            hipStream_t stream)
 {
     using T = LnTile<NT>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (T::LDS_BYTES > 64 * 1024 && !attr_set[dev & 63]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_mfma_ln<NT, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
+    if (T::LDS_BYTES > 64 * 1024) {
+        hipError_t e = allow_dynamic_lds(&gemm_nt_f32_mfma_ln<NT, true>, T::LDS_BYTES);
         if (e != hipSuccess) return e;
 #ifdef KJARNI_TUNING
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_mfma_ln<NT, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
+        e = allow_dynamic_lds(&gemm_nt_f32_mfma_ln<NT, false>, T::LDS_BYTES);
         if (e != hipSuccess) return e;
 #endif
-        attr_set[dev & 63] = true;
     }
     const int64_t total = (M + T::BM - 1) / T::BM;
     // (a grid of the 512 resident workgroups measured +0.6 % on the K = 384 shape and -0.6 % on K = 1536: one workgroup per tile)
@@ -1171,18 +1165,9 @@ hipError_t launch_tiled_as(const float* A, int64_t lda, const float* W, const fl
                            int64_t ldr, float* Y, int64_t ldy, int64_t M, int N, int K, hipStream_t stream)
 {
     using T = Tile<BKT>;
-    if (T::LDS_BYTES > 64 * 1024) {
-        // > 64 KiB of dynamic LDS needs the opt-in once per device.
-        static bool attr_set[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+    if (T::LDS_BYTES > 64 * 1024) {  // > 64 KiB of dynamic LDS needs the opt-in
+        const hipError_t e = allow_dynamic_lds(&gemm_nt_f32_mfma<EPI, BKT, DIAG, OUT_POLICY>, T::LDS_BYTES);
         if (e != hipSuccess) return e;
-        if (!attr_set[dev & 63]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_mfma<EPI, BKT, DIAG, OUT_POLICY>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            attr_set[dev & 63] = true;
-        }
     }
     const int n_tiles = N / BN;
     const int64_t m_tiles = (M + BM - 1) / BM;
@@ -1193,16 +1178,8 @@ hipError_t launch_tiled_as(const float* A, int64_t lda, const float* W, const fl
         const int nk = K / 32;
         if (R == nullptr && nk >= 6 && (nk & 1) == 0 && nk <= kStreamMaxKSteps && (int64_t)BM * ldy * 4 < ((int64_t)1 << 31) && total >= 4 * (int64_t)256 * T::WAVES_PER_SIMD &&
             !tune::no_k_stream_tiles()) {
-            static bool attr_set[64] = {};
-            int dev = 0;
-            hipError_t e = hipGetDevice(&dev);
+            const hipError_t e = allow_dynamic_lds(&gemm_nt_f32_stream<EPI, DIAG, OUT_POLICY>, T::LDS_BYTES);
             if (e != hipSuccess) return e;
-            if (!attr_set[dev & 63]) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_stream<EPI, DIAG, OUT_POLICY>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
-                if (e != hipSuccess) return e;
-                attr_set[dev & 63] = true;
-            }
             hipLaunchKernelGGL((gemm_nt_f32_stream<EPI, DIAG, OUT_POLICY>), dim3((unsigned)((int64_t)256 * T::WAVES_PER_SIMD)), dim3(256),
                                T::LDS_BYTES, stream, A, lda, W, bias, Y, ldy, M, K, n_tiles, total);
             return hipGetLastError();

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 #include "tuning.h"
@@ -354,16 +355,8 @@ hipError_t flex_launch_one(const float* A, int64_t lda, const float* W, int64_t 
 {
     using T = Flex<RA, CB>;
     static_assert(T::LDS_FLOATS * 4 <= kFlexLdsBytes, "tile does not fit the per-launch LDS claim");
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = allow_dynamic_lds(&gemm_nt_f32_flex<RA, CB, VS, DIAG>, kFlexLdsBytes);
     if (e != hipSuccess) return e;
-    if (!attr_set[dev & 63]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_f32_flex<RA, CB, VS, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kFlexLdsBytes);
-        if (e != hipSuccess) return e;
-        attr_set[dev & 63] = true;
-    }
     const int n_tiles = (N + T::BN - 1) / T::BN;
     const int64_t total = (int64_t)((M + T::BM - 1) / T::BM) * n_tiles * ksplit;
     if (total > 0x7fffffff) return hipErrorInvalidValue;

@@ -731,16 +731,11 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_layer_norm(int32_t device, co
 }
 
 #ifdef KJARNI_TUNING
-#include "whisper_kernels.h"
 // Kernel A/B switches (tuning.h): exported by the tuning build only (kjarni_amd/lib/libkjarni_ffi_tuning.so, tools/).
 namespace kjarni { namespace tune { std::atomic<int> g_gemm{0}, g_attention{0}, g_cosine{0}; } }
 KJARNI_EXPORT void kjarni_hip_set_gemm_variant(int32_t variant) { kjarni::tune::g_gemm = variant; }
 KJARNI_EXPORT void kjarni_hip_set_attention_variant(int32_t variant) { kjarni::tune::g_attention = variant; }
 KJARNI_EXPORT void kjarni_hip_set_cosine_variant(int32_t variant) { kjarni::tune::g_cosine = variant; }
-KJARNI_EXPORT int32_t kjarni_hip_attention_stamps(uint64_t* out16, int32_t reset)
-{
-    return out16 && kjarni::attention_stamps(reinterpret_cast<unsigned long long*>(out16), reset) == hipSuccess ? 0 : 5;
-}
 #endif
 
 // ---- cosine scan ----------------------------------------------------------------

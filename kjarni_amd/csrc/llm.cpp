@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -341,9 +340,6 @@ void LlmModel::finish_load()
     // key ranges per head: up to 512 keys each (128 of them are one register-held pass of the attention kernel); few enough
     // that the output projection can merge the slabs itself
     splits_ = std::max(1, std::min(64, (cache_cap_ + 511) / 512));
-#ifdef KJARNI_TUNING
-    if (const char* v = std::getenv("KJARNI_HIP_LLM_SPLITS")) splits_ = std::max(1, std::atoi(v));  // measurements
-#endif
     while ((cache_cap_ + splits_ - 1) / splits_ > 512) ++splits_;
     h_ = dalloc(8 * (size_t)H);
     q_ = dalloc(8 * (size_t)H);
@@ -456,11 +452,7 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
         return;
     }
     // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
-    bool embed_in_qkv = n == 1 && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
-#ifdef KJARNI_TUNING
-    static const bool no_fold = std::getenv("KJARNI_HIP_LLM_NO_FOLD") != nullptr;  // measurements: the embedding gather as its own launch
-    if (no_fold) embed_in_qkv = false;
-#endif
+    const bool embed_in_qkv = n == 1 && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
     if (!embed_in_qkv) hip_check(launch_llm_embed(ids_dev, n, H, c.vocab, embed_, bf16_ ? 1 : 0, h_, s), "embed");
     bool first_layer = true;
     for (const Layer& L : layers_) {
@@ -489,15 +481,6 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
             o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
         }
         hip_check(launch_llm_gemv(o, s), "o proj");
-#ifdef KJARNI_TUNING
-        static const bool touch = std::getenv("KJARNI_HIP_LLM_TOUCH") != nullptr;  // measurements: weights already in the memory-side cache
-        if (touch && n == 1) {
-            const size_t wb = bf16_ ? 2 : 4;
-            hip_check(launch_touch(L.gate, (size_t)I * H * wb, reinterpret_cast<unsigned*>(att_scratch_), s), "touch");
-            hip_check(launch_touch(L.up, (size_t)I * H * wb, reinterpret_cast<unsigned*>(att_scratch_), s), "touch");
-            hip_check(launch_touch(L.down, (size_t)I * H * wb, reinterpret_cast<unsigned*>(att_scratch_), s), "touch");
-        }
-#endif
         LlmGemvArgs g;  // RMSNorm + SwiGLU (swiglu.rs:32-57)
         g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.W2 = L.up; g.bf16 = bf16_; g.swiglu = 1;
         g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
@@ -637,14 +620,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
     const int wb = bf16_ ? 1 : 0;
     constexpr int kChunk = 2048;
-#ifdef KJARNI_TUNING
-    static const int kTileRows = [] {
-        const char* v = std::getenv("KJARNI_HIP_LLM_TILE_ROWS");  // measurements
-        return v ? std::atoi(v) : 512;
-    }();
-#else
     constexpr int kTileRows = 512;  // rows from which a projection may take the encoder's 128 x 128-tile f32 GEMM (if its tiles fill the chip)
-#endif
     if (!ph_) {
         prefill_cap_ = kChunk;
         const size_t P = (size_t)prefill_cap_;
@@ -691,15 +667,10 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
                 wbu = 0;
                 bf = false;
             }
-#ifdef KJARNI_TUNING
-            static const int min_tiles_env = [] { const char* v = std::getenv("KJARNI_HIP_LLM_MIN_TILES"); return v ? std::atoi(v) : 0; }();
-            const int min_tiles = min_tiles_env > 0 ? min_tiles_env : 208;
-#else
             // measured on the 1B shape: 192 tiles (1 536 rows x 2 048 columns) are faster on the 64 x 64 kernel, 224 on the tiles -- with
             // f32 weights (both kernels on the f32 matrix cores) and again with bf16 weights (both on the bf16 matrix cores: 768 /
             // 1 024 tokens 8.1 / 9.8 ms at 208 against 9.9 / 11.2 at 96 and 8.8 / 11.2 with no tiles at all)
             constexpr int min_tiles = 208;
-#endif
             const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
             if (!tiles) {
                 hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
@@ -709,12 +680,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
             ++tile_gemm_calls_;
             // bf16 weights: the bf16 matrix cores take them as they are, the f32 activations as three exact bf16 pieces (the same
             // products as the f32 GEMM on a widened copy: gemm_split.hip) -- 2 048-token prompt 33.8 -> 18.1 ms, no 100 MB copy
-#ifdef KJARNI_TUNING
-            static const bool widen = [] { const char* v = std::getenv("KJARNI_HIP_LLM_WIDEN"); return v && v[0] == '1'; }();
-#else
-            constexpr bool widen = false;
-#endif
-            if (bf && !widen && K % 64 == 0) {
+            if (bf && K % 64 == 0) {
                 if (gate)
                     hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
                 else
@@ -794,14 +760,7 @@ void LlmModel::forward(const uint32_t* ids, int n)
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (n < 1) throw std::runtime_error("forward needs at least one token");
     if (cache_len_ + n > cache_cap_) throw std::runtime_error("context is full");
-#ifdef KJARNI_TUNING
-    static const int kMinGemmRows = [] {
-        const char* v = std::getenv("KJARNI_HIP_LLM_PREFILL_MIN");  // measurements: rows from which the matrix-core route is used
-        return v ? std::atoi(v) : 24;
-    }();
-#else
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
-#endif
     const int kvd = cfg_.kv_heads * cfg_.head_dim;
     if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
         prefill_rows(ids, n);
@@ -1091,15 +1050,6 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         size_t steps = std::min(burst, max_new_tokens - out.size());
         steps = std::min(steps, (size_t)cache_cap_ - (size_t)cache_len_);
         if (steps == 0) break;
-#ifdef KJARNI_TUNING
-        static const bool eager = std::getenv("KJARNI_HIP_LLM_EAGER") != nullptr;  // measurements: the same launches, not replayed
-        if (eager) {
-            for (size_t i = 0; i < steps; ++i) {
-                pass(reinterpret_cast<const uint32_t*>(token_), 1, true);
-                enqueue_argmax(true);
-            }
-        } else
-#endif
         for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
         hip_check(hipMemcpyAsync(hist.data() + produced, hist_ + produced, steps * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
         hip_check(hipStreamSynchronize(stream_), "sync");

@@ -40,9 +40,6 @@ hipError_t launch_llm_gemv(const LlmGemvArgs& args, hipStream_t stream);
 bool llm_gemv_merges_attention(int k, int splits, int head_dim);
 // Does a one-row projection with these sizes take the weight-streaming kernel (which honours norm_out)?
 bool llm_gemv_streams(int k, const void* W, const void* W2);
-#ifdef KJARNI_TUNING
-void set_llm_gemv_variant(int variant);  // 0 = default (single-row kernel for rows == 1), 1 = always the multi-row kernel
-#endif
 
 // One new token: RMSNorm + Q|K|V projection + RoPE in one launch; Q -> Q[n_heads*head_dim], K / V -> row `pos`
 // (or *pos_ptr) of the caches [*, n_kv_heads*head_dim].  W is the fused [Q;K;V] matrix.
@@ -77,9 +74,6 @@ hipError_t launch_swiglu_mul(float* gate, const float* up, size_t n, hipStream_t
 hipError_t launch_rope(float* x, int64_t ldx, int rows, int n_heads, int head_dim, const float* cos_t, const float* sin_t, int pos,
                        const int* pos_ptr, int at_cache_row, hipStream_t stream);
 hipError_t launch_rmsnorm(const float* x, const float* gamma, float eps, int rows, int hidden, float* out, hipStream_t stream);
-#ifdef KJARNI_TUNING
-hipError_t launch_touch(const void* p, size_t bytes, unsigned* sink, hipStream_t stream);  // measurements: warm the memory-side cache
-#endif
 hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, const void* table, int bf16, float* out,
                             hipStream_t stream);
 // GPT-2: out[s] = table[ids[s]] + pos_table[p + s] for n rows, p = *pos_ptr when pos_ptr is non-null (graph replay), else pos;

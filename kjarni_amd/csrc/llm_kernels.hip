@@ -9,9 +9,9 @@
 //             cpu/feedforward/swiglu.rs:32-57
 //   greedy    common/sampling.rs:83-88
 #include <algorithm>
-#include <atomic>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "llm_kernels.h"
 #include "kernels.h"
 
@@ -20,12 +20,6 @@ namespace kjarni {
 namespace {
 
 constexpr int LLM_MAX_ROWS = 8;
-#ifdef KJARNI_TUNING
-std::atomic<int> g_llm_gemv_variant{0};  // 1 = always the multi-row kernel; 3..6 columns per workgroup; 7 = narrow chunks -- tuning build only
-#else
-constexpr int g_llm_gemv_variant = 0;
-#endif
-
 
 struct F8 {
     float v[8];
@@ -301,15 +295,18 @@ __global__ __launch_bounds__(256) void llm_gemv1_kernel(const float* __restrict_
     }
 }
 
-// Single-row GEMV with the K dimension split over the four waves of a workgroup.  A workgroup owns OPW output
+// Single-row GEMV with the K dimension split over the four waves of a workgroup.  A workgroup owns SK_OPW output
 // columns; lane t of the block keeps chunks t, t+256, ... of the input row in registers (normalised in place when
 // NORM — the sum of squares is reduced once through LDS), issues every weight load of its slice before the first
-// FMA (OPW x chunks x 16 bytes per lane in flight) and the four per-wave partial sums meet in LDS.  Compared with
+// FMA (SK_OPW x chunks x 16 bytes per lane in flight) and the four per-wave partial sums meet in LDS.  Compared with
 // one wave per column this puts 4x more workgroups on the chip for the narrow projections (o, down) and reads the
-// input row once per OPW columns instead of once per column.
+// input row once per SK_OPW columns instead of once per column.
 constexpr int SK_MAX_CHUNKS = 8;  // k <= 8 * 256 * 8 = 16384 with 4 waves; long rows (k >= 8192) use 16 waves per workgroup
+// Two columns per workgroup measured best on every projection of the 1B and 8B shapes (1, 4 and 8 were 2-18 % slower end
+// to end): the chip wants many small workgroups more than it wants deep per-lane load queues.
+constexpr int SK_OPW = 2;
 
-template <typename WT, int EPI, int NORM, int OPW, int CH, int NW>
+template <typename WT, int EPI, int NORM, int CH, int NW>
 __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* __restrict__ X, const float* __restrict__ gamma, float eps,
                                                               const WT* __restrict__ W, const WT* __restrict__ W2,
                                                               const float* __restrict__ bias, const float* __restrict__ R,
@@ -318,7 +315,7 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
     constexpr int NM = EPI == LE_SWIGLU ? 2 : 1;
     constexpr int THREADS = 64 * NW;
     __shared__ float red[NW];
-    __shared__ float part[NW][NM * OPW];
+    __shared__ float part[NW][NM * SK_OPW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k8 = k >> 3;
     F8 x[CH];
@@ -331,11 +328,11 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
             for (int e = 0; e < 8; ++e) x[c].v[e] = 0.0f;
         }
     }
-    const int64_t n0 = (int64_t)blockIdx.x * OPW;
+    const int64_t n0 = (int64_t)blockIdx.x * SK_OPW;
     // Weight loads do not depend on the statistics: issue them first so the reduction overlaps their latency.
-    F8 w[OPW][CH], u[EPI == LE_SWIGLU ? OPW : 1][CH];
+    F8 w[SK_OPW][CH], u[EPI == LE_SWIGLU ? SK_OPW : 1][CH];
 #pragma unroll
-    for (int o = 0; o < OPW; ++o) {
+    for (int o = 0; o < SK_OPW; ++o) {
         const int64_t n = n0 + o < n_out ? n0 + o : n_out - 1;
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -408,7 +405,7 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
         }
     }
 #pragma unroll
-    for (int o = 0; o < OPW; ++o) {
+    for (int o = 0; o < SK_OPW; ++o) {
         float acc = 0.0f, acc2 = 0.0f;
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -425,11 +422,11 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
         if (EPI == LE_SWIGLU) acc2 = wave_sum(acc2);
         if (lane == 0) {
             part[wave][o] = acc;
-            if (EPI == LE_SWIGLU) part[wave][OPW + o] = acc2;
+            if (EPI == LE_SWIGLU) part[wave][SK_OPW + o] = acc2;
         }
     }
     __syncthreads();
-    if (tid < OPW && n0 + tid < n_out) {
+    if (tid < SK_OPW && n0 + tid < n_out) {
         const int64_t n = n0 + tid;
         float v = 0.0f;
 #pragma unroll
@@ -438,7 +435,7 @@ __global__ __launch_bounds__(64 * NW) void llm_gemv_splitk_kernel(const float* _
         if (EPI == LE_SWIGLU) {
             float up = 0.0f;
 #pragma unroll
-            for (int wv = 0; wv < NW; ++wv) up += part[wv][OPW + tid];
+            for (int wv = 0; wv < NW; ++wv) up += part[wv][SK_OPW + tid];
             v = (v / (1.0f + expf(-v))) * up;
         }
         if (EPI == LE_GELU_TANH) v = gelu_tanh(v);
@@ -1012,17 +1009,16 @@ __global__ void argmax_finalize_kernel(unsigned long long* __restrict__ best, in
     }
 }
 
-// Prompt-row projections on the fp32 matrix cores: Y[M, N] = A[M, K] . W[N, K]^T (+ bias) (+ R), W in bf16 or f32 as
-// stored.  The encoder's 128 x 128 GEMM (gemm.hip) is sized for 10^5 rows; a prompt has 10^2..10^3, where one
+// Prompt-row projections on the fp32 matrix cores: Y[M, N] = A[M, K] . W[N, K]^T (+ bias) (+ R), W in f32 (bf16 weights
+// take the bf16 matrix cores: launch_prefill_tiles_bf16w).  The encoder's 128 x 128 GEMM (gemm.hip) is sized for 10^5 rows; a prompt has 10^2..10^3, where one
 // 128 x 128 x 2048 tile keeps a CU busy for ~110 us while most CUs have no tile at all.  So: 64 x 64 block tiles
 // (4 waves, one 32 x 32 MFMA tile each) -- 4x more workgroups of a quarter the work --, BK = 32, operands
-// double-buffered in LDS with the next tile's global loads in flight during the MFMAs, bf16 weights widened when they
-// are written to LDS (the same widening the GEMV kernels do).  v_mfma_f32_32x32x2_f32 is an exact k-ordered f32 fma
+// double-buffered in LDS with the next tile's global loads in flight during the MFMAs.  v_mfma_f32_32x32x2_f32 is an exact k-ordered f32 fma
 // chain, so the arithmetic class is the GEMV's; only the summation order differs.
 constexpr int PG_BM = 64, PG_BN = 64, PG_BK = 32, PG_STRIDE = PG_BK + 4;
 
-template <typename WT, bool RESIDUAL>
-__global__ __launch_bounds__(256) void prefill_gemm_kernel(const float* __restrict__ A, int64_t lda, const WT* __restrict__ W,
+template <bool RESIDUAL>
+__global__ __launch_bounds__(256) void prefill_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ W,
                                                            const float* __restrict__ bias, const float* R, int64_t ldr, float* Y,
                                                            int64_t ldy, int M, int N, int K, int m_tiles, int ksplit,
                                                            float* __restrict__ P)
@@ -1045,39 +1041,27 @@ __global__ __launch_bounds__(256) void prefill_gemm_kernel(const float* __restri
     const int n0 = (int)(bid / m_tiles) * PG_BN;
     const int k_len = K / ksplit, k_begin = ks * k_len;
 
-    // A: 64 x 32 floats = 512 float4, two per thread.  W: f32 the same; bf16: 64 x 32 halves = 256 x 16 bytes, one per thread.
+    // A: 64 x 32 floats = 512 float4, two per thread.  W the same.
     const int a_row = tid >> 3, a_c4 = tid & 7;
     const float* a_ptr[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) a_ptr[i] = A + (int64_t)min(m0 + a_row + 32 * i, M - 1) * lda + a_c4 * 4;
-    constexpr bool BF16 = sizeof(WT) == 2;
-    const int b_row = BF16 ? (tid >> 2) : a_row, b_c = BF16 ? (tid & 3) * 8 : a_c4 * 4;
-    const WT* b_ptr[2];
+    const int b_row = a_row, b_c = a_c4 * 4;
+    const float* b_ptr[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) b_ptr[i] = W + (int64_t)min(n0 + b_row + 32 * i, N - 1) * K + b_c;
     f32x4 ga[2], gb[2];
     auto load = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) ga[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + k0);
-        if (BF16) {
-            const F8 w = load8(reinterpret_cast<const uint16_t*>(b_ptr[0]) + k0, 0);
-            gb[0] = f32x4{w.v[0], w.v[1], w.v[2], w.v[3]};
-            gb[1] = f32x4{w.v[4], w.v[5], w.v[6], w.v[7]};
-        } else {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) gb[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(b_ptr[i]) + k0);
-        }
+        for (int i = 0; i < 2; ++i) gb[i] = *reinterpret_cast<const f32x4*>(b_ptr[i] + k0);
     };
     auto store = [&](int stage) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(&sA[stage][(a_row + 32 * i) * PG_STRIDE + a_c4 * 4]) = ga[i];
-        if (BF16) {
-            *reinterpret_cast<f32x4*>(&sB[stage][b_row * PG_STRIDE + b_c]) = gb[0];
-            *reinterpret_cast<f32x4*>(&sB[stage][b_row * PG_STRIDE + b_c + 4]) = gb[1];
-        } else {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(&sB[stage][(b_row + 32 * i) * PG_STRIDE + b_c]) = gb[i];
-        }
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(&sB[stage][(b_row + 32 * i) * PG_STRIDE + b_c]) = gb[i];
     };
 
     f32x16 acc;
@@ -1263,6 +1247,21 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
     const WT* W = static_cast<const WT*>(a.W);
     const WT* W2 = static_cast<const WT*>(a.W2);
     const bool norm = a.gamma != nullptr;
+    // The (epilogue, norm) pairs the callers request (launch_llm_gemv rejects every other one), and the only ones
+    // instantiated; each route below takes those of them it can reach:
+    //   (LE_NONE, NK_RMS)        RMSNorm + Q|K|V (llm.cpp pass: prompt rows, or one row wider than 8192), the decode step's head
+    //   (LE_NONE, NK_NONE)       the vocabulary head after the final norm (pass, pass_gpt2, prefill_rows)
+    //   (LE_RESIDUAL, NK_NONE)   o / down projection + residual (pass, pass_gpt2)
+    //   (LE_SWIGLU, NK_RMS)      RMSNorm + gate / up + SwiGLU (pass)
+    //   (LE_NONE, NK_LN)         LayerNorm + Q|K|V (pass_gpt2)
+    //   (LE_GELU_TANH, NK_LN)    LayerNorm + c_fc + GELU-tanh (pass_gpt2)
+#define KJ_RMS_PAIRS(LAUNCH)                                                                                                         \
+    do {                                                                                                                             \
+        if (a.swiglu) LAUNCH(LE_SWIGLU, NK_RMS);                                                                                     \
+        else if (a.R) LAUNCH(LE_RESIDUAL, NK_NONE);                                                                                  \
+        else if (norm) LAUNCH(LE_NONE, NK_RMS);                                                                                      \
+        else LAUNCH(LE_NONE, NK_NONE);                                                                                               \
+    } while (0)
     // Staging the row in LDS pays when it also has to be normalised (otherwise every wave redoes the statistics); plain
     // projections keep the one-wave-per-column kernel, whose 4x larger grid hides latency better.
     // One row, K = 2048 / 4096 / 8192: the weight-streaming kernel.
@@ -1283,8 +1282,8 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
         const bool loop = (batches + wpw - 1) / wpw > 4096 / wpw;
         const int wgs = loop ? 2048 / wpw : std::max(1, (batches + wpw - 1) / wpw);
 #define KJ_ST4(EPI, NORM, CH, WIDE, LOOP, THREADS)                                                                                   \
-    hipLaunchKernelGGL((llm_gemv_stream_kernel<WT, EPI, NORM, CH, WIDE, LOOP, THREADS>), dim3((unsigned)wgs), dim3(THREADS), 0, stream, \
-                       a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.Y0, 0, 0, a.norm_out)
+    hipLaunchKernelGGL((llm_gemv_stream_kernel<WT, EPI, NORM != NK_NONE, CH, WIDE, LOOP, THREADS>), dim3((unsigned)wgs), dim3(THREADS), \
+                       0, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.Y0, 0, 0, a.norm_out)
 #define KJ_ST3(EPI, NORM, CH, WIDE, LOOP)                                                                                            \
     do {                                                                                                                             \
         if (big) KJ_ST4(EPI, NORM, CH, WIDE, LOOP, 512);                                                                             \
@@ -1319,16 +1318,7 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
         else if (ch == 8) KJ_ST2(EPI, NORM, 8);                                                                                      \
         else KJ_ST2(EPI, NORM, 16);                                                                                                  \
     } while (0)
-        if (a.swiglu) {
-            if (norm) KJ_ST1(LE_SWIGLU, true);
-            else KJ_ST1(LE_SWIGLU, false);
-        } else if (a.R) {
-            if (norm) KJ_ST1(LE_RESIDUAL, true);
-            else KJ_ST1(LE_RESIDUAL, false);
-        } else {
-            if (norm) KJ_ST1(LE_NONE, true);
-            else KJ_ST1(LE_NONE, false);
-        }
+        KJ_RMS_PAIRS(KJ_ST1);
 #undef KJ_ST1
 #undef KJ_ST2
 #undef KJ_ST3
@@ -1338,107 +1328,63 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
         return hipGetLastError();
     }
     // LayerNorm (GPT-2) takes three kernels, each instantiated for the one combination it serves: one row, k <= 2048, the
-    // c_fc stage (LayerNorm + GELU) -> split-K with two columns per workgroup; one row, the Q|K|V stage (LayerNorm, cache
-    // segments) -> the LDS-staged kernel; everything else -> the multi-row kernel below.
+    // c_fc stage (LayerNorm + GELU) -> split-K; one row, the Q|K|V stage (LayerNorm, cache segments) -> the LDS-staged
+    // kernel; everything else -> the multi-row kernel below.
     if (a.layernorm && a.rows == 1 && a.gelu_tanh && a.seg_q == 0 && a.k <= 2048) {
-        hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, LE_GELU_TANH, NK_LN, 2, 1, 4>), dim3((unsigned)((a.n_out + 1) / 2)), dim3(256), 0,
-                           stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta);
+        hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, LE_GELU_TANH, NK_LN, 1, 4>), dim3((unsigned)((a.n_out + SK_OPW - 1) / SK_OPW)), dim3(256),
+                           0, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta);
         return hipGetLastError();
     }
+    const dim3 grid1((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW)));
+    const size_t lds1 = (size_t)a.k * sizeof(float);
+#define KJ_LLM1(EPI, NORM)                                                                                                            \
+    do {                                                                                                                              \
+        auto kern = llm_gemv1_kernel<WT, EPI, NORM>;                                                                                  \
+        if (lds1 > 48 * 1024) {                                                                                                       \
+            const hipError_t e = allow_dynamic_lds(kern, lds1);                                                                       \
+            if (e != hipSuccess) return e;                                                                                            \
+        }                                                                                                                             \
+        hipLaunchKernelGGL(kern, grid1, dim3(256), lds1, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.seg_q,      \
+                           a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);                                    \
+    } while (0)
     if (a.layernorm && a.rows == 1 && !a.gelu_tanh && a.k <= G1_MAX_K) {
-        const size_t lds = (size_t)a.k * sizeof(float);
-        auto kern = llm_gemv1_kernel<WT, LE_NONE, NK_LN>;
-        if (lds > 48 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW))), dim3(256), lds, stream, a.X, a.gamma, a.eps, W,
-                           W2, a.bias, a.R, a.n_out, a.k, a.seg_q, a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);
+        KJ_LLM1(LE_NONE, NK_LN);
         return hipGetLastError();
     }
-    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048 && (g_llm_gemv_variant == 0 || g_llm_gemv_variant >= 3)) {
+    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048) {
         // Long rows (down-proj: k = 8192 .. 14336) are spread over 16 waves per workgroup: a quarter of the loads per lane,
         // four times the waves in flight, at the same two columns per workgroup.
-        const bool wide = a.k >= 8192 && g_llm_gemv_variant != 7;
+        const bool wide = a.k >= 8192;
         const int threads = wide ? 1024 : 256;
         const int chunks = (a.k / 8 + threads - 1) / threads;
-        // Two columns per workgroup measured best on every projection of the 1B and 8B shapes (1, 4 and 8 were 2-18 % slower
-        // end to end): the chip wants many small workgroups more than it wants deep per-lane load queues.
-        int opw = 2;
-#ifdef KJARNI_TUNING
-        if (g_llm_gemv_variant >= 3 && g_llm_gemv_variant <= 6) opw = 1 << (g_llm_gemv_variant - 3);  // measurements: 3 -> 1 ... 6 -> 8
-#endif
-        if (opw > 8) opw = 8;
-        if (chunks > 2 && opw > 4) opw = 4;
-        if (chunks > 4 && opw > 2) opw = 2;
-        if (a.swiglu && chunks > 2 && opw > 2) opw = 2;
-        if (wide && opw > 2) opw = 2;  // the 16-wave kernel is instantiated for <= 2 columns
-        const dim3 gridk((unsigned)((a.n_out + opw - 1) / opw));
-#define KJ_SK4(EPI, NORM, OPW, CH, NW)                                                                                                \
-    hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, EPI, NORM, OPW, CH, NW>), gridk, dim3(64 * NW), 0, stream, a.X, a.gamma, a.eps, W, \
-                       W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta)
-#define KJ_SK3(EPI, NORM, OPW, CH)                                                                                                    \
+        const dim3 gridk((unsigned)((a.n_out + SK_OPW - 1) / SK_OPW));
+#define KJ_SK3(EPI, NORM, CH, NW)                                                                                                     \
+    hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, EPI, NORM, CH, NW>), gridk, dim3(64 * NW), 0, stream, a.X, a.gamma, a.eps, W, W2,  \
+                       a.bias, a.R, a.n_out, a.k, a.Y0, a.beta)
+#define KJ_SK2(EPI, NORM, CH)                                                                                                         \
     do {                                                                                                                              \
-        if (wide) KJ_SK4(EPI, NORM, (OPW > 2 ? 2 : OPW), (CH > 2 ? 2 : CH), 16);                                                      \
-        else KJ_SK4(EPI, NORM, OPW, CH, 4);                                                                                           \
-    } while (0)
-#define KJ_SK2(EPI, NORM, OPW)                                                                                                        \
-    do {                                                                                                                              \
-        if (chunks <= 1) KJ_SK3(EPI, NORM, OPW, 1);                                                                                   \
-        else if (chunks <= 2) KJ_SK3(EPI, NORM, OPW, 2);                                                                              \
-        else if (chunks <= 4) KJ_SK3(EPI, NORM, (OPW > 4 ? 4 : OPW), 4);                                                              \
-        else KJ_SK3(EPI, NORM, (OPW > 2 ? 2 : OPW), 8);                                                                               \
+        if (wide) KJ_SK3(EPI, NORM, (CH > 2 ? 2 : CH), 16);                                                                           \
+        else KJ_SK3(EPI, NORM, CH, 4);                                                                                                \
     } while (0)
 #define KJ_SK1(EPI, NORM)                                                                                                             \
     do {                                                                                                                              \
-        if (opw == 1) KJ_SK2(EPI, NORM, 1);                                                                                           \
-        else if (opw == 2) KJ_SK2(EPI, NORM, 2);                                                                                      \
-        else if (opw == 4) KJ_SK2(EPI, NORM, 4);                                                                                      \
+        if (chunks <= 1) KJ_SK2(EPI, NORM, 1);                                                                                        \
+        else if (chunks <= 2) KJ_SK2(EPI, NORM, 2);                                                                                   \
+        else if (chunks <= 4) KJ_SK2(EPI, NORM, 4);                                                                                   \
         else KJ_SK2(EPI, NORM, 8);                                                                                                    \
     } while (0)
-        if (a.swiglu) {
-            if (norm) KJ_SK1(LE_SWIGLU, true);
-            else KJ_SK1(LE_SWIGLU, false);
-        } else if (a.R) {
-            if (norm) KJ_SK1(LE_RESIDUAL, true);
-            else KJ_SK1(LE_RESIDUAL, false);
-        } else {
-            if (norm) KJ_SK1(LE_NONE, true);
-            else KJ_SK1(LE_NONE, false);
-        }
-#undef KJ_SK4
+        KJ_RMS_PAIRS(KJ_SK1);
 #undef KJ_SK1
 #undef KJ_SK2
 #undef KJ_SK3
         return hipGetLastError();
     }
-    if (!a.layernorm && a.rows == 1 && norm && a.k <= G1_MAX_K && g_llm_gemv_variant != 1) {
-        const dim3 grid1((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW)));
-        const size_t lds = (size_t)a.k * sizeof(float);
-#define KJ_LLM1(EPI, NORM)                                                                                                            \
-    do {                                                                                                                              \
-        auto kern = llm_gemv1_kernel<WT, EPI, NORM>;                                                                                  \
-        if (lds > 48 * 1024) {                                                                                                        \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                     (int)lds);                                                                       \
-            if (e != hipSuccess) return e;                                                                                            \
-        }                                                                                                                             \
-        hipLaunchKernelGGL(kern, grid1, dim3(256), lds, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.seg_q,       \
-                           a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);                                    \
-    } while (0)
-        if (a.swiglu) {
-            if (norm) KJ_LLM1(LE_SWIGLU, true);
-            else KJ_LLM1(LE_SWIGLU, false);
-        } else if (a.R) {
-            if (norm) KJ_LLM1(LE_RESIDUAL, true);
-            else KJ_LLM1(LE_RESIDUAL, false);
-        } else {
-            if (norm) KJ_LLM1(LE_NONE, true);
-            else KJ_LLM1(LE_NONE, false);
-        }
-#undef KJ_LLM1
+    if (!a.layernorm && a.rows == 1 && norm && a.k <= G1_MAX_K) {
+        if (a.swiglu) KJ_LLM1(LE_SWIGLU, NK_RMS);
+        else KJ_LLM1(LE_NONE, NK_RMS);
         return hipGetLastError();
     }
+#undef KJ_LLM1
     const dim3 grid((unsigned)((a.n_out + 3) / 4));
 #define KJ_LLM(EPI, NORM)                                                                                                       \
     hipLaunchKernelGGL((llm_gemv_kernel<WT, EPI, NORM>), grid, dim3(256), 0, stream, a.X, a.ldx, a.rows, a.gamma, a.eps, W, W2,  \
@@ -1447,23 +1393,13 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
     if (a.layernorm) {  // the GPT-2 stages that reach here: 2-8 rows, or a projection too wide for the kernels above
         if (a.gelu_tanh) KJ_LLM(LE_GELU_TANH, NK_LN);
         else KJ_LLM(LE_NONE, NK_LN);
-    } else if (a.swiglu) {
-        if (norm) KJ_LLM(LE_SWIGLU, true);
-        else KJ_LLM(LE_SWIGLU, false);
-    } else if (a.R) {
-        if (norm) KJ_LLM(LE_RESIDUAL, true);
-        else KJ_LLM(LE_RESIDUAL, false);
     } else {
-        if (norm) KJ_LLM(LE_NONE, true);
-        else KJ_LLM(LE_NONE, false);
+        KJ_RMS_PAIRS(KJ_LLM);
     }
 #undef KJ_LLM
+#undef KJ_RMS_PAIRS
     return hipGetLastError();
 }
-
-#ifdef KJARNI_TUNING
-void set_llm_gemv_variant(int v) { g_llm_gemv_variant = v; }
-#endif
 
 int prefill_gemm_ksplit(int M, int N, int K)
 {
@@ -1482,18 +1418,6 @@ size_t prefill_gemm_scratch_floats(int max_rows, int max_n)
     return (size_t)1024 * PG_BM * PG_BN;
 }
 
-namespace {
-inline bool prefill_f32_mfma_for_bf16()
-{
-#ifdef KJARNI_TUNING
-    static const bool v = [] { const char* e = std::getenv("KJARNI_HIP_LLM_WIDEN"); return e && e[0] == '1'; }();
-    return v;
-#else
-    return false;
-#endif
-}
-}  // namespace
-
 hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int bf16, const float* bias, const float* R, int64_t ldr, float* Y,
                                int64_t ldy, int M, int N, int K, hipStream_t stream, float* split_scratch, float* silu_gate)
 {
@@ -1506,20 +1430,18 @@ hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int b
         (!R || (reinterpret_cast<uintptr_t>(R) & 15) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0))
         ksplit = prefill_gemm_ksplit(M, N, K);
     const dim3 grid((unsigned)(m_tiles * n_tiles * ksplit));
-#define KJ_PG(WT, RES)                                                                                                              \
-    hipLaunchKernelGGL((prefill_gemm_kernel<WT, RES>), grid, dim3(256), 0, stream, A, lda, static_cast<const WT*>(W), bias, R, ldr, Y, ldy, \
+#define KJ_PG(RES)                                                                                                                  \
+    hipLaunchKernelGGL((prefill_gemm_kernel<RES>), grid, dim3(256), 0, stream, A, lda, static_cast<const float*>(W), bias, R, ldr, Y, ldy, \
                        M, N, K, m_tiles, ksplit, split_scratch)
-    if (bf16 && !prefill_f32_mfma_for_bf16()) {
+    if (bf16) {
         // bf16 weights: on the bf16 matrix cores, the activations as three exact bf16 pieces (gemm_split.hip)
         const hipError_t e = launch_prefill_tiles_bf16w((unsigned)(m_tiles * n_tiles * ksplit), A, lda, W, bias, R, ldr, Y, ldy, M, N, K, m_tiles,
                                                         ksplit, split_scratch, stream);
         if (e != hipSuccess) return e;
-    } else if (bf16) {
-        if (R) KJ_PG(uint16_t, true);
-        else KJ_PG(uint16_t, false);
+    } else if (R) {
+        KJ_PG(true);
     } else {
-        if (R) KJ_PG(float, true);
-        else KJ_PG(float, false);
+        KJ_PG(false);
     }
 #undef KJ_PG
     if (ksplit > 1) {
@@ -1723,21 +1645,19 @@ hipError_t launch_prefill_attention(const float* q, int64_t ldq, int rows, const
     if (rows <= 0) return hipSuccess;
     if (!prefill_attention_supported(head_dim)) return hipErrorInvalidValue;
     // long blocks of 64- / 128-wide heads: the matrix-core kernel
-    if (rows >= 256 && (head_dim == 64 || head_dim == 128) && g_llm_gemv_variant != 9 && (ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 &&
+    if (rows >= 256 && (head_dim == 64 || head_dim == 128) && (ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0) {
         const dim3 mgrid((unsigned)((rows + PM_Q - 1) / PM_Q), (unsigned)heads);
         const float mscale = 1.0f / sqrtf((float)head_dim);
         const int g = kv_group < 1 ? 1 : kv_group;
         if (head_dim == 64) {
             auto kern = prefill_attention_mfma_kernel<64>;
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     PmSmem<64>::BYTES);
+            const hipError_t e = allow_dynamic_lds(kern, PmSmem<64>::BYTES);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(kern, mgrid, dim3(256), PmSmem<64>::BYTES, stream, q, ldq, rows, K, ldk, V, ldv, base, g, mscale, ctx, ldc);
         } else {
             auto kern = prefill_attention_mfma_kernel<128>;
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     PmSmem<128>::BYTES);
+            const hipError_t e = allow_dynamic_lds(kern, PmSmem<128>::BYTES);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(kern, mgrid, dim3(256), PmSmem<128>::BYTES, stream, q, ldq, rows, K, ldk, V, ldv, base, g, mscale, ctx, ldc);
         }
@@ -1751,8 +1671,7 @@ hipError_t launch_prefill_attention(const float* q, int64_t ldq, int rows, const
     do {                                                                                                                                \
         auto kern = prefill_attention_kernel<DPT>;                                                                                      \
         if (lds > 48 * 1024) {                                                                                                          \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                                     (int)lds);                                                                         \
+            const hipError_t e = allow_dynamic_lds(kern, lds);                                                                          \
             if (e != hipSuccess) return e;                                                                                              \
         }                                                                                                                               \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, q, ldq, rows, K, ldk, V, ldv, base, kv_group < 1 ? 1 : kv_group, scale,  \
@@ -1780,7 +1699,7 @@ hipError_t launch_swiglu_mul(float* gate, const float* up, size_t n, hipStream_t
 bool llm_qkv_rope_embeds(int k, const float* gamma, const void* W, const void* table)
 {
     return (k == 2048 || k == 4096 || k == 8192) && gamma && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(table) & 15) == 0 && g_llm_gemv_variant != 8 && g_llm_gemv_variant != 1;
+           (reinterpret_cast<uintptr_t>(table) & 15) == 0;
 }
 
 hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, const void* W, int bf16, const float* bias, int k,
@@ -1791,8 +1710,7 @@ hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, co
     if ((k & 7) || k > 8192 || (head_dim & 1)) return hipErrorInvalidValue;
     const int tasks = (n_heads * head_dim + 2 * n_kv_heads * head_dim) / 2;
     if (embed_ids && !llm_qkv_rope_embeds(k, gamma, W, table)) return hipErrorInvalidValue;
-    if ((k == 2048 || k == 4096 || k == 8192) && gamma && (reinterpret_cast<uintptr_t>(W) & 15) == 0 && g_llm_gemv_variant != 8 &&
-        g_llm_gemv_variant != 1) {
+    if ((k == 2048 || k == 4096 || k == 8192) && gamma && (reinterpret_cast<uintptr_t>(W) & 15) == 0) {
         const dim3 sgrid((unsigned)((tasks + 3) / 4));
 #define KJ_QKVS(WT, CH)                                                                                                              \
     do {                                                                                                                             \
@@ -1837,13 +1755,11 @@ hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, co
 
 bool llm_gemv_streams(int k, const void* W, const void* W2)
 {
-    return (k == 2048 || k == 4096 || k == 8192) && g_llm_gemv_variant != 8 && g_llm_gemv_variant != 1 &&
-           (reinterpret_cast<uintptr_t>(W) & 15) == 0 && (!W2 || (reinterpret_cast<uintptr_t>(W2) & 15) == 0);
+    return (k == 2048 || k == 4096 || k == 8192) && (reinterpret_cast<uintptr_t>(W) & 15) == 0 && (!W2 || (reinterpret_cast<uintptr_t>(W2) & 15) == 0);
 }
 
 bool llm_gemv_merges_attention(int k, int splits, int head_dim)
 {
-    if (g_llm_gemv_variant == 8 || g_llm_gemv_variant == 1) return false;  // measurements: the kernels before the streaming one
     if (head_dim < 4 || (head_dim & 3) || k % head_dim) return false;
     return (k == 2048 && splits >= 1 && splits <= 8) || (k == 4096 && splits >= 1 && splits <= 4);
 }
@@ -1855,6 +1771,8 @@ hipError_t launch_llm_gemv(const LlmGemvArgs& a, hipStream_t stream)
     // LayerNorm needs gamma and beta and takes no residual / SwiGLU epilogue; GELU-tanh comes only after LayerNorm (GPT-2's c_fc)
     if (a.layernorm && (!a.gamma || !a.beta || a.R || a.swiglu || a.att_splits > 0 || a.norm_out)) return hipErrorInvalidValue;
     if (a.gelu_tanh && (!a.layernorm || a.seg_q != 0)) return hipErrorInvalidValue;
+    // SwiGLU comes only after RMSNorm, a residual only without a norm (the pairs at launch_gemv_t)
+    if ((a.swiglu && (!a.gamma || a.R)) || (a.R && a.gamma)) return hipErrorInvalidValue;
     if (a.rows <= 0 || a.n_out <= 0) return hipSuccess;
     if (a.rows > LLM_MAX_ROWS || (a.k & 7) || (a.ldx & 3) || (reinterpret_cast<uintptr_t>(a.X) & 15) ||
         (reinterpret_cast<uintptr_t>(a.W) & 15))
@@ -1882,27 +1800,6 @@ hipError_t launch_rmsnorm(const float* x, const float* gamma, float eps, int row
     hipLaunchKernelGGL(rmsnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, gamma, eps, rows, hidden, out);
     return hipGetLastError();
 }
-
-#ifdef KJARNI_TUNING
-namespace {
-// Measurements only: pull `bytes` through the memory-side cache (plain loads, values discarded).
-__global__ __launch_bounds__(256) void touch_kernel(const uint4* __restrict__ p, size_t n16, unsigned* __restrict__ sink)
-{
-    unsigned acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
-        const uint4 v = p[i];
-        acc ^= v.x ^ v.y ^ v.z ^ v.w;
-    }
-    if (acc == 0x9e3779b9u) *sink = acc;
-}
-}  // namespace
-
-hipError_t launch_touch(const void* p, size_t bytes, unsigned* sink, hipStream_t stream)
-{
-    hipLaunchKernelGGL(touch_kernel, dim3(2048), dim3(256), 0, stream, static_cast<const uint4*>(p), bytes / 16, sink);
-    return hipGetLastError();
-}
-#endif
 
 hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, const void* table, int bf16, float* out,
                             hipStream_t stream)

@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -440,9 +439,6 @@ std::unique_ptr<WhisperModel> WhisperModel::load(const std::string& dir, int dev
     hip_check(hipMemset(m->dbest_, 0, sizeof(unsigned long long) * kMaxLanes), "memset(pick scratch)");
     hip_check(hipStreamCreateWithFlags(&m->stream_, hipStreamNonBlocking), "hipStreamCreate");
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(load)");
-#ifdef KJARNI_TUNING
-    if (const char* v = std::getenv("KJARNI_HIP_GEMV_ROWS")) set_gemv_rows_variant(std::atoi(v));  // kernel A/B measurements
-#endif
     return m;
 }
 
@@ -547,14 +543,7 @@ void WhisperModel::decoder_pass(const uint32_t* ids_dev, int n, bool device_pos)
     // launches fewer per step; the same arithmetic, element for element) -- where the one-row kernel takes the row (512 / 2048 floats).
     GemvArgs probe;
     probe.rows = 1; probe.k = H; probe.gamma = dec_ln_g_; probe.beta = dec_ln_b_; probe.W = lm_head_; probe.embed_ids = ids_dev;
-    bool fold = n == 1 && gemv_rows_takes_row_extras(probe) && H == 512;
-    bool fold_head = fold;
-#ifdef KJARNI_TUNING
-    static const char* no_fold = std::getenv("KJARNI_HIP_WHISPER_NO_FOLD");  // measurements: "1" neither, "embed" / "head" not that one
-    if (no_fold && no_fold[0] == '1') fold = fold_head = false;
-    if (no_fold && no_fold[0] == 'e') fold = false;
-    if (no_fold && no_fold[0] == 'h') fold_head = false;
-#endif
+    const bool fold = n == 1 && gemv_rows_takes_row_extras(probe) && H == 512;
     if (!fold)
         hip_check(launch_decoder_embed(ids_dev, n, H, cfg_.vocab, tok_emb_, dec_pos_, cfg_.max_target_positions, cache_len_, pos_ptr,
                                        cfg_.scale_embedding ? 1 : 0, dh_, s), "decoder embed");
@@ -603,7 +592,7 @@ void WhisperModel::decoder_pass(const uint32_t* ids_dev, int n, bool device_pos)
     GemvArgs a;
     a.ldx = H; a.rows = 1; a.W = lm_head_; a.n_out = cfg_.vocab; a.k = H; a.Y0 = logits_;
     a.ldy0 = cfg_.vocab; a.epi = EPI_BIAS;
-    if (fold_head) {
+    if (fold) {
         a.X = dh_; a.gamma = dec_ln_g_; a.beta = dec_ln_b_; a.eps = 1e-5f; a.x_norm_out = dlast_;
     } else {
         hip_check(launch_layernorm(dh_, dec_ln_g_, dec_ln_b_, 1e-5f, n, H, dlast_, s), "final ln");

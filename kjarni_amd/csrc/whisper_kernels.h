@@ -61,10 +61,6 @@ struct GemvArgs {
 };
 bool gemv_rows_takes_row_extras(const GemvArgs& args);
 hipError_t launch_gemv_rows(const GemvArgs& args, hipStream_t stream);
-#ifdef KJARNI_TUNING
-hipError_t attention_stamps(unsigned long long* out16, int reset);  // measurements: decode attention's cycles per phase
-void set_gemv_rows_variant(int variant);  // 0 = rows staged in LDS when there are several, 1 = always the per-wave kernel
-#endif
 
 // Attention of `rows` query rows over cached keys/values, split over `splits` key ranges + a combine pass.
 // n_keys_ptr (device int) given: keys = *n_keys_ptr + rows and the causal base = *n_keys_ptr (max_keys bounds it);

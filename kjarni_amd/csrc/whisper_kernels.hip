@@ -7,9 +7,9 @@
 //   decoder step   cpu/encoder_decoder/cpu_decoder.rs:457-516, decoder_cross_attn.rs:71-120,
 //                  encoder_decoder/decoder_self_attn.rs:52-146
 //   token choice   crates/kjarni-models/src/models/whisper/transcriber.rs:243-270
-#include <atomic>
 
 #include "device_utils.h"
+#include "dynamic_lds.h"
 #include "whisper_kernels.h"
 
 namespace kjarni {
@@ -170,12 +170,6 @@ __global__ __launch_bounds__(256) void decoder_embed_kernel(const uint32_t* __re
     }
 }
 
-#ifdef KJARNI_TUNING
-// Measurements (tuning build): shader cycles the decode attention's register path spends per phase, summed over workgroups --
-// [0] entry -> scores (the loads' round trips + the dots), [1] -> block max, [2] -> exp, weighted V, block sum, [3] -> slab
-// stored, [4] workgroups counted; [5] / [6] / [7]: the one-row GEMV's entry -> dot reduced, -> stored, waves sampled.  kjarni_hip_attention_stamps reads / resets them.
-__device__ unsigned long long g_att_stamp[16];   // ([15]: stamps on; [8] .. [12]: the one-row LN GEMV's entry -> row arrived, -> arguments arrived, -> weight requests issued, waves, -> every request issued)
-#endif
 constexpr int GEMV_MAX_ROWS = 8;
 
 // Y[r, n] = epi(LN?(X[r, :]) . W[n, :] + bias[n]) (+ R[r, n]) for a handful of rows r: one wave per output
@@ -280,58 +274,32 @@ struct GemvEmbed {
     float scale;
 };
 
-// COLS output columns per wave, WAVES waves per workgroup: a wave's requests for the row, gamma and beta are the same whatever
-// its column, and on a compute unit they queue behind one another in the one address pipe -- with one column per wave a wave
-// of the 1536-column projection needed ~2 300 cycles just to ISSUE its eight loads (stamps: docs/history/r06.md); with COLS
-// columns a wave issues 6 + 2 COLS instead of 8 COLS.  Each column's dot product keeps its own lane order and reduction.
-template <int EPI, bool LN, int KCH, bool EMBED = false, int COLS = 1, int WAVES = 4>
-__global__ __launch_bounds__(64 * WAVES) void gemv_row_fast_kernel(const float* __restrict__ X, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ beta, float eps,
-                                                                   const float* __restrict__ W, const float* __restrict__ bias,
-                                                                   const float* R, int n_out, int seg, float* Y0,
-                                                                   float* __restrict__ Y1, float* __restrict__ Y2, int64_t ldy12,
-                                                                   int row_off, const int* __restrict__ row_off_ptr,
-                                                                   float* __restrict__ x_raw_out, float* __restrict__ x_norm_out,
-                                                                   GemvEmbed emb)
+template <int EPI, bool LN, int KCH, bool EMBED = false>
+__global__ __launch_bounds__(256) void gemv_row_fast_kernel(const float* __restrict__ X, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, const float* __restrict__ W,
+                                                            const float* __restrict__ bias, const float* R, int n_out, int seg,
+                                                            float* Y0, float* __restrict__ Y1, float* __restrict__ Y2, int64_t ldy12,
+                                                            int row_off, const int* __restrict__ row_off_ptr,
+                                                            float* __restrict__ x_raw_out, float* __restrict__ x_norm_out, GemvEmbed emb)
 {
     constexpr int K = 256 * KCH;
-#ifdef KJARNI_TUNING
-    const unsigned long long gst0 = __builtin_amdgcn_s_memtime();
-#endif
     // (every argument in one batch of scalar loads: device_utils.h)
     kj_args_now(X, gamma, beta, eps, W, bias, R, n_out, seg, Y0, Y1, Y2, ldy12, row_off, row_off_ptr, x_raw_out, x_norm_out);
     if (EMBED) kj_args_now(emb.ids, emb.word, emb.pos_table, emb.vocab, emb.max_pos, emb.pos, emb.pos_ptr, emb.scale);
-#ifdef KJARNI_TUNING
-    unsigned long long gsta;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(gsta) : "s"(x_norm_out), "s"(ldy12) : "memory");   // (arguments arrived)
-#endif
+    // The cache row of segments 1 and 2 (a device counter in a captured step), needed only at the store.  Read through the
+    // constant address space: the counter does not change while the kernel runs, so the compiler issues it as a scalar load
+    // here and waits for it where it is used (a plain load after the asm above is a vector load waited for at once, a round
+    // trip in front of the weight requests).
+    typedef __attribute__((address_space(4))) const int const_int;
+    const int r0 = seg > 0 && row_off_ptr ? *(const_int*)row_off_ptr : row_off;
     const int lane = threadIdx.x & 63;
-    const int wave = WAVES > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-    const int64_t n0 = ((int64_t)blockIdx.x * WAVES + wave) * COLS;
-    if (n0 >= n_out) return;
-    f32x4 x[KCH], w[COLS][KCH], g[KCH], bt[KCH];
-#if defined(KJARNI_TUNING) && defined(KJARNI_GEMV_PROBE)
-    // (timing probe, results garbage: the arrays every wave shares read from a place of the wave's own instead)
-    gamma = W + ((n0 * 7 + 3) % n_out) * (int64_t)K;
-    beta = W + ((n0 * 13 + 5) % n_out) * (int64_t)K;
-    if (KJARNI_GEMV_PROBE >= 2) X = W + ((n0 * 11 + 1) % n_out) * (int64_t)K;
-#endif
-    // Order of issue = order of need, and nothing that waits stands before a request: the row offset (a device counter) is a
-    // scalar load waited for only at the store; the weight rows -- the one stream that comes from HBM -- go first.
-    int r0s = row_off;
-    if (seg > 0 && row_off_ptr) asm volatile("s_load_dword %0, %1, 0x0" : "=s"(r0s) : "s"(row_off_ptr));
+    const int64_t n = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (n >= n_out) return;
+    f32x4 x[KCH], w[KCH], g[KCH], bt[KCH];
+    // Order of issue = order of need: the weight row -- the one stream that comes from HBM -- goes first.
+    const f32x4* w4 = reinterpret_cast<const f32x4*>(W + n * (int64_t)K);
 #pragma unroll
-    for (int c = 0; c < COLS; ++c) {
-        const int64_t nc = COLS > 1 && n0 + c >= n_out ? n_out - 1 : n0 + c;   // (a ragged last wave re-reads the last row)
-        const f32x4* w4 = reinterpret_cast<const f32x4*>(W + nc * (int64_t)K);
-#pragma unroll
-        for (int j = 0; j < KCH; ++j) w[c][j] = __builtin_nontemporal_load(w4 + lane + 64 * j);
-    }
-#ifdef KJARNI_TUNING
-    asm volatile("" ::: "memory");
-    const unsigned long long gstw = __builtin_amdgcn_s_memtime();   // (weight requests issued)
-    asm volatile("" ::: "memory");
-#endif
+    for (int j = 0; j < KCH; ++j) w[j] = __builtin_nontemporal_load(w4 + lane + 64 * j);
     if (EMBED) {
         const uint32_t id = emb.ids[0];
         const int p = emb.pos_ptr ? *emb.pos_ptr : emb.pos;
@@ -350,7 +318,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv_row_fast_kernel(const float* 
             }
             x[j] = v;
         }
-        if (n0 == 0 && x_raw_out) {
+        if (n == 0 && x_raw_out) {
 #pragma unroll
             for (int j = 0; j < KCH; ++j) *reinterpret_cast<f32x4*>(x_raw_out + (lane + 64 * j) * 4) = x[j];
         }
@@ -365,26 +333,16 @@ __global__ __launch_bounds__(64 * WAVES) void gemv_row_fast_kernel(const float* 
             bt[j] = *reinterpret_cast<const f32x4*>(beta + (lane + 64 * j) * 4);
         }
     }
-    // (bias and residual of the wave's columns: lane c holds column n0 + c's)
-    const int64_t nl = n0 + lane < n_out ? n0 + lane : n_out - 1;
+    // (bias and residual of the wave's column: lane 0 holds them)
     float b = 0.0f, res = 0.0f;
-    if (lane < COLS) {
-        if (bias) b = bias[nl];
-        if (EPI == EPI_BIAS_RESIDUAL) res = R[nl];
+    if (lane == 0) {
+        if (bias) b = bias[n];
+        if (EPI == EPI_BIAS_RESIDUAL) res = R[n];
     }
-#ifdef KJARNI_TUNING
-    unsigned long long gstx = 0;
-    asm volatile("" ::: "memory");
-    const unsigned long long gsti = __builtin_amdgcn_s_memtime();   // (every request issued)
-#endif
     if (LN) {
         float s = 0.0f;
 #pragma unroll
         for (int j = 0; j < KCH; ++j) s += (x[j][0] + x[j][1]) + (x[j][2] + x[j][3]);
-#ifdef KJARNI_TUNING
-        asm volatile("" : "+v"(s));
-        gstx = __builtin_amdgcn_s_memtime();   // (the input row has arrived)
-#endif
         const float mu = wave_sum(s) / (float)K;
         float v = 0.0f;
 #pragma unroll
@@ -396,50 +354,23 @@ __global__ __launch_bounds__(64 * WAVES) void gemv_row_fast_kernel(const float* 
         for (int j = 0; j < KCH; ++j)
 #pragma unroll
             for (int c = 0; c < 4; ++c) x[j][c] = (x[j][c] - mu) * rstd * g[j][c] + bt[j][c];
-        if (n0 == 0 && x_norm_out) {
+        if (n == 0 && x_norm_out) {
 #pragma unroll
             for (int j = 0; j < KCH; ++j) *reinterpret_cast<f32x4*>(x_norm_out + (lane + 64 * j) * 4) = x[j];
         }
     }
-    float out = 0.0f;
+    float acc = 0.0f;
 #pragma unroll
-    for (int cc = 0; cc < COLS; ++cc) {
-        float acc = 0.0f;
+    for (int j = 0; j < KCH; ++j)
 #pragma unroll
-        for (int j = 0; j < KCH; ++j)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc = fmaf(x[j][c], w[cc][j][c], acc);
-        const float d = wave_sum(acc);
-        out = lane == cc ? d : out;
-    }
-    float v = out + b;
-#ifdef KJARNI_TUNING
-    asm volatile("" : "+v"(v));
-    const unsigned long long gst1 = __builtin_amdgcn_s_memtime();
-#endif
+        for (int c = 0; c < 4; ++c) acc = fmaf(x[j][c], w[j][c], acc);
+    float v = wave_sum(acc) + b;
     if (EPI == EPI_BIAS_GELU) v = gelu_erf(v);
     if (EPI == EPI_BIAS_RESIDUAL) v += res;
-    const int64_t n = n0 + lane;
     const int which = seg > 0 ? (int)(n >= seg) + (int)(n >= 2 * (int64_t)seg) : 0;   // (n / seg: three segments at most)
     const int64_t col = n - (int64_t)which * seg;
     float* Y = which == 0 ? Y0 : (which == 1 ? Y1 : Y2);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(r0s));
-    if (lane < COLS && n < n_out) Y[(which == 0 ? 0 : (int64_t)r0s * ldy12) + col] = v;
-#ifdef KJARNI_TUNING
-    const unsigned long long gst2 = __builtin_amdgcn_s_memtime();   // (before the flag is read: its round trip is not the store's)
-    if (lane == 0 && n_out <= 4096 && (blockIdx.x & 31) == 0 && wave == 0 && g_att_stamp[15] != 0ull) {   // (a sample of the waves; not the vocabulary head; only while the stamps are being taken)
-        atomicAdd(&g_att_stamp[5], gst1 - gst0);
-        atomicAdd(&g_att_stamp[6], gst2 - gst1);
-        atomicAdd(&g_att_stamp[7], 1ull);
-        if (LN) {
-            atomicAdd(&g_att_stamp[8], gstx - gst0);    // (entry -> the row arrived)
-            atomicAdd(&g_att_stamp[9], gsta - gst0);    // (entry -> arguments arrived)
-            atomicAdd(&g_att_stamp[10], gstw - gst0);   // (entry -> weight requests issued)
-            atomicAdd(&g_att_stamp[11], 1ull);
-            atomicAdd(&g_att_stamp[12], gsti - gst0);   // (entry -> every request issued)
-        }
-    }
-#endif
+    if (lane == 0) Y[(which == 0 ? 0 : (int64_t)r0 * ldy12) + col] = v;
 }
 
 // The same projection for 2..8 rows (several tokens of one sequence, or the lanes of a lock-step decode): the rows are
@@ -790,11 +721,6 @@ __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const flo
 
     float mx = -INFINITY, sum = 0.0f;
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef KJARNI_TUNING
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-    unsigned long long st1 = 0, st2 = 0, st3 = 0;
-    const bool fast_path = t1 - t0 <= ATT_FAST * groups;
-#endif
     if (t1 - t0 <= ATT_FAST * groups) {
         // Short ranges (a decode step over a few hundred cached keys is a chain of latencies, not of bytes): every K and V
         // row of the range is requested at once and held in registers -- one memory round trip instead of one per pass.
@@ -819,13 +745,7 @@ __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const flo
             sv[j] = t < t1 ? v : -INFINITY;
             mx = fmaxf(mx, sv[j]);
         }
-#ifdef KJARNI_TUNING
-        st1 = __builtin_amdgcn_s_memtime();
-#endif
         mx = block_max(mx);
-#ifdef KJARNI_TUNING
-        st2 = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll
         for (int j = 0; j < ATT_FAST; ++j) {
             const float e = t0 + g + j * groups < t1 ? expf(sv[j] - mx) : 0.0f;
@@ -834,9 +754,6 @@ __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const flo
             for (int c = 0; c < 4; ++c) acc[c] = fmaf(e, vr[j][c], acc[c]);
         }
         sum = block_sum(sum);
-#ifdef KJARNI_TUNING
-        st3 = __builtin_amdgcn_s_memtime();
-#endif
     } else {
         for (int t = t0 + g; t < t1; t += groups) {
             const f32x4 kv = *reinterpret_cast<const f32x4*>(K + (int64_t)t * ldk + col);
@@ -880,16 +797,6 @@ __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const flo
     float* out = part + (((int64_t)s * gridDim.x + h) * splits + sp) * (head_dim + 4);
     if (tid < lpk) *reinterpret_cast<f32x4*>(out + 4 + tid * 4) = (accs[tid] + accs[lpk + tid]) + (accs[2 * lpk + tid] + accs[3 * lpk + tid]);
     if (tid == 0) *reinterpret_cast<f32x4*>(out) = f32x4{(t1 > t0) ? mx : -INFINITY, (t1 > t0) ? sum : 0.0f, 0.0f, 0.0f};
-#ifdef KJARNI_TUNING
-    const unsigned long long st4 = __builtin_amdgcn_s_memtime();   // (before the flag is read)
-    if (tid == 0 && fast_path && g_att_stamp[15] != 0ull) {   // (only while the stamps are being taken: the atomics cost a token 0.07 ms)
-        atomicAdd(&g_att_stamp[0], st1 - st0);
-        atomicAdd(&g_att_stamp[1], st2 - st1);
-        atomicAdd(&g_att_stamp[2], st3 - st2);
-        atomicAdd(&g_att_stamp[3], st4 - st3);
-        atomicAdd(&g_att_stamp[4], 1ull);
-    }
-#endif
 }
 
 
@@ -1058,20 +965,6 @@ __global__ void pick_finalize_kernel(unsigned long long* __restrict__ best, int 
 
 }  // namespace
 
-#ifdef KJARNI_TUNING
-hipError_t attention_stamps(unsigned long long* out16, int reset)
-{
-    // reset != 0: counters to zero and the stamps ON ([15] = 1); reset == 0: read them and switch the stamps OFF again
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_att_stamp), 16 * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    unsigned long long next[16] = {};
-    if (reset) next[15] = 1ull;
-    else
-        for (int i = 0; i < 15; ++i) next[i] = out16[i];
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_att_stamp), next, sizeof(next));
-}
-#endif
-
 // ---- launchers --------------------------------------------------------------------------------------
 
 hipError_t launch_mel_frames(const float* audio, int64_t n_samples, const float* window, int n_fft, int hop,
@@ -1132,21 +1025,12 @@ hipError_t launch_decoder_embed(const uint32_t* ids, int n, int hidden, int voca
     return hipGetLastError();
 }
 
-#ifdef KJARNI_TUNING
-std::atomic<int> g_gemv_rows_variant{0};  // 1 = never stage the rows in LDS -- tuning build only
-#else
-constexpr int g_gemv_rows_variant = 0;
-#endif
-#ifdef KJARNI_TUNING
-void set_gemv_rows_variant(int v) { g_gemv_rows_variant = v; }
-#endif
-
 // The one-row kernel for 512- / 2048-float rows is the only one that honours embed_* / x_raw_out / x_norm_out.
 bool gemv_rows_takes_row_extras(const GemvArgs& a)
 {
     const int kch = a.k / 256;
     const bool ln = a.gamma != nullptr;
-    return a.rows == 1 && a.k % 256 == 0 && (kch == 2 || kch == 8) && g_gemv_rows_variant == 0 && (!ln || a.beta) &&
+    return a.rows == 1 && a.k % 256 == 0 && (kch == 2 || kch == 8) && (!ln || a.beta) &&
            (!ln || ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0) && (a.k & 3) == 0 &&
            (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (a.embed_ids || ((a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0));
 }
@@ -1161,9 +1045,48 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
         if (!simple) return hipErrorInvalidValue;
         return launch_gemm(a.X, a.ldx, a.W, a.bias, a.R, a.ldr, a.Y0, a.ldy0, a.rows, a.n_out, a.k, a.epi, stream);
     }
+    const bool ln = a.gamma != nullptr;
+    // The (epilogue, LayerNorm) pairs whisper.cpp's decoder requests, and the only ones instantiated:
+    //   (EPI_BIAS, LN)             LN1 + Q|K|V, LN2 + cross Q, the one-token vocabulary head with the final LayerNorm folded in
+    //   (EPI_BIAS, none)           the vocabulary head after the final LayerNorm
+    //   (EPI_BIAS_GELU, LN)        LN3 + fc1 + GELU
+    //   (EPI_BIAS_RESIDUAL, none)  self / cross output projections, fc2 (+ residual)
+    // Any other pair is hipErrorInvalidValue.
+    if (a.epi == EPI_BIAS_GELU ? !ln : a.epi == EPI_BIAS_RESIDUAL ? ln : a.epi != EPI_BIAS) return hipErrorInvalidValue;
+#define KJ_PAIRS(LAUNCH)                                                                                                         \
+    do {                                                                                                                         \
+        if (a.epi == EPI_BIAS_GELU) LAUNCH(EPI_BIAS_GELU, true);                                                                 \
+        else if (a.epi == EPI_BIAS_RESIDUAL) LAUNCH(EPI_BIAS_RESIDUAL, false);                                                   \
+        else if (ln) LAUNCH(EPI_BIAS, true);                                                                                     \
+        else LAUNCH(EPI_BIAS, false);                                                                                            \
+    } while (0)
     const dim3 grid((unsigned)((a.n_out + 3) / 4));
+    // one row of 512 or 2048 floats (the Whisper-base decoder's widths): the variant with every request issued up front
+    const int kch = a.k / 256;
+    if (a.rows == 1 && a.k % 256 == 0 && (kch == 2 || kch == 8) && (!ln || a.beta) &&
+        (!ln || ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0)) {
+        const GemvEmbed emb{a.embed_ids, a.embed_word, a.embed_pos_table, a.embed_vocab, a.embed_max_pos, a.embed_pos, a.embed_pos_ptr,
+                            a.embed_scale};
+#define KJ_FAST2(EPI, LN, KCH, EMB)                                                                                                \
+    hipLaunchKernelGGL((gemv_row_fast_kernel<EPI, LN, KCH, EMB>), grid, dim3(256), 0, stream, a.X, a.gamma, a.beta, a.eps, a.W, a.bias, \
+                       a.R, a.n_out, a.seg, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.x_raw_out, a.x_norm_out, emb)
+#define KJ_FAST(EPI, LN)                                                                                                           \
+    do {                                                                                                                           \
+        if (kch == 2) KJ_FAST2(EPI, LN, 2, false);                                                                                 \
+        else KJ_FAST2(EPI, LN, 8, false);                                                                                          \
+    } while (0)
+        if (a.embed_ids) {  // the first projection of a one-token step builds its input row itself (LN + Q | K | V, 512-float rows)
+            if (!(ln && a.epi == EPI_BIAS && kch == 2)) return hipErrorInvalidValue;
+            KJ_FAST2(EPI_BIAS, true, 2, true);
+        } else {
+            KJ_PAIRS(KJ_FAST);
+        }
+#undef KJ_FAST
+#undef KJ_FAST2
+        return hipGetLastError();
+    }
     const size_t lds = (size_t)a.rows * a.k * sizeof(float);
-    const bool staged = a.rows >= 2 && lds <= 64 * 1024 && g_gemv_rows_variant == 0;
+    const bool staged = a.rows >= 2 && lds <= 64 * 1024;
     const bool staged_fast = staged && a.k % 256 == 0 && (a.k / 256 == 2 || a.k / 256 == 8) && (!a.gamma || a.beta) &&
                              ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0;
     if (staged_fast && !a.gamma && a.epi == EPI_BIAS && a.seg <= 0 && a.n_out >= 8192 && a.k == 512) {  // the vocabulary head
@@ -1176,8 +1099,7 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
     do {                                                                                                                         \
         auto kern = gemv_rows_lds_fast_kernel<EPI, LN, KCH>;                                                                     \
         if (lds > 48 * 1024) {                                                                                                   \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                     (int)lds);                                                                  \
+            const hipError_t e = allow_dynamic_lds(kern, lds);                                                                   \
             if (e != hipSuccess) return e;                                                                                       \
         }                                                                                                                        \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a.X, a.ldx, a.rows, a.gamma, a.beta, a.eps, a.W, a.bias, a.R, a.ldr, \
@@ -1191,8 +1113,7 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
         } else if (staged) {                                                                                                     \
             auto kern = gemv_rows_lds_kernel<EPI, LN>;                                                                           \
             if (lds > 48 * 1024) {                                                                                               \
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
+                const hipError_t e = allow_dynamic_lds(kern, lds);                                                               \
                 if (e != hipSuccess) return e;                                                                                   \
             }                                                                                                                    \
             hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a.X, a.ldx, a.rows, a.gamma, a.beta, a.eps, a.W, a.bias, a.R, \
@@ -1203,94 +1124,17 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
                                a.row_off, a.row_off_ptr);                                                                        \
         }                                                                                                                        \
     } while (0)
-    const bool ln = a.gamma != nullptr;
-    // one row of 512 or 2048 floats (the Whisper-base decoder's widths): the variant with every request issued up front
-    const int kch = a.k / 256;
-    if (a.rows == 1 && a.k % 256 == 0 && (kch == 2 || kch == 8) && g_gemv_rows_variant == 0 && (!ln || a.beta) &&
-        (!ln || ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0)) {
-        const GemvEmbed emb{a.embed_ids, a.embed_word, a.embed_pos_table, a.embed_vocab, a.embed_max_pos, a.embed_pos, a.embed_pos_ptr,
-                            a.embed_scale};
-        int cols = 1, waves = 4;   // (columns per wave, waves per workgroup)
-#ifdef KJARNI_TUNING
-        if (const char* e = getenv("KJARNI_HIP_GEMV_COLS")) cols = atoi(e);
-        if (const char* e = getenv("KJARNI_HIP_GEMV_WAVES")) waves = atoi(e);
-        if ((cols != 1 && cols != 2 && cols != 4) || (waves != 1 && waves != 4)) return hipErrorInvalidValue;
-#endif
-        const dim3 fgrid((unsigned)((a.n_out + (int64_t)cols * waves - 1) / ((int64_t)cols * waves))), fblock(64 * waves);
-#define KJ_FAST4(EPI, LN, KCH, EMB, COLS, WAVES)                                                                                   \
-    hipLaunchKernelGGL((gemv_row_fast_kernel<EPI, LN, KCH, EMB, COLS, WAVES>), fgrid, fblock, 0, stream, a.X, a.gamma, a.beta, a.eps, \
-                       a.W, a.bias, a.R, a.n_out, a.seg, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.x_raw_out,         \
-                       a.x_norm_out, emb)
-#ifdef KJARNI_TUNING
-#define KJ_FAST3(EPI, LN, KCH, EMB)                                                                                                \
-    do {                                                                                                                           \
-        if (waves == 4) {                                                                                                          \
-            if (cols == 1) KJ_FAST4(EPI, LN, KCH, EMB, 1, 4);                                                                      \
-            else if (cols == 2) KJ_FAST4(EPI, LN, KCH, EMB, 2, 4);                                                                 \
-            else KJ_FAST4(EPI, LN, KCH, EMB, 4, 4);                                                                                \
-        } else {                                                                                                                   \
-            if (cols == 1) KJ_FAST4(EPI, LN, KCH, EMB, 1, 1);                                                                      \
-            else if (cols == 2) KJ_FAST4(EPI, LN, KCH, EMB, 2, 1);                                                                 \
-            else KJ_FAST4(EPI, LN, KCH, EMB, 4, 1);                                                                                \
-        }                                                                                                                          \
-    } while (0)
-#else
-#define KJ_FAST3(EPI, LN, KCH, EMB) KJ_FAST4(EPI, LN, KCH, EMB, 1, 4)
-#endif
-        if (a.embed_ids) {  // the first projection of a one-token step builds its input row itself (LN + Q | K | V, 512-float rows)
-            if (!(ln && a.epi == EPI_BIAS && kch == 2)) return hipErrorInvalidValue;
-            KJ_FAST3(EPI_BIAS, true, 2, true);
-            return hipGetLastError();
-        }
-#define KJ_FAST(EPI, LN)                                                                                                          \
-    do {                                                                                                                          \
-        if (kch == 2) KJ_FAST3(EPI, LN, 2, false);                                                                                \
-        else KJ_FAST3(EPI, LN, 8, false);                                                                                         \
-    } while (0)
-        switch (a.epi) {
-        case EPI_BIAS:
-            if (ln) KJ_FAST(EPI_BIAS, true);
-            else KJ_FAST(EPI_BIAS, false);
-            break;
-        case EPI_BIAS_GELU:
-            if (ln) KJ_FAST(EPI_BIAS_GELU, true);
-            else KJ_FAST(EPI_BIAS_GELU, false);
-            break;
-        case EPI_BIAS_RESIDUAL:
-            if (ln) KJ_FAST(EPI_BIAS_RESIDUAL, true);
-            else KJ_FAST(EPI_BIAS_RESIDUAL, false);
-            break;
-        default: return hipErrorInvalidValue;
-        }
-#undef KJ_FAST
-#undef KJ_FAST3
-#undef KJ_FAST4
-        return hipGetLastError();
-    }
-    switch (a.epi) {
-    case EPI_BIAS:
-        if (ln) KJ_GEMV(EPI_BIAS, true);
-        else KJ_GEMV(EPI_BIAS, false);
-        break;
-    case EPI_BIAS_GELU:
-        if (ln) KJ_GEMV(EPI_BIAS_GELU, true);
-        else KJ_GEMV(EPI_BIAS_GELU, false);
-        break;
-    case EPI_BIAS_RESIDUAL:
-        if (ln) KJ_GEMV(EPI_BIAS_RESIDUAL, true);
-        else KJ_GEMV(EPI_BIAS_RESIDUAL, false);
-        break;
-    default: return hipErrorInvalidValue;
-    }
+    KJ_PAIRS(KJ_GEMV);
 #undef KJ_GEMV
 #undef KJ_STAGED_FAST
+#undef KJ_PAIRS
     return hipGetLastError();
 }
 
 bool gemv_row_att_supported(int k, int splits, int head_dim)
 {
     return (k == 512 || k == 2048) && splits >= 1 && splits <= ATT_MERGE_MAX_SPLITS && head_dim >= 4 && (head_dim & 3) == 0 &&
-           k % head_dim == 0 && g_gemv_rows_variant == 0;
+           k % head_dim == 0;
 }
 
 hipError_t launch_gemv_row_att(const float* slabs, int splits, int head_dim, const float* W, const float* bias, const float* R, int n_out,

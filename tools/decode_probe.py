@@ -1,5 +1,5 @@
-"""ms per greedy token of the two decode paths, for same-box A/Bs (tuning build env switches): best of 5 runs each.
-usage: [KJARNI_FFI_LIB=.../libkjarni_ffi_tuning.so KJARNI_HIP_WHISPER_NO_FOLD=1|embed|head KJARNI_HIP_LLM_NO_FOLD=1] python tools/decode_probe.py whisper|llm [repetitions, default 5]"""
+"""ms per greedy token of the two decode paths, for same-box A/Bs of two builds: best of 5 runs each.
+usage: [KJARNI_FFI_LIB=.../libkjarni_ffi.so] python tools/decode_probe.py whisper|llm [repetitions, default 5]"""
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -9,7 +9,7 @@ from tests import synth
 
 which = sys.argv[1]
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("KJARNI_HIP_")) or "default"
+tag = os.environ.get("KJARNI_FFI_LIB", "default")
 with tempfile.TemporaryDirectory() as tmp:
     if which == "whisper":
         synth.whisper_model(tmp, seed=0, base=True)
