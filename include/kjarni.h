@@ -440,6 +440,11 @@ KjarniErrorCode kjarni_generator_generate(KjarniGenerator* generator, const char
 /* One callback per generated token; the cancel token is looked at before each callback. */
 KjarniErrorCode kjarni_generator_stream(KjarniGenerator* generator, const char* prompt, const KjarniGenerationConfig* gen_config,
                                         KjarniStreamCallbackFn callback, void* user_data, const KjarniCancelToken* cancel_token);
+/* kjarni_generator_generate for every prompt, up to 8 of them decoded in lock step (not in the reference): each prompt is
+ * resolved, BOS-prefixed and decoded exactly as kjarni_generator_generate does; out->strings[i] is prompt i's text.  n == 0:
+ * OK with an empty array.  Free with kjarni_string_array_free. */
+KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* generator, const char* const* prompts, size_t n,
+                                                const KjarniGenerationConfig* gen_config, KjarniStringArray* out);
 /* Without a buffer: the name's byte length; with one: bytes copied, NUL excluded. */
 size_t kjarni_generator_model_name(const KjarniGenerator* generator, char* buf, size_t buf_len);
 size_t kjarni_generator_context_size(const KjarniGenerator* generator);  /* the model's n_ctx / max_position_embeddings */

@@ -545,6 +545,39 @@ KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* decoder, const uin
                                             float repetition_penalty, int32_t no_repeat_ngram_size, KjarniTokenCallbackFn on_token,
                                             void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out);
 
+/* ---- lanes: up to 8 prompts decoded in lock step (NOT in the reference: it generates one sequence at a time) ----
+ * A lane is one sequence with its own KV cache and position; at most 8 lanes run per step, a call may carry any number of
+ * prompts, and a lane that finishes takes the next waiting prompt.
+ *
+ * kjarni_hip_decoder_generate_batch: prompt i is prompt_ids[offsets[i] .. offsets[i + 1]) (n + 1 offsets) and generates up to
+ * max_new_tokens[i] tokens under the rules of kjarni_hip_decoder_generate (stop token not emitted, context limit); the ids
+ * are the ones that call gives for the prompt alone.  lanes: 1..8, 0 = 8.  lane_context: rows of each lane's cache,
+ * <= 0 = the decoder's context (a lane stops where its cache is full).  on_token (may be NULL) gets the prompt's index and is
+ * called in step order, lane order within a step; false ends that prompt only.  Prompt i's ids go to
+ * ids_out[i * capacity ..], n_out[i] = tokens generated (may exceed capacity).  n == 0: OK, nothing written.  lanes outside
+ * 0..8, or a prompt longer than a lane (the message names its index): INVALID_CONFIG before any GPU work. */
+typedef bool (*KjarniBatchTokenCallbackFn)(size_t prompt_index, KjarniToken token, void* user_data);
+KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder* decoder, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                  const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size,
+                                                  int32_t lanes, int32_t lane_context, KjarniBatchTokenCallbackFn on_token, void* user_data,
+                                                  uint32_t* ids_out, size_t capacity, size_t* n_out);
+/* Test hooks (as kjarni_hip_decoder_forward / _kv_rows): empty lane caches for `lanes` lanes; a prompt into one lane; one
+ * lock-step step over ids[lanes] for the lanes with live[lane] != 0 (NULL: all; a frozen lane's cache is neither read nor
+ * written, its output rows are unspecified) -> final-normed hidden rows [lanes, hidden] and logits [lanes, vocab] (either
+ * may be NULL); a lane's cache length (-1: no such lane) and rows; the lanes' capacity; how many projections of lane steps
+ * took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel since load. */
+KjarniErrorCode kjarni_hip_decoder_lanes_begin(KjarniHipDecoder* decoder, int32_t lanes, int32_t lane_context);
+KjarniErrorCode kjarni_hip_decoder_lane_prefill(KjarniHipDecoder* decoder, int32_t lane, const uint32_t* ids, int32_t n);
+KjarniErrorCode kjarni_hip_decoder_lanes_step(KjarniHipDecoder* decoder, const uint32_t* ids, const int32_t* live, float* hidden_out,
+                                              float* logits_out);
+int32_t kjarni_hip_decoder_lane_cache_len(const KjarniHipDecoder* decoder, int32_t lane);
+int32_t kjarni_hip_decoder_lane_capacity(const KjarniHipDecoder* decoder);
+KjarniErrorCode kjarni_hip_decoder_lane_kv_rows(const KjarniHipDecoder* decoder, int32_t lane, int32_t layer, int32_t first, int32_t rows,
+                                                float* k_out, float* v_out);
+void kjarni_hip_decoder_lane_gemv_calls(const KjarniHipDecoder* decoder, uint64_t* streamed, uint64_t* fallback);
+/* The lane count kjarni_generator_generate_batch runs with (1..8, 0 = 8, the default). */
+KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* generator, int32_t lanes);
+
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */
 KjarniErrorCode kjarni_hip_malloc(int32_t device, size_t bytes, void** out_dev);
 KjarniErrorCode kjarni_hip_free(int32_t device, void* ptr_dev);

@@ -190,6 +190,7 @@ class KjarniToken(Structure):
 
 
 KjarniTokenCallbackFn = C.CFUNCTYPE(C.c_bool, KjarniToken, c_void_p)
+KjarniBatchTokenCallbackFn = C.CFUNCTYPE(C.c_bool, c_size_t, KjarniToken, c_void_p)
 
 
 class KjarniTranscriberConfig(Structure):
@@ -422,6 +423,18 @@ SIGNATURES = {
     "kjarni_hip_decoder_forward": (c_int32, [c_void_p, _u32p, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_generate": (c_int32, [c_void_p, _u32p, c_size_t, c_size_t, c_float, c_int32, KjarniTokenCallbackFn, c_void_p,
                                               _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_decoder_generate_batch": (c_int32, [c_void_p, _u32p, POINTER(c_size_t), c_size_t, POINTER(c_size_t), c_float, c_int32, c_int32,
+                                                    c_int32, KjarniBatchTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_decoder_lanes_begin": (c_int32, [c_void_p, c_int32, c_int32]),
+    "kjarni_hip_decoder_lane_prefill": (c_int32, [c_void_p, c_int32, _u32p, c_int32]),
+    "kjarni_hip_decoder_lanes_step": (c_int32, [c_void_p, _u32p, POINTER(c_int32), _f32p, _f32p]),
+    "kjarni_hip_decoder_lane_cache_len": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_lane_capacity": (c_int32, [c_void_p]),
+    "kjarni_hip_decoder_lane_kv_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p]),
+    "kjarni_hip_decoder_lane_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_generator_set_lanes": (c_int32, [c_void_p, c_int32]),
+    "kjarni_generator_generate_batch": (c_int32, [c_void_p, POINTER(c_char_p), c_size_t, POINTER(KjarniGenerationConfig),
+                                                  POINTER(KjarniStringArray)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),
     "kjarni_collect_files": (c_int32, [POINTER(KjarniIndexerConfig), POINTER(c_char_p), c_size_t,
                                        POINTER(KjarniStringArray)]),

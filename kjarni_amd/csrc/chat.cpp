@@ -321,17 +321,15 @@ std::vector<uint32_t> encode_prompt(const BpeTokenizer& tok, const LlmConfig& cf
     return tokens;
 }
 
-// The text side of run_generation_loop shared by Chat and Generator: the resolved config becomes the loop's options, and
-// every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
-std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
-                                const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text)
+// The resolved config as the token loop's options (generator.rs:243-246: max_len from max_new_tokens or max_length, capped
+// at the model's context).
+GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, const GenerationConfig& config,
+                                        const std::vector<uint32_t>& stop_ids, UniformRng& rng)
 {
-    if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     const size_t context_size = (size_t)model.config().max_pos;
     GenerateOptions opt;
-    opt.max_new_tokens = config.max_new_tokens.has ? config.max_new_tokens.value
-                                                   : (config.max_length > tokens.size() ? config.max_length - tokens.size() : 0);
-    opt.max_len = config.max_new_tokens.has ? tokens.size() + config.max_new_tokens.value : config.max_length;
+    opt.max_new_tokens = config.max_new_tokens.has ? config.max_new_tokens.value : (config.max_length > n_tokens ? config.max_length - n_tokens : 0);
+    opt.max_len = config.max_new_tokens.has ? n_tokens + config.max_new_tokens.value : config.max_length;
     opt.max_len = std::min(opt.max_len, context_size);
     opt.repetition_penalty = config.repetition_penalty;
     opt.no_repeat_ngram = (int)config.no_repeat_ngram_size;
@@ -344,6 +342,16 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
         opt.sampling.min_p = config.min_p.has ? config.min_p.value : -1.0f;
         opt.uniform = [&rng] { return rng.next(); };
     }
+    return opt;
+}
+
+// The text side of run_generation_loop shared by Chat and Generator: the resolved config becomes the loop's options, and
+// every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
+std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
+                                const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text)
+{
+    if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
+    const GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
     std::string text;
     std::vector<uint32_t> prompt_tokens = tokens;
     if ((int)prompt_tokens.size() > model.context()) prompt_tokens.resize((size_t)model.context());
@@ -556,6 +564,34 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text);
+}
+
+
+// Generator::run for every prompt, `lanes` of them decoded in lock step (LlmModel::generate_lanes): each prompt is encoded
+// (BOS rule), capped and decoded exactly as run() does.  A sampled request draws from a generator of its own, seeded from
+// the handle's at call start -- one draw per request, in request order -- so a seeded batch does not depend on the lane count.
+std::vector<std::string> Generator::generate_batch(const std::vector<std::string>& prompts, const GenerationOverrides& runtime, int lanes)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    const GenerationConfig config = resolve(runtime);
+    if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
+    std::vector<UniformRng> rngs;
+    rngs.reserve(prompts.size());
+    std::vector<LaneRequest> reqs(prompts.size());
+    for (size_t i = 0; i < prompts.size(); ++i) {
+        rngs.emplace_back(config.strategy == Strategy::Sample ? (uint64_t)(rng_.next() * 16777216.0f) + 1 : 1);
+        std::vector<uint32_t> tokens = encode(prompts[i], config);
+        if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
+        reqs[i].options = text_generation_options(*model_, tokens.size(), config, stop_ids_, rngs[i]);
+        if ((int)tokens.size() > model_->context()) tokens.resize((size_t)model_->context());
+        reqs[i].prompt = std::move(tokens);
+    }
+    std::vector<std::string> texts(prompts.size());
+    model_->generate_lanes(reqs, lanes, 0, [&](size_t r, uint32_t id) {
+        texts[r] += tokenizer_.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
+        return true;
+    });
+    return texts;
 }
 
 }  // namespace kjarni

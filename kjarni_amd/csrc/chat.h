@@ -142,6 +142,10 @@ public:
         return run(prompt, runtime, on_text);
     }
     void reseed(uint64_t seed) { rng_.reseed(seed); }
+    // generate() for every prompt, up to `lanes` (1..8, 0 = 8) of them decoded in lock step; texts in prompt order.
+    std::vector<std::string> generate_batch(const std::vector<std::string>& prompts, const GenerationOverrides& runtime, int lanes);
+    int batch_lanes() const { return batch_lanes_; }
+    void set_batch_lanes(int lanes) { batch_lanes_ = lanes; }  // what kjarni_generator_generate_batch runs with (0 = 8)
 
 private:
     Generator() = default;
@@ -154,6 +158,7 @@ private:
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
     std::mutex mutex_;
+    int batch_lanes_ = 0;
 };
 
 // str::trim (Unicode White_Space at both ends).

@@ -35,6 +35,18 @@ public:
         left_ -= bytes;
         return p;
     }
+    // An allocation of its own whatever its size, which free_own() returns to the device (buffers that are replaced by larger
+    // ones during the model's life: the lane caches).
+    void* alloc_own(size_t bytes) { return fresh(((bytes + 255) & ~(size_t)255) ? ((bytes + 255) & ~(size_t)255) : 256); }
+    void free_own(void* p)
+    {
+        for (size_t i = 0; i < blocks_.size(); ++i)
+            if (blocks_[i] == p) {
+                (void)hipFree(p);
+                blocks_.erase(blocks_.begin() + (long)i);
+                return;
+            }
+    }
     void release()
     {
         for (void* p : blocks_) (void)hipFree(p);

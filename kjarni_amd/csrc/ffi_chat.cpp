@@ -352,6 +352,36 @@ KJARNI_EXPORT KjarniErrorCode kjarni_generator_stream(KjarniGenerator* gen, cons
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* gen, const char* const* prompts, size_t n,
+                                                              const KjarniGenerationConfig* gen_config, KjarniStringArray* out)
+{
+    if (!gen || !out || (n && !prompts)) return KJARNI_ERROR_NULL_POINTER;
+    out->strings = nullptr;
+    out->len = 0;
+    std::vector<std::string> texts(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!prompts[i]) return KJARNI_ERROR_NULL_POINTER;
+        if (!valid_utf8(prompts[i])) return KJARNI_ERROR_INVALID_UTF8;
+        texts[i] = prompts[i];
+    }
+    if (n == 0) return KJARNI_OK;
+    return generation_guarded([&] {
+        const std::vector<std::string> got =
+            gen->inner->generate_batch(texts, gen_config ? to_overrides(*gen_config) : GenerationOverrides(), gen->inner->batch_lanes());
+        char** arr = static_cast<char**>(std::calloc(n, sizeof(char*)));
+        if (!arr) throw std::bad_alloc();
+        try {
+            for (size_t i = 0; i < n; ++i) arr[i] = response_cstr(got[i]);
+        } catch (...) {
+            for (size_t i = 0; i < n; ++i) std::free(arr[i]);
+            std::free(arr);
+            throw;
+        }
+        out->strings = arr;
+        out->len = n;
+    });
+}
+
 KJARNI_EXPORT size_t kjarni_generator_model_name(const KjarniGenerator* gen, char* buf, size_t buf_len)
 {
     if (!gen) return 0;
@@ -638,6 +668,17 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_encode(const KjarniGenerator*
 KJARNI_EXPORT void kjarni_hip_generator_seed(KjarniGenerator* gen, uint64_t seed)
 {
     if (gen) gen->inner->reseed(seed);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* gen, int32_t lanes)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    if (lanes < 0 || lanes > LlmModel::kLanes) {
+        set_last_error("lanes must be 1..8 (0 = 8)");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    gen->inner->set_batch_lanes(lanes);
+    return KJARNI_OK;
 }
 
 KJARNI_EXPORT void kjarni_hip_generator_set_device_sampling(KjarniGenerator* gen, int32_t on)

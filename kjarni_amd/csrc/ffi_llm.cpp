@@ -115,6 +115,114 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, c
     });
 }
 
+// ---- lanes: up to 8 prompts decoded in lock step -------------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                                const size_t* max_new_tokens, float repetition_penalty,
+                                                                int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                                KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                size_t capacity, size_t* n_out)
+{
+    if (!d) return KJARNI_ERROR_NULL_POINTER;
+    if (n == 0) return KJARNI_OK;  // nothing to do, nothing written
+    if (!offsets || !max_new_tokens || !n_out || (capacity && !ids_out) || (offsets[n] && !prompt_ids)) return KJARNI_ERROR_NULL_POINTER;
+    for (size_t i = 0; i < n; ++i) n_out[i] = 0;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (lanes < 0 || lanes > LlmModel::kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+        const int cap = lane_context <= 0 ? d->model->context() : std::min(d->model->context(), (int)lane_context);
+        std::vector<LaneRequest> reqs(n);
+        for (size_t i = 0; i < n; ++i) {
+            if (offsets[i + 1] < offsets[i]) throw InvalidConfig("prompt offsets must not decrease");
+            if (offsets[i + 1] - offsets[i] > (size_t)cap)  // before any GPU work
+                throw InvalidConfig("prompt " + std::to_string(i) + " (" + std::to_string(offsets[i + 1] - offsets[i]) +
+                                    " tokens) does not fit the lane capacity of " + std::to_string(cap) + " tokens");
+            reqs[i].prompt.assign(prompt_ids + offsets[i], prompt_ids + offsets[i + 1]);
+            reqs[i].options.max_new_tokens = max_new_tokens[i];
+            reqs[i].options.repetition_penalty = repetition_penalty;
+            reqs[i].options.no_repeat_ngram = no_repeat_ngram_size;
+        }
+        std::function<bool(size_t, uint32_t)> cb;
+        if (on_token)
+            cb = [&](size_t prompt, uint32_t id) {
+                KjarniToken t;
+                t.text = nullptr;  // token-level API: no tokenizer behind it
+                t.token_id = id;
+                t.is_special = false;
+                return on_token(prompt, t, user_data);
+            };
+        const std::vector<std::vector<uint32_t>> got = d->model->generate_lanes(reqs, lanes, lane_context, cb);
+        for (size_t i = 0; i < n; ++i) {
+            n_out[i] = got[i].size();
+            if (capacity) std::memcpy(ids_out + i * capacity, got[i].data(), std::min(capacity, got[i].size()) * sizeof(uint32_t));
+        }
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lanes_begin(KjarniHipDecoder* d, int32_t lanes, int32_t lane_context)
+{
+    if (!d) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (lanes < 0 || lanes > LlmModel::kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+        d->model->lanes_begin(lanes, lane_context);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_prefill(KjarniHipDecoder* d, int32_t lane, const uint32_t* ids, int32_t n)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->lane_prefill(lane, ids, n);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lanes_step(KjarniHipDecoder* d, const uint32_t* ids, const int32_t* live, float* hidden_out,
+                                                            float* logits_out)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->lanes_step(ids, live, hidden_out, logits_out);
+    });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_lane_cache_len(const KjarniHipDecoder* d, int32_t lane)
+{
+    if (!d) return -1;
+    std::lock_guard<std::mutex> lock(d->mu);
+    try {
+        return d->model->lane_cache_len(lane);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_lane_capacity(const KjarniHipDecoder* d)
+{
+    if (!d) return 0;
+    std::lock_guard<std::mutex> lock(d->mu);
+    return d->model->lane_capacity();
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_kv_rows(const KjarniHipDecoder* d, int32_t lane, int32_t layer, int32_t first, int32_t rows,
+                                                              float* k_out, float* v_out)
+{
+    if (!d || !k_out || !v_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->lane_kv_rows(lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_lane_gemv_calls(const KjarniHipDecoder* d, uint64_t* streamed, uint64_t* fallback)
+{
+    if (streamed) *streamed = d ? d->model->lane_stream_calls() : 0;
+    if (fallback) *fallback = d ? d->model->lane_fallback_calls() : 0;
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* d, char** out)
 {
     if (!d || !out) return KJARNI_ERROR_NULL_POINTER;

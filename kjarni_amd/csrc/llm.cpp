@@ -1,5 +1,6 @@
 #include "host_util.h"
 #include "llm.h"
+#include "ffi_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -139,6 +140,8 @@ LlmModel::~LlmModel()
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (graph_) (void)hipGraphExecDestroy(graph_);
+    for (hipGraphExec_t g : lane_graphs_)
+        if (g) (void)hipGraphExecDestroy(g);
     if (stream_) (void)hipStreamDestroy(stream_);
     arena_.release();
 }
@@ -1056,6 +1059,528 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         produced += steps;
         cache_len_ += (int)steps;
         drain(produced);
+    }
+    return out;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Lanes: up to 8 sequences decoded in lock step.  A lane is one sequence with its own KV cache (lane-major: lane l of a
+// layer sits at base + l * lane_alloc_cap_ * kv) and its own position; token, position, live flag, pick count and stop
+// rules of every lane live on the device (LlmLaneState), so a step is one linear chain of launches on one stream that
+// replays as a captured graph: embed (GPT-2: + wpe[pos[lane]]) -> per layer [norm + Q|K|V into the staging rows -> rotate
+// Q, rotate K and scatter K / V to row pos[lane] of the lane's cache -> ragged attention (pos[lane] + 1 keys) + merge ->
+// o-proj + residual -> norm + gate/up (c_fc + GELU) -> down + residual] -> final norm -> vocabulary head [lanes, vocab] ->
+// lane pick.  Seven launches per layer, two more than the one-token step (which fuses the rotation into the projection and
+// the merge into the o-proj).
+
+void LlmModel::drop_lane_graphs()
+{
+    for (hipGraphExec_t& g : lane_graphs_) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+}
+
+void LlmModel::ensure_lanes(int lanes, int lane_context)
+{
+    if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8");
+    const LlmConfig& c = cfg_;
+    const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
+    const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim);
+    if (lanes > lane_alloc_ || cap > lane_alloc_cap_) {
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        drop_lane_graphs();
+        // everything sized by lanes x rows is one allocation of its own: the caches of every layer, then the pick history and the
+        // processors' history / distinct lists; when the lanes or their rows grow it is replaced and the old one freed
+        const int nl = std::max(lanes, lane_alloc_), nc = std::max(cap, lane_alloc_cap_);
+        const size_t per_cache = ((size_t)nl * nc * kv + 63) & ~(size_t)63, stride = (size_t)nc + 16;
+        const size_t floats = 2 * layers_.size() * per_cache + 3 * (size_t)kLanes * stride;
+        void* fresh = arena_.alloc_own(floats * sizeof(float));
+        if (lane_block_) arena_.free_own(lane_block_);
+        lane_block_ = fresh;
+        float* at = static_cast<float*>(fresh);
+        lane_k_.assign(layers_.size(), nullptr);
+        lane_v_.assign(layers_.size(), nullptr);
+        for (size_t i = 0; i < layers_.size(); ++i) {
+            lane_k_[i] = at;
+            lane_v_[i] = at + per_cache;
+            at += 2 * per_cache;
+        }
+        lane_hist_stride_ = (int)stride;
+        lane_hist_ = reinterpret_cast<int32_t*>(at);
+        lane_ptok_ = reinterpret_cast<int32_t*>(at + (size_t)kLanes * stride);
+        lane_pdistinct_ = reinterpret_cast<int32_t*>(at + 2 * (size_t)kLanes * stride);
+        if (!lane_qkv_) {
+            lane_qkv_ = dalloc((size_t)kLanes * (c.hidden + 2 * kv));
+            lane_logits_ = dalloc((size_t)kLanes * c.vocab);
+            lane_state_ = reinterpret_cast<LlmLaneState*>(dalloc((sizeof(LlmLaneState) + 3) / 4));
+            lane_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kLanes));
+            hip_check(hipMemset(lane_best_, 0, sizeof(unsigned long long) * kLanes), "memset");
+            lane_pcounts_ = reinterpret_cast<int*>(dalloc((size_t)kLanes * c.vocab));
+            lane_pndistinct_ = reinterpret_cast<int*>(dalloc(kLanes));
+            lane_host_ = std::make_unique<LlmLaneState>();
+        }
+        lane_alloc_ = nl;
+        lane_alloc_cap_ = nc;
+    }
+    if (cap != lane_cap_) drop_lane_graphs();  // (the capacity is an argument of the captured launches)
+    lanes_ = lanes;
+    lane_cap_ = cap;
+    std::memset(lane_host_.get(), 0, sizeof(LlmLaneState));
+    std::fill(lane_len_, lane_len_ + kLanes, 0);
+    lane_state_to_device();
+}
+
+void LlmModel::lane_state_to_device()
+{
+    hip_check(hipMemcpyAsync(lane_state_, lane_host_.get(), sizeof(LlmLaneState), hipMemcpyHostToDevice, stream_), "H2D lane state");
+    hip_check(hipStreamSynchronize(stream_), "sync");  // (the mirror is edited again right away)
+}
+
+void LlmModel::lane_state_from_device()
+{
+    hip_check(hipMemcpyAsync(lane_host_.get(), lane_state_, sizeof(LlmLaneState), hipMemcpyDeviceToHost, stream_), "D2H lane state");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+
+void LlmModel::lanes_begin(int lanes, int lane_context)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lanes == 0) lanes = kLanes;
+    ensure_lanes(lanes, lane_context);
+}
+
+// A prompt into one lane, by the prompt routes of forward(): the layers' cache pointers (and the capacity) are pointed at the
+// lane for the duration of the call.  The last position's logits are kept as the lane's logits row.
+void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
+    if (n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
+    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
+    const size_t off = (size_t)lane * lane_alloc_cap_ * kv;
+    std::vector<std::pair<float*, float*>> saved(layers_.size());
+    const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
+    for (size_t i = 0; i < layers_.size(); ++i) {
+        saved[i] = {layers_[i].k_cache, layers_[i].v_cache};
+        layers_[i].k_cache = lane_k_[i] + off;
+        layers_[i].v_cache = lane_v_[i] + off;
+    }
+    cache_len_ = 0;
+    cache_cap_ = lane_cap_;
+    auto restore = [&] {
+        for (size_t i = 0; i < layers_.size(); ++i) {
+            layers_[i].k_cache = saved[i].first;
+            layers_[i].v_cache = saved[i].second;
+        }
+        cache_len_ = saved_len;
+        cache_cap_ = saved_cap;
+        last_rows_ = saved_rows;
+    };
+    try {
+        forward(ids, n);
+        hip_check(hipMemcpyAsync(lane_logits_ + (size_t)lane * cfg_.vocab, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice,
+                                 stream_), "D2D logits");
+        // (forward left the lane's length in pos_: the single-sequence cache's own length goes back)
+        hip_check(hipMemcpyAsync(pos_, &saved_len, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+    } catch (...) {
+        restore();
+        (void)hipMemcpyAsync(pos_, &saved_len, sizeof(int), hipMemcpyHostToDevice, stream_);  // (forward may have left the lane's)
+        (void)hipStreamSynchronize(stream_);
+        throw;
+    }
+    restore();
+    lane_len_[lane] = n;
+}
+
+void LlmModel::lane_gemv(const LlmGemvArgs& a)
+{
+    int streamed = 0;
+    hip_check(launch_llm_gemv_lanes(a, stream_, &streamed), "lane projection");
+    if (streamed) ++lane_stream_calls_;
+    else ++lane_fallback_calls_;
+}
+
+void LlmModel::lane_step(int n)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, I = c.inter;
+    const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = H + 2 * kv;
+    const int64_t stride = (int64_t)lane_alloc_cap_ * kv;
+    const LlmLaneState* st = lane_state_;
+    const uint32_t* toks = reinterpret_cast<const uint32_t*>(st->token);
+    const int wb = bf16_ ? 1 : 0;
+    if (quant_) hip_check(launch_qembed(toks, n, qembed_, h_, s), "embed");
+    else if (gpt2_) hip_check(launch_llm_embed_pos(toks, n, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, h_, s, st->pos), "embed");
+    else hip_check(launch_llm_embed(toks, n, H, c.vocab, embed_, wb, h_, s), "embed");
+    auto q6 = [](const QMat& m) { return m.type == GGML_Q6_K; };
+    auto qsource = [&](QFusedArgs& a, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what) {  // as pass_quant
+        a.k = k; a.rows = n;
+        if (!q8k) {
+            a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = c.eps;
+            return;
+        }
+        hip_check(launch_qprep(X, ldx, n, k, gamma, c.eps, gamma ? xn_ : nullptr, xq_, xd_, s), what);
+        a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
+    };
+    for (size_t li = 0; li < layers_.size(); ++li) {
+        const Layer& L = layers_[li];
+        if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
+            QFusedArgs a;
+            a.mode = QF_PLAIN;
+            qsource(a, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
+            a.W[0] = L.q; a.W[1] = L.k; a.W[2] = L.v;
+            a.seg_jobs[0] = H / 2; a.seg_jobs[1] = kv / 2; a.seg_jobs[2] = kv / 2;
+            a.jobs = H / 2 + kv;
+            a.bias = L.bqkv; a.bias_off[1] = H; a.bias_off[2] = H + kv;
+            a.Y[0] = lane_qkv_; a.Y[1] = lane_qkv_ + H; a.Y[2] = lane_qkv_ + H + kv;
+            a.ldy[0] = a.ldy[1] = a.ldy[2] = ldq;
+            hip_check(launch_qfused(a, s), "norm + qkv");
+        } else {
+            LlmGemvArgs a;
+            a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
+            a.bf16 = wb; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = lane_qkv_; a.ldy0 = ldq;
+            lane_gemv(a);
+        }
+        hip_check(launch_lane_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, cos_, sin_, lane_k_[li], lane_v_[li], stride, lane_cap_, st,
+                                           gpt2_ ? 0 : 1, s), "rotate + scatter");
+        hip_check(launch_decode_attention(lane_qkv_, ldq, n, lane_k_[li], kv, lane_v_[li], kv, lane_cap_, nullptr, lane_cap_, c.heads, d, -1,
+                                          splits_, att_scratch_, ctx_, H, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
+        if (quant_) {
+            QFusedArgs o;
+            qsource(o, ctx_, H, H, nullptr, q6(L.o), "q8k o");
+            o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
+            hip_check(launch_qfused(o, s), "o proj");
+            QFusedArgs g;
+            g.mode = QF_SWIGLU;
+            qsource(g, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
+            g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
+            hip_check(launch_qfused(g, s), "norm + gate/up");
+            QFusedArgs dn;
+            qsource(dn, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
+            dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
+            hip_check(launch_qfused(dn, s), "down proj");
+            continue;
+        }
+        LlmGemvArgs o;
+        o.X = ctx_; o.ldx = H; o.rows = n; o.W = L.wo; o.bf16 = wb; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = H; o.Y0 = h_; o.ldy0 = H;
+        lane_gemv(o);
+        LlmGemvArgs g;
+        g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.bf16 = wb; g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
+        if (gpt2_) {
+            g.beta = L.ln2_b; g.layernorm = 1; g.bias = L.bfc; g.gelu_tanh = 1;
+        } else {
+            g.W2 = L.up; g.swiglu = 1;
+        }
+        lane_gemv(g);
+        LlmGemvArgs dn;
+        dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = wb; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
+        dn.Y0 = h_; dn.ldy0 = H;
+        lane_gemv(dn);
+    }
+    if (gpt2_) hip_check(launch_layernorm(h_, final_norm_, final_norm_b_, c.eps, n, H, last_, s), "ln_f");
+    else hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
+    if (quant_) {
+        qlinear(qhead_, last_, H, n, head_q8k_, lane_logits_, c.vocab, "lm head");
+    } else {
+        LlmGemvArgs lm;
+        lm.X = last_; lm.ldx = H; lm.rows = n; lm.W = lm_head_; lm.bf16 = wb; lm.n_out = c.vocab; lm.k = H; lm.Y0 = lane_logits_; lm.ldy0 = c.vocab;
+        lane_gemv(lm);
+    }
+}
+
+void LlmModel::lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lanes_ < 1) throw std::runtime_error("lanes_begin first");
+    LlmLaneState& h = *lane_host_;
+    for (int l = 0; l < lanes_; ++l) {
+        const bool on = live ? live[l] != 0 : true;
+        if (on && lane_len_[l] >= lane_cap_) throw std::runtime_error("lane " + std::to_string(l) + " is full");
+        h.token[l] = (int32_t)ids[l];
+        h.pos[l] = lane_len_[l];
+        h.live[l] = on ? 1 : 0;
+    }
+    lane_state_to_device();
+    lane_step(lanes_);
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    for (int l = 0; l < lanes_; ++l)
+        if (h.live[l]) lane_len_[l] += 1;
+    if (hidden_out) hip_check(hipMemcpy(hidden_out, last_, (size_t)lanes_ * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
+    if (logits_out)
+        hip_check(hipMemcpy(logits_out, lane_logits_, (size_t)lanes_ * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+}
+
+int LlmModel::lane_cache_len(int lane) const
+{
+    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    return lane_len_[lane];
+}
+
+void LlmModel::lane_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const
+{
+    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > lane_len_[lane] || rows > lane_len_[lane] - first)
+        throw std::runtime_error("cache rows out of range");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
+    const size_t off = ((size_t)lane * lane_alloc_cap_ + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
+    hip_check(hipMemcpy(k_out, lane_k_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+    hip_check(hipMemcpy(v_out, lane_v_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+}
+
+hipGraphExec_t LlmModel::lane_step_graph(int n)
+{
+    if (lane_graphs_[n]) return lane_graphs_[n];
+    hipGraph_t graph = nullptr;
+    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
+    try {
+        lane_step(n);
+        hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_, 1,
+                                   stream_), "lane pick");
+    } catch (...) {
+        (void)hipStreamEndCapture(stream_, &graph);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
+    const hipError_t e = hipGraphInstantiate(&lane_graphs_[n], graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    hip_check(e, "graph instantiate");
+    return lane_graphs_[n];
+}
+
+std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
+                                                            const std::function<bool(size_t, uint32_t)>& on_token)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lanes == 0) lanes = kLanes;
+    if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+    const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
+    bool slow = false;  // some request needs its logits row looked at: processors or sampling
+    for (size_t i = 0; i < reqs.size(); ++i) {  // everything is checked before any GPU work
+        const LaneRequest& r = reqs[i];
+        if (r.prompt.empty()) throw std::runtime_error("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
+        if ((int64_t)r.prompt.size() > cap)
+            throw InvalidConfig("prompt " + std::to_string(i) + " does not fit the lane capacity of " + std::to_string(cap) + " tokens");
+        if (r.options.sample && !r.options.uniform) throw std::runtime_error("sampling needs a uniform source (prompt " + std::to_string(i) + ")");
+        const std::vector<uint32_t>& stops = r.options.stop_ids.empty() ? cfg_.eos_ids : r.options.stop_ids;
+        if ((int)stops.size() > kMaxLaneStops) throw std::runtime_error("more than 16 stop ids (prompt " + std::to_string(i) + ")");
+        slow = slow || r.options.sample || r.options.repetition_penalty != 1.0f || r.options.no_repeat_ngram > 0;
+    }
+    std::vector<std::vector<uint32_t>> out(reqs.size());
+    if (reqs.empty()) return out;
+    const int n = (int)std::min<size_t>((size_t)lanes, reqs.size());
+    ensure_lanes(n, lane_context);
+    LlmLaneState& h = *lane_host_;
+    const size_t vocab = (size_t)cfg_.vocab;
+
+    struct Run {  // the request a lane is working on, with generate()'s bookkeeping
+        int64_t req = -1;
+        std::vector<uint32_t> all;
+        std::vector<uint32_t> stops;
+        size_t context_limit = 0, max_new = 0, seen = 0;
+        bool done = true;
+    };
+    Run run[kLanes];
+    size_t next_req = 0;
+    auto is_stop = [](const Run& r, uint32_t t) { return std::find(r.stops.begin(), r.stops.end(), t) != r.stops.end(); };
+    // generate()'s drain: the token joins the output unless the request is at its limit or the token is a stop id
+    auto take = [&](int l, uint32_t tok) {
+        Run& r = run[l];
+        if (r.done) return;
+        if (r.all.size() >= r.context_limit || is_stop(r, tok)) {
+            r.done = true;
+            return;
+        }
+        r.all.push_back(tok);
+        out[(size_t)r.req].push_back(tok);
+        if ((on_token && !on_token((size_t)r.req, tok)) || out[(size_t)r.req].size() >= r.max_new) r.done = true;
+    };
+    // the next waiting request that has anything to generate goes into lane l (false: none is left); its prompt is prefilled
+    auto start = [&](int l) {
+        Run& r = run[l];
+        while (next_req < reqs.size()) {
+            const size_t i = next_req++;
+            const LaneRequest& q = reqs[i];
+            const GenerateOptions& o = q.options;
+            // generator.rs:243-246 and 309-317, as generate(): stop at the lane's capacity and at max_len
+            const size_t max_len = o.max_len ? o.max_len : q.prompt.size() + o.max_new_tokens;
+            const size_t limit = std::min((size_t)cap, max_len);
+            if (o.max_new_tokens == 0 || q.prompt.size() >= limit) continue;  // nothing to generate
+            r.req = (int64_t)i;
+            r.all = q.prompt;
+            r.stops = o.stop_ids.empty() ? cfg_.eos_ids : o.stop_ids;
+            r.context_limit = limit;
+            r.max_new = o.max_new_tokens;
+            r.seen = 0;
+            r.done = false;
+            lane_prefill(l, q.prompt.data(), (int)q.prompt.size());
+            h.token[l] = 0;
+            h.pos[l] = (int32_t)q.prompt.size();
+            h.live[l] = 1;
+            h.count[l] = 0;
+            h.limit[l] = (int32_t)std::min(r.max_new, limit - q.prompt.size());
+            h.n_stop[l] = (int32_t)r.stops.size();
+            for (size_t e = 0; e < r.stops.size(); ++e) h.stop[l][e] = (int32_t)r.stops[e];
+            return true;
+        }
+        r.req = -1;
+        r.done = true;
+        h.live[l] = 0;
+        return false;
+    };
+    auto any_running = [&] {
+        for (int l = 0; l < n; ++l)
+            if (!run[l].done) return true;
+        return false;
+    };
+
+    if (!slow) {
+        // Greedy without processors: every lane's token, position and live flag stay on the device; one graph replay per step,
+        // the host looks every few steps (generate()'s cadence).  Tokens a lane computed past its stop are discarded.
+        std::vector<int32_t> hist((size_t)lane_hist_stride_);
+        // a lane's first token comes from its prefill's logits row: the lane pick on that row alone
+        auto first_pick = [&](int l) {
+            lane_state_to_device();
+            hip_check(launch_lane_pick(lane_logits_, (int64_t)vocab, (int)vocab, 1, l, lane_best_, lane_state_, lane_hist_, lane_hist_stride_,
+                                       lane_cap_, 0, stream_), "lane pick");
+            lane_state_from_device();
+        };
+        auto drain = [&](size_t steps) {  // step-major, lane order within a step
+            std::vector<std::vector<int32_t>> fresh((size_t)n);
+            for (int l = 0; l < n; ++l) {
+                Run& r = run[l];
+                const size_t have = (size_t)h.count[l];
+                if (r.req < 0 || have <= r.seen) continue;
+                fresh[(size_t)l].resize(have - r.seen);
+                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), lane_hist_ + (size_t)l * lane_hist_stride_ + r.seen,
+                                         (have - r.seen) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
+                r.seen = have;
+            }
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            for (size_t i = 0; i < steps; ++i)
+                for (int l = 0; l < n; ++l)
+                    if (i < fresh[(size_t)l].size()) take(l, (uint32_t)fresh[(size_t)l][i]);
+        };
+        const size_t burst = on_token ? 4 : 16;
+        for (;;) {
+            // a lane that has no request, or whose request ended (on the device, or by the host's rules: a callback said stop),
+            // takes the next waiting one; its first token comes from the prefill's row
+            bool dirty = false;
+            for (int l = 0; l < n; ++l) {
+                Run& r = run[l];
+                if (!r.done && !h.live[l]) r.done = true;
+                if (r.done && h.live[l]) {
+                    h.live[l] = 0;
+                    dirty = true;
+                }
+                while (r.done && next_req < reqs.size()) {
+                    if (!start(l)) break;
+                    first_pick(l);  // (writes the whole state, this pass's edits included)
+                    dirty = false;
+                    lane_len_[l] = h.pos[l];
+                    drain(1);
+                    if (!h.live[l]) r.done = true;
+                }
+            }
+            if (!any_running()) break;
+            if (dirty) lane_state_to_device();
+            hipGraphExec_t exec = lane_step_graph(n);
+            for (size_t i = 0; i < burst; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+            lane_state_from_device();
+            for (int l = 0; l < n; ++l)
+                if (run[l].req >= 0) lane_len_[l] = h.pos[l];
+            drain(burst);
+        }
+        return out;
+    }
+
+    // Processors / sampling: every lane's next token is decided from that lane's logits row -- the processors on the device
+    // with the lane's own history and counts (launch_logits_processors), then the device argmax (four bytes back) or, for a
+    // sampled request, the row to the host and generate()'s full-array sampler with the request's own uniform source.  The
+    // step itself is the same chain of launches, enqueued directly (no graph): correct first, fast later.
+    if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+    std::vector<float> probs;
+    std::vector<uint32_t> ids;
+    auto pstate = [&](int l, int32_t*& tok, int32_t*& distinct, int*& counts, int*& nd) {
+        tok = lane_ptok_ + (size_t)l * lane_hist_stride_;
+        distinct = lane_pdistinct_ + (size_t)l * lane_hist_stride_;
+        counts = lane_pcounts_ + (size_t)l * vocab;
+        nd = lane_pndistinct_ + l;
+    };
+    auto begin_history = [&](int l) {  // the history so far = the prompt
+        const Run& r = run[l];
+        int32_t *tok, *distinct;
+        int *counts, *nd;
+        pstate(l, tok, distinct, counts, nd);
+        hip_check(hipMemsetAsync(counts, 0, vocab * sizeof(int), stream_), "memset counts");
+        hip_check(hipMemsetAsync(nd, 0, sizeof(int), stream_), "memset");
+        hip_check(hipMemcpyAsync(tok, r.all.data(), r.all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+        hip_check(launch_token_counts(tok, (int)r.all.size(), (int)vocab, counts, distinct, nd, stream_), "token counts");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+    };
+    for (int l = 0; l < n; ++l)
+        if (start(l)) begin_history(l);
+    while (any_running()) {
+        for (int l = 0; l < n; ++l) {  // decide, in lane order
+            Run& r = run[l];
+            // (a lane whose request ends takes the next one and decides its first token in the same round, from the prefill's row:
+            // the round's step rewrites every row)
+            while (!r.done) {
+                const GenerateOptions& o = reqs[(size_t)r.req].options;
+                float* row = lane_logits_ + (size_t)l * vocab;
+                int32_t *tok, *distinct;
+                int *counts, *nd;
+                pstate(l, tok, distinct, counts, nd);
+                if (o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0)
+                    hip_check(launch_logits_processors(row, (int)vocab, tok, (int)r.all.size(), counts, distinct, nd, o.repetition_penalty,
+                                                       o.no_repeat_ngram, stream_), "logits processors");
+                uint32_t next;
+                if (o.sample) {
+                    hip_check(hipMemcpyAsync(host_logits_, row, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
+                    hip_check(hipStreamSynchronize(stream_), "sync");
+                    sampling_distribution(host_logits_, vocab, o.sampling, ids, probs);
+                    next = sample_from_distribution(ids, probs, o.uniform(), vocab);
+                    ++tokens_from_logits_;
+                } else {
+                    hip_check(launch_argmax(row, (int)vocab, best_, token_, nullptr, nullptr, nullptr, stream_), "argmax");
+                    int32_t t = 0;
+                    hip_check(hipMemcpyAsync(&t, token_, sizeof(t), hipMemcpyDeviceToHost, stream_), "D2H token");
+                    hip_check(hipStreamSynchronize(stream_), "sync");
+                    next = (uint32_t)t;
+                    ++tokens_from_candidates_;
+                }
+                take(l, next);
+                if (!r.done && r.all.size() >= r.context_limit) r.done = true;
+                if (!r.done) {  // the token is the lane's next input, at the position it took in the sequence
+                    h.token[l] = (int32_t)next;
+                    h.pos[l] = (int32_t)r.all.size() - 1;
+                    h.live[l] = 1;
+                    int32_t* slot = tok + (r.all.size() - 1);
+                    hip_check(hipMemcpyAsync(slot, &h.token[l], sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+                    hip_check(launch_token_counts(slot, 1, (int)vocab, counts, distinct, nd, stream_), "token counts");
+                    hip_check(hipStreamSynchronize(stream_), "sync");
+                    break;
+                }
+                h.live[l] = 0;
+                if (start(l)) begin_history(l);
+            }
+        }
+        bool step = false;
+        for (int l = 0; l < n; ++l) step = step || h.live[l];
+        if (step) {
+            lane_state_to_device();
+            lane_step(n);
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            for (int l = 0; l < n; ++l)
+                if (h.live[l]) lane_len_[l] = h.pos[l] + 1;
+        }
     }
     return out;
 }

@@ -52,6 +52,14 @@ struct GenerateOptions {
     std::function<float()> uniform;  // the draw in [0, 1) for each sampled token
 };
 
+// One request of LlmModel::generate_lanes: a prompt and the options generate() would take for it.
+struct LaneRequest {
+    std::vector<uint32_t> prompt;
+    GenerateOptions options;
+};
+
+struct LlmLaneState;  // llm_kernels.h
+
 class LlmModel {
 public:
     // dir: a safetensors model directory, a `.gguf` file or a directory that holds one (gguf.h: resolve_gguf).
@@ -98,8 +106,40 @@ public:
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
                                    const std::function<bool(uint32_t)>& on_token);
 
+    // ---- lanes: up to kLanes sequences decoded in lock step, each with its own KV cache and position -------------------------
+    static constexpr int kLanes = 8;  // the GEMV kernels are built for <= 8 rows
+    // generate() for every request, `lanes` (1..8, 0 = 8) of them at a time: the prompts are prefilled into lane caches of
+    // min(context(), lane_context) rows (lane_context <= 0: context()) by the prompt routes of forward(), the live lanes then
+    // step together (one captured graph per lane count for greedy requests without processors; requests with a repetition
+    // penalty, an n-gram ban or sampling are decided lane by lane from that lane's logits row, uncaptured), and a lane that
+    // finishes takes the next waiting request.  Returns one id vector per request, in request order: the ids generate() gives
+    // for that request alone.  on_token(request, token) is called in step order, lane order within a step; false ends that
+    // request only.  Throws InvalidConfig (before any GPU work) for lanes outside 0..8 or a prompt longer than a lane.
+    std::vector<std::vector<uint32_t>> generate_lanes(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
+                                                      const std::function<bool(size_t, uint32_t)>& on_token);
+    // Test hooks: lane caches for `lanes` lanes, all empty; a prompt into one lane; one lock-step step over ids[lanes] for the
+    // lanes with live[lane] != 0 (the others are frozen: nothing of theirs is read or written) returning the final-normed
+    // hidden rows [lanes, hidden] and logits [lanes, vocab]; a lane's cache length and rows.
+    void lanes_begin(int lanes, int lane_context);
+    void lane_prefill(int lane, const uint32_t* ids, int n);
+    void lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
+    int lane_cache_len(int lane) const;
+    int lane_capacity() const { return lane_cap_; }
+    void lane_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
+    // Projections of lane steps that took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel
+    // since load (counted when enqueued: a replayed graph counts once, at capture).
+    uint64_t lane_stream_calls() const { return lane_stream_calls_; }
+    uint64_t lane_fallback_calls() const { return lane_fallback_calls_; }
+
 private:
     LlmModel() = default;
+    void ensure_lanes(int lanes, int lane_context);
+    void lane_step(int lanes);                 // enqueue one lock-step step over lanes [0, lanes)
+    void lane_gemv(const struct LlmGemvArgs& a);
+    hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
+    void drop_lane_graphs();
+    void lane_state_to_device();
+    void lane_state_from_device();
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
@@ -165,6 +205,22 @@ private:
     uint64_t tile_gemm_calls_ = 0;
     hipStream_t stream_ = nullptr;
     hipGraphExec_t graph_ = nullptr;
+    // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
+    // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
+    std::vector<float*> lane_k_, lane_v_;
+    void* lane_block_ = nullptr;  // one allocation of its own behind everything sized by lanes x rows, replaced when they grow
+    int lane_alloc_ = 0, lane_alloc_cap_ = 0, lanes_ = 0, lane_cap_ = 0, lane_hist_stride_ = 0;
+    int lane_len_[kLanes] = {};
+    float *lane_qkv_ = nullptr, *lane_logits_ = nullptr;
+    LlmLaneState* lane_state_ = nullptr;
+    std::unique_ptr<LlmLaneState> lane_host_;
+    int32_t* lane_hist_ = nullptr;
+    unsigned long long* lane_best_ = nullptr;
+    // logits processors per lane: history, distinct tokens, counts [lanes][vocab], number of distinct tokens
+    int32_t *lane_ptok_ = nullptr, *lane_pdistinct_ = nullptr;
+    int *lane_pcounts_ = nullptr, *lane_pndistinct_ = nullptr;
+    hipGraphExec_t lane_graphs_[kLanes + 1] = {};
+    uint64_t lane_stream_calls_ = 0, lane_fallback_calls_ = 0;
 };
 
 }  // namespace kjarni

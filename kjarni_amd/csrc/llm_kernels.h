@@ -79,12 +79,41 @@ hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, c
 // GPT-2: out[s] = table[ids[s]] + pos_table[p + s] for n rows, p = *pos_ptr when pos_ptr is non-null (graph replay), else pos;
 // both tables in the weights' dtype, pos_table [max_pos, hidden].
 hipError_t launch_llm_embed_pos(const uint32_t* ids, int n, int hidden, int vocab, const void* table, const void* pos_table, int max_pos,
-                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream);
+                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream,
+                                const int* row_pos = nullptr);  // given (lanes): row s sits at position row_pos[s]
 // In place x = gelu_tanh(x) (activations.rs:62-66) over n floats, n % 4 == 0: the prompt route's c_fc epilogue where the GEMM has none.
 hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream);
 // argmax (last maximum wins); best_scratch: one zero-initialised u64 (re-zeroed by the call); history/count/pos may be null.
 hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* best_scratch, int32_t* out, int32_t* history, int* count,
                          int* pos, hipStream_t stream);
+
+// ---- lanes: up to kMaxLanes independent sequences decoded in lock step (LlmModel::generate_lanes) ------------------------
+constexpr int kMaxLanes = 8, kMaxLaneStops = 16;
+// Everything the next lock-step step needs, on the device (so the step replays as a captured graph); the host reads it back
+// and rewrites it between bursts of steps.
+struct LlmLaneState {
+    int32_t token[kMaxLanes];  // the lane's next input token
+    int32_t pos[kMaxLanes];    // its position = the lane's cache length
+    int32_t live[kMaxLanes];   // 0: frozen (finished, or no prompt) -- the step writes nothing for it
+    int32_t count[kMaxLanes];  // tokens picked for the lane's current request (history entries)
+    int32_t limit[kMaxLanes];  // picks after which the lane is done (max_new_tokens and the context limit)
+    int32_t n_stop[kMaxLanes];
+    int32_t stop[kMaxLanes][kMaxLaneStops];  // picking one of these ends the lane
+};
+// launch_llm_gemv for 2-8 independent rows: the multi-row weight-streaming kernel where llm_gemv_lanes_takes() (k >= 512,
+// 16-byte aligned operands), else launch_llm_gemv's one-wave-per-column kernel; *streamed (may be null) says which ran.
+bool llm_gemv_lanes_takes(const LlmGemvArgs& args);
+hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& args, hipStream_t stream, int* streamed);
+// qkv [lanes, (n_heads + 2 n_kv_heads) * head_dim]: Q rotated in place at state->pos[lane], K rotated (rotate == 0: copied) and V
+// copied to row pos[lane] of cache + lane * lane_stride; frozen lanes and positions >= capacity write nothing.
+hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
+                                    const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
+                                    const LlmLaneState* state, int rotate, hipStream_t stream);
+// Per-lane argmax over rows [first_lane, first_lane + lanes) of logits [kMaxLanes, ld] (last maximum wins) for the live lanes:
+// appended to history[lane, count], count (and pos when `advance`: after a step) + 1, live cleared on a stop id / the limit /
+// a full cache, else token = the pick.  best_scratch: kMaxLanes zero-initialised u64 (re-zeroed by the call).
+hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
+                            LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
 
 // ---- sampled decoding: the O(vocab) part on the device (llm_kernels.hip) ----------------------------------------------
 struct SampleHeader {   // 32 bytes, device memory mirrored to the host per sampled token

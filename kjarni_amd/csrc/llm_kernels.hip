@@ -1817,15 +1817,16 @@ hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, c
 namespace {
 
 // GPT-2 embeddings (gpt2/cpu_decoder.rs:371-376): row s = wte[ids[s]] + wpe[p + s], p = *pos_ptr or pos (an id >= vocab
-// or a position >= max_pos leaves that part zero).
-template <typename WT>
+// or a position >= max_pos leaves that part zero).  ROW_POS (lanes: independent sequences): row s sits at row_pos[s].
+template <typename WT, bool ROW_POS>
 __global__ __launch_bounds__(256) void llm_embed_pos_kernel(const uint32_t* __restrict__ ids, int hidden, int vocab,
                                                             const WT* __restrict__ table, const WT* __restrict__ pos_table, int max_pos,
-                                                            int pos, const int* __restrict__ pos_ptr, float* __restrict__ out)
+                                                            int pos, const int* __restrict__ pos_ptr, float* __restrict__ out,
+                                                            const int* __restrict__ row_pos)
 {
     const int s = blockIdx.x;
     const uint32_t id = ids[s];
-    const int p = (pos_ptr ? *pos_ptr : pos) + s;
+    const int p = ROW_POS ? row_pos[s] : (pos_ptr ? *pos_ptr : pos) + s;
     for (int i = threadIdx.x; i < hidden / 8; i += 256) {
         F8 v, w;
 #pragma unroll
@@ -1856,16 +1857,18 @@ __global__ __launch_bounds__(256) void gelu_tanh_kernel(float* __restrict__ x, s
 }  // namespace
 
 hipError_t launch_llm_embed_pos(const uint32_t* ids, int n, int hidden, int vocab, const void* table, const void* pos_table, int max_pos,
-                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream)
+                                int bf16, int pos, const int* pos_ptr, float* out, hipStream_t stream, const int* row_pos)
 {
     if (hidden & 7) return hipErrorInvalidValue;
     if (n <= 0) return hipSuccess;
-    if (bf16)
-        hipLaunchKernelGGL(llm_embed_pos_kernel<uint16_t>, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,
-                           static_cast<const uint16_t*>(table), static_cast<const uint16_t*>(pos_table), max_pos, pos, pos_ptr, out);
-    else
-        hipLaunchKernelGGL(llm_embed_pos_kernel<float>, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,
-                           static_cast<const float*>(table), static_cast<const float*>(pos_table), max_pos, pos, pos_ptr, out);
+#define KJ_EP(WT, ROW_POS)                                                                                                          \
+    hipLaunchKernelGGL((llm_embed_pos_kernel<WT, ROW_POS>), dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab,            \
+                       static_cast<const WT*>(table), static_cast<const WT*>(pos_table), max_pos, pos, pos_ptr, out, row_pos)
+    if (bf16 && row_pos) KJ_EP(uint16_t, true);
+    else if (bf16) KJ_EP(uint16_t, false);
+    else if (row_pos) KJ_EP(float, true);
+    else KJ_EP(float, false);
+#undef KJ_EP
     return hipGetLastError();
 }
 
@@ -2100,6 +2103,420 @@ hipError_t launch_logits_processors(float* logits, int vocab, const int32_t* tok
     if (no_repeat_ngram > 0 && len + 1 >= no_repeat_ngram && len >= no_repeat_ngram)
         hipLaunchKernelGGL(no_repeat_ngram_kernel, dim3((unsigned)((len - no_repeat_ngram + 1 + 255) / 256)), dim3(256), 0, stream, logits,
                            vocab, tokens, len, no_repeat_ngram);
+    return hipGetLastError();
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Lanes: up to 8 independent sequences decoded in lock step (llm.cpp: LlmModel::lane_step).
+namespace {
+
+// Multi-row weight-streaming GEMV: Y[r, n] = epi(norm?(X[r, :]) . W[n, :] + bias[n]) for 2..8 INDEPENDENT rows, the design of
+// llm_gemv_stream_kernel with every 16-byte weight piece multiplied into all resident rows.
+//
+// LDS scheme (160 KB per CU): the workgroup holds a K-SLICE of every row, [rows][SLICE] f32 with SLICE = CH * 512 (CH = 4:
+// 2 048 columns, 64 KB at 8 rows, two workgroups per CU; CH = 2 serves K = 768 / 3 072 without padded pieces).  K <= SLICE
+// (the Q|K|V, gate/up, c_fc and vocabulary-head stages): the rows are normalised ONCE per workgroup into LDS and the
+// workgroup loops over its batches of columns.  K > SLICE (down projection, K = 8 192 / 14 336; K = 3 072): the slices are
+// staged one after the other and the accumulators of the workgroup's columns stay in registers across them; the grid then
+// covers the columns, so every slice is staged once per workgroup.  Row statistics (RMSNorm / LayerNorm) are taken over the
+// whole row before the first slice: one wave per row.
+// Per (batch, slice) a wave owns CPW columns: CPW x CH (x 2 for f32, x 2 for the SwiGLU pair) non-temporal 16-byte loads
+// per lane, 16 with WIDE, all issued before the first FMA; the slice of the input rows for the next stage is requested
+// BEFORE those weights (the counter retires in order: x must not wait behind the weights) and written to LDS after.  The
+// inner loop is FMAs only: acc[column][row] = fmaf(x, widen(w), acc) -- the arithmetic of llm_gemv_kernel, summed in a
+// different order.  A piece past the end of K reads piece 0 again and meets zeros in LDS.
+constexpr int lanes_cols_per_wave(int ch, int lpp, int nm, bool wide)
+{
+    return !wide ? 1 : (16 / (ch * lpp * nm) < 1 ? 1 : (16 / (ch * lpp * nm) > 4 ? 4 : 16 / (ch * lpp * nm)));
+}
+
+template <typename WT, int EPI, int NORM, int CH, bool WIDE>
+__global__ __launch_bounds__(256) void llm_gemv_lanes_kernel(const float* __restrict__ X, int64_t ldx, int rows,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                             const WT* __restrict__ W, const WT* __restrict__ W2,
+                                                             const float* __restrict__ bias, const float* R, int64_t ldr, int n_out,
+                                                             int k, int seg_q, int seg_kv, float* Y0, int64_t ldy0, float* Y1, float* Y2,
+                                                             int64_t ldy12, int row_off, const int* __restrict__ row_off_ptr)
+{
+    constexpr bool BF16 = sizeof(WT) == 2;
+    constexpr int NM = EPI == LE_SWIGLU ? 2 : 1;
+    constexpr int LPP = BF16 ? 1 : 2;
+    constexpr int CPW = lanes_cols_per_wave(CH, LPP, NM, WIDE);
+    constexpr int SLICE = CH * 512;
+    constexpr int XV = CH / 2;  // f32x4 pieces of one row's slice per thread
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) float lanes_xs[];  // [rows][SLICE]
+    __shared__ float st_mu[LLM_MAX_ROWS], st_sc[LLM_MAX_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ns = (k + SLICE - 1) / SLICE;
+    const int nbatches = (n_out + 4 * CPW - 1) / (4 * CPW);
+
+    f32x4 xv[LLM_MAX_ROWS][XV], gv[XV], bv[XV];
+    auto load_x = [&](int s) {
+#pragma unroll
+        for (int j = 0; j < XV; ++j) {
+            const int col = s * SLICE + (tid + j * 256) * 4;
+            const bool in = col < k;
+            gv[j] = (NORM != NK_NONE && in) ? *reinterpret_cast<const f32x4*>(gamma + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+            bv[j] = (NORM == NK_LN && in) ? *reinterpret_cast<const f32x4*>(beta + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < LLM_MAX_ROWS; ++r)
+                xv[r][j] = (r < rows && in) ? *reinterpret_cast<const f32x4*>(X + r * ldx + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto store_x = [&]() {
+#pragma unroll
+        for (int r = 0; r < LLM_MAX_ROWS; ++r) {
+            if (r < rows) {
+#pragma unroll
+                for (int j = 0; j < XV; ++j) {
+                    f32x4 v = xv[r][j];
+                    if (NORM == NK_RMS) {
+                        const float rms = st_sc[r];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) v[c] = (v[c] / rms) * gv[j][c];
+                    }
+                    if (NORM == NK_LN) {
+                        const float mu = st_mu[r], inv = st_sc[r];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) v[c] = (v[c] - mu) * inv * gv[j][c] + bv[j][c];  // (past K: gamma = beta = 0)
+                    }
+                    *reinterpret_cast<f32x4*>(lanes_xs + r * SLICE + (tid + j * 256) * 4) = v;
+                }
+            }
+        }
+    };
+    u32x4 raw[NM][CPW][CH][LPP];
+    auto issue = [&](int nb, int s) {
+        const int n0 = (nb * 4 + wave) * CPW;
+#pragma unroll
+        for (int m = 0; m < NM; ++m)
+#pragma unroll
+            for (int cc = 0; cc < CPW; ++cc) {
+                const int n = n0 + cc < n_out ? n0 + cc : n_out - 1;
+                const char* row = reinterpret_cast<const char*>((m == 0 ? W : W2) + (int64_t)n * k);
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    int e = s * SLICE + (c * 64 + lane) * 8;
+                    e = e < k ? e : 0;
+#pragma unroll
+                    for (int l = 0; l < LPP; ++l) raw[m][cc][c][l] = load_nt16(row + (size_t)e * sizeof(WT) + l * 16);
+                }
+            }
+    };
+
+    int nb = blockIdx.x, s = 0;
+    load_x(0);
+    issue(nb, 0);
+    // row statistics over the whole row, one wave per row (the loads above are in flight meanwhile)
+    if (NORM != NK_NONE) {
+        const int k8 = k >> 3;
+        for (int r = wave; r < rows; r += 4) {
+            const float* xr = X + r * ldx;
+            float mu = 0.0f, sc;
+            if (NORM == NK_RMS) {
+                float a = 0.0f;
+                for (int i = lane; i < k8; i += 64) {
+                    const F8 x = load8(xr, i);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) a = fmaf(x.v[c], x.v[c], a);
+                }
+                sc = sqrtf(wave_sum(a) / (float)k + eps);  // the rms; the reference divides by it
+            } else {
+                float a = 0.0f;
+                for (int i = lane; i < k8; i += 64) {
+                    const F8 x = load8(xr, i);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) a += x.v[c];
+                }
+                mu = wave_sum(a) / (float)k;
+                float v = 0.0f;
+                for (int i = lane; i < k8; i += 64) {
+                    const F8 x = load8(xr, i);
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) v = fmaf(x.v[c] - mu, x.v[c] - mu, v);
+                }
+                sc = 1.0f / sqrtf(wave_sum(v) / (float)k + eps);  // the inverse standard deviation
+            }
+            if (lane == 0) {
+                st_mu[r] = mu;
+                st_sc[r] = sc;
+            }
+        }
+        __syncthreads();
+    }
+
+    float acc[NM][CPW][LLM_MAX_ROWS];
+#pragma unroll
+    for (int m = 0; m < NM; ++m)
+#pragma unroll
+        for (int cc = 0; cc < CPW; ++cc)
+#pragma unroll
+            for (int r = 0; r < LLM_MAX_ROWS; ++r) acc[m][cc][r] = 0.0f;
+    bool first = true;
+    for (;;) {
+        if (first || ns > 1) {
+            if (!first) __syncthreads();  // every wave is done with the slice in LDS
+            store_x();
+            __syncthreads();
+        }
+        first = false;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+#pragma unroll
+            for (int r = 0; r < LLM_MAX_ROWS; ++r) {
+                if (r < rows) {
+                    const f32x4 xa = *reinterpret_cast<const f32x4*>(lanes_xs + r * SLICE + (c * 64 + lane) * 8);
+                    const f32x4 xb = *reinterpret_cast<const f32x4*>(lanes_xs + r * SLICE + (c * 64 + lane) * 8 + 4);
+#pragma unroll
+                    for (int m = 0; m < NM; ++m)
+#pragma unroll
+                        for (int cc = 0; cc < CPW; ++cc) {
+                            if (BF16) {
+                                acc[m][cc][r] = dot8_bf16(raw[m][cc][c][0], xa, xb, acc[m][cc][r]);
+                            } else {
+                                const f32x4 wa = __builtin_bit_cast(f32x4, raw[m][cc][c][0]);
+                                const f32x4 wb = __builtin_bit_cast(f32x4, raw[m][cc][c][LPP - 1]);
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) acc[m][cc][r] = fmaf(xa[e], wa[e], acc[m][cc][r]);
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) acc[m][cc][r] = fmaf(xb[e], wb[e], acc[m][cc][r]);
+                            }
+                        }
+                }
+            }
+        }
+        // the next (batch, slice): its rows' slice, then its weights, requested before this batch's cross-lane sums and stores
+        int s2 = s + 1, nb2 = nb;
+        if (s2 == ns) {
+            s2 = 0;
+            nb2 = nb + (int)gridDim.x;
+        }
+        const bool more = nb2 < nbatches;
+        if (more) {
+            if (ns > 1) load_x(s2);
+            issue(nb2, s2);
+        }
+        if (s == ns - 1) {
+            const int n0 = (nb * 4 + wave) * CPW;
+#pragma unroll
+            for (int cc = 0; cc < CPW; ++cc) {
+                float mine = 0.0f, mine2 = 0.0f;  // lane r keeps row r's sum
+#pragma unroll
+                for (int r = 0; r < LLM_MAX_ROWS; ++r) {
+                    if (r < rows) {
+                        const float t = wave_sum(acc[0][cc][r]);
+                        mine = lane == r ? t : mine;
+                        if (EPI == LE_SWIGLU) {
+                            const float t2 = wave_sum(acc[NM - 1][cc][r]);
+                            mine2 = lane == r ? t2 : mine2;
+                        }
+                    }
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) acc[m][cc][r] = 0.0f;
+                }
+                const int n = n0 + cc;
+                if (lane < rows && n < n_out) {
+                    float v = mine + (bias ? bias[n] : 0.0f);
+                    if (EPI == LE_SWIGLU) v = (v / (1.0f + expf(-v))) * mine2;  // silu(gate) * up
+                    if (EPI == LE_GELU_TANH) v = gelu_tanh(v);
+                    if (EPI == LE_RESIDUAL) v += R[lane * ldr + n];
+                    int which = 0;
+                    int64_t col = n;
+                    if (seg_q > 0 && n >= seg_q) {
+                        which = 1 + (n - seg_q) / seg_kv;
+                        col = (n - seg_q) - (int64_t)(which - 1) * seg_kv;
+                    }
+                    float* Y = which == 0 ? Y0 : (which == 1 ? Y1 : Y2);
+                    const int64_t ldy = which == 0 ? ldy0 : ldy12;
+                    const int64_t r0 = which == 0 ? 0 : (row_off_ptr ? *row_off_ptr : row_off);
+                    Y[(r0 + lane) * ldy + col] = v;
+                }
+            }
+        }
+        if (!more) break;
+        s = s2;
+        nb = nb2;
+    }
+}
+
+// Lane rotate-and-scatter: row `lane` of the staging buffer [lanes, H + 2 kv] holds Q | K | V of that lane's new token at
+// position pos[lane].  Q is rotated in place (rope/mod.rs:156-176, pairs (i, i + d/2)), K is rotated into row pos[lane] of the
+// lane's cache and V copied there; rotate == 0 (GPT-2): K and V are copied.  A lane that is not live, or whose position is
+// not a row of its cache (a lane stopped at its context limit has pos == capacity), writes nothing.
+__global__ __launch_bounds__(256) void lane_rope_scatter_kernel(float* __restrict__ qkv, int64_t ld, int n_heads, int n_kv_heads,
+                                                                int head_dim, const float* __restrict__ cos_t,
+                                                                const float* __restrict__ sin_t, float* __restrict__ Kc,
+                                                                float* __restrict__ Vc, int64_t lane_stride, int capacity,
+                                                                const int* __restrict__ pos, const int* __restrict__ live, int rotate)
+{
+    const int lane = blockIdx.x;
+    if (!live[lane]) return;
+    const int p = pos[lane];
+    if (p < 0 || p >= capacity) return;
+    const int half = head_dim >> 1, H = n_heads * head_dim, kv = n_kv_heads * head_dim;
+    float* row = qkv + (int64_t)lane * ld;
+    float* kdst = Kc + (int64_t)lane * lane_stride + (int64_t)p * kv;
+    float* vdst = Vc + (int64_t)lane * lane_stride + (int64_t)p * kv;
+    if (rotate) {
+        for (int idx = threadIdx.x; idx < (n_heads + n_kv_heads) * half; idx += 256) {
+            const int i = idx % half, h = idx / half;
+            const float c = cos_t[(int64_t)p * half + i], s = sin_t[(int64_t)p * half + i];
+            const bool is_q = h < n_heads;
+            const float* src = is_q ? row + h * head_dim : row + H + (h - n_heads) * head_dim;
+            float* dst = is_q ? row + h * head_dim : kdst + (h - n_heads) * head_dim;
+            const float x0 = src[i], x1 = src[i + half];
+            dst[i] = x0 * c - x1 * s;
+            dst[i + half] = x0 * s + x1 * c;
+        }
+    } else {
+        for (int i = threadIdx.x; i < kv; i += 256) kdst[i] = row[H + i];
+    }
+    for (int i = threadIdx.x; i < kv; i += 256) vdst[i] = row[H + kv + i];
+}
+
+// Per-lane argmax, the last maximum wins (argmax_key); lanes that are not live are not scanned.
+__global__ __launch_bounds__(256) void lane_argmax_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int first_lane,
+                                                                  const int* __restrict__ live, unsigned long long* __restrict__ best)
+{
+    __shared__ unsigned long long red[4];
+    const int lane_id = first_lane + blockIdx.y;
+    if (!live[lane_id]) return;
+    const float* row = logits + (int64_t)lane_id * ld;
+    unsigned long long key = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
+        const unsigned long long kk = argmax_key(row[i], i);
+        key = kk > key ? kk : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off, kWave);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) key = red[w] > key ? red[w] : key;
+        atomicMax(best + lane_id, key);
+    }
+}
+
+// The pick of a live lane: the token joins the lane's history, count (and, after a step, pos) advance; the lane stays live
+// -- and the token becomes its next input -- unless the token is one of its stop ids, it has its max_new_tokens, or its
+// cache is full.
+__global__ void lane_pick_finalize_kernel(unsigned long long* __restrict__ best, LlmLaneState* __restrict__ st,
+                                          int32_t* __restrict__ history, int hist_stride, int first_lane, int lanes, int capacity,
+                                          int advance)
+{
+    const int l = first_lane + threadIdx.x;
+    if (l >= first_lane + lanes || !st->live[l]) return;
+    const int tok = (int)(uint32_t)(best[l] & 0xFFFFFFFFull);
+    best[l] = 0ull;
+    const int cnt = st->count[l];
+    if (cnt < hist_stride) history[(int64_t)l * hist_stride + cnt] = tok;
+    st->count[l] = cnt + 1;
+    if (advance) st->pos[l] += 1;
+    bool stop = cnt + 1 >= st->limit[l] || st->pos[l] >= capacity;
+    for (int e = 0; e < st->n_stop[l]; ++e) stop = stop || st->stop[l][e] == tok;
+    if (stop) st->live[l] = 0;
+    else st->token[l] = tok;
+}
+
+}  // namespace
+
+bool llm_gemv_lanes_takes(const LlmGemvArgs& a)
+{
+    return a.rows >= 1 && a.rows <= LLM_MAX_ROWS && a.k >= 512 && (a.k & 7) == 0 && (a.ldx & 3) == 0 && a.att_splits == 0 && !a.norm_out &&
+           (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 &&
+           (!a.W2 || (reinterpret_cast<uintptr_t>(a.W2) & 15) == 0) && (!a.gamma || (reinterpret_cast<uintptr_t>(a.gamma) & 15) == 0) &&
+           (!a.beta || (reinterpret_cast<uintptr_t>(a.beta) & 15) == 0);
+}
+
+template <typename WT>
+static hipError_t launch_gemv_lanes_t(const LlmGemvArgs& a, hipStream_t stream)
+{
+    const WT* W = static_cast<const WT*>(a.W);
+    const WT* W2 = static_cast<const WT*>(a.W2);
+    constexpr int LPP = sizeof(WT) == 2 ? 1 : 2;
+    // the slice width that pads K least (K = 768 / 3 072 -> 1 024, else 2 048)
+    const int ch = ((a.k + 1023) / 1024) * 1024 - a.k < ((a.k + 2047) / 2048) * 2048 - a.k ? 2 : 4;
+    const int nm = a.swiglu ? 2 : 1;
+    const int ns = (a.k + ch * 512 - 1) / (ch * 512);
+    // 16 loads per lane in flight where that still leaves two workgroups for every CU, else one column per wave
+    const int cpw_wide = lanes_cols_per_wave(ch, LPP, nm, true);
+    const bool wide = (a.n_out + 4 * cpw_wide - 1) / (4 * cpw_wide) >= 512;
+    const int cpw = wide ? cpw_wide : 1;
+    const int nbatches = (a.n_out + 4 * cpw - 1) / (4 * cpw);
+    // one slice: the rows stay in LDS and the workgroup loops over its batches; several: the grid covers the columns
+    const int wgs = ns == 1 ? std::min(nbatches, 512) : nbatches;
+    const size_t lds = (size_t)a.rows * ch * 512 * sizeof(float);
+#define KJ_LN3(EPI, NORM, CH, WIDE)                                                                                                  \
+    do {                                                                                                                             \
+        auto kern = llm_gemv_lanes_kernel<WT, EPI, NORM, CH, WIDE>;                                                                  \
+        if (lds > 48 * 1024) {                                                                                                       \
+            const hipError_t e = allow_dynamic_lds(kern, lds);                                                                       \
+            if (e != hipSuccess) return e;                                                                                           \
+        }                                                                                                                            \
+        hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds, stream, a.X, a.ldx, a.rows, a.gamma, a.beta, a.eps, W, W2,     \
+                           a.bias, a.R, a.ldr, a.n_out, a.k, a.seg_q, a.seg_kv, a.Y0, a.ldy0, a.Y1, a.Y2, a.ldy12, a.row_off,       \
+                           a.row_off_ptr);                                                                                           \
+    } while (0)
+#define KJ_LN2(EPI, NORM)                                                                                                            \
+    do {                                                                                                                             \
+        if (ch == 2 && wide) KJ_LN3(EPI, NORM, 2, true);                                                                             \
+        else if (ch == 2) KJ_LN3(EPI, NORM, 2, false);                                                                               \
+        else if (wide) KJ_LN3(EPI, NORM, 4, true);                                                                                   \
+        else KJ_LN3(EPI, NORM, 4, false);                                                                                            \
+    } while (0)
+    // the (epilogue, norm) pairs of launch_gemv_t
+    if (a.layernorm) {
+        if (a.gelu_tanh) KJ_LN2(LE_GELU_TANH, NK_LN);
+        else KJ_LN2(LE_NONE, NK_LN);
+    } else if (a.swiglu) KJ_LN2(LE_SWIGLU, NK_RMS);
+    else if (a.R) KJ_LN2(LE_RESIDUAL, NK_NONE);
+    else if (a.gamma) KJ_LN2(LE_NONE, NK_RMS);
+    else KJ_LN2(LE_NONE, NK_NONE);
+#undef KJ_LN2
+#undef KJ_LN3
+    return hipGetLastError();
+}
+
+hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& a, hipStream_t stream, int* streamed)
+{
+    if (streamed) *streamed = 0;
+    if (!llm_gemv_lanes_takes(a)) return launch_llm_gemv(a, stream);  // correct, but the rows are re-read for every column
+    // the pairs launch_llm_gemv accepts
+    if (a.layernorm && (!a.gamma || !a.beta || a.R || a.swiglu)) return hipErrorInvalidValue;
+    if (a.gelu_tanh && (!a.layernorm || a.seg_q != 0)) return hipErrorInvalidValue;
+    if ((a.swiglu && (!a.gamma || a.R || !a.W2)) || (a.R && a.gamma)) return hipErrorInvalidValue;
+    if (a.n_out <= 0) return hipSuccess;
+    if (streamed) *streamed = 1;
+    return a.bf16 ? launch_gemv_lanes_t<uint16_t>(a, stream) : launch_gemv_lanes_t<float>(a, stream);
+}
+
+hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
+                                    const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
+                                    const LlmLaneState* state, int rotate, hipStream_t stream)
+{
+    if (lanes <= 0) return hipSuccess;
+    if (lanes > LLM_MAX_ROWS || (rotate && (head_dim & 1))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lane_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim, cos_t,
+                       sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live, rotate);
+    return hipGetLastError();
+}
+
+hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
+                            LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream)
+{
+    if (lanes <= 0) return hipSuccess;
+    if (first_lane < 0 || first_lane + lanes > LLM_MAX_ROWS) return hipErrorInvalidValue;
+    int blocks = (vocab + 2047) / 2048;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(lane_argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)lanes), dim3(256), 0, stream, logits, ld, vocab,
+                       first_lane, state->live, best_scratch);
+    hipLaunchKernelGGL(lane_pick_finalize_kernel, dim3(1), dim3(64), 0, stream, best_scratch, state, history, hist_stride, first_lane, lanes,
+                       capacity, advance);
     return hipGetLastError();
 }
 

@@ -77,7 +77,10 @@ hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const 
                                    int kv_group = 1,  // grouped-query attention: kv_group query heads per KV head
                                    // lanes: the rows are independent sequences decoded in lock step; row s reads K + s * k_lane_stride
                                    // (V alike), every row sees n_keys (or *n_keys_ptr + 1) keys and there is no causal mask.
-                                   int64_t k_lane_stride = 0, int64_t v_lane_stride = 0, int lanes = 0);
+                                   int64_t k_lane_stride = 0, int64_t v_lane_stride = 0, int lanes = 0,
+                                   // ragged lanes (the LLM's): lane s sees lane_pos[s] + 1 keys (n_keys = the lane capacity), a lane
+                                   // with lane_live[s] == 0 yields zeros without reading its cache
+                                   const int* lane_pos = nullptr, const int* lane_live = nullptr);
 // history/count/pos (device, may be null): append the token, advance the counters (graph-replayed steps).
 hipError_t launch_pick_token(const float* logits, int vocab, int first_special, int eos, int timestamp_begin,
                              int allow_timestamps, int32_t* out, int32_t* history, int* count, int* pos, hipStream_t stream,

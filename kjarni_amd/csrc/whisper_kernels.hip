@@ -675,13 +675,17 @@ __global__ __launch_bounds__(256) void gemv_rows_head_kernel(const float* __rest
 constexpr int ATT_MAX_CHUNK = 512;
 constexpr int ATT_FAST = 8;  // keys per lane group that the short-range path holds in registers (128 keys per split at d = 64)
 
+// RAGGED (the LLM's lanes, prompts of different lengths): lane s holds lane_pos[s] + 1 keys (its cache rows plus this step's
+// own); a lane with lane_live[s] == 0 writes an empty slab (the merge then yields zeros) without reading its cache.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const float* __restrict__ q, int64_t ldq,
                                                                        const float* __restrict__ K0, int64_t ldk,
                                                                        const float* __restrict__ V0, int64_t ldv, int n_keys,
                                                                        const int* __restrict__ n_keys_ptr, int rows, int head_dim,
                                                                        float scale, int causal, int splits, int kv_group,
                                                                        int64_t k_lane_stride, int64_t v_lane_stride, int lanes,
-                                                                       float* __restrict__ part)
+                                                                       float* __restrict__ part, const int* __restrict__ lane_pos,
+                                                                       const int* __restrict__ lane_live)
 {
     __shared__ float sc[ATT_MAX_CHUNK];
     __shared__ float red[4];
@@ -690,7 +694,16 @@ __global__ __launch_bounds__(256) void decode_attention_partial_kernel(const flo
     const int base = n_keys_ptr ? *n_keys_ptr : 0;
     // lanes: the rows are independent sequences in lock step -- each attends to its own cache (row s at K + s * stride),
     // all of them hold the same number of keys (the ones before this step plus this step's own), no mask between rows.
-    const int n = n_keys_ptr ? base + (lanes ? 1 : rows) : n_keys;
+    int n = n_keys_ptr ? base + (lanes ? 1 : rows) : n_keys;
+    if (RAGGED) {
+        n = lane_live[s] ? min(lane_pos[s] + 1, n_keys) : 0;  // (n_keys: the lane capacity)
+        if (n <= 0) {
+            float* out = part + (((int64_t)s * gridDim.x + h) * splits + sp) * (head_dim + 4);
+            if (tid < (head_dim >> 2)) *reinterpret_cast<f32x4*>(out + 4 + tid * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (tid == 0) *reinterpret_cast<f32x4*>(out) = f32x4{-INFINITY, 0.0f, 0.0f, 0.0f};
+            return;
+        }
+    }
     const int causal_base = (causal < 0 || lanes) ? -1 : (n_keys_ptr ? base : causal);
     const float* __restrict__ K = K0 + (int64_t)blockIdx.z * k_lane_stride;
     const float* __restrict__ V = V0 + (int64_t)blockIdx.z * v_lane_stride;
@@ -1157,15 +1170,22 @@ size_t decode_attention_scratch_floats(int rows, int heads, int head_dim, int sp
 hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V,
                                    int64_t ldv, int n_keys, const int* n_keys_ptr, int max_keys, int heads, int head_dim,
                                    int causal_base, int splits, float* scratch, float* ctx, int64_t ldc, hipStream_t stream,
-                                   int kv_group, int64_t k_lane_stride, int64_t v_lane_stride, int lanes)
+                                   int kv_group, int64_t k_lane_stride, int64_t v_lane_stride, int lanes, const int* lane_pos,
+                                   const int* lane_live)
 {
     if (rows <= 0 || (n_keys <= 0 && !n_keys_ptr)) return hipSuccess;
     if (head_dim > 128 || 256 % (head_dim / 4) != 0 || (head_dim & 3) || splits < 1) return hipErrorInvalidValue;
     const int worst = n_keys_ptr ? max_keys : n_keys;
     if ((worst + splits - 1) / splits > ATT_MAX_CHUNK) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_attention_partial_kernel, dim3((unsigned)heads, (unsigned)splits, (unsigned)rows), dim3(256), 0, stream,
+    if (lane_pos) {  // ragged lanes: n_keys is the lane capacity
+        if (!lanes || !lane_live || n_keys_ptr) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(decode_attention_partial_kernel<true>, dim3((unsigned)heads, (unsigned)splits, (unsigned)rows), dim3(256), 0,
+                           stream, q, ldq, K, ldk, V, ldv, n_keys, n_keys_ptr, rows, head_dim, 1.0f / sqrtf((float)head_dim), causal_base,
+                           splits, kv_group < 1 ? 1 : kv_group, k_lane_stride, v_lane_stride, lanes, scratch, lane_pos, lane_live);
+    } else
+    hipLaunchKernelGGL(decode_attention_partial_kernel<false>, dim3((unsigned)heads, (unsigned)splits, (unsigned)rows), dim3(256), 0, stream,
                        q, ldq, K, ldk, V, ldv, n_keys, n_keys_ptr, rows, head_dim, 1.0f / sqrtf((float)head_dim), causal_base, splits,
-                       kv_group < 1 ? 1 : kv_group, k_lane_stride, v_lane_stride, lanes, scratch);
+                       kv_group < 1 ? 1 : kv_group, k_lane_stride, v_lane_stride, lanes, scratch, nullptr, nullptr);
     if (ctx)  // ctx == nullptr: the caller merges the slabs itself (layout above)
         hipLaunchKernelGGL(decode_attention_combine_kernel, dim3((unsigned)heads, (unsigned)rows), dim3(128), 0, stream, scratch, heads,
                            splits, head_dim, ctx, ldc);

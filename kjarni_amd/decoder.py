@@ -16,6 +16,7 @@ WEIGHTS = {"auto": 0, "f32": 1, "bf16": 2}
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
+        self._lanes = 0  # set by lanes_begin()
         check_error(lib().kjarni_hip_decoder_load(model_dir.encode("utf-8"), device, WEIGHTS[weights], max_context, C.byref(self._h)))
         a, b, c, d, e = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         wb = C.c_uint64()
@@ -96,3 +97,84 @@ class HipDecoder:
                                                       repetition_penalty, no_repeat_ngram, fn, None,
                                                       out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)))
         return out[:min(n.value, out.size)].tolist()
+
+    # ---- lanes: up to 8 prompts decoded in lock step ----
+    def generate_batch(self, prompts: Sequence[Sequence[int]], max_new_tokens, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0,
+                       lanes: int = 0, lane_context: int = 0,
+                       on_token: Optional[Callable[[int, int], Optional[bool]]] = None) -> List[List[int]]:
+        """generate() for every prompt, up to `lanes` (1..8, 0 = 8) of them at a time, each in a KV cache of `lane_context` rows
+        (<= 0: the decoder's context).  max_new_tokens: one int for all prompts, or one per prompt.  on_token(prompt index, token)
+        is called in step order, lane order within a step; returning False ends that prompt only."""
+        n = len(prompts)
+        if n == 0:
+            check_error(lib().kjarni_hip_decoder_generate_batch(self._h, None, None, 0, None, repetition_penalty, no_repeat_ngram, lanes,
+                                                                lane_context, _ffi.KjarniBatchTokenCallbackFn(), None, None, 0, None))
+            return []
+        new = [int(max_new_tokens)] * n if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
+        if len(new) != n:
+            raise ValueError("max_new_tokens: one value, or one per prompt")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint32).reshape(-1) for p in prompts]), np.uint32)
+        if flat.size == 0:
+            flat = np.zeros(1, np.uint32)
+        offsets = (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(p) for p in prompts])]).tolist())
+        news = (C.c_size_t * n)(*new)
+        cap = max(max(new), 1)
+        out = np.zeros((n, cap), np.uint32)
+        n_out = (C.c_size_t * n)()
+
+        def cb(i, t, _u):
+            r = on_token(int(i), int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniBatchTokenCallbackFn(cb) if on_token else _ffi.KjarniBatchTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_batch(self._h, flat.ctypes.data_as(C.POINTER(C.c_uint32)), offsets, n, news,
+                                                            repetition_penalty, no_repeat_ngram, lanes, lane_context, fn, None,
+                                                            out.ctypes.data_as(C.POINTER(C.c_uint32)), cap, n_out))
+        return [out[i, :min(int(n_out[i]), cap)].tolist() for i in range(n)]
+
+    def lanes_begin(self, lanes: int = 0, lane_context: int = 0):
+        """Test hook: empty lane caches for `lanes` lanes of `lane_context` rows each."""
+        check_error(lib().kjarni_hip_decoder_lanes_begin(self._h, lanes, lane_context))
+        self._lanes = lanes or 8
+
+    def lane_prefill(self, lane: int, ids: Sequence[int]):
+        a = np.ascontiguousarray(ids, np.uint32)
+        check_error(lib().kjarni_hip_decoder_lane_prefill(self._h, lane, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def lanes_step(self, ids: Sequence[int], live: Optional[Sequence[int]] = None):
+        """One lock-step step: lane l appends ids[l] where live[l] (default: every lane).  Returns the final-normed hidden rows
+        [lanes, hidden] and the logits [lanes, vocab]; the rows of frozen lanes are unspecified."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        if self._lanes and a.size != self._lanes:
+            raise ValueError("one id per lane")
+        lv = np.ascontiguousarray(live, np.int32) if live is not None else None
+        hidden = np.empty((a.size, self.hidden), np.float32)
+        logits = np.empty((a.size, self.vocab), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_lanes_step(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        lv.ctypes.data_as(C.POINTER(C.c_int32)) if lv is not None else None, f(hidden), f(logits)))
+        return hidden, logits
+
+    def lane_cache_len(self, lane: int) -> int:
+        return int(lib().kjarni_hip_decoder_lane_cache_len(self._h, lane))
+
+    def lane_capacity(self) -> int:
+        return int(lib().kjarni_hip_decoder_lane_capacity(self._h))
+
+    def lane_kv_rows(self, lane: int, layer: int, first: int = 0, rows: Optional[int] = None):
+        """kv_rows() of one lane's cache."""
+        if rows is None:
+            rows = self.lane_cache_len(lane) - first
+        if rows < 0:
+            raise ValueError("first is past the end of the lane's cache")
+        kv = self.kv_heads * self.head_dim
+        k, v = np.empty((rows, kv), np.float32), np.empty((rows, kv), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_lane_kv_rows(self._h, lane, layer, first, rows, f(k), f(v)))
+        return k, v
+
+    def lane_gemv_calls(self):
+        """(streamed, fallback): projections of lane steps that took the multi-row weight-streaming kernel / the one-wave-per-
+        column kernel since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_lane_gemv_calls(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)

@@ -3,7 +3,7 @@ crates/kjarni/src/generator/*): no chat template, the output as generated."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
@@ -49,6 +49,21 @@ class Generator:
         out = C.c_void_p()
         check_error(lib().kjarni_generator_generate(self._handle, prompt.encode("utf-8"), _gen(config), C.byref(out)))
         return _take_string(out)
+
+    def generate_batch(self, prompts: Sequence[str], config: Optional[GenerationConfig] = None) -> List[str]:
+        """generate() for every prompt, up to 8 of them (set_lanes) decoded in lock step; texts in prompt order."""
+        arr = _ffi.KjarniStringArray()
+        raw = [p.encode("utf-8") for p in prompts]
+        ptrs = (C.c_char_p * max(len(raw), 1))(*raw)
+        check_error(lib().kjarni_generator_generate_batch(self._handle, ptrs, len(raw), _gen(config), C.byref(arr)))
+        try:
+            return arr.to_list()
+        finally:
+            arr.free()
+
+    def set_lanes(self, lanes: int):
+        """Lanes generate_batch() runs with (1..8, 0 = 8)."""
+        check_error(lib().kjarni_hip_generator_set_lanes(self._handle, lanes))
 
     def stream(self, prompt: str, on_token: Callable[[str], bool], config: Optional[GenerationConfig] = None, cancel=None):
         cb = _stream_cb(on_token)

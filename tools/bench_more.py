@@ -18,6 +18,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            (oracle) timed on a bounded sample of the same work.
   llm      BASELINE.json configs[4]: Llama-3.2-1B-shaped decoder (random init), weights bf16 in HBM, f32 KV cache:
            prefill of a 128-token prompt and greedy decode of 256 tokens; tokens/s and the weight stream vs HBM peak.
+  llm_lanes  (only on request) batched greedy decode, 1 / 2 / 4 / 8 prompts in lock step (HipDecoder.generate_batch) against
+           the single-stream generate() of the same build, alternated twice in one process: Llama-3.2-1B shape (bf16),
+           gpt2-small (bf16, f32) and the 1B shape as a GGUF Q4_K_M-style mix; 128-token prompts; aggregate tokens/s and
+           ms per lock-step step.  KJARNI_LANES_STEPS=N: N steps at 8 lanes on the Llama shape only (for a kernel trace).
 """
 import json
 import os
@@ -723,6 +727,74 @@ def main():
               "config": {"workload": f"Llama-3.2-1B geometry, random init, {n_prompt}-token templated prompt, {n_new} new tokens; "
                                      "greedy = device-resident graph loop, sample = logits to the host + sampler per token"},
               "prompt_tokens": n_prompt, "ms_template_plus_bpe_encode": round(t_enc * 1e3, 3), "runs": rows})
+
+    if "llm_lanes" in which:
+        # Method (measuring guide, section 5): everything in one process on one box; every lane count is warmed first (graph
+        # capture, lane caches); the decode window is a whole generation minus the same call cut after its first token (the
+        # prefills and the first pick), so it holds n_new - 1 lock-step steps; lanes = 1 / 2 / 4 / 8 alternate with the
+        # single-stream generate() -- the yardstick -- twice.
+        from tests import gguf_fixture, gpt2_fixture
+        rng = np.random.default_rng(0)
+        trace_steps = int(os.environ.get("KJARNI_LANES_STEPS", "0"))
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, prompts, n_new, dtype):
+            if trace_steps:  # a short run for rocprofv3 --kernel-trace --stats: 8 lanes, trace_steps lock-step steps
+                dec.generate_batch(prompts, trace_steps + 1, lanes=8)
+                return
+            single_rates, rows = [], {}
+            dec.generate(prompts[0], 8)
+            for lanes in (1, 2, 4, 8):
+                dec.generate_batch(prompts[:lanes], 20, lanes=lanes)               # warm-up: graph capture for this lane count
+            for rep in range(2):
+                for lanes in (1, 2, 4, 8):
+                    dt, out = window(lambda: dec.generate(prompts[0], n_new), lambda: dec.generate(prompts[0], 1))
+                    assert len(out) == n_new
+                    single_rates.append((n_new - 1) / dt)
+                    ps = prompts[:lanes]
+                    dt, outs = window(lambda: dec.generate_batch(ps, n_new, lanes=lanes), lambda: dec.generate_batch(ps, 1, lanes=lanes))
+                    assert all(len(o) == n_new for o in outs)
+                    rows.setdefault(lanes, []).append({"tokens_per_s": round(lanes * (n_new - 1) / dt, 1),
+                                                       "ms_per_step": round(dt * 1e3 / (n_new - 1), 4)})
+            single = float(np.median(single_rates))
+            emit({"metric": f"aggregate tokens/sec greedy decode in lanes, {label}", "unit": "tokens/s",
+                  "value": max(r["tokens_per_s"] for r in rows[8]), "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                  "config": {"workload": f"{label}, random init, one 128-token prompt per lane, {n_new} generated tokens per lane, "
+                                         "lanes 1 / 2 / 4 / 8 alternated twice with single-stream generate() in one process"},
+                  "single_stream_tokens_per_s": {"median": round(single, 1), "min": round(min(single_rates), 1),
+                                                 "max": round(max(single_rates), 1), "runs": [round(r, 1) for r in single_rates]},
+                  "lanes": {str(k): v for k, v in rows.items()},
+                  "x_single_stream_at_8": round(max(r["tokens_per_s"] for r in rows[8]) / single, 2), "weight_bytes": dec.weight_bytes})
+
+        d = os.path.join(tmp, "llama-1b-lanes")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        prompts = [rng.integers(1000, 100000, 128).tolist() for _ in range(8)]
+        measure("Llama-3.2-1B shape, bf16 weights", dec, prompts, 1024, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        if not trace_steps:  # (the trace run is the Llama shape alone)
+            gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+            gd = os.path.join(tmp, "gpt2-small-lanes")
+            gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+            gprompts = [rng.integers(0, 50257, 128).tolist() for _ in range(8)]
+            for weights in ("auto", "f32"):
+                dec = kjarni_amd.HipDecoder(gd, weights=weights)
+                wt = "bf16" if dec.bf16 else "f32"
+                measure(f"gpt2-small shape, {wt} weights", dec, gprompts, 768, f"{wt} weights, f32 activations/accumulate/KV")
+                del dec
+            gpath = os.path.join(tmp, "llama-1b-q4km-lanes.gguf")
+            qcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=synth.LLAMA_1B["vocab_size"] + 1)
+            gguf_fixture.gguf_model(gpath, qcfg, gguf_fixture.q4_k_m_types(qcfg["num_hidden_layers"]), seed=0, rope_freqs=True, keep_hf=False)
+            dec = kjarni_amd.HipDecoder(gpath, max_context=2048)
+            measure("Llama-3.2-1B shape, GGUF Q4_K_M-style mix (Q4_K / Q6_K in HBM)", dec, prompts, 512, "Q4_K / Q6_K weights, f32 activations/KV")
+            del dec
 
 
 if __name__ == "__main__":
