@@ -578,6 +578,49 @@ void kjarni_hip_decoder_lane_gemv_calls(const KjarniHipDecoder* decoder, uint64_
 /* The lane count kjarni_generator_generate_batch runs with (1..8, 0 = 8, the default). */
 KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* generator, int32_t lanes);
 
+/* ---- prompt-lookup speculative decoding (NOT in the reference) ----
+ * Greedy generation that emits several tokens per step.  T = the prompt and every token so far; a step drafts the
+ * continuation of a match of T's suffix inside T: over every position e (a continuation would start at T[e]) whose
+ * preceding ngram_min..ngram_max tokens equal T's last ones, the longest match, then the longest continuation (up to
+ * draft_tokens), then the latest.  The last token and the draft run as ONE causal block of draft_tokens + 1 rows, every row
+ * through the vocabulary head; the model's own argmax tokens are kept up to and including the first that differs from the
+ * draft, so every emitted token is an argmax of the model's logits: the ids are kjarni_hip_decoder_generate's whenever the
+ * two best logits are further apart than the float bar at every step (the multi-row kernels sum in another order).  Off
+ * unless asked for; sampling, repetition penalty and the n-gram ban keep their own paths. */
+typedef struct KjarniHipLookupConfig { int32_t draft_tokens, ngram_max, ngram_min; } KjarniHipLookupConfig;  /* 1..7, 1..4, 1..ngram_max */
+typedef struct KjarniHipLookupStats { uint64_t verify_steps, drafted_tokens, accepted_tokens, single_row_steps; } KjarniHipLookupStats;
+KjarniHipLookupConfig kjarni_hip_lookup_config_default(void);   /* 7, 3, 1 */
+/* kjarni_hip_decoder_generate with repetition_penalty 1 and no n-gram ban, through the lookup loop.  stop_ids / n_stop: the
+ * ids that end the call (not emitted); n_stop == 0: config.json's eos ids.  config NULL: the default.  stats (may be NULL)
+ * covers the steps whose tokens the host consumed: verify_steps (two or more rows), single_row_steps (one row: the last
+ * free row of the cache), drafted_tokens and accepted_tokens summed over both.  A config outside the ranges or a prompt longer
+ * than the context: INVALID_CONFIG before any GPU work, the message names the field. */
+KjarniErrorCode kjarni_hip_decoder_generate_lookup(KjarniHipDecoder* decoder, const uint32_t* prompt, size_t n_prompt, size_t max_new_tokens,
+                                                   const uint32_t* stop_ids, size_t n_stop, const KjarniHipLookupConfig* config,
+                                                   KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out, size_t capacity,
+                                                   size_t* n_out, KjarniHipLookupStats* stats);
+/* The draft kernel alone on a host-given history: draft_out[7], *n_out = draft length. */
+KjarniErrorCode kjarni_hip_op_lookup_draft(int32_t device, const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config,
+                                           uint32_t* draft_out, int32_t* n_out);
+/* Host restatement of the same rule (no GPU). */
+KjarniErrorCode kjarni_lookup_draft(const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config, uint32_t* draft_out,
+                                    int32_t* n_out);
+/* Test hook: one verify step with an explicit draft on the cache as it stands (after kjarni_hip_decoder_forward): `rows` in
+ * n_draft + 1 .. 8 rows are computed (the rows past the draft repeat its last id); tokens_out[0 .. *n_accepted] (room for 8) are
+ * the picks, the cache grows by *n_accepted + 1; logits_out (may be NULL) f32 [n_draft + 1, vocab], every row: row i is the
+ * model's output after token, draft[0..i).  n_draft outside 0..7, rows outside n_draft + 1 .. 8 or cache_len + rows > context:
+ * INVALID_CONFIG before any GPU work. */
+KjarniErrorCode kjarni_hip_decoder_verify_step(KjarniHipDecoder* decoder, uint32_t token, const uint32_t* draft, int32_t n_draft,
+                                               int32_t rows, uint32_t* tokens_out, int32_t* n_accepted, float* logits_out);
+/* Projections of verify steps that took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel
+ * since load (counted when enqueued: a replayed graph counts once, at capture). */
+void kjarni_hip_decoder_verify_gemv_calls(const KjarniHipDecoder* decoder, uint64_t* streamed, uint64_t* fallback);
+/* Prompt lookup for kjarni_generator_generate / _generate_stream: 0 = off (the default), 1..7 drafted tokens per step.  Used
+ * when the resolved config is greedy with repetition_penalty 1 and no n-gram ban; generate_batch and Chat are untouched. */
+KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGenerator* generator, int32_t draft_tokens);
+/* kjarni_hip_decoder_verify_gemv_calls of the generator's model: it moves only when a call took the lookup loop. */
+void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* generator, uint64_t* streamed, uint64_t* fallback);
+
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */
 KjarniErrorCode kjarni_hip_malloc(int32_t device, size_t bytes, void** out_dev);
 KjarniErrorCode kjarni_hip_free(int32_t device, void* ptr_dev);

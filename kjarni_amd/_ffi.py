@@ -234,6 +234,14 @@ class KjarniResolvedGeneration(Structure):
 KjarniStreamCallbackFn = C.CFUNCTYPE(C.c_bool, c_char_p, c_void_p)
 
 
+class KjarniHipLookupConfig(Structure):
+    _fields_ = [("draft_tokens", c_int32), ("ngram_max", c_int32), ("ngram_min", c_int32)]
+
+
+class KjarniHipLookupStats(Structure):
+    _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
+
+
 class KjarniGeneratorConfig(Structure):
     _fields_ = [("device", c_int32), ("cache_dir", c_char_p), ("model_name", c_char_p), ("model_path", c_char_p),
                 ("quiet", c_int32)]
@@ -433,6 +441,16 @@ SIGNATURES = {
     "kjarni_hip_decoder_lane_kv_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_lane_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_lanes": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_lookup_config_default": (KjarniHipLookupConfig, []),
+    "kjarni_hip_decoder_generate_lookup": (c_int32, [c_void_p, _u32p, c_size_t, c_size_t, _u32p, c_size_t, POINTER(KjarniHipLookupConfig),
+                                                     KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
+                                                     POINTER(KjarniHipLookupStats)]),
+    "kjarni_hip_op_lookup_draft": (c_int32, [c_int32, _u32p, c_size_t, POINTER(KjarniHipLookupConfig), _u32p, POINTER(c_int32)]),
+    "kjarni_lookup_draft": (c_int32, [_u32p, c_size_t, POINTER(KjarniHipLookupConfig), _u32p, POINTER(c_int32)]),
+    "kjarni_hip_decoder_verify_step": (c_int32, [c_void_p, C.c_uint32, _u32p, c_int32, c_int32, _u32p, POINTER(c_int32), _f32p]),
+    "kjarni_hip_decoder_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_generator_set_prompt_lookup": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_generator_generate_batch": (c_int32, [c_void_p, POINTER(c_char_p), c_size_t, POINTER(KjarniGenerationConfig),
                                                   POINTER(KjarniStringArray)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),

@@ -348,18 +348,27 @@ GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, 
 // The text side of run_generation_loop shared by Chat and Generator: the resolved config becomes the loop's options, and
 // every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
 std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
-                                const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text)
+                                const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
+                                int prompt_lookup = 0)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     const GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
     std::string text;
     std::vector<uint32_t> prompt_tokens = tokens;
     if ((int)prompt_tokens.size() > model.context()) prompt_tokens.resize((size_t)model.context());
-    model.generate(prompt_tokens, opt, [&](uint32_t id) {
+    const auto on_token = [&](uint32_t id) {
         const std::string piece = tok.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
         text += piece;
         return on_text ? on_text(piece) : true;
-    });
+    };
+    // prompt lookup (when set): greedy requests without processors verify a draft from their own history every step
+    if (prompt_lookup > 0 && !opt.sample && opt.repetition_penalty == 1.0f && opt.no_repeat_ngram <= 0) {
+        LookupConfig lk;
+        lk.draft_tokens = prompt_lookup;
+        model.generate_lookup(prompt_tokens, opt, lk, on_token, nullptr);
+    } else {
+        model.generate(prompt_tokens, opt, on_token);
+    }
     return text;
 }
 
@@ -563,7 +572,7 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
-    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text);
+    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_);
 }
 
 

@@ -146,6 +146,10 @@ public:
     std::vector<std::string> generate_batch(const std::vector<std::string>& prompts, const GenerationOverrides& runtime, int lanes);
     int batch_lanes() const { return batch_lanes_; }
     void set_batch_lanes(int lanes) { batch_lanes_ = lanes; }  // what kjarni_generator_generate_batch runs with (0 = 8)
+    // Prompt-lookup decoding for generate / stream (0 = off, the default; 1..7 drafted tokens per step): used when the resolved
+    // config is greedy without a repetition penalty or an n-gram ban (LlmModel::generate_lookup); generate_batch is untouched.
+    void set_prompt_lookup(int draft_tokens) { prompt_lookup_ = draft_tokens; }
+    int prompt_lookup() const { return prompt_lookup_; }
 
 private:
     Generator() = default;
@@ -159,6 +163,7 @@ private:
     UniformRng rng_;
     std::mutex mutex_;
     int batch_lanes_ = 0;
+    int prompt_lookup_ = 0;
 };
 
 // str::trim (Unicode White_Space at both ends).

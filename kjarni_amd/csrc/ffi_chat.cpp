@@ -10,6 +10,7 @@
 #include "bpe.h"
 #include "chat.h"
 #include "ffi_common.h"
+#include "llm_kernels.h"
 #include "sampling.h"
 #include "unicode.h"
 
@@ -679,6 +680,23 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* ge
     }
     gen->inner->set_batch_lanes(lanes);
     return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGenerator* gen, int32_t draft_tokens)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    if (draft_tokens < 0 || draft_tokens > kLookupMaxDraft) {
+        set_last_error("draft_tokens must be 1..7 (0 = off)");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    gen->inner->set_prompt_lookup(draft_tokens);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
+{
+    if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;
+    if (fallback) *fallback = gen ? gen->inner->model().verify_fallback_calls() : 0;
 }
 
 KJARNI_EXPORT void kjarni_hip_generator_set_device_sampling(KjarniGenerator* gen, int32_t on)

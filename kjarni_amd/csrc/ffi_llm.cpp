@@ -223,6 +223,88 @@ KJARNI_EXPORT void kjarni_hip_decoder_lane_gemv_calls(const KjarniHipDecoder* d,
     if (fallback) *fallback = d ? d->model->lane_fallback_calls() : 0;
 }
 
+// ---- prompt-lookup decoding ---------------------------------------------------------------------------------------------------
+
+static LookupConfig lookup_config(const KjarniHipLookupConfig* c)  // NULL: the default; checked
+{
+    LookupConfig k;
+    if (c) {
+        k.draft_tokens = c->draft_tokens;
+        k.ngram_max = c->ngram_max;
+        k.ngram_min = c->ngram_min;
+    }
+    check_lookup_config(k);
+    return k;
+}
+
+KJARNI_EXPORT KjarniHipLookupConfig kjarni_hip_lookup_config_default(void)
+{
+    const LookupConfig k;
+    return KjarniHipLookupConfig{k.draft_tokens, k.ngram_max, k.ngram_min};
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_lookup(KjarniHipDecoder* d, const uint32_t* prompt, size_t n_prompt,
+                                                                 size_t max_new_tokens, const uint32_t* stop_ids, size_t n_stop,
+                                                                 const KjarniHipLookupConfig* config, KjarniTokenCallbackFn on_token,
+                                                                 void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out,
+                                                                 KjarniHipLookupStats* stats)
+{
+    if (!d || !prompt || !n_out || (capacity && !ids_out) || (n_stop && !stop_ids)) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const LookupConfig lk = lookup_config(config);
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (n_prompt > (size_t)d->model->context())  // before any GPU work
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        std::function<bool(uint32_t)> cb;
+        if (on_token)
+            cb = [&](uint32_t id) {
+                KjarniToken t;
+                t.text = nullptr;  // token-level API: no tokenizer behind it
+                t.token_id = id;
+                t.is_special = false;
+                return on_token(t, user_data);
+            };
+        GenerateOptions opt;
+        opt.max_new_tokens = max_new_tokens;
+        opt.stop_ids.assign(stop_ids, stop_ids + n_stop);
+        LookupStats st;
+        const std::vector<uint32_t> ids = d->model->generate_lookup(std::vector<uint32_t>(prompt, prompt + n_prompt), opt, lk, cb, &st);
+        *n_out = ids.size();
+        if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+        if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_lookup_draft(const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config, uint32_t* draft_out,
+                                                  int32_t* n_out)
+{
+    if ((n && !tokens) || !draft_out || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        const std::vector<uint32_t> draft = lookup_draft_host(tokens, n, lookup_config(config));
+        std::memcpy(draft_out, draft.data(), draft.size() * sizeof(uint32_t));
+        *n_out = (int32_t)draft.size();
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_verify_step(KjarniHipDecoder* d, uint32_t token, const uint32_t* draft, int32_t n_draft,
+                                                             int32_t rows, uint32_t* tokens_out, int32_t* n_accepted, float* logits_out)
+{
+    if (!d || !tokens_out || !n_accepted || (n_draft > 0 && !draft)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        *n_accepted = d->model->verify_step(token, draft, n_draft, rows, tokens_out, logits_out);  // ranges checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_verify_gemv_calls(const KjarniHipDecoder* d, uint64_t* streamed, uint64_t* fallback)
+{
+    if (streamed) *streamed = d ? d->model->verify_stream_calls() : 0;
+    if (fallback) *fallback = d ? d->model->verify_fallback_calls() : 0;
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* d, char** out)
 {
     if (!d || !out) return KJARNI_ERROR_NULL_POINTER;

@@ -11,6 +11,7 @@
 #include "ffi_common.h"
 #include "group.h"
 #include "gguf.h"
+#include "llm.h"
 #include "llm_kernels.h"
 #include "quant_kernels.h"
 #include "tuning.h"
@@ -538,6 +539,38 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_bf16_weights(int32_t device, 
                       "gemm (bf16 weights)");
         });
         hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+    });
+}
+
+// The prompt-lookup draft kernel alone, on a history given by the host.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lookup_draft(int32_t device, const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config,
+                                                         uint32_t* draft_out, int32_t* n_out)
+{
+    if ((n && !tokens) || !draft_out || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        LookupConfig k;
+        if (config) {
+            k.draft_tokens = config->draft_tokens;
+            k.ngram_max = config->ngram_max;
+            k.ngram_min = config->ngram_min;
+        }
+        check_lookup_config(k);
+        if (n > (size_t)std::numeric_limits<int32_t>::max()) throw InvalidConfig("history longer than 2^31 - 1 tokens");
+        use_device(device);
+        if (n == 0) return;
+        DeviceBuf hist(n * sizeof(int32_t)), state(sizeof(LlmLookupState)), ids(8 * sizeof(uint32_t));
+        LlmLookupState st = {};
+        st.n = (int32_t)n;
+        hip_check(hipMemcpy(hist.p, tokens, n * sizeof(int32_t), hipMemcpyHostToDevice), "H2D history");
+        hip_check(hipMemcpy(state.p, &st, sizeof(st), hipMemcpyHostToDevice), "H2D state");
+        hip_check(launch_lookup_draft(static_cast<const int32_t*>(hist.p), static_cast<LlmLookupState*>(state.p), k.ngram_max, k.ngram_min,
+                                      k.draft_tokens, k.draft_tokens + 1, static_cast<uint32_t*>(ids.p), nullptr), "lookup draft");
+        uint32_t rows[8] = {};
+        hip_check(hipMemcpy(&st, state.p, sizeof(st), hipMemcpyDeviceToHost), "D2H state");
+        hip_check(hipMemcpy(rows, ids.p, sizeof(rows), hipMemcpyDeviceToHost), "D2H ids");
+        for (int i = 0; i < st.m; ++i) draft_out[i] = rows[1 + i];
+        *n_out = st.m;
     });
 }
 

@@ -142,6 +142,8 @@ LlmModel::~LlmModel()
     if (graph_) (void)hipGraphExecDestroy(graph_);
     for (hipGraphExec_t g : lane_graphs_)
         if (g) (void)hipGraphExecDestroy(g);
+    for (hipGraphExec_t g : lookup_graphs_)
+        if (g) (void)hipGraphExecDestroy(g);
     if (stream_) (void)hipStreamDestroy(stream_);
     arena_.release();
 }
@@ -440,26 +442,39 @@ void LlmModel::reset()
     hip_check(hipMemsetAsync(count_, 0, sizeof(int), stream_), "reset count");
 }
 
-void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
+void LlmModel::verify_gemv(const LlmGemvArgs& a, const char* what)
+{
+    int streamed = 0;
+    hip_check(launch_llm_gemv_lanes(a, stream_, &streamed), what);
+    if (streamed) ++verify_stream_calls_;
+    else ++verify_fallback_calls_;
+}
+
+void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
     const int* pp = device_pos ? pos_ : nullptr;
     if (quant_) {
-        pass_quant(ids_dev, n, device_pos);
+        pass_quant(ids_dev, n, device_pos, verify);
         return;
     }
     if (gpt2_) {
-        pass_gpt2(ids_dev, n, device_pos);
+        pass_gpt2(ids_dev, n, device_pos, verify);
         return;
     }
+    auto gemv = [&](const LlmGemvArgs& a, const char* what) {
+        if (verify) verify_gemv(a, what);
+        else hip_check(launch_llm_gemv(a, s), what);
+    };
+    const bool one = n == 1 && !verify;  // the one-token fusions
     // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
-    const bool embed_in_qkv = n == 1 && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
+    const bool embed_in_qkv = one && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
     if (!embed_in_qkv) hip_check(launch_llm_embed(ids_dev, n, H, c.vocab, embed_, bf16_ ? 1 : 0, h_, s), "embed");
     bool first_layer = true;
     for (const Layer& L : layers_) {
-        if (n == 1 && H <= 8192) {  // decode step: norm + projection + rotation in one launch
+        if (one && H <= 8192) {  // decode step: norm + projection + rotation in one launch
             const bool emb = embed_in_qkv && first_layer;
             hip_check(launch_llm_qkv_rope(h_, L.ln1, c.eps, L.wqkv, bf16_ ? 1 : 0, L.bqkv, H, c.heads, c.kv_heads, d, cos_, sin_, q_,
                                           L.k_cache, L.v_cache, cache_len_, pp, s, emb ? ids_dev : nullptr, emb ? embed_ : nullptr,
@@ -470,12 +485,12 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
         a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_; a.bias = L.bqkv;
         a.n_out = H + 2 * kv; a.k = H; a.seg_q = H; a.seg_kv = kv; a.Y0 = q_; a.ldy0 = H; a.Y1 = L.k_cache; a.Y2 = L.v_cache; a.ldy12 = kv;
         a.row_off = cache_len_; a.row_off_ptr = pp;
-        hip_check(launch_llm_gemv(a, s), "norm + qkv");
+        gemv(a, "norm + qkv");
         hip_check(launch_rope(q_, H, n, c.heads, d, cos_, sin_, cache_len_, pp, 0, s), "rope q");
         hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pp, 1, s), "rope k");
         }
         // one token: the output projection merges the attention's per-split slabs itself (no combine launch)
-        const bool merge_in_proj = n == 1 && c.heads * d == H && llm_gemv_merges_attention(H, splits_, d);
+        const bool merge_in_proj = one && c.heads * d == H && llm_gemv_merges_attention(H, splits_, d);
         hip_check(launch_decode_attention(q_, H, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
                                           splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, H, s, c.heads / c.kv_heads), "attention");
         LlmGemvArgs o;
@@ -483,18 +498,24 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
         if (merge_in_proj) {
             o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
         }
-        hip_check(launch_llm_gemv(o, s), "o proj");
+        gemv(o, "o proj");
         LlmGemvArgs g;  // RMSNorm + SwiGLU (swiglu.rs:32-57)
         g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.W2 = L.up; g.bf16 = bf16_; g.swiglu = 1;
         g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
-        hip_check(launch_llm_gemv(g, s), "norm + gate/up");
+        gemv(g, "norm + gate/up");
         LlmGemvArgs dn;
         dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I; dn.Y0 = h_; dn.ldy0 = H;
-        hip_check(launch_llm_gemv(dn, s), "down proj");
+        gemv(dn, "down proj");
     }
     LlmGemvArgs lm;
     lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
     lm.Y0 = logits_; lm.ldy0 = c.vocab;
+    if (verify) {  // every row's logits
+        hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
+        lm.X = last_; lm.rows = n; lm.Y0 = vlogits_;
+        verify_gemv(lm, "lm head");
+        return;
+    }
     if (n == 1 && llm_gemv_streams(H, lm_head_, nullptr)) {  // one token: the head normalises the row itself (and stores it)
         lm.X = h_; lm.gamma = final_norm_; lm.eps = c.eps; lm.norm_out = last_;
     } else {
@@ -507,20 +528,24 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos)
 // pass() for GPT-2 (gpt2/cpu_decoder.rs:371-394): the token + position embedding, then per layer the same five launches as
 // the bf16 Llama step -- LayerNorm(ln_1) + Q|K|V + bias (K / V rows into the cache, no rotation), attention, c_proj + bias +
 // residual, LayerNorm(ln_2) + c_fc + bias + GELU-tanh, mlp.c_proj + bias + residual -- and LayerNorm(ln_f) + the tied head.
-void LlmModel::pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos)
+void LlmModel::pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, I = c.inter;
     const int* pp = device_pos ? pos_ : nullptr;
+    auto gemv = [&](const LlmGemvArgs& a, const char* what) {
+        if (verify) verify_gemv(a, what);
+        else hip_check(launch_llm_gemv(a, s), what);
+    };
     hip_check(launch_llm_embed_pos(ids_dev, n, H, c.vocab, embed_, wpe_, c.max_pos, bf16_ ? 1 : 0, cache_len_, pp, h_, s), "embed");
     for (const Layer& L : layers_) {
         LlmGemvArgs a;
         a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = 1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_;
         a.bias = L.bqkv; a.n_out = 3 * H; a.k = H; a.seg_q = H; a.seg_kv = H; a.Y0 = q_; a.ldy0 = H; a.Y1 = L.k_cache; a.Y2 = L.v_cache;
         a.ldy12 = H; a.row_off = cache_len_; a.row_off_ptr = pp;
-        hip_check(launch_llm_gemv(a, s), "ln_1 + c_attn");
-        const bool merge_in_proj = n == 1 && llm_gemv_merges_attention(H, splits_, d);
+        gemv(a, "ln_1 + c_attn");
+        const bool merge_in_proj = n == 1 && !verify && llm_gemv_merges_attention(H, splits_, d);
         hip_check(launch_decode_attention(q_, H, n, L.k_cache, H, L.v_cache, H, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_, splits_,
                                           att_scratch_, merge_in_proj ? nullptr : ctx_, H, s, 1), "attention");
         LlmGemvArgs o;
@@ -528,21 +553,24 @@ void LlmModel::pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos)
         if (merge_in_proj) {
             o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
         }
-        hip_check(launch_llm_gemv(o, s), "attn c_proj");
+        gemv(o, "attn c_proj");
         LlmGemvArgs f;
         f.X = h_; f.ldx = H; f.rows = n; f.gamma = L.ln2; f.beta = L.ln2_b; f.layernorm = 1; f.eps = c.eps; f.W = L.gate; f.bf16 = bf16_;
         f.bias = L.bfc; f.gelu_tanh = 1; f.n_out = I; f.k = H; f.Y0 = mid_; f.ldy0 = I;
-        hip_check(launch_llm_gemv(f, s), "ln_2 + c_fc + gelu");
+        gemv(f, "ln_2 + c_fc + gelu");
         LlmGemvArgs dn;
         dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
         dn.Y0 = h_; dn.ldy0 = H;
-        hip_check(launch_llm_gemv(dn, s), "mlp c_proj");
+        gemv(dn, "mlp c_proj");
     }
     hip_check(launch_layernorm(h_, final_norm_, final_norm_b_, c.eps, n, H, last_, s), "ln_f");
     LlmGemvArgs lm;
     lm.X = last_ + (size_t)(n - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
     lm.Y0 = logits_; lm.ldy0 = c.vocab;
-    hip_check(launch_llm_gemv(lm, s), "lm head");
+    if (verify) {  // every row's logits
+        lm.X = last_; lm.rows = n; lm.Y0 = vlogits_;
+    }
+    gemv(lm, "lm head");
 }
 
 void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what)
@@ -561,7 +589,7 @@ void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, boo
 // (quant_kernels.hip): RMSNorm + Q|K|V (per-segment types) + RoPE + cache write, attention, o-proj + residual, RMSNorm +
 // gate/up + SwiGLU, down + residual.  A stage whose input feeds a Q6_K linear first runs one qprep launch (RMSNorm where the
 // stage has one + the Q8_K codes, shared by every matrix of the stage).
-void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos)
+void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
@@ -609,7 +637,8 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos)
         hip_check(launch_qfused(dn, s), "down proj");
     }
     hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
-    qlinear(qhead_, last_ + (size_t)(n - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
+    if (verify) qlinear(qhead_, last_, H, n, head_q8k_, vlogits_, c.vocab, "lm head");  // every row's logits (the quantized kernels take <= 8 rows as they are)
+    else qlinear(qhead_, last_ + (size_t)(n - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
 }
 
 // Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer RMSNorm ->
@@ -1581,6 +1610,195 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             for (int l = 0; l < n; ++l)
                 if (h.live[l]) lane_len_[l] = h.pos[l] + 1;
         }
+    }
+    return out;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Prompt-lookup decoding: greedy generation that emits several tokens per step.  The draft of a step is the continuation of
+// the latest longest n-gram match of the history's suffix in the history itself (no second model); the verify step runs the
+// last token and the draft as one causal block of rows at the device-held position and the pick keeps the model's own argmax
+// tokens up to and including the first that differs from the draft.  draft -> step -> pick is one linear chain of launches
+// on one stream: 1 + (the step's) + 2 launches, captured once per row count.
+
+void check_lookup_config(const LookupConfig& c)
+{
+    if (c.draft_tokens < 1 || c.draft_tokens > kLookupMaxDraft) throw InvalidConfig("draft_tokens must be 1..7");
+    if (c.ngram_max < 1 || c.ngram_max > kLookupMaxNgram) throw InvalidConfig("ngram_max must be 1..4");
+    if (c.ngram_min < 1 || c.ngram_min > c.ngram_max) throw InvalidConfig("ngram_min must be 1..ngram_max");
+}
+
+// The rule lookup_draft_kernel computes, position by position: the largest (match length, continuation length, position).
+std::vector<uint32_t> lookup_draft_host(const uint32_t* T, size_t n, const LookupConfig& c)
+{
+    size_t best_m = 0, best_c = 0, best_e = 0;
+    for (size_t e = 1; e < n; ++e) {
+        size_t m = 0;
+        while (m < (size_t)c.ngram_max && m < e && T[e - 1 - m] == T[n - 1 - m]) ++m;
+        if (m < (size_t)c.ngram_min) continue;
+        const size_t cont = std::min((size_t)c.draft_tokens, n - e);
+        if (m > best_m || (m == best_m && cont >= best_c)) {  // (e grows: on equal (m, cont) the later position wins)
+            best_m = m;
+            best_c = cont;
+            best_e = e;
+        }
+    }
+    return best_m ? std::vector<uint32_t>(T + best_e, T + best_e + best_c) : std::vector<uint32_t>();
+}
+
+void LlmModel::ensure_lookup()
+{
+    if (vlogits_) return;
+    lk_hist_cap_ = cache_cap_ + 16;
+    vids_ = reinterpret_cast<uint32_t*>(dalloc(kLanes));
+    lk_state_ = reinterpret_cast<LlmLookupState*>(dalloc((sizeof(LlmLookupState) + 3) / 4));
+    lk_hist_ = reinterpret_cast<int32_t*>(dalloc((size_t)lk_hist_cap_));
+    lk_log_ = reinterpret_cast<int32_t*>(dalloc(2 * (size_t)lk_hist_cap_));
+    lk_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kLanes));
+    hip_check(hipMemset(lk_best_, 0, sizeof(unsigned long long) * kLanes), "memset");
+    hip_check(hipMemset(lk_state_, 0, sizeof(LlmLookupState)), "memset");
+    vlogits_ = dalloc((size_t)kLanes * cfg_.vocab);
+}
+
+void LlmModel::enqueue_verify(int rows, int ngram_max, int ngram_min, bool draft, bool record)
+{
+    if (draft) hip_check(launch_lookup_draft(lk_hist_, lk_state_, ngram_max, ngram_min, rows - 1, rows, vids_, stream_), "lookup draft");
+    pass(vids_, rows, true, true);
+    hip_check(launch_lookup_pick(vlogits_, cfg_.vocab, cfg_.vocab, rows, vids_, lk_best_, lk_state_, record ? lk_hist_ : nullptr, lk_hist_cap_,
+                                 pos_, record ? lk_log_ : nullptr, lk_hist_cap_, stream_), "lookup pick");
+}
+
+hipGraphExec_t LlmModel::lookup_graph(int rows, const LookupConfig& c)
+{
+    if (lookup_ngram_[0] != c.ngram_max || lookup_ngram_[1] != c.ngram_min) {  // (arguments of the captured draft launch)
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        for (hipGraphExec_t& g : lookup_graphs_) {
+            if (g) (void)hipGraphExecDestroy(g);
+            g = nullptr;
+        }
+        lookup_ngram_[0] = c.ngram_max;
+        lookup_ngram_[1] = c.ngram_min;
+    }
+    if (lookup_graphs_[rows]) return lookup_graphs_[rows];
+    hipGraph_t graph = nullptr;
+    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
+    try {
+        enqueue_verify(rows, c.ngram_max, c.ngram_min, true, true);
+    } catch (...) {
+        (void)hipStreamEndCapture(stream_, &graph);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
+    const hipError_t e = hipGraphInstantiate(&lookup_graphs_[rows], graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    hip_check(e, "graph instantiate");
+    return lookup_graphs_[rows];
+}
+
+int LlmModel::verify_step(uint32_t token, const uint32_t* draft, int n_draft, int rows, uint32_t* tokens_out, float* logits_out)
+{
+    if (n_draft < 0 || n_draft > kLookupMaxDraft) throw InvalidConfig("n_draft must be 0..7");
+    if (rows < n_draft + 1 || rows > kLanes) throw InvalidConfig("rows must be n_draft + 1 .. 8");
+    if (cache_len_ + rows > cache_cap_)
+        throw InvalidConfig("cache_len + rows (" + std::to_string(cache_len_) + " + " + std::to_string(rows) + ") exceeds the context of " +
+                            std::to_string(cache_cap_) + " tokens");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ensure_lookup();
+    uint32_t ids[kLanes];
+    ids[0] = token;
+    for (int r = 1; r < rows; ++r) ids[r] = r <= n_draft ? draft[r - 1] : ids[r - 1];
+    LlmLookupState st = {};
+    st.n = cache_len_ + 1;
+    st.m = n_draft;
+    hip_check(hipMemcpyAsync(vids_, ids, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, stream_), "H2D ids");
+    hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
+    hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    enqueue_verify(rows, 1, 1, false, false);
+    hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    for (int i = 0; i <= st.a; ++i) tokens_out[i] = (uint32_t)st.picks[i];
+    cache_len_ += st.a + 1;
+    last_rows_ = rows;
+    if (logits_out)
+        hip_check(hipMemcpy(logits_out, vlogits_, (size_t)(n_draft + 1) * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+    return st.a;
+}
+
+std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& prompt, const GenerateOptions& opt, const LookupConfig& lk,
+                                                const std::function<bool(uint32_t)>& on_token, LookupStats* stats)
+{
+    if (stats) *stats = LookupStats();
+    check_lookup_config(lk);
+    if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0) return generate(prompt, opt, on_token);  // not applicable
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
+    if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
+    ensure_lookup();
+    reset();
+    forward(prompt.data(), (int)prompt.size());
+    std::vector<uint32_t> out, all(prompt);
+    const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
+    const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
+    const size_t max_len = opt.max_len ? opt.max_len : prompt.size() + opt.max_new_tokens;
+    const size_t context_limit = std::min((size_t)cache_cap_, max_len);
+    const size_t max_new_tokens = opt.max_new_tokens;
+    bool done = max_new_tokens == 0;
+    auto take = [&](uint32_t tok) {  // generate()'s drain
+        if (all.size() >= context_limit || is_stop(tok)) {
+            done = true;
+            return;
+        }
+        all.push_back(tok);
+        out.push_back(tok);
+        if ((on_token && !on_token(tok)) || out.size() >= max_new_tokens) done = true;
+    };
+    if (done) return out;
+    // the first pick comes from the prompt's logits; the history on the device = the prompt + that pick
+    const uint32_t first = argmax();
+    take(first);
+    if (done) return out;
+    LlmLookupState st = {};
+    st.n = (int32_t)all.size();
+    hip_check(hipMemcpyAsync(lk_hist_, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+    hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
+    hip_check(hipStreamSynchronize(stream_), "sync");  // (`all` grows below: the copy must have read it)
+    const size_t burst = on_token ? 4 : 16;
+    std::vector<int32_t> toks(burst * kLanes), log(2 * burst);
+    int known_n = st.n, known_steps = 0;
+    while (!done) {
+        // a step of `rows` rows writes cache rows [pos, pos + rows) and moves pos by at most `rows`: `steps` of them stay inside
+        // the cache whatever they accept while cache_len_ + steps * rows <= capacity; near the end the steps get narrower
+        const int room = cache_cap_ - cache_len_;
+        if (room <= 0) break;
+        const int rows = std::min(lk.draft_tokens + 1, room);
+        const size_t steps = std::min(std::min(burst, (size_t)(room / rows)), max_new_tokens - out.size());
+        hipGraphExec_t exec = lookup_graph(rows, lk);
+        for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
+        hip_check(hipMemcpyAsync(toks.data(), lk_hist_ + known_n, steps * (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, stream_),
+                  "D2H tokens");
+        hip_check(hipMemcpyAsync(log.data(), lk_log_ + 2 * (size_t)known_steps, 2 * steps * sizeof(int32_t), hipMemcpyDeviceToHost, stream_),
+                  "D2H step log");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        size_t off = 0;
+        for (size_t i = 0; i < steps; ++i) {  // in order; tokens past the end are discarded
+            const int m = log[2 * i], a = log[2 * i + 1];
+            if (!done) {
+                if (stats) {
+                    if (rows == 1) ++stats->single_row_steps;
+                    else ++stats->verify_steps;
+                    stats->drafted_tokens += (uint64_t)m;
+                    stats->accepted_tokens += (uint64_t)a;
+                }
+                for (int j = 0; j <= a && !done; ++j) take((uint32_t)toks[off + (size_t)j]);
+            }
+            off += (size_t)a + 1;
+        }
+        known_n = st.n;
+        known_steps = st.steps;
+        cache_len_ = st.n - 1;
     }
     return out;
 }

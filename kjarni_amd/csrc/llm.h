@@ -59,6 +59,20 @@ struct LaneRequest {
 };
 
 struct LlmLaneState;  // llm_kernels.h
+struct LlmLookupState;
+
+// Prompt-lookup decoding: how the draft of a verify step is found in the sequence's own history.
+struct LookupConfig {
+    int draft_tokens = 7;  // 1..7 tokens drafted per step (a step verifies draft_tokens + 1 rows)
+    int ngram_max = 3;     // 1..4: the longest suffix of the history that is matched
+    int ngram_min = 1;     // 1..ngram_max: the shortest match that drafts anything
+};
+struct LookupStats {  // over the steps the host consumed
+    uint64_t verify_steps = 0, drafted_tokens = 0, accepted_tokens = 0, single_row_steps = 0;
+};
+// The draft rule on a host-side history (what the device kernel computes): the tokens drafted after `tokens`.
+std::vector<uint32_t> lookup_draft_host(const uint32_t* tokens, size_t n, const LookupConfig& config);
+void check_lookup_config(const LookupConfig& config);  // InvalidConfig naming the field
 
 class LlmModel {
 public:
@@ -131,6 +145,26 @@ public:
     uint64_t lane_stream_calls() const { return lane_stream_calls_; }
     uint64_t lane_fallback_calls() const { return lane_fallback_calls_; }
 
+    // ---- prompt-lookup decoding: greedy generate() that emits several tokens per step ----------------------------------------
+    // generate() for a greedy request without logits processors, with every step verifying a draft: the continuation of the
+    // latest longest n-gram match in the prompt + the tokens so far (launch_lookup_draft) runs with the last token as one block
+    // of draft_tokens + 1 rows at the device-held position (verify_pass: causal inside the block, K / V rows into the cache,
+    // every row through the final norm and the vocabulary head), and the pick keeps the model's own argmax tokens up to and
+    // including the first one that differs from the draft.  Draft, step and pick are one chain of launches captured once per
+    // row count and replayed in bursts (generate()'s cadences); near the end of the cache the steps have fewer rows, so that
+    // nothing is written at or past the capacity.  Every emitted token is an argmax of the model's logits: the ids are
+    // generate()'s wherever the two best logits are further apart than the float bar (the multi-row kernels sum in another
+    // order).  A request that samples or has a processor runs generate() unchanged (stats stay zero).
+    std::vector<uint32_t> generate_lookup(const std::vector<uint32_t>& prompt, const GenerateOptions& options, const LookupConfig& lookup,
+                                          const std::function<bool(uint32_t)>& on_token, LookupStats* stats);
+    // Test hook: one verify step on the cache as it stands: `token` and draft[n_draft] as rows 0..n_draft of a block of `rows`
+    // rows (n_draft + 1 .. 8; the rows past the draft repeat its last id).  Returns the accepted length a; tokens_out[0..a] are
+    // the picks, the cache grows by a + 1; logits_out (may be null) receives rows [0, n_draft] of the logits.
+    int verify_step(uint32_t token, const uint32_t* draft, int n_draft, int rows, uint32_t* tokens_out, float* logits_out);
+    // Projections of verify steps that took the multi-row weight-streaming kernel / fell back (counted when enqueued).
+    uint64_t verify_stream_calls() const { return verify_stream_calls_; }
+    uint64_t verify_fallback_calls() const { return verify_fallback_calls_; }
+
 private:
     LlmModel() = default;
     void ensure_lanes(int lanes, int lane_context);
@@ -143,9 +177,15 @@ private:
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
-    void pass(const uint32_t* ids_dev, int n, bool device_pos);
-    void pass_quant(const uint32_t* ids_dev, int n, bool device_pos);  // pass() on quantized matrices (quant_kernels.hip)
-    void pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos);   // pass() for a GPT-2 layer stack
+    // verify (prompt-lookup): the projections take the multi-row weight-streaming kernel where it applies (verify_gemv), the
+    // one-row fusions are off, and the final norm and the vocabulary head run over every row, into vlogits_ [n, vocab]
+    void pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);
+    void pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);  // pass() on quantized matrices (quant_kernels.hip)
+    void pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);   // pass() for a GPT-2 layer stack
+    void verify_gemv(const struct LlmGemvArgs& a, const char* what);
+    void ensure_lookup();
+    void enqueue_verify(int rows, int ngram_max, int ngram_min, bool draft, bool record);  // [draft ->] step -> pick
+    hipGraphExec_t lookup_graph(int rows, const LookupConfig& config);
     void load_gpt2(SafeTensors& st, int weights);                      // GPT-2 tensors (Conv1D matrices transposed on the host)
     void finish_load();                                                // attention splits, workspace, stream
     // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
@@ -221,6 +261,17 @@ private:
     int *lane_pcounts_ = nullptr, *lane_pndistinct_ = nullptr;
     hipGraphExec_t lane_graphs_[kLanes + 1] = {};
     uint64_t lane_stream_calls_ = 0, lane_fallback_calls_ = 0;
+    // prompt-lookup decoding (allocated on first use): the ids and logits rows of a verify step, the device state, the history
+    // (prompt + picks), the per-step (m, a) log, and one captured chain per row count for the n-gram bounds in lookup_ngram_
+    float* vlogits_ = nullptr;
+    uint32_t* vids_ = nullptr;
+    LlmLookupState* lk_state_ = nullptr;
+    int32_t *lk_hist_ = nullptr, *lk_log_ = nullptr;
+    unsigned long long* lk_best_ = nullptr;
+    int lk_hist_cap_ = 0;
+    hipGraphExec_t lookup_graphs_[kLanes + 1] = {};
+    int lookup_ngram_[2] = {0, 0};
+    uint64_t verify_stream_calls_ = 0, verify_fallback_calls_ = 0;
 };
 
 }  // namespace kjarni

@@ -115,6 +115,26 @@ hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_hea
 hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
                             LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
 
+// ---- prompt-lookup decoding (LlmModel::generate_lookup): draft from the sequence's own history, verify in one multi-row step
+constexpr int kLookupMaxDraft = 7, kLookupMaxNgram = 4;
+struct LlmLookupState {
+    int32_t n;          // history length: the prompt, then every pick; the last entry is the token that is not in the cache yet
+    int32_t steps;      // verify steps since the host last zeroed it = entries of the step log
+    int32_t m;          // draft length of the step in flight (rows 1..m of its ids)
+    int32_t a;          // drafted tokens the last step accepted
+    int32_t picks[8];   // its picks p_0..p_a
+};
+// The draft rule (longest match of ngram_min..ngram_max tokens against the history's suffix, then the longest continuation
+// up to draft_tokens <= rows - 1, then the latest) on history[0, state->n): ids[0] = the last token, ids[1..m] = the draft, the
+// other rows repeat the last of them; state->m = m.  One launch of one workgroup, order-free reduction.
+hipError_t launch_lookup_draft(const int32_t* history, LlmLookupState* state, int ngram_max, int ngram_min, int draft_tokens, int rows,
+                               uint32_t* ids, hipStream_t stream);
+// The verify pick on logits [rows, ld] (two launches): per-row argmax p_i (last maximum wins), a = the longest prefix with
+// ids[1 + i] == p_i, i < a <= state->m; p_0..p_a go to state->picks and history[state->n ..] (may be null), state->n and *pos
+// advance by a + 1, (m, a) goes to log[2 * state->steps ..] (may be null).  best_scratch: 8 zero-initialised u64 (re-zeroed).
+hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int rows, const uint32_t* ids, unsigned long long* best_scratch,
+                              LlmLookupState* state, int32_t* history, int hist_cap, int* pos, int32_t* log, int log_cap, hipStream_t stream);
+
 // ---- sampled decoding: the O(vocab) part on the device (llm_kernels.hip) ----------------------------------------------
 struct SampleHeader {   // 32 bytes, device memory mirrored to the host per sampled token
     float mx;           // maximum logit

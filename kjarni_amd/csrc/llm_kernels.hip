@@ -2520,4 +2520,132 @@ hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lane
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Prompt-lookup decoding (llm.cpp: LlmModel::generate_lookup): the draft of the next verify step, and its pick.
+namespace {
+
+constexpr int LOOKUP_THREADS = 1024;
+
+// The draft rule on the history T[0, n) (n = st->n; T[n - 1] is the token that is not in the cache yet): over every e in
+// [1, n) with a match of length m in [ngram_min, ngram_max] that ends just before e against the suffix of T, the largest
+// (m, min(D, n - e), e) -- longest match, then longest continuation, then latest -- packed into one u64 and reduced with
+// max, which is order-free: the result does not depend on how the threads share the positions.  One workgroup; it loops
+// over a long history (131 072 tokens: 128 positions per thread, at most ngram_max + 1 loads each).
+// ids[0] = T[n - 1], ids[1..c] = T[e .. e + c), rows past the draft repeat the last valid id; st->m = c.
+__global__ __launch_bounds__(LOOKUP_THREADS) void lookup_draft_kernel(const int32_t* __restrict__ T, LlmLookupState* __restrict__ st,
+                                                                      int ngram_max, int ngram_min, int D, int rows,
+                                                                      uint32_t* __restrict__ ids)
+{
+    __shared__ unsigned long long red[LOOKUP_THREADS / kWave];
+    const int n = st->n, tid = threadIdx.x;
+    unsigned long long key = 0ull;  // (every valid key has m >= 1: non-zero)
+    for (int e = 1 + tid; e < n; e += LOOKUP_THREADS) {
+        int m = 0;
+        while (m < ngram_max && e - 1 - m >= 0 && T[e - 1 - m] == T[n - 1 - m]) ++m;
+        if (m < ngram_min) continue;
+        const int c = min(D, n - e);
+        const unsigned long long k = ((unsigned long long)m << 40) | ((unsigned long long)c << 32) | (uint32_t)e;
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off, kWave);
+        key = o > key ? o : key;
+    }
+    if ((tid & (kWave - 1)) == 0) red[tid / kWave] = key;
+    __syncthreads();
+    if (tid >= rows) return;
+    key = red[0];
+    for (int w = 1; w < LOOKUP_THREADS / kWave; ++w) key = red[w] > key ? red[w] : key;
+    int c = (int)((key >> 32) & 0xFFull);
+    c = c < rows - 1 ? c : rows - 1;
+    const int e = (int)(uint32_t)(key & 0xFFFFFFFFull);
+    int src = n - 1;                               // row 0, and the pad rows of an empty draft
+    if (tid > 0 && c > 0) src = e + (tid <= c ? tid : c) - 1;
+    ids[tid] = n > 0 ? (uint32_t)T[src] : 0u;
+    if (tid == 0) st->m = c;
+}
+
+// Row-wise argmax of logits [rows, ld], the last maximum wins (argmax_key): blockIdx.y is the row.
+__global__ __launch_bounds__(256) void lookup_argmax_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                                    unsigned long long* __restrict__ best)
+{
+    __shared__ unsigned long long red[4];
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    unsigned long long key = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
+        const unsigned long long kk = argmax_key(row[i], i);
+        key = kk > key ? kk : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off, kWave);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) key = red[w] > key ? red[w] : key;
+        atomicMax(best + blockIdx.y, key);
+    }
+}
+
+// The verify pick: p_i = argmax(row i); a = the longest prefix of the draft with ids[1 + i] == p_i; p_0..p_a are the model's
+// own greedy tokens after the history, so they join it (and st->picks), the position advances by a + 1 (the rows of the
+// rejected and pad positions lie beyond it and are overwritten by the next step), and (m, a) joins the step log.
+__global__ void lookup_pick_kernel(unsigned long long* __restrict__ best, const uint32_t* __restrict__ ids, int rows,
+                                   LlmLookupState* __restrict__ st, int32_t* __restrict__ history, int hist_cap, int* __restrict__ pos,
+                                   int32_t* __restrict__ log, int log_cap)
+{
+    if (threadIdx.x != 0) return;
+    int32_t p[LLM_MAX_ROWS];
+    for (int i = 0; i < rows; ++i) {
+        p[i] = (int32_t)(uint32_t)(best[i] & 0xFFFFFFFFull);
+        best[i] = 0ull;
+    }
+    int m = st->m;
+    m = m < rows - 1 ? m : rows - 1;
+    int a = 0;
+    while (a < m && ids[1 + a] == (uint32_t)p[a]) ++a;
+    const int n = st->n;
+    for (int i = 0; i <= a; ++i) {
+        st->picks[i] = p[i];
+        if (history && n + i < hist_cap) history[n + i] = p[i];
+    }
+    st->n = n + a + 1;
+    st->a = a;
+    *pos += a + 1;
+    const int s = st->steps;
+    if (log && s < log_cap) {
+        log[2 * s] = m;
+        log[2 * s + 1] = a;
+    }
+    st->steps = s + 1;
+}
+
+}  // namespace
+
+hipError_t launch_lookup_draft(const int32_t* history, LlmLookupState* state, int ngram_max, int ngram_min, int draft_tokens, int rows,
+                               uint32_t* ids, hipStream_t stream)
+{
+    if (rows < 1 || rows > LLM_MAX_ROWS || ngram_max < 1 || ngram_max > kLookupMaxNgram || ngram_min < 1 || ngram_min > ngram_max ||
+        draft_tokens < 0 || draft_tokens > rows - 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lookup_draft_kernel, dim3(1), dim3(LOOKUP_THREADS), 0, stream, history, state, ngram_max, ngram_min, draft_tokens, rows,
+                       ids);
+    return hipGetLastError();
+}
+
+hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int rows, const uint32_t* ids, unsigned long long* best_scratch,
+                              LlmLookupState* state, int32_t* history, int hist_cap, int* pos, int32_t* log, int log_cap, hipStream_t stream)
+{
+    if (rows < 1 || rows > LLM_MAX_ROWS) return hipErrorInvalidValue;
+    int blocks = (vocab + 2047) / 2048;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(lookup_argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab,
+                       best_scratch);
+    hipLaunchKernelGGL(lookup_pick_kernel, dim3(1), dim3(64), 0, stream, best_scratch, ids, rows, state, history, hist_cap, pos, log, log_cap);
+    return hipGetLastError();
+}
+
 }  // namespace kjarni

@@ -178,3 +178,46 @@ class HipDecoder:
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_lane_gemv_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+    # ---- prompt-lookup decoding: greedy generation that verifies a draft from its own history every step ----
+    def generate_lookup(self, prompt: Sequence[int], max_new_tokens: int, draft_tokens: int = 7, ngram_max: int = 3, ngram_min: int = 1,
+                        stop_ids: Optional[Sequence[int]] = None, on_token: Optional[Callable[[int], Optional[bool]]] = None):
+        """generate() for a greedy request through the lookup loop: (ids, stats), stats = verify_steps, drafted_tokens,
+        accepted_tokens and single_row_steps over the steps the host consumed.  stop_ids (default: config.json's eos ids)
+        end the call and are not emitted."""
+        p = np.ascontiguousarray(prompt, np.uint32)
+        out = np.empty(max(max_new_tokens, 1), np.uint32)
+        n = C.c_size_t(0)
+        cfg = _ffi.KjarniHipLookupConfig(draft_tokens, ngram_max, ngram_min)
+        st = _ffi.KjarniHipLookupStats()
+        stops = np.ascontiguousarray(stop_ids if stop_ids is not None else [], np.uint32)
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_lookup(self._h, u32(p), p.size, max_new_tokens, u32(stops) if stops.size else None,
+                                                             stops.size, C.byref(cfg), fn, None, u32(out), out.size, C.byref(n), C.byref(st)))
+        stats = {k: int(getattr(st, k)) for k, _ in _ffi.KjarniHipLookupStats._fields_}
+        return out[:min(n.value, out.size)].tolist(), stats
+
+    def verify_step(self, token: int, draft: Sequence[int], rows: Optional[int] = None):
+        """Test hook: one verify step of `rows` rows (default len(draft) + 1) on the cache as it stands.  Returns (picks,
+        accepted, logits [len(draft) + 1, vocab]); the cache grows by accepted + 1."""
+        d = np.ascontiguousarray(draft, np.uint32)
+        rows = d.size + 1 if rows is None else int(rows)
+        picks = np.zeros(8, np.uint32)
+        a = C.c_int32(0)
+        logits = np.empty((d.size + 1, self.vocab), np.float32)
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_verify_step(self._h, int(token), u32(d) if d.size else None, d.size, rows, u32(picks), C.byref(a),
+                                                         logits.ctypes.data_as(C.POINTER(C.c_float))))
+        return picks[:a.value + 1].tolist(), int(a.value), logits
+
+    def verify_gemv_calls(self):
+        """(streamed, fallback): projections of verify steps that took the multi-row weight-streaming kernel / the
+        one-wave-per-column kernel since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_verify_gemv_calls(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)

@@ -65,6 +65,17 @@ class Generator:
         """Lanes generate_batch() runs with (1..8, 0 = 8)."""
         check_error(lib().kjarni_hip_generator_set_lanes(self._handle, lanes))
 
+    def set_prompt_lookup(self, draft_tokens: int):
+        """Prompt-lookup decoding for generate() / stream(): 0 = off (the default), 1..7 drafted tokens per step.  Applies to
+        greedy configs without a repetition penalty or an n-gram ban; the text is the plain path's."""
+        check_error(lib().kjarni_hip_generator_set_prompt_lookup(self._handle, draft_tokens))
+
+    def verify_gemv_calls(self):
+        """(streamed, fallback) projections of prompt-lookup verify steps since load: moves only when a call took the lookup loop."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_generator_verify_gemv_calls(self._handle, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def stream(self, prompt: str, on_token: Callable[[str], bool], config: Optional[GenerationConfig] = None, cancel=None):
         cb = _stream_cb(on_token)
         check_error(lib().kjarni_generator_stream(self._handle, prompt.encode("utf-8"), _gen(config), cb, None,

@@ -188,6 +188,21 @@ def set_cosine_variant(v: int):
     _tuning("kjarni_hip_set_cosine_variant")(int(v))
 
 
+def lookup_draft(tokens, draft_tokens: int = 7, ngram_max: int = 3, ngram_min: int = 1, device: Optional[int] = 0):
+    """The prompt-lookup draft after the history `tokens` (a list of ids): the device kernel, or with device=None the host
+    restatement of the same rule."""
+    t = np.ascontiguousarray(tokens, np.uint32)
+    cfg = _ffi.KjarniHipLookupConfig(draft_tokens, ngram_max, ngram_min)
+    out = np.zeros(8, np.uint32)
+    n = C.c_int32(0)
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+    if device is None:
+        check_error(lib().kjarni_lookup_draft(u32(t), t.size, C.byref(cfg), u32(out), C.byref(n)))
+    else:
+        check_error(lib().kjarni_hip_op_lookup_draft(device, u32(t), t.size, C.byref(cfg), u32(out), C.byref(n)))
+    return out[:n.value].tolist()
+
+
 def topk(scores, k: int, device: int = 0):
     """Top-k of a score matrix [nq, n] on the GPU (kjarni_hip_cosine_topk): (idx int64 [nq,k], score f32 [nq,k]),
     score descending, equal scores by ascending index; entries past n are (-1, -inf)."""

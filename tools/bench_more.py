@@ -22,6 +22,12 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            the single-stream generate() of the same build, alternated twice in one process: Llama-3.2-1B shape (bf16),
            gpt2-small (bf16, f32) and the 1B shape as a GGUF Q4_K_M-style mix; 128-token prompts; aggregate tokens/s and
            ms per lock-step step.  KJARNI_LANES_STEPS=N: N steps at 8 lanes on the Llama shape only (for a kernel trace).
+  llm_lookup  (only on request) prompt-lookup decoding against plain generate() of the same build, alternated twice in one
+           process: Llama-3.2-1B shape (bf16) and gpt2-small (bf16); ms per plain step, ms per verify step at 2 / 4 / 8 rows
+           (HipDecoder.verify_step in a loop with a fixed draft, and the replayed graph inside generate_lookup), the break-even
+           acceptance verify_ms / plain_ms - 1, and end-to-end tokens/s with the acceptance histogram -- on a random-init
+           model, whose greedy output degenerates into repetition: the full-acceptance end of the range, not a workload.
+           KJARNI_LOOKUP_STEPS=N: N verify steps of 8 rows on the Llama shape only (for a kernel trace).
 """
 import json
 import os
@@ -794,6 +800,100 @@ def main():
             gguf_fixture.gguf_model(gpath, qcfg, gguf_fixture.q4_k_m_types(qcfg["num_hidden_layers"]), seed=0, rope_freqs=True, keep_hf=False)
             dec = kjarni_amd.HipDecoder(gpath, max_context=2048)
             measure("Llama-3.2-1B shape, GGUF Q4_K_M-style mix (Q4_K / Q6_K in HBM)", dec, prompts, 512, "Q4_K / Q6_K weights, f32 activations/KV")
+            del dec
+
+    if "llm_lookup" in which:
+        # Method (measuring guide, section 5; as llm_lanes): one process on one box; the plain step graph, the verify hook at
+        # every row count and the lookup graphs are warmed first; then plain generate() -- the yardstick -- alternates with the
+        # verify-step loops (2 / 4 / 8 rows) and generate_lookup (draft_tokens 1 / 3 / 7 = 2 / 4 / 8 rows), twice.  A decode window
+        # is a whole generation minus the same call cut after its first token (prefill and first pick).
+        from tests import gpt2_fixture
+        from tests import lookup_cases
+        rng = np.random.default_rng(0)
+        trace_steps = int(os.environ.get("KJARNI_LOOKUP_STEPS", "0"))
+        ROWS = (2, 4, 8)
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def verify_loop(dec, prompt, draft, rows, steps):
+            """ms per verify_step call: a fixed draft, so the acceptance (and the time) does not depend on the weights' values."""
+            dec.reset()
+            dec.forward(prompt, fetch=False)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                dec.verify_step(prompt[-1], draft[:rows - 1], rows)
+            return (time.perf_counter() - t0) * 1e3 / steps
+
+        def measure(label, dec, prompt, n_new, dtype):
+            draft = prompt[:7]
+            if trace_steps:  # a short run for rocprofv3 --kernel-trace --stats: trace_steps verify steps of 8 rows
+                verify_loop(dec, prompt, draft, 8, trace_steps)
+                return
+            dec.generate(prompt, 8)
+            for rows in ROWS:
+                verify_loop(dec, prompt, draft, rows, 8)
+                dec.generate_lookup(prompt, 40, draft_tokens=rows - 1)
+            plain_ms, plain_rate, hook, replay, e2e = [], [], {}, {}, {}
+            hist = {}
+            for rep in range(2):
+                for rows in ROWS:
+                    dt, out = window(lambda: dec.generate(prompt, n_new), lambda: dec.generate(prompt, 1))
+                    assert len(out) == n_new
+                    plain_ms.append(dt * 1e3 / (n_new - 1))
+                    plain_rate.append((n_new - 1) / dt)
+                    hook.setdefault(rows, []).append(verify_loop(dec, prompt, draft, rows, 64))
+                    dt, (got, st) = window(lambda: dec.generate_lookup(prompt, n_new, draft_tokens=rows - 1),
+                                           lambda: dec.generate_lookup(prompt, 1, draft_tokens=rows - 1))
+                    assert len(got) == n_new
+                    same = got == out
+                    steps = st["verify_steps"] + st["single_row_steps"]
+                    replay.setdefault(rows, []).append(dt * 1e3 / steps)
+                    e2e.setdefault(rows, []).append({"tokens_per_s": round((n_new - 1) / dt, 1), "verify_steps": steps,
+                                                     "drafted": st["drafted_tokens"], "accepted": st["accepted_tokens"],
+                                                     "ids_equal_plain": same})
+                    h = {}
+                    for _, a in lookup_cases.simulate(prompt, got, (rows - 1, 3, 1)):
+                        h[a] = h.get(a, 0) + 1
+                    hist[rows] = {str(k): h[k] for k in sorted(h)}
+            plain = float(np.median(plain_ms))
+            med = lambda xs: float(np.median(xs))  # noqa: E731
+            emit({"metric": f"prompt-lookup decoding, {label}", "unit": "ms per step", "value": round(med(replay[8]), 4), "n_gpus": 1,
+                  "dtype": dtype, "data": "synthetic",
+                  "config": {"workload": f"{label}, random init, one 128-token prompt, {n_new} generated tokens; plain generate() alternated "
+                                         "twice with verify-step loops and generate_lookup at 2 / 4 / 8 rows in one process",
+                             "note": "random-init greedy output degenerates into repetition: the end-to-end rows are the full-acceptance "
+                                     "end of the range, not a workload"},
+                  "plain_ms_per_step": {"median": round(plain, 4), "min": round(min(plain_ms), 4), "max": round(max(plain_ms), 4),
+                                        "runs": [round(x, 4) for x in plain_ms]},
+                  "plain_tokens_per_s": round(med(plain_rate), 1),
+                  "verify_ms_per_step_hook": {str(r): [round(x, 4) for x in hook[r]] for r in ROWS},        # uncaptured, host sync per step
+                  "verify_ms_per_step_replayed": {str(r): [round(x, 4) for x in replay[r]] for r in ROWS},  # inside generate_lookup
+                  "verify_over_plain_replayed": {str(r): round(med(replay[r]) / plain, 3) for r in ROWS},
+                  "break_even_accepted_per_step_replayed": {str(r): round(med(replay[r]) / plain - 1, 3) for r in ROWS},
+                  "break_even_accepted_per_step_hook": {str(r): round(med(hook[r]) / plain - 1, 3) for r in ROWS},
+                  "generate_lookup": {str(r): e2e[r] for r in ROWS}, "accepted_histogram": {str(r): hist[r] for r in ROWS},
+                  "x_plain_tokens_per_s": {str(r): round(max(x["tokens_per_s"] for x in e2e[r]) / med(plain_rate), 2) for r in ROWS},
+                  "weight_bytes": dec.weight_bytes})
+
+        d = os.path.join(tmp, "llama-1b-lookup")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, rng.integers(1000, 100000, 128).tolist(), 512,
+                "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        if not trace_steps:  # (the trace run is the Llama shape alone)
+            gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+            gd = os.path.join(tmp, "gpt2-small-lookup")
+            gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+            dec = kjarni_amd.HipDecoder(gd)
+            measure("gpt2-small shape, bf16 weights", dec, rng.integers(0, 50257, 128).tolist(), 512,
+                    "bf16 weights, f32 activations/accumulate/KV")
             del dec
 
 
