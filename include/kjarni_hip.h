@@ -602,6 +602,37 @@ KjarniErrorCode kjarni_hip_decoder_generate_lookup(KjarniHipDecoder* decoder, co
 /* The draft kernel alone on a host-given history: draft_out[7], *n_out = draft length. */
 KjarniErrorCode kjarni_hip_op_lookup_draft(int32_t device, const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config,
                                            uint32_t* draft_out, int32_t* n_out);
+/* The token-selection kernels alone, on logits given by the host; each entry runs the launcher the models run, on scratch
+ * zero-initialised as theirs, with a guard band behind every output buffer (INFERENCE_FAILED when one is touched, or when
+ * the kernels leave device state other than the contract of their launcher).
+ *
+ * kjarni_hip_op_argmax: `calls` independent greedy picks over logits [calls, rows, ld] (ld >= vocab), the last of equal
+ * maxima wins.  DECODER: rows == 1, the replayed single-sequence pick.  LANES: rows <= 8, live[rows] says which lanes pick;
+ * picks_out of a frozen lane is -1 and its token / history must come back untouched.  LOOKUP: rows <= 8, the verify pick with
+ * the draft draft[calls, n_draft] (n_draft <= rows - 1): accepted_out[call] = a, the longest prefix of the draft that equals
+ * the rows' own picks; picks_out[call, 0..a] = p_0..p_a, -1 past them.  picks_out is [calls, rows]. */
+typedef enum KjarniHipArgmaxRoute { KJARNI_HIP_ARGMAX_DECODER = 0, KJARNI_HIP_ARGMAX_LANES = 1, KJARNI_HIP_ARGMAX_LOOKUP = 2 } KjarniHipArgmaxRoute;
+KjarniErrorCode kjarni_hip_op_argmax(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld, int32_t vocab, int32_t route,
+                                     const int32_t* live, const uint32_t* draft, int32_t n_draft, int32_t* picks_out, int32_t* accepted_out);
+/* Whisper's pick (argmax over the ids that may be produced, the last of equal maxima wins; eos when none can) over logits
+ * [calls, lanes, vocab], lanes <= 8: two_launch == 0 the one-workgroup-per-lane kernel, else the two-launch form of the replayed
+ * step.  tokens_out is [calls, lanes]. */
+KjarniErrorCode kjarni_hip_op_whisper_pick(int32_t device, const float* logits, int32_t calls, int32_t lanes, int32_t vocab,
+                                           int32_t first_special, int32_t eos, int32_t timestamp_begin, int32_t allow_timestamps,
+                                           int32_t two_launch, int32_t* tokens_out);
+/* Repetition penalty and n-gram ban (0 = off) of the history tokens[n] on logits[vocab], the per-token counts built as a
+ * generate call builds them: one launch over the first n_bulk tokens, one per later token.  Ids >= vocab are ignored. */
+KjarniErrorCode kjarni_hip_op_logits_processors(int32_t device, const float* logits, int32_t vocab, const uint32_t* tokens, int32_t n,
+                                                int32_t n_bulk, float repetition_penalty, int32_t no_repeat_ngram, float* logits_out);
+/* The sampler's cut: what the device hands to the host per sampled token.  Row c of `logits` holds vocabs[c] floats, the rows
+ * packed one after another; the calls run in order on ONE scratch, header and candidate buffer, as consecutive tokens of a
+ * generate call do.  top_k / top_p / min_p negative = not set.  Per call: the header, and in ids_out / logits_out
+ * [calls, capacity] the first min(count, capacity) candidates (every token with logit >= floor, in no particular order).
+ * overflow = 1: count exceeds the capacity, or no cut could be placed -- the list is not usable. */
+typedef struct KjarniHipSampleHeader { float mx, sum, floor; uint32_t count, overflow; } KjarniHipSampleHeader;
+KjarniErrorCode kjarni_hip_op_sample_candidates(int32_t device, const float* logits, const int32_t* vocabs, int32_t calls, int64_t top_k,
+                                                float top_p, float min_p, int32_t capacity, KjarniHipSampleHeader* headers_out,
+                                                uint32_t* ids_out, float* logits_out);
 /* Host restatement of the same rule (no GPU). */
 KjarniErrorCode kjarni_lookup_draft(const uint32_t* tokens, size_t n, const KjarniHipLookupConfig* config, uint32_t* draft_out,
                                     int32_t* n_out);
@@ -660,6 +691,11 @@ KjarniErrorCode kjarni_sampling_distribution(const float* logits, size_t vocab, 
 KjarniErrorCode kjarni_sampling_distribution_candidates(const float* logits, size_t vocab, float tau, float temperature, int64_t top_k,
                                                         float top_p, float min_p, float* probs_out, int32_t* decided,
                                                         size_t* n_candidates);
+/* The same decision from a candidate list as the device hands it over (no GPU, no emulation): ids / vals [n] in any order,
+ * the header's mx, floor and sum.  An id >= vocab: INVALID_CONFIG. */
+KjarniErrorCode kjarni_sampling_distribution_from_candidates(const uint32_t* ids, const float* vals, size_t n, float mx, float floor, float sum,
+                                                             size_t vocab, float temperature, int64_t top_k, float top_p, float min_p,
+                                                             float* probs_out, int32_t* decided);
 uint32_t kjarni_sample_from_probs(const float* probs, size_t vocab, float uniform);
 KjarniErrorCode kjarni_logits_process(float* logits, size_t vocab, const uint32_t* tokens, size_t n_tokens, float repetition_penalty,
                                       size_t no_repeat_ngram);

@@ -238,6 +238,10 @@ class KjarniHipLookupConfig(Structure):
     _fields_ = [("draft_tokens", c_int32), ("ngram_max", c_int32), ("ngram_min", c_int32)]
 
 
+class KjarniHipSampleHeader(Structure):
+    _fields_ = [("mx", c_float), ("sum", c_float), ("floor", c_float), ("count", C.c_uint32), ("overflow", C.c_uint32)]
+
+
 class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
@@ -391,6 +395,8 @@ SIGNATURES = {
     "kjarni_sampling_distribution": (c_int32, [_f32p, c_size_t, c_float, c_int64, c_float, c_float, _f32p]),
     "kjarni_sampling_distribution_candidates": (c_int32, [_f32p, c_size_t, c_float, c_float, c_int64, c_float, c_float, _f32p,
                                                         POINTER(c_int32), POINTER(c_size_t)]),
+    "kjarni_sampling_distribution_from_candidates": (c_int32, [_u32p, _f32p, c_size_t, c_float, c_float, c_float, c_size_t, c_float, c_int64,
+                                                             c_float, c_float, _f32p, POINTER(c_int32)]),
     "kjarni_sample_from_probs": (C.c_uint32, [_f32p, c_size_t, c_float]),
     "kjarni_logits_process": (c_int32, [_f32p, c_size_t, _u32p, c_size_t, c_float, c_size_t]),
     "kjarni_generation_resolve": (c_int32, [c_char_p, c_size_t, c_char_p, c_int32, POINTER(KjarniGenerationConfig),
@@ -446,6 +452,13 @@ SIGNATURES = {
                                                      KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
                                                      POINTER(KjarniHipLookupStats)]),
     "kjarni_hip_op_lookup_draft": (c_int32, [c_int32, _u32p, c_size_t, POINTER(KjarniHipLookupConfig), _u32p, POINTER(c_int32)]),
+    "kjarni_hip_op_argmax": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int64, c_int32, c_int32, POINTER(c_int32), _u32p, c_int32,
+                                       POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_op_whisper_pick": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             POINTER(c_int32)]),
+    "kjarni_hip_op_logits_processors": (c_int32, [c_int32, _f32p, c_int32, _u32p, c_int32, c_int32, c_float, c_int32, _f32p]),
+    "kjarni_hip_op_sample_candidates": (c_int32, [c_int32, _f32p, POINTER(c_int32), c_int32, c_int64, c_float, c_float, c_int32,
+                                                  POINTER(KjarniHipSampleHeader), _u32p, _f32p]),
     "kjarni_lookup_draft": (c_int32, [_u32p, c_size_t, POINTER(KjarniHipLookupConfig), _u32p, POINTER(c_int32)]),
     "kjarni_hip_decoder_verify_step": (c_int32, [c_void_p, C.c_uint32, _u32p, c_int32, c_int32, _u32p, POINTER(c_int32), _f32p]),
     "kjarni_hip_decoder_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),

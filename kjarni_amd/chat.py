@@ -282,6 +282,23 @@ def sampling_distribution_candidates(logits, tau: float, temperature: float = 1.
     return (out if decided.value else None), int(n.value)
 
 
+def sampling_distribution_from_candidates(ids, vals, mx: float, floor: float, total: float, vocab: int, temperature: float = 1.0,
+                                          top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None):
+    """The distribution decided from a candidate list as the device hands it over: every (id, logit) with logit >= floor in any
+    order, the maximum `mx` and the sum `total` of exp(logit - mx) over the vocabulary.  Returns probs, or None when the
+    candidates do not decide it."""
+    i = np.ascontiguousarray(ids, np.uint32)
+    v = np.ascontiguousarray(vals, np.float32)
+    out = np.zeros(vocab, np.float32)
+    f = C.POINTER(C.c_float)
+    decided = C.c_int32(0)
+    check_error(lib().kjarni_sampling_distribution_from_candidates(i.ctypes.data_as(C.POINTER(C.c_uint32)), v.ctypes.data_as(f), i.size, mx, floor,
+                                                                   total, vocab, temperature, -1 if top_k is None else top_k,
+                                                                   -1.0 if top_p is None else top_p, -1.0 if min_p is None else min_p,
+                                                                   out.ctypes.data_as(f), C.byref(decided)))
+    return out if decided.value else None
+
+
 def sample_from_probs(probs, uniform: float) -> int:
     p = np.ascontiguousarray(probs, np.float32)
     return int(lib().kjarni_sample_from_probs(p.ctypes.data_as(C.POINTER(C.c_float)), p.size, uniform))

@@ -491,26 +491,47 @@ KJARNI_EXPORT KjarniErrorCode kjarni_sampling_distribution(const float* logits, 
 }
 
 // The candidate form of the same distribution (what the decode loop uses: the device hands over every token within `tau`
-// of the maximum + the maximum + the sum of exp over the vocabulary; sampling.h).  Here the device's part is emulated on
-// the host (sum accumulated in double: a different rounding order, as on the device), so the CPU suite can hold the
-// candidate form to the full one.  *decided = 0: the candidates do not decide the distribution (probs_out untouched).
-KJARNI_EXPORT KjarniErrorCode kjarni_sampling_distribution_candidates(const float* logits, size_t vocab, float tau, float temperature,
-                                                                      int64_t top_k, float top_p, float min_p, float* probs_out,
-                                                                      int32_t* decided, size_t* n_candidates)
+// of the maximum + the maximum + the sum of exp over the vocabulary; sampling.h), decided from a list given by the caller.
+// *decided = 0: the candidates do not decide the distribution (probs_out untouched).
+KJARNI_EXPORT KjarniErrorCode kjarni_sampling_distribution_from_candidates(const uint32_t* ids, const float* vals, size_t n, float mx,
+                                                                           float floor, float sum, size_t vocab, float temperature,
+                                                                           int64_t top_k, float top_p, float min_p, float* probs_out,
+                                                                           int32_t* decided)
 {
-    if (!logits || !probs_out || !decided) return KJARNI_ERROR_NULL_POINTER;
+    if ((n && (!ids || !vals)) || !probs_out || !decided) return KJARNI_ERROR_NULL_POINTER;
+    *decided = 0;
     return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        for (size_t i = 0; i < n; ++i)
+            if (ids[i] >= vocab) throw InvalidConfig("candidate id " + std::to_string(ids[i]) + " is not below the vocabulary size");
         SamplingParams p;
         p.temperature = temperature;
         p.top_k = top_k;
         p.top_p = top_p;
         p.min_p = min_p;
-        float mx = -std::numeric_limits<float>::infinity();
+        std::vector<uint32_t> kept;
+        std::vector<float> probs;
+        *decided = sampling_distribution_candidates(ids, vals, n, mx, floor, sum, vocab, p, kept, probs) ? 1 : 0;
+        if (*decided) {
+            std::fill(probs_out, probs_out + vocab, 0.0f);
+            for (size_t i = 0; i < kept.size(); ++i) probs_out[kept[i]] = probs[i];
+        }
+    });
+}
+
+// The same with the device's part emulated on the host (sum accumulated in double: a different rounding order, as on the
+// device), so the CPU suite can hold the candidate form to the full one.
+KJARNI_EXPORT KjarniErrorCode kjarni_sampling_distribution_candidates(const float* logits, size_t vocab, float tau, float temperature,
+                                                                      int64_t top_k, float top_p, float min_p, float* probs_out,
+                                                                      int32_t* decided, size_t* n_candidates)
+{
+    if (!logits || !probs_out || !decided) return KJARNI_ERROR_NULL_POINTER;
+    float mx = -std::numeric_limits<float>::infinity();
+    double sum = 0.0;
+    std::vector<uint32_t> cid;
+    std::vector<float> cval;
+    const KjarniErrorCode rc = guarded(KJARNI_ERROR_UNKNOWN, [&] {
         for (size_t i = 0; i < vocab; ++i) mx = std::max(mx, logits[i]);
         const float floor = mx - tau;
-        double sum = 0.0;
-        std::vector<uint32_t> cid;
-        std::vector<float> cval;
         for (size_t i = vocab; i-- > 0;) {  // (descending ids: the candidate list arrives in no particular order)
             sum += (double)std::exp(logits[i] - mx);
             if (logits[i] >= floor) {
@@ -519,14 +540,10 @@ KJARNI_EXPORT KjarniErrorCode kjarni_sampling_distribution_candidates(const floa
             }
         }
         if (n_candidates) *n_candidates = cid.size();
-        std::vector<uint32_t> ids;
-        std::vector<float> probs;
-        *decided = sampling_distribution_candidates(cid.data(), cval.data(), cid.size(), mx, floor, (float)sum, vocab, p, ids, probs) ? 1 : 0;
-        if (*decided) {
-            std::fill(probs_out, probs_out + vocab, 0.0f);
-            for (size_t i = 0; i < ids.size(); ++i) probs_out[ids[i]] = probs[i];
-        }
     });
+    if (rc != KJARNI_OK) return rc;
+    return kjarni_sampling_distribution_from_candidates(cid.data(), cval.data(), cid.size(), mx, mx - tau, (float)sum, vocab, temperature, top_k,
+                                                        top_p, min_p, probs_out, decided);
 }
 
 KJARNI_EXPORT uint32_t kjarni_sample_from_probs(const float* probs, size_t vocab, float uniform)

@@ -26,6 +26,7 @@
 #include "registry.h"
 #include "unicode.h"
 #include "whisper.h"
+#include "whisper_kernels.h"
 
 using namespace kjarni;
 
@@ -731,5 +732,79 @@ KJARNI_EXPORT KjarniErrorCode kjarni_bytelevel_decode(const char* tokenizer_json
         ByteLevelVocab v;
         v.load(tokenizer_json_path);
         *out = dup_cstr(v.decode(std::vector<uint32_t>(ids, ids + n), skip_special != 0));
+    });
+}
+
+// ---- Whisper's pick kernels alone, on logits given by the host (include/kjarni_hip.h) ----------------------------------
+namespace {
+
+struct PickDeviceBuf {
+    void* p = nullptr;
+    explicit PickDeviceBuf(size_t bytes) { hip_check(hipMalloc(&p, bytes ? bytes : 4), "hipMalloc"); }
+    ~PickDeviceBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    PickDeviceBuf(const PickDeviceBuf&) = delete;
+    PickDeviceBuf& operator=(const PickDeviceBuf&) = delete;
+};
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_whisper_pick(int32_t device, const float* logits, int32_t calls, int32_t lanes, int32_t vocab,
+                                                         int32_t first_special, int32_t eos, int32_t timestamp_begin, int32_t allow_timestamps,
+                                                         int32_t two_launch, int32_t* tokens_out)
+{
+    if (!logits || !tokens_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (calls < 0 || lanes < 1 || lanes > 8 || vocab < 1) throw InvalidConfig("invalid pick dimensions (calls >= 0, lanes 1..8, vocab >= 1)");
+        const int n_dev = visible_device_count();
+        if (n_dev <= 0) throw GpuUnavailable("no HIP device is visible");
+        if (device < 0 || device >= n_dev) throw GpuUnavailable("HIP device index out of range");
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        if (calls == 0) return;
+        // As the lock-step decoder calls it: the picks also join per-lane histories [lanes, stride] at count[lane], lane 0
+        // advances the position and the cache row.  A guard band follows the tokens and the histories.
+        constexpr uint32_t kGuard = 0x7fc0beefu;
+        constexpr int kGuardWords = 64, kUntouched = -77;
+        const int stride = calls;
+        const size_t call_floats = (size_t)lanes * vocab, n_tok = (size_t)calls * lanes, n_hist = (size_t)lanes * stride;
+        PickDeviceBuf dl((size_t)calls * call_floats * 4), out((n_tok + kGuardWords) * 4), hist((n_hist + kGuardWords) * 4), counters(10 * sizeof(int)),
+            best(8 * sizeof(unsigned long long));
+        hip_check(hipMemcpy(dl.p, logits, (size_t)calls * call_floats * 4, hipMemcpyHostToDevice), "H2D logits");
+        hip_check(hipMemsetD32((hipDeviceptr_t)out.p, kUntouched, n_tok), "memset tokens");
+        hip_check(hipMemsetD32((hipDeviceptr_t)((int32_t*)out.p + n_tok), (int)kGuard, kGuardWords), "guard band");
+        hip_check(hipMemsetD32((hipDeviceptr_t)hist.p, kUntouched, n_hist), "memset history");
+        hip_check(hipMemsetD32((hipDeviceptr_t)((int32_t*)hist.p + n_hist), (int)kGuard, kGuardWords), "guard band");
+        hip_check(hipMemset(counters.p, 0, 10 * sizeof(int)), "memset");
+        hip_check(hipMemset(best.p, 0, 8 * sizeof(unsigned long long)), "memset");
+        int* count = static_cast<int*>(counters.p);  // [8] counts, then the position and the cache row
+        for (int32_t c = 0; c < calls; ++c)
+            hip_check(launch_pick_token(static_cast<const float*>(dl.p) + (size_t)c * call_floats, vocab, first_special, eos, timestamp_begin,
+                                        allow_timestamps ? 1 : 0, static_cast<int32_t*>(out.p) + (size_t)c * lanes, static_cast<int32_t*>(hist.p),
+                                        count, count + 8, nullptr, lanes, stride, count + 9,
+                                        two_launch ? static_cast<unsigned long long*>(best.p) : nullptr),
+                      "pick token");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<int32_t> t(n_tok + kGuardWords), h(n_hist + kGuardWords);
+        int cnt[10] = {};
+        unsigned long long b[8] = {};
+        hip_check(hipMemcpy(t.data(), out.p, t.size() * 4, hipMemcpyDeviceToHost), "D2H tokens");
+        hip_check(hipMemcpy(h.data(), hist.p, h.size() * 4, hipMemcpyDeviceToHost), "D2H history");
+        hip_check(hipMemcpy(cnt, counters.p, sizeof(cnt), hipMemcpyDeviceToHost), "D2H counters");
+        hip_check(hipMemcpy(b, best.p, sizeof(b), hipMemcpyDeviceToHost), "D2H best");
+        for (int i = 0; i < kGuardWords; ++i)
+            if ((uint32_t)t[n_tok + i] != kGuard || (uint32_t)h[n_hist + i] != kGuard) throw std::runtime_error("pick token: guard band touched");
+        for (int i = 0; i < 8; ++i) {
+            if (b[i] != 0ull) throw std::runtime_error("pick token: the accumulator was left non-zero");
+            if (cnt[i] != (i < lanes ? calls : 0)) throw std::runtime_error("pick token: a lane's count did not advance by one per pick");
+        }
+        if (cnt[8] != calls || cnt[9] != calls * lanes) throw std::runtime_error("pick token: position / cache row did not advance as lane 0 should");
+        for (int32_t c = 0; c < calls; ++c)
+            for (int l = 0; l < lanes; ++l) {
+                const int32_t tok = t[(size_t)c * lanes + l];
+                if (h[(size_t)l * stride + c] != tok) throw std::runtime_error("pick token: the history entry is not the pick");
+                tokens_out[(size_t)c * lanes + l] = tok;
+            }
     });
 }

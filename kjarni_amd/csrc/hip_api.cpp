@@ -3,8 +3,10 @@
 #include <mutex>
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
+#include <string>
 #include <vector>
 
 #include "../../include/kjarni_hip.h"
@@ -472,6 +474,33 @@ void time_launches(int32_t iters, float* ms_out, F&& launch)
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
 }
 
+// An output buffer with a guard band behind it: a kernel that writes past the end of its output writes here, silently
+// otherwise.  check() reads the band back.
+struct GuardedBuf {
+    static constexpr uint32_t kGuard = 0x7fc0beefu;
+    static constexpr size_t kGuardWords = 64;
+    size_t bytes;
+    DeviceBuf buf;
+    explicit GuardedBuf(size_t b) : bytes((b + 3) / 4 * 4), buf(bytes + kGuardWords * 4)
+    {
+        hip_check(hipMemsetD32((hipDeviceptr_t)((char*)buf.p + bytes), (int)kGuard, kGuardWords), "guard band");
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(buf.p); }
+    void check(const char* what) const
+    {
+        uint32_t g[kGuardWords];
+        hip_check(hipMemcpy(g, (char*)buf.p + bytes, sizeof(g), hipMemcpyDeviceToHost), "D2H guard band");
+        for (size_t i = 0; i < kGuardWords; ++i)
+            if (g[i] != kGuard) throw std::runtime_error(std::string(what) + ": guard band touched at word " + std::to_string(i));
+    }
+};
+
+void expect(bool ok, const char* what)
+{
+    if (!ok) throw std::runtime_error(what);
+}
+
 }  // namespace
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear(int32_t device, const float* x, const float* w, const float* bias,
@@ -571,6 +600,222 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lookup_draft(int32_t device, const u
         hip_check(hipMemcpy(rows, ids.p, sizeof(rows), hipMemcpyDeviceToHost), "D2H ids");
         for (int i = 0; i < st.m; ++i) draft_out[i] = rows[1 + i];
         *n_out = st.m;
+    });
+}
+
+// The greedy pick kernels alone, on logits given by the host: `calls` independent picks over logits [calls, rows, ld], each
+// through the launcher the models use, on one scratch (which every call must leave zeroed for the next).
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_argmax(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld, int32_t vocab,
+                                                   int32_t route, const int32_t* live, const uint32_t* draft, int32_t n_draft,
+                                                   int32_t* picks_out, int32_t* accepted_out)
+{
+    if (!logits || !picks_out) return KJARNI_ERROR_NULL_POINTER;
+    if (route == KJARNI_HIP_ARGMAX_LANES && !live) return KJARNI_ERROR_NULL_POINTER;
+    if (route == KJARNI_HIP_ARGMAX_LOOKUP && ((n_draft > 0 && !draft) || !accepted_out)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (route < KJARNI_HIP_ARGMAX_DECODER || route > KJARNI_HIP_ARGMAX_LOOKUP) throw InvalidConfig("unknown argmax route");
+        if (calls < 0 || vocab < 1 || ld < vocab) throw InvalidConfig("invalid argmax dimensions (calls >= 0, vocab >= 1, ld >= vocab)");
+        if (rows < 1 || rows > kMaxLanes || (route == KJARNI_HIP_ARGMAX_DECODER && rows != 1))
+            throw InvalidConfig("rows must be 1 (decoder route) or 1..8 (lanes, lookup)");
+        if (route == KJARNI_HIP_ARGMAX_LOOKUP && (n_draft < 0 || n_draft > rows - 1)) throw InvalidConfig("n_draft must be 0..rows - 1");
+        use_device(device);
+        if (calls == 0) return;
+        const size_t call_floats = (size_t)rows * (size_t)ld;
+        DeviceBuf ld_buf((size_t)calls * call_floats * sizeof(float)), best(kMaxLanes * sizeof(unsigned long long));
+        const float* dl = static_cast<const float*>(ld_buf.p);
+        unsigned long long* dbest = static_cast<unsigned long long*>(best.p);
+        hip_check(hipMemcpy(ld_buf.p, logits, (size_t)calls * call_floats * sizeof(float), hipMemcpyHostToDevice), "H2D logits");
+        hip_check(hipMemset(best.p, 0, kMaxLanes * sizeof(unsigned long long)), "memset");
+        const auto best_is_zero = [&] {
+            unsigned long long b[kMaxLanes];
+            hip_check(hipMemcpy(b, best.p, sizeof(b), hipMemcpyDeviceToHost), "D2H best");
+            for (int i = 0; i < kMaxLanes; ++i) expect(b[i] == 0ull, "the pick left its accumulator non-zero");
+        };
+        constexpr int32_t kUntouched = -77;
+
+        if (route == KJARNI_HIP_ARGMAX_DECODER) {
+            // as the replayed greedy step: the token is published, joins the history, count and position advance
+            GuardedBuf out((size_t)calls * 4), hist((size_t)calls * 4);
+            DeviceBuf counters(2 * sizeof(int));
+            int* dc = static_cast<int*>(counters.p);
+            hip_check(hipMemset(counters.p, 0, 2 * sizeof(int)), "memset");
+            for (int32_t c = 0; c < calls; ++c)
+                hip_check(launch_argmax(dl + (size_t)c * call_floats, vocab, dbest, out.as<int32_t>() + c, hist.as<int32_t>(), dc, dc + 1, nullptr),
+                          "argmax");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            std::vector<int32_t> h((size_t)calls);
+            int cnt[2] = {};
+            hip_check(hipMemcpy(picks_out, out.buf.p, (size_t)calls * 4, hipMemcpyDeviceToHost), "D2H picks");
+            hip_check(hipMemcpy(h.data(), hist.buf.p, (size_t)calls * 4, hipMemcpyDeviceToHost), "D2H history");
+            hip_check(hipMemcpy(cnt, counters.p, sizeof(cnt), hipMemcpyDeviceToHost), "D2H counters");
+            out.check("argmax token");
+            hist.check("argmax history");
+            best_is_zero();
+            expect(cnt[0] == calls && cnt[1] == calls, "argmax: count / position did not advance by one per pick");
+            for (int32_t c = 0; c < calls; ++c) expect(h[(size_t)c] == picks_out[c], "argmax: the history entry is not the pick");
+            return;
+        }
+
+        if (route == KJARNI_HIP_ARGMAX_LANES) {
+            constexpr int kStride = 4;
+            GuardedBuf hist((size_t)kMaxLanes * kStride * 4), state(sizeof(LlmLaneState));
+            LlmLaneState init = {};
+            for (int l = 0; l < kMaxLanes; ++l) {
+                init.token[l] = kUntouched - l;
+                init.live[l] = l < rows && live[l] ? 1 : 0;
+                init.limit[l] = 1 << 30;  // (no stop ids, a limit and a capacity no pick reaches: a live lane stays live)
+            }
+            std::vector<int32_t> h((size_t)kMaxLanes * kStride);
+            for (int32_t c = 0; c < calls; ++c) {
+                hip_check(hipMemcpy(state.buf.p, &init, sizeof(init), hipMemcpyHostToDevice), "H2D lane state");
+                hip_check(hipMemsetD32((hipDeviceptr_t)hist.buf.p, kUntouched, (size_t)kMaxLanes * kStride), "memset history");
+                hip_check(launch_lane_pick(dl + (size_t)c * call_floats, ld, vocab, rows, 0, dbest, state.as<LlmLaneState>(), hist.as<int32_t>(),
+                                           kStride, 1 << 30, 1, nullptr), "lane pick");
+                hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+                LlmLaneState st;
+                hip_check(hipMemcpy(&st, state.buf.p, sizeof(st), hipMemcpyDeviceToHost), "D2H lane state");
+                hip_check(hipMemcpy(h.data(), hist.buf.p, h.size() * 4, hipMemcpyDeviceToHost), "D2H history");
+                hist.check("lane history");
+                state.check("lane state");
+                best_is_zero();
+                for (int l = 0; l < kMaxLanes; ++l) {
+                    const int32_t* hl = h.data() + (size_t)l * kStride;
+                    if (init.live[l]) {
+                        expect(st.live[l] == 1 && st.count[l] == 1 && st.pos[l] == 1, "lane pick: a live lane did not advance by one pick");
+                        expect(hl[0] == st.token[l], "lane pick: the history entry is not the lane's next token");
+                        for (int i = 1; i < kStride; ++i) expect(hl[i] == kUntouched, "lane pick: wrote past the lane's history entry");
+                    } else {
+                        expect(st.token[l] == init.token[l] && st.live[l] == 0 && st.count[l] == 0 && st.pos[l] == 0,
+                               "lane pick: the state of a frozen lane changed");
+                        for (int i = 0; i < kStride; ++i) expect(hl[i] == kUntouched, "lane pick: the history of a frozen lane changed");
+                    }
+                    if (l < rows) picks_out[(size_t)c * rows + l] = init.live[l] ? st.token[l] : -1;
+                }
+            }
+            return;
+        }
+
+        // lookup: ids[0] = the last token, ids[1..n_draft] = the draft, the pad rows repeat the last of them (launch_lookup_draft)
+        constexpr int kN0 = 5, kHistCap = kN0 + kMaxLanes;
+        GuardedBuf hist((size_t)kHistCap * 4), state(sizeof(LlmLookupState)), log(2 * 4), pos(4);
+        DeviceBuf ids(kMaxLanes * sizeof(uint32_t));
+        std::vector<int32_t> h((size_t)kHistCap);
+        for (int32_t c = 0; c < calls; ++c) {
+            uint32_t row_ids[kMaxLanes] = {};
+            for (int i = 1; i < kMaxLanes; ++i) row_ids[i] = i <= n_draft ? draft[(size_t)c * n_draft + (i - 1)] : row_ids[i - 1];
+            LlmLookupState init = {};
+            init.n = kN0;
+            init.m = n_draft;
+            for (int i = 0; i < 8; ++i) init.picks[i] = kUntouched;
+            const int pos0 = kN0 - 1;
+            hip_check(hipMemcpy(ids.p, row_ids, sizeof(row_ids), hipMemcpyHostToDevice), "H2D ids");
+            hip_check(hipMemcpy(state.buf.p, &init, sizeof(init), hipMemcpyHostToDevice), "H2D lookup state");
+            hip_check(hipMemcpy(pos.buf.p, &pos0, sizeof(pos0), hipMemcpyHostToDevice), "H2D pos");
+            hip_check(hipMemsetD32((hipDeviceptr_t)hist.buf.p, kUntouched, (size_t)kHistCap), "memset history");
+            hip_check(hipMemsetD32((hipDeviceptr_t)log.buf.p, kUntouched, 2), "memset log");
+            hip_check(launch_lookup_pick(dl + (size_t)c * call_floats, ld, vocab, rows, static_cast<const uint32_t*>(ids.p), dbest,
+                                         state.as<LlmLookupState>(), hist.as<int32_t>(), kHistCap, pos.as<int>(), log.as<int32_t>(), 1, nullptr),
+                      "lookup pick");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            LlmLookupState st;
+            int32_t lg[2] = {};
+            int p1 = 0;
+            hip_check(hipMemcpy(&st, state.buf.p, sizeof(st), hipMemcpyDeviceToHost), "D2H lookup state");
+            hip_check(hipMemcpy(h.data(), hist.buf.p, h.size() * 4, hipMemcpyDeviceToHost), "D2H history");
+            hip_check(hipMemcpy(lg, log.buf.p, sizeof(lg), hipMemcpyDeviceToHost), "D2H log");
+            hip_check(hipMemcpy(&p1, pos.buf.p, sizeof(p1), hipMemcpyDeviceToHost), "D2H pos");
+            hist.check("lookup history");
+            state.check("lookup state");
+            log.check("lookup log");
+            pos.check("lookup position");
+            best_is_zero();
+            const int a = st.a;
+            expect(a >= 0 && a <= n_draft, "lookup pick: accepted count outside 0..m");
+            expect(st.n == kN0 + a + 1 && p1 == pos0 + a + 1 && st.steps == 1 && st.m == n_draft, "lookup pick: history length / position / steps");
+            expect(lg[0] == n_draft && lg[1] == a, "lookup pick: the step log does not hold (m, a)");
+            for (int i = 0; i < kHistCap; ++i) {
+                const bool pick = i >= kN0 && i <= kN0 + a;
+                expect(h[(size_t)i] == (pick ? st.picks[i - kN0] : kUntouched), "lookup pick: the history does not hold exactly the picks p_0..p_a");
+            }
+            for (int i = a + 1; i < 8; ++i) expect(st.picks[i] == kUntouched, "lookup pick: picks past p_a were written");
+            for (int i = 0; i < rows; ++i) picks_out[(size_t)c * rows + i] = i <= a ? st.picks[i] : -1;
+            accepted_out[c] = a;
+        }
+    });
+}
+
+// The logits processors alone: the history's counts built as LlmModel::generate builds them (one launch over the first n_bulk
+// tokens -- the prompt --, one per later token), then the penalty and the n-gram ban over the whole history.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_logits_processors(int32_t device, const float* logits, int32_t vocab, const uint32_t* tokens, int32_t n,
+                                                              int32_t n_bulk, float repetition_penalty, int32_t no_repeat_ngram, float* logits_out)
+{
+    if (!logits || !logits_out || (n > 0 && !tokens)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (vocab < 1 || n < 0 || n_bulk < 0 || n_bulk > n || no_repeat_ngram < 0)
+            throw InvalidConfig("invalid logits-processor arguments (vocab >= 1, 0 <= n_bulk <= n, no_repeat_ngram >= 0)");
+        use_device(device);
+        GuardedBuf lg((size_t)vocab * 4), distinct((size_t)n * 4), counts((size_t)vocab * 4), nd(4);
+        DeviceBuf tok((size_t)n * 4);
+        hip_check(hipMemcpy(lg.buf.p, logits, (size_t)vocab * 4, hipMemcpyHostToDevice), "H2D logits");
+        if (n) hip_check(hipMemcpy(tok.p, tokens, (size_t)n * 4, hipMemcpyHostToDevice), "H2D history");
+        hip_check(hipMemset(counts.buf.p, 0, (size_t)vocab * 4), "memset counts");
+        hip_check(hipMemset(nd.buf.p, 0, 4), "memset");
+        const int32_t* dt = static_cast<const int32_t*>(tok.p);
+        hip_check(launch_token_counts(dt, n_bulk, vocab, counts.as<int>(), distinct.as<int32_t>(), nd.as<int>(), nullptr), "token counts");
+        for (int32_t i = n_bulk; i < n; ++i)
+            hip_check(launch_token_counts(dt + i, 1, vocab, counts.as<int>(), distinct.as<int32_t>(), nd.as<int>(), nullptr), "token counts");
+        hip_check(launch_logits_processors(lg.as<float>(), vocab, dt, n, counts.as<int>(), distinct.as<int32_t>(), nd.as<int>(), repetition_penalty,
+                                           no_repeat_ngram, nullptr), "logits processors");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        hip_check(hipMemcpy(logits_out, lg.buf.p, (size_t)vocab * 4, hipMemcpyDeviceToHost), "D2H logits");
+        lg.check("processed logits");
+        distinct.check("distinct tokens");
+        counts.check("token counts");
+        nd.check("distinct counter");
+    });
+}
+
+// The sampler's cut alone: one launch_sample_candidates per row of logits (row c holds vocabs[c] floats, the rows packed one
+// after another), in order, on ONE scratch and ONE header + candidate buffer as a generate call reuses them token after token.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_sample_candidates(int32_t device, const float* logits, const int32_t* vocabs, int32_t calls,
+                                                              int64_t top_k, float top_p, float min_p, int32_t capacity,
+                                                              KjarniHipSampleHeader* headers_out, uint32_t* ids_out, float* logits_out)
+{
+    if (!logits || !vocabs || !headers_out || !ids_out || !logits_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (calls < 0 || capacity < 1) throw InvalidConfig("invalid sampler arguments (calls >= 0, capacity >= 1)");
+        size_t total = 0;
+        for (int32_t c = 0; c < calls; ++c) {
+            if (vocabs[c] < 1) throw InvalidConfig("vocabulary sizes must be positive");
+            total += (size_t)vocabs[c];
+        }
+        use_device(device);
+        if (calls == 0) return;
+        DeviceBuf dl(total * 4), scratch(sample_scratch_bytes());
+        GuardedBuf out(sizeof(SampleHeader) + (size_t)capacity * sizeof(SampleCandidate));
+        hip_check(hipMemcpy(dl.p, logits, total * 4, hipMemcpyHostToDevice), "H2D logits");
+        hip_check(hipMemset(scratch.p, 0, sample_scratch_bytes()), "memset");
+        hip_check(hipMemset(out.buf.p, 0, out.bytes), "memset");
+        SampleHeader* dh = out.as<SampleHeader>();
+        SampleCandidate* dc = reinterpret_cast<SampleCandidate*>(out.as<uint8_t>() + sizeof(SampleHeader));
+        std::vector<SampleCandidate> cand((size_t)capacity);
+        size_t off = 0;
+        for (int32_t c = 0; c < calls; ++c) {
+            hip_check(launch_sample_candidates(static_cast<const float*>(dl.p) + off, vocabs[c], top_k, top_p, min_p, scratch.p, dh, dc, capacity,
+                                               nullptr), "sample candidates");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            off += (size_t)vocabs[c];
+            SampleHeader h;
+            hip_check(hipMemcpy(&h, dh, sizeof(h), hipMemcpyDeviceToHost), "D2H header");
+            out.check("candidate list");
+            const size_t n = std::min<size_t>(h.count, (size_t)capacity);
+            if (n) hip_check(hipMemcpy(cand.data(), dc, n * sizeof(SampleCandidate), hipMemcpyDeviceToHost), "D2H candidates");
+            headers_out[c] = KjarniHipSampleHeader{h.mx, h.sum, h.floor, h.count, h.overflow};
+            for (size_t i = 0; i < n; ++i) {
+                ids_out[(size_t)c * capacity + i] = cand[i].token;
+                logits_out[(size_t)c * capacity + i] = cand[i].logit;
+            }
+        }
     });
 }
 

@@ -140,7 +140,7 @@ struct SampleHeader {   // 32 bytes, device memory mirrored to the host per samp
     float mx;           // maximum logit
     float sum;          // sum of exp(logit - mx) over the vocabulary (deterministic, not in index order)
     float floor;        // every token with logit >= floor is in the candidate list
-    uint32_t count;     // candidates appended (may exceed the capacity: then overflow is set)
+    uint32_t count;     // tokens with logit >= floor (more than the capacity, or no cut -- then all of them: overflow is set)
     uint32_t overflow;  // 1: the list is not usable (too long, or no cut could be placed) -- fetch the logits
     uint32_t pad[3];
 };

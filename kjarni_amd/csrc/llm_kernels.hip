@@ -967,7 +967,7 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const uint32_t* __restri
 
 __device__ __forceinline__ unsigned long long argmax_key(float v, int idx)
 {
-    uint32_t u = __float_as_uint(v);
+    uint32_t u = v == 0.0f ? 0u : __float_as_uint(v);  // -0.0 == +0.0 (partial_cmp): one key for both, the later index wins
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // larger float -> larger uint
     if (v != v) u = 0;                               // NaN lowest
     return ((unsigned long long)u << 32) | (uint32_t)idx;  // equal values: the LAST index wins (Iterator::max_by)
@@ -2000,8 +2000,11 @@ __global__ __launch_bounds__(256) void sample_compact_kernel(const float* __rest
         }
     }
     __syncthreads();
-    if (s_all) {  // no usable cut: the host takes the logits
-        if (blockIdx.x == 0 && threadIdx.x == 0) header->overflow = 1u;
+    if (s_all) {  // no usable cut: the host takes the logits (floor = -inf: every token is above it, none is appended)
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            header->count = (uint32_t)vocab;
+            header->overflow = 1u;
+        }
         return;
     }
     const float floor = s_floor;

@@ -937,7 +937,7 @@ __global__ __launch_bounds__(256) void pick_partial_kernel(const float* __restri
         const bool ok = i < first_special || i == eos || (allow_timestamps && i >= timestamp_begin);
         if (!ok) continue;
         const float v = logits[i];
-        uint32_t u = __float_as_uint(v);
+        uint32_t u = v == 0.0f ? 0u : __float_as_uint(v);  // -0.0 == +0.0, as the one-launch form compares them
         u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
         if (v != v) u = 1u;  // NaN below every number, above "nothing seen"
         const unsigned long long k = ((unsigned long long)u << 32) | (uint32_t)i;

@@ -203,6 +203,74 @@ def lookup_draft(tokens, draft_tokens: int = 7, ngram_max: int = 3, ngram_min: i
     return out[:n.value].tolist()
 
 
+ARGMAX_DECODER, ARGMAX_LANES, ARGMAX_LOOKUP = 0, 1, 2
+_i32p = C.POINTER(C.c_int32)
+
+
+def argmax(logits, vocab: Optional[int] = None, route: int = ARGMAX_DECODER, live=None, draft=None, device: int = 0):
+    """The greedy pick kernels on logits [calls, rows, ld] (the last of equal maxima wins; columns >= vocab are padding).
+    Returns picks int32 [calls, rows]: decoder route rows == 1; lanes route -1 for the lanes `live` [rows] freezes; lookup
+    route (picks, accepted) with draft [calls, n_draft], picks[c, :accepted[c] + 1] the verify step's tokens, -1 past them."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    calls, rows, ld = lg.shape
+    vocab = ld if vocab is None else int(vocab)
+    picks = np.full((calls, rows), -2, np.int32)
+    acc = np.zeros(calls, np.int32)
+    lv = None if live is None else np.ascontiguousarray(live, np.int32)
+    dr = None if draft is None else np.ascontiguousarray(draft, np.uint32).reshape(calls, -1)
+    if lv is not None and lv.size != rows:
+        raise ValueError("live must hold one flag per row")
+    n_draft = 0 if dr is None else dr.shape[1]
+    check_error(lib().kjarni_hip_op_argmax(device, _f(lg), calls, rows, ld, vocab, route, None if lv is None else lv.ctypes.data_as(_i32p),
+                                           None if dr is None else dr.ctypes.data_as(_ffi._u32p), n_draft, picks.ctypes.data_as(_i32p),
+                                           acc.ctypes.data_as(_i32p)))
+    return (picks, acc) if route == ARGMAX_LOOKUP else picks
+
+
+def whisper_pick(logits, first_special: int, eos: int, timestamp_begin: int, allow_timestamps: bool, two_launch: bool, device: int = 0):
+    """Whisper's pick on logits [calls, lanes, vocab]: tokens int32 [calls, lanes]; two_launch chooses the replayed step's
+    two small launches over the one 1024-thread workgroup per lane."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    calls, lanes, vocab = lg.shape
+    out = np.full((calls, lanes), -2, np.int32)
+    check_error(lib().kjarni_hip_op_whisper_pick(device, _f(lg), calls, lanes, vocab, first_special, eos, timestamp_begin, int(allow_timestamps),
+                                                 int(two_launch), out.ctypes.data_as(_i32p)))
+    return out
+
+
+def logits_processors(logits, tokens, n_bulk: int, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0, device: int = 0):
+    """Repetition penalty + n-gram ban of the history `tokens` on the device; the per-token counts come from one launch over
+    tokens[:n_bulk] and one launch per later token, as in a generate call."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    t = np.ascontiguousarray(tokens, np.uint32)
+    out = np.empty_like(lg)
+    check_error(lib().kjarni_hip_op_logits_processors(device, _f(lg), lg.size, t.ctypes.data_as(_ffi._u32p), t.size, n_bulk,
+                                                      repetition_penalty, no_repeat_ngram, _f(out)))
+    return out
+
+
+def sample_candidates(rows, top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                      capacity: int = 4096, device: int = 0):
+    """The sampler's device cut over each of `rows` (1-D logits arrays, possibly of different lengths), in order, on one
+    scratch / header / candidate buffer.  Per row a dict: mx, sum, floor (np.float32), count, overflow, ids (uint32) and
+    logits (float32) of the first min(count, capacity) candidates."""
+    rows = [np.ascontiguousarray(r, np.float32).ravel() for r in rows]
+    flat = np.concatenate(rows)
+    vocabs = np.array([r.size for r in rows], np.int32)
+    hdr = (_ffi.KjarniHipSampleHeader * len(rows))()
+    ids = np.zeros((len(rows), capacity), np.uint32)
+    vals = np.zeros((len(rows), capacity), np.float32)
+    check_error(lib().kjarni_hip_op_sample_candidates(device, _f(flat), vocabs.ctypes.data_as(_i32p), len(rows), -1 if top_k is None else top_k,
+                                                      -1.0 if top_p is None else top_p, -1.0 if min_p is None else min_p, capacity, hdr,
+                                                      ids.ctypes.data_as(_ffi._u32p), _f(vals)))
+    out = []
+    for c, h in enumerate(hdr):
+        n = min(int(h.count), capacity)
+        out.append({"mx": np.float32(h.mx), "sum": np.float32(h.sum), "floor": np.float32(h.floor), "count": int(h.count),
+                    "overflow": int(h.overflow), "ids": ids[c, :n].copy(), "logits": vals[c, :n].copy()})
+    return out
+
+
 def topk(scores, k: int, device: int = 0):
     """Top-k of a score matrix [nq, n] on the GPU (kjarni_hip_cosine_topk): (idx int64 [nq,k], score f32 [nq,k]),
     score descending, equal scores by ascending index; entries past n are (-1, -inf)."""

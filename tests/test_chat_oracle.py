@@ -289,6 +289,42 @@ def test_candidate_form_equals_the_full_sampler_or_declines(params):
     assert decided_some != only_temperature       # temperature only needs the whole vocabulary: always declined
 
 
+@pytest.mark.parametrize("params", [dict(top_k=40, top_p=0.9, min_p=0.05, temperature=0.7), dict(top_p=0.9, min_p=0.05, temperature=0.6),
+                                    dict(top_k=5), dict(top_p=0.5), dict(min_p=0.2, temperature=1.3), dict(temperature=0.8)])
+def test_candidate_list_entry_is_order_free_and_equals_the_emulating_entry(params):
+    """kjarni_sampling_distribution_from_candidates takes the list as the device hands it over: (id, logit) pairs in no
+    particular order + the header.  Descending and shuffled id order give the same answer, and it is the emulating entry's
+    (which now runs through it).  The header is restated here: the maximum, floor = max - tau in f32, and the sum of f32
+    exponentials accumulated in double over descending ids."""
+    from kjarni_amd import chat as K
+    from kjarni_amd._ffi import KjarniError, KjarniException
+    rng = np.random.default_rng(19)
+    decided_some = False
+    for name, logits in _logit_sets():
+        mx = logits.max()
+        e = np.exp((logits - mx).astype(np.float32)).astype(np.float64)
+        total = np.float32(np.add.accumulate(e[::-1])[-1])
+        for tau in (0.5, 3.0, 8.0, 20.0):
+            floor = np.float32(mx - np.float32(tau))
+            ids = np.flatnonzero(logits >= floor)[::-1].astype(np.uint32)
+            want, n = K.sampling_distribution_candidates(logits, tau, **params)
+            assert n == ids.size
+            answers = []
+            for order in (np.arange(ids.size), rng.permutation(ids.size), rng.permutation(ids.size)):
+                sel = ids[order]
+                answers.append(K.sampling_distribution_from_candidates(sel, logits[sel], mx, floor, total, logits.size, **params))
+            for got in answers:
+                assert (got is None) == (want is None), (name, tau, params)
+                if want is not None:
+                    decided_some = True
+                    assert np.array_equal(got, want), (name, tau, params)
+    only_temperature = not any(k in params for k in ("top_k", "top_p", "min_p"))
+    assert decided_some != only_temperature
+    with pytest.raises(KjarniException) as ei:      # an id outside the vocabulary is refused, not written
+        K.sampling_distribution_from_candidates([5000], [1.0], 1.0, 0.0, 1.0, 5000, top_k=5)
+    assert ei.value.code == KjarniError.INVALID_CONFIG
+
+
 def test_candidate_form_declines_what_it_cannot_decide():
     from kjarni_amd import chat as K
     rng = np.random.default_rng(3)
