@@ -445,6 +445,14 @@ KjarniErrorCode kjarni_generator_stream(KjarniGenerator* generator, const char* 
  * OK with an empty array.  Free with kjarni_string_array_free. */
 KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* generator, const char* const* prompts, size_t n,
                                                 const KjarniGenerationConfig* gen_config, KjarniStringArray* out);
+/* The log-likelihood of `continuation` after `context` (not in the reference, which has no scoring entry point).  The token
+ * rule is lm-eval-harness's, on the encode of kjarni_generator_generate (BOS rule, the model's default config): whole =
+ * encode(context + continuation), first = len(encode(context)), the scored tokens are whole[first:].  An empty context is the
+ * BOS token alone (a model without BOS: INVALID_CONFIG).  sum_logprob: the float64 sum of the tokens' f32 log-probabilities, in
+ * order; n_tokens: their count; is_greedy: 1 iff every scored token is its position's arg-max.  Nothing is truncated: a
+ * continuation that adds no token, or a text longer than the model's context, is INVALID_CONFIG with the reason. */
+typedef struct KjarniScoreResult { double sum_logprob; size_t n_tokens; int32_t is_greedy; } KjarniScoreResult;
+KjarniErrorCode kjarni_generator_score(KjarniGenerator* generator, const char* context, const char* continuation, KjarniScoreResult* out);
 /* Without a buffer: the name's byte length; with one: bytes copied, NUL excluded. */
 size_t kjarni_generator_model_name(const KjarniGenerator* generator, char* buf, size_t buf_len);
 size_t kjarni_generator_context_size(const KjarniGenerator* generator);  /* the model's n_ctx / max_position_embeddings */

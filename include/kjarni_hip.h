@@ -652,6 +652,29 @@ KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGenerator* generato
 /* kjarni_hip_decoder_verify_gemv_calls of the generator's model: it moves only when a call took the lookup loop. */
 void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* generator, uint64_t* streamed, uint64_t* fallback);
 
+/* ---- scoring: per-token log-probabilities of a given sequence (NOT in the reference: it has no scoring entry point; the
+ * arithmetic is its final norm + head, llama/cpu_decoder.rs:196-219, gpt2/cpu_decoder.rs:371-394, and log_softmax_1d,
+ * common/sampling.rs:200-205) ----
+ * kjarni_hip_decoder_score resets the cache and runs ids[0, n) through the routes of kjarni_hip_decoder_forward.  For every
+ * position p in [first, n), 1 <= first < n, entry p - first of the outputs (n - first entries each, any may be NULL) is
+ * log p(ids[p] | ids[0, p)), the arg-max token of that distribution (the last of equal maxima) and the arg-max's
+ * log-probability.  Only the rows first - 1 .. n - 2 reach the vocabulary head.  The fused route (f32 / bf16 heads, hidden a
+ * multiple of 32) runs the head on the fp32 matrix cores and never stores the logits; the rows route (quantized heads, other
+ * geometries, or set_score_fused(0)) takes 8 materialised logits rows at a time.  Afterwards the decoder is in the state
+ * reset + forward(ids, n) leaves.  n < 2, first outside [1, n), n > context or an id >= vocab: INVALID_CONFIG before any GPU
+ * work, the message names the argument. */
+KjarniErrorCode kjarni_hip_decoder_score(KjarniHipDecoder* decoder, const uint32_t* ids, int32_t n, int32_t first, float* logprob_out,
+                                         uint32_t* top_out, float* top_logprob_out);
+void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* decoder, int32_t on);   /* default on; 0: every checkpoint takes the rows route */
+/* Head launches of kjarni_hip_decoder_score by route since load (zeros on NULL). */
+void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* decoder, uint64_t* fused, uint64_t* rows);
+/* The head kernels alone, host pointers (as kjarni_hip_op_linear_ggml): hidden f32 [m, k]; W [vocab, k] f32 (bf16 = 0) or
+ * bf16 bits (bf16 = 1); targets [m]; slab_tiles 0 = automatic; fused 0 = the rows route (materialised in 8-row blocks).
+ * Outputs [m] each, any may be NULL: log-probability of the target, arg-max, its log-probability, the row's log-sum-exp. */
+KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
+                                         int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused, float* logprob_out,
+                                         uint32_t* top_out, float* top_logprob_out, float* lse_out);
+
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */
 KjarniErrorCode kjarni_hip_malloc(int32_t device, size_t bytes, void** out_dev);
 KjarniErrorCode kjarni_hip_free(int32_t device, void* ptr_dev);

@@ -246,6 +246,10 @@ class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
 
+class KjarniScoreResult(Structure):
+    _fields_ = [("sum_logprob", C.c_double), ("n_tokens", c_size_t), ("is_greedy", c_int32)]
+
+
 class KjarniGeneratorConfig(Structure):
     _fields_ = [("device", c_int32), ("cache_dir", c_char_p), ("model_name", c_char_p), ("model_path", c_char_p),
                 ("quiet", c_int32)]
@@ -466,6 +470,12 @@ SIGNATURES = {
     "kjarni_hip_generator_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_generator_generate_batch": (c_int32, [c_void_p, POINTER(c_char_p), c_size_t, POINTER(KjarniGenerationConfig),
                                                   POINTER(KjarniStringArray)]),
+    "kjarni_hip_decoder_score": (c_int32, [c_void_p, _u32p, c_int32, c_int32, _f32p, _u32p, _f32p]),
+    "kjarni_hip_decoder_set_score_fused": (None, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_score_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_op_score_head": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, c_int32, _u32p, c_int32, c_int32, _f32p,
+                                           _u32p, _f32p, _f32p]),
+    "kjarni_generator_score": (c_int32, [c_void_p, c_char_p, c_char_p, POINTER(KjarniScoreResult)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),
     "kjarni_collect_files": (c_int32, [POINTER(KjarniIndexerConfig), POINTER(c_char_p), c_size_t,
                                        POINTER(KjarniStringArray)]),

@@ -575,6 +575,32 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_);
 }
 
+Generator::Score Generator::score(const std::string& context, const std::string& continuation)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    const GenerationConfig config = resolve(GenerationOverrides());
+    const std::vector<uint32_t> whole = encode(context + continuation, config);
+    const size_t first = encode(context, config).size();
+    if (first == 0) throw InvalidConfig("scoring needs at least one context token (the context is empty and the model has no BOS token)");
+    if (first >= whole.size())
+        throw InvalidConfig("the continuation adds no tokens: context + continuation encode to " + std::to_string(whole.size()) +
+                            " tokens, the context alone to " + std::to_string(first));
+    if (whole.size() > (size_t)model_->context())
+        throw InvalidConfig("context + continuation (" + std::to_string(whole.size()) + " tokens) exceed the model's context of " +
+                            std::to_string(model_->context()) + " tokens");
+    const size_t cnt = whole.size() - first;
+    std::vector<float> lp(cnt);
+    std::vector<uint32_t> top(cnt);
+    model_->score(whole.data(), (int)whole.size(), (int)first, lp.data(), top.data(), nullptr);
+    Score r;
+    r.n_tokens = cnt;
+    r.is_greedy = true;
+    for (size_t i = 0; i < cnt; ++i) {
+        r.sum_logprob += (double)lp[i];
+        if (top[i] != whole[first + i]) r.is_greedy = false;
+    }
+    return r;
+}
 
 // Generator::run for every prompt, `lanes` of them decoded in lock step (LlmModel::generate_lanes): each prompt is encoded
 // (BOS rule), capped and decoded exactly as run() does.  A sampled request draws from a generator of its own, seeded from

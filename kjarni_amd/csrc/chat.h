@@ -150,6 +150,16 @@ public:
     // config is greedy without a repetition penalty or an n-gram ban (LlmModel::generate_lookup); generate_batch is untouched.
     void set_prompt_lookup(int draft_tokens) { prompt_lookup_ = draft_tokens; }
     int prompt_lookup() const { return prompt_lookup_; }
+    // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
+    // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
+    // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
+    // that adds no token, more tokens than the model's context.
+    struct Score {
+        double sum_logprob = 0.0;  // the f32 log-probabilities summed in order, in double
+        size_t n_tokens = 0;
+        bool is_greedy = false;    // every scored token is its position's arg-max
+    };
+    Score score(const std::string& context, const std::string& continuation);
 
 private:
     Generator() = default;

@@ -383,6 +383,18 @@ KJARNI_EXPORT KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* g
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_score(KjarniGenerator* gen, const char* context, const char* continuation, KjarniScoreResult* out)
+{
+    if (!gen || !context || !continuation || !out) return KJARNI_ERROR_NULL_POINTER;
+    if (!valid_utf8(context) || !valid_utf8(continuation)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const Generator::Score s = gen->inner->score(context, continuation);
+        out->sum_logprob = s.sum_logprob;
+        out->n_tokens = s.n_tokens;
+        out->is_greedy = s.is_greedy ? 1 : 0;
+    });
+}
+
 KJARNI_EXPORT size_t kjarni_generator_model_name(const KjarniGenerator* gen, char* buf, size_t buf_len)
 {
     if (!gen) return 0;

@@ -305,6 +305,29 @@ KJARNI_EXPORT void kjarni_hip_decoder_verify_gemv_calls(const KjarniHipDecoder* 
     if (fallback) *fallback = d ? d->model->verify_fallback_calls() : 0;
 }
 
+// ---- scoring ---------------------------------------------------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_score(KjarniHipDecoder* d, const uint32_t* ids, int32_t n, int32_t first, float* logprob_out,
+                                                       uint32_t* top_out, float* top_logprob_out)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->score(ids, n, first, logprob_out, top_out, top_logprob_out);  // arguments checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* d, int32_t on)
+{
+    if (d) d->model->set_score_fused(on != 0);
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* d, uint64_t* fused, uint64_t* rows)
+{
+    if (fused) *fused = d ? d->model->score_fused_calls() : 0;
+    if (rows) *rows = d ? d->model->score_rows_calls() : 0;
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* d, char** out)
 {
     if (!d || !out) return KJARNI_ERROR_NULL_POINTER;

@@ -645,7 +645,7 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool 
 // Q, K, V projections (K and V rows land in the cache) -> RoPE -> causal attention over the cache -> o-proj + residual
 // -> RMSNorm -> gate, up -> silu(gate) * up -> down-proj + residual; same formulas as pass().  After the last layer the
 // final norm runs on the last (n - 1) % 8 + 1 rows (what last_hidden() exposes) and the lm head on the last row.
-void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
+void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
@@ -768,6 +768,15 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
             proj(pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
             proj(pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
         }
+        if (score) {  // the chunk's rows whose successor is scored: final norm into the (now free) norm buffer, then the head
+            const int lo = std::max(done, score_first_ - 1), hi = std::min(done + m - 1, score_n_ - 2);
+            if (lo <= hi) {
+                const float* src = ph_ + (size_t)(lo - done) * H;
+                if (gpt2_) hip_check(launch_layernorm(src, final_norm_, final_norm_b_, c.eps, hi - lo + 1, H, pn_, s), "ln_f");
+                else hip_check(launch_rmsnorm(src, final_norm_, c.eps, hi - lo + 1, H, pn_, s), "final norm");
+                score_head_rows(pn_, lo, hi - lo + 1);
+            }
+        }
         cache_len_ += m;
         if (done + m == n) {
             const int rows = (n - 1) % 8 + 1;
@@ -787,7 +796,9 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n)
     }
 }
 
-void LlmModel::forward(const uint32_t* ids, int n)
+void LlmModel::forward(const uint32_t* ids, int n) { forward_rows(ids, n, false); }
+
+void LlmModel::forward_rows(const uint32_t* ids, int n, bool score)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (n < 1) throw std::runtime_error("forward needs at least one token");
@@ -795,18 +806,87 @@ void LlmModel::forward(const uint32_t* ids, int n)
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
     const int kvd = cfg_.kv_heads * cfg_.head_dim;
     if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
-        prefill_rows(ids, n);
+        prefill_rows(ids, n, score);
     } else {
         for (int i = 0; i < n; i += 8) {
             const int m = std::min(8, n - i);
             hip_check(hipMemcpyAsync(ids_, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, stream_), "H2D ids");
             pass(ids_, m, false);
+            if (score) {  // pass() final-norms every row of the block into last_
+                const int lo = std::max(i, score_first_ - 1), hi = std::min(i + m - 1, score_n_ - 2);
+                if (lo <= hi) score_head_rows(last_ + (size_t)(lo - i) * cfg_.hidden, lo, hi - lo + 1);
+            }
             cache_len_ += m;
             last_rows_ = m;
             hip_check(hipStreamSynchronize(stream_), "sync");  // ids_ is reused by the next block
         }
     }
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+
+void LlmModel::ensure_score()
+{
+    if (score_tgt_) return;
+    const size_t cap = (size_t)cache_cap_;
+    score_tgt_ = reinterpret_cast<uint32_t*>(dalloc(cap));
+    score_top_ = reinterpret_cast<uint32_t*>(dalloc(cap));
+    score_lp_ = dalloc(cap);
+    score_tlp_ = dalloc(cap);
+    for (int m = 64; m <= 2048; m += 64)  // a head launch has at most a prompt chunk's rows
+        score_scratch_bytes_ = std::max(score_scratch_bytes_, score_head_scratch_bytes(m, cfg_.vocab, 0));
+    score_scratch_ = dalloc((score_scratch_bytes_ + 3) / 4);
+}
+
+void LlmModel::score_head_rows(const float* Xn, int lo, int cnt)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, out = lo + 1 - score_first_;
+    const uint32_t* tgt = score_tgt_ + lo;
+    if (score_fused_ && !quant_ && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
+        if (score_head_scratch_bytes(cnt, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score: slab scratch too small");
+        hip_check(launch_score_head(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, score_lp_ + out, score_top_ + out,
+                                    score_tlp_ + out, nullptr, stream_), "score head");
+        ++score_fused_calls_;
+        return;
+    }
+    ensure_lookup();  // vlogits_: the verify step's 8 logits rows
+    for (int r = 0; r < cnt; r += 8) {
+        const int rows = std::min(8, cnt - r);
+        if (quant_) {
+            qlinear(qhead_, Xn + (size_t)r * H, H, rows, head_q8k_, vlogits_, c.vocab, "lm head");
+        } else {
+            LlmGemvArgs lm;
+            lm.X = Xn + (size_t)r * H; lm.ldx = H; lm.rows = rows; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
+            lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
+            hip_check(launch_llm_gemv(lm, stream_), "lm head");
+        }
+        hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_lp_ + out + r, score_top_ + out + r, score_tlp_ + out + r,
+                                    nullptr, stream_), "score rows");
+        ++score_rows_calls_;
+    }
+}
+
+void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out)
+{
+    if (n < 2) throw InvalidConfig("n (" + std::to_string(n) + ") must be at least 2: a scored token needs a prefix");
+    if (first < 1 || first >= n) throw InvalidConfig("first (" + std::to_string(first) + ") must be in [1, n) with n = " + std::to_string(n));
+    if (n > cache_cap_) throw InvalidConfig("n (" + std::to_string(n) + " tokens) exceeds the context of " + std::to_string(cache_cap_) + " tokens");
+    for (int i = 0; i < n; ++i)
+        if (ids[i] >= (uint32_t)cfg_.vocab)
+            throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
+                                std::to_string(cfg_.vocab));
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ensure_score();
+    reset();
+    hip_check(hipMemcpyAsync(score_tgt_, ids + 1, (size_t)(n - 1) * 4, hipMemcpyHostToDevice, stream_), "H2D targets");
+    score_first_ = first;
+    score_n_ = n;
+    forward_rows(ids, n, true);
+    const size_t cnt = (size_t)(n - first);
+    if (logprob_out) hip_check(hipMemcpyAsync(logprob_out, score_lp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H logprob");
+    if (top_out) hip_check(hipMemcpyAsync(top_out, score_top_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H top");
+    if (top_logprob_out) hip_check(hipMemcpyAsync(top_logprob_out, score_tlp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H top logprob");
     hip_check(hipStreamSynchronize(stream_), "sync");
 }
 

@@ -107,6 +107,19 @@ public:
     // Appends n tokens (fewer than 24: 8-row passes; more: the matrix-core route in 2 048-row chunks); the logits of the last
     // position stay on the device.
     void forward(const uint32_t* ids, int n);
+    // Scoring: resets the cache, runs ids[0, n) through forward()'s routes and returns, for every position p in [first, n)
+    // (1 <= first < n; entry p - first), log p(ids[p] | ids[0, p)), the arg-max token of that distribution and the arg-max's
+    // log-probability (log_softmax_1d, sampling.rs:200-205); any output may be null.  Only the rows first - 1 .. n - 2 reach
+    // the vocabulary head: on the fp32 matrix cores without storing their logits (launch_score_head; f32 / bf16 heads with
+    // hidden % 32 == 0), else through the 8-row logits buffer of the verify step (launch_score_rows; quantized heads, other
+    // geometries, or set_score_fused(false)).  The results stay on the device until one copy at the end.  Leaves the model as
+    // reset(); forward(ids, n) does.  Throws InvalidConfig naming the argument, before any GPU work, for n < 2, first outside
+    // [1, n), n > context() and an id >= vocab.
+    void score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out);
+    void set_score_fused(bool on) { score_fused_ = on; }
+    // Head launches of score() by route since load.
+    uint64_t score_fused_calls() const { return score_fused_calls_; }
+    uint64_t score_rows_calls() const { return score_rows_calls_; }
     // Cache rows [first, first + rows) of one layer, K after RoPE and V, f32 [rows, kv_heads * head_dim] each (a test hook).
     void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
     void last_hidden(float* out, int rows) const;  // final-normed hidden states of the last (<= 8-row) pass
@@ -190,7 +203,13 @@ private:
     void finish_load();                                                // attention splits, workspace, stream
     // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
     void qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what);
-    void prefill_rows(const uint32_t* ids_host, int n);  // n new tokens through the matrix-core GEMMs
+    // n new tokens through the matrix-core GEMMs; score: each chunk's rows whose successor is scored go through the final norm
+    // and score_head_rows
+    void prefill_rows(const uint32_t* ids_host, int n, bool score = false);
+    void forward_rows(const uint32_t* ids, int n, bool score);  // forward(), with score()'s sink
+    void ensure_score();
+    // cnt final-normed rows Xn [cnt, hidden] of positions lo .. lo + cnt - 1 against the targets ids[lo + 1 ..]
+    void score_head_rows(const float* Xn, int lo, int cnt);
     void enqueue_argmax(bool record);
     hipGraphExec_t step_graph();
 
@@ -272,6 +291,15 @@ private:
     hipGraphExec_t lookup_graphs_[kLanes + 1] = {};
     int lookup_ngram_[2] = {0, 0};
     uint64_t verify_stream_calls_ = 0, verify_fallback_calls_ = 0;
+    // scoring (allocated on first use): the targets (ids shifted by one) and the three result rows [context], the slab
+    // partials of the fused head; first_ / n_ of the call in flight
+    uint32_t *score_tgt_ = nullptr, *score_top_ = nullptr;
+    float *score_lp_ = nullptr, *score_tlp_ = nullptr;
+    void* score_scratch_ = nullptr;
+    size_t score_scratch_bytes_ = 0;
+    int score_first_ = 0, score_n_ = 0;
+    bool score_fused_ = true;
+    uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0;
 };
 
 }  // namespace kjarni

@@ -135,6 +135,22 @@ hipError_t launch_lookup_draft(const int32_t* history, LlmLookupState* state, in
 hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int rows, const uint32_t* ids, unsigned long long* best_scratch,
                               LlmLookupState* state, int32_t* history, int hist_cap, int* pos, int32_t* log, int log_cap, hipStream_t stream);
 
+// ---- scoring (LlmModel::score): per row of final-normed hidden states X[m, k] the log-sum-exp of its `vocab` logits X . W^T,
+// the arg-max (last maximum wins, launch_argmax's rule) and the logit of targets[row]; outputs logprob = target - lse,
+// top, top_logprob = best - lse and lse, each [m] and each may be null (targets null: no logprob).
+// The fused route: the head on the fp32 matrix cores without storing the logits (llm_score_head_kernel + llm_score_merge_kernel),
+// W [vocab, k] f32 or bf16 row-major.  Needs k % 32 == 0, ldx % 4 == 0 and 16-byte aligned X and W (llm_score_head_takes).
+// slab_tiles: 64-wide vocabulary tiles per workgroup, 0 = chosen so that the grid covers the chip; scratch:
+// score_head_scratch_bytes(m, vocab, slab_tiles) bytes, no initialisation needed.
+bool llm_score_head_takes(const float* X, int64_t ldx, const void* W, int bf16, int k);
+int score_head_slab_tiles(int m, int vocab, int slab_tiles);  // the slab width the launch uses
+size_t score_head_scratch_bytes(int m, int vocab, int slab_tiles);
+hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
+                             int slab_tiles, void* scratch, float* logprob, uint32_t* top, float* top_logprob, float* lse, hipStream_t stream);
+// The rows route: the same outputs from up to 8 materialised logits rows [rows, ld] (llm_score_rows_kernel).
+hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, float* logprob, uint32_t* top,
+                             float* top_logprob, float* lse, hipStream_t stream);
+
 // ---- sampled decoding: the O(vocab) part on the device (llm_kernels.hip) ----------------------------------------------
 struct SampleHeader {   // 32 bytes, device memory mirrored to the host per sampled token
     float mx;           // maximum logit

@@ -2651,4 +2651,294 @@ hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int ro
     return hipGetLastError();
 }
 
+// ---- scoring: log-softmax statistics of every row's vocabulary logits (LlmModel::score) -------------------------------------
+//   final norm + head   crates/kjarni-models/src/models/llama/cpu_decoder.rs:196-219, gpt2/cpu_decoder.rs:371-394
+//   log_softmax_1d      crates/kjarni-transformers/src/common/sampling.rs:200-205 (x - max - ln(sum exp(x - max)))
+
+namespace {
+
+constexpr int SC_BM = 64, SC_BN = 64, SC_BK = 32, SC_STRIDE = SC_BK + 4;
+
+// What one slab of vocabulary tiles knows about one row.
+struct ScorePartial {
+    unsigned long long key;  // argmax_key of the slab's best logit (0: nothing seen)
+    float mx;                // the slab's maximum
+    float sm;                // sum of exp(x - mx) over the slab
+    float tgt;               // the target's logit where the target lies in the slab, else 0
+    float pad;
+};
+
+__device__ __forceinline__ float argmax_key_value(unsigned long long key)
+{
+    const uint32_t u = (uint32_t)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+
+// (mx, sm) += (omx, osm): sums of exp(x - mx) brought to the common maximum.
+__device__ __forceinline__ void score_combine(float& mx, float& sm, float omx, float osm)
+{
+    const float m = fmaxf(mx, omx);
+    if (m == -INFINITY) return;  // both empty
+    sm = sm * expf(mx - m) + osm * expf(omx - m);
+    mx = m;
+}
+
+// Eight consecutive weights of a row as two f32x4 (bf16 widened).
+__device__ __forceinline__ void score_load_w(const float* p, f32x4& a, f32x4& b)
+{
+    a = *reinterpret_cast<const f32x4*>(p);
+    b = *reinterpret_cast<const f32x4*>(p + 4);
+}
+__device__ __forceinline__ void score_load_w(const uint16_t* p, f32x4& a, f32x4& b)
+{
+    const F8 w = load8(p, 0);
+    a = f32x4{w.v[0], w.v[1], w.v[2], w.v[3]};
+    b = f32x4{w.v[4], w.v[5], w.v[6], w.v[7]};
+}
+
+// The vocabulary head without its output: for 64 rows of X[M, K] (final-normed hidden states) and a slab of `slab_tiles`
+// consecutive 64-wide tiles of W[N, K] (f32 or bf16, widened while staged), the slab's running maximum, sum of exponentials,
+// best (value, index) and the target's logit per row -- the [M, N] logits are never stored.  The structure is
+// prefill_gemm_kernel's (4 waves, one 32 x 32 MFMA tile each, BK = 32 operand tiles double-buffered in LDS with the next
+// tile's global loads in flight during the MFMAs, v_mfma_f32_32x32x2_f32: an exact k-ordered f32 fma chain), computing the
+// transposed tile W . X^T, so that lane == row: a lane's 16 accumulators are 16 vocabulary entries of its own row and the
+// reduction stays inside the lane until the slab ends, where the two half-waves (shuffle) and the two waves that share
+// rows (LDS) meet once.  Columns >= N contribute nothing (their loads are clamped), rows >= M are not stored.
+template <typename WT>
+__global__ __launch_bounds__(256) void llm_score_head_kernel(const float* __restrict__ X, int64_t ldx, const WT* __restrict__ W,
+                                                             const uint32_t* __restrict__ targets, int M, int N, int K, int m_tiles,
+                                                             int slab_tiles, int n_tiles, int slabs, ScorePartial* __restrict__ P)
+{
+    __shared__ __attribute__((aligned(16))) float sW[2][SC_BN * SC_STRIDE];
+    __shared__ __attribute__((aligned(16))) float sX[2][SC_BM * SC_STRIDE];
+    __shared__ ScorePartial sRed[SC_BM];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wv = wid >> 1, wx = wid & 1, l31 = lane & 31, half = lane >> 5;
+    // XCD-aware order (prefill_gemm_kernel): every XCD takes one contiguous run of workgroups, row tiles fastest, so the
+    // workgroups that stream the same slab of W sit behind the same L2
+    const int64_t nwg = gridDim.x;
+    const int64_t xcd = blockIdx.x % 8, slot = blockIdx.x / 8;
+    const int64_t q8 = nwg / 8, r8 = nwg % 8;
+    const int64_t bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const int mt = (int)(bid % m_tiles), slab = (int)(bid / m_tiles);
+    const int m0 = mt * SC_BM;
+    const int t_begin = slab * slab_tiles, t_end = min(t_begin + slab_tiles, n_tiles);
+
+    // X: 64 x 32 floats = 512 float4, two per thread.  W: 64 rows x 32 weights, eight consecutive ones per thread.
+    const int a_row = tid >> 3, a_c4 = tid & 7;
+    const float* x_ptr[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) x_ptr[i] = X + (int64_t)min(m0 + a_row + 32 * i, M - 1) * ldx + a_c4 * 4;
+    const int w_row = tid >> 2, w_c = (tid & 3) * 8;
+    const WT* w_ptr = W;
+    f32x4 gx[2], gw[2];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) gx[i] = *reinterpret_cast<const f32x4*>(x_ptr[i] + k0);
+        score_load_w(w_ptr + k0, gw[0], gw[1]);
+    };
+    auto store = [&](int stage) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(&sX[stage][(a_row + 32 * i) * SC_STRIDE + a_c4 * 4]) = gx[i];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(&sW[stage][w_row * SC_STRIDE + w_c + 4 * i]) = gw[i];
+    };
+
+    const int row = m0 + wx * 32 + l31;
+    const uint32_t target = (targets && row < M) ? targets[row] : 0xFFFFFFFFu;
+    float mx = -INFINITY, sm = 0.0f, tgt = 0.0f;
+    unsigned long long key = 0ull;
+    const int nk = K / SC_BK;
+    const int fw = (wv * 32 + l31) * SC_STRIDE + half * 4, fx = (wx * 32 + l31) * SC_STRIDE + half * 4;
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = t * SC_BN;
+        w_ptr = W + (int64_t)min(n0 + w_row, N - 1) * K + w_c;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        load(0);
+        store(0);
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+            const int cur = kt & 1;
+            if (kt + 1 < nk) load((kt + 1) * SC_BK);
+#pragma unroll
+            for (int kk = 0; kk < SC_BK / 8; ++kk) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&sW[cur][fw + kk * 8]);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(&sX[cur][fx + kk * 8]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c], b[c], acc, 0, 0, 0);
+            }
+            if (kt + 1 < nk) store(cur ^ 1);
+            __syncthreads();
+        }
+        // acc[r] = logit of (row, n0 + wv * 32 + acc_row(r, half)): fold the 16 into the lane's running state
+        const int c0 = n0 + wv * 32;
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int col = c0 + acc_row(r, half);
+            if (col < N) {
+                tmax = fmaxf(tmax, acc[r]);
+                const unsigned long long kk = argmax_key(acc[r], col);
+                key = kk > key ? kk : key;
+                if ((uint32_t)col == target) tgt = acc[r];
+            }
+        }
+        if (tmax > -INFINITY) {
+            const float nm = fmaxf(mx, tmax);
+            float ts = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (c0 + acc_row(r, half) < N) ts += expf(acc[r] - nm);
+            sm = sm * expf(mx - nm) + ts;
+            mx = nm;
+        }
+    }
+    // the two half-waves of a row, then the two waves
+    {
+        const float omx = __shfl_xor(mx, 32, kWave), osm = __shfl_xor(sm, 32, kWave), otg = __shfl_xor(tgt, 32, kWave);
+        const unsigned long long ok = __shfl_xor(key, 32, kWave);
+        score_combine(mx, sm, omx, osm);
+        tgt += otg;  // at most one of them is not 0
+        key = ok > key ? ok : key;
+    }
+    if (wv == 1 && half == 0) sRed[wx * 32 + l31] = ScorePartial{key, mx, sm, tgt, 0.0f};
+    __syncthreads();
+    if (wv == 0 && half == 0 && row < M) {
+        const ScorePartial o = sRed[wx * 32 + l31];
+        score_combine(mx, sm, o.mx, o.sm);
+        tgt += o.tgt;
+        key = o.key > key ? o.key : key;
+        P[((int64_t)mt * slabs + slab) * SC_BM + wx * 32 + l31] = ScorePartial{key, mx, sm, tgt, 0.0f};
+    }
+}
+
+// One thread per row: the slab partials in slab order.  M = max mx, S = sum sm exp(mx - M), lse = M + log S.
+__global__ __launch_bounds__(256) void llm_score_merge_kernel(const ScorePartial* __restrict__ P, const uint32_t* __restrict__ targets, int M,
+                                                              int vocab, int slabs, int slab_tiles, float* __restrict__ logprob,
+                                                              uint32_t* __restrict__ top, float* __restrict__ top_logprob,
+                                                              float* __restrict__ lse_out)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= M) return;
+    const ScorePartial* p = P + (int64_t)(row / SC_BM) * slabs * SC_BM + row % SC_BM;
+    float mx = -INFINITY;
+    unsigned long long key = 0ull;
+    for (int s = 0; s < slabs; ++s) {
+        const ScorePartial q = p[(int64_t)s * SC_BM];
+        mx = fmaxf(mx, q.mx);
+        key = q.key > key ? q.key : key;
+    }
+    float sum = 0.0f;
+    for (int s = 0; s < slabs; ++s) {
+        const ScorePartial q = p[(int64_t)s * SC_BM];
+        sum += q.sm * expf(q.mx - mx);
+    }
+    const float lse = mx + logf(sum);
+    if (lse_out) lse_out[row] = lse;
+    if (top) top[row] = (uint32_t)(key & 0xFFFFFFFFull);
+    if (top_logprob) top_logprob[row] = argmax_key_value(key) - lse;
+    if (logprob && targets) {
+        const uint32_t t = targets[row];
+        logprob[row] = t < (uint32_t)vocab ? p[(int64_t)((int)(t / SC_BN) / slab_tiles) * SC_BM].tgt - lse : -INFINITY;
+    }
+}
+
+// The same statistics from materialised logits [rows, ld]: one workgroup per row, the maximum (with its index, last one
+// winning) first, then the sum of exp(x - max); both reduced lane -> wave -> workgroup in a fixed order.
+__global__ __launch_bounds__(256) void llm_score_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                             const uint32_t* __restrict__ targets, float* __restrict__ logprob,
+                                                             uint32_t* __restrict__ top, float* __restrict__ top_logprob,
+                                                             float* __restrict__ lse_out)
+{
+    __shared__ unsigned long long red_key[4];
+    __shared__ float red_sum[4];
+    const float* row = logits + (int64_t)blockIdx.x * ld;
+    unsigned long long key = 0ull;
+    for (int i = threadIdx.x; i < vocab; i += 256) {
+        const unsigned long long kk = argmax_key(row[i], i);
+        key = kk > key ? kk : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off, kWave);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) red_key[threadIdx.x >> 6] = key;
+    __syncthreads();
+    key = red_key[0];
+    for (int w = 1; w < 4; ++w) key = red_key[w] > key ? red_key[w] : key;
+    const float mx = argmax_key_value(key);
+    float sum = 0.0f;
+    for (int i = threadIdx.x; i < vocab; i += 256) sum += expf(row[i] - mx);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, kWave);
+    if ((threadIdx.x & 63) == 0) red_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const float lse = mx + logf((red_sum[0] + red_sum[1]) + (red_sum[2] + red_sum[3]));
+    const int r = blockIdx.x;
+    if (lse_out) lse_out[r] = lse;
+    if (top) top[r] = (uint32_t)(key & 0xFFFFFFFFull);
+    if (top_logprob) top_logprob[r] = mx - lse;
+    if (logprob && targets) logprob[r] = targets[r] < (uint32_t)vocab ? row[targets[r]] - lse : -INFINITY;
+}
+
+}  // namespace
+
+bool llm_score_head_takes(const float* X, int64_t ldx, const void* W, int bf16, int k)
+{
+    return k > 0 && k % SC_BK == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
+           (bf16 == 0 || bf16 == 1);
+}
+
+int score_head_slab_tiles(int m, int vocab, int slab_tiles)
+{
+    const int n_tiles = (vocab + SC_BN - 1) / SC_BN, m_tiles = (m + SC_BM - 1) / SC_BM;
+    if (slab_tiles > 0) return std::min(slab_tiles, n_tiles);
+    // four workgroups per CU (their LDS allows that many): row tiles x slabs >= 1 024 where the vocabulary has the tiles
+    const int slabs = std::max(1, std::min(n_tiles, (1024 + m_tiles - 1) / m_tiles));
+    return (n_tiles + slabs - 1) / slabs;
+}
+
+size_t score_head_scratch_bytes(int m, int vocab, int slab_tiles)
+{
+    if (m <= 0 || vocab <= 0) return 0;
+    const int n_tiles = (vocab + SC_BN - 1) / SC_BN, m_tiles = (m + SC_BM - 1) / SC_BM;
+    const int st = score_head_slab_tiles(m, vocab, slab_tiles);
+    return (size_t)m_tiles * ((n_tiles + st - 1) / st) * SC_BM * sizeof(ScorePartial);
+}
+
+hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
+                             int slab_tiles, void* scratch, float* logprob, uint32_t* top, float* top_logprob, float* lse, hipStream_t stream)
+{
+    if (m <= 0) return hipSuccess;
+    if (vocab <= 0 || !scratch || !llm_score_head_takes(X, ldx, W, bf16, k)) return hipErrorInvalidValue;
+    const int n_tiles = (vocab + SC_BN - 1) / SC_BN, m_tiles = (m + SC_BM - 1) / SC_BM;
+    const int st = score_head_slab_tiles(m, vocab, slab_tiles);
+    const int slabs = (n_tiles + st - 1) / st;
+    ScorePartial* P = static_cast<ScorePartial*>(scratch);
+    const dim3 grid((unsigned)(m_tiles * slabs));
+    if (bf16)
+        hipLaunchKernelGGL((llm_score_head_kernel<uint16_t>), grid, dim3(256), 0, stream, X, ldx, static_cast<const uint16_t*>(W), targets, m,
+                           vocab, k, m_tiles, st, n_tiles, slabs, P);
+    else
+        hipLaunchKernelGGL((llm_score_head_kernel<float>), grid, dim3(256), 0, stream, X, ldx, static_cast<const float*>(W), targets, m, vocab,
+                           k, m_tiles, st, n_tiles, slabs, P);
+    hipLaunchKernelGGL(llm_score_merge_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, P, targets, m, vocab, slabs, st, logprob, top,
+                       top_logprob, lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, float* logprob, uint32_t* top,
+                             float* top_logprob, float* lse, hipStream_t stream)
+{
+    if (rows <= 0) return hipSuccess;
+    if (rows > LLM_MAX_ROWS || vocab <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(llm_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, targets, logprob, top, top_logprob,
+                       lse);
+    return hipGetLastError();
+}
+
 }  // namespace kjarni

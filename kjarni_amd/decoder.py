@@ -221,3 +221,28 @@ class HipDecoder:
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_verify_gemv_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+
+    # ---- scoring: per-token log-probabilities of a given sequence ----
+    def score(self, ids: Sequence[int], first: int = 1):
+        """Resets the cache, runs `ids` and returns, for the positions first .. len(ids) - 1: (log p(ids[p] | ids[:p]) f32, the
+        arg-max token of that distribution u32, the arg-max's log-probability f32), len(ids) - first entries each.  Leaves the
+        decoder as reset() + forward(ids) does."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        cnt = max(a.size - int(first), 0)
+        lp, top, tlp = np.empty(cnt, np.float32), np.empty(cnt, np.uint32), np.empty(cnt, np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_score(self._h, u32(a), a.size, int(first), f(lp), u32(top), f(tlp)))
+        return lp, top, tlp
+
+    def set_score_fused(self, on: bool):
+        """On (the default): f32 / bf16 heads are scored on the matrix cores without storing the logits; off: every checkpoint
+        takes the rows route (8 materialised logits rows at a time)."""
+        lib().kjarni_hip_decoder_set_score_fused(self._h, 1 if on else 0)
+
+    def score_calls(self):
+        """(fused, rows): head launches of score() by route since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_score_calls(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)

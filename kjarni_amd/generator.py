@@ -50,6 +50,13 @@ class Generator:
         check_error(lib().kjarni_generator_generate(self._handle, prompt.encode("utf-8"), _gen(config), C.byref(out)))
         return _take_string(out)
 
+    def score(self, context: str, continuation: str):
+        """(sum_logprob, n_tokens, is_greedy) of `continuation` after `context`: the tokens encode(context + continuation)
+        adds to encode(context); an empty context is the BOS token alone."""
+        r = _ffi.KjarniScoreResult()
+        check_error(lib().kjarni_generator_score(self._handle, context.encode("utf-8"), continuation.encode("utf-8"), C.byref(r)))
+        return float(r.sum_logprob), int(r.n_tokens), bool(r.is_greedy)
+
     def generate_batch(self, prompts: Sequence[str], config: Optional[GenerationConfig] = None) -> List[str]:
         """generate() for every prompt, up to 8 of them (set_lanes) decoded in lock step; texts in prompt order."""
         arr = _ffi.KjarniStringArray()

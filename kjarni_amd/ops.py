@@ -302,3 +302,26 @@ def topk(scores, k: int, device: int = 0):
     finally:
         for p in bufs:
             L.kjarni_hip_free(device, p)
+
+
+
+def score_head(hidden, W, targets, bf16=False, slab_tiles=0, fused=True, device=0):
+    """The scoring head kernels alone (kjarni_hip_op_score_head): hidden f32 [m, k] (final-normed rows), W [vocab, k] f32, or
+    with bf16=True its bf16 bits (uint16); targets [m].  Returns (logprob f32 [m], top u32 [m], top_logprob f32 [m], lse f32 [m]).
+    fused: the matrix-core kernel that never stores the logits (slab_tiles 64-wide vocabulary tiles per workgroup, 0 =
+    automatic); else the rows route over logits materialised 8 rows at a time."""
+    import ctypes as C
+    from ._ffi import check_error
+    hidden = np.ascontiguousarray(hidden, np.float32)
+    W = np.ascontiguousarray(W, np.uint16 if bf16 else np.float32)
+    targets = np.ascontiguousarray(targets, np.uint32)
+    m, k = hidden.shape
+    vocab = W.shape[0]
+    if W.shape[1] != k or targets.shape != (m,):
+        raise ValueError("hidden [m, k], W [vocab, k], targets [m]")
+    lp, top, tlp, lse = np.empty(m, np.float32), np.empty(m, np.uint32), np.empty(m, np.float32), np.empty(m, np.float32)
+    f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+    check_error(lib().kjarni_hip_op_score_head(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab, u32(targets),
+                                               slab_tiles, 1 if fused else 0, f(lp), u32(top), f(tlp), f(lse)))
+    return lp, top, tlp, lse

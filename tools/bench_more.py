@@ -28,6 +28,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            acceptance verify_ms / plain_ms - 1, and end-to-end tokens/s with the acceptance histogram -- on a random-init
            model, whose greedy output degenerates into repetition: the full-acceptance end of the range, not a workload.
            KJARNI_LOOKUP_STEPS=N: N verify steps of 8 rows on the Llama shape only (for a kernel trace).
+  llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
+           shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
+           matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
+           end in a synchronise; the head's added time score - forward per route.
+           KJARNI_SCORE_TRACE=N: N fused score() calls of the 2 048-token prompt on the Llama shape only (for a kernel trace).
 """
 import json
 import os
@@ -894,6 +899,76 @@ def main():
             dec = kjarni_amd.HipDecoder(gd)
             measure("gpt2-small shape, bf16 weights", dec, rng.integers(0, 50257, 128).tolist(), 512,
                     "bf16 weights, f32 activations/accumulate/KV")
+            del dec
+
+    if "llm_score" in which:
+        # Method (measuring guide, section 5; as llm_lookup): one process on one box; forward() -- the yardstick --, score() on
+        # the fused route and score() on the rows route are warmed first, then alternated twice; every run ends in a
+        # synchronise (forward() and score() return after one), medians over the runs.  KJARNI_SCORE_TRACE=N: N fused score()
+        # calls of the 2 048-token prompt on the Llama shape only (for a kernel trace of its own).
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        trace_calls = int(os.environ.get("KJARNI_SCORE_TRACE", "0"))
+        LENS = (128, 2048)
+
+        def run_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            return (time.perf_counter() - t0) * 1e3
+
+        def measure(label, dec, vocab, lo, dtype):
+            prompts = {n: rng.integers(lo, vocab, n).tolist() for n in LENS}
+            if trace_calls:
+                for _ in range(trace_calls):
+                    dec.score(prompts[2048])
+                return
+
+            def fwd(ids):
+                dec.reset()
+                dec.forward(ids, fetch=False)
+
+            def score(ids, fused):
+                dec.set_score_fused(fused)
+                dec.score(ids)
+            for n in LENS:
+                fwd(prompts[n])
+                score(prompts[n], True)
+                score(prompts[n], False)
+            runs = {(kind, n): [] for kind in ("forward", "fused", "rows") for n in LENS}
+            for rep in range(2):
+                for n in LENS:
+                    for _ in range(3):
+                        runs[("forward", n)].append(run_ms(lambda: fwd(prompts[n])))
+                        runs[("fused", n)].append(run_ms(lambda: score(prompts[n], True)))
+                        runs[("rows", n)].append(run_ms(lambda: score(prompts[n], False)))
+            dec.set_score_fused(True)
+            med = lambda xs: float(np.median(xs))  # noqa: E731
+            out = {}
+            for n in LENS:
+                f, a, b = med(runs[("forward", n)]), med(runs[("fused", n)]), med(runs[("rows", n)])
+                out[str(n)] = {"forward_ms": round(f, 3), "score_fused_ms": round(a, 3), "score_rows_ms": round(b, 3),
+                               "head_added_fused_ms": round(a - f, 3), "head_added_rows_ms": round(b - f, 3),
+                               "rows_over_fused_added": round((b - f) / (a - f), 2) if a > f else None,
+                               "head_gflop": round(2.0 * (n - 1) * vocab * dec.hidden / 1e9, 2),
+                               "runs": {k: [round(x, 3) for x in runs[(k, n)]] for k in ("forward", "fused", "rows")}}
+            emit({"metric": f"scoring, {label}", "unit": "ms added by the head at 2048 tokens (fused)", "value": out["2048"]["head_added_fused_ms"],
+                  "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                  "config": {"workload": f"{label}, random init; forward() of a 128- and a 2 048-token prompt against score() of the same ids "
+                                         "(first = 1) on the fused and on the rows route, alternated twice in one process, medians of 6 runs, "
+                                         "every run ends in a synchronise"},
+                  "lengths": out, "weight_bytes": dec.weight_bytes})
+
+        d = os.path.join(tmp, "llama-1b-score")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, 100000, 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        if not trace_calls:  # (the trace run is the Llama shape alone)
+            gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=2048, vocab_size=50257, eos_token_id=None)
+            gd = os.path.join(tmp, "gpt2-small-score")
+            gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+            dec = kjarni_amd.HipDecoder(gd)
+            measure("gpt2-small shape, bf16 weights (n_ctx 2048)", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
             del dec
 
 
