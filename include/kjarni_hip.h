@@ -643,6 +643,66 @@ KjarniErrorCode kjarni_lookup_draft(const uint32_t* tokens, size_t n, const Kjar
  * INVALID_CONFIG before any GPU work. */
 KjarniErrorCode kjarni_hip_decoder_verify_step(KjarniHipDecoder* decoder, uint32_t token, const uint32_t* draft, int32_t n_draft,
                                                int32_t rows, uint32_t* tokens_out, int32_t* n_accepted, float* logits_out);
+/* ---- prompt-lookup decoding for sampled requests (NOT in the reference) ----
+ * Lookup drafts are deterministic, so no rejection scheme is needed: the plain loop decides token i as a function of (processed
+ * logits, the i-th draw); a verify step decides row 0 with the next draw and, while the result equals the draft, the next row
+ * with the draw after it; the first token that differs is kept.  Draws are taken one per decided row, never for a row that is
+ * not reached: the ids are the plain loop's for the same draw stream.  The n-gram ban is not built for rows. */
+typedef struct KjarniHipSamplingOptions {
+    size_t max_new_tokens;
+    float repetition_penalty;     /* 1 = off */
+    int32_t no_repeat_ngram;      /* 0 = off */
+    int32_t sample;               /* 0 = greedy */
+    float temperature;
+    int64_t top_k;                /* < 0 = not set */
+    float top_p, min_p;           /* < 0 = not set */
+    const uint32_t* stop_ids;     /* n_stop == 0: config.json's eos ids */
+    size_t n_stop;
+    const float* uniforms;        /* token i uses uniforms[i]; NULL: a generator seeded with `seed` */
+    size_t n_uniforms;            /* >= max_new_tokens when uniforms is given, else INVALID_CONFIG before any GPU work */
+    uint64_t seed;
+} KjarniHipSamplingOptions;
+/* sizeof(KjarniHipSamplingOptions) and the offset of every field in declaration order, as this library was compiled (a binding
+ * checks its mirror against it): writes min(14, capacity) values, returns 14. */
+size_t kjarni_hip_sampling_options_layout(size_t* out, size_t capacity);
+/* kjarni_hip_decoder_generate with these options.  lookup NULL: the plain loop (the token-level API with sampling).  lookup
+ * given: the sampled lookup loop when options->sample and no n-gram ban; greedy without processors takes
+ * kjarni_hip_decoder_generate_lookup's loop; greedy with a penalty, or any n-gram ban, the plain loop (stats zero).  stats as
+ * kjarni_hip_decoder_generate_lookup.  A lookup config outside its ranges, a prompt longer than the context or an empty
+ * prompt: INVALID_CONFIG before any GPU work. */
+KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecoder* decoder, const uint32_t* prompt, size_t n_prompt,
+                                                    const KjarniHipSamplingOptions* options, const KjarniHipLookupConfig* lookup,
+                                                    KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out, size_t capacity,
+                                                    size_t* n_out, KjarniHipLookupStats* stats);
+/* Tokens of sampled / processed requests decided from the device's candidates, and those that needed a logits row, since load. */
+void kjarni_hip_decoder_sampling_routes(const KjarniHipDecoder* decoder, uint64_t* from_candidates, uint64_t* from_logits);
+/* Test hook: kjarni_hip_decoder_verify_step for a sampled request (options->sample != 0, no n-gram ban).  history[n_history]:
+ * the tokens the repetition penalty counts, the last of them `token` (not read when the penalty is 1).  uniforms[n_draft + 1]:
+ * one draw per decided row.  picks_out[0 .. *accepted_out] (room for 8), *draws_used_out = *accepted_out + 1; logits_out (may
+ * be NULL) f32 [n_draft + 1, vocab]: the processed rows.  The cache grows by *accepted_out + 1.  Ranges as
+ * kjarni_hip_decoder_verify_step: INVALID_CONFIG before any GPU work. */
+KjarniErrorCode kjarni_hip_decoder_verify_step_sampled(KjarniHipDecoder* decoder, uint32_t token, const uint32_t* draft, int32_t n_draft,
+                                                       int32_t rows, const KjarniHipSamplingOptions* options, const uint32_t* history,
+                                                       size_t n_history, const float* uniforms, uint32_t* picks_out,
+                                                       int32_t* accepted_out, int32_t* draws_used_out, float* logits_out);
+/* The sampler's cut over `rows` (1..8) logits rows of stride ld >= vocab in one chain of three launches.  Per row r: headers_out[r]
+ * and, in ids_out / logits_out [rows, capacity], its first min(count, capacity) candidates.  A guard band lies behind every
+ * row's `capacity` slots, behind the headers and behind every row's scratch (INFERENCE_FAILED when one is touched). */
+KjarniErrorCode kjarni_hip_op_sample_candidates_rows(int32_t device, const float* logits, int64_t ld, int32_t rows, int32_t vocab,
+                                                     int64_t top_k, float top_p, float min_p, int32_t capacity,
+                                                     KjarniHipSampleHeader* headers_out, uint32_t* ids_out, float* logits_out);
+/* The repetition penalty over the rows of a verify block: logits [rows, ld]; history[n_history] ends with ids[0]; row r is
+ * penalised for the history plus ids[1..r], once per occurrence.  logits_out [rows, ld] (the padding comes back untouched). */
+KjarniErrorCode kjarni_hip_op_repetition_penalty_rows(int32_t device, const float* logits, int64_t ld, int32_t rows, int32_t vocab,
+                                                      const uint32_t* ids, const uint32_t* history, int32_t n_history, float penalty,
+                                                      float* logits_out);
+/* Deciding a block on the host (the specification of the device path): logits [rows, ld] already processed, draft[n_draft];
+ * row by row the distribution of kjarni_sampling_distribution and kjarni_sample_from_probs with uniforms[r]; stops after the
+ * first pick that differs from the draft or after row min(n_draft, rows - 1).  picks_out[0 .. *accepted_out],
+ * *draws_used_out = *accepted_out + 1; draft entries from the first rejection on are not read. */
+KjarniErrorCode kjarni_lookup_accept_sampled(const float* logits, int64_t ld, int32_t rows, size_t vocab, const uint32_t* draft,
+                                             int32_t n_draft, float temperature, int64_t top_k, float top_p, float min_p,
+                                             const float* uniforms, uint32_t* picks_out, int32_t* accepted_out, int32_t* draws_used_out);
 /* Projections of verify steps that took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel
  * since load (counted when enqueued: a replayed graph counts once, at capture). */
 void kjarni_hip_decoder_verify_gemv_calls(const KjarniHipDecoder* decoder, uint64_t* streamed, uint64_t* fallback);
@@ -651,6 +711,11 @@ void kjarni_hip_decoder_verify_gemv_calls(const KjarniHipDecoder* decoder, uint6
 KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGenerator* generator, int32_t draft_tokens);
 /* kjarni_hip_decoder_verify_gemv_calls of the generator's model: it moves only when a call took the lookup loop. */
 void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* generator, uint64_t* streamed, uint64_t* fallback);
+/* Prompt lookup for sampled configs (with or without a repetition penalty): off by default.  When on, prompt lookup is set
+ * (1..7) and the resolved config has no n-gram ban, generate / generate_stream / send take the sampled lookup loop; the draws
+ * come from the handle's generator exactly as on the plain path.  Otherwise nothing changes. */
+KjarniErrorCode kjarni_hip_generator_set_prompt_lookup_sampling(KjarniGenerator* generator, int32_t on);
+KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniChat* chat, int32_t on);
 
 /* ---- scoring: per-token log-probabilities of a given sequence (NOT in the reference: it has no scoring entry point; the
  * arithmetic is its final norm + head, llama/cpu_decoder.rs:196-219, gpt2/cpu_decoder.rs:371-394, and log_softmax_1d,

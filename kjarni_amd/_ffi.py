@@ -242,6 +242,13 @@ class KjarniHipSampleHeader(Structure):
     _fields_ = [("mx", c_float), ("sum", c_float), ("floor", c_float), ("count", C.c_uint32), ("overflow", C.c_uint32)]
 
 
+class KjarniHipSamplingOptions(Structure):
+    _fields_ = [("max_new_tokens", c_size_t), ("repetition_penalty", c_float), ("no_repeat_ngram", c_int32), ("sample", c_int32),
+                ("temperature", c_float), ("top_k", C.c_int64), ("top_p", c_float), ("min_p", c_float),
+                ("stop_ids", POINTER(C.c_uint32)), ("n_stop", c_size_t), ("uniforms", POINTER(c_float)), ("n_uniforms", c_size_t),
+                ("seed", c_uint64)]
+
+
 class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
@@ -467,6 +474,20 @@ SIGNATURES = {
     "kjarni_hip_decoder_verify_step": (c_int32, [c_void_p, C.c_uint32, _u32p, c_int32, c_int32, _u32p, POINTER(c_int32), _f32p]),
     "kjarni_hip_decoder_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_prompt_lookup": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_set_prompt_lookup_sampling": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_chat_set_prompt_lookup_sampling": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_generate_sampled": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
+                                                      POINTER(KjarniHipLookupConfig), KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t,
+                                                      POINTER(c_size_t), POINTER(KjarniHipLookupStats)]),
+    "kjarni_hip_sampling_options_layout": (c_size_t, [POINTER(c_size_t), c_size_t]),
+    "kjarni_hip_decoder_sampling_routes": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_decoder_verify_step_sampled": (c_int32, [c_void_p, C.c_uint32, _u32p, c_int32, c_int32, POINTER(KjarniHipSamplingOptions),
+                                                         _u32p, c_size_t, _f32p, _u32p, POINTER(c_int32), POINTER(c_int32), _f32p]),
+    "kjarni_hip_op_sample_candidates_rows": (c_int32, [c_int32, _f32p, C.c_int64, c_int32, c_int32, C.c_int64, c_float, c_float, c_int32,
+                                                       POINTER(KjarniHipSampleHeader), _u32p, _f32p]),
+    "kjarni_hip_op_repetition_penalty_rows": (c_int32, [c_int32, _f32p, C.c_int64, c_int32, c_int32, _u32p, _u32p, c_int32, c_float, _f32p]),
+    "kjarni_lookup_accept_sampled": (c_int32, [_f32p, C.c_int64, c_int32, c_size_t, _u32p, c_int32, c_float, C.c_int64, c_float, c_float,
+                                               _f32p, _u32p, POINTER(c_int32), POINTER(c_int32)]),
     "kjarni_hip_generator_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_generator_generate_batch": (c_int32, [c_void_p, POINTER(c_char_p), c_size_t, POINTER(KjarniGenerationConfig),
                                                   POINTER(KjarniStringArray)]),

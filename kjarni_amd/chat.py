@@ -176,6 +176,10 @@ class Chat:
         """Sampling / logits processors with the O(vocab) work on the device (default) or on a host copy of the logits."""
         lib().kjarni_hip_chat_set_device_sampling(self._handle, 1 if on else 0)
 
+    def set_prompt_lookup_sampling(self, on: bool):
+        """Prompt-lookup decoding for sampled requests (off by default): the replies are the plain path's for the same seed."""
+        check_error(lib().kjarni_hip_chat_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
+
     def sampling_counters(self):
         """(tokens decided from the device's candidates, tokens that needed the full logits)."""
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -349,7 +349,7 @@ GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, 
 // every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
 std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
                                 const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
-                                int prompt_lookup = 0)
+                                int prompt_lookup = 0, int sampled_lookup = 0)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     const GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
@@ -366,6 +366,11 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
         LookupConfig lk;
         lk.draft_tokens = prompt_lookup;
         model.generate_lookup(prompt_tokens, opt, lk, on_token, nullptr);
+    } else if (sampled_lookup > 0 && opt.sample && opt.no_repeat_ngram <= 0) {
+        // sampled requests (with or without a repetition penalty), when asked for: the same draws decide the same tokens
+        LookupConfig lk;
+        lk.draft_tokens = sampled_lookup;
+        model.generate_lookup_sampled(prompt_tokens, opt, lk, on_token, nullptr);
     } else {
         model.generate(prompt_tokens, opt, on_token);
     }
@@ -488,7 +493,8 @@ std::string Chat::run(const std::string& prompt, const GenerationOverrides& runt
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
-    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text);
+    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, 0,
+                               lookup_sampling_ ? LookupConfig().draft_tokens : 0);
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -572,7 +578,8 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
-    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_);
+    return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_,
+                               lookup_sampling_ ? prompt_lookup_ : 0);
 }
 
 Generator::Score Generator::score(const std::string& context, const std::string& continuation)

@@ -99,6 +99,9 @@ public:
     std::string generate_stream(const std::string& prompt, const GenerationOverrides& runtime,
                                 const std::function<bool(const std::string&)>& on_text);
     void reseed(uint64_t seed) { rng_.reseed(seed); }
+    // Prompt-lookup decoding for sampled requests (LlmModel::generate_lookup_sampled, the default draft length): off by default;
+    // a request with an n-gram ban and every greedy request keep the plain loop.
+    void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
 
 private:
     Chat() = default;
@@ -115,6 +118,7 @@ private:
     GenerationOverrides mode_overrides_;   // Generator::user_overrides
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
+    bool lookup_sampling_ = false;
     std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
 };
 
@@ -150,6 +154,9 @@ public:
     // config is greedy without a repetition penalty or an n-gram ban (LlmModel::generate_lookup); generate_batch is untouched.
     void set_prompt_lookup(int draft_tokens) { prompt_lookup_ = draft_tokens; }
     int prompt_lookup() const { return prompt_lookup_; }
+    // The same for sampled configs, with or without a repetition penalty (LlmModel::generate_lookup_sampled): off by default;
+    // taken when it is on, prompt lookup is set and the resolved config has no n-gram ban.
+    void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
     // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
     // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
     // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
@@ -174,6 +181,7 @@ private:
     std::mutex mutex_;
     int batch_lanes_ = 0;
     int prompt_lookup_ = 0;
+    bool lookup_sampling_ = false;
 };
 
 // str::trim (Unicode White_Space at both ends).

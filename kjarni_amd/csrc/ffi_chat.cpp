@@ -722,6 +722,20 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGener
     return KJARNI_OK;
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_prompt_lookup_sampling(KjarniGenerator* gen, int32_t on)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    gen->inner->set_prompt_lookup_sampling(on != 0);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniChat* chat, int32_t on)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    chat->inner->set_prompt_lookup_sampling(on != 0);
+    return KJARNI_OK;
+}
+
 KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
 {
     if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;

@@ -1,6 +1,7 @@
 // Token-level C ABI of the decoder-only path (kjarni_hip.h).  The reference's string-level chat group
 // (crates/kjarni-ffi/src/chat.rs) sits on top of the same loop (crates/kjarni-transformers/src/decoder/
 // generator.rs:228-381) plus a BPE tokenizer and chat templates, which are not built here.
+#include <cstddef>
 #include <cstring>
 #include <mutex>
 
@@ -296,6 +297,128 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_verify_step(KjarniHipDecoder* d
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
         *n_accepted = d->model->verify_step(token, draft, n_draft, rows, tokens_out, logits_out);  // ranges checked before any GPU work
+    });
+}
+
+// ---- prompt-lookup decoding for sampled requests ------------------------------------------------------------------------------
+
+static GenerateOptions sampling_options(const KjarniHipSamplingOptions& o)
+{
+    GenerateOptions g;
+    g.max_new_tokens = o.max_new_tokens;
+    g.repetition_penalty = o.repetition_penalty;
+    g.no_repeat_ngram = o.no_repeat_ngram;
+    g.sample = o.sample != 0;
+    g.sampling.temperature = o.temperature;
+    g.sampling.top_k = o.top_k;
+    g.sampling.top_p = o.top_p;
+    g.sampling.min_p = o.min_p;
+    if (o.n_stop) g.stop_ids.assign(o.stop_ids, o.stop_ids + o.n_stop);
+    return g;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecoder* d, const uint32_t* prompt, size_t n_prompt,
+                                                                  const KjarniHipSamplingOptions* options, const KjarniHipLookupConfig* lookup,
+                                                                  KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                  size_t capacity, size_t* n_out, KjarniHipLookupStats* stats)
+{
+    if (!options || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    if (options->uniforms && options->n_uniforms < options->max_new_tokens) {  // (the options are judged on their own, ahead of the handle)
+        set_last_error("n_uniforms (" + std::to_string(options->n_uniforms) + ") is less than max_new_tokens (" +
+                       std::to_string(options->max_new_tokens) + ")");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!d || (n_prompt && !prompt) || (capacity && !ids_out) || (options->n_stop && !options->stop_ids)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // everything that can be refused is refused before any GPU work
+        LookupConfig lk;
+        if (lookup) lk = lookup_config(lookup);
+        if (n_prompt == 0) throw InvalidConfig("cannot generate from an empty prompt");
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (n_prompt > (size_t)d->model->context())
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        std::function<bool(uint32_t)> cb;
+        if (on_token)
+            cb = [&](uint32_t id) {
+                KjarniToken t;
+                t.text = nullptr;  // token-level API: no tokenizer behind it
+                t.token_id = id;
+                t.is_special = false;
+                return on_token(t, user_data);
+            };
+        GenerateOptions opt = sampling_options(*options);
+        UniformRng rng(options->seed);
+        size_t drawn = 0;
+        const float* u = options->uniforms;
+        const size_t n_u = options->n_uniforms;
+        if (u)  // one draw per decided token, never more than max_new_tokens of them: a loop that asks for more has gone wrong
+            opt.uniform = [&drawn, u, n_u] {
+                if (drawn >= n_u) throw std::runtime_error("the draw stream is exhausted: more draws than uniforms");
+                return u[drawn++];
+            };
+        else opt.uniform = [&rng] { return rng.next(); };
+        const std::vector<uint32_t> p(prompt, prompt + n_prompt);
+        LookupStats st;
+        const std::vector<uint32_t> ids = lookup ? d->model->generate_lookup_sampled(p, opt, lk, cb, &st) : d->model->generate(p, opt, cb);
+        *n_out = ids.size();
+        if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+        if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
+    });
+}
+
+KJARNI_EXPORT size_t kjarni_hip_sampling_options_layout(size_t* out, size_t capacity)
+{
+    using O = KjarniHipSamplingOptions;
+    const size_t v[] = {sizeof(O), offsetof(O, max_new_tokens), offsetof(O, repetition_penalty), offsetof(O, no_repeat_ngram),
+                        offsetof(O, sample), offsetof(O, temperature), offsetof(O, top_k), offsetof(O, top_p), offsetof(O, min_p),
+                        offsetof(O, stop_ids), offsetof(O, n_stop), offsetof(O, uniforms), offsetof(O, n_uniforms), offsetof(O, seed)};
+    const size_t n = sizeof(v) / sizeof(v[0]);
+    for (size_t i = 0; out && i < n && i < capacity; ++i) out[i] = v[i];
+    return n;
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_sampling_routes(const KjarniHipDecoder* d, uint64_t* from_candidates, uint64_t* from_logits)
+{
+    if (from_candidates) *from_candidates = d ? d->model->tokens_from_candidates() : 0;
+    if (from_logits) *from_logits = d ? d->model->tokens_from_logits() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_verify_step_sampled(KjarniHipDecoder* d, uint32_t token, const uint32_t* draft, int32_t n_draft,
+                                                                     int32_t rows, const KjarniHipSamplingOptions* options,
+                                                                     const uint32_t* history, size_t n_history, const float* uniforms,
+                                                                     uint32_t* picks_out, int32_t* accepted_out, int32_t* draws_used_out,
+                                                                     float* logits_out)
+{
+    if (!d || !options || !uniforms || !picks_out || !accepted_out || (n_draft > 0 && !draft) || (n_history && !history))
+        return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        int used = 0;
+        *accepted_out = d->model->verify_step_sampled(token, draft, n_draft, rows, sampling_options(*options), history, n_history, uniforms, picks_out, &used,
+                                                      logits_out);  // ranges checked before any GPU work
+        if (draws_used_out) *draws_used_out = used;
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_lookup_accept_sampled(const float* logits, int64_t ld, int32_t rows, size_t vocab, const uint32_t* draft,
+                                                           int32_t n_draft, float temperature, int64_t top_k, float top_p, float min_p,
+                                                           const float* uniforms, uint32_t* picks_out, int32_t* accepted_out,
+                                                           int32_t* draws_used_out)
+{
+    if (!logits || !uniforms || !picks_out || !accepted_out || (n_draft > 0 && !draft)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        if (rows < 1 || rows > LlmModel::kLanes || n_draft < 0 || vocab < 1 || ld < (int64_t)vocab)
+            throw InvalidConfig("invalid block (rows 1..8, n_draft >= 0, vocab >= 1, ld >= vocab)");
+        SamplingParams p;
+        p.temperature = temperature;
+        p.top_k = top_k;
+        p.top_p = top_p;
+        p.min_p = min_p;
+        int used = 0;
+        *accepted_out = lookup_accept_sampled(logits, ld, rows, vocab, draft, n_draft, p, [&] { return uniforms[used++]; }, picks_out);
+        if (draws_used_out) *draws_used_out = used;
     });
 }
 

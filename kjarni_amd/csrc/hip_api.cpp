@@ -1,4 +1,5 @@
 // Token-level C ABI (include/kjarni_hip.h).
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <sys/stat.h>
@@ -816,6 +817,89 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_sample_candidates(int32_t device, co
                 logits_out[(size_t)c * capacity + i] = cand[i].logit;
             }
         }
+    });
+}
+
+// The rows cut alone: one launch_sample_candidates_rows over a block of logits rows.  The candidate slots start out as a
+// sentinel: whatever a row does not own by its count must still hold it afterwards (a row that overflows writes nothing past
+// its `capacity` slots, into no neighbour's list), and a guard band lies behind the scratch, the headers and the last list.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_sample_candidates_rows(int32_t device, const float* logits, int64_t ld, int32_t rows, int32_t vocab,
+                                                                   int64_t top_k, float top_p, float min_p, int32_t capacity,
+                                                                   KjarniHipSampleHeader* headers_out, uint32_t* ids_out, float* logits_out)
+{
+    if (!logits || !headers_out || !ids_out || !logits_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 8 || vocab < 1 || ld < vocab || capacity < 1)
+            throw InvalidConfig("invalid rows-sampler arguments (rows 1..8, vocab >= 1, ld >= vocab, capacity >= 1)");
+        use_device(device);
+        constexpr uint32_t kSentinel = 0xffffffffu;
+        const size_t lbytes = (size_t)rows * (size_t)ld * 4, n_slots = sample_rows_entries(capacity);
+        DeviceBuf dl(lbytes);
+        GuardedBuf scratch(sample_scratch_rows_bytes(rows)), heads((size_t)rows * sizeof(SampleHeader)), cands(n_slots * sizeof(SampleCandidate));
+        hip_check(hipMemcpy(dl.p, logits, lbytes, hipMemcpyHostToDevice), "H2D logits");
+        hip_check(hipMemset(scratch.buf.p, 0, scratch.bytes), "memset");
+        hip_check(hipMemset(heads.buf.p, 0, heads.bytes), "memset");
+        hip_check(hipMemset(cands.buf.p, 0xff, cands.bytes), "memset");
+        hip_check(launch_sample_candidates_rows(static_cast<const float*>(dl.p), ld, rows, vocab, top_k, top_p, min_p, scratch.buf.p,
+                                                heads.as<SampleHeader>(), cands.as<SampleCandidate>(), capacity, nullptr), "rows cut");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        std::vector<SampleHeader> h((size_t)rows);
+        std::vector<SampleCandidate> c(n_slots);
+        hip_check(hipMemcpy(h.data(), heads.buf.p, h.size() * sizeof(SampleHeader), hipMemcpyDeviceToHost), "D2H headers");
+        hip_check(hipMemcpy(c.data(), cands.buf.p, c.size() * sizeof(SampleCandidate), hipMemcpyDeviceToHost), "D2H candidates");
+        scratch.check("rows scratch");
+        heads.check("rows headers");
+        cands.check("rows candidates");
+        std::vector<uint8_t> owned(n_slots, 0);
+        for (int32_t r = 0; r < rows; ++r) {
+            const SampleHeader& hr = h[(size_t)r];
+            headers_out[r] = KjarniHipSampleHeader{hr.mx, hr.sum, hr.floor, hr.count, hr.overflow};
+            const size_t own = hr.floor == -INFINITY ? 0 : std::min<size_t>(hr.count, (size_t)capacity);  // (no cut: nothing is appended)
+            for (size_t i = 0; i < (size_t)capacity; ++i) {
+                const size_t at = sample_rows_slot(r, (int)i);
+                if (i < own) owned[at] = 1;
+                ids_out[(size_t)r * capacity + i] = c[at].token;
+                logits_out[(size_t)r * capacity + i] = c[at].logit;
+            }
+        }
+        // every entry no row owns -- past a row's count, past its capacity, the rows that did not run -- still holds the sentinel
+        for (size_t at = 0; at < n_slots; ++at) {
+            uint32_t bits;
+            std::memcpy(&bits, &c[at].logit, 4);
+            if (!owned[at]) expect(c[at].token == kSentinel && bits == kSentinel, "rows cut: a slot that no row owns was written");
+        }
+    });
+}
+
+// The rows penalty alone: the counts of history[n_history] (it ends with ids[0]) built by launch_token_counts, then one
+// launch_repetition_penalty_rows over logits [rows, ld].
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_repetition_penalty_rows(int32_t device, const float* logits, int64_t ld, int32_t rows, int32_t vocab,
+                                                                    const uint32_t* ids, const uint32_t* history, int32_t n_history,
+                                                                    float penalty, float* logits_out)
+{
+    if (!logits || !ids || !logits_out || (n_history > 0 && !history)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 8 || vocab < 1 || ld < vocab || n_history < 0)
+            throw InvalidConfig("invalid rows-penalty arguments (rows 1..8, vocab >= 1, ld >= vocab, n_history >= 0)");
+        use_device(device);
+        const size_t lbytes = (size_t)rows * (size_t)ld * 4;
+        GuardedBuf lg(lbytes), distinct((size_t)n_history * 4), counts((size_t)vocab * 4), nd(4);
+        DeviceBuf tok((size_t)n_history * 4), dids(8 * 4);
+        hip_check(hipMemcpy(lg.buf.p, logits, lbytes, hipMemcpyHostToDevice), "H2D logits");
+        if (n_history) hip_check(hipMemcpy(tok.p, history, (size_t)n_history * 4, hipMemcpyHostToDevice), "H2D history");
+        hip_check(hipMemcpy(dids.p, ids, (size_t)rows * 4, hipMemcpyHostToDevice), "H2D ids");
+        hip_check(hipMemset(counts.buf.p, 0, (size_t)vocab * 4), "memset counts");
+        hip_check(hipMemset(nd.buf.p, 0, 4), "memset");
+        hip_check(launch_token_counts(static_cast<const int32_t*>(tok.p), n_history, vocab, counts.as<int>(), distinct.as<int32_t>(), nd.as<int>(),
+                                      nullptr), "token counts");
+        hip_check(launch_repetition_penalty_rows(lg.as<float>(), ld, rows, vocab, static_cast<const uint32_t*>(dids.p), counts.as<int>(),
+                                                 distinct.as<int32_t>(), nd.as<int>(), penalty, nullptr), "rows penalty");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        hip_check(hipMemcpy(logits_out, lg.buf.p, lbytes, hipMemcpyDeviceToHost), "D2H logits");
+        lg.check("processed rows");
+        distinct.check("distinct tokens");
+        counts.check("token counts");
+        nd.check("distinct counter");
     });
 }
 

@@ -137,12 +137,15 @@ LlmModel::~LlmModel()
 {
     if (host_logits_) (void)hipHostFree(host_logits_);
     if (samp_host_) (void)hipHostFree(samp_host_);
+    if (ls_host_) (void)hipHostFree(ls_host_);
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (graph_) (void)hipGraphExecDestroy(graph_);
     for (hipGraphExec_t g : lane_graphs_)
         if (g) (void)hipGraphExecDestroy(g);
     for (hipGraphExec_t g : lookup_graphs_)
+        if (g) (void)hipGraphExecDestroy(g);
+    for (hipGraphExec_t g : lookup_sampled_graphs_)
         if (g) (void)hipGraphExecDestroy(g);
     if (stream_) (void)hipStreamDestroy(stream_);
     arena_.release();
@@ -952,6 +955,22 @@ hipGraphExec_t LlmModel::step_graph()
     return graph_;
 }
 
+void LlmModel::ensure_sampling()
+{
+    if (samp_scratch_) return;
+    const size_t vocab = (size_t)cfg_.vocab;
+    const size_t out_bytes = sizeof(SampleHeader) + (size_t)kCandCap * sizeof(SampleCandidate);
+    samp_scratch_ = dalloc((sample_scratch_bytes() + 3) / 4);
+    hip_check(hipMemset(samp_scratch_, 0, sample_scratch_bytes()), "memset");
+    samp_out_ = reinterpret_cast<uint8_t*>(dalloc((out_bytes + 3) / 4));
+    hip_check(hipMemset(samp_out_, 0, out_bytes), "memset");
+    hip_check(hipHostMalloc((void**)&samp_host_, out_bytes, hipHostMallocDefault), "hipHostMalloc");
+    samp_tokens_ = reinterpret_cast<int32_t*>(dalloc((size_t)cache_cap_ + 16));
+    samp_distinct_ = reinterpret_cast<int32_t*>(dalloc((size_t)cache_cap_ + 16));
+    samp_counts_ = reinterpret_cast<int*>(dalloc(vocab));
+    samp_ndistinct_ = reinterpret_cast<int*>(dalloc(4));
+}
+
 std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, size_t max_new_tokens, float repetition_penalty,
                                          int no_repeat_ngram, const std::function<bool(uint32_t)>& on_token)
 {
@@ -990,18 +1009,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         // (sampling.cpp); when the candidates cannot decide (rare: a crossing within the rounding of the device's sum, a
         // nearly flat distribution) it fetches the logits -- already processed -- and runs the full-array path.
         const size_t vocab = (size_t)cfg_.vocab;
-        const size_t out_bytes = sizeof(SampleHeader) + (size_t)kCandCap * sizeof(SampleCandidate);
-        if (!samp_scratch_) {
-            samp_scratch_ = dalloc((sample_scratch_bytes() + 3) / 4);
-            hip_check(hipMemset(samp_scratch_, 0, sample_scratch_bytes()), "memset");
-            samp_out_ = reinterpret_cast<uint8_t*>(dalloc((out_bytes + 3) / 4));
-            hip_check(hipMemset(samp_out_, 0, out_bytes), "memset");
-            hip_check(hipHostMalloc((void**)&samp_host_, out_bytes, hipHostMallocDefault), "hipHostMalloc");
-            samp_tokens_ = reinterpret_cast<int32_t*>(dalloc((size_t)cache_cap_ + 16));
-            samp_distinct_ = reinterpret_cast<int32_t*>(dalloc((size_t)cache_cap_ + 16));
-            samp_counts_ = reinterpret_cast<int*>(dalloc(vocab));
-            samp_ndistinct_ = reinterpret_cast<int*>(dalloc(4));
-        }
+        ensure_sampling();
         if (opt.sample && !host_logits_)
             hip_check(hipHostMalloc((void**)&host_logits_, vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
         SampleHeader* header_dev = reinterpret_cast<SampleHeader*>(samp_out_);
@@ -1880,6 +1888,279 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         known_steps = st.steps;
         cache_len_ = st.n - 1;
     }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Prompt-lookup decoding for sampled requests (llm.h).  The device side of a step: draft -> verify pass -> rows penalty -> rows
+// cut, captured once per row count; the copy of [8 headers | the first 512 candidates of each row] follows the replay.
+
+void LlmModel::ensure_lookup_sampled()
+{
+    ensure_lookup();
+    ensure_sampling();
+    if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+    if (ls_scratch_) return;
+    const size_t out_bytes = (size_t)kLanes * sizeof(SampleHeader) + sample_rows_entries(kRowsCandCap) * sizeof(SampleCandidate);
+    ls_scratch_ = dalloc((sample_scratch_rows_bytes(kLanes) + 3) / 4);
+    hip_check(hipMemset(ls_scratch_, 0, sample_scratch_rows_bytes(kLanes)), "memset");
+    ls_out_ = reinterpret_cast<uint8_t*>(dalloc(out_bytes / 4));
+    hip_check(hipMemset(ls_out_, 0, out_bytes), "memset");
+    ls_up_ = reinterpret_cast<int32_t*>(dalloc(16));
+    hip_check(hipHostMalloc((void**)&ls_host_, out_bytes + 16 * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
+    ls_up_host_ = reinterpret_cast<int32_t*>(ls_host_ + out_bytes);
+}
+
+void LlmModel::rows_cut(float* logits, int rows, const GenerateOptions& opt)
+{
+    const int vocab = cfg_.vocab;
+    SampleHeader* headers = reinterpret_cast<SampleHeader*>(ls_out_);
+    SampleCandidate* cands = reinterpret_cast<SampleCandidate*>(ls_out_ + kLanes * sizeof(SampleHeader));
+    if (opt.repetition_penalty != 1.0f)
+        hip_check(launch_repetition_penalty_rows(logits, vocab, rows, vocab, vids_, samp_counts_, samp_distinct_, samp_ndistinct_,
+                                                 opt.repetition_penalty, stream_), "rows penalty");
+    hip_check(launch_sample_candidates_rows(logits, vocab, rows, vocab, opt.sampling.top_k, opt.sampling.top_p, opt.sampling.min_p, ls_scratch_,
+                                            headers, cands, kRowsCandCap, stream_), "rows cut");
+}
+
+void LlmModel::enqueue_verify_sampled(int rows, const LookupConfig& c, const GenerateOptions& opt, bool draft)
+{
+    if (draft) hip_check(launch_lookup_draft(lk_hist_, lk_state_, c.ngram_max, c.ngram_min, rows - 1, rows, vids_, stream_), "lookup draft");
+    pass(vids_, rows, true, true);
+    rows_cut(vlogits_, rows, opt);
+}
+
+void LlmModel::drop_lookup_sampled_graphs()
+{
+    for (hipGraphExec_t& g : lookup_sampled_graphs_) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+}
+
+hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const LookupConfig& c, const GenerateOptions& opt)
+{
+    LookupSampledArgs want;
+    want.ngram_max = c.ngram_max; want.ngram_min = c.ngram_min;
+    want.top_k = opt.sampling.top_k; want.top_p = opt.sampling.top_p; want.min_p = opt.sampling.min_p; want.penalty = opt.repetition_penalty;
+    const auto same = [](float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; };  // (bitwise: a NaN equals itself)
+    if (want.ngram_max != ls_args_.ngram_max || want.ngram_min != ls_args_.ngram_min || want.top_k != ls_args_.top_k ||
+        !same(want.top_p, ls_args_.top_p) || !same(want.min_p, ls_args_.min_p) ||
+        !same(want.penalty, ls_args_.penalty)) {  // (arguments of the captured launches)
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        drop_lookup_sampled_graphs();
+        ls_args_ = want;
+    }
+    if (lookup_sampled_graphs_[rows]) return lookup_sampled_graphs_[rows];
+    hipGraph_t graph = nullptr;
+    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
+    try {
+        enqueue_verify_sampled(rows, c, opt, true);
+    } catch (...) {
+        (void)hipStreamEndCapture(stream_, &graph);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
+    const hipError_t e = hipGraphInstantiate(&lookup_sampled_graphs_[rows], graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    hip_check(e, "graph instantiate");
+    return lookup_sampled_graphs_[rows];
+}
+
+// One row's token from what the step's copy brought over (header + candidates of `row` in the pinned mirror); the row's
+// processed logits are fetched only when the candidates decline.
+uint32_t LlmModel::decide_row(const float* logits_dev, int row, const GenerateOptions& opt, float uniform)
+{
+    const size_t vocab = (size_t)cfg_.vocab;
+    const SampleHeader& h = reinterpret_cast<const SampleHeader*>(ls_host_)[row];
+    const size_t cand_off = kLanes * sizeof(SampleHeader);
+    const SampleCandidate* cand = reinterpret_cast<const SampleCandidate*>(ls_host_ + cand_off);
+    std::vector<uint32_t> ids, cids;
+    std::vector<float> probs, cvals;
+    bool decided = false;
+    if (device_sampling_ && !h.overflow && h.count <= (uint32_t)kRowsCandCap) {
+        const size_t n = h.count;
+        if (n > (size_t)kSampleRowsChunk) {  // the later chunks of this row were not part of the step's copy
+            for (size_t s0 = kSampleRowsChunk; s0 < n; s0 += kSampleRowsChunk) {
+                const size_t at = cand_off + sample_rows_slot(row, (int)s0) * sizeof(SampleCandidate);
+                hip_check(hipMemcpyAsync(ls_host_ + at, ls_out_ + at, std::min<size_t>(kSampleRowsChunk, n - s0) * sizeof(SampleCandidate),
+                                         hipMemcpyDeviceToHost, stream_), "D2H candidates");
+            }
+            hip_check(hipStreamSynchronize(stream_), "sync");
+        }
+        cids.resize(n);
+        cvals.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const SampleCandidate& c = cand[sample_rows_slot(row, (int)i)];
+            cids[i] = c.token;
+            cvals[i] = c.logit;
+        }
+        decided = sampling_distribution_candidates(cids.data(), cvals.data(), n, h.mx, h.floor, h.sum, vocab, opt.sampling, ids, probs);
+    }
+    if (decided) {
+        ++tokens_from_candidates_;
+    } else {
+        ++tokens_from_logits_;
+        hip_check(hipMemcpyAsync(host_logits_, logits_dev + (size_t)row * vocab, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_),
+                  "D2H logits");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        sampling_distribution(host_logits_, vocab, opt.sampling, ids, probs);  // (the penalty already ran, on the device)
+    }
+    return sample_from_distribution(ids, probs, uniform, vocab);
+}
+
+int LlmModel::verify_step_sampled(uint32_t token, const uint32_t* draft, int n_draft, int rows, const GenerateOptions& opt,
+                                  const uint32_t* history, size_t n_history, const float* uniforms, uint32_t* picks_out,
+                                  int* draws_used, float* logits_out)
+{
+    if (n_draft < 0 || n_draft > kLookupMaxDraft) throw InvalidConfig("n_draft must be 0..7");
+    if (rows < n_draft + 1 || rows > kLanes) throw InvalidConfig("rows must be n_draft + 1 .. 8");
+    if (!opt.sample) throw InvalidConfig("verify_step_sampled needs a sampling request");
+    if (opt.no_repeat_ngram > 0) throw InvalidConfig("the n-gram ban is not built for verify rows");
+    if (cache_len_ + rows > cache_cap_)
+        throw InvalidConfig("cache_len + rows (" + std::to_string(cache_len_) + " + " + std::to_string(rows) + ") exceeds the context of " +
+                            std::to_string(cache_cap_) + " tokens");
+    const bool penalty = opt.repetition_penalty != 1.0f;
+    if (penalty && (!history || n_history == 0 || history[n_history - 1] != token || n_history > (size_t)cache_cap_ + 1))
+        throw InvalidConfig("history must end with the token and hold at most context + 1 tokens");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ensure_lookup_sampled();
+    const int vocab = cfg_.vocab;
+    uint32_t ids[kLanes];
+    ids[0] = token;
+    for (int r = 1; r < rows; ++r) ids[r] = r <= n_draft ? draft[r - 1] : ids[r - 1];
+    hip_check(hipMemcpyAsync(vids_, ids, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, stream_), "H2D ids");
+    hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    if (penalty) {
+        hip_check(hipMemsetAsync(samp_counts_, 0, (size_t)vocab * sizeof(int), stream_), "memset counts");
+        hip_check(hipMemsetAsync(samp_ndistinct_, 0, sizeof(int), stream_), "memset");
+        hip_check(hipMemcpyAsync(samp_tokens_, history, n_history * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+        hip_check(launch_token_counts(samp_tokens_, (int)n_history, vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_),
+                  "token counts");
+    }
+    LookupConfig c;
+    enqueue_verify_sampled(rows, c, opt, false);
+    const size_t bytes = kLanes * sizeof(SampleHeader) + (size_t)rows * kSampleRowsChunk * sizeof(SampleCandidate);
+    hip_check(hipMemcpyAsync(ls_host_, ls_out_, bytes, hipMemcpyDeviceToHost, stream_), "D2H candidates");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    int a = 0, used = 0;
+    for (int r = 0; r <= n_draft; ++r) {
+        picks_out[r] = decide_row(vlogits_, r, opt, uniforms[used++]);
+        a = r;
+        if (r == n_draft || picks_out[r] != draft[r]) break;
+    }
+    if (draws_used) *draws_used = used;
+    cache_len_ += a + 1;
+    last_rows_ = rows;
+    const int pos = cache_len_;
+    hip_check(hipMemcpy(pos_, &pos, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
+    if (logits_out)
+        hip_check(hipMemcpy(logits_out, vlogits_, (size_t)(n_draft + 1) * vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+    return a;
+}
+
+std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32_t>& prompt, const GenerateOptions& opt, const LookupConfig& lk,
+                                                        const std::function<bool(uint32_t)>& on_token, LookupStats* stats)
+{
+    if (stats) *stats = LookupStats();
+    check_lookup_config(lk);
+    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
+    if (!opt.sample) return generate_lookup(prompt, opt, lk, on_token, stats);
+    if (!opt.uniform) throw std::runtime_error("sampling needs a uniform source");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
+    if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
+    ensure_lookup_sampled();
+    reset();
+    forward(prompt.data(), (int)prompt.size());
+    const int vocab = cfg_.vocab;
+    std::vector<uint32_t> out, all(prompt);
+    const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
+    const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
+    const size_t max_len = opt.max_len ? opt.max_len : prompt.size() + opt.max_new_tokens;
+    const size_t context_limit = std::min((size_t)cache_cap_, max_len);
+    const size_t max_new_tokens = opt.max_new_tokens;
+    const bool penalty = opt.repetition_penalty != 1.0f;
+    bool done = false;
+    // generate()'s loop, one token: the checks ahead of the draw, the draw, the checks behind it.  False: the token did not join
+    // the output (no draw was taken, or it was a stop token).
+    auto decide = [&](const float* logits_dev, int row, uint32_t* pick) {
+        if (out.size() >= max_new_tokens || all.size() >= context_limit) {
+            done = true;
+            return false;
+        }
+        const uint32_t next = decide_row(logits_dev, row, opt, opt.uniform());
+        *pick = next;
+        if (is_stop(next)) {
+            done = true;
+            return false;
+        }
+        all.push_back(next);
+        out.push_back(next);
+        if ((on_token && !on_token(next)) || all.size() >= context_limit || out.size() >= max_new_tokens) done = true;
+        return true;
+    };
+    const size_t head_bytes = kLanes * sizeof(SampleHeader);
+    if (max_new_tokens == 0 || all.size() >= context_limit) return out;
+    // the device state: the history = the prompt (the picks join it step by step), the counts of the prompt, pos = history - 1
+    LlmLookupState st = {};
+    st.n = (int32_t)all.size();
+    const int pos0 = cache_len_ - 1;
+    hip_check(hipMemcpyAsync(lk_hist_, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+    hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
+    hip_check(hipMemcpyAsync(pos_, &pos0, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    if (penalty) {
+        hip_check(hipMemsetAsync(samp_counts_, 0, (size_t)vocab * sizeof(int), stream_), "memset counts");
+        hip_check(hipMemsetAsync(samp_ndistinct_, 0, sizeof(int), stream_), "memset");
+        hip_check(launch_token_counts(lk_hist_, (int)all.size(), vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
+    }
+    // the first token: the prompt's logits as a block of one row
+    rows_cut(logits_, 1, opt);
+    hip_check(hipMemcpyAsync(ls_host_, ls_out_, head_bytes + (size_t)kSampleRowsChunk * sizeof(SampleCandidate), hipMemcpyDeviceToHost, stream_),
+              "D2H candidates");
+    hip_check(hipStreamSynchronize(stream_), "sync");  // (`all` grows below: the copies must have read it)
+    uint32_t picks[kLanes];
+    int n_picks = decide(logits_, 0, &picks[0]) ? 1 : 0;
+    while (!done) {
+        // as generate_lookup: a step of `rows` rows writes cache rows [pos, pos + rows); near the end of the cache the steps narrow
+        const int room = cache_cap_ - cache_len_;
+        if (room <= 0) break;
+        const int rows = std::min(lk.draft_tokens + 1, room);
+        hipGraphExec_t exec = lookup_sampled_graph(rows, lk, opt);
+        ls_up_host_[0] = n_picks;
+        for (int i = 0; i < n_picks; ++i) ls_up_host_[1 + i] = (int32_t)picks[i];
+        hip_check(hipMemcpyAsync(ls_up_, ls_up_host_, 9 * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D picks");
+        hip_check(launch_lookup_commit(ls_up_, lk_state_, lk_hist_, lk_hist_cap_, pos_, stream_), "lookup commit");
+        if (penalty)
+            hip_check(launch_token_counts(ls_up_ + 1, n_picks, vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
+        hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        hip_check(hipMemcpyAsync(ls_host_, ls_out_, head_bytes + (size_t)rows * kSampleRowsChunk * sizeof(SampleCandidate),
+                                 hipMemcpyDeviceToHost, stream_), "D2H candidates");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        // the draft the device made, from the same rule on the host's copy of the history
+        LookupConfig hc = lk;
+        hc.draft_tokens = rows - 1;
+        const std::vector<uint32_t> draft = rows > 1 ? lookup_draft_host(all.data(), all.size(), hc) : std::vector<uint32_t>();
+        const int m = (int)draft.size();
+        int a = 0;
+        n_picks = 0;
+        for (int r = 0; r <= m && !done; ++r) {
+            if (!decide(vlogits_, r, &picks[r])) break;
+            ++n_picks;
+            if (r == m || picks[r] != draft[(size_t)r]) break;
+            ++a;
+        }
+        if (stats) {
+            if (rows == 1) ++stats->single_row_steps;
+            else ++stats->verify_steps;
+            stats->drafted_tokens += (uint64_t)m;
+            stats->accepted_tokens += (uint64_t)a;
+        }
+        cache_len_ = (int)all.size() - 1;
+    }
+    cache_len_ = (int)all.size() - 1;
+    hip_check(hipMemcpy(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
     return out;
 }
 

@@ -174,6 +174,26 @@ public:
     // rows (n_draft + 1 .. 8; the rows past the draft repeat its last id).  Returns the accepted length a; tokens_out[0..a] are
     // the picks, the cache grows by a + 1; logits_out (may be null) receives rows [0, n_draft] of the logits.
     int verify_step(uint32_t token, const uint32_t* draft, int n_draft, int rows, uint32_t* tokens_out, float* logits_out);
+    // ---- prompt-lookup decoding for sampled requests ---------------------------------------------------------------------------
+    // generate() for a request that samples (with or without a repetition penalty), several tokens per step.  Lookup drafts are
+    // deterministic, so no rejection scheme is needed: generate() decides token i as a function of (processed logits, the i-th
+    // draw); a verify step decides row 0 with the next draw, and while the result equals the draft the next row with the draw
+    // after it; the first differing token is kept (lookup_accept_sampled, sampling.h).  Draws are taken one per decided row and
+    // never for a row that is not reached, so the ids are generate()'s for the same draw stream and the stream is left where
+    // generate() leaves it.  Per step one chain -- draft, verify pass, the rows penalty, the rows cut (captured once per row count
+    // and filter arguments) -- then one copy and one synchronise; the host decides from each row's candidates and fetches a row's
+    // processed logits only when they decline.  The a + 1 picks reach the device history, the token counts and the position in
+    // one small upload ahead of the next step.  Greedy without processors forwards to generate_lookup; greedy with a penalty,
+    // or any n-gram ban, to generate() (stats zero).
+    std::vector<uint32_t> generate_lookup_sampled(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
+                                                  const LookupConfig& lookup, const std::function<bool(uint32_t)>& on_token,
+                                                  LookupStats* stats);
+    // Test hook: verify_step for a sampled request.  history[n_history]: the tokens the penalty counts, the last of them `token`
+    // (not read when the penalty is 1); uniforms: one draw per decided row.  Returns a; picks_out[0..a]; *draws_used = a + 1;
+    // logits_out (may be null) receives rows [0, n_draft] of the processed logits; the cache grows by a + 1.
+    int verify_step_sampled(uint32_t token, const uint32_t* draft, int n_draft, int rows, const GenerateOptions& options,
+                            const uint32_t* history, size_t n_history, const float* uniforms, uint32_t* picks_out, int* draws_used,
+                            float* logits_out);
     // Projections of verify steps that took the multi-row weight-streaming kernel / fell back (counted when enqueued).
     uint64_t verify_stream_calls() const { return verify_stream_calls_; }
     uint64_t verify_fallback_calls() const { return verify_fallback_calls_; }
@@ -199,6 +219,14 @@ private:
     void ensure_lookup();
     void enqueue_verify(int rows, int ngram_max, int ngram_min, bool draft, bool record);  // [draft ->] step -> pick
     hipGraphExec_t lookup_graph(int rows, const LookupConfig& config);
+    void ensure_sampling();        // the device state of sampled decoding and the logits processors
+    void ensure_lookup_sampled();
+    // [draft ->] verify pass -> rows penalty -> rows cut over `src` rows of stride vocab (the verify logits, or logits_ for one row)
+    void enqueue_verify_sampled(int rows, const LookupConfig& config, const GenerateOptions& options, bool draft);
+    hipGraphExec_t lookup_sampled_graph(int rows, const LookupConfig& config, const GenerateOptions& options);
+    void drop_lookup_sampled_graphs();
+    void rows_cut(float* logits, int rows, const GenerateOptions& options);  // rows penalty + rows cut + the copy (no sync)
+    uint32_t decide_row(const float* logits_dev, int row, const GenerateOptions& options, float uniform);
     void load_gpt2(SafeTensors& st, int weights);                      // GPT-2 tensors (Conv1D matrices transposed on the host)
     void finish_load();                                                // attention splits, workspace, stream
     // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
@@ -291,6 +319,19 @@ private:
     hipGraphExec_t lookup_graphs_[kLanes + 1] = {};
     int lookup_ngram_[2] = {0, 0};
     uint64_t verify_stream_calls_ = 0, verify_fallback_calls_ = 0;
+    // sampled prompt-lookup (allocated on first use): per-row scratch, [8 headers | the rows' candidate slots in chunks of 512]
+    // and its pinned mirror (a step copies the headers and the first chunk of its rows in one piece), the upload of a step's
+    // picks, one captured chain per row count for the arguments in ls_args_
+    static constexpr int kRowsCandCap = kCandCap;
+    void* ls_scratch_ = nullptr;
+    uint8_t *ls_out_ = nullptr, *ls_host_ = nullptr;
+    int32_t *ls_up_ = nullptr, *ls_up_host_ = nullptr;
+    hipGraphExec_t lookup_sampled_graphs_[kLanes + 1] = {};
+    struct LookupSampledArgs {
+        int ngram_max = 0, ngram_min = 0;
+        int64_t top_k = 0;
+        float top_p = 0.0f, min_p = 0.0f, penalty = 0.0f;
+    } ls_args_;
     // scoring (allocated on first use): the targets (ids shifted by one) and the three result rows [context], the slab
     // partials of the fused head; first_ / n_ of the call in flight
     uint32_t *score_tgt_ = nullptr, *score_top_ = nullptr;

@@ -175,4 +175,34 @@ hipError_t launch_token_counts(const int32_t* tokens, int n, int vocab, int* cou
 hipError_t launch_logits_processors(float* logits, int vocab, const int32_t* tokens, int len, const int* counts, const int32_t* distinct,
                                     const int* n_distinct, float repetition_penalty, int no_repeat_ngram, hipStream_t stream);
 
+// ---- sampled prompt-lookup decoding (LlmModel::generate_lookup_sampled) ---------------------------------------------------------
+// launch_sample_candidates over `rows` (1..8) logits rows of stride ld >= vocab in three launches (the row is blockIdx.y).  Row r
+// uses scratch + r * sample_scratch_bytes() (sample_scratch_rows_bytes(rows) in all, zero-initialised), headers[r] and its own
+// `capacity` candidate slots: per row the one-row launcher's contract, mx and sum bit-identical to it; an overflowing row
+// reports its own count and touches no slot past its capacity and nothing of its neighbours.
+// The slots are laid out in chunks of kSampleRowsChunk so that the first 512 candidates of all rows are contiguous: slot s of
+// row r is entry sample_rows_slot(r, s) of `candidates` (sample_rows_entries(capacity) entries whatever `rows` is).  With the
+// headers placed right in front, [8 headers | rows x 512 candidates] is ONE contiguous device-to-host copy; a row with more
+// candidates has them in the later chunks.
+constexpr int kSampleRowsChunk = 512, kSampleRowsMax = 8;
+__host__ __device__ inline size_t sample_rows_slot(int row, int slot)
+{
+    return ((size_t)(slot / kSampleRowsChunk) * kSampleRowsMax + (size_t)row) * kSampleRowsChunk + (size_t)(slot % kSampleRowsChunk);
+}
+inline size_t sample_rows_entries(int capacity)
+{
+    return (size_t)((capacity + kSampleRowsChunk - 1) / kSampleRowsChunk) * kSampleRowsMax * kSampleRowsChunk;
+}
+size_t sample_scratch_rows_bytes(int rows);
+hipError_t launch_sample_candidates_rows(const float* logits, int64_t ld, int rows, int vocab, int64_t top_k, float top_p, float min_p,
+                                         void* scratch, SampleHeader* headers, SampleCandidate* candidates, int capacity, hipStream_t stream);
+// The repetition penalty over the rows of a verify block: row r (it predicts the token after ids[0..r]) is penalised for the
+// history that counts / distinct / n_distinct describe (up to and including ids[0]: launch_token_counts's state) plus
+// ids[1..r], once per occurrence, bit-exact against apply_repetition_penalty on the concatenation.
+hipError_t launch_repetition_penalty_rows(float* logits, int64_t ld, int rows, int vocab, const uint32_t* ids, const int* counts,
+                                          const int32_t* distinct, const int* n_distinct, float penalty, hipStream_t stream);
+// The host's decision of a sampled verify step: upload[0] = k (0..8) picks, upload[1..k] join history[state->n ..]; state->n and
+// *pos advance by k.
+hipError_t launch_lookup_commit(const int32_t* upload, LlmLookupState* state, int32_t* history, int hist_cap, int* pos, hipStream_t stream);
+
 }  // namespace kjarni

@@ -1964,6 +1964,35 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(const float* __restric
     }
 }
 
+// The cut of one row from its scratch: m = the maximum, sum = the per-workgroup sums in their fixed order, tau = how far below
+// the maximum the candidates reach -- enough tokens for top-k, enough mass for top-p (the histogram's masses are summed in no
+// fixed order: a relative margin on top of the two bins), everything min-p can keep when it filters the whole vocabulary.
+// Returns whether no usable cut exists.  Shared by the one-row and the rows kernels (inlined into each).
+__device__ __forceinline__ bool sample_cut(const SampleScratch* __restrict__ sc, int vocab, long long top_k, float top_p, float min_p,
+                                           float& m, float& sum, float& tau)
+{
+    m = -INFINITY;
+    sum = 0.0f;
+    for (int b = 0; b < SAMPLE_BLOCKS; ++b) m = fmaxf(m, sc->part_max[b]);
+    for (int b = 0; b < SAMPLE_BLOCKS; ++b) sum += sc->part_sum[b];
+    const bool k_on = top_k >= 0 && top_k < (long long)vocab;  // (top_k >= vocab filters nothing)
+    const double need_count = k_on ? (double)top_k : 1.0;
+    const double need_mass = top_p >= 0.0f ? (double)top_p * (double)sum * 1.001 : 0.0;
+    double cnt = 0.0, mass = 0.0;
+    tau = INFINITY;
+    for (int b = 0; b < SAMPLE_BINS; ++b) {
+        cnt += (double)sc->hist_count[b];
+        mass += (double)sc->hist_mass[b];
+        if (cnt >= need_count && mass > need_mass) {
+            tau = (float)(b + 2) / 8.0f;
+            break;
+        }
+    }
+    const bool minp_on_all = min_p >= 0.0f && !k_on && !(top_p >= 0.0f && top_p < 1.0f);
+    if (minp_on_all) tau = min_p > 0.0f ? fmaxf(tau, -logf(min_p) + 0.25f) : INFINITY;
+    return !(tau < 1e30f) || !(m > -INFINITY) || !(m < INFINITY);
+}
+
 __global__ __launch_bounds__(256) void sample_compact_kernel(const float* __restrict__ logits, int vocab, long long top_k, float top_p,
                                                              float min_p, const SampleScratch* __restrict__ sc,
                                                              SampleHeader* __restrict__ header, SampleCandidate* __restrict__ cand, int cap)
@@ -1971,27 +2000,8 @@ __global__ __launch_bounds__(256) void sample_compact_kernel(const float* __rest
     __shared__ float s_floor;
     __shared__ int s_all;
     if (threadIdx.x == 0) {
-        float m = -INFINITY, sum = 0.0f;
-        for (int b = 0; b < SAMPLE_BLOCKS; ++b) m = fmaxf(m, sc->part_max[b]);
-        for (int b = 0; b < SAMPLE_BLOCKS; ++b) sum += sc->part_sum[b];
-        // the cut: enough tokens for top-k, enough mass for top-p (the histogram's masses are summed in no fixed order:
-        // a relative margin on top of the two bins), everything min-p can keep when it filters the whole vocabulary
-        const bool k_on = top_k >= 0 && top_k < (long long)vocab;  // (top_k >= vocab filters nothing)
-        const double need_count = k_on ? (double)top_k : 1.0;
-        const double need_mass = top_p >= 0.0f ? (double)top_p * (double)sum * 1.001 : 0.0;
-        double cnt = 0.0, mass = 0.0;
-        float tau = INFINITY;
-        for (int b = 0; b < SAMPLE_BINS; ++b) {
-            cnt += (double)sc->hist_count[b];
-            mass += (double)sc->hist_mass[b];
-            if (cnt >= need_count && mass > need_mass) {
-                tau = (float)(b + 2) / 8.0f;
-                break;
-            }
-        }
-        const bool minp_on_all = min_p >= 0.0f && !k_on && !(top_p >= 0.0f && top_p < 1.0f);
-        if (minp_on_all) tau = min_p > 0.0f ? fmaxf(tau, -logf(min_p) + 0.25f) : INFINITY;
-        s_all = !(tau < 1e30f) || !(m > -INFINITY) || !(m < INFINITY);
+        float m, sum, tau;
+        s_all = sample_cut(sc, vocab, top_k, top_p, min_p, m, sum, tau);
         s_floor = m - tau;
         if (blockIdx.x == 0) {
             header->mx = m;
@@ -2938,6 +2948,202 @@ hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int voca
     if (rows > LLM_MAX_ROWS || vocab <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(llm_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, targets, logprob, top, top_logprob,
                        lse);
+    return hipGetLastError();
+}
+
+// ---- sampled prompt-lookup decoding (LlmModel::generate_lookup_sampled): the sampler's cut and the repetition penalty over the
+// rows of a verify block.  The three cut kernels are sample_max / sample_hist / sample_compact with the row in blockIdx.y: the
+// same 64 workgroups per row walk the row in the same order, so a row's mx and sum are bit-identical to the one-row launcher's;
+// every row has its own SampleScratch, SampleHeader and `cap` candidate slots (sample_rows_slot: the rows' first 512 slots lie
+// side by side, so that one contiguous copy brings the headers' neighbours over).  (Kernels of their own rather than the
+// one-row kernels templated: the one-row path keeps its code and registers.)
+namespace {
+
+__global__ __launch_bounds__(256) void sample_max_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                              SampleScratch* __restrict__ scratch, SampleHeader* __restrict__ headers)
+{
+    __shared__ float red[4];
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    SampleScratch* sc = scratch + blockIdx.y;
+    float m = -INFINITY;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) m = fmaxf(m, row[i]);
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) sc->part_max[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    for (int b = blockIdx.x * 256 + threadIdx.x; b <= SAMPLE_BINS; b += gridDim.x * 256) {
+        sc->hist_count[b] = 0u;
+        sc->hist_mass[b] = 0.0f;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        headers[blockIdx.y].count = 0u;
+        headers[blockIdx.y].overflow = 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void sample_hist_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                               SampleScratch* __restrict__ scratch)
+{
+    __shared__ unsigned h_count[SAMPLE_BINS + 1];
+    __shared__ float h_mass[SAMPLE_BINS + 1];
+    __shared__ float red[4];
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    SampleScratch* sc = scratch + blockIdx.y;
+    for (int b = threadIdx.x; b <= SAMPLE_BINS; b += 256) {
+        h_count[b] = 0u;
+        h_mass[b] = 0.0f;
+    }
+    float m = -INFINITY;
+    for (int b = 0; b < SAMPLE_BLOCKS; ++b) m = fmaxf(m, sc->part_max[b]);
+    __syncthreads();
+    float sum = 0.0f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
+        const float v = row[i];
+        const float e = expf(v - m);
+        const float d = (m - v) * 8.0f;
+        const int bin = d < (float)SAMPLE_BINS ? (int)d : SAMPLE_BINS;  // (NaN and -inf land in the last bin)
+        sum += e;
+        atomicAdd(&h_count[bin], 1u);
+        atomicAdd(&h_mass[bin], e);
+    }
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) sc->part_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int b = threadIdx.x; b <= SAMPLE_BINS; b += 256) {
+        if (h_count[b]) {
+            atomicAdd(&sc->hist_count[b], h_count[b]);
+            atomicAdd(&sc->hist_mass[b], h_mass[b]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void sample_compact_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab, long long top_k,
+                                                                  float top_p, float min_p, const SampleScratch* __restrict__ scratch,
+                                                                  SampleHeader* __restrict__ headers, SampleCandidate* __restrict__ candidates,
+                                                                  int cap)
+{
+    __shared__ float s_floor;
+    __shared__ int s_all;
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    const SampleScratch* sc = scratch + blockIdx.y;
+    SampleHeader* header = headers + blockIdx.y;
+    if (threadIdx.x == 0) {  // the cut, from this row's histogram
+        float m, sum, tau;
+        s_all = sample_cut(sc, vocab, top_k, top_p, min_p, m, sum, tau);
+        s_floor = m - tau;
+        if (blockIdx.x == 0) {
+            header->mx = m;
+            header->sum = sum;
+            header->floor = s_all ? -INFINITY : m - tau;
+        }
+    }
+    __syncthreads();
+    if (s_all) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            header->count = (uint32_t)vocab;
+            header->overflow = 1u;
+        }
+        return;
+    }
+    const float floor = s_floor;
+    const int lane = threadIdx.x & 63;
+    for (int i0 = blockIdx.x * 256; i0 < vocab; i0 += gridDim.x * 256) {
+        const int i = i0 + threadIdx.x;
+        const float v = i < vocab ? row[i] : -INFINITY;
+        const bool keep = i < vocab && v >= floor;
+        const unsigned long long bits = __ballot(keep);
+        if (bits == 0ull) continue;
+        unsigned base = 0u;
+        if (lane == 0) base = atomicAdd(&header->count, (unsigned)__popcll(bits));
+        base = __shfl(base, 0, kWave);
+        if (keep) {
+            const unsigned slot = base + (unsigned)__popcll(bits & ((1ull << lane) - 1ull));
+            if (slot < (unsigned)cap) candidates[sample_rows_slot((int)blockIdx.y, (int)slot)] = SampleCandidate{(uint32_t)i, v};
+            else header->overflow = 1u;
+        }
+    }
+}
+
+// Row r of a verify block predicts the token after ids[0..r]: its history is the counted one (up to and including ids[0]) plus
+// ids[1..r].  One thread per distinct token of the counted history, then one per draft position of the row: a draft token the
+// counted history does not hold is handled by the thread of its first occurrence in ids[1..r].  Each thread applies the
+// penalty once per occurrence, each application rounded, as repetition_penalty_kernel does.
+__global__ __launch_bounds__(256) void repetition_penalty_rows_kernel(float* __restrict__ logits, int64_t ld, int vocab,
+                                                                      const uint32_t* __restrict__ ids, const int* __restrict__ counts,
+                                                                      const int32_t* __restrict__ distinct,
+                                                                      const int* __restrict__ n_distinct, float penalty)
+{
+    const int r = blockIdx.y;
+    float* row = logits + (int64_t)r * ld;
+    const int nd = *n_distinct;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < nd + r; j += gridDim.x * 256) {
+        int t, c;
+        if (j < nd) {
+            t = distinct[j];
+            if (t < 0 || t >= vocab) continue;
+            c = counts[t];
+        } else {
+            const int i = j - nd + 1;
+            if (ids[i] >= (uint32_t)vocab) continue;
+            t = (int)ids[i];
+            if (counts[t] != 0) continue;  // (in `distinct`: the thread above has it)
+            bool first = true;
+            for (int q = 1; q < i; ++q) first = first && ids[q] != ids[i];
+            if (!first) continue;
+            c = 0;
+        }
+        for (int q = 1; q <= r; ++q) c += ids[q] == (uint32_t)t ? 1 : 0;
+        float s = row[t];
+        for (; c > 0; --c) s = s < 0.0f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+        row[t] = s;
+    }
+}
+
+// The host's decision of a sampled verify step joins the device state: up[0] = how many picks, up[1..] = the picks.
+__global__ void lookup_commit_kernel(const int32_t* __restrict__ up, LlmLookupState* __restrict__ st, int32_t* __restrict__ history,
+                                     int hist_cap, int* __restrict__ pos)
+{
+    if (threadIdx.x != 0) return;
+    int k = up[0];
+    k = k < 0 ? 0 : (k > LLM_MAX_ROWS ? LLM_MAX_ROWS : k);
+    const int n = st->n;
+    for (int i = 0; i < k; ++i)
+        if (n + i < hist_cap) history[n + i] = up[1 + i];
+    st->n = n + k;
+    *pos += k;
+}
+
+}  // namespace
+
+size_t sample_scratch_rows_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * sizeof(SampleScratch); }
+
+hipError_t launch_sample_candidates_rows(const float* logits, int64_t ld, int rows, int vocab, int64_t top_k, float top_p, float min_p,
+                                         void* scratch, SampleHeader* headers, SampleCandidate* candidates, int capacity, hipStream_t stream)
+{
+    if (rows < 1 || rows > LLM_MAX_ROWS || vocab < 1 || ld < (int64_t)vocab || capacity < 1) return hipErrorInvalidValue;
+    SampleScratch* sc = static_cast<SampleScratch*>(scratch);
+    const dim3 grid(SAMPLE_BLOCKS, (unsigned)rows);
+    hipLaunchKernelGGL(sample_max_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc, headers);
+    hipLaunchKernelGGL(sample_hist_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc);
+    hipLaunchKernelGGL(sample_compact_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, (long long)top_k, top_p, min_p, sc, headers,
+                       candidates, capacity);
+    return hipGetLastError();
+}
+
+hipError_t launch_repetition_penalty_rows(float* logits, int64_t ld, int rows, int vocab, const uint32_t* ids, const int* counts,
+                                          const int32_t* distinct, const int* n_distinct, float penalty, hipStream_t stream)
+{
+    if (rows < 1 || rows > LLM_MAX_ROWS || vocab < 1 || ld < (int64_t)vocab) return hipErrorInvalidValue;
+    if (penalty == 1.0f) return hipSuccess;
+    hipLaunchKernelGGL(repetition_penalty_rows_kernel, dim3(16, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, ids, counts, distinct,
+                       n_distinct, penalty);
+    return hipGetLastError();
+}
+
+hipError_t launch_lookup_commit(const int32_t* upload, LlmLookupState* state, int32_t* history, int hist_cap, int* pos, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lookup_commit_kernel, dim3(1), dim3(64), 0, stream, upload, state, history, hist_cap, pos);
     return hipGetLastError();
 }
 

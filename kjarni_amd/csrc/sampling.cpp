@@ -477,6 +477,22 @@ uint32_t sample_from_distribution(const std::vector<uint32_t>& ids, const std::v
     return (uint32_t)(vocab - 1);
 }
 
+int lookup_accept_sampled(const float* logits, int64_t ld, int rows, size_t vocab, const uint32_t* draft, int n_draft, const SamplingParams& p,
+                          const std::function<float()>& uniform, uint32_t* picks)
+{
+    std::vector<uint32_t> ids;
+    std::vector<float> probs;
+    const int last = std::min(n_draft, rows - 1);
+    int a = 0;
+    for (int r = 0; r <= last; ++r) {
+        sampling_distribution(logits + (int64_t)r * ld, vocab, p, ids, probs);
+        picks[r] = sample_from_distribution(ids, probs, uniform(), vocab);
+        a = r;
+        if (r == last || picks[r] != draft[r]) break;
+    }
+    return a;
+}
+
 UniformRng::UniformRng()
 {
     std::random_device rd;

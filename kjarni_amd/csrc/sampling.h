@@ -9,6 +9,7 @@
 // costs one exp pass instead of two full sorts.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 namespace kjarni {
@@ -50,6 +51,14 @@ bool sampling_distribution_candidates(const uint32_t* cand_ids, const float* can
                                       size_t vocab, const SamplingParams& p, std::vector<uint32_t>& ids, std::vector<float>& probs);
 // sample_from_probs over the full vocabulary: first index whose running sum reaches `uniform`, else vocab - 1.
 uint32_t sample_from_distribution(const std::vector<uint32_t>& ids, const std::vector<float>& probs, float uniform, size_t vocab);
+
+// Deciding a verify block of prompt-lookup decoding for a sampled request: row r of logits [rows, ld] (already processed) is the
+// distribution after the history + draft[0..r).  Row by row, sampling_distribution + sample_from_distribution with one
+// uniform() per decided row; picks[r] is the result.  Stops after the first pick that differs from the draft (that pick is
+// kept), or after row min(n_draft, rows - 1).  Returns a = the drafted tokens accepted: picks[0..a] are valid, a + 1 draws were
+// taken, draft[a..) was not read.  The specification of LlmModel::generate_lookup_sampled's decision.
+int lookup_accept_sampled(const float* logits, int64_t ld, int rows, size_t vocab, const uint32_t* draft, int n_draft, const SamplingParams& p,
+                          const std::function<float()>& uniform, uint32_t* picks);
 
 // rand::Rng::gen::<f32>() analogue: 24 random bits in [0, 1).  xoshiro256**, seeded from the OS or explicitly.
 class UniformRng {

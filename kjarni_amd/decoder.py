@@ -215,6 +215,84 @@ class HipDecoder:
                                                          logits.ctypes.data_as(C.POINTER(C.c_float))))
         return picks[:a.value + 1].tolist(), int(a.value), logits
 
+    # ---- prompt-lookup decoding for sampled requests ----
+    @staticmethod
+    def _sampling_options(max_new_tokens, sample, temperature, top_k, top_p, min_p, repetition_penalty, no_repeat_ngram, stop_ids,
+                          uniforms, seed):
+        """(KjarniHipSamplingOptions, the arrays it points into)."""
+        stops = np.ascontiguousarray(stop_ids if stop_ids is not None else [], np.uint32)
+        u = None if uniforms is None else np.ascontiguousarray(uniforms, np.float32)
+        o = _ffi.KjarniHipSamplingOptions()
+        o.max_new_tokens, o.repetition_penalty, o.no_repeat_ngram, o.sample = max_new_tokens, repetition_penalty, no_repeat_ngram, int(sample)
+        o.temperature = temperature
+        o.top_k = -1 if top_k is None else top_k
+        o.top_p = -1.0 if top_p is None else top_p
+        o.min_p = -1.0 if min_p is None else min_p
+        o.stop_ids = stops.ctypes.data_as(C.POINTER(C.c_uint32)) if stops.size else None
+        o.n_stop = stops.size
+        o.uniforms = u.ctypes.data_as(C.POINTER(C.c_float)) if u is not None else None
+        o.n_uniforms = 0 if u is None else u.size
+        o.seed = seed
+        return o, (stops, u)
+
+    def generate_sampled(self, prompt: Sequence[int], max_new_tokens: int, lookup: Optional[Sequence[int]] = None, sample: bool = True,
+                         temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                         min_p: Optional[float] = None, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0,
+                         stop_ids: Optional[Sequence[int]] = None, uniforms=None, seed: int = 0,
+                         on_token: Optional[Callable[[int], Optional[bool]]] = None):
+        """generate() with a sampling strategy: (ids, stats).  lookup None: the plain loop; (draft_tokens, ngram_max, ngram_min):
+        the sampled lookup loop, which returns the plain loop's ids for the same draws.  uniforms: token i uses uniforms[i]
+        (at least max_new_tokens of them); None: a generator seeded with `seed`."""
+        p = np.ascontiguousarray(prompt, np.uint32)
+        out = np.empty(max(max_new_tokens, 1), np.uint32)
+        n = C.c_size_t(0)
+        o, keep = self._sampling_options(max_new_tokens, sample, temperature, top_k, top_p, min_p, repetition_penalty, no_repeat_ngram,
+                                         stop_ids, uniforms, seed)
+        cfg = None if lookup is None else _ffi.KjarniHipLookupConfig(*[int(x) for x in lookup])
+        st = _ffi.KjarniHipLookupStats()
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_sampled(self._h, u32(p) if p.size else None, p.size, C.byref(o),
+                                                              C.byref(cfg) if cfg is not None else None, fn, None, u32(out), out.size,
+                                                              C.byref(n), C.byref(st)))
+        del keep
+        stats = {k: int(getattr(st, k)) for k, _ in _ffi.KjarniHipLookupStats._fields_}
+        return out[:min(n.value, out.size)].tolist(), stats
+
+    def verify_step_sampled(self, token: int, draft: Sequence[int], uniforms, rows: Optional[int] = None, temperature: float = 1.0,
+                            top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                            repetition_penalty: float = 1.0, history: Optional[Sequence[int]] = None, fetch: bool = True):
+        """Test hook: verify_step() for a sampled request, one draw per decided row.  history: the tokens the penalty counts, ending
+        with `token` (needed when repetition_penalty != 1).  Returns (picks, accepted, draws_used, processed logits
+        [len(draft) + 1, vocab], or None with fetch=False); the cache grows by accepted + 1."""
+        d = np.ascontiguousarray(draft, np.uint32)
+        u = np.ascontiguousarray(uniforms, np.float32)
+        h = np.ascontiguousarray(history if history is not None else [], np.uint32)
+        if u.size < d.size + 1:
+            raise ValueError("one draw per row that may be decided")
+        rows = d.size + 1 if rows is None else int(rows)
+        o, keep = self._sampling_options(0, True, temperature, top_k, top_p, min_p, repetition_penalty, 0, None, None, 0)
+        picks = np.zeros(8, np.uint32)
+        a, used = C.c_int32(0), C.c_int32(0)
+        logits = np.empty((d.size + 1, self.vocab), np.float32) if fetch else None
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_verify_step_sampled(self._h, int(token), u32(d) if d.size else None, d.size, rows, C.byref(o),
+                                                                 u32(h) if h.size else None, h.size,
+                                                                 u.ctypes.data_as(C.POINTER(C.c_float)), u32(picks), C.byref(a),
+                                                                 C.byref(used), logits.ctypes.data_as(C.POINTER(C.c_float)) if fetch else None))
+        del keep
+        return picks[:a.value + 1].tolist(), int(a.value), int(used.value), logits
+
+    def sampling_routes(self):
+        """(tokens decided from the device's candidates, tokens that needed a logits row) since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_sampling_routes(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def verify_gemv_calls(self):
         """(streamed, fallback): projections of verify steps that took the multi-row weight-streaming kernel / the
         one-wave-per-column kernel since load."""

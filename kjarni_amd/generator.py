@@ -77,6 +77,11 @@ class Generator:
         greedy configs without a repetition penalty or an n-gram ban; the text is the plain path's."""
         check_error(lib().kjarni_hip_generator_set_prompt_lookup(self._handle, draft_tokens))
 
+    def set_prompt_lookup_sampling(self, on: bool):
+        """Prompt-lookup decoding for sampled configs too, with or without a repetition penalty (off by default): taken when
+        set_prompt_lookup() is 1..7 and the config has no n-gram ban; the text is the plain path's for the same seed."""
+        check_error(lib().kjarni_hip_generator_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
+
     def verify_gemv_calls(self):
         """(streamed, fallback) projections of prompt-lookup verify steps since load: moves only when a call took the lookup loop."""
         a, b = C.c_uint64(), C.c_uint64()

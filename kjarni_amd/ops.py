@@ -271,6 +271,65 @@ def sample_candidates(rows, top_k: Optional[int] = None, top_p: Optional[float] 
     return out
 
 
+def sample_candidates_rows(block, vocab: Optional[int] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                           min_p: Optional[float] = None, capacity: int = 4096, device: int = 0):
+    """The sampler's cut over the rows of `block` ([rows, ld] logits, rows 1..8, the first `vocab` columns of every row) in one
+    chain of three launches.  Per row a dict as sample_candidates() gives, plus "slots": every one of the row's `capacity`
+    (id, logit-bits) slots as uint32 [capacity, 2] (0xffffffff where nothing was written)."""
+    lg = np.ascontiguousarray(block, np.float32)
+    rows, ld = lg.shape
+    vocab = ld if vocab is None else int(vocab)
+    hdr = (_ffi.KjarniHipSampleHeader * rows)()
+    ids = np.zeros((rows, capacity), np.uint32)
+    vals = np.zeros((rows, capacity), np.float32)
+    check_error(lib().kjarni_hip_op_sample_candidates_rows(device, _f(lg), ld, rows, vocab, -1 if top_k is None else top_k,
+                                                           -1.0 if top_p is None else top_p, -1.0 if min_p is None else min_p, capacity, hdr,
+                                                           ids.ctypes.data_as(_ffi._u32p), _f(vals)))
+    out = []
+    for c, h in enumerate(hdr):
+        n = 0 if h.floor == -np.inf else min(int(h.count), capacity)
+        out.append({"mx": np.float32(h.mx), "sum": np.float32(h.sum), "floor": np.float32(h.floor), "count": int(h.count),
+                    "overflow": int(h.overflow), "ids": ids[c, :n].copy(), "logits": vals[c, :n].copy(),
+                    "slots": np.stack([ids[c], vals[c].view(np.uint32)], axis=1)})
+    return out
+
+
+def repetition_penalty_rows(block, ids, history, penalty: float, vocab: Optional[int] = None, device: int = 0):
+    """The repetition penalty over the rows of a verify block on the device: block [rows, ld]; `history` ends with ids[0]; row
+    r is penalised for history + ids[1:r + 1].  Returns the processed block."""
+    lg = np.ascontiguousarray(block, np.float32)
+    rows, ld = lg.shape
+    vocab = ld if vocab is None else int(vocab)
+    i = np.ascontiguousarray(ids, np.uint32)
+    h = np.ascontiguousarray(history, np.uint32)
+    if i.size < rows:
+        raise ValueError("ids needs one entry per row")
+    out = np.empty_like(lg)
+    check_error(lib().kjarni_hip_op_repetition_penalty_rows(device, _f(lg), ld, rows, vocab, i.ctypes.data_as(_ffi._u32p),
+                                                            h.ctypes.data_as(_ffi._u32p) if h.size else None, h.size, penalty, _f(out)))
+    return out
+
+
+def lookup_accept_sampled(block, draft, uniforms, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                          min_p: Optional[float] = None, vocab: Optional[int] = None):
+    """Deciding a verify block on the host (no GPU): block [rows, ld] processed logits, the draft, one draw per decided row.
+    Returns (picks, accepted, draws_used)."""
+    lg = np.ascontiguousarray(block, np.float32)
+    rows, ld = lg.shape
+    vocab = ld if vocab is None else int(vocab)
+    d = np.ascontiguousarray(draft, np.uint32)
+    u = np.ascontiguousarray(uniforms, np.float32)
+    if u.size < min(d.size, rows - 1) + 1:
+        raise ValueError("one draw per row that may be decided")
+    picks = np.zeros(8, np.uint32)
+    a, used = C.c_int32(0), C.c_int32(0)
+    check_error(lib().kjarni_lookup_accept_sampled(_f(lg), ld, rows, vocab, d.ctypes.data_as(_ffi._u32p) if d.size else None, d.size,
+                                                   temperature, -1 if top_k is None else top_k, -1.0 if top_p is None else top_p,
+                                                   -1.0 if min_p is None else min_p, _f(u), picks.ctypes.data_as(_ffi._u32p), C.byref(a),
+                                                   C.byref(used)))
+    return picks[:a.value + 1].tolist(), int(a.value), int(used.value)
+
+
 def topk(scores, k: int, device: int = 0):
     """Top-k of a score matrix [nq, n] on the GPU (kjarni_hip_cosine_topk): (idx int64 [nq,k], score f32 [nq,k]),
     score descending, equal scores by ascending index; entries past n are (-1, -inf)."""

@@ -28,6 +28,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            acceptance verify_ms / plain_ms - 1, and end-to-end tokens/s with the acceptance histogram -- on a random-init
            model, whose greedy output degenerates into repetition: the full-acceptance end of the range, not a workload.
            KJARNI_LOOKUP_STEPS=N: N verify steps of 8 rows on the Llama shape only (for a kernel trace).
+  llm_lookup_sampled  (only on request) prompt-lookup decoding for sampled requests against the plain sampled loop of the same
+           build, alternated twice in one process, at the family's default sampling config: Llama-3.2-1B shape (bf16) and
+           gpt2-small (bf16); ms per plain sampled step, ms per verify-and-cut step at 2 / 4 / 8 rows (HipDecoder.
+           verify_step_sampled in a loop), the break-even acceptance, and tokens/s at both ends of acceptance (draws of 0 take
+           token 0: everything drafted is accepted; seeded draws on a random-init model: next to nothing is).
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -900,6 +905,104 @@ def main():
             measure("gpt2-small shape, bf16 weights", dec, rng.integers(0, 50257, 128).tolist(), 512,
                     "bf16 weights, f32 activations/accumulate/KV")
             del dec
+
+    if "llm_lookup_sampled" in which:
+        # Method (as llm_lookup): one process on one box, everything warmed first; the plain sampled loop -- the yardstick --
+        # alternates with verify-and-cut steps (the hook: verify pass, rows penalty, rows cut, one copy, one synchronise, the host's
+        # decision) at 2 / 4 / 8 rows and with the sampled lookup loop, twice, at the family's default sampling config.  Every
+        # figure is a median over runs that end in a synchronise.  The two ends of acceptance are steered by the draws: u = 0
+        # takes token 0 whatever the distribution (sample_from_probs), so the output repeats and every drafted token is accepted;
+        # seeded draws over a random-init model give an output that hardly repeats, so next to nothing is drafted or accepted
+        # (not steered to exactly none: that needs every step's distribution; the line reports what was drafted and accepted).
+        from tests import gpt2_fixture
+        from tests import sampled_lookup_cases as SC
+        rng = np.random.default_rng(0)
+        ROWS = (2, 4, 8)
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, prompt, n_new, dtype, family):
+            p = dict(SC.FAMILY_DEFAULTS[family])
+            kw = dict(temperature=p["temperature"], top_k=p["top_k"], top_p=p["top_p"], min_p=p["min_p"],
+                      repetition_penalty=p["repetition_penalty"])
+            zeros = np.zeros(n_new, np.float32)
+            seeded = np.random.default_rng(1).random(n_new).astype(np.float32)
+            draft = prompt[:7]
+
+            def hook_loop(rows, steps):
+                dec.reset()
+                dec.forward(prompt, fetch=False)
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    dec.verify_step_sampled(prompt[-1], draft[:rows - 1], zeros[:rows], rows=rows, history=prompt, fetch=False, **kw)
+                return (time.perf_counter() - t0) * 1e3 / steps
+
+            dec.generate_sampled(prompt, 8, uniforms=seeded[:8], **kw)
+            for rows in ROWS:
+                hook_loop(rows, 8)
+                dec.generate_sampled(prompt, 40, lookup=(rows - 1, 3, 1), uniforms=zeros[:40], **kw)
+            plain_ms, plain_rate, hook, e2e = [], [], {}, {}
+            for rep in range(2):
+                for rows in ROWS:
+                    dt, (out, _) = window(lambda: dec.generate_sampled(prompt, n_new, uniforms=seeded, **kw),
+                                          lambda: dec.generate_sampled(prompt, 1, uniforms=seeded[:1], **kw))
+                    plain_ms.append(dt * 1e3 / max(len(out) - 1, 1))
+                    plain_rate.append(max(len(out) - 1, 1) / dt)
+                    hook.setdefault(rows, []).append(hook_loop(rows, 64))
+                    for end, u in (("all_accepted", zeros), ("none_accepted", seeded)):
+                        dt, (got, st) = window(lambda: dec.generate_sampled(prompt, n_new, lookup=(rows - 1, 3, 1), uniforms=u, **kw),
+                                               lambda: dec.generate_sampled(prompt, 1, lookup=(rows - 1, 3, 1), uniforms=u[:1], **kw))
+                        steps = st["verify_steps"] + st["single_row_steps"]
+                        same = got == dec.generate_sampled(prompt, n_new, uniforms=u, **kw)[0]
+                        e2e.setdefault(end, {}).setdefault(rows, []).append(
+                            {"tokens_per_s": round(max(len(got) - 1, 1) / dt, 1), "ms_per_step": round(dt * 1e3 / max(steps, 1), 4),
+                             "steps": steps, "drafted": st["drafted_tokens"], "accepted": st["accepted_tokens"], "tokens": len(got),
+                             "ids_equal_plain": same})
+            med = lambda xs: float(np.median(xs))  # noqa: E731
+            plain = med(plain_ms)
+            c, l = dec.sampling_routes()
+            emit({"metric": f"sampled prompt-lookup decoding, {label}", "unit": "ms per step",
+                  "value": round(med([x["ms_per_step"] for x in e2e["all_accepted"][8]]), 4), "n_gpus": 1,
+                  "dtype": dtype, "data": "synthetic",
+                  "config": {"workload": f"{label}, random init, one 128-token prompt, {n_new} generated tokens, {family} default sampling "
+                                         f"{kw}; the plain sampled loop alternated twice with verify-and-cut steps and the sampled "
+                                         "lookup loop at 2 / 4 / 8 rows in one process"},
+                  "plain_sampled_ms_per_step": {"median": round(plain, 4), "min": round(min(plain_ms), 4), "max": round(max(plain_ms), 4),
+                                                "runs": [round(x, 4) for x in plain_ms]},
+                  "plain_sampled_tokens_per_s": round(med(plain_rate), 1),
+                  # the loop's own step (captured chain, one copy, one synchronise, the host's decision): whole windows of the
+                  # all-accepted runs over their steps; the hook is uncaptured and re-uploads ids and position every call
+                  "verify_and_cut_ms_per_step_replayed": {str(r): [x["ms_per_step"] for x in e2e["all_accepted"][r]] for r in ROWS},
+                  "verify_and_cut_over_plain_replayed": {str(r): round(med([x["ms_per_step"] for x in e2e["all_accepted"][r]]) / plain, 3)
+                                                         for r in ROWS},
+                  "break_even_accepted_per_step_replayed": {str(r): round(med([x["ms_per_step"] for x in e2e["all_accepted"][r]]) / plain - 1, 3)
+                                                            for r in ROWS},
+                  "verify_and_cut_ms_per_step_hook": {str(r): [round(x, 4) for x in hook[r]] for r in ROWS},
+                  "break_even_accepted_per_step_hook": {str(r): round(med(hook[r]) / plain - 1, 3) for r in ROWS},
+                  "generate_lookup_sampled": {end: {str(r): e2e[end][r] for r in ROWS} for end in e2e},
+                  "x_plain_tokens_per_s": {end: {str(r): round(max(x["tokens_per_s"] for x in e2e[end][r]) / med(plain_rate), 2) for r in ROWS}
+                                           for end in e2e},
+                  "rows_from_candidates": c, "rows_from_logits": l, "weight_bytes": dec.weight_bytes})
+
+        d = os.path.join(tmp, "llama-1b-lookup-sampled")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, rng.integers(1000, 100000, 128).tolist(), 512,
+                "bf16 weights, f32 activations/accumulate/KV", "llama")
+        del dec
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small-lookup-sampled")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        dec = kjarni_amd.HipDecoder(gd)
+        measure("gpt2-small shape, bf16 weights", dec, rng.integers(1, 50257, 128).tolist(), 512,
+                "bf16 weights, f32 activations/accumulate/KV", "gpt2")
+        del dec
 
     if "llm_score" in which:
         # Method (measuring guide, section 5; as llm_lookup): one process on one box; forward() -- the yardstick --, score() on
