@@ -740,6 +740,43 @@ KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, in
                                          int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused, float* logprob_out,
                                          uint32_t* top_out, float* top_logprob_out, float* lse_out);
 
+/* ---- prefix reuse: keep the cached rows of the tokens a call shares with what the cache holds (NOT in the reference, whose
+ * generator clears its cache per call, generator.rs:228-260) ----
+ * Off by default.  On: kjarni_hip_decoder_generate / _generate_lookup / _generate_sampled keep the cache rows of
+ * kjarni_hip_prefix_keep(resident tokens, prompt, n_prompt - 1) and forward the rest of the prompt; kjarni_hip_decoder_score
+ * keeps at most first - 1 rows; kjarni_hip_decoder_generate_batch prefills the prefix all its prompts share (one token short of
+ * the shortest prompt) once, into the single-sequence cache, and copies its rows into every lane that takes a request.  Kept
+ * rows were computed by whichever route wrote them (a reply's rows by one-row decode steps, where a full prefill runs the
+ * prompt GEMM), so logits and cache rows are the reuse-off values inside the decoder's float bar and the ids are the same
+ * wherever the two best logits are further apart than that.  A NULL handle is ignored. */
+void kjarni_hip_decoder_set_prefix_reuse(KjarniHipDecoder* decoder, int32_t on);
+/* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
+ * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
+ * tokens as kept and the rest of the prompt as computed. */
+void kjarni_hip_decoder_prefix_stats(const KjarniHipDecoder* decoder, uint64_t* reused, uint64_t* computed);
+/* Test hook: the tokens whose K / V sit in rows [0, *n) of the single-sequence cache, *n <= cache_len (rows past it belong to
+ * tokens a loop computed and discarded); the first min(*n, capacity) are written. */
+KjarniErrorCode kjarni_hip_decoder_resident(const KjarniHipDecoder* decoder, uint32_t* out, size_t capacity, size_t* n);
+/* Test hook: the logits row [vocab] the last forward of the single-sequence path left on the device (after a generate call
+ * with max_new_tokens 0: the logits of the last prompt token). */
+KjarniErrorCode kjarni_hip_decoder_last_logits(const KjarniHipDecoder* decoder, float* logits_out);
+/* The rule (no GPU, no handle): *keep = min(longest common prefix of resident[n] and prompt[m], limit). */
+KjarniErrorCode kjarni_hip_prefix_keep(const uint32_t* resident, size_t n, const uint32_t* prompt, size_t m, size_t limit, size_t* keep);
+/* Test hook of the lanes' shared prefix (after kjarni_hip_decoder_lanes_begin): rows [0, shared) of the single-sequence cache
+ * (shared <= cache_len) are copied into `lane` in one launch, bit for bit, then ids[n] are prefilled behind them. */
+KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDecoder* decoder, int32_t lane, int32_t shared, const uint32_t* ids,
+                                                       int32_t n);
+/* The copy kernel alone, host pointers: src [2 * layers, src_floats] (K then V per layer); dst [2 * layers, dst_floats] is read,
+ * gets src[c, 0 .. count) at dst[c, dst_offset ..) for every cache c, and is written back.  On the device every source /
+ * destination cache starts src_skew / dst_skew floats (0..3) past a 16-byte boundary.  Out-of-range arguments: INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_kv_prefix_copy(int32_t device, const float* src, int32_t layers, int64_t src_floats, int32_t src_skew,
+                                             int64_t dst_floats, int32_t dst_skew, int64_t dst_offset, int64_t count, float* dst);
+/* The switch and the counters on the Chat and Generator handles' models (send, generate, score and generate_batch take it). */
+KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
+void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);
+KjarniErrorCode kjarni_hip_generator_set_prefix_reuse(KjarniGenerator* generator, int32_t on);
+void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
+
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */
 KjarniErrorCode kjarni_hip_malloc(int32_t device, size_t bytes, void** out_dev);
 KjarniErrorCode kjarni_hip_free(int32_t device, void* ptr_dev);

@@ -497,6 +497,17 @@ SIGNATURES = {
     "kjarni_hip_op_score_head": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, c_int32, _u32p, c_int32, c_int32, _f32p,
                                            _u32p, _f32p, _f32p]),
     "kjarni_generator_score": (c_int32, [c_void_p, c_char_p, c_char_p, POINTER(KjarniScoreResult)]),
+    "kjarni_hip_decoder_set_prefix_reuse": (None, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_decoder_resident": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_decoder_last_logits": (c_int32, [c_void_p, _f32p]),
+    "kjarni_hip_prefix_keep": (c_int32, [_u32p, c_size_t, _u32p, c_size_t, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_decoder_lane_prefill_shared": (c_int32, [c_void_p, c_int32, c_int32, _u32p, c_int32]),
+    "kjarni_hip_op_kv_prefix_copy": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, c_int64, c_int32, c_int64, c_int64, _f32p]),
+    "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_generator_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),
     "kjarni_collect_files": (c_int32, [POINTER(KjarniIndexerConfig), POINTER(c_char_p), c_size_t,
                                        POINTER(KjarniStringArray)]),

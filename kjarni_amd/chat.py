@@ -180,6 +180,17 @@ class Chat:
         """Prompt-lookup decoding for sampled requests (off by default): the replies are the plain path's for the same seed."""
         check_error(lib().kjarni_hip_chat_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
 
+    def set_prefix_reuse(self, on: bool):
+        """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): turn N of a
+        conversation then prefills only what the conversation gained since turn N - 1."""
+        check_error(lib().kjarni_hip_chat_set_prefix_reuse(self._handle, 1 if on else 0))
+
+    def prefix_stats(self):
+        """(reused, computed): prompt tokens whose cache rows were kept / computed by the calls that ran with reuse on."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        lib().kjarni_hip_chat_prefix_stats(self._handle, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def sampling_counters(self):
         """(tokens decided from the device's candidates, tokens that needed the full logits)."""
         a, b = C.c_uint64(0), C.c_uint64(0)

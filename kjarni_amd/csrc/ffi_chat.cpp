@@ -736,6 +736,34 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniC
     return KJARNI_OK;
 }
 
+// Prefix reuse (LlmModel::set_prefix_reuse) on the handle's model: send() then prefills only what the conversation gained since
+// the last turn, score() only what follows the tokens it shares with the call before, generate_batch the shared prefix once.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    chat->inner->model().set_prefix_reuse(on != 0);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed)
+{
+    if (reused) *reused = chat ? chat->inner->model().prefix_reused_tokens() : 0;
+    if (computed) *computed = chat ? chat->inner->model().prefix_computed_tokens() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_prefix_reuse(KjarniGenerator* gen, int32_t on)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    gen->inner->model().set_prefix_reuse(on != 0);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT void kjarni_hip_generator_prefix_stats(KjarniGenerator* gen, uint64_t* reused, uint64_t* computed)
+{
+    if (reused) *reused = gen ? gen->inner->model().prefix_reused_tokens() : 0;
+    if (computed) *computed = gen ? gen->inner->model().prefix_computed_tokens() : 0;
+}
+
 KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
 {
     if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;

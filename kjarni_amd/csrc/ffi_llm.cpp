@@ -451,6 +451,58 @@ KJARNI_EXPORT void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* d, uin
     if (rows) *rows = d ? d->model->score_rows_calls() : 0;
 }
 
+// ---- prefix reuse -----------------------------------------------------------------------------------------------------------
+
+KJARNI_EXPORT void kjarni_hip_decoder_set_prefix_reuse(KjarniHipDecoder* d, int32_t on)
+{
+    if (!d) return;
+    std::lock_guard<std::mutex> lock(d->mu);
+    d->model->set_prefix_reuse(on != 0);
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_prefix_stats(const KjarniHipDecoder* d, uint64_t* reused, uint64_t* computed)
+{
+    if (reused) *reused = d ? d->model->prefix_reused_tokens() : 0;
+    if (computed) *computed = d ? d->model->prefix_computed_tokens() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_resident(const KjarniHipDecoder* d, uint32_t* out, size_t capacity, size_t* n)
+{
+    if (!d || !n || (capacity && !out)) return KJARNI_ERROR_NULL_POINTER;
+    std::lock_guard<std::mutex> lock(d->mu);
+    const std::vector<uint32_t>& r = d->model->resident();
+    *n = r.size();
+    if (capacity) std::memcpy(out, r.data(), std::min(capacity, r.size()) * sizeof(uint32_t));
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_last_logits(const KjarniHipDecoder* d, float* logits_out)
+{
+    if (!d || !logits_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->logits_to_host(logits_out);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_prefix_keep(const uint32_t* resident, size_t n, const uint32_t* prompt, size_t m, size_t limit,
+                                                     size_t* keep)
+{
+    if (!keep || (n && !resident) || (m && !prompt)) return KJARNI_ERROR_NULL_POINTER;
+    *keep = prefix_keep_host(resident, n, prompt, m, limit);
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDecoder* d, int32_t lane, int32_t shared, const uint32_t* ids,
+                                                                     int32_t n)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->lane_prefill_shared(lane, shared, ids, n);  // ranges checked before any GPU work
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* d, char** out)
 {
     if (!d || !out) return KJARNI_ERROR_NULL_POINTER;

@@ -604,6 +604,38 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lookup_draft(int32_t device, const u
     });
 }
 
+// The shared-prefix copy kernel alone, on caches given by the host: src [2 * layers, src_floats] (K then V of each layer),
+// dst [2 * layers, dst_floats] read and written back.  Every cache starts src_skew / dst_skew floats (0..3) past a 16-byte
+// boundary, so a test reaches the 4-byte path; count floats go to dst_offset of every destination cache.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_kv_prefix_copy(int32_t device, const float* src, int32_t layers, int64_t src_floats, int32_t src_skew,
+                                                           int64_t dst_floats, int32_t dst_skew, int64_t dst_offset, int64_t count, float* dst)
+{
+    if (!src || !dst) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (layers < 1 || layers > 1024 || src_floats < 1 || dst_floats < 1 || src_skew < 0 || src_skew > 3 || dst_skew < 0 || dst_skew > 3)
+            throw InvalidConfig("invalid copy dimensions (layers 1..1024, floats >= 1, skews 0..3)");
+        if (count < 0 || count > src_floats || dst_offset < 0 || dst_offset > dst_floats || count > dst_floats - dst_offset)
+            throw InvalidConfig("count / dst_offset reach outside the caches");
+        use_device(device);
+        const size_t n = 2 * (size_t)layers;
+        const size_t sstride = ((size_t)src_floats + 3 + 4) & ~(size_t)3, dstride = ((size_t)dst_floats + 3 + 4) & ~(size_t)3;  // 16-byte strides
+        DeviceBuf sb(n * sstride * sizeof(float)), db(n * dstride * sizeof(float)), table((size_t)layers * sizeof(LlmKvCopyPair));
+        std::vector<LlmKvCopyPair> pairs((size_t)layers);
+        auto sp = [&](size_t i) { return static_cast<float*>(sb.p) + i * sstride + src_skew; };
+        auto dp = [&](size_t i) { return static_cast<float*>(db.p) + i * dstride + dst_skew; };
+        for (size_t i = 0; i < n; ++i) {
+            hip_check(hipMemcpy(sp(i), src + i * (size_t)src_floats, (size_t)src_floats * sizeof(float), hipMemcpyHostToDevice), "H2D src");
+            hip_check(hipMemcpy(dp(i), dst + i * (size_t)dst_floats, (size_t)dst_floats * sizeof(float), hipMemcpyHostToDevice), "H2D dst");
+        }
+        for (size_t l = 0; l < (size_t)layers; ++l) pairs[l] = {sp(2 * l), dp(2 * l), sp(2 * l + 1), dp(2 * l + 1)};
+        hip_check(hipMemcpy(table.p, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D table");
+        hip_check(launch_kv_prefix_copy(static_cast<const LlmKvCopyPair*>(table.p), layers, dst_offset, count, nullptr), "prefix copy");
+        hip_check(hipDeviceSynchronize(), "sync");
+        for (size_t i = 0; i < n; ++i)
+            hip_check(hipMemcpy(dst + i * (size_t)dst_floats, dp(i), (size_t)dst_floats * sizeof(float), hipMemcpyDeviceToHost), "D2H dst");
+    });
+}
+
 // The greedy pick kernels alone, on logits given by the host: `calls` independent picks over logits [calls, rows, ld], each
 // through the launcher the models use, on one scratch (which every call must leave zeroed for the next).
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_argmax(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld, int32_t vocab,

@@ -441,8 +441,53 @@ void LlmModel::reset()
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     cache_len_ = 0;
+    resident_.clear();
     hip_check(hipMemsetAsync(pos_, 0, sizeof(int), stream_), "reset pos");
     hip_check(hipMemsetAsync(count_, 0, sizeof(int), stream_), "reset count");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Prefix reuse.  resident_[i] is the token behind cache row i; a call that starts a sequence keeps the rows of the longest
+// common prefix of resident_ and its prompt, capped so that every row whose output the call needs is computed by the call.
+
+size_t prefix_keep_host(const uint32_t* resident, size_t n_resident, const uint32_t* prompt, size_t n_prompt, size_t limit)
+{
+    const size_t top = std::min(std::min(n_resident, n_prompt), limit);
+    size_t p = 0;
+    while (p < top && resident[p] == prompt[p]) ++p;
+    return p;
+}
+
+int LlmModel::keep_prefix(const uint32_t* prompt, size_t n, size_t limit)
+{
+    const size_t p = prefix_keep_host(resident_.data(), resident_.size(), prompt, n, limit);
+    cache_len_ = (int)p;  // rows [p, ...) are dead: the forward below overwrites them from p on
+    resident_.resize(p);
+    prefix_reused_ += p;
+    prefix_computed_ += n - p;
+    hip_check(hipMemsetAsync(pos_, 0, sizeof(int), stream_), "reset pos");  // (as reset(): forward() sets it to the new length)
+    hip_check(hipMemsetAsync(count_, 0, sizeof(int), stream_), "reset count");
+    return (int)p;
+}
+
+void LlmModel::begin_sequence(const std::vector<uint32_t>& prompt)
+{
+    if (!prefix_reuse_) {
+        reset();
+        forward(prompt.data(), (int)prompt.size());
+        return;
+    }
+    // the last prompt token is always forwarded: its logits decide the first new token
+    const int p = keep_prefix(prompt.data(), prompt.size(), prompt.size() - 1);
+    forward(prompt.data() + p, (int)prompt.size() - p);
+}
+
+// What a generate loop leaves: `all` = the prompt + the emitted tokens.  Every one of them that was fed sits in the row of its
+// index; the last emitted token may not have been fed, and rows past `all` belong to tokens the loop computed and discarded
+// (a burst past a stop, rejected draft rows), so they do not count.
+void LlmModel::leave_resident(const std::vector<uint32_t>& all)
+{
+    resident_.assign(all.begin(), all.begin() + (ptrdiff_t)std::min(all.size(), (size_t)cache_len_));
 }
 
 void LlmModel::verify_gemv(const LlmGemvArgs& a, const char* what)
@@ -648,7 +693,7 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool 
 // Q, K, V projections (K and V rows land in the cache) -> RoPE -> causal attention over the cache -> o-proj + residual
 // -> RMSNorm -> gate, up -> silu(gate) * up -> down-proj + residual; same formulas as pass().  After the last layer the
 // final norm runs on the last (n - 1) % 8 + 1 rows (what last_hidden() exposes) and the lm head on the last row.
-void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score)
+void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int score_base)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
@@ -772,9 +817,10 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score)
             proj(pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
         }
         if (score) {  // the chunk's rows whose successor is scored: final norm into the (now free) norm buffer, then the head
-            const int lo = std::max(done, score_first_ - 1), hi = std::min(done + m - 1, score_n_ - 2);
+            const int at = score_base + done;  // the chunk's first position in the scored sequence
+            const int lo = std::max(at, score_first_ - 1), hi = std::min(at + m - 1, score_n_ - 2);
             if (lo <= hi) {
-                const float* src = ph_ + (size_t)(lo - done) * H;
+                const float* src = ph_ + (size_t)(lo - at) * H;
                 if (gpt2_) hip_check(launch_layernorm(src, final_norm_, final_norm_b_, c.eps, hi - lo + 1, H, pn_, s), "ln_f");
                 else hip_check(launch_rmsnorm(src, final_norm_, c.eps, hi - lo + 1, H, pn_, s), "final norm");
                 score_head_rows(pn_, lo, hi - lo + 1);
@@ -801,23 +847,25 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score)
 
 void LlmModel::forward(const uint32_t* ids, int n) { forward_rows(ids, n, false); }
 
-void LlmModel::forward_rows(const uint32_t* ids, int n, bool score)
+void LlmModel::forward_rows(const uint32_t* ids, int n, bool score, int score_base)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (n < 1) throw std::runtime_error("forward needs at least one token");
     if (cache_len_ + n > cache_cap_) throw std::runtime_error("context is full");
+    const bool tracked = resident_.size() == (size_t)cache_len_;  // (else: untracked rows lie between; resident_ stays a prefix)
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
     const int kvd = cfg_.kv_heads * cfg_.head_dim;
     if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
-        prefill_rows(ids, n, score);
+        prefill_rows(ids, n, score, score_base);
     } else {
         for (int i = 0; i < n; i += 8) {
             const int m = std::min(8, n - i);
             hip_check(hipMemcpyAsync(ids_, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, stream_), "H2D ids");
             pass(ids_, m, false);
             if (score) {  // pass() final-norms every row of the block into last_
-                const int lo = std::max(i, score_first_ - 1), hi = std::min(i + m - 1, score_n_ - 2);
-                if (lo <= hi) score_head_rows(last_ + (size_t)(lo - i) * cfg_.hidden, lo, hi - lo + 1);
+                const int at = score_base + i;  // the block's first position in the scored sequence
+                const int lo = std::max(at, score_first_ - 1), hi = std::min(at + m - 1, score_n_ - 2);
+                if (lo <= hi) score_head_rows(last_ + (size_t)(lo - at) * cfg_.hidden, lo, hi - lo + 1);
             }
             cache_len_ += m;
             last_rows_ = m;
@@ -826,6 +874,7 @@ void LlmModel::forward_rows(const uint32_t* ids, int n, bool score)
     }
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     hip_check(hipStreamSynchronize(stream_), "sync");
+    if (tracked) resident_.insert(resident_.end(), ids, ids + n);
 }
 
 void LlmModel::ensure_score()
@@ -881,11 +930,15 @@ void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, 
                                 std::to_string(cfg_.vocab));
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ensure_score();
-    reset();
+    // prefix reuse: rows first - 1 .. n - 2 must reach the head, so at most first - 1 rows are kept; targets and result slots
+    // stay indexed by absolute position
+    int keep = 0;
+    if (prefix_reuse_) keep = keep_prefix(ids, (size_t)n, (size_t)first - 1);
+    else reset();
     hip_check(hipMemcpyAsync(score_tgt_, ids + 1, (size_t)(n - 1) * 4, hipMemcpyHostToDevice, stream_), "H2D targets");
     score_first_ = first;
     score_n_ = n;
-    forward_rows(ids, n, true);
+    forward_rows(ids + keep, n - keep, true, keep);
     const size_t cnt = (size_t)(n - first);
     if (logprob_out) hip_check(hipMemcpyAsync(logprob_out, score_lp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H logprob");
     if (top_out) hip_check(hipMemcpyAsync(top_out, score_top_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H top");
@@ -988,8 +1041,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw std::runtime_error("prompt does not fit the context");
     if (opt.sample && !opt.uniform) throw std::runtime_error("sampling needs a uniform source");
-    reset();
-    forward(prompt.data(), (int)prompt.size());
+    begin_sequence(prompt);
     std::vector<uint32_t> out, all(prompt);
     const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
     const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
@@ -1098,6 +1150,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             hip_check(hipGraphLaunch(exec, stream_), "graph launch");
             cache_len_ += 1;
         }
+        leave_resident(all);
         return out;
     }
 
@@ -1138,6 +1191,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             hip_check(hipGraphLaunch(exec, stream_), "graph launch");
             cache_len_ += 1;
         }
+        leave_resident(all);
         return out;
     }
 
@@ -1177,6 +1231,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         cache_len_ += (int)steps;
         drain(produced);
     }
+    leave_resident(all);  // (the burst's rows past the last emitted token stay behind cache_len_, uncounted)
     return out;
 }
 
@@ -1240,6 +1295,11 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
         }
         lane_alloc_ = nl;
         lane_alloc_cap_ = nc;
+        // the shared-prefix copy reads its pointers from the device: (main K, lane-0 K, main V, lane-0 V) per layer
+        std::vector<LlmKvCopyPair> pairs(layers_.size());
+        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, lane_k_[i], layers_[i].v_cache, lane_v_[i]};
+        if (!lane_copy_table_) lane_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((pairs.size() * sizeof(LlmKvCopyPair) + 3) / 4));
+        hip_check(hipMemcpy(lane_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
     }
     if (cap != lane_cap_) drop_lane_graphs();  // (the capacity is an argument of the captured launches)
     lanes_ = lanes;
@@ -1270,22 +1330,46 @@ void LlmModel::lanes_begin(int lanes, int lane_context)
 
 // A prompt into one lane, by the prompt routes of forward(): the layers' cache pointers (and the capacity) are pointed at the
 // lane for the duration of the call.  The last position's logits are kept as the lane's logits row.
-void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n)
+void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n) { lane_prefill_at(lane, 0, ids, n); }
+
+// Rows [0, s) of every layer's K and V, single-sequence cache -> lane, in one launch on the model's stream.
+void LlmModel::lane_copy_prefix(int lane, int s)
+{
+    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (s < 0 || s > cache_len_ || s > lane_cap_) throw std::runtime_error("shared prefix out of range");
+    const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
+    hip_check(launch_kv_prefix_copy(lane_copy_table_, (int)layers_.size(), (int64_t)lane * lane_alloc_cap_ * kv, (int64_t)s * kv, stream_),
+              "prefix copy");
+}
+
+void LlmModel::lane_prefill_shared(int lane, int s, const uint32_t* ids, int n)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
     if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
-    if (n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
+    if (s < 0 || s > cache_len_) throw std::runtime_error("shared prefix out of range");
+    if ((int64_t)s + n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
+    lane_copy_prefix(lane, s);
+    lane_prefill_at(lane, s, ids, n);
+}
+
+void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
+    if (base < 0 || (int64_t)base + n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
     const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
     const size_t off = (size_t)lane * lane_alloc_cap_ * kv;
     std::vector<std::pair<float*, float*>> saved(layers_.size());
     const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
+    const size_t saved_resident = resident_.size();
     for (size_t i = 0; i < layers_.size(); ++i) {
         saved[i] = {layers_[i].k_cache, layers_[i].v_cache};
         layers_[i].k_cache = lane_k_[i] + off;
         layers_[i].v_cache = lane_v_[i] + off;
     }
-    cache_len_ = 0;
+    cache_len_ = base;
     cache_cap_ = lane_cap_;
     auto restore = [&] {
         for (size_t i = 0; i < layers_.size(); ++i) {
@@ -1295,6 +1379,7 @@ void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n)
         cache_len_ = saved_len;
         cache_cap_ = saved_cap;
         last_rows_ = saved_rows;
+        resident_.resize(std::min(resident_.size(), saved_resident));  // (forward() may have appended the lane's tokens)
     };
     try {
         forward(ids, n);
@@ -1310,7 +1395,7 @@ void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n)
         throw;
     }
     restore();
-    lane_len_[lane] = n;
+    lane_len_[lane] = base + n;
 }
 
 void LlmModel::lane_gemv(const LlmGemvArgs& a)
@@ -1496,6 +1581,36 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     ensure_lanes(n, lane_context);
     LlmLaneState& h = *lane_host_;
     const size_t vocab = (size_t)cfg_.vocab;
+    // Prefix reuse: the prefix every prompt shares (one token short of the shortest prompt, whose last token must be forwarded
+    // for its logits) is prefilled once into the single-sequence cache -- where it also stays for the next call -- and copied
+    // into each lane that takes a request; the lane prefills the rest behind it.
+    // Only the requests that will enter a lane count (generate()'s rule, as start() below applies it: something to generate).
+    auto enters = [&](const LaneRequest& q) {
+        const GenerateOptions& o = q.options;
+        const size_t max_len = o.max_len ? o.max_len : q.prompt.size() + o.max_new_tokens;
+        return o.max_new_tokens != 0 && q.prompt.size() < std::min((size_t)cap, max_len);
+    };
+    int shared = 0;
+    if (prefix_reuse_) {
+        const LaneRequest* head = nullptr;
+        size_t lcp = 0;
+        for (const LaneRequest& r : reqs) {
+            if (!enters(r)) continue;
+            if (!head) {
+                head = &r;
+                lcp = r.prompt.size() - 1;
+                continue;
+            }
+            lcp = std::min(lcp, r.prompt.size() - 1);
+            lcp = prefix_keep_host(head->prompt.data(), head->prompt.size(), r.prompt.data(), r.prompt.size(), lcp);
+        }
+        shared = (int)lcp;
+        if (shared >= 1) {
+            const int p = keep_prefix(head->prompt.data(), (size_t)shared, (size_t)shared);
+            if (p < shared) forward(head->prompt.data() + p, shared - p);
+            else hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+        }
+    }
 
     struct Run {  // the request a lane is working on, with generate()'s bookkeeping
         int64_t req = -1;
@@ -1529,7 +1644,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             // generator.rs:243-246 and 309-317, as generate(): stop at the lane's capacity and at max_len
             const size_t max_len = o.max_len ? o.max_len : q.prompt.size() + o.max_new_tokens;
             const size_t limit = std::min((size_t)cap, max_len);
-            if (o.max_new_tokens == 0 || q.prompt.size() >= limit) continue;  // nothing to generate
+            if (!enters(q)) continue;  // nothing to generate
             r.req = (int64_t)i;
             r.all = q.prompt;
             r.stops = o.stop_ids.empty() ? cfg_.eos_ids : o.stop_ids;
@@ -1537,7 +1652,14 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             r.max_new = o.max_new_tokens;
             r.seen = 0;
             r.done = false;
-            lane_prefill(l, q.prompt.data(), (int)q.prompt.size());
+            if (shared >= 1) {
+                lane_prefill_shared(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
+                prefix_reused_ += (uint64_t)shared;
+                prefix_computed_ += q.prompt.size() - (size_t)shared;
+            } else {
+                lane_prefill(l, q.prompt.data(), (int)q.prompt.size());
+                if (prefix_reuse_) prefix_computed_ += q.prompt.size();
+            }
             h.token[l] = 0;
             h.pos[l] = (int32_t)q.prompt.size();
             h.live[l] = 1;
@@ -1824,8 +1946,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
     ensure_lookup();
-    reset();
-    forward(prompt.data(), (int)prompt.size());
+    begin_sequence(prompt);
     std::vector<uint32_t> out, all(prompt);
     const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
     const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
@@ -1842,7 +1963,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         out.push_back(tok);
         if ((on_token && !on_token(tok)) || out.size() >= max_new_tokens) done = true;
     };
-    if (done) return out;
+    if (done) return out;  // (resident_ = the prompt, from begin_sequence)
     // the first pick comes from the prompt's logits; the history on the device = the prompt + that pick
     const uint32_t first = argmax();
     take(first);
@@ -1888,6 +2009,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         known_steps = st.steps;
         cache_len_ = st.n - 1;
     }
+    leave_resident(all);  // (`all` is a prefix of the device history: rows of rejected drafts and of picks past the end do not count)
     return out;
 }
 
@@ -2072,8 +2194,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
     ensure_lookup_sampled();
-    reset();
-    forward(prompt.data(), (int)prompt.size());
+    begin_sequence(prompt);
     const int vocab = cfg_.vocab;
     std::vector<uint32_t> out, all(prompt);
     const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
@@ -2161,6 +2282,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     }
     cache_len_ = (int)all.size() - 1;
     hip_check(hipMemcpy(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
+    leave_resident(all);
     return out;
 }
 

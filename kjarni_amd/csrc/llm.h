@@ -60,6 +60,7 @@ struct LaneRequest {
 
 struct LlmLaneState;  // llm_kernels.h
 struct LlmLookupState;
+struct LlmKvCopyPair;
 
 // Prompt-lookup decoding: how the draft of a verify step is found in the sequence's own history.
 struct LookupConfig {
@@ -73,6 +74,9 @@ struct LookupStats {  // over the steps the host consumed
 // The draft rule on a host-side history (what the device kernel computes): the tokens drafted after `tokens`.
 std::vector<uint32_t> lookup_draft_host(const uint32_t* tokens, size_t n, const LookupConfig& config);
 void check_lookup_config(const LookupConfig& config);  // InvalidConfig naming the field
+// Prefix reuse: how many cache rows a call may keep.  min(longest common prefix of the resident tokens and the prompt, limit);
+// a caller that needs the logits of the last prompt token passes limit = n_prompt - 1, score() passes first - 1.
+size_t prefix_keep_host(const uint32_t* resident, size_t n_resident, const uint32_t* prompt, size_t n_prompt, size_t limit);
 
 class LlmModel {
 public:
@@ -104,6 +108,20 @@ public:
     uint64_t tokens_from_logits() const { return tokens_from_logits_; }
 
     void reset();  // empty KV cache
+    // ---- prefix reuse: the entry points keep the cache rows of the longest common prefix with what the cache holds -----------
+    // Off (the default): generate(), generate_lookup(), generate_lookup_sampled() and score() empty the cache and prefill the
+    // whole prompt.  On: they keep the rows of prefix_keep_host(resident tokens, prompt, limit) and forward only the rest, and
+    // generate_lanes() prefills the prefix all its prompts share once, into the single-sequence cache, and copies its rows into
+    // every lane that takes a request (launch_kv_prefix_copy).  Kept rows were computed by whichever route wrote them, so the
+    // results are the no-reuse results inside the float bar.  The resident tokens are tracked whether the switch is on or off.
+    void set_prefix_reuse(bool on) { prefix_reuse_ = on; }
+    bool prefix_reuse() const { return prefix_reuse_; }
+    // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
+    uint64_t prefix_reused_tokens() const { return prefix_reused_; }
+    uint64_t prefix_computed_tokens() const { return prefix_computed_; }
+    // resident()[i] is the token whose K / V sit in row i of the single-sequence cache; size() <= cache_len() (rows past it
+    // belong to tokens a loop computed and then discarded, or to test hooks that do not say what they fed).
+    const std::vector<uint32_t>& resident() const { return resident_; }
     // Appends n tokens (fewer than 24: 8-row passes; more: the matrix-core route in 2 048-row chunks); the logits of the last
     // position stay on the device.
     void forward(const uint32_t* ids, int n);
@@ -149,6 +167,9 @@ public:
     // hidden rows [lanes, hidden] and logits [lanes, vocab]; a lane's cache length and rows.
     void lanes_begin(int lanes, int lane_context);
     void lane_prefill(int lane, const uint32_t* ids, int n);
+    // Test hook of the shared-prefix path: rows [0, s) of the single-sequence cache (s <= cache_len()) are copied into the lane
+    // (one launch_kv_prefix_copy), then ids[0, n) are prefilled behind them; the lane holds s + n rows.
+    void lane_prefill_shared(int lane, int s, const uint32_t* ids, int n);
     void lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
     int lane_cache_len(int lane) const;
     int lane_capacity() const { return lane_cap_; }
@@ -201,6 +222,13 @@ public:
 private:
     LlmModel() = default;
     void ensure_lanes(int lanes, int lane_context);
+    void lane_prefill_at(int lane, int base, const uint32_t* ids, int n);  // lane_prefill behind `base` rows the lane already holds
+    void lane_copy_prefix(int lane, int s);                                // rows [0, s) of every layer's K and V into the lane
+    // Empties the cache down to the rows it may keep for `prompt` (all of them dropped with reuse off) and forwards the rest:
+    // leaves the model as reset(); forward(prompt) does.
+    void begin_sequence(const std::vector<uint32_t>& prompt);
+    int keep_prefix(const uint32_t* prompt, size_t n, size_t limit);  // truncates the cache, counts; returns the rows kept
+    void leave_resident(const std::vector<uint32_t>& all);            // what a generate loop leaves: the fed tokens of `all`
     void lane_step(int lanes);                 // enqueue one lock-step step over lanes [0, lanes)
     void lane_gemv(const struct LlmGemvArgs& a);
     hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
@@ -233,8 +261,9 @@ private:
     void qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what);
     // n new tokens through the matrix-core GEMMs; score: each chunk's rows whose successor is scored go through the final norm
     // and score_head_rows
-    void prefill_rows(const uint32_t* ids_host, int n, bool score = false);
-    void forward_rows(const uint32_t* ids, int n, bool score);  // forward(), with score()'s sink
+    // score_base: the position of ids[0] in the scored sequence (score() with a kept prefix forwards only the rest)
+    void prefill_rows(const uint32_t* ids_host, int n, bool score = false, int score_base = 0);
+    void forward_rows(const uint32_t* ids, int n, bool score, int score_base = 0);  // forward(), with score()'s sink
     void ensure_score();
     // cnt final-normed rows Xn [cnt, hidden] of positions lo .. lo + cnt - 1 against the targets ids[lo + 1 ..]
     void score_head_rows(const float* Xn, int lo, int cnt);
@@ -341,6 +370,12 @@ private:
     int score_first_ = 0, score_n_ = 0;
     bool score_fused_ = true;
     uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0;
+    // prefix reuse: the tokens of the cache rows (host only), the switch, the counters, and the device table of
+    // (main K, lane K base, main V, lane V base) per layer that launch_kv_prefix_copy reads (built in ensure_lanes)
+    std::vector<uint32_t> resident_;
+    bool prefix_reuse_ = false;
+    uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
+    LlmKvCopyPair* lane_copy_table_ = nullptr;
 };
 
 }  // namespace kjarni

@@ -114,6 +114,17 @@ hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_hea
 // a full cache, else token = the pick.  best_scratch: kMaxLanes zero-initialised u64 (re-zeroed by the call).
 hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
                             LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
+// Shared prompt prefix: `count` floats from the start of every layer's single-sequence K and V cache into a lane's caches, one
+// launch for all layers.  table[layer] (device memory) = the source pointers and the lane-0 destination pointers; dst_offset =
+// the lane's offset in floats.  Bit-exact; 16-byte vector copies where source and destination are 16-byte aligned, 4-byte
+// copies otherwise (and for the tail of a count that is no multiple of 4).
+struct LlmKvCopyPair {
+    const float* src_k;
+    float* dst_k;
+    const float* src_v;
+    float* dst_v;
+};
+hipError_t launch_kv_prefix_copy(const LlmKvCopyPair* table, int layers, int64_t dst_offset, int64_t count, hipStream_t stream);
 
 // ---- prompt-lookup decoding (LlmModel::generate_lookup): draft from the sequence's own history, verify in one multi-row step
 constexpr int kLookupMaxDraft = 7, kLookupMaxNgram = 4;

@@ -2534,6 +2534,53 @@ hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lane
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Shared prompt prefix (llm.cpp: LlmModel::lane_copy_prefix): the first rows of the single-sequence cache into a lane's cache.
+namespace {
+
+// grid (x, 2 * layers): blockIdx.y picks the layer and K or V, the x blocks stride over the floats.  A pure stream: each
+// thread moves 16 bytes per trip when both pointers allow it (uniform per block), 4 bytes otherwise and for the last
+// count % 4 floats.  The words are moved as integers, so every bit pattern survives.  The pointers come out of the table, so
+// the compiler cannot know that they are global memory: the address space is stated, for global instead of flat accesses.
+typedef __attribute__((address_space(1))) const uint32_t gconst_u32;
+typedef __attribute__((address_space(1))) uint32_t g_u32;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) const u32x4 gconst_u4;
+typedef __attribute__((address_space(1))) u32x4 g_u4;
+
+__global__ __launch_bounds__(256) void kv_prefix_copy_kernel(const LlmKvCopyPair* __restrict__ table, int64_t dst_offset, int64_t count)
+{
+    const LlmKvCopyPair p = table[blockIdx.y >> 1];
+    const bool v = (blockIdx.y & 1) != 0;
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(v ? p.src_v : p.src_k);
+    const uintptr_t da = reinterpret_cast<uintptr_t>((v ? p.dst_v : p.dst_k) + dst_offset);
+    gconst_u32* __restrict__ src = reinterpret_cast<gconst_u32*>(sa);
+    g_u32* __restrict__ dst = reinterpret_cast<g_u32*>(da);
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    int64_t done = 0;
+    if (((sa | da) & 15) == 0) {
+        const int64_t n4 = count >> 2;
+        gconst_u4* __restrict__ s4 = reinterpret_cast<gconst_u4*>(sa);
+        g_u4* __restrict__ d4 = reinterpret_cast<g_u4*>(da);
+        for (int64_t i = tid; i < n4; i += step) d4[i] = s4[i];
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < count; i += step) dst[i] = src[i];
+}
+
+}  // namespace
+
+hipError_t launch_kv_prefix_copy(const LlmKvCopyPair* table, int layers, int64_t dst_offset, int64_t count, hipStream_t stream)
+{
+    if (layers <= 0 || count <= 0) return hipSuccess;
+    if (!table || dst_offset < 0 || layers > 32767) return hipErrorInvalidValue;
+    int64_t blocks = (count / 4 + 255) / 256;  // one 16-byte trip per thread up to 256 blocks per cache, more trips beyond
+    if (blocks < 1) blocks = 1;
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(kv_prefix_copy_kernel, dim3((unsigned)blocks, (unsigned)(2 * layers)), dim3(256), 0, stream, table, dst_offset, count);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Prompt-lookup decoding (llm.cpp: LlmModel::generate_lookup): the draft of the next verify step, and its pick.
 namespace {
 

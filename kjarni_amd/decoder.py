@@ -13,6 +13,16 @@ from ._ffi import check_error, lib
 WEIGHTS = {"auto": 0, "f32": 1, "bf16": 2}
 
 
+def prefix_keep(resident: Sequence[int], prompt: Sequence[int], limit: int) -> int:
+    """The prefix-reuse rule (no GPU): min(longest common prefix of `resident` and `prompt`, limit) -- the cache rows a call
+    keeps when it starts from `prompt` on a cache that holds `resident`."""
+    r, p = np.ascontiguousarray(resident, np.uint32), np.ascontiguousarray(prompt, np.uint32)
+    keep = C.c_size_t(0)
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32)) if x.size else None  # noqa: E731
+    check_error(lib().kjarni_hip_prefix_keep(u32(r), r.size, u32(p), p.size, int(limit), C.byref(keep)))
+    return int(keep.value)
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
@@ -324,3 +334,36 @@ class HipDecoder:
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_score_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+    # ---- prefix reuse: keep the cached rows of the tokens a call shares with what the cache holds ----
+    def set_prefix_reuse(self, on: bool):
+        """Off (the default): generate*, score and generate_batch prefill whole prompts.  On: they keep the cache rows of
+        prefix_keep(resident(), prompt, limit) -- limit len(prompt) - 1, score: first - 1 -- and forward the rest;
+        generate_batch prefills the prefix its prompts share once and copies its rows into the lanes."""
+        lib().kjarni_hip_decoder_set_prefix_reuse(self._h, 1 if on else 0)
+
+    def prefix_stats(self):
+        """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_prefix_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def resident(self) -> List[int]:
+        """Test hook: the tokens behind cache rows [0, len(result)); never longer than cache_len()."""
+        n = C.c_size_t(0)
+        check_error(lib().kjarni_hip_decoder_resident(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        check_error(lib().kjarni_hip_decoder_resident(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)))
+        return out[:n.value].tolist()
+
+    def last_logits(self):
+        """Test hook: the logits row the last forward of the single-sequence path left on the device."""
+        out = np.empty(self.vocab, np.float32)
+        check_error(lib().kjarni_hip_decoder_last_logits(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def lane_prefill_shared(self, lane: int, shared: int, ids: Sequence[int]):
+        """Test hook (after lanes_begin): rows [0, shared) of the single-sequence cache copied into `lane`, then `ids` prefilled
+        behind them."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        check_error(lib().kjarni_hip_decoder_lane_prefill_shared(self._h, lane, int(shared), a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))

@@ -82,6 +82,17 @@ class Generator:
         set_prompt_lookup() is 1..7 and the config has no n-gram ban; the text is the plain path's for the same seed."""
         check_error(lib().kjarni_hip_generator_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
 
+    def set_prefix_reuse(self, on: bool):
+        """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): score() over several
+        continuations of one context prefills the context once, generate_batch() the prefix its prompts share."""
+        check_error(lib().kjarni_hip_generator_set_prefix_reuse(self._handle, 1 if on else 0))
+
+    def prefix_stats(self):
+        """(reused, computed): prompt tokens whose cache rows were kept / computed by the calls that ran with reuse on."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        lib().kjarni_hip_generator_prefix_stats(self._handle, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def verify_gemv_calls(self):
         """(streamed, fallback) projections of prompt-lookup verify steps since load: moves only when a call took the lookup loop."""
         a, b = C.c_uint64(), C.c_uint64()

@@ -203,6 +203,19 @@ def lookup_draft(tokens, draft_tokens: int = 7, ngram_max: int = 3, ngram_min: i
     return out[:n.value].tolist()
 
 
+def kv_prefix_copy(src, dst, dst_offset: int, count: int, src_skew: int = 0, dst_skew: int = 0, device: int = 0):
+    """The lanes' shared-prefix copy kernel alone: src [2 * layers, src_floats], dst [2 * layers, dst_floats]; returns dst with
+    src[c, :count] at dst[c, dst_offset:dst_offset + count] for every cache c.  The skews (0..3 floats) move the device
+    buffers off their 16-byte boundaries."""
+    s, d = np.ascontiguousarray(src, np.float32), np.array(dst, np.float32, order="C")
+    if s.ndim != 2 or d.ndim != 2 or s.shape[0] != d.shape[0] or s.shape[0] % 2:
+        raise ValueError("src and dst: [2 * layers, floats]")
+    f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check_error(lib().kjarni_hip_op_kv_prefix_copy(device, f(s), s.shape[0] // 2, s.shape[1], src_skew, d.shape[1], dst_skew, int(dst_offset),
+                                                   int(count), f(d)))
+    return d
+
+
 ARGMAX_DECODER, ARGMAX_LANES, ARGMAX_LOOKUP = 0, 1, 2
 _i32p = C.POINTER(C.c_int32)
 

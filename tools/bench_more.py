@@ -38,6 +38,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
            end in a synchronise; the head's added time score - forward per route.
            KJARNI_SCORE_TRACE=N: N fused score() calls of the 2 048-token prompt on the Llama shape only (for a kernel trace).
+  llm_prefix  (only on request) prefix reuse off against on (HipDecoder.set_prefix_reuse) in one process, alternated twice:
+           Llama-3.2-1B shape (bf16) and gpt2-small (bf16).  Time to the first token of turn 2 with a resident history of 512 /
+           2 048 tokens and a 32-token message; five score() calls over one 512-token context with 8-token continuations; 8
+           requests under a 512-token shared prefix on 8 lanes (16-token tails, 16 new tokens), with the prefix not resident
+           and resident.  Medians of runs that end in a synchronise; the lines also go to profiles/llm_prefix_bench.jsonl.
 """
 import json
 import os
@@ -1073,6 +1078,80 @@ def main():
             dec = kjarni_amd.HipDecoder(gd)
             measure("gpt2-small shape, bf16 weights (n_ctx 2048)", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
             del dec
+
+    if "llm_prefix" in which:
+        # Method (measuring guide, section 5; as llm_score): one process on one box; every case is warmed with reuse off and on,
+        # then off and on are alternated twice, three runs each; a run is set up untimed (the cache brought to the state the case
+        # starts from) and ends in a synchronise (generate(), score() and generate_batch() return after one); medians.
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        out_path = os.path.join(ROOT, "profiles", "llm_prefix_bench.jsonl")
+        lines = []
+
+        def run_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            return (time.perf_counter() - t0) * 1e3
+
+        def measure(label, dec, vocab, lo, dtype):
+            ids = lambda n: rng.integers(lo, vocab, n).tolist()  # noqa: E731
+            cases = {}
+            for h in (512, 2048):   # turn 2: the history is resident, the message is new
+                hist, msg = ids(h), ids(32)
+                cases[f"turn2_ttft_history_{h}"] = (lambda hist=hist: dec.generate(hist, 0), lambda hist=hist, msg=msg: dec.generate(hist + msg, 1))
+            ctx, conts = ids(512), [ids(8) for _ in range(5)]
+
+            def five_scores():
+                for c in conts:
+                    dec.score(ctx + c, first=len(ctx))
+            cases["five_scores_context_512"] = (dec.reset, five_scores)
+            shared = ids(512)
+            prompts = [shared + ids(16) for _ in range(8)]
+            batch = lambda: dec.generate_batch(prompts, 16, lanes=8, lane_context=1024)  # noqa: E731
+            cases["lanes_8_shared_512_cold"] = (dec.reset, batch)
+            cases["lanes_8_shared_512_prefix_resident"] = (lambda: dec.generate(shared, 0), batch)
+            runs = {(name, on): [] for name in cases for on in (False, True)}
+            for on in (False, True):   # warm: allocations, graphs
+                dec.set_prefix_reuse(on)
+                for setup, fn in cases.values():
+                    setup()
+                    fn()
+            for rep in range(2):
+                for on in (False, True):
+                    dec.set_prefix_reuse(on)
+                    for name, (setup, fn) in cases.items():
+                        for _ in range(3):
+                            setup()
+                            runs[(name, on)].append(run_ms(fn))
+            dec.set_prefix_reuse(False)
+            med = lambda xs: float(np.median(xs))  # noqa: E731
+            res = {}
+            for name in cases:
+                off, on = med(runs[(name, False)]), med(runs[(name, True)])
+                res[name] = {"off_ms": round(off, 3), "on_ms": round(on, 3), "off_over_on": round(off / on, 2) if on > 0 else None,
+                             "runs_off": [round(x, 3) for x in runs[(name, False)]], "runs_on": [round(x, 3) for x in runs[(name, True)]]}
+            line = {"metric": f"prefix reuse, {label}", "unit": "ms to the first token of turn 2, 2 048-token history (reuse on)",
+                    "value": res["turn2_ttft_history_2048"]["on_ms"], "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"{label}, random init; prefix reuse off against on, alternated twice in one process, medians of 6 "
+                                           "runs, every run set up untimed and ended by a synchronise"},
+                    "cases": res, "weight_bytes": dec.weight_bytes}
+            lines.append(line)
+            emit(line)
+
+        d = os.path.join(tmp, "llama-1b-prefix")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=4096)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, 100000, 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=4096, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small-prefix")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        dec = kjarni_amd.HipDecoder(gd)
+        measure("gpt2-small shape, bf16 weights (n_ctx 4096)", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":
