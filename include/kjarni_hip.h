@@ -762,6 +762,17 @@ KjarniErrorCode kjarni_hip_decoder_resident(const KjarniHipDecoder* decoder, uin
 KjarniErrorCode kjarni_hip_decoder_last_logits(const KjarniHipDecoder* decoder, float* logits_out);
 /* The rule (no GPU, no handle): *keep = min(longest common prefix of resident[n] and prompt[m], limit). */
 KjarniErrorCode kjarni_hip_prefix_keep(const uint32_t* resident, size_t n, const uint32_t* prompt, size_t m, size_t limit, size_t* keep);
+/* The bookkeeping rule of every generation loop (no GPU, no handle), replayed on a given token stream: a request with a prompt of
+ * n_prompt tokens on a cache of `capacity` rows, with max_new_tokens, max_len (0: n_prompt + max_new_tokens) and stop_ids
+ * (n_stop 0: default_stop_ids, as a model's eos ids) is offered stream[0], stream[1], ... while it wants a token.  A token is
+ * emitted unless it is a stop id; the callback returns false at the cancel_after-th emitted token (-1: never).  *n_emitted:
+ * tokens emitted; *n_asked: tokens taken from the stream, the draws a sampled loop would take; *n_fed (may be NULL): emitted
+ * tokens that are the input of another step -- never the one the callback refused, nor the one that fills the context; the
+ * last of max_new_tokens only with feed_last != 0 (the processor / sampling loops of generate; 0: the lanes). */
+KjarniErrorCode kjarni_generation_replay(size_t n_prompt, size_t capacity, size_t max_new_tokens, size_t max_len, const uint32_t* stop_ids,
+                                         size_t n_stop, const uint32_t* default_stop_ids, size_t n_default_stop, const uint32_t* stream,
+                                         size_t n_stream, int64_t cancel_after, int32_t feed_last, size_t* n_emitted, size_t* n_asked,
+                                         size_t* n_fed);
 /* Test hook of the lanes' shared prefix (after kjarni_hip_decoder_lanes_begin): rows [0, shared) of the single-sequence cache
  * (shared <= cache_len) are copied into `lane` in one launch, bit for bit, then ids[n] are prefilled behind them. */
 KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDecoder* decoder, int32_t lane, int32_t shared, const uint32_t* ids,

@@ -502,6 +502,8 @@ SIGNATURES = {
     "kjarni_hip_decoder_resident": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
     "kjarni_hip_decoder_last_logits": (c_int32, [c_void_p, _f32p]),
     "kjarni_hip_prefix_keep": (c_int32, [_u32p, c_size_t, _u32p, c_size_t, c_size_t, POINTER(c_size_t)]),
+    "kjarni_generation_replay": (c_int32, [c_size_t, c_size_t, c_size_t, c_size_t, _u32p, c_size_t, _u32p, c_size_t, _u32p, c_size_t,
+                                           c_int64, c_int32, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
     "kjarni_hip_decoder_lane_prefill_shared": (c_int32, [c_void_p, c_int32, c_int32, _u32p, c_int32]),
     "kjarni_hip_op_kv_prefix_copy": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, c_int64, c_int32, c_int64, c_int64, _f32p]),
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),

@@ -34,6 +34,37 @@ struct InvalidDeviceList : std::runtime_error {  // KJARNI_HIP_DEVICES / an expl
 
 void hip_check(hipError_t e, const char* what);
 
+// Captures what `enqueue` puts on `stream` (thread-local capture mode) and instantiates it.  An exception from `enqueue` ends
+// and destroys the capture before it travels on.
+template <class Enqueue>
+hipGraphExec_t capture_graph(hipStream_t stream, Enqueue&& enqueue)
+{
+    hipGraph_t graph = nullptr;
+    hip_check(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal), "begin capture");
+    try {
+        enqueue();
+    } catch (...) {
+        (void)hipStreamEndCapture(stream, &graph);
+        if (graph) (void)hipGraphDestroy(graph);
+        throw;
+    }
+    hip_check(hipStreamEndCapture(stream, &graph), "end capture");
+    hipGraphExec_t exec = nullptr;
+    const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    hip_check(e, "graph instantiate");
+    return exec;
+}
+
+template <size_t N>
+void drop_graphs(hipGraphExec_t (&graphs)[N])  // destroys and nulls every instantiated graph of the array
+{
+    for (hipGraphExec_t& g : graphs) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+}
+
 // Entry points select their model's device with hipSetDevice, which is state of the CALLING host thread: a caller that
 // shares the thread with other HIP code (torch, its own kernels) must find its current device unchanged afterwards.
 class DeviceGuard {

@@ -91,6 +91,25 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_forward(KjarniHipDecoder* d, co
     });
 }
 
+// The C callback as the loops take it (empty when there is none).  Token-level API: no tokenizer behind it, so no text.
+static std::function<bool(uint32_t)> token_callback(KjarniTokenCallbackFn on_token, void* user_data)
+{
+    if (!on_token) return nullptr;
+    return [on_token, user_data](uint32_t id) {
+        KjarniToken t;
+        t.text = nullptr;
+        t.token_id = id;
+        t.is_special = false;
+        return on_token(t, user_data);
+    };
+}
+
+static void copy_ids_out(const std::vector<uint32_t>& ids, uint32_t* ids_out, size_t capacity, size_t* n_out)
+{
+    *n_out = ids.size();
+    if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, const uint32_t* prompt, size_t n_prompt,
                                                           size_t max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size,
                                                           KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
@@ -100,19 +119,10 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, c
     *n_out = 0;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        std::function<bool(uint32_t)> cb;
-        if (on_token)
-            cb = [&](uint32_t id) {
-                KjarniToken t;
-                t.text = nullptr;  // token-level API: no tokenizer behind it
-                t.token_id = id;
-                t.is_special = false;
-                return on_token(t, user_data);
-            };
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
         const std::vector<uint32_t> ids = d->model->generate(std::vector<uint32_t>(prompt, prompt + n_prompt), max_new_tokens,
                                                              repetition_penalty, no_repeat_ngram_size, cb);
-        *n_out = ids.size();
-        if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+        copy_ids_out(ids, ids_out, capacity, n_out);
     });
 }
 
@@ -258,22 +268,13 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_lookup(KjarniHipDecode
         if (n_prompt > (size_t)d->model->context())  // before any GPU work
             throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
                                 std::to_string(d->model->context()) + " tokens");
-        std::function<bool(uint32_t)> cb;
-        if (on_token)
-            cb = [&](uint32_t id) {
-                KjarniToken t;
-                t.text = nullptr;  // token-level API: no tokenizer behind it
-                t.token_id = id;
-                t.is_special = false;
-                return on_token(t, user_data);
-            };
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
         GenerateOptions opt;
         opt.max_new_tokens = max_new_tokens;
         opt.stop_ids.assign(stop_ids, stop_ids + n_stop);
         LookupStats st;
         const std::vector<uint32_t> ids = d->model->generate_lookup(std::vector<uint32_t>(prompt, prompt + n_prompt), opt, lk, cb, &st);
-        *n_out = ids.size();
-        if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+        copy_ids_out(ids, ids_out, capacity, n_out);
         if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
     });
 }
@@ -339,15 +340,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecod
         if (n_prompt > (size_t)d->model->context())
             throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
                                 std::to_string(d->model->context()) + " tokens");
-        std::function<bool(uint32_t)> cb;
-        if (on_token)
-            cb = [&](uint32_t id) {
-                KjarniToken t;
-                t.text = nullptr;  // token-level API: no tokenizer behind it
-                t.token_id = id;
-                t.is_special = false;
-                return on_token(t, user_data);
-            };
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
         GenerateOptions opt = sampling_options(*options);
         UniformRng rng(options->seed);
         size_t drawn = 0;
@@ -362,8 +355,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecod
         const std::vector<uint32_t> p(prompt, prompt + n_prompt);
         LookupStats st;
         const std::vector<uint32_t> ids = lookup ? d->model->generate_lookup_sampled(p, opt, lk, cb, &st) : d->model->generate(p, opt, cb);
-        *n_out = ids.size();
-        if (capacity) std::memcpy(ids_out, ids.data(), std::min(capacity, ids.size()) * sizeof(uint32_t));
+        copy_ids_out(ids, ids_out, capacity, n_out);
         if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
     });
 }
@@ -491,6 +483,31 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_prefix_keep(const uint32_t* resident, s
     if (!keep || (n && !resident) || (m && !prompt)) return KJARNI_ERROR_NULL_POINTER;
     *keep = prefix_keep_host(resident, n, prompt, m, limit);
     return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_generation_replay(size_t n_prompt, size_t capacity, size_t max_new_tokens, size_t max_len,
+                                                       const uint32_t* stop_ids, size_t n_stop, const uint32_t* default_stop_ids,
+                                                       size_t n_default_stop, const uint32_t* stream, size_t n_stream, int64_t cancel_after,
+                                                       int32_t feed_last, size_t* n_emitted, size_t* n_asked, size_t* n_fed)
+{
+    if (!n_emitted || !n_asked || (n_stop && !stop_ids) || (n_default_stop && !default_stop_ids) || (n_stream && !stream))
+        return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        GenerateOptions opt;
+        opt.max_new_tokens = max_new_tokens;
+        opt.max_len = max_len;
+        opt.stop_ids.assign(stop_ids, stop_ids + n_stop);
+        std::vector<uint32_t> out;
+        GenerationRun run(std::vector<uint32_t>(n_prompt, 0u), opt, capacity, std::vector<uint32_t>(default_stop_ids, default_stop_ids + n_default_stop),
+                          out);
+        const std::function<bool(uint32_t)> cb = [&](uint32_t) { return cancel_after < 0 || (int64_t)out.size() != cancel_after; };
+        size_t asked = 0, fed = 0;
+        while (run.wants_token() && asked < n_stream)
+            if (run.accept(stream[asked++], cb) && run.feeds_accepted(feed_last ? LastToken::Fed : LastToken::NotFed)) ++fed;
+        *n_emitted = out.size();
+        *n_asked = asked;
+        if (n_fed) *n_fed = fed;
+    });
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDecoder* d, int32_t lane, int32_t shared, const uint32_t* ids,

@@ -141,12 +141,9 @@ LlmModel::~LlmModel()
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (graph_) (void)hipGraphExecDestroy(graph_);
-    for (hipGraphExec_t g : lane_graphs_)
-        if (g) (void)hipGraphExecDestroy(g);
-    for (hipGraphExec_t g : lookup_graphs_)
-        if (g) (void)hipGraphExecDestroy(g);
-    for (hipGraphExec_t g : lookup_sampled_graphs_)
-        if (g) (void)hipGraphExecDestroy(g);
+    drop_graphs(lane_graphs_);
+    drop_graphs(lookup_graphs_);
+    drop_graphs(lookup_sampled_graphs_);
     if (stream_) (void)hipStreamDestroy(stream_);
     arena_.release();
 }
@@ -991,21 +988,15 @@ uint32_t LlmModel::argmax()
 hipGraphExec_t LlmModel::step_graph()
 {
     if (graph_) return graph_;
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
+    return graph_ = capture_graph(stream_, [&] {
         pass(reinterpret_cast<const uint32_t*>(token_), 1, true);
         enqueue_argmax(true);
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&graph_, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return graph_;
+    });
+}
+
+void LlmModel::ensure_host_logits()
+{
+    if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
 }
 
 void LlmModel::ensure_sampling()
@@ -1042,17 +1033,30 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     if ((int)prompt.size() > cache_cap_) throw std::runtime_error("prompt does not fit the context");
     if (opt.sample && !opt.uniform) throw std::runtime_error("sampling needs a uniform source");
     begin_sequence(prompt);
-    std::vector<uint32_t> out, all(prompt);
-    const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
-    const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
-    // generator.rs:243-246 and 309-317: stop at the model's context and at max_len = prompt + max_new_tokens | max_length.
-    const size_t max_len = opt.max_len ? opt.max_len : prompt.size() + opt.max_new_tokens;
-    const size_t context_limit = std::min((size_t)cache_cap_, max_len);
-    const size_t max_new_tokens = opt.max_new_tokens;
+    std::vector<uint32_t> out;
+    GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
     const float repetition_penalty = opt.repetition_penalty;
     const int no_repeat_ngram = opt.no_repeat_ngram;
+    const bool processors = repetition_penalty != 1.0f || no_repeat_ngram > 0;
+    const size_t vocab = (size_t)cfg_.vocab;
+    // The two loops below decide a token from the logits of the last step, then run the next step on it: the replayed graph
+    // of the greedy loop, which reads its input token from token_ (overwritten here with the host's choice; the graph's own
+    // argmax result is ignored) and advances position and key count on the device.
+    hipGraphExec_t exec = nullptr;
+    const auto feed = [&](uint32_t next) {
+        if (!exec) exec = step_graph();
+        const int32_t tok = (int32_t)next;
+        hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
+        if (processors && device_sampling_) {
+            int32_t* slot = samp_tokens_ + (run.all.size() - 1);
+            hip_check(hipMemcpyAsync(slot, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D history");
+            hip_check(launch_token_counts(slot, 1, (int)vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
+        }
+        hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        cache_len_ += 1;
+    };
 
-    if ((opt.sample || repetition_penalty != 1.0f || no_repeat_ngram > 0) && device_sampling_) {
+    if ((opt.sample || processors) && device_sampling_) {
         // Logits processors and sampling (generator.rs:331-343), with everything that is O(vocab) on the device
         // (llm_kernels.hip): the processors edit the logits where the vocabulary head left them; for a sampled token three
         // small launches cut the vocabulary down to the candidates within reach of the filters and sum the exponentials,
@@ -1060,31 +1064,20 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         // finishes top-k / top-p / min-p / temperature / the draw on them exactly as the reference does on the full array
         // (sampling.cpp); when the candidates cannot decide (rare: a crossing within the rounding of the device's sum, a
         // nearly flat distribution) it fetches the logits -- already processed -- and runs the full-array path.
-        const size_t vocab = (size_t)cfg_.vocab;
         ensure_sampling();
-        if (opt.sample && !host_logits_)
-            hip_check(hipHostMalloc((void**)&host_logits_, vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+        if (opt.sample) ensure_host_logits();
         SampleHeader* header_dev = reinterpret_cast<SampleHeader*>(samp_out_);
         SampleCandidate* cand_dev = reinterpret_cast<SampleCandidate*>(samp_out_ + sizeof(SampleHeader));
         const SampleHeader* header = reinterpret_cast<const SampleHeader*>(samp_host_);
         const SampleCandidate* cand = reinterpret_cast<const SampleCandidate*>(samp_host_ + sizeof(SampleHeader));
-        const bool processors = repetition_penalty != 1.0f || no_repeat_ngram > 0;
-        if (processors) {  // the history so far = the prompt
-            hip_check(hipMemsetAsync(samp_counts_, 0, vocab * sizeof(int), stream_), "memset counts");
-            hip_check(hipMemsetAsync(samp_ndistinct_, 0, sizeof(int), stream_), "memset");
-            hip_check(hipMemcpyAsync(samp_tokens_, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
-            hip_check(launch_token_counts(samp_tokens_, (int)all.size(), (int)vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_),
-                      "token counts");
+        if (processors) {
+            begin_token_history(samp_tokens_, run.all.data(), run.all.size(), samp_counts_, samp_distinct_, samp_ndistinct_);
             hip_check(hipStreamSynchronize(stream_), "sync");  // (`all` grows below: the copy must have read it)
         }
-        std::vector<float> probs, cvals;
-        std::vector<uint32_t> ids, cids;
-        hipGraphExec_t exec = nullptr;
         int skip_candidates = 0;
-        for (size_t step = 0; step < max_new_tokens; ++step) {
-            if (all.size() >= context_limit) break;
+        while (run.wants_token()) {
             if (processors)
-                hip_check(launch_logits_processors(logits_, (int)vocab, samp_tokens_, (int)all.size(), samp_counts_, samp_distinct_,
+                hip_check(launch_logits_processors(logits_, (int)vocab, samp_tokens_, (int)run.all.size(), samp_counts_, samp_distinct_,
                                                    samp_ndistinct_, repetition_penalty, no_repeat_ngram, stream_), "logits processors");
             uint32_t next;
             if (opt.sample) {
@@ -1100,32 +1093,14 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
                     hip_check(hipStreamSynchronize(stream_), "sync");
                 }
                 bool decided = false;
-                if (attempt && !header->overflow && header->count <= (uint32_t)kCandCap) {
-                    const size_t n = header->count;
-                    if (n > (size_t)kCandFirst) {
-                        hip_check(hipMemcpyAsync(samp_host_ + first, samp_out_ + first, (n - kCandFirst) * sizeof(SampleCandidate),
-                                                 hipMemcpyDeviceToHost, stream_), "D2H candidates");
-                        hip_check(hipStreamSynchronize(stream_), "sync");
-                    }
-                    cids.resize(n);
-                    cvals.resize(n);
-                    for (size_t i = 0; i < n; ++i) {
-                        cids[i] = cand[i].token;
-                        cvals[i] = cand[i].logit;
-                    }
-                    decided = sampling_distribution_candidates(cids.data(), cvals.data(), n, header->mx, header->floor, header->sum, vocab,
-                                                               opt.sampling, ids, probs);
-                }
-                if (decided) {
-                    ++tokens_from_candidates_;
-                } else {
-                    ++tokens_from_logits_;
-                    if (attempt) skip_candidates = 8;
-                    hip_check(hipMemcpyAsync(host_logits_, logits_, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
-                    hip_check(hipStreamSynchronize(stream_), "sync");
-                    sampling_distribution(host_logits_, vocab, opt.sampling, ids, probs);  // (the processors already ran, on the device)
-                }
-                next = sample_from_distribution(ids, probs, opt.uniform(), vocab);
+                next = sample_row(attempt ? header : nullptr, kCandFirst, kCandCap, [&](size_t i) -> const SampleCandidate& { return cand[i]; },
+                                  [&](size_t n) {
+                                      hip_check(hipMemcpyAsync(samp_host_ + first, samp_out_ + first, (n - kCandFirst) * sizeof(SampleCandidate),
+                                                               hipMemcpyDeviceToHost, stream_), "D2H candidates");
+                                      hip_check(hipStreamSynchronize(stream_), "sync");
+                                  },
+                                  logits_, opt.sampling, opt.uniform(), &decided);  // (the processors already ran, on the device)
+                if (!decided && attempt) skip_candidates = 8;
             } else {  // greedy on processed logits: the device's argmax (last maximum wins), four bytes back
                 enqueue_argmax(false);
                 int32_t t = 0;
@@ -1134,42 +1109,28 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
                 next = (uint32_t)t;
                 ++tokens_from_candidates_;
             }
-            if (is_stop(next)) break;
-            all.push_back(next);
-            out.push_back(next);
-            if (on_token && !on_token(next)) break;
-            if (all.size() >= context_limit) break;
-            if (!exec) exec = step_graph();
-            const int32_t tok = (int32_t)next;
-            hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
-            if (processors) {
-                int32_t* slot = samp_tokens_ + (all.size() - 1);
-                hip_check(hipMemcpyAsync(slot, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D history");
-                hip_check(launch_token_counts(slot, 1, (int)vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
-            }
-            hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-            cache_len_ += 1;
+            // LastToken::Fed: one step per emitted token, the last of max_new_tokens included -- under an explicit max_len past
+            // prompt + max_new_tokens; with the default max_len that token fills context_limit and is not fed
+            if (!run.accept(next, on_token) || !run.feeds_accepted(LastToken::Fed)) break;
+            feed(next);
         }
-        leave_resident(all);
+        leave_resident(run.all);
         return out;
     }
 
-    if (opt.sample || repetition_penalty != 1.0f || no_repeat_ngram > 0) {
+    if (opt.sample || processors) {
         // (device sampling switched off: the checker path of the tests)
         // Logits processors and sampling work on the host copy of the logits (generator.rs:331-343): one pass per token.
         // The logits land in a pinned host buffer (one async copy per token at full PCIe rate).
-        if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+        ensure_host_logits();
         float* lg = host_logits_;
-        const size_t vocab = (size_t)cfg_.vocab;
         std::vector<float> probs;
         std::vector<uint32_t> ids;
-        hipGraphExec_t exec = nullptr;
-        for (size_t step = 0; step < max_new_tokens; ++step) {
-            if (all.size() >= context_limit) break;
+        while (run.wants_token()) {
             hip_check(hipMemcpyAsync(lg, logits_, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
             hip_check(hipStreamSynchronize(stream_), "sync");
-            apply_repetition_penalty(lg, vocab, all, repetition_penalty);
-            if (no_repeat_ngram > 0) apply_no_repeat_ngram(lg, vocab, all, (size_t)no_repeat_ngram);
+            apply_repetition_penalty(lg, vocab, run.all, repetition_penalty);
+            if (no_repeat_ngram > 0) apply_no_repeat_ngram(lg, vocab, run.all, (size_t)no_repeat_ngram);
             uint32_t next;
             if (opt.sample) {
                 sampling_distribution(lg, vocab, opt.sampling, ids, probs);
@@ -1177,51 +1138,32 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             } else {
                 next = argmax_last(lg, vocab);
             }
-            if (is_stop(next)) break;
-            all.push_back(next);
-            out.push_back(next);
-            if (on_token && !on_token(next)) break;
-            if (all.size() >= context_limit) break;
-            // The step itself is the replayed graph of the greedy loop: it reads its input token from token_ (overwritten
-            // here with the host's choice; the graph's own argmax result is ignored) and advances position and key count
-            // on the device.
-            if (!exec) exec = step_graph();
-            const int32_t tok = (int32_t)next;
-            hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
-            hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-            cache_len_ += 1;
+            // LastToken::Fed, as the loop above
+            if (!run.accept(next, on_token) || !run.feeds_accepted(LastToken::Fed)) break;
+            feed(next);
         }
-        leave_resident(all);
+        leave_resident(run.all);
         return out;
     }
 
     // Plain greedy: token, position and key count stay on the device; one graph replay per token, the host
-    // looks every few steps.  Tokens computed past a stop token / a stop request are discarded.
+    // looks every few steps.  Tokens computed past a stop token / a stop request are discarded.  The device feeds itself:
+    // a burst is sized by what is left of max_new_tokens, so the last token of max_new_tokens is not fed (LastToken::NotFed).
     enqueue_argmax(true);
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     std::vector<int32_t> hist((size_t)hist_cap_);
     size_t produced = 0, seen = 0;
-    bool done = max_new_tokens == 0;
     auto drain = [&](size_t upto) {
-        for (; seen < upto && !done; ++seen) {
-            const uint32_t tok = (uint32_t)hist[seen];
-            if (all.size() >= context_limit || is_stop(tok)) {
-                done = true;
-                break;
-            }
-            all.push_back(tok);
-            out.push_back(tok);
-            if ((on_token && !on_token(tok)) || out.size() >= max_new_tokens) done = true;
-        }
+        for (; seen < upto && !run.done; ++seen) run.accept((uint32_t)hist[seen], on_token);
     };
     hip_check(hipMemcpyAsync(hist.data(), hist_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H token");
     hip_check(hipStreamSynchronize(stream_), "sync");
     produced = 1;
     drain(1);
-    hipGraphExec_t exec = done ? nullptr : step_graph();
+    if (!run.done) exec = step_graph();
     const size_t burst = on_token ? 4 : 16;
-    while (!done) {
-        size_t steps = std::min(burst, max_new_tokens - out.size());
+    while (!run.done) {
+        size_t steps = std::min(burst, run.max_new - out.size());
         steps = std::min(steps, (size_t)cache_cap_ - (size_t)cache_len_);
         if (steps == 0) break;
         for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
@@ -1231,8 +1173,49 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         cache_len_ += (int)steps;
         drain(produced);
     }
-    leave_resident(all);  // (the burst's rows past the last emitted token stay behind cache_len_, uncounted)
+    leave_resident(run.all);  // (the burst's rows past the last emitted token stay behind cache_len_, uncounted)
     return out;
+}
+
+// The history so far = the given tokens: their counts and the list of the distinct ones.
+void LlmModel::begin_token_history(int32_t* tokens_dev, const uint32_t* host, size_t n, int* counts, int32_t* distinct, int* ndistinct)
+{
+    const int vocab = cfg_.vocab;
+    hip_check(hipMemsetAsync(counts, 0, (size_t)vocab * sizeof(int), stream_), "memset counts");
+    hip_check(hipMemsetAsync(ndistinct, 0, sizeof(int), stream_), "memset");
+    if (host) hip_check(hipMemcpyAsync(tokens_dev, host, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
+    hip_check(launch_token_counts(tokens_dev, (int)n, vocab, counts, distinct, ndistinct, stream_), "token counts");
+}
+
+template <class Cand, class FetchRest>
+uint32_t LlmModel::sample_row(const SampleHeader* header, int first, int capacity, Cand&& cand, FetchRest&& fetch_rest, const float* logits_dev,
+                              const SamplingParams& params, float uniform, bool* decided_out)
+{
+    const size_t vocab = (size_t)cfg_.vocab;
+    bool decided = false;
+    if (header && !header->overflow && header->count <= (uint32_t)capacity) {
+        const size_t n = header->count;
+        if (n > (size_t)first) fetch_rest(n);  // (they were not part of the step's copy)
+        row_cids_.resize(n);
+        row_cvals_.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const SampleCandidate& c = cand(i);
+            row_cids_[i] = c.token;
+            row_cvals_[i] = c.logit;
+        }
+        decided = sampling_distribution_candidates(row_cids_.data(), row_cvals_.data(), n, header->mx, header->floor, header->sum, vocab, params,
+                                                   row_ids_, row_probs_);
+    }
+    if (decided) {
+        ++tokens_from_candidates_;
+    } else {
+        ++tokens_from_logits_;
+        hip_check(hipMemcpyAsync(host_logits_, logits_dev, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        sampling_distribution(host_logits_, vocab, params, row_ids_, row_probs_);
+    }
+    if (decided_out) *decided_out = decided;
+    return sample_from_distribution(row_ids_, row_probs_, uniform, vocab);
 }
 
 
@@ -1246,14 +1229,6 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
 // lane pick.  Seven launches per layer, two more than the one-token step (which fuses the rotation into the projection and
 // the merge into the o-proj).
 
-void LlmModel::drop_lane_graphs()
-{
-    for (hipGraphExec_t& g : lane_graphs_) {
-        if (g) (void)hipGraphExecDestroy(g);
-        g = nullptr;
-    }
-}
-
 void LlmModel::ensure_lanes(int lanes, int lane_context)
 {
     if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8");
@@ -1262,7 +1237,7 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
     const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim);
     if (lanes > lane_alloc_ || cap > lane_alloc_cap_) {
         hip_check(hipStreamSynchronize(stream_), "sync");
-        drop_lane_graphs();
+        drop_graphs(lane_graphs_);
         // everything sized by lanes x rows is one allocation of its own: the caches of every layer, then the pick history and the
         // processors' history / distinct lists; when the lanes or their rows grow it is replaced and the old one freed
         const int nl = std::max(lanes, lane_alloc_), nc = std::max(cap, lane_alloc_cap_);
@@ -1301,7 +1276,7 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
         if (!lane_copy_table_) lane_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((pairs.size() * sizeof(LlmKvCopyPair) + 3) / 4));
         hip_check(hipMemcpy(lane_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
     }
-    if (cap != lane_cap_) drop_lane_graphs();  // (the capacity is an argument of the captured launches)
+    if (cap != lane_cap_) drop_graphs(lane_graphs_);  // (the capacity is an argument of the captured launches)
     lanes_ = lanes;
     lane_cap_ = cap;
     std::memset(lane_host_.get(), 0, sizeof(LlmLaneState));
@@ -1539,22 +1514,11 @@ void LlmModel::lane_kv_rows(int lane, int layer, int first, int rows, float* k_o
 hipGraphExec_t LlmModel::lane_step_graph(int n)
 {
     if (lane_graphs_[n]) return lane_graphs_[n];
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
+    return lane_graphs_[n] = capture_graph(stream_, [&] {
         lane_step(n);
         hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_, 1,
                                    stream_), "lane pick");
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&lane_graphs_[n], graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return lane_graphs_[n];
+    });
 }
 
 std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
@@ -1565,17 +1529,19 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
+    std::vector<std::vector<uint32_t>> out(reqs.size());
+    std::vector<GenerationRun> waiting;  // generate()'s bookkeeping of every request, until a lane takes it
+    waiting.reserve(reqs.size());
     for (size_t i = 0; i < reqs.size(); ++i) {  // everything is checked before any GPU work
         const LaneRequest& r = reqs[i];
         if (r.prompt.empty()) throw std::runtime_error("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
         if ((int64_t)r.prompt.size() > cap)
             throw InvalidConfig("prompt " + std::to_string(i) + " does not fit the lane capacity of " + std::to_string(cap) + " tokens");
         if (r.options.sample && !r.options.uniform) throw std::runtime_error("sampling needs a uniform source (prompt " + std::to_string(i) + ")");
-        const std::vector<uint32_t>& stops = r.options.stop_ids.empty() ? cfg_.eos_ids : r.options.stop_ids;
-        if ((int)stops.size() > kMaxLaneStops) throw std::runtime_error("more than 16 stop ids (prompt " + std::to_string(i) + ")");
+        waiting.emplace_back(r.prompt, r.options, (size_t)cap, cfg_.eos_ids, out[i]);
+        if ((int)waiting.back().stops.size() > kMaxLaneStops) throw std::runtime_error("more than 16 stop ids (prompt " + std::to_string(i) + ")");
         slow = slow || r.options.sample || r.options.repetition_penalty != 1.0f || r.options.no_repeat_ngram > 0;
     }
-    std::vector<std::vector<uint32_t>> out(reqs.size());
     if (reqs.empty()) return out;
     const int n = (int)std::min<size_t>((size_t)lanes, reqs.size());
     ensure_lanes(n, lane_context);
@@ -1585,17 +1551,13 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     // for its logits) is prefilled once into the single-sequence cache -- where it also stays for the next call -- and copied
     // into each lane that takes a request; the lane prefills the rest behind it.
     // Only the requests that will enter a lane count (generate()'s rule, as start() below applies it: something to generate).
-    auto enters = [&](const LaneRequest& q) {
-        const GenerateOptions& o = q.options;
-        const size_t max_len = o.max_len ? o.max_len : q.prompt.size() + o.max_new_tokens;
-        return o.max_new_tokens != 0 && q.prompt.size() < std::min((size_t)cap, max_len);
-    };
     int shared = 0;
     if (prefix_reuse_) {
         const LaneRequest* head = nullptr;
         size_t lcp = 0;
-        for (const LaneRequest& r : reqs) {
-            if (!enters(r)) continue;
+        for (size_t i = 0; i < reqs.size(); ++i) {
+            const LaneRequest& r = reqs[i];
+            if (!waiting[i].wants_token()) continue;
             if (!head) {
                 head = &r;
                 lcp = r.prompt.size() - 1;
@@ -1612,27 +1574,17 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
         }
     }
 
-    struct Run {  // the request a lane is working on, with generate()'s bookkeeping
+    struct Run {  // the request a lane is working on
         int64_t req = -1;
-        std::vector<uint32_t> all;
-        std::vector<uint32_t> stops;
-        size_t context_limit = 0, max_new = 0, seen = 0;
-        bool done = true;
+        size_t seen = 0;
+        GenerationRun g;
+        std::function<bool(uint32_t)> on_token;  // the caller's, bound to the request
     };
     Run run[kLanes];
     size_t next_req = 0;
-    auto is_stop = [](const Run& r, uint32_t t) { return std::find(r.stops.begin(), r.stops.end(), t) != r.stops.end(); };
-    // generate()'s drain: the token joins the output unless the request is at its limit or the token is a stop id
-    auto take = [&](int l, uint32_t tok) {
+    auto take = [&](int l, uint32_t tok) {  // generate()'s drain
         Run& r = run[l];
-        if (r.done) return;
-        if (r.all.size() >= r.context_limit || is_stop(r, tok)) {
-            r.done = true;
-            return;
-        }
-        r.all.push_back(tok);
-        out[(size_t)r.req].push_back(tok);
-        if ((on_token && !on_token((size_t)r.req, tok)) || out[(size_t)r.req].size() >= r.max_new) r.done = true;
+        if (!r.g.done) r.g.accept(tok, r.on_token);
     };
     // the next waiting request that has anything to generate goes into lane l (false: none is left); its prompt is prefilled
     auto start = [&](int l) {
@@ -1640,18 +1592,12 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
         while (next_req < reqs.size()) {
             const size_t i = next_req++;
             const LaneRequest& q = reqs[i];
-            const GenerateOptions& o = q.options;
-            // generator.rs:243-246 and 309-317, as generate(): stop at the lane's capacity and at max_len
-            const size_t max_len = o.max_len ? o.max_len : q.prompt.size() + o.max_new_tokens;
-            const size_t limit = std::min((size_t)cap, max_len);
-            if (!enters(q)) continue;  // nothing to generate
+            if (!waiting[i].wants_token()) continue;  // nothing to generate
             r.req = (int64_t)i;
-            r.all = q.prompt;
-            r.stops = o.stop_ids.empty() ? cfg_.eos_ids : o.stop_ids;
-            r.context_limit = limit;
-            r.max_new = o.max_new_tokens;
             r.seen = 0;
-            r.done = false;
+            r.g = std::move(waiting[i]);
+            r.on_token = nullptr;
+            if (on_token) r.on_token = [&on_token, i](uint32_t tok) { return on_token(i, tok); };
             if (shared >= 1) {
                 lane_prefill_shared(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
                 prefix_reused_ += (uint64_t)shared;
@@ -1664,19 +1610,19 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             h.pos[l] = (int32_t)q.prompt.size();
             h.live[l] = 1;
             h.count[l] = 0;
-            h.limit[l] = (int32_t)std::min(r.max_new, limit - q.prompt.size());
-            h.n_stop[l] = (int32_t)r.stops.size();
-            for (size_t e = 0; e < r.stops.size(); ++e) h.stop[l][e] = (int32_t)r.stops[e];
+            h.limit[l] = (int32_t)r.g.tokens_left();  // the device's copy of the rule: it feeds itself and stops there (LastToken::NotFed)
+            h.n_stop[l] = (int32_t)r.g.stops.size();
+            for (size_t e = 0; e < r.g.stops.size(); ++e) h.stop[l][e] = (int32_t)r.g.stops[e];
             return true;
         }
         r.req = -1;
-        r.done = true;
+        r.g.done = true;
         h.live[l] = 0;
         return false;
     };
     auto any_running = [&] {
         for (int l = 0; l < n; ++l)
-            if (!run[l].done) return true;
+            if (!run[l].g.done) return true;
         return false;
     };
 
@@ -1714,18 +1660,18 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             bool dirty = false;
             for (int l = 0; l < n; ++l) {
                 Run& r = run[l];
-                if (!r.done && !h.live[l]) r.done = true;
-                if (r.done && h.live[l]) {
+                if (!r.g.done && !h.live[l]) r.g.done = true;
+                if (r.g.done && h.live[l]) {
                     h.live[l] = 0;
                     dirty = true;
                 }
-                while (r.done && next_req < reqs.size()) {
+                while (r.g.done && next_req < reqs.size()) {
                     if (!start(l)) break;
                     first_pick(l);  // (writes the whole state, this pass's edits included)
                     dirty = false;
                     lane_len_[l] = h.pos[l];
                     drain(1);
-                    if (!h.live[l]) r.done = true;
+                    if (!h.live[l]) r.g.done = true;
                 }
             }
             if (!any_running()) break;
@@ -1744,7 +1690,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     // with the lane's own history and counts (launch_logits_processors), then the device argmax (four bytes back) or, for a
     // sampled request, the row to the host and generate()'s full-array sampler with the request's own uniform source.  The
     // step itself is the same chain of launches, enqueued directly (no graph): correct first, fast later.
-    if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+    ensure_host_logits();
     std::vector<float> probs;
     std::vector<uint32_t> ids;
     auto pstate = [&](int l, int32_t*& tok, int32_t*& distinct, int*& counts, int*& nd) {
@@ -1758,10 +1704,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
         int32_t *tok, *distinct;
         int *counts, *nd;
         pstate(l, tok, distinct, counts, nd);
-        hip_check(hipMemsetAsync(counts, 0, vocab * sizeof(int), stream_), "memset counts");
-        hip_check(hipMemsetAsync(nd, 0, sizeof(int), stream_), "memset");
-        hip_check(hipMemcpyAsync(tok, r.all.data(), r.all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
-        hip_check(launch_token_counts(tok, (int)r.all.size(), (int)vocab, counts, distinct, nd, stream_), "token counts");
+        begin_token_history(tok, r.g.all.data(), r.g.all.size(), counts, distinct, nd);
         hip_check(hipStreamSynchronize(stream_), "sync");
     };
     for (int l = 0; l < n; ++l)
@@ -1771,14 +1714,14 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             Run& r = run[l];
             // (a lane whose request ends takes the next one and decides its first token in the same round, from the prefill's row:
             // the round's step rewrites every row)
-            while (!r.done) {
+            while (!r.g.done) {
                 const GenerateOptions& o = reqs[(size_t)r.req].options;
                 float* row = lane_logits_ + (size_t)l * vocab;
                 int32_t *tok, *distinct;
                 int *counts, *nd;
                 pstate(l, tok, distinct, counts, nd);
                 if (o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0)
-                    hip_check(launch_logits_processors(row, (int)vocab, tok, (int)r.all.size(), counts, distinct, nd, o.repetition_penalty,
+                    hip_check(launch_logits_processors(row, (int)vocab, tok, (int)r.g.all.size(), counts, distinct, nd, o.repetition_penalty,
                                                        o.no_repeat_ngram, stream_), "logits processors");
                 uint32_t next;
                 if (o.sample) {
@@ -1796,12 +1739,14 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
                     ++tokens_from_candidates_;
                 }
                 take(l, next);
-                if (!r.done && r.all.size() >= r.context_limit) r.done = true;
-                if (!r.done) {  // the token is the lane's next input, at the position it took in the sequence
+                // LastToken::NotFed: a request that has its max_new_tokens leaves the lane at once (asked whatever take() did:
+                // a refused token leaves the run done, which answers no)
+                if (!r.g.feeds_accepted(LastToken::NotFed)) r.g.done = true;
+                if (!r.g.done) {  // the token is the lane's next input, at the position it took in the sequence
                     h.token[l] = (int32_t)next;
-                    h.pos[l] = (int32_t)r.all.size() - 1;
+                    h.pos[l] = (int32_t)r.g.all.size() - 1;
                     h.live[l] = 1;
-                    int32_t* slot = tok + (r.all.size() - 1);
+                    int32_t* slot = tok + (r.g.all.size() - 1);
                     hip_check(hipMemcpyAsync(slot, &h.token[l], sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
                     hip_check(launch_token_counts(slot, 1, (int)vocab, counts, distinct, nd, stream_), "token counts");
                     hip_check(hipStreamSynchronize(stream_), "sync");
@@ -1883,28 +1828,19 @@ hipGraphExec_t LlmModel::lookup_graph(int rows, const LookupConfig& c)
 {
     if (lookup_ngram_[0] != c.ngram_max || lookup_ngram_[1] != c.ngram_min) {  // (arguments of the captured draft launch)
         hip_check(hipStreamSynchronize(stream_), "sync");
-        for (hipGraphExec_t& g : lookup_graphs_) {
-            if (g) (void)hipGraphExecDestroy(g);
-            g = nullptr;
-        }
+        drop_graphs(lookup_graphs_);
         lookup_ngram_[0] = c.ngram_max;
         lookup_ngram_[1] = c.ngram_min;
     }
     if (lookup_graphs_[rows]) return lookup_graphs_[rows];
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
-        enqueue_verify(rows, c.ngram_max, c.ngram_min, true, true);
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&lookup_graphs_[rows], graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return lookup_graphs_[rows];
+    return lookup_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify(rows, c.ngram_max, c.ngram_min, true, true); });
+}
+
+// The ids of a verify block: the token, the draft, and the draft's last id again in the rows past it.
+static void verify_block_ids(uint32_t token, const uint32_t* draft, int n_draft, int rows, uint32_t* ids)
+{
+    ids[0] = token;
+    for (int r = 1; r < rows; ++r) ids[r] = r <= n_draft ? draft[r - 1] : ids[r - 1];
 }
 
 int LlmModel::verify_step(uint32_t token, const uint32_t* draft, int n_draft, int rows, uint32_t* tokens_out, float* logits_out)
@@ -1917,8 +1853,7 @@ int LlmModel::verify_step(uint32_t token, const uint32_t* draft, int n_draft, in
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ensure_lookup();
     uint32_t ids[kLanes];
-    ids[0] = token;
-    for (int r = 1; r < rows; ++r) ids[r] = r <= n_draft ? draft[r - 1] : ids[r - 1];
+    verify_block_ids(token, draft, n_draft, rows, ids);
     LlmLookupState st = {};
     st.n = cache_len_ + 1;
     st.m = n_draft;
@@ -1947,27 +1882,13 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
     ensure_lookup();
     begin_sequence(prompt);
-    std::vector<uint32_t> out, all(prompt);
-    const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
-    const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
-    const size_t max_len = opt.max_len ? opt.max_len : prompt.size() + opt.max_new_tokens;
-    const size_t context_limit = std::min((size_t)cache_cap_, max_len);
-    const size_t max_new_tokens = opt.max_new_tokens;
-    bool done = max_new_tokens == 0;
-    auto take = [&](uint32_t tok) {  // generate()'s drain
-        if (all.size() >= context_limit || is_stop(tok)) {
-            done = true;
-            return;
-        }
-        all.push_back(tok);
-        out.push_back(tok);
-        if ((on_token && !on_token(tok)) || out.size() >= max_new_tokens) done = true;
-    };
-    if (done) return out;  // (resident_ = the prompt, from begin_sequence)
+    std::vector<uint32_t> out;
+    GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
+    const std::vector<uint32_t>& all = run.all;
+    if (run.done) return out;  // (resident_ = the prompt, from begin_sequence)
     // the first pick comes from the prompt's logits; the history on the device = the prompt + that pick
-    const uint32_t first = argmax();
-    take(first);
-    if (done) return out;
+    run.accept(argmax(), on_token);
+    if (run.done) return out;
     LlmLookupState st = {};
     st.n = (int32_t)all.size();
     hip_check(hipMemcpyAsync(lk_hist_, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
@@ -1976,13 +1897,15 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     const size_t burst = on_token ? 4 : 16;
     std::vector<int32_t> toks(burst * kLanes), log(2 * burst);
     int known_n = st.n, known_steps = 0;
-    while (!done) {
+    // The device feeds itself (the verify step's pick is the next step's input), a burst at a time: what it leaves in the cache is
+    // where its history stands, all.size() - 1 or further (picks past the end of the run).
+    while (!run.done) {
         // a step of `rows` rows writes cache rows [pos, pos + rows) and moves pos by at most `rows`: `steps` of them stay inside
         // the cache whatever they accept while cache_len_ + steps * rows <= capacity; near the end the steps get narrower
         const int room = cache_cap_ - cache_len_;
         if (room <= 0) break;
         const int rows = std::min(lk.draft_tokens + 1, room);
-        const size_t steps = std::min(std::min(burst, (size_t)(room / rows)), max_new_tokens - out.size());
+        const size_t steps = std::min(std::min(burst, (size_t)(room / rows)), run.max_new - out.size());
         hipGraphExec_t exec = lookup_graph(rows, lk);
         for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
         hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
@@ -1994,14 +1917,9 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         size_t off = 0;
         for (size_t i = 0; i < steps; ++i) {  // in order; tokens past the end are discarded
             const int m = log[2 * i], a = log[2 * i + 1];
-            if (!done) {
-                if (stats) {
-                    if (rows == 1) ++stats->single_row_steps;
-                    else ++stats->verify_steps;
-                    stats->drafted_tokens += (uint64_t)m;
-                    stats->accepted_tokens += (uint64_t)a;
-                }
-                for (int j = 0; j <= a && !done; ++j) take((uint32_t)toks[off + (size_t)j]);
+            if (!run.done) {
+                if (stats) stats->count(rows, m, a);
+                for (int j = 0; j <= a && !run.done; ++j) run.accept((uint32_t)toks[off + (size_t)j], on_token);
             }
             off += (size_t)a + 1;
         }
@@ -2021,7 +1939,7 @@ void LlmModel::ensure_lookup_sampled()
 {
     ensure_lookup();
     ensure_sampling();
-    if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+    ensure_host_logits();
     if (ls_scratch_) return;
     const size_t out_bytes = (size_t)kLanes * sizeof(SampleHeader) + sample_rows_entries(kRowsCandCap) * sizeof(SampleCandidate);
     ls_scratch_ = dalloc((sample_scratch_rows_bytes(kLanes) + 3) / 4);
@@ -2052,14 +1970,6 @@ void LlmModel::enqueue_verify_sampled(int rows, const LookupConfig& c, const Gen
     rows_cut(vlogits_, rows, opt);
 }
 
-void LlmModel::drop_lookup_sampled_graphs()
-{
-    for (hipGraphExec_t& g : lookup_sampled_graphs_) {
-        if (g) (void)hipGraphExecDestroy(g);
-        g = nullptr;
-    }
-}
-
 hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const LookupConfig& c, const GenerateOptions& opt)
 {
     LookupSampledArgs want;
@@ -2070,66 +1980,31 @@ hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const LookupConfig& c, c
         !same(want.top_p, ls_args_.top_p) || !same(want.min_p, ls_args_.min_p) ||
         !same(want.penalty, ls_args_.penalty)) {  // (arguments of the captured launches)
         hip_check(hipStreamSynchronize(stream_), "sync");
-        drop_lookup_sampled_graphs();
+        drop_graphs(lookup_sampled_graphs_);
         ls_args_ = want;
     }
     if (lookup_sampled_graphs_[rows]) return lookup_sampled_graphs_[rows];
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
-        enqueue_verify_sampled(rows, c, opt, true);
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&lookup_sampled_graphs_[rows], graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return lookup_sampled_graphs_[rows];
+    return lookup_sampled_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify_sampled(rows, c, opt, true); });
 }
 
 // One row's token from what the step's copy brought over (header + candidates of `row` in the pinned mirror); the row's
 // processed logits are fetched only when the candidates decline.
 uint32_t LlmModel::decide_row(const float* logits_dev, int row, const GenerateOptions& opt, float uniform)
 {
-    const size_t vocab = (size_t)cfg_.vocab;
-    const SampleHeader& h = reinterpret_cast<const SampleHeader*>(ls_host_)[row];
+    const SampleHeader* headers = reinterpret_cast<const SampleHeader*>(ls_host_);
     const size_t cand_off = kLanes * sizeof(SampleHeader);
     const SampleCandidate* cand = reinterpret_cast<const SampleCandidate*>(ls_host_ + cand_off);
-    std::vector<uint32_t> ids, cids;
-    std::vector<float> probs, cvals;
-    bool decided = false;
-    if (device_sampling_ && !h.overflow && h.count <= (uint32_t)kRowsCandCap) {
-        const size_t n = h.count;
-        if (n > (size_t)kSampleRowsChunk) {  // the later chunks of this row were not part of the step's copy
-            for (size_t s0 = kSampleRowsChunk; s0 < n; s0 += kSampleRowsChunk) {
-                const size_t at = cand_off + sample_rows_slot(row, (int)s0) * sizeof(SampleCandidate);
-                hip_check(hipMemcpyAsync(ls_host_ + at, ls_out_ + at, std::min<size_t>(kSampleRowsChunk, n - s0) * sizeof(SampleCandidate),
-                                         hipMemcpyDeviceToHost, stream_), "D2H candidates");
-            }
-            hip_check(hipStreamSynchronize(stream_), "sync");
-        }
-        cids.resize(n);
-        cvals.resize(n);
-        for (size_t i = 0; i < n; ++i) {
-            const SampleCandidate& c = cand[sample_rows_slot(row, (int)i)];
-            cids[i] = c.token;
-            cvals[i] = c.logit;
-        }
-        decided = sampling_distribution_candidates(cids.data(), cvals.data(), n, h.mx, h.floor, h.sum, vocab, opt.sampling, ids, probs);
-    }
-    if (decided) {
-        ++tokens_from_candidates_;
-    } else {
-        ++tokens_from_logits_;
-        hip_check(hipMemcpyAsync(host_logits_, logits_dev + (size_t)row * vocab, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_),
-                  "D2H logits");
-        hip_check(hipStreamSynchronize(stream_), "sync");
-        sampling_distribution(host_logits_, vocab, opt.sampling, ids, probs);  // (the penalty already ran, on the device)
-    }
-    return sample_from_distribution(ids, probs, uniform, vocab);
+    return sample_row(device_sampling_ ? headers + row : nullptr, kSampleRowsChunk, kRowsCandCap,
+                      [&](size_t i) -> const SampleCandidate& { return cand[sample_rows_slot(row, (int)i)]; },
+                      [&](size_t n) {  // the later chunks of this row
+                          for (size_t s0 = kSampleRowsChunk; s0 < n; s0 += kSampleRowsChunk) {
+                              const size_t at = cand_off + sample_rows_slot(row, (int)s0) * sizeof(SampleCandidate);
+                              hip_check(hipMemcpyAsync(ls_host_ + at, ls_out_ + at, std::min<size_t>(kSampleRowsChunk, n - s0) * sizeof(SampleCandidate),
+                                                       hipMemcpyDeviceToHost, stream_), "D2H candidates");
+                          }
+                          hip_check(hipStreamSynchronize(stream_), "sync");
+                      },
+                      logits_dev + (size_t)row * (size_t)cfg_.vocab, opt.sampling, uniform, nullptr);  // (the penalty already ran, on the device)
 }
 
 int LlmModel::verify_step_sampled(uint32_t token, const uint32_t* draft, int n_draft, int rows, const GenerateOptions& opt,
@@ -2150,17 +2025,10 @@ int LlmModel::verify_step_sampled(uint32_t token, const uint32_t* draft, int n_d
     ensure_lookup_sampled();
     const int vocab = cfg_.vocab;
     uint32_t ids[kLanes];
-    ids[0] = token;
-    for (int r = 1; r < rows; ++r) ids[r] = r <= n_draft ? draft[r - 1] : ids[r - 1];
+    verify_block_ids(token, draft, n_draft, rows, ids);
     hip_check(hipMemcpyAsync(vids_, ids, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, stream_), "H2D ids");
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
-    if (penalty) {
-        hip_check(hipMemsetAsync(samp_counts_, 0, (size_t)vocab * sizeof(int), stream_), "memset counts");
-        hip_check(hipMemsetAsync(samp_ndistinct_, 0, sizeof(int), stream_), "memset");
-        hip_check(hipMemcpyAsync(samp_tokens_, history, n_history * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
-        hip_check(launch_token_counts(samp_tokens_, (int)n_history, vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_),
-                  "token counts");
-    }
+    if (penalty) begin_token_history(samp_tokens_, history, n_history, samp_counts_, samp_distinct_, samp_ndistinct_);
     LookupConfig c;
     enqueue_verify_sampled(rows, c, opt, false);
     const size_t bytes = kLanes * sizeof(SampleHeader) + (size_t)rows * kSampleRowsChunk * sizeof(SampleCandidate);
@@ -2196,34 +2064,20 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     ensure_lookup_sampled();
     begin_sequence(prompt);
     const int vocab = cfg_.vocab;
-    std::vector<uint32_t> out, all(prompt);
-    const std::vector<uint32_t>& stops = opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids;
-    const auto is_stop = [&](uint32_t t) { return std::find(stops.begin(), stops.end(), t) != stops.end(); };
-    const size_t max_len = opt.max_len ? opt.max_len : prompt.size() + opt.max_new_tokens;
-    const size_t context_limit = std::min((size_t)cache_cap_, max_len);
-    const size_t max_new_tokens = opt.max_new_tokens;
+    std::vector<uint32_t> out;
+    GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
+    const std::vector<uint32_t>& all = run.all;
     const bool penalty = opt.repetition_penalty != 1.0f;
-    bool done = false;
     // generate()'s loop, one token: the checks ahead of the draw, the draw, the checks behind it.  False: the token did not join
-    // the output (no draw was taken, or it was a stop token).
+    // the output (no draw was taken, or it was a stop token).  The picks of a step are the input rows of the next one, the last
+    // token of the run is never one of them: the cache ends at all.size() - 1 rows, however the run ends.
     auto decide = [&](const float* logits_dev, int row, uint32_t* pick) {
-        if (out.size() >= max_new_tokens || all.size() >= context_limit) {
-            done = true;
-            return false;
-        }
-        const uint32_t next = decide_row(logits_dev, row, opt, opt.uniform());
-        *pick = next;
-        if (is_stop(next)) {
-            done = true;
-            return false;
-        }
-        all.push_back(next);
-        out.push_back(next);
-        if ((on_token && !on_token(next)) || all.size() >= context_limit || out.size() >= max_new_tokens) done = true;
-        return true;
+        if (!run.wants_token()) return false;
+        *pick = decide_row(logits_dev, row, opt, opt.uniform());
+        return run.accept(*pick, on_token);
     };
     const size_t head_bytes = kLanes * sizeof(SampleHeader);
-    if (max_new_tokens == 0 || all.size() >= context_limit) return out;
+    if (!run.wants_token()) return out;
     // the device state: the history = the prompt (the picks join it step by step), the counts of the prompt, pos = history - 1
     LlmLookupState st = {};
     st.n = (int32_t)all.size();
@@ -2231,11 +2085,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     hip_check(hipMemcpyAsync(lk_hist_, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D history");
     hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
     hip_check(hipMemcpyAsync(pos_, &pos0, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
-    if (penalty) {
-        hip_check(hipMemsetAsync(samp_counts_, 0, (size_t)vocab * sizeof(int), stream_), "memset counts");
-        hip_check(hipMemsetAsync(samp_ndistinct_, 0, sizeof(int), stream_), "memset");
-        hip_check(launch_token_counts(lk_hist_, (int)all.size(), vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
-    }
+    if (penalty) begin_token_history(lk_hist_, nullptr, all.size(), samp_counts_, samp_distinct_, samp_ndistinct_);
     // the first token: the prompt's logits as a block of one row
     rows_cut(logits_, 1, opt);
     hip_check(hipMemcpyAsync(ls_host_, ls_out_, head_bytes + (size_t)kSampleRowsChunk * sizeof(SampleCandidate), hipMemcpyDeviceToHost, stream_),
@@ -2243,7 +2093,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     hip_check(hipStreamSynchronize(stream_), "sync");  // (`all` grows below: the copies must have read it)
     uint32_t picks[kLanes];
     int n_picks = decide(logits_, 0, &picks[0]) ? 1 : 0;
-    while (!done) {
+    while (run.wants_token()) {
         // as generate_lookup: a step of `rows` rows writes cache rows [pos, pos + rows); near the end of the cache the steps narrow
         const int room = cache_cap_ - cache_len_;
         if (room <= 0) break;
@@ -2266,18 +2116,13 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
         const int m = (int)draft.size();
         int a = 0;
         n_picks = 0;
-        for (int r = 0; r <= m && !done; ++r) {
+        for (int r = 0; r <= m && run.wants_token(); ++r) {
             if (!decide(vlogits_, r, &picks[r])) break;
             ++n_picks;
             if (r == m || picks[r] != draft[(size_t)r]) break;
             ++a;
         }
-        if (stats) {
-            if (rows == 1) ++stats->single_row_steps;
-            else ++stats->verify_steps;
-            stats->drafted_tokens += (uint64_t)m;
-            stats->accepted_tokens += (uint64_t)a;
-        }
+        if (stats) stats->count(rows, m, a);
         cache_len_ = (int)all.size() - 1;
     }
     cache_len_ = (int)all.size() - 1;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "generation_run.h"
 #include "quant_kernels.h"
 #include "sampling.h"
 
@@ -40,18 +41,6 @@ struct LlmConfig {
     static LlmConfig from_json(const std::string& text);
 };
 
-// One run of run_generation_loop (generator.rs:228-381).
-struct GenerateOptions {
-    size_t max_new_tokens = 0;
-    size_t max_len = 0;  // prompt + generated cap (generator.rs:243-246); 0 = prompt + max_new_tokens
-    float repetition_penalty = 1.0f;
-    int no_repeat_ngram = 0;
-    bool sample = false;  // DecodingStrategy::Sample(params) instead of Greedy
-    SamplingParams sampling;
-    std::vector<uint32_t> stop_ids;  // empty: every eos_token_id of config.json
-    std::function<float()> uniform;  // the draw in [0, 1) for each sampled token
-};
-
 // One request of LlmModel::generate_lanes: a prompt and the options generate() would take for it.
 struct LaneRequest {
     std::vector<uint32_t> prompt;
@@ -60,6 +49,7 @@ struct LaneRequest {
 
 struct LlmLaneState;  // llm_kernels.h
 struct LlmLookupState;
+struct SampleHeader;
 struct LlmKvCopyPair;
 
 // Prompt-lookup decoding: how the draft of a verify step is found in the sequence's own history.
@@ -70,6 +60,12 @@ struct LookupConfig {
 };
 struct LookupStats {  // over the steps the host consumed
     uint64_t verify_steps = 0, drafted_tokens = 0, accepted_tokens = 0, single_row_steps = 0;
+    void count(int rows, int drafted, int accepted)  // one consumed step of `rows` rows
+    {
+        ++(rows == 1 ? single_row_steps : verify_steps);
+        drafted_tokens += (uint64_t)drafted;
+        accepted_tokens += (uint64_t)accepted;
+    }
 };
 // The draft rule on a host-side history (what the device kernel computes): the tokens drafted after `tokens`.
 std::vector<uint32_t> lookup_draft_host(const uint32_t* tokens, size_t n, const LookupConfig& config);
@@ -232,7 +228,6 @@ private:
     void lane_step(int lanes);                 // enqueue one lock-step step over lanes [0, lanes)
     void lane_gemv(const struct LlmGemvArgs& a);
     hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
-    void drop_lane_graphs();
     void lane_state_to_device();
     void lane_state_from_device();
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
@@ -252,9 +247,19 @@ private:
     // [draft ->] verify pass -> rows penalty -> rows cut over `src` rows of stride vocab (the verify logits, or logits_ for one row)
     void enqueue_verify_sampled(int rows, const LookupConfig& config, const GenerateOptions& options, bool draft);
     hipGraphExec_t lookup_sampled_graph(int rows, const LookupConfig& config, const GenerateOptions& options);
-    void drop_lookup_sampled_graphs();
     void rows_cut(float* logits, int rows, const GenerateOptions& options);  // rows penalty + rows cut + the copy (no sync)
     uint32_t decide_row(const float* logits_dev, int row, const GenerateOptions& options, float uniform);
+    // One row's sampled token.  header (null: the cut was not attempted) and cand(i), candidate i of the row, are what the
+    // step's copy brought to the host: the first `first` candidates; fetch_rest(n) brings the others of the n there are.  When the
+    // candidates cannot decide, the row's processed logits come over from logits_dev and the full-array sampler runs.  Counts
+    // the token in tokens_from_candidates_ / tokens_from_logits_; *decided (may be null): which of the two.
+    template <class Cand, class FetchRest>
+    uint32_t sample_row(const SampleHeader* header, int first, int capacity, Cand&& cand, FetchRest&& fetch_rest, const float* logits_dev,
+                        const SamplingParams& params, float uniform, bool* decided);
+    // "The history so far": the counts and the distinct list of tokens_dev[0, n), which `host` (may be null: they are there)
+    // is uploaded to first.  Enqueued, not synchronised.
+    void begin_token_history(int32_t* tokens_dev, const uint32_t* host, size_t n, int* counts, int32_t* distinct, int* ndistinct);
+    void ensure_host_logits();  // the pinned row a logits fetch lands in
     void load_gpt2(SafeTensors& st, int weights);                      // GPT-2 tensors (Conv1D matrices transposed on the host)
     void finish_load();                                                // attention splits, workspace, stream
     // rows <= 8 through a quantized matrix; linear: a Q6_K matrix takes Q8_K activations (false: the tied head)
@@ -308,6 +313,8 @@ private:
     float* pw32_ = nullptr;    // f32 copy of the weight matrix a long prompt's GEMM is working on (bf16 checkpoints)
     float* psplit_ = nullptr;  // K-slice partial tiles of the prompt GEMMs (short prompts)
     float* host_logits_ = nullptr;  // pinned
+    std::vector<uint32_t> row_ids_, row_cids_;  // sample_row's scratch: the distribution's ids, the candidates' ids
+    std::vector<float> row_probs_, row_cvals_;  // ... and their probabilities / logits
     // sampled decoding on the device (allocated on first use): candidate header + list and its pinned mirror, the token
     // history with per-token counts and the list of distinct tokens (logits processors)
     static constexpr int kCandCap = 4096, kCandFirst = 512;

@@ -655,21 +655,10 @@ hipGraphExec_t WhisperModel::step_graph(bool timestamps)
 {
     hipGraphExec_t& exec = graphs_[timestamps ? 1 : 0];
     if (exec) return exec;
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
+    return exec = capture_graph(stream_, [&] {
         decoder_pass(reinterpret_cast<const uint32_t*>(dtoken_), 1, true);
         enqueue_pick(timestamps, true);
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return exec;
+    });
 }
 
 std::vector<uint32_t> WhisperModel::greedy(const std::vector<uint32_t>& prompt, bool timestamps, size_t max_tokens,
@@ -799,22 +788,11 @@ hipGraphExec_t WhisperModel::lane_step_graph(bool timestamps, int lanes)
 {
     hipGraphExec_t& exec = lane_graphs_[timestamps ? 1 : 0][lanes];
     if (exec) return exec;
-    hipGraph_t graph = nullptr;
-    hip_check(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal), "begin capture");
-    try {
+    return exec = capture_graph(stream_, [&] {
         decoder_pass_lanes(lanes, true);
         hip_check(launch_pick_token(lane_logits_, cfg_.vocab, (int)kFirstSpecial, (int)eos_, (int)kTimestampBegin, timestamps ? 1 : 0, lane_tokens_,
                                     lane_hist_, lane_counts_, dpos_, stream_, lanes, hist_cap_, drow_, dbest_), "pick token");
-    } catch (...) {
-        (void)hipStreamEndCapture(stream_, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-    }
-    hip_check(hipStreamEndCapture(stream_, &graph), "end capture");
-    const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    hip_check(e, "graph instantiate");
-    return exec;
+    });
 }
 
 std::vector<std::vector<uint32_t>> WhisperModel::greedy_lanes(int lanes, const std::vector<uint32_t>& prompt, bool timestamps, size_t max_tokens,

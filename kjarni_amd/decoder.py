@@ -23,6 +23,22 @@ def prefix_keep(resident: Sequence[int], prompt: Sequence[int], limit: int) -> i
     return int(keep.value)
 
 
+def generation_replay(n_prompt: int, capacity: int, max_new_tokens: int, stream: Sequence[int], max_len: int = 0,
+                      stop_ids: Sequence[int] = (), default_stop_ids: Sequence[int] = (), cancel_after: int = -1,
+                      feed_last: bool = False):
+    """The bookkeeping rule of the generation loops (no GPU) on a given token stream: (emitted, asked, fed) -- tokens emitted,
+    tokens taken from `stream` (the draws of a sampled loop), emitted tokens that are fed to another step.  stop_ids empty:
+    default_stop_ids; cancel_after k: the callback returns false at the k-th emitted token; feed_last: the last token of
+    max_new_tokens counts as fed (generate()'s processor / sampling loops) or not (the lanes)."""
+    arr = [np.ascontiguousarray(x, np.uint32) for x in (stop_ids, default_stop_ids, stream)]
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32)) if x.size else None  # noqa: E731
+    e, a, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    check_error(lib().kjarni_generation_replay(int(n_prompt), int(capacity), int(max_new_tokens), int(max_len), u32(arr[0]), arr[0].size,
+                                               u32(arr[1]), arr[1].size, u32(arr[2]), arr[2].size, int(cancel_after), int(bool(feed_last)),
+                                               C.byref(e), C.byref(a), C.byref(f)))
+    return int(e.value), int(a.value), int(f.value)
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
