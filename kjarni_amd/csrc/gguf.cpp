@@ -184,16 +184,16 @@ const char* ggml_type_name(uint32_t type)
     switch (type) {
     case GGML_F32: return "F32";
     case GGML_F16: return "F16";
-    case 2: return "Q4_0";
-    case 3: return "Q4_1";
-    case 6: return "Q5_0";
-    case 7: return "Q5_1";
+    case GGML_Q4_0: return "Q4_0";
+    case GGML_Q4_1: return "Q4_1";
+    case GGML_Q5_0: return "Q5_0";
+    case GGML_Q5_1: return "Q5_1";
     case GGML_Q8_0: return "Q8_0";
     case 9: return "Q8_1";
     case 10: return "Q2_K";
     case 11: return "Q3_K";
     case GGML_Q4_K: return "Q4_K";
-    case 13: return "Q5_K";
+    case GGML_Q5_K: return "Q5_K";
     case GGML_Q6_K: return "Q6_K";
     case 15: return "Q8_K";
     case GGML_BF16: return "BF16";
@@ -205,8 +205,13 @@ bool ggml_block_geometry(uint32_t type, int64_t* elems, int64_t* bytes)
 {
     switch (type) {
     case GGML_F32: *elems = 1; *bytes = 4; return true;
+    case GGML_Q4_0: *elems = 32; *bytes = 18; return true;
+    case GGML_Q4_1: *elems = 32; *bytes = 20; return true;
+    case GGML_Q5_0: *elems = 32; *bytes = 22; return true;
+    case GGML_Q5_1: *elems = 32; *bytes = 24; return true;
     case GGML_Q8_0: *elems = 32; *bytes = 34; return true;
     case GGML_Q4_K: *elems = 256; *bytes = 144; return true;
+    case GGML_Q5_K: *elems = 256; *bytes = 176; return true;
     case GGML_Q6_K: *elems = 256; *bytes = 210; return true;
     default: return false;
     }
@@ -235,6 +240,46 @@ void ggml_dequantize_row(uint32_t type, const uint8_t* src, int64_t n, float* ou
                 const float d1 = d * (float)s1, mn1 = dmin * (float)m1, d2 = d * (float)s2, mn2 = dmin * (float)m2;
                 for (int l = 0; l < 32; ++l) out[j * 64 + l] = d1 * (float)(qs[j * 32 + l] & 0xF) - mn1;
                 for (int l = 0; l < 32; ++l) out[j * 64 + 32 + l] = d2 * (float)(qs[j * 32 + l] >> 4) - mn2;
+            }
+        }
+        return;
+    case GGML_Q4_0:
+    case GGML_Q4_1:
+    case GGML_Q5_0:
+    case GGML_Q5_1: {
+        // d (, m) (, qh u32), qs[16]: element e < 16 is the low nibble of qs[e], element 16 + e the high one; bit e of qh is
+        // element e's fifth bit.  Every product is exact in f32, so each weight is rounded once (in the add) or not at all.
+        const bool has_m = type == GGML_Q4_1 || type == GGML_Q5_1, has_h = type == GGML_Q5_0 || type == GGML_Q5_1;
+        const int qh_at = has_m ? 4 : 2, qs_at = qh_at + (has_h ? 4 : 0), bytes = qs_at + 16;
+        const int off = has_m ? 0 : (has_h ? 16 : 8);
+        for (int64_t b = 0; b < n / 32; ++b, src += bytes, out += 32) {
+            const float d = half_to_f32(rd16(src)), m = has_m ? half_to_f32(rd16(src + 2)) : 0.0f;
+            uint32_t qh = 0;
+            if (has_h) std::memcpy(&qh, src + qh_at, 4);
+            const uint8_t* qs = src + qs_at;
+            for (int e = 0; e < 32; ++e) {
+                const int nib = e < 16 ? (qs[e] & 0xF) : (qs[e - 16] >> 4);
+                const int q = nib | (int)(((qh >> e) & 1u) << 4);
+                out[e] = has_m ? (float)q * d + m : (float)(q - off) * d;
+            }
+        }
+        return;
+    }
+    case GGML_Q5_K:
+        for (int64_t b = 0; b < n / 256; ++b, src += 176, out += 256) {
+            const float d = half_to_f32(rd16(src)), dmin = half_to_f32(rd16(src + 2));
+            const uint8_t *sc = src + 4, *qh = src + 16, *qs = src + 48;
+            for (int j = 0; j < 4; ++j) {
+                uint8_t s1, m1, s2, m2;
+                scale_min_k4(2 * j, sc, &s1, &m1);
+                scale_min_k4(2 * j + 1, sc, &s2, &m2);
+                const float d1 = d * (float)s1, mn1 = dmin * (float)m1, d2 = d * (float)s2, mn2 = dmin * (float)m2;
+                for (int l = 0; l < 32; ++l) {
+                    const int lo = (qs[j * 32 + l] & 0xF) | (((qh[l] >> (2 * j)) & 1) << 4);
+                    const int hi = (qs[j * 32 + l] >> 4) | (((qh[l] >> (2 * j + 1)) & 1) << 4);
+                    out[j * 64 + l] = d1 * (float)lo - mn1;
+                    out[j * 64 + 32 + l] = d2 * (float)hi - mn2;
+                }
             }
         }
         return;
@@ -429,7 +474,7 @@ const GgufTensor& GgufFile::get_hf(const std::string& hf_name) const
     if (!t) throw std::runtime_error("GGUF: tensor " + to_gguf_name(hf_name) + " (" + hf_name + ") not found in " + path_);
     if (!t->data)
         throw std::runtime_error("GGUF: tensor " + t->name + " has unsupported type " + ggml_type_name(t->type) + " (" +
-                                 std::to_string(t->type) + "); F32, Q8_0, Q4_K and Q6_K are supported");
+                                 std::to_string(t->type) + "); F32, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K and Q6_K are supported");
     return *t;
 }
 

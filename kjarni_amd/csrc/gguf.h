@@ -3,7 +3,8 @@
 //
 //   header      magic "GGUF", version 3, tensor count, metadata count; every metadata value type parses (arrays of
 //               strings included), general.alignment (default 32) places the data section
-//   tensors     name, ne[] (ne[0] = columns), ggml type, offset into the data section; F32 + Q8_0 / Q4_K / Q6_K matrices
+//   tensors     name, ne[] (ne[0] = columns), ggml type, offset into the data section; F32 + Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 /
+//               Q4_K / Q5_K / Q6_K matrices
 //   names       HF names map to GGUF names as gguf_loader.rs:151-187 (+ blk.N.attn_{q,k,v}.bias for Qwen2)
 //   Q/K rows    arch `llama`: llama.cpp's converter interleaved the rows of every head of attn_q / attn_k; rows() undoes it
 //               per head_dim for every type (HF row r < d/2 <- GGUF row 2r, r >= d/2 <- 2(r - d/2) + 1)
@@ -18,7 +19,10 @@
 
 namespace kjarni {
 
-enum GgmlType : uint32_t { GGML_F32 = 0, GGML_F16 = 1, GGML_Q8_0 = 8, GGML_Q4_K = 12, GGML_Q6_K = 14, GGML_BF16 = 30 };
+enum GgmlType : uint32_t {
+    GGML_F32 = 0, GGML_F16 = 1, GGML_Q4_0 = 2, GGML_Q4_1 = 3, GGML_Q5_0 = 6, GGML_Q5_1 = 7, GGML_Q8_0 = 8, GGML_Q4_K = 12, GGML_Q5_K = 13,
+    GGML_Q6_K = 14, GGML_BF16 = 30
+};
 
 const char* ggml_type_name(uint32_t type);
 float f16_to_f32(uint16_t h);
@@ -26,7 +30,8 @@ void q4k_scale_min(int j, const uint8_t* scales, uint8_t* sc, uint8_t* m);  // g
 // Elements per block and bytes per block of a supported type (F32: 1 / 4); false for any other type.
 bool ggml_block_geometry(uint32_t type, int64_t* elems, int64_t* bytes);
 // Dequantizes n elements (n a multiple of the block size) of one row, with the reference's arithmetic
-// (cpu/kernels/dequantize.rs:5-62).
+// (cpu/kernels/dequantize.rs:5-62).  Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K are unknown to the reference; the GGUF format defines
+// them: w = (q - 8) d, q d + m, (q - 16) d, q d + m, (d sc) q - dmin m, each the f32 nearest to the exact value.
 void ggml_dequantize_row(uint32_t type, const uint8_t* src, int64_t n, float* out);
 
 struct GgufTensor {
