@@ -490,7 +490,11 @@ KjarniErrorCode kjarni_audio_load_wav(const char* path, KjarniFloatArray* out, u
 KjarniErrorCode kjarni_bytelevel_decode(const char* tokenizer_json_path, const uint32_t* ids, size_t n, int32_t skip_special,
                                         char** out);
 
-/* ---- decoder-only generation (Llama / Qwen2 / Mistral layouts and GPT-2), token level ----------------------------
+/* ---- decoder-only generation (Llama / Qwen2 / Qwen3 / Mistral layouts and GPT-2), token level --------------------
+ * Qwen3 (model_type "qwen3", safetensors only; a GGUF of that architecture is refused): `head_dim` is read from config.json and
+ * heads * head_dim may differ from hidden_size; every layer carries self_attn.q_norm.weight and self_attn.k_norm.weight
+ * [head_dim], the per-head RMSNorm applied to Q and K before RoPE (a file without one is a load error naming it).  It runs
+ * through every entry point below; the one-token step takes six launches per layer against Llama's five.
  * model_dir: config.json (crates/kjarni-models/src/models/llama/config.rs:98-158, qwen/config.rs:80-125) and
  * model.safetensors with the HF tensor names of llama/config.rs:283-330.  weights_dtype: 0 = as stored (BF16 stays
  * bf16 in HBM, other dtypes are widened to f32), 1 = f32, 2 = bf16 (f32 rounded to nearest even).  Arithmetic,
@@ -510,7 +514,8 @@ uint64_t kjarni_hip_decoder_tile_gemm_calls(const KjarniHipDecoder* decoder);
 void kjarni_hip_decoder_set_device_sampling(KjarniHipDecoder* decoder, int32_t on);
 /* Positions held in the KV cache (0 on NULL). */
 int32_t kjarni_hip_decoder_cache_len(const KjarniHipDecoder* decoder);
-/* Cache rows [first, first + rows) of one layer, a read-back for tests: k_out (after RoPE) and v_out each receive f32
+/* Cache rows [first, first + rows) of one layer, a read-back for tests: k_out (after RoPE; Qwen3: after the head norm and
+ * RoPE) and v_out each receive f32
  * [rows, num_key_value_heads * head_dim].  An error, with nothing copied, for a layer out of range or
  * first + rows > cache_len. */
 KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder* decoder, int32_t layer, int32_t first, int32_t rows, float* k_out,
@@ -782,6 +787,16 @@ KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDecoder* decoder
  * destination cache starts src_skew / dst_skew floats (0..3) past a 16-byte boundary.  Out-of-range arguments: INVALID_CONFIG. */
 KjarniErrorCode kjarni_hip_op_kv_prefix_copy(int32_t device, const float* src, int32_t layers, int64_t src_floats, int32_t src_skew,
                                              int64_t dst_floats, int32_t dst_skew, int64_t dst_offset, int64_t count, float* dst);
+/* Qwen3's per-head RMSNorm + RoPE kernel alone, host pointers: q [q_rows, ldq] and k [k_rows, ldk] are read, `rows` rows are
+ * processed in place and both arrays are written back whole.  Row r sits at position pos + r (pos travels in device memory when
+ * pos_on_device, as in the captured step); every head vector x [head_dim] of its n_heads Q heads (row r of q) and n_kv_heads K
+ * heads (row pos + r of k when k_at_cache_row, else row r) becomes (x / sqrt(mean(x^2) + eps)) * gamma, then its pairs
+ * (i, i + head_dim / 2) are rotated by row pos + r of cos_t / sin_t [table_rows, head_dim / 2].  Out-of-range arguments:
+ * INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_qk_norm_rope(int32_t device, float* q, int64_t ldq, int32_t q_rows, float* k, int64_t ldk, int32_t k_rows,
+                                           int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* gamma_q,
+                                           const float* gamma_k, float eps, const float* cos_t, const float* sin_t, int32_t table_rows,
+                                           int32_t pos, int32_t pos_on_device, int32_t k_at_cache_row);
 /* The switch and the counters on the Chat and Generator handles' models (send, generate, score and generate_batch take it). */
 KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);

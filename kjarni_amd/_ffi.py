@@ -506,6 +506,8 @@ SIGNATURES = {
                                            c_int64, c_int32, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]),
     "kjarni_hip_decoder_lane_prefill_shared": (c_int32, [c_void_p, c_int32, c_int32, _u32p, c_int32]),
     "kjarni_hip_op_kv_prefix_copy": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, c_int64, c_int32, c_int64, c_int64, _f32p]),
+    "kjarni_hip_op_qk_norm_rope": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             _f32p, _f32p, c_float, _f32p, _f32p, c_int32, c_int32, c_int32, c_int32]),
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),

@@ -219,7 +219,7 @@ GenerationConfig model_default_generation_config(const std::string& model_type, 
         c.top_k = Opt<size_t>(40);
         c.top_p = Opt<float>(0.9f);
         c.min_p = Opt<float>(0.05f);
-    } else if (model_type == "qwen2") {  // qwen/model.rs:267-281
+    } else if (model_type == "qwen2" || model_type == "qwen3") {  // qwen/model.rs:267-281 (Qwen3: the Qwen2 block)
         c.max_new_tokens = Opt<size_t>(512);
         c.repetition_penalty = 1.1f;
         c.add_bos_token = false;
@@ -246,7 +246,7 @@ namespace {
 struct ChatModelInfo {
     const char* cli_name;
     const char* arch;     // ModelArchitecture::display_name
-    const char* family;   // llama | qwen2 | mistral | phi3 | gpt | encoder | whisper | seq2seq
+    const char* family;   // llama | qwen2 | qwen3 | mistral | phi3 | gpt | encoder | whisper | seq2seq
     const char* task;     // format!("{:?}", task).to_lowercase()
 };
 // registry.rs ModelType::info(): architecture and task of every registry entry.
@@ -265,6 +265,10 @@ const ChatModelInfo kChatModels[] = {
     {"toxic-bert", "BERT", "encoder", "classification"},
     {"qwen2.5-0.5b-instruct", "Qwen2 (Biased)", "qwen2", "chat"},
     {"qwen2.5-1.5b", "Qwen2 (Biased)", "qwen2", "chat"},
+    {"qwen3-0.6b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
+    {"qwen3-1.7b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
+    {"qwen3-4b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
+    {"qwen3-8b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
     {"llama3.2-1b-instruct", "Llama (Standard)", "llama", "chat"},
     {"llama3.2-3b-instruct", "Llama (Standard)", "llama", "chat"},
     {"phi3.5-mini", "Phi-3 (LongRoPE)", "phi3", "reasoning"},
@@ -411,7 +415,7 @@ std::unique_ptr<Chat> Chat::create(const std::string& model_name, const std::str
 
     std::unique_ptr<Chat> chat(new Chat());
     chat->model_name_ = cli;
-    chat->template_ = family == "qwen2" ? ChatTemplateKind::ChatML : (family == "mistral" ? ChatTemplateKind::Mistral : ChatTemplateKind::Llama3);
+    chat->template_ = (family == "qwen2" || family == "qwen3") ? ChatTemplateKind::ChatML : (family == "mistral" ? ChatTemplateKind::Mistral : ChatTemplateKind::Llama3);
     chat->mode_ = mode;
     if (system_prompt) {
         chat->has_system_ = true;

@@ -636,6 +636,44 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_kv_prefix_copy(int32_t device, const
     });
 }
 
+// Qwen3's per-head RMSNorm + RoPE kernel alone, on arrays given by the host: q [q_rows, ldq] and k [k_rows, ldk] are read,
+// run through launch_qk_norm_rope for `rows` rows at base position `pos` (handed over in device memory when pos_on_device,
+// as the captured step does) and written back whole, so a caller can check what the call left untouched.  cos_t / sin_t are
+// [table_rows, head_dim / 2].
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qk_norm_rope(int32_t device, float* q, int64_t ldq, int32_t q_rows, float* k, int64_t ldk,
+                                                         int32_t k_rows, int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
+                                                         const float* gamma_q, const float* gamma_k, float eps, const float* cos_t,
+                                                         const float* sin_t, int32_t table_rows, int32_t pos, int32_t pos_on_device,
+                                                         int32_t k_at_cache_row)
+{
+    if (!q || !k || !gamma_q || !gamma_k || !cos_t || !sin_t) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (head_dim < 2 || head_dim > 128 || (head_dim & 1) || n_heads < 1 || n_heads > 1024 || n_kv_heads < 1 || n_kv_heads > 1024)
+            throw InvalidConfig("invalid head geometry (head_dim even, 2..128; heads and kv heads 1..1024)");
+        if (rows < 1 || rows > q_rows || ldq < (int64_t)n_heads * head_dim || ldk < (int64_t)n_kv_heads * head_dim)
+            throw InvalidConfig("rows / leading dimensions do not cover the heads");
+        if (pos < 0 || table_rows < 1 || rows > table_rows - pos) throw InvalidConfig("positions reach outside the RoPE tables");
+        if (k_at_cache_row ? (k_rows < 1 || rows > k_rows - pos) : rows > k_rows) throw InvalidConfig("K rows reach outside k");
+        use_device(device);
+        const size_t qb = (size_t)q_rows * (size_t)ldq * 4, kb = (size_t)k_rows * (size_t)ldk * 4, tb = (size_t)table_rows * (head_dim / 2) * 4;
+        DeviceBuf qd(qb), kd(kb), gq((size_t)head_dim * 4), gk((size_t)head_dim * 4), cd(tb), sd(tb), pd(sizeof(int));
+        hip_check(hipMemcpy(qd.p, q, qb, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, kb, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(gq.p, gamma_q, (size_t)head_dim * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(gk.p, gamma_k, (size_t)head_dim * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(cd.p, cos_t, tb, hipMemcpyHostToDevice), "H2D cos");
+        hip_check(hipMemcpy(sd.p, sin_t, tb, hipMemcpyHostToDevice), "H2D sin");
+        hip_check(hipMemcpy(pd.p, &pos, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
+        // (the device-held position wins inside the kernel: the host argument is then a value the result must not depend on)
+        hip_check(launch_qk_norm_rope((float*)qd.p, ldq, (float*)kd.p, ldk, rows, n_heads, n_kv_heads, head_dim, (const float*)gq.p,
+                                      (const float*)gk.p, eps, (const float*)cd.p, (const float*)sd.p, pos_on_device ? 0 : pos,
+                                      pos_on_device ? (const int*)pd.p : nullptr, k_at_cache_row, nullptr), "qk norm + rope");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(q, qd.p, qb, hipMemcpyDeviceToHost), "D2H q");
+        hip_check(hipMemcpy(k, kd.p, kb, hipMemcpyDeviceToHost), "D2H k");
+    });
+}
+
 // The greedy pick kernels alone, on logits given by the host: `calls` independent picks over logits [calls, rows, ld], each
 // through the launcher the models use, on one scratch (which every call must leave zeroed for the next).
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_argmax(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld, int32_t vocab,

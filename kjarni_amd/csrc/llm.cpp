@@ -40,8 +40,8 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         return (int)v->as_int();
     };
     c.model_type = j.get_string("model_type", "llama");
-    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "mistral" && c.model_type != "gpt2")
-        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2, mistral and gpt2 are)");
+    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "qwen3" && c.model_type != "mistral" && c.model_type != "gpt2")
+        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2, qwen3, mistral and gpt2 are)");
     auto ids = [&] {  // eos / bos as for every type
         if (const Json* e = j.find("eos_token_id")) {
             if (e->is_number()) c.eos_ids.push_back((uint32_t)e->as_int());
@@ -102,7 +102,8 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         c.rope_original_max = (int)rs->get_int("original_max_position_embeddings", 8192);
     }
     ids();
-    if (c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.head_dim * c.heads != c.hidden)
+    // Qwen3 sets head_dim apart from hidden / heads (0.6B: 16 heads x 128 over a hidden size of 1024); the others may not
+    if (c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.head_dim <= 0 || (!c.qwen3() && c.head_dim * c.heads != c.hidden))
         throw std::runtime_error("config.json: unsupported head geometry");
     return c;
 }
@@ -167,7 +168,7 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     }
     m->cfg_ = LlmConfig::from_json(m->config_json_);
     const LlmConfig& c = m->cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     if ((d & 3) || d > 128 || 256 % (d / 4) != 0 || (H & 7) || (c.inter & 7)) throw std::runtime_error("unsupported decoder geometry");
     auto contains = [&](const std::string& name) { return is_gguf ? gf.find_hf(name) != nullptr : st.contains(name); };
     if (is_gguf) {
@@ -237,7 +238,7 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         L.wqkv = L.wo = L.gate = L.up = L.down = nullptr;
         std::vector<float> w, b;
         bool any_bias = false;
-        for (const auto& nm : {std::make_pair(std::string("q_proj"), H), std::make_pair(std::string("k_proj"), kv),
+        for (const auto& nm : {std::make_pair(std::string("q_proj"), QD), std::make_pair(std::string("k_proj"), kv),
                                std::make_pair(std::string("v_proj"), kv)}) {
             if (m->quant_) {
                 QMat& q = nm.first == "q_proj" ? L.q : (nm.first == "k_proj" ? L.k : L.v);
@@ -263,7 +264,7 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
             L.down_q = upload_q(p + ".mlp.down_proj.weight", H, c.inter);
         } else {
             L.wqkv = m->upload_weight(w);
-            get(p + ".self_attn.o_proj.weight", {H, H});
+            get(p + ".self_attn.o_proj.weight", {H, QD});
             L.wo = m->upload_weight(buf);
             get(p + ".mlp.gate_proj.weight", {c.inter, H});
             L.gate = m->upload_weight(buf);
@@ -276,6 +277,14 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         L.ln1 = m->upload_f32(buf);
         get(p + ".post_attention_layernorm.weight", {H});
         L.ln2 = m->upload_f32(buf);
+        if (c.qwen3()) {  // per-head RMSNorm weights of Q and K, [head_dim] each
+            for (const char* nm : {"q_norm", "k_norm"}) {
+                const std::string name = p + ".self_attn." + nm + ".weight";
+                if (!contains(name)) throw std::runtime_error("missing tensor " + name);
+                get(name, {d});
+                (nm[0] == 'q' ? L.q_norm : L.k_norm) = m->upload_f32(buf);
+            }
+        }
         L.k_cache = m->dalloc((size_t)m->cache_cap_ * kv);
         L.v_cache = m->dalloc((size_t)m->cache_cap_ * kv);
     }
@@ -341,14 +350,14 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
 void LlmModel::finish_load()
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim;
+    const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
     // key ranges per head: up to 512 keys each (128 of them are one register-held pass of the attention kernel); few enough
     // that the output projection can merge the slabs itself
     splits_ = std::max(1, std::min(64, (cache_cap_ + 511) / 512));
     while ((cache_cap_ + splits_ - 1) / splits_ > 512) ++splits_;
     h_ = dalloc(8 * (size_t)H);
-    q_ = dalloc(8 * (size_t)H);
-    ctx_ = dalloc(8 * (size_t)H);
+    q_ = dalloc(8 * (size_t)QD);
+    ctx_ = dalloc(8 * (size_t)QD);
     last_ = dalloc(8 * (size_t)H);
     mid_ = dalloc(8 * (size_t)c.inter);
     if (quant_) {
@@ -499,7 +508,7 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
     const int* pp = device_pos ? pos_ : nullptr;
     if (quant_) {
         pass_quant(ids_dev, n, device_pos, verify);
@@ -514,12 +523,13 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
         else hip_check(launch_llm_gemv(a, s), what);
     };
     const bool one = n == 1 && !verify;  // the one-token fusions
+    const bool qk_norm = c.qwen3();      // Q and K are normalised per head between projection and rotation: no fused Q|K|V + RoPE launch
     // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
-    const bool embed_in_qkv = one && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
+    const bool embed_in_qkv = one && !qk_norm && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
     if (!embed_in_qkv) hip_check(launch_llm_embed(ids_dev, n, H, c.vocab, embed_, bf16_ ? 1 : 0, h_, s), "embed");
     bool first_layer = true;
     for (const Layer& L : layers_) {
-        if (one && H <= 8192) {  // decode step: norm + projection + rotation in one launch
+        if (one && !qk_norm && H <= 8192) {  // decode step: norm + projection + rotation in one launch
             const bool emb = embed_in_qkv && first_layer;
             hip_check(launch_llm_qkv_rope(h_, L.ln1, c.eps, L.wqkv, bf16_ ? 1 : 0, L.bqkv, H, c.heads, c.kv_heads, d, cos_, sin_, q_,
                                           L.k_cache, L.v_cache, cache_len_, pp, s, emb ? ids_dev : nullptr, emb ? embed_ : nullptr,
@@ -528,18 +538,23 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
         } else {
         LlmGemvArgs a;  // RMSNorm + Q | K | V (decoder_attention.rs:61-82): K / V rows land in the cache
         a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_; a.bias = L.bqkv;
-        a.n_out = H + 2 * kv; a.k = H; a.seg_q = H; a.seg_kv = kv; a.Y0 = q_; a.ldy0 = H; a.Y1 = L.k_cache; a.Y2 = L.v_cache; a.ldy12 = kv;
+        a.n_out = QD + 2 * kv; a.k = H; a.seg_q = QD; a.seg_kv = kv; a.Y0 = q_; a.ldy0 = QD; a.Y1 = L.k_cache; a.Y2 = L.v_cache; a.ldy12 = kv;
         a.row_off = cache_len_; a.row_off_ptr = pp;
         gemv(a, "norm + qkv");
-        hip_check(launch_rope(q_, H, n, c.heads, d, cos_, sin_, cache_len_, pp, 0, s), "rope q");
+        if (qk_norm) {  // Qwen3: head norm + rotation of the Q row(s) and of the K rows where they sit in the cache, one launch
+            hip_check(launch_qk_norm_rope(q_, QD, L.k_cache, kv, n, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_, pp,
+                                          1, s), "qk norm + rope");
+        } else {
+        hip_check(launch_rope(q_, QD, n, c.heads, d, cos_, sin_, cache_len_, pp, 0, s), "rope q");
         hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pp, 1, s), "rope k");
         }
+        }
         // one token: the output projection merges the attention's per-split slabs itself (no combine launch)
-        const bool merge_in_proj = one && c.heads * d == H && llm_gemv_merges_attention(H, splits_, d);
-        hip_check(launch_decode_attention(q_, H, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
-                                          splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, H, s, c.heads / c.kv_heads), "attention");
+        const bool merge_in_proj = one && llm_gemv_merges_attention(QD, splits_, d);
+        hip_check(launch_decode_attention(q_, QD, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
+                                          splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, QD, s, c.heads / c.kv_heads), "attention");
         LlmGemvArgs o;
-        o.X = ctx_; o.ldx = H; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.R = h_; o.ldr = H; o.n_out = H; o.k = H; o.Y0 = h_; o.ldy0 = H;
+        o.X = ctx_; o.ldx = QD; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.R = h_; o.ldr = H; o.n_out = H; o.k = QD; o.Y0 = h_; o.ldy0 = H;
         if (merge_in_proj) {
             o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
         }
@@ -694,7 +709,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
     const int wb = bf16_ ? 1 : 0;
     constexpr int kChunk = 2048;
     constexpr int kTileRows = 512;  // rows from which a projection may take the encoder's 128 x 128-tile f32 GEMM (if its tiles fill the chip)
@@ -703,13 +718,13 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
         const size_t P = (size_t)prefill_cap_;
         ph_ = dalloc(P * H);
         pn_ = dalloc(P * H);
-        pq_ = dalloc(P * H);
-        pctx_ = dalloc(P * H);
+        pq_ = dalloc(P * QD);
+        pctx_ = dalloc(P * QD);
         pg_ = dalloc(P * I);
         pu_ = dalloc(P * I);
         pids_ = reinterpret_cast<uint32_t*>(dalloc(P));
-        psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, H)));
-        if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(H + 2 * kv) * H, (size_t)I * H));
+        psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, std::max(H, QD))));
+        if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(QD + 2 * kv) * H, (size_t)I * H));
         if (quant_) pact_ = dalloc(P * (size_t)std::max(H, I));
     }
     const size_t wsz = bf16_ ? 2 : 4;
@@ -725,7 +740,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
         // at 2 048 rows).  Measured on the 1B shape: 2 048 rows 46.2 -> 42.6 ms, 1 792 rows 40.4 -> 39.1 ms, 1 536 rows 33.1 -> 36.1 ms
         // (the 2 048-wide projections are then 192 tiles on 256 CUs): hence kTileRows.
         // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
-        const bool tile_shapes = H % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
+        const bool tile_shapes = H % 128 == 0 && QD % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
         // gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
         auto proj = [&](const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
                         float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false) {
@@ -781,27 +796,30 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
             float* v_rows = L.v_cache + (size_t)cache_len_ * kv;
             if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
             else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-            proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, H, H, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
-            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)H * H), L.bqkv ? L.bqkv + H : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj",
+            proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
+            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj",
                  quant_ ? &L.k : nullptr);
-            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(H + kv) * H), L.bqkv ? L.bqkv + H + kv : nullptr, nullptr, v_rows, kv, kv, H,
+            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, v_rows, kv, kv, H,
                  nullptr, "v proj", quant_ ? &L.v : nullptr);
-            if (!gpt2_) {  // (GPT-2: learned positions, already in the embedding)
-                hip_check(launch_rope(pq_, H, m, c.heads, d, cos_, sin_, cache_len_, nullptr, 0, s), "rope q");
+            if (c.qwen3()) {  // head norm + rotation over the chunk's Q rows and its K rows in the cache
+                hip_check(launch_qk_norm_rope(pq_, QD, L.k_cache, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_,
+                                              nullptr, 1, s), "qk norm + rope");
+            } else if (!gpt2_) {  // (GPT-2: learned positions, already in the embedding)
+                hip_check(launch_rope(pq_, QD, m, c.heads, d, cos_, sin_, cache_len_, nullptr, 0, s), "rope q");
                 hip_check(launch_rope(L.k_cache, kv, m, c.kv_heads, d, cos_, sin_, cache_len_, nullptr, 1, s), "rope k");
             }
             if (prefill_attention_supported(d)) {
-                hip_check(launch_prefill_attention(pq_, H, m, L.k_cache, kv, L.v_cache, kv, cache_len_, c.heads, d, c.heads / c.kv_heads, pctx_, H, s),
+                hip_check(launch_prefill_attention(pq_, QD, m, L.k_cache, kv, L.v_cache, kv, cache_len_, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
                           "attention");
             } else {
                 for (int r = 0; r < m; r += 8) {  // 8 query rows at a time against everything cached up to them
                     const int rows = std::min(8, m - r);
-                    hip_check(launch_decode_attention(pq_ + (size_t)r * H, H, rows, L.k_cache, kv, L.v_cache, kv, cache_len_ + r + rows, nullptr,
-                                                      cache_cap_, c.heads, d, cache_len_ + r, splits_, att_scratch_, pctx_ + (size_t)r * H, H, s,
+                    hip_check(launch_decode_attention(pq_ + (size_t)r * QD, QD, rows, L.k_cache, kv, L.v_cache, kv, cache_len_ + r + rows, nullptr,
+                                                      cache_cap_, c.heads, d, cache_len_ + r, splits_, att_scratch_, pctx_ + (size_t)r * QD, QD, s,
                                                       c.heads / c.kv_heads), "attention");
                 }
             }
-            proj(pctx_, H, L.wo, L.bo, ph_, ph_, H, H, H, nullptr, "o proj", quant_ ? &L.o : nullptr);
+            proj(pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj", quant_ ? &L.o : nullptr);
             if (gpt2_) {
                 hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
                 proj(pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
@@ -852,7 +870,7 @@ void LlmModel::forward_rows(const uint32_t* ids, int n, bool score, int score_ba
     const bool tracked = resident_.size() == (size_t)cache_len_;  // (else: untracked rows lie between; resident_ stays a prefix)
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
     const int kvd = cfg_.kv_heads * cfg_.head_dim;
-    if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
+    if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.q_dim() % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
         prefill_rows(ids, n, score, score_base);
     } else {
         for (int i = 0; i < n; i += 8) {
@@ -1259,7 +1277,7 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
         lane_ptok_ = reinterpret_cast<int32_t*>(at + (size_t)kLanes * stride);
         lane_pdistinct_ = reinterpret_cast<int32_t*>(at + 2 * (size_t)kLanes * stride);
         if (!lane_qkv_) {
-            lane_qkv_ = dalloc((size_t)kLanes * (c.hidden + 2 * kv));
+            lane_qkv_ = dalloc((size_t)kLanes * (c.q_dim() + 2 * kv));
             lane_logits_ = dalloc((size_t)kLanes * c.vocab);
             lane_state_ = reinterpret_cast<LlmLaneState*>(dalloc((sizeof(LlmLaneState) + 3) / 4));
             lane_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kLanes));
@@ -1385,8 +1403,8 @@ void LlmModel::lane_step(int n)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, I = c.inter;
-    const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = H + 2 * kv;
+    const int H = c.hidden, d = c.head_dim, I = c.inter, QD = c.q_dim();
+    const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
     const int64_t stride = (int64_t)lane_alloc_cap_ * kv;
     const LlmLaneState* st = lane_state_;
     const uint32_t* toks = reinterpret_cast<const uint32_t*>(st->token);
@@ -1423,10 +1441,14 @@ void LlmModel::lane_step(int n)
             a.bf16 = wb; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = lane_qkv_; a.ldy0 = ldq;
             lane_gemv(a);
         }
+        if (c.qwen3())
+            hip_check(launch_lane_qk_norm_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, lane_k_[li],
+                                                       lane_v_[li], stride, lane_cap_, st, s), "head norm + rotate + scatter");
+        else
         hip_check(launch_lane_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, cos_, sin_, lane_k_[li], lane_v_[li], stride, lane_cap_, st,
                                            gpt2_ ? 0 : 1, s), "rotate + scatter");
         hip_check(launch_decode_attention(lane_qkv_, ldq, n, lane_k_[li], kv, lane_v_[li], kv, lane_cap_, nullptr, lane_cap_, c.heads, d, -1,
-                                          splits_, att_scratch_, ctx_, H, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
+                                          splits_, att_scratch_, ctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
         if (quant_) {
             QFusedArgs o;
             qsource(o, ctx_, H, H, nullptr, q6(L.o), "q8k o");
@@ -1444,7 +1466,7 @@ void LlmModel::lane_step(int n)
             continue;
         }
         LlmGemvArgs o;
-        o.X = ctx_; o.ldx = H; o.rows = n; o.W = L.wo; o.bf16 = wb; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = H; o.Y0 = h_; o.ldy0 = H;
+        o.X = ctx_; o.ldx = QD; o.rows = n; o.W = L.wo; o.bf16 = wb; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = QD; o.Y0 = h_; o.ldy0 = H;
         lane_gemv(o);
         LlmGemvArgs g;
         g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.bf16 = wb; g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;

@@ -1,5 +1,7 @@
-// LlmModel: a decoder-only transformer (Llama / Qwen2 / Mistral layouts, and GPT-2) resident in HBM with an f32 KV cache,
-// and the generation loop.
+// LlmModel: a decoder-only transformer (Llama / Qwen2 / Qwen3 / Mistral layouts, and GPT-2) resident in HBM with an f32 KV cache,
+// and the generation loop.  Qwen3 (safetensors only; a GGUF of that architecture is refused): Q and K are RMS-normalised per
+// head before RoPE (launch_qk_norm_rope, one launch more per layer than the Llama step), there are no Q/K/V biases, and
+// head_dim comes from the config, so the query / context width q_dim() = heads * head_dim may differ from hidden.
 //
 //   config + tensor names   crates/kjarni-models/src/models/llama/config.rs:98-330, qwen/config.rs:80-275
 //   layer                   crates/kjarni-transformers/src/cpu/decoder/rope_decoder_layer.rs:18-41
@@ -38,6 +40,8 @@ struct LlmConfig {
     bool has_bos = false;
     uint32_t bos_id = 0;
     bool gpt2() const { return model_type == "gpt2"; }  // LayerNorm + biases, GELU MLP, learned positions, head tied to wte
+    bool qwen3() const { return model_type == "qwen3"; }  // per-head RMSNorm of Q and K before RoPE; head_dim set apart from hidden / heads
+    int q_dim() const { return heads * head_dim; }  // the width of Q and of the attention's context rows (== hidden except for Qwen3)
     static LlmConfig from_json(const std::string& text);
 };
 
@@ -134,7 +138,8 @@ public:
     // Head launches of score() by route since load.
     uint64_t score_fused_calls() const { return score_fused_calls_; }
     uint64_t score_rows_calls() const { return score_rows_calls_; }
-    // Cache rows [first, first + rows) of one layer, K after RoPE and V, f32 [rows, kv_heads * head_dim] each (a test hook).
+    // Cache rows [first, first + rows) of one layer, K after RoPE (Qwen3: after the head norm and RoPE) and V, f32
+    // [rows, kv_heads * head_dim] each (a test hook).
     void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
     void last_hidden(float* out, int rows) const;  // final-normed hidden states of the last (<= 8-row) pass
     void logits_to_host(float* out) const;
@@ -278,6 +283,7 @@ private:
     struct Layer {
         void *wqkv, *wo, *gate, *up, *down;  // GPT-2: c_attn, attn.c_proj, mlp.c_fc (in `gate`), mlp.c_proj (in `down`), as [out, in]
         float *bqkv, *ln1, *ln2;
+        float *q_norm = nullptr, *k_norm = nullptr;  // Qwen3: per-head RMSNorm weights [head_dim]
         float *ln1_b = nullptr, *ln2_b = nullptr, *bo = nullptr, *bfc = nullptr, *bdown = nullptr;  // GPT-2's LayerNorm and projection biases
         float *k_cache, *v_cache;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)

@@ -74,6 +74,13 @@ hipError_t launch_swiglu_mul(float* gate, const float* up, size_t n, hipStream_t
 hipError_t launch_rope(float* x, int64_t ldx, int rows, int n_heads, int head_dim, const float* cos_t, const float* sin_t, int pos,
                        const int* pos_ptr, int at_cache_row, hipStream_t stream);
 hipError_t launch_rmsnorm(const float* x, const float* gamma, float eps, int rows, int hidden, float* out, hipStream_t stream);
+// Qwen3: per-head RMSNorm + RoPE in place, Q heads and K heads in one launch.  Row r sits at position p = (*pos_ptr | pos) + r
+// (pos_ptr is read on the device: graph replay); each head vector x [head_dim] becomes (x / sqrt(mean(x^2) + eps)) * gamma,
+// then its pairs (i, i + head_dim/2) are rotated by row p of the tables.  Q row r is row r of q; K row r is row p of k when
+// k_at_cache_row, else row r.  gamma_q / gamma_k are [head_dim]; head_dim even and <= 128 (one wave per head).
+hipError_t launch_qk_norm_rope(float* q, int64_t ldq, float* k, int64_t ldk, int rows, int n_heads, int n_kv_heads, int head_dim,
+                               const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t, int pos,
+                               const int* pos_ptr, int k_at_cache_row, hipStream_t stream);
 hipError_t launch_llm_embed(const uint32_t* ids, int n, int hidden, int vocab, const void* table, int bf16, float* out,
                             hipStream_t stream);
 // GPT-2: out[s] = table[ids[s]] + pos_table[p + s] for n rows, p = *pos_ptr when pos_ptr is non-null (graph replay), else pos;
@@ -109,6 +116,11 @@ hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& args, hipStream_t stream, in
 hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
                                     const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
                                     const LlmLaneState* state, int rotate, hipStream_t stream);
+// The same for Qwen3: Q and K are RMS-normalised per head (gamma_q / gamma_k [head_dim], eps) before the rotation.
+hipError_t launch_lane_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
+                                            const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
+                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmLaneState* state,
+                                            hipStream_t stream);
 // Per-lane argmax over rows [first_lane, first_lane + lanes) of logits [kMaxLanes, ld] (last maximum wins) for the live lanes:
 // appended to history[lane, count], count (and pos when `advance`: after a step) + 1, live cleared on a stop id / the limit /
 // a full cache, else token = the pick.  best_scratch: kMaxLanes zero-initialised u64 (re-zeroed by the call).

@@ -2581,6 +2581,103 @@ hipError_t launch_kv_prefix_copy(const LlmKvCopyPair* table, int layers, int64_t
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Qwen3: Q and K are RMS-normalised per head before the rotation.  One wave per (row, head); lane i < d/2 holds x[i] and
+// x[i + d/2] (the lanes past d/2 hold zeros), so the sum of squares is one wave_sum, the rotation pairs sit in one lane, and
+// there is no LDS and no barrier.  Arithmetic of rmsnorm_kernel ((x / sqrt(mean(x^2) + eps)) * gamma, rms_norm.rs:19-27), then
+// of rope_kernel (rope/mod.rs:156-176).
+namespace {
+
+// One head in place at x, or from src into dst (the lane kernel's K): normalise, scale by gamma [d], rotate by table row p.
+__device__ __forceinline__ void head_norm_rope(const float* src, float* dst, const float* __restrict__ gamma,
+                                               float eps, const float* __restrict__ cos_t, const float* __restrict__ sin_t, int p,
+                                               int head_dim, int lane)
+{
+    const int half = head_dim >> 1;
+    const bool on = lane < half;
+    const float x0 = on ? src[lane] : 0.0f, x1 = on ? src[lane + half] : 0.0f;
+    float s = fmaf(x0, x0, 0.0f);
+    s = fmaf(x1, x1, s);
+    const float rms = sqrtf(wave_sum(s) / (float)head_dim + eps);  // every lane of the wave is here: the reduction is wave-wide
+    if (!on) return;
+    const float y0 = (x0 / rms) * gamma[lane], y1 = (x1 / rms) * gamma[lane + half];
+    const float c = cos_t[(int64_t)p * half + lane], sn = sin_t[(int64_t)p * half + lane];
+    dst[lane] = y0 * c - y1 * sn;
+    dst[lane + half] = y0 * sn + y1 * c;
+}
+
+// rows x (n_heads + n_kv_heads) heads, four per workgroup.  Row r is at position p = (*pos_ptr | pos) + r; its Q heads are
+// row r of q, its K heads row (k_at_cache_row ? p : r) of k.
+__global__ __launch_bounds__(256) void qk_norm_rope_kernel(float* __restrict__ q, int64_t ldq, float* __restrict__ k, int64_t ldk, int rows,
+                                                           int n_heads, int n_kv_heads, int head_dim,
+                                                           const float* __restrict__ gamma_q, const float* __restrict__ gamma_k, float eps,
+                                                           const float* __restrict__ cos_t, const float* __restrict__ sin_t, int pos,
+                                                           const int* __restrict__ pos_ptr, int k_at_cache_row)
+{
+    const int lane = threadIdx.x & 63;
+    const int per_row = n_heads + n_kv_heads;
+    const int job = blockIdx.x * 4 + (threadIdx.x >> 6);  // uniform over the wave
+    if (job >= rows * per_row) return;
+    const int r = job / per_row, h = job - r * per_row;
+    const int p = (pos_ptr ? *pos_ptr : pos) + r;
+    const bool is_q = h < n_heads;
+    float* x = is_q ? q + (int64_t)r * ldq + h * head_dim : k + (int64_t)(k_at_cache_row ? p : r) * ldk + (h - n_heads) * head_dim;
+    head_norm_rope(x, x, is_q ? gamma_q : gamma_k, eps, cos_t, sin_t, p, head_dim, lane);
+}
+
+// lane_rope_scatter_kernel with the head norm: one workgroup per lane, its four waves stride over the lane's heads; Q in place in
+// the staging row, K into row pos[lane] of the lane's cache, V copied there.  Frozen lanes and positions outside the cache write nothing.
+__global__ __launch_bounds__(256) void lane_qk_norm_rope_scatter_kernel(float* __restrict__ qkv, int64_t ld, int n_heads, int n_kv_heads,
+                                                                        int head_dim, const float* __restrict__ gamma_q,
+                                                                        const float* __restrict__ gamma_k, float eps,
+                                                                        const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                        float* __restrict__ Kc, float* __restrict__ Vc, int64_t lane_stride,
+                                                                        int capacity, const int* __restrict__ pos,
+                                                                        const int* __restrict__ live)
+{
+    const int ln = blockIdx.x;
+    if (!live[ln]) return;
+    const int p = pos[ln];
+    if (p < 0 || p >= capacity) return;
+    const int qd = n_heads * head_dim, kv = n_kv_heads * head_dim;
+    float* row = qkv + (int64_t)ln * ld;
+    float* kdst = Kc + (int64_t)ln * lane_stride + (int64_t)p * kv;
+    float* vdst = Vc + (int64_t)ln * lane_stride + (int64_t)p * kv;
+    const int lane = threadIdx.x & 63;
+    for (int h = threadIdx.x >> 6; h < n_heads + n_kv_heads; h += 4) {  // (uniform over the wave)
+        if (h < n_heads) head_norm_rope(row + h * head_dim, row + h * head_dim, gamma_q, eps, cos_t, sin_t, p, head_dim, lane);
+        else head_norm_rope(row + qd + (h - n_heads) * head_dim, kdst + (h - n_heads) * head_dim, gamma_k, eps, cos_t, sin_t, p, head_dim, lane);
+    }
+    for (int i = threadIdx.x; i < kv; i += 256) vdst[i] = row[qd + kv + i];
+}
+
+}  // namespace
+
+hipError_t launch_qk_norm_rope(float* q, int64_t ldq, float* k, int64_t ldk, int rows, int n_heads, int n_kv_heads, int head_dim,
+                               const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t, int pos,
+                               const int* pos_ptr, int k_at_cache_row, hipStream_t stream)
+{
+    if (rows <= 0 || n_heads + n_kv_heads <= 0) return hipSuccess;
+    if (n_heads < 0 || n_kv_heads < 0 || head_dim < 2 || head_dim > 128 || (head_dim & 1)) return hipErrorInvalidValue;
+    const int64_t jobs = (int64_t)rows * (n_heads + n_kv_heads);
+    if (jobs > (int64_t)1 << 30) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(qk_norm_rope_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, stream, q, ldq, k, ldk, rows, n_heads, n_kv_heads,
+                       head_dim, gamma_q, gamma_k, eps, cos_t, sin_t, pos, pos_ptr, k_at_cache_row);
+    return hipGetLastError();
+}
+
+hipError_t launch_lane_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
+                                            const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
+                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmLaneState* state,
+                                            hipStream_t stream)
+{
+    if (lanes <= 0) return hipSuccess;
+    if (lanes > LLM_MAX_ROWS || head_dim < 2 || head_dim > 128 || (head_dim & 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lane_qk_norm_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim,
+                       gamma_q, gamma_k, eps, cos_t, sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Prompt-lookup decoding (llm.cpp: LlmModel::generate_lookup): the draft of the next verify step, and its pick.
 namespace {
 

@@ -28,6 +28,10 @@ const RegistryEntry kEntries[] = {
     {"toxic-bert", "olafuraron/toxic-bert-safetensors", ModelTask::Classification, ModelArch::Bert},
     {"qwen2.5-0.5b-instruct", "Qwen/Qwen2.5-0.5B-Instruct", ModelTask::Other, ModelArch::Other},
     {"qwen2.5-1.5b", "Qwen/Qwen2.5-1.5B-Instruct", ModelTask::Other, ModelArch::Other},
+    {"qwen3-0.6b", "Qwen/Qwen3-0.6B", ModelTask::Other, ModelArch::Other},
+    {"qwen3-1.7b", "Qwen/Qwen3-1.7B", ModelTask::Other, ModelArch::Other},
+    {"qwen3-4b", "Qwen/Qwen3-4B", ModelTask::Other, ModelArch::Other},
+    {"qwen3-8b", "Qwen/Qwen3-8B", ModelTask::Other, ModelArch::Other},
     {"llama3.2-1b-instruct", "meta-llama/Llama-3.2-1B-Instruct", ModelTask::Other, ModelArch::Other},
     {"llama3.2-3b-instruct", "meta-llama/Llama-3.2-3B-Instruct", ModelTask::Other, ModelArch::Other},
     {"phi3.5-mini", "microsoft/Phi-3.5-mini-instruct", ModelTask::Other, ModelArch::Other},
@@ -74,6 +78,10 @@ const Alias kAliases[] = {
     {"facebook/bart-large-cnn", "bart-large-cnn"},
     {"openai/whisper-small", "whisper-small"},
     {"openai/whisper-large-v3", "whisper-large-v3"},
+    {"qwen/qwen3-0.6b", "qwen3-0.6b"},
+    {"qwen/qwen3-1.7b", "qwen3-1.7b"},
+    {"qwen/qwen3-4b", "qwen3-4b"},
+    {"qwen/qwen3-8b", "qwen3-8b"},
     {"distilgpt2/resolve/main/model.safetensors", "distilgpt2"},
     {"gpt2/resolve/main/model.safetensors", "gpt2"},
 };

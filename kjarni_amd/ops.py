@@ -216,6 +216,25 @@ def kv_prefix_copy(src, dst, dst_offset: int, count: int, src_skew: int = 0, dst
     return d
 
 
+def qk_norm_rope(q, k, rows: int, n_heads: int, n_kv_heads: int, head_dim: int, gamma_q, gamma_k, eps: float, cos, sin, pos: int,
+                 pos_on_device: bool = False, k_at_cache_row: bool = False, device: int = 0):
+    """Qwen3's per-head RMSNorm + RoPE kernel alone: q [q_rows, ldq] and k [k_rows, ldk] (leading dimensions may exceed the
+    used widths) -> (q, k) after the call on `rows` rows at base position `pos`; cos / sin [table_rows, head_dim // 2].
+    K row r is row pos + r of k when k_at_cache_row, else row r."""
+    qa, ka = np.array(q, np.float32, order="C"), np.array(k, np.float32, order="C")
+    gq, gk = np.ascontiguousarray(gamma_q, np.float32), np.ascontiguousarray(gamma_k, np.float32)
+    ct, st = np.ascontiguousarray(cos, np.float32), np.ascontiguousarray(sin, np.float32)
+    if qa.ndim != 2 or ka.ndim != 2 or gq.shape != (head_dim,) or gk.shape != (head_dim,):
+        raise ValueError("q and k: [rows, ld]; gammas: [head_dim]")
+    if ct.ndim != 2 or ct.shape != st.shape or ct.shape[1] != head_dim // 2:
+        raise ValueError("cos and sin: [table_rows, head_dim // 2]")
+    f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check_error(lib().kjarni_hip_op_qk_norm_rope(device, f(qa), qa.shape[1], qa.shape[0], f(ka), ka.shape[1], ka.shape[0], int(rows),
+                                                 int(n_heads), int(n_kv_heads), int(head_dim), f(gq), f(gk), float(eps), f(ct), f(st),
+                                                 ct.shape[0], int(pos), int(bool(pos_on_device)), int(bool(k_at_cache_row))))
+    return qa, ka
+
+
 ARGMAX_DECODER, ARGMAX_LANES, ARGMAX_LOOKUP = 0, 1, 2
 _i32p = C.POINTER(C.c_int32)
 

@@ -43,6 +43,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            2 048 tokens and a 32-token message; five score() calls over one 512-token context with 8-token continuations; 8
            requests under a 512-token shared prefix on 8 lanes (16-token tails, 16 new tokens), with the prefix not resident
            and resident.  Medians of runs that end in a synchronise; the lines also go to profiles/llm_prefix_bench.jsonl.
+  llm_qwen3  (only on request) the Qwen3-0.6B shape (hidden 1024, 28 layers, 16 / 8 heads of 128, intermediate 3072, vocab
+           151 936, tied head, bf16 weights, random init): 128-token prompt time, greedy decode of 256 tokens; tokens/s and
+           ms per token (six launches per layer: the per-head Q / K norm + RoPE is a launch of its own).  The line also goes
+           to profiles/qwen3_bench_llm.jsonl.  KJARNI_QWEN3_TRACE=N: a 128-token prompt and N decode steps only (for a
+           kernel trace).
 """
 import json
 import os
@@ -1152,6 +1157,49 @@ def main():
         with open(out_path, "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+    if "llm_qwen3" in which:
+        from tests import qwen3_fixture
+        geo = dict(qwen3_fixture.Q3_06B_WIDTHS, num_hidden_layers=28, vocab_size=151936, max_position_embeddings=4096, eos_token_id=[])
+        d = os.path.join(tmp, "qwen3-0.6b")
+        qwen3_fixture.qwen3_model(d, geo, seed=0, store_bf16=True, std=0.02)
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        prompt = np.random.default_rng(0).integers(1000, 100000, 128).tolist()
+        trace = int(os.environ.get("KJARNI_QWEN3_TRACE", "0"))
+        if trace:
+            dec.generate(prompt, trace)
+            return
+        n_new = 256
+        dec.generate(prompt, 8)                                               # warm-up (graph capture)
+        runs = []
+        for _ in range(3):                                                    # medians of three runs, each ended by a synchronise
+            t0 = time.perf_counter()
+            dec.reset()
+            dec.forward(prompt, fetch=False)
+            t_prefill = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            out = dec.generate(prompt, n_new)
+            runs.append((t_prefill, time.perf_counter() - t0 - t_prefill, len(out)))
+        t_prefill = float(np.median([r[0] for r in runs]))
+        t_dec = float(np.median([r[1] for r in runs]))
+        n_out = runs[0][2]
+        kv_bytes = 2 * geo["num_hidden_layers"] * geo["num_key_value_heads"] * geo["head_dim"] * 4 * (128 + n_new / 2)
+        per_tok = dec.weight_bytes + kv_bytes
+        line = {"metric": "tokens/sec greedy decode, Qwen3-0.6B shape, bf16 weights, batch 1", "value": round(n_out / t_dec, 1),
+                "unit": "tokens/s", "n_gpus": 1, "dtype": "bf16 weights, f32 activations/accumulate/KV", "data": "synthetic",
+                "config": {"workload": "Qwen3-0.6B geometry (1024 hidden, 28 layers, 16/8 heads of 128, intermediate 3072, vocab 151936, tied "
+                                       f"head), random init, 128-token prompt, {n_out} generated tokens; medians of 3 runs"},
+                "ms_prefill_128": round(t_prefill * 1e3, 2), "ms_per_token": round(t_dec * 1e3 / n_out, 4), "weight_bytes": dec.weight_bytes,
+                "launches_per_layer_per_step": 6,
+                "runs_ms_per_token": [round(r[1] * 1e3 / r[2], 4) for r in runs],
+                "roofline": {"kernel": "llm_gemv kernels (weight stream) + decode_attention_partial", "bound": "hbm",
+                             "achieved": round(per_tok * n_out / t_dec / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                             "frac": round(per_tok * n_out / t_dec / 1e9 / PEAK_HBM_GBS, 4), "traffic": None,
+                             "algorithmic_bytes_per_token": int(per_tok)}}
+        emit(line)
+        with open(os.path.join(ROOT, "profiles", "qwen3_bench_llm.jsonl"), "w") as f:
+            f.write(json.dumps(line) + "\n")
+        del dec
 
 
 if __name__ == "__main__":
