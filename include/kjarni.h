@@ -453,6 +453,22 @@ KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* generator, cons
  * continuation that adds no token, or a text longer than the model's context, is INVALID_CONFIG with the reason. */
 typedef struct KjarniScoreResult { double sum_logprob; size_t n_tokens; int32_t is_greedy; } KjarniScoreResult;
 KjarniErrorCode kjarni_generator_score(KjarniGenerator* generator, const char* context, const char* continuation, KjarniScoreResult* out);
+/* kjarni_generator_score token by token, with the top_k (1 .. 8, not above the vocabulary) most likely tokens of every scored
+ * position (not in the reference).  Encoding rules and errors are kjarni_generator_score's; top_k out of range: INVALID_CONFIG.
+ * tokens / logprobs [n_tokens]: the scored tokens and their log-probabilities (their float64 sum in order is
+ * kjarni_generator_score's sum_logprob); top_tokens / top_logprobs [n_tokens, top_k] row-major, most likely first (equal logits:
+ * the larger id first).  On error *out is zeroed.  Free with kjarni_token_scores_free (NULL and a zeroed struct are fine). */
+typedef struct KjarniTokenScores {
+    uint32_t* tokens;
+    float* logprobs;
+    uint32_t* top_tokens;
+    float* top_logprobs;
+    size_t n_tokens;
+    size_t top_k;
+} KjarniTokenScores;
+KjarniErrorCode kjarni_generator_score_tokens(KjarniGenerator* generator, const char* context, const char* continuation, size_t top_k,
+                                              KjarniTokenScores* out);
+void kjarni_token_scores_free(KjarniTokenScores* scores);
 /* Without a buffer: the name's byte length; with one: bytes copied, NUL excluded. */
 size_t kjarni_generator_model_name(const KjarniGenerator* generator, char* buf, size_t buf_len);
 size_t kjarni_generator_context_size(const KjarniGenerator* generator);  /* the model's n_ctx / max_position_embeddings */

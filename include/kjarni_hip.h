@@ -745,6 +745,25 @@ KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, in
                                          int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused, float* logprob_out,
                                          uint32_t* top_out, float* top_logprob_out, float* lse_out);
 
+/* Top-k alternatives per scored position.  kjarni_hip_decoder_score_topk is kjarni_hip_decoder_score with, instead of the arg-max
+ * alone, the top_k most likely tokens of every position: topk_ids_out / topk_logprob_out are [n - first, top_k] row-major, slot j
+ * the token with the j-th largest logit (equal logits: the larger id first) and its log-probability, non-increasing along a row;
+ * slot 0 is kjarni_hip_decoder_score's top / top_logprob and logprob_out is its logprob_out, bit for bit.  The fused route keeps a
+ * sorted list of KJARNI_SCORE_TOPK_MAX candidates per lane next to the running sums (the logits are still never stored); the rows
+ * route takes them from the materialised rows.  Same routes, chunks, prefix reuse, counters and final state as
+ * kjarni_hip_decoder_score, and its argument errors; top_k outside [1, KJARNI_SCORE_TOPK_MAX] or above the vocabulary:
+ * INVALID_CONFIG naming top_k before any GPU work, the cache untouched.  Any output may be NULL. */
+#ifndef KJARNI_SCORE_TOPK_MAX
+#define KJARNI_SCORE_TOPK_MAX 8
+#endif
+KjarniErrorCode kjarni_hip_decoder_score_topk(KjarniHipDecoder* decoder, const uint32_t* ids, int32_t n, int32_t first, int32_t top_k,
+                                              float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out);
+/* kjarni_hip_op_score_head with top_k: topk_ids_out / topk_logprob_out [m, top_k], logprob_out / lse_out [m], any may be NULL.
+ * logprob, lse and slot 0 are bit-identical to kjarni_hip_op_score_head's with the same slab_tiles and route. */
+KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
+                                              int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused, int32_t top_k,
+                                              float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out, float* lse_out);
+
 /* ---- prefix reuse: keep the cached rows of the tokens a call shares with what the cache holds (NOT in the reference, whose
  * generator clears its cache per call, generator.rs:228-260) ----
  * Off by default.  On: kjarni_hip_decoder_generate / _generate_lookup / _generate_sampled keep the cache rows of

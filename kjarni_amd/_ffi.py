@@ -257,6 +257,11 @@ class KjarniScoreResult(Structure):
     _fields_ = [("sum_logprob", C.c_double), ("n_tokens", c_size_t), ("is_greedy", c_int32)]
 
 
+class KjarniTokenScores(Structure):
+    _fields_ = [("tokens", POINTER(C.c_uint32)), ("logprobs", POINTER(c_float)), ("top_tokens", POINTER(C.c_uint32)),
+                ("top_logprobs", POINTER(c_float)), ("n_tokens", c_size_t), ("top_k", c_size_t)]
+
+
 class KjarniGeneratorConfig(Structure):
     _fields_ = [("device", c_int32), ("cache_dir", c_char_p), ("model_name", c_char_p), ("model_path", c_char_p),
                 ("quiet", c_int32)]
@@ -497,6 +502,11 @@ SIGNATURES = {
     "kjarni_hip_op_score_head": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, c_int32, _u32p, c_int32, c_int32, _f32p,
                                            _u32p, _f32p, _f32p]),
     "kjarni_generator_score": (c_int32, [c_void_p, c_char_p, c_char_p, POINTER(KjarniScoreResult)]),
+    "kjarni_hip_decoder_score_topk": (c_int32, [c_void_p, _u32p, c_int32, c_int32, c_int32, _f32p, _u32p, _f32p]),
+    "kjarni_hip_op_score_head_topk": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, c_int32, _u32p, c_int32, c_int32, c_int32,
+                                                _f32p, _u32p, _f32p, _f32p]),
+    "kjarni_generator_score_tokens": (c_int32, [c_void_p, c_char_p, c_char_p, c_size_t, POINTER(KjarniTokenScores)]),
+    "kjarni_token_scores_free": (None, [POINTER(KjarniTokenScores)]),
     "kjarni_hip_decoder_set_prefix_reuse": (None, [c_void_p, c_int32]),
     "kjarni_hip_decoder_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_decoder_resident": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),

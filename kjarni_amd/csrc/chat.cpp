@@ -586,11 +586,10 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
                                lookup_sampling_ ? prompt_lookup_ : 0);
 }
 
-Generator::Score Generator::score(const std::string& context, const std::string& continuation)
+size_t Generator::encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const
 {
-    std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(GenerationOverrides());
-    const std::vector<uint32_t> whole = encode(context + continuation, config);
+    whole = encode(context + continuation, config);
     const size_t first = encode(context, config).size();
     if (first == 0) throw InvalidConfig("scoring needs at least one context token (the context is empty and the model has no BOS token)");
     if (first >= whole.size())
@@ -599,6 +598,14 @@ Generator::Score Generator::score(const std::string& context, const std::string&
     if (whole.size() > (size_t)model_->context())
         throw InvalidConfig("context + continuation (" + std::to_string(whole.size()) + " tokens) exceed the model's context of " +
                             std::to_string(model_->context()) + " tokens");
+    return first;
+}
+
+Generator::Score Generator::score(const std::string& context, const std::string& continuation)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    std::vector<uint32_t> whole;
+    const size_t first = encode_scored(context, continuation, whole);
     const size_t cnt = whole.size() - first;
     std::vector<float> lp(cnt);
     std::vector<uint32_t> top(cnt);
@@ -610,6 +617,25 @@ Generator::Score Generator::score(const std::string& context, const std::string&
         r.sum_logprob += (double)lp[i];
         if (top[i] != whole[first + i]) r.is_greedy = false;
     }
+    return r;
+}
+
+Generator::TokenScores Generator::score_tokens(const std::string& context, const std::string& continuation, size_t top_k)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    if (top_k < 1 || top_k > (size_t)KJARNI_SCORE_TOPK_MAX || top_k > (size_t)model_->config().vocab)
+        throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                            "] and not above the vocabulary size " + std::to_string(model_->config().vocab));
+    std::vector<uint32_t> whole;
+    const size_t first = encode_scored(context, continuation, whole);
+    const size_t cnt = whole.size() - first;
+    TokenScores r;
+    r.top_k = top_k;
+    r.tokens.assign(whole.begin() + (ptrdiff_t)first, whole.end());
+    r.logprobs.resize(cnt);
+    r.top_tokens.resize(cnt * top_k);
+    r.top_logprobs.resize(cnt * top_k);
+    model_->score_topk(whole.data(), (int)whole.size(), (int)first, (int)top_k, r.logprobs.data(), r.top_tokens.data(), r.top_logprobs.data());
     return r;
 }
 

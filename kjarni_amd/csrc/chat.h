@@ -167,9 +167,21 @@ public:
         bool is_greedy = false;    // every scored token is its position's arg-max
     };
     Score score(const std::string& context, const std::string& continuation);
+    // score() token by token, with the top_k most likely tokens of every scored position (LlmModel::score_topk): the same
+    // tokens and the same errors, plus InvalidConfig for top_k outside [1, KJARNI_SCORE_TOPK_MAX] or above the vocabulary.
+    struct TokenScores {
+        std::vector<uint32_t> tokens;       // whole[first:]
+        std::vector<float> logprobs;        // [n_tokens]
+        std::vector<uint32_t> top_tokens;   // [n_tokens, top_k]
+        std::vector<float> top_logprobs;    // [n_tokens, top_k]
+        size_t top_k = 0;
+    };
+    TokenScores score_tokens(const std::string& context, const std::string& continuation, size_t top_k);
 
 private:
     Generator() = default;
+    // score()'s token rule and checks: whole = encode(context + continuation), returns first = len(encode(context))
+    size_t encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const;
     std::string run(const std::string& prompt, const GenerationOverrides& runtime, const std::function<bool(const std::string&)>& on_text);
 
     std::string model_name_;

@@ -395,6 +395,44 @@ KJARNI_EXPORT KjarniErrorCode kjarni_generator_score(KjarniGenerator* gen, const
     });
 }
 
+KJARNI_EXPORT void kjarni_token_scores_free(KjarniTokenScores* s)
+{
+    if (!s) return;
+    std::free(s->tokens);
+    std::free(s->logprobs);
+    std::free(s->top_tokens);
+    std::free(s->top_logprobs);
+    *s = KjarniTokenScores{};
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_score_tokens(KjarniGenerator* gen, const char* context, const char* continuation, size_t top_k,
+                                                            KjarniTokenScores* out)
+{
+    if (!gen || !context || !continuation || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = KjarniTokenScores{};
+    if (!valid_utf8(context) || !valid_utf8(continuation)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const Generator::TokenScores s = gen->inner->score_tokens(context, continuation, top_k);
+        const size_t n = s.tokens.size();
+        KjarniTokenScores r{};
+        r.tokens = static_cast<uint32_t*>(std::malloc(n * sizeof(uint32_t)));
+        r.logprobs = static_cast<float*>(std::malloc(n * sizeof(float)));
+        r.top_tokens = static_cast<uint32_t*>(std::malloc(n * top_k * sizeof(uint32_t)));
+        r.top_logprobs = static_cast<float*>(std::malloc(n * top_k * sizeof(float)));
+        if (!r.tokens || !r.logprobs || !r.top_tokens || !r.top_logprobs) {
+            kjarni_token_scores_free(&r);
+            throw std::bad_alloc();
+        }
+        std::memcpy(r.tokens, s.tokens.data(), n * sizeof(uint32_t));
+        std::memcpy(r.logprobs, s.logprobs.data(), n * sizeof(float));
+        std::memcpy(r.top_tokens, s.top_tokens.data(), n * top_k * sizeof(uint32_t));
+        std::memcpy(r.top_logprobs, s.top_logprobs.data(), n * top_k * sizeof(float));
+        r.n_tokens = n;
+        r.top_k = top_k;
+        *out = r;
+    });
+}
+
 KJARNI_EXPORT size_t kjarni_generator_model_name(const KjarniGenerator* gen, char* buf, size_t buf_len)
 {
     if (!gen) return 0;

@@ -432,6 +432,16 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_score(KjarniHipDecoder* d, cons
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_score_topk(KjarniHipDecoder* d, const uint32_t* ids, int32_t n, int32_t first, int32_t top_k,
+                                                            float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->score_topk(ids, n, first, top_k, logprob_out, topk_ids_out, topk_logprob_out);  // arguments checked before any GPU work
+    });
+}
+
 KJARNI_EXPORT void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* d, int32_t on)
 {
     if (d) d->model->set_score_fused(on != 0);

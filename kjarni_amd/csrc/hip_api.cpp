@@ -1070,6 +1070,56 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const flo
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
+                                                            int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused,
+                                                            int32_t top_k, float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out,
+                                                            float* lse_out)
+{
+    if (!hidden || !W || !targets) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (m < 0 || m > (1 << 20) || k <= 0 || vocab <= 0 || slab_tiles < 0 || (bf16 != 0 && bf16 != 1))
+            throw InvalidConfig("invalid score head dimensions");
+        if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > vocab)
+            throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                                "] and not above vocab (" + std::to_string(vocab) + ")");
+        if (fused ? k % 32 != 0 : k % 8 != 0) throw InvalidConfig(fused ? "the fused score head needs k % 32 == 0" : "the rows route needs k % 8 == 0");
+        for (int64_t r = 0; r < m; ++r)
+            if (targets[r] >= (uint32_t)vocab) throw InvalidConfig("targets[" + std::to_string(r) + "] is not below vocab");
+        use_device(device);
+        if (m == 0) return;
+        const size_t xb = (size_t)m * k * 4, wb = (size_t)vocab * k * (bf16 ? 2 : 4), ob = (size_t)m * 4, kb = ob * top_k;
+        DeviceBuf xd(xb), wd(wb), td(ob), lp(ob), ti(kb), tl(kb), ls(ob);
+        hip_check(hipMemcpy(xd.p, hidden, xb, hipMemcpyHostToDevice), "H2D hidden");
+        hip_check(hipMemcpy(wd.p, W, wb, hipMemcpyHostToDevice), "H2D W");
+        hip_check(hipMemcpy(td.p, targets, ob, hipMemcpyHostToDevice), "H2D targets");
+        const float* X = static_cast<const float*>(xd.p);
+        const uint32_t* T = static_cast<const uint32_t*>(td.p);
+        float *LP = static_cast<float*>(lp.p), *TL = static_cast<float*>(tl.p), *LS = static_cast<float*>(ls.p);
+        uint32_t* TI = static_cast<uint32_t*>(ti.p);
+        if (fused) {
+            DeviceBuf scratch(score_head_topk_scratch_bytes((int)m, vocab, slab_tiles, top_k));
+            hip_check(launch_score_head_topk(X, k, (int)m, wd.p, bf16, vocab, k, T, slab_tiles, top_k, scratch.p, LP, TI, TL, LS, nullptr),
+                      "score head top-k");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        } else {
+            DeviceBuf logits((size_t)8 * vocab * 4);
+            for (int64_t r = 0; r < m; r += 8) {
+                LlmGemvArgs a;
+                a.X = X + r * k; a.ldx = k; a.rows = (int)std::min<int64_t>(8, m - r); a.W = wd.p; a.bf16 = bf16; a.n_out = vocab; a.k = k;
+                a.Y0 = static_cast<float*>(logits.p); a.ldy0 = vocab;
+                hip_check(launch_llm_gemv(a, nullptr), "lm head");
+                hip_check(launch_score_rows_topk(a.Y0, vocab, a.rows, vocab, T + r, top_k, LP + r, TI + r * top_k, TL + r * top_k, LS + r, nullptr),
+                          "score rows top-k");
+            }
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        }
+        if (logprob_out) hip_check(hipMemcpy(logprob_out, LP, ob, hipMemcpyDeviceToHost), "D2H logprob");
+        if (topk_ids_out) hip_check(hipMemcpy(topk_ids_out, TI, kb, hipMemcpyDeviceToHost), "D2H top-k ids");
+        if (topk_logprob_out) hip_check(hipMemcpy(topk_logprob_out, TL, kb, hipMemcpyDeviceToHost), "D2H top-k logprob");
+        if (lse_out) hip_check(hipMemcpy(lse_out, LS, ob, hipMemcpyDeviceToHost), "D2H lse");
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_attention(int32_t device, const float* qkv, const uint32_t* mask,
                                                       int64_t batch, int32_t seq, int32_t heads, int32_t head_dim,
                                                       float mask_value, float* ctx, int32_t iters, float* ms_out)

@@ -905,12 +905,32 @@ void LlmModel::ensure_score()
     score_scratch_ = dalloc((score_scratch_bytes_ + 3) / 4);
 }
 
+void LlmModel::ensure_score_topk()
+{
+    if (score_tk_ids_) return;
+    const size_t cap = (size_t)cache_cap_ * KJARNI_SCORE_TOPK_MAX;
+    score_tk_ids_ = reinterpret_cast<uint32_t*>(dalloc(cap));
+    score_tk_lp_ = dalloc(cap);
+    for (int m = 64; m <= 2048; m += 64)
+        score_tk_scratch_bytes_ = std::max(score_tk_scratch_bytes_, score_head_topk_scratch_bytes(m, cfg_.vocab, 0, KJARNI_SCORE_TOPK_MAX));
+    score_tk_scratch_ = dalloc((score_tk_scratch_bytes_ + 3) / 4);
+}
+
 void LlmModel::score_head_rows(const float* Xn, int lo, int cnt)
 {
     const LlmConfig& c = cfg_;
     const int H = c.hidden, out = lo + 1 - score_first_;
     const uint32_t* tgt = score_tgt_ + lo;
+    const size_t kout = (size_t)out * score_k_;  // the rows' first slot in the top-k outputs
     if (score_fused_ && !quant_ && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
+        if (score_k_ > 0) {
+            if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, score_k_) > score_tk_scratch_bytes_)
+                throw std::runtime_error("score_topk: slab scratch too small");
+            hip_check(launch_score_head_topk(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_k_, score_tk_scratch_, score_lp_ + out,
+                                             score_tk_ids_ + kout, score_tk_lp_ + kout, nullptr, stream_), "score head top-k");
+            ++score_fused_calls_;
+            return;
+        }
         if (score_head_scratch_bytes(cnt, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score: slab scratch too small");
         hip_check(launch_score_head(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, score_lp_ + out, score_top_ + out,
                                     score_tlp_ + out, nullptr, stream_), "score head");
@@ -928,13 +948,18 @@ void LlmModel::score_head_rows(const float* Xn, int lo, int cnt)
             lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
             hip_check(launch_llm_gemv(lm, stream_), "lm head");
         }
-        hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_lp_ + out + r, score_top_ + out + r, score_tlp_ + out + r,
-                                    nullptr, stream_), "score rows");
+        if (score_k_ > 0)
+            hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_k_, score_lp_ + out + r,
+                                             score_tk_ids_ + kout + (size_t)r * score_k_, score_tk_lp_ + kout + (size_t)r * score_k_, nullptr,
+                                             stream_), "score rows top-k");
+        else
+            hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_lp_ + out + r, score_top_ + out + r,
+                                        score_tlp_ + out + r, nullptr, stream_), "score rows");
         ++score_rows_calls_;
     }
 }
 
-void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out)
+void LlmModel::score_pass(const uint32_t* ids, int n, int first, int top_k)
 {
     if (n < 2) throw InvalidConfig("n (" + std::to_string(n) + ") must be at least 2: a scored token needs a prefix");
     if (first < 1 || first >= n) throw InvalidConfig("first (" + std::to_string(first) + ") must be in [1, n) with n = " + std::to_string(n));
@@ -945,6 +970,7 @@ void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, 
                                 std::to_string(cfg_.vocab));
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ensure_score();
+    if (top_k > 0) ensure_score_topk();
     // prefix reuse: rows first - 1 .. n - 2 must reach the head, so at most first - 1 rows are kept; targets and result slots
     // stay indexed by absolute position
     int keep = 0;
@@ -953,11 +979,31 @@ void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, 
     hip_check(hipMemcpyAsync(score_tgt_, ids + 1, (size_t)(n - 1) * 4, hipMemcpyHostToDevice, stream_), "H2D targets");
     score_first_ = first;
     score_n_ = n;
+    score_k_ = top_k;
     forward_rows(ids + keep, n - keep, true, keep);
+}
+
+void LlmModel::score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out)
+{
+    score_pass(ids, n, first, 0);
     const size_t cnt = (size_t)(n - first);
     if (logprob_out) hip_check(hipMemcpyAsync(logprob_out, score_lp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H logprob");
     if (top_out) hip_check(hipMemcpyAsync(top_out, score_top_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H top");
     if (top_logprob_out) hip_check(hipMemcpyAsync(top_logprob_out, score_tlp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H top logprob");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+
+void LlmModel::score_topk(const uint32_t* ids, int n, int first, int top_k, float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out)
+{
+    if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > cfg_.vocab)
+        throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                            "] and not above the vocabulary size " + std::to_string(cfg_.vocab));
+    score_pass(ids, n, first, top_k);
+    const size_t cnt = (size_t)(n - first);
+    if (logprob_out) hip_check(hipMemcpyAsync(logprob_out, score_lp_, cnt * 4, hipMemcpyDeviceToHost, stream_), "D2H logprob");
+    if (topk_ids_out) hip_check(hipMemcpyAsync(topk_ids_out, score_tk_ids_, cnt * top_k * 4, hipMemcpyDeviceToHost, stream_), "D2H top-k ids");
+    if (topk_logprob_out)
+        hip_check(hipMemcpyAsync(topk_logprob_out, score_tk_lp_, cnt * top_k * 4, hipMemcpyDeviceToHost, stream_), "D2H top-k logprob");
     hip_check(hipStreamSynchronize(stream_), "sync");
 }
 

@@ -56,6 +56,10 @@ struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
 
+#ifndef KJARNI_SCORE_TOPK_MAX
+#define KJARNI_SCORE_TOPK_MAX 8  // (include/kjarni_hip.h): the most alternatives score_topk() returns per position
+#endif
+
 // Prompt-lookup decoding: how the draft of a verify step is found in the sequence's own history.
 struct LookupConfig {
     int draft_tokens = 7;  // 1..7 tokens drafted per step (a step verifies draft_tokens + 1 rows)
@@ -134,6 +138,11 @@ public:
     // reset(); forward(ids, n) does.  Throws InvalidConfig naming the argument, before any GPU work, for n < 2, first outside
     // [1, n), n > context() and an id >= vocab.
     void score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out);
+    // score() with the top_k (1 .. KJARNI_SCORE_TOPK_MAX, <= vocab) most likely tokens of every scored position instead of the
+    // arg-max alone: topk_ids_out / topk_logprob_out are [n - first, top_k] row-major, slot j the j-th largest logit (equal values:
+    // the larger id first), slot 0 what score() returns as top / top_logprob.  Same sink, routes, chunks, prefix reuse, counters
+    // and final state as score(); logprob_out is bit-identical to score()'s.  Any output may be null.
+    void score_topk(const uint32_t* ids, int n, int first, int top_k, float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out);
     void set_score_fused(bool on) { score_fused_ = on; }
     // Head launches of score() by route since load.
     uint64_t score_fused_calls() const { return score_fused_calls_; }
@@ -275,6 +284,8 @@ private:
     void prefill_rows(const uint32_t* ids_host, int n, bool score = false, int score_base = 0);
     void forward_rows(const uint32_t* ids, int n, bool score, int score_base = 0);  // forward(), with score()'s sink
     void ensure_score();
+    void ensure_score_topk();
+    void score_pass(const uint32_t* ids, int n, int first, int top_k);  // score() / score_topk() up to the copies
     // cnt final-normed rows Xn [cnt, hidden] of positions lo .. lo + cnt - 1 against the targets ids[lo + 1 ..]
     void score_head_rows(const float* Xn, int lo, int cnt);
     void enqueue_argmax(bool record);
@@ -381,6 +392,11 @@ private:
     void* score_scratch_ = nullptr;
     size_t score_scratch_bytes_ = 0;
     int score_first_ = 0, score_n_ = 0;
+    int score_k_ = 0;  // top_k of the running score_topk() call, 0 inside score()
+    uint32_t* score_tk_ids_ = nullptr;  // [cache_cap_, KJARNI_SCORE_TOPK_MAX] each, used [n - first, top_k]
+    float* score_tk_lp_ = nullptr;
+    void* score_tk_scratch_ = nullptr;
+    size_t score_tk_scratch_bytes_ = 0;
     bool score_fused_ = true;
     uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0;
     // prefix reuse: the tokens of the cache rows (host only), the switch, the counters, and the device table of

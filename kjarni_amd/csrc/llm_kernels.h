@@ -170,9 +170,23 @@ int score_head_slab_tiles(int m, int vocab, int slab_tiles);  // the slab width 
 size_t score_head_scratch_bytes(int m, int vocab, int slab_tiles);
 hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
                              int slab_tiles, void* scratch, float* logprob, uint32_t* top, float* top_logprob, float* lse, hipStream_t stream);
+#ifndef KJARNI_SCORE_TOPK_MAX
+#define KJARNI_SCORE_TOPK_MAX 8  // (include/kjarni_hip.h)
+#endif
+// Top-k (LlmModel::score_topk): besides logprob and lse, the top_k (1 .. KJARNI_SCORE_TOPK_MAX, <= vocab) largest logits of every
+// row as topk_ids / topk_logprob [m, top_k] row-major, in descending argmax_key order (value, then the larger index; slot 0 is
+// launch_score_head's top / top_logprob).  Every lane of the head kernel keeps a sorted list of keys next to its running sums;
+// logprob, lse and slot 0 are bit-identical to launch_score_head's with the same slab_tiles.  scratch:
+// score_head_topk_scratch_bytes bytes.
+size_t score_head_topk_scratch_bytes(int m, int vocab, int slab_tiles, int top_k);
+hipError_t launch_score_head_topk(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
+                                  int slab_tiles, int top_k, void* scratch, float* logprob, uint32_t* topk_ids, float* topk_logprob, float* lse,
+                                  hipStream_t stream);
 // The rows route: the same outputs from up to 8 materialised logits rows [rows, ld] (llm_score_rows_kernel).
 hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, float* logprob, uint32_t* top,
                              float* top_logprob, float* lse, hipStream_t stream);
+hipError_t launch_score_rows_topk(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, int top_k, float* logprob,
+                                  uint32_t* topk_ids, float* topk_logprob, float* lse, hipStream_t stream);
 
 // ---- sampled decoding: the O(vocab) part on the device (llm_kernels.hip) ----------------------------------------------
 struct SampleHeader {   // 32 bytes, device memory mirrored to the host per sampled token

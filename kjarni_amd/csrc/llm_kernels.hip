@@ -2837,6 +2837,31 @@ __device__ __forceinline__ void score_combine(float& mx, float& sm, float omx, f
     mx = m;
 }
 
+// Top-k lists: TOPK argmax_keys in descending order, every index static so that the list lives in registers; 0 marks an empty
+// slot.  Keys of different columns differ, so "the TOPK largest keys" is one set whatever the order of the insertions.
+constexpr int SC_TOPK = KJARNI_SCORE_TOPK_MAX;
+
+template <int TOPK>
+__device__ __forceinline__ void topk_insert(unsigned long long (&lst)[TOPK], unsigned long long kk)
+{
+    if (kk > lst[TOPK - 1]) {  // the one compare of the common path
+#pragma unroll
+        for (int j = TOPK - 1; j > 0; --j) lst[j] = kk > lst[j - 1] ? lst[j - 1] : (kk > lst[j] ? kk : lst[j]);
+        lst[0] = kk > lst[0] ? kk : lst[0];
+    }
+}
+
+// lst = the TOPK largest of lst and the list lane ^ off holds; every lane of a pair ends with the same list.
+template <int TOPK>
+__device__ __forceinline__ void topk_merge_lane(unsigned long long (&lst)[TOPK], int off)
+{
+    unsigned long long o[TOPK];
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) o[j] = __shfl_xor(lst[j], off, kWave);
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) topk_insert(lst, o[j]);
+}
+
 // Eight consecutive weights of a row as two f32x4 (bf16 widened).
 __device__ __forceinline__ void score_load_w(const float* p, f32x4& a, f32x4& b)
 {
@@ -2858,7 +2883,10 @@ __device__ __forceinline__ void score_load_w(const uint16_t* p, f32x4& a, f32x4&
 // transposed tile W . X^T, so that lane == row: a lane's 16 accumulators are 16 vocabulary entries of its own row and the
 // reduction stays inside the lane until the slab ends, where the two half-waves (shuffle) and the two waves that share
 // rows (LDS) meet once.  Columns >= N contribute nothing (their loads are clamped), rows >= M are not stored.
-template <typename WT>
+// TOPK > 0: every lane also keeps the TOPK largest keys it has seen (topk_insert; lst[0] is `key`), the lists merge where
+// the single key does -- the second wave's through the first stage of sW, which nobody reads after the last tile -- and the
+// workgroup writes them behind the partials, [row tile][slab][slot][row].  mx / sm / tgt are computed exactly as without.
+template <typename WT, int TOPK>
 __global__ __launch_bounds__(256) void llm_score_head_kernel(const float* __restrict__ X, int64_t ldx, const WT* __restrict__ W,
                                                              const uint32_t* __restrict__ targets, int M, int N, int K, int m_tiles,
                                                              int slab_tiles, int n_tiles, int slabs, ScorePartial* __restrict__ P)
@@ -2902,6 +2930,11 @@ __global__ __launch_bounds__(256) void llm_score_head_kernel(const float* __rest
     const uint32_t target = (targets && row < M) ? targets[row] : 0xFFFFFFFFu;
     float mx = -INFINITY, sm = 0.0f, tgt = 0.0f;
     unsigned long long key = 0ull;
+    [[maybe_unused]] unsigned long long lst[TOPK > 0 ? TOPK : 1];
+    if constexpr (TOPK > 0) {
+#pragma unroll
+        for (int j = 0; j < TOPK; ++j) lst[j] = 0ull;
+    }
     const int nk = K / SC_BK;
     const int fw = (wv * 32 + l31) * SC_STRIDE + half * 4, fx = (wx * 32 + l31) * SC_STRIDE + half * 4;
     for (int t = t_begin; t < t_end; ++t) {
@@ -2935,7 +2968,8 @@ __global__ __launch_bounds__(256) void llm_score_head_kernel(const float* __rest
             if (col < N) {
                 tmax = fmaxf(tmax, acc[r]);
                 const unsigned long long kk = argmax_key(acc[r], col);
-                key = kk > key ? kk : key;
+                if constexpr (TOPK > 0) topk_insert(lst, kk);
+                else key = kk > key ? kk : key;
                 if ((uint32_t)col == target) tgt = acc[r];
             }
         }
@@ -2952,18 +2986,39 @@ __global__ __launch_bounds__(256) void llm_score_head_kernel(const float* __rest
     // the two half-waves of a row, then the two waves
     {
         const float omx = __shfl_xor(mx, 32, kWave), osm = __shfl_xor(sm, 32, kWave), otg = __shfl_xor(tgt, 32, kWave);
-        const unsigned long long ok = __shfl_xor(key, 32, kWave);
         score_combine(mx, sm, omx, osm);
         tgt += otg;  // at most one of them is not 0
-        key = ok > key ? ok : key;
+        if constexpr (TOPK > 0) {
+            topk_merge_lane(lst, 32);
+            key = lst[0];
+        } else {
+            const unsigned long long ok = __shfl_xor(key, 32, kWave);
+            key = ok > key ? ok : key;
+        }
     }
-    if (wv == 1 && half == 0) sRed[wx * 32 + l31] = ScorePartial{key, mx, sm, tgt, 0.0f};
+    [[maybe_unused]] unsigned long long* sKeys = reinterpret_cast<unsigned long long*>(&sW[0][0]);  // [TOPK][SC_BM], free after the last tile
+    if (wv == 1 && half == 0) {
+        sRed[wx * 32 + l31] = ScorePartial{key, mx, sm, tgt, 0.0f};
+        if constexpr (TOPK > 0) {
+#pragma unroll
+            for (int j = 0; j < TOPK; ++j) sKeys[j * SC_BM + wx * 32 + l31] = lst[j];
+        }
+    }
     __syncthreads();
     if (wv == 0 && half == 0 && row < M) {
         const ScorePartial o = sRed[wx * 32 + l31];
         score_combine(mx, sm, o.mx, o.sm);
         tgt += o.tgt;
-        key = o.key > key ? o.key : key;
+        if constexpr (TOPK > 0) {
+#pragma unroll
+            for (int j = 0; j < TOPK; ++j) topk_insert(lst, sKeys[j * SC_BM + wx * 32 + l31]);
+            key = lst[0];
+            unsigned long long* PK = reinterpret_cast<unsigned long long*>(P + (int64_t)m_tiles * slabs * SC_BM);
+#pragma unroll
+            for (int j = 0; j < TOPK; ++j) PK[(((int64_t)mt * slabs + slab) * TOPK + j) * SC_BM + wx * 32 + l31] = lst[j];
+        } else {
+            key = o.key > key ? o.key : key;
+        }
         P[((int64_t)mt * slabs + slab) * SC_BM + wx * 32 + l31] = ScorePartial{key, mx, sm, tgt, 0.0f};
     }
 }
@@ -2999,30 +3054,84 @@ __global__ __launch_bounds__(256) void llm_score_merge_kernel(const ScorePartial
     }
 }
 
+// The slabs' top-k lists of one row into the row's: a wave per row (four rows per workgroup).  Lane l walks the slabs l, l + 64,
+// ... in order, then the 64 lists meet in six butterfly steps (topk_merge_lane), after which every lane holds the row's list.
+// Lane j < top_k writes slot j: the key's index, and its value less the lse llm_score_merge_kernel left for the row.
+template <int TOPK>
+__global__ __launch_bounds__(256) void llm_score_topk_merge_kernel(const unsigned long long* __restrict__ PK, const float* __restrict__ lse,
+                                                                   int M, int slabs, int top_k, uint32_t* __restrict__ topk_ids,
+                                                                   float* __restrict__ topk_logprob)
+{
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;  // (the whole wave)
+    const unsigned long long* p = PK + (int64_t)(row / SC_BM) * slabs * TOPK * SC_BM + row % SC_BM;
+    unsigned long long lst[TOPK];
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) lst[j] = 0ull;
+    for (int s = lane; s < slabs; s += 64) {
+#pragma unroll
+        for (int j = 0; j < TOPK; ++j) topk_insert(lst, p[((int64_t)s * TOPK + j) * SC_BM]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) topk_merge_lane(lst, off);
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) mine = lane == j ? lst[j] : mine;
+    if (lane < top_k) {
+        if (topk_ids) topk_ids[(int64_t)row * top_k + lane] = (uint32_t)(mine & 0xFFFFFFFFull);
+        if (topk_logprob) topk_logprob[(int64_t)row * top_k + lane] = argmax_key_value(mine) - lse[row];
+    }
+}
+
 // The same statistics from materialised logits [rows, ld]: one workgroup per row, the maximum (with its index, last one
 // winning) first, then the sum of exp(x - max); both reduced lane -> wave -> workgroup in a fixed order.
+// TOPK > 0: the first pass keeps a list per thread over its strided elements instead of the one key, merged lane -> wave
+// (butterfly) -> workgroup (the four waves' lists through LDS, in wave order); lst[0] is the key, the rest is unchanged.
+template <int TOPK>
 __global__ __launch_bounds__(256) void llm_score_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
                                                              const uint32_t* __restrict__ targets, float* __restrict__ logprob,
                                                              uint32_t* __restrict__ top, float* __restrict__ top_logprob,
-                                                             float* __restrict__ lse_out)
+                                                             float* __restrict__ lse_out, int top_k, uint32_t* __restrict__ topk_ids,
+                                                             float* __restrict__ topk_logprob)
 {
-    __shared__ unsigned long long red_key[4];
+    __shared__ unsigned long long red_key[TOPK > 0 ? 4 * TOPK : 4];
     __shared__ float red_sum[4];
     const float* row = logits + (int64_t)blockIdx.x * ld;
     unsigned long long key = 0ull;
-    for (int i = threadIdx.x; i < vocab; i += 256) {
-        const unsigned long long kk = argmax_key(row[i], i);
-        key = kk > key ? kk : key;
-    }
+    [[maybe_unused]] unsigned long long lst[TOPK > 0 ? TOPK : 1];
+    if constexpr (TOPK > 0) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off, kWave);
-        key = o > key ? o : key;
+        for (int j = 0; j < TOPK; ++j) lst[j] = 0ull;
+        for (int i = threadIdx.x; i < vocab; i += 256) topk_insert(lst, argmax_key(row[i], i));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) topk_merge_lane(lst, off);
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int j = 0; j < TOPK; ++j) red_key[(threadIdx.x >> 6) * TOPK + j] = lst[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < TOPK; ++j) lst[j] = red_key[j];
+        for (int w = 1; w < 4; ++w) {
+#pragma unroll
+            for (int j = 0; j < TOPK; ++j) topk_insert(lst, red_key[w * TOPK + j]);
+        }
+        key = lst[0];
+    } else {
+        for (int i = threadIdx.x; i < vocab; i += 256) {
+            const unsigned long long kk = argmax_key(row[i], i);
+            key = kk > key ? kk : key;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(key, off, kWave);
+            key = o > key ? o : key;
+        }
+        if ((threadIdx.x & 63) == 0) red_key[threadIdx.x >> 6] = key;
+        __syncthreads();
+        key = red_key[0];
+        for (int w = 1; w < 4; ++w) key = red_key[w] > key ? red_key[w] : key;
     }
-    if ((threadIdx.x & 63) == 0) red_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    key = red_key[0];
-    for (int w = 1; w < 4; ++w) key = red_key[w] > key ? red_key[w] : key;
     const float mx = argmax_key_value(key);
     float sum = 0.0f;
     for (int i = threadIdx.x; i < vocab; i += 256) sum += expf(row[i] - mx);
@@ -3037,6 +3146,13 @@ __global__ __launch_bounds__(256) void llm_score_rows_kernel(const float* __rest
     if (top) top[r] = (uint32_t)(key & 0xFFFFFFFFull);
     if (top_logprob) top_logprob[r] = mx - lse;
     if (logprob && targets) logprob[r] = targets[r] < (uint32_t)vocab ? row[targets[r]] - lse : -INFINITY;
+    if constexpr (TOPK > 0) {
+#pragma unroll
+        for (int j = 0; j < TOPK; ++j) {
+            if (topk_ids && j < top_k) topk_ids[(int64_t)r * top_k + j] = (uint32_t)(lst[j] & 0xFFFFFFFFull);
+            if (topk_logprob && j < top_k) topk_logprob[(int64_t)r * top_k + j] = argmax_key_value(lst[j]) - lse;
+        }
+    }
 }
 
 }  // namespace
@@ -3064,6 +3180,42 @@ size_t score_head_scratch_bytes(int m, int vocab, int slab_tiles)
     return (size_t)m_tiles * ((n_tiles + st - 1) / st) * SC_BM * sizeof(ScorePartial);
 }
 
+// scratch of the top-k launch: the partials, the slabs' lists (SC_TOPK keys each, whatever top_k), one lse per row
+size_t score_head_topk_scratch_bytes(int m, int vocab, int slab_tiles, int top_k)
+{
+    if (top_k < 1 || top_k > SC_TOPK) return 0;
+    const size_t partials = score_head_scratch_bytes(m, vocab, slab_tiles);
+    return partials + partials / sizeof(ScorePartial) * SC_TOPK * sizeof(unsigned long long) + (size_t)std::max(m, 0) * sizeof(float);
+}
+
+hipError_t launch_score_head_topk(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
+                                  int slab_tiles, int top_k, void* scratch, float* logprob, uint32_t* topk_ids, float* topk_logprob, float* lse,
+                                  hipStream_t stream)
+{
+    if (m <= 0) return hipSuccess;
+    if (vocab <= 0 || top_k < 1 || top_k > SC_TOPK || top_k > vocab || !scratch || !llm_score_head_takes(X, ldx, W, bf16, k))
+        return hipErrorInvalidValue;
+    const int n_tiles = (vocab + SC_BN - 1) / SC_BN, m_tiles = (m + SC_BM - 1) / SC_BM;
+    const int st = score_head_slab_tiles(m, vocab, slab_tiles);
+    const int slabs = (n_tiles + st - 1) / st;
+    ScorePartial* P = static_cast<ScorePartial*>(scratch);
+    const unsigned long long* PK = reinterpret_cast<const unsigned long long*>(P + (int64_t)m_tiles * slabs * SC_BM);  // where the kernel writes
+    float* row_lse = lse ? lse : const_cast<float*>(reinterpret_cast<const float*>(PK + (int64_t)m_tiles * slabs * SC_TOPK * SC_BM));
+    const dim3 grid((unsigned)(m_tiles * slabs));
+    if (bf16)
+        hipLaunchKernelGGL((llm_score_head_kernel<uint16_t, SC_TOPK>), grid, dim3(256), 0, stream, X, ldx, static_cast<const uint16_t*>(W), targets,
+                           m, vocab, k, m_tiles, st, n_tiles, slabs, P);
+    else
+        hipLaunchKernelGGL((llm_score_head_kernel<float, SC_TOPK>), grid, dim3(256), 0, stream, X, ldx, static_cast<const float*>(W), targets, m,
+                           vocab, k, m_tiles, st, n_tiles, slabs, P);
+    // logprob and lse by score()'s own merge, in its order; then the lists
+    hipLaunchKernelGGL(llm_score_merge_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, P, targets, m, vocab, slabs, st, logprob,
+                       static_cast<uint32_t*>(nullptr), static_cast<float*>(nullptr), row_lse);
+    hipLaunchKernelGGL(llm_score_topk_merge_kernel<SC_TOPK>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, PK, row_lse, m, slabs, top_k,
+                       topk_ids, topk_logprob);
+    return hipGetLastError();
+}
+
 hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
                              int slab_tiles, void* scratch, float* logprob, uint32_t* top, float* top_logprob, float* lse, hipStream_t stream)
 {
@@ -3075,10 +3227,10 @@ hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, 
     ScorePartial* P = static_cast<ScorePartial*>(scratch);
     const dim3 grid((unsigned)(m_tiles * slabs));
     if (bf16)
-        hipLaunchKernelGGL((llm_score_head_kernel<uint16_t>), grid, dim3(256), 0, stream, X, ldx, static_cast<const uint16_t*>(W), targets, m,
+        hipLaunchKernelGGL((llm_score_head_kernel<uint16_t, 0>), grid, dim3(256), 0, stream, X, ldx, static_cast<const uint16_t*>(W), targets, m,
                            vocab, k, m_tiles, st, n_tiles, slabs, P);
     else
-        hipLaunchKernelGGL((llm_score_head_kernel<float>), grid, dim3(256), 0, stream, X, ldx, static_cast<const float*>(W), targets, m, vocab,
+        hipLaunchKernelGGL((llm_score_head_kernel<float, 0>), grid, dim3(256), 0, stream, X, ldx, static_cast<const float*>(W), targets, m, vocab,
                            k, m_tiles, st, n_tiles, slabs, P);
     hipLaunchKernelGGL(llm_score_merge_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, P, targets, m, vocab, slabs, st, logprob, top,
                        top_logprob, lse);
@@ -3090,8 +3242,18 @@ hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int voca
 {
     if (rows <= 0) return hipSuccess;
     if (rows > LLM_MAX_ROWS || vocab <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(llm_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, targets, logprob, top, top_logprob,
-                       lse);
+    hipLaunchKernelGGL(llm_score_rows_kernel<0>, dim3((unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, targets, logprob, top, top_logprob,
+                       lse, 0, static_cast<uint32_t*>(nullptr), static_cast<float*>(nullptr));
+    return hipGetLastError();
+}
+
+hipError_t launch_score_rows_topk(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, int top_k, float* logprob,
+                                  uint32_t* topk_ids, float* topk_logprob, float* lse, hipStream_t stream)
+{
+    if (rows <= 0) return hipSuccess;
+    if (rows > LLM_MAX_ROWS || vocab <= 0 || top_k < 1 || top_k > SC_TOPK || top_k > vocab) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(llm_score_rows_kernel<SC_TOPK>, dim3((unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, targets, logprob,
+                       static_cast<uint32_t*>(nullptr), static_cast<float*>(nullptr), lse, top_k, topk_ids, topk_logprob);
     return hipGetLastError();
 }
 

@@ -340,6 +340,19 @@ class HipDecoder:
         check_error(lib().kjarni_hip_decoder_score(self._h, u32(a), a.size, int(first), f(lp), u32(top), f(tlp)))
         return lp, top, tlp
 
+    def score_topk(self, ids: Sequence[int], first: int = 1, top_k: int = 8):
+        """score() with the top_k (1 .. 8, not above the vocabulary) most likely tokens of every scored position: (logprob f32
+        [cnt], ids u32 [cnt, top_k], logprob f32 [cnt, top_k]) with cnt = len(ids) - first.  Slot j of a row is the token with
+        the j-th largest logit (equal logits: the larger id first); slot 0 is score()'s arg-max, and the first array is
+        score()'s, bit for bit.  Same routes, counters and final state as score()."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        cnt, k = max(a.size - int(first), 0), max(int(top_k), 0)
+        lp, tid, tlp = np.empty(cnt, np.float32), np.empty((cnt, k), np.uint32), np.empty((cnt, k), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_score_topk(self._h, u32(a), a.size, int(first), int(top_k), f(lp), u32(tid), f(tlp)))
+        return lp, tid, tlp
+
     def set_score_fused(self, on: bool):
         """On (the default): f32 / bf16 heads are scored on the matrix cores without storing the logits; off: every checkpoint
         takes the rows route (8 materialised logits rows at a time)."""

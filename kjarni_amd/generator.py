@@ -57,6 +57,19 @@ class Generator:
         check_error(lib().kjarni_generator_score(self._handle, context.encode("utf-8"), continuation.encode("utf-8"), C.byref(r)))
         return float(r.sum_logprob), int(r.n_tokens), bool(r.is_greedy)
 
+    def score_tokens(self, context: str, continuation: str, top_k: int = 5):
+        """score() token by token: (tokens u32 [n], logprobs f32 [n], top_tokens u32 [n, top_k], top_logprobs f32 [n, top_k])
+        for the n tokens `continuation` adds; every row's alternatives most likely first (top_k 1 .. 8)."""
+        r = _ffi.KjarniTokenScores()
+        check_error(lib().kjarni_generator_score_tokens(self._handle, context.encode("utf-8"), continuation.encode("utf-8"), int(top_k),
+                                                        C.byref(r)))
+        try:
+            n, k = int(r.n_tokens), int(r.top_k)
+            return (np.ctypeslib.as_array(r.tokens, (n,)).copy(), np.ctypeslib.as_array(r.logprobs, (n,)).copy(),
+                    np.ctypeslib.as_array(r.top_tokens, (n, k)).copy(), np.ctypeslib.as_array(r.top_logprobs, (n, k)).copy())
+        finally:
+            lib().kjarni_token_scores_free(C.byref(r))
+
     def generate_batch(self, prompts: Sequence[str], config: Optional[GenerationConfig] = None) -> List[str]:
         """generate() for every prompt, up to 8 of them (set_lanes) decoded in lock step; texts in prompt order."""
         arr = _ffi.KjarniStringArray()

@@ -416,3 +416,26 @@ def score_head(hidden, W, targets, bf16=False, slab_tiles=0, fused=True, device=
     check_error(lib().kjarni_hip_op_score_head(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab, u32(targets),
                                                slab_tiles, 1 if fused else 0, f(lp), u32(top), f(tlp), f(lse)))
     return lp, top, tlp, lse
+
+
+def score_head_topk(hidden, W, targets, top_k, bf16=False, slab_tiles=0, fused=True, device=0):
+    """score_head with the top_k (1 .. 8, <= vocab) largest logits of every row (kjarni_hip_op_score_head_topk).  Returns
+    (logprob f32 [m], topk_ids u32 [m, top_k], topk_logprob f32 [m, top_k], lse f32 [m]); slot j holds the j-th largest logit's
+    column and log-probability (equal logits: the larger column first).  logprob, lse and slot 0 are score_head's bits."""
+    import ctypes as C
+    from ._ffi import check_error
+    hidden = np.ascontiguousarray(hidden, np.float32)
+    W = np.ascontiguousarray(W, np.uint16 if bf16 else np.float32)
+    targets = np.ascontiguousarray(targets, np.uint32)
+    m, k = hidden.shape
+    vocab = W.shape[0]
+    if W.shape[1] != k or targets.shape != (m,):
+        raise ValueError("hidden [m, k], W [vocab, k], targets [m]")
+    kk = max(int(top_k), 0)
+    lp, lse = np.empty(m, np.float32), np.empty(m, np.float32)
+    tid, tlp = np.empty((m, kk), np.uint32), np.empty((m, kk), np.float32)
+    f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+    check_error(lib().kjarni_hip_op_score_head_topk(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab,
+                                                    u32(targets), slab_tiles, 1 if fused else 0, int(top_k), f(lp), u32(tid), f(tlp), f(lse)))
+    return lp, tid, tlp, lse

@@ -38,6 +38,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
            end in a synchronise; the head's added time score - forward per route.
            KJARNI_SCORE_TRACE=N: N fused score() calls of the 2 048-token prompt on the Llama shape only (for a kernel trace).
+  llm_score_topk  (only on request) HipDecoder.score_topk() at top_k = 1 and 8 against score() of the same ids in one process,
+           alternated twice: Llama-3.2-1B shape (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused and on the rows
+           route; medians of runs that end in a synchronise; the ratio score_topk / score per case.  One line per (length,
+           route); the lines also go to profiles/llm_score_topk_bench.jsonl.
   llm_prefix  (only on request) prefix reuse off against on (HipDecoder.set_prefix_reuse) in one process, alternated twice:
            Llama-3.2-1B shape (bf16) and gpt2-small (bf16).  Time to the first token of turn 2 with a resident history of 512 /
            2 048 tokens and a 32-token message; five score() calls over one 512-token context with 8-token continuations; 8
@@ -1083,6 +1087,47 @@ def main():
             dec = kjarni_amd.HipDecoder(gd)
             measure("gpt2-small shape, bf16 weights (n_ctx 2048)", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
             del dec
+
+    if "llm_score_topk" in which:
+        # Method (measuring guide, section 5; as llm_score): one process on one box; score() -- the yardstick, the code before
+        # score_topk() existed -- and score_topk() at top_k = 1 and 8 are warmed first, then alternated twice, three runs each;
+        # every run ends in a synchronise (both return after one), medians over the 6 runs of a kind.
+        rng = np.random.default_rng(0)
+        d = os.path.join(tmp, "llama-1b-score-topk")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        kinds = {"score": lambda ids: dec.score(ids), "topk1": lambda ids: dec.score_topk(ids, 1, 1), "topk8": lambda ids: dec.score_topk(ids, 1, 8)}
+        lines = []
+        for n in (128, 2048):
+            ids = rng.integers(1000, 100000, n).tolist()
+            for fused in (True, False):
+                dec.set_score_fused(fused)
+                for fn in kinds.values():
+                    fn(ids)
+                runs = {k: [] for k in kinds}
+                for rep in range(2):
+                    for _ in range(3):
+                        for k, fn in kinds.items():
+                            t0 = time.perf_counter()
+                            fn(ids)
+                            runs[k].append((time.perf_counter() - t0) * 1e3)
+                med = {k: float(np.median(v)) for k, v in runs.items()}
+                line = {"metric": f"score_topk / score, Llama-3.2-1B shape, bf16 weights, {n} tokens, {'fused' if fused else 'rows'} route",
+                        "value": round(med["topk8"] / med["score"], 4), "unit": "ratio of medians at top_k = 8", "n_gpus": 1,
+                        "dtype": "bf16 weights, f32 activations/accumulate/KV", "data": "synthetic",
+                        "config": {"workload": f"random init; score() against score_topk() at top_k 1 and 8 of the same {n} ids (first = 1), "
+                                               "alternated twice in one process, medians of 6 runs, every run ends in a synchronise"},
+                        "tokens": n, "route": "fused" if fused else "rows", "score_ms": round(med["score"], 3),
+                        "score_topk1_ms": round(med["topk1"], 3), "score_topk8_ms": round(med["topk8"], 3),
+                        "topk1_over_score": round(med["topk1"] / med["score"], 4), "topk8_over_score": round(med["topk8"] / med["score"], 4),
+                        "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+                emit(line)
+                lines.append(line)
+        dec.set_score_fused(True)
+        del dec
+        with open(os.path.join(ROOT, "profiles", "llm_score_topk_bench.jsonl"), "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
     if "llm_prefix" in which:
         # Method (measuring guide, section 5; as llm_score): one process on one box; every case is warmed with reuse off and on,
