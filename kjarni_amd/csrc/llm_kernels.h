@@ -91,6 +91,8 @@ hipError_t launch_llm_embed_pos(const uint32_t* ids, int n, int hidden, int voca
 // In place x = gelu_tanh(x) (activations.rs:62-66) over n floats, n % 4 == 0: the prompt route's c_fc epilogue where the GEMM has none.
 hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream);
 // argmax (last maximum wins); best_scratch: one zero-initialised u64 (re-zeroed by the call); history/count/pos may be null.
+// The tie rule (argmax_key: the last maximum wins, +0.0 == -0.0, NaN lowest) lives in ONE kernel, argmax_partial_kernel, a row
+// per blockIdx.y: launch_argmax, launch_lane_pick and launch_lookup_pick are grids over it, each followed by its own finalize.
 hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* best_scratch, int32_t* out, int32_t* history, int* count,
                          int* pos, hipStream_t stream);
 
@@ -201,22 +203,26 @@ struct SampleCandidate {
     uint32_t token;
     float logit;
 };
+// One kernel family (sample_max / sample_hist / sample_compact, the row in blockIdx.y) makes the cut; the two launchers below
+// are grids over it: this one a single row with a contiguous candidate list, launch_sample_candidates_rows up to 8 rows.
 size_t sample_scratch_bytes();   // zero-initialised device scratch of launch_sample_candidates
 // top_k < 0 / top_p < 0 / min_p < 0: that filter is off (as SamplingParams).
 hipError_t launch_sample_candidates(const float* logits, int vocab, int64_t top_k, float top_p, float min_p, void* scratch,
                                     SampleHeader* header, SampleCandidate* candidates, int capacity, hipStream_t stream);
 // Logits processors on the device.  State: counts[vocab] (occurrences of each token in the history), distinct[] (the tokens
 // with a non-zero count) and *n_distinct, all zero-initialised and advanced by launch_token_counts for every token that
-// joins the history; tokens[len] is the history itself, in order.
+// joins the history; tokens[len] is the history itself, in order.  The repetition penalty is row 0 of
+// launch_repetition_penalty_rows's kernel (a row 0 has no draft, so no ids).
 hipError_t launch_token_counts(const int32_t* tokens, int n, int vocab, int* counts, int32_t* distinct, int* n_distinct, hipStream_t stream);
 hipError_t launch_logits_processors(float* logits, int vocab, const int32_t* tokens, int len, const int* counts, const int32_t* distinct,
                                     const int* n_distinct, float repetition_penalty, int no_repeat_ngram, hipStream_t stream);
 
 // ---- sampled prompt-lookup decoding (LlmModel::generate_lookup_sampled) ---------------------------------------------------------
-// launch_sample_candidates over `rows` (1..8) logits rows of stride ld >= vocab in three launches (the row is blockIdx.y).  Row r
-// uses scratch + r * sample_scratch_bytes() (sample_scratch_rows_bytes(rows) in all, zero-initialised), headers[r] and its own
-// `capacity` candidate slots: per row the one-row launcher's contract, mx and sum bit-identical to it; an overflowing row
-// reports its own count and touches no slot past its capacity and nothing of its neighbours.
+// launch_sample_candidates's kernels over `rows` (1..8) logits rows of stride ld >= vocab: the same three launches with `rows`
+// as the grid's y.  Row r uses scratch + r * sample_scratch_bytes() (sample_scratch_rows_bytes(rows) in all, zero-initialised),
+// headers[r] and its own `capacity` candidate slots: per row the one-row launcher's contract, and -- the same code walking the
+// row with the same 64 workgroups -- mx and sum bit-identical to it; an overflowing row reports its own count and touches no
+// slot past its capacity and nothing of its neighbours.
 // The slots are laid out in chunks of kSampleRowsChunk so that the first 512 candidates of all rows are contiguous: slot s of
 // row r is entry sample_rows_slot(r, s) of `candidates` (sample_rows_entries(capacity) entries whatever `rows` is).  With the
 // headers placed right in front, [8 headers | rows x 512 candidates] is ONE contiguous device-to-host copy; a row with more
@@ -235,7 +241,8 @@ hipError_t launch_sample_candidates_rows(const float* logits, int64_t ld, int ro
                                          void* scratch, SampleHeader* headers, SampleCandidate* candidates, int capacity, hipStream_t stream);
 // The repetition penalty over the rows of a verify block: row r (it predicts the token after ids[0..r]) is penalised for the
 // history that counts / distinct / n_distinct describe (up to and including ids[0]: launch_token_counts's state) plus
-// ids[1..r], once per occurrence, bit-exact against apply_repetition_penalty on the concatenation.
+// ids[1..r], once per occurrence, bit-exact against apply_repetition_penalty on the concatenation.  One kernel serves this
+// launcher (grid 16 x rows) and launch_logits_processors (one row); a `distinct` entry outside [0, vocab) is skipped.
 hipError_t launch_repetition_penalty_rows(float* logits, int64_t ld, int rows, int vocab, const uint32_t* ids, const int* counts,
                                           const int32_t* distinct, const int* n_distinct, float penalty, hipStream_t stream);
 // The host's decision of a sampled verify step: upload[0] = k (0..8) picks, upload[1..k] join history[state->n ..]; state->n and

@@ -973,26 +973,45 @@ __device__ __forceinline__ unsigned long long argmax_key(float v, int idx)
     return ((unsigned long long)u << 32) | (uint32_t)idx;  // equal values: the LAST index wins (Iterator::max_by)
 }
 
-__global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, int vocab,
-                                                             unsigned long long* __restrict__ best)
+// The largest key of the wave, in every lane (butterfly).
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long key)
 {
-    __shared__ unsigned long long red[4];
-    unsigned long long key = 0ull;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
-        const unsigned long long k = argmax_key(logits[i], i);
-        key = k > key ? k : key;
-    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const unsigned long long o = __shfl_xor(key, off, kWave);
         key = o > key ? o : key;
     }
+    return key;
+}
+
+// The largest key of a workgroup of 256 threads, in thread 0 only: the wave butterfly, then the four waves through red[4] (LDS).
+__device__ __forceinline__ unsigned long long block_max_key(unsigned long long key, unsigned long long* red)
+{
+    key = wave_max_key(key);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0)
         for (int w = 1; w < 4; ++w) key = red[w] > key ? red[w] : key;
-        atomicMax(best, key);
+    return key;
+}
+
+// Arg-max of row `first_row + blockIdx.y` of logits [., ld] into best[row], the last maximum wins (argmax_key); the x blocks
+// stride over the row.  Every pick is a grid over this kernel: launch_argmax (one row), launch_lane_pick (live = the lanes'
+// flags: a lane that is not live is not scanned and its slot not touched), launch_lookup_pick (the rows of a verify block).
+__global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int first_row,
+                                                             const int* __restrict__ live, unsigned long long* __restrict__ best)
+{
+    __shared__ unsigned long long red[4];
+    const int r = first_row + blockIdx.y;
+    if (live && !live[r]) return;  // (uniform per workgroup, before the barrier)
+    const float* row = logits + (int64_t)r * ld;
+    unsigned long long key = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
+        const unsigned long long k = argmax_key(row[i], i);
+        key = k > key ? k : key;
     }
+    key = block_max_key(key, red);
+    if (threadIdx.x == 0) atomicMax(best + r, key);
 }
 
 // Publishes the winner, resets the accumulator, and (graph replay) appends the token and advances the counters.
@@ -1899,6 +1918,9 @@ hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream)
 //                   vocabulary -- then appends every token with logit >= m - tau to the candidate list.
 // A list longer than its capacity, or a cut the histogram cannot place, is reported in the header and the host falls back
 // to fetching the logits.
+// The three cut kernels take the row from blockIdx.y: row r of logits [., ld] has scratch[r], headers[r] and its own `cap`
+// candidate slots.  The same SAMPLE_BLOCKS workgroups walk a row in the same order whatever the row count, and the per-workgroup
+// maxima and sums are combined in a fixed order, so a row's mx and sum do not depend on the launcher.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int SAMPLE_BLOCKS = 64, SAMPLE_BINS = 512;
 
@@ -1909,12 +1931,14 @@ struct SampleScratch {                 // device memory, zero-initialised once
     float hist_mass[SAMPLE_BINS + 1];
 };
 
-__global__ __launch_bounds__(256) void sample_max_kernel(const float* __restrict__ logits, int vocab, SampleScratch* __restrict__ sc,
-                                                         SampleHeader* __restrict__ header)
+__global__ __launch_bounds__(256) void sample_max_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                         SampleScratch* __restrict__ scratch, SampleHeader* __restrict__ headers)
 {
     __shared__ float red[4];
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    SampleScratch* sc = scratch + blockIdx.y;
     float m = -INFINITY;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) m = fmaxf(m, logits[i]);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) m = fmaxf(m, row[i]);
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -1925,16 +1949,19 @@ __global__ __launch_bounds__(256) void sample_max_kernel(const float* __restrict
         sc->hist_mass[b] = 0.0f;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        header->count = 0u;
-        header->overflow = 0u;
+        headers[blockIdx.y].count = 0u;
+        headers[blockIdx.y].overflow = 0u;
     }
 }
 
-__global__ __launch_bounds__(256) void sample_hist_kernel(const float* __restrict__ logits, int vocab, SampleScratch* __restrict__ sc)
+__global__ __launch_bounds__(256) void sample_hist_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                          SampleScratch* __restrict__ scratch)
 {
     __shared__ unsigned h_count[SAMPLE_BINS + 1];
     __shared__ float h_mass[SAMPLE_BINS + 1];
     __shared__ float red[4];
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    SampleScratch* sc = scratch + blockIdx.y;
     for (int b = threadIdx.x; b <= SAMPLE_BINS; b += 256) {
         h_count[b] = 0u;
         h_mass[b] = 0.0f;
@@ -1944,7 +1971,7 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(const float* __restric
     __syncthreads();
     float sum = 0.0f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
-        const float v = logits[i];
+        const float v = row[i];
         const float e = expf(v - m);
         const float d = (m - v) * 8.0f;
         const int bin = d < (float)SAMPLE_BINS ? (int)d : SAMPLE_BINS;  // (NaN and -inf land in the last bin)
@@ -1967,7 +1994,7 @@ __global__ __launch_bounds__(256) void sample_hist_kernel(const float* __restric
 // The cut of one row from its scratch: m = the maximum, sum = the per-workgroup sums in their fixed order, tau = how far below
 // the maximum the candidates reach -- enough tokens for top-k, enough mass for top-p (the histogram's masses are summed in no
 // fixed order: a relative margin on top of the two bins), everything min-p can keep when it filters the whole vocabulary.
-// Returns whether no usable cut exists.  Shared by the one-row and the rows kernels (inlined into each).
+// Returns whether no usable cut exists.
 __device__ __forceinline__ bool sample_cut(const SampleScratch* __restrict__ sc, int vocab, long long top_k, float top_p, float min_p,
                                            float& m, float& sum, float& tau)
 {
@@ -1993,13 +2020,19 @@ __device__ __forceinline__ bool sample_cut(const SampleScratch* __restrict__ sc,
     return !(tau < 1e30f) || !(m > -INFINITY) || !(m < INFINITY);
 }
 
-__global__ __launch_bounds__(256) void sample_compact_kernel(const float* __restrict__ logits, int vocab, long long top_k, float top_p,
-                                                             float min_p, const SampleScratch* __restrict__ sc,
-                                                             SampleHeader* __restrict__ header, SampleCandidate* __restrict__ cand, int cap)
+// chunked: slot s of the row is entry sample_rows_slot(row, s) of `candidates` (launch_sample_candidates_rows), else entry s
+// (launch_sample_candidates: one row, a contiguous list).
+__global__ __launch_bounds__(256) void sample_compact_kernel(const float* __restrict__ logits, int64_t ld, int vocab, long long top_k,
+                                                             float top_p, float min_p, const SampleScratch* __restrict__ scratch,
+                                                             SampleHeader* __restrict__ headers, SampleCandidate* __restrict__ candidates,
+                                                             int cap, bool chunked)
 {
     __shared__ float s_floor;
     __shared__ int s_all;
-    if (threadIdx.x == 0) {
+    const float* row = logits + (int64_t)blockIdx.y * ld;
+    const SampleScratch* sc = scratch + blockIdx.y;
+    SampleHeader* header = headers + blockIdx.y;
+    if (threadIdx.x == 0) {  // the cut, from this row's histogram
         float m, sum, tau;
         s_all = sample_cut(sc, vocab, top_k, top_p, min_p, m, sum, tau);
         s_floor = m - tau;
@@ -2021,7 +2054,7 @@ __global__ __launch_bounds__(256) void sample_compact_kernel(const float* __rest
     const int lane = threadIdx.x & 63;
     for (int i0 = blockIdx.x * 256; i0 < vocab; i0 += gridDim.x * 256) {
         const int i = i0 + threadIdx.x;
-        const float v = i < vocab ? logits[i] : -INFINITY;
+        const float v = i < vocab ? row[i] : -INFINITY;
         const bool keep = i < vocab && v >= floor;
         const unsigned long long bits = __ballot(keep);
         if (bits == 0ull) continue;
@@ -2030,7 +2063,7 @@ __global__ __launch_bounds__(256) void sample_compact_kernel(const float* __rest
         base = __shfl(base, 0, kWave);
         if (keep) {
             const unsigned slot = base + (unsigned)__popcll(bits & ((1ull << lane) - 1ull));
-            if (slot < (unsigned)cap) cand[slot] = SampleCandidate{(uint32_t)i, v};
+            if (slot < (unsigned)cap) candidates[chunked ? sample_rows_slot((int)blockIdx.y, (int)slot) : slot] = SampleCandidate{(uint32_t)i, v};
             else header->overflow = 1u;
         }
     }
@@ -2048,17 +2081,39 @@ __global__ __launch_bounds__(256) void token_counts_kernel(const int32_t* __rest
 }
 
 // apply_repetition_penalty (sampling.rs:8-27 / generator.rs:331-337): s < 0 ? s * penalty : s / penalty, once per OCCURRENCE
-// of the token in the history, in sequence (each application rounds)
-__global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restrict__ logits, const int* __restrict__ counts,
-                                                                 const int32_t* __restrict__ distinct,
+// of the token in the history, in sequence (each application rounds).
+// Row r = blockIdx.y of a verify block predicts the token after ids[0..r]: its history is the counted one (up to and including
+// ids[0]) plus ids[1..r].  One thread per distinct token of the counted history, then one per draft position of the row: a draft
+// token the counted history does not hold is handled by the thread of its first occurrence in ids[1..r].  Row 0 never reads
+// ids: launch_logits_processors is the grid of one row with ids == nullptr.
+__global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restrict__ logits, int64_t ld, int vocab, const uint32_t* __restrict__ ids,
+                                                                 const int* __restrict__ counts, const int32_t* __restrict__ distinct,
                                                                  const int* __restrict__ n_distinct, float penalty)
 {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= *n_distinct) return;
-    const int t = distinct[j];
-    float s = logits[t];
-    for (int c = counts[t]; c > 0; --c) s = s < 0.0f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
-    logits[t] = s;
+    const int r = blockIdx.y;
+    float* row = logits + (int64_t)r * ld;
+    const int nd = *n_distinct;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < nd + r; j += gridDim.x * 256) {
+        int t, c;
+        if (j < nd) {
+            t = distinct[j];
+            if (t < 0 || t >= vocab) continue;
+            c = counts[t];
+        } else {
+            const int i = j - nd + 1;
+            if (ids[i] >= (uint32_t)vocab) continue;
+            t = (int)ids[i];
+            if (counts[t] != 0) continue;  // (in `distinct`: the thread above has it)
+            bool first = true;
+            for (int q = 1; q < i; ++q) first = first && ids[q] != ids[i];
+            if (!first) continue;
+            c = 0;
+        }
+        for (int q = 1; q <= r; ++q) c += ids[q] == (uint32_t)t ? 1 : 0;
+        float s = row[t];
+        for (; c > 0; --c) s = s < 0.0f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+        row[t] = s;
+    }
 }
 
 // apply_no_repeat_ngram (sampling.rs:29-57): every window of the history whose first n - 1 tokens equal the last n - 1 bans
@@ -2080,7 +2135,8 @@ hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* bes
 {
     int blocks = (vocab + 2047) / 2048;
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, logits, vocab, best_scratch);
+    hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, logits, (int64_t)0, vocab, 0,
+                       static_cast<const int*>(nullptr), best_scratch);
     hipLaunchKernelGGL(argmax_finalize_kernel, dim3(1), dim3(1), 0, stream, best_scratch, out, history, count, pos);
     return hipGetLastError();
 }
@@ -2088,15 +2144,24 @@ hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* bes
 
 size_t sample_scratch_bytes() { return sizeof(SampleScratch); }
 
+// The cut of `rows` rows: SAMPLE_BLOCKS workgroups per row, whatever the row count, so a row's walk order does not depend on it.
+static hipError_t launch_sample_cut(const float* logits, int64_t ld, int rows, int vocab, int64_t top_k, float top_p, float min_p,
+                                    void* scratch, SampleHeader* headers, SampleCandidate* candidates, int capacity, bool chunked,
+                                    hipStream_t stream)
+{
+    SampleScratch* sc = static_cast<SampleScratch*>(scratch);
+    const dim3 grid(SAMPLE_BLOCKS, (unsigned)rows);
+    hipLaunchKernelGGL(sample_max_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc, headers);
+    hipLaunchKernelGGL(sample_hist_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc);
+    hipLaunchKernelGGL(sample_compact_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, (long long)top_k, top_p, min_p, sc, headers,
+                       candidates, capacity, chunked);
+    return hipGetLastError();
+}
+
 hipError_t launch_sample_candidates(const float* logits, int vocab, int64_t top_k, float top_p, float min_p, void* scratch,
                                     SampleHeader* header, SampleCandidate* candidates, int capacity, hipStream_t stream)
 {
-    SampleScratch* sc = static_cast<SampleScratch*>(scratch);
-    hipLaunchKernelGGL(sample_max_kernel, dim3(SAMPLE_BLOCKS), dim3(256), 0, stream, logits, vocab, sc, header);
-    hipLaunchKernelGGL(sample_hist_kernel, dim3(SAMPLE_BLOCKS), dim3(256), 0, stream, logits, vocab, sc);
-    hipLaunchKernelGGL(sample_compact_kernel, dim3(SAMPLE_BLOCKS), dim3(256), 0, stream, logits, vocab, (long long)top_k, top_p, min_p, sc,
-                       header, candidates, capacity);
-    return hipGetLastError();
+    return launch_sample_cut(logits, 0, 1, vocab, top_k, top_p, min_p, scratch, header, candidates, capacity, false, stream);
 }
 
 hipError_t launch_token_counts(const int32_t* tokens, int n, int vocab, int* counts, int32_t* distinct, int* n_distinct, hipStream_t stream)
@@ -2112,7 +2177,7 @@ hipError_t launch_logits_processors(float* logits, int vocab, const int32_t* tok
 {
     if (repetition_penalty != 1.0f && len > 0)
         hipLaunchKernelGGL(repetition_penalty_kernel, dim3((unsigned)((std::min(len, vocab) + 255) / 256)), dim3(256), 0, stream, logits,
-                           counts, distinct, n_distinct, repetition_penalty);
+                           (int64_t)0, vocab, static_cast<const uint32_t*>(nullptr), counts, distinct, n_distinct, repetition_penalty);
     if (no_repeat_ngram > 0 && len + 1 >= no_repeat_ngram && len >= no_repeat_ngram)
         hipLaunchKernelGGL(no_repeat_ngram_kernel, dim3((unsigned)((len - no_repeat_ngram + 1 + 255) / 256)), dim3(256), 0, stream, logits,
                            vocab, tokens, len, no_repeat_ngram);
@@ -2389,32 +2454,6 @@ __global__ __launch_bounds__(256) void lane_rope_scatter_kernel(float* __restric
     for (int i = threadIdx.x; i < kv; i += 256) vdst[i] = row[H + kv + i];
 }
 
-// Per-lane argmax, the last maximum wins (argmax_key); lanes that are not live are not scanned.
-__global__ __launch_bounds__(256) void lane_argmax_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int first_lane,
-                                                                  const int* __restrict__ live, unsigned long long* __restrict__ best)
-{
-    __shared__ unsigned long long red[4];
-    const int lane_id = first_lane + blockIdx.y;
-    if (!live[lane_id]) return;
-    const float* row = logits + (int64_t)lane_id * ld;
-    unsigned long long key = 0ull;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
-        const unsigned long long kk = argmax_key(row[i], i);
-        key = kk > key ? kk : key;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off, kWave);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) key = red[w] > key ? red[w] : key;
-        atomicMax(best + lane_id, key);
-    }
-}
-
 // The pick of a live lane: the token joins the lane's history, count (and, after a step, pos) advance; the lane stays live
 // -- and the token becomes its next input -- unless the token is one of its stop ids, it has its max_new_tokens, or its
 // cache is full.
@@ -2526,8 +2565,8 @@ hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lane
     if (first_lane < 0 || first_lane + lanes > LLM_MAX_ROWS) return hipErrorInvalidValue;
     int blocks = (vocab + 2047) / 2048;
     if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(lane_argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)lanes), dim3(256), 0, stream, logits, ld, vocab,
-                       first_lane, state->live, best_scratch);
+    hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)lanes), dim3(256), 0, stream, logits, ld, vocab, first_lane,
+                       static_cast<const int*>(state->live), best_scratch);
     hipLaunchKernelGGL(lane_pick_finalize_kernel, dim3(1), dim3(64), 0, stream, best_scratch, state, history, hist_stride, first_lane, lanes,
                        capacity, advance);
     return hipGetLastError();
@@ -2704,11 +2743,7 @@ __global__ __launch_bounds__(LOOKUP_THREADS) void lookup_draft_kernel(const int3
         const unsigned long long k = ((unsigned long long)m << 40) | ((unsigned long long)c << 32) | (uint32_t)e;
         key = k > key ? k : key;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off, kWave);
-        key = o > key ? o : key;
-    }
+    key = wave_max_key(key);
     if ((tid & (kWave - 1)) == 0) red[tid / kWave] = key;
     __syncthreads();
     if (tid >= rows) return;
@@ -2721,30 +2756,6 @@ __global__ __launch_bounds__(LOOKUP_THREADS) void lookup_draft_kernel(const int3
     if (tid > 0 && c > 0) src = e + (tid <= c ? tid : c) - 1;
     ids[tid] = n > 0 ? (uint32_t)T[src] : 0u;
     if (tid == 0) st->m = c;
-}
-
-// Row-wise argmax of logits [rows, ld], the last maximum wins (argmax_key): blockIdx.y is the row.
-__global__ __launch_bounds__(256) void lookup_argmax_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                                    unsigned long long* __restrict__ best)
-{
-    __shared__ unsigned long long red[4];
-    const float* row = logits + (int64_t)blockIdx.y * ld;
-    unsigned long long key = 0ull;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
-        const unsigned long long kk = argmax_key(row[i], i);
-        key = kk > key ? kk : key;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off, kWave);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) key = red[w] > key ? red[w] : key;
-        atomicMax(best + blockIdx.y, key);
-    }
 }
 
 // The verify pick: p_i = argmax(row i); a = the longest prefix of the draft with ids[1 + i] == p_i; p_0..p_a are the model's
@@ -2799,8 +2810,8 @@ hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int ro
     if (rows < 1 || rows > LLM_MAX_ROWS) return hipErrorInvalidValue;
     int blocks = (vocab + 2047) / 2048;
     if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(lookup_argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab,
-                       best_scratch);
+    hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, 0,
+                       static_cast<const int*>(nullptr), best_scratch);
     hipLaunchKernelGGL(lookup_pick_kernel, dim3(1), dim3(64), 0, stream, best_scratch, ids, rows, state, history, hist_cap, pos, log, log_cap);
     return hipGetLastError();
 }
@@ -3122,11 +3133,7 @@ __global__ __launch_bounds__(256) void llm_score_rows_kernel(const float* __rest
             const unsigned long long kk = argmax_key(row[i], i);
             key = kk > key ? kk : key;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_xor(key, off, kWave);
-            key = o > key ? o : key;
-        }
+        key = wave_max_key(key);
         if ((threadIdx.x & 63) == 0) red_key[threadIdx.x >> 6] = key;
         __syncthreads();
         key = red_key[0];
@@ -3258,153 +3265,8 @@ hipError_t launch_score_rows_topk(const float* logits, int64_t ld, int rows, int
 }
 
 // ---- sampled prompt-lookup decoding (LlmModel::generate_lookup_sampled): the sampler's cut and the repetition penalty over the
-// rows of a verify block.  The three cut kernels are sample_max / sample_hist / sample_compact with the row in blockIdx.y: the
-// same 64 workgroups per row walk the row in the same order, so a row's mx and sum are bit-identical to the one-row launcher's;
-// every row has its own SampleScratch, SampleHeader and `cap` candidate slots (sample_rows_slot: the rows' first 512 slots lie
-// side by side, so that one contiguous copy brings the headers' neighbours over).  (Kernels of their own rather than the
-// one-row kernels templated: the one-row path keeps its code and registers.)
+// rows of a verify block are the kernels of sampled decoding above with rows in blockIdx.y; the commit of a step's picks.
 namespace {
-
-__global__ __launch_bounds__(256) void sample_max_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                              SampleScratch* __restrict__ scratch, SampleHeader* __restrict__ headers)
-{
-    __shared__ float red[4];
-    const float* row = logits + (int64_t)blockIdx.y * ld;
-    SampleScratch* sc = scratch + blockIdx.y;
-    float m = -INFINITY;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) m = fmaxf(m, row[i]);
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) sc->part_max[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    for (int b = blockIdx.x * 256 + threadIdx.x; b <= SAMPLE_BINS; b += gridDim.x * 256) {
-        sc->hist_count[b] = 0u;
-        sc->hist_mass[b] = 0.0f;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        headers[blockIdx.y].count = 0u;
-        headers[blockIdx.y].overflow = 0u;
-    }
-}
-
-__global__ __launch_bounds__(256) void sample_hist_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                               SampleScratch* __restrict__ scratch)
-{
-    __shared__ unsigned h_count[SAMPLE_BINS + 1];
-    __shared__ float h_mass[SAMPLE_BINS + 1];
-    __shared__ float red[4];
-    const float* row = logits + (int64_t)blockIdx.y * ld;
-    SampleScratch* sc = scratch + blockIdx.y;
-    for (int b = threadIdx.x; b <= SAMPLE_BINS; b += 256) {
-        h_count[b] = 0u;
-        h_mass[b] = 0.0f;
-    }
-    float m = -INFINITY;
-    for (int b = 0; b < SAMPLE_BLOCKS; ++b) m = fmaxf(m, sc->part_max[b]);
-    __syncthreads();
-    float sum = 0.0f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < vocab; i += gridDim.x * 256) {
-        const float v = row[i];
-        const float e = expf(v - m);
-        const float d = (m - v) * 8.0f;
-        const int bin = d < (float)SAMPLE_BINS ? (int)d : SAMPLE_BINS;  // (NaN and -inf land in the last bin)
-        sum += e;
-        atomicAdd(&h_count[bin], 1u);
-        atomicAdd(&h_mass[bin], e);
-    }
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) sc->part_sum[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-    for (int b = threadIdx.x; b <= SAMPLE_BINS; b += 256) {
-        if (h_count[b]) {
-            atomicAdd(&sc->hist_count[b], h_count[b]);
-            atomicAdd(&sc->hist_mass[b], h_mass[b]);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void sample_compact_rows_kernel(const float* __restrict__ logits, int64_t ld, int vocab, long long top_k,
-                                                                  float top_p, float min_p, const SampleScratch* __restrict__ scratch,
-                                                                  SampleHeader* __restrict__ headers, SampleCandidate* __restrict__ candidates,
-                                                                  int cap)
-{
-    __shared__ float s_floor;
-    __shared__ int s_all;
-    const float* row = logits + (int64_t)blockIdx.y * ld;
-    const SampleScratch* sc = scratch + blockIdx.y;
-    SampleHeader* header = headers + blockIdx.y;
-    if (threadIdx.x == 0) {  // the cut, from this row's histogram
-        float m, sum, tau;
-        s_all = sample_cut(sc, vocab, top_k, top_p, min_p, m, sum, tau);
-        s_floor = m - tau;
-        if (blockIdx.x == 0) {
-            header->mx = m;
-            header->sum = sum;
-            header->floor = s_all ? -INFINITY : m - tau;
-        }
-    }
-    __syncthreads();
-    if (s_all) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            header->count = (uint32_t)vocab;
-            header->overflow = 1u;
-        }
-        return;
-    }
-    const float floor = s_floor;
-    const int lane = threadIdx.x & 63;
-    for (int i0 = blockIdx.x * 256; i0 < vocab; i0 += gridDim.x * 256) {
-        const int i = i0 + threadIdx.x;
-        const float v = i < vocab ? row[i] : -INFINITY;
-        const bool keep = i < vocab && v >= floor;
-        const unsigned long long bits = __ballot(keep);
-        if (bits == 0ull) continue;
-        unsigned base = 0u;
-        if (lane == 0) base = atomicAdd(&header->count, (unsigned)__popcll(bits));
-        base = __shfl(base, 0, kWave);
-        if (keep) {
-            const unsigned slot = base + (unsigned)__popcll(bits & ((1ull << lane) - 1ull));
-            if (slot < (unsigned)cap) candidates[sample_rows_slot((int)blockIdx.y, (int)slot)] = SampleCandidate{(uint32_t)i, v};
-            else header->overflow = 1u;
-        }
-    }
-}
-
-// Row r of a verify block predicts the token after ids[0..r]: its history is the counted one (up to and including ids[0]) plus
-// ids[1..r].  One thread per distinct token of the counted history, then one per draft position of the row: a draft token the
-// counted history does not hold is handled by the thread of its first occurrence in ids[1..r].  Each thread applies the
-// penalty once per occurrence, each application rounded, as repetition_penalty_kernel does.
-__global__ __launch_bounds__(256) void repetition_penalty_rows_kernel(float* __restrict__ logits, int64_t ld, int vocab,
-                                                                      const uint32_t* __restrict__ ids, const int* __restrict__ counts,
-                                                                      const int32_t* __restrict__ distinct,
-                                                                      const int* __restrict__ n_distinct, float penalty)
-{
-    const int r = blockIdx.y;
-    float* row = logits + (int64_t)r * ld;
-    const int nd = *n_distinct;
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < nd + r; j += gridDim.x * 256) {
-        int t, c;
-        if (j < nd) {
-            t = distinct[j];
-            if (t < 0 || t >= vocab) continue;
-            c = counts[t];
-        } else {
-            const int i = j - nd + 1;
-            if (ids[i] >= (uint32_t)vocab) continue;
-            t = (int)ids[i];
-            if (counts[t] != 0) continue;  // (in `distinct`: the thread above has it)
-            bool first = true;
-            for (int q = 1; q < i; ++q) first = first && ids[q] != ids[i];
-            if (!first) continue;
-            c = 0;
-        }
-        for (int q = 1; q <= r; ++q) c += ids[q] == (uint32_t)t ? 1 : 0;
-        float s = row[t];
-        for (; c > 0; --c) s = s < 0.0f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
-        row[t] = s;
-    }
-}
 
 // The host's decision of a sampled verify step joins the device state: up[0] = how many picks, up[1..] = the picks.
 __global__ void lookup_commit_kernel(const int32_t* __restrict__ up, LlmLookupState* __restrict__ st, int32_t* __restrict__ history,
@@ -3428,13 +3290,7 @@ hipError_t launch_sample_candidates_rows(const float* logits, int64_t ld, int ro
                                          void* scratch, SampleHeader* headers, SampleCandidate* candidates, int capacity, hipStream_t stream)
 {
     if (rows < 1 || rows > LLM_MAX_ROWS || vocab < 1 || ld < (int64_t)vocab || capacity < 1) return hipErrorInvalidValue;
-    SampleScratch* sc = static_cast<SampleScratch*>(scratch);
-    const dim3 grid(SAMPLE_BLOCKS, (unsigned)rows);
-    hipLaunchKernelGGL(sample_max_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc, headers);
-    hipLaunchKernelGGL(sample_hist_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, sc);
-    hipLaunchKernelGGL(sample_compact_rows_kernel, grid, dim3(256), 0, stream, logits, ld, vocab, (long long)top_k, top_p, min_p, sc, headers,
-                       candidates, capacity);
-    return hipGetLastError();
+    return launch_sample_cut(logits, ld, rows, vocab, top_k, top_p, min_p, scratch, headers, candidates, capacity, true, stream);
 }
 
 hipError_t launch_repetition_penalty_rows(float* logits, int64_t ld, int rows, int vocab, const uint32_t* ids, const int* counts,
@@ -3442,7 +3298,7 @@ hipError_t launch_repetition_penalty_rows(float* logits, int64_t ld, int rows, i
 {
     if (rows < 1 || rows > LLM_MAX_ROWS || vocab < 1 || ld < (int64_t)vocab) return hipErrorInvalidValue;
     if (penalty == 1.0f) return hipSuccess;
-    hipLaunchKernelGGL(repetition_penalty_rows_kernel, dim3(16, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, ids, counts, distinct,
+    hipLaunchKernelGGL(repetition_penalty_kernel, dim3(16, (unsigned)rows), dim3(256), 0, stream, logits, ld, vocab, ids, counts, distinct,
                        n_distinct, penalty);
     return hipGetLastError();
 }
