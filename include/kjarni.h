@@ -99,7 +99,9 @@ typedef struct KjarniEmbedderConfig {
     KjarniDevice device;
     const char* cache_dir;  /* NULL = default cache */
     const char* model_name; /* NULL = "minilm-l6-v2" */
-    const char* model_path; /* NULL = registry */
+    const char* model_path; /* NULL = registry; a llama / qwen2 / qwen3 / mistral directory loads a decoder embedder
+                             * (last-token pooling; tokenizer with add_special_tokens = true; texts cut to
+                             * min(max_position_embeddings, 2048) tokens), as do the names qwen3-embedding-0.6b / -4b / -8b */
     int32_t normalize;      /* honoured by encode / similarity, not by encode_batch */
     int32_t quiet;
 } KjarniEmbedderConfig;

@@ -816,6 +816,56 @@ KjarniErrorCode kjarni_hip_op_qk_norm_rope(int32_t device, float* q, int64_t ldq
                                            int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* gamma_q,
                                            const float* gamma_k, float eps, const float* cos_t, const float* sin_t, int32_t table_rows,
                                            int32_t pos, int32_t pos_on_device, int32_t k_at_cache_row);
+/* ---- decoder embedders: last-token pooling over a packed batch -----------------------------------------------------------------
+ * kjarni_hip_decoder_embed: sequence b is ids[offsets[b], offsets[b + 1]); out [n_sequences, hidden] receives the final-normed
+ * hidden state of every sequence's last token, L2-normalised when `normalize` (x / ||x|| when ||x|| > 0).  The sequences are
+ * packed in order into chunks of at most KJARNI_HIP_EMBED_CHUNK_ROWS rows (kjarni_hip_embed_plan) and every chunk runs the
+ * prompt routes of kjarni_hip_decoder_forward once over all its rows, with causal attention that stops at the sequence
+ * boundaries.  The KV cache, the resident tokens, the lanes, the logits and the last hidden rows are left as they were.
+ * INVALID_CONFIG, before any GPU work, naming the argument and the sequence: offsets that decrease, an empty sequence, an
+ * id >= vocab, a sequence longer than min(context, KJARNI_HIP_EMBED_CHUNK_ROWS); also for GPT-2 and quantized checkpoints and
+ * for hidden / heads * head_dim / intermediate sizes that are no multiple of 32.  n_sequences == 0 is OK and writes nothing. */
+#define KJARNI_HIP_EMBED_CHUNK_ROWS 2048
+KjarniErrorCode kjarni_hip_decoder_embed(KjarniHipDecoder* decoder, const uint32_t* ids, const int32_t* offsets, int32_t n_sequences,
+                                         int32_t normalize, float* out);
+/* The packing rule alone (host only).  lengths[n], each 1 .. KJARNI_HIP_EMBED_CHUNK_ROWS (else INVALID_CONFIG naming the entry):
+ * sequences go greedily, in order, into chunks of at most KJARNI_HIP_EMBED_CHUNK_ROWS rows and never straddle one.
+ * chunk_first_seq (n + 1 entries, may be NULL) receives each chunk's first sequence and, behind the last, n; *n_chunks the count.
+ * A sequence of at least 256 rows with head_dim 64 or 128 contributes one block per 128 query rows to the matrix-core table,
+ * every other sequence one block per 32 query rows to the vector table; a block is four words (chunk, the sequence's first row
+ * in the chunk, the block's first query row in the sequence, the sequence's length).  vec_blocks / mfma_blocks (may be NULL)
+ * receive the first vec_capacity / mfma_capacity blocks, *n_vec / *n_mfma the counts. */
+KjarniErrorCode kjarni_hip_embed_plan(const int32_t* lengths, int32_t n, int32_t head_dim, int32_t* chunk_first_seq, int32_t* n_chunks,
+                                      int32_t* vec_blocks, int32_t vec_capacity, int32_t* n_vec, int32_t* mfma_blocks, int32_t mfma_capacity,
+                                      int32_t* n_mfma);
+/* The packed attention kernels alone, host pointers.  q [buffer_rows, ldq] (heads * head_dim used), k / v [buffer_rows, ldk / ldv]
+ * (kv_heads * head_dim used); sequence b is rows seq_start[b] .. seq_start[b + 1] - 1 (seq_start[0] == 0, increasing,
+ * seq_start[n_sequences] <= buffer_rows).  ctx [buffer_rows, ldc] is read, gets the context rows of every sequence (query row r
+ * sees the keys of its own sequence up to r) and is written back whole.  head_dim 16 / 32 / 64 / 128, leading dimensions
+ * multiples of 4.  Sequences of at least 256 rows with head_dim 64 / 128 run on the matrix-core kernel, the others on the vector
+ * kernel, in the same call.  Out-of-range arguments: INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_packed_causal_attention(int32_t device, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                                      int64_t ldv, int32_t buffer_rows, const int32_t* seq_start, int32_t n_sequences,
+                                                      int32_t heads, int32_t kv_heads, int32_t head_dim, float* ctx, int64_t ldc);
+/* RoPE alone, host pointers: x [x_rows, ldx] is read, its first `rows` rows (n_heads heads of head_dim) are rotated in place and
+ * it is written back whole.  kjarni_hip_op_rope: row r by table row pos + r (the kernel of the prompt and decode paths);
+ * kjarni_hip_op_rope_rows: row r by table row row_pos[r].  cos_t / sin_t [table_rows, head_dim / 2].  Positions outside the
+ * tables: INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_rope(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads, int32_t head_dim,
+                                   const float* cos_t, const float* sin_t, int32_t table_rows, int32_t pos);
+KjarniErrorCode kjarni_hip_op_rope_rows(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads, int32_t head_dim,
+                                        const float* cos_t, const float* sin_t, int32_t table_rows, const int32_t* row_pos);
+/* kjarni_hip_op_qk_norm_rope with row r at position row_pos[r] (its K heads are row r of k). */
+KjarniErrorCode kjarni_hip_op_qk_norm_rope_rows(int32_t device, float* q, int64_t ldq, int32_t q_rows, float* k, int64_t ldk, int32_t k_rows,
+                                                int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* gamma_q,
+                                                const float* gamma_k, float eps, const float* cos_t, const float* sin_t, int32_t table_rows,
+                                                const int32_t* row_pos);
+/* The last-token pool alone, host pointers: x [x_rows, ldx]; out [n_sequences, hidden] receives, for every sequence, row
+ * seq_start[b + 1] - 1 of x through (x / sqrt(mean(x^2) + eps)) * gamma and, when `normalize`, divided by its L2 norm when that is
+ * > 0.  seq_start increasing from >= 0, seq_start[n_sequences] <= x_rows, hidden 1 .. 16384. */
+KjarniErrorCode kjarni_hip_op_last_token_pool(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* seq_start,
+                                              int32_t n_sequences, int32_t hidden, const float* gamma, float eps, int32_t normalize,
+                                              float* out);
 /* The switch and the counters on the Chat and Generator handles' models (send, generate, score and generate_batch take it). */
 KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);
@@ -842,6 +892,13 @@ KjarniErrorCode kjarni_bpe_tokenizer_encode(const KjarniBpeTokenizer* tokenizer,
 KjarniErrorCode kjarni_bpe_tokenizer_decode(const KjarniBpeTokenizer* tokenizer, const uint32_t* ids, size_t n, int32_t skip_special,
                                             char** out);
 KjarniErrorCode kjarni_bpe_tokenizer_pre_tokenize(const KjarniBpeTokenizer* tokenizer, const char* text, KjarniStringArray* out);
+/* The embedding entry of the BPE tokenizer: encode(text, add_special_tokens = true).  The `single` template of a
+ * TemplateProcessing post-processor (top-level or inside a Sequence) frames the ids: the special tokens before and after $A are
+ * added; no post-processor, or ByteLevel alone, adds nothing.  max_length (0: none) truncates the sequence's own tokens from the
+ * right so that the framed length is at most max_length; the framing tokens always survive.  A tokenizer.json with any other
+ * post-processor type: INVALID_CONFIG naming the type. */
+KjarniErrorCode kjarni_bpe_tokenizer_encode_embedding(const KjarniBpeTokenizer* tokenizer, const char* text, size_t max_length,
+                                                      uint32_t* ids_out, size_t capacity, size_t* n_out);
 
 /* ChatTemplate::apply (crates/kjarni-transformers/src/chat/{llama3,chatml,mistral}.rs): template_kind 0 = Llama 3
  * (for_generation), 1 = ChatML, 2 = Mistral; roles 0 system / 1 user / 2 assistant. */

@@ -249,6 +249,17 @@ class BpeTokenizer:
                                                       C.byref(n)))
         return ids[: n.value].tolist()
 
+    def encode_embedding(self, text: str, max_length: int = 0) -> List[int]:
+        """encode(text, add_special_tokens=True): encode()'s ids framed by the special tokens of the post-processor's `single`
+        template; max_length cuts the text's own tokens from the right, the framing tokens survive."""
+        raw = text.encode("utf-8")
+        n = C.c_size_t()
+        cap = len(raw) + 64
+        ids = np.zeros(cap, np.uint32)
+        check_error(lib().kjarni_bpe_tokenizer_encode_embedding(self._handle, raw, max_length, ids.ctypes.data_as(C.POINTER(C.c_uint32)), cap,
+                                                                C.byref(n)))
+        return ids[: n.value].tolist()
+
     def decode(self, ids: Sequence[int], skip_special: bool = False) -> str:
         a = np.ascontiguousarray(ids, np.uint32)
         out = C.c_void_p()

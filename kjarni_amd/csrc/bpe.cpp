@@ -11,6 +11,7 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "ffi_common.h"
 #include "json.h"
 #include "unicode.h"
 
@@ -401,6 +402,74 @@ void BpeTokenizer::load_json(const std::string& text, const std::string& origin)
         }
     for (auto& v : added_by_first_) v.clear();
     for (size_t i = 0; i < added_.size(); ++i) added_by_first_[(uint8_t)added_[i].match[0]].push_back((uint32_t)i);
+
+    // post-processor: only the embedding entry reads it, so a shape it cannot apply is recorded here and refused there
+    frame_before_.clear();
+    frame_after_.clear();
+    frame_error_.clear();
+    if (const Json* pp = j.find("post_processor"); pp && !pp->is_null()) {
+        if (pp->get_string("type", "") == "Sequence") {
+            const Json* list = pp->find("processors");
+            if (!list || !list->is_array()) frame_error_ = origin + ": post_processor Sequence without a list of processors";
+            else
+                for (const Json& e : list->arr) load_post_processor(e, origin);
+        } else {
+            load_post_processor(*pp, origin);
+        }
+    }
+}
+
+// One post-processor: ByteLevel adds no token; TemplateProcessing's `single` template gives the special tokens before and
+// after $A (tokenizers/src/processors/template.rs: pieces {"Sequence": {"id": "A"}} and {"SpecialToken": {"id": name}}, the ids
+// of `name` in special_tokens[name].ids).
+void BpeTokenizer::load_post_processor(const Json& pp, const std::string& origin)
+{
+    if (!frame_error_.empty()) return;
+    const std::string type = pp.get_string("type", "");
+    if (type == "ByteLevel") return;
+    if (type != "TemplateProcessing") {
+        frame_error_ = origin + ": unsupported post_processor '" + type + "' (expected TemplateProcessing and / or ByteLevel)";
+        return;
+    }
+    if (!frame_before_.empty() || !frame_after_.empty()) {
+        frame_error_ = origin + ": more than one TemplateProcessing post_processor";
+        return;
+    }
+    const Json* single = pp.find("single");
+    const Json* specials = pp.find("special_tokens");
+    if (!single || !single->is_array()) {
+        frame_error_ = origin + ": TemplateProcessing without a `single` template";
+        return;
+    }
+    bool seen_a = false;
+    for (const Json& piece : single->arr) {
+        if (const Json* seq = piece.find("Sequence")) {
+            if (seq->get_string("id", "") != "A" || seen_a) {
+                frame_error_ = origin + ": TemplateProcessing `single` template must hold sequence A once";
+                return;
+            }
+            seen_a = true;
+        } else if (const Json* sp = piece.find("SpecialToken")) {
+            const std::string name = sp->get_string("id", "");
+            std::vector<uint32_t>& dst = seen_a ? frame_after_ : frame_before_;
+            const Json* entry = specials ? specials->find(name) : nullptr;
+            const Json* ids = entry ? entry->find("ids") : nullptr;
+            if (ids && ids->is_array() && !ids->arr.empty()) {
+                for (const Json& id : ids->arr) dst.push_back((uint32_t)id.as_int());
+            } else {
+                uint32_t id = 0;
+                if (!token_to_id(name, id)) {
+                    frame_error_ = origin + ": TemplateProcessing special token '" + name + "' has no id";
+                    return;
+                }
+                dst.push_back(id);
+            }
+        } else {
+            frame_error_ = origin + ": TemplateProcessing piece that is neither Sequence nor SpecialToken";
+            return;
+        }
+    }
+    if (!seen_a) frame_error_ = origin + ": TemplateProcessing `single` template without sequence A";
 }
 
 bool BpeTokenizer::token_to_id(const std::string& token, uint32_t& id) const
@@ -804,6 +873,23 @@ std::vector<uint32_t> BpeTokenizer::encode(const std::string& text, size_t max_l
         }
     }
     if (max_length && ids.size() > max_length) ids.resize(max_length);
+    return ids;
+}
+
+std::vector<uint32_t> BpeTokenizer::encode_for_embedding(const std::string& text, size_t max_length) const
+{
+    if (!frame_error_.empty()) throw InvalidConfig(frame_error_);
+    std::vector<uint32_t> own = encode(text, 0);
+    const size_t frame = frame_before_.size() + frame_after_.size();
+    if (max_length) {  // (truncation.rs: the sequence is cut to max_length - the tokens the post-processor adds)
+        const size_t keep = max_length > frame ? max_length - frame : 0;
+        if (own.size() > keep) own.resize(keep);
+    }
+    std::vector<uint32_t> ids;
+    ids.reserve(own.size() + frame);
+    ids.insert(ids.end(), frame_before_.begin(), frame_before_.end());
+    ids.insert(ids.end(), own.begin(), own.end());
+    ids.insert(ids.end(), frame_after_.begin(), frame_after_.end());
     return ids;
 }
 

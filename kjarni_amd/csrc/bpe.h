@@ -9,7 +9,8 @@
 //   pre-tokenizer           -> Split(<Llama 3 | Qwen 2 regex>, Isolated) + ByteLevel(use_regex = false), or
 //                              ByteLevel(use_regex = true) (the GPT-2 regex)
 //   model                   -> BPE (merge ranks, ignore_merges), no dropout
-//   post-processor          -> skipped (add_special_tokens = false)
+//   post-processor          -> skipped by encode() (add_special_tokens = false); encode_for_embedding() applies the `single`
+//                              template of a TemplateProcessing post-processor (add_special_tokens = true)
 // and the SentencePiece-style shape of Llama 2 / Mistral files: Prepend + Replace normalizer (or a non-splitting Metaspace
 // pre-tokenizer), BPE with byte fallback and a fused <unk>, decoder Replace + ByteFallback + Fuse + Strip.
 // Anything else in the file is a load error rather than a silently different tokenization.
@@ -31,6 +32,14 @@ public:
     // Tokenizer::encode(text, add_special_tokens = false).get_ids(), right-truncated to max_length when set.
     std::vector<uint32_t> encode(const std::string& text) const { return encode(text, max_length_); }
     std::vector<uint32_t> encode(const std::string& text, size_t max_length) const;  // 0 = no truncation
+    // Tokenizer::encode(text, add_special_tokens = true).get_ids(), what every embedder of the reference calls: the ids of
+    // encode(text) framed by the special tokens the post-processor's `single` template puts before and after $A
+    // (TemplateProcessing, top-level or inside a Sequence; none, or ByteLevel alone, adds nothing).  max_length (0 = none): the
+    // sequence's own tokens are cut from the right so that the framed length is at most max_length; the framing always survives.
+    // Throws InvalidConfig naming the type when the file has any other post-processor.
+    std::vector<uint32_t> encode_for_embedding(const std::string& text, size_t max_length) const;
+    // Empty, or why encode_for_embedding() refuses this file.
+    const std::string& embedding_frame_error() const { return frame_error_; }
     // Tokenizer::decode(ids, skip_special_tokens) with the ByteLevel decoder: String::from_utf8_lossy of the bytes.
     std::string decode(const std::vector<uint32_t>& ids, bool skip_special) const;
     bool token_to_id(const std::string& token, uint32_t& id) const;
@@ -53,6 +62,7 @@ private:
     };
 
     void split_on_added(const std::string& text, bool normalized_set, std::vector<Split>& out) const;
+    void load_post_processor(const Json& pp, const std::string& origin);
     void encode_segment(const std::string& text, std::vector<uint32_t>& out) const;
     void scan_pieces(const std::vector<uint32_t>& cps, std::vector<std::pair<size_t, size_t>>& pieces) const;
     void bpe_word(const std::string& piece_utf8, std::vector<uint32_t>& out) const;
@@ -73,6 +83,8 @@ private:
     bool nfc_ = false, add_prefix_space_ = false, ignore_merges_ = false, has_unk_ = false, fuse_unk_ = false;
     uint32_t unk_id_ = 0;
     size_t max_length_ = 0;
+    std::vector<uint32_t> frame_before_, frame_after_;  // the `single` template's special tokens around $A
+    std::string frame_error_;
     // SentencePiece-style mode
     bool sp_mode_ = false;
     int sp_prepend_ = 0;  // 0 = Prepend normalizer (every segment), 1 = Metaspace first, 2 = Metaspace always, 3 = never

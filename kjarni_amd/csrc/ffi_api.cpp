@@ -12,10 +12,12 @@
 #include <mutex>
 #include <numeric>
 
+#include "bpe.h"
 #include "host_util.h"
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
 #include "json.h"
+#include "llm.h"
 #include "pipeline.h"
 #include "registry.h"
 #include "unicode.h"
@@ -178,10 +180,83 @@ KJARNI_EXPORT float kjarni_cosine_similarity(const float* a, const float* b, siz
 
 // ---- Embedder ----------------------------------------------------------------
 
+// A decoder checkpoint (llama / qwen2 / qwen3 / mistral) as an embedder: last-token pooling over LlmModel::embed_batch.
+struct DecoderEmbedder {
+    std::unique_ptr<LlmModel> model;
+    BpeTokenizer tokenizer;
+    std::mutex mu;  // embed_batch uses the model's one workspace and stream
+
+    // Tokenizer::encode(text, add_special_tokens = true) per text, framed length at most the embed length limit -> [n, hidden]
+    std::vector<float> embed(const std::vector<std::string>& texts, bool normalize)
+    {
+        const size_t H = (size_t)model->config().hidden;
+        std::vector<uint32_t> ids;
+        std::vector<int32_t> offsets{0};
+        for (const std::string& t : texts) {
+            const std::vector<uint32_t> one = tokenizer.encode_for_embedding(t, (size_t)model->embed_max_tokens());
+            if (one.empty()) throw std::runtime_error("a text tokenizes to no token and the tokenizer adds none: nothing to pool");
+            ids.insert(ids.end(), one.begin(), one.end());
+            if (ids.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error("more than 2^31 - 1 tokens in one call");
+            offsets.push_back((int32_t)ids.size());
+        }
+        std::vector<float> out(texts.size() * H);
+        std::lock_guard<std::mutex> lock(mu);
+        model->embed_batch(ids.data(), offsets.data(), (int)texts.size(), normalize, out.data());
+        return out;
+    }
+};
+
 struct KjarniEmbedder {
     std::unique_ptr<Pipeline> p;
+    std::unique_ptr<DecoderEmbedder> dec;  // set instead of p for a decoder checkpoint
     bool normalize = true;
+    size_t hidden() const { return dec ? (size_t)dec->model->config().hidden : (size_t)p->config().hidden; }
+    std::vector<float> embed(const std::vector<std::string>& texts, bool norm)
+    {
+        return dec ? dec->embed(texts, norm) : embed_texts(*p, texts, POOL_MEAN, norm);
+    }
 };
+
+namespace {
+
+// The directory of a decoder embedder, or "" when the request names an encoder (or nothing this function knows): model_path
+// with a decoder model_type in its config.json, or a registry name of a decoder embedder.
+std::string decoder_embedder_dir(const KjarniEmbedderConfig& c)
+{
+    if (c.model_path) {
+        const std::string dir = c.model_path;
+        if (!is_dir(dir) || !model_files_present(dir)) return "";  // (load_pipeline reports it)
+        std::string type;
+        try {
+            type = Json::parse(slurp(dir + "/config.json")).get_string("model_type", "");
+        } catch (...) {
+            return "";
+        }
+        return (type == "llama" || type == "qwen2" || type == "qwen3" || type == "mistral") ? dir : "";
+    }
+    if (!c.model_name) return "";
+    std::string err;
+    const RegistryEntry* e = resolve_model(c.model_name, err);
+    if (!e || e->arch != ModelArch::Decoder || e->task != ModelTask::Embedding) return "";
+    const std::string dir = model_dir_for(*e, c.cache_dir ? std::string(c.cache_dir) : default_cache_dir());
+    if (!model_files_present(dir))
+        throw ModelNotFound(std::string("Model '") + e->cli_name + "' is not downloaded (expected config.json, tokenizer.json and "
+                            "model.safetensors in " + dir + "); this build never downloads models");
+    return dir;
+}
+
+std::unique_ptr<DecoderEmbedder> load_decoder_embedder(const std::string& dir)
+{
+    auto d = std::make_unique<DecoderEmbedder>();
+    d->tokenizer.load(dir + "/tokenizer.json");
+    if (!d->tokenizer.embedding_frame_error().empty()) throw std::runtime_error(d->tokenizer.embedding_frame_error());
+    const std::vector<int> devs = devices_from_env();
+    // the cache only bounds the sequence length here: max_context = the embed length limit
+    d->model = LlmModel::load(dir, devs.empty() ? 0 : devs[0], 0, KJARNI_HIP_EMBED_CHUNK_ROWS);
+    return d;
+}
+
+}  // namespace
 
 KJARNI_EXPORT KjarniEmbedderConfig kjarni_embedder_config_default(void)
 {
@@ -204,7 +279,9 @@ KJARNI_EXPORT KjarniErrorCode kjarni_embedder_new(const KjarniEmbedderConfig* co
         if (s && !valid_utf8(s)) return KJARNI_ERROR_INVALID_UTF8;
     return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
         auto h = std::make_unique<KjarniEmbedder>();
-        h->p = load_pipeline(c.cache_dir, c.model_name, c.model_path, "minilm-l6-v2", Want::Embedding);
+        const std::string dec_dir = decoder_embedder_dir(c);
+        if (!dec_dir.empty()) h->dec = load_decoder_embedder(dec_dir);
+        else h->p = load_pipeline(c.cache_dir, c.model_name, c.model_path, "minilm-l6-v2", Want::Embedding);
         h->normalize = c.normalize != 0;
         *out = h.release();
     });
@@ -220,7 +297,8 @@ KJARNI_EXPORT KjarniErrorCode kjarni_embedder_encode(KjarniEmbedder* e, const ch
     out->len = 0;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         // Embedder::embed -> encode_with(text, "mean", normalize) (embedder/model.rs:118-140)
-        std::vector<float> v = embed_texts(*e->p, {std::string(text)}, POOL_MEAN, e->normalize);
+        // (a decoder embedder: last-token pool, normalize as configured)
+        std::vector<float> v = e->embed({std::string(text)}, e->normalize);
         float* d = static_cast<float*>(std::malloc(std::max<size_t>(v.size(), 1) * sizeof(float)));
         if (!d) throw std::bad_alloc();
         std::memcpy(d, v.data(), v.size() * sizeof(float));
@@ -246,13 +324,13 @@ KJARNI_EXPORT KjarniErrorCode kjarni_embedder_encode_batch(KjarniEmbedder* e, co
     }
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         // encode_batch_flat: mean pool + L2 normalise ALWAYS (sentence_encoder/model.rs:201-218)
-        std::vector<float> r = embed_texts(*e->p, v, POOL_MEAN, true);
+        std::vector<float> r = e->embed(v, true);
         float* d = static_cast<float*>(std::malloc(std::max<size_t>(r.size(), 1) * sizeof(float)));
         if (!d) throw std::bad_alloc();
         std::memcpy(d, r.data(), r.size() * sizeof(float));
         out->data = d;
         out->rows = num_texts;
-        out->cols = (size_t)e->p->config().hidden;
+        out->cols = e->hidden();
     });
 }
 
@@ -263,13 +341,13 @@ KJARNI_EXPORT KjarniErrorCode kjarni_embedder_similarity(KjarniEmbedder* e, cons
     *out = 0.0f;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         // Embedder::similarity: embed_batch([t1,t2]) (mean, config normalize) -> cosine (model.rs:178-181)
-        std::vector<float> r = embed_texts(*e->p, {std::string(t1), std::string(t2)}, POOL_MEAN, e->normalize);
-        const size_t H = (size_t)e->p->config().hidden;
+        std::vector<float> r = e->embed({std::string(t1), std::string(t2)}, e->normalize);
+        const size_t H = e->hidden();
         *out = cosine_k(r.data(), r.data() + H, H);
     });
 }
 
-KJARNI_EXPORT size_t kjarni_embedder_dim(const KjarniEmbedder* e) { return e ? (size_t)e->p->config().hidden : 0; }
+KJARNI_EXPORT size_t kjarni_embedder_dim(const KjarniEmbedder* e) { return e ? e->hidden() : 0; }
 
 // ---- Reranker ----------------------------------------------------------------
 

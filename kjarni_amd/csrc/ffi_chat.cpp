@@ -474,6 +474,19 @@ KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_encode(const KjarniBpeTokeniz
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_encode_embedding(const KjarniBpeTokenizer* t, const char* text, size_t max_length,
+                                                                    uint32_t* ids_out, size_t capacity, size_t* n_out)
+{
+    if (!t || !text || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    if (!valid_utf8(text)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const std::vector<uint32_t> ids = t->tok.encode_for_embedding(text, max_length);
+        *n_out = ids.size();
+        if (ids_out)
+            for (size_t i = 0; i < ids.size() && i < capacity; ++i) ids_out[i] = ids[i];
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_decode(const KjarniBpeTokenizer* t, const uint32_t* ids, size_t n, int32_t skip_special,
                                                           char** out)
 {

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "decoder_embed_kernels.h"
 #include "llm_kernels.h"
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
@@ -451,6 +452,48 @@ KJARNI_EXPORT void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* d, uin
 {
     if (fused) *fused = d ? d->model->score_fused_calls() : 0;
     if (rows) *rows = d ? d->model->score_rows_calls() : 0;
+}
+
+// ---- embedding --------------------------------------------------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_embed(KjarniHipDecoder* d, const uint32_t* ids, const int32_t* offsets, int32_t n_sequences,
+                                                       int32_t normalize, float* out)
+{
+    if (!d || (n_sequences > 0 && (!ids || !offsets || !out))) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->embed_batch(ids, offsets, n_sequences, normalize != 0, out);  // arguments checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_embed_plan(const int32_t* lengths, int32_t n, int32_t head_dim, int32_t* chunk_first_seq,
+                                                    int32_t* n_chunks, int32_t* vec_blocks, int32_t vec_capacity, int32_t* n_vec,
+                                                    int32_t* mfma_blocks, int32_t mfma_capacity, int32_t* n_mfma)
+{
+    if ((n > 0 && !lengths) || !n_chunks || !n_vec || !n_mfma) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        if (n < 0 || vec_capacity < 0 || mfma_capacity < 0) throw InvalidConfig("n and the capacities must not be negative");
+        const std::vector<EmbedChunk> chunks = embed_plan_host(lengths, n, head_dim);
+        int32_t nv = 0, nm = 0;
+        for (size_t c = 0; c < chunks.size(); ++c) {
+            if (chunk_first_seq) chunk_first_seq[c] = chunks[c].first_seq;
+            auto put = [&](const std::vector<EmbedBlock>& src, int32_t* dst, int32_t cap, int32_t& cnt) {
+                for (const EmbedBlock& b : src) {
+                    if (dst && cnt < cap) {
+                        int32_t* w = dst + 4 * (size_t)cnt;
+                        w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len;
+                    }
+                    ++cnt;
+                }
+            };
+            put(chunks[c].vec, vec_blocks, vec_capacity, nv);
+            put(chunks[c].mfma, mfma_blocks, mfma_capacity, nm);
+        }
+        if (chunk_first_seq) chunk_first_seq[chunks.size()] = n;
+        *n_chunks = (int32_t)chunks.size();
+        *n_vec = nv;
+        *n_mfma = nm;
+    });
 }
 
 // ---- prefix reuse -----------------------------------------------------------------------------------------------------------

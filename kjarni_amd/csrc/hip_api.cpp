@@ -15,6 +15,7 @@
 #include "group.h"
 #include "gguf.h"
 #include "llm.h"
+#include "decoder_embed_kernels.h"
 #include "llm_kernels.h"
 #include "quant_kernels.h"
 #include "tuning.h"
@@ -671,6 +672,174 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qk_norm_rope(int32_t device, float* 
         hip_check(hipDeviceSynchronize(), "sync");
         hip_check(hipMemcpy(q, qd.p, qb, hipMemcpyDeviceToHost), "D2H q");
         hip_check(hipMemcpy(k, kd.p, kb, hipMemcpyDeviceToHost), "D2H k");
+    });
+}
+
+// ---- decoder embedders: the packed-row kernels alone ---------------------------------------------------------------------------
+
+namespace {
+
+// seq_start [n + 1]: starts at `first_min`..., strictly increasing, the last entry at most `rows`
+void check_seq_start(const int32_t* seq_start, int32_t n, int32_t rows, bool from_zero)
+{
+    if (n < 1 || n > (1 << 20)) throw InvalidConfig("n_sequences must be 1 .. 2^20");
+    if (from_zero ? seq_start[0] != 0 : seq_start[0] < 0) throw InvalidConfig(from_zero ? "seq_start[0] must be 0" : "seq_start[0] is negative");
+    for (int32_t b = 0; b < n; ++b)
+        if (seq_start[b + 1] <= seq_start[b])
+            throw InvalidConfig("seq_start[" + std::to_string(b + 1) + "] does not exceed seq_start[" + std::to_string(b) + "]: sequence " +
+                                std::to_string(b) + " is empty or the starts decrease");
+    if (seq_start[n] > rows) throw InvalidConfig("seq_start[n_sequences] = " + std::to_string(seq_start[n]) + " reaches past the " +
+                                                 std::to_string(rows) + " rows given");
+}
+
+void check_row_pos(const int32_t* row_pos, int32_t rows, int32_t table_rows)
+{
+    for (int32_t r = 0; r < rows; ++r)
+        if (row_pos[r] < 0 || row_pos[r] >= table_rows)
+            throw InvalidConfig("row_pos[" + std::to_string(r) + "] = " + std::to_string(row_pos[r]) + " is outside the RoPE tables");
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_packed_causal_attention(int32_t device, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                                                    const float* v, int64_t ldv, int32_t buffer_rows, const int32_t* seq_start,
+                                                                    int32_t n_sequences, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                                                    float* ctx, int64_t ldc)
+{
+    if (!q || !k || !v || !seq_start || !ctx) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128) throw InvalidConfig("head_dim must be 16, 32, 64 or 128");
+        if (heads < 1 || heads > 1024 || kv_heads < 1 || kv_heads > heads || heads % kv_heads)
+            throw InvalidConfig("heads must be 1..1024 and a multiple of kv_heads");
+        if (buffer_rows < 1 || buffer_rows > (1 << 22)) throw InvalidConfig("buffer_rows must be 1 .. 2^22");
+        const int64_t qd = (int64_t)heads * head_dim, kvd = (int64_t)kv_heads * head_dim;
+        if (ldq < qd || ldc < qd || ldk < kvd || ldv < kvd || ((ldq | ldk | ldv | ldc) & 3) || std::max(std::max(ldq, ldc), std::max(ldk, ldv)) > (1 << 20))
+            throw InvalidConfig("leading dimensions must cover the heads, be multiples of 4 and at most 2^20");
+        check_seq_start(seq_start, n_sequences, buffer_rows, true);
+        std::vector<EmbedBlock> vec, mfma;
+        for (int32_t b = 0; b < n_sequences; ++b) {
+            const int32_t first = seq_start[b], len = seq_start[b + 1] - first;
+            const bool m = embed_seq_takes_mfma(len, head_dim);
+            for (int32_t q0 = 0; q0 < len; q0 += m ? 128 : 32) (m ? mfma : vec).push_back(EmbedBlock{first, q0, len});
+        }
+        use_device(device);
+        const size_t R = (size_t)buffer_rows;
+        DeviceBuf qd_(R * (size_t)ldq * 4), kd(R * (size_t)ldk * 4), vd(R * (size_t)ldv * 4), cd(R * (size_t)ldc * 4);
+        DeviceBuf tv(vec.size() * sizeof(EmbedBlock)), tm(mfma.size() * sizeof(EmbedBlock));
+        hip_check(hipMemcpy(qd_.p, q, R * (size_t)ldq * 4, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, R * (size_t)ldk * 4, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(vd.p, v, R * (size_t)ldv * 4, hipMemcpyHostToDevice), "H2D v");
+        hip_check(hipMemcpy(cd.p, ctx, R * (size_t)ldc * 4, hipMemcpyHostToDevice), "H2D ctx");
+        if (!vec.empty()) hip_check(hipMemcpy(tv.p, vec.data(), vec.size() * sizeof(EmbedBlock), hipMemcpyHostToDevice), "H2D blocks");
+        if (!mfma.empty()) hip_check(hipMemcpy(tm.p, mfma.data(), mfma.size() * sizeof(EmbedBlock), hipMemcpyHostToDevice), "H2D blocks");
+        hip_check(launch_packed_causal_attention((const float*)qd_.p, ldq, (const float*)kd.p, ldk, (const float*)vd.p, ldv,
+                                                 (const EmbedBlock*)tv.p, (int)vec.size(), (const EmbedBlock*)tm.p, (int)mfma.size(), heads, head_dim,
+                                                 heads / kv_heads, (float*)cd.p, ldc, nullptr), "packed attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(ctx, cd.p, R * (size_t)ldc * 4, hipMemcpyDeviceToHost), "D2H ctx");
+    });
+}
+
+namespace {
+
+void rope_hook(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads, int32_t head_dim, const float* cos_t,
+               const float* sin_t, int32_t table_rows, int32_t pos, const int32_t* row_pos)
+{
+    if (head_dim < 2 || head_dim > 256 || (head_dim & 1) || n_heads < 1 || n_heads > 1024)
+        throw InvalidConfig("invalid head geometry (head_dim even, 2..256; heads 1..1024)");
+    if (rows < 1 || rows > x_rows || x_rows > (1 << 22) || ldx < (int64_t)n_heads * head_dim || ldx > (1 << 20))
+        throw InvalidConfig("rows / leading dimension do not cover the heads");
+    if (table_rows < 1 || table_rows > (1 << 22)) throw InvalidConfig("table_rows must be 1 .. 2^22");
+    if (row_pos) check_row_pos(row_pos, rows, table_rows);
+    else if (pos < 0 || rows > table_rows - pos) throw InvalidConfig("positions reach outside the RoPE tables");
+    use_device(device);
+    const size_t xb = (size_t)x_rows * (size_t)ldx * 4, tb = (size_t)table_rows * (head_dim / 2) * 4;
+    DeviceBuf xd(xb), cd(tb), sd(tb), pd((size_t)rows * 4);
+    hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+    hip_check(hipMemcpy(cd.p, cos_t, tb, hipMemcpyHostToDevice), "H2D cos");
+    hip_check(hipMemcpy(sd.p, sin_t, tb, hipMemcpyHostToDevice), "H2D sin");
+    if (row_pos) {
+        hip_check(hipMemcpy(pd.p, row_pos, (size_t)rows * 4, hipMemcpyHostToDevice), "H2D row_pos");
+        hip_check(launch_rope_rows((float*)xd.p, ldx, rows, n_heads, head_dim, (const float*)cd.p, (const float*)sd.p, (const int32_t*)pd.p, nullptr),
+                  "rope rows");
+    } else {
+        hip_check(launch_rope((float*)xd.p, ldx, rows, n_heads, head_dim, (const float*)cd.p, (const float*)sd.p, pos, nullptr, 0, nullptr), "rope");
+    }
+    hip_check(hipDeviceSynchronize(), "sync");
+    hip_check(hipMemcpy(x, xd.p, xb, hipMemcpyDeviceToHost), "D2H x");
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_rope(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads,
+                                                 int32_t head_dim, const float* cos_t, const float* sin_t, int32_t table_rows, int32_t pos)
+{
+    if (!x || !cos_t || !sin_t) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { rope_hook(device, x, ldx, x_rows, rows, n_heads, head_dim, cos_t, sin_t, table_rows, pos, nullptr); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_rope_rows(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads,
+                                                      int32_t head_dim, const float* cos_t, const float* sin_t, int32_t table_rows,
+                                                      const int32_t* row_pos)
+{
+    if (!x || !cos_t || !sin_t || !row_pos) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { rope_hook(device, x, ldx, x_rows, rows, n_heads, head_dim, cos_t, sin_t, table_rows, 0, row_pos); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qk_norm_rope_rows(int32_t device, float* q, int64_t ldq, int32_t q_rows, float* k, int64_t ldk,
+                                                              int32_t k_rows, int32_t rows, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim,
+                                                              const float* gamma_q, const float* gamma_k, float eps, const float* cos_t,
+                                                              const float* sin_t, int32_t table_rows, const int32_t* row_pos)
+{
+    if (!q || !k || !gamma_q || !gamma_k || !cos_t || !sin_t || !row_pos) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (head_dim < 2 || head_dim > 128 || (head_dim & 1) || n_heads < 1 || n_heads > 1024 || n_kv_heads < 1 || n_kv_heads > 1024)
+            throw InvalidConfig("invalid head geometry (head_dim even, 2..128; heads and kv heads 1..1024)");
+        if (rows < 1 || rows > q_rows || rows > k_rows || q_rows > (1 << 22) || k_rows > (1 << 22) || ldq < (int64_t)n_heads * head_dim ||
+            ldk < (int64_t)n_kv_heads * head_dim || ldq > (1 << 20) || ldk > (1 << 20))
+            throw InvalidConfig("rows / leading dimensions do not cover the heads");
+        if (table_rows < 1 || table_rows > (1 << 22)) throw InvalidConfig("table_rows must be 1 .. 2^22");
+        check_row_pos(row_pos, rows, table_rows);
+        use_device(device);
+        const size_t qb = (size_t)q_rows * (size_t)ldq * 4, kb = (size_t)k_rows * (size_t)ldk * 4, tb = (size_t)table_rows * (head_dim / 2) * 4;
+        DeviceBuf qd(qb), kd(kb), gq((size_t)head_dim * 4), gk((size_t)head_dim * 4), cd(tb), sd(tb), pd((size_t)rows * 4);
+        hip_check(hipMemcpy(qd.p, q, qb, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, kb, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(gq.p, gamma_q, (size_t)head_dim * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(gk.p, gamma_k, (size_t)head_dim * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(cd.p, cos_t, tb, hipMemcpyHostToDevice), "H2D cos");
+        hip_check(hipMemcpy(sd.p, sin_t, tb, hipMemcpyHostToDevice), "H2D sin");
+        hip_check(hipMemcpy(pd.p, row_pos, (size_t)rows * 4, hipMemcpyHostToDevice), "H2D row_pos");
+        hip_check(launch_qk_norm_rope_rows((float*)qd.p, ldq, (float*)kd.p, ldk, rows, n_heads, n_kv_heads, head_dim, (const float*)gq.p,
+                                           (const float*)gk.p, eps, (const float*)cd.p, (const float*)sd.p, (const int32_t*)pd.p, nullptr),
+                  "qk norm + rope rows");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(q, qd.p, qb, hipMemcpyDeviceToHost), "D2H q");
+        hip_check(hipMemcpy(k, kd.p, kb, hipMemcpyDeviceToHost), "D2H k");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_last_token_pool(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* seq_start,
+                                                            int32_t n_sequences, int32_t hidden, const float* gamma, float eps, int32_t normalize,
+                                                            float* out)
+{
+    if (!x || !seq_start || !gamma || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (hidden < 1 || hidden > 16384 || ldx < hidden || ldx > (1 << 20)) throw InvalidConfig("hidden must be 1 .. 16384 and ldx cover it");
+        if (x_rows < 1 || x_rows > (1 << 22)) throw InvalidConfig("x_rows must be 1 .. 2^22");
+        check_seq_start(seq_start, n_sequences, x_rows, false);
+        use_device(device);
+        const size_t xb = (size_t)x_rows * (size_t)ldx * 4, ob = (size_t)n_sequences * (size_t)hidden * 4;
+        DeviceBuf xd(xb), gd((size_t)hidden * 4), sd(((size_t)n_sequences + 1) * 4);
+        GuardedBuf od(ob);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        hip_check(hipMemcpy(gd.p, gamma, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(sd.p, seq_start, ((size_t)n_sequences + 1) * 4, hipMemcpyHostToDevice), "H2D seq_start");
+        hip_check(launch_last_token_pool((const float*)xd.p, ldx, (const int32_t*)sd.p, n_sequences, hidden, (const float*)gd.p, eps,
+                                         normalize ? 1 : 0, od.as<float>(), nullptr), "last-token pool");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
+        od.check("last-token pool");
     });
 }
 

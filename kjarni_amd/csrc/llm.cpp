@@ -11,6 +11,7 @@
 #include "gguf.h"
 #include "json.h"
 #include "kernels.h"
+#include "decoder_embed_kernels.h"
 #include "llm_kernels.h"
 #include "safetensors.h"
 #include "whisper_kernels.h"
@@ -137,6 +138,7 @@ void* LlmModel::upload_weight(const std::vector<float>& host)
 LlmModel::~LlmModel()
 {
     if (host_logits_) (void)hipHostFree(host_logits_);
+    if (emeta_host_) (void)hipHostFree(emeta_host_);
     if (samp_host_) (void)hipHostFree(samp_host_);
     if (ls_host_) (void)hipHostFree(ls_host_);
     (void)hipSetDevice(device_);
@@ -701,6 +703,85 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool 
     else qlinear(qhead_, last_ + (size_t)(n - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
 }
 
+void LlmModel::ensure_prompt_workspace()
+{
+    if (ph_) return;
+    const int H = cfg_.hidden, kv = cfg_.kv_heads * cfg_.head_dim, I = cfg_.inter, QD = cfg_.q_dim();
+    prefill_cap_ = 2048;
+    const size_t P = (size_t)prefill_cap_;
+    ph_ = dalloc(P * H);
+    pn_ = dalloc(P * H);
+    pq_ = dalloc(P * QD);
+    pctx_ = dalloc(P * QD);
+    pg_ = dalloc(P * I);
+    pu_ = dalloc(P * I);
+    pids_ = reinterpret_cast<uint32_t*>(dalloc(P));
+    psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, std::max(H, QD))));
+    if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(QD + 2 * kv) * H, (size_t)I * H));
+    if (quant_) pact_ = dalloc(P * (size_t)std::max(H, I));
+}
+
+// Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T).  Blocks of >= kTileRows rows run the
+// encoder's 128 x 128-tile f32 GEMM (gemm.hip), bf16 weights on an f32 copy made just before (100 MB moved per 69 GFLOP
+// at 2 048 rows).  Measured on the 1B shape: 2 048 rows 46.2 -> 42.6 ms, 1 792 rows 40.4 -> 39.1 ms, 1 536 rows 33.1 -> 36.1 ms
+// (the 2 048-wide projections are then 192 tiles on 256 CUs): hence kTileRows.
+// per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
+// gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
+void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
+                           float* gate, const char* what, const QMat* qm, bool gelu)
+{
+    hipStream_t s = stream_;
+    const int H = cfg_.hidden, kv = cfg_.kv_heads * cfg_.head_dim, I = cfg_.inter, QD = cfg_.q_dim();
+    constexpr int kTileRows = 512;  // rows from which a projection may take the encoder's 128 x 128-tile f32 GEMM (if its tiles fill the chip)
+    const bool tile_shapes = H % 128 == 0 && QD % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
+    // a quantized matrix: dequantized into the f32 scratch first; a Q6_K linear also takes its activation rows through
+    // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
+    int wbu = bf16_ ? 1 : 0;
+    bool bf = bf16_;
+    if (qm) {
+        hip_check(launch_qdequant(*qm, pw32_, s), what);
+        if (qm->type == GGML_Q6_K) {
+            hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
+            Ain = pact_;
+            lda = K;
+        }
+        W = pw32_;
+        wbu = 0;
+        bf = false;
+    }
+    // measured on the 1B shape: 192 tiles (1 536 rows x 2 048 columns) are faster on the 64 x 64 kernel, 224 on the tiles -- with
+    // f32 weights (both kernels on the f32 matrix cores) and again with bf16 weights (both on the bf16 matrix cores: 768 /
+    // 1 024 tokens 8.1 / 9.8 ms at 208 against 9.9 / 11.2 at 96 and 8.8 / 11.2 with no tiles at all)
+    constexpr int min_tiles = 208;
+    const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
+    if (!tiles) {
+        hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
+        if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
+        return;
+    }
+    ++tile_gemm_calls_;
+    // bf16 weights: the bf16 matrix cores take them as they are, the f32 activations as three exact bf16 pieces (the same
+    // products as the f32 GEMM on a widened copy: gemm_split.hip) -- 2 048-token prompt 33.8 -> 18.1 ms, no 100 MB copy
+    if (bf && K % 64 == 0) {
+        if (gate)
+            hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
+        else
+            hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, R, ldy, Y, ldy, m, N, K, R ? EPI_BIAS_RESIDUAL : EPI_BIAS, s), what);
+        if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
+        return;
+    }
+    const float* W32 = static_cast<const float*>(W);
+    if (bf) {
+        hip_check(launch_widen_bf16(W, pw32_, (size_t)N * K, s), "widen");
+        W32 = pw32_;
+    }
+    if (gate)
+        hip_check(launch_gemm(Ain, lda, W32, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
+    else
+        hip_check(launch_gemm(Ain, lda, W32, bias, R, ldy, Y, ldy, m, N, K, gelu ? EPI_BIAS_GELU_NEW : (R ? EPI_BIAS_RESIDUAL : EPI_BIAS), s),
+                  what);
+}
+
 // Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer RMSNorm ->
 // Q, K, V projections (K and V rows land in the cache) -> RoPE -> causal attention over the cache -> o-proj + residual
 // -> RMSNorm -> gate, up -> silu(gate) * up -> down-proj + residual; same formulas as pass().  After the last layer the
@@ -711,22 +792,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
     const int wb = bf16_ ? 1 : 0;
-    constexpr int kChunk = 2048;
-    constexpr int kTileRows = 512;  // rows from which a projection may take the encoder's 128 x 128-tile f32 GEMM (if its tiles fill the chip)
-    if (!ph_) {
-        prefill_cap_ = kChunk;
-        const size_t P = (size_t)prefill_cap_;
-        ph_ = dalloc(P * H);
-        pn_ = dalloc(P * H);
-        pq_ = dalloc(P * QD);
-        pctx_ = dalloc(P * QD);
-        pg_ = dalloc(P * I);
-        pu_ = dalloc(P * I);
-        pids_ = reinterpret_cast<uint32_t*>(dalloc(P));
-        psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, std::max(H, QD))));
-        if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(QD + 2 * kv) * H, (size_t)I * H));
-        if (quant_) pact_ = dalloc(P * (size_t)std::max(H, I));
-    }
+    ensure_prompt_workspace();
     const size_t wsz = bf16_ ? 2 : 4;
     auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
     for (int done = 0; done < n; done += prefill_cap_) {
@@ -735,61 +801,9 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
         if (quant_) hip_check(launch_qembed(pids_, m, qembed_, ph_, s), "embed");
         else if (gpt2_) hip_check(launch_llm_embed_pos(pids_, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, cache_len_, nullptr, ph_, s), "embed");
         else hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
-        // Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T).  Blocks of >= kTileRows rows run the
-        // encoder's 128 x 128-tile f32 GEMM (gemm.hip), bf16 weights on an f32 copy made just before (100 MB moved per 69 GFLOP
-        // at 2 048 rows).  Measured on the 1B shape: 2 048 rows 46.2 -> 42.6 ms, 1 792 rows 40.4 -> 39.1 ms, 1 536 rows 33.1 -> 36.1 ms
-        // (the 2 048-wide projections are then 192 tiles on 256 CUs): hence kTileRows.
-        // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
-        const bool tile_shapes = H % 128 == 0 && QD % 128 == 0 && I % 128 == 0 && kv % 128 == 0 && (!bf16_ || pw32_);
-        // gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
         auto proj = [&](const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
                         float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false) {
-            // a quantized matrix: dequantized into the f32 scratch first; a Q6_K linear also takes its activation rows through
-            // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
-            int wbu = wb;
-            bool bf = bf16_;
-            if (qm) {
-                hip_check(launch_qdequant(*qm, pw32_, s), what);
-                if (qm->type == GGML_Q6_K) {
-                    hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
-                    Ain = pact_;
-                    lda = K;
-                }
-                W = pw32_;
-                wbu = 0;
-                bf = false;
-            }
-            // measured on the 1B shape: 192 tiles (1 536 rows x 2 048 columns) are faster on the 64 x 64 kernel, 224 on the tiles -- with
-            // f32 weights (both kernels on the f32 matrix cores) and again with bf16 weights (both on the bf16 matrix cores: 768 /
-            // 1 024 tokens 8.1 / 9.8 ms at 208 against 9.9 / 11.2 at 96 and 8.8 / 11.2 with no tiles at all)
-            constexpr int min_tiles = 208;
-            const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
-            if (!tiles) {
-                hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
-                if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
-                return;
-            }
-            ++tile_gemm_calls_;
-            // bf16 weights: the bf16 matrix cores take them as they are, the f32 activations as three exact bf16 pieces (the same
-            // products as the f32 GEMM on a widened copy: gemm_split.hip) -- 2 048-token prompt 33.8 -> 18.1 ms, no 100 MB copy
-            if (bf && K % 64 == 0) {
-                if (gate)
-                    hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
-                else
-                    hip_check(launch_gemm_bf16_weights(Ain, lda, W, bias, R, ldy, Y, ldy, m, N, K, R ? EPI_BIAS_RESIDUAL : EPI_BIAS, s), what);
-                if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
-                return;
-            }
-            const float* W32 = static_cast<const float*>(W);
-            if (bf) {
-                hip_check(launch_widen_bf16(W, pw32_, (size_t)N * K, s), "widen");
-                W32 = pw32_;
-            }
-            if (gate)
-                hip_check(launch_gemm(Ain, lda, W32, bias, gate, ldy, gate, ldy, m, N, K, EPI_BIAS_MUL_SILU, s), what);
-            else
-                hip_check(launch_gemm(Ain, lda, W32, bias, R, ldy, Y, ldy, m, N, K, gelu ? EPI_BIAS_GELU_NEW : (R ? EPI_BIAS_RESIDUAL : EPI_BIAS), s),
-                          what);
+            prompt_proj(m, Ain, lda, W, bias, R, Y, ldy, N, K, gate, what, qm, gelu);
         };
         for (const Layer& L : layers_) {
             float* k_rows = L.k_cache + (size_t)cache_len_ * kv;
@@ -2197,6 +2211,123 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     hip_check(hipMemcpy(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
     leave_resident(all);
     return out;
+}
+
+// ---- embedding ----------------------------------------------------------------------------------------------------------------
+
+std::vector<EmbedChunk> embed_plan_host(const int32_t* lengths, int n, int head_dim)
+{
+    std::vector<EmbedChunk> chunks;
+    for (int i = 0; i < n; ++i) {
+        const int len = lengths[i];
+        if (len < 1 || len > kEmbedChunkRows)
+            throw InvalidConfig("lengths[" + std::to_string(i) + "] = " + std::to_string(len) + " is outside 1 .. " +
+                                std::to_string(kEmbedChunkRows));
+        if (chunks.empty() || chunks.back().rows + len > kEmbedChunkRows) {
+            chunks.emplace_back();
+            chunks.back().first_seq = i;
+        }
+        EmbedChunk& c = chunks.back();
+        const bool mfma = embed_seq_takes_mfma(len, head_dim);
+        const int step = mfma ? 128 : 32;
+        for (int q0 = 0; q0 < len; q0 += step) (mfma ? c.mfma : c.vec).push_back(EmbedBlock{c.rows, q0, len});
+        c.rows += len;
+        ++c.n_seq;
+    }
+    return chunks;
+}
+
+void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, bool normalize, float* out)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    if (gpt2_) throw InvalidConfig("embed: GPT-2 has no RMSNorm layer stack and is no embedding family");
+    if (quant_) throw InvalidConfig("embed: quantized checkpoints are not supported");
+    if (H % 32 || QD % 32 || I % 32 || kv % 4 || !(d == 16 || d == 32 || d == 64 || d == 128))
+        throw InvalidConfig("embed: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
+    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    if (B == 0) return;
+    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
+    const int limit = embed_max_tokens();
+    std::vector<int32_t> lengths((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
+        const std::string seq = " (sequence " + std::to_string(b) + ")";
+        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
+                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
+        if (len == 0) throw InvalidConfig("offsets[" + std::to_string(b) + "] == offsets[" + std::to_string(b + 1) + "]: an empty sequence" + seq);
+        if (len > limit)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the embed length limit of " + std::to_string(limit) + seq);
+        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
+            if (ids[i] >= (uint32_t)c.vocab)
+                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
+                                    std::to_string(c.vocab) + seq);
+        lengths[(size_t)b] = (int32_t)len;
+    }
+    const std::vector<EmbedChunk> chunks = embed_plan_host(lengths.data(), B, d);
+
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hipStream_t s = stream_;
+    ensure_prompt_workspace();
+    // a chunk's metadata: ids [m] | row_pos [m] | seq_start [n + 1] | vec blocks | mfma blocks; the bound: m <= 2048 rows,
+    // n <= 2048 sequences, at most m / 32 + n vec blocks and m / 128 + n / 256 + 1 mfma blocks of 3 words
+    constexpr size_t kMetaWords = 3 * (size_t)kEmbedChunkRows + 4 + 3 * (kEmbedChunkRows / 32 + kEmbedChunkRows) + 3 * 32;
+    if (!ek_) {
+        ek_ = dalloc((size_t)kEmbedChunkRows * kv);
+        ev_ = dalloc((size_t)kEmbedChunkRows * kv);
+        emeta_ = reinterpret_cast<int32_t*>(dalloc(kMetaWords));
+        hip_check(hipHostMalloc((void**)&emeta_host_, kMetaWords * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
+    }
+    const int wb = bf16_ ? 1 : 0;
+    const size_t wsz = bf16_ ? 2 : 4;
+    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
+    for (const EmbedChunk& ch : chunks) {
+        const int m = ch.rows, n = ch.n_seq, nv = (int)ch.vec.size(), nm = (int)ch.mfma.size();
+        const size_t o_pos = (size_t)m, o_start = o_pos + (size_t)m, o_vec = o_start + (size_t)n + 1, o_mfma = o_vec + 3 * (size_t)nv;
+        const size_t words = o_mfma + 3 * (size_t)nm;
+        if (words > kMetaWords) throw std::runtime_error("embed: chunk metadata exceeds its buffer");
+        int32_t* hm = emeta_host_;
+        std::memcpy(hm, ids + offsets[ch.first_seq], (size_t)m * 4);
+        int row = 0;
+        for (int j = 0; j < n; ++j) {
+            hm[o_start + (size_t)j] = row;
+            const int len = lengths[(size_t)(ch.first_seq + j)];
+            for (int t = 0; t < len; ++t) hm[o_pos + (size_t)row++] = t;
+        }
+        hm[o_start + (size_t)n] = row;
+        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
+        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
+        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
+        const uint32_t* ids_dev = reinterpret_cast<const uint32_t*>(emeta_);
+        const int32_t *row_pos = emeta_ + o_pos, *seq_start = emeta_ + o_start;
+        const EmbedBlock* vec = reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec);
+        const EmbedBlock* mfma = reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma);
+        hip_check(launch_llm_embed(ids_dev, m, H, c.vocab, embed_, wb, ph_, s), "embed");
+        for (const Layer& L : layers_) {
+            hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
+            prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj");
+            prompt_proj(m, pn_, H, at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, ek_, kv, kv, H, nullptr, "k proj");
+            prompt_proj(m, pn_, H, at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, ev_, kv, kv, H, nullptr, "v proj");
+            if (c.qwen3()) {
+                hip_check(launch_qk_norm_rope_rows(pq_, QD, ek_, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, row_pos, s),
+                          "qk norm + rope");
+            } else {
+                hip_check(launch_rope_rows(pq_, QD, m, c.heads, d, cos_, sin_, row_pos, s), "rope q");
+                hip_check(launch_rope_rows(ek_, kv, m, c.kv_heads, d, cos_, sin_, row_pos, s), "rope k");
+            }
+            hip_check(launch_packed_causal_attention(pq_, QD, ek_, kv, ev_, kv, vec, nv, mfma, nm, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
+                      "packed attention");
+            prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj");
+            hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
+            prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate");
+            prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu");
+            prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj");
+        }
+        // (the norm buffer is free after the last layer: the pooled rows land there)
+        hip_check(launch_last_token_pool(ph_, H, seq_start, n, H, final_norm_, c.eps, normalize ? 1 : 0, pn_, s), "last-token pool");
+        hip_check(hipMemcpyAsync(out + (size_t)ch.first_seq * H, pn_, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, s), "D2H embeddings");
+        hip_check(hipStreamSynchronize(s), "sync");  // the staging copy and the activations are reused by the next chunk
+    }
 }
 
 }  // namespace kjarni

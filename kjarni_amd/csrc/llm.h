@@ -147,6 +147,18 @@ public:
     // Head launches of score() by route since load.
     uint64_t score_fused_calls() const { return score_fused_calls_; }
     uint64_t score_rows_calls() const { return score_rows_calls_; }
+    // ---- embedding: last-token pooling over a packed batch ---------------------------------------------------------------------
+    // Sequence b is ids[offsets[b], offsets[b + 1]); out[b, :] = the final-normed hidden state of its last token, L2-normalised
+    // when `normalize` (x / ||x|| when ||x|| > 0).  The sequences are packed, in order, into chunks of at most 2 048 rows
+    // (embed_plan_host, decoder_embed_kernels.h) and every chunk runs prefill_rows()'s layer steps once over all its rows: the
+    // projections on the prompt GEMM routes, RoPE by each row's position in its own sequence, causal attention that stops at the
+    // sequence boundaries; K and V live in two scratch buffers, not in the KV cache.  cache_len(), resident(), lanes, lookup
+    // state, the logits and last_hidden() are left as they were.  Throws InvalidConfig naming the argument and the sequence, before
+    // any GPU work, for non-monotone offsets, an empty sequence, an id >= vocab and a sequence longer than
+    // embed_max_tokens(); GPT-2, quantized checkpoints and geometries forward() keeps off the matrix-core route are refused.
+    // B == 0 writes nothing.
+    void embed_batch(const uint32_t* ids, const int32_t* offsets, int B, bool normalize, float* out);
+    int embed_max_tokens() const { return cache_cap_ < 2048 ? cache_cap_ : 2048; }
     // Cache rows [first, first + rows) of one layer, K after RoPE (Qwen3: after the head norm and RoPE) and V, f32
     // [rows, kv_heads * head_dim] each (a test hook).
     void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
@@ -282,6 +294,12 @@ private:
     // and score_head_rows
     // score_base: the position of ids[0] in the scored sequence (score() with a kept prefix forwards only the rest)
     void prefill_rows(const uint32_t* ids_host, int n, bool score = false, int score_base = 0);
+    void ensure_prompt_workspace();  // the 2 048-row activation buffers of the prompt routes
+    // One projection of m prompt rows: Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T); gelu (GPT-2's
+    // c_fc): Y = gelu_tanh(A W^T + bias).  Routes: the 64 x 64 prompt kernel, or from 512 rows and 208 tiles the 128 x 128-tile
+    // GEMM (bf16 weights on the bf16 matrix cores); qm: a quantized matrix, dequantized into the f32 scratch first.
+    void prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
+                     float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false);
     void forward_rows(const uint32_t* ids, int n, bool score, int score_base = 0);  // forward(), with score()'s sink
     void ensure_score();
     void ensure_score_topk();
@@ -329,6 +347,10 @@ private:
     uint32_t* pids_ = nullptr;
     float* pw32_ = nullptr;    // f32 copy of the weight matrix a long prompt's GEMM is working on (bf16 checkpoints)
     float* psplit_ = nullptr;  // K-slice partial tiles of the prompt GEMMs (short prompts)
+    // embed_batch (allocated on first use): a chunk's K and V rows [2048, kv], its ids | row positions | sequence starts | block
+    // tables on the device and their pinned staging copy
+    float *ek_ = nullptr, *ev_ = nullptr;
+    int32_t *emeta_ = nullptr, *emeta_host_ = nullptr;
     float* host_logits_ = nullptr;  // pinned
     std::vector<uint32_t> row_ids_, row_cids_;  // sample_row's scratch: the distribution's ids, the candidates' ids
     std::vector<float> row_probs_, row_cvals_;  // ... and their probabilities / logits

@@ -48,6 +48,14 @@ const RegistryEntry kEntries[] = {
     {"gpt2", "gpt2/resolve", ModelTask::Other, ModelArch::Other},
 };
 
+// Decoder embedders (last-token pooling).  The reference has no such entries: they resolve by name and alias like the others and
+// stay out of its "Did you mean" suggestions.
+const RegistryEntry kDecoderEmbedders[] = {
+    {"qwen3-embedding-0.6b", "Qwen/Qwen3-Embedding-0.6B", ModelTask::Embedding, ModelArch::Decoder},
+    {"qwen3-embedding-4b", "Qwen/Qwen3-Embedding-4B", ModelTask::Embedding, ModelArch::Decoder},
+    {"qwen3-embedding-8b", "Qwen/Qwen3-Embedding-8B", ModelTask::Embedding, ModelArch::Decoder},
+};
+
 struct Alias {
     const char* alias;
     const char* cli_name;
@@ -82,6 +90,9 @@ const Alias kAliases[] = {
     {"qwen/qwen3-1.7b", "qwen3-1.7b"},
     {"qwen/qwen3-4b", "qwen3-4b"},
     {"qwen/qwen3-8b", "qwen3-8b"},
+    {"qwen/qwen3-embedding-0.6b", "qwen3-embedding-0.6b"},
+    {"qwen/qwen3-embedding-4b", "qwen3-embedding-4b"},
+    {"qwen/qwen3-embedding-8b", "qwen3-embedding-8b"},
     {"distilgpt2/resolve/main/model.safetensors", "distilgpt2"},
     {"gpt2/resolve/main/model.safetensors", "gpt2"},
 };
@@ -97,6 +108,8 @@ std::string to_lower(const std::string& s)
 const RegistryEntry* by_cli(const std::string& cli)
 {
     for (const RegistryEntry& e : kEntries)
+        if (cli == e.cli_name) return &e;
+    for (const RegistryEntry& e : kDecoderEmbedders)
         if (cli == e.cli_name) return &e;
     return nullptr;
 }

@@ -12,7 +12,9 @@
 namespace kjarni {
 
 enum class ModelTask { Embedding, ReRanking, Classification, Other };
-enum class ModelArch { Bert, Other };  // Bert: an encoder family this library runs (BERT, DistilBERT, RoBERTa, MPNet)
+// Bert: an encoder family this library runs (BERT, DistilBERT, RoBERTa, MPNet); Decoder: a decoder checkpoint that embeds with
+// last-token pooling (the Embedder loads it on the decoder path)
+enum class ModelArch { Bert, Decoder, Other };
 
 struct RegistryEntry {
     const char* cli_name;

@@ -39,6 +39,26 @@ def generation_replay(n_prompt: int, capacity: int, max_new_tokens: int, stream:
     return int(e.value), int(a.value), int(f.value)
 
 
+EMBED_CHUNK_ROWS = 2048
+
+
+def embed_plan(lengths: Sequence[int], head_dim: int = 64):
+    """The packing rule of HipDecoder.embed (no GPU): sequences of `lengths` tokens go greedily, in order, into chunks of at most
+    EMBED_CHUNK_ROWS rows.  Returns (chunk_first_seq, vec_blocks, mfma_blocks): the first sequence of every chunk followed by
+    len(lengths); the query blocks of the vector route (32 rows each) and of the matrix-core route (128 rows each; sequences
+    of >= 256 rows with head_dim 64 / 128) as int32 [n, 4] rows (chunk, the sequence's first row in the chunk, the block's first
+    query row in the sequence, the sequence's length)."""
+    a = np.ascontiguousarray(lengths, np.int32)
+    i32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    cap = int(np.maximum(a, 0).astype(np.int64).sum() // 32 + a.size + 1)
+    first = np.zeros(a.size + 1, np.int32)
+    vec, mfma = np.zeros((cap, 4), np.int32), np.zeros((cap, 4), np.int32)
+    nc, nv, nm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check_error(lib().kjarni_hip_embed_plan(i32(a) if a.size else None, a.size, int(head_dim), i32(first), C.byref(nc), i32(vec), cap,
+                                            C.byref(nv), i32(mfma), cap, C.byref(nm)))
+    return first[:nc.value + 1].copy(), vec[:nv.value].copy(), mfma[:nm.value].copy()
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
@@ -363,6 +383,31 @@ class HipDecoder:
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_score_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+    # ---- embedding: last-token pooling over a packed batch ----
+    def embed(self, sequences: Sequence[Sequence[int]], normalize: bool = True) -> np.ndarray:
+        """[len(sequences), hidden]: the final-normed hidden state of every sequence's last token, L2-normalised when
+        `normalize`.  All sequences run packed through the prompt routes in chunks of at most EMBED_CHUNK_ROWS rows; the KV cache
+        and everything generate() depends on are left as they were."""
+        n = len(sequences)
+        out = np.zeros((n, self.hidden), np.float32)
+        lens = [len(s) for s in sequences]
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.uint32).reshape(-1) for s in sequences]) if n else [], np.uint32)
+        if flat.size == 0:
+            flat = np.zeros(1, np.uint32)
+        offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens)]), np.int32)
+        self.embed_flat(flat, offsets, normalize, out)
+        return out
+
+    def embed_flat(self, ids, offsets, normalize: bool = True, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """embed() on ids and offsets [n + 1] as the C ABI takes them (sequence b = ids[offsets[b]:offsets[b + 1]])."""
+        a, o = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(offsets, np.int32)
+        n = o.size - 1
+        if out is None:
+            out = np.zeros((n, self.hidden), np.float32)
+        check_error(lib().kjarni_hip_decoder_embed(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), o.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                                   int(bool(normalize)), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     # ---- prefix reuse: keep the cached rows of the tokens a call shares with what the cache holds ----
     def set_prefix_reuse(self, on: bool):

@@ -239,6 +239,82 @@ ARGMAX_DECODER, ARGMAX_LANES, ARGMAX_LOOKUP = 0, 1, 2
 _i32p = C.POINTER(C.c_int32)
 
 
+# ---- decoder embedders: the packed-row kernels alone ----
+def _seq_start(lengths):
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(lengths, np.int64))]), np.int32)
+
+
+def packed_causal_attention(q, k, v, lengths, heads: int, kv_heads: int, head_dim: int, ctx=None, device: int = 0):
+    """Causal grouped-query attention over packed sequences: q [rows, ldq], k / v [rows, ldk / ldv] hold the sequences of
+    `lengths` one after another from row 0 (rows may exceed their total, leading dimensions the used widths).  Returns ctx
+    [rows, ldc] (given, or zeros [rows, heads * head_dim]) with the context rows written; everything else as it was."""
+    qa, ka, va = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+    ca = np.zeros((qa.shape[0], heads * head_dim), np.float32) if ctx is None else np.array(ctx, np.float32, order="C")
+    if any(x.ndim != 2 or x.shape[0] != qa.shape[0] for x in (qa, ka, va, ca)):
+        raise ValueError("q, k, v, ctx: [rows, ld] with the same rows")
+    st = _seq_start(lengths)
+    check_error(lib().kjarni_hip_op_packed_causal_attention(device, _f(qa), qa.shape[1], _f(ka), ka.shape[1], _f(va), va.shape[1], qa.shape[0],
+                                                            st.ctypes.data_as(_i32p), st.size - 1, int(heads), int(kv_heads), int(head_dim),
+                                                            _f(ca), ca.shape[1]))
+    return ca
+
+
+def _tables(cos, sin, head_dim):
+    ct, st = np.ascontiguousarray(cos, np.float32), np.ascontiguousarray(sin, np.float32)
+    if ct.ndim != 2 or ct.shape != st.shape or ct.shape[1] != head_dim // 2:
+        raise ValueError("cos and sin: [table_rows, head_dim // 2]")
+    return ct, st
+
+
+def rope(x, rows: int, n_heads: int, head_dim: int, cos, sin, pos: int, device: int = 0):
+    """The RoPE kernel of the prompt and decode paths alone: x [x_rows, ldx] -> x with its first `rows` rows rotated by table
+    rows pos, pos + 1, ..."""
+    xa = np.array(x, np.float32, order="C")
+    ct, st = _tables(cos, sin, head_dim)
+    check_error(lib().kjarni_hip_op_rope(device, _f(xa), xa.shape[1], xa.shape[0], int(rows), int(n_heads), int(head_dim), _f(ct), _f(st),
+                                         ct.shape[0], int(pos)))
+    return xa
+
+
+def rope_rows(x, row_pos, n_heads: int, head_dim: int, cos, sin, device: int = 0):
+    """rope() with row r rotated by table row row_pos[r]; len(row_pos) rows are processed."""
+    xa = np.array(x, np.float32, order="C")
+    rp = np.ascontiguousarray(row_pos, np.int32)
+    ct, st = _tables(cos, sin, head_dim)
+    check_error(lib().kjarni_hip_op_rope_rows(device, _f(xa), xa.shape[1], xa.shape[0], rp.size, int(n_heads), int(head_dim), _f(ct), _f(st),
+                                              ct.shape[0], rp.ctypes.data_as(_i32p)))
+    return xa
+
+
+def qk_norm_rope_rows(q, k, row_pos, n_heads: int, n_kv_heads: int, head_dim: int, gamma_q, gamma_k, eps: float, cos, sin, device: int = 0):
+    """qk_norm_rope() with row r at position row_pos[r] (its K heads are row r of k): (q, k) after the call on len(row_pos)
+    rows."""
+    qa, ka = np.array(q, np.float32, order="C"), np.array(k, np.float32, order="C")
+    gq, gk = np.ascontiguousarray(gamma_q, np.float32), np.ascontiguousarray(gamma_k, np.float32)
+    rp = np.ascontiguousarray(row_pos, np.int32)
+    ct, st = _tables(cos, sin, head_dim)
+    if qa.ndim != 2 or ka.ndim != 2 or gq.shape != (head_dim,) or gk.shape != (head_dim,):
+        raise ValueError("q and k: [rows, ld]; gammas: [head_dim]")
+    check_error(lib().kjarni_hip_op_qk_norm_rope_rows(device, _f(qa), qa.shape[1], qa.shape[0], _f(ka), ka.shape[1], ka.shape[0], rp.size,
+                                                      int(n_heads), int(n_kv_heads), int(head_dim), _f(gq), _f(gk), float(eps), _f(ct), _f(st),
+                                                      ct.shape[0], rp.ctypes.data_as(_i32p)))
+    return qa, ka
+
+
+def last_token_pool(x, lengths, gamma, eps: float, normalize: bool = True, hidden=None, device: int = 0):
+    """The last-token pool alone: x [rows, ldx] holds the sequences of `lengths` one after another; returns
+    [len(lengths), hidden] -- every sequence's last row through RMSNorm(gamma, eps) and, when `normalize`, divided by its L2 norm
+    where that is > 0."""
+    xa = np.ascontiguousarray(x, np.float32)
+    g = np.ascontiguousarray(gamma, np.float32)
+    hidden = g.size if hidden is None else int(hidden)
+    st = _seq_start(lengths)
+    out = np.zeros((st.size - 1, hidden), np.float32)
+    check_error(lib().kjarni_hip_op_last_token_pool(device, _f(xa), xa.shape[1], xa.shape[0], st.ctypes.data_as(_i32p), st.size - 1, hidden,
+                                                    _f(g), float(eps), int(bool(normalize)), _f(out)))
+    return out
+
+
 def argmax(logits, vocab: Optional[int] = None, route: int = ARGMAX_DECODER, live=None, draft=None, device: int = 0):
     """The greedy pick kernels on logits [calls, rows, ld] (the last of equal maxima wins; columns >= vocab are padding).
     Returns picks int32 [calls, rows]: decoder route rows == 1; lanes route -1 for the lanes `live` [rows] freezes; lookup

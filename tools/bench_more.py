@@ -52,6 +52,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            ms per token (six launches per layer: the per-head Q / K norm + RoPE is a launch of its own).  The line also goes
            to profiles/qwen3_bench_llm.jsonl.  KJARNI_QWEN3_TRACE=N: a 128-token prompt and N decode steps only (for a
            kernel trace).
+  llm_embed  (only on request) HipDecoder.embed() -- decoder embedders, last-token pooling over packed batches -- on the Qwen3-0.6B
+           shape (bf16, random init): sentences/s for 4 096 x 128 tokens and for 4 096 ragged sentences of U{16..128} tokens,
+           the latency of 1, 8 and 64 x 128, and in the same run a loop of forward() + last_hidden() per sentence (what there
+           was before embed()) over the same 64 x 128, alternated twice; medians of runs that end in a synchronise.  The lines
+           also go to profiles/decoder_embed_bench.jsonl.
 """
 import json
 import os
@@ -1245,6 +1250,78 @@ def main():
         with open(os.path.join(ROOT, "profiles", "qwen3_bench_llm.jsonl"), "w") as f:
             f.write(json.dumps(line) + "\n")
         del dec
+
+    if "llm_embed" in which:
+        # Method (measuring guide, section 5): one process on one box; every shape is warmed first; embed() returns after a
+        # synchronise and a device-to-host copy, forward(fetch=True) after the copy of its hidden rows; medians.  The packed call and
+        # the per-sentence loop over 64 x 128 are alternated twice, three runs each.
+        from tests import qwen3_fixture
+        geo = dict(qwen3_fixture.Q3_06B_WIDTHS, num_hidden_layers=28, vocab_size=151936, max_position_embeddings=4096, eos_token_id=[])
+        d = os.path.join(tmp, "qwen3-0.6b-embed")
+        qwen3_fixture.qwen3_model(d, geo, seed=0, store_bf16=True, std=0.02)
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        rng = np.random.default_rng(0)
+        dtype = "bf16 weights, f32 activations/accumulate"
+        shape = "Qwen3-0.6B geometry (1024 hidden, 28 layers, 16/8 heads of 128, intermediate 3072, vocab 151936), random init"
+        lines = []
+
+        def batch(lengths):
+            flat = rng.integers(1000, 100000, int(np.sum(lengths))).astype(np.uint32)
+            return flat, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+
+        def run_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            return (time.perf_counter() - t0) * 1e3
+
+        for label, lengths in (("4096 x 128 tokens", np.full(4096, 128)), ("4096 ragged sentences of U{16..128} tokens", rng.integers(16, 129, 4096))):
+            flat, offsets = batch(lengths)
+            out = np.zeros((len(lengths), dec.hidden), np.float32)
+            dec.embed_flat(flat, offsets, True, out)
+            runs = [run_ms(lambda: dec.embed_flat(flat, offsets, True, out)) for _ in range(3)]
+            ms = float(np.median(runs))
+            first, vec, mfma = kjarni_amd.embed_plan(lengths.tolist(), dec.head_dim)
+            line = {"metric": f"sentences/sec decoder embed (last-token pool), Qwen3-0.6B shape, bf16 weights, {label}",
+                    "value": round(len(lengths) / ms * 1e3, 1), "unit": "sentences/s", "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"{shape}; HipDecoder.embed of token ids, normalize on; medians of 3 runs after one warm-up"},
+                    "tokens": int(np.sum(lengths)), "tokens_per_s": round(float(np.sum(lengths)) / ms * 1e3, 1), "ms": round(ms, 2),
+                    "chunks": len(first) - 1, "runs_ms": [round(x, 2) for x in runs]}
+            emit(line)
+            lines.append(line)
+        for n in (1, 8, 64):
+            flat, offsets = batch(np.full(n, 128))
+            out = np.zeros((n, dec.hidden), np.float32)
+            seqs = [flat[offsets[i]:offsets[i + 1]] for i in range(n)]
+
+            def loop():
+                for s in seqs:
+                    dec.reset()
+                    dec.forward(s)
+            kinds = {"embed": lambda: dec.embed_flat(flat, offsets, True, out)}
+            if n == 64:
+                kinds["forward_loop"] = loop
+            for fn in kinds.values():
+                fn()
+            runs = {k: [] for k in kinds}
+            for rep in range(2):
+                for _ in range(3):
+                    for k, fn in kinds.items():
+                        runs[k].append(run_ms(fn))
+            med = {k: float(np.median(v)) for k, v in runs.items()}
+            line = {"metric": f"latency decoder embed, Qwen3-0.6B shape, bf16 weights, {n} x 128 tokens", "value": round(med["embed"], 3),
+                    "unit": "ms", "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"{shape}; alternated twice in one process, medians of 6 runs, every run ends in a synchronise"},
+                    "sentences": n, "embed_ms": round(med["embed"], 3), "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+            if n == 64:
+                line["forward_loop_ms"] = round(med["forward_loop"], 3)
+                line["forward_loop_over_embed"] = round(med["forward_loop"] / med["embed"], 2)
+            emit(line)
+            lines.append(line)
+        dec.reset()
+        del dec
+        with open(os.path.join(ROOT, "profiles", "decoder_embed_bench.jsonl"), "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
 
 if __name__ == "__main__":
