@@ -455,6 +455,14 @@ KjarniErrorCode kjarni_generator_generate_batch(KjarniGenerator* generator, cons
  * continuation that adds no token, or a text longer than the model's context, is INVALID_CONFIG with the reason. */
 typedef struct KjarniScoreResult { double sum_logprob; size_t n_tokens; int32_t is_greedy; } KjarniScoreResult;
 KjarniErrorCode kjarni_generator_score(KjarniGenerator* generator, const char* context, const char* continuation, KjarniScoreResult* out);
+/* kjarni_generator_score for n (context, continuation) pairs in one call (not in the reference); out [n] is the caller's.  Every
+ * pair is encoded and checked by kjarni_generator_score's rules first: a failure is this call's error, with "pair <index>" in
+ * front of the message, and nothing is computed.  The pairs then run packed, in the caller's order, through
+ * kjarni_hip_decoder_score_batch, so neighbouring pairs that repeat a context compute it once; pairs of more than 2 048 tokens
+ * (inside the model's context), and every pair on a checkpoint the packed path refuses, are scored one by one as
+ * kjarni_generator_score does.  sum_logprob is the float64 sum in order, as there.  n == 0: OK. */
+KjarniErrorCode kjarni_generator_score_batch(KjarniGenerator* generator, const char* const* contexts, const char* const* continuations,
+                                             size_t n, KjarniScoreResult* out);
 /* kjarni_generator_score token by token, with the top_k (1 .. 8, not above the vocabulary) most likely tokens of every scored
  * position (not in the reference).  Encoding rules and errors are kjarni_generator_score's; top_k out of range: INVALID_CONFIG.
  * tokens / logprobs [n_tokens]: the scored tokens and their log-probabilities (their float64 sum in order is

@@ -866,6 +866,59 @@ KjarniErrorCode kjarni_hip_op_qk_norm_rope_rows(int32_t device, float* q, int64_
 KjarniErrorCode kjarni_hip_op_last_token_pool(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* seq_start,
                                               int32_t n_sequences, int32_t hidden, const float* gamma, float eps, int32_t normalize,
                                               float* out);
+/* ---- scoring many sequences in one packed pass ------------------------------------------------------------------------------------
+ * kjarni_hip_decoder_score_batch: kjarni_hip_decoder_score / _score_topk for n_sequences sequences at once.  Sequence b is
+ * ids[offsets[b], offsets[b + 1]) and its scored positions are [firsts[b], len_b), 1 <= firsts[b] < len_b.  The outputs are flat, in
+ * sequence order then position order: logprob_out [S], S = sum(len_b - firsts[b]); topk_ids_out / topk_logprob_out [S, top_k]
+ * row-major (top_k 1 .. KJARNI_SCORE_TOPK_MAX, not above the vocabulary; slot 0 is kjarni_hip_decoder_score's top /
+ * top_logprob).  Any output may be NULL.  The sequences are packed in order into chunks of at most KJARNI_HIP_EMBED_CHUNK_ROWS
+ * rows (kjarni_hip_score_plan) and every chunk runs kjarni_hip_decoder_embed's layer stack once over its rows; a token prefix that
+ * neighbouring sequences share -- never a scored token -- is computed once, and only the rows whose successor is scored reach the
+ * vocabulary head, on kjarni_hip_decoder_score's routes (counted by kjarni_hip_decoder_score_calls).  Sharing is decided from the
+ * input alone.  The KV cache, the resident tokens, the lanes, the logits, the last hidden rows, the prefix-reuse counters and the
+ * buffers of kjarni_hip_decoder_score are left as they were.  INVALID_CONFIG, before any GPU work, naming the argument and the
+ * sequence: offsets that decrease, a sequence shorter than 2 or longer than min(context, KJARNI_HIP_EMBED_CHUNK_ROWS), firsts[b]
+ * out of range, an id >= vocab, top_k out of range; also for quantized checkpoints and for hidden / heads * head_dim /
+ * intermediate sizes that are no multiple of 32 (GPT-2 is accepted).  n_sequences == 0 is OK and writes nothing. */
+#define KJARNI_HIP_SCORE_MIN_SHARED 2 /* the shortest shared prefix kjarni_hip_decoder_score_batch computes once (its plan's min_shared) */
+KjarniErrorCode kjarni_hip_decoder_score_batch(KjarniHipDecoder* decoder, const uint32_t* ids, const int32_t* offsets, int32_t n_sequences,
+                                               const int32_t* firsts, int32_t top_k, float* logprob_out, uint32_t* topk_ids_out,
+                                               float* topk_logprob_out);
+/* Rows kjarni_hip_decoder_score_batch computed, and prefix rows it did not compute a second time (the sum of (members - 1) *
+ * prefix over its groups), since load (zeros on NULL; either output may be NULL). */
+void kjarni_hip_decoder_score_batch_rows(const KjarniHipDecoder* decoder, uint64_t* computed, uint64_t* saved);
+/* The plan alone (host only).  Walking the sequences in order, sequence i gathers the neighbours behind it while the prefix
+ * q = min(prefix so far, firsts[j], common prefix of i and j) stays >= min_shared (>= 1), the group's rows q + sum(len - q) fit
+ * KJARNI_HIP_EMBED_CHUNK_ROWS and every remainder len - q stays below 256 rows; two or more members form a group (its prefix
+ * rows first, then each remainder), else sequence i stays plain.  Units go greedily, in order, into chunks and never straddle
+ * one.  chunk_first_seq (n + 1 entries, may be NULL): each chunk's first sequence and, behind the last, n; chunk_rows (n entries,
+ * may be NULL): each chunk's rows; groups [capacity, 4]: (chunk, first sequence, members, prefix length).  Prefixes and plain
+ * sequences get their blocks by kjarni_hip_embed_plan's rule into vec_blocks / mfma_blocks [capacity, 4] (chunk, first row, the
+ * block's first query row, length); every remainder gets one block per 32 query rows in prefix_blocks [capacity, 6] (chunk, the
+ * remainder's first row, the block's first query row in the remainder, the remainder's length, the prefix's first row, the
+ * prefix length).  gather [capacity, 4]: for every scored position pos, in sequence order then position order, (chunk, the chunk
+ * row of position pos - 1 -- the prefix's last row when pos - 1 is its last token --, the target id, the slot in the flat
+ * outputs).  Every table may be NULL; the counts are always written.  INVALID_CONFIG naming the argument and the sequence for
+ * offsets that decrease, a length outside 2 .. KJARNI_HIP_EMBED_CHUNK_ROWS and firsts[b] outside [1, len_b). */
+KjarniErrorCode kjarni_hip_score_plan(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int32_t n, int32_t head_dim,
+                                      int32_t min_shared, int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks, int32_t* groups,
+                                      int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks, int32_t vec_capacity, int32_t* n_vec,
+                                      int32_t* mfma_blocks, int32_t mfma_capacity, int32_t* n_mfma, int32_t* prefix_blocks,
+                                      int32_t prefix_capacity, int32_t* n_prefix, int32_t* gather, int32_t gather_capacity, int32_t* n_gather);
+/* The prefix attention kernel alone, host pointers; q / k / v / ctx as kjarni_hip_op_packed_causal_attention takes them.
+ * remainders [n_remainders, 4]: (first row, rows, the prefix's first row, prefix rows).  The query at row t of a remainder sees
+ * the prefix rows and the remainder's rows 0 .. t; its context row is what kjarni_hip_op_packed_causal_attention's vector kernel
+ * gives for row prefix + t of the concatenation, bit for bit.  ctx is read and written back whole.  INVALID_CONFIG: rows outside
+ * the buffer, a prefix that overlaps its remainder, head_dim not 16 / 32 / 64 / 128, leading dimensions that are no multiple of 4. */
+KjarniErrorCode kjarni_hip_op_packed_prefix_attention(int32_t device, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                                      int64_t ldv, int32_t buffer_rows, const int32_t* remainders, int32_t n_remainders,
+                                                      int32_t heads, int32_t kv_heads, int32_t head_dim, float* ctx, int64_t ldc);
+/* The gather + final norm alone, host pointers: out[j, 0 .. hidden) = norm(x[src[j], :]) for j < n, out rows ldo floats apart (ldo a
+ * multiple of 4; out is read and written back whole).  beta NULL: (x / sqrt(mean(x^2) + eps)) * gamma, bit for bit
+ * kjarni_hip_op_last_token_pool without normalisation on the same rows; beta given: LayerNorm, bit for bit kjarni_hip_op_layer_norm
+ * on the gathered rows.  src[j] outside [0, x_rows): INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_score_gather_norm(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* src, int32_t n,
+                                                int32_t hidden, const float* gamma, const float* beta, float eps, float* out, int64_t ldo);
 /* The switch and the counters on the Chat and Generator handles' models (send, generate, score and generate_batch take it). */
 KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);

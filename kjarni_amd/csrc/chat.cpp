@@ -620,6 +620,69 @@ Generator::Score Generator::score(const std::string& context, const std::string&
     return r;
 }
 
+std::vector<Generator::Score> Generator::score_batch(const std::vector<std::pair<std::string, std::string>>& pairs)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    const size_t n = pairs.size();
+    std::vector<std::vector<uint32_t>> whole(n);
+    std::vector<size_t> first(n);
+    for (size_t i = 0; i < n; ++i) {
+        try {
+            first[i] = encode_scored(pairs[i].first, pairs[i].second, whole[i]);
+        } catch (const InvalidConfig& e) {
+            throw InvalidConfig("pair " + std::to_string(i) + ": " + e.what());
+        }
+    }
+    std::vector<Score> out(n);
+    auto fill = [&](size_t i, const float* lp, const uint32_t* top) {
+        Score& r = out[i];
+        r.n_tokens = whole[i].size() - first[i];
+        r.is_greedy = true;
+        for (size_t t = 0; t < r.n_tokens; ++t) {
+            r.sum_logprob += (double)lp[t];
+            if (top[t] != whole[i][first[i] + t]) r.is_greedy = false;
+        }
+    };
+    // the packed pairs, in the caller's order
+    const bool packed_model = model_->score_batch_supported();
+    const size_t limit = (size_t)model_->embed_max_tokens();
+    std::vector<size_t> packed;
+    std::vector<uint32_t> ids;
+    std::vector<int32_t> offsets(1, 0), firsts;
+    for (size_t i = 0; i < n; ++i) {
+        if (!packed_model || whole[i].size() > limit || ids.size() + whole[i].size() > (size_t)INT32_MAX) continue;
+        packed.push_back(i);
+        ids.insert(ids.end(), whole[i].begin(), whole[i].end());
+        offsets.push_back((int32_t)ids.size());
+        firsts.push_back((int32_t)first[i]);
+    }
+    if (!packed.empty()) {
+        size_t total = 0;
+        for (size_t i : packed) total += whole[i].size() - first[i];
+        std::vector<float> lp(total);
+        std::vector<uint32_t> top(total);
+        model_->score_batch(ids.data(), offsets.data(), (int)packed.size(), firsts.data(), 1, lp.data(), top.data(), nullptr);
+        size_t at = 0;
+        for (size_t i : packed) {
+            fill(i, lp.data() + at, top.data() + at);
+            at += whole[i].size() - first[i];
+        }
+    }
+    size_t next = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (next < packed.size() && packed[next] == i) {
+            ++next;
+            continue;
+        }
+        const size_t cnt = whole[i].size() - first[i];
+        std::vector<float> lp(cnt);
+        std::vector<uint32_t> top(cnt);
+        model_->score(whole[i].data(), (int)whole[i].size(), (int)first[i], lp.data(), top.data(), nullptr);
+        fill(i, lp.data(), top.data());
+    }
+    return out;
+}
+
 Generator::TokenScores Generator::score_tokens(const std::string& context, const std::string& continuation, size_t top_k)
 {
     std::lock_guard<std::mutex> lock(mutex_);

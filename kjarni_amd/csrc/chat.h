@@ -177,6 +177,12 @@ public:
         size_t top_k = 0;
     };
     TokenScores score_tokens(const std::string& context, const std::string& continuation, size_t top_k);
+    // score() for every (context, continuation) pair.  All pairs are encoded and checked by score()'s rules first: a failure is
+    // the call's InvalidConfig with the pair's index in front of the reason, and nothing is computed.  The pairs the packed path
+    // takes run through LlmModel::score_batch in the caller's order (neighbouring pairs that repeat a context share its rows);
+    // the others -- pairs longer than LlmModel::embed_max_tokens(), or every pair on a checkpoint score_batch refuses -- through
+    // LlmModel::score one by one.
+    std::vector<Score> score_batch(const std::vector<std::pair<std::string, std::string>>& pairs);
 
 private:
     Generator() = default;

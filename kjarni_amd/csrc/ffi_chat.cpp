@@ -395,6 +395,27 @@ KJARNI_EXPORT KjarniErrorCode kjarni_generator_score(KjarniGenerator* gen, const
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_generator_score_batch(KjarniGenerator* gen, const char* const* contexts, const char* const* continuations,
+                                                           size_t n, KjarniScoreResult* out)
+{
+    if (!gen || (n && (!contexts || !continuations || !out))) return KJARNI_ERROR_NULL_POINTER;
+    std::vector<std::pair<std::string, std::string>> pairs(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!contexts[i] || !continuations[i]) return KJARNI_ERROR_NULL_POINTER;
+        if (!valid_utf8(contexts[i]) || !valid_utf8(continuations[i])) return KJARNI_ERROR_INVALID_UTF8;
+        pairs[i] = {contexts[i], continuations[i]};
+    }
+    if (n == 0) return KJARNI_OK;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const std::vector<Generator::Score> got = gen->inner->score_batch(pairs);
+        for (size_t i = 0; i < n; ++i) {
+            out[i].sum_logprob = got[i].sum_logprob;
+            out[i].n_tokens = got[i].n_tokens;
+            out[i].is_greedy = got[i].is_greedy ? 1 : 0;
+        }
+    });
+}
+
 KJARNI_EXPORT void kjarni_token_scores_free(KjarniTokenScores* s)
 {
     if (!s) return;

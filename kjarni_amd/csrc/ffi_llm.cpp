@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "decoder_embed_kernels.h"
+#include "score_batch_kernels.h"
 #include "llm_kernels.h"
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
@@ -452,6 +453,82 @@ KJARNI_EXPORT void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* d, uin
 {
     if (fused) *fused = d ? d->model->score_fused_calls() : 0;
     if (rows) *rows = d ? d->model->score_rows_calls() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_score_batch(KjarniHipDecoder* d, const uint32_t* ids, const int32_t* offsets,
+                                                             int32_t n_sequences, const int32_t* firsts, int32_t top_k, float* logprob_out,
+                                                             uint32_t* topk_ids_out, float* topk_logprob_out)
+{
+    if (!d || (n_sequences > 0 && (!ids || !offsets || !firsts))) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->score_batch(ids, offsets, n_sequences, firsts, top_k, logprob_out, topk_ids_out, topk_logprob_out);  // checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_score_batch_rows(const KjarniHipDecoder* d, uint64_t* computed, uint64_t* saved)
+{
+    if (computed) *computed = d ? d->model->score_batch_rows() : 0;
+    if (saved) *saved = d ? d->model->score_batch_saved_rows() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_score_plan(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int32_t n, int32_t head_dim,
+                                                    int32_t min_shared, int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks,
+                                                    int32_t* groups, int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks,
+                                                    int32_t vec_capacity, int32_t* n_vec, int32_t* mfma_blocks, int32_t mfma_capacity,
+                                                    int32_t* n_mfma, int32_t* prefix_blocks, int32_t prefix_capacity, int32_t* n_prefix,
+                                                    int32_t* gather, int32_t gather_capacity, int32_t* n_gather)
+{
+    if ((n > 0 && (!ids || !offsets || !firsts)) || !n_chunks || !n_groups || !n_vec || !n_mfma || !n_prefix || !n_gather)
+        return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        if (n < 0 || group_capacity < 0 || vec_capacity < 0 || mfma_capacity < 0 || prefix_capacity < 0 || gather_capacity < 0)
+            throw InvalidConfig("n and the capacities must not be negative");
+        const ScorePlan plan = score_plan_host(ids, offsets, firsts, n, head_dim, min_shared);
+        int32_t nv = 0, nm = 0, np = 0, ng = 0;
+        for (size_t c = 0; c < plan.chunks.size(); ++c) {
+            const ScoreChunk& ch = plan.chunks[c];
+            if (chunk_first_seq) chunk_first_seq[c] = ch.first_seq;
+            if (chunk_rows) chunk_rows[c] = ch.rows;
+            auto put = [&](const std::vector<EmbedBlock>& src, int32_t* dst, int32_t cap, int32_t& cnt) {
+                for (const EmbedBlock& b : src) {
+                    if (dst && cnt < cap) {
+                        int32_t* w = dst + 4 * (size_t)cnt;
+                        w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len;
+                    }
+                    ++cnt;
+                }
+            };
+            put(ch.vec, vec_blocks, vec_capacity, nv);
+            put(ch.mfma, mfma_blocks, mfma_capacity, nm);
+            for (const PrefixBlock& b : ch.prefix) {
+                if (prefix_blocks && np < prefix_capacity) {
+                    int32_t* w = prefix_blocks + 6 * (size_t)np;
+                    w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len; w[4] = b.prefix_first; w[5] = b.prefix_len;
+                }
+                ++np;
+            }
+            for (size_t j = 0; j < ch.gather_src.size(); ++j) {
+                if (gather && ng < gather_capacity) {
+                    int32_t* w = gather + 4 * (size_t)ng;
+                    w[0] = (int32_t)c; w[1] = ch.gather_src[j]; w[2] = ch.gather_tgt[j]; w[3] = ch.gather_slot[j];
+                }
+                ++ng;
+            }
+        }
+        if (chunk_first_seq) chunk_first_seq[plan.chunks.size()] = n;
+        for (size_t g = 0; g < plan.groups.size(); ++g)
+            if (groups && (int32_t)g < group_capacity) {
+                int32_t* w = groups + 4 * g;
+                w[0] = plan.groups[g].chunk; w[1] = plan.groups[g].first_seq; w[2] = plan.groups[g].n_seq; w[3] = plan.groups[g].prefix;
+            }
+        *n_chunks = (int32_t)plan.chunks.size();
+        *n_groups = (int32_t)plan.groups.size();
+        *n_vec = nv;
+        *n_mfma = nm;
+        *n_prefix = np;
+        *n_gather = ng;
+    });
 }
 
 // ---- embedding --------------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include "gguf.h"
 #include "llm.h"
 #include "decoder_embed_kernels.h"
+#include "score_batch_kernels.h"
 #include "llm_kernels.h"
 #include "quant_kernels.h"
 #include "tuning.h"
@@ -840,6 +841,82 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_last_token_pool(int32_t device, cons
         hip_check(hipDeviceSynchronize(), "sync");
         hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
         od.check("last-token pool");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_packed_prefix_attention(int32_t device, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                                                    const float* v, int64_t ldv, int32_t buffer_rows, const int32_t* remainders,
+                                                                    int32_t n_remainders, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                                                    float* ctx, int64_t ldc)
+{
+    if (!q || !k || !v || !remainders || !ctx) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128) throw InvalidConfig("head_dim must be 16, 32, 64 or 128");
+        if (heads < 1 || heads > 1024 || kv_heads < 1 || kv_heads > heads || heads % kv_heads)
+            throw InvalidConfig("heads must be 1..1024 and a multiple of kv_heads");
+        if (buffer_rows < 1 || buffer_rows > (1 << 22)) throw InvalidConfig("buffer_rows must be 1 .. 2^22");
+        const int64_t qd = (int64_t)heads * head_dim, kvd = (int64_t)kv_heads * head_dim;
+        if (ldq < qd || ldc < qd || ldk < kvd || ldv < kvd || ((ldq | ldk | ldv | ldc) & 3) || std::max(std::max(ldq, ldc), std::max(ldk, ldv)) > (1 << 20))
+            throw InvalidConfig("leading dimensions must cover the heads, be multiples of 4 and at most 2^20");
+        if (n_remainders < 1 || n_remainders > (1 << 20)) throw InvalidConfig("n_remainders must be 1 .. 2^20");
+        std::vector<PrefixBlock> blocks;
+        for (int32_t r = 0; r < n_remainders; ++r) {
+            const int32_t first = remainders[4 * r], len = remainders[4 * r + 1], pf = remainders[4 * r + 2], pl = remainders[4 * r + 3];
+            const std::string which = "remainders[" + std::to_string(r) + "]";
+            if (first < 0 || len < 1 || len > buffer_rows - first)
+                throw InvalidConfig(which + ": rows " + std::to_string(first) + " .. " + std::to_string((int64_t)first + len - 1) + " are outside the " +
+                                    std::to_string(buffer_rows) + " rows given");
+            if (pl < 0 || pf < 0 || pl > buffer_rows - pf)
+                throw InvalidConfig(which + ": the prefix rows " + std::to_string(pf) + " .. " + std::to_string((int64_t)pf + pl - 1) +
+                                    " are outside the " + std::to_string(buffer_rows) + " rows given");
+            if (pl > 0 && pf < first + len && first < pf + pl) throw InvalidConfig(which + ": the prefix overlaps the remainder");
+            for (int32_t q0 = 0; q0 < len; q0 += 32) blocks.push_back(PrefixBlock{first, q0, len, pf, pl});
+        }
+        use_device(device);
+        const size_t R = (size_t)buffer_rows;
+        DeviceBuf qd_(R * (size_t)ldq * 4), kd(R * (size_t)ldk * 4), vd(R * (size_t)ldv * 4), cd(R * (size_t)ldc * 4);
+        DeviceBuf tb(blocks.size() * sizeof(PrefixBlock));
+        hip_check(hipMemcpy(qd_.p, q, R * (size_t)ldq * 4, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, R * (size_t)ldk * 4, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(vd.p, v, R * (size_t)ldv * 4, hipMemcpyHostToDevice), "H2D v");
+        hip_check(hipMemcpy(cd.p, ctx, R * (size_t)ldc * 4, hipMemcpyHostToDevice), "H2D ctx");
+        hip_check(hipMemcpy(tb.p, blocks.data(), blocks.size() * sizeof(PrefixBlock), hipMemcpyHostToDevice), "H2D blocks");
+        hip_check(launch_packed_prefix_attention((const float*)qd_.p, ldq, (const float*)kd.p, ldk, (const float*)vd.p, ldv, (const PrefixBlock*)tb.p,
+                                                 (int)blocks.size(), heads, head_dim, heads / kv_heads, (float*)cd.p, ldc, nullptr),
+                  "packed prefix attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(ctx, cd.p, R * (size_t)ldc * 4, hipMemcpyDeviceToHost), "D2H ctx");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_gather_norm(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* src,
+                                                              int32_t n, int32_t hidden, const float* gamma, const float* beta, float eps,
+                                                              float* out, int64_t ldo)
+{
+    if (!x || !src || !gamma || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (hidden < 1 || hidden > 16384 || ldx < hidden || ldx > (1 << 20)) throw InvalidConfig("hidden must be 1 .. 16384 and ldx cover it");
+        if (ldo < hidden || ldo > (1 << 20) || (ldo & 3)) throw InvalidConfig("ldo must cover hidden and be a multiple of 4");
+        if (x_rows < 1 || x_rows > (1 << 22)) throw InvalidConfig("x_rows must be 1 .. 2^22");
+        if (n < 1 || n > (1 << 20)) throw InvalidConfig("n must be 1 .. 2^20");
+        for (int32_t j = 0; j < n; ++j)
+            if (src[j] < 0 || src[j] >= x_rows)
+                throw InvalidConfig("src[" + std::to_string(j) + "] = " + std::to_string(src[j]) + " is outside the " + std::to_string(x_rows) +
+                                    " rows given");
+        use_device(device);
+        const size_t xb = (size_t)x_rows * (size_t)ldx * 4, ob = (size_t)n * (size_t)ldo * 4;
+        DeviceBuf xd(xb), gd((size_t)hidden * 4), bd((size_t)hidden * 4), sd((size_t)n * 4);
+        GuardedBuf od(ob);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        hip_check(hipMemcpy(gd.p, gamma, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D gamma");
+        if (beta) hip_check(hipMemcpy(bd.p, beta, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D beta");
+        hip_check(hipMemcpy(sd.p, src, (size_t)n * 4, hipMemcpyHostToDevice), "H2D src");
+        hip_check(hipMemcpy(od.buf.p, out, ob, hipMemcpyHostToDevice), "H2D out");  // (padding columns come back as given)
+        hip_check(launch_score_gather_norm((const float*)xd.p, ldx, (const int32_t*)sd.p, n, hidden, (const float*)gd.p,
+                                           beta ? (const float*)bd.p : nullptr, eps, od.as<float>(), ldo, nullptr), "score gather + norm");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
+        od.check("score gather + norm");
     });
 }
 

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "decoder_embed_kernels.h"
 #include "llm_kernels.h"
+#include "score_batch_kernels.h"
 #include "safetensors.h"
 #include "whisper_kernels.h"
 
@@ -139,6 +140,7 @@ LlmModel::~LlmModel()
 {
     if (host_logits_) (void)hipHostFree(host_logits_);
     if (emeta_host_) (void)hipHostFree(emeta_host_);
+    if (sb_res_host_) (void)hipHostFree(sb_res_host_);
     if (samp_host_) (void)hipHostFree(samp_host_);
     if (ls_host_) (void)hipHostFree(ls_host_);
     (void)hipSetDevice(device_);
@@ -2237,6 +2239,68 @@ std::vector<EmbedChunk> embed_plan_host(const int32_t* lengths, int n, int head_
     return chunks;
 }
 
+namespace {
+
+// A chunk's metadata on the device.  embed_batch: ids [m] | row_pos [m] | seq_start [n + 1] | vec blocks | mfma blocks with
+// m <= 2048 rows, n <= 2048 sequences, at most m / 32 + n vec blocks and m / 128 + n / 256 + 1 mfma blocks of 3 words.
+// score_batch: ids [m] | row_pos [m] | gather rows [g] | targets [g] | vec | mfma | prefix blocks with g < m scored positions, at
+// most m blocks in the vec and in the prefix table (a block has at least one row of its own) of 3 and 5 words.
+constexpr size_t kPackedMetaWords = 4 * (size_t)kEmbedChunkRows + 3 * (size_t)kEmbedChunkRows + 3 * 32 + 5 * (size_t)kEmbedChunkRows + 8;
+
+}  // namespace
+
+void LlmModel::ensure_packed_scratch()
+{
+    if (ek_) return;
+    const int kv = cfg_.kv_heads * cfg_.head_dim;
+    ek_ = dalloc((size_t)kEmbedChunkRows * kv);
+    ev_ = dalloc((size_t)kEmbedChunkRows * kv);
+    emeta_ = reinterpret_cast<int32_t*>(dalloc(kPackedMetaWords));
+    hip_check(hipHostMalloc((void**)&emeta_host_, kPackedMetaWords * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
+}
+
+void LlmModel::packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_pos, const EmbedBlock* vec, int nv, const EmbedBlock* mfma,
+                             int nm, const PrefixBlock* prefix, int np)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    hipStream_t s = stream_;
+    const int wb = bf16_ ? 1 : 0;
+    const size_t wsz = bf16_ ? 2 : 4;
+    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
+    if (gpt2_) hip_check(launch_llm_embed_pos(ids_dev, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, ph_, s, row_pos), "embed");
+    else hip_check(launch_llm_embed(ids_dev, m, H, c.vocab, embed_, wb, ph_, s), "embed");
+    for (const Layer& L : layers_) {
+        if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
+        else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
+        prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj");
+        prompt_proj(m, pn_, H, at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, ek_, kv, kv, H, nullptr, "k proj");
+        prompt_proj(m, pn_, H, at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, ev_, kv, kv, H, nullptr, "v proj");
+        if (c.qwen3()) {
+            hip_check(launch_qk_norm_rope_rows(pq_, QD, ek_, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, row_pos, s),
+                      "qk norm + rope");
+        } else if (!gpt2_) {  // (GPT-2: learned positions, already in the embedding)
+            hip_check(launch_rope_rows(pq_, QD, m, c.heads, d, cos_, sin_, row_pos, s), "rope q");
+            hip_check(launch_rope_rows(ek_, kv, m, c.kv_heads, d, cos_, sin_, row_pos, s), "rope k");
+        }
+        hip_check(launch_packed_causal_attention(pq_, QD, ek_, kv, ev_, kv, vec, nv, mfma, nm, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
+                  "packed attention");
+        hip_check(launch_packed_prefix_attention(pq_, QD, ek_, kv, ev_, kv, prefix, np, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
+                  "packed prefix attention");
+        prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj");
+        if (gpt2_) {
+            hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
+            prompt_proj(m, pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
+            prompt_proj(m, pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
+            continue;
+        }
+        hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
+        prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate");
+        prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu");
+        prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj");
+    }
+}
+
 void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, bool normalize, float* out)
 {
     const LlmConfig& c = cfg_;
@@ -2269,23 +2333,12 @@ void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, b
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hipStream_t s = stream_;
     ensure_prompt_workspace();
-    // a chunk's metadata: ids [m] | row_pos [m] | seq_start [n + 1] | vec blocks | mfma blocks; the bound: m <= 2048 rows,
-    // n <= 2048 sequences, at most m / 32 + n vec blocks and m / 128 + n / 256 + 1 mfma blocks of 3 words
-    constexpr size_t kMetaWords = 3 * (size_t)kEmbedChunkRows + 4 + 3 * (kEmbedChunkRows / 32 + kEmbedChunkRows) + 3 * 32;
-    if (!ek_) {
-        ek_ = dalloc((size_t)kEmbedChunkRows * kv);
-        ev_ = dalloc((size_t)kEmbedChunkRows * kv);
-        emeta_ = reinterpret_cast<int32_t*>(dalloc(kMetaWords));
-        hip_check(hipHostMalloc((void**)&emeta_host_, kMetaWords * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
-    }
-    const int wb = bf16_ ? 1 : 0;
-    const size_t wsz = bf16_ ? 2 : 4;
-    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
+    ensure_packed_scratch();
     for (const EmbedChunk& ch : chunks) {
         const int m = ch.rows, n = ch.n_seq, nv = (int)ch.vec.size(), nm = (int)ch.mfma.size();
         const size_t o_pos = (size_t)m, o_start = o_pos + (size_t)m, o_vec = o_start + (size_t)n + 1, o_mfma = o_vec + 3 * (size_t)nv;
         const size_t words = o_mfma + 3 * (size_t)nm;
-        if (words > kMetaWords) throw std::runtime_error("embed: chunk metadata exceeds its buffer");
+        if (words > kPackedMetaWords) throw std::runtime_error("embed: chunk metadata exceeds its buffer");
         int32_t* hm = emeta_host_;
         std::memcpy(hm, ids + offsets[ch.first_seq], (size_t)m * 4);
         int row = 0;
@@ -2302,32 +2355,228 @@ void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, b
         const int32_t *row_pos = emeta_ + o_pos, *seq_start = emeta_ + o_start;
         const EmbedBlock* vec = reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec);
         const EmbedBlock* mfma = reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma);
-        hip_check(launch_llm_embed(ids_dev, m, H, c.vocab, embed_, wb, ph_, s), "embed");
-        for (const Layer& L : layers_) {
-            hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-            prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj");
-            prompt_proj(m, pn_, H, at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, ek_, kv, kv, H, nullptr, "k proj");
-            prompt_proj(m, pn_, H, at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, ev_, kv, kv, H, nullptr, "v proj");
-            if (c.qwen3()) {
-                hip_check(launch_qk_norm_rope_rows(pq_, QD, ek_, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, row_pos, s),
-                          "qk norm + rope");
-            } else {
-                hip_check(launch_rope_rows(pq_, QD, m, c.heads, d, cos_, sin_, row_pos, s), "rope q");
-                hip_check(launch_rope_rows(ek_, kv, m, c.kv_heads, d, cos_, sin_, row_pos, s), "rope k");
-            }
-            hip_check(launch_packed_causal_attention(pq_, QD, ek_, kv, ev_, kv, vec, nv, mfma, nm, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
-                      "packed attention");
-            prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj");
-            hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
-            prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate");
-            prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu");
-            prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj");
-        }
+        packed_layers(m, ids_dev, row_pos, vec, nv, mfma, nm, nullptr, 0);
         // (the norm buffer is free after the last layer: the pooled rows land there)
         hip_check(launch_last_token_pool(ph_, H, seq_start, n, H, final_norm_, c.eps, normalize ? 1 : 0, pn_, s), "last-token pool");
         hip_check(hipMemcpyAsync(out + (size_t)ch.first_seq * H, pn_, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, s), "D2H embeddings");
         hip_check(hipStreamSynchronize(s), "sync");  // the staging copy and the activations are reused by the next chunk
     }
+}
+
+// ---- scoring many sequences in one packed pass -------------------------------------------------------------------------------
+
+namespace {
+
+// offsets / firsts of score_plan_host and score_batch: InvalidConfig naming the argument and the sequence
+void check_score_sequences(const int32_t* offsets, const int32_t* firsts, int B, int limit)
+{
+    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    if (B == 0) return;
+    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
+        const std::string seq = " (sequence " + std::to_string(b) + ")";
+        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
+                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
+        if (len < 2)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens are fewer than 2: a scored token needs a prefix" + seq);
+        if (len > limit)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the score length limit of " + std::to_string(limit) + seq);
+        if (firsts[b] < 1 || firsts[b] >= len)
+            throw InvalidConfig("firsts[" + std::to_string(b) + "] = " + std::to_string(firsts[b]) + " must be in [1, " + std::to_string(len) +
+                                ")" + seq);
+    }
+}
+
+}  // namespace
+
+ScorePlan score_plan_host(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int B, int head_dim, int min_shared)
+{
+    check_score_sequences(offsets, firsts, B, kEmbedChunkRows);
+    if (min_shared < 1) throw InvalidConfig("min_shared (" + std::to_string(min_shared) + ") must be at least 1");
+    ScorePlan plan;
+    auto len_of = [&](int b) { return offsets[b + 1] - offsets[b]; };
+    auto lcp = [&](int a, int b, int cap) {  // common prefix of sequences a and b, at most cap
+        const uint32_t *x = ids + offsets[a], *y = ids + offsets[b];
+        const int n = std::min(cap, std::min(len_of(a), len_of(b)));
+        int k = 0;
+        while (k < n && x[k] == y[k]) ++k;
+        return k;
+    };
+    std::vector<int64_t> slot0((size_t)B + 1, 0);  // a sequence's first slot in the flat outputs
+    for (int b = 0; b < B; ++b) slot0[(size_t)b + 1] = slot0[(size_t)b] + (len_of(b) - firsts[b]);
+    auto add_blocks = [&](ScoreChunk& c, int first_row, int len) {  // embed_plan_host's rule
+        const bool mf = embed_seq_takes_mfma(len, head_dim);
+        for (int q0 = 0; q0 < len; q0 += mf ? 128 : 32) (mf ? c.mfma : c.vec).push_back(EmbedBlock{first_row, q0, len});
+    };
+    int i = 0;
+    while (i < B) {
+        int p = firsts[i], j = i + 1;
+        int64_t rest = len_of(i);  // sum of the members' lengths
+        int longest = len_of(i);
+        while (j < B) {
+            const int q = lcp(i, j, std::min(p, firsts[j]));  // a shared prefix never contains a scored token
+            if (q < min_shared) break;
+            const int64_t total = rest + len_of(j);
+            const int n_mem = j - i + 1;
+            if (q + (total - (int64_t)n_mem * q) > kEmbedChunkRows) break;  // a group lives in one chunk
+            if (std::max(longest, len_of(j)) - q >= 256) break;             // remainders take the 32-query route only
+            p = q;
+            rest = total;
+            longest = std::max(longest, len_of(j));
+            ++j;
+        }
+        const bool group = j - i >= 2;
+        if (!group) {
+            p = 0;
+            j = i + 1;
+        }
+        const int n_mem = j - i;
+        int cost = p;
+        for (int t = i; t < j; ++t) cost += len_of(t) - p;
+        if (plan.chunks.empty() || plan.chunks.back().rows + cost > kEmbedChunkRows) {
+            plan.chunks.emplace_back();
+            plan.chunks.back().first_seq = i;
+        }
+        ScoreChunk& c = plan.chunks.back();
+        const int prefix_first = c.rows;
+        if (group) {
+            plan.groups.push_back(ScoreGroup{(int)plan.chunks.size() - 1, i, n_mem, p});
+            plan.saved += (int64_t)(n_mem - 1) * p;
+            add_blocks(c, prefix_first, p);
+            for (int r = 0; r < p; ++r) {
+                c.row_tok.push_back(offsets[i] + r);
+                c.row_pos.push_back(r);
+            }
+            c.rows += p;
+        }
+        for (int t = i; t < j; ++t) {
+            const int len = len_of(t), own = len - p, first_row = c.rows;
+            if (group) {
+                for (int q0 = 0; q0 < own; q0 += 32) c.prefix.push_back(PrefixBlock{first_row, q0, own, prefix_first, p});
+            } else {
+                add_blocks(c, first_row, own);
+            }
+            for (int r = p; r < len; ++r) {
+                c.row_tok.push_back(offsets[t] + r);
+                c.row_pos.push_back(r);
+            }
+            for (int pos = firsts[t]; pos < len; ++pos) {  // position pos - 1: the prefix's last row when it is p - 1
+                c.gather_src.push_back(pos - 1 >= p ? first_row + (pos - 1 - p) : prefix_first + p - 1);
+                c.gather_tgt.push_back((int32_t)ids[offsets[t] + pos]);
+                c.gather_slot.push_back((int32_t)(slot0[(size_t)t] + (pos - firsts[t])));
+            }
+            c.rows += own;
+        }
+        c.n_seq += n_mem;
+        plan.rows += cost;
+        i = j;
+    }
+    return plan;
+}
+
+bool LlmModel::score_batch_supported() const
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    return !quant_ && !(H % 32 || QD % 32 || I % 32 || kv % 4 || !(d == 16 || d == 32 || d == 64 || d == 128));
+}
+
+void LlmModel::score_batch(const uint32_t* ids, const int32_t* offsets, int B, const int32_t* firsts, int top_k, float* logprob_out,
+                           uint32_t* topk_ids_out, float* topk_logprob_out)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim;
+    if (quant_) throw InvalidConfig("score_batch: quantized checkpoints are not supported");
+    if (!score_batch_supported())
+        throw InvalidConfig("score_batch: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
+    if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > c.vocab)
+        throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                            "] and not above the vocabulary size " + std::to_string(c.vocab));
+    check_score_sequences(offsets, firsts, B, embed_max_tokens());
+    if (B == 0) return;
+    for (int b = 0; b < B; ++b)
+        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
+            if (ids[i] >= (uint32_t)c.vocab)
+                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
+                                    std::to_string(c.vocab) + " (sequence " + std::to_string(b) + ")");
+    const ScorePlan plan = score_plan_host(ids, offsets, firsts, B, d, kScoreMinShared);
+
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hipStream_t s = stream_;
+    ensure_prompt_workspace();
+    ensure_packed_scratch();
+    ensure_score();  // the slab scratch of the fused head
+    if (top_k > 1) ensure_score_topk();
+    constexpr size_t kResWords = (size_t)kEmbedChunkRows * (1 + 2 * KJARNI_SCORE_TOPK_MAX);
+    if (!sb_res_) {
+        sb_res_ = reinterpret_cast<uint32_t*>(dalloc(kResWords));
+        hip_check(hipHostMalloc((void**)&sb_res_host_, kResWords * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+    }
+    const bool fused = score_fused_ && llm_score_head_takes(pn_, H, lm_head_, bf16_ ? 1 : 0, H);
+    if (!fused) ensure_lookup();  // vlogits_: the verify step's 8 logits rows
+    for (const ScoreChunk& ch : plan.chunks) {
+        const int m = ch.rows, g = (int)ch.gather_src.size(), nv = (int)ch.vec.size(), nm = (int)ch.mfma.size(), np = (int)ch.prefix.size();
+        const size_t o_pos = (size_t)m, o_src = o_pos + (size_t)m, o_tgt = o_src + (size_t)g, o_vec = o_tgt + (size_t)g;
+        const size_t o_mfma = o_vec + 3 * (size_t)nv, o_pre = o_mfma + 3 * (size_t)nm, words = o_pre + 5 * (size_t)np;
+        if (words > kPackedMetaWords || g > kEmbedChunkRows) throw std::runtime_error("score_batch: chunk metadata exceeds its buffer");
+        int32_t* hm = emeta_host_;
+        for (int r = 0; r < m; ++r) hm[r] = (int32_t)ids[ch.row_tok[(size_t)r]];
+        std::memcpy(hm + o_pos, ch.row_pos.data(), (size_t)m * 4);
+        std::memcpy(hm + o_src, ch.gather_src.data(), (size_t)g * 4);
+        std::memcpy(hm + o_tgt, ch.gather_tgt.data(), (size_t)g * 4);
+        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
+        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
+        if (np) std::memcpy(hm + o_pre, ch.prefix.data(), (size_t)np * sizeof(PrefixBlock));
+        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
+        const uint32_t* ids_dev = reinterpret_cast<const uint32_t*>(emeta_);
+        const uint32_t* tgt = reinterpret_cast<const uint32_t*>(emeta_ + o_tgt);
+        packed_layers(m, ids_dev, emeta_ + o_pos, reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec), nv,
+                      reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma), nm, reinterpret_cast<const PrefixBlock*>(emeta_ + o_pre), np);
+        // (the norm buffer is free after the last layer: the gathered rows land there, compact, H floats apart)
+        hip_check(launch_score_gather_norm(ph_, H, emeta_ + o_src, g, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, pn_, H, s),
+                  "score gather + norm");
+        // the chunk's results: logprob [g] | top-k ids [g, top_k] | top-k logprob [g, top_k]
+        float* lp = reinterpret_cast<float*>(sb_res_);
+        uint32_t* tid = sb_res_ + g;
+        float* tlp = reinterpret_cast<float*>(sb_res_ + g + (size_t)g * top_k);
+        if (fused) {
+            if (top_k > 1) {
+                if (score_head_topk_scratch_bytes(g, c.vocab, 0, top_k) > score_tk_scratch_bytes_)
+                    throw std::runtime_error("score_batch: slab scratch too small");
+                hip_check(launch_score_head_topk(pn_, H, g, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, top_k, score_tk_scratch_, lp, tid, tlp,
+                                                 nullptr, s), "score head top-k");
+            } else {
+                if (score_head_scratch_bytes(g, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score_batch: slab scratch too small");
+                hip_check(launch_score_head(pn_, H, g, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, lp, tid, tlp, nullptr, s),
+                          "score head");
+            }
+            ++score_fused_calls_;
+        } else {
+            for (int r = 0; r < g; r += 8) {
+                const int rows = std::min(8, g - r);
+                LlmGemvArgs lm;
+                lm.X = pn_ + (size_t)r * H; lm.ldx = H; lm.rows = rows; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
+                lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
+                hip_check(launch_llm_gemv(lm, s), "lm head");
+                if (top_k > 1)
+                    hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, top_k, lp + r, tid + (size_t)r * top_k,
+                                                     tlp + (size_t)r * top_k, nullptr, s), "score rows top-k");
+                else
+                    hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, lp + r, tid + r, tlp + r, nullptr, s), "score rows");
+                ++score_rows_calls_;
+            }
+        }
+        const size_t res_words = (size_t)g * (1 + 2 * (size_t)top_k);
+        hip_check(hipMemcpyAsync(sb_res_host_, sb_res_, res_words * 4, hipMemcpyDeviceToHost, s), "D2H scores");
+        hip_check(hipStreamSynchronize(s), "sync");  // the staging copies and the activations are reused by the next chunk
+        const size_t slot = (size_t)ch.gather_slot[0];  // (a chunk's slots are consecutive: sequence order, then position order)
+        if (logprob_out) std::memcpy(logprob_out + slot, sb_res_host_, (size_t)g * 4);
+        if (topk_ids_out) std::memcpy(topk_ids_out + slot * top_k, sb_res_host_ + g, (size_t)g * top_k * 4);
+        if (topk_logprob_out) std::memcpy(topk_logprob_out + slot * top_k, sb_res_host_ + g + (size_t)g * top_k, (size_t)g * top_k * 4);
+    }
+    score_batch_rows_ += (uint64_t)plan.rows;
+    score_batch_saved_ += (uint64_t)plan.saved;
 }
 
 }  // namespace kjarni

@@ -55,9 +55,14 @@ struct LlmLaneState;  // llm_kernels.h
 struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
+struct EmbedBlock;   // decoder_embed_kernels.h
+struct PrefixBlock;  // score_batch_kernels.h
 
 #ifndef KJARNI_SCORE_TOPK_MAX
 #define KJARNI_SCORE_TOPK_MAX 8  // (include/kjarni_hip.h): the most alternatives score_topk() returns per position
+#endif
+#ifndef KJARNI_HIP_SCORE_MIN_SHARED
+#define KJARNI_HIP_SCORE_MIN_SHARED 2  // (include/kjarni_hip.h): LlmModel::kScoreMinShared, where the measured reason stands
 #endif
 
 // Prompt-lookup decoding: how the draft of a verify step is found in the sequence's own history.
@@ -159,6 +164,36 @@ public:
     // B == 0 writes nothing.
     void embed_batch(const uint32_t* ids, const int32_t* offsets, int B, bool normalize, float* out);
     int embed_max_tokens() const { return cache_cap_ < 2048 ? cache_cap_ : 2048; }
+    // ---- scoring many sequences in one packed pass -----------------------------------------------------------------------------
+    // score() / score_topk() for B sequences at once.  Sequence b is ids[offsets[b], offsets[b + 1]) and its scored positions are
+    // [firsts[b], len_b), 1 <= firsts[b] < len_b.  The outputs are flat, in sequence order then position order: logprob_out
+    // [sum(len_b - firsts[b])], topk_ids_out / topk_logprob_out [sum, top_k] (top_k 1 .. KJARNI_SCORE_TOPK_MAX, <= vocab; slot 0 is
+    // score()'s top / top_logprob); any output may be null.  score_plan_host (score_batch_kernels.h) packs the sequences into
+    // chunks of at most 2 048 rows and computes a token prefix that neighbouring sequences share once (kScoreMinShared tokens or
+    // more, never a scored token); every chunk runs embed_batch's layer stack once over its rows, the remainders of a group
+    // attending to their prefix through launch_packed_prefix_attention, then only the rows whose successor is scored are
+    // gathered through the final norm (launch_score_gather_norm) and reach the vocabulary head, on score()'s routes.  One
+    // metadata upload and one result copy per chunk.  K and V live in the embed scratch: cache_len(), resident(), lanes, lookup
+    // state, logits, last_hidden(), the prefix-reuse counters and score()'s buffers are left as they were.  Throws InvalidConfig
+    // naming the argument and the sequence, before any GPU work, for non-monotone offsets, a sequence shorter than 2 or longer
+    // than embed_max_tokens(), firsts[b] outside [1, len_b), an id >= vocab and top_k out of range; quantized checkpoints and
+    // geometries forward() keeps off the matrix-core route are refused (GPT-2 is accepted).  B == 0 writes nothing.
+    void score_batch(const uint32_t* ids, const int32_t* offsets, int B, const int32_t* firsts, int top_k, float* logprob_out,
+                     uint32_t* topk_ids_out, float* topk_logprob_out);
+    // Whether score_batch() takes this checkpoint (else it throws InvalidConfig, which says why).
+    bool score_batch_supported() const;
+    // The shortest shared prefix score_batch() computes once (the plan's min_shared).  Measured on the Llama-3.2-1B shape, 64 contexts
+    // x 4 continuations of 16 tokens, a build with the constant at 1 (profiles/llm_score_batch_min_shared_1.jsonl): sharing a prefix of 1 / 4 / 16 / 64 / 256 tokens never
+    // loses against the same shapes unshared (not shared / shared = 1.02 / 1.11 / 1.18 / 2.18 / 3.12), so length as such asks for
+    // no floor.  But the plan's prefix only shrinks as neighbours join, and at 1 a neighbour that shares nothing but its first
+    // token -- every sequence behind a BOS token -- joins a group of real sharers at q = 1 and takes its prefix down to 1: the
+    // 64-token case behind a common first token then plans 20 235 rows in groups of prefix 1 instead of 8 192 in groups of prefix
+    // 64, and 20 480 rows of those shapes measured 174.2 ms against 79.9 ms for the 8 192.  That one-token prefix loses against
+    // not sharing it, hence 2; what 2 gives up is one row per member of a group that shares its first token only.
+    static constexpr int kScoreMinShared = KJARNI_HIP_SCORE_MIN_SHARED;
+    // Rows score_batch() computed / prefix rows it did not compute a second time (sum of (members - 1) * prefix), since load.
+    uint64_t score_batch_rows() const { return score_batch_rows_; }
+    uint64_t score_batch_saved_rows() const { return score_batch_saved_; }
     // Cache rows [first, first + rows) of one layer, K after RoPE (Qwen3: after the head norm and RoPE) and V, f32
     // [rows, kv_heads * head_dim] each (a test hook).
     void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
@@ -295,6 +330,12 @@ private:
     // score_base: the position of ids[0] in the scored sequence (score() with a kept prefix forwards only the rest)
     void prefill_rows(const uint32_t* ids_host, int n, bool score = false, int score_base = 0);
     void ensure_prompt_workspace();  // the 2 048-row activation buffers of the prompt routes
+    void ensure_packed_scratch();    // ek_, ev_, emeta_ and its pinned copy
+    // The packed layer stack of embed_batch and score_batch over m rows of one chunk: embedding of ids_dev (GPT-2: + the learned
+    // position row_pos[r]), then per layer prefill_rows()'s steps with RoPE by row_pos, K and V in ek_ / ev_, attention by the
+    // three block tables.  Leaves the hidden states in ph_; the norm buffer pn_ is free afterwards.
+    void packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_pos, const EmbedBlock* vec, int n_vec, const EmbedBlock* mfma,
+                       int n_mfma, const PrefixBlock* prefix, int n_prefix);
     // One projection of m prompt rows: Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T); gelu (GPT-2's
     // c_fc): Y = gelu_tanh(A W^T + bias).  Routes: the 64 x 64 prompt kernel, or from 512 rows and 208 tiles the 128 x 128-tile
     // GEMM (bf16 weights on the bf16 matrix cores); qm: a quantized matrix, dequantized into the f32 scratch first.
@@ -351,6 +392,10 @@ private:
     // tables on the device and their pinned staging copy
     float *ek_ = nullptr, *ev_ = nullptr;
     int32_t *emeta_ = nullptr, *emeta_host_ = nullptr;
+    // score_batch (allocated on first use): a chunk's results [logprob | top-k ids | top-k logprob], sized by the chunk's rows (a
+    // chunk of many short sequences scores more rows than the context is long), and their pinned landing buffer
+    uint32_t *sb_res_ = nullptr, *sb_res_host_ = nullptr;
+    uint64_t score_batch_rows_ = 0, score_batch_saved_ = 0;
     float* host_logits_ = nullptr;  // pinned
     std::vector<uint32_t> row_ids_, row_cids_;  // sample_row's scratch: the distribution's ids, the candidates' ids
     std::vector<float> row_probs_, row_cvals_;  // ... and their probabilities / logits

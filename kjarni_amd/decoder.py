@@ -59,6 +59,48 @@ def embed_plan(lengths: Sequence[int], head_dim: int = 64):
     return first[:nc.value + 1].copy(), vec[:nv.value].copy(), mfma[:nm.value].copy()
 
 
+def _flatten(seqs):
+    """(ids u32, offsets i32 [n + 1]) of a list of token sequences."""
+    n = len(seqs)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.uint32).reshape(-1) for s in seqs]) if n else [], np.uint32)
+    if flat.size == 0:
+        flat = np.zeros(1, np.uint32)
+    return flat, np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(s) for s in seqs])]), np.int32)
+
+
+SCORE_MIN_SHARED = 2  # KJARNI_HIP_SCORE_MIN_SHARED: the shortest prefix HipDecoder.score_batch computes once
+
+
+def score_plan(seqs: Sequence[Sequence[int]], firsts: Sequence[int], head_dim: int = 64, min_shared: int = SCORE_MIN_SHARED) -> dict:
+    """The plan of HipDecoder.score_batch (no GPU).  Walking the sequences in order, a sequence gathers the neighbours behind it
+    while their common prefix -- capped by every member's `first`, so that it never holds a scored token -- stays at least
+    min_shared tokens, the group fits one chunk of EMBED_CHUNK_ROWS rows and every remainder stays below 256 rows; a group
+    computes its prefix once.  Returns a dict of int32 arrays: chunk_first_seq [chunks + 1], chunk_rows [chunks], groups [n, 4]
+    (chunk, first sequence, members, prefix length), vec / mfma [n, 4] (chunk, first row, first query row, length: plain
+    sequences and prefixes, embed_plan's rule), prefix [n, 6] (chunk, the remainder's first row, the block's first query row,
+    the remainder's length, the prefix's first row, the prefix length: 32 query rows each) and gather [n, 4] (chunk, the chunk
+    row of position pos - 1, the target id, the output slot: one per scored position)."""
+    flat, off = _flatten(seqs)
+    fs = np.ascontiguousarray(firsts, np.int32)
+    n = len(seqs)
+    if fs.size != n:
+        raise ValueError("one `first` per sequence")
+    i32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    total = int(max(off[-1], 0))
+    cap = total + n + 1
+    first, rows = np.zeros(n + 1, np.int32), np.zeros(max(n, 1), np.int32)
+    groups, vec, mfma = np.zeros((n + 1, 4), np.int32), np.zeros((cap, 4), np.int32), np.zeros((cap, 4), np.int32)
+    pre, gather = np.zeros((cap, 6), np.int32), np.zeros((cap, 4), np.int32)
+    cnt = [C.c_int32(0) for _ in range(6)]
+    check_error(lib().kjarni_hip_score_plan(flat.ctypes.data_as(C.POINTER(C.c_uint32)) if n else None, i32(off) if n else None,
+                                            i32(fs) if n else None, n, int(head_dim), int(min_shared), i32(first), i32(rows), C.byref(cnt[0]),
+                                            i32(groups), n + 1, C.byref(cnt[1]), i32(vec), cap, C.byref(cnt[2]), i32(mfma), cap,
+                                            C.byref(cnt[3]), i32(pre), cap, C.byref(cnt[4]), i32(gather), cap, C.byref(cnt[5])))
+    nc, ng, nv, nm, np_, nga = (c.value for c in cnt)
+    return {"chunk_first_seq": first[:nc + 1].copy(), "chunk_rows": rows[:nc].copy(), "groups": groups[:ng].copy(), "vec": vec[:nv].copy(),
+            "mfma": mfma[:nm].copy(), "prefix": pre[:np_].copy(), "gather": gather[:nga].copy()}
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
@@ -382,6 +424,39 @@ class HipDecoder:
         """(fused, rows): head launches of score() by route since load."""
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_score_calls(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    # ---- scoring many sequences in one packed pass ----
+    def score_batch(self, seqs: Sequence[Sequence[int]], firsts: Sequence[int], top_k: int = 1):
+        """score() / score_topk() for every sequence in one packed pass: the scored positions of sequence b are firsts[b] ..
+        len(seqs[b]) - 1.  Returns (logprob f32 [S], ids u32 [S, top_k], logprob f32 [S, top_k]) with S = sum(len - first), flat in
+        sequence order then position order (np.split at np.cumsum(len - first) gives them per sequence); slot 0 of a row is
+        score()'s arg-max.  Neighbouring sequences that start with the same tokens compute them once (score_plan); the KV cache and
+        everything generate() and score() depend on are left as they were."""
+        flat, off = _flatten(seqs)
+        return self.score_batch_flat(flat, off, firsts, top_k)
+
+    def score_batch_flat(self, ids, offsets, firsts, top_k: int = 1):
+        """score_batch() on ids, offsets [n + 1] and firsts [n] as the C ABI takes them."""
+        a, o = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(offsets, np.int32)
+        fs = np.ascontiguousarray(firsts, np.int32)
+        n = o.size - 1
+        if fs.size != n:
+            raise ValueError("one `first` per sequence")
+        cnt = int(np.maximum(np.diff(o.astype(np.int64)) - fs, 0).sum()) if n > 0 else 0
+        k = max(int(top_k), 0)
+        lp, tid, tlp = np.zeros(cnt, np.float32), np.zeros((cnt, k), np.uint32), np.zeros((cnt, k), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        i32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_score_batch(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), i32(o), n, i32(fs) if n > 0 else None,
+                                                         int(top_k), f(lp), tid.ctypes.data_as(C.POINTER(C.c_uint32)), f(tlp)))
+        return lp, tid, tlp
+
+    def score_batch_rows(self):
+        """(computed, saved): rows score_batch() ran through the layer stack, and prefix rows it did not compute a second time,
+        since load."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_score_batch_rows(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     # ---- embedding: last-token pooling over a packed batch ----

@@ -57,6 +57,17 @@ class Generator:
         check_error(lib().kjarni_generator_score(self._handle, context.encode("utf-8"), continuation.encode("utf-8"), C.byref(r)))
         return float(r.sum_logprob), int(r.n_tokens), bool(r.is_greedy)
 
+    def score_batch(self, pairs: Sequence[Sequence[str]]):
+        """score() for every (context, continuation) pair in one packed pass: a list of (sum_logprob, n_tokens, is_greedy).
+        Neighbouring pairs that repeat a context compute it once.  An invalid pair fails the whole call with "pair <index>" in
+        the message, before anything is computed."""
+        n = len(pairs)
+        ctx = [p[0].encode("utf-8") for p in pairs]
+        cont = [p[1].encode("utf-8") for p in pairs]
+        out = (_ffi.KjarniScoreResult * max(n, 1))()
+        check_error(lib().kjarni_generator_score_batch(self._handle, (C.c_char_p * max(n, 1))(*ctx), (C.c_char_p * max(n, 1))(*cont), n, out))
+        return [(float(out[i].sum_logprob), int(out[i].n_tokens), bool(out[i].is_greedy)) for i in range(n)]
+
     def score_tokens(self, context: str, continuation: str, top_k: int = 5):
         """score() token by token: (tokens u32 [n], logprobs f32 [n], top_tokens u32 [n, top_k], top_logprobs f32 [n, top_k])
         for the n tokens `continuation` adds; every row's alternatives most likely first (top_k 1 .. 8)."""

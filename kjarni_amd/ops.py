@@ -315,6 +315,38 @@ def last_token_pool(x, lengths, gamma, eps: float, normalize: bool = True, hidde
     return out
 
 
+def packed_prefix_attention(q, k, v, remainders, heads: int, kv_heads: int, head_dim: int, ctx=None, device: int = 0):
+    """The prefix attention kernel of HipDecoder.score_batch alone: q / k / v / ctx as packed_causal_attention takes them;
+    remainders: rows of (first row, rows, the prefix's first row, prefix rows).  Row t of a remainder attends to its prefix rows
+    and to the remainder's rows 0 .. t.  Returns ctx with the remainders' context rows written; everything else as it was."""
+    qa, ka, va = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+    ca = np.zeros((qa.shape[0], heads * head_dim), np.float32) if ctx is None else np.array(ctx, np.float32, order="C")
+    if any(x.ndim != 2 or x.shape[0] != qa.shape[0] for x in (qa, ka, va, ca)):
+        raise ValueError("q, k, v, ctx: [rows, ld] with the same rows")
+    rem = np.ascontiguousarray(remainders, np.int32).reshape(-1, 4)
+    check_error(lib().kjarni_hip_op_packed_prefix_attention(device, _f(qa), qa.shape[1], _f(ka), ka.shape[1], _f(va), va.shape[1], qa.shape[0],
+                                                            rem.ctypes.data_as(_i32p), rem.shape[0], int(heads), int(kv_heads), int(head_dim),
+                                                            _f(ca), ca.shape[1]))
+    return ca
+
+
+def score_gather_norm(x, src, gamma, beta=None, eps: float = 1e-5, hidden=None, out=None, device: int = 0):
+    """The gather + final norm of HipDecoder.score_batch alone: out[j, :hidden] = norm(x[src[j], :hidden]) -- RMSNorm(gamma, eps),
+    or LayerNorm(gamma, beta, eps) when beta is given.  out: given ([len(src), ldo], its other columns come back as they were), or
+    zeros [len(src), hidden]."""
+    xa = np.ascontiguousarray(x, np.float32)
+    g = np.ascontiguousarray(gamma, np.float32)
+    b = None if beta is None else np.ascontiguousarray(beta, np.float32)
+    hidden = g.size if hidden is None else int(hidden)
+    s = np.ascontiguousarray(src, np.int32)
+    oa = np.zeros((s.size, hidden), np.float32) if out is None else np.array(out, np.float32, order="C")
+    if xa.ndim != 2 or oa.ndim != 2 or oa.shape[0] != s.size:
+        raise ValueError("x: [rows, ldx]; out: [len(src), ldo]")
+    check_error(lib().kjarni_hip_op_score_gather_norm(device, _f(xa), xa.shape[1], xa.shape[0], s.ctypes.data_as(_i32p), s.size, hidden, _f(g),
+                                                      _f(b) if b is not None else None, float(eps), _f(oa), oa.shape[1]))
+    return oa
+
+
 def argmax(logits, vocab: Optional[int] = None, route: int = ARGMAX_DECODER, live=None, draft=None, device: int = 0):
     """The greedy pick kernels on logits [calls, rows, ld] (the last of equal maxima wins; columns >= vocab are padding).
     Returns picks int32 [calls, rows]: decoder route rows == 1; lanes route -1 for the lanes `live` [rows] freezes; lookup

@@ -42,6 +42,13 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            alternated twice: Llama-3.2-1B shape (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused and on the rows
            route; medians of runs that end in a synchronise; the ratio score_topk / score per case.  One line per (length,
            route); the lines also go to profiles/llm_score_topk_bench.jsonl.
+  llm_score_batch  (only on request) HipDecoder.score_batch() -- many sequences scored in one packed pass, shared contexts computed
+           once -- on the Llama-3.2-1B shape (bf16, random init), legs alternated twice in one process, medians of runs that end in a
+           synchronise: N x 128 tokens at first = 1 for N in 8 / 64 / 256 against a loop of score() over the same sequences; 64
+           contexts x 4 continuations of 16 tokens with contexts of 256 / 64 / 16 / 4 / 1 tokens, as given (sharing) against the
+           same batch with every sequence's token 0 made distinct (same shapes, nothing shared), and at 256 the score() loop;
+           the 64- and 16-token cases behind a first token common to all sequences against a first token per context.
+           The lines also go to profiles/llm_score_batch_bench.jsonl.
   llm_prefix  (only on request) prefix reuse off against on (HipDecoder.set_prefix_reuse) in one process, alternated twice:
            Llama-3.2-1B shape (bf16) and gpt2-small (bf16).  Time to the first token of turn 2 with a resident history of 512 /
            2 048 tokens and a 32-token message; five score() calls over one 512-token context with 8-token continuations; 8
@@ -1131,6 +1138,121 @@ def main():
         dec.set_score_fused(True)
         del dec
         with open(os.path.join(ROOT, "profiles", "llm_score_topk_bench.jsonl"), "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+    if "llm_score_batch" in which:
+        # Method (measuring guide, section 5; as llm_score): one process on one box; every leg of a case is warmed first, then the
+        # legs are alternated twice, two runs each; every run ends in a synchronise (score_batch() and score() return after one);
+        # medians over the 4 runs of a leg.  The score() loop over the same sequences is what there was before score_batch().
+        rng = np.random.default_rng(0)
+        d = os.path.join(tmp, "llama-1b-score-batch")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        dtype = "bf16 weights, f32 activations/accumulate"
+        method = "random init; legs alternated twice in one process, medians of 4 runs, every run ends in a synchronise"
+        lines = []
+
+        def flat_of(seqs):
+            return (np.concatenate(seqs).astype(np.uint32), np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int32))
+
+        def measure(legs):
+            for fn in legs.values():
+                fn()
+            runs = {k: [] for k in legs}
+            for rep in range(2):
+                for _ in range(2):
+                    for k, fn in legs.items():
+                        t0 = time.perf_counter()
+                        fn()
+                        runs[k].append((time.perf_counter() - t0) * 1e3)
+            return {k: float(np.median(v)) for k, v in runs.items()}, runs
+
+        def loop_of(seqs, firsts):
+            def loop():
+                for s, f in zip(seqs, firsts):
+                    dec.score(s, f)
+            return loop
+
+        for n in (8, 64, 256):      # (a) N x 128 tokens, every token scored
+            seqs = [rng.integers(1000, 100000, 128).astype(np.uint32) for _ in range(n)]
+            firsts = np.ones(n, np.int32)
+            flat, off = flat_of(seqs)
+            med, runs = measure({"score_batch": lambda: dec.score_batch_flat(flat, off, firsts), "score_loop": loop_of(seqs, firsts)})
+            line = {"metric": f"score loop / score_batch, Llama-3.2-1B shape, bf16 weights, {n} x 128 tokens, first = 1",
+                    "value": round(med["score_loop"] / med["score_batch"], 2), "unit": "ratio of medians", "n_gpus": 1, "dtype": dtype,
+                    "data": "synthetic", "config": {"workload": method}, "sequences": n, "score_batch_ms": round(med["score_batch"], 3),
+                    "score_loop_ms": round(med["score_loop"], 3), "tokens_per_s_score_batch": round(n * 128 / med["score_batch"] * 1e3, 1),
+                    "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+            emit(line)
+            lines.append(line)
+
+        def choice_case(n_ctx, ctx_len, n_cont, cont_len):
+            """(shared, distinct): n_ctx contexts x n_cont continuations; distinct = the same batch with every sequence's token 0 made
+            its own, so that neighbours share nothing at the same shapes."""
+            shared, distinct = [], []
+            for c in range(n_ctx):
+                ctx = rng.integers(1000, 100000, ctx_len).astype(np.uint32)
+                for k in range(n_cont):
+                    s = np.concatenate([ctx, rng.integers(1000, 100000, cont_len).astype(np.uint32)])
+                    shared.append(s)
+                    t = s.copy()
+                    t[0] = 100 + len(distinct)
+                    distinct.append(t)
+            return shared, distinct, np.full(n_ctx * n_cont, ctx_len, np.int32)
+
+        # (b) multiple choice, 64 contexts of 256 tokens x 4 continuations of 16; and shorter contexts, for kScoreMinShared
+        for ctx_len in (256, 64, 16, 4, 1):
+            shared, distinct, firsts = choice_case(64, ctx_len, 4, 16)
+            (fs, os_), (fd, od) = flat_of(shared), flat_of(distinct)
+            legs = {"shared": lambda: dec.score_batch_flat(fs, os_, firsts), "not_shared": lambda: dec.score_batch_flat(fd, od, firsts)}
+            if ctx_len == 256:
+                legs["score_loop"] = loop_of(shared, firsts)
+            r0 = dec.score_batch_rows()
+            dec.score_batch_flat(fs, os_, firsts)
+            r1 = dec.score_batch_rows()
+            dec.score_batch_flat(fd, od, firsts)
+            r2 = dec.score_batch_rows()
+            med, runs = measure(legs)
+            line = {"metric": f"not sharing / sharing, Llama-3.2-1B shape, bf16 weights, 64 contexts of {ctx_len} x 4 continuations of 16 tokens",
+                    "value": round(med["not_shared"] / med["shared"], 3), "unit": "ratio of medians", "n_gpus": 1, "dtype": dtype,
+                    "data": "synthetic", "config": {"workload": method + "; not_shared: every sequence's token 0 made distinct"},
+                    "context_tokens": ctx_len, "shared_ms": round(med["shared"], 3), "not_shared_ms": round(med["not_shared"], 3),
+                    "rows_shared": r1[0] - r0[0], "rows_saved_shared": r1[1] - r0[1], "rows_not_shared": r2[0] - r1[0],
+                    "rows_saved_not_shared": r2[1] - r1[1], "min_shared": kjarni_amd.decoder.SCORE_MIN_SHARED,
+                    "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+            if "score_loop" in med:
+                line["score_loop_ms"] = round(med["score_loop"], 3)
+                line["score_loop_over_shared"] = round(med["score_loop"] / med["shared"], 2)
+            emit(line)
+            lines.append(line)
+        # (c) the same multiple choice behind a BOS token every sequence starts with (what a tokenizer that prepends BOS gives):
+        # as planned, against the same batch with the first token made distinct per context, so that no two contexts share it
+        for ctx_len in (64, 16):
+            shared, _, firsts = choice_case(64, ctx_len, 4, 16)
+            bos = [s.copy() for s in shared]
+            for s in bos:
+                s[0] = 1
+            (fb, ob), (fs, os_) = flat_of(bos), flat_of(shared)
+            r0 = dec.score_batch_rows()
+            dec.score_batch_flat(fb, ob, firsts)
+            r1 = dec.score_batch_rows()
+            dec.score_batch_flat(fs, os_, firsts)
+            r2 = dec.score_batch_rows()
+            med, runs = measure({"common_first_token": lambda: dec.score_batch_flat(fb, ob, firsts),
+                                 "first_token_per_context": lambda: dec.score_batch_flat(fs, os_, firsts)})
+            line = {"metric": f"common first token / first token per context, Llama-3.2-1B shape, bf16 weights, 64 contexts of {ctx_len} x 4 "
+                              "continuations of 16 tokens", "value": round(med["common_first_token"] / med["first_token_per_context"], 3),
+                    "unit": "ratio of medians", "n_gpus": 1, "dtype": dtype, "data": "synthetic", "config": {"workload": method},
+                    "context_tokens": ctx_len, "common_first_token_ms": round(med["common_first_token"], 3),
+                    "first_token_per_context_ms": round(med["first_token_per_context"], 3), "rows_common_first_token": r1[0] - r0[0],
+                    "rows_saved_common_first_token": r1[1] - r0[1], "rows_first_token_per_context": r2[0] - r1[0],
+                    "rows_saved_first_token_per_context": r2[1] - r1[1], "min_shared": kjarni_amd.decoder.SCORE_MIN_SHARED,
+                    "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+            emit(line)
+            lines.append(line)
+        del dec
+        with open(os.path.join(ROOT, "profiles", "llm_score_batch_bench.jsonl"), "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
 
