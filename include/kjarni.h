@@ -167,7 +167,9 @@ typedef struct KjarniRerankerConfig {
     KjarniDevice device;
     const char* cache_dir;
     const char* model_name; /* NULL = "minilm-l6-v2-cross-encoder" */
-    const char* model_path;
+    const char* model_path; /* a llama / qwen2 / qwen3 / mistral directory loads a decoder reranker (a yes / no prompt per
+                             * document, score = sigmoid(l_yes - l_no) at its last token, prompts cut to
+                             * min(max_position_embeddings, 2048) tokens), as do the names qwen3-reranker-0.6b / -4b / -8b */
     int32_t quiet;
 } KjarniRerankerConfig;
 
@@ -185,6 +187,10 @@ KjarniErrorCode kjarni_reranker_rerank(KjarniReranker* reranker, const char* que
 KjarniErrorCode kjarni_reranker_rerank_top_k(KjarniReranker* reranker, const char* query,
                                              const char* const* documents, size_t num_docs,
                                              size_t top_k, KjarniRerankResults* out); /* :272-322 */
+/* The instruction line of a decoder reranker's prompt (not in the reference); NULL restores the default, "Given a web search
+ * query, retrieve relevant passages that answer the query".  INVALID_UTF8 as elsewhere; INVALID_CONFIG, with a message, on a
+ * cross-encoder reranker, which has no instruction. */
+KjarniErrorCode kjarni_reranker_set_instruction(KjarniReranker* reranker, const char* instruction);
 
 /* ---- Searcher: kjarni-ffi/src/searcher.rs:12-491 ------------------------------
  * The index is the reference's segmented on-disk layout (crates/kjarni-rag/src/segment.rs,

@@ -919,6 +919,59 @@ KjarniErrorCode kjarni_hip_op_packed_prefix_attention(int32_t device, const floa
  * on the gathered rows.  src[j] outside [0, x_rows): INVALID_CONFIG. */
 KjarniErrorCode kjarni_hip_op_score_gather_norm(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* src, int32_t n,
                                                 int32_t hidden, const float* gamma, const float* beta, float eps, float* out, int64_t ldo);
+/* ---- answer logits: a few chosen logits at the end of many sequences ---------------------------------------------------------------
+ * kjarni_hip_decoder_answer_logits: logits_out[b, t] (row-major [n_sequences, n_targets]) is the logit of token targets[t] at the
+ * position after the last token of sequence b = ids[offsets[b], offsets[b + 1]): the dot product of the final-normed last hidden
+ * row with row targets[t] of the (tied or untied, f32 or bf16) head.  The targets, 1 .. KJARNI_HIP_ANSWER_MAX_TARGETS of them, are
+ * shared by the batch: two for a yes / no reranker (kjarni_reranker_* on a decoder checkpoint), up to eight for multiple choice
+ * by answer letter.  The sequences are packed as kjarni_hip_decoder_score_batch packs them (kjarni_hip_answer_plan); a token prefix
+ * that neighbouring sequences share -- never with a sequence's last token in it -- is computed once, and the vocabulary head does
+ * not run: one kernel reads the last rows and the targeted head rows.  The KV cache, the resident tokens, the lanes, the logits,
+ * the last hidden rows, the prefix-reuse counters and the buffers and counters of kjarni_hip_decoder_score / _score_batch are left
+ * as they were.  INVALID_CONFIG, before any GPU work, naming the argument and the sequence: offsets that decrease, a sequence
+ * shorter than 2 or longer than min(context, KJARNI_HIP_EMBED_CHUNK_ROWS), an id or a target >= vocab, n_targets out of range;
+ * also for quantized checkpoints and for hidden / heads * head_dim / intermediate sizes that are no multiple of 32 (GPT-2 is
+ * accepted).  n_sequences == 0 is OK and writes nothing. */
+#define KJARNI_HIP_ANSWER_MAX_TARGETS 8
+KjarniErrorCode kjarni_hip_decoder_answer_logits(KjarniHipDecoder* decoder, const uint32_t* ids, const int32_t* offsets, int32_t n_sequences,
+                                                 const uint32_t* targets, int32_t n_targets, float* logits_out);
+/* Rows kjarni_hip_decoder_answer_logits computed, and prefix rows it did not compute a second time, since load (zeros on NULL;
+ * either output may be NULL).  kjarni_hip_decoder_score_batch_rows counts its own calls only. */
+void kjarni_hip_decoder_answer_rows(const KjarniHipDecoder* decoder, uint64_t* computed, uint64_t* saved);
+/* The plan alone (host only): kjarni_hip_score_plan's rule and tables with firsts[b] = len_b - 1, so that no prefix holds a
+ * sequence's last token -- two identical sequences share all but their last token, and a sequence that is a prefix of its
+ * neighbour shares all but its own last token.  gather [capacity, 3]: for every sequence, in order, (chunk, the chunk row of its
+ * last token, the sequence's index = its row in logits_out).  Every table may be NULL; the counts are always written.
+ * INVALID_CONFIG naming the argument and the sequence for offsets that decrease and a length outside 2 ..
+ * KJARNI_HIP_EMBED_CHUNK_ROWS. */
+KjarniErrorCode kjarni_hip_answer_plan(const uint32_t* ids, const int32_t* offsets, int32_t n, int32_t head_dim, int32_t min_shared,
+                                       int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks, int32_t* groups,
+                                       int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks, int32_t vec_capacity, int32_t* n_vec,
+                                       int32_t* mfma_blocks, int32_t mfma_capacity, int32_t* n_mfma, int32_t* prefix_blocks,
+                                       int32_t prefix_capacity, int32_t* n_prefix, int32_t* gather, int32_t gather_capacity, int32_t* n_gather);
+/* The answer-logits kernel alone, host pointers: out[j, t] = dot(norm(x[src[j], 0 .. hidden)), head[targets[t], :]) for j < n,
+ * t < n_targets, out [n, n_targets].  x [x_rows, ldx] f32; head [head_rows, hidden] f32, or bf16 when head_is_bf16.  beta NULL:
+ * (x / sqrt(mean(x^2) + eps)) * gamma; beta given: LayerNorm.  hidden 1 .. 16384.  The kernel reads rows src[j] of x, gamma, beta
+ * and the targeted head rows, nothing else.  src[j] outside [0, x_rows), targets[t] >= head_rows, n_targets outside 1 ..
+ * KJARNI_HIP_ANSWER_MAX_TARGETS: INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_answer_logits(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* src, int32_t n,
+                                            int32_t hidden, const float* gamma, const float* beta, float eps, const void* head,
+                                            int32_t head_rows, int32_t head_is_bf16, const uint32_t* targets, int32_t n_targets, float* out);
+/* The prompt rule of the decoder rerankers alone (host only), on the tokenizer.json at tokenizer_json_path:
+ *   P    = "<|im_start|>system\nJudge whether the Document meets the requirements based on the Query and the Instruct provided. Note
+ *          that the answer can only be \"yes\" or \"no\".<|im_end|>\n<|im_start|>user\n"
+ *   body = "<Instruct>: {instruction}\n<Query>: {query}\n<Document>: {document}"
+ *   S    = "<|im_end|>\n<|im_start|>assistant\n<think>\n\n</think>\n\n"
+ * each encoded on its own (added tokens recognised, no BOS / EOS added); ids = P + body[0 .. max_tokens - |P| - |S|) + S, the body
+ * cut from the right so that only the document loses tokens.  instruction NULL: "Given a web search query, retrieve relevant
+ * passages that answer the query".  Writes min(n, capacity) ids to ids_out (may be NULL with capacity 0) and n to n_out.
+ * INVALID_CONFIG when the cut would reach into the query; LOAD_FAILED when the file does not load, or when "yes" or "no" is not
+ * exactly one token of it (the message names the word). */
+KjarniErrorCode kjarni_hip_rerank_prompt_ids(const char* tokenizer_json_path, const char* instruction, const char* query, const char* document,
+                                             int32_t max_tokens, uint32_t* ids_out, size_t capacity, size_t* n_out);
+/* A test hook: kjarni_hip_decoder_answer_rows of a decoder reranker's model (zeros on NULL and on a cross-encoder reranker), so
+ * that a test of the string-level calls can see that the query was computed once. */
+void kjarni_hip_reranker_answer_rows(const KjarniReranker* reranker, uint64_t* computed, uint64_t* saved);
 /* The switch and the counters on the Chat and Generator handles' models (send, generate, score and generate_batch take it). */
 KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);

@@ -15,7 +15,7 @@ from .reranker import Reranker, RerankResult  # noqa: F401,E402
 from .searcher import Searcher, search_keywords  # noqa: F401,E402
 from .indexer import CancelToken, Indexer, index_delete, index_info  # noqa: F401,E402
 from .transcriber import HipWhisper, Transcriber  # noqa: F401,E402
-from .decoder import HipDecoder, embed_plan, generation_replay, prefix_keep, score_plan  # noqa: F401,E402
+from .decoder import HipDecoder, answer_plan, embed_plan, generation_replay, prefix_keep, score_plan  # noqa: F401,E402
 from .chat import BpeTokenizer, Chat, ChatConversation, GenerationConfig  # noqa: F401,E402
 from .generator import Generator  # noqa: F401,E402
 from .tokenizer import Tokenizer  # noqa: F401,E402

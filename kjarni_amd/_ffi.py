@@ -541,6 +541,17 @@ SIGNATURES = {
     "kjarni_hip_op_score_gather_norm": (c_int32, [c_int32, _f32p, c_int64, c_int32, POINTER(c_int32), c_int32, c_int32, _f32p, _f32p, c_float,
                                                   _f32p, c_int64]),
     "kjarni_generator_score_batch": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_size_t, POINTER(KjarniScoreResult)]),
+    "kjarni_hip_decoder_answer_logits": (c_int32, [c_void_p, _u32p, POINTER(c_int32), c_int32, _u32p, c_int32, _f32p]),
+    "kjarni_hip_decoder_answer_rows": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_answer_plan": (c_int32, [_u32p, POINTER(c_int32), c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
+                                         POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                         POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                         POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_int32)]),
+    "kjarni_hip_op_answer_logits": (c_int32, [c_int32, _f32p, c_int64, c_int32, POINTER(c_int32), c_int32, c_int32, _f32p, _f32p, c_float,
+                                              c_void_p, c_int32, c_int32, _u32p, c_int32, _f32p]),
+    "kjarni_reranker_set_instruction": (c_int32, [c_void_p, c_char_p]),
+    "kjarni_hip_rerank_prompt_ids": (c_int32, [c_char_p, c_char_p, c_char_p, c_char_p, c_int32, _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_reranker_answer_rows": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_bpe_tokenizer_encode_embedding": (c_int32, [c_void_p, c_char_p, c_size_t, _u32p, c_size_t, POINTER(c_size_t)]),
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -219,12 +219,12 @@ struct KjarniEmbedder {
 
 namespace {
 
-// The directory of a decoder embedder, or "" when the request names an encoder (or nothing this function knows): model_path
-// with a decoder model_type in its config.json, or a registry name of a decoder embedder.
-std::string decoder_embedder_dir(const KjarniEmbedderConfig& c)
+// The directory of a decoder embedder / reranker, or "" when the request names an encoder (or nothing this function knows):
+// model_path with a decoder model_type in its config.json, or a registry name of a decoder checkpoint of that task.
+std::string decoder_dir(const char* model_path, const char* model_name, const char* cache_dir, ModelTask task)
 {
-    if (c.model_path) {
-        const std::string dir = c.model_path;
+    if (model_path) {
+        const std::string dir = model_path;
         if (!is_dir(dir) || !model_files_present(dir)) return "";  // (load_pipeline reports it)
         std::string type;
         try {
@@ -234,16 +234,18 @@ std::string decoder_embedder_dir(const KjarniEmbedderConfig& c)
         }
         return (type == "llama" || type == "qwen2" || type == "qwen3" || type == "mistral") ? dir : "";
     }
-    if (!c.model_name) return "";
+    if (!model_name) return "";
     std::string err;
-    const RegistryEntry* e = resolve_model(c.model_name, err);
-    if (!e || e->arch != ModelArch::Decoder || e->task != ModelTask::Embedding) return "";
-    const std::string dir = model_dir_for(*e, c.cache_dir ? std::string(c.cache_dir) : default_cache_dir());
+    const RegistryEntry* e = resolve_model(model_name, err);
+    if (!e || e->arch != ModelArch::Decoder || e->task != task) return "";
+    const std::string dir = model_dir_for(*e, cache_dir ? std::string(cache_dir) : default_cache_dir());
     if (!model_files_present(dir))
         throw ModelNotFound(std::string("Model '") + e->cli_name + "' is not downloaded (expected config.json, tokenizer.json and "
                             "model.safetensors in " + dir + "); this build never downloads models");
     return dir;
 }
+
+std::string decoder_embedder_dir(const KjarniEmbedderConfig& c) { return decoder_dir(c.model_path, c.model_name, c.cache_dir, ModelTask::Embedding); }
 
 std::unique_ptr<DecoderEmbedder> load_decoder_embedder(const std::string& dir)
 {
@@ -351,8 +353,99 @@ KJARNI_EXPORT size_t kjarni_embedder_dim(const KjarniEmbedder* e) { return e ? e
 
 // ---- Reranker ----------------------------------------------------------------
 
+namespace {
+
+// The prompt of the decoder rerankers: the published Qwen3-Reranker format, fixed here as the project's definition.
+const char* const kRerankHead =
+    "<|im_start|>system\nJudge whether the Document meets the requirements based on the Query and the Instruct provided. Note that the "
+    "answer can only be \"yes\" or \"no\".<|im_end|>\n<|im_start|>user\n";
+const char* const kRerankTail = "<|im_end|>\n<|im_start|>assistant\n<think>\n\n</think>\n\n";
+const char* const kRerankInstruction = "Given a web search query, retrieve relevant passages that answer the query";
+
+struct RerankPrompt {
+    std::vector<uint32_t> head, tail;  // P and S, encoded on their own
+    uint32_t yes = 0, no = 0;
+
+    // Chat's encode of a rendered template: added tokens recognised, no BOS / EOS, no truncation
+    void load(const BpeTokenizer& tok)
+    {
+        head = tok.encode(kRerankHead, 0);
+        tail = tok.encode(kRerankTail, 0);
+        auto one = [&](const char* word) {
+            const std::vector<uint32_t> ids = tok.encode(word, 0);
+            if (ids.size() != 1)
+                throw std::runtime_error(std::string("the tokenizer encodes \"") + word + "\" to " + std::to_string(ids.size()) +
+                                         " tokens: a decoder reranker needs \"" + word + "\" to be exactly one token");
+            return ids[0];
+        };
+        yes = one("yes");
+        no = one("no");
+    }
+
+    // ids = P + body[: limit - |P| - |S|] + S: the body is cut from the right, so only the document loses tokens
+    std::vector<uint32_t> ids(const BpeTokenizer& tok, const std::string& instruction, const std::string& query, const std::string& document,
+                              size_t limit) const
+    {
+        const std::string front = "<Instruct>: " + instruction + "\n<Query>: " + query;
+        std::vector<uint32_t> body = tok.encode(front + "\n<Document>: " + document, 0);
+        const size_t frame = head.size() + tail.size();
+        const size_t keep = limit > frame ? limit - frame : 0;
+        if (body.size() > keep) {
+            // The query's end is defined by count: the tokens of the instruction and the query encoded on their own.  The body is
+            // encoded as one text, and a pre-tokenizer may join the query's last punctuation with the "\n" behind it into one
+            // piece, so the joint encoding's boundary can sit one token off that count; a cut that lands exactly there keeps or
+            // drops that one piece.  Part of the definition, never more than one token.
+            const size_t need = tok.encode(front, 0).size();
+            if (keep < need)
+                throw InvalidConfig("the rerank prompt does not fit " + std::to_string(limit) + " tokens: the frame takes " + std::to_string(frame) +
+                                    " and the instruction and the query " + std::to_string(need) + ", so the cut would reach into the query");
+            body.resize(keep);
+        }
+        std::vector<uint32_t> out(head);
+        out.insert(out.end(), body.begin(), body.end());
+        out.insert(out.end(), tail.begin(), tail.end());
+        return out;
+    }
+};
+
+}  // namespace
+
+// A decoder checkpoint (llama / qwen2 / qwen3 / mistral) as a reranker: score = sigmoid(l_yes - l_no) at the last token of the
+// prompt, all documents of a call through one LlmModel::answer_logits_batch in the caller's order (the system block, the
+// instruction and the query are a prefix neighbouring documents share: computed once per chunk).
+struct DecoderReranker {
+    std::unique_ptr<LlmModel> model;
+    BpeTokenizer tokenizer;
+    RerankPrompt prompt;
+    std::string instruction = kRerankInstruction;
+    std::mutex mu;  // answer_logits_batch uses the model's one workspace and stream
+
+    std::vector<float> scores(const std::string& query, const std::vector<std::string>& docs)
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        std::vector<uint32_t> ids;
+        std::vector<int32_t> offsets{0};
+        for (const std::string& d : docs) {
+            const std::vector<uint32_t> one = prompt.ids(tokenizer, instruction, query, d, (size_t)model->embed_max_tokens());
+            ids.insert(ids.end(), one.begin(), one.end());
+            if (ids.size() > (size_t)std::numeric_limits<int32_t>::max()) throw std::runtime_error("more than 2^31 - 1 tokens in one call");
+            offsets.push_back((int32_t)ids.size());
+        }
+        const uint32_t targets[2] = {prompt.yes, prompt.no};
+        std::vector<float> logits(docs.size() * 2), out(docs.size());
+        model->answer_logits_batch(ids.data(), offsets.data(), (int)docs.size(), targets, 2, logits.data());
+        for (size_t i = 0; i < docs.size(); ++i) out[i] = 1.0f / (1.0f + std::exp(-(logits[2 * i] - logits[2 * i + 1])));
+        return out;
+    }
+};
+
 struct KjarniReranker {
     std::unique_ptr<Pipeline> p;
+    std::unique_ptr<DecoderReranker> dec;  // set instead of p for a decoder checkpoint
+    std::vector<float> scores(const std::string& query, const std::vector<std::string>& docs)
+    {
+        return dec ? dec->scores(query, docs) : rerank_scores(*p, query, docs);
+    }
 };
 
 KJARNI_EXPORT void kjarni_rerank_results_free(const KjarniRerankResults* r)
@@ -381,12 +474,61 @@ KJARNI_EXPORT KjarniErrorCode kjarni_reranker_new(const KjarniRerankerConfig* co
         if (s && !valid_utf8(s)) return KJARNI_ERROR_INVALID_UTF8;
     return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
         auto h = std::make_unique<KjarniReranker>();
-        h->p = load_pipeline(c.cache_dir, c.model_name, c.model_path, "minilm-l6-v2-cross-encoder", Want::Reranking);
+        const std::string dec_dir = decoder_dir(c.model_path, c.model_name, c.cache_dir, ModelTask::ReRanking);
+        if (!dec_dir.empty()) {
+            auto d = std::make_unique<DecoderReranker>();
+            d->tokenizer.load(dec_dir + "/tokenizer.json");
+            d->prompt.load(d->tokenizer);
+            const std::vector<int> devs = devices_from_env();
+            // the cache only bounds the sequence length here: max_context = the packed length limit
+            d->model = LlmModel::load(dec_dir, devs.empty() ? 0 : devs[0], 0, KJARNI_HIP_EMBED_CHUNK_ROWS);
+            h->dec = std::move(d);
+        } else {
+            h->p = load_pipeline(c.cache_dir, c.model_name, c.model_path, "minilm-l6-v2-cross-encoder", Want::Reranking);
+        }
         *out = h.release();
     });
 }
 
 KJARNI_EXPORT void kjarni_reranker_free(KjarniReranker* r) { delete r; }
+
+KJARNI_EXPORT KjarniErrorCode kjarni_reranker_set_instruction(KjarniReranker* r, const char* instruction)
+{
+    if (!r) return KJARNI_ERROR_NULL_POINTER;
+    if (instruction && !valid_utf8(instruction)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_INVALID_CONFIG, [&] {
+        if (!r->dec)
+            throw InvalidConfig("set_instruction: this reranker is a cross-encoder, which takes (query, document) pairs and has no instruction");
+        std::lock_guard<std::mutex> lock(r->dec->mu);
+        r->dec->instruction = instruction ? instruction : kRerankInstruction;
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_reranker_answer_rows(const KjarniReranker* r, uint64_t* computed, uint64_t* saved)
+{
+    const bool dec = r && r->dec;
+    if (computed) *computed = dec ? r->dec->model->answer_rows() : 0;
+    if (saved) *saved = dec ? r->dec->model->answer_saved_rows() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_rerank_prompt_ids(const char* tokenizer_json_path, const char* instruction, const char* query,
+                                                           const char* document, int32_t max_tokens, uint32_t* ids_out, size_t capacity,
+                                                           size_t* n_out)
+{
+    if (!tokenizer_json_path || !query || !document || !n_out || (capacity > 0 && !ids_out)) return KJARNI_ERROR_NULL_POINTER;
+    for (const char* s : {tokenizer_json_path, instruction, query, document})
+        if (s && !valid_utf8(s)) return KJARNI_ERROR_INVALID_UTF8;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
+        if (max_tokens < 1) throw InvalidConfig("max_tokens (" + std::to_string(max_tokens) + ") must be at least 1");
+        BpeTokenizer tok;
+        tok.load(tokenizer_json_path);
+        RerankPrompt prompt;
+        prompt.load(tok);
+        const std::vector<uint32_t> ids = prompt.ids(tok, instruction ? instruction : kRerankInstruction, query, document, (size_t)max_tokens);
+        for (size_t i = 0; i < ids.size() && i < capacity; ++i) ids_out[i] = ids[i];
+        *n_out = ids.size();
+    });
+}
 
 namespace kjarni {
 
@@ -424,7 +566,7 @@ KjarniErrorCode rerank_impl(KjarniReranker* r, const char* query, const char* co
         docs.emplace_back(documents[i]);
     }
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
-        const std::vector<float> scores = rerank_scores(*r->p, query, docs);
+        const std::vector<float> scores = r->scores(query, docs);
         // CrossEncoder::rerank: stable sort by score descending, partial_cmp (NaN == Equal)
         // (cross_encoder/model.rs:251-252); Reranker::rerank_with_config truncates to top_k
         // (crates/kjarni/src/reranker/model.rs:270-273).
@@ -453,7 +595,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_reranker_score(KjarniReranker* r, const cha
     if (!valid_utf8(query) || !valid_utf8(document)) return KJARNI_ERROR_INVALID_UTF8;
     *out = 0.0f;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
-        *out = rerank_scores(*r->p, query, {std::string(document)})[0];
+        *out = r->scores(query, {std::string(document)})[0];
     });
 }
 

@@ -7,6 +7,7 @@
 
 #include "decoder_embed_kernels.h"
 #include "score_batch_kernels.h"
+#include "answer_logits_kernels.h"
 #include "llm_kernels.h"
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
@@ -472,6 +473,53 @@ KJARNI_EXPORT void kjarni_hip_decoder_score_batch_rows(const KjarniHipDecoder* d
     if (saved) *saved = d ? d->model->score_batch_saved_rows() : 0;
 }
 
+namespace {
+
+// The chunks, the groups and the three block tables of a plan into the caller's arrays (kjarni_hip_score_plan and
+// kjarni_hip_answer_plan share them; the gather table is each one's own).  Tables may be null; the counts are always written.
+void put_plan_tables(const ScorePlan& plan, int32_t n, int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks, int32_t* groups,
+                     int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks, int32_t vec_capacity, int32_t* n_vec, int32_t* mfma_blocks,
+                     int32_t mfma_capacity, int32_t* n_mfma, int32_t* prefix_blocks, int32_t prefix_capacity, int32_t* n_prefix)
+{
+    int32_t nv = 0, nm = 0, np = 0;
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const ScoreChunk& ch = plan.chunks[c];
+        if (chunk_first_seq) chunk_first_seq[c] = ch.first_seq;
+        if (chunk_rows) chunk_rows[c] = ch.rows;
+        auto put = [&](const std::vector<EmbedBlock>& src, int32_t* dst, int32_t cap, int32_t& cnt) {
+            for (const EmbedBlock& b : src) {
+                if (dst && cnt < cap) {
+                    int32_t* w = dst + 4 * (size_t)cnt;
+                    w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len;
+                }
+                ++cnt;
+            }
+        };
+        put(ch.vec, vec_blocks, vec_capacity, nv);
+        put(ch.mfma, mfma_blocks, mfma_capacity, nm);
+        for (const PrefixBlock& b : ch.prefix) {
+            if (prefix_blocks && np < prefix_capacity) {
+                int32_t* w = prefix_blocks + 6 * (size_t)np;
+                w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len; w[4] = b.prefix_first; w[5] = b.prefix_len;
+            }
+            ++np;
+        }
+    }
+    if (chunk_first_seq) chunk_first_seq[plan.chunks.size()] = n;
+    for (size_t g = 0; g < plan.groups.size(); ++g)
+        if (groups && (int32_t)g < group_capacity) {
+            int32_t* w = groups + 4 * g;
+            w[0] = plan.groups[g].chunk; w[1] = plan.groups[g].first_seq; w[2] = plan.groups[g].n_seq; w[3] = plan.groups[g].prefix;
+        }
+    *n_chunks = (int32_t)plan.chunks.size();
+    *n_groups = (int32_t)plan.groups.size();
+    *n_vec = nv;
+    *n_mfma = nm;
+    *n_prefix = np;
+}
+
+}  // namespace
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_score_plan(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int32_t n, int32_t head_dim,
                                                     int32_t min_shared, int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks,
                                                     int32_t* groups, int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks,
@@ -485,29 +533,11 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_score_plan(const uint32_t* ids, const i
         if (n < 0 || group_capacity < 0 || vec_capacity < 0 || mfma_capacity < 0 || prefix_capacity < 0 || gather_capacity < 0)
             throw InvalidConfig("n and the capacities must not be negative");
         const ScorePlan plan = score_plan_host(ids, offsets, firsts, n, head_dim, min_shared);
-        int32_t nv = 0, nm = 0, np = 0, ng = 0;
+        put_plan_tables(plan, n, chunk_first_seq, chunk_rows, n_chunks, groups, group_capacity, n_groups, vec_blocks, vec_capacity, n_vec,
+                        mfma_blocks, mfma_capacity, n_mfma, prefix_blocks, prefix_capacity, n_prefix);
+        int32_t ng = 0;
         for (size_t c = 0; c < plan.chunks.size(); ++c) {
             const ScoreChunk& ch = plan.chunks[c];
-            if (chunk_first_seq) chunk_first_seq[c] = ch.first_seq;
-            if (chunk_rows) chunk_rows[c] = ch.rows;
-            auto put = [&](const std::vector<EmbedBlock>& src, int32_t* dst, int32_t cap, int32_t& cnt) {
-                for (const EmbedBlock& b : src) {
-                    if (dst && cnt < cap) {
-                        int32_t* w = dst + 4 * (size_t)cnt;
-                        w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len;
-                    }
-                    ++cnt;
-                }
-            };
-            put(ch.vec, vec_blocks, vec_capacity, nv);
-            put(ch.mfma, mfma_blocks, mfma_capacity, nm);
-            for (const PrefixBlock& b : ch.prefix) {
-                if (prefix_blocks && np < prefix_capacity) {
-                    int32_t* w = prefix_blocks + 6 * (size_t)np;
-                    w[0] = (int32_t)c; w[1] = b.first; w[2] = b.q0; w[3] = b.len; w[4] = b.prefix_first; w[5] = b.prefix_len;
-                }
-                ++np;
-            }
             for (size_t j = 0; j < ch.gather_src.size(); ++j) {
                 if (gather && ng < gather_capacity) {
                     int32_t* w = gather + 4 * (size_t)ng;
@@ -516,17 +546,56 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_score_plan(const uint32_t* ids, const i
                 ++ng;
             }
         }
-        if (chunk_first_seq) chunk_first_seq[plan.chunks.size()] = n;
-        for (size_t g = 0; g < plan.groups.size(); ++g)
-            if (groups && (int32_t)g < group_capacity) {
-                int32_t* w = groups + 4 * g;
-                w[0] = plan.groups[g].chunk; w[1] = plan.groups[g].first_seq; w[2] = plan.groups[g].n_seq; w[3] = plan.groups[g].prefix;
+        *n_gather = ng;
+    });
+}
+
+// ---- answer logits ---------------------------------------------------------------------------------------------------------
+
+static_assert(kAnswerMaxTargets == KJARNI_HIP_ANSWER_MAX_TARGETS, "the header's limit is the kernel's");
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_answer_logits(KjarniHipDecoder* d, const uint32_t* ids, const int32_t* offsets,
+                                                               int32_t n_sequences, const uint32_t* targets, int32_t n_targets,
+                                                               float* logits_out)
+{
+    if (!d || !targets || (n_sequences > 0 && (!ids || !offsets || !logits_out))) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->answer_logits_batch(ids, offsets, n_sequences, targets, n_targets, logits_out);  // checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT void kjarni_hip_decoder_answer_rows(const KjarniHipDecoder* d, uint64_t* computed, uint64_t* saved)
+{
+    if (computed) *computed = d ? d->model->answer_rows() : 0;
+    if (saved) *saved = d ? d->model->answer_saved_rows() : 0;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_answer_plan(const uint32_t* ids, const int32_t* offsets, int32_t n, int32_t head_dim, int32_t min_shared,
+                                                     int32_t* chunk_first_seq, int32_t* chunk_rows, int32_t* n_chunks, int32_t* groups,
+                                                     int32_t group_capacity, int32_t* n_groups, int32_t* vec_blocks, int32_t vec_capacity,
+                                                     int32_t* n_vec, int32_t* mfma_blocks, int32_t mfma_capacity, int32_t* n_mfma,
+                                                     int32_t* prefix_blocks, int32_t prefix_capacity, int32_t* n_prefix, int32_t* gather,
+                                                     int32_t gather_capacity, int32_t* n_gather)
+{
+    if ((n > 0 && (!ids || !offsets)) || !n_chunks || !n_groups || !n_vec || !n_mfma || !n_prefix || !n_gather) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_UNKNOWN, [&] {
+        if (n < 0 || group_capacity < 0 || vec_capacity < 0 || mfma_capacity < 0 || prefix_capacity < 0 || gather_capacity < 0)
+            throw InvalidConfig("n and the capacities must not be negative");
+        const ScorePlan plan = answer_plan_host(ids, offsets, n, head_dim, min_shared);
+        put_plan_tables(plan, n, chunk_first_seq, chunk_rows, n_chunks, groups, group_capacity, n_groups, vec_blocks, vec_capacity, n_vec,
+                        mfma_blocks, mfma_capacity, n_mfma, prefix_blocks, prefix_capacity, n_prefix);
+        int32_t ng = 0;
+        for (size_t c = 0; c < plan.chunks.size(); ++c) {
+            const ScoreChunk& ch = plan.chunks[c];
+            for (size_t j = 0; j < ch.gather_src.size(); ++j) {  // (chunk, the chunk row of the sequence's last token, the sequence)
+                if (gather && ng < gather_capacity) {
+                    int32_t* w = gather + 3 * (size_t)ng;
+                    w[0] = (int32_t)c; w[1] = ch.gather_src[j]; w[2] = ch.gather_slot[j];
+                }
+                ++ng;
             }
-        *n_chunks = (int32_t)plan.chunks.size();
-        *n_groups = (int32_t)plan.groups.size();
-        *n_vec = nv;
-        *n_mfma = nm;
-        *n_prefix = np;
+        }
         *n_gather = ng;
     });
 }

@@ -17,6 +17,7 @@
 #include "llm.h"
 #include "decoder_embed_kernels.h"
 #include "score_batch_kernels.h"
+#include "answer_logits_kernels.h"
 #include "llm_kernels.h"
 #include "quant_kernels.h"
 #include "tuning.h"
@@ -917,6 +918,47 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_gather_norm(int32_t device, co
         hip_check(hipDeviceSynchronize(), "sync");
         hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
         od.check("score gather + norm");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_answer_logits(int32_t device, const float* x, int64_t ldx, int32_t x_rows, const int32_t* src, int32_t n,
+                                                          int32_t hidden, const float* gamma, const float* beta, float eps, const void* head,
+                                                          int32_t head_rows, int32_t head_is_bf16, const uint32_t* targets, int32_t n_targets,
+                                                          float* out)
+{
+    if (!x || !src || !gamma || !head || !targets || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (hidden < 1 || hidden > 16384 || ldx < hidden || ldx > (1 << 20)) throw InvalidConfig("hidden must be 1 .. 16384 and ldx cover it");
+        if (x_rows < 1 || x_rows > (1 << 22)) throw InvalidConfig("x_rows must be 1 .. 2^22");
+        if (n < 1 || n > (1 << 20)) throw InvalidConfig("n must be 1 .. 2^20");
+        if (head_rows < 1 || head_rows > (1 << 22)) throw InvalidConfig("head_rows must be 1 .. 2^22");
+        if (n_targets < 1 || n_targets > kAnswerMaxTargets)
+            throw InvalidConfig("n_targets (" + std::to_string(n_targets) + ") must be in [1, " + std::to_string(kAnswerMaxTargets) + "]");
+        for (int32_t j = 0; j < n; ++j)
+            if (src[j] < 0 || src[j] >= x_rows)
+                throw InvalidConfig("src[" + std::to_string(j) + "] = " + std::to_string(src[j]) + " is outside the " + std::to_string(x_rows) +
+                                    " rows given");
+        for (int32_t t = 0; t < n_targets; ++t)
+            if (targets[t] >= (uint32_t)head_rows)
+                throw InvalidConfig("targets[" + std::to_string(t) + "] = " + std::to_string(targets[t]) + " is outside the " +
+                                    std::to_string(head_rows) + " head rows given");
+        use_device(device);
+        const size_t xb = (size_t)x_rows * (size_t)ldx * 4, hb = (size_t)head_rows * (size_t)hidden * (head_is_bf16 ? 2 : 4);
+        const size_t ob = (size_t)n * (size_t)n_targets * 4;
+        DeviceBuf xd(xb), gd((size_t)hidden * 4), bd((size_t)hidden * 4), sd((size_t)n * 4), hd(hb), td((size_t)n_targets * 4);
+        GuardedBuf od(ob);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        hip_check(hipMemcpy(gd.p, gamma, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D gamma");
+        if (beta) hip_check(hipMemcpy(bd.p, beta, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D beta");
+        hip_check(hipMemcpy(sd.p, src, (size_t)n * 4, hipMemcpyHostToDevice), "H2D src");
+        hip_check(hipMemcpy(hd.p, head, hb, hipMemcpyHostToDevice), "H2D head");
+        hip_check(hipMemcpy(td.p, targets, (size_t)n_targets * 4, hipMemcpyHostToDevice), "H2D targets");
+        hip_check(launch_answer_logits((const float*)xd.p, ldx, (const int32_t*)sd.p, n, hidden, (const float*)gd.p,
+                                       beta ? (const float*)bd.p : nullptr, eps, hd.p, head_is_bf16 ? 1 : 0, (const uint32_t*)td.p, n_targets,
+                                       od.as<float>(), nullptr), "answer logits");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
+        od.check("answer logits");
     });
 }
 

@@ -14,6 +14,7 @@
 #include "decoder_embed_kernels.h"
 #include "llm_kernels.h"
 #include "score_batch_kernels.h"
+#include "answer_logits_kernels.h"
 #include "safetensors.h"
 #include "whisper_kernels.h"
 
@@ -2577,6 +2578,98 @@ void LlmModel::score_batch(const uint32_t* ids, const int32_t* offsets, int B, c
     }
     score_batch_rows_ += (uint64_t)plan.rows;
     score_batch_saved_ += (uint64_t)plan.saved;
+}
+
+// ---- answer logits: a few chosen logits at the end of many sequences ----------------------------------------------------------
+
+ScorePlan answer_plan_host(const uint32_t* ids, const int32_t* offsets, int B, int head_dim, int min_shared)
+{
+    // the one scored position of a sequence is its last token: score_plan_host's rule then keeps that token out of every prefix
+    std::vector<int32_t> firsts((size_t)std::max(B, 0));
+    for (int b = 0; b < B; ++b) firsts[(size_t)b] = (int32_t)std::max<int64_t>((int64_t)offsets[b + 1] - offsets[b] - 1, 1);
+    ScorePlan plan = score_plan_host(ids, offsets, firsts.data(), B, head_dim, min_shared);
+    for (ScoreChunk& c : plan.chunks) {
+        // rows and sequences both run in order, and a last token is a row of its sequence alone
+        c.gather_src.clear();
+        c.gather_tgt.clear();
+        c.gather_slot.clear();
+        int t = c.first_seq;
+        for (int r = 0; r < c.rows && t < c.first_seq + c.n_seq; ++r)
+            if (c.row_tok[(size_t)r] == offsets[t + 1] - 1) {
+                c.gather_src.push_back(r);
+                c.gather_slot.push_back(t++);
+            }
+        if ((int)c.gather_src.size() != c.n_seq) throw std::runtime_error("answer plan: a sequence's last token has no row");
+    }
+    return plan;
+}
+
+void LlmModel::answer_logits_batch(const uint32_t* ids, const int32_t* offsets, int B, const uint32_t* targets, int n_targets,
+                                   float* logits_out)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim;
+    if (quant_) throw InvalidConfig("answer_logits: quantized checkpoints are not supported");
+    if (!score_batch_supported())
+        throw InvalidConfig("answer_logits: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
+    if (n_targets < 1 || n_targets > kAnswerMaxTargets)
+        throw InvalidConfig("n_targets (" + std::to_string(n_targets) + ") must be in [1, " + std::to_string(kAnswerMaxTargets) + "]");
+    for (int t = 0; t < n_targets; ++t)
+        if (targets[t] >= (uint32_t)c.vocab)
+            throw InvalidConfig("targets[" + std::to_string(t) + "] = " + std::to_string(targets[t]) + " is not below the vocabulary size " +
+                                std::to_string(c.vocab));
+    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    if (B == 0) return;
+    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
+    const int limit = embed_max_tokens();
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
+        const std::string seq = " (sequence " + std::to_string(b) + ")";
+        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
+                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
+        if (len < 2) throw InvalidConfig("offsets: " + std::to_string(len) + " tokens are fewer than 2" + seq);
+        if (len > limit)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the answer length limit of " + std::to_string(limit) + seq);
+        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
+            if (ids[i] >= (uint32_t)c.vocab)
+                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
+                                    std::to_string(c.vocab) + seq);
+    }
+    const ScorePlan plan = answer_plan_host(ids, offsets, B, d, kScoreMinShared);
+
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hipStream_t s = stream_;
+    ensure_prompt_workspace();
+    ensure_packed_scratch();
+    for (const ScoreChunk& ch : plan.chunks) {
+        const int m = ch.rows, n = ch.n_seq, nv = (int)ch.vec.size(), nm = (int)ch.mfma.size(), np = (int)ch.prefix.size();
+        const size_t o_pos = (size_t)m, o_src = o_pos + (size_t)m, o_tgt = o_src + (size_t)n, o_vec = o_tgt + (size_t)n_targets;
+        const size_t o_mfma = o_vec + 3 * (size_t)nv, o_pre = o_mfma + 3 * (size_t)nm, words = o_pre + 5 * (size_t)np;
+        if (words > kPackedMetaWords) throw std::runtime_error("answer_logits: chunk metadata exceeds its buffer");
+        int32_t* hm = emeta_host_;
+        for (int r = 0; r < m; ++r) hm[r] = (int32_t)ids[ch.row_tok[(size_t)r]];
+        std::memcpy(hm + o_pos, ch.row_pos.data(), (size_t)m * 4);
+        std::memcpy(hm + o_src, ch.gather_src.data(), (size_t)n * 4);
+        std::memcpy(hm + o_tgt, targets, (size_t)n_targets * 4);
+        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
+        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
+        if (np) std::memcpy(hm + o_pre, ch.prefix.data(), (size_t)np * sizeof(PrefixBlock));
+        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
+        packed_layers(m, reinterpret_cast<const uint32_t*>(emeta_), emeta_ + o_pos, reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec), nv,
+                      reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma), nm, reinterpret_cast<const PrefixBlock*>(emeta_ + o_pre), np);
+        // (the norm buffer is free after the last layer: the chunk's [n, n_targets] logits land there)
+        hip_check(launch_answer_logits(ph_, H, emeta_ + o_src, n, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, lm_head_, bf16_ ? 1 : 0,
+                                       reinterpret_cast<const uint32_t*>(emeta_ + o_tgt), n_targets, pn_, s), "answer logits");
+        // They land in the pinned staging buffer, as score_batch's results land in a pinned one: the chunk's upload from it is
+        // behind us on the stream, and n * n_targets <= 1 024 * 8 words fit it.
+        static_assert((size_t)(kEmbedChunkRows / 2) * kAnswerMaxTargets <= kPackedMetaWords, "a chunk's logits fit the staging buffer");
+        hip_check(hipMemcpyAsync(emeta_host_, pn_, (size_t)n * n_targets * sizeof(float), hipMemcpyDeviceToHost, s), "D2H answer logits");
+        hip_check(hipStreamSynchronize(s), "sync");  // the staging copy and the activations are reused by the next chunk
+        // (a chunk's sequences are consecutive: its logits are one block of the output)
+        std::memcpy(logits_out + (size_t)ch.first_seq * n_targets, emeta_host_, (size_t)n * n_targets * sizeof(float));
+    }
+    answer_rows_ += (uint64_t)plan.rows;
+    answer_saved_ += (uint64_t)plan.saved;
 }
 
 }  // namespace kjarni

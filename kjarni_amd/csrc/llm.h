@@ -194,6 +194,22 @@ public:
     // Rows score_batch() computed / prefix rows it did not compute a second time (sum of (members - 1) * prefix), since load.
     uint64_t score_batch_rows() const { return score_batch_rows_; }
     uint64_t score_batch_saved_rows() const { return score_batch_saved_; }
+    // ---- answer logits: a few chosen logits at the end of many sequences ------------------------------------------------------
+    // logits_out[b, t] (row-major [B, n_targets]) = the logit of token targets[t] at the position after the last token of sequence
+    // b = ids[offsets[b], offsets[b + 1]): dot(final_norm(h_last), head_row[targets[t]]), tied or untied head, f32 or bf16.  The
+    // targets (1 .. kAnswerMaxTargets) are shared by the batch: 2 for a yes / no reranker, up to 8 for multiple choice by answer
+    // letter.  answer_plan_host (score_batch_kernels.h) packs the sequences as score_batch does and computes a prefix that
+    // neighbouring sequences share once, never with a sequence's last token in it; every chunk takes one metadata upload, runs
+    // the packed layer stack, then launch_answer_logits over its sequences' last rows -- no vocabulary head -- and one copy of
+    // its [n_seq, n_targets] logits.  K and V live in the embed scratch: cache_len(), resident(), lanes, lookup state, logits,
+    // last_hidden(), the prefix-reuse counters and the buffers and counters of score() and score_batch() are left as they were.
+    // Throws InvalidConfig naming the argument and the sequence, before any GPU work, for non-monotone offsets, a sequence
+    // shorter than 2 or longer than embed_max_tokens(), an id or a target >= vocab and n_targets out of range; takes the
+    // checkpoints score_batch() takes.  B == 0 writes nothing.
+    void answer_logits_batch(const uint32_t* ids, const int32_t* offsets, int B, const uint32_t* targets, int n_targets, float* logits_out);
+    // Rows answer_logits_batch() computed / prefix rows it did not compute a second time, since load (score_batch's pair is its own).
+    uint64_t answer_rows() const { return answer_rows_; }
+    uint64_t answer_saved_rows() const { return answer_saved_; }
     // Cache rows [first, first + rows) of one layer, K after RoPE (Qwen3: after the head norm and RoPE) and V, f32
     // [rows, kv_heads * head_dim] each (a test hook).
     void kv_rows(int layer, int first, int rows, float* k_out, float* v_out) const;
@@ -396,6 +412,7 @@ private:
     // chunk of many short sequences scores more rows than the context is long), and their pinned landing buffer
     uint32_t *sb_res_ = nullptr, *sb_res_host_ = nullptr;
     uint64_t score_batch_rows_ = 0, score_batch_saved_ = 0;
+    uint64_t answer_rows_ = 0, answer_saved_ = 0;  // answer_logits_batch (its logits land in the norm buffer: no buffer of its own)
     float* host_logits_ = nullptr;  // pinned
     std::vector<uint32_t> row_ids_, row_cids_;  // sample_row's scratch: the distribution's ids, the candidates' ids
     std::vector<float> row_probs_, row_cvals_;  // ... and their probabilities / logits

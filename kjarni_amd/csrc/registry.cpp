@@ -56,6 +56,13 @@ const RegistryEntry kDecoderEmbedders[] = {
     {"qwen3-embedding-8b", "Qwen/Qwen3-Embedding-8B", ModelTask::Embedding, ModelArch::Decoder},
 };
 
+// Decoder rerankers (yes / no logits at the last token), kept apart for the same reason.
+const RegistryEntry kDecoderRerankers[] = {
+    {"qwen3-reranker-0.6b", "Qwen/Qwen3-Reranker-0.6B", ModelTask::ReRanking, ModelArch::Decoder},
+    {"qwen3-reranker-4b", "Qwen/Qwen3-Reranker-4B", ModelTask::ReRanking, ModelArch::Decoder},
+    {"qwen3-reranker-8b", "Qwen/Qwen3-Reranker-8B", ModelTask::ReRanking, ModelArch::Decoder},
+};
+
 struct Alias {
     const char* alias;
     const char* cli_name;
@@ -93,6 +100,9 @@ const Alias kAliases[] = {
     {"qwen/qwen3-embedding-0.6b", "qwen3-embedding-0.6b"},
     {"qwen/qwen3-embedding-4b", "qwen3-embedding-4b"},
     {"qwen/qwen3-embedding-8b", "qwen3-embedding-8b"},
+    {"qwen/qwen3-reranker-0.6b", "qwen3-reranker-0.6b"},
+    {"qwen/qwen3-reranker-4b", "qwen3-reranker-4b"},
+    {"qwen/qwen3-reranker-8b", "qwen3-reranker-8b"},
     {"distilgpt2/resolve/main/model.safetensors", "distilgpt2"},
     {"gpt2/resolve/main/model.safetensors", "gpt2"},
 };
@@ -110,6 +120,8 @@ const RegistryEntry* by_cli(const std::string& cli)
     for (const RegistryEntry& e : kEntries)
         if (cli == e.cli_name) return &e;
     for (const RegistryEntry& e : kDecoderEmbedders)
+        if (cli == e.cli_name) return &e;
+    for (const RegistryEntry& e : kDecoderRerankers)
         if (cli == e.cli_name) return &e;
     return nullptr;
 }

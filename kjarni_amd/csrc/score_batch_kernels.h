@@ -47,6 +47,12 @@ struct ScorePlan {
 // for offsets that decrease, a length outside 2 .. kEmbedChunkRows and firsts[b] outside [1, len_b).
 ScorePlan score_plan_host(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int B, int head_dim, int min_shared);
 
+// The plan of LlmModel::answer_logits_batch: score_plan_host's rule (packing, grouping, block tables, rows and saved) with
+// firsts[b] = len_b - 1, so that a shared prefix never contains a sequence's last token.  The gather table differs: one entry per
+// sequence, in order -- gather_src the chunk row of the sequence's last token (always a row of its own: a plain sequence's or a
+// remainder's last row), gather_slot the sequence's index; gather_tgt stays empty.  Throws as score_plan_host does.
+ScorePlan answer_plan_host(const uint32_t* ids, const int32_t* offsets, int B, int head_dim, int min_shared);
+
 // packed_attention_kernel (decoder_embed_kernels.hip) over a virtual sequence: the keys of a block are its prefix rows, then the
 // remainder's own rows; the query at remainder row t sees virtual keys 0 .. prefix_len + t.  Tiles start at virtual key 0 in
 // steps of 64, so a remainder's rows are what launch_packed_causal_attention's vector kernel gives on the concatenation, bit

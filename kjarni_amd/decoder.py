@@ -101,6 +101,30 @@ def score_plan(seqs: Sequence[Sequence[int]], firsts: Sequence[int], head_dim: i
             "mfma": mfma[:nm].copy(), "prefix": pre[:np_].copy(), "gather": gather[:nga].copy()}
 
 
+ANSWER_MAX_TARGETS = 8  # KJARNI_HIP_ANSWER_MAX_TARGETS
+
+
+def answer_plan(seqs: Sequence[Sequence[int]], head_dim: int = 64, min_shared: int = SCORE_MIN_SHARED) -> dict:
+    """The plan of HipDecoder.answer_logits (no GPU): score_plan's rule and tables with every sequence's `first` at its last token,
+    so that no shared prefix holds a sequence's last token.  The dict is score_plan's, but gather is [n, 3]: per sequence, in
+    order, (chunk, the chunk row of its last token, the sequence's index)."""
+    flat, off = _flatten(seqs)
+    n = len(seqs)
+    i32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    cap = int(max(off[-1], 0)) + n + 1
+    first, rows = np.zeros(n + 1, np.int32), np.zeros(max(n, 1), np.int32)
+    groups, vec, mfma = np.zeros((n + 1, 4), np.int32), np.zeros((cap, 4), np.int32), np.zeros((cap, 4), np.int32)
+    pre, gather = np.zeros((cap, 6), np.int32), np.zeros((n + 1, 3), np.int32)
+    cnt = [C.c_int32(0) for _ in range(6)]
+    check_error(lib().kjarni_hip_answer_plan(flat.ctypes.data_as(C.POINTER(C.c_uint32)) if n else None, i32(off) if n else None, n, int(head_dim),
+                                             int(min_shared), i32(first), i32(rows), C.byref(cnt[0]), i32(groups), n + 1, C.byref(cnt[1]),
+                                             i32(vec), cap, C.byref(cnt[2]), i32(mfma), cap, C.byref(cnt[3]), i32(pre), cap, C.byref(cnt[4]),
+                                             i32(gather), n + 1, C.byref(cnt[5])))
+    nc, ng, nv, nm, np_, nga = (c.value for c in cnt)
+    return {"chunk_first_seq": first[:nc + 1].copy(), "chunk_rows": rows[:nc].copy(), "groups": groups[:ng].copy(), "vec": vec[:nv].copy(),
+            "mfma": mfma[:nm].copy(), "prefix": pre[:np_].copy(), "gather": gather[:nga].copy()}
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
@@ -457,6 +481,34 @@ class HipDecoder:
         since load."""
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_score_batch_rows(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    # ---- answer logits: a few chosen logits at the end of many sequences ----
+    def answer_logits(self, seqs: Sequence[Sequence[int]], targets: Sequence[int]) -> np.ndarray:
+        """f32 [len(seqs), len(targets)]: the logit of every target token (1 .. ANSWER_MAX_TARGETS ids, shared by the batch) at the
+        position after each sequence's last token, in one packed pass without the vocabulary head.  Neighbouring sequences that
+        start with the same tokens compute them once, their last tokens excepted (answer_plan); the KV cache and everything
+        generate(), score() and score_batch() depend on are left as they were."""
+        flat, off = _flatten(seqs)
+        return self.answer_logits_flat(flat, off, targets)
+
+    def answer_logits_flat(self, ids, offsets, targets) -> np.ndarray:
+        """answer_logits() on ids and offsets [n + 1] as the C ABI takes them."""
+        a, o = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(offsets, np.int32)
+        t = np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        n = o.size - 1
+        buf = np.zeros(max(n * t.size, 1), np.float32)
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        tp = u32(t) if t.size else u32(np.zeros(1, np.uint32))
+        check_error(lib().kjarni_hip_decoder_answer_logits(self._h, u32(a), o.ctypes.data_as(C.POINTER(C.c_int32)), n, tp, t.size,
+                                                           buf.ctypes.data_as(C.POINTER(C.c_float))))
+        return buf[:max(n, 0) * t.size].reshape(max(n, 0), t.size)
+
+    def answer_rows(self):
+        """(computed, saved): rows answer_logits() ran through the layer stack, and prefix rows it did not compute a second time,
+        since load (score_batch_rows() counts its own calls only)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_decoder_answer_rows(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     # ---- embedding: last-token pooling over a packed batch ----

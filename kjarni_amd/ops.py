@@ -347,6 +347,32 @@ def score_gather_norm(x, src, gamma, beta=None, eps: float = 1e-5, hidden=None, 
     return oa
 
 
+def answer_logits(x, src, gamma, head, targets, beta=None, eps: float = 1e-6, hidden=None, head_is_bf16: bool = False, device: int = 0):
+    """The answer-logits kernel of HipDecoder.answer_logits alone: out[j, t] = dot(norm(x[src[j], :hidden]), head[targets[t], :]) --
+    RMSNorm(gamma, eps), or LayerNorm(gamma, beta, eps) when beta is given.  x: [rows, ldx] f32; head: [head_rows, hidden] f32, or
+    uint16 bf16 bit patterns with head_is_bf16.  Returns f32 [len(src), len(targets)]."""
+    xa = np.ascontiguousarray(x, np.float32)
+    g = np.ascontiguousarray(gamma, np.float32)
+    b = None if beta is None else np.ascontiguousarray(beta, np.float32)
+    hidden = g.size if hidden is None else int(hidden)
+    ha = np.ascontiguousarray(head, np.uint16 if head_is_bf16 else np.float32)
+    s, t = np.ascontiguousarray(src, np.int32), np.ascontiguousarray(targets, np.uint32)
+    if xa.ndim != 2 or ha.ndim != 2 or ha.shape[1] != hidden:
+        raise ValueError("x: [rows, ldx]; head: [head_rows, hidden]")
+    out = np.zeros(max(s.size * t.size, 1), np.float32)
+    tp = t if t.size else np.zeros(1, np.uint32)        # (an empty list still reaches the check that names n_targets)
+    check_error(lib().kjarni_hip_op_answer_logits(device, _f(xa), xa.shape[1], xa.shape[0], s.ctypes.data_as(_i32p), s.size, hidden, _f(g),
+                                                  _f(b) if b is not None else None, float(eps), ha.ctypes.data_as(C.c_void_p), ha.shape[0],
+                                                  int(bool(head_is_bf16)), tp.ctypes.data_as(_ffi._u32p), t.size, _f(out)))
+    return out[:s.size * t.size].reshape(s.size, t.size)
+
+
+def answer_plan(seqs, head_dim: int = 64, min_shared: Optional[int] = None) -> dict:
+    """The plan of HipDecoder.answer_logits (no GPU): decoder.answer_plan."""
+    from . import decoder
+    return decoder.answer_plan(seqs, head_dim, decoder.SCORE_MIN_SHARED if min_shared is None else min_shared)
+
+
 def argmax(logits, vocab: Optional[int] = None, route: int = ARGMAX_DECODER, live=None, draft=None, device: int = 0):
     """The greedy pick kernels on logits [calls, rows, ld] (the last of equal maxima wins; columns >= vocab are padding).
     Returns picks int32 [calls, rows]: decoder route rows == 1; lanes route -1 for the lanes `live` [rows] freezes; lookup

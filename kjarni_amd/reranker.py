@@ -13,6 +13,17 @@ class RerankResult(NamedTuple):
     document: str
 
 
+def rerank_prompt_ids(tokenizer_json: str, query: str, document: str, instruction: Optional[str] = None, max_tokens: int = 2048) -> List[int]:
+    """The token ids a decoder reranker scores for (query, document) (no GPU; kjarni_hip_rerank_prompt_ids): system block +
+    "<Instruct>: ..\\n<Query>: ..\\n<Document>: .." cut from the right to fit max_tokens + the assistant turn with an empty
+    think block."""
+    n = C.c_size_t(0)
+    buf = (C.c_uint32 * max(int(max_tokens), 1))()
+    check_error(lib().kjarni_hip_rerank_prompt_ids(tokenizer_json.encode("utf-8"), None if instruction is None else instruction.encode("utf-8"),
+                                                   query.encode("utf-8"), document.encode("utf-8"), int(max_tokens), buf, len(buf), C.byref(n)))
+    return list(buf[:min(n.value, len(buf))])
+
+
 class Reranker:
     def __init__(self, model: Optional[str] = None, device: str = "cpu", cache_dir: Optional[str] = None,
                  quiet: bool = False, model_path: Optional[str] = None):
@@ -28,6 +39,18 @@ class Reranker:
         if getattr(self, "_handle", None) and self._handle.value:
             lib().kjarni_reranker_free(self._handle)
             self._handle = C.c_void_p()
+
+    def set_instruction(self, instruction: Optional[str]):
+        """The instruction line of a decoder reranker's prompt; None restores the default.  A cross-encoder reranker has none and
+        answers INVALID_CONFIG."""
+        check_error(lib().kjarni_reranker_set_instruction(self._handle, None if instruction is None else instruction.encode("utf-8")))
+
+    def answer_rows(self):
+        """(computed, saved) of a decoder reranker's model: rows its calls ran through the layer stack, and prefix rows -- the
+        system block, the instruction and the query of neighbouring documents -- they did not compute a second time."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_reranker_answer_rows(self._handle, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
 
     def score(self, query: str, document: str) -> float:
         result = C.c_float()

@@ -64,6 +64,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            the latency of 1, 8 and 64 x 128, and in the same run a loop of forward() + last_hidden() per sentence (what there
            was before embed()) over the same 64 x 128, alternated twice; medians of runs that end in a synchronise.  The lines
            also go to profiles/decoder_embed_bench.jsonl.
+  llm_rerank  (only on request) HipDecoder.answer_logits() -- decoder rerankers: two chosen logits at the end of many prompts in one
+           packed pass, the query computed once -- on the Qwen3-0.6B shape (bf16, random init): one query of 64 tokens in front of
+           16 / 64 / 256 documents of 128 tokens, as given (sharing) against the same batch with every sequence's token 0 made
+           distinct (nothing shared) and against a loop of forward() over the same sequences; legs alternated twice, medians of
+           runs that end in a synchronise.  The lines also go to profiles/decoder_rerank_bench.jsonl.
 """
 import json
 import os
@@ -1442,6 +1447,67 @@ def main():
         dec.reset()
         del dec
         with open(os.path.join(ROOT, "profiles", "decoder_embed_bench.jsonl"), "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+    if "llm_rerank" in which:
+        # Method (measuring guide, section 5; as llm_score_batch): one process on one box; every leg of a case is warmed first,
+        # then the legs are alternated twice, two runs each; every run ends in a synchronise (answer_logits() returns after one,
+        # forward(fetch=True) after the copy of its logits); medians over the 4 runs of a leg.  The forward() loop over the same
+        # sequences is what there was before answer_logits().
+        from tests import qwen3_fixture
+        geo = dict(qwen3_fixture.Q3_06B_WIDTHS, num_hidden_layers=28, vocab_size=151936, max_position_embeddings=4096, eos_token_id=[])
+        d = os.path.join(tmp, "qwen3-0.6b-rerank")
+        qwen3_fixture.qwen3_model(d, geo, seed=0, store_bf16=True, std=0.02)
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        rng = np.random.default_rng(0)
+        dtype = "bf16 weights, f32 activations/accumulate"
+        shape = "Qwen3-0.6B geometry (1024 hidden, 28 layers, 16/8 heads of 128, intermediate 3072, vocab 151936), random init"
+        method = "legs alternated twice in one process, medians of 4 runs, every run ends in a synchronise"
+        targets = np.array([9693, 2152], np.uint32)
+        lines = []
+        for n in (16, 64, 256):     # one query of 64 tokens in front of n documents of 128
+            query = rng.integers(1000, 100000, 64).astype(np.uint32)
+            shared = [np.concatenate([query, rng.integers(1000, 100000, 128).astype(np.uint32)]) for _ in range(n)]
+            distinct = [s.copy() for s in shared]
+            for i, s in enumerate(distinct):
+                s[0] = 100 + i                                                  # (same shapes, nothing shared)
+            off = np.concatenate([[0], np.cumsum([len(s) for s in shared])]).astype(np.int32)
+            fs, fd = np.concatenate(shared), np.concatenate(distinct)
+
+            def loop():
+                for s in shared:
+                    dec.reset()
+                    dec.forward(s)
+            legs = {"shared": lambda: dec.answer_logits_flat(fs, off, targets), "not_shared": lambda: dec.answer_logits_flat(fd, off, targets),
+                    "forward_loop": loop}
+            r0 = dec.answer_rows()
+            legs["shared"]()
+            r1 = dec.answer_rows()
+            legs["not_shared"]()
+            r2 = dec.answer_rows()
+            legs["forward_loop"]()
+            runs = {k: [] for k in legs}
+            for rep in range(2):
+                for _ in range(2):
+                    for k, fn in legs.items():
+                        t0 = time.perf_counter()
+                        fn()
+                        runs[k].append((time.perf_counter() - t0) * 1e3)
+            med = {k: float(np.median(v)) for k, v in runs.items()}
+            line = {"metric": f"forward loop / answer_logits, Qwen3-0.6B shape, bf16 weights, a 64-token query x {n} documents of 128 tokens",
+                    "value": round(med["forward_loop"] / med["shared"], 2), "unit": "ratio of medians", "n_gpus": 1, "dtype": dtype,
+                    "data": "synthetic", "config": {"workload": f"{shape}; {method}; not_shared: every sequence's token 0 made distinct"},
+                    "documents": n, "shared_ms": round(med["shared"], 3), "not_shared_ms": round(med["not_shared"], 3),
+                    "forward_loop_ms": round(med["forward_loop"], 3), "not_shared_over_shared": round(med["not_shared"] / med["shared"], 3),
+                    "documents_per_s": round(n / med["shared"] * 1e3, 1), "rows_shared": r1[0] - r0[0], "rows_saved_shared": r1[1] - r0[1],
+                    "rows_not_shared": r2[0] - r1[0], "rows_saved_not_shared": r2[1] - r1[1],
+                    "runs": {k: [round(x, 3) for x in v] for k, v in runs.items()}}
+            emit(line)
+            lines.append(line)
+        dec.reset()
+        del dec
+        with open(os.path.join(ROOT, "profiles", "decoder_rerank_bench.jsonl"), "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
 
