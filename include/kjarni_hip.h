@@ -722,6 +722,39 @@ void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* generator, uint64_t
 KjarniErrorCode kjarni_hip_generator_set_prompt_lookup_sampling(KjarniGenerator* generator, int32_t on);
 KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniChat* chat, int32_t on);
 
+/* ---- speculative decoding with a draft model (NOT in the reference) ----
+ * The verify step of prompt lookup with the draft coming from `draft`, a second decoder on the same device with the same vocab
+ * and a context at least the decoder's.  Per round the drafter proposes draft_tokens tokens greedily (one 2-row pass that
+ * re-runs the last cached row, then one-row steps), the decoder verifies them in one multi-row step, and every emitted token
+ * is the decoder's own decision: the ids are those of kjarni_hip_decoder_generate_sampled without lookup for the same options
+ * and draws (greedy: wherever the two best logits are further apart than the float bar).  A round is one captured chain on the
+ * decoder's stream.  draft_tokens (1..7) is required: DESIGN §6 has the table a caller chooses from.  Routing: greedy without
+ * processors -> the greedy loop; options->sample without an n-gram ban (with or without a repetition penalty) -> the sampled
+ * loop; greedy with a penalty, or any n-gram ban -> the plain loop (stats zero, the drafter untouched).  stats as
+ * kjarni_hip_decoder_generate_lookup: drafted_tokens = rows - 1 per verify step.  draft NULL, draft == decoder, another
+ * device, another vocab, a shorter context, draft_tokens outside 1..7, an empty or over-long prompt: INVALID_CONFIG before any
+ * GPU work, the message names the argument.  Afterwards the drafter's cache is one row behind the decoder's. */
+KjarniErrorCode kjarni_hip_decoder_generate_draft(KjarniHipDecoder* decoder, KjarniHipDecoder* draft, const uint32_t* prompt, size_t n_prompt,
+                                                  const KjarniHipSamplingOptions* options, int32_t draft_tokens,
+                                                  KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out, size_t capacity,
+                                                  size_t* n_out, KjarniHipLookupStats* stats);
+/* Test hook: one greedy round of `rows` (2..8) rows on the two caches as they stand, like kjarni_hip_decoder_verify_step with
+ * the draft coming from the drafter.  `token` is the token in neither cache; the one before it is the last of the decoder's
+ * resident tokens, which must cover its cache (>= 1 row); the drafter's resident tokens must be the decoder's up to
+ * cache_len - 1, else INVALID_CONFIG.  draft_out[rows - 1] (room for 7): the proposals; tokens_out[0 .. *n_accepted] (room for
+ * 8): the picks; logits_out (may be NULL) f32 [rows, vocab].  The decoder's cache grows by *n_accepted + 1; the drafter's ends
+ * at the decoder's length, or one row short when every proposal was accepted. */
+KjarniErrorCode kjarni_hip_decoder_draft_round(KjarniHipDecoder* decoder, KjarniHipDecoder* draft, uint32_t token, int32_t rows,
+                                               uint32_t* draft_out, uint32_t* tokens_out, int32_t* n_accepted, float* logits_out);
+/* A drafter for kjarni_generator_generate / _generate_stream and kjarni_chat_send*: loads model_dir_or_gguf on the handle's
+ * device with its weights as stored and the handle's context; the handle owns it.  NULL or draft_tokens == 0 frees it.  While
+ * set it takes precedence over prompt lookup, under the routing of kjarni_hip_decoder_generate_draft; generate_batch is
+ * untouched.  draft_tokens outside 0..7 or a checkpoint with another vocab: INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_generator_set_draft_model(KjarniGenerator* generator, const char* model_dir_or_gguf, int32_t draft_tokens);
+KjarniErrorCode kjarni_hip_chat_set_draft_model(KjarniChat* chat, const char* model_dir_or_gguf, int32_t draft_tokens);
+/* kjarni_hip_decoder_verify_gemv_calls of the chat's model: it moves only when a call took a lookup or a draft loop. */
+void kjarni_hip_chat_verify_gemv_calls(KjarniChat* chat, uint64_t* streamed, uint64_t* fallback);
+
 /* ---- scoring: per-token log-probabilities of a given sequence (NOT in the reference: it has no scoring entry point; the
  * arithmetic is its final norm + head, llama/cpu_decoder.rs:196-219, gpt2/cpu_decoder.rs:371-394, and log_softmax_1d,
  * common/sampling.rs:200-205) ----

@@ -484,6 +484,13 @@ SIGNATURES = {
     "kjarni_hip_decoder_generate_sampled": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
                                                       POINTER(KjarniHipLookupConfig), KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t,
                                                       POINTER(c_size_t), POINTER(KjarniHipLookupStats)]),
+    "kjarni_hip_decoder_generate_draft": (c_int32, [c_void_p, c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions), c_int32,
+                                                    KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
+                                                    POINTER(KjarniHipLookupStats)]),
+    "kjarni_hip_decoder_draft_round": (c_int32, [c_void_p, c_void_p, C.c_uint32, c_int32, _u32p, _u32p, POINTER(c_int32), _f32p]),
+    "kjarni_hip_generator_set_draft_model": (c_int32, [c_void_p, c_char_p, c_int32]),
+    "kjarni_hip_chat_set_draft_model": (c_int32, [c_void_p, c_char_p, c_int32]),
+    "kjarni_hip_chat_verify_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_sampling_options_layout": (c_size_t, [POINTER(c_size_t), c_size_t]),
     "kjarni_hip_decoder_sampling_routes": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_decoder_verify_step_sampled": (c_int32, [c_void_p, C.c_uint32, _u32p, c_int32, c_int32, POINTER(KjarniHipSamplingOptions),

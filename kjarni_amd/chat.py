@@ -180,6 +180,18 @@ class Chat:
         """Prompt-lookup decoding for sampled requests (off by default): the replies are the plain path's for the same seed."""
         check_error(lib().kjarni_hip_chat_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
 
+    def set_draft_model(self, model_dir_or_gguf: Optional[str], draft_tokens: int = 0):
+        """A draft model for send(): the checkpoint is loaded on this handle's device and owned by it, and proposes
+        draft_tokens (1..7) tokens per verify step; None / 0 frees it.  The replies are the plain path's for the same seed."""
+        path = model_dir_or_gguf.encode("utf-8") if model_dir_or_gguf else None
+        check_error(lib().kjarni_hip_chat_set_draft_model(self._handle, path, int(draft_tokens)))
+
+    def verify_gemv_calls(self):
+        """(streamed, fallback) projections of verify steps since load: moves only when a call took a lookup or a draft loop."""
+        a, b = C.c_uint64(), C.c_uint64()
+        lib().kjarni_hip_chat_verify_gemv_calls(self._handle, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def set_prefix_reuse(self, on: bool):
         """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): turn N of a
         conversation then prefills only what the conversation gained since turn N - 1."""

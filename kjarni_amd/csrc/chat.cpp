@@ -353,7 +353,7 @@ GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, 
 // every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
 std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
                                 const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
-                                int prompt_lookup = 0, int sampled_lookup = 0)
+                                int prompt_lookup = 0, int sampled_lookup = 0, LlmModel* drafter = nullptr, int draft_tokens = 0)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     const GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
@@ -365,8 +365,11 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
         text += piece;
         return on_text ? on_text(piece) : true;
     };
-    // prompt lookup (when set): greedy requests without processors verify a draft from their own history every step
-    if (prompt_lookup > 0 && !opt.sample && opt.repetition_penalty == 1.0f && opt.no_repeat_ngram <= 0) {
+    // a draft model (when set) takes precedence over prompt lookup: greedy requests without processors and sampled requests
+    // without an n-gram ban verify the drafter's proposals every step; the others take the plain loop inside generate_draft
+    if (drafter && draft_tokens > 0) {
+        model.generate_draft(drafter, prompt_tokens, opt, draft_tokens, on_token, nullptr);
+    } else if (prompt_lookup > 0 && !opt.sample && opt.repetition_penalty == 1.0f && opt.no_repeat_ngram <= 0) {
         LookupConfig lk;
         lk.draft_tokens = prompt_lookup;
         model.generate_lookup(prompt_tokens, opt, lk, on_token, nullptr);
@@ -492,13 +495,41 @@ std::vector<uint32_t> Chat::encode(const std::string& prompt, const GenerationCo
     return encode_prompt(tokenizer_, model_->config(), prompt, config);
 }
 
+// The drafter of a handle: `path` loaded on the target's device with its weights as stored and the target's context, checked
+// against the target before it replaces the old one; an empty path or draft_tokens == 0 frees it.
+static void set_handle_drafter(LlmModel& target, const std::string& path, int draft_tokens, std::unique_ptr<LlmModel>& drafter, int& tokens)
+{
+    if (draft_tokens < 0 || draft_tokens > 7) throw InvalidConfig("draft_tokens must be 1..7 (0 = off)");
+    if (path.empty() || draft_tokens == 0) {
+        drafter.reset();
+        tokens = 0;
+        return;
+    }
+    std::unique_ptr<LlmModel> fresh = LlmModel::load(path, target.device(), 0, target.context());
+    target.check_draft_pair(fresh.get(), draft_tokens);
+    drafter = std::move(fresh);
+    tokens = draft_tokens;
+}
+
+void Chat::set_draft_model(const std::string& path, int draft_tokens)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_drafter(*model_, path, draft_tokens, drafter_, draft_tokens_);
+}
+
+void Generator::set_draft_model(const std::string& path, int draft_tokens)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_drafter(*model_, path, draft_tokens, drafter_, draft_tokens_);
+}
+
 std::string Chat::run(const std::string& prompt, const GenerationOverrides& runtime, const std::function<bool(const std::string&)>& on_text)
 {
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, 0,
-                               lookup_sampling_ ? LookupConfig().draft_tokens : 0);
+                               lookup_sampling_ ? LookupConfig().draft_tokens : 0, drafter_.get(), draft_tokens_);
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -583,7 +614,7 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_,
-                               lookup_sampling_ ? prompt_lookup_ : 0);
+                               lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_);
 }
 
 size_t Generator::encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const

@@ -102,6 +102,10 @@ public:
     // Prompt-lookup decoding for sampled requests (LlmModel::generate_lookup_sampled, the default draft length): off by default;
     // a request with an n-gram ban and every greedy request keep the plain loop.
     void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
+    // A draft model for send (LlmModel::generate_draft): `path` (a model directory or a .gguf) is loaded on the model's device
+    // with its weights as stored and the model's context, and owned by the handle; an empty path or draft_tokens == 0 frees it.
+    // While set it takes precedence over prompt lookup.  InvalidConfig for draft_tokens outside 0..7 or another vocabulary.
+    void set_draft_model(const std::string& path, int draft_tokens);
 
 private:
     Chat() = default;
@@ -119,6 +123,8 @@ private:
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
     bool lookup_sampling_ = false;
+    std::unique_ptr<LlmModel> drafter_;
+    int draft_tokens_ = 0;
     std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
 };
 
@@ -157,6 +163,8 @@ public:
     // The same for sampled configs, with or without a repetition penalty (LlmModel::generate_lookup_sampled): off by default;
     // taken when it is on, prompt lookup is set and the resolved config has no n-gram ban.
     void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
+    // A draft model for generate / stream (Chat::set_draft_model's contract); generate_batch is untouched.
+    void set_draft_model(const std::string& path, int draft_tokens);
     // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
     // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
     // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
@@ -200,6 +208,8 @@ private:
     int batch_lanes_ = 0;
     int prompt_lookup_ = 0;
     bool lookup_sampling_ = false;
+    std::unique_ptr<LlmModel> drafter_;
+    int draft_tokens_ = 0;
 };
 
 // str::trim (Unicode White_Space at both ends).

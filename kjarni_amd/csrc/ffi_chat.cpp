@@ -808,6 +808,25 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniC
     return KJARNI_OK;
 }
 
+// A draft model owned by the handle (Chat::set_draft_model): NULL / 0 frees it.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_draft_model(KjarniGenerator* gen, const char* model_dir_or_gguf, int32_t draft_tokens)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] { gen->inner->set_draft_model(model_dir_or_gguf ? model_dir_or_gguf : "", draft_tokens); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_draft_model(KjarniChat* chat, const char* model_dir_or_gguf, int32_t draft_tokens)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] { chat->inner->set_draft_model(model_dir_or_gguf ? model_dir_or_gguf : "", draft_tokens); });
+}
+
+KJARNI_EXPORT void kjarni_hip_chat_verify_gemv_calls(KjarniChat* chat, uint64_t* streamed, uint64_t* fallback)
+{
+    if (streamed) *streamed = chat ? chat->inner->model().verify_stream_calls() : 0;
+    if (fallback) *fallback = chat ? chat->inner->model().verify_fallback_calls() : 0;
+}
+
 // Prefix reuse (LlmModel::set_prefix_reuse) on the handle's model: send() then prefills only what the conversation gained since
 // the last turn, score() only what follows the tokens it shares with the call before, generate_batch the shared prefix once.
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on)

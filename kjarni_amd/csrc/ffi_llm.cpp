@@ -363,6 +363,76 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecod
     });
 }
 
+// ---- speculative decoding with a draft model -----------------------------------------------------------------------------------
+
+// Both handles' locks, in address order (two calls with the handles swapped cannot deadlock); draft == d is refused before.
+struct DraftPairLock {
+    std::unique_lock<std::mutex> first, second;
+    DraftPairLock(KjarniHipDecoder* a, KjarniHipDecoder* b)
+    {
+        if (b < a) std::swap(a, b);
+        first = std::unique_lock<std::mutex>(a->mu);
+        second = std::unique_lock<std::mutex>(b->mu);
+    }
+};
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_draft(KjarniHipDecoder* d, KjarniHipDecoder* draft, const uint32_t* prompt,
+                                                                size_t n_prompt, const KjarniHipSamplingOptions* options,
+                                                                int32_t draft_tokens, KjarniTokenCallbackFn on_token, void* user_data,
+                                                                uint32_t* ids_out, size_t capacity, size_t* n_out,
+                                                                KjarniHipLookupStats* stats)
+{
+    if (!options || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    if (options->uniforms && options->n_uniforms < options->max_new_tokens) {
+        set_last_error("n_uniforms (" + std::to_string(options->n_uniforms) + ") is less than max_new_tokens (" +
+                       std::to_string(options->max_new_tokens) + ")");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!d || (n_prompt && !prompt) || (capacity && !ids_out) || (options->n_stop && !options->stop_ids)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // everything that can be refused is refused before any GPU work
+        if (!draft) throw InvalidConfig("draft must not be null");
+        if (draft == d) throw InvalidConfig("draft must be another model than the decoder itself");
+        DraftPairLock lock(d, draft);
+        d->model->check_draft_pair(draft->model.get(), draft_tokens);
+        if (n_prompt == 0) throw InvalidConfig("prompt must not be empty");
+        if (n_prompt > (size_t)d->model->context())
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
+        GenerateOptions opt = sampling_options(*options);
+        UniformRng rng(options->seed);
+        size_t drawn = 0;
+        const float* u = options->uniforms;
+        const size_t n_u = options->n_uniforms;
+        if (u)
+            opt.uniform = [&drawn, u, n_u] {
+                if (drawn >= n_u) throw std::runtime_error("the draw stream is exhausted: more draws than uniforms");
+                return u[drawn++];
+            };
+        else opt.uniform = [&rng] { return rng.next(); };
+        LookupStats st;
+        const std::vector<uint32_t> ids =
+            d->model->generate_draft(draft->model.get(), std::vector<uint32_t>(prompt, prompt + n_prompt), opt, draft_tokens, cb, &st);
+        copy_ids_out(ids, ids_out, capacity, n_out);
+        if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_draft_round(KjarniHipDecoder* d, KjarniHipDecoder* draft, uint32_t token, int32_t rows,
+                                                             uint32_t* draft_out, uint32_t* tokens_out, int32_t* n_accepted,
+                                                             float* logits_out)
+{
+    if (!d || !draft_out || !tokens_out || !n_accepted) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!draft) throw InvalidConfig("draft must not be null");
+        if (draft == d) throw InvalidConfig("draft must be another model than the decoder itself");
+        DraftPairLock lock(d, draft);
+        *n_accepted = d->model->draft_round(draft->model.get(), token, rows, draft_out, tokens_out, logits_out);  // checked before any GPU work
+    });
+}
+
 KJARNI_EXPORT size_t kjarni_hip_sampling_options_layout(size_t* out, size_t capacity)
 {
     using O = KjarniHipSamplingOptions;

@@ -3,6 +3,7 @@
 #include "ffi_common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -12,6 +13,7 @@
 #include "json.h"
 #include "kernels.h"
 #include "decoder_embed_kernels.h"
+#include "draft_model_kernels.h"
 #include "llm_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
@@ -159,6 +161,8 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     if (visible_device_count() <= device) throw GpuUnavailable("no usable HIP device " + std::to_string(device));
     std::unique_ptr<LlmModel> m(new LlmModel());
     m->device_ = device;
+    static std::atomic<uint64_t> next_serial{1};  // (0 is "no drafter" in the graph keys)
+    m->serial_ = next_serial.fetch_add(1);
     hip_check(hipSetDevice(device), "hipSetDevice");
     // a `.gguf` file, or a directory: safetensors win, else its first `*.gguf` (model_weights.rs:45-77)
     const std::string gguf_path = resolve_gguf(dir);
@@ -1901,24 +1905,62 @@ void LlmModel::ensure_lookup()
     vlogits_ = dalloc((size_t)kLanes * cfg_.vocab);
 }
 
-void LlmModel::enqueue_verify(int rows, int ngram_max, int ngram_min, bool draft, bool record)
+LlmModel::StreamScope::StreamScope(LlmModel* model, hipStream_t stream) : model_(model), saved_(nullptr)
 {
-    if (draft) hip_check(launch_lookup_draft(lk_hist_, lk_state_, ngram_max, ngram_min, rows - 1, rows, vids_, stream_), "lookup draft");
+    if (!model_) return;
+    hip_check(hipStreamSynchronize(model_->stream_), "sync");  // what the model enqueued on its own stream is done
+    saved_ = model_->stream_;
+    model_->stream_ = stream;
+}
+
+LlmModel::StreamScope::~StreamScope()
+{
+    if (model_) model_->stream_ = saved_;
+}
+
+// The draft of a verify step, enqueued on stream_.  The lookup rule: one launch.  A drafter (which enqueues on stream_ too: the
+// caller holds a StreamScope and has called ensure_lookup() on it): begin, one 2-row pass at n - 2, then rows - 2 single-row
+// steps that each read the id handed over before them; rows == 1: the begin alone, no drafter kernel.  The 2-row pass takes the
+// verify route (the multi-row weight-streaming kernels, both rows' logits in the drafter's vlogits_, of which row 1 is used):
+// measured on the Llama-1B shape it costs 0.93 ms there against 1.42 ms on the non-verify route, whose projections of 2 .. 8
+// rows are the prompt's one-wave-per-column kernels (a plain step: 0.62 ms).
+void LlmModel::enqueue_draft(int rows, const DraftSource& src)
+{
+    if (!src.drafter) {
+        hip_check(launch_lookup_draft(lk_hist_, lk_state_, src.ngram_max, src.ngram_min, rows - 1, rows, vids_, stream_), "lookup draft");
+        return;
+    }
+    LlmModel& d = *src.drafter;
+    hip_check(launch_draft_begin(lk_hist_, lk_hist_cap_, lk_state_, rows, d.ids_, d.pos_, vids_, stream_), "draft begin");
+    if (rows < 2) return;
+    d.pass(d.ids_, 2, true, true);
+    hip_check(launch_draft_handoff(d.vlogits_ + d.cfg_.vocab, d.cfg_.vocab, d.best_, vids_ + 1, d.pos_, 2, stream_), "draft hand-off");
+    for (int i = 1; i <= rows - 2; ++i) {
+        d.pass(vids_ + i, 1, true);
+        hip_check(launch_draft_handoff(d.logits_, d.cfg_.vocab, d.best_, vids_ + i + 1, d.pos_, 1, stream_), "draft hand-off");
+    }
+}
+
+void LlmModel::enqueue_verify(int rows, const DraftSource* src, bool record)
+{
+    if (src) enqueue_draft(rows, *src);
     pass(vids_, rows, true, true);
     hip_check(launch_lookup_pick(vlogits_, cfg_.vocab, cfg_.vocab, rows, vids_, lk_best_, lk_state_, record ? lk_hist_ : nullptr, lk_hist_cap_,
                                  pos_, record ? lk_log_ : nullptr, lk_hist_cap_, stream_), "lookup pick");
 }
 
-hipGraphExec_t LlmModel::lookup_graph(int rows, const LookupConfig& c)
+hipGraphExec_t LlmModel::lookup_graph(int rows, const DraftSource& c)
 {
-    if (lookup_ngram_[0] != c.ngram_max || lookup_ngram_[1] != c.ngram_min) {  // (arguments of the captured draft launch)
+    // (arguments of the captured draft launch, or the drafter whose pointers the captured chain holds)
+    if (lookup_ngram_[0] != c.ngram_max || lookup_ngram_[1] != c.ngram_min || lookup_serial_ != c.serial()) {
         hip_check(hipStreamSynchronize(stream_), "sync");
         drop_graphs(lookup_graphs_);
         lookup_ngram_[0] = c.ngram_max;
         lookup_ngram_[1] = c.ngram_min;
+        lookup_serial_ = c.serial();
     }
     if (lookup_graphs_[rows]) return lookup_graphs_[rows];
-    return lookup_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify(rows, c.ngram_max, c.ngram_min, true, true); });
+    return lookup_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify(rows, &c, true); });
 }
 
 // The ids of a verify block: the token, the draft, and the draft's last id again in the rows past it.
@@ -1945,7 +1987,7 @@ int LlmModel::verify_step(uint32_t token, const uint32_t* draft, int n_draft, in
     hip_check(hipMemcpyAsync(vids_, ids, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, stream_), "H2D ids");
     hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
-    enqueue_verify(rows, 1, 1, false, false);
+    enqueue_verify(rows, nullptr, false);
     hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
     hip_check(hipStreamSynchronize(stream_), "sync");
     for (int i = 0; i <= st.a; ++i) tokens_out[i] = (uint32_t)st.picks[i];
@@ -1962,11 +2004,46 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     if (stats) *stats = LookupStats();
     check_lookup_config(lk);
     if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0) return generate(prompt, opt, on_token);  // not applicable
+    DraftSource src;
+    src.ngram_max = lk.ngram_max;
+    src.ngram_min = lk.ngram_min;
+    return greedy_draft_loop(prompt, opt, src, lk.draft_tokens, on_token, stats);
+}
+
+// The drafter's side of a loop's start: its own stream is synchronised, its cache holds the prompt (by its own prefix-reuse
+// switch).  The caller then holds a StreamScope for the rounds.
+void LlmModel::drafter_begin(const DraftSource& src, const std::vector<uint32_t>& prompt)
+{
+    if (!src.drafter) return;
+    hip_check(hipStreamSynchronize(src.drafter->stream_), "sync");
+    src.drafter->ensure_lookup();  // (the rows of its 2-row pass land in its vlogits_: allocated here, never inside a capture)
+    src.drafter->begin_sequence(prompt);
+}
+
+// ... and of its end.  A round on a history of n tokens leaves valid drafter rows for T[0 .. n - 2 + min(a, m - 1)]: with the
+// target's cache at cache_len_ rows, rows [0, cache_len_ - 1) of the drafter hold the target's tokens whatever was accepted.
+void LlmModel::drafter_leave(const DraftSource& src, const std::vector<uint32_t>& all, bool rounds_ran)
+{
+    if (!src.drafter || !rounds_ran) return;  // (no round: the drafter is as begin_sequence(prompt) left it)
+    LlmModel& d = *src.drafter;
+    d.cache_len_ = cache_len_ - 1;
+    d.last_rows_ = 1;
+    d.resident_.assign(all.begin(), all.begin() + (ptrdiff_t)std::min(all.size(), (size_t)d.cache_len_));
+    hip_check(hipMemcpyAsync(d.pos_, &d.cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+
+std::vector<uint32_t> LlmModel::greedy_draft_loop(const std::vector<uint32_t>& prompt, const GenerateOptions& opt, const DraftSource& src,
+                                                  int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats)
+{
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
     ensure_lookup();
     begin_sequence(prompt);
+    drafter_begin(src, prompt);
+    StreamScope on_this_stream(src.drafter, stream_);
+    bool rounds_ran = false;
     std::vector<uint32_t> out;
     GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
     const std::vector<uint32_t>& all = run.all;
@@ -1989,10 +2066,11 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         // the cache whatever they accept while cache_len_ + steps * rows <= capacity; near the end the steps get narrower
         const int room = cache_cap_ - cache_len_;
         if (room <= 0) break;
-        const int rows = std::min(lk.draft_tokens + 1, room);
+        const int rows = std::min(draft_tokens + 1, room);
         const size_t steps = std::min(std::min(burst, (size_t)(room / rows)), run.max_new - out.size());
-        hipGraphExec_t exec = lookup_graph(rows, lk);
+        hipGraphExec_t exec = lookup_graph(rows, src);
         for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        rounds_ran = rounds_ran || steps > 0;
         hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
         hip_check(hipMemcpyAsync(toks.data(), lk_hist_ + known_n, steps * (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, stream_),
                   "D2H tokens");
@@ -2013,6 +2091,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
         cache_len_ = st.n - 1;
     }
     leave_resident(all);  // (`all` is a prefix of the device history: rows of rejected drafts and of picks past the end do not count)
+    drafter_leave(src, all, rounds_ran);
     return out;
 }
 
@@ -2032,8 +2111,9 @@ void LlmModel::ensure_lookup_sampled()
     ls_out_ = reinterpret_cast<uint8_t*>(dalloc(out_bytes / 4));
     hip_check(hipMemset(ls_out_, 0, out_bytes), "memset");
     ls_up_ = reinterpret_cast<int32_t*>(dalloc(16));
-    hip_check(hipHostMalloc((void**)&ls_host_, out_bytes + 16 * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
+    hip_check(hipHostMalloc((void**)&ls_host_, out_bytes + 32 * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
     ls_up_host_ = reinterpret_cast<int32_t*>(ls_host_ + out_bytes);
+    ls_draft_host_ = reinterpret_cast<uint32_t*>(ls_up_host_ + 16);
 }
 
 void LlmModel::rows_cut(float* logits, int rows, const GenerateOptions& opt)
@@ -2048,20 +2128,21 @@ void LlmModel::rows_cut(float* logits, int rows, const GenerateOptions& opt)
                                             headers, cands, kRowsCandCap, stream_), "rows cut");
 }
 
-void LlmModel::enqueue_verify_sampled(int rows, const LookupConfig& c, const GenerateOptions& opt, bool draft)
+void LlmModel::enqueue_verify_sampled(int rows, const DraftSource* src, const GenerateOptions& opt)
 {
-    if (draft) hip_check(launch_lookup_draft(lk_hist_, lk_state_, c.ngram_max, c.ngram_min, rows - 1, rows, vids_, stream_), "lookup draft");
+    if (src) enqueue_draft(rows, *src);
     pass(vids_, rows, true, true);
     rows_cut(vlogits_, rows, opt);
 }
 
-hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const LookupConfig& c, const GenerateOptions& opt)
+hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const DraftSource& c, const GenerateOptions& opt)
 {
     LookupSampledArgs want;
-    want.ngram_max = c.ngram_max; want.ngram_min = c.ngram_min;
+    want.ngram_max = c.ngram_max; want.ngram_min = c.ngram_min; want.serial = c.serial();
     want.top_k = opt.sampling.top_k; want.top_p = opt.sampling.top_p; want.min_p = opt.sampling.min_p; want.penalty = opt.repetition_penalty;
     const auto same = [](float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; };  // (bitwise: a NaN equals itself)
-    if (want.ngram_max != ls_args_.ngram_max || want.ngram_min != ls_args_.ngram_min || want.top_k != ls_args_.top_k ||
+    if (want.ngram_max != ls_args_.ngram_max || want.ngram_min != ls_args_.ngram_min || want.serial != ls_args_.serial ||
+        want.top_k != ls_args_.top_k ||
         !same(want.top_p, ls_args_.top_p) || !same(want.min_p, ls_args_.min_p) ||
         !same(want.penalty, ls_args_.penalty)) {  // (arguments of the captured launches)
         hip_check(hipStreamSynchronize(stream_), "sync");
@@ -2069,7 +2150,7 @@ hipGraphExec_t LlmModel::lookup_sampled_graph(int rows, const LookupConfig& c, c
         ls_args_ = want;
     }
     if (lookup_sampled_graphs_[rows]) return lookup_sampled_graphs_[rows];
-    return lookup_sampled_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify_sampled(rows, c, opt, true); });
+    return lookup_sampled_graphs_[rows] = capture_graph(stream_, [&] { enqueue_verify_sampled(rows, &c, opt); });
 }
 
 // One row's token from what the step's copy brought over (header + candidates of `row` in the pinned mirror); the row's
@@ -2114,8 +2195,7 @@ int LlmModel::verify_step_sampled(uint32_t token, const uint32_t* draft, int n_d
     hip_check(hipMemcpyAsync(vids_, ids, sizeof(uint32_t) * (size_t)rows, hipMemcpyHostToDevice, stream_), "H2D ids");
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     if (penalty) begin_token_history(samp_tokens_, history, n_history, samp_counts_, samp_distinct_, samp_ndistinct_);
-    LookupConfig c;
-    enqueue_verify_sampled(rows, c, opt, false);
+    enqueue_verify_sampled(rows, nullptr, opt);
     const size_t bytes = kLanes * sizeof(SampleHeader) + (size_t)rows * kSampleRowsChunk * sizeof(SampleCandidate);
     hip_check(hipMemcpyAsync(ls_host_, ls_out_, bytes, hipMemcpyDeviceToHost, stream_), "D2H candidates");
     hip_check(hipStreamSynchronize(stream_), "sync");
@@ -2142,12 +2222,24 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     check_lookup_config(lk);
     if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
     if (!opt.sample) return generate_lookup(prompt, opt, lk, on_token, stats);
+    DraftSource src;
+    src.ngram_max = lk.ngram_max;
+    src.ngram_min = lk.ngram_min;
+    return sampled_draft_loop(prompt, opt, src, lk.draft_tokens, on_token, stats);
+}
+
+std::vector<uint32_t> LlmModel::sampled_draft_loop(const std::vector<uint32_t>& prompt, const GenerateOptions& opt, const DraftSource& src,
+                                                   int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats)
+{
     if (!opt.uniform) throw std::runtime_error("sampling needs a uniform source");
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw InvalidConfig("prompt does not fit the context");
     ensure_lookup_sampled();
     begin_sequence(prompt);
+    drafter_begin(src, prompt);
+    StreamScope on_this_stream(src.drafter, stream_);
+    bool rounds_ran = false;
     const int vocab = cfg_.vocab;
     std::vector<uint32_t> out;
     GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
@@ -2182,8 +2274,8 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
         // as generate_lookup: a step of `rows` rows writes cache rows [pos, pos + rows); near the end of the cache the steps narrow
         const int room = cache_cap_ - cache_len_;
         if (room <= 0) break;
-        const int rows = std::min(lk.draft_tokens + 1, room);
-        hipGraphExec_t exec = lookup_sampled_graph(rows, lk, opt);
+        const int rows = std::min(draft_tokens + 1, room);
+        hipGraphExec_t exec = lookup_sampled_graph(rows, src, opt);
         ls_up_host_[0] = n_picks;
         for (int i = 0; i < n_picks; ++i) ls_up_host_[1 + i] = (int32_t)picks[i];
         hip_check(hipMemcpyAsync(ls_up_, ls_up_host_, 9 * sizeof(int32_t), hipMemcpyHostToDevice, stream_), "H2D picks");
@@ -2191,13 +2283,23 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
         if (penalty)
             hip_check(launch_token_counts(ls_up_ + 1, n_picks, vocab, samp_counts_, samp_distinct_, samp_ndistinct_, stream_), "token counts");
         hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        rounds_ran = true;
         hip_check(hipMemcpyAsync(ls_host_, ls_out_, head_bytes + (size_t)rows * kSampleRowsChunk * sizeof(SampleCandidate),
                                  hipMemcpyDeviceToHost, stream_), "D2H candidates");
+        if (src.drafter && rows > 1)  // a model's draft cannot be recomputed here: it comes back with the step's copy
+            hip_check(hipMemcpyAsync(ls_draft_host_, vids_, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H draft");
         hip_check(hipStreamSynchronize(stream_), "sync");
-        // the draft the device made, from the same rule on the host's copy of the history
-        LookupConfig hc = lk;
-        hc.draft_tokens = rows - 1;
-        const std::vector<uint32_t> draft = rows > 1 ? lookup_draft_host(all.data(), all.size(), hc) : std::vector<uint32_t>();
+        // the draft the device made: a drafter's as copied, the lookup rule's from the same rule on the host's copy of the history
+        std::vector<uint32_t> draft;
+        if (src.drafter) {
+            if (rows > 1) draft.assign(ls_draft_host_ + 1, ls_draft_host_ + rows);
+        } else if (rows > 1) {
+            LookupConfig hc;
+            hc.ngram_max = src.ngram_max;
+            hc.ngram_min = src.ngram_min;
+            hc.draft_tokens = rows - 1;
+            draft = lookup_draft_host(all.data(), all.size(), hc);
+        }
         const int m = (int)draft.size();
         int a = 0;
         n_picks = 0;
@@ -2213,7 +2315,88 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     cache_len_ = (int)all.size() - 1;
     hip_check(hipMemcpy(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
     leave_resident(all);
+    drafter_leave(src, all, rounds_ran);
     return out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Speculative decoding with a draft model (llm.h): the two loops above with a drafter as the draft source.
+
+void LlmModel::check_draft_pair(const LlmModel* drafter, int draft_tokens) const
+{
+    if (!drafter) throw InvalidConfig("draft must not be null");
+    if (drafter == this) throw InvalidConfig("draft must be another model than the decoder itself");
+    if (drafter->device_ != device_)
+        throw InvalidConfig("draft is on device " + std::to_string(drafter->device_) + ", the decoder on device " + std::to_string(device_));
+    if (drafter->cfg_.vocab != cfg_.vocab)
+        throw InvalidConfig("draft has a vocab of " + std::to_string(drafter->cfg_.vocab) + ", the decoder of " + std::to_string(cfg_.vocab));
+    if (drafter->cache_cap_ < cache_cap_)
+        throw InvalidConfig("draft has a context of " + std::to_string(drafter->cache_cap_) + " tokens, shorter than the decoder's " +
+                            std::to_string(cache_cap_));
+    if (draft_tokens < 1 || draft_tokens > kLookupMaxDraft) throw InvalidConfig("draft_tokens must be 1..7");
+}
+
+std::vector<uint32_t> LlmModel::generate_draft(LlmModel* drafter, const std::vector<uint32_t>& prompt, const GenerateOptions& opt,
+                                               int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats)
+{
+    if (stats) *stats = LookupStats();
+    check_draft_pair(drafter, draft_tokens);
+    if (prompt.empty()) throw InvalidConfig("prompt must not be empty");
+    if (prompt.size() > (size_t)cache_cap_)
+        throw InvalidConfig("prompt (" + std::to_string(prompt.size()) + " tokens) does not fit the context of " + std::to_string(cache_cap_) +
+                            " tokens");
+    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
+    DraftSource src;
+    src.drafter = drafter;
+    if (opt.sample) return sampled_draft_loop(prompt, opt, src, draft_tokens, on_token, stats);
+    return greedy_draft_loop(prompt, opt, src, draft_tokens, on_token, stats);
+}
+
+int LlmModel::draft_round(LlmModel* drafter, uint32_t token, int rows, uint32_t* draft_out, uint32_t* tokens_out, float* logits_out)
+{
+    if (rows < 2 || rows > kLanes) throw InvalidConfig("rows must be 2..8");
+    check_draft_pair(drafter, rows - 1);
+    const int len = cache_len_;
+    if (len < 1 || resident_.size() != (size_t)len)
+        throw InvalidConfig("the decoder's resident tokens must cover its cache of at least one row");
+    if (len + rows > cache_cap_)
+        throw InvalidConfig("cache_len + rows (" + std::to_string(len) + " + " + std::to_string(rows) + ") exceeds the context of " +
+                            std::to_string(cache_cap_) + " tokens");
+    if (drafter->cache_len_ < len - 1 || drafter->resident_.size() < (size_t)(len - 1) ||
+        !std::equal(resident_.begin(), resident_.begin() + (len - 1), drafter->resident_.begin()))
+        throw InvalidConfig("draft does not hold the decoder's tokens up to cache_len - 1");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ensure_lookup();
+    drafter->ensure_lookup();
+    StreamScope on_this_stream(drafter, stream_);
+    const int32_t tail[2] = {(int32_t)resident_[(size_t)len - 1], (int32_t)token};
+    LlmLookupState st = {};
+    st.n = len + 1;
+    hip_check(hipMemcpyAsync(lk_hist_ + (len - 1), tail, sizeof(tail), hipMemcpyHostToDevice, stream_), "H2D history");
+    hip_check(hipMemcpyAsync(lk_state_, &st, sizeof(st), hipMemcpyHostToDevice, stream_), "H2D lookup state");
+    hip_check(hipMemcpyAsync(pos_, &len, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
+    DraftSource src;
+    src.drafter = drafter;
+    enqueue_verify(rows, &src, false);
+    uint32_t ids[kLanes];
+    hip_check(hipMemcpyAsync(&st, lk_state_, sizeof(st), hipMemcpyDeviceToHost, stream_), "D2H lookup state");
+    hip_check(hipMemcpyAsync(ids, vids_, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, stream_), "D2H ids");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    const int a = st.a, m = rows - 1;
+    for (int i = 0; i < m; ++i) draft_out[i] = ids[1 + i];
+    for (int i = 0; i <= a; ++i) tokens_out[i] = (uint32_t)st.picks[i];
+    resident_.push_back(token);
+    for (int i = 0; i < a; ++i) resident_.push_back(tokens_out[i]);
+    cache_len_ = len + a + 1;
+    last_rows_ = rows;
+    // the drafter computed rows for T[len - 1], the token and drafts 1 .. m - 1: valid through draft min(a, m - 1)
+    drafter->cache_len_ = len + 1 + std::min(a, m - 1);
+    drafter->last_rows_ = 1;
+    drafter->resident_.assign(resident_.begin(), resident_.begin() + drafter->cache_len_);
+    hip_check(hipMemcpy(drafter->pos_, &drafter->cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
+    if (logits_out)
+        hip_check(hipMemcpy(logits_out, vlogits_, (size_t)rows * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+    return a;
 }
 
 // ---- embedding ----------------------------------------------------------------------------------------------------------------

@@ -106,6 +106,10 @@ public:
     const std::string& config_json() const { return config_json_; }  // config.json, or the config synthesized from GGUF metadata
     int context() const { return cache_cap_; }
     int cache_len() const { return cache_len_; }
+    int device() const { return device_; }
+    // A number no other model of this process has had (assigned at load, never reused): what a captured chain that holds another
+    // model's pointers is keyed by -- an address can come back after a free, a serial cannot.
+    uint64_t serial() const { return serial_; }
     // Prompt projections that ran the encoder's 128 x 128-tile GEMM since load (the other route is the 64 x 64 prompt kernel):
     // lets a test assert which route a geometry took.
     uint64_t tile_gemm_calls() const { return tile_gemm_calls_; }
@@ -288,6 +292,30 @@ public:
     int verify_step_sampled(uint32_t token, const uint32_t* draft, int n_draft, int rows, const GenerateOptions& options,
                             const uint32_t* history, size_t n_history, const float* uniforms, uint32_t* picks_out, int* draws_used,
                             float* logits_out);
+    // ---- speculative decoding with a draft model ---------------------------------------------------------------------------------
+    // generate_lookup() / generate_lookup_sampled() with the draft of every verify step coming from `drafter`, a second model on
+    // the same device with the same vocabulary and at least this model's context, instead of from the history.  One round on the
+    // history T[0, n) (T[n - 1] in neither cache): launch_draft_begin puts the drafter at position n - 2 with the ids T[n - 2],
+    // T[n - 1]; the drafter runs one 2-row pass (its argmax is draft 1) and rows - 2 single-row steps, each reading the id the
+    // one before it handed over (launch_draft_handoff); then the target's verify pass and the pick (greedy) or the rows penalty
+    // and the rows cut (sampled) run as in the lookup loops.  The drafter enqueues on this model's stream for the duration of the
+    // call (StreamScope), so a round is one linear chain, captured once per (row count, drafter serial, options).  Re-running row
+    // n - 2 keeps the launch shape fixed: after a round that accepted a of m drafts the drafter holds this model's rows, or one
+    // fewer when a == m.  Every emitted token is this model's own decision: the ids are generate()'s (greedy: wherever the two
+    // best logits are further apart than the float bar), whatever the drafter proposes.  Routing as generate_lookup_sampled:
+    // greedy with a penalty, or any n-gram ban, runs generate() unchanged (stats zero, the drafter untouched).  Throws
+    // InvalidConfig naming the argument, before any GPU work: drafter null / this model / on another device / another vocab / a
+    // shorter context, draft_tokens outside 1..7, an empty or over-long prompt.  Afterwards the drafter's cache_len() is this
+    // model's minus one (when a round ran) and its resident() the tokens of those rows.
+    std::vector<uint32_t> generate_draft(LlmModel* drafter, const std::vector<uint32_t>& prompt, const GenerateOptions& options,
+                                         int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats);
+    // Test hook: one greedy round of `rows` (2..8) rows on the two caches as they stand, `token` being the token that is in
+    // neither.  Needs resident() to cover this model's cache (>= 1 row) and the drafter to hold the same tokens up to
+    // cache_len() - 1.  draft_out[rows - 1]: the drafter's proposals; returns a, tokens_out[0..a] the picks; logits_out (may be
+    // null) receives the `rows` logits rows.  Both caches and resident lists advance as a loop's would.
+    int draft_round(LlmModel* drafter, uint32_t token, int rows, uint32_t* draft_out, uint32_t* tokens_out, float* logits_out);
+    // The refusals of generate_draft() that do not depend on the prompt.
+    void check_draft_pair(const LlmModel* drafter, int draft_tokens) const;
     // Projections of verify steps that took the multi-row weight-streaming kernel / fell back (counted when enqueued).
     uint64_t verify_stream_calls() const { return verify_stream_calls_; }
     uint64_t verify_fallback_calls() const { return verify_fallback_calls_; }
@@ -317,13 +345,38 @@ private:
     void pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);   // pass() for a GPT-2 layer stack
     void verify_gemv(const struct LlmGemvArgs& a, const char* what);
     void ensure_lookup();
-    void enqueue_verify(int rows, int ngram_max, int ngram_min, bool draft, bool record);  // [draft ->] step -> pick
-    hipGraphExec_t lookup_graph(int rows, const LookupConfig& config);
+    // Where the draft of a verify step comes from: the lookup rule on the history (drafter null), or a drafter model.
+    struct DraftSource {
+        LlmModel* drafter = nullptr;
+        int ngram_max = 1, ngram_min = 1;  // the lookup rule's bounds (not read with a drafter)
+        uint64_t serial() const { return drafter ? drafter->serial_ : 0; }
+    };
+    // For its lifetime `model` enqueues on `stream` instead of its own (which is synchronised first): how a drafter joins the
+    // target's chain without a second stream or an event inside a capture.
+    class StreamScope {
+    public:
+        StreamScope(LlmModel* model, hipStream_t stream);
+        ~StreamScope();
+        StreamScope(const StreamScope&) = delete;
+        StreamScope& operator=(const StreamScope&) = delete;
+    private:
+        LlmModel* model_;
+        hipStream_t saved_;
+    };
+    void enqueue_draft(int rows, const DraftSource& src);  // the ids of a verify block of `rows` rows into vids_, state->m
+    void enqueue_verify(int rows, const DraftSource* src, bool record);  // [draft ->] step -> pick (src null: the ids are there)
+    hipGraphExec_t lookup_graph(int rows, const DraftSource& src);
+    std::vector<uint32_t> greedy_draft_loop(const std::vector<uint32_t>& prompt, const GenerateOptions& options, const DraftSource& src,
+                                            int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats);
+    std::vector<uint32_t> sampled_draft_loop(const std::vector<uint32_t>& prompt, const GenerateOptions& options, const DraftSource& src,
+                                             int draft_tokens, const std::function<bool(uint32_t)>& on_token, LookupStats* stats);
+    void drafter_begin(const DraftSource& src, const std::vector<uint32_t>& prompt);  // the drafter's prompt rows (no-op without one)
+    void drafter_leave(const DraftSource& src, const std::vector<uint32_t>& all, bool rounds_ran);
     void ensure_sampling();        // the device state of sampled decoding and the logits processors
     void ensure_lookup_sampled();
     // [draft ->] verify pass -> rows penalty -> rows cut over `src` rows of stride vocab (the verify logits, or logits_ for one row)
-    void enqueue_verify_sampled(int rows, const LookupConfig& config, const GenerateOptions& options, bool draft);
-    hipGraphExec_t lookup_sampled_graph(int rows, const LookupConfig& config, const GenerateOptions& options);
+    void enqueue_verify_sampled(int rows, const DraftSource* src, const GenerateOptions& options);
+    hipGraphExec_t lookup_sampled_graph(int rows, const DraftSource& src, const GenerateOptions& options);
     void rows_cut(float* logits, int rows, const GenerateOptions& options);  // rows penalty + rows cut + the copy (no sync)
     uint32_t decide_row(const float* logits_dev, int row, const GenerateOptions& options, float uniform);
     // One row's sampled token.  header (null: the cut was not attempted) and cand(i), candidate i of the row, are what the
@@ -376,6 +429,7 @@ private:
     };
     LlmConfig cfg_;
     int device_ = 0;
+    uint64_t serial_ = 0;
     bool bf16_ = false, quant_ = false, gpt2_ = false;
     size_t weight_bytes_ = 0;
     uint64_t bytes_by_type_[32] = {};
@@ -455,6 +509,7 @@ private:
     int lk_hist_cap_ = 0;
     hipGraphExec_t lookup_graphs_[kLanes + 1] = {};
     int lookup_ngram_[2] = {0, 0};
+    uint64_t lookup_serial_ = 0;  // the drafter the captured chains hold (0: the lookup rule)
     uint64_t verify_stream_calls_ = 0, verify_fallback_calls_ = 0;
     // sampled prompt-lookup (allocated on first use): per-row scratch, [8 headers | the rows' candidate slots in chunks of 512]
     // and its pinned mirror (a step copies the headers and the first chunk of its rows in one piece), the upload of a step's
@@ -463,9 +518,11 @@ private:
     void* ls_scratch_ = nullptr;
     uint8_t *ls_out_ = nullptr, *ls_host_ = nullptr;
     int32_t *ls_up_ = nullptr, *ls_up_host_ = nullptr;
+    uint32_t* ls_draft_host_ = nullptr;  // pinned: the ids of a step's verify block (a drafter's proposals, read back with the step's copy)
     hipGraphExec_t lookup_sampled_graphs_[kLanes + 1] = {};
     struct LookupSampledArgs {
         int ngram_max = 0, ngram_min = 0;
+        uint64_t serial = 0;
         int64_t top_k = 0;
         float top_p = 0.0f, min_p = 0.0f, penalty = 0.0f;
     } ls_args_;

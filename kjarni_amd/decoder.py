@@ -412,6 +412,49 @@ class HipDecoder:
         lib().kjarni_hip_decoder_verify_gemv_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    # ---- speculative decoding with a draft model ----
+    def generate_draft(self, draft: "HipDecoder", prompt: Sequence[int], max_new_tokens: int, draft_tokens: int, sample: bool = False,
+                       temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                       min_p: Optional[float] = None, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0,
+                       stop_ids: Optional[Sequence[int]] = None, uniforms=None, seed: int = 0,
+                       on_token: Optional[Callable[[int], Optional[bool]]] = None):
+        """generate() / generate_sampled() with `draft`, a second HipDecoder on the same device with the same vocabulary,
+        proposing draft_tokens (1..7, required) tokens per verify step: (ids, stats).  Every emitted token is this decoder's
+        own decision, so the ids are the plain loop's for the same options and draws; the drafter only changes the speed.
+        Greedy with a penalty, or any n-gram ban, takes the plain loop (stats zero)."""
+        p = np.ascontiguousarray(prompt, np.uint32)
+        out = np.empty(max(max_new_tokens, 1), np.uint32)
+        n = C.c_size_t(0)
+        o, keep = self._sampling_options(max_new_tokens, sample, temperature, top_k, top_p, min_p, repetition_penalty, no_repeat_ngram,
+                                         stop_ids, uniforms, seed)
+        st = _ffi.KjarniHipLookupStats()
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_draft(self._h, draft._h if draft is not None else None, u32(p) if p.size else None,
+                                                            p.size, C.byref(o), int(draft_tokens), fn, None, u32(out), out.size,
+                                                            C.byref(n), C.byref(st)))
+        del keep
+        stats = {k: int(getattr(st, k)) for k, _ in _ffi.KjarniHipLookupStats._fields_}
+        return out[:min(n.value, out.size)].tolist(), stats
+
+    def draft_round(self, draft: "HipDecoder", token: int, rows: int, fetch: bool = True):
+        """Test hook: one greedy round of `rows` (2..8) rows on the two caches as they stand; `token` is in neither.  Returns
+        (proposals [rows - 1], picks, accepted, logits [rows, vocab] or None with fetch=False); this cache grows by
+        accepted + 1, the drafter's ends there or one row short (every proposal accepted)."""
+        rows = int(rows)
+        proposals = np.zeros(7, np.uint32)
+        picks = np.zeros(8, np.uint32)
+        a = C.c_int32(0)
+        logits = np.empty((max(rows, 1), self.vocab), np.float32) if fetch else None
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_draft_round(self._h, draft._h if draft is not None else None, int(token), rows, u32(proposals),
+                                                         u32(picks), C.byref(a),
+                                                         logits.ctypes.data_as(C.POINTER(C.c_float)) if fetch else None))
+        return proposals[:max(rows - 1, 0)].tolist(), picks[:a.value + 1].tolist(), int(a.value), logits
 
     # ---- scoring: per-token log-probabilities of a given sequence ----
     def score(self, ids: Sequence[int], first: int = 1):

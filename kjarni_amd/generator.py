@@ -106,6 +106,14 @@ class Generator:
         set_prompt_lookup() is 1..7 and the config has no n-gram ban; the text is the plain path's for the same seed."""
         check_error(lib().kjarni_hip_generator_set_prompt_lookup_sampling(self._handle, 1 if on else 0))
 
+    def set_draft_model(self, model_dir_or_gguf: Optional[str], draft_tokens: int = 0):
+        """A draft model for generate() / stream(): the checkpoint is loaded on this handle's device and owned by it, and
+        proposes draft_tokens (1..7) tokens per verify step; None / 0 frees it.  While set it takes precedence over prompt
+        lookup for greedy configs without processors and sampled configs without an n-gram ban; the text is the plain
+        path's for the same seed."""
+        path = model_dir_or_gguf.encode("utf-8") if model_dir_or_gguf else None
+        check_error(lib().kjarni_hip_generator_set_draft_model(self._handle, path, int(draft_tokens)))
+
     def set_prefix_reuse(self, on: bool):
         """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): score() over several
         continuations of one context prefills the context once, generate_batch() the prefix its prompts share."""

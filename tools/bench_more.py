@@ -33,6 +33,12 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            gpt2-small (bf16); ms per plain sampled step, ms per verify-and-cut step at 2 / 4 / 8 rows (HipDecoder.
            verify_step_sampled in a loop), the break-even acceptance, and tokens/s at both ends of acceptance (draws of 0 take
            token 0: everything drafted is accepted; seeded draws on a random-init model: next to nothing is).
+  llm_draft  (only on request) speculative decoding with a draft model (HipDecoder.generate_draft) on the Llama-3.2-1B shape (bf16)
+           as target, against plain generate() of the same build, alternated twice in one process: ms per round at 2 / 4 / 8
+           rows from the replayed chain, next to the target's plain step and to the verify step of the same row count plus
+           (rows - 1) drafter steps (what the chain is made of), the break-even accepted tokens per round, and end-to-end
+           tokens/s with a copy of the target as drafter (every draft accepted) and with an unrelated checkpoint; a 4-layer
+           drafter of the same width for the per-round cost only.  Ends of a range, not workloads.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1034,6 +1040,94 @@ def main():
         measure("gpt2-small shape, bf16 weights", dec, rng.integers(1, 50257, 128).tolist(), 512,
                 "bf16 weights, f32 activations/accumulate/KV", "gpt2")
         del dec
+
+    if "llm_draft" in which:
+        # Method (as llm_lookup): one process on one box; the Llama-3.2-1B shape (bf16, random init) as target, everything warmed
+        # first; plain generate() of the target -- the yardstick -- alternates with generate_lookup (the verify step of the same
+        # row count, replayed), the drafter's own plain generate() (its step) and generate_draft at 2 / 4 / 8 rows, twice.  A decode
+        # window is a whole generation minus the same call cut after its first token.  The round time does not depend on what is
+        # accepted; the end-to-end rows are the two ends random weights allow -- a copy of the target as drafter (every draft
+        # accepted: the ceiling) and an unrelated checkpoint (next to nothing accepted: the floor; what it accepts is in the
+        # line) -- ends of a range, not workloads.  A drafter of the same width with 4 layers gives the per-round cost of a
+        # cheaper drafter only.
+        rng = np.random.default_rng(0)
+        ROWS = (2, 4, 8)
+        n_new = int(os.environ.get("KJARNI_DRAFT_TOKENS", "256"))
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+        prompt = rng.integers(1000, 100000, 128).tolist()
+        d = os.path.join(tmp, "llama-1b-draft-target")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        d_other = os.path.join(tmp, "llama-1b-draft-other")
+        synth.llm_model(d_other, synth.LLAMA_1B, seed=1, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        d_shallow = os.path.join(tmp, "llama-1b-draft-shallow")
+        synth.llm_model(d_shallow, synth.LLAMA_1B, seed=2, store_bf16=True, max_position_embeddings=4096, eos_token_id=[], num_hidden_layers=4)
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        drafters = {"copy of the target": kjarni_amd.HipDecoder(d, max_context=2048),
+                    "unrelated checkpoint, same shape": kjarni_amd.HipDecoder(d_other, max_context=2048),
+                    "same width, 4 layers": kjarni_amd.HipDecoder(d_shallow, max_context=2048)}
+        dec.generate(prompt, 8)
+        for rows in ROWS:
+            dec.generate_lookup(prompt, 40, draft_tokens=rows - 1)
+        for drf in drafters.values():
+            drf.generate(prompt, 8)
+            for rows in ROWS:
+                dec.generate_draft(drf, prompt, 40, rows - 1)
+        plain_ms, plain_rate, verify_ms = [], [], {r: [] for r in ROWS}
+        step_ms = {k: [] for k in drafters}
+        round_ms = {k: {r: [] for r in ROWS} for k in drafters}
+        e2e = {k: {r: [] for r in ROWS} for k in drafters}
+        for rep in range(2):
+            dt, out = window(lambda: dec.generate(prompt, n_new), lambda: dec.generate(prompt, 1))
+            assert len(out) == n_new
+            plain_ms.append(dt * 1e3 / (n_new - 1))
+            plain_rate.append((n_new - 1) / dt)
+            for rows in ROWS:
+                dt, (got, st) = window(lambda: dec.generate_lookup(prompt, n_new, draft_tokens=rows - 1),
+                                       lambda: dec.generate_lookup(prompt, 1, draft_tokens=rows - 1))
+                verify_ms[rows].append(dt * 1e3 / (st["verify_steps"] + st["single_row_steps"]))
+            for name, drf in drafters.items():
+                dt, dout = window(lambda: drf.generate(prompt, n_new), lambda: drf.generate(prompt, 1))
+                step_ms[name].append(dt * 1e3 / (n_new - 1))
+                for rows in ROWS:
+                    dt, (got, st) = window(lambda: dec.generate_draft(drf, prompt, n_new, rows - 1),
+                                           lambda: dec.generate_draft(drf, prompt, 1, rows - 1))
+                    assert len(got) == n_new
+                    rounds = st["verify_steps"] + st["single_row_steps"]
+                    round_ms[name][rows].append(dt * 1e3 / rounds)
+                    e2e[name][rows].append({"tokens_per_s": round((n_new - 1) / dt, 1), "rounds": rounds, "drafted": st["drafted_tokens"],
+                                            "accepted": st["accepted_tokens"], "ids_equal_plain": got == out})
+        plain = med(plain_ms)
+        for name in drafters:
+            parts = {r: med(verify_ms[r]) + (r - 1) * med(step_ms[name]) for r in ROWS}   # (b): what the chain is made of
+            emit({"metric": f"draft-model decoding, Llama-3.2-1B shape target, drafter: {name}", "unit": "ms per round",
+                  "value": round(med(round_ms[name][8]), 4), "n_gpus": 1, "dtype": "bf16 weights, f32 activations/accumulate/KV",
+                  "data": "synthetic",
+                  "config": {"workload": f"random init, one 128-token prompt, {n_new} generated tokens; plain generate(), generate_lookup, the "
+                                         "drafter's generate() and generate_draft at 2 / 4 / 8 rows alternated twice in one process",
+                             "note": "the end-to-end rows are ends of a range (what a random-init drafter happens to accept), not workloads; "
+                                     "the round time does not depend on the acceptance"},
+                  "plain_ms_per_step": {"median": round(plain, 4), "runs": [round(x, 4) for x in plain_ms]},
+                  "plain_tokens_per_s": round(med(plain_rate), 1),
+                  "drafter_ms_per_step": {"median": round(med(step_ms[name]), 4), "runs": [round(x, 4) for x in step_ms[name]]},
+                  "verify_ms_per_step_replayed": {str(r): [round(x, 4) for x in verify_ms[r]] for r in ROWS},
+                  "round_ms_replayed": {str(r): [round(x, 4) for x in round_ms[name][r]] for r in ROWS},
+                  "round_over_plain": {str(r): round(med(round_ms[name][r]) / plain, 3) for r in ROWS},
+                  "verify_plus_drafter_steps_ms": {str(r): round(parts[r], 4) for r in ROWS},
+                  "round_over_verify_plus_drafter_steps": {str(r): round(med(round_ms[name][r]) / parts[r], 3) for r in ROWS},
+                  "break_even_accepted_per_round": {str(r): round(med(round_ms[name][r]) / plain - 1, 3) for r in ROWS},
+                  "generate_draft": {str(r): e2e[name][r] for r in ROWS},
+                  "x_plain_tokens_per_s": {str(r): round(max(x["tokens_per_s"] for x in e2e[name][r]) / med(plain_rate), 2) for r in ROWS},
+                  "weight_bytes": dec.weight_bytes, "drafter_weight_bytes": drafters[name].weight_bytes})
+        del dec, drafters
 
     if "llm_score" in which:
         # Method (measuring guide, section 5; as llm_lookup): one process on one box; forward() -- the yardstick --, score() on
