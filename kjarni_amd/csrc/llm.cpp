@@ -654,33 +654,57 @@ void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, boo
     hip_check(launch_qgemv(a, stream_), what);
 }
 
+namespace {
+
+bool q6(const QMat& m) { return m.type == GGML_Q6_K; }
+
+}  // namespace
+
+void LlmModel::quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what)
+{
+    a.k = k; a.rows = n;
+    if (!q8k) {
+        a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = cfg_.eps;
+        return;
+    }
+    hip_check(launch_qprep(X, ldx, n, k, gamma, cfg_.eps, gamma ? xn_ : nullptr, xq_, xd_, stream_), what);
+    a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
+}
+
+void LlmModel::quant_finish(int n, const Layer& L)
+{
+    hipStream_t s = stream_;
+    const int H = cfg_.hidden, I = cfg_.inter;
+    QFusedArgs o;
+    quant_source(o, n, ctx_, H, H, nullptr, q6(L.o), "q8k o");
+    o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
+    hip_check(launch_qfused(o, s), "o proj");
+    QFusedArgs g;
+    g.mode = QF_SWIGLU;
+    quant_source(g, n, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
+    g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
+    hip_check(launch_qfused(g, s), "norm + gate/up");
+    QFusedArgs dn;
+    quant_source(dn, n, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
+    dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
+    hip_check(launch_qfused(dn, s), "down proj");
+}
+
 // pass() for a checkpoint whose matrices stay quantized: the same stages and formulas, five fused launches per layer
-// (quant_kernels.hip): RMSNorm + Q|K|V (per-segment types) + RoPE + cache write, attention, o-proj + residual, RMSNorm +
-// gate/up + SwiGLU, down + residual.  A stage whose input feeds a Q6_K linear first runs one qprep launch (RMSNorm where the
-// stage has one + the Q8_K codes, shared by every matrix of the stage).
+// (quant_kernels.hip): RMSNorm + Q|K|V (per-segment types) + RoPE + cache write, attention, then quant_finish(): o-proj +
+// residual, RMSNorm + gate/up + SwiGLU, down + residual.  A stage whose input feeds a Q6_K linear first runs one qprep launch
+// (quant_source(): RMSNorm where the stage has one + the Q8_K codes, shared by every matrix of the stage).
 void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d;
     const int* pp = device_pos ? pos_ : nullptr;
-    // the activation source of a stage: rows X (normalised by gamma inside the GEMV), or -- when a Q6_K linear reads them --
-    // one qprep launch writing the normalised rows and their Q8_K codes
-    auto source = [&](QFusedArgs& a, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what) {
-        a.k = k; a.rows = n;
-        if (!q8k) {
-            a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = c.eps;
-            return;
-        }
-        hip_check(launch_qprep(X, ldx, n, k, gamma, c.eps, gamma ? xn_ : nullptr, xq_, xd_, s), what);
-        a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
-    };
-    auto q6 = [](const QMat& m) { return m.type == GGML_Q6_K; };
     hip_check(launch_qembed(ids_dev, n, qembed_, h_, s), "embed");
     for (const Layer& L : layers_) {
         QFusedArgs qkv;
         qkv.mode = QF_QKV;
-        source(qkv, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
+        quant_source(qkv, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
         qkv.W[0] = L.q; qkv.W[1] = L.k; qkv.W[2] = L.v;
         qkv.seg_jobs[0] = H / 2; qkv.seg_jobs[1] = kv / 2; qkv.seg_jobs[2] = kv / 2;
         qkv.jobs = H / 2 + kv;
@@ -691,19 +715,7 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool 
         hip_check(launch_qfused(qkv, s), "norm + qkv + rope");
         hip_check(launch_decode_attention(q_, H, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
                                           splits_, att_scratch_, ctx_, H, s, c.heads / c.kv_heads), "attention");
-        QFusedArgs o;
-        source(o, ctx_, H, H, nullptr, q6(L.o), "q8k o");
-        o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
-        hip_check(launch_qfused(o, s), "o proj");
-        QFusedArgs g;
-        g.mode = QF_SWIGLU;
-        source(g, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
-        g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
-        hip_check(launch_qfused(g, s), "norm + gate/up");
-        QFusedArgs dn;
-        source(dn, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
-        dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
-        hip_check(launch_qfused(dn, s), "down proj");
+        quant_finish(n, L);
     }
     hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
     if (verify) qlinear(qhead_, last_, H, n, head_q8k_, vlogits_, c.vocab, "lm head");  // every row's logits (the quantized kernels take <= 8 rows as they are)
@@ -789,39 +801,62 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
                   what);
 }
 
-// Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer RMSNorm ->
-// Q, K, V projections (K and V rows land in the cache) -> RoPE -> causal attention over the cache -> o-proj + residual
-// -> RMSNorm -> gate, up -> silu(gate) * up -> down-proj + residual; same formulas as pass().  After the last layer the
-// final norm runs on the last (n - 1) % 8 + 1 rows (what last_hidden() exposes) and the lm head on the last row.
+// The first half of a rows-route layer: RMSNorm (GPT-2: LayerNorm) of ph_ into pn_, then the Q, K and V projections out of the
+// fused Q|K|V matrix (quantized checkpoints: three matrices of their own), Q into pq_, K and V into the rows given.
+void LlmModel::rows_qkv(int m, const Layer& L, float* k_rows, float* v_rows)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, kv = c.kv_heads * c.head_dim, QD = c.q_dim();
+    const size_t wsz = bf16_ ? 2 : 4;
+    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
+    if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
+    else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
+    prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
+    prompt_proj(m, pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, k_rows, kv, kv, H, nullptr,
+                "k proj", quant_ ? &L.k : nullptr);
+    prompt_proj(m, pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, v_rows, kv, kv, H,
+                nullptr, "v proj", quant_ ? &L.v : nullptr);
+}
+
+// The second half, behind the attention's context rows in pctx_: o-proj + residual -> RMSNorm -> gate, up -> silu(gate) * up ->
+// down-proj + residual (GPT-2: LayerNorm -> c_fc + GELU -> mlp.c_proj + residual), the hidden states staying in ph_.
+void LlmModel::rows_finish(int m, const Layer& L)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, I = c.inter, QD = c.q_dim();
+    prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj", quant_ ? &L.o : nullptr);
+    if (gpt2_) {
+        hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
+        prompt_proj(m, pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
+        prompt_proj(m, pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
+        return;
+    }
+    hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
+    prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", quant_ ? &L.gate_q : nullptr);
+    prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
+    prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
+}
+
+// Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer rows_qkv() (K and V
+// rows land in the cache) -> RoPE -> causal attention over the cache -> rows_finish(); same formulas as pass().  After the last
+// layer the final norm runs on the last (n - 1) % 8 + 1 rows (what last_hidden() exposes) and the lm head on the last row.
 void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int score_base)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     const int wb = bf16_ ? 1 : 0;
     ensure_prompt_workspace();
-    const size_t wsz = bf16_ ? 2 : 4;
-    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
     for (int done = 0; done < n; done += prefill_cap_) {
         const int m = std::min(prefill_cap_, n - done);
         hip_check(hipMemcpyAsync(pids_, ids_host + done, (size_t)m * 4, hipMemcpyHostToDevice, s), "H2D ids");
         if (quant_) hip_check(launch_qembed(pids_, m, qembed_, ph_, s), "embed");
         else if (gpt2_) hip_check(launch_llm_embed_pos(pids_, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, cache_len_, nullptr, ph_, s), "embed");
         else hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
-        auto proj = [&](const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                        float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false) {
-            prompt_proj(m, Ain, lda, W, bias, R, Y, ldy, N, K, gate, what, qm, gelu);
-        };
         for (const Layer& L : layers_) {
-            float* k_rows = L.k_cache + (size_t)cache_len_ * kv;
-            float* v_rows = L.v_cache + (size_t)cache_len_ * kv;
-            if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
-            else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-            proj(pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
-            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, k_rows, kv, kv, H, nullptr, "k proj",
-                 quant_ ? &L.k : nullptr);
-            proj(pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, v_rows, kv, kv, H,
-                 nullptr, "v proj", quant_ ? &L.v : nullptr);
+            rows_qkv(m, L, L.k_cache + (size_t)cache_len_ * kv, L.v_cache + (size_t)cache_len_ * kv);
             if (c.qwen3()) {  // head norm + rotation over the chunk's Q rows and its K rows in the cache
                 hip_check(launch_qk_norm_rope(pq_, QD, L.k_cache, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_,
                                               nullptr, 1, s), "qk norm + rope");
@@ -840,17 +875,7 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
                                                       c.heads / c.kv_heads), "attention");
                 }
             }
-            proj(pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj", quant_ ? &L.o : nullptr);
-            if (gpt2_) {
-                hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
-                proj(pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
-                proj(pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
-                continue;
-            }
-            hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
-            proj(pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", quant_ ? &L.gate_q : nullptr);
-            proj(pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
-            proj(pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
+            rows_finish(m, L);
         }
         if (score) {  // the chunk's rows whose successor is scored: final norm into the (now free) norm buffer, then the head
             const int at = score_base + done;  // the chunk's first position in the scored sequence
@@ -881,6 +906,28 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
     }
 }
 
+namespace {
+
+// The two geometry rules of the rows route.  forward() takes it for widths the prompt GEMM tiles and any even head_dim (other
+// shapes run pass() 8 rows at a time); the packed entry points have no such fallback, and their attention kernels exist for
+// four head dims.
+bool rows_geometry(const LlmConfig& c)
+{
+    return c.hidden % 32 == 0 && c.q_dim() % 32 == 0 && c.inter % 32 == 0 && (c.kv_heads * c.head_dim) % 4 == 0 && c.head_dim % 2 == 0;
+}
+bool packed_geometry(const LlmConfig& c)
+{
+    const int d = c.head_dim;
+    return c.hidden % 32 == 0 && c.q_dim() % 32 == 0 && c.inter % 32 == 0 && (c.kv_heads * d) % 4 == 0 &&
+           (d == 16 || d == 32 || d == 64 || d == 128);
+}
+std::string packed_geometry_refusal(const char* entry)
+{
+    return std::string(entry) + ": hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128";
+}
+
+}  // namespace
+
 void LlmModel::forward(const uint32_t* ids, int n) { forward_rows(ids, n, false); }
 
 void LlmModel::forward_rows(const uint32_t* ids, int n, bool score, int score_base)
@@ -890,8 +937,7 @@ void LlmModel::forward_rows(const uint32_t* ids, int n, bool score, int score_ba
     if (cache_len_ + n > cache_cap_) throw std::runtime_error("context is full");
     const bool tracked = resident_.size() == (size_t)cache_len_;  // (else: untracked rows lie between; resident_ stays a prefix)
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
-    const int kvd = cfg_.kv_heads * cfg_.head_dim;
-    if (n >= kMinGemmRows && cfg_.hidden % 32 == 0 && cfg_.q_dim() % 32 == 0 && cfg_.inter % 32 == 0 && kvd % 4 == 0 && cfg_.head_dim % 2 == 0) {
+    if (n >= kMinGemmRows && rows_geometry(cfg_)) {
         prefill_rows(ids, n, score, score_base);
     } else {
         for (int i = 0; i < n; i += 8) {
@@ -939,26 +985,32 @@ void LlmModel::ensure_score_topk()
 
 void LlmModel::score_head_rows(const float* Xn, int lo, int cnt)
 {
-    const LlmConfig& c = cfg_;
-    const int H = c.hidden, out = lo + 1 - score_first_;
-    const uint32_t* tgt = score_tgt_ + lo;
+    const int out = lo + 1 - score_first_;
     const size_t kout = (size_t)out * score_k_;  // the rows' first slot in the top-k outputs
+    if (score_k_ > 0) score_head(Xn, cnt, score_tgt_ + lo, score_k_, score_lp_ + out, score_tk_ids_ + kout, score_tk_lp_ + kout);
+    else score_head(Xn, cnt, score_tgt_ + lo, 0, score_lp_ + out, score_top_ + out, score_tlp_ + out);
+}
+
+void LlmModel::score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, float* lp, uint32_t* ids, float* tlp)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden;
     if (score_fused_ && !quant_ && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
-        if (score_k_ > 0) {
-            if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, score_k_) > score_tk_scratch_bytes_)
-                throw std::runtime_error("score_topk: slab scratch too small");
-            hip_check(launch_score_head_topk(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_k_, score_tk_scratch_, score_lp_ + out,
-                                             score_tk_ids_ + kout, score_tk_lp_ + kout, nullptr, stream_), "score head top-k");
-            ++score_fused_calls_;
-            return;
+        if (k > 0) {
+            if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, k) > score_tk_scratch_bytes_)
+                throw std::runtime_error("score head: top-k slab scratch too small");
+            hip_check(launch_score_head_topk(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, k, score_tk_scratch_, lp, ids, tlp, nullptr,
+                                             stream_), "score head top-k");
+        } else {
+            if (score_head_scratch_bytes(cnt, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score head: slab scratch too small");
+            hip_check(launch_score_head(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, lp, ids, tlp, nullptr, stream_),
+                      "score head");
         }
-        if (score_head_scratch_bytes(cnt, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score: slab scratch too small");
-        hip_check(launch_score_head(Xn, H, cnt, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, score_lp_ + out, score_top_ + out,
-                                    score_tlp_ + out, nullptr, stream_), "score head");
         ++score_fused_calls_;
         return;
     }
     ensure_lookup();  // vlogits_: the verify step's 8 logits rows
+    const size_t slots = k > 0 ? (size_t)k : 1;  // per row in ids / tlp
     for (int r = 0; r < cnt; r += 8) {
         const int rows = std::min(8, cnt - r);
         if (quant_) {
@@ -969,13 +1021,12 @@ void LlmModel::score_head_rows(const float* Xn, int lo, int cnt)
             lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
             hip_check(launch_llm_gemv(lm, stream_), "lm head");
         }
-        if (score_k_ > 0)
-            hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_k_, score_lp_ + out + r,
-                                             score_tk_ids_ + kout + (size_t)r * score_k_, score_tk_lp_ + kout + (size_t)r * score_k_, nullptr,
+        if (k > 0)
+            hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, k, lp + r, ids + r * slots, tlp + r * slots, nullptr,
                                              stream_), "score rows top-k");
         else
-            hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, score_lp_ + out + r, score_top_ + out + r,
-                                        score_tlp_ + out + r, nullptr, stream_), "score rows");
+            hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, lp + r, ids + r * slots, tlp + r * slots, nullptr, stream_),
+                      "score rows");
         ++score_rows_calls_;
     }
 }
@@ -1479,22 +1530,12 @@ void LlmModel::lane_step(int n)
     if (quant_) hip_check(launch_qembed(toks, n, qembed_, h_, s), "embed");
     else if (gpt2_) hip_check(launch_llm_embed_pos(toks, n, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, h_, s, st->pos), "embed");
     else hip_check(launch_llm_embed(toks, n, H, c.vocab, embed_, wb, h_, s), "embed");
-    auto q6 = [](const QMat& m) { return m.type == GGML_Q6_K; };
-    auto qsource = [&](QFusedArgs& a, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what) {  // as pass_quant
-        a.k = k; a.rows = n;
-        if (!q8k) {
-            a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = c.eps;
-            return;
-        }
-        hip_check(launch_qprep(X, ldx, n, k, gamma, c.eps, gamma ? xn_ : nullptr, xq_, xd_, s), what);
-        a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
-    };
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
         if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
             QFusedArgs a;
             a.mode = QF_PLAIN;
-            qsource(a, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
+            quant_source(a, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
             a.W[0] = L.q; a.W[1] = L.k; a.W[2] = L.v;
             a.seg_jobs[0] = H / 2; a.seg_jobs[1] = kv / 2; a.seg_jobs[2] = kv / 2;
             a.jobs = H / 2 + kv;
@@ -1517,19 +1558,7 @@ void LlmModel::lane_step(int n)
         hip_check(launch_decode_attention(lane_qkv_, ldq, n, lane_k_[li], kv, lane_v_[li], kv, lane_cap_, nullptr, lane_cap_, c.heads, d, -1,
                                           splits_, att_scratch_, ctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
         if (quant_) {
-            QFusedArgs o;
-            qsource(o, ctx_, H, H, nullptr, q6(L.o), "q8k o");
-            o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
-            hip_check(launch_qfused(o, s), "o proj");
-            QFusedArgs g;
-            g.mode = QF_SWIGLU;
-            qsource(g, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
-            g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
-            hip_check(launch_qfused(g, s), "norm + gate/up");
-            QFusedArgs dn;
-            qsource(dn, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
-            dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
-            hip_check(launch_qfused(dn, s), "down proj");
+            quant_finish(n, L);
             continue;
         }
         LlmGemvArgs o;
@@ -2431,6 +2460,33 @@ namespace {
 // most m blocks in the vec and in the prefix table (a block has at least one row of its own) of 3 and 5 words.
 constexpr size_t kPackedMetaWords = 4 * (size_t)kEmbedChunkRows + 3 * (size_t)kEmbedChunkRows + 3 * 32 + 5 * (size_t)kEmbedChunkRows + 8;
 
+// The sequences of a packed call, b = ids[offsets[b], offsets[b + 1]): InvalidConfig naming the argument and the sequence for
+// B < 0, decreasing offsets, a sequence shorter than min_len (1 or 2) or longer than `limit`, and an id >= vocab (ids null: not
+// checked).  `noun` is the entry's word in the messages: embed, score or answer.
+void check_packed_sequences(const char* noun, const uint32_t* ids, const int32_t* offsets, int B, int min_len, int limit, int vocab)
+{
+    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    if (B == 0) return;
+    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
+        const std::string seq = " (sequence " + std::to_string(b) + ")";
+        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
+                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
+        if (len == 0 && min_len == 1)
+            throw InvalidConfig("offsets[" + std::to_string(b) + "] == offsets[" + std::to_string(b + 1) + "]: an empty sequence" + seq);
+        if (len < min_len)  // (score's own words say why)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens are fewer than " + std::to_string(min_len) +
+                                (std::strcmp(noun, "score") == 0 ? ": a scored token needs a prefix" : "") + seq);
+        if (len > limit)
+            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the " + noun + " length limit of " + std::to_string(limit) + seq);
+        for (int32_t i = offsets[b]; ids && i < offsets[b + 1]; ++i)
+            if (ids[i] >= (uint32_t)vocab)
+                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
+                                    std::to_string(vocab) + seq);
+    }
+}
+
 }  // namespace
 
 void LlmModel::ensure_packed_scratch()
@@ -2443,23 +2499,42 @@ void LlmModel::ensure_packed_scratch()
     hip_check(hipHostMalloc((void**)&emeta_host_, kPackedMetaWords * sizeof(int32_t), hipHostMallocDefault), "hipHostMalloc");
 }
 
+LlmModel::PackedMeta LlmModel::upload_packed_meta(const char* entry, int m, const uint32_t* ids, const int32_t* row_tok, const int32_t* row_pos,
+                                                  const void* extra_a, size_t n_a, const void* extra_b, size_t n_b,
+                                                  const std::vector<EmbedBlock>& vec, const std::vector<EmbedBlock>& mfma,
+                                                  const std::vector<PrefixBlock>& prefix)
+{
+    const size_t o_pos = (size_t)m, o_a = o_pos + (size_t)m, o_b = o_a + n_a, o_vec = o_b + n_b, o_mfma = o_vec + 3 * vec.size();
+    const size_t o_pre = o_mfma + 3 * mfma.size(), words = o_pre + 5 * prefix.size();
+    static_assert(sizeof(EmbedBlock) == 3 * sizeof(int32_t) && sizeof(PrefixBlock) == 5 * sizeof(int32_t), "the block tables' words");
+    if (words > kPackedMetaWords) throw std::runtime_error(std::string(entry) + ": chunk metadata exceeds its buffer");
+    int32_t* hm = emeta_host_;
+    if (row_tok)
+        for (int r = 0; r < m; ++r) hm[r] = (int32_t)ids[row_tok[r]];
+    else std::memcpy(hm, ids, (size_t)m * 4);
+    std::memcpy(hm + o_pos, row_pos, (size_t)m * 4);
+    if (n_a) std::memcpy(hm + o_a, extra_a, n_a * 4);
+    if (n_b) std::memcpy(hm + o_b, extra_b, n_b * 4);
+    if (!vec.empty()) std::memcpy(hm + o_vec, vec.data(), vec.size() * sizeof(EmbedBlock));
+    if (!mfma.empty()) std::memcpy(hm + o_mfma, mfma.data(), mfma.size() * sizeof(EmbedBlock));
+    if (!prefix.empty()) std::memcpy(hm + o_pre, prefix.data(), prefix.size() * sizeof(PrefixBlock));
+    hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, stream_), "H2D chunk");
+    return PackedMeta{reinterpret_cast<const uint32_t*>(emeta_), emeta_ + o_pos, emeta_ + o_a, emeta_ + o_b,
+                      reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec), reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma),
+                      reinterpret_cast<const PrefixBlock*>(emeta_ + o_pre)};
+}
+
 void LlmModel::packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_pos, const EmbedBlock* vec, int nv, const EmbedBlock* mfma,
                              int nm, const PrefixBlock* prefix, int np)
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     hipStream_t s = stream_;
     const int wb = bf16_ ? 1 : 0;
-    const size_t wsz = bf16_ ? 2 : 4;
-    auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
     if (gpt2_) hip_check(launch_llm_embed_pos(ids_dev, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, ph_, s, row_pos), "embed");
     else hip_check(launch_llm_embed(ids_dev, m, H, c.vocab, embed_, wb, ph_, s), "embed");
     for (const Layer& L : layers_) {
-        if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
-        else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-        prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj");
-        prompt_proj(m, pn_, H, at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, ek_, kv, kv, H, nullptr, "k proj");
-        prompt_proj(m, pn_, H, at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, ev_, kv, kv, H, nullptr, "v proj");
+        rows_qkv(m, L, ek_, ev_);
         if (c.qwen3()) {
             hip_check(launch_qk_norm_rope_rows(pq_, QD, ek_, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, row_pos, s),
                       "qk norm + rope");
@@ -2471,77 +2546,42 @@ void LlmModel::packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_
                   "packed attention");
         hip_check(launch_packed_prefix_attention(pq_, QD, ek_, kv, ev_, kv, prefix, np, c.heads, d, c.heads / c.kv_heads, pctx_, QD, s),
                   "packed prefix attention");
-        prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj");
-        if (gpt2_) {
-            hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
-            prompt_proj(m, pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
-            prompt_proj(m, pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
-            continue;
-        }
-        hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
-        prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate");
-        prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu");
-        prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj");
+        rows_finish(m, L);
     }
 }
 
 void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, bool normalize, float* out)
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
+    const int H = c.hidden;
     if (gpt2_) throw InvalidConfig("embed: GPT-2 has no RMSNorm layer stack and is no embedding family");
     if (quant_) throw InvalidConfig("embed: quantized checkpoints are not supported");
-    if (H % 32 || QD % 32 || I % 32 || kv % 4 || !(d == 16 || d == 32 || d == 64 || d == 128))
-        throw InvalidConfig("embed: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
-    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    if (!packed_geometry(c)) throw InvalidConfig(packed_geometry_refusal("embed"));
+    check_packed_sequences("embed", ids, offsets, B, 1, embed_max_tokens(), c.vocab);
     if (B == 0) return;
-    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
-    const int limit = embed_max_tokens();
     std::vector<int32_t> lengths((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
-        const std::string seq = " (sequence " + std::to_string(b) + ")";
-        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
-                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
-        if (len == 0) throw InvalidConfig("offsets[" + std::to_string(b) + "] == offsets[" + std::to_string(b + 1) + "]: an empty sequence" + seq);
-        if (len > limit)
-            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the embed length limit of " + std::to_string(limit) + seq);
-        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
-            if (ids[i] >= (uint32_t)c.vocab)
-                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
-                                    std::to_string(c.vocab) + seq);
-        lengths[(size_t)b] = (int32_t)len;
-    }
-    const std::vector<EmbedChunk> chunks = embed_plan_host(lengths.data(), B, d);
+    for (int b = 0; b < B; ++b) lengths[(size_t)b] = offsets[b + 1] - offsets[b];
+    const std::vector<EmbedChunk> chunks = embed_plan_host(lengths.data(), B, c.head_dim);
 
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hipStream_t s = stream_;
     ensure_prompt_workspace();
     ensure_packed_scratch();
+    std::vector<int32_t> row_pos, seq_start;
     for (const EmbedChunk& ch : chunks) {
-        const int m = ch.rows, n = ch.n_seq, nv = (int)ch.vec.size(), nm = (int)ch.mfma.size();
-        const size_t o_pos = (size_t)m, o_start = o_pos + (size_t)m, o_vec = o_start + (size_t)n + 1, o_mfma = o_vec + 3 * (size_t)nv;
-        const size_t words = o_mfma + 3 * (size_t)nm;
-        if (words > kPackedMetaWords) throw std::runtime_error("embed: chunk metadata exceeds its buffer");
-        int32_t* hm = emeta_host_;
-        std::memcpy(hm, ids + offsets[ch.first_seq], (size_t)m * 4);
-        int row = 0;
+        const int m = ch.rows, n = ch.n_seq;
+        row_pos.clear();
+        seq_start.clear();
         for (int j = 0; j < n; ++j) {
-            hm[o_start + (size_t)j] = row;
-            const int len = lengths[(size_t)(ch.first_seq + j)];
-            for (int t = 0; t < len; ++t) hm[o_pos + (size_t)row++] = t;
+            seq_start.push_back((int32_t)row_pos.size());
+            for (int t = 0; t < lengths[(size_t)(ch.first_seq + j)]; ++t) row_pos.push_back(t);
         }
-        hm[o_start + (size_t)n] = row;
-        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
-        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
-        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
-        const uint32_t* ids_dev = reinterpret_cast<const uint32_t*>(emeta_);
-        const int32_t *row_pos = emeta_ + o_pos, *seq_start = emeta_ + o_start;
-        const EmbedBlock* vec = reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec);
-        const EmbedBlock* mfma = reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma);
-        packed_layers(m, ids_dev, row_pos, vec, nv, mfma, nm, nullptr, 0);
+        seq_start.push_back((int32_t)row_pos.size());
+        const PackedMeta meta = upload_packed_meta("embed", m, ids + offsets[ch.first_seq], nullptr, row_pos.data(), seq_start.data(),
+                                                   seq_start.size(), nullptr, 0, ch.vec, ch.mfma, {});
+        packed_layers(m, meta.ids, meta.row_pos, meta.vec, (int)ch.vec.size(), meta.mfma, (int)ch.mfma.size(), nullptr, 0);
         // (the norm buffer is free after the last layer: the pooled rows land there)
-        hip_check(launch_last_token_pool(ph_, H, seq_start, n, H, final_norm_, c.eps, normalize ? 1 : 0, pn_, s), "last-token pool");
+        hip_check(launch_last_token_pool(ph_, H, meta.extra_a, n, H, final_norm_, c.eps, normalize ? 1 : 0, pn_, s), "last-token pool");
         hip_check(hipMemcpyAsync(out + (size_t)ch.first_seq * H, pn_, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, s), "D2H embeddings");
         hip_check(hipStreamSynchronize(s), "sync");  // the staging copy and the activations are reused by the next chunk
     }
@@ -2551,24 +2591,14 @@ void LlmModel::embed_batch(const uint32_t* ids, const int32_t* offsets, int B, b
 
 namespace {
 
-// offsets / firsts of score_plan_host and score_batch: InvalidConfig naming the argument and the sequence
-void check_score_sequences(const int32_t* offsets, const int32_t* firsts, int B, int limit)
+// firsts of score_plan_host and score_batch, behind check_packed_sequences: InvalidConfig naming the argument and the sequence
+void check_firsts(const int32_t* offsets, const int32_t* firsts, int B)
 {
-    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
-    if (B == 0) return;
-    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
     for (int b = 0; b < B; ++b) {
-        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
-        const std::string seq = " (sequence " + std::to_string(b) + ")";
-        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
-                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
-        if (len < 2)
-            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens are fewer than 2: a scored token needs a prefix" + seq);
-        if (len > limit)
-            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the score length limit of " + std::to_string(limit) + seq);
+        const int32_t len = offsets[b + 1] - offsets[b];
         if (firsts[b] < 1 || firsts[b] >= len)
             throw InvalidConfig("firsts[" + std::to_string(b) + "] = " + std::to_string(firsts[b]) + " must be in [1, " + std::to_string(len) +
-                                ")" + seq);
+                                ") (sequence " + std::to_string(b) + ")");
     }
 }
 
@@ -2576,7 +2606,8 @@ void check_score_sequences(const int32_t* offsets, const int32_t* firsts, int B,
 
 ScorePlan score_plan_host(const uint32_t* ids, const int32_t* offsets, const int32_t* firsts, int B, int head_dim, int min_shared)
 {
-    check_score_sequences(offsets, firsts, B, kEmbedChunkRows);
+    check_packed_sequences("score", nullptr, offsets, B, 2, kEmbedChunkRows, 0);
+    check_firsts(offsets, firsts, B);
     if (min_shared < 1) throw InvalidConfig("min_shared (" + std::to_string(min_shared) + ") must be at least 1");
     ScorePlan plan;
     auto len_of = [&](int b) { return offsets[b + 1] - offsets[b]; };
@@ -2659,32 +2690,22 @@ ScorePlan score_plan_host(const uint32_t* ids, const int32_t* offsets, const int
     return plan;
 }
 
-bool LlmModel::score_batch_supported() const
-{
-    const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
-    return !quant_ && !(H % 32 || QD % 32 || I % 32 || kv % 4 || !(d == 16 || d == 32 || d == 64 || d == 128));
-}
+bool LlmModel::score_batch_supported() const { return !quant_ && packed_geometry(cfg_); }
 
 void LlmModel::score_batch(const uint32_t* ids, const int32_t* offsets, int B, const int32_t* firsts, int top_k, float* logprob_out,
                            uint32_t* topk_ids_out, float* topk_logprob_out)
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim;
+    const int H = c.hidden;
     if (quant_) throw InvalidConfig("score_batch: quantized checkpoints are not supported");
-    if (!score_batch_supported())
-        throw InvalidConfig("score_batch: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
+    if (!packed_geometry(c)) throw InvalidConfig(packed_geometry_refusal("score_batch"));
     if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > c.vocab)
         throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
                             "] and not above the vocabulary size " + std::to_string(c.vocab));
-    check_score_sequences(offsets, firsts, B, embed_max_tokens());
+    check_packed_sequences("score", ids, offsets, B, 2, embed_max_tokens(), c.vocab);
+    check_firsts(offsets, firsts, B);
     if (B == 0) return;
-    for (int b = 0; b < B; ++b)
-        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
-            if (ids[i] >= (uint32_t)c.vocab)
-                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
-                                    std::to_string(c.vocab) + " (sequence " + std::to_string(b) + ")");
-    const ScorePlan plan = score_plan_host(ids, offsets, firsts, B, d, kScoreMinShared);
+    const ScorePlan plan = score_plan_host(ids, offsets, firsts, B, c.head_dim, kScoreMinShared);
 
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hipStream_t s = stream_;
@@ -2697,60 +2718,18 @@ void LlmModel::score_batch(const uint32_t* ids, const int32_t* offsets, int B, c
         sb_res_ = reinterpret_cast<uint32_t*>(dalloc(kResWords));
         hip_check(hipHostMalloc((void**)&sb_res_host_, kResWords * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
     }
-    const bool fused = score_fused_ && llm_score_head_takes(pn_, H, lm_head_, bf16_ ? 1 : 0, H);
-    if (!fused) ensure_lookup();  // vlogits_: the verify step's 8 logits rows
     for (const ScoreChunk& ch : plan.chunks) {
-        const int m = ch.rows, g = (int)ch.gather_src.size(), nv = (int)ch.vec.size(), nm = (int)ch.mfma.size(), np = (int)ch.prefix.size();
-        const size_t o_pos = (size_t)m, o_src = o_pos + (size_t)m, o_tgt = o_src + (size_t)g, o_vec = o_tgt + (size_t)g;
-        const size_t o_mfma = o_vec + 3 * (size_t)nv, o_pre = o_mfma + 3 * (size_t)nm, words = o_pre + 5 * (size_t)np;
-        if (words > kPackedMetaWords || g > kEmbedChunkRows) throw std::runtime_error("score_batch: chunk metadata exceeds its buffer");
-        int32_t* hm = emeta_host_;
-        for (int r = 0; r < m; ++r) hm[r] = (int32_t)ids[ch.row_tok[(size_t)r]];
-        std::memcpy(hm + o_pos, ch.row_pos.data(), (size_t)m * 4);
-        std::memcpy(hm + o_src, ch.gather_src.data(), (size_t)g * 4);
-        std::memcpy(hm + o_tgt, ch.gather_tgt.data(), (size_t)g * 4);
-        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
-        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
-        if (np) std::memcpy(hm + o_pre, ch.prefix.data(), (size_t)np * sizeof(PrefixBlock));
-        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
-        const uint32_t* ids_dev = reinterpret_cast<const uint32_t*>(emeta_);
-        const uint32_t* tgt = reinterpret_cast<const uint32_t*>(emeta_ + o_tgt);
-        packed_layers(m, ids_dev, emeta_ + o_pos, reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec), nv,
-                      reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma), nm, reinterpret_cast<const PrefixBlock*>(emeta_ + o_pre), np);
+        const int m = ch.rows, g = (int)ch.gather_src.size();
+        if (g > kEmbedChunkRows) throw std::runtime_error("score_batch: chunk metadata exceeds its buffer");  // (sb_res_ holds 2 048 rows)
+        const PackedMeta meta = upload_packed_meta("score_batch", m, ids, ch.row_tok.data(), ch.row_pos.data(), ch.gather_src.data(), (size_t)g,
+                                                   ch.gather_tgt.data(), (size_t)g, ch.vec, ch.mfma, ch.prefix);
+        packed_layers(m, meta.ids, meta.row_pos, meta.vec, (int)ch.vec.size(), meta.mfma, (int)ch.mfma.size(), meta.prefix, (int)ch.prefix.size());
         // (the norm buffer is free after the last layer: the gathered rows land there, compact, H floats apart)
-        hip_check(launch_score_gather_norm(ph_, H, emeta_ + o_src, g, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, pn_, H, s),
+        hip_check(launch_score_gather_norm(ph_, H, meta.extra_a, g, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, pn_, H, s),
                   "score gather + norm");
-        // the chunk's results: logprob [g] | top-k ids [g, top_k] | top-k logprob [g, top_k]
-        float* lp = reinterpret_cast<float*>(sb_res_);
-        uint32_t* tid = sb_res_ + g;
-        float* tlp = reinterpret_cast<float*>(sb_res_ + g + (size_t)g * top_k);
-        if (fused) {
-            if (top_k > 1) {
-                if (score_head_topk_scratch_bytes(g, c.vocab, 0, top_k) > score_tk_scratch_bytes_)
-                    throw std::runtime_error("score_batch: slab scratch too small");
-                hip_check(launch_score_head_topk(pn_, H, g, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, top_k, score_tk_scratch_, lp, tid, tlp,
-                                                 nullptr, s), "score head top-k");
-            } else {
-                if (score_head_scratch_bytes(g, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score_batch: slab scratch too small");
-                hip_check(launch_score_head(pn_, H, g, lm_head_, bf16_ ? 1 : 0, c.vocab, H, tgt, 0, score_scratch_, lp, tid, tlp, nullptr, s),
-                          "score head");
-            }
-            ++score_fused_calls_;
-        } else {
-            for (int r = 0; r < g; r += 8) {
-                const int rows = std::min(8, g - r);
-                LlmGemvArgs lm;
-                lm.X = pn_ + (size_t)r * H; lm.ldx = H; lm.rows = rows; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-                lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
-                hip_check(launch_llm_gemv(lm, s), "lm head");
-                if (top_k > 1)
-                    hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, top_k, lp + r, tid + (size_t)r * top_k,
-                                                     tlp + (size_t)r * top_k, nullptr, s), "score rows top-k");
-                else
-                    hip_check(launch_score_rows(vlogits_, c.vocab, rows, c.vocab, tgt + r, lp + r, tid + r, tlp + r, nullptr, s), "score rows");
-                ++score_rows_calls_;
-            }
-        }
+        // the chunk's results: logprob [g] | top-k ids [g, top_k] | top-k logprob [g, top_k]; top_k 1 is score()'s plain head
+        score_head(pn_, g, reinterpret_cast<const uint32_t*>(meta.extra_b), top_k > 1 ? top_k : 0, reinterpret_cast<float*>(sb_res_), sb_res_ + g,
+                   reinterpret_cast<float*>(sb_res_ + g + (size_t)g * top_k));
         const size_t res_words = (size_t)g * (1 + 2 * (size_t)top_k);
         hip_check(hipMemcpyAsync(sb_res_host_, sb_res_, res_words * 4, hipMemcpyDeviceToHost, s), "D2H scores");
         hip_check(hipStreamSynchronize(s), "sync");  // the staging copies and the activations are reused by the next chunk
@@ -2791,58 +2770,31 @@ void LlmModel::answer_logits_batch(const uint32_t* ids, const int32_t* offsets, 
                                    float* logits_out)
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim;
+    const int H = c.hidden;
     if (quant_) throw InvalidConfig("answer_logits: quantized checkpoints are not supported");
-    if (!score_batch_supported())
-        throw InvalidConfig("answer_logits: hidden, heads * head_dim and intermediate_size must be multiples of 32 and head_dim one of 16, 32, 64, 128");
+    if (!packed_geometry(c)) throw InvalidConfig(packed_geometry_refusal("answer_logits"));
     if (n_targets < 1 || n_targets > kAnswerMaxTargets)
         throw InvalidConfig("n_targets (" + std::to_string(n_targets) + ") must be in [1, " + std::to_string(kAnswerMaxTargets) + "]");
     for (int t = 0; t < n_targets; ++t)
         if (targets[t] >= (uint32_t)c.vocab)
             throw InvalidConfig("targets[" + std::to_string(t) + "] = " + std::to_string(targets[t]) + " is not below the vocabulary size " +
                                 std::to_string(c.vocab));
-    if (B < 0) throw InvalidConfig("n_sequences (" + std::to_string(B) + ") is negative");
+    check_packed_sequences("answer", ids, offsets, B, 2, embed_max_tokens(), c.vocab);
     if (B == 0) return;
-    if (offsets[0] < 0) throw InvalidConfig("offsets[0] = " + std::to_string(offsets[0]) + " is negative (sequence 0)");
-    const int limit = embed_max_tokens();
-    for (int b = 0; b < B; ++b) {
-        const int64_t len = (int64_t)offsets[b + 1] - offsets[b];
-        const std::string seq = " (sequence " + std::to_string(b) + ")";
-        if (len < 0) throw InvalidConfig("offsets[" + std::to_string(b + 1) + "] = " + std::to_string(offsets[b + 1]) + " is below offsets[" +
-                                         std::to_string(b) + "] = " + std::to_string(offsets[b]) + ": offsets must not decrease" + seq);
-        if (len < 2) throw InvalidConfig("offsets: " + std::to_string(len) + " tokens are fewer than 2" + seq);
-        if (len > limit)
-            throw InvalidConfig("offsets: " + std::to_string(len) + " tokens exceed the answer length limit of " + std::to_string(limit) + seq);
-        for (int32_t i = offsets[b]; i < offsets[b + 1]; ++i)
-            if (ids[i] >= (uint32_t)c.vocab)
-                throw InvalidConfig("ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) + " is not below the vocabulary size " +
-                                    std::to_string(c.vocab) + seq);
-    }
-    const ScorePlan plan = answer_plan_host(ids, offsets, B, d, kScoreMinShared);
+    const ScorePlan plan = answer_plan_host(ids, offsets, B, c.head_dim, kScoreMinShared);
 
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hipStream_t s = stream_;
     ensure_prompt_workspace();
     ensure_packed_scratch();
     for (const ScoreChunk& ch : plan.chunks) {
-        const int m = ch.rows, n = ch.n_seq, nv = (int)ch.vec.size(), nm = (int)ch.mfma.size(), np = (int)ch.prefix.size();
-        const size_t o_pos = (size_t)m, o_src = o_pos + (size_t)m, o_tgt = o_src + (size_t)n, o_vec = o_tgt + (size_t)n_targets;
-        const size_t o_mfma = o_vec + 3 * (size_t)nv, o_pre = o_mfma + 3 * (size_t)nm, words = o_pre + 5 * (size_t)np;
-        if (words > kPackedMetaWords) throw std::runtime_error("answer_logits: chunk metadata exceeds its buffer");
-        int32_t* hm = emeta_host_;
-        for (int r = 0; r < m; ++r) hm[r] = (int32_t)ids[ch.row_tok[(size_t)r]];
-        std::memcpy(hm + o_pos, ch.row_pos.data(), (size_t)m * 4);
-        std::memcpy(hm + o_src, ch.gather_src.data(), (size_t)n * 4);
-        std::memcpy(hm + o_tgt, targets, (size_t)n_targets * 4);
-        if (nv) std::memcpy(hm + o_vec, ch.vec.data(), (size_t)nv * sizeof(EmbedBlock));
-        if (nm) std::memcpy(hm + o_mfma, ch.mfma.data(), (size_t)nm * sizeof(EmbedBlock));
-        if (np) std::memcpy(hm + o_pre, ch.prefix.data(), (size_t)np * sizeof(PrefixBlock));
-        hip_check(hipMemcpyAsync(emeta_, hm, words * 4, hipMemcpyHostToDevice, s), "H2D chunk");
-        packed_layers(m, reinterpret_cast<const uint32_t*>(emeta_), emeta_ + o_pos, reinterpret_cast<const EmbedBlock*>(emeta_ + o_vec), nv,
-                      reinterpret_cast<const EmbedBlock*>(emeta_ + o_mfma), nm, reinterpret_cast<const PrefixBlock*>(emeta_ + o_pre), np);
+        const int m = ch.rows, n = ch.n_seq;
+        const PackedMeta meta = upload_packed_meta("answer_logits", m, ids, ch.row_tok.data(), ch.row_pos.data(), ch.gather_src.data(), (size_t)n,
+                                                   targets, (size_t)n_targets, ch.vec, ch.mfma, ch.prefix);
+        packed_layers(m, meta.ids, meta.row_pos, meta.vec, (int)ch.vec.size(), meta.mfma, (int)ch.mfma.size(), meta.prefix, (int)ch.prefix.size());
         // (the norm buffer is free after the last layer: the chunk's [n, n_targets] logits land there)
-        hip_check(launch_answer_logits(ph_, H, emeta_ + o_src, n, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, lm_head_, bf16_ ? 1 : 0,
-                                       reinterpret_cast<const uint32_t*>(emeta_ + o_tgt), n_targets, pn_, s), "answer logits");
+        hip_check(launch_answer_logits(ph_, H, meta.extra_a, n, H, final_norm_, gpt2_ ? final_norm_b_ : nullptr, c.eps, lm_head_, bf16_ ? 1 : 0,
+                                       reinterpret_cast<const uint32_t*>(meta.extra_b), n_targets, pn_, s), "answer logits");
         // They land in the pinned staging buffer, as score_batch's results land in a pinned one: the chunk's upload from it is
         // behind us on the stream, and n * n_targets <= 1 024 * 8 words fit it.
         static_assert((size_t)(kEmbedChunkRows / 2) * kAnswerMaxTargets <= kPackedMetaWords, "a chunk's logits fit the staging buffer");

@@ -141,9 +141,9 @@ public:
     // Scoring: resets the cache, runs ids[0, n) through forward()'s routes and returns, for every position p in [first, n)
     // (1 <= first < n; entry p - first), log p(ids[p] | ids[0, p)), the arg-max token of that distribution and the arg-max's
     // log-probability (log_softmax_1d, sampling.rs:200-205); any output may be null.  Only the rows first - 1 .. n - 2 reach
-    // the vocabulary head: on the fp32 matrix cores without storing their logits (launch_score_head; f32 / bf16 heads with
-    // hidden % 32 == 0), else through the 8-row logits buffer of the verify step (launch_score_rows; quantized heads, other
-    // geometries, or set_score_fused(false)).  The results stay on the device until one copy at the end.  Leaves the model as
+    // the vocabulary head, score_head(): on the fp32 matrix cores without storing their logits (launch_score_head; f32 / bf16
+    // heads with hidden % 32 == 0), else through the 8-row logits buffer of the verify step (launch_score_rows; quantized heads,
+    // other geometries, or set_score_fused(false)).  The results stay on the device until one copy at the end.  Leaves the model as
     // reset(); forward(ids, n) does.  Throws InvalidConfig naming the argument, before any GPU work, for n < 2, first outside
     // [1, n), n > context() and an id >= vocab.
     void score(const uint32_t* ids, int n, int first, float* logprob_out, uint32_t* top_out, float* top_logprob_out);
@@ -159,8 +159,8 @@ public:
     // ---- embedding: last-token pooling over a packed batch ---------------------------------------------------------------------
     // Sequence b is ids[offsets[b], offsets[b + 1]); out[b, :] = the final-normed hidden state of its last token, L2-normalised
     // when `normalize` (x / ||x|| when ||x|| > 0).  The sequences are packed, in order, into chunks of at most 2 048 rows
-    // (embed_plan_host, decoder_embed_kernels.h) and every chunk runs prefill_rows()'s layer steps once over all its rows: the
-    // projections on the prompt GEMM routes, RoPE by each row's position in its own sequence, causal attention that stops at the
+    // (embed_plan_host, decoder_embed_kernels.h) and every chunk runs prefill_rows()'s layer body (rows_qkv / rows_finish) once
+    // over all its rows: the projections on the prompt GEMM routes, RoPE by each row's position in its own sequence, causal attention that stops at the
     // sequence boundaries; K and V live in two scratch buffers, not in the KV cache.  cache_len(), resident(), lanes, lookup
     // state, the logits and last_hidden() are left as they were.  Throws InvalidConfig naming the argument and the sequence, before
     // any GPU work, for non-monotone offsets, an empty sequence, an id >= vocab and a sequence longer than
@@ -176,7 +176,7 @@ public:
     // chunks of at most 2 048 rows and computes a token prefix that neighbouring sequences share once (kScoreMinShared tokens or
     // more, never a scored token); every chunk runs embed_batch's layer stack once over its rows, the remainders of a group
     // attending to their prefix through launch_packed_prefix_attention, then only the rows whose successor is scored are
-    // gathered through the final norm (launch_score_gather_norm) and reach the vocabulary head, on score()'s routes.  One
+    // gathered through the final norm (launch_score_gather_norm) and reach the vocabulary head, score()'s score_head().  One
     // metadata upload and one result copy per chunk.  K and V live in the embed scratch: cache_len(), resident(), lanes, lookup
     // state, logits, last_hidden(), the prefix-reuse counters and score()'s buffers are left as they were.  Throws InvalidConfig
     // naming the argument and the sequence, before any GPU work, for non-monotone offsets, a sequence shorter than 2 or longer
@@ -401,10 +401,22 @@ private:
     void ensure_prompt_workspace();  // the 2 048-row activation buffers of the prompt routes
     void ensure_packed_scratch();    // ek_, ev_, emeta_ and its pinned copy
     // The packed layer stack of embed_batch and score_batch over m rows of one chunk: embedding of ids_dev (GPT-2: + the learned
-    // position row_pos[r]), then per layer prefill_rows()'s steps with RoPE by row_pos, K and V in ek_ / ev_, attention by the
-    // three block tables.  Leaves the hidden states in ph_; the norm buffer pn_ is free afterwards.
+    // position row_pos[r]), then per layer rows_qkv() with K and V in ek_ / ev_, RoPE by row_pos, attention by the three block
+    // tables, rows_finish().  Leaves the hidden states in ph_; the norm buffer pn_ is free afterwards.
     void packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_pos, const EmbedBlock* vec, int n_vec, const EmbedBlock* mfma,
                        int n_mfma, const PrefixBlock* prefix, int n_prefix);
+    // A packed chunk's metadata on the device: what upload_packed_meta() wrote, in its word order.
+    struct PackedMeta {
+        const uint32_t* ids;
+        const int32_t *row_pos, *extra_a, *extra_b;
+        const EmbedBlock *vec, *mfma;
+        const PrefixBlock* prefix;
+    };
+    // ids [m] | row_pos [m] | extra_a [n_a] | extra_b [n_b] | vec | mfma | prefix into the pinned staging copy, then the chunk's one
+    // upload.  Row r's id is ids[row_tok[r]], or ids[r] with row_tok null.  `entry` names the caller when the words exceed the buffer.
+    PackedMeta upload_packed_meta(const char* entry, int m, const uint32_t* ids, const int32_t* row_tok, const int32_t* row_pos,
+                                  const void* extra_a, size_t n_a, const void* extra_b, size_t n_b, const std::vector<EmbedBlock>& vec,
+                                  const std::vector<EmbedBlock>& mfma, const std::vector<PrefixBlock>& prefix);
     // One projection of m prompt rows: Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T); gelu (GPT-2's
     // c_fc): Y = gelu_tanh(A W^T + bias).  Routes: the 64 x 64 prompt kernel, or from 512 rows and 208 tiles the 128 x 128-tile
     // GEMM (bf16 weights on the bf16 matrix cores); qm: a quantized matrix, dequantized into the f32 scratch first.
@@ -414,8 +426,14 @@ private:
     void ensure_score();
     void ensure_score_topk();
     void score_pass(const uint32_t* ids, int n, int first, int top_k);  // score() / score_topk() up to the copies
-    // cnt final-normed rows Xn [cnt, hidden] of positions lo .. lo + cnt - 1 against the targets ids[lo + 1 ..]
+    // cnt final-normed rows Xn [cnt, hidden] of positions lo .. lo + cnt - 1 against the targets ids[lo + 1 ..]: their slots in
+    // score()'s result rows, then score_head()
     void score_head_rows(const float* Xn, int lo, int cnt);
+    // The vocabulary head of score(), score_topk() and score_batch() over cnt final-normed rows Xn [cnt, hidden] against tgt [cnt]:
+    // the fused slab head where llm_score_head_takes (f32 / bf16 heads, unless set_score_fused(false)), else 8 rows at a time
+    // through vlogits_ (quantized heads: qlinear) and the rows kernels; counted in score_fused_calls_ / score_rows_calls_.
+    // k == 0: the plain kernels, ids / tlp [cnt] the arg-max and its log-probability; k >= 1: the top-k kernels, ids / tlp [cnt, k].
+    void score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, float* lp, uint32_t* ids, float* tlp);
     void enqueue_argmax(bool record);
     hipGraphExec_t step_graph();
 
@@ -427,6 +445,16 @@ private:
         float *k_cache, *v_cache;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
     };
+    // The layer body of the rows route, around the caller's own RoPE / head norm and attention (prefill_rows: the KV cache,
+    // packed_layers: ek_ / ev_ and the block tables).  rows_qkv: norm 1 of ph_ into pn_, Q into pq_, K and V into the rows given.
+    // rows_finish: o-proj of pctx_ + residual, norm 2, the SwiGLU or GPT-2 MLP, all into ph_.
+    void rows_qkv(int m, const Layer& L, float* k_rows, float* v_rows);
+    void rows_finish(int m, const Layer& L);
+    // The quantized stages pass_quant() and lane_step() share, over n <= 8 rows.  quant_source: the activation source of a stage,
+    // rows X (normalised by gamma inside the GEMV), or -- when a Q6_K linear reads them -- one qprep launch writing the normalised
+    // rows and their Q8_K codes.  quant_finish: o-proj + residual, RMSNorm + gate/up + SwiGLU, down + residual.
+    void quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what);
+    void quant_finish(int n, const Layer& L);
     LlmConfig cfg_;
     int device_ = 0;
     uint64_t serial_ = 0;
