@@ -880,6 +880,38 @@ KjarniErrorCode kjarni_hip_embed_plan(const int32_t* lengths, int32_t n, int32_t
 KjarniErrorCode kjarni_hip_op_packed_causal_attention(int32_t device, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                                                       int64_t ldv, int32_t buffer_rows, const int32_t* seq_start, int32_t n_sequences,
                                                       int32_t heads, int32_t kv_heads, int32_t head_dim, float* ctx, int64_t ldc);
+/* ---- the decode attention and the projections that merge its slabs, alone ---------------------------------------------------------
+ * kjarni_hip_op_decode_attention: the split-key attention of every decode step (launch_decode_attention) on host arrays, every
+ * argument of the launcher exposed.  q [rows, ldq] (heads * head_dim used).  k / v: k_floats / v_floats floats each, key row t of
+ * query row s at k + s * k_lane_stride + t * ldk, KV head h / kv_group at columns [(h / kv_group) * head_dim, + head_dim) (v
+ * alike; the lane strides are 0 unless the rows are lanes).  Keys: n_keys; with keys_on_device, n_keys is instead uploaded to a
+ * device int and the kernel sees n_keys + rows keys (n_keys + 1 with lanes) and, when causal_base >= 0, the causal base n_keys
+ * (max_keys must bound the sum).  causal_base >= 0: query row s sees keys <= causal_base + s; < 0: no mask.  lanes == rows: the
+ * rows are independent sequences, no mask.  lane_pos / lane_live [rows] (may be NULL; ragged lanes): row s sees
+ * min(lane_pos[s] + 1, n_keys) keys, a row with lane_live[s] == 0 gives zeros.  ctx [rows, ldc] is read, gets the context rows and
+ * is written back whole.  slabs (may be NULL) receives the scratch [rows, heads, splits, head_dim + 4] = (max, sum of exp, 0, 0,
+ * sum of exp * V) per key range; the scratch is filled with NaN before the launch.  INVALID_CONFIG, before any GPU work, for
+ * what the launcher refuses (head_dim not a multiple of 4 that divides 1024 or above 128, splits < 1, more than 512 keys per split,
+ * lane_pos without lanes / lane_live or with keys_on_device) and for keys that reach outside k_floats / v_floats, leading
+ * dimensions that do not cover the heads or are no multiple of 4, rows outside 1 .. 64. */
+KjarniErrorCode kjarni_hip_op_decode_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k, int64_t k_floats,
+                                               int64_t ldk, const float* v, int64_t v_floats, int64_t ldv, int32_t n_keys,
+                                               int32_t keys_on_device, int32_t max_keys, int32_t heads, int32_t head_dim, int32_t causal_base,
+                                               int32_t splits, int32_t kv_group, int64_t k_lane_stride, int64_t v_lane_stride, int32_t lanes,
+                                               const int32_t* lane_pos, const int32_t* lane_live, float* ctx, int64_t ldc, float* slabs);
+/* Whisper's one-token output projection fed by attention slabs (launch_gemv_row_att): y [n_out] = merged(slabs) . w[n, :] + bias[n]
+ * + r[n]; slabs [k / head_dim, splits, head_dim + 4], w [n_out, k], bias may be NULL.  in_place: the residual row is also the
+ * output row on the device, as in the decoder.  two_step: the route the kernel replaces runs instead -- the combine pass, then the
+ * one-row projection with bias + residual -- on the same arguments.  INVALID_CONFIG, before any GPU work, for what the launcher
+ * refuses: k not 512 / 2048, splits outside 1 .. 16, head_dim no multiple of 4 or not dividing k, r NULL. */
+KjarniErrorCode kjarni_hip_op_gemv_row_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const float* w,
+                                           const float* bias, const float* r, int32_t n_out, int32_t k, int32_t in_place, int32_t two_step,
+                                           float* y);
+/* The decoder-only models' output projection fed by attention slabs (launch_llm_gemv with att_splits / att_head_dim): the same
+ * inputs, w f32 or bf16 bits (bf16 = 1) [n_out, k], `rows` rows asked of the launcher.  INVALID_CONFIG, before any GPU work, for
+ * what the launcher refuses: rows != 1, k 2048 with more than 8 splits, k 4096 with more than 4, any other k, r NULL. */
+KjarniErrorCode kjarni_hip_op_llm_gemv_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const void* w, int32_t bf16,
+                                           const float* bias, const float* r, int32_t n_out, int32_t k, int32_t rows, float* y);
 /* RoPE alone, host pointers: x [x_rows, ldx] is read, its first `rows` rows (n_heads heads of head_dim) are rotated in place and
  * it is written back whole.  kjarni_hip_op_rope: row r by table row pos + r (the kernel of the prompt and decode paths);
  * kjarni_hip_op_rope_rows: row r by table row row_pos[r].  cos_t / sin_t [table_rows, head_dim / 2].  Positions outside the

@@ -19,6 +19,7 @@
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
 #include "llm_kernels.h"
+#include "whisper_kernels.h"
 #include "quant_kernels.h"
 #include "tuning.h"
 
@@ -739,6 +740,142 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_packed_causal_attention(int32_t devi
                                                  heads / kv_heads, (float*)cd.p, ldc, nullptr), "packed attention");
         hip_check(hipDeviceSynchronize(), "sync");
         hip_check(hipMemcpy(ctx, cd.p, R * (size_t)ldc * 4, hipMemcpyDeviceToHost), "D2H ctx");
+    });
+}
+
+// ---- the decode attention and the projections that merge its slabs, alone ---------------------------------------------------------
+
+namespace {
+
+// A launcher's hipErrorInvalidValue is the caller's mistake, not a failed run.
+void launcher_check(hipError_t e, const char* what)
+{
+    if (e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        throw InvalidConfig(std::string(what) + ": the launcher refuses these arguments");
+    }
+    hip_check(e, what);
+}
+
+size_t slab_floats(int32_t k, int32_t splits, int32_t head_dim) { return (size_t)(k / head_dim) * (size_t)splits * (size_t)(head_dim + 4); }
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_decode_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k,
+                                                             int64_t k_floats, int64_t ldk, const float* v, int64_t v_floats, int64_t ldv,
+                                                             int32_t n_keys, int32_t keys_on_device, int32_t max_keys, int32_t heads,
+                                                             int32_t head_dim, int32_t causal_base, int32_t splits, int32_t kv_group,
+                                                             int64_t k_lane_stride, int64_t v_lane_stride, int32_t lanes,
+                                                             const int32_t* lane_pos, const int32_t* lane_live, float* ctx, int64_t ldc,
+                                                             float* slabs)
+{
+    if (!q || !k || !v || !ctx) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 64 || heads < 1 || heads > 1024 || splits > 256 || kv_group < 1 || kv_group > heads)
+            throw InvalidConfig("rows must be 1..64, heads 1..1024, splits at most 256, kv_group 1..heads");
+        if (keys_on_device ? (n_keys < 0 || max_keys < 1 || max_keys > (1 << 20)) : (n_keys < 1 || n_keys > (1 << 20)))
+            throw InvalidConfig("n_keys must be 1 .. 2^20 (with the count on the device: >= 0, and max_keys 1 .. 2^20)");
+        if (!decode_attention_accepts(head_dim, splits, keys_on_device ? max_keys : n_keys, lanes, lane_pos != nullptr, lane_live != nullptr,
+                                      keys_on_device != 0))
+            throw InvalidConfig("launch_decode_attention refuses these arguments (head_dim a multiple of 4 dividing 1024, at most 128; splits "
+                                ">= 1; at most 512 keys per split; ragged lanes need lanes, lane_live and the key count on the host)");
+        if (lanes != 0 && lanes != rows) throw InvalidConfig("lanes must be 0 or rows");
+        // every key row the kernel may touch lies inside the buffers given: the worst key count is what the form allows
+        const int64_t keys = keys_on_device ? (int64_t)n_keys + (lanes ? 1 : rows) : n_keys;
+        if (keys_on_device && keys > max_keys) throw InvalidConfig("the device count plus this step's rows exceeds max_keys");
+        const int64_t qd = (int64_t)heads * head_dim, kvd = (int64_t)((heads - 1) / kv_group + 1) * head_dim;
+        if (ldq < qd || ldc < qd || ldk < kvd || ldv < kvd || ((ldq | ldk | ldv | k_lane_stride | v_lane_stride) & 3) ||
+            std::max(std::max(ldq, ldc), std::max(ldk, ldv)) > (1 << 20) || k_lane_stride < 0 || v_lane_stride < 0 ||
+            std::max(k_lane_stride, v_lane_stride) > ((int64_t)1 << 28))
+            throw InvalidConfig("leading dimensions must cover the heads, be multiples of 4 and at most 2^20; lane strides multiples of 4");
+        if ((rows - 1) * k_lane_stride + (keys - 1) * ldk + kvd > k_floats || (rows - 1) * v_lane_stride + (keys - 1) * ldv + kvd > v_floats)
+            throw InvalidConfig("the keys reach outside k_floats / v_floats");
+        if (std::max(k_floats, v_floats) > ((int64_t)1 << 26)) throw InvalidConfig("k_floats / v_floats above 2^26");
+        use_device(device);
+        const size_t qb = (size_t)rows * (size_t)ldq * 4, cb = (size_t)rows * (size_t)ldc * 4;
+        const size_t sb = decode_attention_scratch_floats(rows, heads, head_dim, splits) * 4;
+        DeviceBuf qd_(qb), kd((size_t)k_floats * 4), vd((size_t)v_floats * 4), cd(cb), sd(sb), nd(sizeof(int)), pd((size_t)rows * 4), ld((size_t)rows * 4);
+        hip_check(hipMemcpy(qd_.p, q, qb, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, (size_t)k_floats * 4, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(vd.p, v, (size_t)v_floats * 4, hipMemcpyHostToDevice), "H2D v");
+        hip_check(hipMemcpy(cd.p, ctx, cb, hipMemcpyHostToDevice), "H2D ctx");
+        hip_check(hipMemset(sd.p, 0xFF, sb), "poison scratch");  // (all-ones words are NaN: a slab the kernel skips would show)
+        hip_check(hipMemcpy(nd.p, &n_keys, sizeof(int), hipMemcpyHostToDevice), "H2D n_keys");
+        if (lane_pos) hip_check(hipMemcpy(pd.p, lane_pos, (size_t)rows * 4, hipMemcpyHostToDevice), "H2D lane_pos");
+        if (lane_live) hip_check(hipMemcpy(ld.p, lane_live, (size_t)rows * 4, hipMemcpyHostToDevice), "H2D lane_live");
+        // (with the count on the device the host's n_keys is a value the result must not depend on)
+        launcher_check(launch_decode_attention((const float*)qd_.p, ldq, rows, (const float*)kd.p, ldk, (const float*)vd.p, ldv,
+                                               keys_on_device ? 0 : n_keys, keys_on_device ? (const int*)nd.p : nullptr, max_keys, heads, head_dim,
+                                               causal_base, splits, (float*)sd.p, (float*)cd.p, ldc, nullptr, kv_group, k_lane_stride,
+                                               v_lane_stride, lanes, lane_pos ? (const int*)pd.p : nullptr,
+                                               lane_live ? (const int*)ld.p : nullptr), "decode attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(ctx, cd.p, cb, hipMemcpyDeviceToHost), "D2H ctx");
+        if (slabs) hip_check(hipMemcpy(slabs, sd.p, sb, hipMemcpyDeviceToHost), "D2H slabs");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_gemv_row_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const float* w,
+                                                         const float* bias, const float* r, int32_t n_out, int32_t k, int32_t in_place,
+                                                         int32_t two_step, float* y)
+{
+    if (!slabs || !w || !y) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_out < 1 || n_out > 65536) throw InvalidConfig("n_out must be 1 .. 65536");
+        if (!gemv_row_att_supported(k, splits, head_dim) || !r)
+            throw InvalidConfig("launch_gemv_row_att refuses these arguments (k 512 or 2048, 1..16 splits, head_dim a multiple of 4 dividing k, "
+                                "a residual)");
+        use_device(device);
+        const size_t sb = slab_floats(k, splits, head_dim) * 4, wb = (size_t)n_out * (size_t)k * 4, ob = (size_t)n_out * 4;
+        DeviceBuf sd(sb), wd(wb), bd(ob), rd(ob), yd(ob), cd((size_t)k * 4);
+        hip_check(hipMemcpy(sd.p, slabs, sb, hipMemcpyHostToDevice), "H2D slabs");
+        hip_check(hipMemcpy(wd.p, w, wb, hipMemcpyHostToDevice), "H2D w");
+        if (bias) hip_check(hipMemcpy(bd.p, bias, ob, hipMemcpyHostToDevice), "H2D bias");
+        hip_check(hipMemcpy(rd.p, r, ob, hipMemcpyHostToDevice), "H2D r");
+        hip_check(hipMemset(yd.p, 0xFF, ob), "poison y");
+        hip_check(hipMemset(cd.p, 0xFF, (size_t)k * 4), "poison ctx");
+        float* out = in_place ? (float*)rd.p : (float*)yd.p;  // in place: the residual row is the output row, as in the decoder
+        if (two_step) {  // the route the merging kernel replaces: combine, then the one-row projection + bias + residual
+            launcher_check(launch_decode_attention_combine((const float*)sd.p, 1, k / head_dim, splits, head_dim, (float*)cd.p, k, nullptr),
+                           "combine");
+            GemvArgs a;
+            a.X = (const float*)cd.p; a.ldx = k; a.rows = 1; a.W = (const float*)wd.p; a.bias = bias ? (const float*)bd.p : nullptr;
+            a.R = (const float*)rd.p; a.ldr = n_out; a.n_out = n_out; a.k = k; a.Y0 = out; a.ldy0 = n_out; a.epi = EPI_BIAS_RESIDUAL;
+            launcher_check(launch_gemv_rows(a, nullptr), "one-row projection");
+        } else {
+            launcher_check(launch_gemv_row_att((const float*)sd.p, splits, head_dim, (const float*)wd.p, bias ? (const float*)bd.p : nullptr,
+                                               (const float*)rd.p, n_out, k, out, nullptr), "gemv_row_att");
+        }
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(y, out, ob, hipMemcpyDeviceToHost), "D2H y");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_gemv_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const void* w,
+                                                         int32_t bf16, const float* bias, const float* r, int32_t n_out, int32_t k,
+                                                         int32_t rows, float* y)
+{
+    if (!slabs || !w || !y) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_out < 1 || n_out > 4096) throw InvalidConfig("n_out must be 1 .. 4096");
+        if (rows != 1 || !llm_gemv_merges_attention(k, splits, head_dim) || !r)
+            throw InvalidConfig("launch_llm_gemv refuses these arguments (one row; k 2048 with 1..8 splits or k 4096 with 1..4; head_dim a "
+                                "multiple of 4 dividing k; a residual)");
+        use_device(device);
+        const size_t sb = slab_floats(k, splits, head_dim) * 4, wb = (size_t)n_out * (size_t)k * (bf16 ? 2 : 4), ob = (size_t)n_out * 4;
+        DeviceBuf sd(sb), wd(wb), bd(ob), rd(ob), yd(ob);
+        hip_check(hipMemcpy(sd.p, slabs, sb, hipMemcpyHostToDevice), "H2D slabs");
+        hip_check(hipMemcpy(wd.p, w, wb, hipMemcpyHostToDevice), "H2D w");
+        if (bias) hip_check(hipMemcpy(bd.p, bias, ob, hipMemcpyHostToDevice), "H2D bias");
+        hip_check(hipMemcpy(rd.p, r, ob, hipMemcpyHostToDevice), "H2D r");
+        hip_check(hipMemset(yd.p, 0xFF, ob), "poison y");
+        LlmGemvArgs a;
+        a.X = (const float*)sd.p; a.ldx = k; a.rows = rows; a.W = wd.p; a.bf16 = bf16 ? 1 : 0; a.bias = bias ? (const float*)bd.p : nullptr;
+        a.R = (const float*)rd.p; a.ldr = n_out; a.n_out = n_out; a.k = k; a.Y0 = (float*)yd.p; a.ldy0 = n_out;
+        a.att_splits = splits; a.att_head_dim = head_dim;
+        launcher_check(launch_llm_gemv(a, nullptr), "llm gemv + merge");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(y, yd.p, ob, hipMemcpyDeviceToHost), "D2H y");
     });
 }
 

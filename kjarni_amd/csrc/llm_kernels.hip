@@ -1785,7 +1785,9 @@ bool llm_gemv_merges_attention(int k, int splits, int head_dim)
 
 hipError_t launch_llm_gemv(const LlmGemvArgs& a, hipStream_t stream)
 {
-    if (a.att_splits > 0 && (a.rows != 1 || a.seg_q != 0)) return hipErrorInvalidValue;
+    // (slabs are merged by the weight-streaming kernel alone: any other size would read them as a context row)
+    if (a.att_splits > 0 && (a.rows != 1 || a.seg_q != 0 || !a.R || !llm_gemv_merges_attention(a.k, a.att_splits, a.att_head_dim)))
+        return hipErrorInvalidValue;
     if (a.norm_out && !(a.rows == 1 && a.seg_q == 0 && a.gamma && llm_gemv_streams(a.k, a.W, a.W2))) return hipErrorInvalidValue;
     // LayerNorm needs gamma and beta and takes no residual / SwiGLU epilogue; GELU-tanh comes only after LayerNorm (GPT-2's c_fc)
     if (a.layernorm && (!a.gamma || !a.beta || a.R || a.swiglu || a.att_splits > 0 || a.norm_out)) return hipErrorInvalidValue;

@@ -71,6 +71,13 @@ size_t decode_attention_scratch_floats(int rows, int heads, int head_dim, int sp
 bool gemv_row_att_supported(int k, int splits, int head_dim);
 hipError_t launch_gemv_row_att(const float* slabs, int splits, int head_dim, const float* W, const float* bias, const float* R, int n_out,
                                int k, float* Y, hipStream_t stream);
+// Does launch_decode_attention take these arguments (else hipErrorInvalidValue and nothing is launched)?  head_dim a multiple
+// of 4 that divides 1024, at most 128; no key range longer than 512 keys (worst_keys = max_keys with the device count, else
+// n_keys); ragged lanes (lane_pos given) need `lanes`, lane_live and the key count on the host.
+bool decode_attention_accepts(int head_dim, int splits, int worst_keys, int lanes, bool ragged, bool has_lane_live, bool keys_on_device);
+// The merge pass of launch_decode_attention alone: slabs [rows, heads, splits, head_dim + 4] -> ctx [rows, ldc].
+hipError_t launch_decode_attention_combine(const float* scratch, int rows, int heads, int splits, int head_dim, float* ctx, int64_t ldc,
+                                           hipStream_t stream);
 hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V,
                                    int64_t ldv, int n_keys, const int* n_keys_ptr, int max_keys, int heads, int head_dim,
                                    int causal_base, int splits, float* scratch, float* ctx, int64_t ldc, hipStream_t stream,

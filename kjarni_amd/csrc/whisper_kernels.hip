@@ -1167,6 +1167,23 @@ size_t decode_attention_scratch_floats(int rows, int heads, int head_dim, int sp
     return (size_t)rows * heads * splits * (head_dim + 4);
 }
 
+bool decode_attention_accepts(int head_dim, int splits, int worst_keys, int lanes, bool ragged, bool has_lane_live, bool keys_on_device)
+{
+    if (head_dim < 4 || head_dim > 128 || (head_dim & 3) || 256 % (head_dim / 4) != 0 || splits < 1) return false;
+    if ((worst_keys + splits - 1) / splits > ATT_MAX_CHUNK) return false;
+    return !ragged || (lanes && has_lane_live && !keys_on_device);  // ragged lanes: n_keys is the lane capacity
+}
+
+hipError_t launch_decode_attention_combine(const float* scratch, int rows, int heads, int splits, int head_dim, float* ctx, int64_t ldc,
+                                           hipStream_t stream)
+{
+    if (rows <= 0) return hipSuccess;
+    if (head_dim < 1 || head_dim > 128 || splits < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_attention_combine_kernel, dim3((unsigned)heads, (unsigned)rows), dim3(128), 0, stream, scratch, heads, splits,
+                       head_dim, ctx, ldc);
+    return hipGetLastError();
+}
+
 hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V,
                                    int64_t ldv, int n_keys, const int* n_keys_ptr, int max_keys, int heads, int head_dim,
                                    int causal_base, int splits, float* scratch, float* ctx, int64_t ldc, hipStream_t stream,
@@ -1174,11 +1191,10 @@ hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const 
                                    const int* lane_live)
 {
     if (rows <= 0 || (n_keys <= 0 && !n_keys_ptr)) return hipSuccess;
-    if (head_dim > 128 || 256 % (head_dim / 4) != 0 || (head_dim & 3) || splits < 1) return hipErrorInvalidValue;
-    const int worst = n_keys_ptr ? max_keys : n_keys;
-    if ((worst + splits - 1) / splits > ATT_MAX_CHUNK) return hipErrorInvalidValue;
-    if (lane_pos) {  // ragged lanes: n_keys is the lane capacity
-        if (!lanes || !lane_live || n_keys_ptr) return hipErrorInvalidValue;
+    if (!decode_attention_accepts(head_dim, splits, n_keys_ptr ? max_keys : n_keys, lanes, lane_pos != nullptr, lane_live != nullptr,
+                                  n_keys_ptr != nullptr))
+        return hipErrorInvalidValue;
+    if (lane_pos) {
         hipLaunchKernelGGL(decode_attention_partial_kernel<true>, dim3((unsigned)heads, (unsigned)splits, (unsigned)rows), dim3(256), 0,
                            stream, q, ldq, K, ldk, V, ldv, n_keys, n_keys_ptr, rows, head_dim, 1.0f / sqrtf((float)head_dim), causal_base,
                            splits, kv_group < 1 ? 1 : kv_group, k_lane_stride, v_lane_stride, lanes, scratch, lane_pos, lane_live);
@@ -1187,8 +1203,7 @@ hipError_t launch_decode_attention(const float* q, int64_t ldq, int rows, const 
                        q, ldq, K, ldk, V, ldv, n_keys, n_keys_ptr, rows, head_dim, 1.0f / sqrtf((float)head_dim), causal_base, splits,
                        kv_group < 1 ? 1 : kv_group, k_lane_stride, v_lane_stride, lanes, scratch, nullptr, nullptr);
     if (ctx)  // ctx == nullptr: the caller merges the slabs itself (layout above)
-        hipLaunchKernelGGL(decode_attention_combine_kernel, dim3((unsigned)heads, (unsigned)rows), dim3(128), 0, stream, scratch, heads,
-                           splits, head_dim, ctx, ldc);
+        return launch_decode_attention_combine(scratch, rows, heads, splits, head_dim, ctx, ldc, stream);
     return hipGetLastError();
 }
 

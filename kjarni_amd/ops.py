@@ -259,6 +259,67 @@ def packed_causal_attention(q, k, v, lengths, heads: int, kv_heads: int, head_di
     return ca
 
 
+# ---- the decode attention and the projections that merge its slabs, alone ----
+def decode_attention(q, k, v, ldk: int, ldv: int, n_keys: int, heads: int, head_dim: int, splits: int, causal_base: int = -1,
+                     kv_group: int = 1, keys_on_device: bool = False, max_keys: int = 0, k_lane_stride: int = 0, v_lane_stride: int = 0,
+                     lanes: int = 0, lane_pos=None, lane_live=None, ctx=None, want_slabs: bool = False, device: int = 0):
+    """launch_decode_attention on host arrays (kjarni_hip_op_decode_attention).  q [rows, ldq]; k and v are flat float buffers the
+    caller lays out itself (key row t of query row s at s * lane stride + t * ldk).  Returns ctx [rows, ldc] (given, or NaN
+    [rows, heads * head_dim]) with the context rows written and, with want_slabs, the scratch [rows, heads, splits, head_dim + 4]."""
+    qa = np.ascontiguousarray(q, np.float32)
+    ka, va = np.ascontiguousarray(k, np.float32).reshape(-1), np.ascontiguousarray(v, np.float32).reshape(-1)
+    if qa.ndim != 2:
+        raise ValueError("q: [rows, ldq]")
+    rows = qa.shape[0]
+    ca = np.full((rows, heads * head_dim), np.nan, np.float32) if ctx is None else np.array(ctx, np.float32, order="C")
+    if ca.ndim != 2 or ca.shape[0] != rows:
+        raise ValueError("ctx: [rows, ldc]")
+    pos = None if lane_pos is None else np.ascontiguousarray(lane_pos, np.int32)
+    live = None if lane_live is None else np.ascontiguousarray(lane_live, np.int32)
+    if any(x is not None and x.shape != (rows,) for x in (pos, live)):
+        raise ValueError("lane_pos / lane_live: [rows]")
+    sl = np.empty((rows, heads, max(int(splits), 0), head_dim + 4), np.float32) if want_slabs else None
+    p = lambda x: None if x is None else x.ctypes.data_as(_i32p)  # noqa: E731
+    check_error(lib().kjarni_hip_op_decode_attention(device, _f(qa), qa.shape[1], rows, _f(ka), ka.size, int(ldk), _f(va), va.size, int(ldv),
+                                                     int(n_keys), int(bool(keys_on_device)), int(max_keys), int(heads), int(head_dim),
+                                                     int(causal_base), int(splits), int(kv_group), int(k_lane_stride), int(v_lane_stride),
+                                                     int(lanes), p(pos), p(live), _f(ca), ca.shape[1], _f(sl)))
+    return (ca, sl) if want_slabs else ca
+
+
+def _slab_args(slabs, w, bias, r, head_dim):
+    sa = np.ascontiguousarray(slabs, np.float32)
+    if sa.ndim != 3 or sa.shape[2] != head_dim + 4 or w.ndim != 2 or w.shape[1] != sa.shape[0] * head_dim:
+        raise ValueError("slabs: [heads, splits, head_dim + 4]; w: [n_out, heads * head_dim]")
+    n_out = w.shape[0]
+    ba, ra = (None if x is None else np.ascontiguousarray(x, np.float32) for x in (bias, r))
+    if any(x is not None and x.shape != (n_out,) for x in (ba, ra)):
+        raise ValueError("bias / r: [n_out]")
+    return sa, ba, ra, n_out
+
+
+def gemv_row_att(slabs, w, bias, r, head_dim: int, in_place: bool = False, two_step: bool = False, device: int = 0):
+    """y [n_out] = merged(slabs) . w^T + bias + r by launch_gemv_row_att (kjarni_hip_op_gemv_row_att); two_step: by the combine
+    pass and the one-row projection instead.  slabs [heads, splits, head_dim + 4], w [n_out, heads * head_dim]."""
+    wa = np.ascontiguousarray(w, np.float32)
+    sa, ba, ra, n_out = _slab_args(slabs, wa, bias, r, head_dim)
+    y = np.full(n_out, np.nan, np.float32)
+    check_error(lib().kjarni_hip_op_gemv_row_att(device, _f(sa), sa.shape[1], int(head_dim), _f(wa), _f(ba), _f(ra), n_out, wa.shape[1],
+                                                 int(bool(in_place)), int(bool(two_step)), _f(y)))
+    return y
+
+
+def llm_gemv_att(slabs, w, bias, r, head_dim: int, bf16: bool = False, rows: int = 1, device: int = 0):
+    """The same through launch_llm_gemv's slab-merging branch (kjarni_hip_op_llm_gemv_att); w f32, or bf16 bit patterns
+    (uint16) with bf16 = True."""
+    wa = np.ascontiguousarray(w, np.uint16 if bf16 else np.float32)
+    sa, ba, ra, n_out = _slab_args(slabs, wa, bias, r, head_dim)
+    y = np.full(n_out, np.nan, np.float32)
+    check_error(lib().kjarni_hip_op_llm_gemv_att(device, _f(sa), sa.shape[1], int(head_dim), wa.ctypes.data_as(C.c_void_p), int(bool(bf16)),
+                                                 _f(ba), _f(ra), n_out, wa.shape[1], int(rows), _f(y)))
+    return y
+
+
 def _tables(cos, sin, head_dim):
     ct, st = np.ascontiguousarray(cos, np.float32), np.ascontiguousarray(sin, np.float32)
     if ct.ndim != 2 or ct.shape != st.shape or ct.shape[1] != head_dim // 2:
