@@ -505,141 +505,31 @@ void LlmModel::leave_resident(const std::vector<uint32_t>& all)
     resident_.assign(all.begin(), all.begin() + (ptrdiff_t)std::min(all.size(), (size_t)cache_len_));
 }
 
-void LlmModel::verify_gemv(const LlmGemvArgs& a, const char* what)
+void LlmModel::project(StepRoute route, const LlmGemvArgs& a, const char* what)
 {
+    if (route == StepRoute::Step) {
+        hip_check(launch_llm_gemv(a, stream_), what);
+        return;
+    }
     int streamed = 0;
     hip_check(launch_llm_gemv_lanes(a, stream_, &streamed), what);
-    if (streamed) ++verify_stream_calls_;
-    else ++verify_fallback_calls_;
+    if (route == StepRoute::Verify) ++(streamed ? verify_stream_calls_ : verify_fallback_calls_);
+    else ++(streamed ? lane_stream_calls_ : lane_fallback_calls_);
 }
 
-void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
+void LlmModel::embed_rows(const uint32_t* ids, int n, float* dst, int pos, const int* pos_ptr, const int* row_pos)
 {
-    hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, I = c.inter, QD = c.q_dim();
-    const int* pp = device_pos ? pos_ : nullptr;
-    if (quant_) {
-        pass_quant(ids_dev, n, device_pos, verify);
-        return;
-    }
-    if (gpt2_) {
-        pass_gpt2(ids_dev, n, device_pos, verify);
-        return;
-    }
-    auto gemv = [&](const LlmGemvArgs& a, const char* what) {
-        if (verify) verify_gemv(a, what);
-        else hip_check(launch_llm_gemv(a, s), what);
-    };
-    const bool one = n == 1 && !verify;  // the one-token fusions
-    const bool qk_norm = c.qwen3();      // Q and K are normalised per head between projection and rotation: no fused Q|K|V + RoPE launch
-    // one token: the first layer's projection gathers the embedding row itself (one launch fewer per step)
-    const bool embed_in_qkv = one && !qk_norm && H <= 8192 && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
-    if (!embed_in_qkv) hip_check(launch_llm_embed(ids_dev, n, H, c.vocab, embed_, bf16_ ? 1 : 0, h_, s), "embed");
-    bool first_layer = true;
-    for (const Layer& L : layers_) {
-        if (one && !qk_norm && H <= 8192) {  // decode step: norm + projection + rotation in one launch
-            const bool emb = embed_in_qkv && first_layer;
-            hip_check(launch_llm_qkv_rope(h_, L.ln1, c.eps, L.wqkv, bf16_ ? 1 : 0, L.bqkv, H, c.heads, c.kv_heads, d, cos_, sin_, q_,
-                                          L.k_cache, L.v_cache, cache_len_, pp, s, emb ? ids_dev : nullptr, emb ? embed_ : nullptr,
-                                          c.vocab, emb ? h_ : nullptr), "norm + qkv + rope");
-            first_layer = false;
-        } else {
-        LlmGemvArgs a;  // RMSNorm + Q | K | V (decoder_attention.rs:61-82): K / V rows land in the cache
-        a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_; a.bias = L.bqkv;
-        a.n_out = QD + 2 * kv; a.k = H; a.seg_q = QD; a.seg_kv = kv; a.Y0 = q_; a.ldy0 = QD; a.Y1 = L.k_cache; a.Y2 = L.v_cache; a.ldy12 = kv;
-        a.row_off = cache_len_; a.row_off_ptr = pp;
-        gemv(a, "norm + qkv");
-        if (qk_norm) {  // Qwen3: head norm + rotation of the Q row(s) and of the K rows where they sit in the cache, one launch
-            hip_check(launch_qk_norm_rope(q_, QD, L.k_cache, kv, n, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_, pp,
-                                          1, s), "qk norm + rope");
-        } else {
-        hip_check(launch_rope(q_, QD, n, c.heads, d, cos_, sin_, cache_len_, pp, 0, s), "rope q");
-        hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pp, 1, s), "rope k");
-        }
-        }
-        // one token: the output projection merges the attention's per-split slabs itself (no combine launch)
-        const bool merge_in_proj = one && llm_gemv_merges_attention(QD, splits_, d);
-        hip_check(launch_decode_attention(q_, QD, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
-                                          splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, QD, s, c.heads / c.kv_heads), "attention");
-        LlmGemvArgs o;
-        o.X = ctx_; o.ldx = QD; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.R = h_; o.ldr = H; o.n_out = H; o.k = QD; o.Y0 = h_; o.ldy0 = H;
-        if (merge_in_proj) {
-            o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
-        }
-        gemv(o, "o proj");
-        LlmGemvArgs g;  // RMSNorm + SwiGLU (swiglu.rs:32-57)
-        g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.W2 = L.up; g.bf16 = bf16_; g.swiglu = 1;
-        g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
-        gemv(g, "norm + gate/up");
-        LlmGemvArgs dn;
-        dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I; dn.Y0 = h_; dn.ldy0 = H;
-        gemv(dn, "down proj");
-    }
-    LlmGemvArgs lm;
-    lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-    lm.Y0 = logits_; lm.ldy0 = c.vocab;
-    if (verify) {  // every row's logits
-        hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
-        lm.X = last_; lm.rows = n; lm.Y0 = vlogits_;
-        verify_gemv(lm, "lm head");
-        return;
-    }
-    if (n == 1 && llm_gemv_streams(H, lm_head_, nullptr)) {  // one token: the head normalises the row itself (and stores it)
-        lm.X = h_; lm.gamma = final_norm_; lm.eps = c.eps; lm.norm_out = last_;
-    } else {
-        hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
-        lm.X = last_ + (size_t)(n - 1) * H;
-    }
-    hip_check(launch_llm_gemv(lm, s), "lm head");
+    const int wb = bf16_ ? 1 : 0;
+    if (quant_) hip_check(launch_qembed(ids, n, qembed_, dst, stream_), "embed");
+    else if (gpt2_) hip_check(launch_llm_embed_pos(ids, n, c.hidden, c.vocab, embed_, wpe_, c.max_pos, wb, pos, pos_ptr, dst, stream_, row_pos), "embed");
+    else hip_check(launch_llm_embed(ids, n, c.hidden, c.vocab, embed_, wb, dst, stream_), "embed");
 }
 
-// pass() for GPT-2 (gpt2/cpu_decoder.rs:371-394): the token + position embedding, then per layer the same five launches as
-// the bf16 Llama step -- LayerNorm(ln_1) + Q|K|V + bias (K / V rows into the cache, no rotation), attention, c_proj + bias +
-// residual, LayerNorm(ln_2) + c_fc + bias + GELU-tanh, mlp.c_proj + bias + residual -- and LayerNorm(ln_f) + the tied head.
-void LlmModel::pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
+void LlmModel::final_norm(const float* src, int rows, float* dst)
 {
-    hipStream_t s = stream_;
-    const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, I = c.inter;
-    const int* pp = device_pos ? pos_ : nullptr;
-    auto gemv = [&](const LlmGemvArgs& a, const char* what) {
-        if (verify) verify_gemv(a, what);
-        else hip_check(launch_llm_gemv(a, s), what);
-    };
-    hip_check(launch_llm_embed_pos(ids_dev, n, H, c.vocab, embed_, wpe_, c.max_pos, bf16_ ? 1 : 0, cache_len_, pp, h_, s), "embed");
-    for (const Layer& L : layers_) {
-        LlmGemvArgs a;
-        a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = 1; a.eps = c.eps; a.W = L.wqkv; a.bf16 = bf16_;
-        a.bias = L.bqkv; a.n_out = 3 * H; a.k = H; a.seg_q = H; a.seg_kv = H; a.Y0 = q_; a.ldy0 = H; a.Y1 = L.k_cache; a.Y2 = L.v_cache;
-        a.ldy12 = H; a.row_off = cache_len_; a.row_off_ptr = pp;
-        gemv(a, "ln_1 + c_attn");
-        const bool merge_in_proj = n == 1 && !verify && llm_gemv_merges_attention(H, splits_, d);
-        hip_check(launch_decode_attention(q_, H, n, L.k_cache, H, L.v_cache, H, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_, splits_,
-                                          att_scratch_, merge_in_proj ? nullptr : ctx_, H, s, 1), "attention");
-        LlmGemvArgs o;
-        o.X = ctx_; o.ldx = H; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = H; o.Y0 = h_; o.ldy0 = H;
-        if (merge_in_proj) {
-            o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = d;
-        }
-        gemv(o, "attn c_proj");
-        LlmGemvArgs f;
-        f.X = h_; f.ldx = H; f.rows = n; f.gamma = L.ln2; f.beta = L.ln2_b; f.layernorm = 1; f.eps = c.eps; f.W = L.gate; f.bf16 = bf16_;
-        f.bias = L.bfc; f.gelu_tanh = 1; f.n_out = I; f.k = H; f.Y0 = mid_; f.ldy0 = I;
-        gemv(f, "ln_2 + c_fc + gelu");
-        LlmGemvArgs dn;
-        dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
-        dn.Y0 = h_; dn.ldy0 = H;
-        gemv(dn, "mlp c_proj");
-    }
-    hip_check(launch_layernorm(h_, final_norm_, final_norm_b_, c.eps, n, H, last_, s), "ln_f");
-    LlmGemvArgs lm;
-    lm.X = last_ + (size_t)(n - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-    lm.Y0 = logits_; lm.ldy0 = c.vocab;
-    if (verify) {  // every row's logits
-        lm.X = last_; lm.rows = n; lm.Y0 = vlogits_;
-    }
-    gemv(lm, "lm head");
+    if (gpt2_) hip_check(launch_layernorm(src, final_norm_, final_norm_b_, cfg_.eps, rows, cfg_.hidden, dst, stream_), "ln_f");
+    else hip_check(launch_rmsnorm(src, final_norm_, cfg_.eps, rows, cfg_.hidden, dst, stream_), "final norm");
 }
 
 void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what)
@@ -690,18 +580,32 @@ void LlmModel::quant_finish(int n, const Layer& L)
     hip_check(launch_qfused(dn, s), "down proj");
 }
 
-// pass() for a checkpoint whose matrices stay quantized: the same stages and formulas, five fused launches per layer
-// (quant_kernels.hip): RMSNorm + Q|K|V (per-segment types) + RoPE + cache write, attention, then quant_finish(): o-proj +
-// residual, RMSNorm + gate/up + SwiGLU, down + residual.  A stage whose input feeds a Q6_K linear first runs one qprep launch
-// (quant_source(): RMSNorm where the stage has one + the Q8_K codes, shared by every matrix of the stage).
-void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
+void LlmModel::head(StepRoute route, const float* X, int rows, float* Y, bool norm_in_head)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden;
+    if (quant_) {  // (the quantized kernels take <= 8 rows as they are)
+        qlinear(qhead_, X, H, rows, head_q8k_, Y, c.vocab, "lm head");
+        return;
+    }
+    LlmGemvArgs lm;
+    lm.X = X; lm.ldx = H; lm.rows = rows; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H; lm.Y0 = Y; lm.ldy0 = c.vocab;
+    if (norm_in_head) {
+        lm.gamma = final_norm_; lm.eps = c.eps; lm.norm_out = last_;
+    }
+    project(route, lm, "lm head");
+}
+
+// Norm + Q | K | V + rotation of n rows (decoder_attention.rs:61-82), three forms.  Quantized matrices: one fused launch
+// (quant_kernels.hip: RMSNorm + per-segment types + RoPE + cache write; a Q6_K linear first takes one qprep launch,
+// quant_source()).  fused: the one-token Llama launch.  Else the GEMV with the K / V segments landing in the cache rows, then
+// the rotation where they sit: Qwen3 head norm + RoPE in one launch, Llama RoPE of Q and of K, GPT-2 (learned positions) none.
+void LlmModel::step_qkv(StepRoute route, int n, const Layer& L, const int* pos, bool fused, const uint32_t* embed_ids)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d;
-    const int* pp = device_pos ? pos_ : nullptr;
-    hip_check(launch_qembed(ids_dev, n, qembed_, h_, s), "embed");
-    for (const Layer& L : layers_) {
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
+    if (quant_) {
         QFusedArgs qkv;
         qkv.mode = QF_QKV;
         quant_source(qkv, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
@@ -710,16 +614,89 @@ void LlmModel::pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool 
         qkv.jobs = H / 2 + kv;
         qkv.bias = L.bqkv; qkv.bias_off[1] = H; qkv.bias_off[2] = H + kv;
         qkv.Y[0] = q_; qkv.ldy[0] = H; qkv.Y[1] = L.k_cache; qkv.Y[2] = L.v_cache; qkv.ldy[1] = qkv.ldy[2] = kv;
-        qkv.row_off = cache_len_; qkv.row_off_ptr = pp;
+        qkv.row_off = cache_len_; qkv.row_off_ptr = pos;
         qkv.head_dim = d; qkv.cos_t = cos_; qkv.sin_t = sin_;
         hip_check(launch_qfused(qkv, s), "norm + qkv + rope");
-        hip_check(launch_decode_attention(q_, H, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
-                                          splits_, att_scratch_, ctx_, H, s, c.heads / c.kv_heads), "attention");
-        quant_finish(n, L);
+        return;
     }
-    hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
-    if (verify) qlinear(qhead_, last_, H, n, head_q8k_, vlogits_, c.vocab, "lm head");  // every row's logits (the quantized kernels take <= 8 rows as they are)
-    else qlinear(qhead_, last_ + (size_t)(n - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
+    if (fused) {
+        hip_check(launch_llm_qkv_rope(h_, L.ln1, c.eps, L.wqkv, bf16_ ? 1 : 0, L.bqkv, H, c.heads, c.kv_heads, d, cos_, sin_, q_, L.k_cache,
+                                      L.v_cache, cache_len_, pos, s, embed_ids, embed_ids ? embed_ : nullptr, c.vocab, embed_ids ? h_ : nullptr),
+                  "norm + qkv + rope");
+        return;
+    }
+    LlmGemvArgs a;
+    a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
+    a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = QD + 2 * kv; a.k = H; a.seg_q = QD; a.seg_kv = kv; a.Y0 = q_; a.ldy0 = QD;
+    a.Y1 = L.k_cache; a.Y2 = L.v_cache; a.ldy12 = kv; a.row_off = cache_len_; a.row_off_ptr = pos;
+    project(route, a, "norm + qkv");
+    if (c.qwen3()) {
+        hip_check(launch_qk_norm_rope(q_, QD, L.k_cache, kv, n, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_, pos, 1,
+                                      s), "qk norm + rope");
+    } else if (!gpt2_) {
+        hip_check(launch_rope(q_, QD, n, c.heads, d, cos_, sin_, cache_len_, pos, 0, s), "rope q");
+        hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pos, 1, s), "rope k");
+    }
+}
+
+void LlmModel::layer_finish(StepRoute route, int n, const Layer& L, bool slabs)
+{
+    if (quant_) {
+        quant_finish(n, L);
+        return;
+    }
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, I = c.inter, QD = c.q_dim();
+    LlmGemvArgs o;
+    o.X = ctx_; o.ldx = QD; o.rows = n; o.W = L.wo; o.bf16 = bf16_; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = QD; o.Y0 = h_; o.ldy0 = H;
+    if (slabs) {
+        o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = c.head_dim;
+    }
+    project(route, o, "o proj");
+    LlmGemvArgs g;  // RMSNorm + SwiGLU (swiglu.rs:32-57); GPT-2: LayerNorm(ln_2) + c_fc + bias + GELU-tanh
+    g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.beta = L.ln2_b; g.eps = c.eps; g.W = L.gate; g.bf16 = bf16_; g.bias = L.bfc;
+    g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
+    if (gpt2_) {
+        g.layernorm = 1; g.gelu_tanh = 1;
+    } else {
+        g.W2 = L.up; g.swiglu = 1;
+    }
+    project(route, g, "norm + mlp in");
+    LlmGemvArgs dn;
+    dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
+    dn.Y0 = h_; dn.ldy0 = H;
+    project(route, dn, "down proj");
+}
+
+// One pass of n <= 8 rows for every family (llama/cpu_decoder.rs:142-219, gpt2/cpu_decoder.rs:371-394): the embedding (GPT-2:
+// token + learned position), per layer step_qkv -> attention -> layer_finish, then the final norm and the vocabulary head.
+// The one-token step (n == 1, not verify) fuses where the kernels allow: the Llama layer's norm + Q|K|V + RoPE in one launch,
+// whose first layer also gathers the embedding row; the attention's slab merge inside the output projection (not quantized);
+// the final norm inside the head (Llama / Qwen3).
+void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify)
+{
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
+    const StepRoute route = verify ? StepRoute::Verify : StepRoute::Step;
+    const int* pp = device_pos ? pos_ : nullptr;
+    const bool one = n == 1 && !verify, llama = !quant_ && !gpt2_;
+    const bool fused_qkv = one && llama && !c.qwen3() && H <= 8192;  // (Qwen3 normalises Q and K per head between projection and rotation)
+    const bool embed_in_qkv = fused_qkv && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
+    const bool merge_in_proj = one && !quant_ && llm_gemv_merges_attention(QD, splits_, d);  // no combine launch
+    if (!embed_in_qkv) embed_rows(ids_dev, n, h_, cache_len_, pp, nullptr);
+    for (const Layer& L : layers_) {
+        step_qkv(route, n, L, pp, fused_qkv, embed_in_qkv && &L == &layers_[0] ? ids_dev : nullptr);
+        hip_check(launch_decode_attention(q_, QD, n, L.k_cache, kv, L.v_cache, kv, cache_len_ + n, pp, cache_cap_, c.heads, d, cache_len_,
+                                          splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, QD, stream_, c.heads / c.kv_heads), "attention");
+        layer_finish(route, n, L, merge_in_proj);
+    }
+    if (one && llama && llm_gemv_streams(H, lm_head_, nullptr)) {  // the head normalises the row itself (and stores it in last_)
+        head(route, h_, 1, logits_, true);
+        return;
+    }
+    final_norm(h_, n, last_);  // every row: forward_rows() scores from them
+    if (verify) head(route, last_, n, vlogits_);  // every row's logits
+    else head(route, last_ + (size_t)(n - 1) * H, 1, logits_);
 }
 
 void LlmModel::ensure_prompt_workspace()
@@ -847,14 +824,11 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
-    const int wb = bf16_ ? 1 : 0;
     ensure_prompt_workspace();
     for (int done = 0; done < n; done += prefill_cap_) {
         const int m = std::min(prefill_cap_, n - done);
         hip_check(hipMemcpyAsync(pids_, ids_host + done, (size_t)m * 4, hipMemcpyHostToDevice, s), "H2D ids");
-        if (quant_) hip_check(launch_qembed(pids_, m, qembed_, ph_, s), "embed");
-        else if (gpt2_) hip_check(launch_llm_embed_pos(pids_, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, cache_len_, nullptr, ph_, s), "embed");
-        else hip_check(launch_llm_embed(pids_, m, H, c.vocab, embed_, wb, ph_, s), "embed");
+        embed_rows(pids_, m, ph_, cache_len_, nullptr, nullptr);
         for (const Layer& L : layers_) {
             rows_qkv(m, L, L.k_cache + (size_t)cache_len_ * kv, L.v_cache + (size_t)cache_len_ * kv);
             if (c.qwen3()) {  // head norm + rotation over the chunk's Q rows and its K rows in the cache
@@ -881,25 +855,15 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
             const int at = score_base + done;  // the chunk's first position in the scored sequence
             const int lo = std::max(at, score_first_ - 1), hi = std::min(at + m - 1, score_n_ - 2);
             if (lo <= hi) {
-                const float* src = ph_ + (size_t)(lo - at) * H;
-                if (gpt2_) hip_check(launch_layernorm(src, final_norm_, final_norm_b_, c.eps, hi - lo + 1, H, pn_, s), "ln_f");
-                else hip_check(launch_rmsnorm(src, final_norm_, c.eps, hi - lo + 1, H, pn_, s), "final norm");
+                final_norm(ph_ + (size_t)(lo - at) * H, hi - lo + 1, pn_);
                 score_head_rows(pn_, lo, hi - lo + 1);
             }
         }
         cache_len_ += m;
         if (done + m == n) {
             const int rows = (n - 1) % 8 + 1;
-            if (gpt2_) hip_check(launch_layernorm(ph_ + (size_t)(m - rows) * H, final_norm_, final_norm_b_, c.eps, rows, H, last_, s), "ln_f");
-            else hip_check(launch_rmsnorm(ph_ + (size_t)(m - rows) * H, final_norm_, c.eps, rows, H, last_, s), "final norm");
-            if (quant_) {
-                qlinear(qhead_, last_ + (size_t)(rows - 1) * H, H, 1, head_q8k_, logits_, c.vocab, "lm head");
-            } else {
-                LlmGemvArgs lm;
-                lm.X = last_ + (size_t)(rows - 1) * H; lm.ldx = H; lm.rows = 1; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-                lm.Y0 = logits_; lm.ldy0 = c.vocab;
-                hip_check(launch_llm_gemv(lm, s), "lm head");
-            }
+            final_norm(ph_ + (size_t)(m - rows) * H, rows, last_);
+            head(StepRoute::Step, last_ + (size_t)(rows - 1) * H, 1, logits_);
             last_rows_ = rows;
         }
         hip_check(hipStreamSynchronize(s), "sync");  // pids_ and the activations are reused by the next chunk
@@ -1013,14 +977,7 @@ void LlmModel::score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, 
     const size_t slots = k > 0 ? (size_t)k : 1;  // per row in ids / tlp
     for (int r = 0; r < cnt; r += 8) {
         const int rows = std::min(8, cnt - r);
-        if (quant_) {
-            qlinear(qhead_, Xn + (size_t)r * H, H, rows, head_q8k_, vlogits_, c.vocab, "lm head");
-        } else {
-            LlmGemvArgs lm;
-            lm.X = Xn + (size_t)r * H; lm.ldx = H; lm.rows = rows; lm.W = lm_head_; lm.bf16 = bf16_; lm.n_out = c.vocab; lm.k = H;
-            lm.Y0 = vlogits_; lm.ldy0 = c.vocab;
-            hip_check(launch_llm_gemv(lm, stream_), "lm head");
-        }
+        head(StepRoute::Step, Xn + (size_t)r * H, rows, vlogits_);
         if (k > 0)
             hip_check(launch_score_rows_topk(vlogits_, c.vocab, rows, c.vocab, tgt + r, k, lp + r, ids + r * slots, tlp + r * slots, nullptr,
                                              stream_), "score rows top-k");
@@ -1509,27 +1466,18 @@ void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
     lane_len_[lane] = base + n;
 }
 
-void LlmModel::lane_gemv(const LlmGemvArgs& a)
-{
-    int streamed = 0;
-    hip_check(launch_llm_gemv_lanes(a, stream_, &streamed), "lane projection");
-    if (streamed) ++lane_stream_calls_;
-    else ++lane_fallback_calls_;
-}
-
+// One lock-step step: pass()'s stages with one row per lane.  Its own first half of the layer -- Q | K | V of every lane into the
+// staging rows, then one kernel rotates them and scatters K and V to row pos[lane] of each lane's cache -- and the ragged
+// attention; embedding, layer_finish, final norm and head are pass()'s.
 void LlmModel::lane_step(int n)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, I = c.inter, QD = c.q_dim();
+    const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
     const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
     const int64_t stride = (int64_t)lane_alloc_cap_ * kv;
     const LlmLaneState* st = lane_state_;
-    const uint32_t* toks = reinterpret_cast<const uint32_t*>(st->token);
-    const int wb = bf16_ ? 1 : 0;
-    if (quant_) hip_check(launch_qembed(toks, n, qembed_, h_, s), "embed");
-    else if (gpt2_) hip_check(launch_llm_embed_pos(toks, n, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, h_, s, st->pos), "embed");
-    else hip_check(launch_llm_embed(toks, n, H, c.vocab, embed_, wb, h_, s), "embed");
+    embed_rows(reinterpret_cast<const uint32_t*>(st->token), n, h_, 0, nullptr, st->pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
         if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
@@ -1546,8 +1494,8 @@ void LlmModel::lane_step(int n)
         } else {
             LlmGemvArgs a;
             a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
-            a.bf16 = wb; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = lane_qkv_; a.ldy0 = ldq;
-            lane_gemv(a);
+            a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = lane_qkv_; a.ldy0 = ldq;
+            project(StepRoute::Lanes, a, "norm + qkv");
         }
         if (c.qwen3())
             hip_check(launch_lane_qk_norm_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, lane_k_[li],
@@ -1557,35 +1505,10 @@ void LlmModel::lane_step(int n)
                                            gpt2_ ? 0 : 1, s), "rotate + scatter");
         hip_check(launch_decode_attention(lane_qkv_, ldq, n, lane_k_[li], kv, lane_v_[li], kv, lane_cap_, nullptr, lane_cap_, c.heads, d, -1,
                                           splits_, att_scratch_, ctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
-        if (quant_) {
-            quant_finish(n, L);
-            continue;
-        }
-        LlmGemvArgs o;
-        o.X = ctx_; o.ldx = QD; o.rows = n; o.W = L.wo; o.bf16 = wb; o.bias = L.bo; o.R = h_; o.ldr = H; o.n_out = H; o.k = QD; o.Y0 = h_; o.ldy0 = H;
-        lane_gemv(o);
-        LlmGemvArgs g;
-        g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = c.eps; g.W = L.gate; g.bf16 = wb; g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
-        if (gpt2_) {
-            g.beta = L.ln2_b; g.layernorm = 1; g.bias = L.bfc; g.gelu_tanh = 1;
-        } else {
-            g.W2 = L.up; g.swiglu = 1;
-        }
-        lane_gemv(g);
-        LlmGemvArgs dn;
-        dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = wb; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
-        dn.Y0 = h_; dn.ldy0 = H;
-        lane_gemv(dn);
+        layer_finish(StepRoute::Lanes, n, L, false);
     }
-    if (gpt2_) hip_check(launch_layernorm(h_, final_norm_, final_norm_b_, c.eps, n, H, last_, s), "ln_f");
-    else hip_check(launch_rmsnorm(h_, final_norm_, c.eps, n, H, last_, s), "final norm");
-    if (quant_) {
-        qlinear(qhead_, last_, H, n, head_q8k_, lane_logits_, c.vocab, "lm head");
-    } else {
-        LlmGemvArgs lm;
-        lm.X = last_; lm.ldx = H; lm.rows = n; lm.W = lm_head_; lm.bf16 = wb; lm.n_out = c.vocab; lm.k = H; lm.Y0 = lane_logits_; lm.ldy0 = c.vocab;
-        lane_gemv(lm);
-    }
+    final_norm(h_, n, last_);
+    head(StepRoute::Lanes, last_, n, lane_logits_);
 }
 
 void LlmModel::lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
@@ -2528,11 +2451,9 @@ void LlmModel::packed_layers(int m, const uint32_t* ids_dev, const int32_t* row_
                              int nm, const PrefixBlock* prefix, int np)
 {
     const LlmConfig& c = cfg_;
-    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
+    const int d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     hipStream_t s = stream_;
-    const int wb = bf16_ ? 1 : 0;
-    if (gpt2_) hip_check(launch_llm_embed_pos(ids_dev, m, H, c.vocab, embed_, wpe_, c.max_pos, wb, 0, nullptr, ph_, s, row_pos), "embed");
-    else hip_check(launch_llm_embed(ids_dev, m, H, c.vocab, embed_, wb, ph_, s), "embed");
+    embed_rows(ids_dev, m, ph_, 0, nullptr, row_pos);
     for (const Layer& L : layers_) {
         rows_qkv(m, L, ek_, ev_);
         if (c.qwen3()) {

@@ -259,7 +259,7 @@ public:
     // ---- prompt-lookup decoding: greedy generate() that emits several tokens per step ----------------------------------------
     // generate() for a greedy request without logits processors, with every step verifying a draft: the continuation of the
     // latest longest n-gram match in the prompt + the tokens so far (launch_lookup_draft) runs with the last token as one block
-    // of draft_tokens + 1 rows at the device-held position (verify_pass: causal inside the block, K / V rows into the cache,
+    // of draft_tokens + 1 rows at the device-held position (pass(), verify: causal inside the block, K / V rows into the cache,
     // every row through the final norm and the vocabulary head), and the pick keeps the model's own argmax tokens up to and
     // including the first one that differs from the draft.  Draft, step and pick are one chain of launches captured once per
     // row count and replayed in bursts (generate()'s cadences); near the end of the cache the steps have fewer rows, so that
@@ -331,19 +331,12 @@ private:
     int keep_prefix(const uint32_t* prompt, size_t n, size_t limit);  // truncates the cache, counts; returns the rows kept
     void leave_resident(const std::vector<uint32_t>& all);            // what a generate loop leaves: the fed tokens of `all`
     void lane_step(int lanes);                 // enqueue one lock-step step over lanes [0, lanes)
-    void lane_gemv(const struct LlmGemvArgs& a);
     hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
     void lane_state_to_device();
     void lane_state_from_device();
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
-    // verify (prompt-lookup): the projections take the multi-row weight-streaming kernel where it applies (verify_gemv), the
-    // one-row fusions are off, and the final norm and the vocabulary head run over every row, into vlogits_ [n, vocab]
-    void pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);
-    void pass_quant(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);  // pass() on quantized matrices (quant_kernels.hip)
-    void pass_gpt2(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);   // pass() for a GPT-2 layer stack
-    void verify_gemv(const struct LlmGemvArgs& a, const char* what);
     void ensure_lookup();
     // Where the draft of a verify step comes from: the lookup rule on the history (drafter null), or a drafter model.
     struct DraftSource {
@@ -450,9 +443,31 @@ private:
     // rows_finish: o-proj of pctx_ + residual, norm 2, the SwiGLU or GPT-2 MLP, all into ph_.
     void rows_qkv(int m, const Layer& L, float* k_rows, float* v_rows);
     void rows_finish(int m, const Layer& L);
-    // The quantized stages pass_quant() and lane_step() share, over n <= 8 rows.  quant_source: the activation source of a stage,
-    // rows X (normalised by gamma inside the GEMV), or -- when a Q6_K linear reads them -- one qprep launch writing the normalised
-    // rows and their Q8_K codes.  quant_finish: o-proj + residual, RMSNorm + gate/up + SwiGLU, down + residual.
+    // The steps route: passes of n <= 8 rows through the GEMV kernels, for every family.  Step: the decode step (n = 1, captured)
+    // and prompt blocks; Verify: a block at the device-held position whose rows all reach the head; Lanes: one row per lane.
+    enum class StepRoute { Step, Verify, Lanes };
+    // One projection.  Step: launch_llm_gemv.  Verify / Lanes: launch_llm_gemv_lanes (the multi-row weight-streaming kernel where
+    // it applies), counted in verify_stream_calls_ / verify_fallback_calls_ or lane_stream_calls_ / lane_fallback_calls_.
+    void project(StepRoute route, const struct LlmGemvArgs& a, const char* what);
+    // n new tokens at cache_len_ (device_pos: at *pos_): embedding, per layer step_qkv -> attention -> layer_finish, head.
+    // verify: the one-row fusions are off and the final norm and the vocabulary head run over every row, into vlogits_ [n, vocab].
+    void pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify = false);
+    // pass()'s first half of a layer: norm + Q|K|V + rotation, Q into q_, K and V into the cache rows at cache_len_ / *pos.
+    // fused: the one-token Llama launch; embed_ids (non-null only with it, in the first layer): it gathers the embedding row too.
+    void step_qkv(StepRoute route, int n, const Layer& L, const int* pos, bool fused, const uint32_t* embed_ids);
+    // The second half, shared with lane_step(): o-proj + residual, norm + MLP-in (SwiGLU, or GPT-2's LayerNorm + c_fc + GELU-tanh),
+    // down + residual, h_ -> h_.  slabs: the o-proj reads and merges the attention's split slabs in att_scratch_ instead of ctx_.
+    // Quantized checkpoints: quant_finish().
+    void layer_finish(StepRoute route, int n, const Layer& L, bool slabs);
+    // The family branches every route shares.  embed_rows: n ids into dst (GPT-2 adds the learned position: pos + s, *pos_ptr + s,
+    // or row_pos[s]).  final_norm: RMSNorm, GPT-2 LayerNorm.  head: rows normalised rows X into Y [rows, vocab]; norm_in_head (one
+    // row, where llm_gemv_streams): X is the raw row, the head normalises it itself and stores it in last_.
+    void embed_rows(const uint32_t* ids, int n, float* dst, int pos, const int* pos_ptr, const int* row_pos);
+    void final_norm(const float* src, int rows, float* dst);
+    void head(StepRoute route, const float* X, int rows, float* Y, bool norm_in_head = false);
+    // The quantized stages over n <= 8 rows.  quant_source: the activation source of a stage, rows X (normalised by gamma inside
+    // the GEMV), or -- when a Q6_K linear reads them -- one qprep launch writing the normalised rows and their Q8_K codes.
+    // quant_finish (layer_finish's quantized form): o-proj + residual, RMSNorm + gate/up + SwiGLU, down + residual.
     void quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what);
     void quant_finish(int n, const Layer& L);
     LlmConfig cfg_;

@@ -227,3 +227,8 @@ def test_long_prompt_at_1b_widths_takes_the_tiles(tmp_path):
     _, a = q.forward(ids40)
     _, b = f.forward(ids40)
     assert np.abs(a - b).max() < TOL * max(1.0, np.abs(b).max())
+    # one-token steps at q_dim 2048, where the f32 load merges the attention's slabs inside its output projection and folds the
+    # final norm into its head, and the quantized load must do neither
+    for t in ids[40:43]:
+        (hq, a), (hf_, b) = q.forward([t]), f.forward([t])
+        assert np.abs(hq - hf_).max() < TOL and np.abs(a - b).max() < TOL * max(1.0, np.abs(b).max())
