@@ -1141,6 +1141,93 @@ KjarniErrorCode kjarni_hip_generator_encode(const KjarniGenerator* generator, co
 void kjarni_hip_generator_seed(KjarniGenerator* generator, uint64_t seed);
 void kjarni_hip_generator_set_device_sampling(KjarniGenerator* generator, int32_t on);
 
+/* ---- constrained decoding: regex-guided generation with a device token mask (NOT in the reference) ----
+ * A regular expression restricts what a generate call may emit: after every token, the bytes of all emitted tokens are a prefix
+ * of some string the pattern matches in full; in an accepting state the call's stop ids become legal.
+ *
+ * The pattern compiles, on the host, to a DFA over bytes.  Syntax: literals (non-ASCII ones match as their UTF-8 bytes), the
+ * escapes \\ \. \n \t \r \f \v \" \xHH and escaped metacharacters, \d \w \s (ASCII), `.` (any Unicode scalar except \n),
+ * classes [a-z0-9_] and negated classes [^...] over ASCII members, groups ( ) and (?: ), alternation, and the quantifiers
+ * * + ? {m} {m,} {m,n} with n <= 255.  `.` and a negated class also match every well-formed non-ASCII UTF-8 scalar.  The match is
+ * a full match, with the semantics of Python's re.fullmatch(pattern, text, re.ASCII) compared on text.encode().  Anchors, lazy
+ * and possessive quantifiers, back-references, look-around, named groups, inline flags, the negated shorthands, a non-ASCII
+ * class member, more than KJARNI_CONSTRAINT_MAX_STATES states (the message gives the count) and an empty language:
+ * INVALID_CONFIG, the message naming the construct and its byte offset.
+ *
+ * The table: trans[states][256] (uint16), state 0 the start state, accepting[states], closed[states] (accepting, no live
+ * outgoing byte).  The DFA is minimal and holds no state that cannot reach an accepting one: a transition into such a state is
+ * KJARNI_CONSTRAINT_DEAD. */
+#define KJARNI_CONSTRAINT_DEAD 0xFFFFu
+#define KJARNI_CONSTRAINT_MAX_STATES 4096
+#define KJARNI_CONSTRAINT_MAX_STOPS 16
+typedef struct KjarniHipRegex KjarniHipRegex;
+KjarniErrorCode kjarni_hip_regex_compile(const char* pattern, KjarniHipRegex** out);
+void kjarni_hip_regex_free(KjarniHipRegex* regex);
+KjarniErrorCode kjarni_hip_regex_dims(const KjarniHipRegex* regex, int32_t* states, uint32_t* start);
+/* trans_out [states * 256], accepting_out / closed_out [states]; any may be NULL. */
+KjarniErrorCode kjarni_hip_regex_table(const KjarniHipRegex* regex, uint16_t* trans_out, uint8_t* accepting_out, uint8_t* closed_out);
+/* *state_out = the state after bytes[n] from `state`, KJARNI_CONSTRAINT_DEAD when the walk dies or `state` is no state. */
+KjarniErrorCode kjarni_hip_regex_step(const KjarniHipRegex* regex, uint32_t state, const uint8_t* bytes, size_t n, uint32_t* state_out);
+/* The raw bytes token `id` contributes to the output (not through decode, which trims): byte-level BPE: the GPT-2 byte map
+ * inverted; the SentencePiece-style shape: U+2581 -> space, <0xNN> -> that byte; added and special tokens, and ids the file does
+ * not define: zero bytes.  Writes min(*n_out, capacity) bytes. */
+KjarniErrorCode kjarni_bpe_tokenizer_token_bytes(const KjarniBpeTokenizer* tokenizer, uint32_t id, uint8_t* bytes_out, size_t capacity,
+                                                 size_t* n_out);
+/* The device constraint: the DFA, the token table (token t contributes tok_bytes[tok_off[t], tok_off[t + 1]); tok_off has
+ * vocab + 1 entries) and the mask built from them on the device: mask[states][ceil(vocab / 64)] 64-bit words, bit (q, t) set iff
+ * token t has at least one byte and walking its bytes from q never reaches DEAD, and count[states], the set bits per state.
+ * A mask beyond 256 MiB or a malformed table: INVALID_CONFIG before any GPU work.  The regex may be freed afterwards. */
+typedef struct KjarniHipConstraint KjarniHipConstraint;
+KjarniErrorCode kjarni_hip_constraint_new(int32_t device, const KjarniHipRegex* regex, const uint32_t* tok_off, const uint8_t* tok_bytes,
+                                          int32_t vocab, KjarniHipConstraint** out);
+void kjarni_hip_constraint_free(KjarniHipConstraint* constraint);
+KjarniErrorCode kjarni_hip_constraint_dims(const KjarniHipConstraint* constraint, int32_t* states, int32_t* vocab, int32_t* words);
+KjarniErrorCode kjarni_hip_constraint_mask(const KjarniHipConstraint* constraint, uint32_t state, uint64_t* words_out);
+KjarniErrorCode kjarni_hip_constraint_counts(const KjarniHipConstraint* constraint, uint32_t* counts_out);
+/* The three kernels alone, through the launchers the loops run, with a guard band behind every output buffer.
+ * kjarni_hip_op_constraint_mask: the mask build on tables given by the host: mask_out [states * ceil(vocab / 64)], counts_out
+ * [states].
+ * kjarni_hip_op_constraint_apply: logits [rows, ld] (ld >= vocab) with the per-row states[rows] and done[rows] flags and the stop
+ * ids (n_stop <= 16): where done is clear, a logit keeps its bits when its token's mask bit is set, or, for a stop id, when the
+ * state is accepting (whatever the stop id's bytes); every other logit of the row becomes -inf.  logits_out [rows, ld]: all of it,
+ * the floats between vocab and ld included.
+ * kjarni_hip_op_constraint_advance: picked[rows] moves states[rows] / done[rows] in place and writes violated_out[rows]: a stop
+ * id in an accepting state keeps the state and sets done; any other token walks its bytes, done when the new state is closed;
+ * a token the mask does not allow sets violated (and done: the state no longer moves).  A row whose done is set is left alone. */
+KjarniErrorCode kjarni_hip_op_constraint_mask(int32_t device, const uint16_t* trans, int32_t states, const uint32_t* tok_off,
+                                              const uint8_t* tok_bytes, int32_t vocab, uint64_t* mask_out, uint32_t* counts_out);
+KjarniErrorCode kjarni_hip_op_constraint_apply(int32_t device, const KjarniHipConstraint* constraint, const float* logits, int32_t rows, int64_t ld,
+                                               const uint32_t* states, const int32_t* done, const uint32_t* stop_ids, int32_t n_stop,
+                                               float* logits_out);
+KjarniErrorCode kjarni_hip_op_constraint_advance(int32_t device, const KjarniHipConstraint* constraint, const int32_t* picked, int32_t rows,
+                                                 uint32_t* states, int32_t* done, const uint32_t* stop_ids, int32_t n_stop,
+                                                 int32_t* violated_out);
+/* How a constrained call ended.  final_state: the automaton's state after the emitted tokens, as the host walked it;
+ * device_state: the same as the device left it (the device sampling route and plain greedy; equal to final_state unless violated);
+ * accepted: final_state is accepting; complete: the run ended on a stop id in an accepting state or in a closed state (not on a
+ * limit or the callback); violated: a token outside the mask was picked (never, unless the logits are all NaN). */
+typedef struct KjarniHipConstraintResult { uint32_t final_state, device_state; int32_t accepted, complete, violated; } KjarniHipConstraintResult;
+/* kjarni_hip_decoder_generate_sampled's plain loop (no lookup, no drafter) under a constraint.  Every step applies the mask
+ * before any logits processor and before the pick or the cut: plain greedy replays a captured chain pass -> apply -> argmax ->
+ * advance in bursts; with processors or sampling the order is apply, processors, argmax or the sampler's cut, and the state
+ * advances after the token is fed; with device sampling off the same mask is applied to the host copy of the logits.  Reaching a
+ * closed state ends the run without a stop token.  Before any GPU work, INVALID_CONFIG: a constraint of another device or
+ * vocabulary, more than 16 stop ids, and a state a run can be in (the start state and what the allowed tokens lead to from it)
+ * that is neither closed, nor accepting with stop ids in the call, nor offers a token that is no stop id (the message names the
+ * state).  result may be NULL. */
+KjarniErrorCode kjarni_hip_decoder_generate_constrained(KjarniHipDecoder* decoder, const KjarniHipConstraint* constraint, const uint32_t* prompt,
+                                                        size_t n_prompt, const KjarniHipSamplingOptions* options, KjarniTokenCallbackFn on_token,
+                                                        void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out,
+                                                        KjarniHipConstraintResult* result);
+/* A pattern for every later request of the handle (NULL or "": none, the plain behaviour).  The token table comes from the
+ * handle's own tokenizer, built once per pattern; the compiled constraint is kept until the pattern changes.  While set, requests
+ * run through the plain loop even when prompt lookup or a draft model is switched on; generate_batch is not constrained. */
+KjarniErrorCode kjarni_hip_generator_set_constraint(KjarniGenerator* generator, const char* pattern);
+KjarniErrorCode kjarni_hip_chat_set_constraint(KjarniChat* chat, const char* pattern);
+/* The result of the handle's last constrained request (zeros before one). */
+KjarniErrorCode kjarni_hip_generator_constraint_result(const KjarniGenerator* generator, KjarniHipConstraintResult* out);
+KjarniErrorCode kjarni_hip_chat_constraint_result(const KjarniChat* chat, KjarniHipConstraintResult* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .transcriber import HipWhisper, Transcriber  # noqa: F401,E402
 from .decoder import HipDecoder, answer_plan, embed_plan, generation_replay, prefix_keep, score_plan  # noqa: F401,E402
 from .chat import BpeTokenizer, Chat, ChatConversation, GenerationConfig  # noqa: F401,E402
 from .generator import Generator  # noqa: F401,E402
+from . import constraints  # noqa: F401,E402
 from .tokenizer import Tokenizer  # noqa: F401,E402
 
 __version__ = "0.1.0"

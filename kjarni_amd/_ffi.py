@@ -253,6 +253,11 @@ class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
 
+class KjarniHipConstraintResult(Structure):
+    _fields_ = [("final_state", C.c_uint32), ("device_state", C.c_uint32), ("accepted", c_int32), ("complete", c_int32),
+                ("violated", c_int32)]
+
+
 class KjarniScoreResult(Structure):
     _fields_ = [("sum_logprob", C.c_double), ("n_tokens", c_size_t), ("is_greedy", c_int32)]
 
@@ -567,6 +572,29 @@ SIGNATURES = {
     "kjarni_hip_rerank_prompt_ids": (c_int32, [c_char_p, c_char_p, c_char_p, c_char_p, c_int32, _u32p, c_size_t, POINTER(c_size_t)]),
     "kjarni_hip_reranker_answer_rows": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_bpe_tokenizer_encode_embedding": (c_int32, [c_void_p, c_char_p, c_size_t, _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_regex_compile": (c_int32, [c_char_p, POINTER(c_void_p)]),
+    "kjarni_hip_regex_free": (None, [c_void_p]),
+    "kjarni_hip_regex_dims": (c_int32, [c_void_p, POINTER(c_int32), _u32p]),
+    "kjarni_hip_regex_table": (c_int32, [c_void_p, POINTER(C.c_uint16), POINTER(C.c_uint8), POINTER(C.c_uint8)]),
+    "kjarni_hip_regex_step": (c_int32, [c_void_p, C.c_uint32, POINTER(C.c_uint8), c_size_t, _u32p]),
+    "kjarni_bpe_tokenizer_token_bytes": (c_int32, [c_void_p, C.c_uint32, POINTER(C.c_uint8), c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_constraint_new": (c_int32, [c_int32, c_void_p, _u32p, POINTER(C.c_uint8), c_int32, POINTER(c_void_p)]),
+    "kjarni_hip_constraint_free": (None, [c_void_p]),
+    "kjarni_hip_constraint_dims": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_constraint_mask": (c_int32, [c_void_p, C.c_uint32, POINTER(c_uint64)]),
+    "kjarni_hip_constraint_counts": (c_int32, [c_void_p, _u32p]),
+    "kjarni_hip_op_constraint_mask": (c_int32, [c_int32, POINTER(C.c_uint16), c_int32, _u32p, POINTER(C.c_uint8), c_int32, POINTER(c_uint64),
+                                                _u32p]),
+    "kjarni_hip_op_constraint_apply": (c_int32, [c_int32, c_void_p, _f32p, c_int32, c_int64, _u32p, POINTER(c_int32), _u32p, c_int32, _f32p]),
+    "kjarni_hip_op_constraint_advance": (c_int32, [c_int32, c_void_p, POINTER(c_int32), c_int32, _u32p, POINTER(c_int32), _u32p, c_int32,
+                                                   POINTER(c_int32)]),
+    "kjarni_hip_decoder_generate_constrained": (c_int32, [c_void_p, c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
+                                                          KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
+                                                          POINTER(KjarniHipConstraintResult)]),
+    "kjarni_hip_generator_set_constraint": (c_int32, [c_void_p, c_char_p]),
+    "kjarni_hip_chat_set_constraint": (c_int32, [c_void_p, c_char_p]),
+    "kjarni_hip_generator_constraint_result": (c_int32, [c_void_p, POINTER(KjarniHipConstraintResult)]),
+    "kjarni_hip_chat_constraint_result": (c_int32, [c_void_p, POINTER(KjarniHipConstraintResult)]),
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),

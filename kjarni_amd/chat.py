@@ -186,6 +186,19 @@ class Chat:
         path = model_dir_or_gguf.encode("utf-8") if model_dir_or_gguf else None
         check_error(lib().kjarni_hip_chat_set_draft_model(self._handle, path, int(draft_tokens)))
 
+    def set_constraint(self, pattern: Optional[str]):
+        """Constrained decoding for send(): every later reply is text that `pattern` matches in full (builders in
+        kjarni_amd.constraints); None restores the plain behaviour.  While set, requests take the plain loop even when prompt
+        lookup or a draft model is switched on.  Nested or recursive JSON schemas are out of scope."""
+        check_error(lib().kjarni_hip_chat_set_constraint(self._handle, pattern.encode("utf-8") if pattern else None))
+
+    def constraint_result(self):
+        """How the last constrained request ended: final_state, device_state, accepted, complete, violated."""
+        from .constraints import result_dict
+        r = _ffi.KjarniHipConstraintResult()
+        check_error(lib().kjarni_hip_chat_constraint_result(self._handle, C.byref(r)))
+        return result_dict(r)
+
     def verify_gemv_calls(self):
         """(streamed, fallback) projections of verify steps since load: moves only when a call took a lookup or a draft loop."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -278,6 +291,16 @@ class BpeTokenizer:
         check_error(lib().kjarni_bpe_tokenizer_decode(self._handle, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, int(skip_special),
                                                       C.byref(out)))
         return _take_string(out)
+
+    def token_bytes(self, token_id: int) -> bytes:
+        """The raw bytes a token contributes to the output (not through decode(), which trims): empty for added and special tokens."""
+        n = C.c_size_t()
+        buf = (C.c_uint8 * 512)()
+        check_error(lib().kjarni_bpe_tokenizer_token_bytes(self._handle, int(token_id), buf, 512, C.byref(n)))
+        if n.value > 512:
+            buf = (C.c_uint8 * n.value)()
+            check_error(lib().kjarni_bpe_tokenizer_token_bytes(self._handle, int(token_id), buf, n.value, C.byref(n)))
+        return bytes(buf[: n.value])
 
     def pre_tokenize(self, text: str) -> List[str]:
         arr = _ffi.KjarniStringArray()

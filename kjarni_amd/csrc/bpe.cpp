@@ -377,6 +377,7 @@ void BpeTokenizer::load_json(const std::string& text, const std::string& origin)
 
     // added tokens
     added_.clear();
+    is_added_.clear();
     if (const Json* added = j.find("added_tokens"); added && added->is_array())
         for (const Json& a : added->arr) {
             const Json* id = a.find("id");
@@ -391,6 +392,8 @@ void BpeTokenizer::load_json(const std::string& text, const std::string& origin)
             t.rstrip = a.get_bool("rstrip", false);
             t.single_word = a.get_bool("single_word", false);
             put(t.id, t.content, t.special);
+            if (t.id >= is_added_.size()) is_added_.resize((size_t)t.id + 1, 0);
+            is_added_[t.id] = 1;
             t.match = t.content;
             if (t.normalized && nfc_) {  // normalized tokens are matched against normalized text
                 std::vector<uint32_t> in, o;
@@ -503,6 +506,39 @@ std::string BpeTokenizer::decode(const std::vector<uint32_t>& ids, bool skip_spe
         bytes += ok ? mapped : tok;  // a token with a character outside the alphabet keeps its own bytes
     }
     return from_utf8_lossy(bytes);
+}
+
+// The bytes a token contributes to the output, before any decoder step that looks at its neighbours (decode() trims and
+// replaces): ByteLevel: every character of the token through the inverted byte map (a token with a character outside the
+// alphabet keeps its own bytes, as decode() has it); SentencePiece style: <0xNN> is that byte, U+2581 a space.
+std::string BpeTokenizer::token_bytes(uint32_t id) const
+{
+    if (id >= id_to_token_.size() || !has_token_[id] || special_[id] || (id < is_added_.size() && is_added_[id])) return std::string();
+    const std::string& tok = id_to_token_[id];
+    if (sp_mode_) {
+        if (tok.size() == 6 && tok.compare(0, 3, "<0x") == 0 && tok[5] == '>') {
+            const auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+            const int hi = hex(tok[3]), lo = hex(tok[4]);
+            if (hi >= 0 && lo >= 0) return std::string(1, (char)(hi * 16 + lo));
+        }
+        std::string bytes;
+        for (size_t i = 0; i < tok.size();) {
+            if (tok.compare(i, 3, "\xE2\x96\x81") == 0) {
+                bytes += ' ';
+                i += 3;
+            } else bytes += tok[i++];
+        }
+        return bytes;
+    }
+    std::vector<uint32_t> cps;
+    if (!unicode::decode_utf8(tok.data(), tok.size(), cps)) return tok;
+    std::string mapped;
+    for (uint32_t cp : cps) {
+        const auto it = char_bytes_.find(cp);
+        if (it == char_bytes_.end()) return tok;
+        mapped.push_back((char)it->second);
+    }
+    return mapped;
 }
 
 // AddedVocabulary::find_matches over one of the two token sets (normalized = false: raw text; true: normalized text).

@@ -42,6 +42,10 @@ public:
     const std::string& embedding_frame_error() const { return frame_error_; }
     // Tokenizer::decode(ids, skip_special_tokens) with the ByteLevel decoder: String::from_utf8_lossy of the bytes.
     std::string decode(const std::vector<uint32_t>& ids, bool skip_special) const;
+    // The raw bytes token `id` contributes to the output: the byte map inverted (ByteLevel), or U+2581 -> space and <0xNN> -> that
+    // byte (SentencePiece style).  Added and special tokens, and ids the file does not define, give no bytes.  Not decode(), which
+    // trims and replaces invalid UTF-8.
+    std::string token_bytes(uint32_t id) const;
     bool token_to_id(const std::string& token, uint32_t& id) const;
     size_t vocab_size() const { return id_to_token_.size(); }
     void set_truncation(size_t max_length) { max_length_ = max_length; }
@@ -71,7 +75,7 @@ private:
     std::string decode_sp(const std::vector<uint32_t>& ids, bool skip_special) const;
 
     std::vector<std::string> id_to_token_;
-    std::vector<uint8_t> has_token_, special_;
+    std::vector<uint8_t> has_token_, special_, is_added_;
     std::unordered_map<std::string, uint32_t> vocab_;        // model vocabulary
     std::unordered_map<std::string, uint32_t> token_to_id_;  // vocabulary + added tokens
     std::unordered_map<uint64_t, std::pair<uint32_t, uint32_t>> merges_;  // (a << 32 | b) -> (rank, merged id)

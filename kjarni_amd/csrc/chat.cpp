@@ -353,10 +353,13 @@ GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, 
 // every generated token is decoded on its own, specials kept (generator.rs:343-345), and handed to on_text.
 std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
                                 const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
-                                int prompt_lookup = 0, int sampled_lookup = 0, LlmModel* drafter = nullptr, int draft_tokens = 0)
+                                int prompt_lookup = 0, int sampled_lookup = 0, LlmModel* drafter = nullptr, int draft_tokens = 0,
+                                const DeviceConstraint* constraint = nullptr, ConstraintOutcome* outcome = nullptr)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
-    const GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
+    GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
+    opt.constraint = constraint;
+    opt.constraint_outcome = constraint ? outcome : nullptr;
     std::string text;
     std::vector<uint32_t> prompt_tokens = tokens;
     if ((int)prompt_tokens.size() > model.context()) prompt_tokens.resize((size_t)model.context());
@@ -367,7 +370,10 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
     };
     // a draft model (when set) takes precedence over prompt lookup: greedy requests without processors and sampled requests
     // without an n-gram ban verify the drafter's proposals every step; the others take the plain loop inside generate_draft
-    if (drafter && draft_tokens > 0) {
+    // (a constrained request takes the plain loop: the lookup and draft loops do not carry the automaton)
+    if (constraint) {
+        model.generate(prompt_tokens, opt, on_token);
+    } else if (drafter && draft_tokens > 0) {
         model.generate_draft(drafter, prompt_tokens, opt, draft_tokens, on_token, nullptr);
     } else if (prompt_lookup > 0 && !opt.sample && opt.repetition_penalty == 1.0f && opt.no_repeat_ngram <= 0) {
         LookupConfig lk;
@@ -511,6 +517,47 @@ static void set_handle_drafter(LlmModel& target, const std::string& path, int dr
     tokens = draft_tokens;
 }
 
+// The constraint of a handle: `pattern` compiled and its mask built over the model's vocabulary, with the bytes of every token
+// from the handle's tokenizer (ids past the tokenizer's own: no bytes); an empty pattern frees it.
+static void set_handle_constraint(const LlmModel& model, const BpeTokenizer& tok, const std::string& pattern, std::string& current,
+                                  std::unique_ptr<DeviceConstraint>& constraint)
+{
+    if (pattern.empty()) {
+        constraint.reset();
+        current.clear();
+        return;
+    }
+    if (constraint && pattern == current) return;
+    ConstraintDfa dfa;
+    try {
+        dfa = compile_constraint(pattern);
+    } catch (const ConstraintError& e) {
+        throw InvalidConfig(e.what());
+    }
+    TokenTable table;
+    const size_t vocab = (size_t)model.config().vocab;
+    table.off.assign(vocab + 1, 0);
+    for (size_t t = 0; t < vocab; ++t) {
+        const std::string bytes = tok.token_bytes((uint32_t)t);
+        table.bytes.insert(table.bytes.end(), bytes.begin(), bytes.end());
+        table.off[t + 1] = (uint32_t)table.bytes.size();
+    }
+    constraint = std::make_unique<DeviceConstraint>(model.device(), std::move(dfa), std::move(table));
+    current = pattern;
+}
+
+void Chat::set_constraint(const std::string& pattern)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_constraint(*model_, tokenizer_, pattern, constraint_pattern_, constraint_);
+}
+
+void Generator::set_constraint(const std::string& pattern)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_constraint(*model_, tokenizer_, pattern, constraint_pattern_, constraint_);
+}
+
 void Chat::set_draft_model(const std::string& path, int draft_tokens)
 {
     std::lock_guard<std::mutex> lock(mutex_);
@@ -529,7 +576,8 @@ std::string Chat::run(const std::string& prompt, const GenerationOverrides& runt
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, 0,
-                               lookup_sampling_ ? LookupConfig().draft_tokens : 0, drafter_.get(), draft_tokens_);
+                               lookup_sampling_ ? LookupConfig().draft_tokens : 0, drafter_.get(), draft_tokens_, constraint_.get(),
+                               &constraint_outcome_);
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -614,7 +662,7 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_,
-                               lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_);
+                               lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_, constraint_.get(), &constraint_outcome_);
 }
 
 size_t Generator::encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bpe.h"
+#include "constraint_kernels.h"
 #include "llm.h"
 #include "registry.h"
 #include "sampling.h"
@@ -106,6 +107,13 @@ public:
     // with its weights as stored and the model's context, and owned by the handle; an empty path or draft_tokens == 0 frees it.
     // While set it takes precedence over prompt lookup.  InvalidConfig for draft_tokens outside 0..7 or another vocabulary.
     void set_draft_model(const std::string& path, int draft_tokens);
+    // Constrained decoding (LlmModel::generate with a constraint): every later request emits only what `pattern` (constraint.h's
+    // syntax) matches in full; an empty pattern restores the plain behaviour.  The token table is built from the handle's
+    // tokenizer (BpeTokenizer::token_bytes over the model's vocabulary) once per pattern and the compiled constraint is kept until
+    // the pattern changes.  While set, requests take the plain loop even when prompt lookup or a draft model is switched on.
+    // InvalidConfig for a pattern the compiler refuses.  Nested or recursive formats (JSON schemas) are out of scope.
+    void set_constraint(const std::string& pattern);
+    ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }  // of the last constrained request
 
 private:
     Chat() = default;
@@ -125,6 +133,9 @@ private:
     bool lookup_sampling_ = false;
     std::unique_ptr<LlmModel> drafter_;
     int draft_tokens_ = 0;
+    std::string constraint_pattern_;
+    std::unique_ptr<DeviceConstraint> constraint_;
+    ConstraintOutcome constraint_outcome_;
     std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
 };
 
@@ -165,6 +176,9 @@ public:
     void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
     // A draft model for generate / stream (Chat::set_draft_model's contract); generate_batch is untouched.
     void set_draft_model(const std::string& path, int draft_tokens);
+    // Constrained decoding for generate / stream (Chat::set_constraint's contract); generate_batch is untouched.
+    void set_constraint(const std::string& pattern);
+    ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }
     // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
     // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
     // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
@@ -210,6 +224,9 @@ private:
     bool lookup_sampling_ = false;
     std::unique_ptr<LlmModel> drafter_;
     int draft_tokens_ = 0;
+    std::string constraint_pattern_;
+    std::unique_ptr<DeviceConstraint> constraint_;
+    ConstraintOutcome constraint_outcome_;
 };
 
 // str::trim (Unicode White_Space at both ends).

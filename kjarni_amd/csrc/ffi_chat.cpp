@@ -808,6 +808,50 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_prompt_lookup_sampling(KjarniC
     return KJARNI_OK;
 }
 
+// A constraint for every later request of the handle (Chat::set_constraint): NULL / "" removes it.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_constraint(KjarniGenerator* gen, const char* pattern)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->set_constraint(pattern ? pattern : ""); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_constraint(KjarniChat* chat, const char* pattern)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->set_constraint(pattern ? pattern : ""); });
+}
+
+static KjarniHipConstraintResult constraint_result(const ConstraintOutcome& o)
+{
+    return KjarniHipConstraintResult{o.final_state, o.device_state, o.accepted ? 1 : 0, o.complete ? 1 : 0, o.violated ? 1 : 0};
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_constraint_result(const KjarniGenerator* gen, KjarniHipConstraintResult* out)
+{
+    if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = constraint_result(gen->inner->constraint_outcome());
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_constraint_result(const KjarniChat* chat, KjarniHipConstraintResult* out)
+{
+    if (!chat || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = constraint_result(chat->inner->constraint_outcome());
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_token_bytes(const KjarniBpeTokenizer* t, uint32_t id, uint8_t* bytes_out, size_t capacity,
+                                                               size_t* n_out)
+{
+    if (!t || !n_out || (capacity && !bytes_out)) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const std::string bytes = t->tok.token_bytes(id);
+        *n_out = bytes.size();
+        if (capacity) std::memcpy(bytes_out, bytes.data(), std::min(capacity, bytes.size()));
+    });
+}
+
 // A draft model owned by the handle (Chat::set_draft_model): NULL / 0 frees it.
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_draft_model(KjarniGenerator* gen, const char* model_dir_or_gguf, int32_t draft_tokens)
 {

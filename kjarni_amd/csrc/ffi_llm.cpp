@@ -11,6 +11,7 @@
 #include "llm_kernels.h"
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
+#include "ffi_constraint.h"
 #include "llm.h"
 #include "gguf.h"
 #include "host_util.h"
@@ -360,6 +361,54 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_sampled(KjarniHipDecod
         const std::vector<uint32_t> ids = lookup ? d->model->generate_lookup_sampled(p, opt, lk, cb, &st) : d->model->generate(p, opt, cb);
         copy_ids_out(ids, ids_out, capacity, n_out);
         if (stats) *stats = KjarniHipLookupStats{st.verify_steps, st.drafted_tokens, st.accepted_tokens, st.single_row_steps};
+    });
+}
+
+// ---- constrained decoding --------------------------------------------------------------------------------------------------------
+
+// kjarni_hip_decoder_generate_sampled's plain loop with options.constraint set; the draws as there.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_constrained(KjarniHipDecoder* d, const KjarniHipConstraint* constraint,
+                                                                      const uint32_t* prompt, size_t n_prompt,
+                                                                      const KjarniHipSamplingOptions* options, KjarniTokenCallbackFn on_token,
+                                                                      void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out,
+                                                                      KjarniHipConstraintResult* result)
+{
+    if (!options || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    if (result) *result = KjarniHipConstraintResult{};
+    if (options->uniforms && options->n_uniforms < options->max_new_tokens) {  // (the options are judged on their own, ahead of the handles)
+        set_last_error("n_uniforms (" + std::to_string(options->n_uniforms) + ") is less than max_new_tokens (" +
+                       std::to_string(options->max_new_tokens) + ")");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!d || !constraint || (n_prompt && !prompt) || (capacity && !ids_out) || (options->n_stop && !options->stop_ids))
+        return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_prompt == 0) throw InvalidConfig("cannot generate from an empty prompt");
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (n_prompt > (size_t)d->model->context())
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
+        GenerateOptions opt = sampling_options(*options);
+        UniformRng rng(options->seed);
+        size_t drawn = 0;
+        const float* u = options->uniforms;
+        const size_t n_u = options->n_uniforms;
+        if (u)
+            opt.uniform = [&drawn, u, n_u] {
+                if (drawn >= n_u) throw std::runtime_error("the draw stream is exhausted: more draws than uniforms");
+                return u[drawn++];
+            };
+        else opt.uniform = [&rng] { return rng.next(); };
+        ConstraintOutcome outcome;
+        opt.constraint = constraint->inner.get();
+        opt.constraint_outcome = &outcome;
+        const std::vector<uint32_t> ids = d->model->generate(std::vector<uint32_t>(prompt, prompt + n_prompt), opt, cb);  // refusals first
+        copy_ids_out(ids, ids_out, capacity, n_out);
+        if (result)
+            *result = KjarniHipConstraintResult{outcome.final_state, outcome.device_state, outcome.accepted ? 1 : 0, outcome.complete ? 1 : 0,
+                                                outcome.violated ? 1 : 0};
     });
 }
 

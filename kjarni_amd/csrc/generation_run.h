@@ -11,6 +11,17 @@
 
 namespace kjarni {
 
+class DeviceConstraint;  // constraint_kernels.h
+
+// How a constrained run ended (LlmModel::generate with GenerateOptions::constraint).
+struct ConstraintOutcome {
+    uint32_t final_state = 0;   // the automaton's state after the emitted tokens, as the host walked it
+    uint32_t device_state = 0;  // ... and as the device held it after the last emitted token (the host checker path: the host's)
+    bool accepted = false;      // final_state is accepting
+    bool complete = false;      // the run ended on a stop id in an accepting state, or in a closed state
+    bool violated = false;      // a token outside the mask was picked (never, for finite logits)
+};
+
 // One run of run_generation_loop (generator.rs:228-381).
 struct GenerateOptions {
     size_t max_new_tokens = 0;
@@ -21,6 +32,9 @@ struct GenerateOptions {
     SamplingParams sampling;
     std::vector<uint32_t> stop_ids;  // empty: every eos_token_id of config.json
     std::function<float()> uniform;  // the draw in [0, 1) for each sampled token
+    // Constrained decoding: generate() alone takes it (the lane, lookup and draft entry points refuse it).
+    const DeviceConstraint* constraint = nullptr;
+    ConstraintOutcome* constraint_outcome = nullptr;  // may be null
 };
 
 // What a loop does with the last token of a run that ends on max_new_tokens.  The choice shows in the cache length a call

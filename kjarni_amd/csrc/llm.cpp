@@ -15,6 +15,7 @@
 #include "decoder_embed_kernels.h"
 #include "draft_model_kernels.h"
 #include "llm_kernels.h"
+#include "constraint_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
 #include "safetensors.h"
@@ -149,6 +150,7 @@ LlmModel::~LlmModel()
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (graph_) (void)hipGraphExecDestroy(graph_);
+    if (cgraph_) (void)hipGraphExecDestroy(cgraph_);
     drop_graphs(lane_graphs_);
     drop_graphs(lookup_graphs_);
     drop_graphs(lookup_sampled_graphs_);
@@ -1087,6 +1089,25 @@ hipGraphExec_t LlmModel::step_graph()
     });
 }
 
+void LlmModel::ensure_constraint()
+{
+    if (cview_) return;
+    cview_ = reinterpret_cast<ConstraintView*>(dalloc((sizeof(ConstraintView) + 3) / 4));
+    crow_ = reinterpret_cast<ConstraintRow*>(dalloc((sizeof(ConstraintRow) + 3) / 4));
+    cstate_log_ = reinterpret_cast<uint32_t*>(dalloc((size_t)hist_cap_));
+}
+
+hipGraphExec_t LlmModel::constrained_step_graph()
+{
+    if (cgraph_) return cgraph_;
+    return cgraph_ = capture_graph(stream_, [&] {
+        pass(reinterpret_cast<const uint32_t*>(token_), 1, true);
+        hip_check(launch_constraint_apply(logits_, cfg_.vocab, 1, cfg_.vocab, cview_, crow_, stream_), "constraint apply");
+        enqueue_argmax(true);
+        hip_check(launch_constraint_advance(token_, 1, cview_, crow_, cstate_log_, count_, hist_cap_, stream_), "constraint advance");
+    });
+}
+
 void LlmModel::ensure_host_logits()
 {
     if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
@@ -1125,9 +1146,60 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw std::runtime_error("prompt does not fit the context");
     if (opt.sample && !opt.uniform) throw std::runtime_error("sampling needs a uniform source");
+    const DeviceConstraint* con = opt.constraint;
+    if (con) {  // everything that can be refused is refused before any GPU work
+        if (con->device() != device_)
+            throw InvalidConfig("the constraint lives on device " + std::to_string(con->device()) + ", the model on device " + std::to_string(device_));
+        if (con->vocab() != cfg_.vocab)
+            throw InvalidConfig("the constraint's token table has " + std::to_string(con->vocab()) + " tokens, the model's vocabulary " +
+                                std::to_string(cfg_.vocab));
+        con->check_states(opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids);
+    }
     begin_sequence(prompt);
     std::vector<uint32_t> out;
     GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
+    // The constrained run: the host walks its own copy of the automaton over the tokens it takes (`hq`), the device holds the
+    // state the kernels read (crow_).  take() is run.accept() under the constraint: a stop id ends the run (complete when the
+    // state is accepting), any other token moves hq, and a closed state ends the run behind the token.
+    ConstraintOutcome outcome;
+    uint32_t hq = con ? con->dfa().start : 0;
+    if (con) {
+        ensure_constraint();
+        const ConstraintView view = con->view(run.stops);
+        const ConstraintRow row = {hq, 0, 0, 0};
+        hip_check(hipMemcpyAsync(cview_, &view, sizeof(view), hipMemcpyHostToDevice, stream_), "H2D constraint view");
+        hip_check(hipMemcpyAsync(crow_, &row, sizeof(row), hipMemcpyHostToDevice, stream_), "H2D constraint state");
+        hip_check(hipStreamSynchronize(stream_), "sync");  // (both sources are locals)
+        outcome.device_state = hq;
+    }
+    const auto take = [&](uint32_t tok) -> bool {
+        if (!con) return run.accept(tok, on_token);
+        if (!run.wants_token()) {
+            run.done = true;
+            return false;
+        }
+        if (run.is_stop(tok)) {
+            (con->dfa().accepting[hq] ? outcome.complete : outcome.violated) = true;
+            run.done = true;
+            return false;
+        }
+        const uint32_t next = con->allows(hq, tok) ? con->step_token(hq, tok) : (uint32_t)kConstraintDead;
+        if (next == kConstraintDead) {
+            outcome.violated = true;
+            run.done = true;
+            return false;
+        }
+        hq = next;
+        const bool taken = run.accept(tok, on_token);
+        if (con->dfa().closed[hq]) outcome.complete = run.done = true;
+        return taken;
+    };
+    const auto finish = [&] {
+        if (!con) return;
+        outcome.final_state = hq;
+        outcome.accepted = con->dfa().accepting[hq] != 0;
+        if (opt.constraint_outcome) *opt.constraint_outcome = outcome;
+    };
     const float repetition_penalty = opt.repetition_penalty;
     const int no_repeat_ngram = opt.no_repeat_ngram;
     const bool processors = repetition_penalty != 1.0f || no_repeat_ngram > 0;
@@ -1169,6 +1241,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         }
         int skip_candidates = 0;
         while (run.wants_token()) {
+            if (con) hip_check(launch_constraint_apply(logits_, (int64_t)vocab, 1, (int)vocab, cview_, crow_, stream_), "constraint apply");
             if (processors)
                 hip_check(launch_logits_processors(logits_, (int)vocab, samp_tokens_, (int)run.all.size(), samp_counts_, samp_distinct_,
                                                    samp_ndistinct_, repetition_penalty, no_repeat_ngram, stream_), "logits processors");
@@ -1204,9 +1277,23 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             }
             // LastToken::Fed: one step per emitted token, the last of max_new_tokens included -- under an explicit max_len past
             // prompt + max_new_tokens; with the default max_len that token fills context_limit and is not fed
-            if (!run.accept(next, on_token) || !run.feeds_accepted(LastToken::Fed)) break;
+            if (!take(next)) break;
+            if (con) {  // the device's automaton takes the host's choice (fed or not, so that it ends where the host's does)
+                const int32_t tok = (int32_t)next;
+                hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
+                hip_check(launch_constraint_advance(token_, 1, cview_, crow_, nullptr, nullptr, 0, stream_), "constraint advance");
+            }
+            if (outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;  // (a closed state: nothing follows the token)
             feed(next);
         }
+        if (con) {
+            ConstraintRow row = {};
+            hip_check(hipMemcpyAsync(&row, crow_, sizeof(row), hipMemcpyDeviceToHost, stream_), "D2H constraint state");
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            outcome.device_state = row.state;
+            outcome.violated = outcome.violated || row.violated != 0;
+        }
+        finish();
         leave_resident(run.all);
         return out;
     }
@@ -1222,6 +1309,9 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         while (run.wants_token()) {
             hip_check(hipMemcpyAsync(lg, logits_, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
             hip_check(hipStreamSynchronize(stream_), "sync");
+            if (con)  // the same mask from the host's DFA and token table
+                for (size_t v = 0; v < vocab; ++v)
+                    if (!(run.is_stop((uint32_t)v) ? con->dfa().accepting[hq] != 0 : con->allows(hq, (uint32_t)v))) lg[v] = -INFINITY;
             apply_repetition_penalty(lg, vocab, run.all, repetition_penalty);
             if (no_repeat_ngram > 0) apply_no_repeat_ngram(lg, vocab, run.all, (size_t)no_repeat_ngram);
             uint32_t next;
@@ -1232,9 +1322,11 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
                 next = argmax_last(lg, vocab);
             }
             // LastToken::Fed, as the loop above
-            if (!run.accept(next, on_token) || !run.feeds_accepted(LastToken::Fed)) break;
+            if (!take(next) || outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;
             feed(next);
         }
+        outcome.device_state = hq;  // (no device automaton on this path)
+        finish();
         leave_resident(run.all);
         return out;
     }
@@ -1242,30 +1334,46 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     // Plain greedy: token, position and key count stay on the device; one graph replay per token, the host
     // looks every few steps.  Tokens computed past a stop token / a stop request are discarded.  The device feeds itself:
     // a burst is sized by what is left of max_new_tokens, so the last token of max_new_tokens is not fed (LastToken::NotFed).
+    // Constrained: the chain is pass -> apply -> argmax -> advance; the host steps its own automaton per drained token and ends the
+    // run at a stop id, a closed state or the limits, discarding what the device ran past that point as it does past a stop id.
+    if (con) hip_check(launch_constraint_apply(logits_, (int64_t)vocab, 1, (int)vocab, cview_, crow_, stream_), "constraint apply");
     enqueue_argmax(true);
+    if (con) hip_check(launch_constraint_advance(token_, 1, cview_, crow_, cstate_log_, count_, hist_cap_, stream_), "constraint advance");
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     std::vector<int32_t> hist((size_t)hist_cap_);
+    std::vector<uint32_t> states(con ? (size_t)hist_cap_ : 0);
     size_t produced = 0, seen = 0;
     auto drain = [&](size_t upto) {
-        for (; seen < upto && !run.done; ++seen) run.accept((uint32_t)hist[seen], on_token);
+        for (; seen < upto && !run.done; ++seen)
+            if (take((uint32_t)hist[seen]) && con) outcome.device_state = states[seen];
     };
-    hip_check(hipMemcpyAsync(hist.data(), hist_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H token");
-    hip_check(hipStreamSynchronize(stream_), "sync");
+    const auto fetch = [&](size_t first, size_t n) {  // the picks [first, first + n) and, constrained, the states behind them
+        hip_check(hipMemcpyAsync(hist.data() + first, hist_ + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
+        if (con)
+            hip_check(hipMemcpyAsync(states.data() + first, cstate_log_ + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H states");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+    };
+    fetch(0, 1);
     produced = 1;
     drain(1);
-    if (!run.done) exec = step_graph();
+    if (!run.done) exec = con ? constrained_step_graph() : step_graph();
     const size_t burst = on_token ? 4 : 16;
     while (!run.done) {
         size_t steps = std::min(burst, run.max_new - out.size());
         steps = std::min(steps, (size_t)cache_cap_ - (size_t)cache_len_);
         if (steps == 0) break;
         for (size_t i = 0; i < steps; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-        hip_check(hipMemcpyAsync(hist.data() + produced, hist_ + produced, steps * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
-        hip_check(hipStreamSynchronize(stream_), "sync");
+        fetch(produced, steps);
         produced += steps;
         cache_len_ += (int)steps;
         drain(produced);
     }
+    if (con) {
+        ConstraintRow row = {};
+        hip_check(hipMemcpy(&row, crow_, sizeof(row), hipMemcpyDeviceToHost), "D2H constraint state");
+        outcome.violated = outcome.violated || row.violated != 0;  // (steps past the run's end included: they pick under the mask too)
+    }
+    finish();
     leave_resident(run.all);  // (the burst's rows past the last emitted token stay behind cache_len_, uncounted)
     return out;
 }
@@ -1568,6 +1676,8 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (lanes == 0) lanes = kLanes;
     if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+    for (const LaneRequest& r : reqs)
+        if (r.options.constraint) throw InvalidConfig("generate_lanes does not take a constraint (generate does)");
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
     std::vector<std::vector<uint32_t>> out(reqs.size());
@@ -1955,6 +2065,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
 {
     if (stats) *stats = LookupStats();
     check_lookup_config(lk);
+    if (opt.constraint) throw InvalidConfig("generate_lookup does not take a constraint (generate does)");
     if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0) return generate(prompt, opt, on_token);  // not applicable
     DraftSource src;
     src.ngram_max = lk.ngram_max;
@@ -2172,6 +2283,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
 {
     if (stats) *stats = LookupStats();
     check_lookup_config(lk);
+    if (opt.constraint) throw InvalidConfig("generate_lookup_sampled does not take a constraint (generate does)");
     if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
     if (!opt.sample) return generate_lookup(prompt, opt, lk, on_token, stats);
     DraftSource src;
@@ -2293,6 +2405,7 @@ std::vector<uint32_t> LlmModel::generate_draft(LlmModel* drafter, const std::vec
 {
     if (stats) *stats = LookupStats();
     check_draft_pair(drafter, draft_tokens);
+    if (opt.constraint) throw InvalidConfig("generate_draft does not take a constraint (generate does)");
     if (prompt.empty()) throw InvalidConfig("prompt must not be empty");
     if (prompt.size() > (size_t)cache_cap_)
         throw InvalidConfig("prompt (" + std::to_string(prompt.size()) + " tokens) does not fit the context of " + std::to_string(cache_cap_) +

@@ -52,6 +52,8 @@ struct LaneRequest {
 };
 
 struct LlmLaneState;  // llm_kernels.h
+struct ConstraintView;  // constraint_kernels.h
+struct ConstraintRow;
 struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
@@ -225,6 +227,15 @@ public:
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, size_t max_new_tokens, float repetition_penalty,
                                    int no_repeat_ngram, const std::function<bool(uint32_t)>& on_token);
     // The same loop with a sampling strategy, explicit stop tokens and the max_length cap.
+    // options.constraint (constraint_kernels.h: a byte DFA with its token mask on this model's device, over this model's
+    // vocabulary): after every token the bytes of the emitted tokens are a prefix of a string the pattern matches; in an accepting
+    // state the stop ids are legal.  Every step applies the mask before any logits processor and before the pick or the cut
+    // (launch_constraint_apply), and the automaton's state lives on the device next to the token (launch_constraint_advance):
+    // plain greedy replays pass -> apply -> argmax -> advance as one captured chain in the usual bursts and the host walks its own
+    // copy of the DFA over the drained tokens; the device-sampling loop runs apply, the processors, then argmax or the cut; with
+    // device sampling off the host masks its copy of the logits from the DFA and the token table.  A run also ends, without a stop
+    // token, when the state is closed.  Throws InvalidConfig before any GPU work: a constraint of another device or vocabulary,
+    // more than 16 stop ids, a state from which nothing can be emitted (DeviceConstraint::check_states).
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
                                    const std::function<bool(uint32_t)>& on_token);
 
@@ -429,6 +440,8 @@ private:
     void score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, float* lp, uint32_t* ids, float* tlp);
     void enqueue_argmax(bool record);
     hipGraphExec_t step_graph();
+    void ensure_constraint();                 // the model's descriptor, row state and state log
+    hipGraphExec_t constrained_step_graph();  // pass -> apply -> argmax(record) -> advance, captured once (it reads cview_)
 
     struct Layer {
         void *wqkv, *wo, *gate, *up, *down;  // GPT-2: c_attn, attn.c_proj, mlp.c_fc (in `gate`), mlp.c_proj (in `down`), as [out, in]
@@ -526,6 +539,12 @@ private:
     uint64_t tile_gemm_calls_ = 0;
     hipStream_t stream_ = nullptr;
     hipGraphExec_t graph_ = nullptr;
+    // constrained decoding (allocated on first use): the descriptor of the running call's constraint, its row state, the state
+    // after every recorded pick (beside hist_), and the captured constrained step
+    ConstraintView* cview_ = nullptr;
+    ConstraintRow* crow_ = nullptr;
+    uint32_t* cstate_log_ = nullptr;
+    hipGraphExec_t cgraph_ = nullptr;
     // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
     // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
     std::vector<float*> lane_k_, lane_v_;

@@ -375,6 +375,34 @@ class HipDecoder:
         stats = {k: int(getattr(st, k)) for k, _ in _ffi.KjarniHipLookupStats._fields_}
         return out[:min(n.value, out.size)].tolist(), stats
 
+    def generate_constrained(self, constraint, prompt: Sequence[int], max_new_tokens: int, sample: bool = False,
+                             temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                             min_p: Optional[float] = None, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0,
+                             stop_ids: Optional[Sequence[int]] = None, uniforms=None, seed: int = 0,
+                             on_token: Optional[Callable[[int], Optional[bool]]] = None):
+        """generate() / generate_sampled()'s plain loop under a kjarni_amd.constraints.Constraint: (ids, result).  After every
+        token the bytes of the emitted tokens are a prefix of a string the pattern matches in full; in an accepting state the
+        stop ids are legal; a closed state ends the run without a stop token.  result: final_state, device_state, accepted,
+        complete, violated (kjarni_hip.h: KjarniHipConstraintResult)."""
+        from .constraints import result_dict
+        p = np.ascontiguousarray(prompt, np.uint32)
+        out = np.empty(max(max_new_tokens, 1), np.uint32)
+        n = C.c_size_t(0)
+        o, keep = self._sampling_options(max_new_tokens, sample, temperature, top_k, top_p, min_p, repetition_penalty, no_repeat_ngram,
+                                         stop_ids, uniforms, seed)
+        res = _ffi.KjarniHipConstraintResult()
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_constrained(self._h, constraint._h if constraint is not None else None,
+                                                                  u32(p) if p.size else None, p.size, C.byref(o), fn, None, u32(out), out.size,
+                                                                  C.byref(n), C.byref(res)))
+        del keep
+        return out[:min(n.value, out.size)].tolist(), result_dict(res)
+
     def verify_step_sampled(self, token: int, draft: Sequence[int], uniforms, rows: Optional[int] = None, temperature: float = 1.0,
                             top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                             repetition_penalty: float = 1.0, history: Optional[Sequence[int]] = None, fetch: bool = True):

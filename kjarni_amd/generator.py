@@ -114,6 +114,21 @@ class Generator:
         path = model_dir_or_gguf.encode("utf-8") if model_dir_or_gguf else None
         check_error(lib().kjarni_hip_generator_set_draft_model(self._handle, path, int(draft_tokens)))
 
+    def set_constraint(self, pattern: Optional[str]):
+        """Constrained decoding for generate() / stream(): every later request emits only text that `pattern` matches in full
+        (kjarni_amd.constraints has builders: choices, integer, number, json_string, json_object); None restores the plain
+        behaviour.  The token table comes from this handle's tokenizer, once per pattern.  While set, requests take the plain
+        loop even when prompt lookup or a draft model is switched on; generate_batch() is not constrained.  Nested or recursive
+        JSON schemas are out of scope."""
+        check_error(lib().kjarni_hip_generator_set_constraint(self._handle, pattern.encode("utf-8") if pattern else None))
+
+    def constraint_result(self):
+        """How the last constrained request ended: final_state, device_state, accepted, complete, violated."""
+        from .constraints import result_dict
+        r = _ffi.KjarniHipConstraintResult()
+        check_error(lib().kjarni_hip_generator_constraint_result(self._handle, C.byref(r)))
+        return result_dict(r)
+
     def set_prefix_reuse(self, on: bool):
         """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): score() over several
         continuations of one context prefills the context once, generate_batch() the prefix its prompts share."""

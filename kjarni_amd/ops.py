@@ -476,6 +476,53 @@ def logits_processors(logits, tokens, n_bulk: int, repetition_penalty: float = 1
     return out
 
 
+def constraint_mask(trans, tok_off, tok_bytes, device: int = 0):
+    """The constrained-decoding mask build alone: trans uint16 [S, 256], the token table (tok_off [V + 1], tok_bytes).  Returns
+    (mask uint64 [S, ceil(V / 64)], counts uint32 [S])."""
+    tr = np.ascontiguousarray(trans, np.uint16)
+    off = np.ascontiguousarray(tok_off, np.uint32)
+    by = np.ascontiguousarray(tok_bytes, np.uint8)
+    S, V = tr.shape[0], off.size - 1
+    mask = np.empty((S, (V + 63) // 64), np.uint64)
+    counts = np.empty(S, np.uint32)
+    check_error(lib().kjarni_hip_op_constraint_mask(device, tr.ctypes.data_as(C.POINTER(C.c_uint16)), S, off.ctypes.data_as(_ffi._u32p),
+                                                    by.ctypes.data_as(C.POINTER(C.c_uint8)) if by.size else None, V,
+                                                    mask.ctypes.data_as(C.POINTER(C.c_uint64)), counts.ctypes.data_as(_ffi._u32p)))
+    return mask, counts
+
+
+def constraint_apply(constraint, logits, states, done, stop_ids=(), device: int = 0):
+    """The mask applied to logits [rows, ld] (ld >= the constraint's vocabulary) with a state and a done flag per row: the
+    whole buffer back, the columns past the vocabulary included."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    rows, ld = lg.shape
+    st = np.ascontiguousarray(states, np.uint32)
+    dn = np.ascontiguousarray(done, np.int32)
+    sp = np.ascontiguousarray(stop_ids, np.uint32)
+    if st.size != rows or dn.size != rows:
+        raise ValueError("one state and one done flag per row")
+    out = np.empty_like(lg)
+    check_error(lib().kjarni_hip_op_constraint_apply(device, constraint._h, _f(lg), rows, ld, st.ctypes.data_as(_ffi._u32p),
+                                                     dn.ctypes.data_as(_i32p), sp.ctypes.data_as(_ffi._u32p) if sp.size else None, sp.size,
+                                                     _f(out)))
+    return out
+
+
+def constraint_advance(constraint, picked, states, done, stop_ids=(), device: int = 0):
+    """The automaton step alone: (states, done, violated) after the picks, one per row."""
+    pk = np.ascontiguousarray(picked, np.int32)
+    st = np.array(states, np.uint32)
+    dn = np.array(done, np.int32)
+    sp = np.ascontiguousarray(stop_ids, np.uint32)
+    if st.size != pk.size or dn.size != pk.size:
+        raise ValueError("one state and one done flag per pick")
+    bad = np.full(pk.size, -2, np.int32)
+    check_error(lib().kjarni_hip_op_constraint_advance(device, constraint._h, pk.ctypes.data_as(_i32p), pk.size, st.ctypes.data_as(_ffi._u32p),
+                                                       dn.ctypes.data_as(_i32p), sp.ctypes.data_as(_ffi._u32p) if sp.size else None, sp.size,
+                                                       bad.ctypes.data_as(_i32p)))
+    return st, dn, bad
+
+
 def sample_candidates(rows, top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                       capacity: int = 4096, device: int = 0):
     """The sampler's device cut over each of `rows` (1-D logits arrays, possibly of different lengths), in order, on one

@@ -39,6 +39,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            (rows - 1) drafter steps (what the chain is made of), the break-even accepted tokens per round, and end-to-end
            tokens/s with a copy of the target as drafter (every draft accepted) and with an unrelated checkpoint; a 4-layer
            drafter of the same width for the per-round cost only.  Ends of a range, not workloads.
+  llm_constraint  (only on request) constrained decoding (HipDecoder.generate_constrained) against the plain loop of the same build,
+           alternated twice in one process, greedy and sampled: Llama-3.2-1B shape (bf16) and gpt2-small (bf16), a pattern that
+           masks nothing (the ids are the plain loop's, asserted), so the ratio is the cost of the two launches per step; and the
+           mask build of a 100-state pattern at each shape's vocabulary.  The lines also go to profiles/llm_constraint_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1424,6 +1428,94 @@ def main():
         gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
         dec = kjarni_amd.HipDecoder(gd)
         measure("gpt2-small shape, bf16 weights (n_ctx 4096)", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+    if "llm_constraint" in which:
+        # Method (as llm_lookup): one process on one box, everything warmed first; the plain loop of the same build -- the yardstick
+        # -- alternates with the constrained loop, twice, greedy and sampled (the family-neutral config below, one seed).  A decode
+        # window is a whole generation minus the same call cut after its first token.  The pattern is [ -~]* over a table in which
+        # every token is printable ASCII: nothing is masked, so both loops emit the same ids (asserted) and the difference is the
+        # two launches per step (apply, advance) alone.  The mask build: a 100-state pattern, [a-z]{99}, over seeded lower-case
+        # tokens of 1..8 bytes at the shape's vocabulary: the whole constructor (upload, kernel, counts, the reachable states) and
+        # the kernel entry alone (kjarni_hip_op_constraint_mask: upload, kernel, the mask copied back), medians of 3.
+        from kjarni_amd import constraints as KC
+        from kjarni_amd import ops as KO
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        n_new = int(os.environ.get("KJARNI_CONSTRAINT_TOKENS", "256"))
+        out_path = os.path.join(ROOT, "profiles", "llm_constraint_bench.jsonl")
+        lines = []
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+        SAMPLING = dict(temperature=0.8, top_k=40, top_p=0.9, min_p=0.05)
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, vocab, lo, dtype):
+            prompt = rng.integers(lo, vocab, 128).tolist()
+            con = KC.Constraint(r"[ -~]*", [("t%d " % i).encode() for i in range(vocab)])
+            legs = {
+                "greedy_plain": lambda n: dec.generate(prompt, n),
+                "greedy_constrained": lambda n: dec.generate_constrained(con, prompt, n)[0],
+                "sampled_plain": lambda n: dec.generate_sampled(prompt, n, sample=True, seed=7, **SAMPLING)[0],
+                "sampled_constrained": lambda n: dec.generate_constrained(con, prompt, n, sample=True, seed=7, **SAMPLING)[0],
+            }
+            for fn in legs.values():
+                fn(8)
+            rate = {k: [] for k in legs}
+            outs = {}
+            for rep in range(2):
+                for k, fn in legs.items():
+                    dt, out = window(lambda: fn(n_new), lambda: fn(1))
+                    assert len(out) == n_new, (k, len(out))
+                    rate[k].append((n_new - 1) / dt)
+                    outs[k] = out
+            assert outs["greedy_plain"] == outs["greedy_constrained"] and outs["sampled_plain"] == outs["sampled_constrained"]
+            words = [bytes(rng.integers(97, 123, int(rng.integers(1, 9))).astype(np.uint8)) for _ in range(vocab)]
+            rx = KC.Regex(r"[a-z]{99}")
+            assert rx.states == 100
+            off, data = KC.token_table(words)
+            new_ms, op_ms = [], []
+            for _ in range(4):   # (the first run of each is the warm-up)
+                t0 = time.perf_counter()
+                c = KC.Constraint(rx, words)
+                new_ms.append((time.perf_counter() - t0) * 1e3)
+                c.close()
+                t0 = time.perf_counter()
+                KO.constraint_mask(rx.trans, off, data)
+                op_ms.append((time.perf_counter() - t0) * 1e3)
+            g, s = med(rate["greedy_constrained"]) / med(rate["greedy_plain"]), med(rate["sampled_constrained"]) / med(rate["sampled_plain"])
+            line = {"metric": f"constrained decoding, {label}", "unit": "constrained / plain tokens per second, greedy", "value": round(g, 4),
+                    "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"random init, one 128-token prompt, {n_new} generated tokens; the plain and the constrained loop "
+                                           "alternated twice in one process, greedy and sampled (temperature 0.8, top-k 40, top-p 0.9, min-p "
+                                           "0.05, one seed); pattern [ -~]* over an all-ASCII table: nothing masked, ids equal (asserted)"},
+                    "tokens_per_s": {k: {"median": round(med(v), 1), "runs": [round(x, 1) for x in v]} for k, v in rate.items()},
+                    "sampled_constrained_over_plain": round(s, 4),
+                    "mask_build_100_states": {"vocab": vocab, "constructor_ms": round(med(new_ms[1:]), 3), "kernel_entry_ms": round(med(op_ms[1:]), 3),
+                                              "mask_bytes": 100 * ((vocab + 63) // 64) * 8},
+                    "weight_bytes": dec.weight_bytes}
+            lines.append(line)
+            emit(line)
+
+        d = os.path.join(tmp, "llama-1b-constraint")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, synth.LLAMA_1B["vocab_size"], 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small-constraint")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        dec = kjarni_amd.HipDecoder(gd)
+        measure("gpt2-small shape, bf16 weights", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
         del dec
         with open(out_path, "w") as f:
             for line in lines:
