@@ -499,7 +499,17 @@ KjarniErrorCode kjarni_bytelevel_decode(const char* tokenizer_json_path, const u
  * model.safetensors with the HF tensor names of llama/config.rs:283-330.  weights_dtype: 0 = as stored (BF16 stays
  * bf16 in HBM, other dtypes are widened to f32), 1 = f32, 2 = bf16 (f32 rounded to nearest even).  Arithmetic,
  * activations and the KV cache are f32 either way, as in the reference's bf16 LinearLayer.  max_context <= 0 =
- * max_position_embeddings.  No tokenizer is involved: prompts and results are token ids. */
+ * max_position_embeddings.  No tokenizer is involved: prompts and results are token ids.
+ * FP8 checkpoints (llama, qwen2, mistral, qwen3; single file or sharded): a linear weight `X.weight` of dtype F8_E4M3 (OCP
+ * e4m3fn) beside exactly one scale tensor, `X.weight_scale_inv` or `X.weight_scale` (F32, BF16 or F16; both names mean
+ * w = decode(code) * scale).  The scale's shape decides its kind: one element = per tensor, [n] or [n, 1] = per output channel,
+ * [ceil(n / 128), k / 128] = 128 x 128 blocks (k % 128 == 0; n need not be a multiple of 128); every kind needs k % 16 == 0.
+ * quantization_config.fmt, when present, must be "e4m3" and quantization_config.weight_block_size, when present, [128, 128];
+ * input_scale tensors and activation_scheme are not read: the arithmetic is weight-only, f32 activations x dequantized weights.
+ * weights_dtype 0 keeps the codes and f32 scales in HBM when the seven matrices of every layer (q/k/v/o_proj, gate/up/down_proj)
+ * are all FP8 (a layer that mixes FP8 with another dtype is refused; 1 or 2 loads such a file); the embedding table and lm_head
+ * stay as stored.  1 dequantizes to f32, 2 dequantizes and rounds to bf16.  A missing scale, both scale names, a scale shape that
+ * fits no kind, another block size, another fmt and a NaN code (0x7F, 0xFF) in a weight are load errors that name the tensor. */
 typedef struct KjarniHipDecoder KjarniHipDecoder;
 KjarniErrorCode kjarni_hip_decoder_load(const char* model_dir, int32_t device, int32_t weights_dtype, int32_t max_context,
                                         KjarniHipDecoder** out);
@@ -523,7 +533,9 @@ KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder* decoder, int3
 /* GGUF checkpoints (model_dir: a `.gguf` file, or a directory without safetensors that holds one; weights_dtype 0 keeps
  * Q8_0 / Q4_K / Q6_K matrices quantized in HBM, 1 dequantizes everything to f32, 2 to bf16).
  * config_json: the resolved config (config.json, or the one synthesized from GGUF metadata); free with kjarni_string_free.
- * weight_bytes_by_type: out[t] = device bytes of weights held in GGML type t (0 F32, 8 Q8_0, 12 Q4_K, 14 Q6_K, 30 BF16), t < n. */
+ * weight_bytes_by_type: out[t] = device bytes of weights held in GGML type t (0 F32, 8 Q8_0, 12 Q4_K, 14 Q6_K, 30 BF16), t < n;
+ * out[KJARNI_HIP_WEIGHT_TYPE_F8_E4M3] = the FP8 codes of an FP8 checkpoint (their scales count as F32). */
+#define KJARNI_HIP_WEIGHT_TYPE_F8_E4M3 31 /* no GGML type in use here has this number */
 KjarniErrorCode kjarni_hip_decoder_config_json(const KjarniHipDecoder* decoder, char** out);
 KjarniErrorCode kjarni_hip_decoder_weight_bytes_by_type(const KjarniHipDecoder* decoder, uint64_t* out, size_t n);
 /* Host-only GGUF views: the synthesized decoder config, and one tensor by its HF name, dequantized to f32 in HF row order
@@ -536,6 +548,17 @@ KjarniErrorCode kjarni_gguf_tensor_f32(const char* path, const char* hf_name, fl
  * prompt route (dequantized weights, f32 matrix cores). */
 KjarniErrorCode kjarni_hip_op_linear_ggml(int32_t device, const float* x, int64_t m, const void* blocks, int32_t ggml_type, int32_t n,
                                           int32_t k, float* y);
+/* Host-only view of an FP8 checkpoint (model_dir as kjarni_hip_decoder_load; no device is needed): the F8_E4M3 matrix `hf_name`
+ * read and dequantized as the loader does it, out[j, i] = decode(code) * scale in f32, with all of the loader's refusals
+ * (*n_out = elements, may exceed capacity; shape_out[0..1] = rows, cols; *ndim_out = 2). */
+KjarniErrorCode kjarni_fp8_tensor_f32(const char* model_dir, const char* hf_name, float* out, size_t capacity, size_t* n_out,
+                                      int64_t* shape_out, int32_t* ndim_out);
+/* y[m, n] = x[m, k] . W^T with W given as FP8 e4m3fn codes [n, k] and f32 scales [scale_rows, scale_cols] ([1, 1] per tensor,
+ * [n, 1] per channel, [ceil(n / 128), k / 128] block) on host memory, through the decoder's FP8 kernels: m < 24 in 8-row passes
+ * of the weight-streaming projection (k % 16 == 0), m >= 24 through the prompt route (weights dequantized to f32, f32 matrix
+ * cores; k % 32 == 0).  A NaN code or a scale shape that fits no kind is KJARNI_ERROR_INVALID_CONFIG. */
+KjarniErrorCode kjarni_hip_op_linear_fp8(int32_t device, const float* x, int64_t m, const void* codes, const float* scale,
+                                         int32_t scale_rows, int32_t scale_cols, int32_t n, int32_t k, float* y);
 /* CpuDecoder::forward + final norm + lm head (llama/cpu_decoder.rs:196-219): appends n tokens to the cache.  Fewer
  * than 24 tokens run 8 rows at a time; longer prompts (when the geometry allows) go through the matrix-core route in
  * 2 048-row chunks.  hidden_out receives the final-normed rows of the LAST 8-row block, f32 [((n-1) mod 8) + 1, hidden];

@@ -3,6 +3,8 @@
 // generator.rs:228-381) plus a BPE tokenizer and chat templates, which are not built here.
 #include <cstddef>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <mutex>
 
 #include "decoder_embed_kernels.h"
@@ -13,6 +15,7 @@
 #include "ffi_common.h"
 #include "ffi_constraint.h"
 #include "llm.h"
+#include "fp8_weights.h"
 #include "gguf.h"
 #include "host_util.h"
 
@@ -850,6 +853,36 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_weight_bytes_by_type(const Kjar
     if (!d || (n && !out)) return KJARNI_ERROR_NULL_POINTER;
     for (size_t t = 0; t < n; ++t) out[t] = d->model->weight_bytes_of_type((int)t);
     return KJARNI_OK;
+}
+
+static_assert(KJARNI_HIP_WEIGHT_TYPE_F8_E4M3 == kFp8WeightType && KJARNI_HIP_WEIGHT_TYPE_F8_E4M3 < 32, "the FP8 entry of the per-type byte counts");
+
+KJARNI_EXPORT KjarniErrorCode kjarni_fp8_tensor_f32(const char* model_dir, const char* hf_name, float* out, size_t capacity, size_t* n_out,
+                                                    int64_t* shape_out, int32_t* ndim_out)
+{
+    if (!model_dir || !hf_name || !n_out || (capacity && !out)) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    return guarded(KJARNI_ERROR_LOAD_FAILED, [&] {
+        const std::string dir = model_dir;
+        SafeTensors st;
+        st.open_dir(dir);
+        std::string config;
+        {
+            std::ifstream f(dir + "/config.json", std::ios::binary);
+            if (f) config.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        }
+        const Fp8Checkpoint f8(st, config);
+        if (!st.contains(hf_name)) throw std::runtime_error(std::string("tensor not found: ") + hf_name);
+        std::vector<float> v;
+        const std::vector<int64_t> shape = f8.read_f32(hf_name, v);
+        *n_out = v.size();
+        if (ndim_out) *ndim_out = (int32_t)shape.size();
+        if (shape_out) {
+            shape_out[0] = shape[0];
+            shape_out[1] = shape[1];
+        }
+        if (capacity) std::memcpy(out, v.data(), std::min(capacity, v.size()) * sizeof(float));
+    });
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_gguf_config_json(const char* path, char** out)

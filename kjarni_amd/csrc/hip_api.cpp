@@ -1450,6 +1450,46 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_ggml(int32_t device, const fl
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_fp8(int32_t device, const float* x, int64_t m, const void* codes, const float* scale,
+                                                       int32_t scale_rows, int32_t scale_cols, int32_t n, int32_t k, float* y)
+{
+    if (!x || !codes || !scale || !y) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (m < 0 || n <= 0 || k <= 0 || k % 16 != 0) throw InvalidConfig("invalid FP8 linear dimensions (n, k >= 1, k % 16 == 0)");
+        const int kind = fp8_scale_kind(n, k, scale_rows, scale_cols);
+        if (kind < 0)
+            throw InvalidConfig("FP8 linear: a scale of shape [" + std::to_string(scale_rows) + ", " + std::to_string(scale_cols) +
+                                "] is neither [1, 1] (per tensor), [n, 1] (per channel) nor [ceil(n / 128), k / 128] (block)");
+        const uint8_t* c = static_cast<const uint8_t*>(codes);
+        for (int64_t i = 0, e = (int64_t)n * k; i < e; ++i)
+            if ((c[i] & 0x7F) == 0x7F) throw InvalidConfig("FP8 linear: NaN code at element " + std::to_string(i));
+        use_device(device);
+        if (m == 0) return;
+        const size_t wb = (size_t)n * k, sb = (size_t)scale_rows * scale_cols * 4, xb = (size_t)m * k * 4, yb = (size_t)m * n * 4;
+        DeviceBuf wd(wb), sd(sb), xd(xb), yd(yb);
+        hip_check(hipMemcpy(wd.p, codes, wb, hipMemcpyHostToDevice), "H2D codes");
+        hip_check(hipMemcpy(sd.p, scale, sb, hipMemcpyHostToDevice), "H2D scales");
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        Fp8Mat W;
+        W.n = n; W.k = k; W.codes = static_cast<const uint8_t*>(wd.p); W.scale = static_cast<const float*>(sd.p); W.kind = kind;
+        const float* X = static_cast<const float*>(xd.p);
+        float* Y = static_cast<float*>(yd.p);
+        if (m < 24) {  // the decoder's 8-row passes
+            for (int64_t r = 0; r < m; r += 8) {
+                Fp8ProjArgs a;
+                a.W[0] = W; a.X = X + r * k; a.ldx = k; a.rows = (int)std::min<int64_t>(8, m - r); a.Y[0] = Y + r * n; a.ldy[0] = n;
+                hip_check(launch_fp8_proj(a, nullptr), "fp8 projection");
+            }
+        } else {  // the prompt route: dequantized weights on the f32 matrix cores
+            DeviceBuf w32(wb * 4);
+            hip_check(launch_fp8_dequant(W, static_cast<float*>(w32.p), nullptr), "dequantize");
+            hip_check(launch_prefill_gemm(X, k, w32.p, 0, nullptr, nullptr, n, Y, n, (int)m, n, k, nullptr), "prefill gemm");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        }
+        hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
                                                        int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused,
                                                        float* logprob_out, uint32_t* top_out, float* top_logprob_out, float* lse_out)

@@ -9,6 +9,7 @@
 #include <fstream>
 #include <sstream>
 
+#include "fp8_weights.h"
 #include "gguf.h"
 #include "json.h"
 #include "kernels.h"
@@ -208,8 +209,35 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         }
         m->bf16_ = weights == 2 || (weights == 0 && st.get("model.layers.0.self_attn.q_proj.weight").dtype == "BF16");
     }
+    // FP8 checkpoints (fp8_weights.h): as stored, the seven matrices of every layer stay FP8 codes in HBM -- all of them or none
+    const Fp8Checkpoint f8(st, is_gguf ? std::string() : m->config_json_);
+    if (!is_gguf && weights == 0) {
+        std::string first_fp8, first_other, other_dtype;
+        for (int i = 0; i < c.layers; ++i)
+            for (const char* nm : {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                                   "mlp.down_proj"}) {
+                const std::string name = "model.layers." + std::to_string(i) + "." + nm + ".weight";
+                if (f8.is_fp8(name)) {
+                    if (first_fp8.empty()) first_fp8 = name;
+                } else if (first_other.empty() && st.contains(name)) {
+                    first_other = name;
+                    other_dtype = st.get(name).dtype;
+                }
+            }
+        if (!first_fp8.empty() && !first_other.empty())
+            throw std::runtime_error("mixed FP8 checkpoint: " + first_other + " is " + other_dtype + " while " + first_fp8 +
+                                     " is F8_E4M3; weights_dtype 0 keeps FP8 layers only when all seven matrices of every layer are FP8 "
+                                     "(weights_dtype 1 or 2 loads the file)");
+        if (!first_fp8.empty()) {
+            m->quant_ = m->fp8_ = true;
+            m->bf16_ = st.get("model.embed_tokens.weight").dtype == "BF16";  // the table and the head stay as stored
+        }
+    }
     std::vector<float> buf, tmp;
-    auto read = [&](const std::string& name, std::vector<float>& out) { return is_gguf ? gf.read_f32(name, out) : st.read_f32(name, out); };
+    auto read = [&](const std::string& name, std::vector<float>& out) {
+        if (is_gguf) return gf.read_f32(name, out);
+        return f8.is_fp8(name) ? f8.read_f32(name, out) : st.read_f32(name, out);
+    };
     auto get = [&](const std::string& name, std::vector<int64_t> want) {
         const std::vector<int64_t> shape = read(name, buf);
         if (shape != want) throw std::runtime_error("tensor " + name + " has an unexpected shape");
@@ -240,7 +268,24 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         q.s2 = ptr[3];
         return q;
     };
-    if (m->quant_ && (H % 256 || c.inter % 256)) throw std::runtime_error("quantized GGUF decoder needs hidden and intermediate sizes that are multiples of 256");
+    // an FP8 matrix [n, k]: the codes as they are in the file, the scales widened to f32 (counted as F32)
+    auto upload_f8 = [&](const std::string& name, int n, int k) {
+        const Fp8Tensor t = f8.read(name);
+        if (t.n != n || t.k != k) throw std::runtime_error("tensor " + name + " has an unexpected shape");
+        const size_t bytes = (size_t)n * k;
+        void* dp = m->dalloc((bytes + 3) / 4);
+        hip_check(hipMemcpy(dp, t.codes, bytes, hipMemcpyHostToDevice), "hipMemcpy(weights)");
+        m->weight_bytes_ += bytes;
+        m->bytes_by_type_[kFp8WeightType] += bytes;
+        Fp8Mat f;
+        f.n = n;
+        f.k = k;
+        f.codes = static_cast<const uint8_t*>(dp);
+        f.scale = m->upload_f32(t.scale);
+        f.kind = t.kind;
+        return f;
+    };
+    if (m->quant_ && !m->fp8_ && (H % 256 || c.inter % 256)) throw std::runtime_error("quantized GGUF decoder needs hidden and intermediate sizes that are multiples of 256");
     m->layers_.resize((size_t)c.layers);
     m->cache_cap_ = std::min(max_context > 0 ? max_context : c.max_pos, c.max_pos);
     for (int i = 0; i < c.layers; ++i) {
@@ -251,7 +296,10 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         bool any_bias = false;
         for (const auto& nm : {std::make_pair(std::string("q_proj"), QD), std::make_pair(std::string("k_proj"), kv),
                                std::make_pair(std::string("v_proj"), kv)}) {
-            if (m->quant_) {
+            if (m->fp8_) {
+                Fp8Mat& f = nm.first == "q_proj" ? L.fq : (nm.first == "k_proj" ? L.fk : L.fv);
+                f = upload_f8(p + ".self_attn." + nm.first + ".weight", nm.second, H);
+            } else if (m->quant_) {
                 QMat& q = nm.first == "q_proj" ? L.q : (nm.first == "k_proj" ? L.k : L.v);
                 q = upload_q(p + ".self_attn." + nm.first + ".weight", nm.second, H);
             } else {
@@ -268,7 +316,12 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
             }
         }
         L.bqkv = any_bias ? m->upload_f32(b) : nullptr;
-        if (m->quant_) {
+        if (m->fp8_) {
+            L.fo = upload_f8(p + ".self_attn.o_proj.weight", H, QD);
+            L.fgate = upload_f8(p + ".mlp.gate_proj.weight", c.inter, H);
+            L.fup = upload_f8(p + ".mlp.up_proj.weight", c.inter, H);
+            L.fdown = upload_f8(p + ".mlp.down_proj.weight", H, c.inter);
+        } else if (m->quant_) {
             L.o = upload_q(p + ".self_attn.o_proj.weight", H, H);
             L.gate_q = upload_q(p + ".mlp.gate_proj.weight", c.inter, H);
             L.up_q = upload_q(p + ".mlp.up_proj.weight", c.inter, H);
@@ -300,7 +353,7 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         L.v_cache = m->dalloc((size_t)m->cache_cap_ * kv);
     }
     const bool tied = c.tie_embeddings || !contains("lm_head.weight");
-    if (m->quant_) {
+    if (m->quant_ && !m->fp8_) {
         m->qembed_ = upload_q("model.embed_tokens.weight", c.vocab, H);
         m->qhead_ = tied ? m->qembed_ : upload_q("lm_head.weight", c.vocab, H);
         m->head_q8k_ = !tied;  // a tied head is the embedding table: dequantized rows x f32 activations (cpu/embeddings/mod.rs:94-132)
@@ -523,7 +576,7 @@ void LlmModel::embed_rows(const uint32_t* ids, int n, float* dst, int pos, const
 {
     const LlmConfig& c = cfg_;
     const int wb = bf16_ ? 1 : 0;
-    if (quant_) hip_check(launch_qembed(ids, n, qembed_, dst, stream_), "embed");
+    if (quant_ && !fp8_) hip_check(launch_qembed(ids, n, qembed_, dst, stream_), "embed");
     else if (gpt2_) hip_check(launch_llm_embed_pos(ids, n, c.hidden, c.vocab, embed_, wpe_, c.max_pos, wb, pos, pos_ptr, dst, stream_, row_pos), "embed");
     else hip_check(launch_llm_embed(ids, n, c.hidden, c.vocab, embed_, wb, dst, stream_), "embed");
 }
@@ -582,11 +635,38 @@ void LlmModel::quant_finish(int n, const Layer& L)
     hip_check(launch_qfused(dn, s), "down proj");
 }
 
+void LlmModel::fp8_qkv(int n, const Layer& L, float* q, int64_t ldq, float* kdst, float* vdst, int64_t ldkv, int row_off, const int* row_off_ptr)
+{
+    Fp8ProjArgs a;
+    a.mode = F8_QKV;
+    a.W[0] = L.fq; a.W[1] = L.fk; a.W[2] = L.fv;
+    a.X = h_; a.ldx = cfg_.hidden; a.rows = n; a.gamma = L.ln1; a.eps = cfg_.eps; a.bias = L.bqkv;
+    a.Y[0] = q; a.ldy[0] = ldq; a.Y[1] = kdst; a.Y[2] = vdst; a.ldy[1] = a.ldy[2] = ldkv;
+    a.row_off = row_off; a.row_off_ptr = row_off_ptr;
+    hip_check(launch_fp8_proj(a, stream_), "norm + qkv");
+}
+
+void LlmModel::fp8_finish(int n, const Layer& L)
+{
+    hipStream_t s = stream_;
+    const int H = cfg_.hidden, I = cfg_.inter, QD = cfg_.q_dim();
+    Fp8ProjArgs o;
+    o.W[0] = L.fo; o.X = ctx_; o.ldx = QD; o.rows = n; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
+    hip_check(launch_fp8_proj(o, s), "o proj");
+    Fp8ProjArgs g;
+    g.mode = F8_SWIGLU;
+    g.W[0] = L.fgate; g.W[1] = L.fup; g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = cfg_.eps; g.Y[0] = mid_; g.ldy[0] = I;
+    hip_check(launch_fp8_proj(g, s), "norm + gate/up");
+    Fp8ProjArgs dn;
+    dn.W[0] = L.fdown; dn.X = mid_; dn.ldx = I; dn.rows = n; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
+    hip_check(launch_fp8_proj(dn, s), "down proj");
+}
+
 void LlmModel::head(StepRoute route, const float* X, int rows, float* Y, bool norm_in_head)
 {
     const LlmConfig& c = cfg_;
     const int H = c.hidden;
-    if (quant_) {  // (the quantized kernels take <= 8 rows as they are)
+    if (quant_ && !fp8_) {  // (the quantized kernels take <= 8 rows as they are; an FP8 checkpoint's head is f32 / bf16)
         qlinear(qhead_, X, H, rows, head_q8k_, Y, c.vocab, "lm head");
         return;
     }
@@ -602,11 +682,23 @@ void LlmModel::head(StepRoute route, const float* X, int rows, float* Y, bool no
 // (quant_kernels.hip: RMSNorm + per-segment types + RoPE + cache write; a Q6_K linear first takes one qprep launch,
 // quant_source()).  fused: the one-token Llama launch.  Else the GEMV with the K / V segments landing in the cache rows, then
 // the rotation where they sit: Qwen3 head norm + RoPE in one launch, Llama RoPE of Q and of K, GPT-2 (learned positions) none.
+// FP8 matrices take that last form with fp8_qkv() (fp8_kernels.hip) as the GEMV.
 void LlmModel::step_qkv(StepRoute route, int n, const Layer& L, const int* pos, bool fused, const uint32_t* embed_ids)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
+    if (fp8_) {  // plain segments (Q of q_dim() columns, K / V into the cache rows), then the rotation where they sit
+        fp8_qkv(n, L, q_, QD, L.k_cache, L.v_cache, kv, cache_len_, pos);
+        if (c.qwen3()) {
+            hip_check(launch_qk_norm_rope(q_, QD, L.k_cache, kv, n, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_, pos, 1,
+                                          s), "qk norm + rope");
+        } else {
+            hip_check(launch_rope(q_, QD, n, c.heads, d, cos_, sin_, cache_len_, pos, 0, s), "rope q");
+            hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pos, 1, s), "rope k");
+        }
+        return;
+    }
     if (quant_) {
         QFusedArgs qkv;
         qkv.mode = QF_QKV;
@@ -644,7 +736,8 @@ void LlmModel::step_qkv(StepRoute route, int n, const Layer& L, const int* pos, 
 void LlmModel::layer_finish(StepRoute route, int n, const Layer& L, bool slabs)
 {
     if (quant_) {
-        quant_finish(n, L);
+        if (fp8_) fp8_finish(n, L);
+        else quant_finish(n, L);
         return;
     }
     const LlmConfig& c = cfg_;
@@ -692,7 +785,7 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
                                           splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, QD, stream_, c.heads / c.kv_heads), "attention");
         layer_finish(route, n, L, merge_in_proj);
     }
-    if (one && llama && llm_gemv_streams(H, lm_head_, nullptr)) {  // the head normalises the row itself (and stores it in last_)
+    if (one && (llama || fp8_) && llm_gemv_streams(H, lm_head_, nullptr)) {  // the head normalises the row itself (and stores it in last_)
         head(route, h_, 1, logits_, true);
         return;
     }
@@ -726,7 +819,7 @@ void LlmModel::ensure_prompt_workspace()
 // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
 // gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
 void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                           float* gate, const char* what, const QMat* qm, bool gelu)
+                           float* gate, const char* what, const QMat* qm, bool gelu, const Fp8Mat* fm)
 {
     hipStream_t s = stream_;
     const int H = cfg_.hidden, kv = cfg_.kv_heads * cfg_.head_dim, I = cfg_.inter, QD = cfg_.q_dim();
@@ -736,7 +829,12 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
     // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
     int wbu = bf16_ ? 1 : 0;
     bool bf = bf16_;
-    if (qm) {
+    if (fm) {  // an FP8 matrix: decode(code) * scale into the f32 scratch, then the f32 route
+        hip_check(launch_fp8_dequant(*fm, pw32_, s), what);
+        W = pw32_;
+        wbu = 0;
+        bf = false;
+    } else if (qm) {
         hip_check(launch_qdequant(*qm, pw32_, s), what);
         if (qm->type == GGML_Q6_K) {
             hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
@@ -789,13 +887,15 @@ void LlmModel::rows_qkv(int m, const Layer& L, float* k_rows, float* v_rows)
     const int H = c.hidden, kv = c.kv_heads * c.head_dim, QD = c.q_dim();
     const size_t wsz = bf16_ ? 2 : 4;
     auto at = [&](const void* w, size_t elems) { return static_cast<const void*>(static_cast<const char*>(w) + elems * wsz); };
+    auto gq = [&](const QMat& m) { return quant_ && !fp8_ ? &m : nullptr; };  // the layer's matrix as prompt_proj's qm / fm
+    auto fq = [&](const Fp8Mat& m) { return fp8_ ? &m : nullptr; };
     if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, m, H, pn_, s), "ln_1");
     else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, m, H, pn_, s), "rmsnorm 1");
-    prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj", quant_ ? &L.q : nullptr);
+    prompt_proj(m, pn_, H, L.wqkv, L.bqkv, nullptr, pq_, QD, QD, H, nullptr, "q proj", gq(L.q), false, fq(L.fq));
     prompt_proj(m, pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)QD * H), L.bqkv ? L.bqkv + QD : nullptr, nullptr, k_rows, kv, kv, H, nullptr,
-                "k proj", quant_ ? &L.k : nullptr);
+                "k proj", gq(L.k), false, fq(L.fk));
     prompt_proj(m, pn_, H, quant_ ? nullptr : at(L.wqkv, (size_t)(QD + kv) * H), L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, v_rows, kv, kv, H,
-                nullptr, "v proj", quant_ ? &L.v : nullptr);
+                nullptr, "v proj", gq(L.v), false, fq(L.fv));
 }
 
 // The second half, behind the attention's context rows in pctx_: o-proj + residual -> RMSNorm -> gate, up -> silu(gate) * up ->
@@ -805,7 +905,9 @@ void LlmModel::rows_finish(int m, const Layer& L)
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const int H = c.hidden, I = c.inter, QD = c.q_dim();
-    prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj", quant_ ? &L.o : nullptr);
+    auto gq = [&](const QMat& m) { return quant_ && !fp8_ ? &m : nullptr; };
+    auto fq = [&](const Fp8Mat& m) { return fp8_ ? &m : nullptr; };
+    prompt_proj(m, pctx_, QD, L.wo, L.bo, ph_, ph_, H, H, QD, nullptr, "o proj", gq(L.o), false, fq(L.fo));
     if (gpt2_) {
         hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
         prompt_proj(m, pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
@@ -813,9 +915,9 @@ void LlmModel::rows_finish(int m, const Layer& L)
         return;
     }
     hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");
-    prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", quant_ ? &L.gate_q : nullptr);
-    prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", quant_ ? &L.up_q : nullptr);
-    prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", quant_ ? &L.down_q : nullptr);
+    prompt_proj(m, pn_, H, L.gate, nullptr, nullptr, pg_, I, I, H, nullptr, "gate", gq(L.gate_q), false, fq(L.fgate));
+    prompt_proj(m, pn_, H, L.up, nullptr, nullptr, pu_, I, I, H, pg_, "up + swiglu", gq(L.up_q), false, fq(L.fup));
+    prompt_proj(m, pg_, I, L.down, nullptr, ph_, ph_, H, H, I, nullptr, "down proj", gq(L.down_q), false, fq(L.fdown));
 }
 
 // Prompt rows through the fp32 matrix cores (prefill_gemm_kernel) instead of 8-row GEMV passes: per layer rows_qkv() (K and V
@@ -961,7 +1063,7 @@ void LlmModel::score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, 
 {
     const LlmConfig& c = cfg_;
     const int H = c.hidden;
-    if (score_fused_ && !quant_ && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
+    if (score_fused_ && (!quant_ || fp8_) && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
         if (k > 0) {
             if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, k) > score_tk_scratch_bytes_)
                 throw std::runtime_error("score head: top-k slab scratch too small");
@@ -1588,7 +1690,9 @@ void LlmModel::lane_step(int n)
     embed_rows(reinterpret_cast<const uint32_t*>(st->token), n, h_, 0, nullptr, st->pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
-        if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
+        if (fp8_) {
+            fp8_qkv(n, L, lane_qkv_, ldq, lane_qkv_ + QD, lane_qkv_ + QD + kv, ldq, 0, nullptr);
+        } else if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
             QFusedArgs a;
             a.mode = QF_PLAIN;
             quant_source(a, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "fp8_kernels.h"
 #include "generation_run.h"
 #include "quant_kernels.h"
 #include "sampling.h"
@@ -423,9 +424,9 @@ private:
                                   const std::vector<EmbedBlock>& mfma, const std::vector<PrefixBlock>& prefix);
     // One projection of m prompt rows: Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T); gelu (GPT-2's
     // c_fc): Y = gelu_tanh(A W^T + bias).  Routes: the 64 x 64 prompt kernel, or from 512 rows and 208 tiles the 128 x 128-tile
-    // GEMM (bf16 weights on the bf16 matrix cores); qm: a quantized matrix, dequantized into the f32 scratch first.
+    // GEMM (bf16 weights on the bf16 matrix cores); qm / fm: a GGUF-quantized / FP8 matrix, dequantized into the f32 scratch first.
     void prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                     float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false);
+                     float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false, const Fp8Mat* fm = nullptr);
     void forward_rows(const uint32_t* ids, int n, bool score, int score_base = 0);  // forward(), with score()'s sink
     void ensure_score();
     void ensure_score_topk();
@@ -450,6 +451,7 @@ private:
         float *ln1_b = nullptr, *ln2_b = nullptr, *bo = nullptr, *bfc = nullptr, *bdown = nullptr;  // GPT-2's LayerNorm and projection biases
         float *k_cache, *v_cache;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
+        Fp8Mat fq, fk, fv, fo, fgate, fup, fdown;  // FP8 checkpoints (quant_ && fp8_): the codes and scales of the seven matrices
     };
     // The layer body of the rows route, around the caller's own RoPE / head norm and attention (prefill_rows: the KV cache,
     // packed_layers: ek_ / ev_ and the block tables).  rows_qkv: norm 1 of ph_ into pn_, Q into pq_, K and V into the rows given.
@@ -483,10 +485,15 @@ private:
     // quant_finish (layer_finish's quantized form): o-proj + residual, RMSNorm + gate/up + SwiGLU, down + residual.
     void quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what);
     void quant_finish(int n, const Layer& L);
+    // FP8 checkpoints ride the quantized control flow with kernels of their own (fp8_kernels.hip).  fp8_qkv: norm + Q | K | V
+    // as plain segments in one launch, Q into `q` (rows of ldq), K / V into rows row_off / *row_off_ptr + r of `kdst` / `vdst`.
+    void fp8_qkv(int n, const Layer& L, float* q, int64_t ldq, float* kdst, float* vdst, int64_t ldkv, int row_off, const int* row_off_ptr);
+    void fp8_finish(int n, const Layer& L);
     LlmConfig cfg_;
     int device_ = 0;
     uint64_t serial_ = 0;
     bool bf16_ = false, quant_ = false, gpt2_ = false;
+    bool fp8_ = false;  // with quant_: the layers' matrices are FP8 codes; bf16_ then describes the embedding table and the head
     size_t weight_bytes_ = 0;
     uint64_t bytes_by_type_[32] = {};
     std::string config_json_;

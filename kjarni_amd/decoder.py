@@ -11,6 +11,7 @@ from . import _ffi
 from ._ffi import check_error, lib
 
 WEIGHTS = {"auto": 0, "f32": 1, "bf16": 2}
+WEIGHT_TYPE_F8_E4M3 = 31  # KJARNI_HIP_WEIGHT_TYPE_F8_E4M3: the FP8 codes' entry in weight_bytes_by_type
 
 
 def prefix_keep(resident: Sequence[int], prompt: Sequence[int], limit: int) -> int:
@@ -154,10 +155,11 @@ class HipDecoder:
         return s
 
     def weight_bytes_by_type(self) -> dict:
-        """Device bytes of the weights per GGML type name (F32, BF16, Q8_0, Q4_K, Q6_K), non-zero entries only."""
+        """Device bytes of the weights per type name (F32, BF16, Q8_0, Q4_K, Q6_K; F8_E4M3: the codes of an FP8 checkpoint, whose
+        scales count as F32), non-zero entries only."""
         out = (C.c_uint64 * 32)()
         check_error(lib().kjarni_hip_decoder_weight_bytes_by_type(self._h, out, 32))
-        names = {0: "F32", 8: "Q8_0", 12: "Q4_K", 14: "Q6_K", 30: "BF16"}
+        names = {0: "F32", 8: "Q8_0", 12: "Q4_K", 14: "Q6_K", 30: "BF16", WEIGHT_TYPE_F8_E4M3: "F8_E4M3"}
         return {names[t]: int(out[t]) for t in names if out[t]}
 
     def reset(self):

@@ -677,6 +677,61 @@ def main():
                            "frac": round(q_tok * len(qout) / q_dec / 1e9 / PEAK_HBM_GBS, 4), "traffic": None,
                            "algorithmic_bytes_per_token": int(q_tok)}})
         del qdec
+        # FP8 (e4m3) checkpoints, the codes kept in HBM (tests/fp8_fixture.py): the Llama-1B shape with per-channel scales beside
+        # the bf16 entry above, and the Qwen3-0.6B shape with 128 x 128 block scales beside a bf16 load of the same shape.
+        from tests import fp8_fixture, qwen3_fixture
+
+        def decode_run(d8):
+            d8.generate(prompt, 8)                                            # warm-up (graph capture)
+            t0 = time.perf_counter()
+            d8.reset()
+            d8.forward(prompt, fetch=False)
+            pre = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            o = d8.generate(prompt, n_new)
+            return pre, time.perf_counter() - t0 - pre, len(o)
+
+        def fp8_entry(label, fdec, base, kvb, what):
+            f_pre, f_dec, f_n = decode_run(fdec)
+            table = fdec.weight_bytes_by_type().get("BF16", 0)                # one row of the table is read; the tied head streams it
+            f_tok = fdec.weight_bytes + kvb
+            emit({"metric": f"tokens/sec greedy decode, {label}, FP8 e4m3 weights in HBM, batch 1", "value": round(f_n / f_dec, 1),
+                  "unit": "tokens/s", "n_gpus": 1, "dtype": "F8_E4M3 layer weights + f32 scales, bf16 table / head, f32 activations/accumulate/KV",
+                  "data": "synthetic", "config": {"workload": f"{what}; random codes, 128-token prompt, {f_n} generated tokens"},
+                  "ms_prefill_128": round(f_pre * 1e3, 2), "ms_per_token": round(f_dec * 1e3 / f_n, 4),
+                  "weight_bytes": fdec.weight_bytes, "weight_bytes_by_type": fdec.weight_bytes_by_type(), "table_bytes": table,
+                  "bf16_same_run": base, "speedup_vs_bf16": round((f_n / f_dec) / base["tokens_per_s"], 3),
+                  "prefill_ratio_vs_bf16": round(f_pre * 1e3 / base["ms_prefill_128"], 3),
+                  "weight_bytes_ratio_vs_bf16": round(fdec.weight_bytes / base["weight_bytes"], 3),
+                  "roofline": {"kernel": "fp8_proj_kernel (weight stream) + decode_attention_partial", "bound": "hbm",
+                               "achieved": round(f_tok * f_n / f_dec / 1e9, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                               "frac": round(f_tok * f_n / f_dec / 1e9 / PEAK_HBM_GBS, 4), "traffic": None,
+                               "algorithmic_bytes_per_token": int(f_tok)}})
+
+        fdir = os.path.join(tmp, "llama-1b-fp8")
+        fcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=cfg_l["vocab_size"] + 1)
+        fp8_fixture.fp8_model(fdir, fcfg, "channel", seed=0, keep_hf=False)
+        fdec = kjarni_amd.HipDecoder(fdir, max_context=2048)
+        fp8_entry("Llama-3.2-1B shape", fdec, {"tokens_per_s": res["value"], "ms_per_token": res["ms_per_token"],
+                                                "ms_prefill_128": res["ms_prefill_128"], "weight_bytes": dec.weight_bytes}, kv_bytes,
+                  "Llama-3.2-1B geometry, the seven matrices of every layer F8_E4M3 with per-channel scales")
+        del fdec
+        q3 = dict(fp8_fixture.QWEN3_06B, max_position_embeddings=4096, eos_token_id=fp8_fixture.QWEN3_06B["vocab_size"] + 1)
+        bdir = os.path.join(tmp, "qwen3-06b-bf16")
+        qwen3_fixture.qwen3_model(bdir, q3, seed=0, store_bf16=True)
+        bdec = kjarni_amd.HipDecoder(bdir, max_context=2048)
+        b_pre, b_dec, b_n = decode_run(bdec)
+        base = {"tokens_per_s": round(b_n / b_dec, 1), "ms_per_token": round(b_dec * 1e3 / b_n, 4), "ms_prefill_128": round(b_pre * 1e3, 2),
+                "weight_bytes": bdec.weight_bytes}
+        del bdec
+        fdir = os.path.join(tmp, "qwen3-06b-fp8")
+        fp8_fixture.fp8_model(fdir, q3, "block", seed=0, keep_hf=False)
+        fdec = kjarni_amd.HipDecoder(fdir, max_context=2048)
+        q3_kv = 2 * q3["num_hidden_layers"] * q3["num_key_value_heads"] * q3["head_dim"] * 4 * (128 + n_new / 2)
+        fp8_entry("Qwen3-0.6B shape", fdec, base, q3_kv,
+                  "Qwen3-0.6B geometry (hidden 1024, 28 layers, 16/8 heads of 128, inter 3072, vocab 151936, tied head), the seven matrices "
+                  "of every layer F8_E4M3 with 128 x 128 block scales")
+        del fdec
 
     if "llm8b" in which:
         # The same decode path on the Llama-3.1-8B geometry (16 GB of bf16 weights): the per-kernel floor that bounds the 1B
