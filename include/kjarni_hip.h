@@ -559,6 +559,42 @@ KjarniErrorCode kjarni_fp8_tensor_f32(const char* model_dir, const char* hf_name
  * cores; k % 32 == 0).  A NaN code or a scale shape that fits no kind is KJARNI_ERROR_INVALID_CONFIG. */
 KjarniErrorCode kjarni_hip_op_linear_fp8(int32_t device, const float* x, int64_t m, const void* codes, const float* scale,
                                          int32_t scale_rows, int32_t scale_cols, int32_t n, int32_t k, float* y);
+/* ---- the decode step's fused projections and their preparation kernels, alone -----------------------------------------------------
+ * kjarni_hip_op_fused_proj_fp8 / _ggml: ONE call of launch_fp8_proj / launch_qfused on host arrays, every mode of the launcher
+ * exposed.  mode 0 plain (1 matrix, y[0]), 1 Q | K | V (3 matrices, y[0..2]), 2 SwiGLU (gate, up; y[0]).  Arrays indexed by matrix
+ * or output have 3 entries; those past the mode's count are ignored.  Matrix i is [n[i], k]: FP8 codes + f32 scales
+ * [scale_rows[i], scale_cols[i]] (the kind by fp8_scale_kind; a NaN code is refused), or raw GGUF blocks of ggml_types[i] in HF row
+ * order.  x [rows_alloc, ldx], of which `rows` rows and k columns are the input.  gamma [k] (may be NULL) with eps: the RMSNorm
+ * prologue.  bias (may be NULL): FP8 over the concatenated columns; GGUF bias_floats floats, segment i from bias_off[i].  r
+ * [rows, ldr] (may be NULL), or r_is_y0: the residual is y[0] itself, added in place.  y[i] [out_rows[i], ldy[i]] is uploaded as
+ * given, written by the kernel and returned whole: y[0] rows 0 .. rows-1, y[1] / y[2] rows row_off .. row_off+rows-1.
+ * offset_on_device: row_off goes to a device int that the kernel reads (row_off_ptr), and the launcher's by-value row_off gets
+ * another in-range row.  GGUF Q | K | V rotates Q and K in the epilogue (head_dim, cos_t / sin_t [positions, head_dim / 2], row r at
+ * position row_off + r); jobs per segment are n[i] / 2 as the decoder derives them.  q8k: the rows go through launch_qprep first
+ * (RMSNorm when gamma, Q8_K codes), as the decoder does for Q6_K linears; xn_out [rows, k] (written when gamma), xq_out [rows, k]
+ * and xd_out [rows, k / 256] (each may be NULL) then return what the device produced.
+ * INVALID_CONFIG, before any GPU work and with the outputs untouched: rows that do not fit out_rows, positions past the table, ldx /
+ * ldy / ldr that do not cover their columns, ldx % 4, gate and up of different n, Q / K rows no multiple of head_dim, bias_off
+ * outside bias_floats; and, after the upload, whatever the launcher itself refuses (rows outside 1 .. 8, k % 16 / k % 256, ...). */
+KjarniErrorCode kjarni_hip_op_fused_proj_fp8(int32_t device, int32_t mode, const void* const* codes, const float* const* scales,
+                                             const int32_t* scale_rows, const int32_t* scale_cols, const int32_t* n, int32_t k,
+                                             const float* x, int32_t rows_alloc, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                             const float* bias, const float* r, int64_t ldr, int32_t r_is_y0, float* const* y,
+                                             const int32_t* out_rows, const int64_t* ldy, int32_t row_off, int32_t offset_on_device);
+KjarniErrorCode kjarni_hip_op_fused_proj_ggml(int32_t device, int32_t mode, const void* const* blocks, const int32_t* ggml_types,
+                                              const int32_t* n, int32_t k, const float* x, int32_t rows_alloc, int64_t ldx, int32_t rows,
+                                              const float* gamma, float eps, const float* bias, int32_t bias_floats, const int32_t* bias_off,
+                                              const float* r, int64_t ldr, int32_t r_is_y0, float* const* y, const int32_t* out_rows,
+                                              const int64_t* ldy, int32_t row_off, int32_t offset_on_device, int32_t head_dim,
+                                              const float* cos_t, const float* sin_t, int32_t positions, int32_t q8k, float* xn_out,
+                                              int8_t* xq_out, float* xd_out);
+/* launch_qembed alone: out [n_ids, k] (uploaded as given, returned whole) = the dequantized rows ids[i] of the table [vocab, k]
+ * given as raw GGUF blocks; an id >= vocab gives zeros. */
+KjarniErrorCode kjarni_hip_op_qembed(int32_t device, const uint32_t* ids, int32_t n_ids, const void* blocks, int32_t ggml_type, int32_t vocab,
+                                     int32_t k, float* out);
+/* launch_q8k_quantize alone: x [rows, ldx] -> codes_out [rows, k] (int8), scales_out [rows, k / 256], deq_out [rows, k]. */
+KjarniErrorCode kjarni_hip_op_q8k_quantize(int32_t device, const float* x, int32_t rows, int64_t ldx, int32_t k, int8_t* codes_out,
+                                           float* scales_out, float* deq_out);
 /* CpuDecoder::forward + final norm + lm head (llama/cpu_decoder.rs:196-219): appends n tokens to the cache.  Fewer
  * than 24 tokens run 8 rows at a time; longer prompts (when the geometry allows) go through the matrix-core route in
  * 2 048-row chunks.  hidden_out receives the final-normed rows of the LAST 8-row block, f32 [((n-1) mod 8) + 1, hidden];

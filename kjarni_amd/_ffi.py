@@ -456,6 +456,15 @@ SIGNATURES = {
     "kjarni_hip_op_linear_ggml": (c_int32, [c_int32, _f32p, c_int64, c_void_p, c_int32, c_int32, c_int32, _f32p]),
     "kjarni_fp8_tensor_f32": (c_int32, [c_char_p, c_char_p, _f32p, c_size_t, POINTER(c_size_t), POINTER(C.c_int64), POINTER(c_int32)]),
     "kjarni_hip_op_linear_fp8": (c_int32, [c_int32, _f32p, c_int64, c_void_p, _f32p, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_fused_proj_fp8": (c_int32, [c_int32, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32),
+                                               POINTER(c_int32), c_int32, _f32p, c_int32, c_int64, c_int32, _f32p, c_float, _f32p, _f32p,
+                                               c_int64, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32]),
+    "kjarni_hip_op_fused_proj_ggml": (c_int32, [c_int32, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, _f32p, c_int32,
+                                                c_int64, c_int32, _f32p, c_float, _f32p, c_int32, POINTER(c_int32), _f32p, c_int64, c_int32,
+                                                POINTER(c_void_p), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32, c_int32, _f32p, _f32p,
+                                                c_int32, c_int32, _f32p, c_void_p, _f32p]),
+    "kjarni_hip_op_qembed": (c_int32, [c_int32, _u32p, c_int32, c_void_p, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_q8k_quantize": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, c_void_p, _f32p, _f32p]),
     "kjarni_hip_decoder_set_device_sampling": (None, [c_void_p, c_int32]),
     "kjarni_hip_decoder_forward": (c_int32, [c_void_p, _u32p, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_generate": (c_int32, [c_void_p, _u32p, c_size_t, c_size_t, c_float, c_int32, KjarniTokenCallbackFn, c_void_p,

@@ -1490,6 +1490,302 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_linear_fp8(int32_t device, const flo
     });
 }
 
+// ---- the decode step's fused projections and their preparation kernels, alone -----------------------------------------------------
+
+namespace {
+
+// What the two fused-projection entries share, checked before any GPU work: every element a kernel may read or write lies inside
+// the buffers given.  n_mats / n_outs: matrices and output buffers of the mode.
+struct ProjShape {
+    int n_mats = 1, n_outs = 1;
+    int64_t n_tot = 0;  // columns of the launch (SwiGLU: of one matrix)
+};
+
+ProjShape check_fused_proj(int32_t mode, const int32_t* n, int32_t k, int32_t rows_alloc, int64_t ldx, int32_t rows, const float* r, int64_t ldr,
+                           int32_t r_is_y0, float* const* y, const int32_t* out_rows, const int64_t* ldy, int32_t row_off)
+{
+    if (mode < 0 || mode > 2) throw InvalidConfig("mode must be 0 (plain), 1 (Q | K | V) or 2 (SwiGLU)");
+    ProjShape s;
+    s.n_mats = mode == 1 ? 3 : (mode == 2 ? 2 : 1);
+    s.n_outs = mode == 1 ? 3 : 1;
+    if (k < 1 || k > (1 << 20)) throw InvalidConfig("k must be 1 .. 2^20");
+    for (int i = 0; i < s.n_mats; ++i) {
+        if (n[i] < 1 || n[i] > (1 << 20)) throw InvalidConfig("every matrix needs 1 .. 2^20 rows");
+        s.n_tot += n[i];
+    }
+    if (mode == 2) {
+        if (n[1] != n[0]) throw InvalidConfig("gate and up must have the same number of rows");
+        s.n_tot = n[0];
+    }
+    if (rows < 0 || rows > 64 || rows_alloc < 1 || rows > rows_alloc || rows_alloc > 64) throw InvalidConfig("rows must be 0 .. rows_alloc <= 64");
+    if (ldx < k || ldx > (1 << 21) || (ldx & 3)) throw InvalidConfig("ldx must cover k, be a multiple of 4 and at most 2^21");
+    if (row_off < 0) throw InvalidConfig("row_off must not be negative");
+    for (int i = 0; i < s.n_outs; ++i) {
+        if (!y[i]) throw InvalidConfig("an output of this mode is NULL");
+        const int64_t cols = mode == 2 ? n[0] : n[i];
+        if (ldy[i] < cols || ldy[i] > (1 << 21) || out_rows[i] < 1 || out_rows[i] > 4096) throw InvalidConfig("ldy must cover the matrix's rows; out_rows 1 .. 4096");
+        if ((int64_t)(i == 0 ? 0 : row_off) + rows > out_rows[i])
+            throw InvalidConfig("rows " + std::to_string(i == 0 ? 0 : row_off) + " .. +" + std::to_string(rows) + " do not fit the " +
+                                std::to_string(out_rows[i]) + " rows of output " + std::to_string(i));
+    }
+    if (r && r_is_y0) throw InvalidConfig("r_is_y0 takes the residual from y[0]: r must be NULL");
+    if ((r || r_is_y0) && mode == 1) throw InvalidConfig("no residual with Q | K | V: its columns span three outputs");
+    if (r && (ldr < s.n_tot || ldr > (1 << 21))) throw InvalidConfig("ldr must cover the columns");
+    return s;
+}
+
+// The output buffers of a fused projection on the device: uploaded whole, a guard band behind each, downloaded whole.
+struct ProjOutputs {
+    std::vector<std::unique_ptr<GuardedBuf>> buf;
+    std::vector<size_t> bytes;
+    ProjOutputs(const ProjShape& s, float* const* y, const int32_t* out_rows, const int64_t* ldy)
+    {
+        for (int i = 0; i < s.n_outs; ++i) {
+            bytes.push_back((size_t)out_rows[i] * (size_t)ldy[i] * 4);
+            buf.push_back(std::make_unique<GuardedBuf>(bytes.back()));
+            hip_check(hipMemcpy(buf.back()->buf.p, y[i], bytes.back(), hipMemcpyHostToDevice), "H2D y");
+        }
+    }
+    float* dev(int i) const { return i < (int)buf.size() ? buf[i]->as<float>() : nullptr; }
+    void fetch(float* const* y) const
+    {
+        for (size_t i = 0; i < buf.size(); ++i) {
+            buf[i]->check("fused projection output");
+            hip_check(hipMemcpy(y[i], buf[i]->buf.p, bytes[i], hipMemcpyDeviceToHost), "D2H y");
+        }
+    }
+};
+
+// With the offset on the device the launcher's row_off is a value the result must not depend on: another row that is still inside
+// every buffer (`room` = the largest offset all of them allow), so that a kernel reading the wrong one writes a wrong row, not
+// outside.
+int decoy_offset(int32_t row_off, int64_t room) { return row_off != 0 ? 0 : (int)std::max<int64_t>(room, 0); }
+
+std::unique_ptr<DeviceBuf> upload(const void* src, size_t bytes, const char* what)
+{
+    auto d = std::make_unique<DeviceBuf>(bytes);
+    if (src && bytes) hip_check(hipMemcpy(d->p, src, bytes, hipMemcpyHostToDevice), what);
+    return d;
+}
+
+// Raw GGUF blocks [n, k] of one type -> the device planes of a QMat (kept alive by `keep`).
+// (a Q8_0 matrix with k % 256 != 0 can be repacked: it is the launcher that refuses it)
+void check_qmat_type(int32_t ggml_type, int32_t k)
+{
+    if (!ggml_matrix_type((uint32_t)ggml_type)) throw InvalidConfig(std::string("unsupported GGML matrix type ") + ggml_type_name((uint32_t)ggml_type));
+    if (k % 32 || (ggml_type != (int32_t)GGML_Q8_0 && k % 256)) throw InvalidConfig("k must be a whole number of the type's blocks");
+}
+
+QMat upload_qmat(int32_t ggml_type, const void* blocks, int32_t n, int32_t k, std::vector<std::unique_ptr<DeviceBuf>>& keep)
+{
+    const QPlanes planes = repack_ggml((uint32_t)ggml_type, static_cast<const uint8_t*>(blocks), n, k);
+    const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; ++i) {
+        if (planes.plane[i].empty()) continue;
+        keep.push_back(upload(planes.plane[i].data(), planes.plane[i].size(), "H2D weights"));
+        ptr[i] = keep.back()->p;
+    }
+    QMat W;
+    W.type = (uint32_t)ggml_type; W.n = n; W.k = k; W.q = ptr[0]; W.q2 = ptr[1]; W.s = ptr[2]; W.s2 = ptr[3];
+    return W;
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_fused_proj_fp8(int32_t device, int32_t mode, const void* const* codes, const float* const* scales,
+                                                           const int32_t* scale_rows, const int32_t* scale_cols, const int32_t* n, int32_t k,
+                                                           const float* x, int32_t rows_alloc, int64_t ldx, int32_t rows, const float* gamma,
+                                                           float eps, const float* bias, const float* r, int64_t ldr, int32_t r_is_y0,
+                                                           float* const* y, const int32_t* out_rows, const int64_t* ldy, int32_t row_off,
+                                                           int32_t offset_on_device)
+{
+    if (!codes || !scales || !scale_rows || !scale_cols || !n || !x || !y || !out_rows || !ldy) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const ProjShape s = check_fused_proj(mode, n, k, rows_alloc, ldx, rows, r, ldr, r_is_y0, y, out_rows, ldy, row_off);
+        int kind[3] = {0, 0, 0};
+        for (int i = 0; i < s.n_mats; ++i) {
+            if (!codes[i] || !scales[i]) throw InvalidConfig("a matrix of this mode is NULL");
+            kind[i] = fp8_scale_kind(n[i], k, scale_rows[i], scale_cols[i]);
+            if (kind[i] < 0)
+                throw InvalidConfig("FP8 projection: a scale of shape [" + std::to_string(scale_rows[i]) + ", " + std::to_string(scale_cols[i]) +
+                                    "] is neither [1, 1] (per tensor), [n, 1] (per channel) nor [ceil(n / 128), k / 128] (block)");
+            const uint8_t* c = static_cast<const uint8_t*>(codes[i]);
+            for (int64_t e = 0, end = (int64_t)n[i] * k; e < end; ++e)
+                if ((c[e] & 0x7F) == 0x7F) throw InvalidConfig("FP8 projection: NaN code at element " + std::to_string(e));
+        }
+        use_device(device);
+        std::vector<std::unique_ptr<DeviceBuf>> keep;
+        Fp8ProjArgs a;
+        a.mode = mode == 1 ? F8_QKV : (mode == 2 ? F8_SWIGLU : F8_PLAIN);
+        for (int i = 0; i < s.n_mats; ++i) {
+            keep.push_back(upload(codes[i], (size_t)n[i] * k, "H2D codes"));
+            a.W[i].codes = static_cast<const uint8_t*>(keep.back()->p);
+            keep.push_back(upload(scales[i], (size_t)scale_rows[i] * scale_cols[i] * 4, "H2D scales"));
+            a.W[i].scale = static_cast<const float*>(keep.back()->p);
+            a.W[i].n = n[i]; a.W[i].k = k; a.W[i].kind = kind[i];
+        }
+        const auto xd = upload(x, (size_t)rows_alloc * (size_t)ldx * 4, "H2D x");
+        const auto gd = upload(gamma, (size_t)k * 4, "H2D gamma");
+        const auto bd = upload(bias, (size_t)s.n_tot * 4, "H2D bias");
+        const auto rd = upload(r, (size_t)std::max(rows, 1) * (size_t)ldr * 4, "H2D r");
+        const auto od = upload(&row_off, sizeof(int), "H2D row_off");
+        const ProjOutputs out(s, y, out_rows, ldy);
+        a.X = static_cast<const float*>(xd->p); a.ldx = ldx; a.rows = rows;
+        a.gamma = gamma ? static_cast<const float*>(gd->p) : nullptr; a.eps = eps;
+        a.bias = bias ? static_cast<const float*>(bd->p) : nullptr;
+        if (r_is_y0) {
+            a.R = out.dev(0); a.ldr = ldy[0];
+        } else if (r) {
+            a.R = static_cast<const float*>(rd->p); a.ldr = ldr;
+        }
+        for (int i = 0; i < s.n_outs; ++i) {
+            a.Y[i] = out.dev(i); a.ldy[i] = ldy[i];
+        }
+        a.row_off = row_off;
+        if (offset_on_device) {
+            a.row_off_ptr = static_cast<const int*>(od->p);
+            a.row_off = decoy_offset(row_off, mode == 1 ? std::min(out_rows[1], out_rows[2]) - rows : 0);
+        }
+        launcher_check(launch_fp8_proj(a, nullptr), "fp8 projection");
+        hip_check(hipDeviceSynchronize(), "sync");
+        out.fetch(y);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_fused_proj_ggml(int32_t device, int32_t mode, const void* const* blocks, const int32_t* ggml_types,
+                                                            const int32_t* n, int32_t k, const float* x, int32_t rows_alloc, int64_t ldx,
+                                                            int32_t rows, const float* gamma, float eps, const float* bias, int32_t bias_floats,
+                                                            const int32_t* bias_off, const float* r, int64_t ldr, int32_t r_is_y0,
+                                                            float* const* y, const int32_t* out_rows, const int64_t* ldy, int32_t row_off,
+                                                            int32_t offset_on_device, int32_t head_dim, const float* cos_t, const float* sin_t,
+                                                            int32_t positions, int32_t q8k, float* xn_out, int8_t* xq_out, float* xd_out)
+{
+    if (!blocks || !ggml_types || !n || !x || !y || !out_rows || !ldy) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const ProjShape s = check_fused_proj(mode, n, k, rows_alloc, ldx, rows, r, ldr, r_is_y0, y, out_rows, ldy, row_off);
+        for (int i = 0; i < s.n_mats; ++i) {
+            if (!blocks[i]) throw InvalidConfig("a matrix of this mode is NULL");
+            check_qmat_type(ggml_types[i], k);
+        }
+        if (bias) {
+            if (!bias_off) throw InvalidConfig("a bias needs bias_off[3]");
+            for (int i = 0; i < (mode == 2 ? 1 : s.n_mats); ++i)
+                if (bias_off[i] < 0 || (int64_t)bias_off[i] + n[i] > bias_floats) throw InvalidConfig("bias_off + the segment's columns exceed bias_floats");
+        }
+        if (mode == 1) {  // Q and K are rotated in the epilogue: whole heads, and a table row for every position
+            if (head_dim < 2 || (head_dim & 1) || n[0] % head_dim || n[1] % head_dim || !cos_t || !sin_t)
+                throw InvalidConfig("Q | K | V needs an even head_dim dividing the Q and K rows, and cos / sin tables");
+            if (positions < 1 || (int64_t)row_off + rows > positions)
+                throw InvalidConfig("positions " + std::to_string(row_off) + " .. +" + std::to_string(rows) + " are past the table's " +
+                                    std::to_string(positions) + " rows");
+        }
+        use_device(device);
+        std::vector<std::unique_ptr<DeviceBuf>> keep;
+        QFusedArgs a;
+        a.mode = mode == 1 ? QF_QKV : (mode == 2 ? QF_SWIGLU : QF_PLAIN);
+        for (int i = 0; i < s.n_mats; ++i) a.W[i] = upload_qmat(ggml_types[i], blocks[i], n[i], k, keep);
+        if (mode == 1) {  // (LlmModel::step_qkv: a job is a pair of columns)
+            a.seg_jobs[0] = n[0] / 2; a.seg_jobs[1] = n[1] / 2; a.seg_jobs[2] = (n[2] + 1) / 2;
+            a.jobs = a.seg_jobs[0] + a.seg_jobs[1] + a.seg_jobs[2];
+        } else if (mode == 2) {
+            a.jobs = n[0];
+        } else {
+            a.seg_jobs[0] = a.jobs = (n[0] + 1) / 2;
+        }
+        const int nb = k / 256;
+        const auto xd = upload(x, (size_t)rows_alloc * (size_t)ldx * 4, "H2D x");
+        const auto gd = upload(gamma, (size_t)k * 4, "H2D gamma");
+        const auto bd = upload(bias, bias ? (size_t)bias_floats * 4 : 0, "H2D bias");
+        const auto rd = upload(r, (size_t)std::max(rows, 1) * (size_t)ldr * 4, "H2D r");
+        const auto od = upload(&row_off, sizeof(int), "H2D row_off");
+        const size_t tb = mode == 1 ? (size_t)positions * (size_t)(head_dim / 2) * 4 : 0;
+        const auto cd = upload(mode == 1 ? cos_t : nullptr, tb, "H2D cos"), sd = upload(mode == 1 ? sin_t : nullptr, tb, "H2D sin");
+        const size_t rk = (size_t)std::max(rows, 1) * (size_t)k;
+        GuardedBuf xn(rk * 4), xq(rk), xs((size_t)std::max(rows, 1) * (size_t)std::max(nb, 1) * 4);
+        const ProjOutputs out(s, y, out_rows, ldy);
+        a.k = k; a.rows = rows;
+        const float* G = gamma ? static_cast<const float*>(gd->p) : nullptr;
+        if (!q8k) {  // (LlmModel::quant_source)
+            a.X = static_cast<const float*>(xd->p); a.ldx = ldx; a.gamma = G; a.eps = eps;
+        } else {
+            launcher_check(launch_qprep(static_cast<const float*>(xd->p), ldx, rows, k, G, eps, G ? xn.as<float>() : nullptr, xq.as<int8_t>(),
+                                        xs.as<float>(), nullptr), "qprep");
+            a.X = G ? xn.as<float>() : static_cast<const float*>(xd->p); a.ldx = G ? k : ldx; a.Xq = xq.as<int8_t>(); a.Xd = xs.as<float>();
+        }
+        if (bias) {
+            a.bias = static_cast<const float*>(bd->p);
+            for (int i = 0; i < 3; ++i) a.bias_off[i] = i < s.n_mats ? bias_off[i] : 0;
+        }
+        if (r_is_y0) {
+            a.R = out.dev(0); a.ldr = ldy[0];
+        } else if (r) {
+            a.R = static_cast<const float*>(rd->p); a.ldr = ldr;
+        }
+        for (int i = 0; i < s.n_outs; ++i) {
+            a.Y[i] = out.dev(i); a.ldy[i] = ldy[i];
+        }
+        a.row_off = row_off;
+        if (offset_on_device) {
+            a.row_off_ptr = static_cast<const int*>(od->p);
+            a.row_off = decoy_offset(row_off, mode == 1 ? std::min(std::min(out_rows[1], out_rows[2]), positions) - rows : 0);
+        }
+        if (mode == 1) {
+            a.head_dim = head_dim; a.cos_t = static_cast<const float*>(cd->p); a.sin_t = static_cast<const float*>(sd->p);
+        }
+        launcher_check(launch_qfused(a, nullptr), "quantized projection");
+        hip_check(hipDeviceSynchronize(), "sync");
+        out.fetch(y);
+        if (q8k) {
+            xn.check("normalised rows"); xq.check("Q8_K codes"); xs.check("Q8_K scales");
+            if (xn_out && G) hip_check(hipMemcpy(xn_out, xn.buf.p, rk * 4, hipMemcpyDeviceToHost), "D2H xn");
+            if (xq_out) hip_check(hipMemcpy(xq_out, xq.buf.p, rk, hipMemcpyDeviceToHost), "D2H codes");
+            if (xd_out) hip_check(hipMemcpy(xd_out, xs.buf.p, (size_t)rows * nb * 4, hipMemcpyDeviceToHost), "D2H scales");
+        }
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qembed(int32_t device, const uint32_t* ids, int32_t n_ids, const void* blocks, int32_t ggml_type,
+                                                   int32_t vocab, int32_t k, float* out)
+{
+    if (!ids || !blocks || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_ids < 1 || n_ids > 4096 || vocab < 1 || vocab > (1 << 20) || k < 1 || k > (1 << 20)) throw InvalidConfig("n_ids 1 .. 4096; vocab, k 1 .. 2^20");
+        if (!ggml_matrix_type((uint32_t)ggml_type) || k % 256) throw InvalidConfig("a Q8_0 / Q4_K / Q6_K table with k % 256 == 0");
+        use_device(device);
+        std::vector<std::unique_ptr<DeviceBuf>> keep;
+        const QMat table = upload_qmat(ggml_type, blocks, vocab, k, keep);
+        const auto idd = upload(ids, (size_t)n_ids * 4, "H2D ids");
+        const size_t ob = (size_t)n_ids * (size_t)k * 4;
+        GuardedBuf od(ob);
+        hip_check(hipMemcpy(od.buf.p, out, ob, hipMemcpyHostToDevice), "H2D out");
+        launcher_check(launch_qembed(static_cast<const uint32_t*>(idd->p), n_ids, table, od.as<float>(), nullptr), "qembed");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.check("embedding rows");
+        hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_q8k_quantize(int32_t device, const float* x, int32_t rows, int64_t ldx, int32_t k, int8_t* codes_out,
+                                                         float* scales_out, float* deq_out)
+{
+    if (!x || !codes_out || !scales_out || !deq_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 64 || k < 1 || k > (1 << 20) || k % 256 || ldx < k || (ldx & 3) || ldx > (1 << 21))
+            throw InvalidConfig("rows 1 .. 64; k a multiple of 256; ldx a multiple of 4 covering k");
+        use_device(device);
+        const auto xd = upload(x, (size_t)rows * (size_t)ldx * 4, "H2D x");
+        const size_t rk = (size_t)rows * (size_t)k, sb = (size_t)rows * (k / 256) * 4;
+        GuardedBuf cd(rk), sd(sb), dd(rk * 4);
+        launcher_check(launch_q8k_quantize(static_cast<const float*>(xd->p), ldx, rows, k, cd.as<int8_t>(), sd.as<float>(), dd.as<float>(), nullptr),
+                       "q8k quantize");
+        hip_check(hipDeviceSynchronize(), "sync");
+        cd.check("Q8_K codes"); sd.check("Q8_K scales"); dd.check("Q8_K deq");
+        hip_check(hipMemcpy(codes_out, cd.buf.p, rk, hipMemcpyDeviceToHost), "D2H codes");
+        hip_check(hipMemcpy(scales_out, sd.buf.p, sb, hipMemcpyDeviceToHost), "D2H scales");
+        hip_check(hipMemcpy(deq_out, dd.buf.p, rk * 4, hipMemcpyDeviceToHost), "D2H deq");
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
                                                        int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused,
                                                        float* logprob_out, uint32_t* top_out, float* top_logprob_out, float* lse_out)

@@ -293,6 +293,128 @@ def llm_gemv_att(slabs, w, bias, r, head_dim: int, bf16: bool = False, rows: int
     return y
 
 
+# ---- the decode step's fused projections and their preparation kernels, alone ----
+PROJ_PLAIN, PROJ_QKV, PROJ_SWIGLU = 0, 1, 2
+
+
+def _proj_common(mats, x, ys, r, rows, in_place=False):
+    """The arrays both fused-projection entries take: x [rows_alloc, ldx], ys copied (the entry writes into the copies; in_place:
+    into ys themselves, which must then be C-contiguous float32 arrays -- a refused call must leave them as they are)."""
+    xa = np.ascontiguousarray(x, np.float32)
+    if in_place and any(not (isinstance(y, np.ndarray) and y.dtype == np.float32 and y.flags.c_contiguous) for y in ys):
+        raise ValueError("in_place: ys must be C-contiguous float32 arrays")
+    out = list(ys) if in_place else [np.array(y, np.float32, order="C") for y in ys]
+    if xa.ndim != 2 or any(y.ndim != 2 for y in out) or not 1 <= len(out) <= 3 or not 1 <= len(mats) <= 3:
+        raise ValueError("x: [rows_alloc, ldx]; ys: 1-3 arrays [out_rows, ldy]; 1-3 matrices")
+    yp = (C.c_void_p * 3)(*[y.ctypes.data for y in out])
+    orows = (C.c_int32 * 3)(*[y.shape[0] for y in out])
+    ldy = (C.c_int64 * 3)(*[y.shape[1] for y in out])
+    ra = None if r is None else np.ascontiguousarray(r, np.float32)
+    if ra is not None and (ra.ndim != 2 or ra.shape[0] < max(int(rows), 1)):
+        raise ValueError("r: [rows, ldr]")
+    return xa, out, yp, orows, ldy, ra
+
+
+def _proj_vector(a, n, what):
+    """A vector the entry reads n floats of."""
+    a = _c(a)
+    if a is not None and a.size != n:
+        raise ValueError(f"{what}: {n} floats, not {a.size}")
+    return a
+
+
+_GGML_BLOCK = {8: (32, 34), 12: (256, 144), 14: (256, 210)}      # type: (elements, bytes) per block
+
+
+def _ggml_blocks(ggml_type, blocks, n, k):
+    """Raw blocks [n, bytes per row] of a type this module knows, checked against k (the entry refuses the other types, and a k
+    that is no whole number of blocks, before it reads them)."""
+    ba = np.ascontiguousarray(blocks, np.uint8)
+    be, bb = _GGML_BLOCK.get(int(ggml_type), (0, 0))
+    if be and k % be == 0 and ba.size != n * (k // be) * bb:
+        raise ValueError(f"blocks: {n} rows of {k // be} blocks of {bb} bytes, not {ba.size} bytes")
+    return ba
+
+
+def fused_proj_fp8(mode: int, mats, x, rows: int, ys, gamma=None, eps: float = 0.0, bias=None, r=None, r_is_y0: bool = False,
+                   row_off: int = 0, offset_on_device: bool = False, in_place: bool = False, device: int = 0):
+    """One launch_fp8_proj on host arrays (kjarni_hip_op_fused_proj_fp8).  mats: 1-3 of (codes uint8 [n, k], scale f32
+    [scale_rows, scale_cols]); x [rows_alloc, ldx]; ys: the mode's outputs [out_rows, ldy] as they are before the launch.  Returns
+    the outputs after it."""
+    xa, out, yp, orows, ldy, ra = _proj_common(mats, x, ys, r, rows, in_place)
+    codes = [np.ascontiguousarray(c, np.uint8) for c, _ in mats]
+    scales = [np.ascontiguousarray(s, np.float32) for _, s in mats]
+    if any(c.ndim != 2 or s.ndim != 2 for c, s in zip(codes, scales)):
+        raise ValueError("codes [n, k], scale [scale_rows, scale_cols]")
+    cp = (C.c_void_p * 3)(*[c.ctypes.data for c in codes])
+    sp = (C.c_void_p * 3)(*[s.ctypes.data for s in scales])
+    sr = (C.c_int32 * 3)(*[s.shape[0] for s in scales])
+    sc = (C.c_int32 * 3)(*[s.shape[1] for s in scales])
+    n = (C.c_int32 * 3)(*[c.shape[0] for c in codes])
+    k = codes[0].shape[1]
+    if any(c.shape[1] != k for c in codes):
+        raise ValueError("the matrices must share k")
+    g = _proj_vector(gamma, k, "gamma")
+    b = _proj_vector(bias, codes[0].shape[0] if int(mode) != PROJ_QKV else sum(c.shape[0] for c in codes), "bias (the concatenated columns)")
+    check_error(lib().kjarni_hip_op_fused_proj_fp8(device, int(mode), cp, sp, sr, sc, n, k, _f(xa), xa.shape[0], xa.shape[1],
+                                                   int(rows), _f(g), float(eps), _f(b), _f(ra), 0 if ra is None else ra.shape[1],
+                                                   int(bool(r_is_y0)), yp, orows, ldy, int(row_off), int(bool(offset_on_device))))
+    return out
+
+
+def fused_proj_ggml(mode: int, mats, x, rows: int, ys, gamma=None, eps: float = 0.0, bias=None, bias_off=(0, 0, 0), r=None,
+                    r_is_y0: bool = False, row_off: int = 0, offset_on_device: bool = False, head_dim: int = 0, cos=None, sin=None,
+                    q8k: bool = False, k: Optional[int] = None, in_place: bool = False, device: int = 0):
+    """One launch_qfused on host arrays (kjarni_hip_op_fused_proj_ggml), after launch_qprep when q8k.  mats: 1-3 of (ggml type, raw
+    blocks uint8 [n, bytes per row]); k: the matrices' columns (default: x's).  Returns (outputs, None), or with q8k (outputs,
+    (xn [rows, k] -- NaN without gamma --, codes int8 [rows, k], scales [rows, k // 256])) as the device produced them."""
+    xa, out, yp, orows, ldy, ra = _proj_common(mats, x, ys, r, rows, in_place)
+    k = xa.shape[1] if k is None else int(k)
+    if any(np.ndim(b) != 2 for _, b in mats):
+        raise ValueError("blocks [n, bytes per row]")
+    blocks = [_ggml_blocks(t, b, np.shape(b)[0], k) for t, b in mats]
+    bp = (C.c_void_p * 3)(*[b.ctypes.data for b in blocks])
+    ty = (C.c_int32 * 3)(*[int(t) for t, _ in mats])
+    n = (C.c_int32 * 3)(*[b.shape[0] for b in blocks])
+    g, b = _proj_vector(gamma, k, "gamma"), _c(bias)      # (the entry holds bias_off + n against the bias's own length)
+    boff = (C.c_int32 * 3)(*[int(v) for v in bias_off])
+    ct = st = None
+    if cos is not None:
+        ct, st = _tables(cos, sin, head_dim)
+    rws = max(int(rows), 1)
+    xn = np.full((rws, k), np.nan, np.float32)
+    xq = np.zeros((rws, k), np.int8)
+    xd = np.full((rws, max(k // 256, 1)), np.nan, np.float32)
+    check_error(lib().kjarni_hip_op_fused_proj_ggml(device, int(mode), bp, ty, n, k, _f(xa), xa.shape[0], xa.shape[1], int(rows), _f(g), float(eps),
+                                                    _f(b), 0 if b is None else b.size, boff, _f(ra), 0 if ra is None else ra.shape[1],
+                                                    int(bool(r_is_y0)), yp, orows, ldy, int(row_off), int(bool(offset_on_device)), int(head_dim),
+                                                    _f(ct), _f(st), 0 if ct is None else ct.shape[0], int(bool(q8k)), _f(xn),
+                                                    xq.ctypes.data_as(C.c_void_p), _f(xd)))
+    return out, ((xn, xq, xd) if q8k else None)
+
+
+def qembed(ids, ggml_type: int, blocks, vocab: int, k: int, out=None, device: int = 0):
+    """launch_qembed alone (kjarni_hip_op_qembed): the dequantized table rows ids[i] [len(ids), k]; an id >= vocab gives zeros."""
+    ia = np.ascontiguousarray(ids, np.uint32)
+    ba = _ggml_blocks(ggml_type, blocks, int(vocab), int(k))
+    oa = np.full((ia.size, k), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+    if oa.size != ia.size * k:
+        raise ValueError("out: [len(ids), k]")
+    check_error(lib().kjarni_hip_op_qembed(device, ia.ctypes.data_as(C.POINTER(C.c_uint32)), ia.size, ba.ctypes.data_as(C.c_void_p),
+                                           int(ggml_type), int(vocab), int(k), _f(oa)))
+    return oa
+
+
+def q8k_quantize(x, k: int, device: int = 0):
+    """launch_q8k_quantize alone (kjarni_hip_op_q8k_quantize): x [rows, ldx] -> (codes int8 [rows, k], scales [rows, k // 256],
+    deq [rows, k])."""
+    xa = np.ascontiguousarray(x, np.float32)
+    rows = xa.shape[0]
+    codes, scales, deq = np.zeros((rows, k), np.int8), np.full((rows, max(k // 256, 1)), np.nan, np.float32), np.full((rows, k), np.nan, np.float32)
+    check_error(lib().kjarni_hip_op_q8k_quantize(device, _f(xa), rows, xa.shape[1], int(k), codes.ctypes.data_as(C.c_void_p), _f(scales), _f(deq)))
+    return codes, scales, deq
+
+
 def _tables(cos, sin, head_dim):
     ct, st = np.ascontiguousarray(cos, np.float32), np.ascontiguousarray(sin, np.float32)
     if ct.ndim != 2 or ct.shape != st.shape or ct.shape[1] != head_dim // 2:
