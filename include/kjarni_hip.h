@@ -971,6 +971,31 @@ KjarniErrorCode kjarni_hip_op_gemv_row_att(int32_t device, const float* slabs, i
  * what the launcher refuses: rows != 1, k 2048 with more than 8 splits, k 4096 with more than 4, any other k, r NULL. */
 KjarniErrorCode kjarni_hip_op_llm_gemv_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const void* w, int32_t bf16,
                                            const float* bias, const float* r, int32_t n_out, int32_t k, int32_t rows, float* y);
+/* ---- the prompt-route GEMM and the two prefill attention kernels, alone -------------------------------------------------------------
+ * kjarni_hip_op_prefill_gemm: y[m, n] = a[m, k] . w[n, k]^T (+ bias) (+ r) through launch_prefill_gemm (64 x 64 tiles, K slices
+ * added by the reduce kernel), as the decoders' prompt projections call it.  a [a_rows, lda] (a_rows >= m, lda >= k); w [n, k] f32,
+ * or bf16 bit patterns with bf16 = 1; bias [n] or NULL.  Residual: r [m, ldr] (NULL: none), or with r_is_y the output itself
+ * (r and ldr are then ignored and the residual's stride is ldy).  y [m, ldy] is read, gets the result and is written back whole.
+ * gate [m, n] (may be NULL) is read and becomes silu(gate) * (the product); with a K split y is then left as it was, without one
+ * y also holds the product.  split: 0 passes the launcher no scratch, 1 a scratch of prefill_gemm_scratch_floats() floats filled
+ * with NaN (all-ones words) before the launch; *scratch_written (may be NULL; needs split) receives the number of scratch words
+ * that no longer hold that pattern.  *ksplit_used: the number of K slices the launcher took (1, 2, 4 or 8; by the launcher's own
+ * rule).  INVALID_CONFIG, before any GPU work and with every output untouched: k % 32, lda % 4, m < 0 or above 4096, n or k < 1
+ * (n above 2^17, k above 2^16, n * k above 2^26), a gate with ldy != n or n % 4, lda < k, ldy < n, a residual with ldr < n. */
+KjarniErrorCode kjarni_hip_op_prefill_gemm(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* w, int32_t bf16,
+                                           const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
+                                           int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used, int64_t* scratch_written);
+/* kjarni_hip_op_prefill_attention: causal grouped-query attention of `rows` prompt rows at positions base .. base + rows - 1 over
+ * key rows 0 .. base + rows - 1 through launch_prefill_attention: query row s sees keys <= base + s.  q [rows, ldq]
+ * (heads * head_dim used); k / v: k_floats / v_floats floats, key row t at k + t * ldk, KV head h / kv_group at columns
+ * [(h / kv_group) * head_dim, + head_dim).  ctx [rows, ldc] is read, gets the context rows and is written back whole.  *route: the
+ * kernel the launcher took, 0 the vector kernel, 1 the matrix-core kernel (blocks of at least 256 rows at head_dim 64 / 128).
+ * INVALID_CONFIG, before any GPU work and with every output untouched: head_dim not 16 / 32 / 64 / 128, rows < 1, base < 0,
+ * kv_group < 1 or not dividing heads, leading dimensions that are no multiple of 4 or do not cover the heads, key rows that reach
+ * outside k_floats / v_floats. */
+KjarniErrorCode kjarni_hip_op_prefill_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k, int64_t k_floats,
+                                                int64_t ldk, const float* v, int64_t v_floats, int64_t ldv, int32_t base, int32_t heads,
+                                                int32_t head_dim, int32_t kv_group, float* ctx, int64_t ldc, int32_t* route);
 /* RoPE alone, host pointers: x [x_rows, ldx] is read, its first `rows` rows (n_heads heads of head_dim) are rotated in place and
  * it is written back whole.  kjarni_hip_op_rope: row r by table row pos + r (the kernel of the prompt and decode paths);
  * kjarni_hip_op_rope_rows: row r by table row row_pos[r].  cos_t / sin_t [table_rows, head_dim / 2].  Positions outside the

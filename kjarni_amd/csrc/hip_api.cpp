@@ -878,6 +878,87 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_gemv_att(int32_t device, const f
     });
 }
 
+// ---- the prompt-route GEMM and the two prefill attention kernels, alone -----------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* w, int32_t bf16,
+                                                         const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy,
+                                                         float* gate, int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used,
+                                                         int64_t* scratch_written)
+{
+    if (!a || !w || !y || !ksplit_used) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (m < 0 || m > 4096 || a_rows < std::max(m, 1) || a_rows > 8192) throw InvalidConfig("m must be 0 .. 4096 and a_rows max(m, 1) .. 8192");
+        if (n < 1 || k < 1 || n > (1 << 17) || k > (1 << 16) || (int64_t)n * k > ((int64_t)1 << 26))
+            throw InvalidConfig("n must be 1 .. 2^17, k 1 .. 2^16, n * k at most 2^26");
+        if (k % 32 || lda % 4) throw InvalidConfig("launch_prefill_gemm refuses these arguments: k a multiple of 32, lda a multiple of 4");
+        if (lda < k || ldy < n || std::max(lda, ldy) > (1 << 18)) throw InvalidConfig("lda must cover k and ldy n (at most 2^18)");
+        const bool res = r_is_y || r;
+        const int64_t ldr_ = r_is_y ? ldy : ldr;  // in place the residual is the output: one stride, as rows_finish calls it
+        if (res && (ldr_ < n || ldr_ > (1 << 18))) throw InvalidConfig("ldr must cover n (at most 2^18)");
+        if (gate && (ldy != n || (n & 3))) throw InvalidConfig("launch_prefill_gemm refuses these arguments: a gate needs ldy == n and n a multiple of 4");
+        if (split != 0 && split != 1) throw InvalidConfig("split must be 0 or 1");
+        if (scratch_written && !split) throw InvalidConfig("scratch_written without split");
+        use_device(device);
+        const size_t ab = (size_t)a_rows * (size_t)lda * 4, wb = (size_t)n * (size_t)k * (bf16 ? 2 : 4), yb = (size_t)m * (size_t)ldy * 4;
+        const size_t rb = r && !r_is_y ? (size_t)m * (size_t)ldr * 4 : 0, gb = gate ? (size_t)m * (size_t)n * 4 : 0;
+        const size_t sb = split ? prefill_gemm_scratch_floats(m, n) * 4 : 0;
+        DeviceBuf ad(ab), wd(wb), bd((size_t)n * 4), rd(rb), yd(yb), gd(gb), sd(sb);
+        hip_check(hipMemcpy(ad.p, a, ab, hipMemcpyHostToDevice), "H2D a");
+        hip_check(hipMemcpy(wd.p, w, wb, hipMemcpyHostToDevice), "H2D w");
+        if (bias) hip_check(hipMemcpy(bd.p, bias, (size_t)n * 4, hipMemcpyHostToDevice), "H2D bias");
+        if (rb) hip_check(hipMemcpy(rd.p, r, rb, hipMemcpyHostToDevice), "H2D r");
+        if (yb) hip_check(hipMemcpy(yd.p, y, yb, hipMemcpyHostToDevice), "H2D y");
+        if (gb) hip_check(hipMemcpy(gd.p, gate, gb, hipMemcpyHostToDevice), "H2D gate");
+        if (sb) hip_check(hipMemset(sd.p, 0xFF, sb), "poison scratch");  // (all-ones words are NaN: a slab the kernels skip would show)
+        const float* bp = bias ? (const float*)bd.p : nullptr;
+        const float* rp = r_is_y ? (const float*)yd.p : (r ? (const float*)rd.p : nullptr);
+        float* sp = split ? (float*)sd.p : nullptr;
+        *ksplit_used = prefill_gemm_launch_ksplit(bp, rp, ldr_, (const float*)yd.p, ldy, m, n, k, sp);
+        launcher_check(launch_prefill_gemm((const float*)ad.p, lda, wd.p, bf16 ? 1 : 0, bp, rp, ldr_, (float*)yd.p, ldy, m, n, k, nullptr, sp,
+                                           gate ? (float*)gd.p : nullptr), "prefill gemm");
+        hip_check(hipDeviceSynchronize(), "sync");
+        if (yb) hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+        if (gb) hip_check(hipMemcpy(gate, gd.p, gb, hipMemcpyDeviceToHost), "D2H gate");
+        if (scratch_written) {  // the scratch words that no longer hold the poison
+            std::vector<uint32_t> words(sb / 4);
+            hip_check(hipMemcpy(words.data(), sd.p, sb, hipMemcpyDeviceToHost), "D2H scratch");
+            *scratch_written = (int64_t)(words.size() - (size_t)std::count(words.begin(), words.end(), 0xFFFFFFFFu));
+        }
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k,
+                                                              int64_t k_floats, int64_t ldk, const float* v, int64_t v_floats, int64_t ldv,
+                                                              int32_t base, int32_t heads, int32_t head_dim, int32_t kv_group, float* ctx,
+                                                              int64_t ldc, int32_t* route)
+{
+    if (!q || !k || !v || !ctx || !route) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!prefill_attention_supported(head_dim)) throw InvalidConfig("launch_prefill_attention refuses these arguments: head_dim must be 16, 32, 64 or 128");
+        if (rows < 1 || rows > 8192 || base < 0 || base > (1 << 20)) throw InvalidConfig("rows must be 1 .. 8192, base 0 .. 2^20");
+        if (heads < 1 || heads > 1024 || kv_group < 1 || kv_group > heads || heads % kv_group)
+            throw InvalidConfig("heads must be 1 .. 1024 and a multiple of kv_group");
+        const int64_t qd = (int64_t)heads * head_dim, kvd = (int64_t)(heads / kv_group) * head_dim;
+        if (ldq < qd || ldc < qd || ldk < kvd || ldv < kvd || ((ldq | ldk | ldv | ldc) & 3) || std::max(std::max(ldq, ldc), std::max(ldk, ldv)) > (1 << 20))
+            throw InvalidConfig("leading dimensions must cover the heads, be multiples of 4 and at most 2^20");
+        const int64_t keys = (int64_t)base + rows;
+        if ((keys - 1) * ldk + kvd > k_floats || (keys - 1) * ldv + kvd > v_floats) throw InvalidConfig("the keys reach outside k_floats / v_floats");
+        if (std::max(k_floats, v_floats) > ((int64_t)1 << 26)) throw InvalidConfig("k_floats / v_floats above 2^26");
+        use_device(device);
+        const size_t qb = (size_t)rows * (size_t)ldq * 4, cb = (size_t)rows * (size_t)ldc * 4;
+        DeviceBuf qd_(qb), kd((size_t)k_floats * 4), vd((size_t)v_floats * 4), cd(cb);
+        hip_check(hipMemcpy(qd_.p, q, qb, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.p, k, (size_t)k_floats * 4, hipMemcpyHostToDevice), "H2D k");
+        hip_check(hipMemcpy(vd.p, v, (size_t)v_floats * 4, hipMemcpyHostToDevice), "H2D v");
+        hip_check(hipMemcpy(cd.p, ctx, cb, hipMemcpyHostToDevice), "H2D ctx");
+        *route = prefill_attention_route((const float*)qd_.p, ldq, rows, (const float*)kd.p, ldk, (const float*)vd.p, ldv, head_dim);
+        launcher_check(launch_prefill_attention((const float*)qd_.p, ldq, rows, (const float*)kd.p, ldk, (const float*)vd.p, ldv, base, heads,
+                                                head_dim, kv_group, (float*)cd.p, ldc, nullptr), "prefill attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(ctx, cd.p, cb, hipMemcpyDeviceToHost), "D2H ctx");
+    });
+}
+
 namespace {
 
 void rope_hook(int32_t device, float* x, int64_t ldx, int32_t x_rows, int32_t rows, int32_t n_heads, int32_t head_dim, const float* cos_t,

@@ -57,12 +57,18 @@ hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int b
                                int64_t ldy, int M, int N, int K, hipStream_t stream, float* split_scratch = nullptr,
                                float* silu_gate = nullptr);  // silu_gate: [M, N] gate activations, overwritten with silu(gate) * (this product)
 size_t prefill_gemm_scratch_floats(int max_rows, int max_n);
+// The number of K slices launch_prefill_gemm takes for these arguments (1: the unsplit kernel, whatever the scratch): the
+// launcher's own decision, for callers that report it.
+int prefill_gemm_launch_ksplit(const float* bias, const float* R, int64_t ldr, const float* Y, int64_t ldy, int M, int N, int K,
+                               const float* split_scratch);
 // bf16 -> f32 copy of n values (n % 8 == 0): long prompts run the f32 tile GEMM (gemm.hip) on a widened weight matrix.
 hipError_t launch_widen_bf16(const void* src, float* dst, size_t n, hipStream_t stream);
 
 // Prefill: causal grouped-query attention of `rows` new rows (positions base .. base + rows - 1) over the cache rows
 // 0 .. base + rows - 1; head_dim in {16, 32, 64, 128}.
 bool prefill_attention_supported(int head_dim);
+// The kernel launch_prefill_attention takes for these arguments: 0 the vector kernel, 1 the matrix-core kernel (its own decision).
+int prefill_attention_route(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V, int64_t ldv, int head_dim);
 hipError_t launch_prefill_attention(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V, int64_t ldv, int base,
                                     int heads, int head_dim, int kv_group, float* ctx, int64_t ldc, hipStream_t stream);
 

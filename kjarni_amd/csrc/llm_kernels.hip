@@ -1437,6 +1437,16 @@ size_t prefill_gemm_scratch_floats(int max_rows, int max_n)
     return (size_t)1024 * PG_BM * PG_BN;
 }
 
+int prefill_gemm_launch_ksplit(const float* bias, const float* R, int64_t ldr, const float* Y, int64_t ldy, int M, int N, int K,
+                               const float* split_scratch)
+{
+    // the reduce kernel moves float4s: a scratch, N and every row stride multiples of 4, every base 16-byte aligned
+    if (split_scratch && (N & 3) == 0 && (ldy & 3) == 0 && (!R || (ldr & 3) == 0) && (reinterpret_cast<uintptr_t>(Y) & 15) == 0 &&
+        (!R || (reinterpret_cast<uintptr_t>(R) & 15) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0))
+        return prefill_gemm_ksplit(M, N, K);
+    return 1;
+}
+
 hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int bf16, const float* bias, const float* R, int64_t ldr, float* Y,
                                int64_t ldy, int M, int N, int K, hipStream_t stream, float* split_scratch, float* silu_gate)
 {
@@ -1444,10 +1454,7 @@ hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int b
     if (K % PG_BK || lda % 4 || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return hipErrorInvalidValue;
     if (silu_gate && (ldy != N || (N & 3) || (reinterpret_cast<uintptr_t>(silu_gate) & 15))) return hipErrorInvalidValue;
     const int m_tiles = (M + PG_BM - 1) / PG_BM, n_tiles = (N + PG_BN - 1) / PG_BN;
-    int ksplit = 1;
-    if (split_scratch && (N & 3) == 0 && (ldy & 3) == 0 && (!R || (ldr & 3) == 0) && (reinterpret_cast<uintptr_t>(Y) & 15) == 0 &&
-        (!R || (reinterpret_cast<uintptr_t>(R) & 15) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0))
-        ksplit = prefill_gemm_ksplit(M, N, K);
+    const int ksplit = prefill_gemm_launch_ksplit(bias, R, ldr, Y, ldy, M, N, K, split_scratch);
     const dim3 grid((unsigned)(m_tiles * n_tiles * ksplit));
 #define KJ_PG(RES)                                                                                                                  \
     hipLaunchKernelGGL((prefill_gemm_kernel<RES>), grid, dim3(256), 0, stream, A, lda, static_cast<const float*>(W), bias, R, ldr, Y, ldy, \
@@ -1658,14 +1665,21 @@ __global__ __launch_bounds__(256, D <= 64 ? 2 : 1) void prefill_attention_mfma_k
 
 bool prefill_attention_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128; }
 
+int prefill_attention_route(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V, int64_t ldv, int head_dim)
+{
+    // long blocks of 64- / 128-wide heads: the matrix-core kernel
+    return rows >= 256 && (head_dim == 64 || head_dim == 128) && (ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0
+               ? 1
+               : 0;
+}
+
 hipError_t launch_prefill_attention(const float* q, int64_t ldq, int rows, const float* K, int64_t ldk, const float* V, int64_t ldv, int base,
                                     int heads, int head_dim, int kv_group, float* ctx, int64_t ldc, hipStream_t stream)
 {
     if (rows <= 0) return hipSuccess;
     if (!prefill_attention_supported(head_dim)) return hipErrorInvalidValue;
-    // long blocks of 64- / 128-wide heads: the matrix-core kernel
-    if (rows >= 256 && (head_dim == 64 || head_dim == 128) && (ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(V)) & 15) == 0) {
+    if (prefill_attention_route(q, ldq, rows, K, ldk, V, ldv, head_dim) == 1) {
         const dim3 mgrid((unsigned)((rows + PM_Q - 1) / PM_Q), (unsigned)heads);
         const float mscale = 1.0f / sqrtf((float)head_dim);
         const int g = kv_group < 1 ? 1 : kv_group;

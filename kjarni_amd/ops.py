@@ -293,6 +293,50 @@ def llm_gemv_att(slabs, w, bias, r, head_dim: int, bf16: bool = False, rows: int
     return y
 
 
+# ---- the prompt-route GEMM and the two prefill attention kernels, alone ----
+def prefill_gemm(a, w, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=None, bf16: bool = False, split: bool = True,
+                 want_scratch_written: bool = False, device: int = 0):
+    """launch_prefill_gemm on host arrays (kjarni_hip_op_prefill_gemm): a [a_rows, lda] (k = w's width used), w [n, k] f32 or bf16
+    bit patterns (uint16, bf16 = True), y [m, ldy] given with whatever its padding holds, r [m, ldr] or r_is_y (the residual is y),
+    gate [m, n].  Returns (y, gate or None, ksplit_used[, scratch words written]) -- copies; the arguments stay as they were."""
+    aa = np.ascontiguousarray(a, np.float32)
+    wa = np.ascontiguousarray(w, np.uint16 if bf16 else np.float32)
+    ya = np.array(y, np.float32, order="C")
+    if aa.ndim != 2 or wa.ndim != 2 or ya.ndim != 2 or ya.shape[0] != int(m):
+        raise ValueError("a: [a_rows, lda]; w: [n, k]; y: [m, ldy]")
+    n, k = wa.shape
+    ba = _proj_vector(bias, n, "bias")
+    ra = None if r is None else np.ascontiguousarray(r, np.float32)
+    if ra is not None and (ra.ndim != 2 or ra.shape[0] != int(m)):
+        raise ValueError("r: [m, ldr]")
+    ga = None if gate is None else np.array(gate, np.float32, order="C")
+    if ga is not None and ga.shape != (int(m), n):
+        raise ValueError("gate: [m, n]")
+    used, written = C.c_int32(-1), C.c_int64(-1)
+    check_error(lib().kjarni_hip_op_prefill_gemm(device, _f(aa), aa.shape[1], aa.shape[0], wa.ctypes.data_as(C.c_void_p), int(bool(bf16)), _f(ba),
+                                                 _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y)), _f(ya), ya.shape[1], _f(ga), int(m),
+                                                 n, k, int(bool(split)), C.byref(used), C.byref(written) if want_scratch_written else None))
+    return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
+
+
+def prefill_attention(q, k, v, ldk: int, ldv: int, base: int, heads: int, head_dim: int, kv_group: int = 1, ctx=None, device: int = 0):
+    """launch_prefill_attention on host arrays (kjarni_hip_op_prefill_attention): q [rows, ldq]; k and v flat float buffers, key row
+    t at t * ldk; row s sees keys <= base + s.  Returns (ctx [rows, ldc] -- given, or NaN [rows, heads * head_dim] -- with the context
+    rows written, route): 0 the vector kernel, 1 the matrix-core kernel."""
+    qa = np.ascontiguousarray(q, np.float32)
+    ka, va = np.ascontiguousarray(k, np.float32).reshape(-1), np.ascontiguousarray(v, np.float32).reshape(-1)
+    if qa.ndim != 2:
+        raise ValueError("q: [rows, ldq]")
+    rows = qa.shape[0]
+    ca = np.full((rows, heads * head_dim), np.nan, np.float32) if ctx is None else np.array(ctx, np.float32, order="C")
+    if ca.ndim != 2 or ca.shape[0] != rows:
+        raise ValueError("ctx: [rows, ldc]")
+    route = C.c_int32(-1)
+    check_error(lib().kjarni_hip_op_prefill_attention(device, _f(qa), qa.shape[1], rows, _f(ka), ka.size, int(ldk), _f(va), va.size, int(ldv),
+                                                      int(base), int(heads), int(head_dim), int(kv_group), _f(ca), ca.shape[1], C.byref(route)))
+    return ca, route.value
+
+
 # ---- the decode step's fused projections and their preparation kernels, alone ----
 PROJ_PLAIN, PROJ_QKV, PROJ_SWIGLU = 0, 1, 2
 

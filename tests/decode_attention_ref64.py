@@ -98,3 +98,15 @@ def merge_project64(slabs, w, bias, r, bf16=False):
     if bias is not None:
         y = y + np.asarray(bias, np.float64)
     return y + np.asarray(r, np.float64)
+
+
+def exact_score_inputs(rng, d, levels, rows=1, heads=2):
+    """q [rows, heads * d] and K [n, heads * d] whose every score is exact in float32: 1 / sqrt(d) is a power of two at
+    d = 4, 16, 64, every entry is a multiple of 0.25, and q[:, 0] = sqrt(d) turns K's first column into the score's level:
+    score(t) = levels[t] + (a sum of at most d - 1 products of quarters in [-1, 1]) / sqrt(d)."""
+    n = len(levels)
+    quarters = lambda shape: (rng.integers(-4, 5, shape) * 0.25).astype(np.float32)  # noqa: E731
+    q, k = quarters((rows, heads, d)), quarters((n, heads, d))
+    q[:, :, 0] = np.sqrt(float(d))
+    k[:, :, 0] = np.asarray(levels, np.float32)[:, None]
+    return q.reshape(rows, heads * d), k.reshape(n, heads * d)

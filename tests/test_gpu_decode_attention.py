@@ -199,23 +199,11 @@ def test_ragged_lanes():
 
 # ---- scores far from zero --------------------------------------------------------------------------------------------------------
 
-def _exact_inputs(rng, d, levels):
-    """q [1, 2 * d] and K [n, 2 * d] (two heads) whose every score is exact in float32: 1 / sqrt(d) is a power of two at
-    d = 4, 16, 64, every entry is a multiple of 0.25, and q[0] = sqrt(d) turns K's first column into the score's level:
-    score(t) = levels[t] + (a sum of at most d - 1 products of quarters in [-1, 1]) / sqrt(d)."""
-    n = len(levels)
-    quarters = lambda shape: (rng.integers(-4, 5, shape) * 0.25).astype(np.float32)  # noqa: E731
-    q, k = quarters((1, 2, d)), quarters((n, 2, d))
-    q[:, :, 0] = np.sqrt(float(d))
-    k[:, :, 0] = np.asarray(levels, np.float32)[:, None]
-    return q.reshape(1, 2 * d), k.reshape(n, 2 * d)
-
-
 def _stress(d, levels, splits, causal_base, seed):
     """Run the exact-score case with and without the mask; returns the float64 scores of the unmasked run."""
     rng = np.random.default_rng(seed)
     n = len(levels)
-    q, kk = _exact_inputs(rng, d, levels)
+    q, kk = R.exact_score_inputs(rng, d, levels)
     k = np.full((n + 2, 2 * d), np.nan, np.float32)
     k[:n] = kk
     v, ldv, _ = _kv(rng, [n], n + 2, 2 * d)
