@@ -996,6 +996,34 @@ KjarniErrorCode kjarni_hip_op_prefill_gemm(int32_t device, const float* a, int64
 KjarniErrorCode kjarni_hip_op_prefill_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k, int64_t k_floats,
                                                 int64_t ldk, const float* v, int64_t v_floats, int64_t ldv, int32_t base, int32_t heads,
                                                 int32_t head_dim, int32_t kv_group, float* ctx, int64_t ldc, int32_t* route);
+/* ---- mixture-of-experts (qwen3_moe): the router pick and the sparse FFN, alone ------------------------------------------------------
+ * kjarni_hip_op_moe_route: softmax over the E router logits of each row, the k largest (on equal logits the lower expert first),
+ * with norm_topk the k weights divided by their sum.  logits [rows, E]; ids_out [rows, k] (int32), weights_out [rows, k], slot 0
+ * the largest.  INVALID_CONFIG, before any GPU work and with every output untouched: E outside 2 .. 256, k outside 1 .. 8 or
+ * above E, rows outside 1 .. 2^20. */
+KjarniErrorCode kjarni_hip_op_moe_route(int32_t device, const float* logits, int32_t rows, int32_t E, int32_t k, int32_t norm_topk,
+                                        int32_t* ids_out, float* weights_out);
+/* kjarni_hip_op_moe_ffn: y = r + sum_j w_j * down_{e_j}( silu(gate_{e_j} xn) * (up_{e_j} xn) ), xn = RMSNorm(x, gamma, eps) (gamma
+ * NULL: x as it is), experts and weights by the route of xn . router^T, summed in slot order j = 0 .. k - 1.  x [rows, ldx]
+ * (`hidden` used); router [E, hidden], gate / up [E, Im, hidden], down [E, hidden, Im], f32 or bf16 bit patterns (bf16 = 1).
+ * Residual: r [rows, ldr], or with r_is_y the output itself (r and ldr are then ignored).  y [rows, ldy] is read, gets the result
+ * and is written back whole.  route: 0 the decoders' rule (fewer than 24 rows: the steps kernels in blocks of 8 rows, else the
+ * grouped kernels), 1 the steps kernels, 2 the grouped kernels; *route_used gets 1 or 2, *tiles_used the number of non-empty
+ * 64-slot tiles of the grouped plan (0 on the steps route).  ids_out / weights_out [rows, k]: what the router chose.
+ * INVALID_CONFIG, before any GPU work and with every output untouched: E outside 2 .. 256, k outside 1 .. 8 or above E, Im % 32,
+ * hidden % 32 or above 8192, k * Im above 16384, rows outside 1 .. 4096, a stack above 2^27 elements, a leading dimension that is
+ * no multiple of 4 or does not cover hidden, route outside 0 .. 2, no residual. */
+KjarniErrorCode kjarni_hip_op_moe_ffn(int32_t device, const float* x, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                      const void* router, const void* gate, const void* up, const void* down, int32_t bf16, int32_t hidden,
+                                      int32_t E, int32_t k, int32_t Im, int32_t norm_topk, const float* r, int64_t ldr, int32_t r_is_y, float* y,
+                                      int64_t ldy, int32_t route, int32_t* ids_out, float* weights_out, int32_t* route_used,
+                                      int32_t* tiles_used);
+/* kjarni_hip_decoder_moe_routing: what sparse layer `layer` of a qwen3_moe decoder chose in its last pass (a decode step: 1 row;
+ * a verify block or a lane step: its rows; a prompt chunk or a packed pass: its rows, at most 2048).  *rows gets the number of
+ * rows recorded; ids_out / weights_out (each may be NULL to ask for the count alone; capacity rows_capacity * k) get [rows, k].
+ * INVALID_CONFIG for a dense layer, a dense model, a layer out of range or a capacity below the rows recorded. */
+KjarniErrorCode kjarni_hip_decoder_moe_routing(KjarniHipDecoder* decoder, int32_t layer, int32_t rows_capacity, int32_t* rows, int32_t* ids_out,
+                                               float* weights_out);
 /* RoPE alone, host pointers: x [x_rows, ldx] is read, its first `rows` rows (n_heads heads of head_dim) are rotated in place and
  * it is written back whole.  kjarni_hip_op_rope: row r by table row pos + r (the kernel of the prompt and decode paths);
  * kjarni_hip_op_rope_rows: row r by table row row_pos[r].  cos_t / sin_t [table_rows, head_dim / 2].  Positions outside the

@@ -557,6 +557,11 @@ SIGNATURES = {
                                              _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "kjarni_hip_op_prefill_attention": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int64, _f32p, c_int64, c_int64, c_int32,
                                                   c_int32, c_int32, c_int32, _f32p, c_int64, POINTER(c_int32)]),
+    "kjarni_hip_op_moe_route": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), _f32p]),
+    "kjarni_hip_op_moe_ffn": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                        c_int32, c_int32, c_int32, c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int32, POINTER(c_int32),
+                                        _f32p, POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_decoder_moe_routing": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), _f32p]),
     "kjarni_hip_op_rope": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p, c_int32, c_int32]),
     "kjarni_hip_op_rope_rows": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p, c_int32,
                                           POINTER(c_int32)]),

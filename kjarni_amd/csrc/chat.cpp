@@ -219,7 +219,7 @@ GenerationConfig model_default_generation_config(const std::string& model_type, 
         c.top_k = Opt<size_t>(40);
         c.top_p = Opt<float>(0.9f);
         c.min_p = Opt<float>(0.05f);
-    } else if (model_type == "qwen2" || model_type == "qwen3") {  // qwen/model.rs:267-281 (Qwen3: the Qwen2 block)
+    } else if (model_type == "qwen2" || model_type == "qwen3" || model_type == "qwen3_moe") {  // qwen/model.rs:267-281 (Qwen3: the Qwen2 block)
         c.max_new_tokens = Opt<size_t>(512);
         c.repetition_penalty = 1.1f;
         c.add_bos_token = false;
@@ -269,6 +269,8 @@ const ChatModelInfo kChatModels[] = {
     {"qwen3-1.7b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
     {"qwen3-4b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
     {"qwen3-8b", "Qwen3 (QK-Norm)", "qwen3", "chat"},
+    {"qwen3-30b-a3b", "Qwen3-MoE (128 experts, 8 active)", "qwen3", "chat"},
+    {"qwen3-30b-a3b-instruct-2507", "Qwen3-MoE (128 experts, 8 active)", "qwen3", "chat"},
     {"llama3.2-1b-instruct", "Llama (Standard)", "llama", "chat"},
     {"llama3.2-3b-instruct", "Llama (Standard)", "llama", "chat"},
     {"phi3.5-mini", "Phi-3 (LongRoPE)", "phi3", "reasoning"},

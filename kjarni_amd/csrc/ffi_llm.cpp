@@ -72,6 +72,22 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_kv_rows(const KjarniHipDecoder*
     });
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_moe_routing(KjarniHipDecoder* d, int32_t layer, int32_t rows_capacity, int32_t* rows,
+                                                             int32_t* ids_out, float* weights_out)
+{
+    if (!d || !rows) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        const int n = d->model->moe_record_rows(layer);  // InvalidConfig for a dense layer or model, before anything is copied
+        if (ids_out || weights_out) {
+            if (!ids_out || !weights_out) throw InvalidConfig("ids_out and weights_out come together");
+            if (rows_capacity < n) throw InvalidConfig("rows_capacity is below the " + std::to_string(n) + " rows recorded");
+            d->model->moe_routing(layer, ids_out, weights_out);
+        }
+        *rows = n;
+    });
+}
+
 KJARNI_EXPORT void kjarni_hip_decoder_set_device_sampling(KjarniHipDecoder* d, int32_t on)
 {
     if (d) d->model->set_device_sampling(on != 0);

@@ -515,6 +515,9 @@ std::vector<int64_t> GgufFile::read_f32(const std::string& hf_name, std::vector<
 std::string GgufFile::config_json() const
 {
     const std::string& a = arch_;
+    if (a == "qwen3moe")
+        throw std::runtime_error("GGUF: unsupported architecture 'qwen3moe': quantized mixture-of-experts checkpoints (FP8, GGUF) are out of scope; "
+                                 "qwen3_moe loads from bf16 or f32 safetensors");
     if (a != "llama" && a != "qwen2") throw std::runtime_error("GGUF: unsupported architecture '" + a + "' (llama and qwen2 are)");
     auto req = [&](const std::string& key) {
         uint32_t v = 0;

@@ -21,6 +21,7 @@
 #include "llm_kernels.h"
 #include "whisper_kernels.h"
 #include "quant_kernels.h"
+#include "moe_kernels.h"
 
 using namespace kjarni;
 
@@ -956,6 +957,107 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_attention(int32_t device, co
                                                 head_dim, kv_group, (float*)cd.p, ldc, nullptr), "prefill attention");
         hip_check(hipDeviceSynchronize(), "sync");
         hip_check(hipMemcpy(ctx, cd.p, cb, hipMemcpyDeviceToHost), "D2H ctx");
+    });
+}
+
+// ---- mixture-of-experts: the router pick and the sparse FFN, alone ------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_moe_route(int32_t device, const float* logits, int32_t rows, int32_t E, int32_t k, int32_t norm_topk,
+                                                      int32_t* ids_out, float* weights_out)
+{
+    if (!logits || !ids_out || !weights_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (E < 2 || E > MOE_MAX_EXPERTS) throw InvalidConfig("E must be 2 .. 256");
+        if (k < 1 || k > MOE_MAX_TOPK || k > E) throw InvalidConfig("k must be 1 .. 8 and at most E");
+        if (rows < 1 || rows > (1 << 20)) throw InvalidConfig("rows must be 1 .. 2^20");
+        use_device(device);
+        const size_t lb = (size_t)rows * (size_t)E * 4, ob = (size_t)rows * (size_t)k * 4;
+        DeviceBuf ld(lb), idd(ob), wd(ob);
+        hip_check(hipMemcpy(ld.p, logits, lb, hipMemcpyHostToDevice), "H2D logits");
+        hip_check(hipMemset(idd.p, 0xFF, ob), "poison ids");
+        hip_check(hipMemset(wd.p, 0xFF, ob), "poison weights");
+        launcher_check(launch_moe_route((const float*)ld.p, E, rows, E, k, norm_topk ? 1 : 0, (int32_t*)idd.p, (float*)wd.p, nullptr), "moe route");
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(ids_out, idd.p, ob, hipMemcpyDeviceToHost), "D2H ids");
+        hip_check(hipMemcpy(weights_out, wd.p, ob, hipMemcpyDeviceToHost), "D2H weights");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_moe_ffn(int32_t device, const float* x, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                                    const void* router, const void* gate, const void* up, const void* down, int32_t bf16,
+                                                    int32_t hidden, int32_t E, int32_t k, int32_t Im, int32_t norm_topk, const float* r, int64_t ldr,
+                                                    int32_t r_is_y, float* y, int64_t ldy, int32_t route, int32_t* ids_out, float* weights_out,
+                                                    int32_t* route_used, int32_t* tiles_used)
+{
+    if (!x || !router || !gate || !up || !down || !y || !ids_out || !weights_out || !route_used || !tiles_used) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 4096) throw InvalidConfig("rows must be 1 .. 4096");
+        if (route < 0 || route > 2) throw InvalidConfig("route must be 0 (the decoders' rule), 1 (steps) or 2 (grouped)");
+        if (!r_is_y && !r) throw InvalidConfig("a residual is needed: r, or r_is_y");
+        const int64_t ldr_ = r_is_y ? ldy : ldr;
+        MoeFfnArgs a;
+        a.ldx = ldx; a.rows = rows; a.eps = eps; a.bf16 = bf16 ? 1 : 0; a.E = E; a.k = k; a.Im = Im; a.H = hidden; a.norm_topk = norm_topk ? 1 : 0;
+        a.ldr = ldr_; a.ldy = ldy;
+        MoeFfnArgs chk = a;
+        chk.rows = 1;  // (the op runs the steps route in blocks of 8 rows and normalises a contiguous copy on the grouped route)
+        chk.ldx = std::max<int64_t>(ldx, 0);
+        if (const char* why = moe_ffn_refusal(chk, false)) throw InvalidConfig(std::string("the launchers refuse these arguments: ") + why);
+        if (std::max(std::max(ldx, ldy), ldr_) > (1 << 18)) throw InvalidConfig("leading dimensions above 2^18");
+        const int64_t stack = (int64_t)E * Im * hidden;
+        if (stack > ((int64_t)1 << 27)) throw InvalidConfig("an expert stack above 2^27 elements");
+        const bool grouped = route == 2 || (route == 0 && rows >= 24);
+        use_device(device);
+        const size_t wsz = bf16 ? 2 : 4, S = (size_t)rows * (size_t)k;
+        const size_t xb = (size_t)rows * (size_t)ldx * 4, yb = (size_t)rows * (size_t)ldy * 4, rb = r_is_y ? 0 : (size_t)rows * (size_t)ldr * 4;
+        DeviceBuf xd(xb), gd((size_t)hidden * 4), rtd((size_t)E * hidden * wsz), gtd((size_t)stack * wsz), upd((size_t)stack * wsz),
+            dnd((size_t)stack * wsz), rd(rb), yd(yb), lg((size_t)rows * E * 4), idd(S * 4), wtd(S * 4), mid(S * (size_t)Im * 4);
+        DeviceBuf xc(grouped && gamma ? (size_t)rows * hidden * 4 : 0), xn(grouped && gamma ? (size_t)rows * hidden * 4 : 0);
+        DeviceBuf ys(grouped ? S * (size_t)hidden * 4 : 0), plan(grouped ? moe_plan_ints((int)S, E) * 4 : 0);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        if (gamma) hip_check(hipMemcpy(gd.p, gamma, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(rtd.p, router, (size_t)E * hidden * wsz, hipMemcpyHostToDevice), "H2D router");
+        hip_check(hipMemcpy(gtd.p, gate, (size_t)stack * wsz, hipMemcpyHostToDevice), "H2D gate");
+        hip_check(hipMemcpy(upd.p, up, (size_t)stack * wsz, hipMemcpyHostToDevice), "H2D up");
+        hip_check(hipMemcpy(dnd.p, down, (size_t)stack * wsz, hipMemcpyHostToDevice), "H2D down");
+        if (rb) hip_check(hipMemcpy(rd.p, r, rb, hipMemcpyHostToDevice), "H2D r");
+        hip_check(hipMemcpy(yd.p, y, yb, hipMemcpyHostToDevice), "H2D y");
+        hip_check(hipMemset(mid.p, 0xFF, S * (size_t)Im * 4), "poison mid");  // (all-ones words are NaN: a slot the kernels skip would show)
+        hip_check(hipMemset(idd.p, 0xFF, S * 4), "poison ids");
+        hip_check(hipMemset(wtd.p, 0xFF, S * 4), "poison weights");
+        if (grouped) hip_check(hipMemset(ys.p, 0xFF, S * (size_t)hidden * 4), "poison y slots");
+        a.gamma = gamma ? (const float*)gd.p : nullptr;
+        a.router = rtd.p; a.gate = gtd.p; a.up = upd.p; a.down = dnd.p;
+        *route_used = grouped ? 2 : 1;
+        *tiles_used = 0;
+        if (grouped) {
+            a.X = (const float*)xd.p;
+            if (gamma && ldx != hidden) {  // the norm kernel reads contiguous rows
+                hip_check(hipMemcpy2D(xc.p, (size_t)hidden * 4, xd.p, (size_t)ldx * 4, (size_t)hidden * 4, (size_t)rows, hipMemcpyDeviceToDevice), "pack x");
+                a.X = (const float*)xc.p;
+                a.ldx = hidden;
+            }
+            a.xn = (float*)xn.p;
+            a.R = r_is_y ? (const float*)yd.p : (const float*)rd.p; a.Y = (float*)yd.p;
+            a.logits = (float*)lg.p; a.ids = (int32_t*)idd.p; a.weights = (float*)wtd.p; a.mid = (float*)mid.p; a.y = (float*)ys.p;
+            a.plan = (int32_t*)plan.p;
+            launcher_check(launch_moe_ffn_grouped(a, nullptr), "moe ffn (grouped)");
+        } else {
+            for (int r0 = 0; r0 < rows; r0 += 8) {
+                MoeFfnArgs b = a;
+                b.rows = std::min(8, rows - r0);
+                b.X = (const float*)xd.p + (size_t)r0 * ldx;
+                b.R = (r_is_y ? (const float*)yd.p : (const float*)rd.p) + (size_t)r0 * ldr_;
+                b.Y = (float*)yd.p + (size_t)r0 * ldy;
+                b.logits = (float*)lg.p + (size_t)r0 * E; b.ids = (int32_t*)idd.p + (size_t)r0 * k; b.weights = (float*)wtd.p + (size_t)r0 * k;
+                b.mid = (float*)mid.p + (size_t)r0 * k * Im;
+                launcher_check(launch_moe_ffn_steps(b, nullptr), "moe ffn (steps)");
+            }
+        }
+        hip_check(hipDeviceSynchronize(), "sync");
+        hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+        hip_check(hipMemcpy(ids_out, idd.p, S * 4, hipMemcpyDeviceToHost), "D2H ids");
+        hip_check(hipMemcpy(weights_out, wtd.p, S * 4, hipMemcpyDeviceToHost), "D2H weights");
+        if (grouped) hip_check(hipMemcpy(tiles_used, moe_plan_at((int32_t*)plan.p, (int)S, E).ntiles, 4, hipMemcpyDeviceToHost), "D2H tiles");
     });
 }
 

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <sstream>
 
 #include "fp8_weights.h"
@@ -16,6 +17,7 @@
 #include "decoder_embed_kernels.h"
 #include "draft_model_kernels.h"
 #include "llm_kernels.h"
+#include "moe_kernels.h"
 #include "constraint_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
@@ -47,8 +49,9 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         return (int)v->as_int();
     };
     c.model_type = j.get_string("model_type", "llama");
-    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "qwen3" && c.model_type != "mistral" && c.model_type != "gpt2")
-        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2, qwen3, mistral and gpt2 are)");
+    if (c.model_type != "llama" && c.model_type != "qwen2" && c.model_type != "qwen3" && c.model_type != "qwen3_moe" && c.model_type != "mistral" &&
+        c.model_type != "gpt2")
+        throw std::runtime_error("unsupported decoder model_type '" + c.model_type + "' (llama, qwen2, qwen3, qwen3_moe, mistral and gpt2 are)");
     auto ids = [&] {  // eos / bos as for every type
         if (const Json* e = j.find("eos_token_id")) {
             if (e->is_number()) c.eos_ids.push_back((uint32_t)e->as_int());
@@ -109,10 +112,98 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         c.rope_original_max = (int)rs->get_int("original_max_position_embeddings", 8192);
     }
     ids();
+    if (c.moe()) {  // (HF Qwen3MoeConfig: norm_topk_prob defaults to false, decoder_sparse_step to 1, mlp_only_layers to [])
+        c.num_experts = req("num_experts");
+        c.experts_per_tok = req("num_experts_per_tok");
+        c.moe_inter = req("moe_intermediate_size");
+        c.norm_topk = j.get_bool("norm_topk_prob", false);
+        c.sparse_step = (int)j.get_int("decoder_sparse_step", 1);
+        if (const Json* ml = j.find("mlp_only_layers"); ml && ml->is_array())
+            for (const Json& x : ml->arr)
+                if (x.is_number()) c.mlp_only_layers.push_back((int)x.as_int());
+        if (c.num_experts < 2 || c.num_experts > 256)
+            throw std::runtime_error("config.json: num_experts is " + std::to_string(c.num_experts) + "; 2 .. 256 are supported");
+        if (c.experts_per_tok < 1 || c.experts_per_tok > 8 || c.experts_per_tok > c.num_experts)
+            throw std::runtime_error("config.json: num_experts_per_tok is " + std::to_string(c.experts_per_tok) + " with num_experts " +
+                                     std::to_string(c.num_experts) + "; 1 .. 8 and at most num_experts are supported");
+        if (c.moe_inter < 32 || c.moe_inter % 32)
+            throw std::runtime_error("config.json: moe_intermediate_size is " + std::to_string(c.moe_inter) + "; a positive multiple of 32 is needed");
+        if (c.sparse_step < 1) throw std::runtime_error("config.json: decoder_sparse_step is " + std::to_string(c.sparse_step) + "; it must be at least 1");
+        if (j.find("quantization_config"))
+            throw std::runtime_error("config.json: a qwen3_moe checkpoint with a quantization_config: quantized mixture-of-experts checkpoints "
+                                     "(FP8, GGUF) are out of scope, bf16 and f32 are supported");
+    }
     // Qwen3 sets head_dim apart from hidden / heads (0.6B: 16 heads x 128 over a hidden size of 1024); the others may not
     if (c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.head_dim <= 0 || (!c.qwen3() && c.head_dim * c.heads != c.hidden))
         throw std::runtime_error("config.json: unsupported head geometry");
     return c;
+}
+
+bool LlmConfig::sparse_layer(int i) const
+{
+    if (num_experts <= 0 || sparse_step < 1) return false;
+    if (std::find(mlp_only_layers.begin(), mlp_only_layers.end(), i) != mlp_only_layers.end()) return false;
+    return (i + 1) % sparse_step == 0;
+}
+
+// Everything about a qwen3_moe directory that can be refused without a device: the config (from_json), then per layer the
+// tensors its kind needs, by name and shape.  A sparse layer: mlp.gate.weight [E, hidden] and, per expert, gate_proj / up_proj
+// [Im, hidden] and down_proj [hidden, Im], and no dense mlp.gate_proj beside them; a dense layer: the three Qwen3 matrices.
+void LlmModel::check_moe_checkpoint(const std::string& dir)
+{
+    std::string text;
+    {
+        std::ifstream f(dir + "/config.json", std::ios::binary);
+        if (!f) return;  // a .gguf file (its reader refuses the qwen3moe architecture by name) or nothing load() can read
+        text.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    }
+    try {
+        if (Json::parse(text).get_string("model_type", "llama") != "qwen3_moe") return;
+    } catch (const std::exception&) {
+        return;
+    }
+    const LlmConfig c = LlmConfig::from_json(text);
+    const int H = c.hidden, E = c.num_experts, Im = c.moe_inter;
+    if (H % 32 || H > 8192) throw std::runtime_error("qwen3_moe: hidden_size is " + std::to_string(H) + "; a multiple of 32 up to 8192 is needed");
+    if ((int64_t)c.experts_per_tok * Im > 16384)
+        throw std::runtime_error("qwen3_moe: num_experts_per_tok * moe_intermediate_size is " + std::to_string((int64_t)c.experts_per_tok * Im) +
+                                 "; at most 16384 is supported");
+    SafeTensors st;
+    if (!resolve_gguf(dir).empty())  // (no safetensors beside the config, a .gguf file instead)
+        throw std::runtime_error("GGUF qwen3_moe checkpoint: quantized mixture-of-experts checkpoints (FP8, GGUF) are out of scope; bf16 and f32 "
+                                 "safetensors are supported");
+    st.open_dir(dir);
+    auto shape_text = [](const std::vector<int64_t>& s) {
+        std::string t = "[";
+        for (size_t i = 0; i < s.size(); ++i) t += (i ? ", " : "") + std::to_string(s[i]);
+        return t + "]";
+    };
+    auto need = [&](const std::string& name, std::vector<int64_t> want) {
+        if (!st.contains(name)) throw std::runtime_error("missing tensor " + name);
+        const TensorView& t = st.get(name);
+        if (t.dtype != "F32" && t.dtype != "F16" && t.dtype != "BF16")
+            throw std::runtime_error("tensor " + name + " is " + t.dtype + ": a qwen3_moe checkpoint holds F32, F16 or BF16 tensors; quantized "
+                                     "mixture-of-experts checkpoints (FP8, GGUF) are out of scope");
+        if (t.shape != want) throw std::runtime_error("tensor " + name + " has shape " + shape_text(t.shape) + ", expected " + shape_text(want));
+    };
+    for (int i = 0; i < c.layers; ++i) {
+        const std::string p = "model.layers." + std::to_string(i) + ".mlp.";
+        if (!c.sparse_layer(i)) {
+            need(p + "gate_proj.weight", {c.inter, H});
+            need(p + "up_proj.weight", {c.inter, H});
+            need(p + "down_proj.weight", {H, c.inter});
+            continue;
+        }
+        if (st.contains(p + "gate_proj.weight"))
+            throw std::runtime_error("sparse layer " + std::to_string(i) + " also carries the dense tensor " + p + "gate_proj.weight");
+        need(p + "gate.weight", {E, H});
+        for (int e = 0; e < E; ++e) {
+            const std::string q = p + "experts." + std::to_string(e) + ".";
+            need(q + "gate_proj.weight", {Im, H});
+            need(q + "up_proj.weight", {Im, H});
+            need(q + "down_proj.weight", {H, Im});
+        }
+    }
 }
 
 float* LlmModel::dalloc(size_t floats)
@@ -161,6 +252,7 @@ LlmModel::~LlmModel()
 
 std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int weights, int max_context)
 {
+    check_moe_checkpoint(dir);  // (returns at once for every other kind of checkpoint)
     if (visible_device_count() <= device) throw GpuUnavailable("no usable HIP device " + std::to_string(device));
     std::unique_ptr<LlmModel> m(new LlmModel());
     m->device_ = device;
@@ -330,12 +422,48 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
             L.wqkv = m->upload_weight(w);
             get(p + ".self_attn.o_proj.weight", {H, QD});
             L.wo = m->upload_weight(buf);
-            get(p + ".mlp.gate_proj.weight", {c.inter, H});
-            L.gate = m->upload_weight(buf);
-            get(p + ".mlp.up_proj.weight", {c.inter, H});
-            L.up = m->upload_weight(buf);
-            get(p + ".mlp.down_proj.weight", {H, c.inter});
-            L.down = m->upload_weight(buf);
+            if (c.sparse_layer(i)) {
+                // the router and the three expert stacks in the weights' dtype, each expert uploaded into its place in a
+                // preallocated stack (no host copy of a whole stack: 128 experts of the 30B model are 1.2 GB per layer)
+                const int E = c.num_experts, Im = c.moe_inter;
+                L.moe = true;
+                get(p + ".mlp.gate.weight", {E, H});
+                L.router = m->upload_weight(buf);
+                const size_t per = (size_t)Im * H, wsz = m->bf16_ ? 2 : 4;
+                void* stacks[3];
+                for (void*& sp : stacks) sp = m->dalloc(((size_t)E * per * wsz + 3) / 4);
+                std::vector<uint16_t> half;
+                for (int e = 0; e < E; ++e) {
+                    const std::string q = p + ".mlp.experts." + std::to_string(e) + ".";
+                    const char* names[3] = {"gate_proj.weight", "up_proj.weight", "down_proj.weight"};
+                    for (int t = 0; t < 3; ++t) {
+                        if (!contains(q + names[t])) throw std::runtime_error("missing tensor " + q + names[t]);
+                        get(q + names[t], t == 2 ? std::vector<int64_t>{H, Im} : std::vector<int64_t>{Im, H});
+                        const void* src = buf.data();
+                        if (m->bf16_) {
+                            half.resize(per);
+                            for (size_t x = 0; x < per; ++x) half[x] = f32_to_bf16(buf[x]);  // exact when the file already held bf16
+                            src = half.data();
+                        }
+                        hip_check(hipMemcpy(static_cast<char*>(stacks[t]) + (size_t)e * per * wsz, src, per * wsz, hipMemcpyHostToDevice),
+                                  "hipMemcpy(expert)");
+                    }
+                }
+                m->weight_bytes_ += 3 * (size_t)E * per * wsz;
+                m->bytes_by_type_[m->bf16_ ? GGML_BF16 : GGML_F32] += 3 * (uint64_t)E * per * wsz;
+                L.gate_stack = stacks[0];
+                L.up_stack = stacks[1];
+                L.down_stack = stacks[2];
+                L.moe_ids = reinterpret_cast<int32_t*>(m->dalloc((size_t)kMoeRecordRows * c.experts_per_tok));
+                L.moe_weights = m->dalloc((size_t)kMoeRecordRows * c.experts_per_tok);
+            } else {
+                get(p + ".mlp.gate_proj.weight", {c.inter, H});
+                L.gate = m->upload_weight(buf);
+                get(p + ".mlp.up_proj.weight", {c.inter, H});
+                L.up = m->upload_weight(buf);
+                get(p + ".mlp.down_proj.weight", {H, c.inter});
+                L.down = m->upload_weight(buf);
+            }
         }
         get(p + ".input_layernorm.weight", {H});
         L.ln1 = m->upload_f32(buf);
@@ -429,6 +557,10 @@ void LlmModel::finish_load()
         xn_ = dalloc(8 * wide);
         xq_ = reinterpret_cast<int8_t*>(dalloc(2 * wide));
         xd_ = dalloc(8 * wide / 256 + 4);
+    }
+    if (c.moe()) {
+        moe_logits_ = dalloc(8 * (size_t)c.num_experts);
+        moe_mid_ = dalloc(8 * (size_t)c.experts_per_tok * c.moe_inter);
     }
     logits_ = dalloc((size_t)c.vocab);
     att_scratch_ = dalloc(decode_attention_scratch_floats(8, c.heads, d, splits_));
@@ -748,6 +880,10 @@ void LlmModel::layer_finish(StepRoute route, int n, const Layer& L, bool slabs)
         o.X = att_scratch_; o.att_splits = splits_; o.att_head_dim = c.head_dim;
     }
     project(route, o, "o proj");
+    if (L.moe) {
+        moe_steps(n, L);
+        return;
+    }
     LlmGemvArgs g;  // RMSNorm + SwiGLU (swiglu.rs:32-57); GPT-2: LayerNorm(ln_2) + c_fc + bias + GELU-tanh
     g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.beta = L.ln2_b; g.eps = c.eps; g.W = L.gate; g.bf16 = bf16_; g.bias = L.bfc;
     g.n_out = I; g.k = H; g.Y0 = mid_; g.ldy0 = I;
@@ -761,6 +897,70 @@ void LlmModel::layer_finish(StepRoute route, int n, const Layer& L, bool slabs)
     dn.X = mid_; dn.ldx = I; dn.rows = n; dn.W = L.down; dn.bf16 = bf16_; dn.bias = L.bdown; dn.R = h_; dn.ldr = H; dn.n_out = H; dn.k = I;
     dn.Y0 = h_; dn.ldy0 = H;
     project(route, dn, "down proj");
+}
+
+// The sparse FFN of a qwen3_moe layer behind the o-proj (moe_kernels.h), in place on the residual stream.  The routing record of
+// the layer is what the route kernel writes: the last pass's ids and weights stay readable (moe_routing()).
+namespace {
+
+MoeFfnArgs moe_args(const LlmConfig& c, bool bf16)
+{
+    MoeFfnArgs a;
+    a.E = c.num_experts; a.k = c.experts_per_tok; a.Im = c.moe_inter; a.H = c.hidden; a.norm_topk = c.norm_topk ? 1 : 0; a.eps = c.eps;
+    a.bf16 = bf16 ? 1 : 0;
+    return a;
+}
+
+}  // namespace
+
+void LlmModel::moe_steps(int n, const Layer& L)
+{
+    const int H = cfg_.hidden;
+    MoeFfnArgs a = moe_args(cfg_, bf16_);
+    a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln2;
+    a.router = L.router; a.gate = L.gate_stack; a.up = L.up_stack; a.down = L.down_stack;
+    a.R = h_; a.ldr = H; a.Y = h_; a.ldy = H;
+    a.logits = moe_logits_; a.ids = L.moe_ids; a.weights = L.moe_weights; a.mid = moe_mid_;
+    hip_check(launch_moe_ffn_steps(a, stream_), "moe ffn (steps)");
+    L.moe_rec_rows = n;
+}
+
+void LlmModel::moe_rows(int m, const Layer& L)
+{
+    const int H = cfg_.hidden, k = cfg_.experts_per_tok;
+    if (m > kMoeRecordRows) throw std::runtime_error("moe_rows: more rows than the routing record holds");
+    for (int r0 = 0; r0 < m; r0 += kMoeBlockRows) {
+        const int rows = std::min(kMoeBlockRows, m - r0);
+        MoeFfnArgs a = moe_args(cfg_, bf16_);
+        float* h = ph_ + (size_t)r0 * H;
+        a.X = h; a.ldx = H; a.rows = rows; a.gamma = L.ln2; a.xn = pn_ + (size_t)r0 * H;
+        a.router = L.router; a.gate = L.gate_stack; a.up = L.up_stack; a.down = L.down_stack;
+        a.R = h; a.ldr = H; a.Y = h; a.ldy = H;
+        a.logits = pmoe_logits_; a.ids = L.moe_ids + (size_t)r0 * k; a.weights = L.moe_weights + (size_t)r0 * k;
+        a.mid = pmoe_mid_; a.y = pmoe_y_; a.plan = pmoe_plan_;
+        hip_check(launch_moe_ffn_grouped(a, stream_), "moe ffn (rows)");
+    }
+    L.moe_rec_rows = m;
+}
+
+int LlmModel::moe_record_rows(int layer) const
+{
+    if (!cfg_.moe()) throw InvalidConfig("moe_routing: the model is dense (model_type '" + cfg_.model_type + "')");
+    if (layer < 0 || layer >= cfg_.layers) throw InvalidConfig("moe_routing: layer must be 0 .. " + std::to_string(cfg_.layers - 1));
+    if (!layers_[(size_t)layer].moe) throw InvalidConfig("moe_routing: layer " + std::to_string(layer) + " is a dense layer");
+    return layers_[(size_t)layer].moe_rec_rows;
+}
+
+void LlmModel::moe_routing(int layer, int32_t* ids_out, float* weights_out)
+{
+    const int rows = moe_record_rows(layer);
+    if (rows <= 0) return;
+    const Layer& L = layers_[(size_t)layer];
+    const size_t n = (size_t)rows * cfg_.experts_per_tok;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    hip_check(hipMemcpy(ids_out, L.moe_ids, n * 4, hipMemcpyDeviceToHost), "D2H moe ids");
+    hip_check(hipMemcpy(weights_out, L.moe_weights, n * 4, hipMemcpyDeviceToHost), "D2H moe weights");
 }
 
 // One pass of n <= 8 rows for every family (llama/cpu_decoder.rs:142-219, gpt2/cpu_decoder.rs:371-394): the embedding (GPT-2:
@@ -810,6 +1010,13 @@ void LlmModel::ensure_prompt_workspace()
     psplit_ = dalloc(prefill_gemm_scratch_floats(prefill_cap_, std::max(I, std::max(H, QD))));
     if (bf16_ || quant_) pw32_ = dalloc(std::max((size_t)(QD + 2 * kv) * H, (size_t)I * H));
     if (quant_) pact_ = dalloc(P * (size_t)std::max(H, I));
+    if (cfg_.moe()) {  // the slot-major scratch of one block of rows: kMoeBlockRows * k * (hidden + Im) floats
+        const size_t B = (size_t)kMoeBlockRows, k = (size_t)cfg_.experts_per_tok;
+        pmoe_logits_ = dalloc(B * cfg_.num_experts);
+        pmoe_mid_ = dalloc(B * k * cfg_.moe_inter);
+        pmoe_y_ = dalloc(B * k * H);
+        pmoe_plan_ = reinterpret_cast<int32_t*>(dalloc(moe_plan_ints((int)(B * k), cfg_.num_experts)));
+    }
 }
 
 // Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T).  Blocks of >= kTileRows rows run the
@@ -912,6 +1119,10 @@ void LlmModel::rows_finish(int m, const Layer& L)
         hip_check(launch_layernorm(ph_, L.ln2, L.ln2_b, c.eps, m, H, pn_, s), "ln_2");
         prompt_proj(m, pn_, H, L.gate, L.bfc, nullptr, pg_, I, I, H, nullptr, "c_fc", nullptr, true);
         prompt_proj(m, pg_, I, L.down, L.bdown, ph_, ph_, H, H, I, nullptr, "mlp c_proj");
+        return;
+    }
+    if (L.moe) {
+        moe_rows(m, L);
         return;
     }
     hip_check(launch_rmsnorm(ph_, L.ln2, c.eps, m, H, pn_, s), "rmsnorm 2");

@@ -41,7 +41,14 @@ struct LlmConfig {
     bool has_bos = false;
     uint32_t bos_id = 0;
     bool gpt2() const { return model_type == "gpt2"; }  // LayerNorm + biases, GELU MLP, learned positions, head tied to wte
-    bool qwen3() const { return model_type == "qwen3"; }  // per-head RMSNorm of Q and K before RoPE; head_dim set apart from hidden / heads
+    bool moe() const { return model_type == "qwen3_moe"; }  // Qwen3 in everything but the FFN: a router and E experts in the sparse layers
+    bool qwen3() const { return model_type == "qwen3" || moe(); }  // per-head RMSNorm of Q and K before RoPE; head_dim set apart from hidden / heads
+    // qwen3_moe: E experts of width moe_inter, k of them per token; layer i is sparse iff it is not in mlp_only_layers and
+    // (i + 1) % sparse_step == 0, else a dense Qwen3 layer of `inter`
+    int num_experts = 0, experts_per_tok = 0, moe_inter = 0, sparse_step = 1;
+    bool norm_topk = false;
+    std::vector<int> mlp_only_layers;
+    bool sparse_layer(int i) const;
     int q_dim() const { return heads * head_dim; }  // the width of Q and of the attention's context rows (== hidden except for Qwen3)
     static LlmConfig from_json(const std::string& text);
 };
@@ -116,6 +123,13 @@ public:
     // Prompt projections that ran the encoder's 128 x 128-tile GEMM since load (the other route is the 64 x 64 prompt kernel):
     // lets a test assert which route a geometry took.
     uint64_t tile_gemm_calls() const { return tile_gemm_calls_; }
+    // A qwen3_moe directory checked on the host alone (config, every expert tensor's presence and shape, the refusals), before
+    // load() touches a device; any other directory returns at once.  Throws what load() would.
+    static void check_moe_checkpoint(const std::string& dir);
+    // What sparse layer `layer` chose in its last pass: rows of k expert ids and weights.  Returns the rows recorded (the
+    // caller's arrays hold moe_record_rows(layer) * k values); InvalidConfig for a dense layer or a dense model.
+    int moe_record_rows(int layer) const;
+    void moe_routing(int layer, int32_t* ids_out, float* weights_out);
     // Sampled decoding / logits processors: the O(vocab) work runs on the device and the host decides on a candidate list
     // (default); off = the logits travel to the host every token (the checker in tests).  The counters say how many tokens
     // were decided from candidates and how many needed the logits after all.
@@ -452,7 +466,19 @@ private:
         float *k_cache, *v_cache;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
         Fp8Mat fq, fk, fv, fo, fgate, fup, fdown;  // FP8 checkpoints (quant_ && fp8_): the codes and scales of the seven matrices
+        // a sparse layer (qwen3_moe): the router [E, hidden] and the expert stacks [E, Im, hidden] x 2, [E, hidden, Im] in the weights'
+        // dtype (gate / up / down are then null), and the record of the last pass: ids / weights [moe_rec_rows, k]
+        bool moe = false;
+        void *router = nullptr, *gate_stack = nullptr, *up_stack = nullptr, *down_stack = nullptr;
+        int32_t* moe_ids = nullptr;
+        float* moe_weights = nullptr;
+        mutable int moe_rec_rows = 0;
     };
+    // The sparse FFN behind the o-proj, h += MoE(RMSNorm(h)) (moe_kernels.h).  moe_steps: n <= 8 rows of h_, 4 launches;
+    // moe_rows: m rows of ph_ in blocks of kMoeBlockRows rows (what bounds the slot-major scratch), 8 launches per block.
+    static constexpr int kMoeBlockRows = 1024, kMoeRecordRows = 2048;
+    void moe_steps(int n, const Layer& L);
+    void moe_rows(int m, const Layer& L);
     // The layer body of the rows route, around the caller's own RoPE / head norm and attention (prefill_rows: the KV cache,
     // packed_layers: ek_ / ev_ and the block tables).  rows_qkv: norm 1 of ph_ into pn_, Q into pq_, K and V into the rows given.
     // rows_finish: o-proj of pctx_ + residual, norm 2, the SwiGLU or GPT-2 MLP, all into ph_.
@@ -517,6 +543,9 @@ private:
     unsigned long long* best_ = nullptr;
     int cache_len_ = 0, cache_cap_ = 0, last_rows_ = 0, hist_cap_ = 0, splits_ = 16;
     // prefill workspace (allocated on first use)
+    float *moe_logits_ = nullptr, *moe_mid_ = nullptr;  // steps route: [8, E], [8 * k, Im]
+    float *pmoe_logits_ = nullptr, *pmoe_mid_ = nullptr, *pmoe_y_ = nullptr;  // rows route: [block, E], [block * k, Im], [block * k, hidden]
+    int32_t* pmoe_plan_ = nullptr;
     float *ph_ = nullptr, *pn_ = nullptr, *pq_ = nullptr, *pctx_ = nullptr, *pg_ = nullptr, *pu_ = nullptr;
     uint32_t* pids_ = nullptr;
     float* pw32_ = nullptr;    // f32 copy of the weight matrix a long prompt's GEMM is working on (bf16 checkpoints)

@@ -63,6 +63,12 @@ const RegistryEntry kDecoderRerankers[] = {
     {"qwen3-reranker-8b", "Qwen/Qwen3-Reranker-8B", ModelTask::ReRanking, ModelArch::Decoder},
 };
 
+// Mixture-of-experts decoders (model_type qwen3_moe), kept apart for the same reason.
+const RegistryEntry kMoeDecoders[] = {
+    {"qwen3-30b-a3b", "Qwen/Qwen3-30B-A3B", ModelTask::Other, ModelArch::Other},
+    {"qwen3-30b-a3b-instruct-2507", "Qwen/Qwen3-30B-A3B-Instruct-2507", ModelTask::Other, ModelArch::Other},
+};
+
 struct Alias {
     const char* alias;
     const char* cli_name;
@@ -97,6 +103,8 @@ const Alias kAliases[] = {
     {"qwen/qwen3-1.7b", "qwen3-1.7b"},
     {"qwen/qwen3-4b", "qwen3-4b"},
     {"qwen/qwen3-8b", "qwen3-8b"},
+    {"qwen/qwen3-30b-a3b", "qwen3-30b-a3b"},
+    {"qwen/qwen3-30b-a3b-instruct-2507", "qwen3-30b-a3b-instruct-2507"},
     {"qwen/qwen3-embedding-0.6b", "qwen3-embedding-0.6b"},
     {"qwen/qwen3-embedding-4b", "qwen3-embedding-4b"},
     {"qwen/qwen3-embedding-8b", "qwen3-embedding-8b"},
@@ -122,6 +130,8 @@ const RegistryEntry* by_cli(const std::string& cli)
     for (const RegistryEntry& e : kDecoderEmbedders)
         if (cli == e.cli_name) return &e;
     for (const RegistryEntry& e : kDecoderRerankers)
+        if (cli == e.cli_name) return &e;
+    for (const RegistryEntry& e : kMoeDecoders)
         if (cli == e.cli_name) return &e;
     return nullptr;
 }

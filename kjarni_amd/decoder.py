@@ -189,6 +189,17 @@ class HipDecoder:
         check_error(lib().kjarni_hip_decoder_kv_rows(self._h, layer, first, rows, f(k), f(v)))
         return k, v
 
+    def moe_routing(self, layer: int):
+        """What sparse layer `layer` of a qwen3_moe decoder chose in its last pass: (ids int32 [rows, k], weights f32 [rows, k]),
+        slot 0 the largest weight.  A dense layer or a dense model raises (InvalidConfig)."""
+        n = C.c_int32(0)
+        check_error(lib().kjarni_hip_decoder_moe_routing(self._h, layer, 0, C.byref(n), None, None))
+        k = int(json.loads(self.config_json()).get("num_experts_per_tok", 1))
+        ids, w = np.empty((n.value, k), np.int32), np.empty((n.value, k), np.float32)
+        check_error(lib().kjarni_hip_decoder_moe_routing(self._h, layer, n.value, C.byref(n), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         w.ctypes.data_as(C.POINTER(C.c_float))))
+        return ids[:n.value], w[:n.value]
+
     def forward(self, ids: Sequence[int], fetch: bool = True):
         a = np.ascontiguousarray(ids, np.uint32)
         hidden = np.empty(((a.size - 1) % 8 + 1, self.hidden), np.float32) if fetch else None   # rows of the last 8-row block

@@ -319,6 +319,51 @@ def prefill_gemm(a, w, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=
     return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
 
 
+# ---- mixture-of-experts: the router pick and the sparse FFN, alone ----
+def moe_route(logits, k: int, norm_topk: bool = False, device: int = 0):
+    """launch_moe_route on host arrays (kjarni_hip_op_moe_route): logits [rows, E] -> (ids int32 [rows, k], weights f32 [rows, k]),
+    slot 0 the largest, the lower expert first on equal logits."""
+    la = np.ascontiguousarray(logits, np.float32)
+    if la.ndim != 2:
+        raise ValueError("logits: [rows, E]")
+    rows, e = la.shape
+    ids = np.full((rows, max(int(k), 0)), -1, np.int32)
+    w = np.full((rows, max(int(k), 0)), np.nan, np.float32)
+    check_error(lib().kjarni_hip_op_moe_route(device, _f(la), rows, e, int(k), int(bool(norm_topk)), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              _f(w)))
+    return ids, w
+
+
+def moe_ffn(x, router, gate, up, down, k: int, y, r=None, r_is_y: bool = False, gamma=None, eps: float = 1e-6, norm_topk: bool = False,
+            bf16: bool = False, route: int = 0, hidden: Optional[int] = None, device: int = 0):
+    """The sparse FFN on host arrays (kjarni_hip_op_moe_ffn): x [rows, ldx]; router [E, hidden], gate / up [E, Im, hidden], down
+    [E, hidden, Im] f32 or bf16 bit patterns (uint16, bf16 = True); y [rows, ldy] given with whatever its padding holds; r [rows, ldr]
+    or r_is_y.  route: 0 the decoders' rule, 1 steps, 2 grouped.  Returns (y, ids, weights, route_used, tiles_used) -- copies."""
+    wt = np.uint16 if bf16 else np.float32
+    xa = np.ascontiguousarray(x, np.float32)
+    ra_, ga, ua, da = (np.ascontiguousarray(t, wt) for t in (router, gate, up, down))
+    ya = np.array(y, np.float32, order="C")
+    if xa.ndim != 2 or ya.ndim != 2 or ya.shape[0] != xa.shape[0] or ra_.ndim != 2 or ga.ndim != 3 or ua.shape != ga.shape or da.ndim != 3:
+        raise ValueError("x: [rows, ldx]; y: [rows, ldy]; router: [E, hidden]; gate, up: [E, Im, hidden]; down: [E, hidden, Im]")
+    e, im, h = ga.shape
+    if ra_.shape != (e, h) or da.shape != (e, h, im) or (hidden is not None and int(hidden) != h):
+        raise ValueError("router: [E, hidden]; down: [E, hidden, Im]")
+    rows = xa.shape[0]
+    gm = _proj_vector(gamma, h, "gamma")
+    rr = None if r is None else np.ascontiguousarray(r, np.float32)
+    if rr is not None and (rr.ndim != 2 or rr.shape[0] != rows):
+        raise ValueError("r: [rows, ldr]")
+    kk = max(int(k), 0)
+    ids, w = np.full((rows, kk), -1, np.int32), np.full((rows, kk), np.nan, np.float32)
+    used, tiles = C.c_int32(-1), C.c_int32(-1)
+    v = lambda t: t.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check_error(lib().kjarni_hip_op_moe_ffn(device, _f(xa), xa.shape[1], rows, _f(gm), float(eps), v(ra_), v(ga), v(ua), v(da), int(bool(bf16)), h, e,
+                                            int(k), im, int(bool(norm_topk)), _f(rr), 0 if rr is None else rr.shape[1], int(bool(r_is_y)), _f(ya),
+                                            ya.shape[1], int(route), ids.ctypes.data_as(C.POINTER(C.c_int32)), _f(w), C.byref(used),
+                                            C.byref(tiles)))
+    return ya, ids, w, used.value, tiles.value
+
+
 def prefill_attention(q, k, v, ldk: int, ldv: int, base: int, heads: int, head_dim: int, kv_group: int = 1, ctx=None, device: int = 0):
     """launch_prefill_attention on host arrays (kjarni_hip_op_prefill_attention): q [rows, ldq]; k and v flat float buffers, key row
     t at t * ldk; row s sees keys <= base + s.  Returns (ctx [rows, ldc] -- given, or NaN [rows, heads * head_dim] -- with the context

@@ -39,6 +39,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            (rows - 1) drafter steps (what the chain is made of), the break-even accepted tokens per round, and end-to-end
            tokens/s with a copy of the target as drafter (every draft accepted) and with an unrelated checkpoint; a 4-layer
            drafter of the same width for the per-round cost only.  Ends of a range, not workloads.
+  llm_moe  (only on request) a random-weight qwen3_moe model at the Qwen3-30B-A3B widths (128 experts of 768, 8 per token, bf16, cut
+           to 4 layers: a 5 GB fixture) against a dense Qwen3 model of the same widths with intermediate_size 6144 (the same active
+           FFN bytes and FLOPs) in one process, alternated twice: greedy ms / token and the 128-token prompt time of both, their
+           ratios, and the sparse step's streamed bytes against the HBM peak.
   llm_constraint  (only on request) constrained decoding (HipDecoder.generate_constrained) against the plain loop of the same build,
            alternated twice in one process, greedy and sampled: Llama-3.2-1B shape (bf16) and gpt2-small (bf16), a pattern that
            masks nothing (the ids are the plain loop's, asserted), so the ratio is the cost of the two launches per step; and the
@@ -1487,6 +1491,104 @@ def main():
         with open(out_path, "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+    if "llm_moe" in which:
+        # Method: one process on one box.  A random-weight qwen3_moe model at the Qwen3-30B-A3B widths (hidden 2048, 32 / 4 heads of
+        # 128, 128 experts of 768, 8 per token, bf16) cut to 4 layers so that the fixture stays near 5 GB, and a dense Qwen3 model of
+        # the same widths with intermediate_size = 8 x 768 = 6144: the same active bytes and FLOPs in the FFN, on the existing dense
+        # path -- the yardstick.  Both warmed first, then alternated twice: greedy ms / token (a 128-token generation minus the same
+        # call cut after its first token) and the 128-token prompt time (forward(), which returns after a synchronise); medians.
+        # The ratio is what routing and gathering cost; the sparse step's streamed bytes against the HBM peak says how far it is
+        # from streaming its weights.  (Random routers spread tokens evenly over the experts; a trained router is more skewed.)
+        import torch as _t
+        from safetensors.torch import save_file as _save
+        rng = np.random.default_rng(0)
+        H, NH, NKV, D, E_, K_, IM, LAYERS, VOC = 2048, 32, 4, 128, 128, 8, 768, 4, 32000
+        n_new = int(os.environ.get("KJARNI_MOE_TOKENS", "128"))
+
+        def rand_bf16(*shape):   # bf16 bit patterns, magnitudes 2^-7 .. 2^-4, made as bits: no 10 GB of f32 on the host
+            n = int(np.prod(shape))
+            bits = (rng.integers(0, 2, n, dtype=np.uint16) << 15) | ((rng.integers(120, 123, n, dtype=np.uint16)) << 7) | rng.integers(0, 128, n, dtype=np.uint16)
+            return _t.from_numpy(bits.view(np.int16).reshape(shape)).view(_t.bfloat16)
+
+        def write(path, moe):
+            os.makedirs(path, exist_ok=True)
+            cfg = dict(model_type="qwen3_moe" if moe else "qwen3", hidden_size=H, num_hidden_layers=LAYERS, num_attention_heads=NH,
+                       num_key_value_heads=NKV, head_dim=D, intermediate_size=K_ * IM, vocab_size=VOC, max_position_embeddings=4096,
+                       rms_norm_eps=1e-6, rope_theta=1000000.0, tie_word_embeddings=True, eos_token_id=[])
+            if moe:
+                cfg.update(num_experts=E_, num_experts_per_tok=K_, moe_intermediate_size=IM, norm_topk_prob=True, decoder_sparse_step=1,
+                           mlp_only_layers=[])
+            json.dump(cfg, open(os.path.join(path, "config.json"), "w"))
+            ones = lambda n: _t.ones(n, dtype=_t.float32)  # noqa: E731
+            t = {"model.embed_tokens.weight": rand_bf16(VOC, H), "model.norm.weight": ones(H)}
+            for i in range(LAYERS):
+                q = f"model.layers.{i}."
+                t[q + "self_attn.q_proj.weight"], t[q + "self_attn.o_proj.weight"] = rand_bf16(NH * D, H), rand_bf16(H, NH * D)
+                t[q + "self_attn.k_proj.weight"], t[q + "self_attn.v_proj.weight"] = rand_bf16(NKV * D, H), rand_bf16(NKV * D, H)
+                t[q + "self_attn.q_norm.weight"], t[q + "self_attn.k_norm.weight"] = ones(D), ones(D)
+                t[q + "input_layernorm.weight"], t[q + "post_attention_layernorm.weight"] = ones(H), ones(H)
+                if moe:
+                    t[q + "mlp.gate.weight"] = rand_bf16(E_, H)
+                    for e in range(E_):
+                        for nm, shape in (("gate_proj", (IM, H)), ("up_proj", (IM, H)), ("down_proj", (H, IM))):
+                            t[f"{q}mlp.experts.{e}.{nm}.weight"] = rand_bf16(*shape)
+                else:
+                    for nm, shape in (("gate_proj", (K_ * IM, H)), ("up_proj", (K_ * IM, H)), ("down_proj", (H, K_ * IM))):
+                        t[f"{q}mlp.{nm}.weight"] = rand_bf16(*shape)
+            _save(t, os.path.join(path, "model.safetensors"))
+            return path
+
+        t0 = time.perf_counter()
+        decs = {"moe": kjarni_amd.HipDecoder(write(os.path.join(tmp, "moe-30b-a3b-4l"), True), max_context=1024),
+                "dense": kjarni_amd.HipDecoder(write(os.path.join(tmp, "dense-6144-4l"), False), max_context=1024)}
+        setup_s = time.perf_counter() - t0
+        prompt = rng.integers(1000, VOC, 128).tolist()
+        step_ms, prompt_ms = {"moe": [], "dense": []}, {"moe": [], "dense": []}
+
+        def once(dec):
+            dec.reset()
+            t0 = time.perf_counter()
+            dec.generate(prompt, 1)
+            t1 = time.perf_counter()
+            dec.reset()
+            out = dec.generate(prompt, n_new)
+            t2 = time.perf_counter()
+            dec.reset()
+            t3 = time.perf_counter()
+            dec.forward(prompt, fetch=False)
+            t4 = time.perf_counter()
+            return ((t2 - t1) - (t1 - t0)) * 1e3 / max(len(out) - 1, 1), (t4 - t3) * 1e3
+
+        for name in ("moe", "dense"):
+            once(decs[name])       # warm: captures the step, allocates the prompt workspace
+        for _ in range(2):
+            for name in ("moe", "dense"):
+                for _ in range(3):
+                    a, b = once(decs[name])
+                    step_ms[name].append(a)
+                    prompt_ms[name].append(b)
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+        attn = ((NH + 2 * NKV) * D * H + H * NH * D) * 2
+        moe_tok = LAYERS * (attn + E_ * H * 2 + K_ * 3 * IM * H * 2) + VOC * H * 2          # bytes one sparse step streams
+        dense_tok = LAYERS * (attn + 3 * K_ * IM * H * 2) + VOC * H * 2
+        emit({"metric": "greedy ms/token and 128-token prompt ms, qwen3_moe at the Qwen3-30B-A3B widths (4 layers, bf16) against a dense "
+                        "Qwen3 of the same active FFN bytes", "section": "llm_moe",
+              "config": {"hidden": H, "heads": NH, "kv_heads": NKV, "head_dim": D, "experts": E_, "experts_per_tok": K_, "moe_intermediate": IM,
+                         "layers": LAYERS, "vocab": VOC, "dense_intermediate": K_ * IM, "tokens": n_new, "prompt": 128},
+              "moe_ms_per_token": round(med(step_ms["moe"]), 4), "dense_ms_per_token": round(med(step_ms["dense"]), 4),
+              "moe_over_dense_step": round(med(step_ms["moe"]) / med(step_ms["dense"]), 3),
+              "moe_prompt_ms": round(med(prompt_ms["moe"]), 3), "dense_prompt_ms": round(med(prompt_ms["dense"]), 3),
+              "moe_over_dense_prompt": round(med(prompt_ms["moe"]) / med(prompt_ms["dense"]), 3),
+              "moe_streamed_bytes_per_token": moe_tok, "dense_streamed_bytes_per_token": dense_tok,
+              "moe_frac_hbm_peak": round(moe_tok / (med(step_ms["moe"]) * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+              "dense_frac_hbm_peak": round(dense_tok / (med(step_ms["dense"]) * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+              "all_step_ms": {k: [round(x, 4) for x in v] for k, v in step_ms.items()},
+              "all_prompt_ms": {k: [round(x, 3) for x in v] for k, v in prompt_ms.items()},
+              "weight_bytes": {k: d.weight_bytes for k, d in decs.items()}, "fixture_and_load_s": round(setup_s, 1),
+              "note": "4 layers: the per-token streams (a few hundred MB) fit the 256 MiB Infinity Cache only in part; the fractions "
+                      "may overstate what HBM delivered"})
+        del decs
 
     if "llm_constraint" in which:
         # Method (as llm_lookup): one process on one box, everything warmed first; the plain loop of the same build -- the yardstick
