@@ -971,6 +971,49 @@ KjarniErrorCode kjarni_hip_op_gemv_row_att(int32_t device, const float* slabs, i
  * what the launcher refuses: rows != 1, k 2048 with more than 8 splits, k 4096 with more than 4, any other k, r NULL. */
 KjarniErrorCode kjarni_hip_op_llm_gemv_att(int32_t device, const float* slabs, int32_t splits, int32_t head_dim, const void* w, int32_t bf16,
                                            const float* bias, const float* r, int32_t n_out, int32_t k, int32_t rows, float* y);
+/* ---- the dense (f32 / bf16) decode-step projections, alone --------------------------------------------------------------------------
+ * kjarni_hip_op_llm_gemv: ONE call of launch_llm_gemv (lanes = 0) or launch_llm_gemv_lanes (lanes = 1) on host arrays, every field
+ * of the launchers' argument block exposed except the attention slabs (kjarni_hip_op_llm_gemv_att).  Y[r, n] = epi(norm(x[r, :]) .
+ * w[n, :] + bias[n]) for `rows` rows.  x [x_rows, ldx] (x_rows >= rows, k columns used).  Norm: gamma [k] (NULL: none) is RMSNorm,
+ * x / sqrt(mean(x^2) + eps) * gamma; with layernorm, (x - mean) / sqrt(var + eps) * gamma + beta [k].  w, w2 [n_out, k] f32, or bf16
+ * bit patterns with bf16 = 1; bias [n_out] or NULL.  Epilogue: swiglu, silu(x . w + bias) * (x . w2); gelu_tanh (after LayerNorm);
+ * residual r [rows, ldr], or with r_is_y0 the output y[0] itself (its stride is then ldy0).  Outputs: seg_q == 0, y[0] [out_rows[0],
+ * ldy0] gets row r at row r; seg_q > 0 (seg_q + 2 * seg_kv == n_out), columns [0, seg_q) go to y[0] row r, the next seg_kv to y[1]
+ * and the last seg_kv to y[2], both [out_rows[i], ldy12], at row row_off + r.  offset_on_device: row_off is read from device memory
+ * and the launcher's by-value copy is another row inside the outputs.  norm_out [k] (may be NULL; one row, gamma, k 2048 / 4096 /
+ * 8192): also receives the normalised row.  Every y[i] and norm_out is uploaded as given, written by the kernel and returned
+ * whole, so whatever the caller put into rows, padding columns and outputs the call does not own comes back as it was; each has a
+ * guard band behind it on the device.  route_out [16] (int32) receives the launcher's own route (llm_gemv_route /
+ * llm_gemv_lanes_route, the functions the launchers call): lanes = 0: kernel (0 stream, 1 split-K, 2 one-row LDS, 3 generic), ch,
+ * wide, threads, loop, rows_per_batch, workgroups; lanes = 1: taken, ch, ns, wide, cpw, workgroups, streamed (what the launcher
+ * reported), and when it fell back, the seven values of the lanes = 0 form from slot 8.  Every operand is uploaded 16-byte aligned:
+ * a misaligned w2, which takes K = 2048 off the streaming kernel, cannot be asked for.  INVALID_CONFIG, before any GPU work and with
+ * every output untouched: rows outside 0 .. 8 or above x_rows, k % 8, ldx % 4, ldx < k, ldy < the output's columns, ldr < n_out,
+ * n_out < 1 or above 2^17, k above 2^16, n_out * k above 2^26, seg_q + 2 * seg_kv != n_out, rows that do not fit an output at
+ * row_off, swiglu without w2, and the (epilogue, norm) pairs the launcher rejects: LayerNorm without gamma / beta or with a
+ * residual, SwiGLU or norm_out; GELU-tanh without LayerNorm or with segments; SwiGLU without gamma or with a residual; a residual
+ * with gamma; norm_out outside its route; an in-place residual with segments. */
+KjarniErrorCode kjarni_hip_op_llm_gemv(int32_t device, int32_t lanes, const float* x, int32_t x_rows, int64_t ldx, int32_t rows,
+                                       const float* gamma, const float* beta, float eps, int32_t layernorm, int32_t gelu_tanh, const void* w,
+                                       const void* w2, int32_t bf16, int32_t swiglu, const float* bias, const float* r, int64_t ldr,
+                                       int32_t r_is_y0, int32_t n_out, int32_t k, int32_t seg_q, int32_t seg_kv, float* const* y,
+                                       const int32_t* out_rows, int64_t ldy0, int64_t ldy12, int32_t row_off, int32_t offset_on_device,
+                                       float* norm_out, int32_t* route_out);
+/* kjarni_hip_op_llm_qkv_rope: ONE call of launch_llm_qkv_rope, the one-token RMSNorm + Q | K | V projection + RoPE.  The input row is
+ * x [k], or (x NULL) row *embed_ids of table [vocab, k] (the weights' dtype; an id >= vocab gives zeros), which x_raw_out [k] (may
+ * be NULL) then also receives.  gamma [k]; w [(n_heads + 2 n_kv_heads) * head_dim, k] f32 or bf16 bit patterns; bias or NULL.
+ * cos_t / sin_t [positions, head_dim / 2]; Q and K are rotated on pairs (i, i + head_dim / 2) by row pos.  q [n_heads * head_dim]
+ * gets Q; row pos of k_cache / v_cache [cache_rows, n_kv_heads * head_dim] gets K / V.  offset_on_device: pos is read from device
+ * memory and the by-value copy is another row.  q, both caches and x_raw_out are uploaded as given and returned whole, with guard
+ * bands on the device.  route [3]: kernel (0 a workgroup per pair, 1 streaming, 2 streaming with the gather), ch, workgroups, by
+ * llm_qkv_rope_route, which the launcher calls.  INVALID_CONFIG, before any GPU work and with every output untouched: gamma NULL,
+ * k % 8 or above 8192, head_dim odd, pos outside the tables or the caches, both or neither of x and embed_ids, a gather without a
+ * table or at k other than 2048 / 4096 / 8192, a table or x_raw_out without the gather, sizes above the caps. */
+KjarniErrorCode kjarni_hip_op_llm_qkv_rope(int32_t device, const float* x, const uint32_t* embed_ids, const void* table, int32_t vocab,
+                                           const float* gamma, float eps, const void* w, int32_t bf16, const float* bias, int32_t k,
+                                           int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* cos_t, const float* sin_t,
+                                           int32_t positions, int32_t pos, int32_t offset_on_device, float* q, float* k_cache, float* v_cache,
+                                           int32_t cache_rows, float* x_raw_out, int32_t* route);
 /* ---- the prompt-route GEMM and the two prefill attention kernels, alone -------------------------------------------------------------
  * kjarni_hip_op_prefill_gemm: y[m, n] = a[m, k] . w[n, k]^T (+ bias) (+ r) through launch_prefill_gemm (64 x 64 tiles, K slices
  * added by the reduce kernel), as the decoders' prompt projections call it.  a [a_rows, lda] (a_rows >= m, lda >= k); w [n, k] f32,

@@ -553,6 +553,12 @@ SIGNATURES = {
                                              _f32p]),
     "kjarni_hip_op_llm_gemv_att": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_void_p, c_int32, _f32p, _f32p, c_int32, c_int32, c_int32,
                                              _f32p]),
+    "kjarni_hip_op_llm_gemv": (c_int32, [c_int32, c_int32, _f32p, c_int32, c_int64, c_int32, _f32p, _f32p, c_float, c_int32, c_int32, c_void_p,
+                                         c_void_p, c_int32, c_int32, _f32p, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         POINTER(c_void_p), POINTER(c_int32), c_int64, c_int64, c_int32, c_int32, _f32p, POINTER(c_int32)]),
+    "kjarni_hip_op_llm_qkv_rope": (c_int32, [c_int32, _f32p, _u32p, c_void_p, c_int32, _f32p, c_float, c_void_p, c_int32, _f32p, c_int32,
+                                             c_int32, c_int32, c_int32, _f32p, _f32p, c_int32, c_int32, c_int32, _f32p, _f32p, _f32p, c_int32,
+                                             _f32p, POINTER(c_int32)]),
     "kjarni_hip_op_prefill_gemm": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, _f32p, _f32p, c_int64, c_int32, _f32p, c_int64,
                                              _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "kjarni_hip_op_prefill_attention": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int64, _f32p, c_int64, c_int64, c_int32,

@@ -1927,6 +1927,175 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_fused_proj_ggml(int32_t device, int3
     });
 }
 
+// ---- the dense (f32 / bf16) decode-step projections, alone ---------------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_gemv(int32_t device, int32_t lanes, const float* x, int32_t x_rows, int64_t ldx, int32_t rows,
+                                                     const float* gamma, const float* beta, float eps, int32_t layernorm, int32_t gelu_tanh,
+                                                     const void* w, const void* w2, int32_t bf16, int32_t swiglu, const float* bias,
+                                                     const float* r, int64_t ldr, int32_t r_is_y0, int32_t n_out, int32_t k, int32_t seg_q,
+                                                     int32_t seg_kv, float* const* y, const int32_t* out_rows, int64_t ldy0, int64_t ldy12,
+                                                     int32_t row_off, int32_t offset_on_device, float* norm_out, int32_t* route_out)
+{
+    if (!x || !w || !y || !out_rows || !route_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // every element a kernel may read or write lies inside the buffers uploaded below
+        if (lanes != 0 && lanes != 1) throw InvalidConfig("lanes must be 0 (launch_llm_gemv) or 1 (launch_llm_gemv_lanes)");
+        if (rows < 0 || rows > 8 || x_rows < std::max(rows, 1) || x_rows > 64) throw InvalidConfig("rows must be 0 .. 8 and x_rows max(rows, 1) .. 64");
+        if (n_out < 1 || k < 8 || n_out > (1 << 17) || k > (1 << 16) || (int64_t)n_out * k > ((int64_t)1 << 26))
+            throw InvalidConfig("n_out must be 1 .. 2^17, k 8 .. 2^16, n_out * k at most 2^26");
+        if ((k & 7) || (ldx & 3)) throw InvalidConfig("launch_llm_gemv refuses these arguments: k a multiple of 8, ldx a multiple of 4");
+        if (ldx < k || ldx > (1 << 18)) throw InvalidConfig("ldx must cover k (at most 2^18)");
+        if (layernorm && (!gamma || !beta || r || r_is_y0 || swiglu || norm_out))
+            throw InvalidConfig("launch_llm_gemv refuses these arguments: LayerNorm needs gamma and beta and takes no residual, SwiGLU or norm_out");
+        if (gelu_tanh && (!layernorm || seg_q != 0)) throw InvalidConfig("launch_llm_gemv refuses these arguments: GELU-tanh comes after LayerNorm, without segments");
+        if (r && r_is_y0) throw InvalidConfig("r_is_y0 takes the residual from y[0]: r must be NULL");
+        const bool res = r || r_is_y0;
+        if (swiglu && !w2) throw InvalidConfig("SwiGLU needs w2");
+        if ((swiglu && (!gamma || res)) || (res && gamma))
+            throw InvalidConfig("launch_llm_gemv refuses these arguments: SwiGLU comes after RMSNorm without a residual, a residual without a norm");
+        if (norm_out && !(rows == 1 && seg_q == 0 && gamma && (k == 2048 || k == 4096 || k == 8192)))
+            throw InvalidConfig("launch_llm_gemv refuses these arguments: norm_out needs one row, gamma, no segments and k 2048 / 4096 / 8192");
+        if (seg_q < 0 || seg_kv < 0 || (seg_q == 0 && seg_kv != 0)) throw InvalidConfig("seg_q and seg_kv must not be negative; seg_kv needs seg_q");
+        const bool seg = seg_q > 0;
+        if (seg && (seg_kv < 1 || (int64_t)seg_q + 2 * (int64_t)seg_kv != n_out)) throw InvalidConfig("seg_q + 2 * seg_kv must be n_out");
+        if (seg && r_is_y0) throw InvalidConfig("no in-place residual with segments: y[0] holds seg_q of the n_out columns");
+        if (row_off < 0) throw InvalidConfig("row_off must not be negative");
+        const int n_outs = seg ? 3 : 1;
+        const int64_t cols[3] = {seg ? seg_q : n_out, seg_kv, seg_kv}, ldy[3] = {ldy0, ldy12, ldy12};
+        for (int i = 0; i < n_outs; ++i) {
+            if (!y[i]) throw InvalidConfig("an output of this call is NULL");
+            if (ldy[i] < cols[i] || ldy[i] > (1 << 18) || out_rows[i] < 1 || out_rows[i] > 4096 || (int64_t)out_rows[i] * ldy[i] > ((int64_t)1 << 24))
+                throw InvalidConfig("ldy must cover the output's columns (at most 2^18); out_rows 1 .. 4096; at most 2^24 elements");
+            if ((int64_t)(i == 0 ? 0 : row_off) + rows > out_rows[i])
+                throw InvalidConfig("rows " + std::to_string(i == 0 ? 0 : row_off) + " .. +" + std::to_string(rows) + " do not fit the " +
+                                    std::to_string(out_rows[i]) + " rows of output " + std::to_string(i));
+        }
+        if (r && (ldr < n_out || ldr > (1 << 18))) throw InvalidConfig("ldr must cover n_out (at most 2^18)");
+        use_device(device);
+        const size_t wb = (size_t)n_out * (size_t)k * (bf16 ? 2 : 4);
+        const auto xd = upload(x, (size_t)x_rows * (size_t)ldx * 4, "H2D x");
+        const auto gd = upload(gamma, (size_t)k * 4, "H2D gamma"), bed = upload(beta, (size_t)k * 4, "H2D beta");
+        const auto wd = upload(w, wb, "H2D w"), w2d = upload(w2, w2 ? wb : 0, "H2D w2");
+        const auto bd = upload(bias, (size_t)n_out * 4, "H2D bias");
+        const auto rd = upload(r, r ? (size_t)std::max(rows, 1) * (size_t)ldr * 4 : 0, "H2D r");
+        const auto od = upload(&row_off, sizeof(int), "H2D row_off");
+        std::vector<std::unique_ptr<GuardedBuf>> out;
+        for (int i = 0; i < n_outs; ++i) {
+            out.push_back(std::make_unique<GuardedBuf>((size_t)out_rows[i] * (size_t)ldy[i] * 4));
+            hip_check(hipMemcpy(out.back()->buf.p, y[i], out.back()->bytes, hipMemcpyHostToDevice), "H2D y");
+        }
+        GuardedBuf nd((size_t)k * 4);
+        if (norm_out) hip_check(hipMemcpy(nd.buf.p, norm_out, (size_t)k * 4, hipMemcpyHostToDevice), "H2D norm_out");
+        LlmGemvArgs a;
+        a.X = static_cast<const float*>(xd->p); a.ldx = ldx; a.rows = rows;
+        a.gamma = gamma ? static_cast<const float*>(gd->p) : nullptr; a.beta = beta ? static_cast<const float*>(bed->p) : nullptr;
+        a.eps = eps; a.layernorm = layernorm ? 1 : 0; a.gelu_tanh = gelu_tanh ? 1 : 0;
+        a.W = wd->p; a.W2 = w2 ? w2d->p : nullptr; a.bf16 = bf16 ? 1 : 0; a.swiglu = swiglu ? 1 : 0;
+        a.bias = bias ? static_cast<const float*>(bd->p) : nullptr;
+        if (r_is_y0) {
+            a.R = out[0]->as<float>(); a.ldr = ldy0;
+        } else if (r) {
+            a.R = static_cast<const float*>(rd->p); a.ldr = ldr;
+        }
+        a.n_out = n_out; a.k = k; a.seg_q = seg_q; a.seg_kv = seg_kv;
+        a.Y0 = out[0]->as<float>(); a.ldy0 = ldy0;
+        if (seg) {
+            a.Y1 = out[1]->as<float>(); a.Y2 = out[2]->as<float>(); a.ldy12 = ldy12;
+        }
+        a.row_off = row_off;
+        if (offset_on_device) {
+            a.row_off_ptr = static_cast<const int*>(od->p);
+            a.row_off = decoy_offset(row_off, seg ? std::min(out_rows[1], out_rows[2]) - rows : 0);
+        }
+        a.norm_out = norm_out ? nd.as<float>() : nullptr;
+        int32_t route[16] = {0};
+        const LlmGemvRoute g = llm_gemv_route(a);
+        const int32_t gr[7] = {g.kernel, g.ch, g.wide, g.threads, g.loop, g.rows_per_batch, g.workgroups};
+        if (lanes) {
+            const LlmGemvLanesRoute l = llm_gemv_lanes_route(a);
+            int streamed = -1;
+            launcher_check(launch_llm_gemv_lanes(a, nullptr, &streamed), "llm gemv, lanes");
+            const int32_t lr[7] = {l.taken, l.ch, l.ns, l.wide, l.cpw, l.workgroups, streamed};
+            std::copy(lr, lr + 7, route);
+            if (!l.taken) std::copy(gr, gr + 7, route + 8);  // the fallback's own route
+        } else {
+            launcher_check(launch_llm_gemv(a, nullptr), "llm gemv");
+            std::copy(gr, gr + 7, route);
+        }
+        hip_check(hipDeviceSynchronize(), "sync");
+        for (int i = 0; i < n_outs; ++i) {
+            out[i]->check("llm gemv output");
+            hip_check(hipMemcpy(y[i], out[i]->buf.p, (size_t)out_rows[i] * (size_t)ldy[i] * 4, hipMemcpyDeviceToHost), "D2H y");
+        }
+        nd.check("norm_out");
+        if (norm_out) hip_check(hipMemcpy(norm_out, nd.buf.p, (size_t)k * 4, hipMemcpyDeviceToHost), "D2H norm_out");
+        std::copy(route, route + 16, route_out);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_qkv_rope(int32_t device, const float* x, const uint32_t* embed_ids, const void* table, int32_t vocab,
+                                                         const float* gamma, float eps, const void* w, int32_t bf16, const float* bias, int32_t k,
+                                                         int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* cos_t,
+                                                         const float* sin_t, int32_t positions, int32_t pos, int32_t offset_on_device, float* q,
+                                                         float* k_cache, float* v_cache, int32_t cache_rows, float* x_raw_out, int32_t* route)
+{
+    if (!w || !cos_t || !sin_t || !q || !k_cache || !v_cache || !route) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!gamma) throw InvalidConfig("launch_llm_qkv_rope refuses these arguments: gamma is NULL (both kernels normalise the row)");
+        if (k < 8 || (k & 7) || k > 8192 || head_dim < 2 || (head_dim & 1))
+            throw InvalidConfig("launch_llm_qkv_rope refuses these arguments: k a multiple of 8 and at most 8192, head_dim even");
+        if (head_dim > 1024 || n_heads < 1 || n_heads > 256 || n_kv_heads < 1 || n_kv_heads > n_heads)
+            throw InvalidConfig("head_dim at most 1024, n_heads 1 .. 256, n_kv_heads 1 .. n_heads");
+        const int64_t q_dim = (int64_t)n_heads * head_dim, kv_dim = (int64_t)n_kv_heads * head_dim, n_out = q_dim + 2 * kv_dim;
+        if (n_out * k > ((int64_t)1 << 26)) throw InvalidConfig("(n_heads + 2 n_kv_heads) * head_dim * k at most 2^26");
+        if (!x == !embed_ids) throw InvalidConfig("the input row is x or the embedding of *embed_ids: exactly one of them");
+        if (embed_ids) {
+            if (!table || vocab < 1 || vocab > (1 << 17) || (int64_t)vocab * k > ((int64_t)1 << 26))
+                throw InvalidConfig("the embedding gather needs a table, vocab 1 .. 2^17 and vocab * k at most 2^26");
+            if (k != 2048 && k != 4096 && k != 8192) throw InvalidConfig("launch_llm_qkv_rope refuses these arguments: the gather needs k 2048 / 4096 / 8192");
+        } else if (table || x_raw_out) {
+            throw InvalidConfig("table and x_raw_out belong to the embedding gather");
+        }
+        if (positions < 1 || positions > (1 << 20) || cache_rows < 1 || cache_rows > 4096 || (int64_t)cache_rows * kv_dim > ((int64_t)1 << 24))
+            throw InvalidConfig("positions must be 1 .. 2^20, cache_rows 1 .. 4096, a cache at most 2^24 elements");
+        if (pos < 0 || pos >= positions || pos >= cache_rows) throw InvalidConfig("pos is no row of the tables or of the caches");
+        use_device(device);
+        const int half = head_dim / 2;
+        const size_t es = bf16 ? 2 : 4, tb = (size_t)positions * (size_t)half * 4, cb = (size_t)cache_rows * (size_t)kv_dim * 4;
+        const auto xd = upload(x, x ? (size_t)k * 4 : 0, "H2D x");
+        const auto idd = upload(embed_ids, embed_ids ? 4 : 0, "H2D id");
+        const auto td = upload(table, embed_ids ? (size_t)vocab * (size_t)k * es : 0, "H2D table");
+        const auto gd = upload(gamma, (size_t)k * 4, "H2D gamma");
+        const auto wd = upload(w, (size_t)n_out * (size_t)k * es, "H2D w");
+        const auto bd = upload(bias, bias ? (size_t)n_out * 4 : 0, "H2D bias");
+        const auto cd = upload(cos_t, tb, "H2D cos"), sd = upload(sin_t, tb, "H2D sin");
+        const auto pd = upload(&pos, sizeof(int), "H2D pos");
+        GuardedBuf qd((size_t)q_dim * 4), kd(cb), vd(cb), rd((size_t)k * 4);
+        hip_check(hipMemcpy(qd.buf.p, q, (size_t)q_dim * 4, hipMemcpyHostToDevice), "H2D q");
+        hip_check(hipMemcpy(kd.buf.p, k_cache, cb, hipMemcpyHostToDevice), "H2D k_cache");
+        hip_check(hipMemcpy(vd.buf.p, v_cache, cb, hipMemcpyHostToDevice), "H2D v_cache");
+        if (x_raw_out) hip_check(hipMemcpy(rd.buf.p, x_raw_out, (size_t)k * 4, hipMemcpyHostToDevice), "H2D x_raw_out");
+        const float* G = static_cast<const float*>(gd->p);
+        const uint32_t* ids = embed_ids ? static_cast<const uint32_t*>(idd->p) : nullptr;
+        // (with the position on the device the by-value one is another row of the tables and the caches)
+        const int by_value = offset_on_device ? decoy_offset(pos, std::min(positions, cache_rows) - 1) : pos;
+        const LlmQkvRopeRoute rt = llm_qkv_rope_route(k, G, wd->p, n_heads, n_kv_heads, head_dim, ids);
+        launcher_check(launch_llm_qkv_rope(x ? static_cast<const float*>(xd->p) : nullptr, G, eps, wd->p, bf16 ? 1 : 0,
+                                           bias ? static_cast<const float*>(bd->p) : nullptr, k, n_heads, n_kv_heads, head_dim,
+                                           static_cast<const float*>(cd->p), static_cast<const float*>(sd->p), qd.as<float>(), kd.as<float>(),
+                                           vd.as<float>(), by_value, offset_on_device ? static_cast<const int*>(pd->p) : nullptr, nullptr, ids,
+                                           embed_ids ? td->p : nullptr, embed_ids ? vocab : 0, x_raw_out ? rd.as<float>() : nullptr),
+                       "llm qkv + rope");
+        hip_check(hipDeviceSynchronize(), "sync");
+        qd.check("q"); kd.check("k_cache"); vd.check("v_cache"); rd.check("x_raw_out");
+        hip_check(hipMemcpy(q, qd.buf.p, (size_t)q_dim * 4, hipMemcpyDeviceToHost), "D2H q");
+        hip_check(hipMemcpy(k_cache, kd.buf.p, cb, hipMemcpyDeviceToHost), "D2H k_cache");
+        hip_check(hipMemcpy(v_cache, vd.buf.p, cb, hipMemcpyDeviceToHost), "D2H v_cache");
+        if (x_raw_out) hip_check(hipMemcpy(x_raw_out, rd.buf.p, (size_t)k * 4, hipMemcpyDeviceToHost), "D2H x_raw_out");
+        route[0] = rt.kernel; route[1] = rt.ch; route[2] = rt.workgroups;
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qembed(int32_t device, const uint32_t* ids, int32_t n_ids, const void* blocks, int32_t ggml_type,
                                                    int32_t vocab, int32_t k, float* out)
 {

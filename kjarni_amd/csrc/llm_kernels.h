@@ -36,6 +36,20 @@ struct LlmGemvArgs {
     float* norm_out = nullptr;     // rows == 1 with gamma (only where llm_gemv_streams()): the normalised row is also stored here
 };
 hipError_t launch_llm_gemv(const LlmGemvArgs& args, hipStream_t stream);
+// The kernel launch_llm_gemv takes for these arguments and the form it takes it in (the launcher's own decision: it calls this).
+// stream: llm_gemv_stream_kernel (one row, K = 2048 / 4096 / 8192); splitk: llm_gemv_splitk_kernel (one row, K over the waves of a
+// workgroup); one: llm_gemv1_kernel (one row staged in LDS, cache segments); generic: llm_gemv_kernel (a wave per column, 1-8 rows).
+enum : int { LLM_GEMV_STREAM = 0, LLM_GEMV_SPLITK = 1, LLM_GEMV_ONE = 2, LLM_GEMV_GENERIC = 3 };
+struct LlmGemvRoute {
+    int kernel = LLM_GEMV_GENERIC;
+    int ch = 0;              // stream: 512-column pieces of K (4 / 8 / 16); splitk: 8-column chunks per lane (1 / 2 / 4 / 8); else 0
+    int wide = 0;            // stream: 16 loads per lane in flight; splitk: 16 waves per workgroup
+    int threads = 256;       // per workgroup: 256, 512 (stream) or 1024 (splitk, wide)
+    int loop = 0;            // stream: the grid does not cover the columns, every wave walks several batches
+    int rows_per_batch = 1;  // weight rows (columns of Y) per wave and batch (stream, one, generic) or per workgroup (splitk)
+    int workgroups = 0;
+};
+LlmGemvRoute llm_gemv_route(const LlmGemvArgs& args);
 // One row, + residual, no norm: can the projection merge `splits` attention slabs of `head_dim`-wide heads itself?
 bool llm_gemv_merges_attention(int k, int splits, int head_dim);
 // Does a one-row projection with these sizes take the weight-streaming kernel (which honours norm_out)?
@@ -50,6 +64,14 @@ hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, co
                                float* Vc, int pos, const int* pos_ptr, hipStream_t stream, const uint32_t* embed_ids = nullptr,
                                const void* table = nullptr, int vocab = 0, float* x_raw_out = nullptr);
 bool llm_qkv_rope_embeds(int k, const float* gamma, const void* W, const void* table);
+// The kernel launch_llm_qkv_rope takes (its own decision): a workgroup per pair of columns with `ch` 8-column chunks per lane
+// (1 / 2 / 4), or the weight-streaming form (a wave per pair, ch = k / 512), the latter with or without the embedding gather.
+enum : int { LLM_QKV_PAIR = 0, LLM_QKV_STREAM = 1, LLM_QKV_STREAM_EMBED = 2 };
+struct LlmQkvRopeRoute {
+    int kernel = LLM_QKV_PAIR, ch = 0, workgroups = 0;
+};
+LlmQkvRopeRoute llm_qkv_rope_route(int k, const float* gamma, const void* W, int n_heads, int n_kv_heads, int head_dim,
+                                   const uint32_t* embed_ids);
 
 // Prefill: Y[M, N] = A[M, K] . W[N, K]^T + bias (+ R) on the fp32 matrix cores, W bf16 or f32; K % 32 == 0.  R may alias Y.
 // split_scratch (prefill_gemm_scratch_floats() floats, or null): short prompts split K over up to 8 workgroups per tile.
@@ -118,6 +140,12 @@ struct LlmLaneState {
 // launch_llm_gemv for 2-8 independent rows: the multi-row weight-streaming kernel where llm_gemv_lanes_takes() (k >= 512,
 // 16-byte aligned operands), else launch_llm_gemv's one-wave-per-column kernel; *streamed (may be null) says which ran.
 bool llm_gemv_lanes_takes(const LlmGemvArgs& args);
+// The form of llm_gemv_lanes_kernel launch_llm_gemv_lanes takes (its own decision; taken == 0: it falls back to launch_llm_gemv and
+// the other fields stay 0): slices of ch * 512 columns of K, ns of them, cpw columns per wave and batch (wide: more than one).
+struct LlmGemvLanesRoute {
+    int taken = 0, ch = 0, ns = 0, wide = 0, cpw = 0, workgroups = 0;
+};
+LlmGemvLanesRoute llm_gemv_lanes_route(const LlmGemvArgs& args);
 hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& args, hipStream_t stream, int* streamed);
 // qkv [lanes, (n_heads + 2 n_kv_heads) * head_dim]: Q rotated in place at state->pos[lane], K rotated (rotate == 0: copied) and V
 // copied to row pos[lane] of cache + lane * lane_stride; frozen lanes and positions >= capacity write nothing.

@@ -1260,12 +1260,74 @@ __global__ __launch_bounds__(256) void swiglu_mul_kernel(float* __restrict__ gat
 
 }  // namespace
 
+LlmGemvRoute llm_gemv_route(const LlmGemvArgs& a)
+{
+    LlmGemvRoute r;
+    const bool norm = a.gamma != nullptr;
+    // Staging the row in LDS pays when it also has to be normalised (otherwise every wave redoes the statistics); plain
+    // projections keep the one-wave-per-column kernel, whose 4x larger grid hides latency better.
+    // One row, K = 2048 / 4096 / 8192: the weight-streaming kernel.
+    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && llm_gemv_streams(a.k, a.W, a.W2)) {
+        const int ch = a.k / 512;
+        const int nm = a.swiglu ? 2 : 1, lpp = a.bf16 ? 1 : 2;
+        // 16 loads per lane in flight where that still leaves >= 8 waves per CU, else one row per wave
+        const bool wide = a.n_out / stream_rows_per_batch(ch, lpp, nm, true) >= 2048;
+        const int rb = stream_rows_per_batch(ch, lpp, nm, wide);
+        const int batches = (a.n_out + rb - 1) / rb;
+        // 8-wave workgroups where they still cover every CU and staging the input row is the larger cost (a long row, or the
+        // attention slabs to merge: each workgroup stages the whole row, so fewer, larger ones re-read it less; measured on
+        // the 1B shape: down-proj 8.0 -> 7.6 us, output projection with the merge 6.4 -> 4.9 us, gate/up 12.8 -> 13.2 us);
+        // the layer's projections get one batch per wave, the vocabulary head loops
+        const bool big = batches >= 2048 && (ch >= 16 || a.att_splits > 0);
+        const int wpw = big ? 8 : 4;
+        const bool loop = (batches + wpw - 1) / wpw > 4096 / wpw;
+        r.kernel = LLM_GEMV_STREAM;
+        r.ch = ch;
+        r.wide = (wide || loop) ? 1 : 0;  // the looping form is instantiated with the 16-load batches only
+        r.threads = big ? 512 : 256;
+        r.loop = loop ? 1 : 0;
+        r.rows_per_batch = stream_rows_per_batch(ch, lpp, nm, r.wide != 0);
+        r.workgroups = loop ? 2048 / wpw : std::max(1, (batches + wpw - 1) / wpw);
+        return r;
+    }
+    // LayerNorm (GPT-2) takes three kernels, each instantiated for the one combination it serves: one row, k <= 2048, the
+    // c_fc stage (LayerNorm + GELU) -> split-K; one row, the Q|K|V stage (LayerNorm, cache segments) -> the LDS-staged
+    // kernel; everything else -> the multi-row kernel.
+    const bool ln_splitk = a.layernorm && a.rows == 1 && a.gelu_tanh && a.seg_q == 0 && a.k <= 2048;
+    const bool ln_one = a.layernorm && a.rows == 1 && !a.gelu_tanh && a.k <= G1_MAX_K;
+    const bool rms_splitk = !a.layernorm && a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048;
+    const bool rms_one = !a.layernorm && a.rows == 1 && norm && a.k <= G1_MAX_K;
+    if (ln_splitk || (!ln_one && rms_splitk)) {
+        const bool wide = !ln_splitk && a.k >= 8192;  // 16 waves per workgroup
+        const int threads = wide ? 1024 : 256;
+        const int chunks = (a.k / 8 + threads - 1) / threads;
+        const int ch = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : (chunks <= 4 ? 4 : 8));
+        r.kernel = LLM_GEMV_SPLITK;
+        r.ch = ln_splitk ? 1 : (wide && ch > 2 ? 2 : ch);
+        r.wide = wide ? 1 : 0;
+        r.threads = threads;
+        r.rows_per_batch = SK_OPW;
+        r.workgroups = (a.n_out + SK_OPW - 1) / SK_OPW;
+        return r;
+    }
+    if (ln_one || rms_one) {
+        r.kernel = LLM_GEMV_ONE;
+        r.rows_per_batch = G1_OPW;
+        r.workgroups = (a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW);
+        return r;
+    }
+    r.kernel = LLM_GEMV_GENERIC;
+    r.workgroups = (a.n_out + 3) / 4;
+    return r;
+}
+
 template <typename WT>
 static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
 {
     const WT* W = static_cast<const WT*>(a.W);
     const WT* W2 = static_cast<const WT*>(a.W2);
     const bool norm = a.gamma != nullptr;
+    const LlmGemvRoute rt = llm_gemv_route(a);  // which kernel, in which form: every decision below is read from it
     // The (epilogue, norm) pairs the callers request (launch_llm_gemv rejects every other one), and the only ones
     // instantiated; each route below takes those of them it can reach:
     //   (LE_NONE, NK_RMS)        RMSNorm + Q|K|V (llm.cpp pass: prompt rows, or one row wider than 8192), the decode step's head
@@ -1284,22 +1346,10 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
     // Staging the row in LDS pays when it also has to be normalised (otherwise every wave redoes the statistics); plain
     // projections keep the one-wave-per-column kernel, whose 4x larger grid hides latency better.
     // One row, K = 2048 / 4096 / 8192: the weight-streaming kernel.
-    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && llm_gemv_streams(a.k, a.W, a.W2)) {
-        constexpr bool BF = sizeof(WT) == 2;
-        const int ch = a.k / 512;
-        const int nm = a.swiglu ? 2 : 1, lpp = BF ? 1 : 2;
-        // 16 loads per lane in flight where that still leaves >= 8 waves per CU, else one row per wave
-        const bool wide = a.n_out / stream_rows_per_batch(ch, lpp, nm, true) >= 2048;
-        const int rb = stream_rows_per_batch(ch, lpp, nm, wide);
-        const int batches = (a.n_out + rb - 1) / rb;
-        // 8-wave workgroups where they still cover every CU and staging the input row is the larger cost (a long row, or the
-        // attention slabs to merge: each workgroup stages the whole row, so fewer, larger ones re-read it less; measured on
-        // the 1B shape: down-proj 8.0 -> 7.6 us, output projection with the merge 6.4 -> 4.9 us, gate/up 12.8 -> 13.2 us);
-        // the layer's projections get one batch per wave, the vocabulary head loops
-        const bool big = batches >= 2048 && (ch >= 16 || a.att_splits > 0);
-        const int wpw = big ? 8 : 4;
-        const bool loop = (batches + wpw - 1) / wpw > 4096 / wpw;
-        const int wgs = loop ? 2048 / wpw : std::max(1, (batches + wpw - 1) / wpw);
+    if (rt.kernel == LLM_GEMV_STREAM) {
+        // (the rule -- 16 loads per lane in flight, 8-wave workgroups, the looping head -- is llm_gemv_route's)
+        const int ch = rt.ch, wgs = rt.workgroups;
+        const bool wide = rt.wide != 0, loop = rt.loop != 0, big = rt.threads == 512;
 #define KJ_ST4(EPI, NORM, CH, WIDE, LOOP, THREADS)                                                                                   \
     hipLaunchKernelGGL((llm_gemv_stream_kernel<WT, EPI, NORM != NK_NONE, CH, WIDE, LOOP, THREADS>), dim3((unsigned)wgs), dim3(THREADS), \
                        0, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.Y0, 0, 0, a.norm_out)
@@ -1349,12 +1399,12 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
     // LayerNorm (GPT-2) takes three kernels, each instantiated for the one combination it serves: one row, k <= 2048, the
     // c_fc stage (LayerNorm + GELU) -> split-K; one row, the Q|K|V stage (LayerNorm, cache segments) -> the LDS-staged
     // kernel; everything else -> the multi-row kernel below.
-    if (a.layernorm && a.rows == 1 && a.gelu_tanh && a.seg_q == 0 && a.k <= 2048) {
-        hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, LE_GELU_TANH, NK_LN, 1, 4>), dim3((unsigned)((a.n_out + SK_OPW - 1) / SK_OPW)), dim3(256),
+    if (rt.kernel == LLM_GEMV_SPLITK && a.layernorm) {
+        hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, LE_GELU_TANH, NK_LN, 1, 4>), dim3((unsigned)rt.workgroups), dim3(256),
                            0, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.Y0, a.beta);
         return hipGetLastError();
     }
-    const dim3 grid1((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW)));
+    const dim3 grid1((unsigned)((a.n_out + 4 * G1_OPW - 1) / (4 * G1_OPW)));  // (= rt.workgroups where the route is this kernel)
     const size_t lds1 = (size_t)a.k * sizeof(float);
 #define KJ_LLM1(EPI, NORM)                                                                                                            \
     do {                                                                                                                              \
@@ -1366,17 +1416,16 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
         hipLaunchKernelGGL(kern, grid1, dim3(256), lds1, stream, a.X, a.gamma, a.eps, W, W2, a.bias, a.R, a.n_out, a.k, a.seg_q,      \
                            a.seg_kv, a.Y0, a.Y1, a.Y2, a.ldy12, a.row_off, a.row_off_ptr, a.beta);                                    \
     } while (0)
-    if (a.layernorm && a.rows == 1 && !a.gelu_tanh && a.k <= G1_MAX_K) {
+    if (rt.kernel == LLM_GEMV_ONE && a.layernorm) {
         KJ_LLM1(LE_NONE, NK_LN);
         return hipGetLastError();
     }
-    if (!a.layernorm && a.rows == 1 && a.seg_q == 0 && a.k <= SK_MAX_CHUNKS * 2048) {
+    if (rt.kernel == LLM_GEMV_SPLITK) {
         // Long rows (down-proj: k = 8192 .. 14336) are spread over 16 waves per workgroup: a quarter of the loads per lane,
         // four times the waves in flight, at the same two columns per workgroup.
-        const bool wide = a.k >= 8192;
-        const int threads = wide ? 1024 : 256;
-        const int chunks = (a.k / 8 + threads - 1) / threads;
-        const dim3 gridk((unsigned)((a.n_out + SK_OPW - 1) / SK_OPW));
+        const bool wide = rt.wide != 0;
+        const int chunks = rt.ch;
+        const dim3 gridk((unsigned)rt.workgroups);
 #define KJ_SK3(EPI, NORM, CH, NW)                                                                                                     \
     hipLaunchKernelGGL((llm_gemv_splitk_kernel<WT, EPI, NORM, CH, NW>), gridk, dim3(64 * NW), 0, stream, a.X, a.gamma, a.eps, W, W2,  \
                        a.bias, a.R, a.n_out, a.k, a.Y0, a.beta)
@@ -1398,13 +1447,13 @@ static hipError_t launch_gemv_t(const LlmGemvArgs& a, hipStream_t stream)
 #undef KJ_SK3
         return hipGetLastError();
     }
-    if (!a.layernorm && a.rows == 1 && norm && a.k <= G1_MAX_K) {
+    if (rt.kernel == LLM_GEMV_ONE) {
         if (a.swiglu) KJ_LLM1(LE_SWIGLU, NK_RMS);
         else KJ_LLM1(LE_NONE, NK_RMS);
         return hipGetLastError();
     }
 #undef KJ_LLM1
-    const dim3 grid((unsigned)((a.n_out + 3) / 4));
+    const dim3 grid((unsigned)rt.workgroups);
 #define KJ_LLM(EPI, NORM)                                                                                                       \
     hipLaunchKernelGGL((llm_gemv_kernel<WT, EPI, NORM>), grid, dim3(256), 0, stream, a.X, a.ldx, a.rows, a.gamma, a.eps, W, W2,  \
                        a.bias, a.R, a.ldr, a.n_out, a.k, a.seg_q, a.seg_kv, a.Y0, a.ldy0, a.Y1, a.Y2, a.ldy12, a.row_off,       \
@@ -1735,16 +1784,35 @@ bool llm_qkv_rope_embeds(int k, const float* gamma, const void* W, const void* t
            (reinterpret_cast<uintptr_t>(table) & 15) == 0;
 }
 
+LlmQkvRopeRoute llm_qkv_rope_route(int k, const float* gamma, const void* W, int n_heads, int n_kv_heads, int head_dim,
+                                   const uint32_t* embed_ids)
+{
+    LlmQkvRopeRoute r;
+    const int tasks = (n_heads * head_dim + 2 * n_kv_heads * head_dim) / 2;  // pairs of output columns
+    if ((k == 2048 || k == 4096 || k == 8192) && gamma && (reinterpret_cast<uintptr_t>(W) & 15) == 0) {
+        r.kernel = embed_ids ? LLM_QKV_STREAM_EMBED : LLM_QKV_STREAM;
+        r.ch = k / 512;
+        r.workgroups = (tasks + 3) / 4;  // one wave per pair
+        return r;
+    }
+    const int chunks = (k / 8 + 255) / 256;
+    r.kernel = LLM_QKV_PAIR;
+    r.ch = chunks <= 1 ? 1 : (chunks <= 2 ? 2 : 4);
+    r.workgroups = tasks;  // one workgroup per pair
+    return r;
+}
+
 hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, const void* W, int bf16, const float* bias, int k,
                                int n_heads, int n_kv_heads, int head_dim, const float* cos_t, const float* sin_t, float* Q, float* Kc,
                                float* Vc, int pos, const int* pos_ptr, hipStream_t stream, const uint32_t* embed_ids, const void* table,
                                int vocab, float* x_raw_out)
 {
-    if ((k & 7) || k > 8192 || (head_dim & 1)) return hipErrorInvalidValue;
-    const int tasks = (n_heads * head_dim + 2 * n_kv_heads * head_dim) / 2;
+    // (both kernels read gamma: the step is RMSNorm + projection + RoPE, there is no form without the norm)
+    if ((k & 7) || k > 8192 || (head_dim & 1) || !gamma) return hipErrorInvalidValue;
     if (embed_ids && !llm_qkv_rope_embeds(k, gamma, W, table)) return hipErrorInvalidValue;
-    if ((k == 2048 || k == 4096 || k == 8192) && gamma && (reinterpret_cast<uintptr_t>(W) & 15) == 0) {
-        const dim3 sgrid((unsigned)((tasks + 3) / 4));
+    const LlmQkvRopeRoute rt = llm_qkv_rope_route(k, gamma, W, n_heads, n_kv_heads, head_dim, embed_ids);
+    if (rt.kernel != LLM_QKV_PAIR) {
+        const dim3 sgrid((unsigned)rt.workgroups);
 #define KJ_QKVS(WT, CH)                                                                                                              \
     do {                                                                                                                             \
         if (embed_ids)                                                                                                               \
@@ -1768,8 +1836,8 @@ hipError_t launch_llm_qkv_rope(const float* X, const float* gamma, float eps, co
 #undef KJ_QKVS
         return hipGetLastError();
     }
-    const dim3 grid((unsigned)tasks);
-    const int chunks = (k / 8 + 255) / 256;
+    const dim3 grid((unsigned)rt.workgroups);
+    const int chunks = rt.ch;
 #define KJ_QKV(WT, CH)                                                                                                              \
     hipLaunchKernelGGL((llm_qkv_rope_kernel<WT, CH>), grid, dim3(256), 0, stream, X, gamma, eps, static_cast<const WT*>(W), bias, k, \
                        n_heads, n_kv_heads, head_dim, cos_t, sin_t, Q, Kc, Vc, pos, pos_ptr)
@@ -2501,23 +2569,39 @@ bool llm_gemv_lanes_takes(const LlmGemvArgs& a)
            (!a.beta || (reinterpret_cast<uintptr_t>(a.beta) & 15) == 0);
 }
 
-template <typename WT>
-static hipError_t launch_gemv_lanes_t(const LlmGemvArgs& a, hipStream_t stream)
+LlmGemvLanesRoute llm_gemv_lanes_route(const LlmGemvArgs& a)
 {
-    const WT* W = static_cast<const WT*>(a.W);
-    const WT* W2 = static_cast<const WT*>(a.W2);
-    constexpr int LPP = sizeof(WT) == 2 ? 1 : 2;
+    LlmGemvLanesRoute r;
+    r.taken = llm_gemv_lanes_takes(a) ? 1 : 0;
+    if (!r.taken || a.n_out <= 0) return r;
+    const int lpp = a.bf16 ? 1 : 2;
     // the slice width that pads K least (K = 768 / 3 072 -> 1 024, else 2 048)
     const int ch = ((a.k + 1023) / 1024) * 1024 - a.k < ((a.k + 2047) / 2048) * 2048 - a.k ? 2 : 4;
     const int nm = a.swiglu ? 2 : 1;
     const int ns = (a.k + ch * 512 - 1) / (ch * 512);
     // 16 loads per lane in flight where that still leaves two workgroups for every CU, else one column per wave
-    const int cpw_wide = lanes_cols_per_wave(ch, LPP, nm, true);
+    const int cpw_wide = lanes_cols_per_wave(ch, lpp, nm, true);
     const bool wide = (a.n_out + 4 * cpw_wide - 1) / (4 * cpw_wide) >= 512;
     const int cpw = wide ? cpw_wide : 1;
     const int nbatches = (a.n_out + 4 * cpw - 1) / (4 * cpw);
+    r.ch = ch;
+    r.ns = ns;
+    r.wide = wide ? 1 : 0;
+    r.cpw = cpw;
     // one slice: the rows stay in LDS and the workgroup loops over its batches; several: the grid covers the columns
-    const int wgs = ns == 1 ? std::min(nbatches, 512) : nbatches;
+    r.workgroups = ns == 1 ? std::min(nbatches, 512) : nbatches;
+    return r;
+}
+
+template <typename WT>
+static hipError_t launch_gemv_lanes_t(const LlmGemvArgs& a, hipStream_t stream)
+{
+    const WT* W = static_cast<const WT*>(a.W);
+    const WT* W2 = static_cast<const WT*>(a.W2);
+    // (the slice width, the 16-load form and the grid are llm_gemv_lanes_route's)
+    const LlmGemvLanesRoute rt = llm_gemv_lanes_route(a);
+    const int ch = rt.ch, wgs = rt.workgroups;
+    const bool wide = rt.wide != 0;
     const size_t lds = (size_t)a.rows * ch * 512 * sizeof(float);
 #define KJ_LN3(EPI, NORM, CH, WIDE)                                                                                                  \
     do {                                                                                                                             \

@@ -319,6 +319,90 @@ def prefill_gemm(a, w, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=
     return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
 
 
+# ---- the dense (f32 / bf16) decode-step projections, alone ----
+GEMV_STREAM, GEMV_SPLITK, GEMV_ONE, GEMV_GENERIC = 0, 1, 2, 3
+QKV_PAIR, QKV_STREAM, QKV_STREAM_EMBED = 0, 1, 2
+
+
+def llm_gemv(x, w, rows: int, ys, k: Optional[int] = None, lanes: bool = False, gamma=None, beta=None, eps: float = 0.0,
+             layernorm: bool = False, gelu_tanh: bool = False, w2=None, bf16: bool = False, swiglu: bool = False, bias=None, r=None,
+             r_is_y0: bool = False, seg_q: int = 0, seg_kv: int = 0, row_off: int = 0, offset_on_device: bool = False, norm_out=None,
+             device: int = 0):
+    """One launch_llm_gemv (lanes: launch_llm_gemv_lanes) on host arrays (kjarni_hip_op_llm_gemv).  x [x_rows, ldx] (k = w's width
+    unless given); w, w2 [n_out, k] f32 or bf16 bit patterns (uint16, bf16 = True); ys: 1 or 3 outputs [out_rows, ldy] as they are
+    before the launch (seg_q > 0: Q, K, V; the two caches share their stride); r [rows, ldr] or r_is_y0; norm_out [k] as it is
+    before the launch.  Returns (outputs, norm_out or None, route) -- copies; route is a dict of the launcher's own decisions."""
+    xa = np.ascontiguousarray(x, np.float32)
+    wa = np.ascontiguousarray(w, np.uint16 if bf16 else np.float32)
+    w2a = None if w2 is None else np.ascontiguousarray(w2, np.uint16 if bf16 else np.float32)
+    out = [np.array(y, np.float32, order="C") for y in ys]
+    if xa.ndim != 2 or wa.ndim != 2 or len(out) not in (1, 3) or any(y.ndim != 2 for y in out) or (w2a is not None and w2a.shape != wa.shape):
+        raise ValueError("x: [x_rows, ldx]; w, w2: [n_out, k]; ys: 1 or 3 arrays [out_rows, ldy]")
+    if len(out) == 3 and out[1].shape[1] != out[2].shape[1]:
+        raise ValueError("ys[1] and ys[2] share ldy12")
+    n_out = wa.shape[0]
+    kk = wa.shape[1] if k is None else int(k)
+    g, be, b = _proj_vector(gamma, kk, "gamma"), _proj_vector(beta, kk, "beta"), _proj_vector(bias, n_out, "bias")
+    ra = None if r is None else np.ascontiguousarray(r, np.float32)
+    if ra is not None and (ra.ndim != 2 or ra.shape[0] < max(int(rows), 1)):
+        raise ValueError("r: [rows, ldr]")
+    no = None if norm_out is None else np.array(norm_out, np.float32, order="C")
+    if no is not None and no.size != kk:
+        raise ValueError("norm_out: [k]")
+    yp = (C.c_void_p * 3)(*[y.ctypes.data for y in out])
+    orows = (C.c_int32 * 3)(*[y.shape[0] for y in out])
+    route = (C.c_int32 * 16)(*([-1] * 16))
+    v = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check_error(lib().kjarni_hip_op_llm_gemv(device, int(bool(lanes)), _f(xa), xa.shape[0], xa.shape[1], int(rows), _f(g), _f(be), float(eps),
+                                             int(bool(layernorm)), int(bool(gelu_tanh)), v(wa), v(w2a), int(bool(bf16)), int(bool(swiglu)), _f(b),
+                                             _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y0)), n_out, kk, int(seg_q), int(seg_kv), yp,
+                                             orows, out[0].shape[1], out[1].shape[1] if len(out) == 3 else 0, int(row_off),
+                                             int(bool(offset_on_device)), _f(no), route))
+    names = ("taken", "ch", "ns", "wide", "cpw", "workgroups", "streamed") if lanes else \
+        ("kernel", "ch", "wide", "threads", "loop", "rows_per_batch", "workgroups")
+    rt = dict(zip(names, list(route)[:7]))
+    if lanes and not rt["taken"]:
+        rt["fallback"] = dict(zip(("kernel", "ch", "wide", "threads", "loop", "rows_per_batch", "workgroups"), list(route)[8:15]))
+    return out, no, rt
+
+
+def llm_qkv_rope(w, gamma, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, sin_t, pos: int, q, k_cache, v_cache, x=None,
+                 embed_id: Optional[int] = None, table=None, eps: float = 0.0, bf16: bool = False, bias=None, offset_on_device: bool = False,
+                 x_raw_out=None, device: int = 0):
+    """One launch_llm_qkv_rope on host arrays (kjarni_hip_op_llm_qkv_rope).  x [k], or embed_id with table [vocab, k] (the weights'
+    dtype); w [(n_heads + 2 n_kv_heads) * head_dim, k]; cos_t / sin_t [positions, head_dim / 2]; q [n_heads * head_dim], k_cache /
+    v_cache [cache_rows, n_kv_heads * head_dim] and x_raw_out [k] as they are before the launch.  Returns (q, k_cache, v_cache,
+    x_raw_out or None, route) -- copies; route is a dict of the launcher's own decisions."""
+    wt = np.uint16 if bf16 else np.float32
+    wa = np.ascontiguousarray(w, wt)
+    if wa.ndim != 2 or wa.shape[0] != (int(n_heads) + 2 * int(n_kv_heads)) * int(head_dim):
+        raise ValueError("w: [(n_heads + 2 n_kv_heads) * head_dim, k]")
+    kk = wa.shape[1]
+    xa = _proj_vector(x, kk, "x")
+    ta = None if table is None else np.ascontiguousarray(table, wt)
+    if ta is not None and (ta.ndim != 2 or ta.shape[1] != kk):
+        raise ValueError("table: [vocab, k]")
+    ida = None if embed_id is None else np.array([int(embed_id)], np.uint32)
+    g, b = _proj_vector(gamma, kk, "gamma"), _proj_vector(bias, wa.shape[0], "bias")
+    ca, sa = np.ascontiguousarray(cos_t, np.float32), np.ascontiguousarray(sin_t, np.float32)
+    if ca.ndim != 2 or ca.shape != sa.shape or ca.shape[1] != int(head_dim) // 2:
+        raise ValueError("cos_t, sin_t: [positions, head_dim / 2]")
+    qa, ka, va = (np.array(t, np.float32, order="C") for t in (q, k_cache, v_cache))
+    kv = int(n_kv_heads) * int(head_dim)
+    if qa.size != int(n_heads) * int(head_dim) or ka.ndim != 2 or ka.shape != va.shape or ka.shape[1] != kv:
+        raise ValueError("q: [n_heads * head_dim]; k_cache, v_cache: [cache_rows, n_kv_heads * head_dim]")
+    ro = None if x_raw_out is None else np.array(x_raw_out, np.float32, order="C")
+    if ro is not None and ro.size != kk:
+        raise ValueError("x_raw_out: [k]")
+    route = (C.c_int32 * 3)(-1, -1, -1)
+    v = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check_error(lib().kjarni_hip_op_llm_qkv_rope(device, _f(xa), None if ida is None else ida.ctypes.data_as(_ffi._u32p), v(ta),
+                                                 0 if ta is None else ta.shape[0], _f(g), float(eps), v(wa), int(bool(bf16)), _f(b), kk,
+                                                 int(n_heads), int(n_kv_heads), int(head_dim), _f(ca), _f(sa), ca.shape[0], int(pos),
+                                                 int(bool(offset_on_device)), _f(qa), _f(ka), _f(va), ka.shape[0], _f(ro), route))
+    return qa, ka, va, ro, dict(zip(("kernel", "ch", "workgroups"), list(route)))
+
+
 # ---- mixture-of-experts: the router pick and the sparse FFN, alone ----
 def moe_route(logits, k: int, norm_topk: bool = False, device: int = 0):
     """launch_moe_route on host arrays (kjarni_hip_op_moe_route): logits [rows, E] -> (ids int32 [rows, k], weights f32 [rows, k]),
