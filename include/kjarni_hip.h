@@ -642,6 +642,35 @@ void kjarni_hip_decoder_lane_gemv_calls(const KjarniHipDecoder* decoder, uint64_
 /* The lane count kjarni_generator_generate_batch runs with (1..8, 0 = 8, the default). */
 KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* generator, int32_t lanes);
 
+/* ---- wide lanes: up to 64 prompts decoded in lock step on the matrix cores (NOT in the reference) ----
+ * kjarni_hip_decoder_generate_wide is kjarni_hip_decoder_generate_batch with lanes 1..64 (0 = 64).  An effective width
+ * min(lanes, n) of 8 or less runs generate_batch's own step; 9..64 runs every projection of the step as one 64-row tile of the
+ * prompt GEMM (the weights are read once per step whatever the width), the rest being the lanes' kernels.  Results, callback
+ * order, stop rules and lane turnover are generate_batch's.  The lane caches take 2 * layers * lanes * rows * kv_heads *
+ * head_dim * 4 bytes with rows = min(context, lane_context) -- 64 KB per token per lane on the Llama-1B shape -- so set
+ * lane_context.  INVALID_CONFIG before any GPU work: lanes outside 0..64, an empty prompt or one longer than a lane (the
+ * message names its index), more than 16 stop ids, and above 8 lanes a quantized (GGUF) or FP8 checkpoint (the prompt GEMM would
+ * dequantize every matrix in every step) or widths that are no multiples of 32. */
+KjarniErrorCode kjarni_hip_decoder_generate_wide(KjarniHipDecoder* decoder, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                 const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size,
+                                                 int32_t lanes, int32_t lane_context, KjarniBatchTokenCallbackFn on_token, void* user_data,
+                                                 uint32_t* ids_out, size_t capacity, size_t* n_out);
+/* Test hooks of the wide route, as the lane hooks above.  wide_begin takes 9..64 lanes (0 = 64): 8 or fewer are refused, that
+ * width is kjarni_hip_decoder_lanes_begin's. */
+KjarniErrorCode kjarni_hip_decoder_wide_begin(KjarniHipDecoder* decoder, int32_t lanes, int32_t lane_context);
+KjarniErrorCode kjarni_hip_decoder_wide_prefill(KjarniHipDecoder* decoder, int32_t lane, const uint32_t* ids, int32_t n);
+KjarniErrorCode kjarni_hip_decoder_wide_prefill_shared(KjarniHipDecoder* decoder, int32_t lane, int32_t shared, const uint32_t* ids,
+                                                       int32_t n);
+KjarniErrorCode kjarni_hip_decoder_wide_step(KjarniHipDecoder* decoder, const uint32_t* ids, const int32_t* live, float* hidden_out,
+                                             float* logits_out);
+int32_t kjarni_hip_decoder_wide_cache_len(const KjarniHipDecoder* decoder, int32_t lane);
+int32_t kjarni_hip_decoder_wide_capacity(const KjarniHipDecoder* decoder);
+KjarniErrorCode kjarni_hip_decoder_wide_kv_rows(const KjarniHipDecoder* decoder, int32_t lane, int32_t layer, int32_t first, int32_t rows,
+                                                float* k_out, float* v_out);
+/* 1..64: kjarni_generator_generate_batch runs generate_wide with that width; 0 (the default) = off, the lanes path as set by
+ * kjarni_hip_generator_set_lanes. */
+KjarniErrorCode kjarni_hip_generator_set_wide_lanes(KjarniGenerator* generator, int32_t lanes);
+
 /* ---- prompt-lookup speculative decoding (NOT in the reference) ----
  * Greedy generation that emits several tokens per step.  T = the prompt and every token so far; a step drafts the
  * continuation of a match of T's suffix inside T: over every position e (a continuation would start at T[e]) whose
@@ -1039,6 +1068,43 @@ KjarniErrorCode kjarni_hip_op_prefill_gemm(int32_t device, const float* a, int64
 KjarniErrorCode kjarni_hip_op_prefill_attention(int32_t device, const float* q, int64_t ldq, int32_t rows, const float* k, int64_t k_floats,
                                                 int64_t ldk, const float* v, int64_t v_floats, int64_t ldv, int32_t base, int32_t heads,
                                                 int32_t head_dim, int32_t kv_group, float* ctx, int64_t ldc, int32_t* route);
+/* ---- wide lanes: the per-lane kernels of the wide step, alone ---------------------------------------------------------------------
+ * KjarniHipWideState: what the wide step keeps on the device per lane -- the next input token, the position (= the lane's cache
+ * length), live (0: frozen, nothing of the lane is read or written), the picks so far, the picks after which the lane is done,
+ * and its stop ids.  kjarni_hip_wide_state_size() = sizeof of the native struct (a binding checks its mirror against it). */
+#define KJARNI_HIP_WIDE_LANES 64
+#define KJARNI_HIP_LANE_STOPS 16
+typedef struct KjarniHipWideState {
+    int32_t token[KJARNI_HIP_WIDE_LANES];
+    int32_t pos[KJARNI_HIP_WIDE_LANES];
+    int32_t live[KJARNI_HIP_WIDE_LANES];
+    int32_t count[KJARNI_HIP_WIDE_LANES];
+    int32_t limit[KJARNI_HIP_WIDE_LANES];
+    int32_t n_stop[KJARNI_HIP_WIDE_LANES];
+    int32_t stop[KJARNI_HIP_WIDE_LANES][KJARNI_HIP_LANE_STOPS];
+} KjarniHipWideState;
+size_t kjarni_hip_wide_state_size(void);
+/* kjarni_hip_op_wide_rope_scatter: ONE call of launch_wide_rope_scatter (gamma_q and gamma_k NULL) or of
+ * launch_wide_qk_norm_rope_scatter (both given: Qwen3's per-head RMSNorm of Q and K before the rotation).  Row `lane` of qkv
+ * [lanes, ld] holds Q | K | V of the lane's new token: Q is rotated in place at pos[lane]; K is rotated (rotate == 0: copied) and V
+ * copied to row pos[lane] of k_cache / v_cache + lane * lane_stride.  A lane with live == 0 or pos >= capacity writes nothing.
+ * qkv, k_cache and v_cache [lanes, lane_stride] are read and written back whole, each behind a guard band.  cos_t / sin_t
+ * [table_rows, head_dim / 2].  INVALID_CONFIG, before any GPU work and with every output untouched: lanes outside 1..64,
+ * head_dim odd or outside 2..128, n_kv_heads above n_heads, ld short of Q | K | V, lane_stride short of capacity rows, a
+ * negative position, a live position inside the capacity but outside the tables, one gamma without the other, the Qwen3 form
+ * with rotate == 0. */
+KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, float* qkv, int64_t ld, int32_t lanes, int32_t n_heads, int32_t n_kv_heads,
+                                                int32_t head_dim, const float* gamma_q, const float* gamma_k, float eps, const float* cos_t,
+                                                const float* sin_t, int32_t table_rows, float* k_cache, float* v_cache, int64_t lane_stride,
+                                                int32_t capacity, const int32_t* pos, const int32_t* live, int32_t rotate);
+/* kjarni_hip_op_wide_pick: ONE call of launch_wide_pick over lanes [first_lane, first_lane + lanes) of logits
+ * [first_lane + lanes, ld]: for every live lane the argmax (the last maximum wins, +0 == -0, NaN lowest) is appended to
+ * history[lane * hist_stride + count], count (and pos when advance) + 1, live cleared on a stop id, at count == limit or at
+ * pos >= capacity, else token = the pick.  state and history [64, hist_stride] are read and written back whole.
+ * INVALID_CONFIG, before any GPU work and with every output untouched: lanes outside 0..64, ld < vocab, hist_stride < 1,
+ * n_stop outside 0..16, a live lane whose count is no entry of its history. */
+KjarniErrorCode kjarni_hip_op_wide_pick(int32_t device, const float* logits, int64_t ld, int32_t vocab, int32_t lanes, int32_t first_lane,
+                                        KjarniHipWideState* state, int32_t* history, int32_t hist_stride, int32_t capacity, int32_t advance);
 /* ---- mixture-of-experts (qwen3_moe): the router pick and the sparse FFN, alone ------------------------------------------------------
  * kjarni_hip_op_moe_route: softmax over the E router logits of each row, the k largest (on equal logits the lower expert first),
  * with norm_topk the k weights divided by their sum.  logits [rows, E]; ids_out [rows, k] (int32), weights_out [rows, k], slot 0

@@ -249,6 +249,12 @@ class KjarniHipSamplingOptions(Structure):
                 ("seed", c_uint64)]
 
 
+class KjarniHipWideState(Structure):
+    """The wide step's per-lane state (kjarni_hip.h); kjarni_hip_wide_state_size() is the native size."""
+    _fields_ = [("token", c_int32 * 64), ("pos", c_int32 * 64), ("live", c_int32 * 64), ("count", c_int32 * 64), ("limit", c_int32 * 64),
+                ("n_stop", c_int32 * 64), ("stop", (c_int32 * 16) * 64)]
+
+
 class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
@@ -479,6 +485,21 @@ SIGNATURES = {
     "kjarni_hip_decoder_lane_kv_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p]),
     "kjarni_hip_decoder_lane_gemv_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_lanes": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_generate_wide": (c_int32, [c_void_p, _u32p, POINTER(c_size_t), c_size_t, POINTER(c_size_t), c_float, c_int32, c_int32,
+                                                   c_int32, KjarniBatchTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
+    "kjarni_hip_decoder_wide_begin": (c_int32, [c_void_p, c_int32, c_int32]),
+    "kjarni_hip_decoder_wide_prefill": (c_int32, [c_void_p, c_int32, _u32p, c_int32]),
+    "kjarni_hip_decoder_wide_prefill_shared": (c_int32, [c_void_p, c_int32, c_int32, _u32p, c_int32]),
+    "kjarni_hip_decoder_wide_step": (c_int32, [c_void_p, _u32p, POINTER(c_int32), _f32p, _f32p]),
+    "kjarni_hip_decoder_wide_cache_len": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_wide_capacity": (c_int32, [c_void_p]),
+    "kjarni_hip_decoder_wide_kv_rows": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p]),
+    "kjarni_hip_generator_set_wide_lanes": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_wide_state_size": (c_size_t, []),
+    "kjarni_hip_op_wide_rope_scatter": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p, c_float, _f32p,
+                                                  _f32p, c_int32, _f32p, _f32p, c_int64, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32]),
+    "kjarni_hip_op_wide_pick": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, POINTER(KjarniHipWideState), POINTER(c_int32),
+                                          c_int32, c_int32, c_int32]),
     "kjarni_hip_lookup_config_default": (KjarniHipLookupConfig, []),
     "kjarni_hip_decoder_generate_lookup": (c_int32, [c_void_p, _u32p, c_size_t, c_size_t, _u32p, c_size_t, POINTER(KjarniHipLookupConfig),
                                                      KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),

@@ -803,10 +803,12 @@ std::vector<std::string> Generator::generate_batch(const std::vector<std::string
         reqs[i].prompt = std::move(tokens);
     }
     std::vector<std::string> texts(prompts.size());
-    model_->generate_lanes(reqs, lanes, 0, [&](size_t r, uint32_t id) {
+    const std::function<bool(size_t, uint32_t)> on_token = [&](size_t r, uint32_t id) {
         texts[r] += tokenizer_.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
         return true;
-    });
+    };
+    if (wide_lanes_ > 0) model_->generate_wide(reqs, wide_lanes_, 0, on_token);  // (set_wide_lanes: up to 64, the wide step above 8)
+    else model_->generate_lanes(reqs, lanes, 0, on_token);
     return texts;
 }
 

@@ -167,6 +167,9 @@ public:
     std::vector<std::string> generate_batch(const std::vector<std::string>& prompts, const GenerationOverrides& runtime, int lanes);
     int batch_lanes() const { return batch_lanes_; }
     void set_batch_lanes(int lanes) { batch_lanes_ = lanes; }  // what kjarni_generator_generate_batch runs with (0 = 8)
+    // 1..64: generate_batch runs LlmModel::generate_wide with that width instead of generate_lanes; 0 (the default) = off
+    int wide_lanes() const { return wide_lanes_; }
+    void set_wide_lanes(int lanes) { wide_lanes_ = lanes; }
     // Prompt-lookup decoding for generate / stream (0 = off, the default; 1..7 drafted tokens per step): used when the resolved
     // config is greedy without a repetition penalty or an n-gram ban (LlmModel::generate_lookup); generate_batch is untouched.
     void set_prompt_lookup(int draft_tokens) { prompt_lookup_ = draft_tokens; }
@@ -219,7 +222,7 @@ private:
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
     std::mutex mutex_;
-    int batch_lanes_ = 0;
+    int batch_lanes_ = 0, wide_lanes_ = 0;
     int prompt_lookup_ = 0;
     bool lookup_sampling_ = false;
     std::unique_ptr<LlmModel> drafter_;

@@ -783,6 +783,17 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* ge
     return KJARNI_OK;
 }
 
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_wide_lanes(KjarniGenerator* gen, int32_t lanes)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    if (lanes < 0 || lanes > LlmModel::kWideLanes) {
+        set_last_error("wide lanes must be 0..64 (0 = off)");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    gen->inner->set_wide_lanes(lanes);
+    return KJARNI_OK;
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_prompt_lookup(KjarniGenerator* gen, int32_t draft_tokens)
 {
     if (!gen) return KJARNI_ERROR_NULL_POINTER;

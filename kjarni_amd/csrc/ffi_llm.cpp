@@ -151,11 +151,11 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, c
 
 // ---- lanes: up to 8 prompts decoded in lock step -------------------------------------------------------------------------
 
-KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
-                                                                const size_t* max_new_tokens, float repetition_penalty,
-                                                                int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
-                                                                KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
-                                                                size_t capacity, size_t* n_out)
+// generate_batch and generate_wide: the same marshalling, the lanes route (1..8) or the wide entry (1..64)
+static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                         const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t lanes,
+                                         int32_t lane_context, KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                         size_t capacity, size_t* n_out)
 {
     if (!d) return KJARNI_ERROR_NULL_POINTER;
     if (n == 0) return KJARNI_OK;  // nothing to do, nothing written
@@ -163,11 +163,13 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder
     for (size_t i = 0; i < n; ++i) n_out[i] = 0;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        if (lanes < 0 || lanes > LlmModel::kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+        if (wide && (lanes < 0 || lanes > LlmModel::kWideLanes)) throw InvalidConfig("lanes must be 0..64 (0 = 64)");
+        if (!wide && (lanes < 0 || lanes > LlmModel::kLanes)) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
         const int cap = lane_context <= 0 ? d->model->context() : std::min(d->model->context(), (int)lane_context);
         std::vector<LaneRequest> reqs(n);
         for (size_t i = 0; i < n; ++i) {
             if (offsets[i + 1] < offsets[i]) throw InvalidConfig("prompt offsets must not decrease");
+            if (wide && offsets[i + 1] == offsets[i]) throw InvalidConfig("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
             if (offsets[i + 1] - offsets[i] > (size_t)cap)  // before any GPU work
                 throw InvalidConfig("prompt " + std::to_string(i) + " (" + std::to_string(offsets[i + 1] - offsets[i]) +
                                     " tokens) does not fit the lane capacity of " + std::to_string(cap) + " tokens");
@@ -185,11 +187,103 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder
                 t.is_special = false;
                 return on_token(prompt, t, user_data);
             };
-        const std::vector<std::vector<uint32_t>> got = d->model->generate_lanes(reqs, lanes, lane_context, cb);
+        const std::vector<std::vector<uint32_t>> got =
+            wide ? d->model->generate_wide(reqs, lanes, lane_context, cb) : d->model->generate_lanes(reqs, lanes, lane_context, cb);
         for (size_t i = 0; i < n; ++i) {
             n_out[i] = got[i].size();
             if (capacity) std::memcpy(ids_out + i * capacity, got[i].data(), std::min(capacity, got[i].size()) * sizeof(uint32_t));
         }
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_batch(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                                const size_t* max_new_tokens, float repetition_penalty,
+                                                                int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                                KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                size_t capacity, size_t* n_out)
+{
+    return generate_batch_on(d, false, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
+                             on_token, user_data, ids_out, capacity, n_out);
+}
+
+// ---- wide lanes: up to 64 prompts in lock step (LlmModel::generate_wide) ------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_wide(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                               const size_t* max_new_tokens, float repetition_penalty,
+                                                               int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                               KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                               size_t capacity, size_t* n_out)
+{
+    return generate_batch_on(d, true, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
+                             on_token, user_data, ids_out, capacity, n_out);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_begin(KjarniHipDecoder* d, int32_t lanes, int32_t lane_context)
+{
+    if (!d) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (lanes != 0 && (lanes <= LlmModel::kLanes || lanes > LlmModel::kWideLanes))
+            throw InvalidConfig("wide lanes must be 9..64 (0 = 64); 8 or fewer belong to lanes_begin");
+        d->model->wide_begin(lanes, lane_context);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_prefill(KjarniHipDecoder* d, int32_t lane, const uint32_t* ids, int32_t n)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->wide_prefill(lane, ids, n);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_prefill_shared(KjarniHipDecoder* d, int32_t lane, int32_t shared, const uint32_t* ids,
+                                                                     int32_t n)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->wide_prefill_shared(lane, shared, ids, n);  // ranges checked before any GPU work
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_step(KjarniHipDecoder* d, const uint32_t* ids, const int32_t* live, float* hidden_out,
+                                                           float* logits_out)
+{
+    if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->wide_step(ids, live, hidden_out, logits_out);
+    });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_wide_cache_len(const KjarniHipDecoder* d, int32_t lane)
+{
+    if (!d) return -1;
+    std::lock_guard<std::mutex> lock(d->mu);
+    try {
+        return d->model->wide_cache_len(lane);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_wide_capacity(const KjarniHipDecoder* d)
+{
+    if (!d) return 0;
+    std::lock_guard<std::mutex> lock(d->mu);
+    return d->model->wide_capacity();
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_kv_rows(const KjarniHipDecoder* d, int32_t lane, int32_t layer, int32_t first, int32_t rows,
+                                                              float* k_out, float* v_out)
+{
+    if (!d || !k_out || !v_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        std::lock_guard<std::mutex> lock(d->mu);
+        d->model->wide_kv_rows(lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
     });
 }
 

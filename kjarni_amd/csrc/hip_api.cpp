@@ -2096,6 +2096,106 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_qkv_rope(int32_t device, const f
     });
 }
 
+// ---- wide lanes: the rotate-and-scatter launchers and the pick alone ------------------------------------------------------------
+
+static_assert(sizeof(KjarniHipWideState) == sizeof(LlmWideState) && KJARNI_HIP_WIDE_LANES == kMaxWideLanes &&
+                  KJARNI_HIP_LANE_STOPS == kMaxLaneStops, "the header's wide state is the kernels'");
+
+KJARNI_EXPORT size_t kjarni_hip_wide_state_size(void) { return sizeof(LlmWideState); }
+
+// ONE call of launch_wide_rope_scatter (gamma_q / gamma_k NULL) or launch_wide_qk_norm_rope_scatter (both given) on host
+// arrays: qkv [lanes, ld] and k_cache / v_cache [lanes, lane_stride] are read, run and written back whole, each with a guard
+// band behind it, so a caller can check what the call left untouched.  pos / live [lanes]; cos_t / sin_t [table_rows, head_dim / 2].
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, float* qkv, int64_t ld, int32_t lanes, int32_t n_heads,
+                                                              int32_t n_kv_heads, int32_t head_dim, const float* gamma_q, const float* gamma_k,
+                                                              float eps, const float* cos_t, const float* sin_t, int32_t table_rows,
+                                                              float* k_cache, float* v_cache, int64_t lane_stride, int32_t capacity,
+                                                              const int32_t* pos, const int32_t* live, int32_t rotate)
+{
+    if (!qkv || !cos_t || !sin_t || !k_cache || !v_cache || !pos || !live) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!gamma_q != !gamma_k) throw InvalidConfig("gamma_q and gamma_k go together (both: the Qwen3 form, neither: the plain form)");
+        if (gamma_q && !rotate) throw InvalidConfig("the Qwen3 form always rotates: rotate must be 1 with gamma_q / gamma_k");
+        if (lanes < 1 || lanes > kMaxWideLanes) throw InvalidConfig("lanes must be 1..64");
+        if (head_dim < 2 || head_dim > 128 || (head_dim & 1) || n_heads < 1 || n_heads > 256 || n_kv_heads < 1 || n_kv_heads > n_heads)
+            throw InvalidConfig("invalid head geometry (head_dim even, 2..128; n_heads 1..256; n_kv_heads 1..n_heads)");
+        const int64_t kv = (int64_t)n_kv_heads * head_dim, width = (int64_t)n_heads * head_dim + 2 * kv;
+        if (ld < width || ld > ((int64_t)1 << 20)) throw InvalidConfig("ld does not cover Q | K | V (or exceeds 2^20)");
+        if (capacity < 1 || capacity > (1 << 16) || lane_stride < (int64_t)capacity * kv || lane_stride > ((int64_t)1 << 24))
+            throw InvalidConfig("capacity 1..2^16 rows, lane_stride at least capacity * kv floats and at most 2^24");
+        if (table_rows < 1 || table_rows > (1 << 20)) throw InvalidConfig("table_rows must be 1..2^20");
+        for (int32_t l = 0; l < lanes; ++l) {
+            if (pos[l] < 0) throw InvalidConfig("pos[" + std::to_string(l) + "] is negative");
+            if (live[l] && pos[l] < capacity && pos[l] >= table_rows)
+                throw InvalidConfig("pos[" + std::to_string(l) + "] = " + std::to_string(pos[l]) + " is outside the RoPE tables");
+        }
+        use_device(device);
+        const size_t qb = (size_t)lanes * (size_t)ld * 4, cb = (size_t)lanes * (size_t)lane_stride * 4, tb = (size_t)table_rows * (head_dim / 2) * 4;
+        LlmWideState st = {};
+        for (int32_t l = 0; l < lanes; ++l) {
+            st.pos[l] = pos[l];
+            st.live[l] = live[l] ? 1 : 0;
+        }
+        const auto sd = upload(&st, sizeof(st), "H2D state");
+        const auto cd = upload(cos_t, tb, "H2D cos"), snd = upload(sin_t, tb, "H2D sin");
+        const auto gq = upload(gamma_q, gamma_q ? (size_t)head_dim * 4 : 0, "H2D gamma_q"), gk = upload(gamma_k, gamma_k ? (size_t)head_dim * 4 : 0, "H2D gamma_k");
+        GuardedBuf qd(qb), kd(cb), vd(cb);
+        hip_check(hipMemcpy(qd.buf.p, qkv, qb, hipMemcpyHostToDevice), "H2D qkv");
+        hip_check(hipMemcpy(kd.buf.p, k_cache, cb, hipMemcpyHostToDevice), "H2D k_cache");
+        hip_check(hipMemcpy(vd.buf.p, v_cache, cb, hipMemcpyHostToDevice), "H2D v_cache");
+        const LlmWideState* ds = static_cast<const LlmWideState*>(sd->p);
+        if (gamma_q)
+            launcher_check(launch_wide_qk_norm_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(gq->p),
+                                                            static_cast<const float*>(gk->p), eps, static_cast<const float*>(cd->p),
+                                                            static_cast<const float*>(snd->p), kd.as<float>(), vd.as<float>(), lane_stride, capacity,
+                                                            ds, nullptr), "wide head norm + rotate + scatter");
+        else
+            launcher_check(launch_wide_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(cd->p),
+                                                    static_cast<const float*>(snd->p), kd.as<float>(), vd.as<float>(), lane_stride, capacity, ds,
+                                                    rotate ? 1 : 0, nullptr), "wide rotate + scatter");
+        hip_check(hipDeviceSynchronize(), "sync");
+        qd.check("qkv"); kd.check("k_cache"); vd.check("v_cache");
+        hip_check(hipMemcpy(qkv, qd.buf.p, qb, hipMemcpyDeviceToHost), "D2H qkv");
+        hip_check(hipMemcpy(k_cache, kd.buf.p, cb, hipMemcpyDeviceToHost), "D2H k_cache");
+        hip_check(hipMemcpy(v_cache, vd.buf.p, cb, hipMemcpyDeviceToHost), "D2H v_cache");
+    });
+}
+
+// ONE call of launch_wide_pick on host arrays: logits [first_lane + lanes, ld], the state and history [64, hist_stride] read,
+// picked over lanes [first_lane, first_lane + lanes) and written back whole; the scratch must come back zeroed.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_pick(int32_t device, const float* logits, int64_t ld, int32_t vocab, int32_t lanes,
+                                                      int32_t first_lane, KjarniHipWideState* state, int32_t* history, int32_t hist_stride,
+                                                      int32_t capacity, int32_t advance)
+{
+    if (!logits || !state || !history) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (lanes < 1 || first_lane < 0 || first_lane > kMaxWideLanes - lanes) throw InvalidConfig("lanes [first_lane, first_lane + lanes) must lie in 0..64");
+        if (vocab < 1 || ld < vocab || ld > (1 << 20)) throw InvalidConfig("vocab >= 1, vocab <= ld <= 2^20");
+        if (hist_stride < 1 || hist_stride > (1 << 16) || capacity < 0) throw InvalidConfig("hist_stride 1..2^16, capacity >= 0");
+        for (int l = first_lane; l < first_lane + lanes; ++l) {
+            if (state->n_stop[l] < 0 || state->n_stop[l] > kMaxLaneStops) throw InvalidConfig("n_stop[" + std::to_string(l) + "] must be 0..16");
+            if (state->live[l] && (state->count[l] < 0 || state->count[l] >= hist_stride))
+                throw InvalidConfig("count[" + std::to_string(l) + "] is no entry of the lane's history");
+        }
+        use_device(device);
+        const size_t lb = (size_t)(first_lane + lanes) * (size_t)ld * 4, hb = (size_t)kMaxWideLanes * (size_t)hist_stride * 4;
+        const auto dl = upload(logits, lb, "H2D logits");
+        GuardedBuf sd(sizeof(LlmWideState)), hd(hb), best(kMaxWideLanes * sizeof(unsigned long long));
+        hip_check(hipMemcpy(sd.buf.p, state, sizeof(LlmWideState), hipMemcpyHostToDevice), "H2D state");
+        hip_check(hipMemcpy(hd.buf.p, history, hb, hipMemcpyHostToDevice), "H2D history");
+        hip_check(hipMemset(best.buf.p, 0, kMaxWideLanes * sizeof(unsigned long long)), "memset");
+        launcher_check(launch_wide_pick(static_cast<const float*>(dl->p), ld, vocab, lanes, first_lane, best.as<unsigned long long>(),
+                                        sd.as<LlmWideState>(), hd.as<int32_t>(), hist_stride, capacity, advance ? 1 : 0, nullptr), "wide pick");
+        hip_check(hipDeviceSynchronize(), "sync");
+        sd.check("wide state"); hd.check("wide history"); best.check("wide pick scratch");
+        unsigned long long b[kMaxWideLanes];
+        hip_check(hipMemcpy(b, best.buf.p, sizeof(b), hipMemcpyDeviceToHost), "D2H best");
+        for (int i = 0; i < kMaxWideLanes; ++i) expect(b[i] == 0ull, "the wide pick left its accumulator non-zero");
+        hip_check(hipMemcpy(state, sd.buf.p, sizeof(LlmWideState), hipMemcpyDeviceToHost), "D2H state");
+        hip_check(hipMemcpy(history, hd.buf.p, hb, hipMemcpyDeviceToHost), "D2H history");
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_qembed(int32_t device, const uint32_t* ids, int32_t n_ids, const void* blocks, int32_t ggml_type,
                                                    int32_t vocab, int32_t k, float* out)
 {

@@ -244,6 +244,7 @@ LlmModel::~LlmModel()
     if (graph_) (void)hipGraphExecDestroy(graph_);
     if (cgraph_) (void)hipGraphExecDestroy(cgraph_);
     drop_graphs(lane_graphs_);
+    drop_graphs(wide_graphs_);
     drop_graphs(lookup_graphs_);
     drop_graphs(lookup_sampled_graphs_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -1849,17 +1850,23 @@ void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
     if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
     if (base < 0 || (int64_t)base + n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
     const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    const size_t off = (size_t)lane * lane_alloc_cap_ * kv;
+    prefill_into(lane_k_, lane_v_, (size_t)lane * lane_alloc_cap_ * kv, lane_cap_, lane_logits_ + (size_t)lane * cfg_.vocab, base, ids, n);
+    lane_len_[lane] = base + n;
+}
+
+void LlmModel::prefill_into(const std::vector<float*>& k, const std::vector<float*>& v, size_t off, int cap, float* logits_row, int base,
+                            const uint32_t* ids, int n)
+{
     std::vector<std::pair<float*, float*>> saved(layers_.size());
     const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
     const size_t saved_resident = resident_.size();
     for (size_t i = 0; i < layers_.size(); ++i) {
         saved[i] = {layers_[i].k_cache, layers_[i].v_cache};
-        layers_[i].k_cache = lane_k_[i] + off;
-        layers_[i].v_cache = lane_v_[i] + off;
+        layers_[i].k_cache = k[i] + off;
+        layers_[i].v_cache = v[i] + off;
     }
     cache_len_ = base;
-    cache_cap_ = lane_cap_;
+    cache_cap_ = cap;
     auto restore = [&] {
         for (size_t i = 0; i < layers_.size(); ++i) {
             layers_[i].k_cache = saved[i].first;
@@ -1872,8 +1879,7 @@ void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
     };
     try {
         forward(ids, n);
-        hip_check(hipMemcpyAsync(lane_logits_ + (size_t)lane * cfg_.vocab, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice,
-                                 stream_), "D2D logits");
+        hip_check(hipMemcpyAsync(logits_row, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice, stream_), "D2D logits");
         // (forward left the lane's length in pos_: the single-sequence cache's own length goes back)
         hip_check(hipMemcpyAsync(pos_, &saved_len, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
         hip_check(hipStreamSynchronize(stream_), "sync");
@@ -1884,7 +1890,6 @@ void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
         throw;
     }
     restore();
-    lane_len_[lane] = base + n;
 }
 
 // One lock-step step: pass()'s stages with one row per lane.  Its own first half of the layer -- Q | K | V of every lane into the
@@ -1988,11 +1993,50 @@ hipGraphExec_t LlmModel::lane_step_graph(int n)
 std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
                                                             const std::function<bool(size_t, uint32_t)>& on_token)
 {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
     if (lanes == 0) lanes = kLanes;
     if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
+    return generate_on_lanes(reqs, lanes, lane_context, on_token, false, false);
+}
+
+// The 8-lane set as the scheduling loop sees it: the enqueue functions are the launches generate_lanes has always made.
+LlmModel::LaneSet LlmModel::lane_set()
+{
+    LlmLaneState& h = *lane_host_;
+    LaneSet S;
+    S.token = h.token; S.pos = h.pos; S.live = h.live; S.count = h.count; S.limit = h.limit; S.n_stop = h.n_stop; S.stop = h.stop;
+    S.len = lane_len_;
+    S.hist_stride = lane_hist_stride_;
+    S.hist = lane_hist_; S.ptok = lane_ptok_; S.pdistinct = lane_pdistinct_; S.pcounts = lane_pcounts_; S.pndistinct = lane_pndistinct_;
+    S.logits = lane_logits_;
+    S.to_device = [this] { lane_state_to_device(); };
+    S.from_device = [this] { lane_state_from_device(); };
+    S.first_pick = [this](int l) {
+        hip_check(launch_lane_pick(lane_logits_, (int64_t)cfg_.vocab, cfg_.vocab, 1, l, lane_best_, lane_state_, lane_hist_, lane_hist_stride_,
+                                   lane_cap_, 0, stream_), "lane pick");
+    };
+    S.prefill = [this](int l, int shared, const uint32_t* ids, int n) {
+        if (shared >= 1) lane_prefill_shared(l, shared, ids, n);
+        else lane_prefill(l, ids, n);
+    };
+    S.step = [this](int n) { lane_step(n); };
+    S.burst = [this](int n, size_t times) {
+        hipGraphExec_t exec = lane_step_graph(n);
+        for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+    };
+    return S;
+}
+
+std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
+                                                               const std::function<bool(size_t, uint32_t)>& on_token, bool wide, bool strict)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    const char* entry = strict ? "generate_wide" : "generate_lanes";
+    auto refuse = [&](const std::string& what) {  // generate_lanes' own refusals keep their types
+        if (strict) throw InvalidConfig(what);
+        throw std::runtime_error(what);
+    };
     for (const LaneRequest& r : reqs)
-        if (r.options.constraint) throw InvalidConfig("generate_lanes does not take a constraint (generate does)");
+        if (r.options.constraint) throw InvalidConfig(std::string(entry) + " does not take a constraint (generate does)");
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
     std::vector<std::vector<uint32_t>> out(reqs.size());
@@ -2000,18 +2044,20 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     waiting.reserve(reqs.size());
     for (size_t i = 0; i < reqs.size(); ++i) {  // everything is checked before any GPU work
         const LaneRequest& r = reqs[i];
-        if (r.prompt.empty()) throw std::runtime_error("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
+        if (r.prompt.empty()) refuse("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
         if ((int64_t)r.prompt.size() > cap)
             throw InvalidConfig("prompt " + std::to_string(i) + " does not fit the lane capacity of " + std::to_string(cap) + " tokens");
-        if (r.options.sample && !r.options.uniform) throw std::runtime_error("sampling needs a uniform source (prompt " + std::to_string(i) + ")");
+        if (r.options.sample && !r.options.uniform) refuse("sampling needs a uniform source (prompt " + std::to_string(i) + ")");
         waiting.emplace_back(r.prompt, r.options, (size_t)cap, cfg_.eos_ids, out[i]);
-        if ((int)waiting.back().stops.size() > kMaxLaneStops) throw std::runtime_error("more than 16 stop ids (prompt " + std::to_string(i) + ")");
+        if ((int)waiting.back().stops.size() > kMaxLaneStops) refuse("more than 16 stop ids (prompt " + std::to_string(i) + ")");
         slow = slow || r.options.sample || r.options.repetition_penalty != 1.0f || r.options.no_repeat_ngram > 0;
     }
     if (reqs.empty()) return out;
     const int n = (int)std::min<size_t>((size_t)lanes, reqs.size());
-    ensure_lanes(n, lane_context);
-    LlmLaneState& h = *lane_host_;
+    if (wide) ensure_wide(n, lane_context);
+    else ensure_lanes(n, lane_context);
+    const LaneSet S = wide ? wide_set() : lane_set();
+    const LaneSet& h = S;  // (the mirror's fields, as the loop has always named them)
     const size_t vocab = (size_t)cfg_.vocab;
     // Prefix reuse: the prefix every prompt shares (one token short of the shortest prompt, whose last token must be forwarded
     // for its logits) is prefilled once into the single-sequence cache -- where it also stays for the next call -- and copied
@@ -2046,7 +2092,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
         GenerationRun g;
         std::function<bool(uint32_t)> on_token;  // the caller's, bound to the request
     };
-    Run run[kLanes];
+    std::vector<Run> run((size_t)n);
     size_t next_req = 0;
     auto take = [&](int l, uint32_t tok) {  // generate()'s drain
         Run& r = run[l];
@@ -2065,11 +2111,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             r.on_token = nullptr;
             if (on_token) r.on_token = [&on_token, i](uint32_t tok) { return on_token(i, tok); };
             if (shared >= 1) {
-                lane_prefill_shared(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
+                S.prefill(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
                 prefix_reused_ += (uint64_t)shared;
                 prefix_computed_ += q.prompt.size() - (size_t)shared;
             } else {
-                lane_prefill(l, q.prompt.data(), (int)q.prompt.size());
+                S.prefill(l, 0, q.prompt.data(), (int)q.prompt.size());
                 if (prefix_reuse_) prefix_computed_ += q.prompt.size();
             }
             h.token[l] = 0;
@@ -2095,13 +2141,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     if (!slow) {
         // Greedy without processors: every lane's token, position and live flag stay on the device; one graph replay per step,
         // the host looks every few steps (generate()'s cadence).  Tokens a lane computed past its stop are discarded.
-        std::vector<int32_t> hist((size_t)lane_hist_stride_);
         // a lane's first token comes from its prefill's logits row: the lane pick on that row alone
         auto first_pick = [&](int l) {
-            lane_state_to_device();
-            hip_check(launch_lane_pick(lane_logits_, (int64_t)vocab, (int)vocab, 1, l, lane_best_, lane_state_, lane_hist_, lane_hist_stride_,
-                                       lane_cap_, 0, stream_), "lane pick");
-            lane_state_from_device();
+            S.to_device();
+            S.first_pick(l);
+            S.from_device();
         };
         auto drain = [&](size_t steps) {  // step-major, lane order within a step
             std::vector<std::vector<int32_t>> fresh((size_t)n);
@@ -2110,7 +2154,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
                 const size_t have = (size_t)h.count[l];
                 if (r.req < 0 || have <= r.seen) continue;
                 fresh[(size_t)l].resize(have - r.seen);
-                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), lane_hist_ + (size_t)l * lane_hist_stride_ + r.seen,
+                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), S.hist + (size_t)l * S.hist_stride + r.seen,
                                          (have - r.seen) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
                 r.seen = have;
             }
@@ -2135,18 +2179,17 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
                     if (!start(l)) break;
                     first_pick(l);  // (writes the whole state, this pass's edits included)
                     dirty = false;
-                    lane_len_[l] = h.pos[l];
+                    S.len[l] = h.pos[l];
                     drain(1);
                     if (!h.live[l]) r.g.done = true;
                 }
             }
             if (!any_running()) break;
-            if (dirty) lane_state_to_device();
-            hipGraphExec_t exec = lane_step_graph(n);
-            for (size_t i = 0; i < burst; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-            lane_state_from_device();
+            if (dirty) S.to_device();
+            S.burst(n, burst);
+            S.from_device();
             for (int l = 0; l < n; ++l)
-                if (run[l].req >= 0) lane_len_[l] = h.pos[l];
+                if (run[l].req >= 0) S.len[l] = h.pos[l];
             drain(burst);
         }
         return out;
@@ -2160,10 +2203,10 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
     std::vector<float> probs;
     std::vector<uint32_t> ids;
     auto pstate = [&](int l, int32_t*& tok, int32_t*& distinct, int*& counts, int*& nd) {
-        tok = lane_ptok_ + (size_t)l * lane_hist_stride_;
-        distinct = lane_pdistinct_ + (size_t)l * lane_hist_stride_;
-        counts = lane_pcounts_ + (size_t)l * vocab;
-        nd = lane_pndistinct_ + l;
+        tok = S.ptok + (size_t)l * S.hist_stride;
+        distinct = S.pdistinct + (size_t)l * S.hist_stride;
+        counts = S.pcounts + (size_t)l * vocab;
+        nd = S.pndistinct + l;
     };
     auto begin_history = [&](int l) {  // the history so far = the prompt
         const Run& r = run[l];
@@ -2182,7 +2225,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
             // the round's step rewrites every row)
             while (!r.g.done) {
                 const GenerateOptions& o = reqs[(size_t)r.req].options;
-                float* row = lane_logits_ + (size_t)l * vocab;
+                float* row = S.logits + (size_t)l * vocab;
                 int32_t *tok, *distinct;
                 int *counts, *nd;
                 pstate(l, tok, distinct, counts, nd);
@@ -2225,16 +2268,264 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
         bool step = false;
         for (int l = 0; l < n; ++l) step = step || h.live[l];
         if (step) {
-            lane_state_to_device();
-            lane_step(n);
+            S.to_device();
+            S.step(n);
             hip_check(hipStreamSynchronize(stream_), "sync");
             for (int l = 0; l < n; ++l)
-                if (h.live[l]) lane_len_[l] = h.pos[l] + 1;
+                if (h.live[l]) S.len[l] = h.pos[l] + 1;
         }
     }
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Wide lanes: 9..64 sequences in lock step.  The lanes' state, staging layout, scatter, ragged attention and pick, with every
+// projection on the prompt GEMM (one 64-row M-tile: the weights are read once per step whatever the width) instead of the
+// 8-row GEMV kernels.  The scheduling loop is generate_on_lanes() above, on wide_set().
+
+void LlmModel::ensure_wide(int lanes, int lane_context)
+{
+    if (lanes <= kLanes || lanes > kWideLanes) throw InvalidConfig("wide lanes must be 9..64 (8 or fewer are the lanes route's)");
+    if (quant_)  // (fp8_ implies quant_)
+        throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
+                            " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
+    const LlmConfig& c = cfg_;
+    const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
+    if (!rows_geometry(c) || !decode_attention_accepts(c.head_dim, splits_, cap, 1, true, true, false))
+        throw InvalidConfig("more than 8 lanes need hidden, heads * head_dim and intermediate_size multiples of 32 and a head_dim that is a "
+                            "multiple of 4 dividing 1024 (8 lanes or fewer run other shapes)");
+    ensure_prompt_workspace();
+    const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim), vocab = (size_t)c.vocab;
+    if (!wide_state_) {
+        wide_state_ = reinterpret_cast<LlmWideState*>(dalloc((sizeof(LlmWideState) + 3) / 4));
+        wide_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kWideLanes));
+        hip_check(hipMemset(wide_best_, 0, sizeof(unsigned long long) * kWideLanes), "memset");
+        wide_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((layers_.size() * sizeof(LlmKvCopyPair) + 3) / 4));
+        wide_host_ = std::make_unique<LlmWideState>();
+    }
+    if (lanes > wide_alloc_ || cap > wide_alloc_cap_) {
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        drop_graphs(wide_graphs_);
+        // one allocation of its own, sized by the width and the rows asked for, replaced when either grows
+        const size_t nl = (size_t)std::max(lanes, wide_alloc_), nc = (size_t)std::max(cap, wide_alloc_cap_), stride = nc + 16;
+        auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
+        const size_t per_cache = pad(nl * nc * kv), qkv = pad(nl * ((size_t)c.q_dim() + 2 * kv)), logits = pad(nl * vocab);
+        const size_t att = pad(decode_attention_scratch_floats((int)nl, c.heads, c.head_dim, splits_)), hist = pad(nl * stride);
+        const size_t floats = 2 * layers_.size() * per_cache + qkv + 2 * logits + att + 3 * hist + pad(nl);
+        void* fresh = arena_.alloc_own(floats * sizeof(float));
+        if (wide_block_) arena_.free_own(wide_block_);
+        wide_block_ = fresh;
+        float* at = static_cast<float*>(fresh);
+        auto take = [&](size_t n) {
+            float* p = at;
+            at += n;
+            return p;
+        };
+        wide_k_.assign(layers_.size(), nullptr);
+        wide_v_.assign(layers_.size(), nullptr);
+        for (size_t i = 0; i < layers_.size(); ++i) {
+            wide_k_[i] = take(per_cache);
+            wide_v_[i] = take(per_cache);
+        }
+        wide_qkv_ = take(qkv);
+        wide_logits_ = take(logits);
+        wide_pcounts_ = reinterpret_cast<int*>(take(logits));
+        wide_att_ = take(att);
+        wide_hist_stride_ = (int)stride;
+        wide_hist_ = reinterpret_cast<int32_t*>(take(hist));
+        wide_ptok_ = reinterpret_cast<int32_t*>(take(hist));
+        wide_pdistinct_ = reinterpret_cast<int32_t*>(take(hist));
+        wide_pndistinct_ = reinterpret_cast<int*>(take(pad(nl)));
+        wide_alloc_ = (int)nl;
+        wide_alloc_cap_ = (int)nc;
+        std::vector<LlmKvCopyPair> pairs(layers_.size());
+        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, wide_k_[i], layers_[i].v_cache, wide_v_[i]};
+        hip_check(hipMemcpy(wide_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
+    }
+    if (cap != wide_cap_) drop_graphs(wide_graphs_);  // (the capacity is an argument of the captured launches)
+    wide_lanes_ = lanes;
+    wide_cap_ = cap;
+    std::memset(wide_host_.get(), 0, sizeof(LlmWideState));
+    std::fill(wide_len_, wide_len_ + kWideLanes, 0);
+    wide_state_to_device();
+}
+
+void LlmModel::wide_state_to_device()
+{
+    hip_check(hipMemcpyAsync(wide_state_, wide_host_.get(), sizeof(LlmWideState), hipMemcpyHostToDevice, stream_), "H2D wide state");
+    hip_check(hipStreamSynchronize(stream_), "sync");  // (the mirror is edited again right away)
+}
+
+void LlmModel::wide_state_from_device()
+{
+    hip_check(hipMemcpyAsync(wide_host_.get(), wide_state_, sizeof(LlmWideState), hipMemcpyDeviceToHost, stream_), "D2H wide state");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+
+void LlmModel::wide_begin(int lanes, int lane_context)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lanes == 0) lanes = kWideLanes;
+    ensure_wide(lanes, lane_context);
+}
+
+void LlmModel::wide_prefill(int lane, const uint32_t* ids, int n) { wide_prefill_at(lane, 0, ids, n); }
+
+void LlmModel::wide_copy_prefix(int lane, int s)
+{
+    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
+    if (s < 0 || s > cache_len_ || s > wide_cap_) throw std::runtime_error("shared prefix out of range");
+    const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
+    hip_check(launch_kv_prefix_copy(wide_copy_table_, (int)layers_.size(), (int64_t)lane * wide_alloc_cap_ * kv, (int64_t)s * kv, stream_),
+              "prefix copy");
+}
+
+void LlmModel::wide_prefill_shared(int lane, int s, const uint32_t* ids, int n)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
+    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
+    if (s < 0 || s > cache_len_) throw std::runtime_error("shared prefix out of range");
+    if ((int64_t)s + n > wide_cap_) throw std::runtime_error("prompt does not fit the lane");
+    wide_copy_prefix(lane, s);
+    wide_prefill_at(lane, s, ids, n);
+}
+
+void LlmModel::wide_prefill_at(int lane, int base, const uint32_t* ids, int n)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
+    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
+    if (base < 0 || (int64_t)base + n > wide_cap_) throw std::runtime_error("prompt does not fit the lane");
+    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
+    prefill_into(wide_k_, wide_v_, (size_t)lane * wide_alloc_cap_ * kv, wide_cap_, wide_logits_ + (size_t)lane * cfg_.vocab, base, ids, n);
+    wide_len_[lane] = base + n;
+}
+
+// One wide step, a linear chain on the model's stream: the embedding at the lanes' positions, per layer norm 1 -> ONE GEMM of
+// the fused [Q;K;V] matrix into the lanes' staging rows -> rotate-and-scatter -> ragged attention -> rows_finish() (o-proj,
+// norm 2, SwiGLU / GPT-2 MLP / the MoE rows hook), then the final norm and the head as a GEMM into wide_logits_.  Frozen lanes
+// ride along as rows of the GEMMs (each output row depends on its own input row only); the scatter and the attention skip them.
+void LlmModel::wide_step_enqueue(int n)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
+    const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
+    const int64_t stride = (int64_t)wide_alloc_cap_ * kv;
+    const LlmWideState* st = wide_state_;
+    embed_rows(reinterpret_cast<const uint32_t*>(st->token), n, ph_, 0, nullptr, st->pos);
+    for (size_t li = 0; li < layers_.size(); ++li) {
+        const Layer& L = layers_[li];
+        if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, n, H, pn_, s), "ln_1");
+        else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, n, H, pn_, s), "rmsnorm 1");
+        prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, wide_qkv_, ldq, ldq, H, nullptr, "q|k|v proj");
+        if (c.qwen3())
+            hip_check(launch_wide_qk_norm_rope_scatter(wide_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, wide_k_[li],
+                                                       wide_v_[li], stride, wide_cap_, st, s), "head norm + rotate + scatter");
+        else
+            hip_check(launch_wide_rope_scatter(wide_qkv_, ldq, n, c.heads, kvh, d, cos_, sin_, wide_k_[li], wide_v_[li], stride, wide_cap_, st,
+                                               gpt2_ ? 0 : 1, s), "rotate + scatter");
+        hip_check(launch_decode_attention(wide_qkv_, ldq, n, wide_k_[li], kv, wide_v_[li], kv, wide_cap_, nullptr, wide_cap_, c.heads, d, -1,
+                                          splits_, wide_att_, pctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
+        rows_finish(n, L);
+    }
+    final_norm(ph_, n, pn_);  // (the norm buffer is free behind the last layer)
+    prompt_proj(n, pn_, H, lm_head_, nullptr, nullptr, wide_logits_, c.vocab, c.vocab, H, nullptr, "lm head");
+}
+
+void LlmModel::wide_pick_enqueue(int lanes, int first, int advance)
+{
+    hip_check(launch_wide_pick(wide_logits_, cfg_.vocab, cfg_.vocab, lanes, first, wide_best_, wide_state_, wide_hist_, wide_hist_stride_,
+                               wide_cap_, advance, stream_), "wide pick");
+}
+
+hipGraphExec_t LlmModel::wide_step_graph(int n)
+{
+    if (wide_graphs_[n]) return wide_graphs_[n];
+    return wide_graphs_[n] = capture_graph(stream_, [&] {
+        wide_step_enqueue(n);
+        wide_pick_enqueue(n, 0, 1);
+    });
+}
+
+void LlmModel::wide_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
+{
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (wide_lanes_ < 1) throw std::runtime_error("wide_begin first");
+    LlmWideState& h = *wide_host_;
+    for (int l = 0; l < wide_lanes_; ++l) {
+        const bool on = live ? live[l] != 0 : true;
+        if (on && wide_len_[l] >= wide_cap_) throw std::runtime_error("lane " + std::to_string(l) + " is full");
+        h.token[l] = (int32_t)ids[l];
+        h.pos[l] = wide_len_[l];
+        h.live[l] = on ? 1 : 0;
+    }
+    wide_state_to_device();
+    wide_step_enqueue(wide_lanes_);
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    for (int l = 0; l < wide_lanes_; ++l)
+        if (h.live[l]) wide_len_[l] += 1;
+    if (hidden_out) hip_check(hipMemcpy(hidden_out, pn_, (size_t)wide_lanes_ * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
+    if (logits_out)
+        hip_check(hipMemcpy(logits_out, wide_logits_, (size_t)wide_lanes_ * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+}
+
+int LlmModel::wide_cache_len(int lane) const
+{
+    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
+    return wide_len_[lane];
+}
+
+void LlmModel::wide_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const
+{
+    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
+    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > wide_len_[lane] || rows > wide_len_[lane] - first)
+        throw std::runtime_error("cache rows out of range");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
+    const size_t off = ((size_t)lane * wide_alloc_cap_ + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
+    hip_check(hipMemcpy(k_out, wide_k_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+    hip_check(hipMemcpy(v_out, wide_v_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+}
+
+LlmModel::LaneSet LlmModel::wide_set()
+{
+    LlmWideState& h = *wide_host_;
+    LaneSet S;
+    S.token = h.token; S.pos = h.pos; S.live = h.live; S.count = h.count; S.limit = h.limit; S.n_stop = h.n_stop; S.stop = h.stop;
+    S.len = wide_len_;
+    S.hist_stride = wide_hist_stride_;
+    S.hist = wide_hist_; S.ptok = wide_ptok_; S.pdistinct = wide_pdistinct_; S.pcounts = wide_pcounts_; S.pndistinct = wide_pndistinct_;
+    S.logits = wide_logits_;
+    S.to_device = [this] { wide_state_to_device(); };
+    S.from_device = [this] { wide_state_from_device(); };
+    S.first_pick = [this](int l) { wide_pick_enqueue(1, l, 0); };
+    S.prefill = [this](int l, int shared, const uint32_t* ids, int n) {
+        if (shared >= 1) wide_prefill_shared(l, shared, ids, n);
+        else wide_prefill(l, ids, n);
+    };
+    S.step = [this](int n) { wide_step_enqueue(n); };
+    S.burst = [this](int n, size_t times) {  // (no stage of the chain reads anything back, the MoE rows hook included: always captured)
+        hipGraphExec_t exec = wide_step_graph(n);
+        for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+        for (const Layer& L : layers_)  // (a replay runs no host code: the routing record's row count is set here)
+            if (L.moe) L.moe_rec_rows = n;
+    };
+    return S;
+}
+
+std::vector<std::vector<uint32_t>> LlmModel::generate_wide(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
+                                                           const std::function<bool(size_t, uint32_t)>& on_token)
+{
+    if (lanes < 0 || lanes > kWideLanes) throw InvalidConfig("lanes must be 0..64 (0 = 64)");
+    if (lanes == 0) lanes = kWideLanes;
+    const size_t width = std::min<size_t>((size_t)lanes, reqs.size());
+    if (width <= (size_t)kLanes)  // generate_lanes' route (its GEMV step), under this entry's refusals
+        return generate_on_lanes(reqs, (int)std::max<size_t>(width, 1), lane_context, on_token, false, true);
+    return generate_on_lanes(reqs, lanes, lane_context, on_token, true, true);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Prompt-lookup decoding: greedy generation that emits several tokens per step.  The draft of a step is the continuation of

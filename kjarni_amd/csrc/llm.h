@@ -60,6 +60,7 @@ struct LaneRequest {
 };
 
 struct LlmLaneState;  // llm_kernels.h
+struct LlmWideState;
 struct ConstraintView;  // constraint_kernels.h
 struct ConstraintRow;
 struct LlmLookupState;
@@ -282,6 +283,28 @@ public:
     uint64_t lane_stream_calls() const { return lane_stream_calls_; }
     uint64_t lane_fallback_calls() const { return lane_fallback_calls_; }
 
+    // ---- wide lanes: 9..kWideLanes sequences in lock step, the projections on the prompt GEMM's 64-row tile ------------------
+    static constexpr int kWideLanes = 64;  // one M-tile of launch_prefill_gemm: every width up to it reads the weights once per step
+    // generate_lanes() for `lanes` (1..64, 0 = 64) requests at a time.  An effective width min(lanes, requests) of 8 or less runs
+    // generate_lanes' own GEMV step; 9..64 runs wide_step(): the rows-route layer body (one Q|K|V GEMM into the lanes' staging
+    // layout, rotate-and-scatter, the ragged decode attention, rows_finish()), the head as a GEMM, the wide pick -- captured once
+    // per (width, lane capacity) for greedy requests without processors.  Results, callback order, stop rules, lane turnover,
+    // prefix reuse and the processors / sampling path are generate_lanes'.  The lane caches cost 2 * layers * lanes * rows * kv
+    // * 4 bytes with rows = min(context(), lane_context): 64 KB per token per lane on the Llama-1B shape (16 layers, kv 512),
+    // 34 GB at 64 lanes of 8 192 rows -- set lane_context.  Throws InvalidConfig (before any GPU work) for lanes outside 0..64, an
+    // empty prompt, a prompt longer than a lane, more than 16 stop ids, a constraint, and -- above 8 lanes -- a quantized or FP8
+    // checkpoint or a geometry the rows route does not take.
+    std::vector<std::vector<uint32_t>> generate_wide(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
+                                                     const std::function<bool(size_t, uint32_t)>& on_token = nullptr);
+    // Test hooks of the wide route, mirroring the lane hooks (wide_begin takes 9..64 lanes: fewer belong to lanes_begin).
+    void wide_begin(int lanes, int lane_context);
+    void wide_prefill(int lane, const uint32_t* ids, int n);
+    void wide_prefill_shared(int lane, int s, const uint32_t* ids, int n);
+    void wide_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
+    int wide_cache_len(int lane) const;
+    int wide_capacity() const { return wide_cap_; }
+    void wide_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
+
     // ---- prompt-lookup decoding: greedy generate() that emits several tokens per step ----------------------------------------
     // generate() for a greedy request without logits processors, with every step verifying a draft: the continuation of the
     // latest longest n-gram match in the prompt + the tokens so far (launch_lookup_draft) runs with the last token as one block
@@ -360,6 +383,41 @@ private:
     hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
     void lane_state_to_device();
     void lane_state_from_device();
+    // A prompt through forward()'s routes into caches other than the single-sequence ones: the layers' cache pointers are
+    // pointed at k[layer] + off / v[layer] + off (capacity cap, `base` rows already there) for the call, the last position's
+    // logits go to logits_row.  lane_prefill_at and wide_prefill_at are this.
+    void prefill_into(const std::vector<float*>& k, const std::vector<float*>& v, size_t off, int cap, float* logits_row, int base,
+                      const uint32_t* ids, int n);
+    // What generate_lanes' scheduling loop needs of a set of lanes: the host mirror of the device state by field (the 8-lane and
+    // the wide state differ in their array lengths only), the lane buffers, and how to enqueue a prefill, a step and a pick.
+    struct LaneSet {
+        int32_t *token, *pos, *live, *count, *limit, *n_stop;
+        int32_t (*stop)[16];
+        int* len;  // the lanes' cache lengths (host)
+        int hist_stride;
+        int32_t *hist, *ptok, *pdistinct;
+        int *pcounts, *pndistinct;
+        float* logits;
+        std::function<void()> to_device, from_device;
+        std::function<void(int lane)> first_pick;  // the pick on the lane's prefill row alone (no advance)
+        std::function<void(int lane, int shared, const uint32_t* ids, int n)> prefill;  // behind `shared` copied prefix rows
+        std::function<void(int n)> step;                                                // one step, enqueued directly
+        std::function<void(int n, size_t times)> burst;  // `times` x (step + pick), replayed from a captured graph where one exists
+    };
+    LaneSet lane_set();
+    LaneSet wide_set();
+    // generate_lanes / generate_wide behind their own checks of `lanes`: n = min(lanes, requests) lanes of the 8-lane set, or of
+    // the wide set when `wide`.  strict: every refusal is an InvalidConfig (generate_wide's contract).
+    std::vector<std::vector<uint32_t>> generate_on_lanes(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
+                                                         const std::function<bool(size_t, uint32_t)>& on_token, bool wide, bool strict);
+    void ensure_wide(int lanes, int lane_context);
+    void wide_prefill_at(int lane, int base, const uint32_t* ids, int n);
+    void wide_copy_prefix(int lane, int s);
+    void wide_step_enqueue(int lanes);            // one wide step over lanes [0, lanes), logits into wide_logits_
+    void wide_pick_enqueue(int lanes, int first, int advance);
+    hipGraphExec_t wide_step_graph(int lanes);    // wide step + pick, captured once per (width, lane capacity)
+    void wide_state_to_device();
+    void wide_state_from_device();
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
@@ -597,6 +655,22 @@ private:
     int *lane_pcounts_ = nullptr, *lane_pndistinct_ = nullptr;
     hipGraphExec_t lane_graphs_[kLanes + 1] = {};
     uint64_t lane_stream_calls_ = 0, lane_fallback_calls_ = 0;
+    // wide lanes (allocated on first use, sized by the width asked for): one allocation of its own holds the lane-major caches
+    // of every layer, the staging rows, the logits rows, the attention scratch, the pick history and the processors' per-lane
+    // history / distinct list / counts; the state (device + host mirror), the pick scratch and the prefix-copy table are fixed
+    std::vector<float*> wide_k_, wide_v_;
+    void* wide_block_ = nullptr;
+    int wide_alloc_ = 0, wide_alloc_cap_ = 0, wide_lanes_ = 0, wide_cap_ = 0, wide_hist_stride_ = 0;
+    int wide_len_[kWideLanes] = {};
+    float *wide_qkv_ = nullptr, *wide_logits_ = nullptr, *wide_att_ = nullptr;
+    LlmWideState* wide_state_ = nullptr;
+    std::unique_ptr<LlmWideState> wide_host_;
+    int32_t* wide_hist_ = nullptr;
+    unsigned long long* wide_best_ = nullptr;
+    int32_t *wide_ptok_ = nullptr, *wide_pdistinct_ = nullptr;
+    int *wide_pcounts_ = nullptr, *wide_pndistinct_ = nullptr;
+    LlmKvCopyPair* wide_copy_table_ = nullptr;
+    hipGraphExec_t wide_graphs_[kWideLanes + 1] = {};
     // prompt-lookup decoding (allocated on first use): the ids and logits rows of a verify step, the device state, the history
     // (prompt + picks), the per-step (m, a) log, and one captured chain per row count for the n-gram bounds in lookup_ngram_
     float* vlogits_ = nullptr;

@@ -174,6 +174,32 @@ struct LlmKvCopyPair {
 };
 hipError_t launch_kv_prefix_copy(const LlmKvCopyPair* table, int layers, int64_t dst_offset, int64_t count, hipStream_t stream);
 
+// ---- wide lanes: 9..kMaxWideLanes sequences in lock step, the projections on the prompt GEMM (LlmModel::generate_wide) -------
+constexpr int kMaxWideLanes = 64;  // one M-tile of the prompt GEMM: every width up to it streams the weights once per step
+// LlmLaneState for kMaxWideLanes lanes (same fields, same meaning).
+struct LlmWideState {
+    int32_t token[kMaxWideLanes];
+    int32_t pos[kMaxWideLanes];
+    int32_t live[kMaxWideLanes];
+    int32_t count[kMaxWideLanes];
+    int32_t limit[kMaxWideLanes];
+    int32_t n_stop[kMaxWideLanes];
+    int32_t stop[kMaxWideLanes][kMaxLaneStops];
+};
+// launch_lane_rope_scatter / launch_lane_qk_norm_rope_scatter over an LlmWideState: the same two kernels (they take the position
+// and live arrays, a workgroup per lane), for up to kMaxWideLanes lanes.
+hipError_t launch_wide_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
+                                    const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
+                                    const LlmWideState* state, int rotate, hipStream_t stream);
+hipError_t launch_wide_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
+                                            const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
+                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmWideState* state,
+                                            hipStream_t stream);
+// launch_lane_pick over an LlmWideState: argmax_partial_kernel over rows [first_lane, first_lane + lanes) of logits
+// [kMaxWideLanes, ld], then the wide finalize.  best_scratch: kMaxWideLanes zero-initialised u64 (re-zeroed by the call).
+hipError_t launch_wide_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
+                            LlmWideState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
+
 // ---- prompt-lookup decoding (LlmModel::generate_lookup): draft from the sequence's own history, verify in one multi-row step
 constexpr int kLookupMaxDraft = 7, kLookupMaxNgram = 4;
 struct LlmLookupState {

@@ -230,10 +230,14 @@ class HipDecoder:
         """generate() for every prompt, up to `lanes` (1..8, 0 = 8) of them at a time, each in a KV cache of `lane_context` rows
         (<= 0: the decoder's context).  max_new_tokens: one int for all prompts, or one per prompt.  on_token(prompt index, token)
         is called in step order, lane order within a step; returning False ends that prompt only."""
+        return self._generate_many(lib().kjarni_hip_decoder_generate_batch, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram, lanes,
+                                   lane_context, on_token)
+
+    def _generate_many(self, entry, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram, lanes, lane_context, on_token):
         n = len(prompts)
         if n == 0:
-            check_error(lib().kjarni_hip_decoder_generate_batch(self._h, None, None, 0, None, repetition_penalty, no_repeat_ngram, lanes,
-                                                                lane_context, _ffi.KjarniBatchTokenCallbackFn(), None, None, 0, None))
+            check_error(entry(self._h, None, None, 0, None, repetition_penalty, no_repeat_ngram, lanes,
+                              lane_context, _ffi.KjarniBatchTokenCallbackFn(), None, None, 0, None))
             return []
         new = [int(max_new_tokens)] * n if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
         if len(new) != n:
@@ -251,10 +255,67 @@ class HipDecoder:
             r = on_token(int(i), int(t.token_id))
             return True if r is None else bool(r)
         fn = _ffi.KjarniBatchTokenCallbackFn(cb) if on_token else _ffi.KjarniBatchTokenCallbackFn()
-        check_error(lib().kjarni_hip_decoder_generate_batch(self._h, flat.ctypes.data_as(C.POINTER(C.c_uint32)), offsets, n, news,
-                                                            repetition_penalty, no_repeat_ngram, lanes, lane_context, fn, None,
-                                                            out.ctypes.data_as(C.POINTER(C.c_uint32)), cap, n_out))
+        check_error(entry(self._h, flat.ctypes.data_as(C.POINTER(C.c_uint32)), offsets, n, news,
+                          repetition_penalty, no_repeat_ngram, lanes, lane_context, fn, None,
+                          out.ctypes.data_as(C.POINTER(C.c_uint32)), cap, n_out))
         return [out[i, :min(int(n_out[i]), cap)].tolist() for i in range(n)]
+
+    # ---- wide lanes: up to 64 prompts decoded in lock step, the projections on the matrix cores ----
+    def generate_wide(self, prompts: Sequence[Sequence[int]], max_new_tokens, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0,
+                      lanes: int = 0, lane_context: int = 0,
+                      on_token: Optional[Callable[[int, int], Optional[bool]]] = None) -> List[List[int]]:
+        """generate_batch() with up to `lanes` (1..64, 0 = 64) prompts at a time.  An effective width min(lanes, len(prompts)) of 8
+        or less runs generate_batch's own step; 9..64 runs the wide step (f32 / bf16 safetensors checkpoints).  The lane caches
+        take 2 * layers * lanes * rows * kv * 4 bytes with rows = min(context, lane_context): set lane_context."""
+        return self._generate_many(lib().kjarni_hip_decoder_generate_wide, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram, lanes,
+                                   lane_context, on_token)
+
+    def wide_begin(self, lanes: int = 0, lane_context: int = 0):
+        """Test hook: empty wide-lane caches for `lanes` (9..64, 0 = 64) lanes of `lane_context` rows each."""
+        check_error(lib().kjarni_hip_decoder_wide_begin(self._h, lanes, lane_context))
+        self._wide_lanes = lanes or 64
+
+    def wide_prefill(self, lane: int, ids: Sequence[int]):
+        a = np.ascontiguousarray(ids, np.uint32)
+        check_error(lib().kjarni_hip_decoder_wide_prefill(self._h, lane, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def wide_prefill_shared(self, lane: int, shared: int, ids: Sequence[int]):
+        a = np.ascontiguousarray(ids, np.uint32)
+        check_error(lib().kjarni_hip_decoder_wide_prefill_shared(self._h, lane, int(shared), a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size))
+
+    def wide_step(self, ids: Sequence[int], live: Optional[Sequence[int]] = None):
+        """One wide step: lane l appends ids[l] where live[l] (default: every lane).  Returns the final-normed hidden rows
+        [lanes, hidden] and the logits [lanes, vocab]; the rows of frozen lanes are unspecified."""
+        a = np.ascontiguousarray(ids, np.uint32)
+        if a.size != getattr(self, "_wide_lanes", 0):
+            raise ValueError("one id per lane (after wide_begin)")
+        lv = np.ascontiguousarray(live, np.int32) if live is not None else None
+        if lv is not None and lv.size != a.size:
+            raise ValueError("one live flag per lane")
+        hidden = np.empty((a.size, self.hidden), np.float32)
+        logits = np.empty((a.size, self.vocab), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_wide_step(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       lv.ctypes.data_as(C.POINTER(C.c_int32)) if lv is not None else None, f(hidden), f(logits)))
+        return hidden, logits
+
+    def wide_cache_len(self, lane: int) -> int:
+        return int(lib().kjarni_hip_decoder_wide_cache_len(self._h, lane))
+
+    def wide_capacity(self) -> int:
+        return int(lib().kjarni_hip_decoder_wide_capacity(self._h))
+
+    def wide_kv_rows(self, lane: int, layer: int, first: int = 0, rows: Optional[int] = None):
+        """kv_rows() of one wide lane's cache."""
+        if rows is None:
+            rows = self.wide_cache_len(lane) - first
+        if rows < 0:
+            raise ValueError("first is past the end of the lane's cache")
+        kv = self.kv_heads * self.head_dim
+        k, v = np.empty((rows, kv), np.float32), np.empty((rows, kv), np.float32)
+        f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_wide_kv_rows(self._h, lane, layer, first, rows, f(k), f(v)))
+        return k, v
 
     def lanes_begin(self, lanes: int = 0, lane_context: int = 0):
         """Test hook: empty lane caches for `lanes` lanes of `lane_context` rows each."""

@@ -96,6 +96,11 @@ class Generator:
         """Lanes generate_batch() runs with (1..8, 0 = 8)."""
         check_error(lib().kjarni_hip_generator_set_lanes(self._handle, lanes))
 
+    def set_wide_lanes(self, lanes: int):
+        """1..64: generate_batch() runs the decoder's generate_wide with that width (the wide step above 8 lanes, f32 / bf16
+        safetensors checkpoints); 0 (the default) = off, the lanes path as set by set_lanes()."""
+        check_error(lib().kjarni_hip_generator_set_wide_lanes(self._handle, lanes))
+
     def set_prompt_lookup(self, draft_tokens: int):
         """Prompt-lookup decoding for generate() / stream(): 0 = off (the default), 1..7 drafted tokens per step.  Applies to
         greedy configs without a repetition penalty or an n-gram ban; the text is the plain path's."""

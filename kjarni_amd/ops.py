@@ -949,3 +949,43 @@ def score_head_topk(hidden, W, targets, top_k, bf16=False, slab_tiles=0, fused=T
     check_error(lib().kjarni_hip_op_score_head_topk(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab,
                                                     u32(targets), slab_tiles, 1 if fused else 0, int(top_k), f(lp), u32(tid), f(tlp), f(lse)))
     return lp, tid, tlp, lse
+
+
+def wide_rope_scatter(qkv, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, sin_t, k_cache, v_cache, capacity: int, pos, live,
+                      rotate: bool = True, gamma_q=None, gamma_k=None, eps: float = 0.0, device: int = 0):
+    """One launch_wide_rope_scatter (gamma_q / gamma_k given: launch_wide_qk_norm_rope_scatter, the Qwen3 form) on host arrays
+    (kjarni_hip_op_wide_rope_scatter).  qkv [lanes, ld] holds Q | K | V of each lane's new token; k_cache / v_cache
+    [lanes, lane rows, kv] (lane rows >= capacity).  Returns copies (qkv, k_cache, v_cache) after the call: Q rotated in place,
+    K rotated (rotate False: copied) and V copied to row pos[lane] of the lane's caches, nothing for a lane with live == 0 or
+    pos >= capacity."""
+    q = np.array(qkv, np.float32, order="C")
+    kc, vc = np.array(k_cache, np.float32, order="C"), np.array(v_cache, np.float32, order="C")
+    if q.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.shape[0] != q.shape[0]:
+        raise ValueError("qkv [lanes, ld]; k_cache and v_cache [lanes, lane rows, kv]")
+    lanes = q.shape[0]
+    ps, lv = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(live, np.int32)
+    ct, st = _c(cos_t), _c(sin_t)
+    if ps.size != lanes or lv.size != lanes or ct.shape != st.shape or ct.ndim != 2:
+        raise ValueError("pos / live [lanes]; cos_t / sin_t [table rows, head_dim / 2]")
+    gq, gk = _c(gamma_q), _c(gamma_k)
+    check_error(lib().kjarni_hip_op_wide_rope_scatter(device, _f(q), q.shape[1], lanes, int(n_heads), int(n_kv_heads), int(head_dim), _f(gq),
+                                                      _f(gk), float(eps), _f(ct), _f(st), ct.shape[0], _f(kc), _f(vc),
+                                                      kc.shape[1] * kc.shape[2], int(capacity), ps.ctypes.data_as(_i32p),
+                                                      lv.ctypes.data_as(_i32p), int(bool(rotate))))
+    return q, kc, vc
+
+
+def wide_pick(logits, state: "_ffi.KjarniHipWideState", history, capacity: int, lanes: Optional[int] = None, first_lane: int = 0,
+              advance: bool = True, vocab: Optional[int] = None, device: int = 0):
+    """One launch_wide_pick (kjarni_hip_op_wide_pick) over lanes [first_lane, first_lane + lanes) of logits [rows, ld]: `state` is
+    updated in place; returns the history [64, stride] after the call (a copy)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    hist = np.array(history, np.int32, order="C")
+    if lg.ndim != 2 or hist.ndim != 2 or hist.shape[0] != 64:
+        raise ValueError("logits [rows, ld]; history [64, stride]")
+    lanes = lg.shape[0] - first_lane if lanes is None else int(lanes)
+    if first_lane < 0 or lanes < 0 or first_lane + lanes > lg.shape[0]:
+        raise ValueError("logits must hold rows [0, first_lane + lanes)")
+    check_error(lib().kjarni_hip_op_wide_pick(device, _f(lg), lg.shape[1], lg.shape[1] if vocab is None else int(vocab), lanes, int(first_lane),
+                                              C.byref(state), hist.ctypes.data_as(_i32p), hist.shape[1], int(capacity), int(bool(advance))))
+    return hist

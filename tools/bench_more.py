@@ -22,6 +22,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            the single-stream generate() of the same build, alternated twice in one process: Llama-3.2-1B shape (bf16),
            gpt2-small (bf16, f32) and the 1B shape as a GGUF Q4_K_M-style mix; 128-token prompts; aggregate tokens/s and
            ms per lock-step step.  KJARNI_LANES_STEPS=N: N steps at 8 lanes on the Llama shape only (for a kernel trace).
+  llm_wide   (only on request) wide lanes: generate_wide at 16 / 32 / 64 prompts in lock step against single-stream generate()
+           and generate_batch at 8 lanes of the same build (the baselines), twice in one process: Llama-3.2-1B shape (bf16) and
+           gpt2-small (bf16); 128-token prompts, 128 new tokens, lane_context 512; aggregate tokens/s and ms per step.
+           KJARNI_WIDE_STEPS=N: N steps at 64 lanes on the Llama shape only (for a kernel trace).
   llm_lookup  (only on request) prompt-lookup decoding against plain generate() of the same build, alternated twice in one
            process: Llama-3.2-1B shape (bf16) and gpt2-small (bf16); ms per plain step, ms per verify step at 2 / 4 / 8 rows
            (HipDecoder.verify_step in a loop with a fixed draft, and the replayed graph inside generate_lookup), the break-even
@@ -910,6 +914,66 @@ def main():
             gguf_fixture.gguf_model(gpath, qcfg, gguf_fixture.q4_k_m_types(qcfg["num_hidden_layers"]), seed=0, rope_freqs=True, keep_hf=False)
             dec = kjarni_amd.HipDecoder(gpath, max_context=2048)
             measure("Llama-3.2-1B shape, GGUF Q4_K_M-style mix (Q4_K / Q6_K in HBM)", dec, prompts, 512, "Q4_K / Q6_K weights, f32 activations/KV")
+            del dec
+
+    if "llm_wide" in which:
+        # Method (as llm_lanes): one process on one box; every leg is warmed first (graph capture, lane caches); a decode window is
+        # a whole call minus the same call cut after its first token (the prefills and the first pick), so it holds n_new - 1
+        # lock-step steps.  Legs, twice over: single-stream generate() and generate_batch at 8 lanes -- both code from before the
+        # wide route, the baselines -- then generate_wide at 16 / 32 / 64 lanes.  One 128-token prompt per lane, 128 new tokens,
+        # lane_context 512.
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        trace_steps = int(os.environ.get("KJARNI_WIDE_STEPS", "0"))
+        n_new, ctx = 128, 512
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure_wide(label, dec, prompts, dtype):
+            if trace_steps:  # a short run for rocprofv3 --kernel-trace --stats: 64 lanes, trace_steps wide steps
+                dec.generate_wide(prompts, trace_steps + 1, lanes=64, lane_context=ctx)
+                return
+            legs = {"single": lambda n: [dec.generate(prompts[0], n)],
+                    "lanes-8": lambda n: dec.generate_batch(prompts[:8], n, lanes=8, lane_context=ctx)}
+            for w in (16, 32, 64):
+                legs[f"wide-{w}"] = (lambda w: lambda n: dec.generate_wide(prompts[:w], n, lanes=w, lane_context=ctx))(w)
+            width = {"single": 1, "lanes-8": 8, "wide-16": 16, "wide-32": 32, "wide-64": 64}
+            for fn in legs.values():
+                fn(20)
+            rows = {}
+            for rep in range(2):
+                for name, fn in legs.items():
+                    dt, outs = window(lambda: fn(n_new), lambda: fn(1))
+                    assert all(len(o) == n_new for o in outs)
+                    rows.setdefault(name, []).append({"tokens_per_s": round(width[name] * (n_new - 1) / dt, 1),
+                                                      "ms_per_step": round(dt * 1e3 / (n_new - 1), 4)})
+            best = {k: max(r["tokens_per_s"] for r in v) for k, v in rows.items()}
+            emit({"metric": f"aggregate tokens/sec greedy decode in wide lanes, {label}", "unit": "tokens/s", "value": best["wide-64"],
+                  "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                  "config": {"workload": f"{label}, random init, one 128-token prompt per lane, {n_new} generated tokens per lane, lane_context "
+                                         f"{ctx}; generate(), generate_batch at 8 lanes, generate_wide at 16 / 32 / 64, twice, in one process"},
+                  "legs": rows, "x_lanes_8": {k: round(best[k] / best["lanes-8"], 2) for k in ("wide-16", "wide-32", "wide-64")},
+                  "x_single_stream": {k: round(best[k] / best["single"], 2) for k in best if k != "single"}, "weight_bytes": dec.weight_bytes})
+
+        d = os.path.join(tmp, "llama-1b-wide")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        prompts = [rng.integers(1000, 100000, 128).tolist() for _ in range(64)]
+        measure_wide("Llama-3.2-1B shape, bf16 weights", dec, prompts, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        if not trace_steps:  # (the trace run is the Llama shape alone)
+            gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+            gd = os.path.join(tmp, "gpt2-small-wide")
+            gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+            gprompts = [rng.integers(0, 50257, 128).tolist() for _ in range(64)]
+            dec = kjarni_amd.HipDecoder(gd)
+            measure_wide("gpt2-small shape, bf16 weights", dec, gprompts, "bf16 weights, f32 activations/accumulate/KV")
             del dec
 
     if "llm_lookup" in which:
