@@ -1043,6 +1043,64 @@ KjarniErrorCode kjarni_hip_op_llm_qkv_rope(int32_t device, const float* x, const
                                            int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, const float* cos_t, const float* sin_t,
                                            int32_t positions, int32_t pos, int32_t offset_on_device, float* q, float* k_cache, float* v_cache,
                                            int32_t cache_rows, float* x_raw_out, int32_t* route);
+/* ---- the Whisper decoder's row projections and the front-end kernels, alone -----------------------------------------------------------
+ * kjarni_hip_op_gemv_rows: ONE call of launch_gemv_rows on host arrays, every field of GemvArgs exposed.  Y[r, n] = epi(LN?(x[r, :])
+ * . w[n, :] + bias[n]) (+ R[r, n]) for `rows` rows.  x [x_rows, ldx] (NULL with embed_id); gamma, beta [k] (gamma given: LayerNorm,
+ * (x - mean) / sqrt(var + eps) * gamma + beta); w [n_out, k]; bias [n_out] or NULL; epi: 0 bias, 1 erf GELU, 5 residual -- r [rows,
+ * ldr], or with r_is_y0 the output y[0] itself, as the decoder calls it.  seg == 0: y[0] [out_rows[0], ldy0] gets row r at row r;
+ * seg > 0: columns [0, seg) go to y[0] row r, [seg, 2 seg) to y[1] and [2 seg, 3 seg) to y[2], both [out_rows[i], ldy12], at row
+ * row_off + r.  offset_on_device: row_off is read from device memory and the launcher's by-value copy is another row inside the
+ * outputs.  embed_id (one id, or NULL): the kernel builds its input row as embed_word [embed_vocab, k] row id * embed_scale +
+ * embed_pos_table [embed_max_pos, k] (or NULL) row embed_pos -- zeros for an id or a position outside its table;
+ * embed_pos_on_device as offset_on_device.  x_raw_out [k] (or NULL; with embed_id): the row as built; x_norm_out [k] (or NULL; with
+ * gamma): the row after the LayerNorm.
+ * misalign: a mask (1 x, 2 w, 4 gamma, 8 beta) of operands uploaded 4 bytes past a 16-byte boundary.  Every y[i], x_raw_out and
+ * x_norm_out is uploaded as given, written by the kernel and returned whole, with a guard band behind it on the device.
+ * *route_out: gemv_rows_route's answer, which the launcher follows: 0 nothing to do (rows or n_out <= 0), 1 one-row fast, 2 one-row
+ * fast + embed, 3 staged fast, 4 head, 5 staged, 6 general, 7 GEMM.  INVALID_CONFIG, before any GPU work and with every output
+ * untouched: sizes outside the caps, ldx < k, ldy < the output's columns, ldr < n_out, rows that do not fit an output at row_off,
+ * an in-place residual with segments, embed fields without embed_id -- and everything the launcher's rule refuses (route 8):
+ * LayerNorm without beta, a residual epilogue without a residual, an (epilogue, LayerNorm) pair outside the four, n_out above
+ * 3 seg, the embed or x_raw_out / x_norm_out outside the one-row kernel, x_raw_out without embed_id, x_norm_out without gamma,
+ * gamma or segments on the GEMM route. */
+KjarniErrorCode kjarni_hip_op_gemv_rows(int32_t device, const float* x, int32_t x_rows, int64_t ldx, int32_t rows, const float* gamma,
+                                        const float* beta, float eps, const float* w, const float* bias, const float* r, int64_t ldr,
+                                        int32_t r_is_y0, int32_t n_out, int32_t k, int32_t seg, float* const* y, const int32_t* out_rows,
+                                        int64_t ldy0, int64_t ldy12, int32_t row_off, int32_t offset_on_device, int32_t epi,
+                                        const uint32_t* embed_id, const float* embed_word, int32_t embed_vocab, const float* embed_pos_table,
+                                        int32_t embed_max_pos, int32_t embed_pos, int32_t embed_pos_on_device, float embed_scale,
+                                        float* x_raw_out, float* x_norm_out, int32_t misalign, int32_t* route_out);
+/* gemv_rows_route alone, no device needed: the route (0 .. 8 as above) for arguments given as sizes and flags; every pointer the
+ * rule tests is made non-NULL where its flag is set and 16-byte aligned unless `misalign` (the mask above) shifts it. */
+KjarniErrorCode kjarni_hip_gemv_rows_route(int32_t rows, int32_t n_out, int32_t k, int64_t ldx, int32_t seg, int32_t epi, int32_t has_gamma,
+                                           int32_t has_beta, int32_t has_r, int32_t embed, int32_t x_raw_out, int32_t x_norm_out,
+                                           int32_t misalign, int32_t* route_out);
+/* The Whisper front-end kernels, one launch per call on host arrays; every output is uploaded as given and returned whole, with a
+ * guard band behind it.  INVALID_CONFIG before any GPU work for sizes outside the caps or a stride that does not cover its row.
+ * mel_frames: frames [n_frames, ld] = the signal reflect-padded by n_fft / 2, framed every `hop` samples and windowed; columns
+ *   >= n_fft and frames past the padded end are zero.
+ * mel_power: power [n_frames, ld_out] = sqrt(re^2 + im^2)^2, re at column k and im at column im_off + k of dft [n_frames, ld_dft];
+ *   columns >= n_bins are zero.
+ * mel_log_normalize: mel [n_frames, ld] becomes log10(max(mel, 1e-10)) over its first n_mels columns; out [n_frames, ld_out] =
+ *   (max(log, max log - 8) + 4) / 4.
+ * im2col3: cols [t_out, ld_cols], column j * channels + c = x [t * stride + j - pad, c] (zero outside [0, t_in), zero from column
+ *   3 * channels on); x [t_in, ldx].
+ * add_rows: x [rows, hidden] += table [r % period] where r % period < table_rows; table [table_alloc_rows, hidden].
+ * decoder_embed: out [n, hidden] = word [ids[s]] * (sqrt(hidden) with scale_embeddings) + pos [offset + s] (lanes: offset for every
+ *   row); zeros for ids >= vocab, nothing added for positions >= max_pos; pos may be NULL; offset_on_device as above. */
+KjarniErrorCode kjarni_hip_op_mel_frames(int32_t device, const float* audio, int64_t n_samples, const float* window, int32_t n_fft,
+                                         int32_t hop, int32_t n_frames, int32_t ld, float* frames);
+KjarniErrorCode kjarni_hip_op_mel_power(int32_t device, const float* dft, int32_t ld_dft, int32_t im_off, int32_t n_bins, int32_t ld_out,
+                                        int32_t n_frames, float* power);
+KjarniErrorCode kjarni_hip_op_mel_log_normalize(int32_t device, float* mel, int32_t ld, int32_t n_mels, int32_t n_frames, int32_t ld_out,
+                                                float* out);
+KjarniErrorCode kjarni_hip_op_im2col3(int32_t device, const float* x, int64_t ldx, int32_t t_in, int32_t channels, int32_t stride,
+                                      int32_t pad, int32_t t_out, int32_t ld_cols, float* cols);
+KjarniErrorCode kjarni_hip_op_add_rows(int32_t device, float* x, int32_t rows, int32_t hidden, int32_t period, const float* table,
+                                       int32_t table_rows, int32_t table_alloc_rows);
+KjarniErrorCode kjarni_hip_op_decoder_embed(int32_t device, const uint32_t* ids, int32_t n, int32_t hidden, int32_t vocab, const float* word,
+                                            const float* pos, int32_t max_pos, int32_t offset, int32_t offset_on_device,
+                                            int32_t scale_embeddings, int32_t lanes, float* out);
 /* ---- the prompt-route GEMM and the two prefill attention kernels, alone -------------------------------------------------------------
  * kjarni_hip_op_prefill_gemm: y[m, n] = a[m, k] . w[n, k]^T (+ bias) (+ r) through launch_prefill_gemm (64 x 64 tiles, K slices
  * added by the reduce kernel), as the decoders' prompt projections call it.  a [a_rows, lda] (a_rows >= m, lda >= k); w [n, k] f32,

@@ -580,6 +580,19 @@ SIGNATURES = {
     "kjarni_hip_op_llm_qkv_rope": (c_int32, [c_int32, _f32p, _u32p, c_void_p, c_int32, _f32p, c_float, c_void_p, c_int32, _f32p, c_int32,
                                              c_int32, c_int32, c_int32, _f32p, _f32p, c_int32, c_int32, c_int32, _f32p, _f32p, _f32p, c_int32,
                                              _f32p, POINTER(c_int32)]),
+    "kjarni_hip_op_gemv_rows": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, _f32p, _f32p, c_float, _f32p, _f32p, _f32p, c_int64, c_int32,
+                                          c_int32, c_int32, c_int32, POINTER(c_void_p), POINTER(c_int32), c_int64, c_int64, c_int32, c_int32,
+                                          c_int32, _u32p, _f32p, c_int32, _f32p, c_int32, c_int32, c_int32, c_float, _f32p, _f32p, c_int32,
+                                          POINTER(c_int32)]),
+    "kjarni_hip_gemv_rows_route": (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             c_int32, c_int32, POINTER(c_int32)]),
+    "kjarni_hip_op_mel_frames": (c_int32, [c_int32, _f32p, c_int64, _f32p, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_mel_power": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_mel_log_normalize": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_im2col3": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_add_rows": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, _f32p, c_int32, c_int32]),
+    "kjarni_hip_op_decoder_embed": (c_int32, [c_int32, _u32p, c_int32, c_int32, c_int32, _f32p, _f32p, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, _f32p]),
     "kjarni_hip_op_prefill_gemm": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, _f32p, _f32p, c_int64, c_int32, _f32p, c_int64,
                                              _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "kjarni_hip_op_prefill_attention": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int64, _f32p, c_int64, c_int64, c_int32,

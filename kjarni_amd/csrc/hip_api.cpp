@@ -2096,6 +2096,282 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_qkv_rope(int32_t device, const f
     });
 }
 
+// ---- the Whisper decoder's row projections and the front-end kernels, alone ------------------------------------------------------
+
+namespace {
+
+// A device copy of `floats` host floats that starts `shift` floats (0 or 1) past a 16-byte boundary.
+struct ShiftedBuf {
+    DeviceBuf buf;
+    int shift;
+    ShiftedBuf(const float* src, size_t floats, int shift_, const char* what) : buf((floats + 1) * 4), shift(shift_)
+    {
+        if (src && floats) hip_check(hipMemcpy(static_cast<float*>(buf.p) + shift, src, floats * 4, hipMemcpyHostToDevice), what);
+    }
+    const float* p() const { return static_cast<const float*>(buf.p) + shift; }
+};
+
+// A whole host array on the device with a guard band behind it, and back.
+struct RoundTrip {
+    GuardedBuf d;
+    float* host;
+    RoundTrip(float* h, size_t floats) : d(floats * 4), host(h)
+    {
+        if (h && floats) hip_check(hipMemcpy(d.buf.p, h, floats * 4, hipMemcpyHostToDevice), "H2D output");
+    }
+    float* p() const { return d.as<float>(); }
+    void fetch(const char* what, size_t floats) const
+    {
+        d.check(what);
+        if (host && floats) hip_check(hipMemcpy(host, d.buf.p, floats * 4, hipMemcpyDeviceToHost), "D2H output");
+    }
+};
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_gemv_rows(int32_t device, const float* x, int32_t x_rows, int64_t ldx, int32_t rows, const float* gamma,
+                                                      const float* beta, float eps, const float* w, const float* bias, const float* r,
+                                                      int64_t ldr, int32_t r_is_y0, int32_t n_out, int32_t k, int32_t seg, float* const* y,
+                                                      const int32_t* out_rows, int64_t ldy0, int64_t ldy12, int32_t row_off,
+                                                      int32_t offset_on_device, int32_t epi, const uint32_t* embed_id, const float* embed_word,
+                                                      int32_t embed_vocab, const float* embed_pos_table, int32_t embed_max_pos,
+                                                      int32_t embed_pos, int32_t embed_pos_on_device, float embed_scale, float* x_raw_out,
+                                                      float* x_norm_out, int32_t misalign, int32_t* route_out)
+{
+    if (!w || !y || !out_rows || !route_out || (!x && !embed_id)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // every element a kernel may read or write lies inside the buffers uploaded below
+        if (rows < -1 || rows > 16 || x_rows < std::max(rows, 1) || x_rows > 64) throw InvalidConfig("rows must be -1 .. 16 and x_rows max(rows, 1) .. 64");
+        if (n_out < -1 || k < 1 || n_out > (1 << 17) || k > (1 << 16) || (int64_t)std::max(n_out, 1) * k > ((int64_t)1 << 26))
+            throw InvalidConfig("n_out must be -1 .. 2^17, k 1 .. 2^16, n_out * k at most 2^26");
+        if (ldx < k || ldx > (1 << 18)) throw InvalidConfig("ldx must cover k (at most 2^18)");
+        if (epi < 0 || epi > (int)EPI_BIAS_MUL_SILU) throw InvalidConfig("epi is no epilogue");
+        if (misalign < 0 || misalign > 15) throw InvalidConfig("misalign is a mask of X (1), W (2), gamma (4), beta (8)");
+        if (r && r_is_y0) throw InvalidConfig("r_is_y0 takes the residual from y[0]: r must be NULL");
+        if (seg < 0 || row_off < 0) throw InvalidConfig("seg and row_off must not be negative");
+        if (seg > 0 && r_is_y0) throw InvalidConfig("no in-place residual with segments: y[0] holds seg of the n_out columns");
+        const int nn = std::max(n_out, 1), n_outs = seg > 0 ? 3 : 1;
+        const int64_t cols[3] = {seg > 0 ? seg : nn, seg, seg}, ldy[3] = {ldy0, ldy12, ldy12};
+        for (int i = 0; i < n_outs; ++i) {
+            if (!y[i]) throw InvalidConfig("an output of this call is NULL");
+            if (ldy[i] < cols[i] || ldy[i] > (1 << 18) || out_rows[i] < 1 || out_rows[i] > 4096 || (int64_t)out_rows[i] * ldy[i] > ((int64_t)1 << 24))
+                throw InvalidConfig("ldy must cover the output's columns (at most 2^18); out_rows 1 .. 4096; at most 2^24 elements");
+            if ((int64_t)(i == 0 ? 0 : row_off) + std::max(rows, 0) > out_rows[i])
+                throw InvalidConfig("rows " + std::to_string(i == 0 ? 0 : row_off) + " .. +" + std::to_string(rows) + " do not fit the " +
+                                    std::to_string(out_rows[i]) + " rows of output " + std::to_string(i));
+        }
+        if (r && (ldr < nn || ldr > (1 << 18))) throw InvalidConfig("ldr must cover n_out (at most 2^18)");
+        if (embed_id) {  // the word row id * k and the position row p * k are read only below vocab / max_pos: the tables hold that many rows
+            if (embed_vocab < 0 || embed_vocab > (1 << 17) || (int64_t)embed_vocab * k > ((int64_t)1 << 26) || embed_max_pos < 0 ||
+                embed_max_pos > (1 << 16) || embed_pos < 0)
+                throw InvalidConfig("embed: vocab 0 .. 2^17 (vocab * k at most 2^26), max_pos 0 .. 2^16, pos not negative");
+        } else if (embed_word || embed_pos_table || embed_pos_on_device) {
+            throw InvalidConfig("embed_word, embed_pos_table and embed_pos_on_device belong to embed_id");
+        }
+        // The launcher's own refusals, asked of its rule before any GPU work: the rule looks at the pointers only for NULL and for
+        // their alignment, which the uploads below reproduce.
+        const auto fake = [](bool given, int shift) { return given ? reinterpret_cast<float*>((uintptr_t)4096 + 4 * (uintptr_t)shift) : nullptr; };
+        const int sx = misalign & 1, sw = (misalign >> 1) & 1, sg = (misalign >> 2) & 1, sb = (misalign >> 3) & 1;
+        GemvArgs a;
+        a.X = fake(x != nullptr, sx); a.ldx = ldx; a.rows = rows; a.gamma = fake(gamma != nullptr, sg); a.beta = fake(beta != nullptr, sb);
+        a.eps = eps; a.W = fake(true, sw); a.bias = fake(bias != nullptr, 0); a.R = fake(r || r_is_y0, 0); a.ldr = r_is_y0 ? ldy0 : ldr;
+        a.n_out = n_out; a.k = k; a.seg = seg; a.Y0 = fake(true, 0); a.ldy0 = ldy0;
+        if (seg > 0) {
+            a.Y1 = fake(true, 0); a.Y2 = fake(true, 0); a.ldy12 = ldy12;
+        }
+        a.epi = (GemmEpilogue)epi;
+        a.embed_ids = embed_id ? reinterpret_cast<const uint32_t*>(fake(true, 0)) : nullptr;
+        a.embed_word = fake(embed_word != nullptr, 0); a.embed_pos_table = fake(embed_pos_table != nullptr, 0);
+        a.embed_vocab = embed_vocab; a.embed_max_pos = embed_max_pos; a.embed_scale = embed_scale;
+        a.x_raw_out = fake(x_raw_out != nullptr, 0); a.x_norm_out = fake(x_norm_out != nullptr, 0);
+        const GemvRowsRoute route = gemv_rows_route(a);
+        if (route == GEMV_ROWS_REFUSED) throw InvalidConfig("launch_gemv_rows refuses these arguments");
+        use_device(device);
+        const ShiftedBuf xd(x, x ? (size_t)x_rows * (size_t)ldx : 0, sx, "H2D x"), wd(w, (size_t)nn * (size_t)k, sw, "H2D w");
+        const ShiftedBuf gd(gamma, (size_t)k, sg, "H2D gamma"), bed(beta, (size_t)k, sb, "H2D beta");
+        const auto bd = upload(bias, (size_t)nn * 4, "H2D bias");
+        const auto rd = upload(r, r ? (size_t)std::max(rows, 1) * (size_t)ldr * 4 : 0, "H2D r");
+        const auto od = upload(&row_off, sizeof(int), "H2D row_off"), pd = upload(&embed_pos, sizeof(int), "H2D embed_pos");
+        const auto idd = upload(embed_id, embed_id ? 4 : 0, "H2D embed_id");
+        const auto wordd = upload(embed_word, embed_id ? (size_t)embed_vocab * (size_t)k * 4 : 0, "H2D embed_word");
+        const auto posd = upload(embed_pos_table, embed_id ? (size_t)embed_max_pos * (size_t)k * 4 : 0, "H2D embed_pos_table");
+        std::vector<std::unique_ptr<RoundTrip>> out;
+        for (int i = 0; i < n_outs; ++i) out.push_back(std::make_unique<RoundTrip>(y[i], (size_t)out_rows[i] * (size_t)ldy[i]));
+        const RoundTrip raw(x_raw_out, x_raw_out ? (size_t)k : 0), norm(x_norm_out, x_norm_out ? (size_t)k : 0);
+        a.X = x ? xd.p() : nullptr; a.gamma = gamma ? gd.p() : nullptr; a.beta = beta ? bed.p() : nullptr; a.W = wd.p();
+        a.bias = bias ? static_cast<const float*>(bd->p) : nullptr;
+        a.R = r_is_y0 ? out[0]->p() : (r ? static_cast<const float*>(rd->p) : nullptr);
+        a.Y0 = out[0]->p();
+        if (seg > 0) {
+            a.Y1 = out[1]->p(); a.Y2 = out[2]->p();
+        }
+        a.row_off = row_off;
+        if (offset_on_device) {  // (the by-value copy is then another row inside both caches)
+            a.row_off_ptr = static_cast<const int*>(od->p);
+            a.row_off = decoy_offset(row_off, seg > 0 ? std::min(out_rows[1], out_rows[2]) - std::max(rows, 0) : 0);
+        }
+        if (embed_id) {
+            a.embed_ids = static_cast<const uint32_t*>(idd->p);
+            a.embed_word = embed_word ? static_cast<const float*>(wordd->p) : nullptr;
+            a.embed_pos_table = embed_pos_table ? static_cast<const float*>(posd->p) : nullptr;
+            a.embed_pos = embed_pos;
+            if (embed_pos_on_device) {
+                a.embed_pos_ptr = static_cast<const int*>(pd->p);
+                a.embed_pos = decoy_offset(embed_pos, embed_max_pos - 1);
+            }
+        }
+        a.x_raw_out = x_raw_out ? raw.p() : nullptr; a.x_norm_out = x_norm_out ? norm.p() : nullptr;
+        expect(gemv_rows_route(a) == route, "the route changed between the check and the launch");
+        launcher_check(launch_gemv_rows(a, nullptr), "gemv rows");
+        hip_check(hipDeviceSynchronize(), "sync");
+        for (int i = 0; i < n_outs; ++i) out[i]->fetch("gemv rows output", (size_t)out_rows[i] * (size_t)ldy[i]);
+        raw.fetch("x_raw_out", x_raw_out ? (size_t)k : 0);
+        norm.fetch("x_norm_out", x_norm_out ? (size_t)k : 0);
+        *route_out = (int32_t)route;
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_gemv_rows_route(int32_t rows, int32_t n_out, int32_t k, int64_t ldx, int32_t seg, int32_t epi,
+                                                         int32_t has_gamma, int32_t has_beta, int32_t has_r, int32_t embed, int32_t x_raw_out,
+                                                         int32_t x_norm_out, int32_t misalign, int32_t* route_out)
+{
+    if (!route_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const auto fake = [](bool given, int shift) { return given ? reinterpret_cast<float*>((uintptr_t)4096 + 4 * (uintptr_t)shift) : nullptr; };
+        GemvArgs a;
+        a.X = fake(true, misalign & 1); a.ldx = ldx; a.rows = rows; a.gamma = fake(has_gamma != 0, (misalign >> 2) & 1);
+        a.beta = fake(has_beta != 0, (misalign >> 3) & 1); a.W = fake(true, (misalign >> 1) & 1); a.R = fake(has_r != 0, 0);
+        a.n_out = n_out; a.k = k; a.seg = seg; a.Y0 = fake(true, 0); a.Y1 = fake(seg > 0, 0); a.Y2 = fake(seg > 0, 0);
+        a.epi = (GemmEpilogue)epi;
+        a.embed_ids = embed ? reinterpret_cast<const uint32_t*>(fake(true, 0)) : nullptr; a.embed_word = fake(embed != 0, 0);
+        a.x_raw_out = fake(x_raw_out != 0, 0); a.x_norm_out = fake(x_norm_out != 0, 0);
+        *route_out = (int32_t)gemv_rows_route(a);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mel_frames(int32_t device, const float* audio, int64_t n_samples, const float* window, int32_t n_fft,
+                                                       int32_t hop, int32_t n_frames, int32_t ld, float* frames)
+{
+    if (!audio || !window || !frames) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // (the kernel's clamps keep every sample index inside [0, n_samples) once there is a sample; window [n_fft]; frames [n_frames, ld])
+        if (n_samples < 1 || n_samples > (1 << 24) || n_fft < 2 || n_fft > 4096 || hop < 1 || hop > 4096 || n_frames < 1 || n_frames > (1 << 16) ||
+            ld < n_fft || ld > 8192 || (int64_t)n_frames * ld > ((int64_t)1 << 24))
+            throw InvalidConfig("mel_frames: n_samples 1 .. 2^24, n_fft 2 .. 4096, hop 1 .. 4096, n_frames 1 .. 2^16, ld n_fft .. 8192");
+        use_device(device);
+        const auto ad = upload(audio, (size_t)n_samples * 4, "H2D audio"), wd = upload(window, (size_t)n_fft * 4, "H2D window");
+        const size_t fl = (size_t)n_frames * (size_t)ld;
+        const RoundTrip fd(frames, fl);
+        launcher_check(launch_mel_frames(static_cast<const float*>(ad->p), n_samples, static_cast<const float*>(wd->p), n_fft, hop, n_frames, ld,
+                                         fd.p(), nullptr), "mel_frames");
+        hip_check(hipDeviceSynchronize(), "sync");
+        fd.fetch("frames", fl);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mel_power(int32_t device, const float* dft, int32_t ld_dft, int32_t im_off, int32_t n_bins,
+                                                      int32_t ld_out, int32_t n_frames, float* power)
+{
+    if (!dft || !power) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_frames < 1 || n_frames > (1 << 16) || n_bins < 0 || n_bins > ld_out || ld_out < 1 || ld_out > 8192 || im_off < 0 ||
+            (int64_t)im_off + n_bins > ld_dft || ld_dft > 8192)
+            throw InvalidConfig("mel_power: n_frames 1 .. 2^16, n_bins 0 .. ld_out, im_off + n_bins within ld_dft, strides at most 8192");
+        use_device(device);
+        const auto dd = upload(dft, (size_t)n_frames * (size_t)ld_dft * 4, "H2D dft");
+        const size_t pl = (size_t)n_frames * (size_t)ld_out;
+        const RoundTrip pw(power, pl);
+        launcher_check(launch_mel_power(static_cast<const float*>(dd->p), ld_dft, im_off, n_bins, ld_out, n_frames, pw.p(), nullptr), "mel_power");
+        hip_check(hipDeviceSynchronize(), "sync");
+        pw.fetch("power", pl);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mel_log_normalize(int32_t device, float* mel, int32_t ld, int32_t n_mels, int32_t n_frames,
+                                                              int32_t ld_out, float* out)
+{
+    if (!mel || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_frames < 1 || n_frames > (1 << 16) || n_mels < 1 || ld < n_mels || ld_out < n_mels || ld > 4096 || ld_out > 4096)
+            throw InvalidConfig("mel_log_normalize: n_frames 1 .. 2^16, n_mels 1 .. ld and ld_out, strides at most 4096");
+        use_device(device);
+        const size_t ml = (size_t)n_frames * (size_t)ld, ol = (size_t)n_frames * (size_t)ld_out;
+        const RoundTrip md(mel, ml), od(out, ol);
+        GuardedBuf mx(4);
+        hip_check(hipMemset(mx.buf.p, 0xFF, 4), "poison max");  // (the launcher zeroes it itself)
+        launcher_check(launch_mel_log_normalize(md.p(), ld, n_mels, n_frames, mx.as<uint32_t>(), ld_out, od.p(), nullptr), "mel_log_normalize");
+        hip_check(hipDeviceSynchronize(), "sync");
+        mx.check("max scratch");
+        md.fetch("mel", ml);
+        od.fetch("out", ol);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_im2col3(int32_t device, const float* x, int64_t ldx, int32_t t_in, int32_t channels, int32_t stride,
+                                                    int32_t pad, int32_t t_out, int32_t ld_cols, float* cols)
+{
+    if (!x || !cols) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // (x [t_in, ldx]: the kernel tests every row it reads against [0, t_in); cols [t_out, ld_cols])
+        if (t_in < 1 || t_in > (1 << 16) || channels < 1 || channels > 4096 || ldx < channels || ldx > 8192 || stride < 1 || stride > 16 || pad < 0 ||
+            pad > 16 || t_out < 1 || t_out > (1 << 16) || ld_cols < 3 * channels || ld_cols > (1 << 14) || (int64_t)t_out * ld_cols > ((int64_t)1 << 24))
+            throw InvalidConfig("im2col3: t_in, t_out 1 .. 2^16, channels 1 .. 4096 within ldx, stride 1 .. 16, pad 0 .. 16, ld_cols at least 3 channels");
+        use_device(device);
+        const auto xd = upload(x, (size_t)t_in * (size_t)ldx * 4, "H2D x");
+        const size_t cl = (size_t)t_out * (size_t)ld_cols;
+        const RoundTrip cd(cols, cl);
+        launcher_check(launch_im2col3(static_cast<const float*>(xd->p), ldx, t_in, channels, stride, pad, t_out, ld_cols, cd.p(), nullptr), "im2col3");
+        hip_check(hipDeviceSynchronize(), "sync");
+        cd.fetch("cols", cl);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_add_rows(int32_t device, float* x, int32_t rows, int32_t hidden, int32_t period, const float* table,
+                                                     int32_t table_rows, int32_t table_alloc_rows)
+{
+    if (!x || !table) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // (table [table_alloc_rows, hidden], of which the call may use the first table_rows)
+        if (rows < 1 || rows > (1 << 16) || hidden < 1 || hidden > 8192 || period < 1 || table_rows < 0 || table_alloc_rows < std::max(table_rows, 1) ||
+            table_alloc_rows > (1 << 16))
+            throw InvalidConfig("add_rows: rows 1 .. 2^16, hidden 1 .. 8192, period at least 1, table_rows 0 .. table_alloc_rows (1 .. 2^16)");
+        use_device(device);
+        const auto td = upload(table, (size_t)table_alloc_rows * (size_t)hidden * 4, "H2D table");
+        const size_t xl = (size_t)rows * (size_t)hidden;
+        const RoundTrip xd(x, xl);
+        launcher_check(launch_add_rows(xd.p(), rows, hidden, period, static_cast<const float*>(td->p), table_rows, nullptr), "add_rows");
+        hip_check(hipDeviceSynchronize(), "sync");
+        xd.fetch("x", xl);
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_decoder_embed(int32_t device, const uint32_t* ids, int32_t n, int32_t hidden, int32_t vocab,
+                                                          const float* word, const float* pos, int32_t max_pos, int32_t offset,
+                                                          int32_t offset_on_device, int32_t scale_embeddings, int32_t lanes, float* out)
+{
+    if (!ids || !word || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        // (word [vocab, hidden], pos [max_pos, hidden] or NULL: the kernel reads row id only below vocab, row p only below max_pos)
+        if (n < 1 || n > 64 || hidden < 1 || hidden > 8192 || vocab < 1 || vocab > (1 << 17) || (int64_t)vocab * hidden > ((int64_t)1 << 26) ||
+            max_pos < 0 || max_pos > (1 << 16) || offset < 0 || (pos && max_pos < 1))
+            throw InvalidConfig("decoder_embed: n 1 .. 64, hidden 1 .. 8192, vocab 1 .. 2^17, max_pos 0 .. 2^16, offset not negative");
+        use_device(device);
+        const auto idd = upload(ids, (size_t)n * 4, "H2D ids");
+        const auto wd = upload(word, (size_t)vocab * (size_t)hidden * 4, "H2D word"), pd = upload(pos, pos ? (size_t)max_pos * (size_t)hidden * 4 : 0, "H2D pos");
+        const auto od = upload(&offset, sizeof(int), "H2D offset");
+        const size_t ol = (size_t)n * (size_t)hidden;
+        const RoundTrip out_d(out, ol);
+        // (with the position on the device the by-value one is another row: the kernel stays inside the table for any of them)
+        launcher_check(launch_decoder_embed(static_cast<const uint32_t*>(idd->p), n, hidden, vocab, static_cast<const float*>(wd->p),
+                                            pos ? static_cast<const float*>(pd->p) : nullptr, max_pos,
+                                            offset_on_device ? decoy_offset(offset, max_pos - 1) : offset,
+                                            offset_on_device ? static_cast<const int*>(od->p) : nullptr, scale_embeddings ? 1 : 0, out_d.p(), nullptr,
+                                            lanes ? 1 : 0), "decoder_embed");
+        hip_check(hipDeviceSynchronize(), "sync");
+        out_d.fetch("out", ol);
+    });
+}
+
 // ---- wide lanes: the rotate-and-scatter launchers and the pick alone ------------------------------------------------------------
 
 static_assert(sizeof(KjarniHipWideState) == sizeof(LlmWideState) && KJARNI_HIP_WIDE_LANES == kMaxWideLanes &&

@@ -49,9 +49,9 @@ struct GemvArgs {
     GemmEpilogue epi = EPI_BIAS;
     // One row of 512 / 2048 floats only (gemv_rows_takes_row_extras): the kernel can build its input row itself as
     // launch_decoder_embed would (embed_ids != null: word[*embed_ids] * embed_scale + pos_table[*embed_pos_ptr | embed_pos]; X is
-    // then unused; LayerNorm + EPI_BIAS, 512-float rows) and leave copies of it: x_raw_out = the row as read / built (the residual
-    // stream), x_norm_out = the row after the LayerNorm (the model's last hidden state when the vocabulary head folds the final
-    // norm in).
+    // then unused; LayerNorm + EPI_BIAS, 512-float rows) and leave copies of it: x_raw_out = the row as built (the residual
+    // stream; with embed_ids only -- no other form stores it), x_norm_out = the row after the LayerNorm (the model's last hidden
+    // state when the vocabulary head folds the final norm in).
     const uint32_t* embed_ids = nullptr;
     const float *embed_word = nullptr, *embed_pos_table = nullptr;
     int embed_vocab = 0, embed_max_pos = 0, embed_pos = 0;
@@ -60,6 +60,20 @@ struct GemvArgs {
     float *x_raw_out = nullptr, *x_norm_out = nullptr;
 };
 bool gemv_rows_takes_row_extras(const GemvArgs& args);
+// Which kernel launch_gemv_rows runs for these arguments: a pure host function, the launcher's only decision (it launches what
+// this returns), so a test can hold a case to the kernel it is meant for.
+enum GemvRowsRoute {
+    GEMV_ROWS_NOTHING = 0,         // rows <= 0 or n_out <= 0: hipSuccess, no launch
+    GEMV_ROWS_ONE_FAST = 1,        // gemv_row_fast_kernel: one row of 512 / 2048 floats
+    GEMV_ROWS_ONE_FAST_EMBED = 2,  // ... building its input row itself (embed_ids)
+    GEMV_ROWS_STAGED_FAST = 3,     // gemv_rows_lds_fast_kernel: 2..8 rows of 512 / 2048 floats, rows * k * 4 <= 64 KiB
+    GEMV_ROWS_HEAD = 4,            // gemv_rows_head_kernel: the same rows of 512 floats against >= 8192 columns, EPI_BIAS alone
+    GEMV_ROWS_STAGED = 5,          // gemv_rows_lds_kernel: 2..8 rows of any k % 4 == 0 within 64 KiB
+    GEMV_ROWS_GENERAL = 6,         // gemv_rows_kernel: everything else up to 8 rows
+    GEMV_ROWS_GEMM = 7,            // launch_gemm: more than 8 rows, k or ldx no multiple of 4, X or W not 16-byte aligned
+    GEMV_ROWS_REFUSED = 8,         // hipErrorInvalidValue, nothing launched
+};
+GemvRowsRoute gemv_rows_route(const GemvArgs& args);
 hipError_t launch_gemv_rows(const GemvArgs& args, hipStream_t stream);
 
 // Attention of `rows` query rows over cached keys/values, split over `splits` key ranges + a combine pass.

@@ -983,6 +983,9 @@ __global__ void pick_finalize_kernel(unsigned long long* __restrict__ best, int 
 hipError_t launch_mel_frames(const float* audio, int64_t n_samples, const float* window, int n_fft, int hop,
                              int n_frames, int ld, float* frames, hipStream_t stream)
 {
+    // (an empty signal has nothing to reflect: the clamps of mel_frames_kernel would read audio[-1])
+    if (n_frames <= 0) return hipSuccess;
+    if (!audio || !window || !frames || n_samples < 1 || n_fft < 2 || hop < 1 || ld < n_fft) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mel_frames_kernel, dim3((unsigned)n_frames), dim3(256), 0, stream, audio, n_samples, window,
                        n_fft, hop, n_frames, ld, frames);
     return hipGetLastError();
@@ -991,6 +994,8 @@ hipError_t launch_mel_frames(const float* audio, int64_t n_samples, const float*
 hipError_t launch_mel_power(const float* dft, int ld_dft, int im_off, int n_bins, int ld_out, int64_t n_frames,
                             float* power, hipStream_t stream)
 {
+    if (n_frames <= 0 || ld_out <= 0) return hipSuccess;
+    if (!dft || !power || n_bins < 0 || n_bins > ld_out || im_off < 0 || (int64_t)im_off + n_bins > ld_dft) return hipErrorInvalidValue;
     const int64_t total = n_frames * ld_out;
     hipLaunchKernelGGL(mel_power_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dft, ld_dft,
                        im_off, n_bins, ld_out, n_frames, power);
@@ -1000,6 +1005,8 @@ hipError_t launch_mel_power(const float* dft, int ld_dft, int im_off, int n_bins
 hipError_t launch_mel_log_normalize(float* mel, int ld, int n_mels, int64_t n_frames, uint32_t* max_scratch,
                                     int ld_out, float* out, hipStream_t stream)
 {
+    if (n_frames <= 0 || n_mels <= 0) return hipSuccess;
+    if (!mel || !max_scratch || !out || ld < n_mels || ld_out < n_mels) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(max_scratch, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     const int64_t total = n_frames * n_mels;
@@ -1014,6 +1021,10 @@ hipError_t launch_mel_log_normalize(float* mel, int ld, int n_mels, int64_t n_fr
 hipError_t launch_im2col3(const float* x, int64_t ldx, int t_in, int channels, int stride, int pad, int t_out,
                           int ld_cols, float* cols, hipStream_t stream)
 {
+    if (t_out <= 0 || ld_cols <= 0) return hipSuccess;
+    // (every row t * stride + k - pad the kernel reads is tested against [0, t_in): only the column count can lead it out)
+    if (!x || !cols || t_in < 0 || channels < 1 || stride < 1 || pad < 0 || ldx < channels || ld_cols < 3 * (int64_t)channels)
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(im2col3_kernel, dim3((unsigned)t_out), dim3(256), 0, stream, x, ldx, t_in, channels, stride, pad,
                        t_out, ld_cols, cols);
     return hipGetLastError();
@@ -1022,6 +1033,8 @@ hipError_t launch_im2col3(const float* x, int64_t ldx, int t_in, int channels, i
 hipError_t launch_add_rows(float* x, int64_t rows, int hidden, int period, const float* table, int table_rows,
                            hipStream_t stream)
 {
+    if (rows <= 0 || hidden <= 0) return hipSuccess;
+    if (!x || period < 1 || (table_rows > 0 && !table)) return hipErrorInvalidValue;  // (period 0: r % period)
     const int64_t total = rows * hidden;
     hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, rows, hidden,
                        period, table, table_rows);
@@ -1032,6 +1045,9 @@ hipError_t launch_decoder_embed(const uint32_t* ids, int n, int hidden, int voca
                                 int max_pos, int offset, const int* offset_ptr, int scale_embeddings, float* out,
                                 hipStream_t stream, int lanes)
 {
+    if (n <= 0 || hidden <= 0) return hipSuccess;
+    // (a negative position passes the kernel's p < max_pos and reads in front of the table)
+    if (!ids || !word || !out || vocab < 0 || (!offset_ptr && offset < 0)) return hipErrorInvalidValue;
     const float scale = scale_embeddings ? sqrtf((float)hidden) : 1.0f;
     hipLaunchKernelGGL(decoder_embed_kernel, dim3((unsigned)n), dim3(256), 0, stream, ids, hidden, vocab, word, pos, max_pos,
                        offset, offset_ptr, lanes ? 0 : 1, scale, out);
@@ -1048,24 +1064,55 @@ bool gemv_rows_takes_row_extras(const GemvArgs& a)
            (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (a.embed_ids || ((a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0));
 }
 
+// The rule of launch_gemv_rows, stated once.  Refused before anything else: what a kernel would follow out of its buffers
+// (LayerNorm without beta, a residual epilogue without R, segments that n_out does not fit or whose outputs are missing, an
+// embedding without its table), the extras outside the one-row kernel or where it would not write them (x_raw_out without the
+// embedding, x_norm_out without LayerNorm), and every (epilogue, LayerNorm) pair but the four that
+// whisper.cpp's decoder requests -- the only ones instantiated:
+//   (EPI_BIAS, LN)             LN1 + Q|K|V, LN2 + cross Q, the one-token vocabulary head with the final LayerNorm folded in
+//   (EPI_BIAS, none)           the vocabulary head after the final LayerNorm
+//   (EPI_BIAS_GELU, LN)        LN3 + fc1 + GELU
+//   (EPI_BIAS_RESIDUAL, none)  self / cross output projections, fc2 (+ residual)
+GemvRowsRoute gemv_rows_route(const GemvArgs& a)
+{
+    if (a.rows <= 0 || a.n_out <= 0) return GEMV_ROWS_NOTHING;
+    const bool ln = a.gamma != nullptr;
+    if (!a.W || !a.Y0 || (!a.X && !a.embed_ids) || (ln && !a.beta) || (a.epi == EPI_BIAS_RESIDUAL && !a.R)) return GEMV_ROWS_REFUSED;
+    if (a.seg > 0 && (a.n_out > 3 * (int64_t)a.seg || (a.n_out > a.seg && !a.Y1) || (a.n_out > 2 * (int64_t)a.seg && !a.Y2)))
+        return GEMV_ROWS_REFUSED;
+    // (only the EMBED variant stores x_raw_out and only a LayerNorm form x_norm_out: elsewhere they would stay unwritten)
+    if ((a.embed_ids && !a.embed_word) || (a.x_raw_out && !a.embed_ids) || (a.x_norm_out && !ln)) return GEMV_ROWS_REFUSED;
+    if ((a.embed_ids || a.x_raw_out || a.x_norm_out) && !gemv_rows_takes_row_extras(a)) return GEMV_ROWS_REFUSED;
+    if (a.epi == EPI_BIAS_GELU ? !ln : a.epi == EPI_BIAS_RESIDUAL ? ln : a.epi != EPI_BIAS) return GEMV_ROWS_REFUSED;
+    if (a.rows > GEMV_MAX_ROWS || (a.k & 3) || (a.ldx & 3) || (reinterpret_cast<uintptr_t>(a.X) & 15) ||
+        (reinterpret_cast<uintptr_t>(a.W) & 15))
+        return !ln && a.seg <= 0 ? GEMV_ROWS_GEMM : GEMV_ROWS_REFUSED;
+    // rows of 512 or 2048 floats (the Whisper-base decoder's widths) with 16-byte aligned gamma / beta: the variants with
+    // every request issued up front
+    const int kch = a.k / 256;
+    const bool fast = a.k % 256 == 0 && (kch == 2 || kch == 8) &&
+                      ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0;
+    if (a.rows == 1 && fast) {
+        // the first projection of a one-token step builds its input row itself (LN + Q | K | V, 512-float rows)
+        if (a.embed_ids) return ln && a.epi == EPI_BIAS && kch == 2 ? GEMV_ROWS_ONE_FAST_EMBED : GEMV_ROWS_REFUSED;
+        return GEMV_ROWS_ONE_FAST;
+    }
+    const bool staged = a.rows >= 2 && (size_t)a.rows * a.k * sizeof(float) <= 64 * 1024;
+    if (staged && fast) {
+        if (!ln && a.epi == EPI_BIAS && a.seg <= 0 && a.n_out >= 8192 && a.k == 512) return GEMV_ROWS_HEAD;  // the vocabulary head
+        return GEMV_ROWS_STAGED_FAST;
+    }
+    return staged ? GEMV_ROWS_STAGED : GEMV_ROWS_GENERAL;
+}
+
 hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
 {
-    if (a.rows <= 0 || a.n_out <= 0) return hipSuccess;
-    if ((a.embed_ids || a.x_raw_out || a.x_norm_out) && !gemv_rows_takes_row_extras(a)) return hipErrorInvalidValue;
-    const bool simple = !a.gamma && a.seg <= 0;
-    if (a.rows > GEMV_MAX_ROWS || (a.k & 3) || (a.ldx & 3) || (reinterpret_cast<uintptr_t>(a.X) & 15) ||
-        (reinterpret_cast<uintptr_t>(a.W) & 15)) {
-        if (!simple) return hipErrorInvalidValue;
+    const GemvRowsRoute route = gemv_rows_route(a);  // which kernel: every decision below is read from it
+    if (route == GEMV_ROWS_NOTHING) return hipSuccess;
+    if (route == GEMV_ROWS_REFUSED) return hipErrorInvalidValue;
+    if (route == GEMV_ROWS_GEMM)
         return launch_gemm(a.X, a.ldx, a.W, a.bias, a.R, a.ldr, a.Y0, a.ldy0, a.rows, a.n_out, a.k, a.epi, stream);
-    }
     const bool ln = a.gamma != nullptr;
-    // The (epilogue, LayerNorm) pairs whisper.cpp's decoder requests, and the only ones instantiated:
-    //   (EPI_BIAS, LN)             LN1 + Q|K|V, LN2 + cross Q, the one-token vocabulary head with the final LayerNorm folded in
-    //   (EPI_BIAS, none)           the vocabulary head after the final LayerNorm
-    //   (EPI_BIAS_GELU, LN)        LN3 + fc1 + GELU
-    //   (EPI_BIAS_RESIDUAL, none)  self / cross output projections, fc2 (+ residual)
-    // Any other pair is hipErrorInvalidValue.
-    if (a.epi == EPI_BIAS_GELU ? !ln : a.epi == EPI_BIAS_RESIDUAL ? ln : a.epi != EPI_BIAS) return hipErrorInvalidValue;
 #define KJ_PAIRS(LAUNCH)                                                                                                         \
     do {                                                                                                                         \
         if (a.epi == EPI_BIAS_GELU) LAUNCH(EPI_BIAS_GELU, true);                                                                 \
@@ -1074,10 +1121,8 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
         else LAUNCH(EPI_BIAS, false);                                                                                            \
     } while (0)
     const dim3 grid((unsigned)((a.n_out + 3) / 4));
-    // one row of 512 or 2048 floats (the Whisper-base decoder's widths): the variant with every request issued up front
     const int kch = a.k / 256;
-    if (a.rows == 1 && a.k % 256 == 0 && (kch == 2 || kch == 8) && (!ln || a.beta) &&
-        (!ln || ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0)) {
+    if (route == GEMV_ROWS_ONE_FAST || route == GEMV_ROWS_ONE_FAST_EMBED) {
         const GemvEmbed emb{a.embed_ids, a.embed_word, a.embed_pos_table, a.embed_vocab, a.embed_max_pos, a.embed_pos, a.embed_pos_ptr,
                             a.embed_scale};
 #define KJ_FAST2(EPI, LN, KCH, EMB)                                                                                                \
@@ -1088,8 +1133,7 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
         if (kch == 2) KJ_FAST2(EPI, LN, 2, false);                                                                                 \
         else KJ_FAST2(EPI, LN, 8, false);                                                                                          \
     } while (0)
-        if (a.embed_ids) {  // the first projection of a one-token step builds its input row itself (LN + Q | K | V, 512-float rows)
-            if (!(ln && a.epi == EPI_BIAS && kch == 2)) return hipErrorInvalidValue;
+        if (route == GEMV_ROWS_ONE_FAST_EMBED) {
             KJ_FAST2(EPI_BIAS, true, 2, true);
         } else {
             KJ_PAIRS(KJ_FAST);
@@ -1099,10 +1143,7 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
         return hipGetLastError();
     }
     const size_t lds = (size_t)a.rows * a.k * sizeof(float);
-    const bool staged = a.rows >= 2 && lds <= 64 * 1024;
-    const bool staged_fast = staged && a.k % 256 == 0 && (a.k / 256 == 2 || a.k / 256 == 8) && (!a.gamma || a.beta) &&
-                             ((reinterpret_cast<uintptr_t>(a.gamma) | reinterpret_cast<uintptr_t>(a.beta)) & 15) == 0;
-    if (staged_fast && !a.gamma && a.epi == EPI_BIAS && a.seg <= 0 && a.n_out >= 8192 && a.k == 512) {  // the vocabulary head
+    if (route == GEMV_ROWS_HEAD) {
         constexpr int CPW = 4;
         hipLaunchKernelGGL((gemv_rows_head_kernel<2, CPW>), dim3((unsigned)((a.n_out + 4 * CPW - 1) / (4 * CPW))), dim3(256), lds, stream,
                            a.X, a.ldx, a.rows, a.W, a.bias, a.n_out, a.Y0, a.ldy0);
@@ -1120,10 +1161,10 @@ hipError_t launch_gemv_rows(const GemvArgs& a, hipStream_t stream)
     } while (0)
 #define KJ_GEMV(EPI, LN)                                                                                                         \
     do {                                                                                                                         \
-        if (staged_fast) {                                                                                                       \
+        if (route == GEMV_ROWS_STAGED_FAST) {                                                                                    \
             if (a.k == 512) KJ_STAGED_FAST(EPI, LN, 2);                                                                          \
             else KJ_STAGED_FAST(EPI, LN, 8);                                                                                     \
-        } else if (staged) {                                                                                                     \
+        } else if (route == GEMV_ROWS_STAGED) {                                                                                  \
             auto kern = gemv_rows_lds_kernel<EPI, LN>;                                                                           \
             if (lds > 48 * 1024) {                                                                                               \
                 const hipError_t e = allow_dynamic_lds(kern, lds);                                                               \

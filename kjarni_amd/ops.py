@@ -403,6 +403,138 @@ def llm_qkv_rope(w, gamma, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, 
     return qa, ka, va, ro, dict(zip(("kernel", "ch", "workgroups"), list(route)))
 
 
+# ---- the Whisper decoder's row projections and the front-end kernels, alone ----
+(GEMV_ROWS_NOTHING, GEMV_ROWS_ONE_FAST, GEMV_ROWS_ONE_FAST_EMBED, GEMV_ROWS_STAGED_FAST, GEMV_ROWS_HEAD, GEMV_ROWS_STAGED, GEMV_ROWS_GENERAL,
+ GEMV_ROWS_GEMM, GEMV_ROWS_REFUSED) = range(9)
+MISALIGN_X, MISALIGN_W, MISALIGN_GAMMA, MISALIGN_BETA = 1, 2, 4, 8
+
+
+def gemv_rows(x, w, rows: int, ys, k: Optional[int] = None, n_out: Optional[int] = None, gamma=None, beta=None, eps: float = 0.0, bias=None,
+              r=None, r_is_y0: bool = False, seg: int = 0, row_off: int = 0, offset_on_device: bool = False, epi: int = EPI_BIAS, embed=None,
+              x_raw_out=None, x_norm_out=None, misalign: int = 0, device: int = 0):
+    """One launch_gemv_rows on host arrays (kjarni_hip_op_gemv_rows).  x [x_rows, ldx] (None with embed; k = w's width unless given);
+    w [n_out, k]; ys: 1 or 3 outputs [out_rows, ldy] as they are before the launch (seg > 0: Q, K, V; the two caches share their
+    stride); r [rows, ldr] or r_is_y0; embed: dict(id, word [vocab, k], pos_table [max_pos, k] or None, pos, pos_on_device, scale);
+    x_raw_out / x_norm_out [k] as they are before the launch.  Returns (outputs, x_raw_out or None, x_norm_out or None, route) --
+    copies."""
+    xa = None if x is None else np.ascontiguousarray(x, np.float32)
+    wa = np.ascontiguousarray(w, np.float32)
+    out = [np.array(y, np.float32, order="C") for y in ys]
+    if (xa is not None and xa.ndim != 2) or wa.ndim != 2 or len(out) not in (1, 3) or any(y.ndim != 2 for y in out):
+        raise ValueError("x: [x_rows, ldx]; w: [n_out, k]; ys: 1 or 3 arrays [out_rows, ldy]")
+    if len(out) == 3 and out[1].shape[1] != out[2].shape[1]:
+        raise ValueError("ys[1] and ys[2] share ldy12")
+    if (xa is None) == (embed is None):
+        raise ValueError("the input row is x or the embedding: exactly one of them")
+    nn = wa.shape[0] if n_out is None else int(n_out)
+    kk = wa.shape[1] if k is None else int(k)
+    g, be, b = _proj_vector(gamma, kk, "gamma"), _proj_vector(beta, kk, "beta"), _proj_vector(bias, max(nn, 1), "bias")
+    ra = None if r is None else np.ascontiguousarray(r, np.float32)
+    if ra is not None and (ra.ndim != 2 or ra.shape[0] < max(int(rows), 1)):
+        raise ValueError("r: [rows, ldr]")
+    raw = None if x_raw_out is None else np.array(x_raw_out, np.float32, order="C")
+    nrm = None if x_norm_out is None else np.array(x_norm_out, np.float32, order="C")
+    if any(t is not None and t.size != kk for t in (raw, nrm)):
+        raise ValueError("x_raw_out, x_norm_out: [k]")
+    ida = word = pos_t = None
+    vocab = max_pos = pos = pos_dev = 0
+    scale = 1.0
+    if embed is not None:
+        ida = np.array([int(embed["id"])], np.uint32)
+        word = np.ascontiguousarray(embed["word"], np.float32)
+        pos_t = None if embed.get("pos_table") is None else np.ascontiguousarray(embed["pos_table"], np.float32)
+        if word.ndim != 2 or word.shape[1] != kk or (pos_t is not None and (pos_t.ndim != 2 or pos_t.shape[1] != kk)):
+            raise ValueError("embed word: [vocab, k]; pos_table: [max_pos, k]")
+        vocab, max_pos = word.shape[0], 0 if pos_t is None else pos_t.shape[0]
+        pos, pos_dev, scale = int(embed.get("pos", 0)), int(bool(embed.get("pos_on_device", False))), float(embed.get("scale", 1.0))
+    yp = (C.c_void_p * 3)(*[y.ctypes.data for y in out])
+    orows = (C.c_int32 * 3)(*[y.shape[0] for y in out])
+    route = C.c_int32(-1)
+    check_error(lib().kjarni_hip_op_gemv_rows(device, _f(xa), 1 if xa is None else xa.shape[0], kk if xa is None else xa.shape[1], int(rows), _f(g),
+                                              _f(be), float(eps), _f(wa), _f(b), _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y0)), nn,
+                                              kk, int(seg), yp, orows, out[0].shape[1], out[1].shape[1] if len(out) == 3 else 0, int(row_off),
+                                              int(bool(offset_on_device)), int(epi), None if ida is None else ida.ctypes.data_as(_ffi._u32p),
+                                              _f(word), vocab, _f(pos_t), max_pos, pos, pos_dev, scale, _f(raw), _f(nrm), int(misalign),
+                                              C.byref(route)))
+    return out, raw, nrm, int(route.value)
+
+
+def gemv_rows_route(rows: int, n_out: int, k: int, ldx: Optional[int] = None, seg: int = 0, epi: int = EPI_BIAS, gamma: bool = False,
+                    beta: Optional[bool] = None, r: Optional[bool] = None, embed: bool = False, x_raw_out: bool = False, x_norm_out: bool = False,
+                    misalign: int = 0) -> int:
+    """gemv_rows_route (the rule launch_gemv_rows follows) for arguments given as sizes and flags; no device.  beta defaults to
+    gamma, r to what the epilogue needs."""
+    route = C.c_int32(-1)
+    check_error(lib().kjarni_hip_gemv_rows_route(int(rows), int(n_out), int(k), int(k if ldx is None else ldx), int(seg), int(epi), int(bool(gamma)),
+                                                 int(bool(gamma if beta is None else beta)), int(bool(epi == EPI_BIAS_RESIDUAL if r is None else r)),
+                                                 int(bool(embed)), int(bool(x_raw_out)), int(bool(x_norm_out)), int(misalign), C.byref(route)))
+    return int(route.value)
+
+
+def mel_frames(audio, window, hop: int, frames, device: int = 0) -> np.ndarray:
+    """launch_mel_frames on host arrays: frames [n_frames, ld] as it is before the launch; n_fft = len(window).  Returns a copy."""
+    a, wn = np.ascontiguousarray(audio, np.float32).reshape(-1), np.ascontiguousarray(window, np.float32).reshape(-1)
+    fr = np.array(frames, np.float32, order="C")
+    if fr.ndim != 2:
+        raise ValueError("frames: [n_frames, ld]")
+    check_error(lib().kjarni_hip_op_mel_frames(device, _f(a), a.size, _f(wn), wn.size, int(hop), fr.shape[0], fr.shape[1], _f(fr)))
+    return fr
+
+
+def mel_power(dft, im_off: int, n_bins: int, power, device: int = 0) -> np.ndarray:
+    """launch_mel_power: dft [n_frames, ld_dft] -> power [n_frames, ld_out] (as it is before the launch).  Returns a copy."""
+    d, pw = np.ascontiguousarray(dft, np.float32), np.array(power, np.float32, order="C")
+    if d.ndim != 2 or pw.ndim != 2 or d.shape[0] != pw.shape[0]:
+        raise ValueError("dft: [n_frames, ld_dft]; power: [n_frames, ld_out]")
+    check_error(lib().kjarni_hip_op_mel_power(device, _f(d), d.shape[1], int(im_off), int(n_bins), pw.shape[1], pw.shape[0], _f(pw)))
+    return pw
+
+
+def mel_log_normalize(mel, n_mels: int, out, device: int = 0):
+    """launch_mel_log_normalize: mel [n_frames, ld] and out [n_frames, ld_out] as they are before the launch.  Returns copies
+    (mel after the in-place log10, out)."""
+    m, o = np.array(mel, np.float32, order="C"), np.array(out, np.float32, order="C")
+    if m.ndim != 2 or o.ndim != 2 or m.shape[0] != o.shape[0]:
+        raise ValueError("mel: [n_frames, ld]; out: [n_frames, ld_out]")
+    check_error(lib().kjarni_hip_op_mel_log_normalize(device, _f(m), m.shape[1], int(n_mels), m.shape[0], o.shape[1], _f(o)))
+    return m, o
+
+
+def im2col3(x, channels: int, stride: int, pad: int, cols, device: int = 0) -> np.ndarray:
+    """launch_im2col3: x [t_in, ldx] -> cols [t_out, ld_cols] (as it is before the launch).  Returns a copy."""
+    xa, c = np.ascontiguousarray(x, np.float32), np.array(cols, np.float32, order="C")
+    if xa.ndim != 2 or c.ndim != 2:
+        raise ValueError("x: [t_in, ldx]; cols: [t_out, ld_cols]")
+    check_error(lib().kjarni_hip_op_im2col3(device, _f(xa), xa.shape[1], xa.shape[0], int(channels), int(stride), int(pad), c.shape[0], c.shape[1],
+                                            _f(c)))
+    return c
+
+
+def add_rows(x, period: int, table, table_rows: int, device: int = 0) -> np.ndarray:
+    """launch_add_rows: x [rows, hidden] += table [r % period] where r % period < table_rows; table [>= table_rows, hidden].
+    Returns a copy."""
+    xa, t = np.array(x, np.float32, order="C"), np.ascontiguousarray(table, np.float32)
+    if xa.ndim != 2 or t.ndim != 2 or t.shape[1] != xa.shape[1]:
+        raise ValueError("x: [rows, hidden]; table: [table rows, hidden]")
+    check_error(lib().kjarni_hip_op_add_rows(device, _f(xa), xa.shape[0], xa.shape[1], int(period), _f(t), int(table_rows), t.shape[0]))
+    return xa
+
+
+def decoder_embed(ids, word, pos, offset: int, out, offset_on_device: bool = False, scale_embeddings: bool = False, lanes: bool = False,
+                  device: int = 0) -> np.ndarray:
+    """launch_decoder_embed: ids [n], word [vocab, hidden], pos [max_pos, hidden] or None -> out [n, hidden] (as it is before the
+    launch).  Returns a copy."""
+    ia, wd = np.ascontiguousarray(ids, np.uint32).reshape(-1), np.ascontiguousarray(word, np.float32)
+    pt = None if pos is None else np.ascontiguousarray(pos, np.float32)
+    o = np.array(out, np.float32, order="C")
+    if wd.ndim != 2 or o.shape != (ia.size, wd.shape[1]) or (pt is not None and (pt.ndim != 2 or pt.shape[1] != wd.shape[1])):
+        raise ValueError("word: [vocab, hidden]; pos: [max_pos, hidden]; out: [n, hidden]")
+    check_error(lib().kjarni_hip_op_decoder_embed(device, ia.ctypes.data_as(_ffi._u32p), ia.size, wd.shape[1], wd.shape[0], _f(wd), _f(pt),
+                                                  0 if pt is None else pt.shape[0], int(offset), int(bool(offset_on_device)),
+                                                  int(bool(scale_embeddings)), int(bool(lanes)), _f(o)))
+    return o
+
+
 # ---- mixture-of-experts: the router pick and the sparse FFN, alone ----
 def moe_route(logits, k: int, norm_topk: bool = False, device: int = 0):
     """launch_moe_route on host arrays (kjarni_hip_op_moe_route): logits [rows, E] -> (ids int32 [rows, k], weights f32 [rows, k]),
