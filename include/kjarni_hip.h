@@ -1507,6 +1507,106 @@ KjarniErrorCode kjarni_hip_chat_set_constraint(KjarniChat* chat, const char* pat
 KjarniErrorCode kjarni_hip_generator_constraint_result(const KjarniGenerator* generator, KjarniHipConstraintResult* out);
 KjarniErrorCode kjarni_hip_chat_constraint_result(const KjarniChat* chat, KjarniHipConstraintResult* out);
 
+/* ---- constrained decoding with a stack: grammars compiled to a stack automaton, and its two kernels (NOT in the reference) ----
+ * A grammar is a list of rules (name, pattern); rule 0 is the start rule.  A pattern is the syntax above plus one construct,
+ * (?&name): a string of rule `name` here (names are [A-Za-z_][A-Za-z0-9_]*; kjarni_hip_regex_compile keeps refusing the
+ * construct).  The language is the context-free language the rules define, full match from rule 0, over bytes, with at most
+ * KJARNI_GRAMMAR_MAX_DEPTH calls open at a time: a string that nests deeper is not matched.
+ *
+ * Each rule compiles to a DFA over bytes and one symbol per called rule; the states of all rules share one numbering, state 0
+ * the start state of rule 0.  The table: action[states][256] (uint32) and flags[states].  Entry bits 31..30: 0 none, 1 move,
+ * 2 call.  A move holds the next state in bits 11..0; a call holds the callee's start state in bits 11..0 and the state to return
+ * to in bits 23..12.  Flags bit 0: accepting in its rule; bit 1: no_out, no byte has a move or a call.  One byte b at (state q,
+ * stack of return states, depth d):
+ *     loop: a = action[q][b]
+ *           move: q = a.next; done
+ *           call: d == 64 -> dead;  push a.ret;  q = a.next;  again      (the callee sees the same byte)
+ *           none: accepting[q] and d > 0 -> q = pop;  again               (the rule ended before this byte)
+ *                 otherwise dead
+ * A configuration is accepted when every level (the state and all return states) is accepting, and closed when every level is
+ * no_out.  The machine is deterministic by construction, and the compiler refuses, INVALID_CONFIG with the rule named (and the
+ * byte, where there is one), every grammar for which it would not recognise exactly the grammar's language: two ways to continue
+ * on one byte in one state (a byte edge and the FIRST set of a call, or two calls); a rule that may either end or go on at a byte
+ * that may also follow one of its calls (LL(1): FOLLOW through accepting return states, transitively); a called rule that matches
+ * the empty string; left recursion, direct or through a chain of first calls; a rule with no finite string; an undefined, duplicate
+ * or bad name; more than KJARNI_GRAMMAR_MAX_RULES rules or KJARNI_GRAMMAR_MAX_STATES states (the message gives the count); and
+ * every per-pattern refusal above, prefixed with the rule's name.  Rules that rule 0 never reaches are dropped. */
+#define KJARNI_GRAMMAR_MAX_RULES 256
+#define KJARNI_GRAMMAR_MAX_STATES 4096
+#define KJARNI_GRAMMAR_MAX_DEPTH 64
+#define KJARNI_GRAMMAR_TOKEN_PUSHES 16
+typedef struct KjarniHipGrammar KjarniHipGrammar;
+KjarniErrorCode kjarni_hip_grammar_compile(const char* const* names, const char* const* patterns, int32_t n_rules, KjarniHipGrammar** out);
+void kjarni_hip_grammar_free(KjarniHipGrammar* grammar);
+/* rules: the rules kept (those rule 0 reaches). */
+KjarniErrorCode kjarni_hip_grammar_dims(const KjarniHipGrammar* grammar, int32_t* states, int32_t* rules);
+/* action_out [states * 256], flags_out [states], rule_of_out [states] (the kept rule a state belongs to, rule 0 first); any may
+ * be NULL. */
+KjarniErrorCode kjarni_hip_grammar_table(const KjarniHipGrammar* grammar, uint32_t* action_out, uint8_t* flags_out, uint16_t* rule_of_out);
+/* The walk of bytes[n] from (state, stack[depth], depth), on the host.  *alive_out = 0 when the walk dies or the start is no
+ * configuration of the table (the other outputs are then left alone); else state_out, depth_out and stack_out [64, written up to
+ * the new depth].  as_token != 0: the bytes are one token's, and a walk that holds more than KJARNI_GRAMMAR_TOKEN_PUSHES of its
+ * own pushes at once dies: the rule the kernels keep. */
+KjarniErrorCode kjarni_hip_grammar_walk(const KjarniHipGrammar* grammar, uint32_t state, const uint16_t* stack, int32_t depth, const uint8_t* bytes,
+                                        size_t n, int32_t as_token, uint32_t* state_out, uint16_t* stack_out, int32_t* depth_out, int32_t* alive_out);
+/* The device object: the automaton and a token table (as kjarni_hip_constraint_new takes it) in device memory.  There is no
+ * mask made once per state: which tokens are legal depends on the stack.  A malformed table: INVALID_CONFIG before any GPU work.
+ * The grammar may be freed afterwards. */
+typedef struct KjarniHipGrammarConstraint KjarniHipGrammarConstraint;
+KjarniErrorCode kjarni_hip_grammar_constraint_new(int32_t device, const KjarniHipGrammar* grammar, const uint32_t* tok_off, const uint8_t* tok_bytes,
+                                                  int32_t vocab, KjarniHipGrammarConstraint** out);
+void kjarni_hip_grammar_constraint_free(KjarniHipGrammarConstraint* constraint);
+KjarniErrorCode kjarni_hip_grammar_constraint_dims(const KjarniHipGrammarConstraint* constraint, int32_t* states, int32_t* vocab);
+/* The two kernels alone, through their launchers, with a guard band behind every output buffer; every refusal (dimensions, a row
+ * that is no configuration of the automaton, more than 16 stop ids, another device) is made before any GPU work.  A row is
+ * states[r], depths[r] (0..64), stacks[r][64] and done[r].
+ * kjarni_hip_op_grammar_apply: logits [rows, ld] (rows <= 64, ld >= vocab): where done is clear, every token's bytes are walked
+ * from the row's configuration; a logit keeps its bits when its token has at least one byte and the walk does not die, or, for a
+ * stop id, when the configuration is accepted (whatever the stop id's bytes); every other logit of the row becomes -inf.
+ * logits_out [rows, ld]: all of it, the floats between vocab and ld included.
+ * kjarni_hip_op_grammar_advance: picked[rows] moves the rows in place and writes violated_out[rows]: a stop id in an accepted
+ * configuration keeps it and sets done; any other token walks its bytes and moves state, depth and stack (the stack words above the
+ * new depth are left as they were), done when the new configuration is closed; a token apply masks sets violated and done and
+ * moves nothing.  A row whose done is set is left alone.  log_cap > 0 (rows == 1 only): the state and depth after the step are
+ * stored at state_log[log_count - 1] / depth_log[log_count - 1] when that index is within log_cap, as the generation loop logs
+ * them behind each recorded pick; both arrays [log_cap], passed in and out. */
+KjarniErrorCode kjarni_hip_op_grammar_apply(int32_t device, const KjarniHipGrammarConstraint* constraint, const float* logits, int32_t rows, int64_t ld,
+                                            const uint32_t* states, const int32_t* depths, const uint16_t* stacks, const int32_t* done,
+                                            const uint32_t* stop_ids, int32_t n_stop, float* logits_out);
+KjarniErrorCode kjarni_hip_op_grammar_advance(int32_t device, const KjarniHipGrammarConstraint* constraint, const int32_t* picked, int32_t rows,
+                                              uint32_t* states, int32_t* depths, uint16_t* stacks, int32_t* done, const uint32_t* stop_ids,
+                                              int32_t n_stop, int32_t* violated_out, int32_t log_count, int32_t log_cap, uint32_t* state_log,
+                                              int32_t* depth_log);
+/* How a grammar-constrained call ended.  final_state / final_depth: the configuration's state and stack depth after the emitted
+ * tokens, as the host walked them; device_state / device_depth: the same as the device left them (equal unless violated);
+ * accepted: every level of the final configuration is accepting; complete: the run ended on a stop id in an accepted
+ * configuration or in a closed one (not on a limit or the callback); violated: a token outside the mask was picked (all-NaN
+ * logits, or a configuration with nothing left that the refusal below let through). */
+typedef struct KjarniHipGrammarResult { uint32_t final_state, device_state; int32_t final_depth, device_depth, accepted, complete, violated; } KjarniHipGrammarResult;
+/* kjarni_hip_decoder_generate_constrained with a grammar in the constraint's place: the same loop.  Plain greedy replays a third
+ * captured chain pass -> grammar apply -> argmax -> grammar advance in bursts, the host walking its own configuration per drained
+ * token; with processors or sampling the order is apply, processors, argmax or the sampler's cut, and the device automaton takes
+ * the host's choice before the token is fed; with device sampling off the same mask is applied to the host copy of the logits from
+ * the host's walk.  The run ends at a stop id, a closed configuration or the limits.  Before any GPU work, INVALID_CONFIG: a
+ * grammar constraint of another device or vocabulary, more than 16 stop ids, and the refusal on states: a state a run can be in
+ * (state 0 and wherever a token can end from such a state, a walk that pops below the token's own pushes going on in every return
+ * state of the calls of the rule it leaves: an over-approximation) that offers no token other than a stop id and is either not
+ * accepting, or accepting in rule 0 with a way on while the call has no stop id (the message names the state and its rule).  What
+ * that lets through is caught at run time and ends the run with violated = 1.  The lane, wide, lookup and draft entries refuse a
+ * grammar as they refuse a constraint.  result may be NULL. */
+KjarniErrorCode kjarni_hip_decoder_generate_grammar(KjarniHipDecoder* decoder, const KjarniHipGrammarConstraint* grammar, const uint32_t* prompt,
+                                                    size_t n_prompt, const KjarniHipSamplingOptions* options, KjarniTokenCallbackFn on_token,
+                                                    void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out,
+                                                    KjarniHipGrammarResult* result);
+/* A grammar for every later request of the handle, as kjarni_hip_generator_set_constraint sets a pattern (names / patterns NULL or
+ * n_rules <= 0: none).  A handle holds a pattern or a grammar: setting a grammar clears a set pattern and the other way round.  The
+ * token table comes from the handle's own tokenizer.  A refused grammar leaves the handle as it was. */
+KjarniErrorCode kjarni_hip_generator_set_grammar(KjarniGenerator* generator, const char* const* names, const char* const* patterns, int32_t n_rules);
+KjarniErrorCode kjarni_hip_chat_set_grammar(KjarniChat* chat, const char* const* names, const char* const* patterns, int32_t n_rules);
+/* The result of the handle's last request under a grammar (zeros before one). */
+KjarniErrorCode kjarni_hip_generator_grammar_result(const KjarniGenerator* generator, KjarniHipGrammarResult* out);
+KjarniErrorCode kjarni_hip_chat_grammar_result(const KjarniChat* chat, KjarniHipGrammarResult* out);
+
 #ifdef __cplusplus
 }
 #endif

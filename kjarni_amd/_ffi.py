@@ -264,6 +264,11 @@ class KjarniHipConstraintResult(Structure):
                 ("violated", c_int32)]
 
 
+class KjarniHipGrammarResult(Structure):
+    _fields_ = [("final_state", C.c_uint32), ("device_state", C.c_uint32), ("final_depth", c_int32), ("device_depth", c_int32),
+                ("accepted", c_int32), ("complete", c_int32), ("violated", c_int32)]
+
+
 class KjarniScoreResult(Structure):
     _fields_ = [("sum_logprob", C.c_double), ("n_tokens", c_size_t), ("is_greedy", c_int32)]
 
@@ -655,6 +660,27 @@ SIGNATURES = {
     "kjarni_hip_chat_set_constraint": (c_int32, [c_void_p, c_char_p]),
     "kjarni_hip_generator_constraint_result": (c_int32, [c_void_p, POINTER(KjarniHipConstraintResult)]),
     "kjarni_hip_chat_constraint_result": (c_int32, [c_void_p, POINTER(KjarniHipConstraintResult)]),
+    # constrained decoding with a stack: the grammar compiler, the host walk, the device object and the two kernels alone
+    "kjarni_hip_grammar_compile": (c_int32, [POINTER(c_char_p), POINTER(c_char_p), c_int32, POINTER(c_void_p)]),
+    "kjarni_hip_grammar_free": (None, [c_void_p]),
+    "kjarni_hip_grammar_dims": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_grammar_table": (c_int32, [c_void_p, _u32p, POINTER(C.c_uint8), POINTER(C.c_uint16)]),
+    "kjarni_hip_grammar_walk": (c_int32, [c_void_p, C.c_uint32, POINTER(C.c_uint16), c_int32, POINTER(C.c_uint8), c_size_t, c_int32, _u32p,
+                                          POINTER(C.c_uint16), POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_grammar_constraint_new": (c_int32, [c_int32, c_void_p, _u32p, POINTER(C.c_uint8), c_int32, POINTER(c_void_p)]),
+    "kjarni_hip_grammar_constraint_free": (None, [c_void_p]),
+    "kjarni_hip_grammar_constraint_dims": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_op_grammar_apply": (c_int32, [c_int32, c_void_p, _f32p, c_int32, c_int64, _u32p, POINTER(c_int32), POINTER(C.c_uint16),
+                                              POINTER(c_int32), _u32p, c_int32, _f32p]),
+    "kjarni_hip_decoder_generate_grammar": (c_int32, [c_void_p, c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
+                                                      KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
+                                                      POINTER(KjarniHipGrammarResult)]),
+    "kjarni_hip_generator_set_grammar": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_int32]),
+    "kjarni_hip_chat_set_grammar": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_int32]),
+    "kjarni_hip_generator_grammar_result": (c_int32, [c_void_p, POINTER(KjarniHipGrammarResult)]),
+    "kjarni_hip_chat_grammar_result": (c_int32, [c_void_p, POINTER(KjarniHipGrammarResult)]),
+    "kjarni_hip_op_grammar_advance": (c_int32, [c_int32, c_void_p, POINTER(c_int32), c_int32, _u32p, POINTER(c_int32), POINTER(C.c_uint16),
+                                                POINTER(c_int32), _u32p, c_int32, POINTER(c_int32), c_int32, c_int32, _u32p, POINTER(c_int32)]),
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),

@@ -189,7 +189,7 @@ class Chat:
     def set_constraint(self, pattern: Optional[str]):
         """Constrained decoding for send(): every later reply is text that `pattern` matches in full (builders in
         kjarni_amd.constraints); None restores the plain behaviour.  While set, requests take the plain loop even when prompt
-        lookup or a draft model is switched on.  Nested or recursive JSON schemas are out of scope."""
+        lookup or a draft model is switched on.  Nested or recursive JSON is a grammar: set_grammar."""
         check_error(lib().kjarni_hip_chat_set_constraint(self._handle, pattern.encode("utf-8") if pattern else None))
 
     def constraint_result(self):
@@ -198,6 +198,23 @@ class Chat:
         r = _ffi.KjarniHipConstraintResult()
         check_error(lib().kjarni_hip_chat_constraint_result(self._handle, C.byref(r)))
         return result_dict(r)
+
+    def set_grammar(self, rules):
+        """Constrained decoding under a grammar: rules [(name, pattern)] as kjarni_amd.constraints.json_value / json_schema
+        return them (rule 0 the start rule, patterns calling each other with (?&name)); None or [] removes it.  A handle holds a
+        pattern or a grammar: setting one clears the other.  Requests take the plain loop as under set_constraint."""
+        rules = list(rules or [])
+        names = (C.c_char_p * max(len(rules), 1))(*[n.encode("utf-8") for n, _ in rules])
+        pats = (C.c_char_p * max(len(rules), 1))(*[p.encode("utf-8") for _, p in rules])
+        check_error(lib().kjarni_hip_chat_set_grammar(self._handle, names, pats, len(rules)))
+
+    def grammar_result(self):
+        """How the last request under a grammar ended: final_state, final_depth, device_state, device_depth, accepted, complete,
+        violated."""
+        from .constraints import grammar_result_dict
+        r = _ffi.KjarniHipGrammarResult()
+        check_error(lib().kjarni_hip_chat_grammar_result(self._handle, C.byref(r)))
+        return grammar_result_dict(r)
 
     def verify_gemv_calls(self):
         """(streamed, fallback) projections of verify steps since load: moves only when a call took a lookup or a draft loop."""

@@ -356,12 +356,14 @@ GenerateOptions text_generation_options(const LlmModel& model, size_t n_tokens, 
 std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const std::vector<uint32_t>& tokens, const GenerationConfig& config,
                                 const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
                                 int prompt_lookup = 0, int sampled_lookup = 0, LlmModel* drafter = nullptr, int draft_tokens = 0,
-                                const DeviceConstraint* constraint = nullptr, ConstraintOutcome* outcome = nullptr)
+                                const DeviceConstraint* constraint = nullptr, ConstraintOutcome* outcome = nullptr,
+                                const DeviceGrammar* grammar = nullptr)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
     opt.constraint = constraint;
-    opt.constraint_outcome = constraint ? outcome : nullptr;
+    opt.grammar = grammar;
+    opt.constraint_outcome = constraint || grammar ? outcome : nullptr;
     std::string text;
     std::vector<uint32_t> prompt_tokens = tokens;
     if ((int)prompt_tokens.size() > model.context()) prompt_tokens.resize((size_t)model.context());
@@ -373,7 +375,7 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
     // a draft model (when set) takes precedence over prompt lookup: greedy requests without processors and sampled requests
     // without an n-gram ban verify the drafter's proposals every step; the others take the plain loop inside generate_draft
     // (a constrained request takes the plain loop: the lookup and draft loops do not carry the automaton)
-    if (constraint) {
+    if (constraint || grammar) {
         model.generate(prompt_tokens, opt, on_token);
     } else if (drafter && draft_tokens > 0) {
         model.generate_draft(drafter, prompt_tokens, opt, draft_tokens, on_token, nullptr);
@@ -548,16 +550,57 @@ static void set_handle_constraint(const LlmModel& model, const BpeTokenizer& tok
     current = pattern;
 }
 
+// The grammar of a handle: the rules compiled and placed on the model's device with the same token table; no rule frees it.
+static void set_handle_grammar(const LlmModel& model, const BpeTokenizer& tok, const std::vector<std::pair<std::string, std::string>>& rules,
+                               std::unique_ptr<DeviceGrammar>& grammar)
+{
+    if (rules.empty()) {
+        grammar.reset();
+        return;
+    }
+    Grammar compiled;
+    try {
+        compiled = compile_grammar(rules);
+    } catch (const GrammarError& e) {
+        throw InvalidConfig(e.what());
+    }
+    TokenTable table;
+    const size_t vocab = (size_t)model.config().vocab;
+    table.off.assign(vocab + 1, 0);
+    for (size_t t = 0; t < vocab; ++t) {
+        const std::string bytes = tok.token_bytes((uint32_t)t);
+        table.bytes.insert(table.bytes.end(), bytes.begin(), bytes.end());
+        table.off[t + 1] = (uint32_t)table.bytes.size();
+    }
+    grammar = std::make_unique<DeviceGrammar>(model.device(), std::move(compiled), std::move(table));
+}
+
 void Chat::set_constraint(const std::string& pattern)
 {
     std::lock_guard<std::mutex> lock(mutex_);
     set_handle_constraint(*model_, tokenizer_, pattern, constraint_pattern_, constraint_);
+    if (constraint_) grammar_.reset();
 }
 
 void Generator::set_constraint(const std::string& pattern)
 {
     std::lock_guard<std::mutex> lock(mutex_);
     set_handle_constraint(*model_, tokenizer_, pattern, constraint_pattern_, constraint_);
+    if (constraint_) grammar_.reset();
+}
+
+void Chat::set_grammar(const std::vector<std::pair<std::string, std::string>>& rules)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_grammar(*model_, tokenizer_, rules, grammar_);
+    if (grammar_) set_handle_constraint(*model_, tokenizer_, "", constraint_pattern_, constraint_);
+}
+
+void Generator::set_grammar(const std::vector<std::pair<std::string, std::string>>& rules)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    set_handle_grammar(*model_, tokenizer_, rules, grammar_);
+    if (grammar_) set_handle_constraint(*model_, tokenizer_, "", constraint_pattern_, constraint_);
 }
 
 void Chat::set_draft_model(const std::string& path, int draft_tokens)
@@ -579,7 +622,7 @@ std::string Chat::run(const std::string& prompt, const GenerationOverrides& runt
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, 0,
                                lookup_sampling_ ? LookupConfig().draft_tokens : 0, drafter_.get(), draft_tokens_, constraint_.get(),
-                               &constraint_outcome_);
+                               &constraint_outcome_, grammar_.get());
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -664,7 +707,8 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_,
-                               lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_, constraint_.get(), &constraint_outcome_);
+                               lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_, constraint_.get(), &constraint_outcome_,
+                               grammar_.get());
 }
 
 size_t Generator::encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const

@@ -18,6 +18,7 @@
 
 #include "bpe.h"
 #include "constraint_kernels.h"
+#include "grammar_kernels.h"
 #include "llm.h"
 #include "registry.h"
 #include "sampling.h"
@@ -114,6 +115,9 @@ public:
     // InvalidConfig for a pattern the compiler refuses.  Nested or recursive formats (JSON schemas) are out of scope.
     void set_constraint(const std::string& pattern);
     ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }  // of the last constrained request
+    // The same with a grammar (grammar.h: rules (name, pattern), rule 0 the start rule) in the pattern's place; no rule removes it.
+    // A handle holds a pattern or a grammar: setting one clears the other.  constraint_outcome() reports either kind of request.
+    void set_grammar(const std::vector<std::pair<std::string, std::string>>& rules);
 
 private:
     Chat() = default;
@@ -135,6 +139,7 @@ private:
     int draft_tokens_ = 0;
     std::string constraint_pattern_;
     std::unique_ptr<DeviceConstraint> constraint_;
+    std::unique_ptr<DeviceGrammar> grammar_;
     ConstraintOutcome constraint_outcome_;
     std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
 };
@@ -182,6 +187,7 @@ public:
     // Constrained decoding for generate / stream (Chat::set_constraint's contract); generate_batch is untouched.
     void set_constraint(const std::string& pattern);
     ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }
+    void set_grammar(const std::vector<std::pair<std::string, std::string>>& rules);  // (Chat::set_grammar's contract)
     // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
     // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
     // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
@@ -229,6 +235,7 @@ private:
     int draft_tokens_ = 0;
     std::string constraint_pattern_;
     std::unique_ptr<DeviceConstraint> constraint_;
+    std::unique_ptr<DeviceGrammar> grammar_;
     ConstraintOutcome constraint_outcome_;
 };
 

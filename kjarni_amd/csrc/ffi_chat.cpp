@@ -832,6 +832,51 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_constraint(KjarniChat* chat, c
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->set_constraint(pattern ? pattern : ""); });
 }
 
+// A grammar for every later request of the handle (Chat::set_grammar): NULL / no rule removes it.
+static std::vector<std::pair<std::string, std::string>> grammar_rules(const char* const* names, const char* const* patterns, int32_t n_rules)
+{
+    std::vector<std::pair<std::string, std::string>> rules;
+    if (!names || !patterns || n_rules <= 0) return rules;
+    if (n_rules > KJARNI_GRAMMAR_MAX_RULES)
+        throw InvalidConfig("grammar: " + std::to_string(n_rules) + " rules, the limit is " + std::to_string(KJARNI_GRAMMAR_MAX_RULES));
+    for (int32_t r = 0; r < n_rules; ++r) {
+        if (!names[r] || !patterns[r]) throw InvalidConfig("grammar: rule " + std::to_string(r) + " is NULL");
+        rules.emplace_back(names[r], patterns[r]);
+    }
+    return rules;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_grammar(KjarniGenerator* gen, const char* const* names, const char* const* patterns, int32_t n_rules)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->set_grammar(grammar_rules(names, patterns, n_rules)); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_grammar(KjarniChat* chat, const char* const* names, const char* const* patterns, int32_t n_rules)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->set_grammar(grammar_rules(names, patterns, n_rules)); });
+}
+
+static KjarniHipGrammarResult grammar_result(const ConstraintOutcome& o)
+{
+    return KjarniHipGrammarResult{o.final_state, o.device_state, o.final_depth, o.device_depth, o.accepted ? 1 : 0, o.complete ? 1 : 0, o.violated ? 1 : 0};
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_grammar_result(const KjarniGenerator* gen, KjarniHipGrammarResult* out)
+{
+    if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = grammar_result(gen->inner->constraint_outcome());
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_grammar_result(const KjarniChat* chat, KjarniHipGrammarResult* out)
+{
+    if (!chat || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = grammar_result(chat->inner->constraint_outcome());
+    return KJARNI_OK;
+}
+
 static KjarniHipConstraintResult constraint_result(const ConstraintOutcome& o)
 {
     return KjarniHipConstraintResult{o.final_state, o.device_state, o.accepted ? 1 : 0, o.complete ? 1 : 0, o.violated ? 1 : 0};

@@ -14,6 +14,7 @@
 #include "../../include/kjarni_hip.h"
 #include "ffi_common.h"
 #include "ffi_constraint.h"
+#include "ffi_grammar.h"
 #include "llm.h"
 #include "fp8_weights.h"
 #include "gguf.h"
@@ -522,6 +523,50 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_constrained(KjarniHipD
         if (result)
             *result = KjarniHipConstraintResult{outcome.final_state, outcome.device_state, outcome.accepted ? 1 : 0, outcome.complete ? 1 : 0,
                                                 outcome.violated ? 1 : 0};
+    });
+}
+
+// kjarni_hip_decoder_generate_constrained with a grammar in the constraint's place (options.grammar): the same loop, the draws as there.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_grammar(KjarniHipDecoder* d, const KjarniHipGrammarConstraint* grammar, const uint32_t* prompt,
+                                                                  size_t n_prompt, const KjarniHipSamplingOptions* options,
+                                                                  KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out, size_t capacity,
+                                                                  size_t* n_out, KjarniHipGrammarResult* result)
+{
+    if (!options || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    if (result) *result = KjarniHipGrammarResult{};
+    if (options->uniforms && options->n_uniforms < options->max_new_tokens) {  // (the options are judged on their own, ahead of the handles)
+        set_last_error("n_uniforms (" + std::to_string(options->n_uniforms) + ") is less than max_new_tokens (" +
+                       std::to_string(options->max_new_tokens) + ")");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!d || !grammar || (n_prompt && !prompt) || (capacity && !ids_out) || (options->n_stop && !options->stop_ids)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_prompt == 0) throw InvalidConfig("cannot generate from an empty prompt");
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (n_prompt > (size_t)d->model->context())
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
+        GenerateOptions opt = sampling_options(*options);
+        UniformRng rng(options->seed);
+        size_t drawn = 0;
+        const float* u = options->uniforms;
+        const size_t n_u = options->n_uniforms;
+        if (u)
+            opt.uniform = [&drawn, u, n_u] {
+                if (drawn >= n_u) throw std::runtime_error("the draw stream is exhausted: more draws than uniforms");
+                return u[drawn++];
+            };
+        else opt.uniform = [&rng] { return rng.next(); };
+        ConstraintOutcome outcome;
+        opt.grammar = grammar->inner.get();
+        opt.constraint_outcome = &outcome;
+        const std::vector<uint32_t> ids = d->model->generate(std::vector<uint32_t>(prompt, prompt + n_prompt), opt, cb);  // refusals first
+        copy_ids_out(ids, ids_out, capacity, n_out);
+        if (result)
+            *result = KjarniHipGrammarResult{outcome.final_state, outcome.device_state, outcome.final_depth, outcome.device_depth,
+                                             outcome.accepted ? 1 : 0, outcome.complete ? 1 : 0, outcome.violated ? 1 : 0};
     });
 }
 

@@ -12,14 +12,17 @@
 namespace kjarni {
 
 class DeviceConstraint;  // constraint_kernels.h
+class DeviceGrammar;     // grammar_kernels.h
 
-// How a constrained run ended (LlmModel::generate with GenerateOptions::constraint).
+// How a constrained run ended (LlmModel::generate with GenerateOptions::constraint or ::grammar; under a grammar "state" reads
+// "configuration": accepted = every level accepting, closed = every level without a way on).
 struct ConstraintOutcome {
     uint32_t final_state = 0;   // the automaton's state after the emitted tokens, as the host walked it
     uint32_t device_state = 0;  // ... and as the device held it after the last emitted token (the host checker path: the host's)
     bool accepted = false;      // final_state is accepting
     bool complete = false;      // the run ended on a stop id in an accepting state, or in a closed state
     bool violated = false;      // a token outside the mask was picked (never, for finite logits)
+    int32_t final_depth = 0, device_depth = 0;  // under a grammar: the stack depths that go with the two states
 };
 
 // One run of run_generation_loop (generator.rs:228-381).
@@ -35,6 +38,8 @@ struct GenerateOptions {
     // Constrained decoding: generate() alone takes it (the lane, lookup and draft entry points refuse it).
     const DeviceConstraint* constraint = nullptr;
     ConstraintOutcome* constraint_outcome = nullptr;  // may be null
+    // ... or a grammar (a stack automaton: grammar_kernels.h) in its place; setting both is InvalidConfig.  The outcome as above.
+    const DeviceGrammar* grammar = nullptr;
 };
 
 // What a loop does with the last token of a run that ends on max_new_tokens.  The choice shows in the cache length a call

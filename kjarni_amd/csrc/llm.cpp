@@ -19,6 +19,7 @@
 #include "llm_kernels.h"
 #include "moe_kernels.h"
 #include "constraint_kernels.h"
+#include "grammar_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
 #include "safetensors.h"
@@ -243,6 +244,7 @@ LlmModel::~LlmModel()
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (graph_) (void)hipGraphExecDestroy(graph_);
     if (cgraph_) (void)hipGraphExecDestroy(cgraph_);
+    if (ggraph_) (void)hipGraphExecDestroy(ggraph_);
     drop_graphs(lane_graphs_);
     drop_graphs(wide_graphs_);
     drop_graphs(lookup_graphs_);
@@ -1422,6 +1424,66 @@ hipGraphExec_t LlmModel::constrained_step_graph()
     });
 }
 
+void LlmModel::ensure_grammar()
+{
+    if (gview_) return;
+    gview_ = reinterpret_cast<GrammarView*>(dalloc((sizeof(GrammarView) + 3) / 4));
+    grow_ = reinterpret_cast<GrammarRow*>(dalloc((sizeof(GrammarRow) + 3) / 4));
+    gstate_log_ = reinterpret_cast<uint32_t*>(dalloc((size_t)hist_cap_));
+    gdepth_log_ = reinterpret_cast<int32_t*>(dalloc((size_t)hist_cap_));
+}
+
+hipGraphExec_t LlmModel::grammar_step_graph()
+{
+    if (ggraph_) return ggraph_;
+    return ggraph_ = capture_graph(stream_, [&] {
+        pass(reinterpret_cast<const uint32_t*>(token_), 1, true);
+        hip_check(launch_grammar_apply(logits_, cfg_.vocab, 1, cfg_.vocab, gview_, grow_, stream_), "grammar apply");
+        enqueue_argmax(true);
+        hip_check(launch_grammar_advance(token_, 1, gview_, grow_, gstate_log_, gdepth_log_, count_, hist_cap_, stream_), "grammar advance");
+    });
+}
+
+namespace {
+
+// What generate() needs of the host's copy of the automaton, regular (a DeviceConstraint: one state) or with a stack (a
+// DeviceGrammar: a configuration).  The loop below is written once against it.
+struct AutomatonCursor {
+    const DeviceConstraint* con = nullptr;
+    const DeviceGrammar* gram = nullptr;
+    uint32_t hq = 0;   // under a constraint
+    GrammarConfig hc;  // under a grammar
+
+    explicit operator bool() const { return con || gram; }
+    uint32_t state() const { return con ? hq : hc.state; }
+    int32_t depth() const { return con ? 0 : hc.depth; }
+    bool accepting() const { return con ? con->dfa().accepting[hq] != 0 : gram->grammar().accepted(hc); }
+    bool closed() const { return con ? con->dfa().closed[hq] != 0 : gram->grammar().closed(hc); }
+    // Would the mask leave token t (no stop id) as it is?
+    bool allows(uint32_t t) const
+    {
+        if (con) return con->allows(hq, t);
+        GrammarConfig c = hc;
+        return gram->step_token(&c, t);
+    }
+    // Moves by token t; false (and no move) when the mask does not allow it.
+    bool step(uint32_t t)
+    {
+        if (con) {
+            const uint32_t next = con->allows(hq, t) ? con->step_token(hq, t) : (uint32_t)kConstraintDead;
+            if (next == kConstraintDead) return false;
+            hq = next;
+            return true;
+        }
+        GrammarConfig c = hc;
+        if (!gram->step_token(&c, t)) return false;
+        hc = c;
+        return true;
+    }
+};
+
+}  // namespace
+
 void LlmModel::ensure_host_logits()
 {
     if (!host_logits_) hip_check(hipHostMalloc((void**)&host_logits_, (size_t)cfg_.vocab * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
@@ -1469,14 +1531,69 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
                                 std::to_string(cfg_.vocab));
         con->check_states(opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids);
     }
+    const DeviceGrammar* gram = opt.grammar;
+    if (gram) {
+        if (con) throw InvalidConfig("a call takes a constraint or a grammar, not both");
+        if (gram->device() != device_)
+            throw InvalidConfig("the grammar lives on device " + std::to_string(gram->device()) + ", the model on device " + std::to_string(device_));
+        if (gram->vocab() != cfg_.vocab)
+            throw InvalidConfig("the grammar's token table has " + std::to_string(gram->vocab()) + " tokens, the model's vocabulary " +
+                                std::to_string(cfg_.vocab));
+        gram->check_states(opt.stop_ids.empty() ? cfg_.eos_ids : opt.stop_ids);
+    }
     begin_sequence(prompt);
     std::vector<uint32_t> out;
     GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
     // The constrained run: the host walks its own copy of the automaton over the tokens it takes (`hq`), the device holds the
     // state the kernels read (crow_).  take() is run.accept() under the constraint: a stop id ends the run (complete when the
     // state is accepting), any other token moves hq, and a closed state ends the run behind the token.
+    // Under a grammar the same holds with "configuration" for "state" (grow_, the kernels of grammar_kernels.h).
     ConstraintOutcome outcome;
-    uint32_t hq = con ? con->dfa().start : 0;
+    AutomatonCursor cur;
+    cur.con = con;
+    cur.gram = gram;
+    cur.hq = con ? con->dfa().start : 0;
+    const uint32_t hq = cur.hq;
+    if (gram) {
+        ensure_grammar();
+        const GrammarView view = gram->view(run.stops);
+        GrammarRow row = {};
+        hip_check(hipMemcpyAsync(gview_, &view, sizeof(view), hipMemcpyHostToDevice, stream_), "H2D grammar view");
+        hip_check(hipMemcpyAsync(grow_, &row, sizeof(row), hipMemcpyHostToDevice, stream_), "H2D grammar state");
+        hip_check(hipStreamSynchronize(stream_), "sync");  // (both sources are locals)
+    }
+    const auto launch_apply = [&] {
+        if (con) hip_check(launch_constraint_apply(logits_, (int64_t)cfg_.vocab, 1, cfg_.vocab, cview_, crow_, stream_), "constraint apply");
+        if (gram) hip_check(launch_grammar_apply(logits_, (int64_t)cfg_.vocab, 1, cfg_.vocab, gview_, grow_, stream_), "grammar apply");
+    };
+    const auto launch_advance = [&](bool logged) {
+        if (con)
+            hip_check(launch_constraint_advance(token_, 1, cview_, crow_, logged ? cstate_log_ : nullptr, logged ? count_ : nullptr,
+                                                logged ? hist_cap_ : 0, stream_), "constraint advance");
+        if (gram)
+            hip_check(launch_grammar_advance(token_, 1, gview_, grow_, logged ? gstate_log_ : nullptr, logged ? gdepth_log_ : nullptr,
+                                             logged ? count_ : nullptr, logged ? hist_cap_ : 0, stream_), "grammar advance");
+    };
+    // The device's row after the run: its state (and depth), and whether any step picked a masked token.
+    const auto read_device_row = [&](bool state_too) {
+        if (con) {
+            ConstraintRow row = {};
+            hip_check(hipMemcpyAsync(&row, crow_, sizeof(row), hipMemcpyDeviceToHost, stream_), "D2H constraint state");
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            if (state_too) outcome.device_state = row.state;
+            outcome.violated = outcome.violated || row.violated != 0;
+        }
+        if (gram) {
+            GrammarRow row = {};
+            hip_check(hipMemcpyAsync(&row, grow_, 16, hipMemcpyDeviceToHost, stream_), "D2H grammar state");  // (state, depth, done, violated)
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            if (state_too) {
+                outcome.device_state = row.state;
+                outcome.device_depth = row.depth;
+            }
+            outcome.violated = outcome.violated || row.violated != 0;
+        }
+    };
     if (con) {
         ensure_constraint();
         const ConstraintView view = con->view(run.stops);
@@ -1487,31 +1604,30 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         outcome.device_state = hq;
     }
     const auto take = [&](uint32_t tok) -> bool {
-        if (!con) return run.accept(tok, on_token);
+        if (!cur) return run.accept(tok, on_token);
         if (!run.wants_token()) {
             run.done = true;
             return false;
         }
         if (run.is_stop(tok)) {
-            (con->dfa().accepting[hq] ? outcome.complete : outcome.violated) = true;
+            (cur.accepting() ? outcome.complete : outcome.violated) = true;
             run.done = true;
             return false;
         }
-        const uint32_t next = con->allows(hq, tok) ? con->step_token(hq, tok) : (uint32_t)kConstraintDead;
-        if (next == kConstraintDead) {
+        if (!cur.step(tok)) {
             outcome.violated = true;
             run.done = true;
             return false;
         }
-        hq = next;
         const bool taken = run.accept(tok, on_token);
-        if (con->dfa().closed[hq]) outcome.complete = run.done = true;
+        if (cur.closed()) outcome.complete = run.done = true;
         return taken;
     };
     const auto finish = [&] {
-        if (!con) return;
-        outcome.final_state = hq;
-        outcome.accepted = con->dfa().accepting[hq] != 0;
+        if (!cur) return;
+        outcome.final_state = cur.state();
+        outcome.final_depth = cur.depth();
+        outcome.accepted = cur.accepting();
         if (opt.constraint_outcome) *opt.constraint_outcome = outcome;
     };
     const float repetition_penalty = opt.repetition_penalty;
@@ -1555,7 +1671,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         }
         int skip_candidates = 0;
         while (run.wants_token()) {
-            if (con) hip_check(launch_constraint_apply(logits_, (int64_t)vocab, 1, (int)vocab, cview_, crow_, stream_), "constraint apply");
+            launch_apply();
             if (processors)
                 hip_check(launch_logits_processors(logits_, (int)vocab, samp_tokens_, (int)run.all.size(), samp_counts_, samp_distinct_,
                                                    samp_ndistinct_, repetition_penalty, no_repeat_ngram, stream_), "logits processors");
@@ -1592,21 +1708,15 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             // LastToken::Fed: one step per emitted token, the last of max_new_tokens included -- under an explicit max_len past
             // prompt + max_new_tokens; with the default max_len that token fills context_limit and is not fed
             if (!take(next)) break;
-            if (con) {  // the device's automaton takes the host's choice (fed or not, so that it ends where the host's does)
+            if (cur) {  // the device's automaton takes the host's choice (fed or not, so that it ends where the host's does)
                 const int32_t tok = (int32_t)next;
                 hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
-                hip_check(launch_constraint_advance(token_, 1, cview_, crow_, nullptr, nullptr, 0, stream_), "constraint advance");
+                launch_advance(false);
             }
             if (outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;  // (a closed state: nothing follows the token)
             feed(next);
         }
-        if (con) {
-            ConstraintRow row = {};
-            hip_check(hipMemcpyAsync(&row, crow_, sizeof(row), hipMemcpyDeviceToHost, stream_), "D2H constraint state");
-            hip_check(hipStreamSynchronize(stream_), "sync");
-            outcome.device_state = row.state;
-            outcome.violated = outcome.violated || row.violated != 0;
-        }
+        read_device_row(true);
         finish();
         leave_resident(run.all);
         return out;
@@ -1623,9 +1733,11 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         while (run.wants_token()) {
             hip_check(hipMemcpyAsync(lg, logits_, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
             hip_check(hipStreamSynchronize(stream_), "sync");
-            if (con)  // the same mask from the host's DFA and token table
+            if (cur) {  // the same mask from the host's automaton and token table
+                const bool accepting = cur.accepting();
                 for (size_t v = 0; v < vocab; ++v)
-                    if (!(run.is_stop((uint32_t)v) ? con->dfa().accepting[hq] != 0 : con->allows(hq, (uint32_t)v))) lg[v] = -INFINITY;
+                    if (!(run.is_stop((uint32_t)v) ? accepting : cur.allows((uint32_t)v))) lg[v] = -INFINITY;
+            }
             apply_repetition_penalty(lg, vocab, run.all, repetition_penalty);
             if (no_repeat_ngram > 0) apply_no_repeat_ngram(lg, vocab, run.all, (size_t)no_repeat_ngram);
             uint32_t next;
@@ -1639,7 +1751,8 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             if (!take(next) || outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;
             feed(next);
         }
-        outcome.device_state = hq;  // (no device automaton on this path)
+        outcome.device_state = cur.state();  // (no device automaton on this path)
+        outcome.device_depth = cur.depth();
         finish();
         leave_resident(run.all);
         return out;
@@ -1650,27 +1763,35 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     // a burst is sized by what is left of max_new_tokens, so the last token of max_new_tokens is not fed (LastToken::NotFed).
     // Constrained: the chain is pass -> apply -> argmax -> advance; the host steps its own automaton per drained token and ends the
     // run at a stop id, a closed state or the limits, discarding what the device ran past that point as it does past a stop id.
-    if (con) hip_check(launch_constraint_apply(logits_, (int64_t)vocab, 1, (int)vocab, cview_, crow_, stream_), "constraint apply");
+    launch_apply();
     enqueue_argmax(true);
-    if (con) hip_check(launch_constraint_advance(token_, 1, cview_, crow_, cstate_log_, count_, hist_cap_, stream_), "constraint advance");
+    launch_advance(true);
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     std::vector<int32_t> hist((size_t)hist_cap_);
-    std::vector<uint32_t> states(con ? (size_t)hist_cap_ : 0);
+    std::vector<uint32_t> states(cur ? (size_t)hist_cap_ : 0);
+    std::vector<int32_t> depths(gram ? (size_t)hist_cap_ : 0);
     size_t produced = 0, seen = 0;
     auto drain = [&](size_t upto) {
         for (; seen < upto && !run.done; ++seen)
-            if (take((uint32_t)hist[seen]) && con) outcome.device_state = states[seen];
+            if (take((uint32_t)hist[seen]) && cur) {
+                outcome.device_state = states[seen];
+                if (gram) outcome.device_depth = depths[seen];
+            }
     };
     const auto fetch = [&](size_t first, size_t n) {  // the picks [first, first + n) and, constrained, the states behind them
         hip_check(hipMemcpyAsync(hist.data() + first, hist_ + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
         if (con)
             hip_check(hipMemcpyAsync(states.data() + first, cstate_log_ + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H states");
+        if (gram) {
+            hip_check(hipMemcpyAsync(states.data() + first, gstate_log_ + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H states");
+            hip_check(hipMemcpyAsync(depths.data() + first, gdepth_log_ + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H depths");
+        }
         hip_check(hipStreamSynchronize(stream_), "sync");
     };
     fetch(0, 1);
     produced = 1;
     drain(1);
-    if (!run.done) exec = con ? constrained_step_graph() : step_graph();
+    if (!run.done) exec = con ? constrained_step_graph() : gram ? grammar_step_graph() : step_graph();
     const size_t burst = on_token ? 4 : 16;
     while (!run.done) {
         size_t steps = std::min(burst, run.max_new - out.size());
@@ -1682,11 +1803,7 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         cache_len_ += (int)steps;
         drain(produced);
     }
-    if (con) {
-        ConstraintRow row = {};
-        hip_check(hipMemcpy(&row, crow_, sizeof(row), hipMemcpyDeviceToHost), "D2H constraint state");
-        outcome.violated = outcome.violated || row.violated != 0;  // (steps past the run's end included: they pick under the mask too)
-    }
+    read_device_row(false);  // violated alone (steps past the run's end included: they pick under the mask too)
     finish();
     leave_resident(run.all);  // (the burst's rows past the last emitted token stay behind cache_len_, uncounted)
     return out;
@@ -2035,8 +2152,10 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         if (strict) throw InvalidConfig(what);
         throw std::runtime_error(what);
     };
-    for (const LaneRequest& r : reqs)
+    for (const LaneRequest& r : reqs) {
         if (r.options.constraint) throw InvalidConfig(std::string(entry) + " does not take a constraint (generate does)");
+        if (r.options.grammar) throw InvalidConfig(std::string(entry) + " does not take a grammar (generate does)");
+    }
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
     std::vector<std::vector<uint32_t>> out(reqs.size());
@@ -2672,6 +2791,7 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     if (stats) *stats = LookupStats();
     check_lookup_config(lk);
     if (opt.constraint) throw InvalidConfig("generate_lookup does not take a constraint (generate does)");
+    if (opt.grammar) throw InvalidConfig("generate_lookup does not take a grammar (generate does)");
     if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0) return generate(prompt, opt, on_token);  // not applicable
     DraftSource src;
     src.ngram_max = lk.ngram_max;
@@ -2890,6 +3010,7 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     if (stats) *stats = LookupStats();
     check_lookup_config(lk);
     if (opt.constraint) throw InvalidConfig("generate_lookup_sampled does not take a constraint (generate does)");
+    if (opt.grammar) throw InvalidConfig("generate_lookup_sampled does not take a grammar (generate does)");
     if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
     if (!opt.sample) return generate_lookup(prompt, opt, lk, on_token, stats);
     DraftSource src;
@@ -3012,6 +3133,7 @@ std::vector<uint32_t> LlmModel::generate_draft(LlmModel* drafter, const std::vec
     if (stats) *stats = LookupStats();
     check_draft_pair(drafter, draft_tokens);
     if (opt.constraint) throw InvalidConfig("generate_draft does not take a constraint (generate does)");
+    if (opt.grammar) throw InvalidConfig("generate_draft does not take a grammar (generate does)");
     if (prompt.empty()) throw InvalidConfig("prompt must not be empty");
     if (prompt.size() > (size_t)cache_cap_)
         throw InvalidConfig("prompt (" + std::to_string(prompt.size()) + " tokens) does not fit the context of " + std::to_string(cache_cap_) +

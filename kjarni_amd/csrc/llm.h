@@ -63,6 +63,8 @@ struct LlmLaneState;  // llm_kernels.h
 struct LlmWideState;
 struct ConstraintView;  // constraint_kernels.h
 struct ConstraintRow;
+struct GrammarView;  // grammar_kernels.h
+struct GrammarRow;
 struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
@@ -252,6 +254,9 @@ public:
     // device sampling off the host masks its copy of the logits from the DFA and the token table.  A run also ends, without a stop
     // token, when the state is closed.  Throws InvalidConfig before any GPU work: a constraint of another device or vocabulary,
     // more than 16 stop ids, a state from which nothing can be emitted (DeviceConstraint::check_states).
+    // options.grammar (grammar_kernels.h: a stack automaton in the DFA's place; both set is InvalidConfig): the same loop, with
+    // "configuration" (state and stack) for "state", launch_grammar_apply / launch_grammar_advance for the two kernels, a third
+    // captured chain for plain greedy, and DeviceGrammar::check_states for the refusal.
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
                                    const std::function<bool(uint32_t)>& on_token);
 
@@ -515,6 +520,8 @@ private:
     hipGraphExec_t step_graph();
     void ensure_constraint();                 // the model's descriptor, row state and state log
     hipGraphExec_t constrained_step_graph();  // pass -> apply -> argmax(record) -> advance, captured once (it reads cview_)
+    void ensure_grammar();                    // the same for a grammar: descriptor, row state, state and depth logs
+    hipGraphExec_t grammar_step_graph();      // pass -> grammar apply -> argmax(record) -> grammar advance (it reads gview_)
 
     struct Layer {
         void *wqkv, *wo, *gate, *up, *down;  // GPT-2: c_attn, attn.c_proj, mlp.c_fc (in `gate`), mlp.c_proj (in `down`), as [out, in]
@@ -639,6 +646,12 @@ private:
     ConstraintRow* crow_ = nullptr;
     uint32_t* cstate_log_ = nullptr;
     hipGraphExec_t cgraph_ = nullptr;
+    // ... and under a grammar: the descriptor, the row (state, depth, stack), the state and depth logs, the captured chain
+    GrammarView* gview_ = nullptr;
+    GrammarRow* grow_ = nullptr;
+    uint32_t* gstate_log_ = nullptr;
+    int32_t* gdepth_log_ = nullptr;
+    hipGraphExec_t ggraph_ = nullptr;
     // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
     // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
     std::vector<float*> lane_k_, lane_v_;

@@ -477,6 +477,33 @@ class HipDecoder:
         del keep
         return out[:min(n.value, out.size)].tolist(), result_dict(res)
 
+    def generate_grammar(self, grammar, prompt: Sequence[int], max_new_tokens: int, sample: bool = False, temperature: float = 1.0,
+                         top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+                         repetition_penalty: float = 1.0, no_repeat_ngram: int = 0, stop_ids: Optional[Sequence[int]] = None,
+                         uniforms=None, seed: int = 0, on_token: Optional[Callable[[int], Optional[bool]]] = None):
+        """generate_constrained() under a kjarni_amd.constraints.GrammarConstraint (a stack automaton in the DFA's place):
+        (ids, result).  After every token the bytes of the emitted tokens are a prefix of a string of the grammar; in an accepted
+        configuration the stop ids are legal; a closed configuration ends the run without a stop token.  result: final_state,
+        final_depth, device_state, device_depth, accepted, complete, violated (kjarni_hip.h: KjarniHipGrammarResult)."""
+        from .constraints import grammar_result_dict
+        p = np.ascontiguousarray(prompt, np.uint32)
+        out = np.empty(max(max_new_tokens, 1), np.uint32)
+        n = C.c_size_t(0)
+        o, keep = self._sampling_options(max_new_tokens, sample, temperature, top_k, top_p, min_p, repetition_penalty, no_repeat_ngram,
+                                         stop_ids, uniforms, seed)
+        res = _ffi.KjarniHipGrammarResult()
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_grammar(self._h, grammar._h if grammar is not None else None,
+                                                              u32(p) if p.size else None, p.size, C.byref(o), fn, None, u32(out), out.size,
+                                                              C.byref(n), C.byref(res)))
+        del keep
+        return out[:min(n.value, out.size)].tolist(), grammar_result_dict(res)
+
     def verify_step_sampled(self, token: int, draft: Sequence[int], uniforms, rows: Optional[int] = None, temperature: float = 1.0,
                             top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
                             repetition_penalty: float = 1.0, history: Optional[Sequence[int]] = None, fetch: bool = True):

@@ -124,7 +124,7 @@ class Generator:
         (kjarni_amd.constraints has builders: choices, integer, number, json_string, json_object); None restores the plain
         behaviour.  The token table comes from this handle's tokenizer, once per pattern.  While set, requests take the plain
         loop even when prompt lookup or a draft model is switched on; generate_batch() is not constrained.  Nested or recursive
-        JSON schemas are out of scope."""
+        JSON is a grammar: set_grammar."""
         check_error(lib().kjarni_hip_generator_set_constraint(self._handle, pattern.encode("utf-8") if pattern else None))
 
     def constraint_result(self):
@@ -133,6 +133,23 @@ class Generator:
         r = _ffi.KjarniHipConstraintResult()
         check_error(lib().kjarni_hip_generator_constraint_result(self._handle, C.byref(r)))
         return result_dict(r)
+
+    def set_grammar(self, rules):
+        """Constrained decoding under a grammar: rules [(name, pattern)] as kjarni_amd.constraints.json_value / json_schema
+        return them (rule 0 the start rule, patterns calling each other with (?&name)); None or [] removes it.  A handle holds a
+        pattern or a grammar: setting one clears the other.  Requests take the plain loop as under set_constraint."""
+        rules = list(rules or [])
+        names = (C.c_char_p * max(len(rules), 1))(*[n.encode("utf-8") for n, _ in rules])
+        pats = (C.c_char_p * max(len(rules), 1))(*[p.encode("utf-8") for _, p in rules])
+        check_error(lib().kjarni_hip_generator_set_grammar(self._handle, names, pats, len(rules)))
+
+    def grammar_result(self):
+        """How the last request under a grammar ended: final_state, final_depth, device_state, device_depth, accepted, complete,
+        violated."""
+        from .constraints import grammar_result_dict
+        r = _ffi.KjarniHipGrammarResult()
+        check_error(lib().kjarni_hip_generator_grammar_result(self._handle, C.byref(r)))
+        return grammar_result_dict(r)
 
     def set_prefix_reuse(self, on: bool):
         """Keep the cached rows of the tokens a call's prompt shares with the call before (off by default): score() over several

@@ -51,6 +51,9 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            alternated twice in one process, greedy and sampled: Llama-3.2-1B shape (bf16) and gpt2-small (bf16), a pattern that
            masks nothing (the ids are the plain loop's, asserted), so the ratio is the cost of the two launches per step; and the
            mask build of a 100-state pattern at each shape's vocabulary.  The lines also go to profiles/llm_constraint_bench.jsonl.
+  llm_grammar  (only on request) grammar-constrained decoding (HipDecoder.generate_grammar) against the pattern route and the plain
+           loop of the same run, Llama-3.2-1B and gpt2-small shapes, greedy and sampled; json_value on random weights and the device
+           object's constructor at V = 128 256 for information.  The lines also go to profiles/llm_grammar_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1734,6 +1737,104 @@ def main():
         del dec
         gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
         gd = os.path.join(tmp, "gpt2-small-constraint")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        dec = kjarni_amd.HipDecoder(gd)
+        measure("gpt2-small shape, bf16 weights", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+    if "llm_grammar" in which:
+        # Method (as llm_constraint): one process on one box, everything warmed first; three loops alternate twice in one run, greedy
+        # and sampled: the plain loop, the pattern route with a pattern that masks nothing ([ -~]* over an all-ASCII table: the
+        # parent's route, the yardstick) and the grammar route with the one-rule grammar of the same language.  The grammar route's
+        # ids are asserted equal to the plain loop's.  A decode window is a whole generation minus the same call cut after its first
+        # token.  The spread is what the two alternations of one loop differ by.  The per-step cost of the two grammar launches is
+        # the difference of the grammar and the plain loop's time per token.  For information: json_value on random weights (the
+        # run may end early: the tokens it emitted are reported) and the whole GrammarConstraint constructor at V = 128 256.
+        from kjarni_amd import constraints as KC
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        n_new = int(os.environ.get("KJARNI_GRAMMAR_TOKENS", "256"))
+        out_path = os.path.join(ROOT, "profiles", "llm_grammar_bench.jsonl")
+        lines = []
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+        SAMPLING = dict(temperature=0.8, top_k=40, top_p=0.9, min_p=0.05)
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, vocab, lo, dtype):
+            prompt = rng.integers(lo, vocab, 128).tolist()
+            table = [("t%d " % i).encode() for i in range(vocab)]
+            con = KC.Constraint(r"[ -~]*", table)
+            t0 = time.perf_counter()
+            gram = KC.GrammarConstraint([("s", r"[ -~]*")], table)
+            one_rule_ms = (time.perf_counter() - t0) * 1e3
+            legs = {
+                "greedy_plain": lambda n: dec.generate(prompt, n),
+                "greedy_regex": lambda n: dec.generate_constrained(con, prompt, n)[0],
+                "greedy_grammar": lambda n: dec.generate_grammar(gram, prompt, n)[0],
+                "sampled_plain": lambda n: dec.generate_sampled(prompt, n, sample=True, seed=7, **SAMPLING)[0],
+                "sampled_regex": lambda n: dec.generate_constrained(con, prompt, n, sample=True, seed=7, **SAMPLING)[0],
+                "sampled_grammar": lambda n: dec.generate_grammar(gram, prompt, n, sample=True, seed=7, **SAMPLING)[0],
+            }
+            for fn in legs.values():
+                fn(8)
+            rate = {k: [] for k in legs}
+            outs = {}
+            for rep in range(2):
+                for k, fn in legs.items():
+                    dt, out = window(lambda: fn(n_new), lambda: fn(1))
+                    assert len(out) == n_new, (k, len(out))
+                    rate[k].append((n_new - 1) / dt)
+                    outs[k] = out
+            assert outs["greedy_plain"] == outs["greedy_grammar"] == outs["greedy_regex"]
+            assert outs["sampled_plain"] == outs["sampled_grammar"] == outs["sampled_regex"]
+            spread = {k: round(abs(v[0] - v[1]) / med(v), 4) for k, v in rate.items()}
+            ratio = {m: round(med(rate[m + "_grammar"]) / med(rate[m + "_regex"]), 4) for m in ("greedy", "sampled")}
+            cost_us = {m: round((1.0 / med(rate[m + "_grammar"]) - 1.0 / med(rate[m + "_plain"])) * 1e6, 2) for m in ("greedy", "sampled")}
+            regex_cost_us = {m: round((1.0 / med(rate[m + "_regex"]) - 1.0 / med(rate[m + "_plain"])) * 1e6, 2) for m in ("greedy", "sampled")}
+            # for information: any JSON value on random weights, over a table of single printable characters and a few words
+            chars = [bytes([32 + i % 95]) for i in range(vocab)]
+            for i, w in enumerate(("true", "false", "null", "\"a\":", "[1,", "{\"", "\"}", "]]", "},")):
+                chars[100 + i] = w.encode()
+            t0 = time.perf_counter()
+            jv = KC.GrammarConstraint(KC.json_value(), chars)
+            jv_new_ms = (time.perf_counter() - t0) * 1e3
+            dec.generate_grammar(jv, prompt, 8)
+            t0 = time.perf_counter()
+            ids, res = dec.generate_grammar(jv, prompt, n_new)
+            jv_s = time.perf_counter() - t0
+            line = {"metric": f"grammar-constrained decoding, {label}", "unit": "grammar / regex-route tokens per second, greedy",
+                    "value": ratio["greedy"], "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"random init, one 128-token prompt, {n_new} generated tokens; the plain loop, the pattern route "
+                                           "([ -~]* over an all-ASCII table: nothing masked) and the grammar route (the one-rule grammar of the "
+                                           "same language) alternated twice in one process, greedy and sampled (temperature 0.8, top-k 40, "
+                                           "top-p 0.9, min-p 0.05, one seed); ids equal (asserted)", "vocab": vocab},
+                    "tokens_per_s": {k: {"median": round(med(v), 1), "runs": [round(x, 1) for x in v]} for k, v in rate.items()},
+                    "spread_between_alternations": spread, "sampled_grammar_over_regex": ratio["sampled"],
+                    "grammar_launches_us_per_step": cost_us, "regex_launches_us_per_step": regex_cost_us,
+                    "constructor_ms": {"one_rule": round(one_rule_ms, 1), "json_value": round(jv_new_ms, 1), "vocab": vocab},
+                    "json_value_random_weights": {"tokens": len(ids), "seconds": round(jv_s, 4), "complete": res["complete"],
+                                                  "violated": res["violated"], "final_depth": res["final_depth"]},
+                    "weight_bytes": dec.weight_bytes}
+            lines.append(line)
+            emit(line)
+
+        d = os.path.join(tmp, "llama-1b-grammar")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, synth.LLAMA_1B["vocab_size"], 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small-grammar")
         gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
         dec = kjarni_amd.HipDecoder(gd)
         measure("gpt2-small shape, bf16 weights", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
