@@ -1101,6 +1101,64 @@ KjarniErrorCode kjarni_hip_op_add_rows(int32_t device, float* x, int32_t rows, i
 KjarniErrorCode kjarni_hip_op_decoder_embed(int32_t device, const uint32_t* ids, int32_t n, int32_t hidden, int32_t vocab, const float* word,
                                             const float* pos, int32_t max_pos, int32_t offset, int32_t offset_on_device,
                                             int32_t scale_embeddings, int32_t lanes, float* out);
+/* ---- the encoder's packed-row kernels, alone ----------------------------------------------------------------------------------------
+ * A ragged batch runs over its kept tokens only: sentence b is rows cu[b] .. cu[b+1] of every activation buffer and tok_src[row] is
+ * the row's index in the padded [batch, seq] arrays.  Each hook below makes ONE launcher call on host arrays.  Every argument is
+ * checked before a device is asked for (INVALID_CONFIG / NULL_POINTER with the outputs untouched); every output is uploaded as given
+ * and returned whole, so what the kernel does not own keeps the caller's pattern; a guard band lies behind every device buffer
+ * (128 rows behind qkv, ctx and the hidden states), checked behind outputs and NaN behind inputs.
+ *
+ * mask_lengths: lens_out[b] = kept tokens (mask != 0) of sentence b of mask [batch, seq]; bit 31 set when mask[b, 0] == 0 or a mask
+ *   value is > 1 (the sentence needs the padded layout).
+ * pack_index: tok_src[cu[b] + r] = b * seq + s for the r-th kept token of sentence b; tok_src [capacity] otherwise untouched.  The
+ *   kernel writes tok_src + cu[b] unchecked, so the hook refuses a cu that does not start at 0, decreases, whose steps are not the
+ *   mask's kept counts, or that ends beyond capacity.
+ * encoder_embed: launch_embed_layernorm.  out [rows, hidden]: row t = token tok_src[t] (t without tok_src) of ids / type_ids
+ *   [batch, seq]: word [id] (zeros when id >= vocab) * sqrt(hidden) with scale_embeddings, + pos [pos_offset + s] when that is below
+ *   max_pos, + type [type id] (row 0 without type_ids); LayerNorm(gamma, beta, eps) when gamma is given.  pos, type, type_ids, gamma /
+ *   beta and tok_src may be NULL.  Refused: tok_src[t] outside [0, batch * seq), a type id >= type_vocab, gamma without beta, pos with
+ *   max_pos <= 0, rows > batch * seq without tok_src.
+ * encoder_rope: launch_rope_qk on qkv [rows, 3 * heads * head_dim] in place (the V third untouched); position of row t =
+ *   tok_src[t] % seq (t % seq without); cos_t / sin_t [seq, head_dim].  Refused: odd head_dim, a negative tok_src entry.
+ * attention_packed: launch_attention(..., cu) on qkv [buffer_rows, 3 hidden] -> ctx [buffer_rows, hidden]; max_len = the longest
+ *   sentence the call is sized for.  Refused: a cu that is not strictly increasing from 0 (the kernels compute extents from len - 1),
+ *   a sentence longer than max_len (the grids cover max_len queries: a caller's precondition of launch_attention), cu[batch] >
+ *   buffer_rows.  route_out [2] = the kernel (KjarniHipAttentionKernel) and the item-per-workgroup kernels' grid, as
+ *   kjarni_hip_attention_route gives them.
+ * pool_packed: launch_pool(..., cu) on hidden_states [cu[batch], hidden] -> out [batch, hidden]; the same cu checks against `seq`;
+ *   hidden <= 1024.  (launch_pool ignores a mask when cu is given: every packed row is a kept token.)
+ * small_linear: out [rows, n] = feat [rows, ld] (the first k of every row) . w [n, k]^T + bias [n] (NULL: none).
+ * row_softmax: out [rows, n] = softmax of every row of in, or 1 / (1 + exp(-x)) per element with sigmoid.
+ * attention_route: host only, no device.  Which kernel launch_attention takes for (batch, seq or longest sentence, heads, head_dim),
+ *   `aligned` = hidden % 4 == 0 and 16-byte aligned buffers, `packed` = cu given; route_out [2] as above. */
+typedef enum {
+    KJARNI_HIP_ATTN_NOTHING = 0,     /* batch <= 0 or seq <= 0 */
+    KJARNI_HIP_ATTN_SPLIT = 1,       /* the small-call kernel: at most 128 (sentence, head) items, seq <= 128 */
+    KJARNI_HIP_ATTN_PIPE_PADDED = 2, /* item per workgroup, MODE 0: padded rows, 96 < seq <= 128 */
+    KJARNI_HIP_ATTN_PIPE_PACKED = 3, /* item per workgroup, MODE 1: packed rows, longest sentence <= 128 */
+    KJARNI_HIP_ATTN_PIPE_SHORT = 4,  /* item per workgroup, MODE 2: padded rows, seq <= 96 */
+    KJARNI_HIP_ATTN_CHUNKED = 5,     /* seq > 128: online softmax over chunks of 128 keys */
+    KJARNI_HIP_ATTN_GENERIC = 6      /* head_dim other than 32 / 64, or not aligned */
+} KjarniHipAttentionKernel;
+KjarniErrorCode kjarni_hip_op_mask_lengths(int32_t device, const uint32_t* mask, int64_t batch, int32_t seq, uint32_t* lens_out);
+KjarniErrorCode kjarni_hip_op_pack_index(int32_t device, const uint32_t* mask, const int32_t* cu, int64_t batch, int32_t seq,
+                                         int32_t* tok_src, int32_t capacity);
+KjarniErrorCode kjarni_hip_op_encoder_embed(int32_t device, const uint32_t* ids, const uint32_t* type_ids, const float* word, const float* pos,
+                                            const float* type, const float* gamma, const float* beta, float eps, int64_t rows, int64_t batch,
+                                            int32_t seq, int32_t hidden, int32_t vocab, int32_t max_pos, int32_t type_vocab, int32_t pos_offset,
+                                            int32_t scale_embeddings, const int32_t* tok_src, float* out);
+KjarniErrorCode kjarni_hip_op_encoder_rope(int32_t device, float* qkv, const float* cos_t, const float* sin_t, int64_t rows, int32_t seq,
+                                           int32_t heads, int32_t head_dim, const int32_t* tok_src);
+KjarniErrorCode kjarni_hip_op_attention_packed(int32_t device, const float* qkv, const int32_t* cu, int64_t batch, int32_t max_len,
+                                               int32_t heads, int32_t head_dim, float mask_value, float* ctx, int64_t buffer_rows,
+                                               int32_t* route_out);
+KjarniErrorCode kjarni_hip_op_pool_packed(int32_t device, const float* hidden_states, const int32_t* cu, int64_t batch, int32_t seq,
+                                          int32_t hidden, KjarniHipPooling pooling, int32_t normalize, float* out);
+KjarniErrorCode kjarni_hip_op_small_linear(int32_t device, const float* feat, int64_t ld, const float* w, const float* bias, int64_t rows,
+                                           int32_t k, int32_t n, float* out);
+KjarniErrorCode kjarni_hip_op_row_softmax(int32_t device, const float* in, int64_t rows, int32_t n, int32_t sigmoid, float* out);
+KjarniErrorCode kjarni_hip_attention_route(int64_t batch, int32_t seq_or_max_len, int32_t heads, int32_t head_dim, int32_t aligned,
+                                           int32_t packed, int32_t* route_out);
 /* ---- the prompt-route GEMM and the two prefill attention kernels, alone -------------------------------------------------------------
  * kjarni_hip_op_prefill_gemm: y[m, n] = a[m, k] . w[n, k]^T (+ bias) (+ r) through launch_prefill_gemm (64 x 64 tiles, K slices
  * added by the reduce kernel), as the decoders' prompt projections call it.  a [a_rows, lda] (a_rows >= m, lda >= k); w [n, k] f32,

@@ -735,6 +735,18 @@ SIGNATURES = {
     "kjarni_hip_op_attention": (c_int32, [c_int32, _f32p, _u32p, c_int64, c_int32, c_int32, c_int32, c_float,
                                           _f32p, c_int32, _f32p]),
     "kjarni_hip_op_pool": (c_int32, [c_int32, _f32p, _u32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    # the encoder's packed-row kernels, alone
+    "kjarni_hip_op_mask_lengths": (c_int32, [c_int32, _u32p, c_int64, c_int32, _u32p]),
+    "kjarni_hip_op_pack_index": (c_int32, [c_int32, _u32p, POINTER(c_int32), c_int64, c_int32, POINTER(c_int32), c_int32]),
+    "kjarni_hip_op_encoder_embed": (c_int32, [c_int32, _u32p, _u32p, _f32p, _f32p, _f32p, _f32p, _f32p, c_float, c_int64, c_int64, c_int32,
+                                              c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), _f32p]),
+    "kjarni_hip_op_encoder_rope": (c_int32, [c_int32, _f32p, _f32p, _f32p, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "kjarni_hip_op_attention_packed": (c_int32, [c_int32, _f32p, POINTER(c_int32), c_int64, c_int32, c_int32, c_int32, c_float, _f32p,
+                                                 c_int64, POINTER(c_int32)]),
+    "kjarni_hip_op_pool_packed": (c_int32, [c_int32, _f32p, POINTER(c_int32), c_int64, c_int32, c_int32, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_small_linear": (c_int32, [c_int32, _f32p, c_int64, _f32p, _f32p, c_int64, c_int32, c_int32, _f32p]),
+    "kjarni_hip_op_row_softmax": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, _f32p]),
+    "kjarni_hip_attention_route": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
     "kjarni_hip_op_attention_biased": (c_int32, [c_int32, _f32p, _u32p, _f32p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
                                                  c_float, _f32p]),
     "kjarni_hip_op_layer_norm": (c_int32, [c_int32, _f32p, _f32p, _f32p, c_float, c_int64, c_int32, _f32p,

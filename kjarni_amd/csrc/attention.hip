@@ -780,7 +780,7 @@ __global__ __launch_bounds__(64) void attention_generic_kernel(const float* __re
 }
 
 template <int D>
-hipError_t launch_d(const float* qkv, const uint32_t* mask, int64_t batch, int seq, int heads,
+hipError_t launch_d(const AttentionRoute route, const float* qkv, const uint32_t* mask, int64_t batch, int seq, int heads,
                     float mask_value, float* ctx, hipStream_t stream, const int32_t* cu)
 {
     using SM = AttnSmem<D>;
@@ -790,30 +790,25 @@ hipError_t launch_d(const float* qkv, const uint32_t* mask, int64_t batch, int s
         if (e != hipSuccess) return e;
     }
     const float scale = 1.0f / sqrtf((float)D);  // encoder_self_attention.rs:43
-    if (seq <= KCHUNK && batch * heads <= kSplitMaxItems) {
+    if (route.kernel == ATTN_SPLIT) {
         // a few items: each over up to four workgroups, a key tile per wave (latency, not throughput)
         hipLaunchKernelGGL(attention_split_kernel<D>, dim3((unsigned)((seq + 31) / 32), (unsigned)heads, (unsigned)batch), dim3(256), 0, stream,
                            qkv, mask, seq, heads, scale, mask_value, cu, ctx);
         return hipGetLastError();
     }
-    if (seq <= KCHUNK) {
+    if (route.kernel == ATTN_PIPE_PADDED || route.kernel == ATTN_PIPE_PACKED || route.kernel == ATTN_PIPE_SHORT) {
         const int64_t n_items = batch * heads;
-        // head_dim 32: three resident workgroups per CU (35.8 KiB of LDS and <= 168 VGPRs each): the third hides what two
-        // leave exposed of the K / V / Q streams' latency (measured 274 -> 264 us per launch of 12 288 items).
-        // head_dim 64: 68.6 KiB of LDS per workgroup -- two per CU, and the kernel is compiled for that (<= 256 VGPRs).
-        constexpr int kResident = D >= 64 ? 2 : 3;
-        const int64_t max_blocks = 256 * kResident;
-        const unsigned grid = (unsigned)(n_items < max_blocks ? n_items : max_blocks);
+        const unsigned grid = route.grid;  // (attention_route: the item count, capped at the resident workgroups)
         if (SM::BYTES > 64 * 1024) {  // the dynamic-LDS opt-in of the three kernels below
             e = allow_dynamic_lds(&attention_pipe_kernel<D, 1>, SM::BYTES);
             if (e == hipSuccess) e = allow_dynamic_lds(&attention_pipe_kernel<D, 0>, SM::BYTES);
             if (e == hipSuccess) e = allow_dynamic_lds(&attention_pipe_kernel<D, 2>, SM::BYTES);
             if (e != hipSuccess) return e;
         }
-        if (cu)
+        if (route.kernel == ATTN_PIPE_PACKED)
             hipLaunchKernelGGL((attention_pipe_kernel<D, 1>), dim3(grid), dim3(256), SM::BYTES, stream, qkv, nullptr, n_items,
                                seq, heads, scale, mask_value, cu, ctx);
-        else if (seq <= 96)  // at least one 32-key tile and one wave of every item are empty
+        else if (route.kernel == ATTN_PIPE_SHORT)  // at least one 32-key tile and one wave of every item are empty
             hipLaunchKernelGGL((attention_pipe_kernel<D, 2>), dim3(grid), dim3(256), SM::BYTES, stream, qkv, mask, n_items,
                                seq, heads, scale, mask_value, nullptr, ctx);
         else
@@ -821,7 +816,7 @@ hipError_t launch_d(const float* qkv, const uint32_t* mask, int64_t batch, int s
                                seq, heads, scale, mask_value, nullptr, ctx);
         return hipGetLastError();
     }
-    // grid.z is limited to 65535 sentences per launch.
+    // ATTN_CHUNKED.  grid.z is limited to 65535 sentences per launch.
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
         const int64_t nb = (batch - b0 < 65535) ? (batch - b0) : 65535;
         dim3 grid((unsigned)((seq + QBLK - 1) / QBLK), (unsigned)heads, (unsigned)nb);
@@ -863,15 +858,51 @@ hipError_t launch_generic(const float* qkv, const uint32_t* mask, int64_t batch,
 }
 }  // namespace
 
+// Which kernel a call takes, and the grid of the item-per-workgroup ("pipe") kernels: a pure function of the call's sizes, so
+// that a test can ask it without a device.  seq = the padded length, or with packed rows the longest sentence of the call;
+// aligned = hidden % 4 == 0 and qkv / ctx on 16-byte boundaries.
+//   head_dim other than 32 / 64, or not aligned          -> the any-shape kernel (one wave per query row)
+//   seq <= 128 and batch * heads <= 128 items            -> the small-call kernel (an item over up to four workgroups)
+//   seq <= 128: packed rows -> MODE 1; padded, seq <= 96 -> MODE 2; else MODE 0;
+//               grid = min(items, 256 CUs x resident workgroups: 3 at head_dim 32, 2 at head_dim 64)
+//   seq > 128                                            -> the chunked kernel
+AttentionRoute attention_route(int64_t batch, int seq, int heads, int head_dim, bool aligned, bool packed)
+{
+    AttentionRoute r;
+    if (batch <= 0 || seq <= 0) return r;
+    if ((head_dim != 32 && head_dim != 64) || !aligned) {
+        r.kernel = ATTN_GENERIC;
+        return r;
+    }
+    if (seq > KCHUNK) {
+        r.kernel = ATTN_CHUNKED;
+        return r;
+    }
+    const int64_t n_items = batch * heads;
+    if (n_items <= kSplitMaxItems) {
+        r.kernel = ATTN_SPLIT;
+        return r;
+    }
+    // head_dim 32: three resident workgroups per CU (35.8 KiB of LDS and <= 168 VGPRs each): the third hides what two
+    // leave exposed of the K / V / Q streams' latency (measured 274 -> 264 us per launch of 12 288 items).
+    // head_dim 64: 68.6 KiB of LDS per workgroup -- two per CU, and the kernel is compiled for that (<= 256 VGPRs).
+    const int64_t max_blocks = 256 * (head_dim >= 64 ? 2 : 3);
+    r.grid = (unsigned)(n_items < max_blocks ? n_items : max_blocks);
+    r.kernel = packed ? ATTN_PIPE_PACKED : (seq <= 96 ? ATTN_PIPE_SHORT : ATTN_PIPE_PADDED);
+    return r;
+}
+
 hipError_t launch_attention(const float* qkv, const uint32_t* mask, int64_t batch, int seq, int heads,
                             int head_dim, float mask_value, float* ctx, hipStream_t stream, const int32_t* cu)
 {
-    if (batch <= 0 || seq <= 0) return hipSuccess;
     const bool aligned = ((heads * head_dim) % 4 == 0) && ((reinterpret_cast<uintptr_t>(qkv) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(ctx) & 15) == 0);  // (16-byte loads of qkv, 16-byte stores of ctx)
-    if (head_dim == 32 && aligned) return launch_d<32>(qkv, mask, batch, seq, heads, mask_value, ctx, stream, cu);
-    if (head_dim == 64 && aligned) return launch_d<64>(qkv, mask, batch, seq, heads, mask_value, ctx, stream, cu);
-    return launch_generic(qkv, mask, batch, seq, heads, head_dim, mask_value, ctx, stream, cu, nullptr, 0, true);
+    const AttentionRoute route = attention_route(batch, seq, heads, head_dim, aligned, cu != nullptr);
+    if (route.kernel == ATTN_NOTHING) return hipSuccess;
+    if (route.kernel == ATTN_GENERIC)
+        return launch_generic(qkv, mask, batch, seq, heads, head_dim, mask_value, ctx, stream, cu, nullptr, 0, true);
+    if (head_dim == 32) return launch_d<32>(route, qkv, mask, batch, seq, heads, mask_value, ctx, stream, cu);
+    return launch_d<64>(route, qkv, mask, batch, seq, heads, mask_value, ctx, stream, cu);
 }
 
 hipError_t launch_attention_biased(const float* qkv, const uint32_t* mask, const float* pos_bias, int bias_seq, int64_t batch, int seq,

@@ -2679,6 +2679,265 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_pool(int32_t device, const float* hi
     });
 }
 
+// ---- the encoder's packed-row kernels, alone --------------------------------------------------------------------------------------
+// One launcher call per hook on host arrays.  Every argument is checked before a device is asked for; every output is uploaded as
+// the caller gave it and returned whole; a guard band lies behind every device buffer -- checked behind an output, NaN behind an
+// input, so that a read past its end poisons the result.
+
+namespace {
+
+// A device copy of `bytes` host bytes with `guard_words` words of the guard pattern (a NaN) behind it.
+struct BandBuf {
+    static constexpr uint32_t kGuard = GuardedBuf::kGuard;
+    size_t bytes, guard_words;
+    DeviceBuf buf;
+    BandBuf(const void* src, size_t b, size_t guard_words_, const char* what) : bytes((b + 3) / 4 * 4), guard_words(guard_words_), buf(bytes + guard_words_ * 4)
+    {
+        if (src && b) hip_check(hipMemcpy(buf.p, src, b, hipMemcpyHostToDevice), what);
+        hip_check(hipMemsetD32((hipDeviceptr_t)((char*)buf.p + bytes), (int)kGuard, guard_words), "guard band");
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(buf.p); }
+    // the band intact, then the buffer back to the host
+    void fetch(void* host, size_t b, const char* what) const
+    {
+        std::vector<uint32_t> g(guard_words);
+        hip_check(hipMemcpy(g.data(), (char*)buf.p + bytes, guard_words * 4, hipMemcpyDeviceToHost), "D2H guard band");
+        for (size_t i = 0; i < guard_words; ++i)
+            if (g[i] != kGuard) throw std::runtime_error(std::string(what) + ": guard band touched at word " + std::to_string(i));
+        if (host && b) hip_check(hipMemcpy(host, buf.p, b, hipMemcpyDeviceToHost), what);
+    }
+};
+
+static_assert((int)KJARNI_HIP_ATTN_NOTHING == ATTN_NOTHING && (int)KJARNI_HIP_ATTN_SPLIT == ATTN_SPLIT && (int)KJARNI_HIP_ATTN_PIPE_PADDED == ATTN_PIPE_PADDED &&
+                  (int)KJARNI_HIP_ATTN_PIPE_PACKED == ATTN_PIPE_PACKED && (int)KJARNI_HIP_ATTN_PIPE_SHORT == ATTN_PIPE_SHORT &&
+                  (int)KJARNI_HIP_ATTN_CHUNKED == ATTN_CHUNKED && (int)KJARNI_HIP_ATTN_GENERIC == ATTN_GENERIC, "the header's attention kernels are the launcher's");
+
+constexpr size_t kBandWords = 64;    // behind the small buffers
+constexpr int64_t kBandRows = 128;   // behind qkv, ctx and the hidden states: a whole query block / key chunk of rows
+
+// cu [n + 1]: prefix sums of the sentences' lengths from 0; every sentence holds 1 .. max_len rows (the kernels compute extents
+// from len - 1 and size their grids by max_len); the last entry at most `rows`.
+void check_cu(const int32_t* cu, int64_t n, int32_t max_len, int64_t rows)
+{
+    if (n < 1 || n > (1 << 20)) throw InvalidConfig("batch must be 1 .. 2^20");
+    if (max_len < 1 || max_len > 8192) throw InvalidConfig("the longest sentence must be 1 .. 8192 rows");
+    if (cu[0] != 0) throw InvalidConfig("cu[0] must be 0");
+    for (int64_t b = 0; b < n; ++b) {
+        if (cu[b + 1] <= cu[b])
+            throw InvalidConfig("cu[" + std::to_string(b + 1) + "] does not exceed cu[" + std::to_string(b) + "]: sentence " + std::to_string(b) +
+                                " is empty or cu decreases");
+        if (cu[b + 1] - cu[b] > max_len)
+            throw InvalidConfig("sentence " + std::to_string(b) + " is longer than the " + std::to_string(max_len) + " rows the call is sized for");
+    }
+    if (cu[n] > rows) throw InvalidConfig("cu[batch] = " + std::to_string(cu[n]) + " reaches past the " + std::to_string(rows) + " rows given");
+}
+
+void check_mask_shape(int64_t batch, int32_t seq)
+{
+    if (batch < 1 || batch > (1 << 20) || seq < 1 || seq > (1 << 16) || batch * seq > ((int64_t)1 << 26))
+        throw InvalidConfig("batch must be 1 .. 2^20, seq 1 .. 2^16, batch * seq at most 2^26");
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mask_lengths(int32_t device, const uint32_t* mask, int64_t batch, int32_t seq, uint32_t* lens_out)
+{
+    if (!mask || !lens_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        check_mask_shape(batch, seq);
+        use_device(device);
+        const BandBuf md(mask, (size_t)batch * seq * 4, kBandWords, "H2D mask"), ld(lens_out, (size_t)batch * 4, kBandWords, "H2D lens");
+        launcher_check(launch_mask_lengths(md.as<uint32_t>(), batch, seq, ld.as<uint32_t>(), nullptr), "mask_lengths");
+        hip_check(hipDeviceSynchronize(), "sync");
+        ld.fetch(lens_out, (size_t)batch * 4, "lens");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_pack_index(int32_t device, const uint32_t* mask, const int32_t* cu, int64_t batch, int32_t seq,
+                                                       int32_t* tok_src, int32_t capacity)
+{
+    if (!mask || !cu || !tok_src) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        check_mask_shape(batch, seq);
+        if (capacity < 0 || capacity > (1 << 26)) throw InvalidConfig("capacity must be 0 .. 2^26");
+        // the kernel writes tok_src + cu[b] + (rank of the kept token) unchecked: cu must be the prefix sums of the mask's own counts
+        if (cu[0] != 0) throw InvalidConfig("cu[0] must be 0");
+        for (int64_t b = 0; b < batch; ++b) {
+            if (cu[b + 1] < cu[b]) throw InvalidConfig("cu decreases at " + std::to_string(b + 1));
+            int32_t kept = 0;
+            for (int32_t s = 0; s < seq; ++s) kept += mask[b * seq + s] != 0u;
+            if (cu[b + 1] - cu[b] != kept)
+                throw InvalidConfig("cu gives sentence " + std::to_string(b) + " " + std::to_string(cu[b + 1] - cu[b]) + " rows, its mask keeps " +
+                                    std::to_string(kept));
+        }
+        if (cu[batch] > capacity) throw InvalidConfig("cu[batch] = " + std::to_string(cu[batch]) + " exceeds the capacity of tok_src");
+        use_device(device);
+        const BandBuf md(mask, (size_t)batch * seq * 4, kBandWords, "H2D mask"), cd(cu, (size_t)(batch + 1) * 4, kBandWords, "H2D cu");
+        const BandBuf td(tok_src, (size_t)capacity * 4, kBandWords, "H2D tok_src");
+        launcher_check(launch_pack_index(md.as<uint32_t>(), cd.as<int32_t>(), batch, seq, td.as<int32_t>(), nullptr), "pack_index");
+        hip_check(hipDeviceSynchronize(), "sync");
+        td.fetch(tok_src, (size_t)capacity * 4, "tok_src");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_encoder_embed(int32_t device, const uint32_t* ids, const uint32_t* type_ids, const float* word,
+                                                          const float* pos, const float* type, const float* gamma, const float* beta, float eps,
+                                                          int64_t rows, int64_t batch, int32_t seq, int32_t hidden, int32_t vocab, int32_t max_pos,
+                                                          int32_t type_vocab, int32_t pos_offset, int32_t scale_embeddings,
+                                                          const int32_t* tok_src, float* out)
+{
+    if (!ids || !word || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        check_mask_shape(batch, seq);
+        const int64_t padded = batch * seq;
+        if (rows < 1 || rows > (1 << 22) || hidden < 1 || hidden > 8192 || rows * hidden > ((int64_t)1 << 28))
+            throw InvalidConfig("rows must be 1 .. 2^22, hidden 1 .. 8192, rows * hidden at most 2^28");
+        if (vocab < 1 || vocab > (1 << 20) || (int64_t)vocab * hidden > ((int64_t)1 << 26)) throw InvalidConfig("vocab must be 1 .. 2^20, vocab * hidden at most 2^26");
+        if (!tok_src && rows > padded) throw InvalidConfig("without tok_src row t is token t: rows must not exceed batch * seq");
+        if (tok_src)
+            for (int64_t t = 0; t < rows; ++t)
+                if (tok_src[t] < 0 || tok_src[t] >= padded)
+                    throw InvalidConfig("tok_src[" + std::to_string(t) + "] = " + std::to_string(tok_src[t]) + " is outside [0, batch * seq)");
+        if (gamma && !beta) throw InvalidConfig("LayerNorm needs beta with gamma");
+        if (pos && (max_pos <= 0 || max_pos > (1 << 16))) throw InvalidConfig("pos needs max_pos 1 .. 2^16");
+        if (!pos && max_pos < 0) throw InvalidConfig("max_pos must not be negative");
+        if (pos_offset < 0 || pos_offset > (1 << 16)) throw InvalidConfig("pos_offset must be 0 .. 2^16");
+        if (type && (type_vocab < 1 || type_vocab > 4096)) throw InvalidConfig("type needs type_vocab 1 .. 4096");
+        if (type && type_ids)  // (the kernel clamps them; the reference panics: the host validates, rowops.hip)
+            for (int64_t i = 0; i < padded; ++i)
+                if (type_ids[i] >= (uint32_t)type_vocab)
+                    throw InvalidConfig("type_ids[" + std::to_string(i) + "] = " + std::to_string(type_ids[i]) + " is not below type_vocab");
+        use_device(device);
+        const size_t hb = (size_t)hidden * 4;
+        const BandBuf idd(ids, (size_t)padded * 4, kBandWords, "H2D ids"), tyd(type_ids, type_ids ? (size_t)padded * 4 : 0, kBandWords, "H2D type_ids");
+        const BandBuf wd(word, (size_t)vocab * hb, kBandWords, "H2D word"), pd(pos, pos ? (size_t)max_pos * hb : 0, kBandWords, "H2D pos");
+        const BandBuf td(type, type ? (size_t)type_vocab * hb : 0, kBandWords, "H2D type"), gd(gamma, gamma ? hb : 0, kBandWords, "H2D gamma");
+        const BandBuf bd(beta, beta ? hb : 0, kBandWords, "H2D beta"), sd(tok_src, tok_src ? (size_t)rows * 4 : 0, kBandWords, "H2D tok_src");
+        const BandBuf od(out, (size_t)rows * hb, (size_t)kBandRows * hidden, "H2D out");
+        launcher_check(launch_embed_layernorm(idd.as<uint32_t>(), type_ids ? tyd.as<uint32_t>() : nullptr, wd.as<float>(), pos ? pd.as<float>() : nullptr,
+                                              type ? td.as<float>() : nullptr, gamma ? gd.as<float>() : nullptr, beta ? bd.as<float>() : nullptr, eps,
+                                              rows, seq, hidden, vocab, max_pos, type_vocab, pos_offset, scale_embeddings ? 1 : 0, od.as<float>(),
+                                              nullptr, tok_src ? sd.as<int32_t>() : nullptr), "embed");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.fetch(out, (size_t)rows * hb, "out");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_encoder_rope(int32_t device, float* qkv, const float* cos_t, const float* sin_t, int64_t rows,
+                                                         int32_t seq, int32_t heads, int32_t head_dim, const int32_t* tok_src)
+{
+    if (!qkv || !cos_t || !sin_t) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (head_dim < 2 || head_dim > 256 || (head_dim & 1) || heads < 1 || heads > 1024) throw InvalidConfig("head_dim must be even, 2 .. 256; heads 1 .. 1024");
+        if (seq < 1 || seq > (1 << 16)) throw InvalidConfig("seq must be 1 .. 2^16");
+        const int64_t width = 3 * (int64_t)heads * head_dim;
+        if (rows < 1 || rows > (1 << 22) || rows * width > ((int64_t)1 << 28)) throw InvalidConfig("rows must be 1 .. 2^22, rows * 3 hidden at most 2^28");
+        // the position of row t is tok_src[t] % seq (t % seq without tok_src): a negative entry would read in front of the tables
+        if (tok_src)
+            for (int64_t t = 0; t < rows; ++t)
+                if (tok_src[t] < 0) throw InvalidConfig("tok_src[" + std::to_string(t) + "] is negative");
+        use_device(device);
+        const size_t tb = (size_t)seq * head_dim * 4, qb = (size_t)rows * width * 4;
+        const BandBuf cd(cos_t, tb, kBandWords, "H2D cos"), snd(sin_t, tb, kBandWords, "H2D sin"), sd(tok_src, tok_src ? (size_t)rows * 4 : 0, kBandWords, "H2D tok_src");
+        const BandBuf qd(qkv, qb, (size_t)width, "H2D qkv");
+        launcher_check(launch_rope_qk(qd.as<float>(), cd.as<float>(), snd.as<float>(), rows, seq, heads, head_dim, nullptr,
+                                      tok_src ? sd.as<int32_t>() : nullptr), "rope");
+        hip_check(hipDeviceSynchronize(), "sync");
+        qd.fetch(qkv, qb, "qkv");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_attention_route(int64_t batch, int32_t seq_or_max_len, int32_t heads, int32_t head_dim, int32_t aligned,
+                                                         int32_t packed, int32_t* route_out)
+{
+    if (!route_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (heads < 1 || head_dim < 1 || heads > (1 << 16) || head_dim > (1 << 16) || batch > ((int64_t)1 << 32))
+            throw InvalidConfig("heads and head_dim must be 1 .. 2^16, batch at most 2^32");
+        const AttentionRoute r = attention_route(batch, seq_or_max_len, heads, head_dim, aligned != 0, packed != 0);
+        route_out[0] = (int32_t)r.kernel;
+        route_out[1] = (int32_t)r.grid;
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_attention_packed(int32_t device, const float* qkv, const int32_t* cu, int64_t batch, int32_t max_len,
+                                                             int32_t heads, int32_t head_dim, float mask_value, float* ctx, int64_t buffer_rows,
+                                                             int32_t* route_out)
+{
+    if (!qkv || !cu || !ctx || !route_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (heads < 1 || heads > 1024 || head_dim < 1 || head_dim > 256) throw InvalidConfig("heads must be 1 .. 1024, head_dim 1 .. 256");
+        const int64_t H = (int64_t)heads * head_dim;
+        if (buffer_rows < 1 || buffer_rows > (1 << 22) || (buffer_rows + kBandRows) * 3 * H > ((int64_t)1 << 28))
+            throw InvalidConfig("buffer_rows must be 1 .. 2^22, (buffer_rows + 128) * 3 hidden at most 2^28");
+        check_cu(cu, batch, max_len, buffer_rows);
+        // (hipMalloc returns 256-byte aligned blocks: `aligned` is the hidden width's alone)
+        const AttentionRoute route = attention_route(batch, max_len, heads, head_dim, H % 4 == 0, true);
+        use_device(device);
+        const size_t qb = (size_t)buffer_rows * 3 * H * 4, cb = (size_t)buffer_rows * H * 4;
+        const BandBuf qd(qkv, qb, (size_t)kBandRows * 3 * H, "H2D qkv"), cd(cu, (size_t)(batch + 1) * 4, kBandWords, "H2D cu");
+        const BandBuf od(ctx, cb, (size_t)kBandRows * H, "H2D ctx");
+        launcher_check(launch_attention(qd.as<float>(), nullptr, batch, max_len, heads, head_dim, mask_value, od.as<float>(), nullptr, cd.as<int32_t>()),
+                       "attention (packed rows)");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.fetch(ctx, cb, "ctx");
+        route_out[0] = (int32_t)route.kernel;
+        route_out[1] = (int32_t)route.grid;
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_pool_packed(int32_t device, const float* hidden_states, const int32_t* cu, int64_t batch, int32_t seq,
+                                                        int32_t hidden, KjarniHipPooling pooling, int32_t normalize, float* out)
+{
+    if (!hidden_states || !cu || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (hidden < 1 || hidden > 1024) throw InvalidConfig("hidden must be 1 .. 1024");
+        const PoolMode mode = pool_mode(pooling);   // (throws InvalidConfig for a value outside the enum)
+        check_cu(cu, batch, seq, (int64_t)1 << 22);
+        use_device(device);
+        const size_t hb = (size_t)cu[batch] * hidden * 4, ob = (size_t)batch * hidden * 4;
+        const BandBuf hd(hidden_states, hb, (size_t)kBandRows * hidden, "H2D hidden states"), cd(cu, (size_t)(batch + 1) * 4, kBandWords, "H2D cu");
+        const BandBuf od(out, ob, (size_t)4 * hidden, "H2D out");
+        launcher_check(launch_pool(hd.as<float>(), nullptr, batch, seq, hidden, mode, normalize ? 1 : 0, od.as<float>(), nullptr, cd.as<int32_t>()),
+                       "pool (packed rows)");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.fetch(out, ob, "out");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_small_linear(int32_t device, const float* feat, int64_t ld, const float* w, const float* bias,
+                                                         int64_t rows, int32_t k, int32_t n, float* out)
+{
+    if (!feat || !w || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > (1 << 20) || k < 1 || k > (1 << 16) || n < 1 || n > 4096 || ld < k || ld > (1 << 20) || rows * ld > ((int64_t)1 << 28))
+            throw InvalidConfig("rows must be 1 .. 2^20, k 1 .. 2^16, n 1 .. 4096, ld k .. 2^20, rows * ld at most 2^28");
+        use_device(device);
+        const size_t ob = (size_t)rows * n * 4;
+        const BandBuf fd(feat, (size_t)rows * ld * 4, kBandWords, "H2D feat"), wd(w, (size_t)n * k * 4, kBandWords, "H2D w");
+        const BandBuf bd(bias, bias ? (size_t)n * 4 : 0, kBandWords, "H2D bias"), od(out, ob, kBandWords, "H2D out");
+        launcher_check(launch_small_linear(fd.as<float>(), ld, wd.as<float>(), bias ? bd.as<float>() : nullptr, rows, k, n, od.as<float>(), nullptr),
+                       "small_linear");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.fetch(out, ob, "out");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_row_softmax(int32_t device, const float* in, int64_t rows, int32_t n, int32_t sigmoid, float* out)
+{
+    if (!in || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > (1 << 20) || n < 1 || n > 4096 || rows * n > ((int64_t)1 << 26)) throw InvalidConfig("rows must be 1 .. 2^20, n 1 .. 4096");
+        use_device(device);
+        const size_t b = (size_t)rows * n * 4;
+        const BandBuf id(in, b, kBandWords, "H2D in"), od(out, b, kBandWords, "H2D out");
+        launcher_check(launch_row_softmax(id.as<float>(), rows, n, sigmoid ? 1 : 0, od.as<float>(), nullptr), "row_softmax");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.fetch(out, b, "out");
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_layer_norm(int32_t device, const float* x, const float* gamma,
                                                        const float* beta, float eps, int64_t rows, int32_t hidden,
                                                        float* y, int32_t iters, float* ms_out)

@@ -113,6 +113,10 @@ hipError_t launch_prefill_tiles_bf16w(unsigned grid, const float* A, int64_t lda
 // qkv is [tokens, 3*hidden] (Q | K | V), mask is u32 [batch, seq], ctx is
 // [tokens, hidden] with heads merged.
 // Packed rows: cu != null, mask is ignored (every row is a kept token), seq = the longest sentence of the call.
+// The caller's preconditions with cu (device data no launcher can look at; EncoderModel's plan_packing builds cu that way and
+// kjarni_hip_op_attention_packed refuses anything else): cu starts at 0 and increases strictly -- the kernels compute an item's
+// extent from len - 1, so an empty sentence must never reach them -- and no sentence is longer than seq: the grids cover seq
+// queries, the item-per-workgroup kernels hold 128 keys.
 hipError_t launch_attention(const float* qkv, const uint32_t* mask, int64_t batch, int seq,
                             int heads, int head_dim, float mask_value, float* ctx,
                             hipStream_t stream, const int32_t* cu = nullptr);
@@ -125,15 +129,34 @@ hipError_t launch_attention(const float* qkv, const uint32_t* mask, int64_t batc
 hipError_t launch_attention_biased(const float* qkv, const uint32_t* mask, const float* pos_bias, int bias_seq, int64_t batch, int seq,
                                    int heads, int head_dim, bool scale_qk, float mask_value, float* ctx, hipStream_t stream);
 
+// The kernel launch_attention takes for a call, and the grid of the item-per-workgroup kernels (0 for the others): a pure host
+// function the launcher follows (attention.hip has the rule), so that the op hooks and the tests can hold a call to its route.
+enum AttentionKernel : int {
+    ATTN_NOTHING = 0,      // batch <= 0 or seq <= 0
+    ATTN_SPLIT = 1,        // attention_split_kernel: at most 128 (sentence, head) items, seq <= 128
+    ATTN_PIPE_PADDED = 2,  // attention_pipe_kernel MODE 0: padded rows, 96 < seq <= 128
+    ATTN_PIPE_PACKED = 3,  // attention_pipe_kernel MODE 1: packed rows (cu), longest sentence <= 128
+    ATTN_PIPE_SHORT = 4,   // attention_pipe_kernel MODE 2: padded rows, seq <= 96
+    ATTN_CHUNKED = 5,      // attention_kernel: seq > 128, online softmax over chunks of 128 keys
+    ATTN_GENERIC = 6,      // attention_generic_kernel: head_dim other than 32 / 64, or operands not 16-byte aligned
+};
+struct AttentionRoute {
+    AttentionKernel kernel = ATTN_NOTHING;
+    unsigned grid = 0;
+};
+AttentionRoute attention_route(int64_t batch, int seq, int heads, int head_dim, bool aligned, bool packed);
+
 int attention_small_call_items();  // calls of up to this many (sentence, head) items take the small-call attention kernel
 
 // RoPE on the Q and K thirds of qkv [tokens, 3*hidden] in place, position = token index within its sentence
 // (RoPE::apply_3d with offset 0, cpu/rope/mod.rs:118-170, 210-245; encoder_self_attention.rs:81-85).
-// cos / sin are the reference's caches [>= seq, head_dim].
+// cos / sin are the reference's caches [>= seq, head_dim].  With tok_src the position is tok_src[t] % seq: any entry >= 0 stays
+// inside the tables, a negative one would read in front of them (the caller's precondition; pack_index_kernel writes none).
 hipError_t launch_rope_qk(float* qkv, const float* cos_t, const float* sin_t, int64_t tokens, int seq, int heads,
                           int head_dim, hipStream_t stream, const int32_t* tok_src = nullptr);
 
-// R11: pooling (+ optional L2 normalisation) of [batch, seq, hidden].
+// R11: pooling (+ optional L2 normalisation) of [batch, seq, hidden].  With cu (packed rows) the mask is ignored, as in
+// launch_attention, and sentence b is rows cu[b] .. cu[b+1]; hidden <= 1024 (hipErrorInvalidValue beyond).
 hipError_t launch_pool(const float* hidden_states, const uint32_t* mask, int64_t batch, int seq,
                        int hidden, PoolMode mode, int normalize, float* out, hipStream_t stream, const int32_t* cu = nullptr);
 

@@ -535,6 +535,124 @@ def decoder_embed(ids, word, pos, offset: int, out, offset_on_device: bool = Fal
     return o
 
 
+# ---- the encoder's packed-row kernels, alone (kjarni_hip.h has the contract of every hook) ----
+ATTN_NOTHING, ATTN_SPLIT, ATTN_PIPE_PADDED, ATTN_PIPE_PACKED, ATTN_PIPE_SHORT, ATTN_CHUNKED, ATTN_GENERIC = range(7)
+_i32p = C.POINTER(C.c_int32)
+
+
+def _u(a):
+    return None if a is None else a.ctypes.data_as(_ffi._u32p)
+
+
+def _i(a):
+    return None if a is None else a.ctypes.data_as(_i32p)
+
+
+def _cu(lengths_or_cu, is_cu):
+    a = np.asarray(lengths_or_cu, np.int64).reshape(-1)
+    return np.ascontiguousarray(a if is_cu else np.concatenate([[0], np.cumsum(a)]), np.int32)
+
+
+def mask_lengths(mask, lens, device: int = 0) -> np.ndarray:
+    """launch_mask_lengths: mask u32 [B, S] -> lens u32 [B] (as it is before the launch).  Returns a copy."""
+    m, ln = np.ascontiguousarray(mask, np.uint32), np.array(lens, np.uint32, order="C")
+    if m.ndim != 2 or ln.shape != (m.shape[0],):
+        raise ValueError("mask: [B, S]; lens: [B]")
+    check_error(lib().kjarni_hip_op_mask_lengths(device, _u(m), m.shape[0], m.shape[1], _u(ln)))
+    return ln
+
+
+def pack_index(mask, cu, tok_src, device: int = 0) -> np.ndarray:
+    """launch_pack_index: mask u32 [B, S], cu i32 [B + 1] -> tok_src i32 [capacity] (as it is before the launch).  Returns a copy."""
+    m, c, t = np.ascontiguousarray(mask, np.uint32), _cu(cu, True), np.array(tok_src, np.int32, order="C")
+    if m.ndim != 2 or c.size != m.shape[0] + 1 or t.ndim != 1:
+        raise ValueError("mask: [B, S]; cu: [B + 1]; tok_src: [capacity]")
+    check_error(lib().kjarni_hip_op_pack_index(device, _u(m), _i(c), m.shape[0], m.shape[1], _i(t), t.size))
+    return t
+
+
+def encoder_embed(ids, word, out, pos=None, type=None, type_ids=None, gamma=None, beta=None, eps: float = 0.0, vocab: Optional[int] = None,
+                  max_pos: Optional[int] = None, type_vocab: Optional[int] = None, pos_offset: int = 0, scale_embeddings: bool = False,
+                  tok_src=None, device: int = 0) -> np.ndarray:
+    """launch_embed_layernorm: ids u32 [B, S], word [>= vocab, H], pos [>= max_pos, H], type [>= type_vocab, H] -> out [rows, H] (as it
+    is before the launch).  vocab / max_pos / type_vocab default to the tables' rows.  Returns a copy."""
+    ia, wd, o = np.ascontiguousarray(ids, np.uint32), _c(word), np.array(out, np.float32, order="C")
+    pt, tt, g, b = _c(pos), _c(type), _c(gamma), _c(beta)
+    ty = None if type_ids is None else np.ascontiguousarray(type_ids, np.uint32)
+    ts = None if tok_src is None else np.ascontiguousarray(tok_src, np.int32)
+    if ia.ndim != 2 or wd.ndim != 2 or o.ndim != 2 or o.shape[1] != wd.shape[1] or (ts is not None and ts.shape != (o.shape[0],)) or \
+            (ty is not None and ty.shape != ia.shape):
+        raise ValueError("ids, type_ids: [B, S]; word: [vocab, H]; out: [rows, H]; tok_src: [rows]")
+    check_error(lib().kjarni_hip_op_encoder_embed(
+        device, _u(ia), _u(ty), _f(wd), _f(pt), _f(tt), _f(g), _f(b), float(eps), o.shape[0], ia.shape[0], ia.shape[1], o.shape[1],
+        wd.shape[0] if vocab is None else int(vocab), (0 if pt is None else pt.shape[0]) if max_pos is None else int(max_pos),
+        (0 if tt is None else tt.shape[0]) if type_vocab is None else int(type_vocab), int(pos_offset), int(bool(scale_embeddings)), _i(ts), _f(o)))
+    return o
+
+
+def encoder_rope(qkv, cos, sin, heads: int, head_dim: int, tok_src=None, device: int = 0) -> np.ndarray:
+    """launch_rope_qk: qkv [rows, 3 * heads * head_dim] (as it is before the launch), cos / sin [S, head_dim].  Returns a copy."""
+    q, c, s = np.array(qkv, np.float32, order="C"), _c(cos), _c(sin)
+    ts = None if tok_src is None else np.ascontiguousarray(tok_src, np.int32)
+    if q.ndim != 2 or q.shape[1] != 3 * heads * head_dim or c.shape != s.shape or c.ndim != 2 or c.shape[1] != head_dim or \
+            (ts is not None and ts.shape != (q.shape[0],)):
+        raise ValueError("qkv: [rows, 3 * heads * head_dim]; cos, sin: [S, head_dim]; tok_src: [rows]")
+    check_error(lib().kjarni_hip_op_encoder_rope(device, _f(q), _f(c), _f(s), q.shape[0], c.shape[0], int(heads), int(head_dim), _i(ts)))
+    return q
+
+
+def attention_route(batch: int, seq: int, heads: int, head_dim: int, aligned: bool = True, packed: bool = False) -> Tuple[int, int]:
+    """attention_route (the rule launch_attention follows): (kernel, grid of the item-per-workgroup kernels); no device."""
+    r = (C.c_int32 * 2)(-1, -1)
+    check_error(lib().kjarni_hip_attention_route(int(batch), int(seq), int(heads), int(head_dim), int(bool(aligned)), int(bool(packed)), r))
+    return int(r[0]), int(r[1])
+
+
+def attention_packed(qkv, lengths, heads: int, head_dim: int, ctx, max_len: Optional[int] = None, mask_value: float = -1e9, device: int = 0):
+    """launch_attention(..., cu): qkv [buffer_rows, 3 * heads * head_dim], sentence b = rows cu[b] .. cu[b + 1] with cu the prefix
+    sums of `lengths`; ctx [buffer_rows, heads * head_dim] as it is before the launch; max_len defaults to the longest sentence.
+    Returns (a copy of ctx, (kernel, grid))."""
+    q, o, cu = _c(qkv), np.array(ctx, np.float32, order="C"), _cu(lengths, False)
+    hidden = heads * head_dim
+    if q.ndim != 2 or q.shape[1] != 3 * hidden or o.shape != (q.shape[0], hidden):
+        raise ValueError("qkv: [buffer_rows, 3 * hidden]; ctx: [buffer_rows, hidden]")
+    r = (C.c_int32 * 2)(-1, -1)
+    ml = int(np.diff(cu).max()) if max_len is None else int(max_len)
+    check_error(lib().kjarni_hip_op_attention_packed(device, _f(q), _i(cu), cu.size - 1, ml, int(heads), int(head_dim), float(mask_value), _f(o),
+                                                     q.shape[0], r))
+    return o, (int(r[0]), int(r[1]))
+
+
+def pool_packed(hidden_states, lengths, out, pooling: int = POOL_MEAN, normalize: bool = False, seq: Optional[int] = None, device: int = 0):
+    """launch_pool(..., cu): hidden_states [sum(lengths), H] -> out [B, H] (as it is before the launch).  Returns a copy."""
+    h, o, cu = _c(hidden_states), np.array(out, np.float32, order="C"), _cu(lengths, False)
+    if h.ndim != 2 or h.shape[0] != cu[-1] or o.shape != (cu.size - 1, h.shape[1]):
+        raise ValueError("hidden_states: [sum(lengths), H]; out: [B, H]")
+    check_error(lib().kjarni_hip_op_pool_packed(device, _f(h), _i(cu), cu.size - 1, int(np.diff(cu).max()) if seq is None else int(seq), h.shape[1],
+                                                int(pooling), int(bool(normalize)), _f(o)))
+    return o
+
+
+def small_linear(feat, w, bias, out, k: Optional[int] = None, device: int = 0) -> np.ndarray:
+    """launch_small_linear: feat [rows, ld] (the first k columns of every row), w [n, k], bias [n] or None -> out [rows, n] (as it is
+    before the launch).  Returns a copy."""
+    x, wt, b, o = _c(feat), _c(w), _c(bias), np.array(out, np.float32, order="C")
+    if x.ndim != 2 or wt.ndim != 2 or o.shape != (x.shape[0], wt.shape[0]):
+        raise ValueError("feat: [rows, ld]; w: [n, k]; out: [rows, n]")
+    check_error(lib().kjarni_hip_op_small_linear(device, _f(x), x.shape[1], _f(wt), _f(b), x.shape[0], wt.shape[1] if k is None else int(k),
+                                                 wt.shape[0], _f(o)))
+    return o
+
+
+def row_softmax(x, out, sigmoid: bool = False, device: int = 0) -> np.ndarray:
+    """launch_row_softmax: x [rows, n] -> out [rows, n] (as it is before the launch).  Returns a copy."""
+    a, o = _c(x), np.array(out, np.float32, order="C")
+    if a.ndim != 2 or o.shape != a.shape:
+        raise ValueError("x, out: [rows, n]")
+    check_error(lib().kjarni_hip_op_row_softmax(device, _f(a), a.shape[0], a.shape[1], int(bool(sigmoid)), _f(o)))
+    return o
+
+
 # ---- mixture-of-experts: the router pick and the sparse FFN, alone ----
 def moe_route(logits, k: int, norm_topk: bool = False, device: int = 0):
     """launch_moe_route on host arrays (kjarni_hip_op_moe_route): logits [rows, E] -> (ids int32 [rows, k], weights f32 [rows, k]),
