@@ -1665,6 +1665,74 @@ KjarniErrorCode kjarni_hip_chat_set_grammar(KjarniChat* chat, const char* const*
 KjarniErrorCode kjarni_hip_generator_grammar_result(const KjarniGenerator* generator, KjarniHipGrammarResult* out);
 KjarniErrorCode kjarni_hip_chat_grammar_result(const KjarniChat* chat, KjarniHipGrammarResult* out);
 
+/* ---- generation log-probabilities: per emitted token its logprob and the top_k most likely alternatives ------------------------
+ * The distribution is the log-softmax of the logits as the vocabulary head wrote them: before the constraint or grammar mask,
+ * before the repetition penalty and the n-gram ban, before temperature and the sampler's cut -- kjarni_hip_decoder_score's
+ * distribution, so generating and then scoring prompt + output gives the same numbers inside the float bar.  The top_k
+ * alternatives are in kjarni_hip_decoder_score_topk's order: descending logit, among equal logits the larger id first; slot 0 is
+ * the greedy pick of the unmasked row.  top_k is 0 .. KJARNI_SCORE_TOPK_MAX and not above the vocabulary; 0 gives the emitted
+ * token's logprob alone.
+ *
+ * The slab rule of the kernels (0 outside rows 1..64 / vocab >= 1): slabs = min(64, ceil(vocab / 1024), max(1, ceil(512 / rows))),
+ * the slab length rounded up to a multiple of 4 elements and the slabs recounted over it.  No device is touched. */
+int32_t kjarni_hip_token_logprob_slabs(int32_t rows, int32_t vocab);
+/* The kernel pair alone on logits given by the host: one launch pair per call over logits [calls, rows, ld] (rows 1..64,
+ * ld >= vocab; what lies behind `vocab` in a row is not read).  tokens [calls, rows]: the chosen token of each row, -1 = skip:
+ * the outputs of a skipped row come back as the caller passed them.  logprob_out / lse_out [calls, rows], topk_ids_out /
+ * topk_logprob_out [calls, rows, top_k]; every output but logprob_out may be NULL.  *slabs_out: the slabs a row was cut into.
+ * Odd calls take the raw copy in the slab pass and read the chosen logit from it (INFERENCE_FAILED when the copy is not the
+ * row, or a guard band behind a device buffer was touched).  Every argument is checked before a device is asked for:
+ * INVALID_CONFIG names it. */
+KjarniErrorCode kjarni_hip_op_token_logprobs(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld, int32_t vocab,
+                                             const int32_t* tokens, int32_t top_k, float* logprob_out, uint32_t* topk_ids_out,
+                                             float* topk_logprob_out, float* lse_out, int32_t* slabs_out);
+/* Timing for tools/bench_more.py: the milliseconds of one launch pair over logits [rows, vocab] (rows 1..64, top_k 1..8) and of
+ * the one-workgroup-per-row score kernel (the rows route of kjarni_hip_decoder_score_topk, 8 rows a launch) over the same rows,
+ * each the mean of `iters` back-to-back repeats between two events. */
+KjarniErrorCode kjarni_hip_op_token_logprobs_bench(int32_t device, const float* logits, int32_t rows, int32_t vocab, int32_t top_k, int32_t iters,
+                                                   float* pair_ms_out, float* score_rows_ms_out);
+/* The plain loop of kjarni_hip_decoder_generate_sampled (no lookup, no drafter: a request that asks for log-probabilities takes
+ * the plain loop), under `constraint` or `grammar` when one is given (both: INVALID_CONFIG), with the records of the first
+ * min(*n_out, capacity) emitted tokens: logprob_out [capacity], topk_ids_out / topk_logprob_out [capacity, top_k] (NULL allowed
+ * for each; entries past the emitted tokens are not written).  The ids are those of the entry without log-probabilities for
+ * the same options and draws.  A stop id is not emitted and has no record.  Plain greedy replays a chain of its own, pass ->
+ * slab pass -> argmax -> record (constrained: pass -> slab pass with the raw copy -> apply -> argmax -> record -> advance),
+ * the records fetched with the tokens; with processors or sampling the slab pass runs ahead of the mask and the processors and
+ * the record is written once the host has decided; with device sampling off the host computes the record in float32 from the
+ * raw row.  Refusals are those entries', plus top_k outside 0 .. KJARNI_SCORE_TOPK_MAX or above the vocabulary
+ * (INVALID_CONFIG naming top_k), before any GPU work, with the outputs and the cache untouched.  constraint_result /
+ * grammar_result may be NULL. */
+KjarniErrorCode kjarni_hip_decoder_generate_logprobs(KjarniHipDecoder* decoder, const KjarniHipConstraint* constraint,
+                                                     const KjarniHipGrammarConstraint* grammar, const uint32_t* prompt, size_t n_prompt,
+                                                     const KjarniHipSamplingOptions* options, int32_t top_k, KjarniTokenCallbackFn on_token,
+                                                     void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out, float* logprob_out,
+                                                     uint32_t* topk_ids_out, float* topk_logprob_out, KjarniHipConstraintResult* constraint_result,
+                                                     KjarniHipGrammarResult* grammar_result);
+/* kjarni_hip_decoder_generate_wide with records: its arguments, then top_k and logprob_out [n, capacity], topk_ids_out /
+ * topk_logprob_out [n, capacity, top_k] (NULL allowed for each), prompt i's records for its first min(n_out[i], capacity) tokens.
+ * Every width 1..64 is served (8 or fewer on the lanes step, as kjarni_hip_decoder_generate_wide forwards).  The kernel pair
+ * runs over all lane rows in one launch ahead of the pick, inside the captured step; a lane's record index is its own
+ * device-held count, so a lane that takes the next waiting prompt starts at record 0.  A request with a penalty or an n-gram
+ * ban is recorded lane by lane, as the single-sequence loop does.  The ids are kjarni_hip_decoder_generate_wide's.  top_k outside
+ * 0 .. KJARNI_SCORE_TOPK_MAX or above the vocabulary: INVALID_CONFIG naming top_k, before any GPU work. */
+KjarniErrorCode kjarni_hip_decoder_generate_wide_logprobs(KjarniHipDecoder* decoder, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                          const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size,
+                                                          int32_t lanes, int32_t lane_context, KjarniBatchTokenCallbackFn on_token,
+                                                          void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out, int32_t top_k,
+                                                          float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out);
+/* Log-probabilities for every later request of the handle: top_k 0 .. KJARNI_SCORE_TOPK_MAX (not above the vocabulary), -1 = off
+ * (the default); another value is INVALID_CONFIG and leaves the handle as it was.  While set, generate / stream / send take the
+ * plain loop even when prompt lookup or a draft model is switched on, as under a constraint, and generate_batch records every
+ * prompt on its lanes. */
+KjarniErrorCode kjarni_hip_generator_set_logprobs(KjarniGenerator* generator, int32_t top_k);
+KjarniErrorCode kjarni_hip_chat_set_logprobs(KjarniChat* chat, int32_t top_k);
+/* The tokens the handle's last generate / stream / send* call emitted (prompt_index 0) -- or prompt `prompt_index` of its last
+ * generate_batch call -- with their log-probabilities and alternatives, as kjarni_generator_score_tokens lays them out.  Zeros
+ * before any call, after a call that ran with log-probabilities off, and for an index the call did not have.  Free with
+ * kjarni_token_scores_free. */
+KjarniErrorCode kjarni_hip_generator_last_logprobs(const KjarniGenerator* generator, size_t prompt_index, KjarniTokenScores* out);
+KjarniErrorCode kjarni_hip_chat_last_logprobs(const KjarniChat* chat, KjarniTokenScores* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -675,6 +675,20 @@ SIGNATURES = {
     "kjarni_hip_decoder_generate_grammar": (c_int32, [c_void_p, c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
                                                       KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t),
                                                       POINTER(KjarniHipGrammarResult)]),
+    "kjarni_hip_token_logprob_slabs": (c_int32, [c_int32, c_int32]),
+    "kjarni_hip_op_token_logprobs_bench": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p]),
+    "kjarni_hip_decoder_generate_wide_logprobs": (c_int32, [c_void_p, _u32p, POINTER(c_size_t), c_size_t, POINTER(c_size_t), c_float, c_int32,
+                                                            c_int32, c_int32, KjarniBatchTokenCallbackFn, c_void_p, _u32p, c_size_t,
+                                                            POINTER(c_size_t), c_int32, _f32p, _u32p, _f32p]),
+    "kjarni_hip_generator_set_logprobs": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_chat_set_logprobs": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_last_logprobs": (c_int32, [c_void_p, c_size_t, POINTER(KjarniTokenScores)]),
+    "kjarni_hip_chat_last_logprobs": (c_int32, [c_void_p, POINTER(KjarniTokenScores)]),
+    "kjarni_hip_op_token_logprobs": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int64, c_int32, POINTER(c_int32), c_int32, _f32p, _u32p,
+                                               _f32p, _f32p, POINTER(c_int32)]),
+    "kjarni_hip_decoder_generate_logprobs": (c_int32, [c_void_p, c_void_p, c_void_p, _u32p, c_size_t, POINTER(KjarniHipSamplingOptions),
+                                                       c_int32, KjarniTokenCallbackFn, c_void_p, _u32p, c_size_t, POINTER(c_size_t), _f32p,
+                                                       _u32p, _f32p, POINTER(KjarniHipConstraintResult), POINTER(KjarniHipGrammarResult)]),
     "kjarni_hip_generator_set_grammar": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_int32]),
     "kjarni_hip_chat_set_grammar": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_int32]),
     "kjarni_hip_generator_grammar_result": (c_int32, [c_void_p, POINTER(KjarniHipGrammarResult)]),

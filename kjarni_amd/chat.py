@@ -186,6 +186,27 @@ class Chat:
         path = model_dir_or_gguf.encode("utf-8") if model_dir_or_gguf else None
         check_error(lib().kjarni_hip_chat_set_draft_model(self._handle, path, int(draft_tokens)))
 
+    def set_logprobs(self, top_k: Optional[int]):
+        """Log-probabilities for every later request: top_k 0..8 alternatives per emitted token (0: the token's own logprob
+        alone), None or -1 = off (the default).  While set, requests take the plain loop even when prompt lookup or a draft
+        model is switched on.  The distribution is score()'s: the raw logits, before processors, temperature and the cut."""
+        check_error(lib().kjarni_hip_chat_set_logprobs(self._handle, -1 if top_k is None else int(top_k)))
+
+    def last_logprobs(self):
+        """(tokens u32 [n], logprobs f32 [n], top_tokens u32 [n, top_k], top_logprobs f32 [n, top_k]) of the tokens the last
+        send() / stream() call emitted; empty arrays before any call and after one that ran with logprobs off."""
+        r = _ffi.KjarniTokenScores()
+        check_error(lib().kjarni_hip_chat_last_logprobs(self._handle, C.byref(r)))
+        try:
+            n, k = int(r.n_tokens), int(r.top_k)
+            if n == 0:
+                return (np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros((0, k), np.uint32), np.zeros((0, k), np.float32))
+            top = (np.ctypeslib.as_array(r.top_tokens, (n, k)).copy(), np.ctypeslib.as_array(r.top_logprobs, (n, k)).copy()) if k else \
+                (np.zeros((n, 0), np.uint32), np.zeros((n, 0), np.float32))
+            return (np.ctypeslib.as_array(r.tokens, (n,)).copy(), np.ctypeslib.as_array(r.logprobs, (n,)).copy()) + top
+        finally:
+            lib().kjarni_token_scores_free(C.byref(r))
+
     def set_constraint(self, pattern: Optional[str]):
         """Constrained decoding for send(): every later reply is text that `pattern` matches in full (builders in
         kjarni_amd.constraints); None restores the plain behaviour.  While set, requests take the plain loop even when prompt

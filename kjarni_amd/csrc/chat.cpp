@@ -357,10 +357,16 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
                                 const std::vector<uint32_t>& stop_ids, UniformRng& rng, const std::function<bool(const std::string&)>& on_text,
                                 int prompt_lookup = 0, int sampled_lookup = 0, LlmModel* drafter = nullptr, int draft_tokens = 0,
                                 const DeviceConstraint* constraint = nullptr, ConstraintOutcome* outcome = nullptr,
-                                const DeviceGrammar* grammar = nullptr)
+                                const DeviceGrammar* grammar = nullptr, int logprobs = -1, GeneratedLogprobs* generated = nullptr)
 {
     if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt");
     GenerateOptions opt = text_generation_options(model, tokens.size(), config, stop_ids, rng);
+    if (generated) *generated = GeneratedLogprobs{};
+    const bool records = logprobs >= 0 && generated;
+    if (records) {
+        opt.logprobs = logprobs;
+        opt.logprob_sink = &generated->records;
+    }
     opt.constraint = constraint;
     opt.grammar = grammar;
     opt.constraint_outcome = constraint || grammar ? outcome : nullptr;
@@ -370,12 +376,14 @@ std::string run_text_generation(LlmModel& model, const BpeTokenizer& tok, const 
     const auto on_token = [&](uint32_t id) {
         const std::string piece = tok.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
         text += piece;
+        if (records) generated->tokens.push_back(id);
         return on_text ? on_text(piece) : true;
     };
     // a draft model (when set) takes precedence over prompt lookup: greedy requests without processors and sampled requests
     // without an n-gram ban verify the drafter's proposals every step; the others take the plain loop inside generate_draft
     // (a constrained request takes the plain loop: the lookup and draft loops do not carry the automaton)
-    if (constraint || grammar) {
+    // (a request that records log-probabilities takes the plain loop too)
+    if (constraint || grammar || records) {
         model.generate(prompt_tokens, opt, on_token);
     } else if (drafter && draft_tokens > 0) {
         model.generate_draft(drafter, prompt_tokens, opt, draft_tokens, on_token, nullptr);
@@ -603,6 +611,39 @@ void Generator::set_grammar(const std::vector<std::pair<std::string, std::string
     if (grammar_) set_handle_constraint(*model_, tokenizer_, "", constraint_pattern_, constraint_);
 }
 
+static void check_handle_logprobs(const LlmModel& model, int top_k)
+{
+    if (top_k < -1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > model.config().vocab)
+        throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be -1 (off) or in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                            "] and not above the vocabulary size " + std::to_string(model.config().vocab));
+}
+
+void Chat::set_logprobs(int top_k)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    check_handle_logprobs(*model_, top_k);
+    logprobs_ = top_k;
+}
+
+void Generator::set_logprobs(int top_k)
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    check_handle_logprobs(*model_, top_k);
+    logprobs_ = top_k;
+}
+
+GeneratedLogprobs Chat::last_logprobs() const
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    return last_logprobs_;
+}
+
+GeneratedLogprobs Generator::last_logprobs(size_t prompt_index) const
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    return prompt_index < last_logprobs_.size() ? last_logprobs_[prompt_index] : GeneratedLogprobs{};
+}
+
 void Chat::set_draft_model(const std::string& path, int draft_tokens)
 {
     std::lock_guard<std::mutex> lock(mutex_);
@@ -622,7 +663,7 @@ std::string Chat::run(const std::string& prompt, const GenerationOverrides& runt
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, 0,
                                lookup_sampling_ ? LookupConfig().draft_tokens : 0, drafter_.get(), draft_tokens_, constraint_.get(),
-                               &constraint_outcome_, grammar_.get());
+                               &constraint_outcome_, grammar_.get(), logprobs_, &last_logprobs_);
 }
 
 std::string Chat::generate(const std::string& prompt, const GenerationOverrides& runtime)
@@ -706,9 +747,10 @@ std::string Generator::run(const std::string& prompt, const GenerationOverrides&
     std::lock_guard<std::mutex> lock(mutex_);
     const GenerationConfig config = resolve(runtime);
     if (config.strategy == Strategy::BeamSearch) throw std::runtime_error("generation failed: Beam search is not supported in this generator.");
+    last_logprobs_.assign(1, GeneratedLogprobs{});
     return run_text_generation(*model_, tokenizer_, encode(prompt, config), config, stop_ids_, rng_, on_text, prompt_lookup_,
                                lookup_sampling_ ? prompt_lookup_ : 0, drafter_.get(), draft_tokens_, constraint_.get(), &constraint_outcome_,
-                               grammar_.get());
+                               grammar_.get(), logprobs_, &last_logprobs_[0]);
 }
 
 size_t Generator::encode_scored(const std::string& context, const std::string& continuation, std::vector<uint32_t>& whole) const
@@ -838,17 +880,23 @@ std::vector<std::string> Generator::generate_batch(const std::vector<std::string
     std::vector<UniformRng> rngs;
     rngs.reserve(prompts.size());
     std::vector<LaneRequest> reqs(prompts.size());
+    last_logprobs_.assign(prompts.size(), GeneratedLogprobs{});
     for (size_t i = 0; i < prompts.size(); ++i) {
         rngs.emplace_back(config.strategy == Strategy::Sample ? (uint64_t)(rng_.next() * 16777216.0f) + 1 : 1);
         std::vector<uint32_t> tokens = encode(prompts[i], config);
         if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
         reqs[i].options = text_generation_options(*model_, tokens.size(), config, stop_ids_, rngs[i]);
+        if (logprobs_ >= 0) {
+            reqs[i].options.logprobs = logprobs_;
+            reqs[i].options.logprob_sink = &last_logprobs_[i].records;
+        }
         if ((int)tokens.size() > model_->context()) tokens.resize((size_t)model_->context());
         reqs[i].prompt = std::move(tokens);
     }
     std::vector<std::string> texts(prompts.size());
     const std::function<bool(size_t, uint32_t)> on_token = [&](size_t r, uint32_t id) {
         texts[r] += tokenizer_.decode({id}, false);  // one token at a time, specials kept (generator.rs:343-345)
+        if (logprobs_ >= 0) last_logprobs_[r].tokens.push_back(id);
         return true;
     };
     if (wide_lanes_ > 0) model_->generate_wide(reqs, wide_lanes_, 0, on_token);  // (set_wide_lanes: up to 64, the wide step above 8)

@@ -75,6 +75,12 @@ GenerationConfig resolve_generation_config(GenerationConfig model_defaults, cons
 GenerationConfig model_default_generation_config(const std::string& model_type, size_t max_position_embeddings,
                                                  const std::string* generation_config_json);
 
+// The tokens a handle's last request emitted and their log-probability records (Chat / Generator::last_logprobs).
+struct GeneratedLogprobs {
+    std::vector<uint32_t> tokens;
+    TokenLogprobs records;
+};
+
 class Chat {
 public:
     // model_name: registry name (decides architecture, template and the on-disk directory); model_dir overrides the
@@ -118,6 +124,14 @@ public:
     // The same with a grammar (grammar.h: rules (name, pattern), rule 0 the start rule) in the pattern's place; no rule removes it.
     // A handle holds a pattern or a grammar: setting one clears the other.  constraint_outcome() reports either kind of request.
     void set_grammar(const std::vector<std::pair<std::string, std::string>>& rules);
+    // Log-probabilities of the generated tokens (GenerateOptions::logprobs): -1 = off (the default), 0..KJARNI_SCORE_TOPK_MAX = every
+    // later request records, per emitted token, its log-probability under the raw distribution and that many alternatives.  While
+    // set, requests take the plain loop even when prompt lookup or a draft model is switched on (as under a constraint).
+    // InvalidConfig for a value outside -1..KJARNI_SCORE_TOPK_MAX or above the vocabulary.
+    void set_logprobs(int top_k);
+    int logprobs() const { return logprobs_; }
+    // The tokens of the last request and their records (empty before any request, and after one that ran with logprobs off).
+    GeneratedLogprobs last_logprobs() const;
 
 private:
     Chat() = default;
@@ -141,7 +155,9 @@ private:
     std::unique_ptr<DeviceConstraint> constraint_;
     std::unique_ptr<DeviceGrammar> grammar_;
     ConstraintOutcome constraint_outcome_;
-    std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
+    int logprobs_ = -1;
+    GeneratedLogprobs last_logprobs_;
+    mutable std::mutex mutex_;  // one generation at a time per handle (the KV cache is the handle's)
 };
 
 // Raw text completion (the reference's Generator): validation, model defaults (GenerationConfig::default() for GPT-2) and the
@@ -188,6 +204,15 @@ public:
     void set_constraint(const std::string& pattern);
     ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }
     void set_grammar(const std::vector<std::pair<std::string, std::string>>& rules);  // (Chat::set_grammar's contract)
+    // Log-probabilities of the generated tokens (GenerateOptions::logprobs): -1 = off (the default), 0..KJARNI_SCORE_TOPK_MAX = every
+    // later request records, per emitted token, its log-probability under the raw distribution and that many alternatives.  While
+    // set, requests take the plain loop even when prompt lookup or a draft model is switched on (as under a constraint).
+    // InvalidConfig for a value outside -1..KJARNI_SCORE_TOPK_MAX or above the vocabulary.
+    void set_logprobs(int top_k);
+    int logprobs() const { return logprobs_; }
+    // The tokens and records of prompt `prompt_index` of the last generate / stream (index 0) / generate_batch call; empty before
+    // any call, after a call that ran with logprobs off, and for an index the call did not have.
+    GeneratedLogprobs last_logprobs(size_t prompt_index) const;
     // The log-likelihood of `continuation` after `context` (LlmModel::score).  Tokens as lm-eval-harness takes them, with
     // encode() under the model's default config: whole = encode(context + continuation), first = len(encode(context)), scored
     // whole[first:].  InvalidConfig, nothing truncated: no context token (empty context, model without BOS), a continuation
@@ -227,7 +252,7 @@ private:
     GenerationConfig generation_config_;  // the model's defaults (no builder overrides through the C ABI)
     std::vector<uint32_t> stop_ids_;
     UniformRng rng_;
-    std::mutex mutex_;
+    mutable std::mutex mutex_;
     int batch_lanes_ = 0, wide_lanes_ = 0;
     int prompt_lookup_ = 0;
     bool lookup_sampling_ = false;
@@ -237,6 +262,8 @@ private:
     std::unique_ptr<DeviceConstraint> constraint_;
     std::unique_ptr<DeviceGrammar> grammar_;
     ConstraintOutcome constraint_outcome_;
+    int logprobs_ = -1;
+    std::vector<GeneratedLogprobs> last_logprobs_;
 };
 
 // str::trim (Unicode White_Space at both ends).

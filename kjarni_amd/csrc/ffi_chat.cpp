@@ -908,6 +908,57 @@ KJARNI_EXPORT KjarniErrorCode kjarni_bpe_tokenizer_token_bytes(const KjarniBpeTo
     });
 }
 
+// ---- generation log-probabilities on the handles -------------------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_logprobs(KjarniGenerator* gen, int32_t top_k)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->set_logprobs(top_k); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_logprobs(KjarniChat* chat, int32_t top_k)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->set_logprobs(top_k); });
+}
+
+// The records of a request as a KjarniTokenScores the caller frees (zeros for an empty one).
+static void fill_token_scores(const GeneratedLogprobs& g, KjarniTokenScores* out)
+{
+    const size_t n = std::min(g.tokens.size(), g.records.logprob.size()), k = (size_t)std::max(g.records.top_k, 0);
+    if (n == 0) return;
+    KjarniTokenScores r{};
+    r.tokens = static_cast<uint32_t*>(std::malloc(n * sizeof(uint32_t)));
+    r.logprobs = static_cast<float*>(std::malloc(n * sizeof(float)));
+    r.top_tokens = static_cast<uint32_t*>(std::malloc(std::max<size_t>(n * k, 1) * sizeof(uint32_t)));
+    r.top_logprobs = static_cast<float*>(std::malloc(std::max<size_t>(n * k, 1) * sizeof(float)));
+    if (!r.tokens || !r.logprobs || !r.top_tokens || !r.top_logprobs) {
+        kjarni_token_scores_free(&r);
+        throw std::bad_alloc();
+    }
+    std::memcpy(r.tokens, g.tokens.data(), n * sizeof(uint32_t));
+    std::memcpy(r.logprobs, g.records.logprob.data(), n * sizeof(float));
+    if (k) std::memcpy(r.top_tokens, g.records.topk_ids.data(), n * k * sizeof(uint32_t));
+    if (k) std::memcpy(r.top_logprobs, g.records.topk_logprob.data(), n * k * sizeof(float));
+    r.n_tokens = n;
+    r.top_k = k;
+    *out = r;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_last_logprobs(const KjarniGenerator* gen, size_t prompt_index, KjarniTokenScores* out)
+{
+    if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = KjarniTokenScores{};
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { fill_token_scores(gen->inner->last_logprobs(prompt_index), out); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_last_logprobs(const KjarniChat* chat, KjarniTokenScores* out)
+{
+    if (!chat || !out) return KJARNI_ERROR_NULL_POINTER;
+    *out = KjarniTokenScores{};
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { fill_token_scores(chat->inner->last_logprobs(), out); });
+}
+
 // A draft model owned by the handle (Chat::set_draft_model): NULL / 0 frees it.
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_draft_model(KjarniGenerator* gen, const char* model_dir_or_gguf, int32_t draft_tokens)
 {

@@ -156,7 +156,8 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate(KjarniHipDecoder* d, c
 static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
                                          const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t lanes,
                                          int32_t lane_context, KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
-                                         size_t capacity, size_t* n_out)
+                                         size_t capacity, size_t* n_out, int32_t top_k = -1, float* logprob_out = nullptr,
+                                         uint32_t* topk_ids_out = nullptr, float* topk_logprob_out = nullptr)
 {
     if (!d) return KJARNI_ERROR_NULL_POINTER;
     if (n == 0) return KJARNI_OK;  // nothing to do, nothing written
@@ -167,7 +168,11 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
         if (wide && (lanes < 0 || lanes > LlmModel::kWideLanes)) throw InvalidConfig("lanes must be 0..64 (0 = 64)");
         if (!wide && (lanes < 0 || lanes > LlmModel::kLanes)) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
         const int cap = lane_context <= 0 ? d->model->context() : std::min(d->model->context(), (int)lane_context);
+        if (top_k < -1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > d->model->config().vocab)  // (-1: the entries without records)
+            throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                                "] and not above the vocabulary (" + std::to_string(d->model->config().vocab) + ")");
         std::vector<LaneRequest> reqs(n);
+        std::vector<TokenLogprobs> records(top_k >= 0 ? n : 0);
         for (size_t i = 0; i < n; ++i) {
             if (offsets[i + 1] < offsets[i]) throw InvalidConfig("prompt offsets must not decrease");
             if (wide && offsets[i + 1] == offsets[i]) throw InvalidConfig("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
@@ -178,6 +183,10 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
             reqs[i].options.max_new_tokens = max_new_tokens[i];
             reqs[i].options.repetition_penalty = repetition_penalty;
             reqs[i].options.no_repeat_ngram = no_repeat_ngram_size;
+            if (top_k >= 0) {
+                reqs[i].options.logprobs = top_k;
+                reqs[i].options.logprob_sink = &records[i];
+            }
         }
         std::function<bool(size_t, uint32_t)> cb;
         if (on_token)
@@ -193,6 +202,13 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
         for (size_t i = 0; i < n; ++i) {
             n_out[i] = got[i].size();
             if (capacity) std::memcpy(ids_out + i * capacity, got[i].data(), std::min(capacity, got[i].size()) * sizeof(uint32_t));
+            if (top_k < 0) continue;
+            const TokenLogprobs& r = records[i];
+            if (r.logprob.size() != got[i].size()) throw std::runtime_error("generate: the records do not match the emitted tokens");
+            const size_t m = std::min(capacity, got[i].size()), k = (size_t)top_k;
+            if (logprob_out && m) std::memcpy(logprob_out + i * capacity, r.logprob.data(), m * sizeof(float));
+            if (topk_ids_out && m && k) std::memcpy(topk_ids_out + i * capacity * k, r.topk_ids.data(), m * k * sizeof(uint32_t));
+            if (topk_logprob_out && m && k) std::memcpy(topk_logprob_out + i * capacity * k, r.topk_logprob.data(), m * k * sizeof(float));
         }
     });
 }
@@ -217,6 +233,21 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_wide(KjarniHipDecoder*
 {
     return generate_batch_on(d, true, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
                              on_token, user_data, ids_out, capacity, n_out);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_wide_logprobs(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets,
+                                                                        size_t n, const size_t* max_new_tokens, float repetition_penalty,
+                                                                        int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                                        KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                        size_t capacity, size_t* n_out, int32_t top_k, float* logprob_out,
+                                                                        uint32_t* topk_ids_out, float* topk_logprob_out)
+{
+    if (top_k < 0 || top_k > KJARNI_SCORE_TOPK_MAX) {  // (judged ahead of the handle)
+        set_last_error("top_k (" + std::to_string(top_k) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) + "]");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    return generate_batch_on(d, true, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
+                             on_token, user_data, ids_out, capacity, n_out, top_k, logprob_out, topk_ids_out, topk_logprob_out);
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_begin(KjarniHipDecoder* d, int32_t lanes, int32_t lane_context)
@@ -567,6 +598,77 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_grammar(KjarniHipDecod
         if (result)
             *result = KjarniHipGrammarResult{outcome.final_state, outcome.device_state, outcome.final_depth, outcome.device_depth,
                                              outcome.accepted ? 1 : 0, outcome.complete ? 1 : 0, outcome.violated ? 1 : 0};
+    });
+}
+
+// ---- generation log-probabilities ------------------------------------------------------------------------------------------------
+
+// The plain loop of the three entries above (constraint / grammar: at most one, either may be NULL) with options.logprobs set;
+// the draws as there.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_logprobs(KjarniHipDecoder* d, const KjarniHipConstraint* constraint,
+                                                                   const KjarniHipGrammarConstraint* grammar, const uint32_t* prompt, size_t n_prompt,
+                                                                   const KjarniHipSamplingOptions* options, int32_t top_k,
+                                                                   KjarniTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                   size_t capacity, size_t* n_out, float* logprob_out, uint32_t* topk_ids_out,
+                                                                   float* topk_logprob_out, KjarniHipConstraintResult* constraint_result,
+                                                                   KjarniHipGrammarResult* grammar_result)
+{
+    if (!options || !n_out) return KJARNI_ERROR_NULL_POINTER;
+    *n_out = 0;
+    if (constraint_result) *constraint_result = KjarniHipConstraintResult{};
+    if (grammar_result) *grammar_result = KjarniHipGrammarResult{};
+    if (options->uniforms && options->n_uniforms < options->max_new_tokens) {  // (the options are judged on their own, ahead of the handles)
+        set_last_error("n_uniforms (" + std::to_string(options->n_uniforms) + ") is less than max_new_tokens (" +
+                       std::to_string(options->max_new_tokens) + ")");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (top_k < 0 || top_k > KJARNI_SCORE_TOPK_MAX) {
+        set_last_error("top_k (" + std::to_string(top_k) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) + "]");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (constraint && grammar) {
+        set_last_error("a call takes a constraint or a grammar, not both");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    if (!d || (n_prompt && !prompt) || (capacity && !ids_out) || (options->n_stop && !options->stop_ids)) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n_prompt == 0) throw InvalidConfig("cannot generate from an empty prompt");
+        std::lock_guard<std::mutex> lock(d->mu);
+        if (n_prompt > (size_t)d->model->context())
+            throw InvalidConfig("prompt (" + std::to_string(n_prompt) + " tokens) does not fit the context of " +
+                                std::to_string(d->model->context()) + " tokens");
+        const std::function<bool(uint32_t)> cb = token_callback(on_token, user_data);
+        GenerateOptions opt = sampling_options(*options);
+        UniformRng rng(options->seed);
+        size_t drawn = 0;
+        const float* u = options->uniforms;
+        const size_t n_u = options->n_uniforms;
+        if (u)
+            opt.uniform = [&drawn, u, n_u] {
+                if (drawn >= n_u) throw std::runtime_error("the draw stream is exhausted: more draws than uniforms");
+                return u[drawn++];
+            };
+        else opt.uniform = [&rng] { return rng.next(); };
+        ConstraintOutcome outcome;
+        if (constraint) opt.constraint = constraint->inner.get();
+        if (grammar) opt.grammar = grammar->inner.get();
+        opt.constraint_outcome = &outcome;
+        TokenLogprobs records;
+        opt.logprobs = top_k;
+        opt.logprob_sink = &records;
+        const std::vector<uint32_t> ids = d->model->generate(std::vector<uint32_t>(prompt, prompt + n_prompt), opt, cb);  // refusals first
+        copy_ids_out(ids, ids_out, capacity, n_out);
+        const size_t n = std::min(std::min(ids.size(), capacity), records.logprob.size());
+        if (logprob_out && n) std::memcpy(logprob_out, records.logprob.data(), n * sizeof(float));
+        if (topk_ids_out && n && top_k) std::memcpy(topk_ids_out, records.topk_ids.data(), n * (size_t)top_k * sizeof(uint32_t));
+        if (topk_logprob_out && n && top_k) std::memcpy(topk_logprob_out, records.topk_logprob.data(), n * (size_t)top_k * sizeof(float));
+        if (records.logprob.size() != ids.size()) throw std::runtime_error("generate: the records do not match the emitted tokens");
+        if (constraint && constraint_result)
+            *constraint_result = KjarniHipConstraintResult{outcome.final_state, outcome.device_state, outcome.accepted ? 1 : 0,
+                                                           outcome.complete ? 1 : 0, outcome.violated ? 1 : 0};
+        if (grammar && grammar_result)
+            *grammar_result = KjarniHipGrammarResult{outcome.final_state, outcome.device_state, outcome.final_depth, outcome.device_depth,
+                                                     outcome.accepted ? 1 : 0, outcome.complete ? 1 : 0, outcome.violated ? 1 : 0};
     });
 }
 

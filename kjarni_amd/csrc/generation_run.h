@@ -25,6 +25,28 @@ struct ConstraintOutcome {
     int32_t final_depth = 0, device_depth = 0;  // under a grammar: the stack depths that go with the two states
 };
 
+// The log-probability records of a run (GenerateOptions::logprobs), one per emitted token, in emission order.
+struct TokenLogprobs {
+    int top_k = 0;
+    std::vector<float> logprob;        // [tokens]: the emitted token's log-probability
+    std::vector<uint32_t> topk_ids;    // [tokens, top_k]: the most likely tokens, score_topk's order
+    std::vector<float> topk_logprob;   // [tokens, top_k]
+    void clear(int k)
+    {
+        top_k = k;
+        logprob.clear();
+        topk_ids.clear();
+        topk_logprob.clear();
+    }
+    // ids / lps: at least top_k entries
+    void push(float lp, const uint32_t* ids, const float* lps)
+    {
+        logprob.push_back(lp);
+        topk_ids.insert(topk_ids.end(), ids, ids + top_k);
+        topk_logprob.insert(topk_logprob.end(), lps, lps + top_k);
+    }
+};
+
 // One run of run_generation_loop (generator.rs:228-381).
 struct GenerateOptions {
     size_t max_new_tokens = 0;
@@ -40,6 +62,12 @@ struct GenerateOptions {
     ConstraintOutcome* constraint_outcome = nullptr;  // may be null
     // ... or a grammar (a stack automaton: grammar_kernels.h) in its place; setting both is InvalidConfig.  The outcome as above.
     const DeviceGrammar* grammar = nullptr;
+    // Log-probabilities of the emitted tokens (logprob_kernels.h): -1 = off (nothing changes: the same graphs, the same launches),
+    // 0 .. KJARNI_SCORE_TOPK_MAX = the emitted token's logprob and that many alternatives, under the log-softmax of the logits as
+    // the vocabulary head wrote them (before the mask, the processors, temperature and the cut).  generate() alone takes it; the
+    // lookup and draft loops forward a request that sets it to generate() (stats zero, the drafter untouched).
+    int logprobs = -1;
+    TokenLogprobs* logprob_sink = nullptr;  // cleared, then one record per emitted token; may be null
 };
 
 // What a loop does with the last token of a run that ends on max_new_tokens.  The choice shows in the cache length a call

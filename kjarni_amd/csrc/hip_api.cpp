@@ -22,6 +22,7 @@
 #include "whisper_kernels.h"
 #include "quant_kernels.h"
 #include "moe_kernels.h"
+#include "logprob_kernels.h"
 
 using namespace kjarni;
 
@@ -2605,6 +2606,109 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, cons
         if (topk_ids_out) hip_check(hipMemcpy(topk_ids_out, TI, kb, hipMemcpyDeviceToHost), "D2H top-k ids");
         if (topk_logprob_out) hip_check(hipMemcpy(topk_logprob_out, TL, kb, hipMemcpyDeviceToHost), "D2H top-k logprob");
         if (lse_out) hip_check(hipMemcpy(lse_out, LS, ob, hipMemcpyDeviceToHost), "D2H lse");
+    });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_token_logprob_slabs(int32_t rows, int32_t vocab)
+{
+    return rows < 1 || rows > kLogprobMaxRows || vocab < 1 ? 0 : token_logprob_slabs(rows, vocab);
+}
+
+// The generation log-probability kernels alone (logprob_kernels.h), on logits given by the host: one launcher pair per call over
+// logits [calls, rows, ld].  Even calls read the chosen logit from the row itself; odd calls take raw_copy in the slab pass and
+// read it from the copy, which must come back as the row's bits.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_token_logprobs(int32_t device, const float* logits, int32_t calls, int32_t rows, int64_t ld,
+                                                           int32_t vocab, const int32_t* tokens, int32_t top_k, float* logprob_out,
+                                                           uint32_t* topk_ids_out, float* topk_logprob_out, float* lse_out, int32_t* slabs_out)
+{
+    if (!logits || !tokens || !logprob_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (calls < 0 || calls > 4096 || vocab < 1 || ld < vocab || ld > (1 << 24))
+            throw InvalidConfig("invalid token_logprobs dimensions (calls 0 .. 4096, vocab >= 1, ld >= vocab)");
+        if (rows < 1 || rows > kLogprobMaxRows) throw InvalidConfig("rows must be 1.." + std::to_string(kLogprobMaxRows));
+        if (top_k < 0 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > vocab)
+            throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                                "] and not above vocab (" + std::to_string(vocab) + ")");
+        const size_t n = (size_t)calls * (size_t)rows;
+        for (size_t i = 0; i < n; ++i)
+            if (tokens[i] < -1 || tokens[i] >= vocab) throw InvalidConfig("tokens[" + std::to_string(i) + "] is neither -1 nor below vocab");
+        use_device(device);
+        if (slabs_out) *slabs_out = token_logprob_slabs(rows, vocab);
+        if (calls == 0) return;
+        const size_t call_floats = (size_t)rows * (size_t)ld, ob = n * 4, kb = std::max<size_t>(ob * (size_t)top_k, 4);
+        const auto ld_buf = upload(logits, (size_t)calls * call_floats * 4, "H2D logits");
+        const auto tk_buf = upload(tokens, ob, "H2D tokens");
+        GuardedBuf lp(ob), ti(kb), tl(kb), ls(ob), scratch(token_logprob_scratch_bytes(rows, vocab)), copy((size_t)rows * (size_t)vocab * 4);
+        // what a skipped row must come back as: the caller's own values
+        hip_check(hipMemcpy(lp.buf.p, logprob_out, ob, hipMemcpyHostToDevice), "H2D logprob");
+        if (topk_ids_out && top_k) hip_check(hipMemcpy(ti.buf.p, topk_ids_out, ob * top_k, hipMemcpyHostToDevice), "H2D top-k ids");
+        if (topk_logprob_out && top_k) hip_check(hipMemcpy(tl.buf.p, topk_logprob_out, ob * top_k, hipMemcpyHostToDevice), "H2D top-k logprob");
+        if (lse_out) hip_check(hipMemcpy(ls.buf.p, lse_out, ob, hipMemcpyHostToDevice), "H2D lse");
+        std::vector<float> back((size_t)rows * (size_t)vocab);
+        for (int32_t c = 0; c < calls; ++c) {
+            const float* lg = static_cast<const float*>(ld_buf->p) + (size_t)c * call_floats;
+            const bool copied = (c & 1) != 0;
+            TokenLogprobArgs a;
+            a.logits = lg; a.ld = ld; a.rows = rows; a.vocab = vocab; a.top_k = top_k; a.scratch = scratch.buf.p;
+            if (copied) { a.raw_copy = copy.as<float>(); a.ld_copy = vocab; }
+            TokenLogprobRecord r;
+            r.raw = copied ? copy.as<float>() : lg; r.ld_raw = copied ? (int64_t)vocab : ld;
+            r.tokens = static_cast<const int32_t*>(tk_buf->p) + (size_t)c * rows;
+            r.slots = top_k;
+            r.logprob = lp.as<float>() + (size_t)c * rows; r.lse = ls.as<float>() + (size_t)c * rows;
+            r.topk_ids = ti.as<uint32_t>() + (size_t)c * rows * top_k; r.topk_logprob = tl.as<float>() + (size_t)c * rows * top_k;
+            launcher_check(launch_token_logprob_partial(a, nullptr), "token logprob partial");
+            launcher_check(launch_token_logprob_finish(a, r, nullptr), "token logprob finish");
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            if (copied) {
+                hip_check(hipMemcpy(back.data(), copy.buf.p, back.size() * 4, hipMemcpyDeviceToHost), "D2H raw copy");
+                for (int32_t q = 0; q < rows; ++q)
+                    expect(std::memcmp(back.data() + (size_t)q * vocab, logits + (size_t)c * call_floats + (size_t)q * ld, (size_t)vocab * 4) == 0,
+                           "token logprobs: the raw copy is not the row");
+            }
+        }
+        lp.check("logprob"); ti.check("top-k ids"); tl.check("top-k logprob"); ls.check("lse"); scratch.check("slab scratch"); copy.check("raw copy");
+        hip_check(hipMemcpy(logprob_out, lp.buf.p, ob, hipMemcpyDeviceToHost), "D2H logprob");
+        if (topk_ids_out && top_k) hip_check(hipMemcpy(topk_ids_out, ti.buf.p, ob * top_k, hipMemcpyDeviceToHost), "D2H top-k ids");
+        if (topk_logprob_out && top_k) hip_check(hipMemcpy(topk_logprob_out, tl.buf.p, ob * top_k, hipMemcpyDeviceToHost), "D2H top-k logprob");
+        if (lse_out) hip_check(hipMemcpy(lse_out, ls.buf.p, ob, hipMemcpyDeviceToHost), "D2H lse");
+    });
+}
+
+// Timing of the pair against the kernel it replaces on the step (tools/bench_more.py llm_logprobs): `iters` launch pairs over
+// logits [rows, vocab], and `iters` passes of launch_score_rows_topk over the same rows, 8 at a time, with the rows' own arg-max
+// ids as targets.  top_k 1..8.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_token_logprobs_bench(int32_t device, const float* logits, int32_t rows, int32_t vocab, int32_t top_k,
+                                                                 int32_t iters, float* pair_ms_out, float* score_rows_ms_out)
+{
+    if (!logits || !pair_ms_out || !score_rows_ms_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > kLogprobMaxRows || vocab < 1 || vocab > (1 << 24) || iters < 1 || iters > 100000)
+            throw InvalidConfig("rows 1..64, vocab 1..2^24, iters 1..100000");
+        if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > vocab) throw InvalidConfig("top_k must be 1..8 and not above vocab");
+        use_device(device);
+        const size_t n = (size_t)rows, kb = n * (size_t)top_k * 4;
+        const auto lg = upload(logits, n * (size_t)vocab * 4, "H2D logits");
+        GuardedBuf lp(n * 4), ti(kb), tl(kb), scratch(token_logprob_scratch_bytes(rows, vocab)), tg(n * 4);
+        hip_check(hipMemset(tg.buf.p, 0, n * 4), "memset targets");
+        TokenLogprobArgs a;
+        a.logits = static_cast<const float*>(lg->p); a.ld = vocab; a.rows = rows; a.vocab = vocab; a.top_k = top_k; a.scratch = scratch.buf.p;
+        TokenLogprobRecord r;
+        r.raw = a.logits; r.ld_raw = vocab; r.slots = top_k;
+        r.logprob = lp.as<float>(); r.topk_ids = ti.as<uint32_t>(); r.topk_logprob = tl.as<float>();
+        time_launches(iters, pair_ms_out, [&] {
+            launcher_check(launch_token_logprob_partial(a, nullptr), "token logprob partial");
+            launcher_check(launch_token_logprob_finish(a, r, nullptr), "token logprob finish");
+        });
+        time_launches(iters, score_rows_ms_out, [&] {
+            for (int q = 0; q < rows; q += 8) {
+                const int m = std::min(8, rows - q);
+                launcher_check(launch_score_rows_topk(a.logits + (size_t)q * vocab, vocab, m, vocab, tg.as<uint32_t>() + q, top_k, lp.as<float>() + q,
+                                                      ti.as<uint32_t>() + (size_t)q * top_k, tl.as<float>() + (size_t)q * top_k, nullptr, nullptr),
+                               "score rows top-k");
+            }
+        });
+        lp.check("logprob"); ti.check("top-k ids"); tl.check("top-k logprob"); scratch.check("slab scratch");
     });
 }
 

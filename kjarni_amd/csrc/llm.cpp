@@ -20,6 +20,7 @@
 #include "moe_kernels.h"
 #include "constraint_kernels.h"
 #include "grammar_kernels.h"
+#include "logprob_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
 #include "safetensors.h"
@@ -245,8 +246,13 @@ LlmModel::~LlmModel()
     if (graph_) (void)hipGraphExecDestroy(graph_);
     if (cgraph_) (void)hipGraphExecDestroy(cgraph_);
     if (ggraph_) (void)hipGraphExecDestroy(ggraph_);
+    for (auto& kind : lp_graphs_)
+        for (hipGraphExec_t& g : kind)
+            if (g) (void)hipGraphExecDestroy(g);
     drop_graphs(lane_graphs_);
     drop_graphs(wide_graphs_);
+    drop_lane_logprob_graphs(false);
+    drop_lane_logprob_graphs(true);
     drop_graphs(lookup_graphs_);
     drop_graphs(lookup_sampled_graphs_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -1444,7 +1450,169 @@ hipGraphExec_t LlmModel::grammar_step_graph()
     });
 }
 
+void LlmModel::ensure_logprobs()
+{
+    if (lp_scratch_) return;
+    lp_copy_ = dalloc((size_t)cfg_.vocab);
+    lp_log_ = dalloc((size_t)hist_cap_);
+    lp_tlp_log_ = dalloc((size_t)hist_cap_ * KJARNI_SCORE_TOPK_MAX);
+    lp_ids_log_ = reinterpret_cast<uint32_t*>(dalloc((size_t)hist_cap_ * KJARNI_SCORE_TOPK_MAX));
+    lp_tok_ = reinterpret_cast<int32_t*>(dalloc(4));
+    lp_scratch_ = dalloc((token_logprob_scratch_bytes(1, cfg_.vocab) + 3) / 4);
+}
+
+void LlmModel::logprob_partial_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, float* copy)
+{
+    TokenLogprobArgs a;
+    a.logits = logits; a.ld = cfg_.vocab; a.rows = rows; a.vocab = cfg_.vocab; a.top_k = k; a.live = live; a.scratch = scratch;
+    if (copy) { a.raw_copy = copy; a.ld_copy = cfg_.vocab; }
+    hip_check(launch_token_logprob_partial(a, stream_), "token logprob partial");
+}
+
+void LlmModel::logprob_finish_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, const float* raw, const int32_t* token,
+                                 const int* count, int bias, int stride, float* lp, uint32_t* ids, float* tlp)
+{
+    TokenLogprobArgs a;
+    a.logits = logits; a.ld = cfg_.vocab; a.rows = rows; a.vocab = cfg_.vocab; a.top_k = k; a.live = live; a.scratch = scratch;
+    TokenLogprobRecord r;
+    r.raw = raw; r.ld_raw = cfg_.vocab;
+    r.tokens = token;
+    r.count = count; r.index_bias = bias;
+    r.rec_stride = stride; r.rec_cap = stride; r.slots = KJARNI_SCORE_TOPK_MAX;
+    r.logprob = lp; r.topk_ids = ids; r.topk_logprob = tlp;
+    hip_check(launch_token_logprob_finish(a, r, stream_), "token logprob finish");
+}
+
+void LlmModel::enqueue_logprob_partial(int k, bool copy) { logprob_partial_on(logits_, 1, nullptr, k, lp_scratch_, copy ? lp_copy_ : nullptr); }
+
+void LlmModel::enqueue_logprob_finish(int k, bool from_copy, const int32_t* token, const int* count, int bias)
+{
+    logprob_finish_on(logits_, 1, nullptr, k, lp_scratch_, from_copy ? lp_copy_ : logits_, token, count, bias, hist_cap_, lp_log_, lp_ids_log_,
+                      lp_tlp_log_);
+}
+
+// ---- lanes ----
+void LlmModel::drop_lane_logprob_graphs(bool wide)
+{
+    for (int v = 0; v < 2; ++v) {
+        if (wide) drop_graphs(wide_lp_graphs_[v]);
+        else drop_graphs(lane_lp_graphs_[v]);
+    }
+}
+
+void LlmModel::ensure_lane_logprobs(bool wide)
+{
+    LaneLogs& L = lane_logs_[wide ? 1 : 0];
+    const int rows = wide ? kWideLanes : kLanes, stride = wide ? wide_hist_stride_ : lane_hist_stride_;
+    if (L.block && L.stride == stride) return;
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    drop_lane_logprob_graphs(wide);
+    constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
+    auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
+    const size_t one = pad((size_t)rows * stride), many = pad((size_t)rows * stride * S), row = pad((size_t)cfg_.vocab);
+    const size_t scratch = pad((token_logprob_scratch_bytes(rows, cfg_.vocab) + 3) / 4);
+    void* fresh = arena_.alloc_own((one + 2 * many + row + scratch) * sizeof(float));
+    if (L.block) arena_.free_own(L.block);
+    L.block = fresh;
+    float* at = static_cast<float*>(fresh);
+    L.lp = at;
+    L.tlp = at + one;
+    L.ids = reinterpret_cast<uint32_t*>(at + one + many);
+    L.copy = at + one + 2 * many;
+    L.scratch = at + one + 2 * many + row;
+    L.stride = stride;
+}
+
+void LlmModel::lane_logprobs_enqueue(bool wide, int first, int rows, int k)
+{
+    const LaneLogs& L = lane_logs_[wide ? 1 : 0];
+    constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
+    const float* logits = (wide ? wide_logits_ : lane_logits_) + (size_t)first * cfg_.vocab;
+    const int32_t* live = (wide ? wide_state_->live : lane_state_->live) + first;  // (addresses in device memory: nothing is read here)
+    const int* count = (wide ? wide_state_->count : lane_state_->count) + first;
+    logprob_partial_on(logits, rows, live, k, L.scratch, nullptr);
+    logprob_finish_on(logits, rows, live, k, L.scratch, logits, nullptr, count, 0, L.stride, L.lp + (size_t)first * L.stride,
+                      L.ids + (size_t)first * L.stride * S, L.tlp + (size_t)first * L.stride * S);
+}
+
+hipGraphExec_t LlmModel::lane_logprob_step_graph(bool wide, int n, int k)
+{
+    hipGraphExec_t& g = wide ? wide_lp_graphs_[k > 1 ? 1 : 0][n] : lane_lp_graphs_[k > 1 ? 1 : 0][n];
+    if (g) return g;
+    return g = capture_graph(stream_, [&] {
+        if (wide) wide_step_enqueue(n);
+        else lane_step(n);
+        lane_logprobs_enqueue(wide, 0, n, k);  // ahead of the pick: it reads the lanes' flags and counts as the step found them
+        if (wide) wide_pick_enqueue(n, 0, 1);
+        else
+            hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_,
+                                       1, stream_), "lane pick");
+    });
+}
+
+hipGraphExec_t LlmModel::logprob_step_graph(int kind, int k)
+{
+    hipGraphExec_t& g = lp_graphs_[kind][k > 1 ? 1 : 0];
+    if (g) return g;
+    return g = capture_graph(stream_, [&] {
+        pass(reinterpret_cast<const uint32_t*>(token_), 1, true);
+        enqueue_logprob_partial(k, kind != 0);
+        if (kind == 1) hip_check(launch_constraint_apply(logits_, cfg_.vocab, 1, cfg_.vocab, cview_, crow_, stream_), "constraint apply");
+        if (kind == 2) hip_check(launch_grammar_apply(logits_, cfg_.vocab, 1, cfg_.vocab, gview_, grow_, stream_), "grammar apply");
+        enqueue_argmax(true);
+        enqueue_logprob_finish(k, kind != 0, token_, count_, -1);  // (the pick is recorded at *count - 1)
+        if (kind == 1) hip_check(launch_constraint_advance(token_, 1, cview_, crow_, cstate_log_, count_, hist_cap_, stream_), "constraint advance");
+        if (kind == 2)
+            hip_check(launch_grammar_advance(token_, 1, gview_, grow_, gstate_log_, gdepth_log_, count_, hist_cap_, stream_), "grammar advance");
+    });
+}
+
+void LlmModel::fetch_logprobs(size_t first, size_t n, float* lp, uint32_t* ids, float* tlp)
+{
+    constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
+    hip_check(hipMemcpyAsync(lp + first, lp_log_ + first, n * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logprobs");
+    hip_check(hipMemcpyAsync(ids + first * S, lp_ids_log_ + first * S, n * S * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H top-k ids");
+    hip_check(hipMemcpyAsync(tlp + first * S, lp_tlp_log_ + first * S, n * S * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H top-k logprobs");
+}
+
 namespace {
+
+// The record of one raw logits row on the host, in float32 (the loop with device sampling off): lse = max + log(sum exp(x - max)),
+// the sum taken over blocks of 1 024 elements and then over the blocks; ids / lps [k] in the kernels' order (descending value,
+// among equal values the larger id first, +0.0 == -0.0, NaN lowest).  A NaN at index 0 has key 0, the empty-slot marker: harmless,
+// here as in the kernels, since an empty slot decodes to id 0 -- the same id.
+float host_token_record(const float* x, size_t vocab, int k, uint32_t* ids, float* lps)
+{
+    const auto key = [](float v, size_t i) {
+        uint32_t u;
+        std::memcpy(&u, &v, 4);
+        if (v == 0.0f) u = 0;
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        if (v != v) u = 0;
+        return ((uint64_t)u << 32) | (uint32_t)i;
+    };
+    uint64_t lst[KJARNI_SCORE_TOPK_MAX + 1] = {};
+    float mx = -INFINITY;
+    for (size_t i = 0; i < vocab; ++i) {
+        mx = std::fmax(mx, x[i]);
+        const uint64_t kk = key(x[i], i);
+        int j = k;
+        for (; j > 0 && kk > lst[j - 1]; --j) lst[j] = lst[j - 1];
+        lst[j] = kk;
+    }
+    float sum = 0.0f;
+    for (size_t b = 0; b < vocab; b += 1024) {
+        float part = 0.0f;
+        for (size_t i = b; i < std::min(vocab, b + 1024); ++i) part += std::exp(x[i] - mx);
+        sum += part;
+    }
+    const float lse = mx + std::log(sum);
+    for (int j = 0; j < k; ++j) {
+        ids[j] = (uint32_t)(lst[j] & 0xFFFFFFFFull);
+        lps[j] = x[ids[j]] - lse;
+    }
+    return lse;
+}
 
 // What generate() needs of the host's copy of the automaton, regular (a DeviceConstraint: one state) or with a stack (a
 // DeviceGrammar: a configuration).  The loop below is written once against it.
@@ -1522,6 +1690,9 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     if (prompt.empty()) throw std::runtime_error("cannot generate from empty prompt");
     if ((int)prompt.size() > cache_cap_) throw std::runtime_error("prompt does not fit the context");
     if (opt.sample && !opt.uniform) throw std::runtime_error("sampling needs a uniform source");
+    if (opt.logprobs < -1 || opt.logprobs > KJARNI_SCORE_TOPK_MAX || opt.logprobs > cfg_.vocab)
+        throw InvalidConfig("top_k (" + std::to_string(opt.logprobs) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                            "] and not above the vocabulary (" + std::to_string(cfg_.vocab) + ")");
     const DeviceConstraint* con = opt.constraint;
     if (con) {  // everything that can be refused is refused before any GPU work
         if (con->device() != device_)
@@ -1544,6 +1715,21 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     begin_sequence(prompt);
     std::vector<uint32_t> out;
     GenerationRun run(prompt, opt, (size_t)cache_cap_, cfg_.eos_ids, out);
+    // Log-probabilities: off unless asked for and given a sink.  lpk: the width the device computes (llm.h).
+    TokenLogprobs* const sink = opt.logprobs >= 0 ? opt.logprob_sink : nullptr;
+    const bool lp = sink != nullptr;
+    const int lpk = opt.logprobs <= 1 ? 1 : std::min(KJARNI_SCORE_TOPK_MAX, cfg_.vocab);
+    constexpr size_t kSlots = KJARNI_SCORE_TOPK_MAX;
+    std::vector<float> lp_host, lp_tlp_host;
+    std::vector<uint32_t> lp_ids_host;
+    if (lp) {
+        sink->clear(opt.logprobs);
+        ensure_logprobs();
+        lp_host.resize((size_t)hist_cap_);
+        lp_ids_host.resize((size_t)hist_cap_ * kSlots);
+        lp_tlp_host.resize((size_t)hist_cap_ * kSlots);
+    }
+    const auto push_record = [&](size_t i) { sink->push(lp_host[i], lp_ids_host.data() + i * kSlots, lp_tlp_host.data() + i * kSlots); };
     // The constrained run: the host walks its own copy of the automaton over the tokens it takes (`hq`), the device holds the
     // state the kernels read (crow_).  take() is run.accept() under the constraint: a stop id ends the run (complete when the
     // state is accepting), any other token moves hq, and a closed state ends the run behind the token.
@@ -1670,7 +1856,9 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             hip_check(hipStreamSynchronize(stream_), "sync");  // (`all` grows below: the copy must have read it)
         }
         int skip_candidates = 0;
+        const bool edits = cur || processors;  // logits_ is edited in place before the token is known: the record reads the copy
         while (run.wants_token()) {
+            if (lp) enqueue_logprob_partial(lpk, edits);
             launch_apply();
             if (processors)
                 hip_check(launch_logits_processors(logits_, (int)vocab, samp_tokens_, (int)run.all.size(), samp_counts_, samp_distinct_,
@@ -1708,6 +1896,11 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             // LastToken::Fed: one step per emitted token, the last of max_new_tokens included -- under an explicit max_len past
             // prompt + max_new_tokens; with the default max_len that token fills context_limit and is not fed
             if (!take(next)) break;
+            if (lp) {  // the record of the emitted token, fed or not, at its index in the output
+                const int32_t tok = (int32_t)next;
+                hip_check(hipMemcpyAsync(lp_tok_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
+                enqueue_logprob_finish(lpk, edits, lp_tok_, nullptr, (int)out.size() - 1);
+            }
             if (cur) {  // the device's automaton takes the host's choice (fed or not, so that it ends where the host's does)
                 const int32_t tok = (int32_t)next;
                 hip_check(hipMemcpyAsync(token_, &tok, sizeof(tok), hipMemcpyHostToDevice, stream_), "H2D token");
@@ -1717,6 +1910,11 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             feed(next);
         }
         read_device_row(true);
+        if (lp && !out.empty()) {
+            fetch_logprobs(0, out.size(), lp_host.data(), lp_ids_host.data(), lp_tlp_host.data());
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            for (size_t i = 0; i < out.size(); ++i) push_record(i);
+        }
         finish();
         leave_resident(run.all);
         return out;
@@ -1728,11 +1926,17 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
         // The logits land in a pinned host buffer (one async copy per token at full PCIe rate).
         ensure_host_logits();
         float* lg = host_logits_;
-        std::vector<float> probs;
+        std::vector<float> probs, lp_raw;
         std::vector<uint32_t> ids;
         while (run.wants_token()) {
             hip_check(hipMemcpyAsync(lg, logits_, vocab * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logits");
             hip_check(hipStreamSynchronize(stream_), "sync");
+            float rec_lse = 0.0f, rec_lps[kSlots] = {};
+            uint32_t rec_ids[kSlots] = {};
+            if (lp) {  // the record from the raw row, before anything below edits it
+                rec_lse = host_token_record(lg, vocab, opt.logprobs, rec_ids, rec_lps);
+                lp_raw.assign(lg, lg + vocab);  // (the mask and the processors edit lg in place; the chosen token's raw logit is read below)
+            }
             if (cur) {  // the same mask from the host's automaton and token table
                 const bool accepting = cur.accepting();
                 for (size_t v = 0; v < vocab; ++v)
@@ -1748,7 +1952,9 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
                 next = argmax_last(lg, vocab);
             }
             // LastToken::Fed, as the loop above
-            if (!take(next) || outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;
+            const bool taken = take(next);
+            if (taken && lp) sink->push(lp_raw[next] - rec_lse, rec_ids, rec_lps);
+            if (!taken || outcome.complete || !run.feeds_accepted(LastToken::Fed)) break;
             feed(next);
         }
         outcome.device_state = cur.state();  // (no device automaton on this path)
@@ -1763,8 +1969,10 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     // a burst is sized by what is left of max_new_tokens, so the last token of max_new_tokens is not fed (LastToken::NotFed).
     // Constrained: the chain is pass -> apply -> argmax -> advance; the host steps its own automaton per drained token and ends the
     // run at a stop id, a closed state or the limits, discarding what the device ran past that point as it does past a stop id.
+    if (lp) enqueue_logprob_partial(lpk, (bool)cur);
     launch_apply();
     enqueue_argmax(true);
+    if (lp) enqueue_logprob_finish(lpk, (bool)cur, token_, count_, -1);
     launch_advance(true);
     hip_check(hipMemcpyAsync(pos_, &cache_len_, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
     std::vector<int32_t> hist((size_t)hist_cap_);
@@ -1772,11 +1980,14 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
     std::vector<int32_t> depths(gram ? (size_t)hist_cap_ : 0);
     size_t produced = 0, seen = 0;
     auto drain = [&](size_t upto) {
-        for (; seen < upto && !run.done; ++seen)
-            if (take((uint32_t)hist[seen]) && cur) {
+        for (; seen < upto && !run.done; ++seen) {
+            if (!take((uint32_t)hist[seen])) continue;
+            if (lp) push_record(seen);
+            if (cur) {
                 outcome.device_state = states[seen];
                 if (gram) outcome.device_depth = depths[seen];
             }
+        }
     };
     const auto fetch = [&](size_t first, size_t n) {  // the picks [first, first + n) and, constrained, the states behind them
         hip_check(hipMemcpyAsync(hist.data() + first, hist_ + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
@@ -1786,12 +1997,14 @@ std::vector<uint32_t> LlmModel::generate(const std::vector<uint32_t>& prompt, co
             hip_check(hipMemcpyAsync(states.data() + first, gstate_log_ + first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_), "D2H states");
             hip_check(hipMemcpyAsync(depths.data() + first, gdepth_log_ + first, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H depths");
         }
+        if (lp) fetch_logprobs(first, n, lp_host.data(), lp_ids_host.data(), lp_tlp_host.data());
         hip_check(hipStreamSynchronize(stream_), "sync");
     };
     fetch(0, 1);
     produced = 1;
     drain(1);
-    if (!run.done) exec = con ? constrained_step_graph() : gram ? grammar_step_graph() : step_graph();
+    if (!run.done)
+        exec = lp ? logprob_step_graph(con ? 1 : gram ? 2 : 0, lpk) : con ? constrained_step_graph() : gram ? grammar_step_graph() : step_graph();
     const size_t burst = on_token ? 4 : 16;
     while (!run.done) {
         size_t steps = std::min(burst, run.max_new - out.size());
@@ -1870,6 +2083,7 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
     if (lanes > lane_alloc_ || cap > lane_alloc_cap_) {
         hip_check(hipStreamSynchronize(stream_), "sync");
         drop_graphs(lane_graphs_);
+        drop_lane_logprob_graphs(false);
         // everything sized by lanes x rows is one allocation of its own: the caches of every layer, then the pick history and the
         // processors' history / distinct lists; when the lanes or their rows grow it is replaced and the old one freed
         const int nl = std::max(lanes, lane_alloc_), nc = std::max(cap, lane_alloc_cap_);
@@ -1908,7 +2122,10 @@ void LlmModel::ensure_lanes(int lanes, int lane_context)
         if (!lane_copy_table_) lane_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((pairs.size() * sizeof(LlmKvCopyPair) + 3) / 4));
         hip_check(hipMemcpy(lane_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
     }
-    if (cap != lane_cap_) drop_graphs(lane_graphs_);  // (the capacity is an argument of the captured launches)
+    if (cap != lane_cap_) {  // (the capacity is an argument of the captured launches)
+        drop_graphs(lane_graphs_);
+        drop_lane_logprob_graphs(false);
+    }
     lanes_ = lanes;
     lane_cap_ = cap;
     std::memset(lane_host_.get(), 0, sizeof(LlmLaneState));
@@ -2136,8 +2353,8 @@ LlmModel::LaneSet LlmModel::lane_set()
         else lane_prefill(l, ids, n);
     };
     S.step = [this](int n) { lane_step(n); };
-    S.burst = [this](int n, size_t times) {
-        hipGraphExec_t exec = lane_step_graph(n);
+    S.burst = [this](int n, size_t times, hipGraphExec_t chain) {
+        hipGraphExec_t exec = chain ? chain : lane_step_graph(n);
         for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
     };
     return S;
@@ -2158,6 +2375,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
     }
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
+    // Log-probabilities: on when some request asks for them and gives a sink; lpk is the width the device computes for every lane
+    // (llm.h), each request keeping its own top_k of them.
+    bool lp = false;
+    int lpk = 1;
+    constexpr size_t kSlots = KJARNI_SCORE_TOPK_MAX;
     std::vector<std::vector<uint32_t>> out(reqs.size());
     std::vector<GenerationRun> waiting;  // generate()'s bookkeeping of every request, until a lane takes it
     waiting.reserve(reqs.size());
@@ -2170,11 +2392,25 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         waiting.emplace_back(r.prompt, r.options, (size_t)cap, cfg_.eos_ids, out[i]);
         if ((int)waiting.back().stops.size() > kMaxLaneStops) refuse("more than 16 stop ids (prompt " + std::to_string(i) + ")");
         slow = slow || r.options.sample || r.options.repetition_penalty != 1.0f || r.options.no_repeat_ngram > 0;
+        if (r.options.logprobs < -1 || r.options.logprobs > KJARNI_SCORE_TOPK_MAX || r.options.logprobs > cfg_.vocab)
+            throw InvalidConfig("top_k (" + std::to_string(r.options.logprobs) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
+                                "] and not above the vocabulary (" + std::to_string(cfg_.vocab) + ") (prompt " + std::to_string(i) + ")");
+        if (r.options.logprobs >= 0 && r.options.logprob_sink) {
+            lp = true;
+            if (r.options.logprobs > 1) lpk = std::min(KJARNI_SCORE_TOPK_MAX, cfg_.vocab);
+        }
     }
     if (reqs.empty()) return out;
     const int n = (int)std::min<size_t>((size_t)lanes, reqs.size());
     if (wide) ensure_wide(n, lane_context);
     else ensure_lanes(n, lane_context);
+    if (lp) {
+        ensure_logprobs();
+        ensure_lane_logprobs(wide);
+        for (const LaneRequest& r : reqs)
+            if (r.options.logprobs >= 0 && r.options.logprob_sink) r.options.logprob_sink->clear(r.options.logprobs);
+    }
+    const LaneLogs& LL = lane_logs_[wide ? 1 : 0];
     const LaneSet S = wide ? wide_set() : lane_set();
     const LaneSet& h = S;  // (the mirror's fields, as the loop has always named them)
     const size_t vocab = (size_t)cfg_.vocab;
@@ -2210,12 +2446,13 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         size_t seen = 0;
         GenerationRun g;
         std::function<bool(uint32_t)> on_token;  // the caller's, bound to the request
+        TokenLogprobs* sink = nullptr;           // where the request's records go (null: it asked for none)
     };
     std::vector<Run> run((size_t)n);
     size_t next_req = 0;
-    auto take = [&](int l, uint32_t tok) {  // generate()'s drain
+    auto take = [&](int l, uint32_t tok) {  // generate()'s drain; true: the token was emitted
         Run& r = run[l];
-        if (!r.g.done) r.g.accept(tok, r.on_token);
+        return !r.g.done && r.g.accept(tok, r.on_token);
     };
     // the next waiting request that has anything to generate goes into lane l (false: none is left); its prompt is prefilled
     auto start = [&](int l) {
@@ -2228,6 +2465,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             r.seen = 0;
             r.g = std::move(waiting[i]);
             r.on_token = nullptr;
+            r.sink = q.options.logprobs >= 0 ? q.options.logprob_sink : nullptr;
             if (on_token) r.on_token = [&on_token, i](uint32_t tok) { return on_token(i, tok); };
             if (shared >= 1) {
                 S.prefill(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
@@ -2263,24 +2501,52 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         // a lane's first token comes from its prefill's logits row: the lane pick on that row alone
         auto first_pick = [&](int l) {
             S.to_device();
+            if (lp) lane_logprobs_enqueue(wide, l, 1, lpk);  // (the lane's count is 0: record 0 of its new request)
             S.first_pick(l);
             S.from_device();
         };
         auto drain = [&](size_t steps) {  // step-major, lane order within a step
             std::vector<std::vector<int32_t>> fresh((size_t)n);
+            // the records behind the tokens: the lanes step together, so their new log entries lie in nearly the same columns
+            // [lo, hi) of the lanes' logs, and one strided copy per array fetches that window of every lane
+            std::vector<size_t> first_new((size_t)n, 0);
+            size_t lo = SIZE_MAX, hi = 0;
             for (int l = 0; l < n; ++l) {
                 Run& r = run[l];
                 const size_t have = (size_t)h.count[l];
                 if (r.req < 0 || have <= r.seen) continue;
-                fresh[(size_t)l].resize(have - r.seen);
-                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), S.hist + (size_t)l * S.hist_stride + r.seen,
-                                         (have - r.seen) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
+                const size_t m = have - r.seen, at = (size_t)l * S.hist_stride + r.seen;
+                fresh[(size_t)l].resize(m);
+                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), S.hist + at, m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
+                first_new[(size_t)l] = r.seen;
+                if (lp && r.sink) {
+                    lo = std::min(lo, r.seen);
+                    hi = std::max(hi, have);
+                }
                 r.seen = have;
+            }
+            const size_t win = hi > lo ? hi - lo : 0;
+            std::vector<float> flp((size_t)n * win), ftlp((size_t)n * win * kSlots);
+            std::vector<uint32_t> fids((size_t)n * win * kSlots);
+            if (win) {
+                const size_t pitch = (size_t)S.hist_stride;
+                hip_check(hipMemcpy2DAsync(flp.data(), win * sizeof(float), LL.lp + lo, pitch * sizeof(float), win * sizeof(float), (size_t)n,
+                                           hipMemcpyDeviceToHost, stream_), "D2H logprobs");
+                hip_check(hipMemcpy2DAsync(fids.data(), win * kSlots * sizeof(uint32_t), LL.ids + lo * kSlots, pitch * kSlots * sizeof(uint32_t),
+                                           win * kSlots * sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToHost, stream_), "D2H top-k ids");
+                hip_check(hipMemcpy2DAsync(ftlp.data(), win * kSlots * sizeof(float), LL.tlp + lo * kSlots, pitch * kSlots * sizeof(float),
+                                           win * kSlots * sizeof(float), (size_t)n, hipMemcpyDeviceToHost, stream_), "D2H top-k logprobs");
             }
             hip_check(hipStreamSynchronize(stream_), "sync");
             for (size_t i = 0; i < steps; ++i)
-                for (int l = 0; l < n; ++l)
-                    if (i < fresh[(size_t)l].size()) take(l, (uint32_t)fresh[(size_t)l][i]);
+                for (int l = 0; l < n; ++l) {
+                    if (i >= fresh[(size_t)l].size()) continue;
+                    Run& r = run[l];
+                    if (take(l, (uint32_t)fresh[(size_t)l][i]) && lp && r.sink) {
+                        const size_t at = (size_t)l * win + (first_new[(size_t)l] + i - lo);  // the token's log entry in the window
+                        r.sink->push(flp[at], fids.data() + at * kSlots, ftlp.data() + at * kSlots);
+                    }
+                }
         };
         const size_t burst = on_token ? 4 : 16;
         for (;;) {
@@ -2305,7 +2571,8 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             }
             if (!any_running()) break;
             if (dirty) S.to_device();
-            S.burst(n, burst);
+            // (with records: the chain that has them in it, captured per (set, lanes, width), through the set's own burst)
+            S.burst(n, burst, lp ? lane_logprob_step_graph(wide, n, lpk) : nullptr);
             S.from_device();
             for (int l = 0; l < n; ++l)
                 if (run[l].req >= 0) S.len[l] = h.pos[l];
@@ -2348,6 +2615,8 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                 int32_t *tok, *distinct;
                 int *counts, *nd;
                 pstate(l, tok, distinct, counts, nd);
+                const bool rec = lp && r.sink, edits = o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0;
+                if (rec) logprob_partial_on(row, 1, nullptr, lpk, LL.scratch, edits ? LL.copy : nullptr);  // ahead of the processors
                 if (o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0)
                     hip_check(launch_logits_processors(row, (int)vocab, tok, (int)r.g.all.size(), counts, distinct, nd, o.repetition_penalty,
                                                        o.no_repeat_ngram, stream_), "logits processors");
@@ -2366,7 +2635,12 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                     next = (uint32_t)t;
                     ++tokens_from_candidates_;
                 }
-                take(l, next);
+                if (take(l, next) && rec) {  // the record at the token's index in the request's output, in the lane's own log
+                    hip_check(hipMemsetD32Async((hipDeviceptr_t)lp_tok_, (int)next, 1, stream_), "token");
+                    logprob_finish_on(row, 1, nullptr, lpk, LL.scratch, edits ? LL.copy : row, lp_tok_, nullptr, (int)r.g.out->size() - 1, LL.stride,
+                                      LL.lp + (size_t)l * LL.stride, LL.ids + (size_t)l * LL.stride * kSlots,
+                                      LL.tlp + (size_t)l * LL.stride * kSlots);
+                }
                 // LastToken::NotFed: a request that has its max_new_tokens leaves the lane at once (asked whatever take() did:
                 // a refused token leaves the run done, which answers no)
                 if (!r.g.feeds_accepted(LastToken::NotFed)) r.g.done = true;
@@ -2381,6 +2655,18 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                     break;
                 }
                 h.live[l] = 0;
+                if (rec && !r.g.out->empty()) {  // the request has ended: its records, before the lane's log starts over
+                    const size_t m = r.g.out->size(), at = (size_t)l * LL.stride;
+                    std::vector<float> flp(m), ftlp(m * kSlots);
+                    std::vector<uint32_t> fids(m * kSlots);
+                    hip_check(hipMemcpyAsync(flp.data(), LL.lp + at, m * sizeof(float), hipMemcpyDeviceToHost, stream_), "D2H logprobs");
+                    hip_check(hipMemcpyAsync(fids.data(), LL.ids + at * kSlots, m * kSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_),
+                              "D2H top-k ids");
+                    hip_check(hipMemcpyAsync(ftlp.data(), LL.tlp + at * kSlots, m * kSlots * sizeof(float), hipMemcpyDeviceToHost, stream_),
+                              "D2H top-k logprobs");
+                    hip_check(hipStreamSynchronize(stream_), "sync");
+                    for (size_t i = 0; i < m; ++i) r.sink->push(flp[i], fids.data() + i * kSlots, ftlp.data() + i * kSlots);
+                }
                 if (start(l)) begin_history(l);
             }
         }
@@ -2425,6 +2711,7 @@ void LlmModel::ensure_wide(int lanes, int lane_context)
     if (lanes > wide_alloc_ || cap > wide_alloc_cap_) {
         hip_check(hipStreamSynchronize(stream_), "sync");
         drop_graphs(wide_graphs_);
+        drop_lane_logprob_graphs(true);
         // one allocation of its own, sized by the width and the rows asked for, replaced when either grows
         const size_t nl = (size_t)std::max(lanes, wide_alloc_), nc = (size_t)std::max(cap, wide_alloc_cap_), stride = nc + 16;
         auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
@@ -2461,7 +2748,10 @@ void LlmModel::ensure_wide(int lanes, int lane_context)
         for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, wide_k_[i], layers_[i].v_cache, wide_v_[i]};
         hip_check(hipMemcpy(wide_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
     }
-    if (cap != wide_cap_) drop_graphs(wide_graphs_);  // (the capacity is an argument of the captured launches)
+    if (cap != wide_cap_) {  // (the capacity is an argument of the captured launches)
+        drop_graphs(wide_graphs_);
+        drop_lane_logprob_graphs(true);
+    }
     wide_lanes_ = lanes;
     wide_cap_ = cap;
     std::memset(wide_host_.get(), 0, sizeof(LlmWideState));
@@ -2626,8 +2916,8 @@ LlmModel::LaneSet LlmModel::wide_set()
         else wide_prefill(l, ids, n);
     };
     S.step = [this](int n) { wide_step_enqueue(n); };
-    S.burst = [this](int n, size_t times) {  // (no stage of the chain reads anything back, the MoE rows hook included: always captured)
-        hipGraphExec_t exec = wide_step_graph(n);
+    S.burst = [this](int n, size_t times, hipGraphExec_t chain) {  // (no stage of the chain reads anything back, the MoE rows hook included: always captured)
+        hipGraphExec_t exec = chain ? chain : wide_step_graph(n);
         for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
         for (const Layer& L : layers_)  // (a replay runs no host code: the routing record's row count is set here)
             if (L.moe) L.moe_rec_rows = n;
@@ -2792,7 +3082,8 @@ std::vector<uint32_t> LlmModel::generate_lookup(const std::vector<uint32_t>& pro
     check_lookup_config(lk);
     if (opt.constraint) throw InvalidConfig("generate_lookup does not take a constraint (generate does)");
     if (opt.grammar) throw InvalidConfig("generate_lookup does not take a grammar (generate does)");
-    if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0) return generate(prompt, opt, on_token);  // not applicable
+    if (opt.sample || opt.repetition_penalty != 1.0f || opt.no_repeat_ngram > 0 || opt.logprobs >= 0)
+        return generate(prompt, opt, on_token);  // not applicable (log-probabilities: the plain loop records them)
     DraftSource src;
     src.ngram_max = lk.ngram_max;
     src.ngram_min = lk.ngram_min;
@@ -3011,7 +3302,8 @@ std::vector<uint32_t> LlmModel::generate_lookup_sampled(const std::vector<uint32
     check_lookup_config(lk);
     if (opt.constraint) throw InvalidConfig("generate_lookup_sampled does not take a constraint (generate does)");
     if (opt.grammar) throw InvalidConfig("generate_lookup_sampled does not take a grammar (generate does)");
-    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
+    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f) || opt.logprobs >= 0)
+        return generate(prompt, opt, on_token);  // not built (log-probabilities: the plain loop records them)
     if (!opt.sample) return generate_lookup(prompt, opt, lk, on_token, stats);
     DraftSource src;
     src.ngram_max = lk.ngram_max;
@@ -3138,7 +3430,8 @@ std::vector<uint32_t> LlmModel::generate_draft(LlmModel* drafter, const std::vec
     if (prompt.size() > (size_t)cache_cap_)
         throw InvalidConfig("prompt (" + std::to_string(prompt.size()) + " tokens) does not fit the context of " + std::to_string(cache_cap_) +
                             " tokens");
-    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f)) return generate(prompt, opt, on_token);  // not built
+    if (opt.no_repeat_ngram > 0 || (!opt.sample && opt.repetition_penalty != 1.0f) || opt.logprobs >= 0)
+        return generate(prompt, opt, on_token);  // not built (log-probabilities: the plain loop records them)
     DraftSource src;
     src.drafter = drafter;
     if (opt.sample) return sampled_draft_loop(prompt, opt, src, draft_tokens, on_token, stats);

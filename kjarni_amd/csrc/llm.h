@@ -257,6 +257,14 @@ public:
     // options.grammar (grammar_kernels.h: a stack automaton in the DFA's place; both set is InvalidConfig): the same loop, with
     // "configuration" (state and stack) for "state", launch_grammar_apply / launch_grammar_advance for the two kernels, a third
     // captured chain for plain greedy, and DeviceGrammar::check_states for the refusal.
+    // options.logprobs >= 0 with a sink (generation_run.h; logprob_kernels.h): one record per emitted token -- its log-probability
+    // and the top_k most likely tokens under the log-softmax of the logits as the vocabulary head wrote them, before the mask, the
+    // processors, temperature and the cut -- in every loop above: plain, constrained and grammar greedy replay chains of their own
+    // with the slab pass and the record in them, the device-sampling loop runs the slab pass ahead of the mask and the processors
+    // and the record once the host has decided, the host-sampling loop computes the record in float32 from the raw row.  The
+    // prompt-lookup and draft-model loops are out of scope: generate_lookup, generate_lookup_sampled and generate_draft forward a
+    // request that asks for records here (stats zero, the drafter untouched).  InvalidConfig before any GPU work for logprobs
+    // outside -1 .. KJARNI_SCORE_TOPK_MAX or above the vocabulary.  generate_lanes / generate_wide take it per request.
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
                                    const std::function<bool(uint32_t)>& on_token);
 
@@ -407,7 +415,9 @@ private:
         std::function<void(int lane)> first_pick;  // the pick on the lane's prefill row alone (no advance)
         std::function<void(int lane, int shared, const uint32_t* ids, int n)> prefill;  // behind `shared` copied prefix rows
         std::function<void(int n)> step;                                                // one step, enqueued directly
-        std::function<void(int n, size_t times)> burst;  // `times` x (step + pick), replayed from a captured graph where one exists
+        // `times` x (step + pick), replayed from a captured graph where one exists; chain: another captured chain of the same step
+        // to replay in its place (the one with the log-probability records in it), with the burst's own host-side steps around it
+        std::function<void(int n, size_t times, hipGraphExec_t chain)> burst;
     };
     LaneSet lane_set();
     LaneSet wide_set();
@@ -522,6 +532,36 @@ private:
     hipGraphExec_t constrained_step_graph();  // pass -> apply -> argmax(record) -> advance, captured once (it reads cview_)
     void ensure_grammar();                    // the same for a grammar: descriptor, row state, state and depth logs
     hipGraphExec_t grammar_step_graph();      // pass -> grammar apply -> argmax(record) -> grammar advance (it reads gview_)
+    // Generation log-probabilities (GenerateOptions::logprobs; logprob_kernels.h).  k is the width the device computes: 1 for a
+    // request of 0 or 1 alternatives, else min(KJARNI_SCORE_TOPK_MAX, vocab) -- the host keeps the request's own top_k of them.
+    void ensure_logprobs();                           // slab scratch, the raw copy of a row, the record logs beside hist_
+    // The two launches over `rows` rows of `logits` [rows, vocab].  Finish: the chosen logit from `raw` (pitch vocab), the token at
+    // token[row] (null: the row's arg-max), the record at index (count ? count[row] : 0) + bias of row `row`'s `stride` log entries.
+    void logprob_partial_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, float* copy);
+    void logprob_finish_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, const float* raw, const int32_t* token,
+                           const int* count, int bias, int stride, float* lp, uint32_t* ids, float* tlp);
+    // Lanes (generate_lanes / generate_wide with a request that sets logprobs): the record logs of a lane set, [lanes, hist stride]
+    // and [lanes, hist stride, KJARNI_SCORE_TOPK_MAX], a slab scratch for all its rows and one raw-copy row; the two launches over
+    // lanes [first, first + rows) ahead of the pick (frozen lanes write nothing; the record index is the lane's own device-held
+    // count, so a lane that takes the next request starts at record 0); the captured chain step -> records -> pick.
+    struct LaneLogs {
+        void* block = nullptr;
+        int stride = 0;
+        float *lp = nullptr, *tlp = nullptr, *copy = nullptr;
+        uint32_t* ids = nullptr;
+        void* scratch = nullptr;
+    };
+    void ensure_lane_logprobs(bool wide);
+    void drop_lane_logprob_graphs(bool wide);
+    void lane_logprobs_enqueue(bool wide, int first, int rows, int k);
+    hipGraphExec_t lane_logprob_step_graph(bool wide, int lanes, int k);
+    void enqueue_logprob_partial(int k, bool copy);   // the slab pass over logits_ (copy: the row also goes to lp_copy_)
+    // The record of the token at *token: read from lp_copy_ (from_copy) or logits_, written at index (count ? *count : 0) + bias.
+    void enqueue_logprob_finish(int k, bool from_copy, const int32_t* token, const int* count, int bias);
+    // The chains of plain greedy with records, captured once per (kind, k): kind 0 pass -> slab pass -> argmax(record) -> finish;
+    // 1 / 2 pass -> slab pass (+ copy) -> constraint / grammar apply -> argmax(record) -> finish -> advance.
+    hipGraphExec_t logprob_step_graph(int kind, int k);
+    void fetch_logprobs(size_t first, size_t n, float* lp, uint32_t* ids, float* tlp);  // async copies of log rows [first, first + n)
 
     struct Layer {
         void *wqkv, *wo, *gate, *up, *down;  // GPT-2: c_attn, attn.c_proj, mlp.c_fc (in `gate`), mlp.c_proj (in `down`), as [out, in]
@@ -652,6 +692,16 @@ private:
     uint32_t* gstate_log_ = nullptr;
     int32_t* gdepth_log_ = nullptr;
     hipGraphExec_t ggraph_ = nullptr;
+    // generation log-probabilities (allocated on first use): the slab scratch of one row, the raw copy of the row (taken before a
+    // mask or a processor edits logits_), the token a host-decided step records, the record logs [hist_cap_] and [hist_cap_,
+    // KJARNI_SCORE_TOPK_MAX] indexed as hist_, and the captured chains [plain | constrained | grammar][k == 1 | k > 1]
+    void* lp_scratch_ = nullptr;
+    float *lp_copy_ = nullptr, *lp_log_ = nullptr, *lp_tlp_log_ = nullptr;
+    uint32_t* lp_ids_log_ = nullptr;
+    int32_t* lp_tok_ = nullptr;
+    hipGraphExec_t lp_graphs_[3][2] = {};
+    LaneLogs lane_logs_[2];  // [lanes | wide]
+    hipGraphExec_t lane_lp_graphs_[2][kLanes + 1] = {}, wide_lp_graphs_[2][kWideLanes + 1] = {};  // [k == 1 | k > 1][lanes]
     // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
     // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
     std::vector<float*> lane_k_, lane_v_;

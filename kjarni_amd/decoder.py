@@ -126,6 +126,9 @@ def answer_plan(seqs: Sequence[Sequence[int]], head_dim: int = 64, min_shared: i
             "mfma": mfma[:nm].copy(), "prefix": pre[:np_].copy(), "gather": gather[:nga].copy()}
 
 
+LOGPROB_GUARD = 8  # entries the generate_*_logprobs wrappers allocate behind the capacity they pass on (a test hook)
+
+
 class HipDecoder:
     def __init__(self, model_dir: str, device: int = 0, weights: str = "auto", max_context: int = 0):
         self._h = C.c_void_p()
@@ -269,6 +272,53 @@ class HipDecoder:
         take 2 * layers * lanes * rows * kv * 4 bytes with rows = min(context, lane_context): set lane_context."""
         return self._generate_many(lib().kjarni_hip_decoder_generate_wide, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram, lanes,
                                    lane_context, on_token)
+
+    def generate_wide_logprobs(self, prompts: Sequence[Sequence[int]], max_new_tokens, top_k: int = 0, repetition_penalty: float = 1.0,
+                               no_repeat_ngram: int = 0, lanes: int = 0, lane_context: int = 0,
+                               on_token: Optional[Callable[[int, int], Optional[bool]]] = None, capacity: Optional[int] = None):
+        """generate_wide() with the log-probability of every emitted token and its top_k (0..8) alternatives: a list, one dict
+        per prompt, of ids, logprob [n], topk_ids / topk_logprob [n, top_k].  Every width 1..64 is served.  The distribution is
+        score()'s (the raw logits); a lane that takes the next waiting prompt starts at that prompt's record 0.
+        guard (a test hook): as generate_logprobs', per prompt; the last prompt's also holds the LOGPROB_GUARD entries behind the arrays."""
+        n = len(prompts)
+        if n == 0:
+            return []
+        new = [int(max_new_tokens)] * n if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
+        if len(new) != n:
+            raise ValueError("max_new_tokens: one value, or one per prompt")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint32).reshape(-1) for p in prompts]), np.uint32)
+        if flat.size == 0:
+            flat = np.zeros(1, np.uint32)
+        offsets = (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(p) for p in prompts])]).tolist())
+        news = (C.c_size_t * n)(*new)
+        cap = max(max(new), 1) if capacity is None else int(capacity)
+        k = max(int(top_k), 0)
+        # [n, cap] rows as the C entry lays them out, then LOGPROB_GUARD entries the call must not touch (a test hook)
+        room = n * cap + LOGPROB_GUARD
+        out_f, lp_f = np.full(room, 0xFFFFFFFF, np.uint32), np.full(room, np.nan, np.float32)
+        ids_f, tlp_f = np.full((room, k), 0xFFFFFFFF, np.uint32), np.full((room, k), np.nan, np.float32)
+        out, lp = out_f[:n * cap].reshape(n, cap), lp_f[:n * cap].reshape(n, cap)
+        ids, tlp = ids_f[:n * cap].reshape(n, cap, k), tlp_f[:n * cap].reshape(n, cap, k)
+        n_out = (C.c_size_t * n)()
+
+        def cb(i, t, _u):
+            r = on_token(int(i), int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniBatchTokenCallbackFn(cb) if on_token else _ffi.KjarniBatchTokenCallbackFn()
+        f32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_generate_wide_logprobs(self._h, u32(flat), offsets, n, news, repetition_penalty, no_repeat_ngram,
+                                                                    lanes, lane_context, fn, None, u32(out_f), cap, n_out, int(top_k), f32(lp_f),
+                                                                    u32(ids_f) if k else None, f32(tlp_f) if k else None))
+        res = []
+        for i in range(n):
+            m = min(int(n_out[i]), cap)
+            # guard: the entries of the prompt's own rows behind its records; the last prompt's also holds the entries behind the arrays
+            tail = slice(n * cap, None) if i == n - 1 else slice(0, 0)
+            guard = tuple(np.concatenate([a[i, m:], f[tail]]) for a, f in ((out, out_f), (lp, lp_f), (ids, ids_f), (tlp, tlp_f)))
+            res.append({"ids": out[i, :m].tolist(), "n": int(n_out[i]), "logprob": lp[i, :m].copy(), "topk_ids": ids[i, :m].copy(),
+                        "topk_logprob": tlp[i, :m].copy(), "guard": guard})
+        return res
 
     def wide_begin(self, lanes: int = 0, lane_context: int = 0):
         """Test hook: empty wide-lane caches for `lanes` (9..64, 0 = 64) lanes of `lane_context` rows each."""
@@ -503,6 +553,49 @@ class HipDecoder:
                                                               C.byref(n), C.byref(res)))
         del keep
         return out[:min(n.value, out.size)].tolist(), grammar_result_dict(res)
+
+    def generate_logprobs(self, prompt: Sequence[int], max_new_tokens: int, top_k: int = 0, constraint=None, grammar=None,
+                          sample: bool = False, temperature: float = 1.0, sampling_top_k: Optional[int] = None,
+                          top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty: float = 1.0,
+                          no_repeat_ngram: int = 0, stop_ids: Optional[Sequence[int]] = None, uniforms=None, seed: int = 0,
+                          on_token: Optional[Callable[[int], Optional[bool]]] = None, capacity: Optional[int] = None):
+        """The plain loop of generate_sampled() / generate_constrained() / generate_grammar() with the log-probability of every
+        emitted token and its top_k (0..8) most likely alternatives: a dict with ids, logprob [n], topk_ids / topk_logprob
+        [n, top_k] and result (the constraint's or grammar's, else None).  The distribution is score()'s: the log-softmax of the
+        logits as the vocabulary head wrote them, before the mask, the processors, temperature and the sampler's cut.
+        sampling_top_k is the sampler's cut (generate_sampled's top_k).  capacity: the size of the output arrays (default
+        max_new_tokens); the records cover the first min(n, capacity) tokens.  n: the tokens emitted; guard (a test hook): every
+        output array is allocated LOGPROB_GUARD entries longer than the capacity the C entry is told, filled with 0xFFFFFFFF /
+        NaN; guard holds the entries of each array behind min(n, capacity), which the call must leave as they were."""
+        from .constraints import grammar_result_dict, result_dict
+        p = np.ascontiguousarray(prompt, np.uint32)
+        cap = max(max_new_tokens, 1) if capacity is None else int(capacity)
+        k = max(int(top_k), 0)
+        room = max(cap, 0) + LOGPROB_GUARD
+        out = np.full(room, 0xFFFFFFFF, np.uint32)
+        lp = np.full(room, np.nan, np.float32)
+        ids = np.full((room, k), 0xFFFFFFFF, np.uint32)
+        tlp = np.full((room, k), np.nan, np.float32)
+        n = C.c_size_t(0)
+        o, keep = self._sampling_options(max_new_tokens, sample, temperature, sampling_top_k, top_p, min_p, repetition_penalty,
+                                         no_repeat_ngram, stop_ids, uniforms, seed)
+        cres, gres = _ffi.KjarniHipConstraintResult(), _ffi.KjarniHipGrammarResult()
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        f32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+
+        def cb(t, _u):
+            r = on_token(int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniTokenCallbackFn(cb) if on_token else _ffi.KjarniTokenCallbackFn()
+        check_error(lib().kjarni_hip_decoder_generate_logprobs(
+            self._h, constraint._h if constraint is not None else None, grammar._h if grammar is not None else None,
+            u32(p) if p.size else None, p.size, C.byref(o), int(top_k), fn, None, u32(out), cap, C.byref(n), f32(lp),
+            u32(ids) if ids.size else None, f32(tlp) if tlp.size else None, C.byref(cres), C.byref(gres)))
+        del keep
+        m = min(n.value, cap)
+        result = result_dict(cres) if constraint is not None else grammar_result_dict(gres) if grammar is not None else None
+        return {"ids": out[:m].tolist(), "n": int(n.value), "logprob": lp[:m].copy(), "topk_ids": ids[:m].copy(),
+                "topk_logprob": tlp[:m].copy(), "result": result, "guard": (out[m:], lp[m:], ids[m:], tlp[m:])}
 
     def verify_step_sampled(self, token: int, draft: Sequence[int], uniforms, rows: Optional[int] = None, temperature: float = 1.0,
                             top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,

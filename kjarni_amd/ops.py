@@ -972,6 +972,43 @@ def argmax(logits, vocab: Optional[int] = None, route: int = ARGMAX_DECODER, liv
     return (picks, acc) if route == ARGMAX_LOOKUP else picks
 
 
+def token_logprob_slabs(rows: int, vocab: int) -> int:
+    """The slabs the generation log-probability kernels cut a row of `vocab` logits into when `rows` rows run together (no GPU)."""
+    return int(lib().kjarni_hip_token_logprob_slabs(int(rows), int(vocab)))
+
+
+def token_logprobs(logits, tokens, top_k: int, vocab: Optional[int] = None, device: int = 0, out=None):
+    """The generation log-probability kernels on logits [calls, rows, ld] (columns >= vocab are padding) and the chosen tokens
+    [calls, rows] (-1: the row is skipped and its outputs come back as `out` gave them).  Returns a dict: logprob, lse
+    [calls, rows], topk_ids, topk_logprob [calls, rows, top_k], slabs.  out: (logprob, topk_ids, topk_logprob, lse) initial values
+    (default NaN / 0xFFFFFFFF)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    calls, rows, ld = lg.shape
+    vocab = ld if vocab is None else int(vocab)
+    tk = np.ascontiguousarray(tokens, np.int32).reshape(calls, rows)
+    k = max(int(top_k), 0)
+    if out is None:
+        lp, lse = np.full((calls, rows), np.nan, np.float32), np.full((calls, rows), np.nan, np.float32)
+        ids, tlp = np.full((calls, rows, k), 0xFFFFFFFF, np.uint32), np.full((calls, rows, k), np.nan, np.float32)
+    else:
+        lp, ids, tlp, lse = (np.ascontiguousarray(a).copy() for a in out)
+    slabs = C.c_int32(0)
+    check_error(lib().kjarni_hip_op_token_logprobs(device, _f(lg), calls, rows, ld, vocab, tk.ctypes.data_as(_i32p), int(top_k), _f(lp),
+                                                   ids.ctypes.data_as(_ffi._u32p) if ids.size else None, _f(tlp) if tlp.size else None,
+                                                   _f(lse), C.byref(slabs)))
+    return {"logprob": lp, "topk_ids": ids, "topk_logprob": tlp, "lse": lse, "slabs": int(slabs.value)}
+
+
+def token_logprobs_bench(logits, top_k: int = 8, iters: int = 50, device: int = 0):
+    """(pair ms, score-rows ms) per pass over logits [rows, vocab]: the generation log-probability launch pair, and the
+    one-workgroup-per-row score kernel over the same rows 8 at a time (tools/bench_more.py llm_logprobs)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    rows, vocab = lg.shape
+    a, b = C.c_float(0), C.c_float(0)
+    check_error(lib().kjarni_hip_op_token_logprobs_bench(device, _f(lg), rows, vocab, int(top_k), int(iters), C.byref(a), C.byref(b)))
+    return float(a.value), float(b.value)
+
+
 def whisper_pick(logits, first_special: int, eos: int, timestamp_begin: int, allow_timestamps: bool, two_launch: bool, device: int = 0):
     """Whisper's pick on logits [calls, lanes, vocab]: tokens int32 [calls, lanes]; two_launch chooses the replayed step's
     two small launches over the one 1024-thread workgroup per lane."""

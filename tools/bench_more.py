@@ -47,6 +47,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            to 4 layers: a 5 GB fixture) against a dense Qwen3 model of the same widths with intermediate_size 6144 (the same active
            FFN bytes and FLOPs) in one process, alternated twice: greedy ms / token and the 128-token prompt time of both, their
            ratios, and the sparse step's streamed bytes against the HBM peak.
+  llm_logprobs  (only on request) generation log-probabilities (HipDecoder.generate_logprobs / generate_wide_logprobs) against the same
+           loop with them off: greedy and sampled, top_k 0 and 8, on the Llama-1B and gpt2-small shapes; 64 wide lanes off and on;
+           the kernel pair alone at V = 128 256 / 151 936 for 1 and 64 rows against the one-workgroup-per-row score kernel on the same
+           rows.  The lines also go to profiles/llm_logprobs_bench.jsonl.
   llm_constraint  (only on request) constrained decoding (HipDecoder.generate_constrained) against the plain loop of the same build,
            alternated twice in one process, greedy and sampled: Llama-3.2-1B shape (bf16) and gpt2-small (bf16), a pattern that
            masks nothing (the ids are the plain loop's, asserted), so the ratio is the cost of the two launches per step; and the
@@ -1885,6 +1889,111 @@ def main():
         with open(os.path.join(ROOT, "profiles", "qwen3_bench_llm.jsonl"), "w") as f:
             f.write(json.dumps(line) + "\n")
         del dec
+
+    if "llm_logprobs" in which:
+        # Method (as llm_constraint): one process on one box, everything warmed first; the same loop with log-probabilities off -- the
+        # yardstick -- alternates with top_k 0 and top_k 8, twice, greedy and sampled (the family-neutral config below, one seed); a
+        # decode window is a whole generation minus the same call cut after its first token; the ids of the three legs are equal
+        # (asserted).  Wide: 64 lanes, one 128-token prompt per lane, 128 new tokens, generate_wide against generate_wide_logprobs
+        # at top_k 8.  The kernel pair alone: kjarni_hip_op_token_logprobs_bench over seeded rows at V = 128 256 and 151 936, 1 and
+        # 64 rows, against the one-workgroup-per-row score kernel on the same rows 8 at a time (50 repeats between two events).
+        # A leg whose two runs differ by more than 10 % of their median goes into "unstable_legs" and its ratio is null.
+        from kjarni_amd import ops as KO
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        n_new = int(os.environ.get("KJARNI_LOGPROBS_TOKENS", "256"))
+        out_path = os.path.join(ROOT, "profiles", "llm_logprobs_bench.jsonl")
+        lines = []
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+        SAMPLING = dict(temperature=0.8, top_p=0.9, min_p=0.05)
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, vocab, lo, dtype):
+            prompt = rng.integers(lo, vocab, 128).tolist()
+            legs = {
+                "greedy_off": lambda n: dec.generate(prompt, n),
+                "greedy_k0": lambda n: dec.generate_logprobs(prompt, n, top_k=0)["ids"],
+                "greedy_k8": lambda n: dec.generate_logprobs(prompt, n, top_k=8)["ids"],
+                "sampled_off": lambda n: dec.generate_sampled(prompt, n, sample=True, seed=7, top_k=40, **SAMPLING)[0],
+                "sampled_k0": lambda n: dec.generate_logprobs(prompt, n, top_k=0, sample=True, seed=7, sampling_top_k=40, **SAMPLING)["ids"],
+                "sampled_k8": lambda n: dec.generate_logprobs(prompt, n, top_k=8, sample=True, seed=7, sampling_top_k=40, **SAMPLING)["ids"],
+            }
+            for fn in legs.values():
+                fn(8)
+            rate = {k: [] for k in legs}
+            outs = {}
+            for rep in range(2):
+                for k, fn in legs.items():
+                    dt, out = window(lambda: fn(n_new), lambda: fn(1))
+                    assert len(out) == n_new, (k, len(out))
+                    rate[k].append((n_new - 1) / dt)
+                    outs[k] = out
+            assert outs["greedy_off"] == outs["greedy_k0"] == outs["greedy_k8"] and outs["sampled_off"] == outs["sampled_k0"] == outs["sampled_k8"]
+            prompts = [rng.integers(lo, vocab, 128).tolist() for _ in range(64)]
+            wide = {"wide64_off": lambda n: dec.generate_wide(prompts, n, lanes=64, lane_context=512),
+                    "wide64_k8": lambda n: [g["ids"] for g in dec.generate_wide_logprobs(prompts, n, top_k=8, lanes=64, lane_context=512)]}
+            for fn in wide.values():
+                fn(20)
+            wrate = {k: [] for k in wide}
+            wouts = {}
+            for rep in range(2):
+                for k, fn in wide.items():
+                    dt, out = window(lambda: fn(128), lambda: fn(1))
+                    assert all(len(o) == 128 for o in out), k
+                    wrate[k].append(64 * 127 / dt)
+                    wouts[k] = out
+            assert wouts["wide64_off"] == wouts["wide64_k8"]
+            # a leg whose two runs lie more than 10 % of their median apart is no figure: it is listed and its ratio left out
+            unstable = sorted(k for k, v in {**rate, **wrate}.items() if (max(v) - min(v)) > 0.10 * med(v))
+            ratio = lambda a, b, r=rate: None if a in unstable or b in unstable else round(med(r[a]) / med(r[b]), 4)  # noqa: E731
+            line = {"metric": f"generation log-probabilities, {label}", "unit": "top_k 8 / off tokens per second, greedy", "value": ratio("greedy_k8", "greedy_off"),
+                    "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"random init, one 128-token prompt, {n_new} generated tokens; log-probabilities off, top_k 0 and top_k 8 "
+                                           "alternated twice in one process, greedy and sampled (temperature 0.8, top-k 40, top-p 0.9, min-p 0.05, "
+                                           "one seed), ids equal (asserted); 64 wide lanes: one 128-token prompt per lane, 128 tokens, off and top_k 8"},
+                    "tokens_per_s": {k: {"median": round(med(v), 1), "runs": [round(x, 1) for x in v]} for k, v in {**rate, **wrate}.items()},
+                    "over_off": {"greedy_k0": ratio("greedy_k0", "greedy_off"), "greedy_k8": ratio("greedy_k8", "greedy_off"),
+                                 "sampled_k0": ratio("sampled_k0", "sampled_off"), "sampled_k8": ratio("sampled_k8", "sampled_off"),
+                                 "wide64_k8": ratio("wide64_k8", "wide64_off", wrate)},
+                    "unstable_legs": unstable, "weight_bytes": dec.weight_bytes}
+            lines.append(line)
+            emit(line)
+
+        d = os.path.join(tmp, "llama-1b-logprobs")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, synth.LLAMA_1B["vocab_size"], 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+        gd = os.path.join(tmp, "gpt2-small-logprobs")
+        gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+        dec = kjarni_amd.HipDecoder(gd)
+        measure("gpt2-small shape, bf16 weights", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        for vocab in (128256, 151936):
+            for rows in (1, 64):
+                x = (rng.standard_normal((rows, vocab)) * 3.0).astype(np.float32)
+                KO.token_logprobs_bench(x, 8, 5)
+                runs = [KO.token_logprobs_bench(x, 8, 50) for _ in range(3)]
+                pair, score = med([r[0] for r in runs]), med([r[1] for r in runs])
+                line = {"metric": f"log-probability kernel pair alone, V {vocab}, {rows} row(s)", "unit": "score-rows kernel ms / pair ms",
+                        "value": round(score / pair, 3), "n_gpus": 1, "dtype": "f32", "data": "synthetic",
+                        "config": {"workload": "seeded normal logits x 3; 50 back-to-back repeats between two events, median of 3; the pair: slab "
+                                               "pass + finish, top_k 8; the score-rows kernel: one 256-thread workgroup per row, 8 rows a launch"},
+                        "pair_us": round(pair * 1e3, 2), "score_rows_us": round(score * 1e3, 2), "slabs": KO.token_logprob_slabs(rows, vocab),
+                        "row_bytes": vocab * 4}
+                lines.append(line)
+                emit(line)
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
     if "llm_embed" in which:
         # Method (measuring guide, section 5): one process on one box; every shape is warmed first; embed() returns after a
