@@ -1558,7 +1558,8 @@ KjarniErrorCode kjarni_hip_decoder_generate_constrained(KjarniHipDecoder* decode
                                                         KjarniHipConstraintResult* result);
 /* A pattern for every later request of the handle (NULL or "": none, the plain behaviour).  The token table comes from the
  * handle's own tokenizer, built once per pattern; the compiled constraint is kept until the pattern changes.  While set, requests
- * run through the plain loop even when prompt lookup or a draft model is switched on; generate_batch is not constrained. */
+ * run through the plain loop even when prompt lookup or a draft model is switched on; generate_batch constrains every prompt of the batch on its lane
+ * (kjarni_hip_generator_batch_constraint_result). */
 KjarniErrorCode kjarni_hip_generator_set_constraint(KjarniGenerator* generator, const char* pattern);
 KjarniErrorCode kjarni_hip_chat_set_constraint(KjarniChat* chat, const char* pattern);
 /* The result of the handle's last constrained request (zeros before one). */
@@ -1650,8 +1651,8 @@ typedef struct KjarniHipGrammarResult { uint32_t final_state, device_state; int3
  * (state 0 and wherever a token can end from such a state, a walk that pops below the token's own pushes going on in every return
  * state of the calls of the rule it leaves: an over-approximation) that offers no token other than a stop id and is either not
  * accepting, or accepting in rule 0 with a way on while the call has no stop id (the message names the state and its rule).  What
- * that lets through is caught at run time and ends the run with violated = 1.  The lane, wide, lookup and draft entries refuse a
- * grammar as they refuse a constraint.  result may be NULL. */
+ * that lets through is caught at run time and ends the run with violated = 1.  The lookup and draft entries refuse a grammar as they
+ * refuse a constraint; the lanes take one per prompt (kjarni_hip_decoder_generate_wide_constrained).  result may be NULL. */
 KjarniErrorCode kjarni_hip_decoder_generate_grammar(KjarniHipDecoder* decoder, const KjarniHipGrammarConstraint* grammar, const uint32_t* prompt,
                                                     size_t n_prompt, const KjarniHipSamplingOptions* options, KjarniTokenCallbackFn on_token,
                                                     void* user_data, uint32_t* ids_out, size_t capacity, size_t* n_out,
@@ -1732,6 +1733,89 @@ KjarniErrorCode kjarni_hip_chat_set_logprobs(KjarniChat* chat, int32_t top_k);
  * kjarni_token_scores_free. */
 KjarniErrorCode kjarni_hip_generator_last_logprobs(const KjarniGenerator* generator, size_t prompt_index, KjarniTokenScores* out);
 KjarniErrorCode kjarni_hip_chat_last_logprobs(const KjarniChat* chat, KjarniTokenScores* out);
+
+/* ---- constrained decoding in the lanes: a pattern or a grammar per prompt, up to 64 prompts in lock step ----------------------
+ * The device keeps one table of KJARNI_HIP_WIDE_LANES slots for both lane sets; slot l holds the kind of the request in lane l
+ * (0 none, 1 pattern, 2 grammar), that request's tables and stop ids, and the lane's row (pattern: state, done, violated; grammar:
+ * state, depth, done, violated, stack[64]).  Two kernels read it:
+ *   lane apply    grid (ceil(vocab / 256), lanes): the mask of kjarni_hip_op_constraint_apply or the walk of
+ *                 kjarni_hip_op_grammar_apply from the lane's own slot, by the same rules (an allowed logit keeps its bits, a stop id
+ *                 is governed by accepting / accepted alone, everything else becomes -inf); nothing is written for a frozen lane
+ *                 (live == 0), a lane of kind 0 or a done row.  The logits are rewritten in place and the lanes' pick runs on them.
+ *   lane advance  one thread per lane, right behind the lanes' pick: for a lane that was live at the pick, the picked token (the
+ *                 lane's newest history entry) moves the lane's row as kjarni_hip_op_constraint_advance / _grammar_advance would.
+ *                 A stop id in an accepting state (accepted configuration) sets done; a closed state (configuration) sets done and
+ *                 clears live -- the token stays in the history, nothing more is fed; a token the mask would not have allowed sets
+ *                 violated and done and clears live.  The limit, the full cache and the token hand-over stay the pick's.
+ * The two test hooks below make ONE launcher call on host arrays, check every argument before a device is asked for
+ * (INVALID_CONFIG names it), keep a guard band behind every device buffer and return their outputs whole.  Per lane l of
+ * [first_lane, first_lane + lanes): kinds[l] and, by kind, constraints[l] or grammars[l] (the other may be NULL; both arrays
+ * [64], as every per-lane array here), states[l], depths[l], stacks[l][64], done[l], and the lane's stop ids stop_ids[l][16] /
+ * n_stop[l] (the automaton's own: independent of state->stop).  Lanes outside the range are neither read nor written. */
+/* KjarniHipWideState for the 8-lane set (kjarni_hip_decoder_generate_batch's lanes): the same fields, 8 entries each. */
+#define KJARNI_HIP_BATCH_LANES 8
+typedef struct KjarniHipLaneState {
+    int32_t token[KJARNI_HIP_BATCH_LANES];
+    int32_t pos[KJARNI_HIP_BATCH_LANES];
+    int32_t live[KJARNI_HIP_BATCH_LANES];
+    int32_t count[KJARNI_HIP_BATCH_LANES];
+    int32_t limit[KJARNI_HIP_BATCH_LANES];
+    int32_t n_stop[KJARNI_HIP_BATCH_LANES];
+    int32_t stop[KJARNI_HIP_BATCH_LANES][KJARNI_HIP_LANE_STOPS];
+} KjarniHipLaneState;
+/* logits [first_lane + lanes, ld] -> logits_out (the same shape, all of it). */
+KjarniErrorCode kjarni_hip_op_lane_automaton_apply(int32_t device, const float* logits, int64_t ld, int32_t vocab, int32_t lanes, int32_t first_lane,
+                                                   const int32_t* live, const int32_t* kinds, const KjarniHipConstraint* const* constraints,
+                                                   const KjarniHipGrammarConstraint* const* grammars, const uint32_t* states, const int32_t* depths,
+                                                   const uint16_t* stacks, const int32_t* done, const uint32_t* stop_ids, const int32_t* n_stop,
+                                                   float* logits_out);
+/* kjarni_hip_op_wide_pick (wide != 0: state is a KjarniHipWideState, history [64, hist_stride]; wide == 0: the 8-lane layout, the
+ * same fields with 8 entries each and stop [8][16], history [8, hist_stride], lanes within 0..8) followed by the lane advance:
+ * state and history are picked in place, states / depths / stacks / done move in place, violated_out [64] is written for the
+ * lanes of the range. */
+KjarniErrorCode kjarni_hip_op_lane_automaton_pick(int32_t device, int32_t wide, const float* logits, int64_t ld, int32_t vocab, int32_t lanes,
+                                                  int32_t first_lane, void* state, int32_t* history, int32_t hist_stride, int32_t capacity,
+                                                  int32_t advance, const int32_t* kinds, const KjarniHipConstraint* const* constraints,
+                                                  const KjarniHipGrammarConstraint* const* grammars, uint32_t* states, int32_t* depths,
+                                                  uint16_t* stacks, int32_t* done, const uint32_t* stop_ids, const int32_t* n_stop,
+                                                  int32_t* violated_out);
+/* How prompt i of a constrained lane call ended: kind (0 none, 1 pattern, 2 grammar) and the fields of KjarniHipGrammarResult
+ * (depths 0 under a pattern).  device_state / device_depth: the lane's row as read back when the lane went dead on the device;
+ * the host's values where the callback ended the prompt. */
+typedef struct KjarniHipLaneAutomatonResult {
+    int32_t kind;
+    uint32_t final_state, device_state;
+    int32_t final_depth, device_depth, accepted, complete, violated;
+} KjarniHipLaneAutomatonResult;
+/* kjarni_hip_decoder_generate_wide_logprobs with an automaton per prompt: its arguments (top_k = -1: no records), then
+ * constraints [n] and grammars [n] (either array may be NULL, and so may any entry: a prompt with neither runs as in
+ * kjarni_hip_decoder_generate_wide) and results [n] (may be NULL).  A lane that takes prompt i gets that prompt's tables, the
+ * model's stop ids and a fresh row before its first pick; greedy prompts replay one captured chain step -> (slab pass) -> lane
+ * apply -> pick -> lane advance (-> record) per (lane set, width, records), prompts with a penalty or an n-gram ban are decided
+ * lane by lane with the mask ahead of the processors.  Prompt i's ids and result are those of
+ * kjarni_hip_decoder_generate_constrained / _grammar / _generate on that prompt alone; the records stay those of the raw
+ * distribution.  Widths of 8 or fewer run the 8-lane set.  Before any GPU work, INVALID_CONFIG naming the prompt index: both a
+ * constraint and a grammar for one prompt, an automaton of another device or vocabulary, more than 16 stop ids, and the refusal
+ * on states of that prompt's automaton; the other refusals are kjarni_hip_decoder_generate_wide_logprobs'.  The lookup and draft
+ * entries keep refusing constraints. */
+KjarniErrorCode kjarni_hip_decoder_generate_wide_constrained(KjarniHipDecoder* decoder, const uint32_t* prompt_ids, const size_t* offsets, size_t n,
+                                                             const size_t* max_new_tokens, float repetition_penalty,
+                                                             int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                             KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                             size_t capacity, size_t* n_out, int32_t top_k, float* logprob_out,
+                                                             uint32_t* topk_ids_out, float* topk_logprob_out,
+                                                             const KjarniHipConstraint* const* constraints,
+                                                             const KjarniHipGrammarConstraint* const* grammars,
+                                                             KjarniHipLaneAutomatonResult* results);
+/* generate_batch under the handle's pattern or grammar: every prompt of the batch is constrained by it on its lane, and this is
+ * the result of prompt `prompt_index` of the handle's last generate_batch call (zeros, kind 0, before one, after an
+ * unconstrained one and for an index the call did not have). */
+KjarniErrorCode kjarni_hip_generator_batch_constraint_result(const KjarniGenerator* generator, size_t prompt_index,
+                                                             KjarniHipLaneAutomatonResult* out);
+/* Test hook: the seed of the generator that prompt `prompt_index` of the handle's last generate_batch call drew from (every prompt
+ * of a batch draws from its own, seeded from the handle's in prompt order at call start); 1 for a greedy batch, 0 for NULL or an index
+ * the call did not have.  kjarni_hip_generator_seed with it, then generate of that prompt alone, takes the same draws. */
+uint64_t kjarni_hip_generator_batch_seed(const KjarniGenerator* generator, size_t prompt_index);
 
 #ifdef __cplusplus
 }

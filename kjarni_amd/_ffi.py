@@ -255,6 +255,18 @@ class KjarniHipWideState(Structure):
                 ("n_stop", c_int32 * 64), ("stop", (c_int32 * 16) * 64)]
 
 
+class KjarniHipLaneState(Structure):
+    """KjarniHipWideState for the 8-lane set (kjarni_hip.h)."""
+    _fields_ = [("token", c_int32 * 8), ("pos", c_int32 * 8), ("live", c_int32 * 8), ("count", c_int32 * 8), ("limit", c_int32 * 8),
+                ("n_stop", c_int32 * 8), ("stop", (c_int32 * 16) * 8)]
+
+
+class KjarniHipLaneAutomatonResult(Structure):
+    """How one prompt of a constrained lane call ended (kjarni_hip.h)."""
+    _fields_ = [("kind", c_int32), ("final_state", C.c_uint32), ("device_state", C.c_uint32), ("final_depth", c_int32),
+                ("device_depth", c_int32), ("accepted", c_int32), ("complete", c_int32), ("violated", c_int32)]
+
+
 class KjarniHipLookupStats(Structure):
     _fields_ = [("verify_steps", c_uint64), ("drafted_tokens", c_uint64), ("accepted_tokens", c_uint64), ("single_row_steps", c_uint64)]
 
@@ -680,6 +692,20 @@ SIGNATURES = {
     "kjarni_hip_decoder_generate_wide_logprobs": (c_int32, [c_void_p, _u32p, POINTER(c_size_t), c_size_t, POINTER(c_size_t), c_float, c_int32,
                                                             c_int32, c_int32, KjarniBatchTokenCallbackFn, c_void_p, _u32p, c_size_t,
                                                             POINTER(c_size_t), c_int32, _f32p, _u32p, _f32p]),
+    # constrained decoding in the lanes: the two kernels alone, the decoder entry, the Generator's per-prompt result
+    "kjarni_hip_op_lane_automaton_apply": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
+                                                     POINTER(c_void_p), POINTER(c_void_p), _u32p, POINTER(c_int32), POINTER(C.c_uint16),
+                                                     POINTER(c_int32), _u32p, POINTER(c_int32), _f32p]),
+    "kjarni_hip_op_lane_automaton_pick": (c_int32, [c_int32, c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_void_p, POINTER(c_int32),
+                                                    c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p), _u32p,
+                                                    POINTER(c_int32), POINTER(C.c_uint16), POINTER(c_int32), _u32p, POINTER(c_int32),
+                                                    POINTER(c_int32)]),
+    "kjarni_hip_decoder_generate_wide_constrained": (c_int32, [c_void_p, _u32p, POINTER(c_size_t), c_size_t, POINTER(c_size_t), c_float, c_int32,
+                                                               c_int32, c_int32, KjarniBatchTokenCallbackFn, c_void_p, _u32p, c_size_t,
+                                                               POINTER(c_size_t), c_int32, _f32p, _u32p, _f32p, POINTER(c_void_p),
+                                                               POINTER(c_void_p), POINTER(KjarniHipLaneAutomatonResult)]),
+    "kjarni_hip_generator_batch_constraint_result": (c_int32, [c_void_p, c_size_t, POINTER(KjarniHipLaneAutomatonResult)]),
+    "kjarni_hip_generator_batch_seed": (c_uint64, [c_void_p, c_size_t]),
     "kjarni_hip_generator_set_logprobs": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_set_logprobs": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_generator_last_logprobs": (c_int32, [c_void_p, c_size_t, POINTER(KjarniTokenScores)]),

@@ -494,3 +494,95 @@ class GrammarConstraint:
 def grammar_result_dict(r: "_ffi.KjarniHipGrammarResult") -> Dict[str, int]:
     return {"final_state": int(r.final_state), "device_state": int(r.device_state), "final_depth": int(r.final_depth),
             "device_depth": int(r.device_depth), "accepted": int(r.accepted), "complete": int(r.complete), "violated": int(r.violated)}
+
+
+# ---- the lanes: an automaton per lane (the result struct, and the test hook of the two kernels) ----------------------------------------------------------------------------------------------
+
+LANE_SLOTS = 64
+
+
+def lane_result_dict(r: "_ffi.KjarniHipLaneAutomatonResult") -> Dict[str, int]:
+    return {"kind": int(r.kind), "final_state": int(r.final_state), "device_state": int(r.device_state), "final_depth": int(r.final_depth),
+            "device_depth": int(r.device_depth), "accepted": int(r.accepted), "complete": int(r.complete), "violated": int(r.violated)}
+
+
+class LaneAutomata:
+    """TEST HOOK, not part of the decoding interface (generate_wide_constrained and Generator.generate_batch are): the per-lane host
+    arrays that kjarni_hip_op_lane_automaton_apply / _pick take, so that the two kernels can be run alone, as Constraint.apply and
+    GrammarConstraint.apply / advance run theirs.  violated starts at -7 so that a caller can tell what a call wrote.  `lanes`: one entry per lane from lane 0, each None (kind 0), or a dict with
+    "automaton" (a Constraint: a pattern lane, "state"; a GrammarConstraint: a grammar lane, "config" = (state, stack[, all 64
+    stack words])), and optionally "done" and "stop_ids".  Lanes behind the list are kind 0."""
+
+    def __init__(self, lanes):
+        n = LANE_SLOTS
+        self.kinds = np.zeros(n, np.int32)
+        self.constraints = (C.c_void_p * n)()
+        self.grammars = (C.c_void_p * n)()
+        self.states = np.zeros(n, np.uint32)
+        self.depths = np.zeros(n, np.int32)
+        self.stacks = np.zeros((n, GRAMMAR_MAX_DEPTH), np.uint16)
+        self.done = np.zeros(n, np.int32)
+        self.stops = np.zeros((n, 16), np.uint32)
+        self.n_stop = np.zeros(n, np.int32)
+        self.violated = np.full(n, -7, np.int32)
+        self._keep = list(lanes)
+        for l, e in enumerate(lanes):
+            if e is None:
+                continue
+            a = e["automaton"]
+            stops = list(e.get("stop_ids", ()))
+            self.n_stop[l] = len(stops)
+            self.stops[l, :min(len(stops), 16)] = stops[:16]
+            self.done[l] = 1 if e.get("done") else 0
+            if isinstance(a, GrammarConstraint):
+                self.kinds[l] = 2
+                self.grammars[l] = a._h.value
+                c = e.get("config", (0, []))
+                self.states[l] = c[0]
+                self.depths[l] = len(c[1])
+                if len(c) > 2:
+                    self.stacks[l] = c[2]
+                self.stacks[l, :min(len(c[1]), GRAMMAR_MAX_DEPTH)] = c[1][:GRAMMAR_MAX_DEPTH]
+            else:
+                self.kinds[l] = 1
+                self.constraints[l] = a._h.value
+                self.states[l] = e.get("state", 0)
+
+    def _args(self):
+        i32, u32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        return (self.kinds.ctypes.data_as(i32), self.constraints, self.grammars, self.states.ctypes.data_as(u32), self.depths.ctypes.data_as(i32),
+                self.stacks.ctypes.data_as(C.POINTER(C.c_uint16)), self.done.ctypes.data_as(i32), self.stops.ctypes.data_as(u32),
+                self.n_stop.ctypes.data_as(i32))
+
+    def apply(self, logits: np.ndarray, live, lanes: Optional[int] = None, first_lane: int = 0, vocab: Optional[int] = None,
+              device: int = 0) -> np.ndarray:
+        """lane_automaton_apply_kernel alone (kjarni_hip_op_lane_automaton_apply): logits [first_lane + lanes, ld] float32, live [64]."""
+        logits = np.ascontiguousarray(logits, np.float32)
+        rows, ld = logits.shape
+        lanes = rows - first_lane if lanes is None else int(lanes)
+        lv = np.zeros(LANE_SLOTS, np.int32)
+        lv[:len(live)] = live
+        out = np.empty_like(logits)
+        check_error(lib().kjarni_hip_op_lane_automaton_apply(device, logits.ctypes.data_as(C.POINTER(C.c_float)), ld, ld if vocab is None else int(vocab),
+                                                             lanes, int(first_lane), lv.ctypes.data_as(C.POINTER(C.c_int32)), *self._args(),
+                                                             out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def pick(self, logits: np.ndarray, state, history: np.ndarray, capacity: int, lanes: Optional[int] = None, first_lane: int = 0,
+             advance: int = 1, vocab: Optional[int] = None, device: int = 0):
+        """The lanes' pick and the lane advance behind it (kjarni_hip_op_lane_automaton_pick): `state` is a _ffi.KjarniHipWideState
+        (history [64, stride]) or a _ffi.KjarniHipLaneState (history [8, stride]), picked in place, as `history` (int32) and this
+        object's states / depths / stacks / done; violated is written for the lanes of the range."""
+        logits = np.ascontiguousarray(logits, np.float32)
+        rows, ld = logits.shape
+        lanes = rows - first_lane if lanes is None else int(lanes)
+        wide = 1 if isinstance(state, _ffi.KjarniHipWideState) else 0
+        if history.dtype != np.int32 or not history.flags["C_CONTIGUOUS"] or history.shape[0] != (64 if wide else 8):
+            raise ValueError("history: a contiguous int32 array of 64 (wide state) or 8 rows")
+        args = self._args()
+        check_error(lib().kjarni_hip_op_lane_automaton_pick(device, wide, logits.ctypes.data_as(C.POINTER(C.c_float)), ld,
+                                                            ld if vocab is None else int(vocab), lanes, int(first_lane),
+                                                            C.cast(C.byref(state), C.c_void_p), history.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            history.shape[1], int(capacity), int(advance), *args,
+                                                            self.violated.ctypes.data_as(C.POINTER(C.c_int32))))
+        return self

@@ -881,14 +881,25 @@ std::vector<std::string> Generator::generate_batch(const std::vector<std::string
     rngs.reserve(prompts.size());
     std::vector<LaneRequest> reqs(prompts.size());
     last_logprobs_.assign(prompts.size(), GeneratedLogprobs{});
+    // the handle's pattern or grammar (it holds at most one) constrains every prompt on its lane
+    batch_kind_ = constraint_ ? 1 : grammar_ ? 2 : 0;
+    batch_outcomes_.assign(batch_kind_ ? prompts.size() : 0, ConstraintOutcome{});
+    batch_seeds_.clear();
     for (size_t i = 0; i < prompts.size(); ++i) {
-        rngs.emplace_back(config.strategy == Strategy::Sample ? (uint64_t)(rng_.next() * 16777216.0f) + 1 : 1);
+        const uint64_t seed = config.strategy == Strategy::Sample ? (uint64_t)(rng_.next() * 16777216.0f) + 1 : 1;
+        rngs.emplace_back(seed);
+        batch_seeds_.push_back(seed);
         std::vector<uint32_t> tokens = encode(prompts[i], config);
         if (tokens.empty()) throw std::runtime_error("generation failed: cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
         reqs[i].options = text_generation_options(*model_, tokens.size(), config, stop_ids_, rngs[i]);
         if (logprobs_ >= 0) {
             reqs[i].options.logprobs = logprobs_;
             reqs[i].options.logprob_sink = &last_logprobs_[i].records;
+        }
+        if (batch_kind_) {
+            reqs[i].options.constraint = constraint_.get();
+            reqs[i].options.grammar = grammar_.get();
+            reqs[i].options.constraint_outcome = &batch_outcomes_[i];
         }
         if ((int)tokens.size() > model_->context()) tokens.resize((size_t)model_->context());
         reqs[i].prompt = std::move(tokens);
@@ -902,6 +913,20 @@ std::vector<std::string> Generator::generate_batch(const std::vector<std::string
     if (wide_lanes_ > 0) model_->generate_wide(reqs, wide_lanes_, 0, on_token);  // (set_wide_lanes: up to 64, the wide step above 8)
     else model_->generate_lanes(reqs, lanes, 0, on_token);
     return texts;
+}
+
+uint64_t Generator::batch_seed(size_t prompt_index) const
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    return prompt_index < batch_seeds_.size() ? batch_seeds_[prompt_index] : 0;
+}
+
+ConstraintOutcome Generator::batch_constraint_outcome(size_t prompt_index, int* kind) const
+{
+    std::lock_guard<std::mutex> lock(mutex_);
+    const bool have = prompt_index < batch_outcomes_.size();
+    if (kind) *kind = have ? batch_kind_ : 0;
+    return have ? batch_outcomes_[prompt_index] : ConstraintOutcome{};
 }
 
 }  // namespace kjarni

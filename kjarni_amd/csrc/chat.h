@@ -200,9 +200,17 @@ public:
     void set_prompt_lookup_sampling(bool on) { lookup_sampling_ = on; }
     // A draft model for generate / stream (Chat::set_draft_model's contract); generate_batch is untouched.
     void set_draft_model(const std::string& path, int draft_tokens);
-    // Constrained decoding for generate / stream (Chat::set_constraint's contract); generate_batch is untouched.
+    // Constrained decoding for generate / stream (Chat::set_constraint's contract).  generate_batch passes the handle's pattern or
+    // grammar to every prompt of the batch (LlmModel::generate_lanes / generate_wide take one per request) and keeps one outcome
+    // per prompt.
     void set_constraint(const std::string& pattern);
     ConstraintOutcome constraint_outcome() const { return constraint_outcome_; }
+    // Prompt `prompt_index` of the last generate_batch call: *kind 0 none, 1 pattern, 2 grammar, and its outcome (zeros with kind 0
+    // before a call, after an unconstrained one and for an index the call did not have).
+    ConstraintOutcome batch_constraint_outcome(size_t prompt_index, int* kind) const;
+    // Test hook: the seed of the generator prompt `prompt_index` of the last generate_batch call drew from (0: no such prompt).
+    // reseed() with it and generate() of that prompt alone take the same draws.
+    uint64_t batch_seed(size_t prompt_index) const;
     void set_grammar(const std::vector<std::pair<std::string, std::string>>& rules);  // (Chat::set_grammar's contract)
     // Log-probabilities of the generated tokens (GenerateOptions::logprobs): -1 = off (the default), 0..KJARNI_SCORE_TOPK_MAX = every
     // later request records, per emitted token, its log-probability under the raw distribution and that many alternatives.  While
@@ -262,6 +270,9 @@ private:
     std::unique_ptr<DeviceConstraint> constraint_;
     std::unique_ptr<DeviceGrammar> grammar_;
     ConstraintOutcome constraint_outcome_;
+    std::vector<ConstraintOutcome> batch_outcomes_;  // of the last generate_batch call under batch_kind_ (empty: unconstrained)
+    int batch_kind_ = 0;
+    std::vector<uint64_t> batch_seeds_;
     int logprobs_ = -1;
     std::vector<GeneratedLogprobs> last_logprobs_;
 };

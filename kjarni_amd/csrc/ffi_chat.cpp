@@ -772,6 +772,11 @@ KJARNI_EXPORT void kjarni_hip_generator_seed(KjarniGenerator* gen, uint64_t seed
     if (gen) gen->inner->reseed(seed);
 }
 
+KJARNI_EXPORT uint64_t kjarni_hip_generator_batch_seed(const KjarniGenerator* gen, size_t prompt_index)
+{
+    return gen ? gen->inner->batch_seed(prompt_index) : 0;
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_lanes(KjarniGenerator* gen, int32_t lanes)
 {
     if (!gen) return KJARNI_ERROR_NULL_POINTER;
@@ -886,6 +891,17 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_constraint_result(const Kjarn
 {
     if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
     *out = constraint_result(gen->inner->constraint_outcome());
+    return KJARNI_OK;
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_batch_constraint_result(const KjarniGenerator* gen, size_t prompt_index,
+                                                                           KjarniHipLaneAutomatonResult* out)
+{
+    if (!gen || !out) return KJARNI_ERROR_NULL_POINTER;
+    int kind = 0;
+    const ConstraintOutcome o = gen->inner->batch_constraint_outcome(prompt_index, &kind);
+    *out = KjarniHipLaneAutomatonResult{kind, o.final_state, o.device_state, o.final_depth, o.device_depth, o.accepted ? 1 : 0, o.complete ? 1 : 0,
+                                        o.violated ? 1 : 0};
     return KJARNI_OK;
 }
 

@@ -157,7 +157,9 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
                                          const size_t* max_new_tokens, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t lanes,
                                          int32_t lane_context, KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
                                          size_t capacity, size_t* n_out, int32_t top_k = -1, float* logprob_out = nullptr,
-                                         uint32_t* topk_ids_out = nullptr, float* topk_logprob_out = nullptr)
+                                         uint32_t* topk_ids_out = nullptr, float* topk_logprob_out = nullptr,
+                                         const KjarniHipConstraint* const* constraints = nullptr,
+                                         const KjarniHipGrammarConstraint* const* grammars = nullptr, KjarniHipLaneAutomatonResult* results = nullptr)
 {
     if (!d) return KJARNI_ERROR_NULL_POINTER;
     if (n == 0) return KJARNI_OK;  // nothing to do, nothing written
@@ -173,7 +175,11 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
                                 "] and not above the vocabulary (" + std::to_string(d->model->config().vocab) + ")");
         std::vector<LaneRequest> reqs(n);
         std::vector<TokenLogprobs> records(top_k >= 0 ? n : 0);
+        std::vector<ConstraintOutcome> outcomes(constraints || grammars ? n : 0);
         for (size_t i = 0; i < n; ++i) {
+            if (constraints && constraints[i]) reqs[i].options.constraint = constraints[i]->inner.get();
+            if (grammars && grammars[i]) reqs[i].options.grammar = grammars[i]->inner.get();
+            if (!outcomes.empty()) reqs[i].options.constraint_outcome = &outcomes[i];
             if (offsets[i + 1] < offsets[i]) throw InvalidConfig("prompt offsets must not decrease");
             if (wide && offsets[i + 1] == offsets[i]) throw InvalidConfig("cannot generate from empty prompt (prompt " + std::to_string(i) + ")");
             if (offsets[i + 1] - offsets[i] > (size_t)cap)  // before any GPU work
@@ -202,6 +208,12 @@ static KjarniErrorCode generate_batch_on(KjarniHipDecoder* d, bool wide, const u
         for (size_t i = 0; i < n; ++i) {
             n_out[i] = got[i].size();
             if (capacity) std::memcpy(ids_out + i * capacity, got[i].data(), std::min(capacity, got[i].size()) * sizeof(uint32_t));
+            if (results) {
+                const int32_t kind = reqs[i].options.constraint ? 1 : reqs[i].options.grammar ? 2 : 0;
+                const ConstraintOutcome o = kind ? outcomes[i] : ConstraintOutcome();
+                results[i] = KjarniHipLaneAutomatonResult{kind, o.final_state, o.device_state, o.final_depth, o.device_depth, o.accepted ? 1 : 0,
+                                                          o.complete ? 1 : 0, o.violated ? 1 : 0};
+            }
             if (top_k < 0) continue;
             const TokenLogprobs& r = records[i];
             if (r.logprob.size() != got[i].size()) throw std::runtime_error("generate: the records do not match the emitted tokens");
@@ -248,6 +260,26 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_wide_logprobs(KjarniHi
     }
     return generate_batch_on(d, true, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
                              on_token, user_data, ids_out, capacity, n_out, top_k, logprob_out, topk_ids_out, topk_logprob_out);
+}
+
+// generate_wide_logprobs with an automaton per prompt (top_k = -1: no records)
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_generate_wide_constrained(KjarniHipDecoder* d, const uint32_t* prompt_ids, const size_t* offsets,
+                                                                           size_t n, const size_t* max_new_tokens, float repetition_penalty,
+                                                                           int32_t no_repeat_ngram_size, int32_t lanes, int32_t lane_context,
+                                                                           KjarniBatchTokenCallbackFn on_token, void* user_data, uint32_t* ids_out,
+                                                                           size_t capacity, size_t* n_out, int32_t top_k, float* logprob_out,
+                                                                           uint32_t* topk_ids_out, float* topk_logprob_out,
+                                                                           const KjarniHipConstraint* const* constraints,
+                                                                           const KjarniHipGrammarConstraint* const* grammars,
+                                                                           KjarniHipLaneAutomatonResult* results)
+{
+    if (top_k < -1 || top_k > KJARNI_SCORE_TOPK_MAX) {  // (judged ahead of the handle)
+        set_last_error("top_k (" + std::to_string(top_k) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) + "] (-1: no records)");
+        return KJARNI_ERROR_INVALID_CONFIG;
+    }
+    return generate_batch_on(d, true, prompt_ids, offsets, n, max_new_tokens, repetition_penalty, no_repeat_ngram_size, lanes, lane_context,
+                             on_token, user_data, ids_out, capacity, n_out, top_k, logprob_out, topk_ids_out, topk_logprob_out, constraints, grammars,
+                             results);
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_begin(KjarniHipDecoder* d, int32_t lanes, int32_t lane_context)

@@ -57,7 +57,8 @@ struct GenerateOptions {
     SamplingParams sampling;
     std::vector<uint32_t> stop_ids;  // empty: every eos_token_id of config.json
     std::function<float()> uniform;  // the draw in [0, 1) for each sampled token
-    // Constrained decoding: generate() alone takes it (the lane, lookup and draft entry points refuse it).
+    // Constrained decoding: generate() takes it, and the lanes per request (generate_lanes / generate_wide); the lookup and draft
+    // entry points refuse it.
     const DeviceConstraint* constraint = nullptr;
     ConstraintOutcome* constraint_outcome = nullptr;  // may be null
     // ... or a grammar (a stack automaton: grammar_kernels.h) in its place; setting both is InvalidConfig.  The outcome as above.

@@ -20,6 +20,7 @@
 #include "moe_kernels.h"
 #include "constraint_kernels.h"
 #include "grammar_kernels.h"
+#include "lane_constraint_kernels.h"
 #include "logprob_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
@@ -1498,6 +1499,10 @@ void LlmModel::drop_lane_logprob_graphs(bool wide)
         if (wide) drop_graphs(wide_lp_graphs_[v]);
         else drop_graphs(lane_lp_graphs_[v]);
     }
+    for (int v = 0; v < 3; ++v) {  // (the constrained chains hold the same lane buffers and capacity: they go where these go)
+        if (wide) drop_graphs(wide_auto_graphs_[v]);
+        else drop_graphs(lane_auto_graphs_[v]);
+    }
 }
 
 void LlmModel::ensure_lane_logprobs(bool wide)
@@ -1547,6 +1552,51 @@ hipGraphExec_t LlmModel::lane_logprob_step_graph(bool wide, int n, int k)
         else
             hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_,
                                        1, stream_), "lane pick");
+    });
+}
+
+// ---- constrained lanes ----
+void LlmModel::ensure_lane_automata()
+{
+    if (lane_auto_) return;
+    lane_auto_ = reinterpret_cast<LaneAutomatonTable*>(dalloc((sizeof(LaneAutomatonTable) + 3) / 4));
+    lane_auto_host_ = std::make_unique<LaneAutomatonTable>();
+    std::memset(lane_auto_host_.get(), 0, sizeof(LaneAutomatonTable));
+    hip_check(hipMemcpy(lane_auto_, lane_auto_host_.get(), sizeof(LaneAutomatonTable), hipMemcpyHostToDevice), "H2D lane automata");
+}
+
+void LlmModel::lane_automaton_pick_enqueue(bool wide, int first, int rows, int advance, bool records, int k)
+{
+    const LaneLogs& L = lane_logs_[wide ? 1 : 0];
+    constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
+    float* logits = wide ? wide_logits_ : lane_logits_;
+    const float* part = logits + (size_t)first * cfg_.vocab;
+    int32_t* live = wide ? wide_state_->live : lane_state_->live;  // (addresses in device memory: nothing is read here)
+    const int* count = wide ? wide_state_->count : lane_state_->count;
+    if (records) logprob_partial_on(part, rows, live + first, k, L.scratch, nullptr);  // the raw rows, ahead of the mask
+    hip_check(launch_lane_automaton_apply(logits, cfg_.vocab, cfg_.vocab, rows, first, lane_auto_, live, stream_), "lane automaton apply");
+    if (wide)
+        hip_check(launch_wide_automaton_pick(wide_logits_, cfg_.vocab, cfg_.vocab, rows, first, wide_best_, wide_state_, wide_hist_, wide_hist_stride_,
+                                             wide_cap_, advance, lane_auto_, stream_), "wide automaton pick");
+    else
+        hip_check(launch_lane_automaton_pick(lane_logits_, cfg_.vocab, cfg_.vocab, rows, first, lane_best_, lane_state_, lane_hist_,
+                                             lane_hist_stride_, lane_cap_, advance, lane_auto_, stream_), "lane automaton pick");
+    // the record of the lanes that picked, at index count - 1 (the pick has counted); the picked logit is an allowed one, which the
+    // mask did not rewrite
+    if (records)
+        logprob_finish_on(part, rows, lane_auto_->fresh + first, k, L.scratch, part, lane_auto_->picked + first, count + first, -1, L.stride,
+                          L.lp + (size_t)first * L.stride, L.ids + (size_t)first * L.stride * S, L.tlp + (size_t)first * L.stride * S);
+}
+
+hipGraphExec_t LlmModel::lane_automaton_step_graph(bool wide, int n, bool records, int k)
+{
+    const int v = !records ? 0 : k > 1 ? 2 : 1;
+    hipGraphExec_t& g = wide ? wide_auto_graphs_[v][n] : lane_auto_graphs_[v][n];
+    if (g) return g;
+    return g = capture_graph(stream_, [&] {
+        if (wide) wide_step_enqueue(n);
+        else lane_step(n);
+        lane_automaton_pick_enqueue(wide, 0, n, 1, records, k);
     });
 }
 
@@ -2364,15 +2414,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                                                                const std::function<bool(size_t, uint32_t)>& on_token, bool wide, bool strict)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    const char* entry = strict ? "generate_wide" : "generate_lanes";
     auto refuse = [&](const std::string& what) {  // generate_lanes' own refusals keep their types
         if (strict) throw InvalidConfig(what);
         throw std::runtime_error(what);
     };
-    for (const LaneRequest& r : reqs) {
-        if (r.options.constraint) throw InvalidConfig(std::string(entry) + " does not take a constraint (generate does)");
-        if (r.options.grammar) throw InvalidConfig(std::string(entry) + " does not take a grammar (generate does)");
-    }
+    bool automata = false;  // some request carries a pattern or a grammar: the constrained chains, the lanes' automaton table
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     bool slow = false;  // some request needs its logits row looked at: processors or sampling
     // Log-probabilities: on when some request asks for them and gives a sink; lpk is the width the device computes for every lane
@@ -2391,6 +2437,26 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         if (r.options.sample && !r.options.uniform) refuse("sampling needs a uniform source (prompt " + std::to_string(i) + ")");
         waiting.emplace_back(r.prompt, r.options, (size_t)cap, cfg_.eos_ids, out[i]);
         if ((int)waiting.back().stops.size() > kMaxLaneStops) refuse("more than 16 stop ids (prompt " + std::to_string(i) + ")");
+        if (r.options.constraint || r.options.grammar) {  // generate()'s refusals, by prompt
+            const std::string who = " (prompt " + std::to_string(i) + ")";
+            if (r.options.constraint && r.options.grammar) throw InvalidConfig("a request takes a constraint or a grammar, not both" + who);
+            const int adev = r.options.constraint ? r.options.constraint->device() : r.options.grammar->device();
+            const int avocab = r.options.constraint ? r.options.constraint->vocab() : r.options.grammar->vocab();
+            const char* what = r.options.constraint ? "constraint" : "grammar";
+            if (adev != device_)
+                throw InvalidConfig(std::string("the ") + what + " lives on device " + std::to_string(adev) + ", the model on device " +
+                                    std::to_string(device_) + who);
+            if (avocab != cfg_.vocab)
+                throw InvalidConfig(std::string("the ") + what + "'s token table has " + std::to_string(avocab) + " tokens, the model's vocabulary " +
+                                    std::to_string(cfg_.vocab) + who);
+            try {
+                if (r.options.constraint) r.options.constraint->check_states(waiting.back().stops);
+                else r.options.grammar->check_states(waiting.back().stops);
+            } catch (const InvalidConfig& e) {
+                throw InvalidConfig(std::string(e.what()) + who);
+            }
+            automata = true;
+        }
         slow = slow || r.options.sample || r.options.repetition_penalty != 1.0f || r.options.no_repeat_ngram > 0;
         if (r.options.logprobs < -1 || r.options.logprobs > KJARNI_SCORE_TOPK_MAX || r.options.logprobs > cfg_.vocab)
             throw InvalidConfig("top_k (" + std::to_string(r.options.logprobs) + ") must be in [0, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
@@ -2410,6 +2476,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         for (const LaneRequest& r : reqs)
             if (r.options.logprobs >= 0 && r.options.logprob_sink) r.options.logprob_sink->clear(r.options.logprobs);
     }
+    if (automata) ensure_lane_automata();
     const LaneLogs& LL = lane_logs_[wide ? 1 : 0];
     const LaneSet S = wide ? wide_set() : lane_set();
     const LaneSet& h = S;  // (the mirror's fields, as the loop has always named them)
@@ -2447,25 +2514,103 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         GenerationRun g;
         std::function<bool(uint32_t)> on_token;  // the caller's, bound to the request
         TokenLogprobs* sink = nullptr;           // where the request's records go (null: it asked for none)
+        AutomatonCursor cur;                     // the host's copy of the request's automaton (empty: the request has none)
+        ConstraintOutcome outcome;
+        ConstraintOutcome* outcome_out = nullptr;
+        bool reported = true;                    // the outcome has been written, or there is none to write
     };
     std::vector<Run> run((size_t)n);
     size_t next_req = 0;
     auto take = [&](int l, uint32_t tok) {  // generate()'s drain; true: the token was emitted
         Run& r = run[l];
-        return !r.g.done && r.g.accept(tok, r.on_token);
+        if (r.g.done) return false;
+        if (!r.cur) return r.g.accept(tok, r.on_token);
+        // ... under an automaton, as generate() has it: a stop id ends the request (complete when the state is accepting), any
+        // other token moves the host's cursor, and a closed state ends the request behind the token
+        if (!r.g.wants_token()) {
+            r.g.done = true;
+            return false;
+        }
+        if (r.g.is_stop(tok)) {
+            (r.cur.accepting() ? r.outcome.complete : r.outcome.violated) = true;
+            r.g.done = true;
+            return false;
+        }
+        if (!r.cur.step(tok)) {
+            r.outcome.violated = true;
+            r.g.done = true;
+            return false;
+        }
+        const bool taken = r.g.accept(tok, r.on_token);
+        if (r.cur.closed()) r.outcome.complete = r.g.done = true;
+        return taken;
+    };
+    // The outcome of the constrained request that lane l has finished: the host's walk, and the lane's row as the device left it
+    // (the host's own values where a callback ended the request: the device went on until the host froze the lane).
+    auto report = [&](int l) {
+        Run& r = run[l];
+        if (r.reported) return;
+        r.reported = true;
+        LaneAutomatonSlot& slot = lane_auto_host_->slot[l];
+        hip_check(hipMemcpyAsync(&slot, lane_auto_->slot + l, sizeof(slot), hipMemcpyDeviceToHost, stream_), "D2H lane automaton");
+        hip_check(hipStreamSynchronize(stream_), "sync");
+        const bool pattern = slot.kind == kLaneKindPattern;
+        r.outcome.final_state = r.cur.state();
+        r.outcome.final_depth = r.cur.depth();
+        r.outcome.accepted = r.cur.accepting();
+        r.outcome.violated = r.outcome.violated || (pattern ? slot.crow.violated : slot.grow.violated) != 0;
+        r.outcome.device_state = r.g.cancelled ? r.outcome.final_state : pattern ? slot.crow.state : slot.grow.state;
+        r.outcome.device_depth = r.g.cancelled ? r.outcome.final_depth : pattern ? 0 : slot.grow.depth;
+        if (r.outcome_out) *r.outcome_out = r.outcome;
+    };
+    auto new_cursor = [](const LaneRequest& q) {
+        AutomatonCursor cur;
+        cur.con = q.options.constraint;
+        cur.gram = q.options.grammar;
+        cur.hq = cur.con ? cur.con->dfa().start : 0;
+        return cur;
     };
     // the next waiting request that has anything to generate goes into lane l (false: none is left); its prompt is prefilled
     auto start = [&](int l) {
         Run& r = run[l];
+        report(l);  // (the request the lane leaves, before its slot is rewritten)
         while (next_req < reqs.size()) {
             const size_t i = next_req++;
             const LaneRequest& q = reqs[i];
-            if (!waiting[i].wants_token()) continue;  // nothing to generate
+            if (!waiting[i].wants_token()) {  // nothing to generate: the automaton stays where it starts
+                const AutomatonCursor at = new_cursor(q);
+                if (at && q.options.constraint_outcome) {
+                    ConstraintOutcome o;
+                    o.final_state = o.device_state = at.state();
+                    o.accepted = at.accepting();
+                    *q.options.constraint_outcome = o;
+                }
+                continue;
+            }
             r.req = (int64_t)i;
             r.seen = 0;
             r.g = std::move(waiting[i]);
             r.on_token = nullptr;
             r.sink = q.options.logprobs >= 0 ? q.options.logprob_sink : nullptr;
+            r.cur = new_cursor(q);
+            r.outcome = ConstraintOutcome();
+            r.outcome_out = q.options.constraint_outcome;
+            r.reported = !r.cur;
+            if (automata) {  // the lane's slot: the request's view with its own stop ids, and a fresh row
+                LaneAutomatonSlot& slot = lane_auto_host_->slot[l];
+                std::memset(&slot, 0, sizeof(slot));
+                if (r.cur.con) {
+                    slot.kind = kLaneKindPattern;
+                    slot.cview = r.cur.con->view(r.g.stops);
+                    slot.crow.state = r.cur.hq;
+                } else if (r.cur.gram) {
+                    slot.kind = kLaneKindGrammar;
+                    slot.gview = r.cur.gram->view(r.g.stops);
+                }
+                // (no sync of its own: the stream is in order, the prefill below ends in one, and this host slot is not written
+                // again before report() has synchronised)
+                hip_check(hipMemcpyAsync(lane_auto_->slot + l, &slot, sizeof(slot), hipMemcpyHostToDevice, stream_), "H2D lane automaton");
+            }
             if (on_token) r.on_token = [&on_token, i](uint32_t tok) { return on_token(i, tok); };
             if (shared >= 1) {
                 S.prefill(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
@@ -2501,8 +2646,12 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         // a lane's first token comes from its prefill's logits row: the lane pick on that row alone
         auto first_pick = [&](int l) {
             S.to_device();
-            if (lp) lane_logprobs_enqueue(wide, l, 1, lpk);  // (the lane's count is 0: record 0 of its new request)
-            S.first_pick(l);
+            if (automata) {  // the lane's mask on the prefill's row, the pick, the automaton's first move
+                lane_automaton_pick_enqueue(wide, l, 1, 0, lp, lpk);
+            } else {
+                if (lp) lane_logprobs_enqueue(wide, l, 1, lpk);  // (the lane's count is 0: record 0 of its new request)
+                S.first_pick(l);
+            }
             S.from_device();
         };
         auto drain = [&](size_t steps) {  // step-major, lane order within a step
@@ -2572,12 +2721,14 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             if (!any_running()) break;
             if (dirty) S.to_device();
             // (with records: the chain that has them in it, captured per (set, lanes, width), through the set's own burst)
-            S.burst(n, burst, lp ? lane_logprob_step_graph(wide, n, lpk) : nullptr);
+            // (under automata: the chain with the lane apply and advance around the pick, one per (set, lanes, records))
+            S.burst(n, burst, automata ? lane_automaton_step_graph(wide, n, lp, lpk) : lp ? lane_logprob_step_graph(wide, n, lpk) : nullptr);
             S.from_device();
             for (int l = 0; l < n; ++l)
                 if (run[l].req >= 0) S.len[l] = h.pos[l];
             drain(burst);
         }
+        for (int l = 0; l < n; ++l) report(l);
         return out;
     }
 
@@ -2615,8 +2766,15 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                 int32_t *tok, *distinct;
                 int *counts, *nd;
                 pstate(l, tok, distinct, counts, nd);
-                const bool rec = lp && r.sink, edits = o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0;
-                if (rec) logprob_partial_on(row, 1, nullptr, lpk, LL.scratch, edits ? LL.copy : nullptr);  // ahead of the processors
+                const bool rec = lp && r.sink, edits = o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0 || r.cur;
+                if (rec) logprob_partial_on(row, 1, nullptr, lpk, LL.scratch, edits ? LL.copy : nullptr);  // ahead of the mask and the processors
+                // the lane's mask, through the single-row launchers on the lane's slot of the table
+                if (r.cur.con)
+                    hip_check(launch_constraint_apply(row, (int64_t)vocab, 1, (int)vocab, &lane_auto_->slot[l].cview, &lane_auto_->slot[l].crow, stream_),
+                              "constraint apply");
+                if (r.cur.gram)
+                    hip_check(launch_grammar_apply(row, (int64_t)vocab, 1, (int)vocab, &lane_auto_->slot[l].gview, &lane_auto_->slot[l].grow, stream_),
+                              "grammar apply");
                 if (o.repetition_penalty != 1.0f || o.no_repeat_ngram > 0)
                     hip_check(launch_logits_processors(row, (int)vocab, tok, (int)r.g.all.size(), counts, distinct, nd, o.repetition_penalty,
                                                        o.no_repeat_ngram, stream_), "logits processors");
@@ -2635,11 +2793,21 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                     next = (uint32_t)t;
                     ++tokens_from_candidates_;
                 }
-                if (take(l, next) && rec) {  // the record at the token's index in the request's output, in the lane's own log
+                const bool taken = take(l, next);
+                if (taken && rec) {  // the record at the token's index in the request's output, in the lane's own log
                     hip_check(hipMemsetD32Async((hipDeviceptr_t)lp_tok_, (int)next, 1, stream_), "token");
                     logprob_finish_on(row, 1, nullptr, lpk, LL.scratch, edits ? LL.copy : row, lp_tok_, nullptr, (int)r.g.out->size() - 1, LL.stride,
                                       LL.lp + (size_t)l * LL.stride, LL.ids + (size_t)l * LL.stride * kSlots,
                                       LL.tlp + (size_t)l * LL.stride * kSlots);
+                }
+                if (taken && r.cur) {  // the device's automaton takes the host's choice (fed or not, so that it ends where the host's does)
+                    hip_check(hipMemsetD32Async((hipDeviceptr_t)token_, (int)next, 1, stream_), "token");
+                    if (r.cur.con)
+                        hip_check(launch_constraint_advance(token_, 1, &lane_auto_->slot[l].cview, &lane_auto_->slot[l].crow, nullptr, nullptr, 0, stream_),
+                                  "constraint advance");
+                    else
+                        hip_check(launch_grammar_advance(token_, 1, &lane_auto_->slot[l].gview, &lane_auto_->slot[l].grow, nullptr, nullptr, nullptr, 0,
+                                                         stream_), "grammar advance");
                 }
                 // LastToken::NotFed: a request that has its max_new_tokens leaves the lane at once (asked whatever take() did:
                 // a refused token leaves the run done, which answers no)
@@ -2680,6 +2848,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                 if (h.live[l]) S.len[l] = h.pos[l] + 1;
         }
     }
+    for (int l = 0; l < n; ++l) report(l);
     return out;
 }
 

@@ -65,6 +65,7 @@ struct ConstraintView;  // constraint_kernels.h
 struct ConstraintRow;
 struct GrammarView;  // grammar_kernels.h
 struct GrammarRow;
+struct LaneAutomatonTable;  // lane_constraint_kernels.h
 struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
@@ -305,8 +306,17 @@ public:
     // prefix reuse and the processors / sampling path are generate_lanes'.  The lane caches cost 2 * layers * lanes * rows * kv
     // * 4 bytes with rows = min(context(), lane_context): 64 KB per token per lane on the Llama-1B shape (16 layers, kv 512),
     // 34 GB at 64 lanes of 8 192 rows -- set lane_context.  Throws InvalidConfig (before any GPU work) for lanes outside 0..64, an
-    // empty prompt, a prompt longer than a lane, more than 16 stop ids, a constraint, and -- above 8 lanes -- a quantized or FP8
-    // checkpoint or a geometry the rows route does not take.
+    // empty prompt, a prompt longer than a lane, more than 16 stop ids, and -- above 8 lanes -- a quantized or FP8 checkpoint or a
+    // geometry the rows route does not take.
+    // Constrained requests (options.constraint or options.grammar, per request; generate_lanes takes them too): the lane that takes
+    // the request gets the request's view and a fresh row in its slot of the device's lane automaton table (lane_constraint_kernels.h)
+    // before its first pick.  Greedy requests without processors replay step -> (records' slab pass) -> lane apply -> pick -> lane
+    // advance (-> records' finish) as one captured chain per (set, width, records), and the host walks its own copy of each
+    // request's automaton over the drained tokens, ending the request where generate() would; requests with processors or sampling
+    // are decided lane by lane through the single-row launchers on the lane's slot, the mask ahead of the processors.  The ids and
+    // the outcome (options.constraint_outcome) are generate()'s for that request alone.  A call whose requests carry no automaton
+    // replays the plain chains: nothing of it changes.  InvalidConfig before any GPU work, naming the prompt: both set on one
+    // request, an automaton of another device or vocabulary, more than 16 stop ids, check_states of that request's automaton.
     std::vector<std::vector<uint32_t>> generate_wide(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
                                                      const std::function<bool(size_t, uint32_t)>& on_token = nullptr);
     // Test hooks of the wide route, mirroring the lane hooks (wide_begin takes 9..64 lanes: fewer belong to lanes_begin).
@@ -555,6 +565,12 @@ private:
     void drop_lane_logprob_graphs(bool wide);
     void lane_logprobs_enqueue(bool wide, int first, int rows, int k);
     hipGraphExec_t lane_logprob_step_graph(bool wide, int lanes, int k);
+    // Constrained lanes: the device's automaton table (allocated on first use) with its host copy; the pick of lanes [first, first
+    // + rows) under their automata -- (records' slab pass) -> lane apply -> pick -> lane advance (-> records' finish, on the lanes
+    // and tokens the advance reports) --; the captured chain step -> that, per (set, lanes, no records | k == 1 | k > 1).
+    void ensure_lane_automata();
+    void lane_automaton_pick_enqueue(bool wide, int first, int rows, int advance, bool records, int k);
+    hipGraphExec_t lane_automaton_step_graph(bool wide, int lanes, bool records, int k);
     void enqueue_logprob_partial(int k, bool copy);   // the slab pass over logits_ (copy: the row also goes to lp_copy_)
     // The record of the token at *token: read from lp_copy_ (from_copy) or logits_, written at index (count ? *count : 0) + bias.
     void enqueue_logprob_finish(int k, bool from_copy, const int32_t* token, const int* count, int bias);
@@ -702,6 +718,9 @@ private:
     hipGraphExec_t lp_graphs_[3][2] = {};
     LaneLogs lane_logs_[2];  // [lanes | wide]
     hipGraphExec_t lane_lp_graphs_[2][kLanes + 1] = {}, wide_lp_graphs_[2][kWideLanes + 1] = {};  // [k == 1 | k > 1][lanes]
+    LaneAutomatonTable* lane_auto_ = nullptr;
+    std::unique_ptr<LaneAutomatonTable> lane_auto_host_;
+    hipGraphExec_t lane_auto_graphs_[3][kLanes + 1] = {}, wide_auto_graphs_[3][kWideLanes + 1] = {};  // [no records | k == 1 | k > 1][lanes]
     // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
     // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
     std::vector<float*> lane_k_, lane_v_;

@@ -320,6 +320,63 @@ class HipDecoder:
                         "topk_logprob": tlp[i, :m].copy(), "guard": guard})
         return res
 
+    def generate_wide_constrained(self, prompts: Sequence[Sequence[int]], max_new_tokens, automata=None, top_k: int = -1,
+                                  repetition_penalty: float = 1.0, no_repeat_ngram: int = 0, lanes: int = 0, lane_context: int = 0,
+                                  on_token: Optional[Callable[[int, int], Optional[bool]]] = None):
+        """generate_wide() with an automaton per prompt: automata[i] is None (the plain behaviour), a constraints.Constraint (a
+        pattern) or a constraints.GrammarConstraint; the model's stop ids end a prompt where its automaton accepts.  Returns a list,
+        one dict per prompt: ids, result (constraints.lane_result_dict: kind, final_state, device_state, final_depth,
+        device_depth, accepted, complete, violated) and, with top_k >= 0, logprob [n], topk_ids / topk_logprob [n, top_k] under
+        the raw distribution.  Prompt i's ids and result are those of generate_constrained / generate_grammar / generate on it alone."""
+        from .constraints import GrammarConstraint, lane_result_dict
+        n = len(prompts)
+        if n == 0:
+            return []
+        automata = [None] * n if automata is None else list(automata)
+        if len(automata) != n:
+            raise ValueError("automata: one entry per prompt (None: unconstrained)")
+        new = [int(max_new_tokens)] * n if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
+        if len(new) != n:
+            raise ValueError("max_new_tokens: one value, or one per prompt")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint32).reshape(-1) for p in prompts]), np.uint32)
+        if flat.size == 0:
+            flat = np.zeros(1, np.uint32)
+        offsets = (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(p) for p in prompts])]).tolist())
+        news = (C.c_size_t * n)(*new)
+        cap = max(max(new), 1)
+        k = max(int(top_k), 0)
+        out, lp = np.full((n, cap), 0xFFFFFFFF, np.uint32), np.full((n, cap), np.nan, np.float32)
+        ids, tlp = np.full((n, cap, k), 0xFFFFFFFF, np.uint32), np.full((n, cap, k), np.nan, np.float32)
+        n_out = (C.c_size_t * n)()
+        cons, grams = (C.c_void_p * n)(), (C.c_void_p * n)()
+        for i, a in enumerate(automata):
+            if a is None:
+                continue
+            if isinstance(a, GrammarConstraint):
+                grams[i] = a._h.value
+            else:
+                cons[i] = a._h.value
+        results = (_ffi.KjarniHipLaneAutomatonResult * n)()
+
+        def cb(i, t, _u):
+            r = on_token(int(i), int(t.token_id))
+            return True if r is None else bool(r)
+        fn = _ffi.KjarniBatchTokenCallbackFn(cb) if on_token else _ffi.KjarniBatchTokenCallbackFn()
+        f32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
+        check_error(lib().kjarni_hip_decoder_generate_wide_constrained(self._h, u32(flat), offsets, n, news, repetition_penalty, no_repeat_ngram,
+                                                                       lanes, lane_context, fn, None, u32(out), cap, n_out, int(top_k),
+                                                                       f32(lp) if top_k >= 0 else None, u32(ids) if k else None,
+                                                                       f32(tlp) if k else None, cons, grams, results))
+        res = []
+        for i in range(n):
+            m = min(int(n_out[i]), cap)
+            d = {"ids": out[i, :m].tolist(), "result": lane_result_dict(results[i])}
+            if top_k >= 0:
+                d.update(logprob=lp[i, :m].copy(), topk_ids=ids[i, :m].copy(), topk_logprob=tlp[i, :m].copy())
+            res.append(d)
+        return res
+
     def wide_begin(self, lanes: int = 0, lane_context: int = 0):
         """Test hook: empty wide-lane caches for `lanes` (9..64, 0 = 64) lanes of `lane_context` rows each."""
         check_error(lib().kjarni_hip_decoder_wide_begin(self._h, lanes, lane_context))

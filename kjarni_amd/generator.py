@@ -144,8 +144,8 @@ class Generator:
         """Constrained decoding for generate() / stream(): every later request emits only text that `pattern` matches in full
         (kjarni_amd.constraints has builders: choices, integer, number, json_string, json_object); None restores the plain
         behaviour.  The token table comes from this handle's tokenizer, once per pattern.  While set, requests take the plain
-        loop even when prompt lookup or a draft model is switched on; generate_batch() is not constrained.  Nested or recursive
-        JSON is a grammar: set_grammar."""
+        loop even when prompt lookup or a draft model is switched on; generate_batch() constrains every prompt of the batch on
+        its lane (batch_constraint_result).  Nested or recursive JSON is a grammar: set_grammar."""
         check_error(lib().kjarni_hip_generator_set_constraint(self._handle, pattern.encode("utf-8") if pattern else None))
 
     def constraint_result(self):
@@ -154,6 +154,20 @@ class Generator:
         r = _ffi.KjarniHipConstraintResult()
         check_error(lib().kjarni_hip_generator_constraint_result(self._handle, C.byref(r)))
         return result_dict(r)
+
+    def batch_constraint_result(self, prompt_index: int):
+        """How prompt `prompt_index` of the last generate_batch() ended under the handle's pattern or grammar: kind (0 none, 1
+        pattern, 2 grammar), final_state, final_depth, device_state, device_depth, accepted, complete, violated.  Zeros with
+        kind 0 before a call, after an unconstrained one and for an index the call did not have."""
+        from .constraints import lane_result_dict
+        r = _ffi.KjarniHipLaneAutomatonResult()
+        check_error(lib().kjarni_hip_generator_batch_constraint_result(self._handle, int(prompt_index), C.byref(r)))
+        return lane_result_dict(r)
+
+    def batch_seed(self, prompt_index: int) -> int:
+        """Test hook: the seed of the generator prompt `prompt_index` of the last generate_batch() drew from; seed() with it and
+        generate() of that prompt alone take the same draws."""
+        return int(lib().kjarni_hip_generator_batch_seed(self._handle, int(prompt_index)))
 
     def set_grammar(self, rules):
         """Constrained decoding under a grammar: rules [(name, pattern)] as kjarni_amd.constraints.json_value / json_schema

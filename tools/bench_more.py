@@ -58,6 +58,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
   llm_grammar  (only on request) grammar-constrained decoding (HipDecoder.generate_grammar) against the pattern route and the plain
            loop of the same run, Llama-3.2-1B and gpt2-small shapes, greedy and sampled; json_value on random weights and the device
            object's constructor at V = 128 256 for information.  The lines also go to profiles/llm_grammar_bench.jsonl.
+  llm_wide_constraint  (only on request) constrained decoding in 64 wide lanes (HipDecoder.generate_wide_constrained) against plain
+           generate_wide of the same run, alternated twice: a pattern that masks nothing and the one-rule grammar of the same
+           language in every lane, Llama-3.2-1B and gpt2-small shapes (bf16), 128-token prompts, 128 new tokens, lane_context 512;
+           tokens/s and ms per step of each leg, the spread, the added launches' time per step; json_value at 64 lanes on random
+           weights for information.  The lines also go to profiles/llm_wide_constraint_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1846,6 +1851,101 @@ def main():
         with open(out_path, "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+    if "llm_wide_constraint" in which:
+        # Method (as llm_wide and llm_grammar): one process on one box, every leg warmed first (graph capture, lane caches); plain
+        # generate_wide at 64 lanes -- the parent's route, the yardstick -- alternates twice with generate_wide_constrained under (a)
+        # a pattern that masks nothing ([ -~]* over an all-ASCII table) in every lane and (b) the one-rule grammar of the same
+        # language; the ids are asserted equal to the plain run's.  A decode window is a whole call minus the same call cut after
+        # its first token, so it holds n_new - 1 lock-step steps.  The spread is what the two alternations of one leg differ by;
+        # the per-step cost of the added launches is the difference of a leg's and the plain leg's time per step (a kernel trace of
+        # KJARNI_WIDE_CONSTRAINT_STEPS=N steps of one leg, KJARNI_WIDE_CONSTRAINT_LEG=plain|pattern|grammar, names the kernels).  For
+        # information: json_value at 64 lanes over single-character tokens on random weights (runs may end early).
+        from kjarni_amd import constraints as KC
+        from tests import gpt2_fixture
+        rng = np.random.default_rng(0)
+        n_new, ctx, W = 128, 512, 64
+        trace_steps = int(os.environ.get("KJARNI_WIDE_CONSTRAINT_STEPS", "0"))
+        trace_leg = os.environ.get("KJARNI_WIDE_CONSTRAINT_LEG", "grammar")
+        out_path = os.path.join(ROOT, "profiles", "llm_wide_constraint_bench.jsonl")
+        lines = []
+        med = lambda xs: float(np.median(xs))  # noqa: E731
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def measure(label, dec, vocab, lo, dtype):
+            prompts = [rng.integers(lo, vocab, 128).tolist() for _ in range(W)]
+            table = [("t%d " % i).encode() for i in range(vocab)]
+            con = KC.Constraint(r"[ -~]*", table)
+            gram = KC.GrammarConstraint([("s", r"[ -~]*")], table)
+            ids_of = lambda got: [g["ids"] for g in got]  # noqa: E731
+            legs = {
+                "plain": lambda n: dec.generate_wide(prompts, n, lanes=W, lane_context=ctx),
+                "pattern": lambda n: ids_of(dec.generate_wide_constrained(prompts, n, [con] * W, lanes=W, lane_context=ctx)),
+                "grammar": lambda n: ids_of(dec.generate_wide_constrained(prompts, n, [gram] * W, lanes=W, lane_context=ctx)),
+            }
+            if trace_steps:  # a short run for rocprofv3 --kernel-trace --stats
+                legs[trace_leg](trace_steps + 1)
+                return
+            for fn in legs.values():
+                fn(20)
+            rate, ms, outs = {k: [] for k in legs}, {k: [] for k in legs}, {}
+            for rep in range(2):
+                for k, fn in legs.items():
+                    dt, out = window(lambda: fn(n_new), lambda: fn(1))
+                    assert all(len(o) == n_new for o in out), k
+                    rate[k].append(W * (n_new - 1) / dt)
+                    ms[k].append(dt * 1e3 / (n_new - 1))
+                    outs[k] = out
+            assert outs["plain"] == outs["pattern"] == outs["grammar"]
+            spread = {k: round(abs(v[0] - v[1]) / med(v), 4) for k, v in rate.items()}
+            chars = [bytes([32 + i % 95]) for i in range(vocab)]
+            for i, w in enumerate(("true", "false", "null", "\"a\":", "[1,", "{\"", "\"}", "]]", "},")):
+                chars[100 + i] = w.encode()
+            jv = KC.GrammarConstraint(KC.json_value(), chars)
+            dec.generate_wide_constrained(prompts, 8, [jv] * W, lanes=W, lane_context=ctx)
+            t0 = time.perf_counter()
+            got = dec.generate_wide_constrained(prompts, n_new, [jv] * W, lanes=W, lane_context=ctx)
+            jv_s = time.perf_counter() - t0
+            line = {"metric": f"constrained decoding in 64 wide lanes, {label}", "unit": "pattern-route / plain tokens per second at 64 lanes",
+                    "value": round(med(rate["pattern"]) / med(rate["plain"]), 4), "n_gpus": 1, "dtype": dtype, "data": "synthetic",
+                    "config": {"workload": f"random init, one 128-token prompt per lane, {n_new} generated tokens per lane, lane_context {ctx}; plain "
+                                           "generate_wide, a pattern that masks nothing and the one-rule grammar of the same language in every "
+                                           "lane, alternated twice in one process; ids equal (asserted)", "vocab": vocab, "lanes": W},
+                    "tokens_per_s": {k: {"median": round(med(v), 1), "runs": [round(x, 1) for x in v]} for k, v in rate.items()},
+                    "ms_per_step": {k: {"median": round(med(v), 4), "runs": [round(x, 4) for x in v]} for k, v in ms.items()},
+                    "spread_between_alternations": spread,
+                    "grammar_over_pattern": round(med(rate["grammar"]) / med(rate["pattern"]), 4),
+                    "grammar_over_plain": round(med(rate["grammar"]) / med(rate["plain"]), 4),
+                    "added_launches_us_per_step": {k: round((med(ms[k]) - med(ms["plain"])) * 1e3, 2) for k in ("pattern", "grammar")},
+                    "json_value_random_weights": {"tokens": sum(len(g["ids"]) for g in got), "seconds": round(jv_s, 4),
+                                                  "complete": sum(g["result"]["complete"] for g in got),
+                                                  "violated": sum(g["result"]["violated"] for g in got)},
+                    "weight_bytes": dec.weight_bytes}
+            lines.append(line)
+            emit(line)
+
+        d = os.path.join(tmp, "llama-1b-wide-constraint")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=2048)
+        measure("Llama-3.2-1B shape, bf16 weights", dec, synth.LLAMA_1B["vocab_size"], 1000, "bf16 weights, f32 activations/accumulate/KV")
+        del dec
+        if not trace_steps:  # (the trace run is the Llama shape alone)
+            gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=1024, vocab_size=50257, eos_token_id=None)
+            gd = os.path.join(tmp, "gpt2-small-wide-constraint")
+            gpt2_fixture.gpt2_model(gd, gcfg, seed=0, store_bf16=True, buffers=False, std=0.02)
+            dec = kjarni_amd.HipDecoder(gd)
+            measure("gpt2-small shape, bf16 weights", dec, 50257, 0, "bf16 weights, f32 activations/accumulate/KV")
+            del dec
+            with open(out_path, "w") as f:
+                for line in lines:
+                    f.write(json.dumps(line) + "\n")
 
     if "llm_qwen3" in which:
         from tests import qwen3_fixture
