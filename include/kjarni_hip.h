@@ -895,6 +895,14 @@ KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, const float* hidde
  * prompt GEMM), so logits and cache rows are the reuse-off values inside the decoder's float bar and the ids are the same
  * wherever the two best logits are further apart than that.  A NULL handle is ignored. */
 void kjarni_hip_decoder_set_prefix_reuse(KjarniHipDecoder* decoder, int32_t on);
+/* FP8 checkpoints on the matrix cores (off by default; a no-op on a checkpoint that is not FP8; a NULL handle is ignored).  On:
+ * the prompt projections of up to a few hundred rows multiply the FP8 codes themselves on the bf16 matrix cores
+ * (launch_prefill_gemm_fp8) instead of writing every matrix as f32 first, and the checkpoint is accepted on the wide lanes
+ * (9 .. 64), whose step then runs Q, K, V and the MLP through the same GEMM.  Off: everything enqueued is what it was before the
+ * switch existed, the refusal above 8 lanes included.  Flipping it drops the captured wide-step graphs.
+ * kjarni_hip_decoder_fp8_matrix_cores reads it back (0 for NULL). */
+void kjarni_hip_decoder_set_fp8_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
+int32_t kjarni_hip_decoder_fp8_matrix_cores(const KjarniHipDecoder* decoder);
 /* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
  * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
  * tokens as kept and the rest of the prompt as computed. */
@@ -1173,6 +1181,17 @@ KjarniErrorCode kjarni_hip_attention_route(int64_t batch, int32_t seq_or_max_len
 KjarniErrorCode kjarni_hip_op_prefill_gemm(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* w, int32_t bf16,
                                            const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
                                            int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used, int64_t* scratch_written);
+/* kjarni_hip_op_prefill_gemm_fp8: the same call through launch_prefill_gemm_fp8 -- the weights as FP8 (e4m3fn) codes [n, k], one
+ * byte each, with scale [scale_rows, scale_cols] of shape [1, 1] (per tensor), [n, 1] (per channel) or [ceil(n / 128), k / 128]
+ * (128 x 128 blocks): y = a . (decode(code) * scale)^T (+ bias) (+ r), the codes decoded in the tile loader and multiplied on the
+ * bf16 matrix cores, the scale applied in f32.  Every other argument, the split scratch, *ksplit_used and *scratch_written as in
+ * kjarni_hip_op_prefill_gemm; a guard band lies behind every device buffer and the outputs come back whole.  INVALID_CONFIG, before
+ * any GPU work and with every output untouched: the refusals of kjarni_hip_op_prefill_gemm, a scale shape that fits no kind, a NaN
+ * code (0x7F, 0xFF). */
+KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* codes, const float* scale,
+                                               int32_t scale_rows, int32_t scale_cols, const float* bias, const float* r, int64_t ldr,
+                                               int32_t r_is_y, float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
+                                               int32_t* ksplit_used, int64_t* scratch_written);
 /* kjarni_hip_op_prefill_attention: causal grouped-query attention of `rows` prompt rows at positions base .. base + rows - 1 over
  * key rows 0 .. base + rows - 1 through launch_prefill_attention: query row s sees keys <= base + s.  q [rows, ldq]
  * (heads * head_dim used); k / v: k_floats / v_floats floats, key row t at k + t * ldk, KV head h / kv_group at columns
@@ -1378,6 +1397,9 @@ void kjarni_hip_reranker_answer_rows(const KjarniReranker* reranker, uint64_t* c
 KjarniErrorCode kjarni_hip_chat_set_prefix_reuse(KjarniChat* chat, int32_t on);
 void kjarni_hip_chat_prefix_stats(KjarniChat* chat, uint64_t* reused, uint64_t* computed);
 KjarniErrorCode kjarni_hip_generator_set_prefix_reuse(KjarniGenerator* generator, int32_t on);
+/* kjarni_hip_decoder_set_fp8_matrix_cores on the handle's model. */
+KjarniErrorCode kjarni_hip_chat_set_fp8_matrix_cores(KjarniChat* chat, int32_t on);
+KjarniErrorCode kjarni_hip_generator_set_fp8_matrix_cores(KjarniGenerator* generator, int32_t on);
 void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
 
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */

@@ -569,6 +569,8 @@ SIGNATURES = {
     "kjarni_generator_score_tokens": (c_int32, [c_void_p, c_char_p, c_char_p, c_size_t, POINTER(KjarniTokenScores)]),
     "kjarni_token_scores_free": (None, [POINTER(KjarniTokenScores)]),
     "kjarni_hip_decoder_set_prefix_reuse": (None, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_set_fp8_matrix_cores": (None, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_fp8_matrix_cores": (c_int32, [c_void_p]),
     "kjarni_hip_decoder_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_decoder_resident": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
     "kjarni_hip_decoder_last_logits": (c_int32, [c_void_p, _f32p]),
@@ -612,6 +614,8 @@ SIGNATURES = {
                                               c_int32, _f32p]),
     "kjarni_hip_op_prefill_gemm": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, _f32p, _f32p, c_int64, c_int32, _f32p, c_int64,
                                              _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]),
+    "kjarni_hip_op_prefill_gemm_fp8": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, _f32p, c_int32, c_int32, _f32p, _f32p, c_int64, c_int32,
+                                                 _f32p, c_int64, _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "kjarni_hip_op_prefill_attention": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int64, _f32p, c_int64, c_int64, c_int32,
                                                   c_int32, c_int32, c_int32, _f32p, c_int64, POINTER(c_int32)]),
     "kjarni_hip_op_moe_route": (c_int32, [c_int32, _f32p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), _f32p]),
@@ -724,6 +728,8 @@ SIGNATURES = {
     "kjarni_hip_chat_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_generator_set_prefix_reuse": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_chat_set_fp8_matrix_cores": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_set_fp8_matrix_cores": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_generator_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),
     "kjarni_collect_files": (c_int32, [POINTER(KjarniIndexerConfig), POINTER(c_char_p), c_size_t,

@@ -248,6 +248,11 @@ class Chat:
         conversation then prefills only what the conversation gained since turn N - 1."""
         check_error(lib().kjarni_hip_chat_set_prefix_reuse(self._handle, 1 if on else 0))
 
+    def set_fp8_matrix_cores(self, on: bool):
+        """FP8 checkpoints: multiply the codes themselves on the bf16 matrix cores in the prompt GEMM, and accept the checkpoint on
+        more than 8 lanes.  Off by default; a no-op on a checkpoint that is not FP8."""
+        check_error(lib().kjarni_hip_chat_set_fp8_matrix_cores(self._handle, 1 if on else 0))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose cache rows were kept / computed by the calls that ran with reuse on."""
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -1022,6 +1022,19 @@ KJARNI_EXPORT void kjarni_hip_generator_prefix_stats(KjarniGenerator* gen, uint6
     if (computed) *computed = gen ? gen->inner->model().prefix_computed_tokens() : 0;
 }
 
+// FP8 checkpoints on the matrix cores (LlmModel::set_fp8_matrix_cores) on the handle's model.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_fp8_matrix_cores(KjarniChat* chat, int32_t on)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->model().set_fp8_matrix_cores(on != 0); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_fp8_matrix_cores(KjarniGenerator* gen, int32_t on)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->model().set_fp8_matrix_cores(on != 0); });
+}
+
 KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
 {
     if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;

@@ -1062,6 +1062,17 @@ KJARNI_EXPORT void kjarni_hip_decoder_set_prefix_reuse(KjarniHipDecoder* d, int3
     d->model->set_prefix_reuse(on != 0);
 }
 
+// ---- FP8 checkpoints on the matrix cores (LlmModel::set_fp8_matrix_cores) ------------------------------------------------------
+
+KJARNI_EXPORT void kjarni_hip_decoder_set_fp8_matrix_cores(KjarniHipDecoder* d, int32_t on)
+{
+    if (!d) return;
+    std::lock_guard<std::mutex> lock(d->mu);
+    (void)guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { d->model->set_fp8_matrix_cores(on != 0); });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_fp8_matrix_cores(const KjarniHipDecoder* d) { return d && d->model->fp8_matrix_cores() ? 1 : 0; }
+
 KJARNI_EXPORT void kjarni_hip_decoder_prefix_stats(const KjarniHipDecoder* d, uint64_t* reused, uint64_t* computed)
 {
     if (reused) *reused = d ? d->model->prefix_reused_tokens() : 0;

@@ -52,4 +52,12 @@ hipError_t launch_fp8_proj(const Fp8ProjArgs& a, hipStream_t stream);
 // W dequantized into out [n, k] f32: decode(code) * scale, one f32 product per weight (the prompt route's scratch).
 hipError_t launch_fp8_dequant(const Fp8Mat& W, float* out, hipStream_t stream);
 
+// The prompt GEMM on the codes (fp8_gemm.hip): Y[M, N] = A[M, K] . W^T (+ bias) (+ R), N = W.n, K = W.k, on the bf16 matrix cores --
+// the codes become exact bf16 operands in the tile loader, the f32 activations three exact bf16 pieces, the scale is applied in f32.
+// launch_prefill_gemm's contract (llm_kernels.h): its tile order, its K-slice rule (prefill_gemm_launch_ksplit), its scratch layout
+// and reduce kernel, R may alias Y, silu_gate as there.  Refused (hipErrorInvalidValue): K % 32, lda % 4, A or the codes not 16-byte
+// aligned, block scales with K % 128.
+hipError_t launch_prefill_gemm_fp8(const float* A, int64_t lda, const Fp8Mat& W, const float* bias, const float* R, int64_t ldr, float* Y,
+                                   int64_t ldy, int M, hipStream_t stream, float* split_scratch = nullptr, float* silu_gate = nullptr);
+
 }  // namespace kjarni

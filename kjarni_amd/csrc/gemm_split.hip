@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "bf16_split.h"
 #include "device_utils.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
@@ -32,11 +33,6 @@ constexpr int EPI_STRIDE = 68;     // floats per staged output row (64 + 4), as 
 // operand (layout below).  Not the default: the reference computes in f32, and whether an
 // f32 result assembled from bf16 pieces counts as "the reference's precision" is the integrator's call; non-finite inputs
 // (inf - inf in the split) come out as NaN where the f32 path keeps an infinity.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int SP_BK = 16;                              // K per step: one 32 x 32 x 16 MFMA block
 // LDS rows are 16 bf16 = 32 bytes with NO padding; the two 16-byte halves of a row swap places in rows 8..15 of every 16
 // (half ^ ((row >> 3) & 1)).  A fragment read (16 lanes x 16 bytes: rows r .. r + 15, one logical half) then covers all 64
@@ -48,24 +44,7 @@ constexpr int SP_STAGE = 2 * 3 * SP_PLANE;             // A and W, three planes 
 constexpr int SP_LDS_BYTES = 2 * SP_STAGE * 2;         // two stages: 49 152 bytes
 static_assert(4 * 32 * EPI_STRIDE * 4 <= SP_LDS_BYTES, "four wave-private epilogue regions must fit the operand planes");
 
-__device__ __forceinline__ uint32_t sp_pack(float a, float b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2v{a, b}, bf16x2));  // v_cvt_pk_bf16_f32, round to nearest even
-}
-__device__ __forceinline__ void sp_split(const f32x4 x, u32x2& p1, u32x2& p2, u32x2& p3)
-{
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        const uint32_t a = sp_pack(x0, x1);
-        const float r0 = x0 - __builtin_bit_cast(float, a << 16), r1 = x1 - __builtin_bit_cast(float, a & 0xffff0000u);
-        const uint32_t b = sp_pack(r0, r1);
-        const float s0 = r0 - __builtin_bit_cast(float, b << 16), s1 = r1 - __builtin_bit_cast(float, b & 0xffff0000u);
-        p1[i] = a;
-        p2[i] = b;
-        p3[i] = sp_pack(s0, s1);
-    }
-}
+// (sp_pack / sp_split: bf16_split.h)
 
 // Epilogue through LDS, as gemm_nt_f32_mfma's: the accumulators of a 32-row tile go to a wave-private [32][68] region (the
 // operand planes are free after the barrier), then 16 lanes own a row: 16-byte row-contiguous loads of the residual and

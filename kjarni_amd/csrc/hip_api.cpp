@@ -2845,6 +2845,63 @@ void check_mask_shape(int64_t batch, int32_t seq)
 
 }  // namespace
 
+// launch_prefill_gemm_fp8 on host arrays: kjarni_hip_op_prefill_gemm's arguments with the weights as FP8 codes [n, k] and their
+// scales [scale_rows, scale_cols] (the kind from fp8_scale_kind()).
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* codes,
+                                                             const float* scale, int32_t scale_rows, int32_t scale_cols, const float* bias,
+                                                             const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
+                                                             int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used,
+                                                             int64_t* scratch_written)
+{
+    if (!a || !codes || !scale || !y || !ksplit_used) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (m < 0 || m > 4096 || a_rows < std::max(m, 1) || a_rows > 8192) throw InvalidConfig("m must be 0 .. 4096 and a_rows max(m, 1) .. 8192");
+        if (n < 1 || k < 1 || n > (1 << 17) || k > (1 << 16) || (int64_t)n * k > ((int64_t)1 << 26))
+            throw InvalidConfig("n must be 1 .. 2^17, k 1 .. 2^16, n * k at most 2^26");
+        if (k % 32 || lda % 4) throw InvalidConfig("launch_prefill_gemm_fp8 refuses these arguments: k a multiple of 32, lda a multiple of 4");
+        if (lda < k || ldy < n || std::max(lda, ldy) > (1 << 18)) throw InvalidConfig("lda must cover k and ldy n (at most 2^18)");
+        const bool res = r_is_y || r;
+        const int64_t ldr_ = r_is_y ? ldy : ldr;
+        if (res && (ldr_ < n || ldr_ > (1 << 18))) throw InvalidConfig("ldr must cover n (at most 2^18)");
+        if (gate && (ldy != n || (n & 3))) throw InvalidConfig("launch_prefill_gemm_fp8 refuses these arguments: a gate needs ldy == n and n a multiple of 4");
+        if (split != 0 && split != 1) throw InvalidConfig("split must be 0 or 1");
+        if (scratch_written && !split) throw InvalidConfig("scratch_written without split");
+        const int kind = scale_rows < 1 || scale_cols < 1 ? -1 : fp8_scale_kind(n, k, scale_rows, scale_cols);
+        if (kind < 0)
+            throw InvalidConfig("FP8 prompt GEMM: a scale of shape [" + std::to_string(scale_rows) + ", " + std::to_string(scale_cols) +
+                                "] is neither [1, 1] (per tensor), [n, 1] (per channel) nor [ceil(n / 128), k / 128] (block)");
+        const uint8_t* c = static_cast<const uint8_t*>(codes);
+        for (int64_t i = 0, e = (int64_t)n * k; i < e; ++i)
+            if ((c[i] & 0x7F) == 0x7F) throw InvalidConfig("FP8 prompt GEMM: NaN code at element " + std::to_string(i));
+        use_device(device);
+        const size_t ab = (size_t)a_rows * (size_t)lda * 4, wb = (size_t)n * (size_t)k, yb = (size_t)m * (size_t)ldy * 4;
+        const size_t scb = (size_t)scale_rows * (size_t)scale_cols * 4;
+        const size_t rb = r && !r_is_y ? (size_t)m * (size_t)ldr * 4 : 0, gb = gate ? (size_t)m * (size_t)n * 4 : 0;
+        const size_t sb = split ? prefill_gemm_scratch_floats(m, n) * 4 : 0;
+        BandBuf ad(a, ab, kBandWords, "H2D a"), wd(codes, wb, kBandWords, "H2D codes"), scd(scale, scb, kBandWords, "H2D scales");
+        BandBuf bd(bias, bias ? (size_t)n * 4 : 0, kBandWords, "H2D bias"), rd(rb ? r : nullptr, rb, kBandWords, "H2D r");
+        BandBuf yd(y, yb, kBandWords, "H2D y"), gd(gate, gb, kBandWords, "H2D gate"), sd(nullptr, sb, kBandWords, "scratch");
+        if (sb) hip_check(hipMemset(sd.buf.p, 0xFF, sb), "poison scratch");  // (all-ones words are NaN: a slab the kernels skip would show)
+        Fp8Mat W;
+        W.n = n; W.k = k; W.codes = wd.as<const uint8_t>(); W.scale = scd.as<const float>(); W.kind = kind;
+        const float* bp = bias ? bd.as<const float>() : nullptr;
+        const float* rp = r_is_y ? yd.as<const float>() : (r ? rd.as<const float>() : nullptr);
+        float* sp = split ? sd.as<float>() : nullptr;
+        *ksplit_used = prefill_gemm_launch_ksplit(bp, rp, ldr_, yd.as<const float>(), ldy, m, n, k, sp);
+        launcher_check(launch_prefill_gemm_fp8(ad.as<const float>(), lda, W, bp, rp, ldr_, yd.as<float>(), ldy, m, nullptr, sp,
+                                               gate ? gd.as<float>() : nullptr), "fp8 prefill gemm");
+        hip_check(hipDeviceSynchronize(), "sync");
+        yd.fetch(y, yb, "D2H y");
+        gd.fetch(gate, gb, "D2H gate");
+        sd.fetch(nullptr, 0, "scratch");
+        if (scratch_written) {  // the scratch words that no longer hold the poison
+            std::vector<uint32_t> words(sb / 4);
+            hip_check(hipMemcpy(words.data(), sd.buf.p, sb, hipMemcpyDeviceToHost), "D2H scratch");
+            *scratch_written = (int64_t)(words.size() - (size_t)std::count(words.begin(), words.end(), 0xFFFFFFFFu));
+        }
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mask_lengths(int32_t device, const uint32_t* mask, int64_t batch, int32_t seq, uint32_t* lens_out)
 {
     if (!mask || !lens_out) return KJARNI_ERROR_NULL_POINTER;

@@ -1046,6 +1046,15 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
     // Q8_K and back (the quantization the decode kernels apply), then everything is the f32 route
     int wbu = bf16_ ? 1 : 0;
     bool bf = bf16_;
+    // measured on the 1B shape: 192 tiles (1 536 rows x 2 048 columns) are faster on the 64 x 64 kernel, 224 on the tiles -- with
+    // f32 weights (both kernels on the f32 matrix cores) and again with bf16 weights (both on the bf16 matrix cores: 768 /
+    // 1 024 tokens 8.1 / 9.8 ms at 208 against 9.9 / 11.2 at 96 and 8.8 / 11.2 with no tiles at all)
+    constexpr int min_tiles = 208;
+    const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
+    if (fm && fp8_mc_ && !tiles) {  // the switch: the codes themselves on the bf16 matrix cores, no f32 copy of the matrix
+        hip_check(launch_prefill_gemm_fp8(Ain, lda, *fm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
+        return;
+    }
     if (fm) {  // an FP8 matrix: decode(code) * scale into the f32 scratch, then the f32 route
         hip_check(launch_fp8_dequant(*fm, pw32_, s), what);
         W = pw32_;
@@ -1062,11 +1071,6 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
         wbu = 0;
         bf = false;
     }
-    // measured on the 1B shape: 192 tiles (1 536 rows x 2 048 columns) are faster on the 64 x 64 kernel, 224 on the tiles -- with
-    // f32 weights (both kernels on the f32 matrix cores) and again with bf16 weights (both on the bf16 matrix cores: 768 /
-    // 1 024 tokens 8.1 / 9.8 ms at 208 against 9.9 / 11.2 at 96 and 8.8 / 11.2 with no tiles at all)
-    constexpr int min_tiles = 208;
-    const bool tiles = tile_shapes && m >= kTileRows && (int64_t)((m + 127) / 128) * (N / 128) >= min_tiles;
     if (!tiles) {
         hip_check(launch_prefill_gemm(Ain, lda, W, wbu, bias, R, ldy, Y, ldy, m, N, K, s, psplit_, gate), what);
         if (gelu) hip_check(launch_gelu_tanh(Y, (size_t)m * N, s), what);
@@ -2860,7 +2864,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
 void LlmModel::ensure_wide(int lanes, int lane_context)
 {
     if (lanes <= kLanes || lanes > kWideLanes) throw InvalidConfig("wide lanes must be 9..64 (8 or fewer are the lanes route's)");
-    if (quant_)  // (fp8_ implies quant_)
+    if (quant_ && !fp8_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_: with the switch on, the FP8 prompt GEMM reads the codes)
         throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
                             " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
     const LlmConfig& c = cfg_;
@@ -2926,6 +2930,17 @@ void LlmModel::ensure_wide(int lanes, int lane_context)
     std::memset(wide_host_.get(), 0, sizeof(LlmWideState));
     std::fill(wide_len_, wide_len_ + kWideLanes, 0);
     wide_state_to_device();
+}
+
+void LlmModel::set_fp8_matrix_cores(bool on)
+{
+    if (!fp8_ || on == fp8_mc_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    drop_graphs(wide_graphs_);  // (they hold the route's launches)
+    drop_lane_logprob_graphs(true);
+    wide_lanes_ = 0;  // a wide session ends here: wide_begin() decides again
+    fp8_mc_ = on;
 }
 
 void LlmModel::wide_state_to_device()
@@ -2997,7 +3012,15 @@ void LlmModel::wide_step_enqueue(int n)
         const Layer& L = layers_[li];
         if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, n, H, pn_, s), "ln_1");
         else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, n, H, pn_, s), "rmsnorm 1");
-        prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, wide_qkv_, ldq, ldq, H, nullptr, "q|k|v proj");
+        if (fp8_) {  // three matrices of their own (ensure_wide: only with the switch on), each into its column segment of the rows
+            prompt_proj(n, pn_, H, nullptr, L.bqkv, nullptr, wide_qkv_, ldq, QD, H, nullptr, "q proj", nullptr, false, &L.fq);
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD : nullptr, nullptr, wide_qkv_ + QD, ldq, kv, H, nullptr, "k proj", nullptr, false,
+                        &L.fk);
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, wide_qkv_ + QD + kv, ldq, kv, H, nullptr, "v proj", nullptr,
+                        false, &L.fv);
+        } else {
+            prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, wide_qkv_, ldq, ldq, H, nullptr, "q|k|v proj");
+        }
         if (c.qwen3())
             hip_check(launch_wide_qk_norm_rope_scatter(wide_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, wide_k_[li],
                                                        wide_v_[li], stride, wide_cap_, st, s), "head norm + rotate + scatter");

@@ -150,6 +150,14 @@ public:
     // results are the no-reuse results inside the float bar.  The resident tokens are tracked whether the switch is on or off.
     void set_prefix_reuse(bool on) { prefix_reuse_ = on; }
     bool prefix_reuse() const { return prefix_reuse_; }
+    // ---- FP8 checkpoints on the matrix cores (off by default; a no-op on a checkpoint that is not FP8) --------------------------
+    // On: a prompt projection on the 64 x 64 route multiplies the FP8 codes themselves (launch_prefill_gemm_fp8) instead of
+    // dequantizing the matrix into the f32 scratch first, and ensure_wide() takes the checkpoint: the wide step then writes Q, K
+    // and V from their three matrices into the staging rows' column segments and rows_finish() runs on the same GEMM.  Off:
+    // everything enqueued is what it was before the switch existed.  Flipping it drops the captured wide graphs and ends a wide
+    // session (wide_begin again).
+    void set_fp8_matrix_cores(bool on);
+    bool fp8_matrix_cores() const { return fp8_mc_; }
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
     uint64_t prefix_reused_tokens() const { return prefix_reused_; }
     uint64_t prefix_computed_tokens() const { return prefix_computed_; }
@@ -798,6 +806,7 @@ private:
     // (main K, lane K base, main V, lane V base) per layer that launch_kv_prefix_copy reads (built in ensure_lanes)
     std::vector<uint32_t> resident_;
     bool prefix_reuse_ = false;
+    bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
     LlmKvCopyPair* lane_copy_table_ = nullptr;
 };

@@ -83,6 +83,10 @@ size_t prefill_gemm_scratch_floats(int max_rows, int max_n);
 // launcher's own decision, for callers that report it.
 int prefill_gemm_launch_ksplit(const float* bias, const float* R, int64_t ldr, const float* Y, int64_t ldy, int M, int N, int K,
                                const float* split_scratch);
+// The epilogue of a split launch: Y = the ksplit partial slabs [ksplit][M][N] added in slice order (+ bias) (+ R), or with silu_gate
+// the SwiGLU product into the gate buffer.  For the GEMMs that share the slab layout (launch_prefill_gemm, launch_prefill_gemm_fp8).
+hipError_t launch_prefill_splitk_reduce(const float* partials, int ksplit, const float* bias, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                                        int M, int N, float* silu_gate, hipStream_t stream);
 // bf16 -> f32 copy of n values (n % 8 == 0): long prompts run the f32 tile GEMM (gemm.hip) on a widened weight matrix.
 hipError_t launch_widen_bf16(const void* src, float* dst, size_t n, hipStream_t stream);
 

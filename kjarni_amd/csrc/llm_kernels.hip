@@ -1496,6 +1496,15 @@ int prefill_gemm_launch_ksplit(const float* bias, const float* R, int64_t ldr, c
     return 1;
 }
 
+hipError_t launch_prefill_splitk_reduce(const float* partials, int ksplit, const float* bias, const float* R, int64_t ldr, float* Y, int64_t ldy,
+                                        int M, int N, float* silu_gate, hipStream_t stream)
+{
+    const int64_t total = (int64_t)M * (N / 4);
+    const unsigned blocks = (unsigned)std::min<int64_t>(2048, (total + 255) / 256);
+    hipLaunchKernelGGL(prefill_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, partials, ksplit, bias, R, ldr, Y, ldy, M, N, silu_gate);
+    return hipGetLastError();
+}
+
 hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int bf16, const float* bias, const float* R, int64_t ldr, float* Y,
                                int64_t ldy, int M, int N, int K, hipStream_t stream, float* split_scratch, float* silu_gate)
 {
@@ -1520,10 +1529,7 @@ hipError_t launch_prefill_gemm(const float* A, int64_t lda, const void* W, int b
     }
 #undef KJ_PG
     if (ksplit > 1) {
-        const int64_t total = (int64_t)M * (N / 4);
-        const unsigned blocks = (unsigned)std::min<int64_t>(2048, (total + 255) / 256);
-        hipLaunchKernelGGL(prefill_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, split_scratch, ksplit, bias, R, ldr, Y, ldy, M, N,
-                           silu_gate);
+        return launch_prefill_splitk_reduce(split_scratch, ksplit, bias, R, ldr, Y, ldy, M, N, silu_gate, stream);
     } else if (silu_gate) {
         return launch_swiglu_mul(silu_gate, Y, (size_t)M * N, stream);
     }

@@ -865,6 +865,16 @@ class HipDecoder:
         generate_batch prefills the prefix its prompts share once and copies its rows into the lanes."""
         lib().kjarni_hip_decoder_set_prefix_reuse(self._h, 1 if on else 0)
 
+    # ---- FP8 checkpoints on the matrix cores ----
+    def set_fp8_matrix_cores(self, on: bool):
+        """Off (the default): an FP8 checkpoint's prompt projections dequantize each matrix to f32 first, and more than 8 lanes
+        refuse it.  On: the prompt GEMM multiplies the FP8 codes themselves on the bf16 matrix cores (launch_prefill_gemm_fp8) and
+        generate_wide / the wide hooks accept the checkpoint.  A no-op on a checkpoint that is not FP8."""
+        lib().kjarni_hip_decoder_set_fp8_matrix_cores(self._h, 1 if on else 0)
+
+    def fp8_matrix_cores(self) -> bool:
+        return bool(lib().kjarni_hip_decoder_fp8_matrix_cores(self._h))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
         a, b = C.c_uint64(), C.c_uint64()

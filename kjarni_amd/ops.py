@@ -319,6 +319,33 @@ def prefill_gemm(a, w, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=
     return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
 
 
+def prefill_gemm_fp8(a, codes, scale, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=None, split: bool = True,
+                     want_scratch_written: bool = False, device: int = 0):
+    """launch_prefill_gemm_fp8 on host arrays (kjarni_hip_op_prefill_gemm_fp8): prefill_gemm's arguments with the weights as FP8
+    (e4m3fn) codes [n, k] (uint8) and their scales [scale_rows, scale_cols] (2-D: [1, 1], [n, 1] or [ceil(n / 128), k / 128]).
+    Returns (y, gate or None, ksplit_used[, scratch words written]) -- copies; the arguments stay as they were."""
+    aa = np.ascontiguousarray(a, np.float32)
+    ca = np.ascontiguousarray(codes, np.uint8)
+    sa = np.ascontiguousarray(scale, np.float32)
+    ya = np.array(y, np.float32, order="C")
+    if aa.ndim != 2 or ca.ndim != 2 or sa.ndim != 2 or ya.ndim != 2 or ya.shape[0] != int(m):
+        raise ValueError("a: [a_rows, lda]; codes: [n, k]; scale: [scale_rows, scale_cols]; y: [m, ldy]")
+    n, k = ca.shape
+    ba = _proj_vector(bias, n, "bias")
+    ra = None if r is None else np.ascontiguousarray(r, np.float32)
+    if ra is not None and (ra.ndim != 2 or ra.shape[0] != int(m)):
+        raise ValueError("r: [m, ldr]")
+    ga = None if gate is None else np.array(gate, np.float32, order="C")
+    if ga is not None and ga.shape != (int(m), n):
+        raise ValueError("gate: [m, n]")
+    used, written = C.c_int32(-1), C.c_int64(-1)
+    check_error(lib().kjarni_hip_op_prefill_gemm_fp8(device, _f(aa), aa.shape[1], aa.shape[0], ca.ctypes.data_as(C.c_void_p), _f(sa), sa.shape[0],
+                                                     sa.shape[1], _f(ba), _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y)), _f(ya),
+                                                     ya.shape[1], _f(ga), int(m), n, k, int(bool(split)), C.byref(used),
+                                                     C.byref(written) if want_scratch_written else None))
+    return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
+
+
 # ---- the dense (f32 / bf16) decode-step projections, alone ----
 GEMV_STREAM, GEMV_SPLITK, GEMV_ONE, GEMV_GENERIC = 0, 1, 2, 3
 QKV_PAIR, QKV_STREAM, QKV_STREAM_EMBED = 0, 1, 2

@@ -63,6 +63,11 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            language in every lane, Llama-3.2-1B and gpt2-small shapes (bf16), 128-token prompts, 128 new tokens, lane_context 512;
            tokens/s and ms per step of each leg, the spread, the added launches' time per step; json_value at 64 lanes on random
            weights for information.  The lines also go to profiles/llm_wide_constraint_bench.jsonl.
+  llm_wide_fp8  (only on request) FP8 checkpoints on the matrix cores (HipDecoder.set_fp8_matrix_cores): generate_wide at 16 / 32 / 64
+           lanes with the switch on against FP8 generate_batch at 8 lanes and against a bf16 load of the same shape at the same
+           widths, and the prompt's time at 128 / 384 tokens with the switch off, on and for bf16; Llama-3.2-1B shape (per-channel
+           scales) and Qwen3-0.6B shape (block scales), every leg twice, best of two.  The lines also go to
+           profiles/llm_wide_fp8_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -987,6 +992,97 @@ def main():
             dec = kjarni_amd.HipDecoder(gd)
             measure_wide("gpt2-small shape, bf16 weights", dec, gprompts, "bf16 weights, f32 activations/accumulate/KV")
             del dec
+
+    if "llm_wide_fp8" in which:
+        # FP8 checkpoints on the matrix cores (HipDecoder.set_fp8_matrix_cores).  Method (as llm_wide): one process on one box, every
+        # leg warmed first, every leg twice, best of two; a decode window is a whole call minus the same call cut after its first
+        # token.  Per shape -- Llama-3.2-1B with per-channel scales, Qwen3-0.6B with 128 x 128 block scales, random codes of
+        # tests/fp8_fixture.py -- FP8 generate_batch at 8 lanes (the switch off: all an FP8 checkpoint could do before), FP8
+        # generate_wide at 16 / 32 / 64 with the switch on, a bf16 load of the same shape at the same widths; and the prompt's
+        # time at 128 and 384 tokens with the switch off, on, and for bf16 (median of 5 forward() calls that end in a synchronise).
+        from tests import fp8_fixture, qwen3_fixture
+        rng = np.random.default_rng(0)
+        n_new, ctx = 64, 512
+        out_path = os.path.join(ROOT, "profiles", "llm_wide_fp8_bench.jsonl")
+        lines = []
+
+        def window(fn_full, fn_first):
+            t0 = time.perf_counter()
+            fn_first()
+            t1 = time.perf_counter()
+            out = fn_full()
+            t2 = time.perf_counter()
+            return (t2 - t1) - (t1 - t0), out
+
+        def wide_legs(dec, prompts, names):
+            legs = {"lanes-8": (8, lambda n: dec.generate_batch(prompts[:8], n, lanes=8, lane_context=ctx))}
+            for w in (16, 32, 64):
+                legs[f"wide-{w}"] = (w, (lambda w: lambda n: dec.generate_wide(prompts[:w], n, lanes=w, lane_context=ctx))(w))
+            legs = {k: v for k, v in legs.items() if k in names}
+            for _, fn in legs.values():
+                fn(12)
+            rows = {}
+            for rep in range(2):
+                for name, (width, fn) in legs.items():
+                    dt, outs = window(lambda: fn(n_new), lambda: fn(1))
+                    assert all(len(o) == n_new for o in outs)
+                    rows.setdefault(name, []).append({"tokens_per_s": round(width * (n_new - 1) / dt, 1), "ms_per_step": round(dt * 1e3 / (n_new - 1), 4)})
+            return {k: max(v, key=lambda r: r["tokens_per_s"]) for k, v in rows.items()}
+
+        def prompt_ms(dec, ids):
+            ts = []
+            for _ in range(6):
+                dec.reset()
+                t0 = time.perf_counter()
+                dec.forward(ids, fetch=False)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            return round(float(np.median(ts[1:])), 3)
+
+        def shape(label, fdir, bdir, vocab_lo, vocab_hi):
+            prompts = [rng.integers(vocab_lo, vocab_hi, 128).tolist() for _ in range(64)]
+            long_ids = {n: rng.integers(vocab_lo, vocab_hi, n).tolist() for n in (128, 384)}
+            fdec = kjarni_amd.HipDecoder(fdir, max_context=2048)
+            off = wide_legs(fdec, prompts, ("lanes-8",))
+            p_off = {n: prompt_ms(fdec, ids) for n, ids in long_ids.items()}
+            fdec.set_fp8_matrix_cores(True)
+            on = wide_legs(fdec, prompts, ("lanes-8", "wide-16", "wide-32", "wide-64"))
+            p_on = {n: prompt_ms(fdec, ids) for n, ids in long_ids.items()}
+            fbytes = fdec.weight_bytes
+            del fdec
+            bdec = kjarni_amd.HipDecoder(bdir, max_context=2048)
+            bf = wide_legs(bdec, prompts, ("lanes-8", "wide-16", "wide-32", "wide-64"))
+            p_bf = {n: prompt_ms(bdec, ids) for n, ids in long_ids.items()}
+            bbytes = bdec.weight_bytes
+            del bdec
+            wides = ("wide-16", "wide-32", "wide-64")
+            line = {"metric": f"aggregate tokens/sec greedy decode in wide lanes, {label}, FP8 e4m3 weights on the bf16 matrix cores",
+                    "unit": "tokens/s", "value": on["wide-64"]["tokens_per_s"], "n_gpus": 1, "data": "synthetic",
+                    "dtype": "F8_E4M3 layer weights + f32 scales, bf16 table / head, f32 activations/accumulate/KV",
+                    "config": {"workload": f"{label}, random codes, one 128-token prompt per lane, {n_new} generated tokens per lane, lane_context "
+                                           f"{ctx}; every leg twice in one process, best of two"},
+                    "fp8_switch_off": off, "fp8_switch_on": on, "bf16_same_shape": bf,
+                    "x_fp8_lanes_8": {k: round(on[k]["tokens_per_s"] / off["lanes-8"]["tokens_per_s"], 3) for k in wides},
+                    "x_bf16_same_width": {k: round(on[k]["tokens_per_s"] / bf[k]["tokens_per_s"], 3) for k in wides},
+                    "prompt_ms": {"fp8_switch_off": p_off, "fp8_switch_on": p_on, "bf16": p_bf},
+                    "prompt_x_switch_off": {n: round(p_on[n] / p_off[n], 3) for n in p_on},
+                    "prompt_x_bf16": {n: round(p_on[n] / p_bf[n], 3) for n in p_on},
+                    "weight_bytes": {"fp8": fbytes, "bf16": bbytes}}
+            emit(line)
+            lines.append(line)
+
+        fcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=synth.LLAMA_1B["vocab_size"] + 1)
+        fdir, bdir = os.path.join(tmp, "llama-1b-fp8-wide"), os.path.join(tmp, "llama-1b-bf16-wide")
+        fp8_fixture.fp8_model(fdir, fcfg, "channel", seed=0, keep_hf=False)
+        synth.llm_model(bdir, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        shape("Llama-3.2-1B shape, per-channel scales", fdir, bdir, 1000, 100000)
+        q3 = dict(fp8_fixture.QWEN3_06B, max_position_embeddings=4096, eos_token_id=fp8_fixture.QWEN3_06B["vocab_size"] + 1)
+        fdir, bdir = os.path.join(tmp, "qwen3-06b-fp8-wide"), os.path.join(tmp, "qwen3-06b-bf16-wide")
+        fp8_fixture.fp8_model(fdir, q3, "block", seed=0, keep_hf=False)
+        qwen3_fixture.qwen3_model(bdir, q3, seed=0, store_bf16=True)
+        shape("Qwen3-0.6B shape, 128 x 128 block scales", fdir, bdir, 1000, 100000)
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
 
     if "llm_lookup" in which:
         # Method (measuring guide, section 5; as llm_lanes): one process on one box; the plain step graph, the verify hook at
