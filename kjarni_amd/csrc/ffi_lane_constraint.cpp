@@ -174,14 +174,9 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lane_automaton_pick(int32_t device, 
         hd.put(history, hb, "H2D history");
         dt.put(table.data(), sizeof(LaneAutomatonTable), "H2D table");
         hip_check(hipMemset(best.p, 0, kMaxWideLanes * sizeof(unsigned long long)), "memset");
-        if (wide)
-            hip_check(launch_wide_automaton_pick(dl.as<float>(), ld, vocab, lanes, first_lane, best.as<unsigned long long>(), sd.as<LlmWideState>(),
-                                                 hd.as<int32_t>(), hist_stride, capacity, advance ? 1 : 0, dt.as<LaneAutomatonTable>(), nullptr),
-                      "wide automaton pick");
-        else
-            hip_check(launch_lane_automaton_pick(dl.as<float>(), ld, vocab, lanes, first_lane, best.as<unsigned long long>(), sd.as<LlmLaneState>(),
-                                                 hd.as<int32_t>(), hist_stride, capacity, advance ? 1 : 0, dt.as<LaneAutomatonTable>(), nullptr),
-                      "lane automaton pick");
+        hip_check(launch_lane_automaton_pick(dl.as<float>(), ld, vocab, lanes, first_lane, best.as<unsigned long long>(),
+                                             LaneStateRef::at(sd.p, set_lanes), hd.as<int32_t>(), hist_stride, capacity, advance ? 1 : 0,
+                                             dt.as<LaneAutomatonTable>(), nullptr), wide ? "wide automaton pick" : "lane automaton pick");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         dl.check("logits"); sd.check("lane state"); hd.check("lane history"); best.check("pick scratch"); dt.check("lane automaton table");
         unsigned long long b[kMaxWideLanes];

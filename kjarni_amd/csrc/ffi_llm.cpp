@@ -289,7 +289,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_begin(KjarniHipDecoder* d,
         std::lock_guard<std::mutex> lock(d->mu);
         if (lanes != 0 && (lanes <= LlmModel::kLanes || lanes > LlmModel::kWideLanes))
             throw InvalidConfig("wide lanes must be 9..64 (0 = 64); 8 or fewer belong to lanes_begin");
-        d->model->wide_begin(lanes, lane_context);
+        d->model->lanes_begin(LlmModel::Bank::Wide, lanes, lane_context);
     });
 }
 
@@ -298,7 +298,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_prefill(KjarniHipDecoder* 
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->wide_prefill(lane, ids, n);
+        d->model->lane_prefill(LlmModel::Bank::Wide, lane, ids, n);
     });
 }
 
@@ -308,7 +308,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_prefill_shared(KjarniHipDe
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->wide_prefill_shared(lane, shared, ids, n);  // ranges checked before any GPU work
+        d->model->lane_prefill_shared(LlmModel::Bank::Wide, lane, shared, ids, n);  // ranges checked before any GPU work
     });
 }
 
@@ -318,7 +318,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_step(KjarniHipDecoder* d, 
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->wide_step(ids, live, hidden_out, logits_out);
+        d->model->lanes_step(LlmModel::Bank::Wide, ids, live, hidden_out, logits_out);
     });
 }
 
@@ -327,7 +327,7 @@ KJARNI_EXPORT int32_t kjarni_hip_decoder_wide_cache_len(const KjarniHipDecoder* 
     if (!d) return -1;
     std::lock_guard<std::mutex> lock(d->mu);
     try {
-        return d->model->wide_cache_len(lane);
+        return d->model->lane_cache_len(LlmModel::Bank::Wide, lane);
     } catch (const std::exception& e) {
         set_last_error(e.what());
         return -1;
@@ -338,7 +338,7 @@ KJARNI_EXPORT int32_t kjarni_hip_decoder_wide_capacity(const KjarniHipDecoder* d
 {
     if (!d) return 0;
     std::lock_guard<std::mutex> lock(d->mu);
-    return d->model->wide_capacity();
+    return d->model->lane_capacity(LlmModel::Bank::Wide);
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_kv_rows(const KjarniHipDecoder* d, int32_t lane, int32_t layer, int32_t first, int32_t rows,
@@ -347,7 +347,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_wide_kv_rows(const KjarniHipDec
     if (!d || !k_out || !v_out) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->wide_kv_rows(lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
+        d->model->lane_kv_rows(LlmModel::Bank::Wide, lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
     });
 }
 
@@ -357,7 +357,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lanes_begin(KjarniHipDecoder* d
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
         if (lanes < 0 || lanes > LlmModel::kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
-        d->model->lanes_begin(lanes, lane_context);
+        d->model->lanes_begin(LlmModel::Bank::Lanes, lanes, lane_context);
     });
 }
 
@@ -366,7 +366,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_prefill(KjarniHipDecoder* 
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->lane_prefill(lane, ids, n);
+        d->model->lane_prefill(LlmModel::Bank::Lanes, lane, ids, n);
     });
 }
 
@@ -376,7 +376,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lanes_step(KjarniHipDecoder* d,
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->lanes_step(ids, live, hidden_out, logits_out);
+        d->model->lanes_step(LlmModel::Bank::Lanes, ids, live, hidden_out, logits_out);
     });
 }
 
@@ -385,7 +385,7 @@ KJARNI_EXPORT int32_t kjarni_hip_decoder_lane_cache_len(const KjarniHipDecoder* 
     if (!d) return -1;
     std::lock_guard<std::mutex> lock(d->mu);
     try {
-        return d->model->lane_cache_len(lane);
+        return d->model->lane_cache_len(LlmModel::Bank::Lanes, lane);
     } catch (const std::exception& e) {
         set_last_error(e.what());
         return -1;
@@ -396,7 +396,7 @@ KJARNI_EXPORT int32_t kjarni_hip_decoder_lane_capacity(const KjarniHipDecoder* d
 {
     if (!d) return 0;
     std::lock_guard<std::mutex> lock(d->mu);
-    return d->model->lane_capacity();
+    return d->model->lane_capacity(LlmModel::Bank::Lanes);
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_kv_rows(const KjarniHipDecoder* d, int32_t lane, int32_t layer, int32_t first, int32_t rows,
@@ -405,7 +405,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_kv_rows(const KjarniHipDec
     if (!d || !k_out || !v_out) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->lane_kv_rows(lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
+        d->model->lane_kv_rows(LlmModel::Bank::Lanes, lane, layer, first, rows, k_out, v_out);  // range checked before anything is copied
     });
 }
 
@@ -1137,7 +1137,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_lane_prefill_shared(KjarniHipDe
     if (!d || !ids) return KJARNI_ERROR_NULL_POINTER;
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         std::lock_guard<std::mutex> lock(d->mu);
-        d->model->lane_prefill_shared(lane, shared, ids, n);  // ranges checked before any GPU work
+        d->model->lane_prefill_shared(LlmModel::Bank::Lanes, lane, shared, ids, n);  // ranges checked before any GPU work
     });
 }
 

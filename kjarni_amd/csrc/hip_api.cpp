@@ -2380,9 +2380,10 @@ static_assert(sizeof(KjarniHipWideState) == sizeof(LlmWideState) && KJARNI_HIP_W
 
 KJARNI_EXPORT size_t kjarni_hip_wide_state_size(void) { return sizeof(LlmWideState); }
 
-// ONE call of launch_wide_rope_scatter (gamma_q / gamma_k NULL) or launch_wide_qk_norm_rope_scatter (both given) on host
-// arrays: qkv [lanes, ld] and k_cache / v_cache [lanes, lane_stride] are read, run and written back whole, each with a guard
-// band behind it, so a caller can check what the call left untouched.  pos / live [lanes]; cos_t / sin_t [table_rows, head_dim / 2].
+// ONE call of launch_lane_rope_scatter (gamma_q / gamma_k NULL) or launch_lane_qk_norm_rope_scatter (both given) over the
+// 64-lane state layout on host arrays: qkv [lanes, ld] and k_cache / v_cache [lanes, lane_stride] are read, run and written back
+// whole, each with a guard band behind it, so a caller can check what the call left untouched.  pos / live [lanes]; cos_t /
+// sin_t [table_rows, head_dim / 2].
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, float* qkv, int64_t ld, int32_t lanes, int32_t n_heads,
                                                               int32_t n_kv_heads, int32_t head_dim, const float* gamma_q, const float* gamma_k,
                                                               float eps, const float* cos_t, const float* sin_t, int32_t table_rows,
@@ -2420,14 +2421,14 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, fl
         hip_check(hipMemcpy(qd.buf.p, qkv, qb, hipMemcpyHostToDevice), "H2D qkv");
         hip_check(hipMemcpy(kd.buf.p, k_cache, cb, hipMemcpyHostToDevice), "H2D k_cache");
         hip_check(hipMemcpy(vd.buf.p, v_cache, cb, hipMemcpyHostToDevice), "H2D v_cache");
-        const LlmWideState* ds = static_cast<const LlmWideState*>(sd->p);
+        const LaneStateRef ds(static_cast<LlmWideState*>(sd->p));
         if (gamma_q)
-            launcher_check(launch_wide_qk_norm_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(gq->p),
+            launcher_check(launch_lane_qk_norm_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(gq->p),
                                                             static_cast<const float*>(gk->p), eps, static_cast<const float*>(cd->p),
                                                             static_cast<const float*>(snd->p), kd.as<float>(), vd.as<float>(), lane_stride, capacity,
                                                             ds, nullptr), "wide head norm + rotate + scatter");
         else
-            launcher_check(launch_wide_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(cd->p),
+            launcher_check(launch_lane_rope_scatter(qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(cd->p),
                                                     static_cast<const float*>(snd->p), kd.as<float>(), vd.as<float>(), lane_stride, capacity, ds,
                                                     rotate ? 1 : 0, nullptr), "wide rotate + scatter");
         hip_check(hipDeviceSynchronize(), "sync");
@@ -2438,8 +2439,9 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, fl
     });
 }
 
-// ONE call of launch_wide_pick on host arrays: logits [first_lane + lanes, ld], the state and history [64, hist_stride] read,
-// picked over lanes [first_lane, first_lane + lanes) and written back whole; the scratch must come back zeroed.
+// ONE call of launch_lane_pick over the 64-lane state layout on host arrays: logits [first_lane + lanes, ld], the state and
+// history [64, hist_stride] read, picked over lanes [first_lane, first_lane + lanes) and written back whole; the scratch must
+// come back zeroed.
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_pick(int32_t device, const float* logits, int64_t ld, int32_t vocab, int32_t lanes,
                                                       int32_t first_lane, KjarniHipWideState* state, int32_t* history, int32_t hist_stride,
                                                       int32_t capacity, int32_t advance)
@@ -2461,7 +2463,7 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_pick(int32_t device, const floa
         hip_check(hipMemcpy(sd.buf.p, state, sizeof(LlmWideState), hipMemcpyHostToDevice), "H2D state");
         hip_check(hipMemcpy(hd.buf.p, history, hb, hipMemcpyHostToDevice), "H2D history");
         hip_check(hipMemset(best.buf.p, 0, kMaxWideLanes * sizeof(unsigned long long)), "memset");
-        launcher_check(launch_wide_pick(static_cast<const float*>(dl->p), ld, vocab, lanes, first_lane, best.as<unsigned long long>(),
+        launcher_check(launch_lane_pick(static_cast<const float*>(dl->p), ld, vocab, lanes, first_lane, best.as<unsigned long long>(),
                                         sd.as<LlmWideState>(), hd.as<int32_t>(), hist_stride, capacity, advance ? 1 : 0, nullptr), "wide pick");
         hip_check(hipDeviceSynchronize(), "sync");
         sd.check("wide state"); hd.check("wide history"); best.check("wide pick scratch");

@@ -54,12 +54,9 @@ hipError_t launch_lane_automaton_apply(float* logits, int64_t ld, int vocab, int
 // Behind a pick over the same lanes: live / count are the lane state's arrays, history [., hist_stride] the pick's.
 hipError_t launch_lane_automaton_advance(LaneAutomatonTable* table, int lanes, int first_lane, int32_t* live, const int32_t* count,
                                          const int32_t* history, int hist_stride, hipStream_t stream);
-// launch_lane_pick / launch_wide_pick, then the advance: the constrained pick of either lane set.
+// launch_lane_pick, then the advance: the constrained pick of either state layout.
 hipError_t launch_lane_automaton_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                                      LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance,
-                                      LaneAutomatonTable* table, hipStream_t stream);
-hipError_t launch_wide_automaton_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                                      LlmWideState* state, int32_t* history, int hist_stride, int capacity, int advance,
+                                      LaneStateRef state, int32_t* history, int hist_stride, int capacity, int advance,
                                       LaneAutomatonTable* table, hipStream_t stream);
 
 }  // namespace kjarni

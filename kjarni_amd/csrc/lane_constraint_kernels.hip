@@ -270,25 +270,13 @@ hipError_t launch_lane_automaton_advance(LaneAutomatonTable* table, int lanes, i
 }
 
 hipError_t launch_lane_automaton_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                                      LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance,
+                                      LaneStateRef state, int32_t* history, int hist_stride, int capacity, int advance,
                                       LaneAutomatonTable* table, hipStream_t stream)
 {
-    if (lanes <= 0) return hipSuccess;
-    if (first_lane < 0 || first_lane + lanes > kMaxLanes || vocab < 1 || hist_stride < 1) return hipErrorInvalidValue;
+    if (lanes <= 0) return hipSuccess;  // (the range, vocab and hist_stride are launch_lane_pick's refusals)
     const hipError_t e = launch_lane_pick(logits, ld, vocab, lanes, first_lane, best_scratch, state, history, hist_stride, capacity, advance, stream);
     if (e != hipSuccess) return e;
-    return launch_lane_automaton_advance(table, lanes, first_lane, state->live, state->count, history, hist_stride, stream);
-}
-
-hipError_t launch_wide_automaton_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                                      LlmWideState* state, int32_t* history, int hist_stride, int capacity, int advance,
-                                      LaneAutomatonTable* table, hipStream_t stream)
-{
-    if (lanes <= 0) return hipSuccess;
-    if (first_lane < 0 || first_lane + lanes > kMaxWideLanes || vocab < 1 || hist_stride < 1) return hipErrorInvalidValue;
-    const hipError_t e = launch_wide_pick(logits, ld, vocab, lanes, first_lane, best_scratch, state, history, hist_stride, capacity, advance, stream);
-    if (e != hipSuccess) return e;
-    return launch_lane_automaton_advance(table, lanes, first_lane, state->live, state->count, history, hist_stride, stream);
+    return launch_lane_automaton_advance(table, lanes, first_lane, state.live, state.count, history, hist_stride, stream);
 }
 
 }  // namespace kjarni

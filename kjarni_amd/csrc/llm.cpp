@@ -250,10 +250,8 @@ LlmModel::~LlmModel()
     for (auto& kind : lp_graphs_)
         for (hipGraphExec_t& g : kind)
             if (g) (void)hipGraphExecDestroy(g);
-    drop_graphs(lane_graphs_);
-    drop_graphs(wide_graphs_);
-    drop_lane_logprob_graphs(false);
-    drop_lane_logprob_graphs(true);
+    drop_lane_graphs(lane_bank_);
+    drop_lane_graphs(wide_bank_);
     drop_graphs(lookup_graphs_);
     drop_graphs(lookup_sampled_graphs_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -1497,25 +1495,25 @@ void LlmModel::enqueue_logprob_finish(int k, bool from_copy, const int32_t* toke
 }
 
 // ---- lanes ----
-void LlmModel::drop_lane_logprob_graphs(bool wide)
+void LlmModel::drop_lane_record_graphs(LaneBank& b)
 {
-    for (int v = 0; v < 2; ++v) {
-        if (wide) drop_graphs(wide_lp_graphs_[v]);
-        else drop_graphs(lane_lp_graphs_[v]);
-    }
-    for (int v = 0; v < 3; ++v) {  // (the constrained chains hold the same lane buffers and capacity: they go where these go)
-        if (wide) drop_graphs(wide_auto_graphs_[v]);
-        else drop_graphs(lane_auto_graphs_[v]);
-    }
+    for (auto& g : b.lp_graphs) drop_graphs(g);
+    for (auto& g : b.auto_graphs) drop_graphs(g);  // (the constrained chains hold the same lane buffers and capacity: they go where these go)
 }
 
-void LlmModel::ensure_lane_logprobs(bool wide)
+void LlmModel::drop_lane_graphs(LaneBank& b)
 {
-    LaneLogs& L = lane_logs_[wide ? 1 : 0];
-    const int rows = wide ? kWideLanes : kLanes, stride = wide ? wide_hist_stride_ : lane_hist_stride_;
+    drop_graphs(b.graphs);
+    drop_lane_record_graphs(b);
+}
+
+void LlmModel::ensure_lane_logprobs(LaneBank& b)
+{
+    LaneLogs& L = b.logs;
+    const int rows = b.max_lanes, stride = b.hist_stride;
     if (L.block && L.stride == stride) return;
     hip_check(hipStreamSynchronize(stream_), "sync");
-    drop_lane_logprob_graphs(wide);
+    drop_lane_record_graphs(b);
     constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
     auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
     const size_t one = pad((size_t)rows * stride), many = pad((size_t)rows * stride * S), row = pad((size_t)cfg_.vocab);
@@ -1532,30 +1530,26 @@ void LlmModel::ensure_lane_logprobs(bool wide)
     L.stride = stride;
 }
 
-void LlmModel::lane_logprobs_enqueue(bool wide, int first, int rows, int k)
+void LlmModel::lane_logprobs_enqueue(LaneBank& b, int first, int rows, int k)
 {
-    const LaneLogs& L = lane_logs_[wide ? 1 : 0];
+    const LaneLogs& L = b.logs;
     constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
-    const float* logits = (wide ? wide_logits_ : lane_logits_) + (size_t)first * cfg_.vocab;
-    const int32_t* live = (wide ? wide_state_->live : lane_state_->live) + first;  // (addresses in device memory: nothing is read here)
-    const int* count = (wide ? wide_state_->count : lane_state_->count) + first;
+    const float* logits = b.logits + (size_t)first * cfg_.vocab;
+    const int32_t* live = b.dev.live + first;
+    const int* count = b.dev.count + first;
     logprob_partial_on(logits, rows, live, k, L.scratch, nullptr);
     logprob_finish_on(logits, rows, live, k, L.scratch, logits, nullptr, count, 0, L.stride, L.lp + (size_t)first * L.stride,
                       L.ids + (size_t)first * L.stride * S, L.tlp + (size_t)first * L.stride * S);
 }
 
-hipGraphExec_t LlmModel::lane_logprob_step_graph(bool wide, int n, int k)
+hipGraphExec_t LlmModel::lane_logprob_step_graph(LaneBank& b, int n, int k)
 {
-    hipGraphExec_t& g = wide ? wide_lp_graphs_[k > 1 ? 1 : 0][n] : lane_lp_graphs_[k > 1 ? 1 : 0][n];
+    hipGraphExec_t& g = b.lp_graphs[k > 1 ? 1 : 0][n];
     if (g) return g;
     return g = capture_graph(stream_, [&] {
-        if (wide) wide_step_enqueue(n);
-        else lane_step(n);
-        lane_logprobs_enqueue(wide, 0, n, k);  // ahead of the pick: it reads the lanes' flags and counts as the step found them
-        if (wide) wide_pick_enqueue(n, 0, 1);
-        else
-            hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_,
-                                       1, stream_), "lane pick");
+        lane_step_enqueue(b, n);
+        lane_logprobs_enqueue(b, 0, n, k);  // ahead of the pick: it reads the lanes' flags and counts as the step found them
+        lane_pick_enqueue(b, n, 0, 1);
     });
 }
 
@@ -1569,22 +1563,18 @@ void LlmModel::ensure_lane_automata()
     hip_check(hipMemcpy(lane_auto_, lane_auto_host_.get(), sizeof(LaneAutomatonTable), hipMemcpyHostToDevice), "H2D lane automata");
 }
 
-void LlmModel::lane_automaton_pick_enqueue(bool wide, int first, int rows, int advance, bool records, int k)
+void LlmModel::lane_automaton_pick_enqueue(LaneBank& b, int first, int rows, int advance, bool records, int k)
 {
-    const LaneLogs& L = lane_logs_[wide ? 1 : 0];
+    const LaneLogs& L = b.logs;
     constexpr size_t S = KJARNI_SCORE_TOPK_MAX;
-    float* logits = wide ? wide_logits_ : lane_logits_;
+    float* logits = b.logits;
     const float* part = logits + (size_t)first * cfg_.vocab;
-    int32_t* live = wide ? wide_state_->live : lane_state_->live;  // (addresses in device memory: nothing is read here)
-    const int* count = wide ? wide_state_->count : lane_state_->count;
+    int32_t* live = b.dev.live;
+    const int* count = b.dev.count;
     if (records) logprob_partial_on(part, rows, live + first, k, L.scratch, nullptr);  // the raw rows, ahead of the mask
     hip_check(launch_lane_automaton_apply(logits, cfg_.vocab, cfg_.vocab, rows, first, lane_auto_, live, stream_), "lane automaton apply");
-    if (wide)
-        hip_check(launch_wide_automaton_pick(wide_logits_, cfg_.vocab, cfg_.vocab, rows, first, wide_best_, wide_state_, wide_hist_, wide_hist_stride_,
-                                             wide_cap_, advance, lane_auto_, stream_), "wide automaton pick");
-    else
-        hip_check(launch_lane_automaton_pick(lane_logits_, cfg_.vocab, cfg_.vocab, rows, first, lane_best_, lane_state_, lane_hist_,
-                                             lane_hist_stride_, lane_cap_, advance, lane_auto_, stream_), "lane automaton pick");
+    hip_check(launch_lane_automaton_pick(logits, cfg_.vocab, cfg_.vocab, rows, first, b.best, b.dev, b.hist, b.hist_stride, b.cap, advance,
+                                         lane_auto_, stream_), "lane automaton pick");
     // the record of the lanes that picked, at index count - 1 (the pick has counted); the picked logit is an allowed one, which the
     // mask did not rewrite
     if (records)
@@ -1592,15 +1582,13 @@ void LlmModel::lane_automaton_pick_enqueue(bool wide, int first, int rows, int a
                           L.lp + (size_t)first * L.stride, L.ids + (size_t)first * L.stride * S, L.tlp + (size_t)first * L.stride * S);
 }
 
-hipGraphExec_t LlmModel::lane_automaton_step_graph(bool wide, int n, bool records, int k)
+hipGraphExec_t LlmModel::lane_automaton_step_graph(LaneBank& b, int n, bool records, int k)
 {
-    const int v = !records ? 0 : k > 1 ? 2 : 1;
-    hipGraphExec_t& g = wide ? wide_auto_graphs_[v][n] : lane_auto_graphs_[v][n];
+    hipGraphExec_t& g = b.auto_graphs[!records ? 0 : k > 1 ? 2 : 1][n];
     if (g) return g;
     return g = capture_graph(stream_, [&] {
-        if (wide) wide_step_enqueue(n);
-        else lane_step(n);
-        lane_automaton_pick_enqueue(wide, 0, n, 1, records, k);
+        lane_step_enqueue(b, n);
+        lane_automaton_pick_enqueue(b, 0, n, 1, records, k);
     });
 }
 
@@ -2119,142 +2107,150 @@ uint32_t LlmModel::sample_row(const SampleHeader* header, int first, int capacit
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Lanes: up to 8 sequences decoded in lock step.  A lane is one sequence with its own KV cache (lane-major: lane l of a
-// layer sits at base + l * lane_alloc_cap_ * kv) and its own position; token, position, live flag, pick count and stop
-// rules of every lane live on the device (LlmLaneState), so a step is one linear chain of launches on one stream that
-// replays as a captured graph: embed (GPT-2: + wpe[pos[lane]]) -> per layer [norm + Q|K|V into the staging rows -> rotate
-// Q, rotate K and scatter K / V to row pos[lane] of the lane's cache -> ragged attention (pos[lane] + 1 keys) + merge ->
-// o-proj + residual -> norm + gate/up (c_fc + GELU) -> down + residual] -> final norm -> vocabulary head [lanes, vocab] ->
-// lane pick.  Seven launches per layer, two more than the one-token step (which fuses the rotation into the projection and
-// the merge into the o-proj).
+// Lanes: sequences decoded in lock step, in two banks (LaneBank) that one loop, generate_on_lanes(), schedules: 1..8 lanes on
+// the GEMV kernels (lane_step) and 9..64 on the prompt GEMM (wide_step_enqueue, further down).  A lane is one sequence with its
+// own KV cache (lane-major: lane l of a layer sits at base + l * alloc_cap * kv) and its own position; token, position, live
+// flag, pick count and stop rules of every lane live on the device (LlmLaneState / LlmWideState), so a step is one linear chain
+// of launches on one stream that replays as a captured graph.  The lanes bank's: embed (GPT-2: + wpe[pos[lane]]) -> per layer
+// [norm + Q|K|V into the staging rows -> rotate Q, rotate K and scatter K / V to row pos[lane] of the lane's cache -> ragged
+// attention (pos[lane] + 1 keys) + merge -> o-proj + residual -> norm + gate/up (c_fc + GELU) -> down + residual] -> final
+// norm -> vocabulary head [lanes, vocab] -> lane pick.  Seven launches per layer, two more than the one-token step (which
+// fuses the rotation into the projection and the merge into the o-proj).
 
-void LlmModel::ensure_lanes(int lanes, int lane_context)
+void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
 {
-    if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8");
+    if (lanes < b.min_lanes || lanes > b.max_lanes) throw InvalidConfig(b.range_error);
     const LlmConfig& c = cfg_;
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
-    const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim);
-    if (lanes > lane_alloc_ || cap > lane_alloc_cap_) {
+    if (b.wide) {  // what the wide step alone asks of the checkpoint
+        if (quant_ && !fp8_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_: with the switch on, the FP8 prompt GEMM reads the codes)
+            throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
+                                " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
+        if (!rows_geometry(c) || !decode_attention_accepts(c.head_dim, splits_, cap, 1, true, true, false))
+            throw InvalidConfig("more than 8 lanes need hidden, heads * head_dim and intermediate_size multiples of 32 and a head_dim that is a "
+                                "multiple of 4 dividing 1024 (8 lanes or fewer run other shapes)");
+        ensure_prompt_workspace();
+    }
+    const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim), vocab = (size_t)c.vocab;
+    if (!b.state) {  // what the layout's width sizes: allocated once
+        b.state = dalloc((b.state_bytes + 3) / 4);
+        b.dev = LaneStateRef::at(b.state, b.width);
+        b.mirror = std::make_unique<int32_t[]>(b.state_bytes / sizeof(int32_t));
+        b.host = LaneStateRef::at(b.mirror.get(), b.width);
+        b.best = reinterpret_cast<unsigned long long*>(dalloc(2 * (size_t)b.width));
+        hip_check(hipMemset(b.best, 0, sizeof(unsigned long long) * b.width), "memset");
+        b.copy_table = reinterpret_cast<LlmKvCopyPair*>(dalloc((layers_.size() * sizeof(LlmKvCopyPair) + 3) / 4));
+    }
+    if (lanes > b.alloc || cap > b.alloc_cap) {
         hip_check(hipStreamSynchronize(stream_), "sync");
-        drop_graphs(lane_graphs_);
-        drop_lane_logprob_graphs(false);
-        // everything sized by lanes x rows is one allocation of its own: the caches of every layer, then the pick history and the
-        // processors' history / distinct lists; when the lanes or their rows grow it is replaced and the old one freed
-        const int nl = std::max(lanes, lane_alloc_), nc = std::max(cap, lane_alloc_cap_);
-        const size_t per_cache = ((size_t)nl * nc * kv + 63) & ~(size_t)63, stride = (size_t)nc + 16;
-        const size_t floats = 2 * layers_.size() * per_cache + 3 * (size_t)kLanes * stride;
+        drop_lane_graphs(b);
+        // one allocation of its own, sized by the lanes and the rows asked for, replaced (and the old one freed) when either grows.
+        // Kept as they are: the lanes bank's step works in the single-sequence att_scratch_, ctx_, h_ and last_ (layer_finish() and
+        // head() are pass()'s), the wide bank's in the prompt workspace with an attention scratch of its own, carved here.
+        const size_t nl = (size_t)std::max(lanes, b.alloc), nc = (size_t)std::max(cap, b.alloc_cap), stride = nc + 16;
+        auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
+        const size_t per_cache = pad(nl * nc * kv), qkv = pad(nl * ((size_t)c.q_dim() + 2 * kv)), logits = pad(nl * vocab);
+        const size_t att = b.wide ? pad(decode_attention_scratch_floats((int)nl, c.heads, c.head_dim, splits_)) : 0, hist = pad(nl * stride);
+        const size_t floats = 2 * layers_.size() * per_cache + qkv + 2 * logits + att + 3 * hist + pad(nl);
         void* fresh = arena_.alloc_own(floats * sizeof(float));
-        if (lane_block_) arena_.free_own(lane_block_);
-        lane_block_ = fresh;
+        if (b.block) arena_.free_own(b.block);
+        b.block = fresh;
         float* at = static_cast<float*>(fresh);
-        lane_k_.assign(layers_.size(), nullptr);
-        lane_v_.assign(layers_.size(), nullptr);
+        auto take = [&](size_t n) {
+            float* p = at;
+            at += n;
+            return p;
+        };
+        b.k.assign(layers_.size(), nullptr);
+        b.v.assign(layers_.size(), nullptr);
         for (size_t i = 0; i < layers_.size(); ++i) {
-            lane_k_[i] = at;
-            lane_v_[i] = at + per_cache;
-            at += 2 * per_cache;
+            b.k[i] = take(per_cache);
+            b.v[i] = take(per_cache);
         }
-        lane_hist_stride_ = (int)stride;
-        lane_hist_ = reinterpret_cast<int32_t*>(at);
-        lane_ptok_ = reinterpret_cast<int32_t*>(at + (size_t)kLanes * stride);
-        lane_pdistinct_ = reinterpret_cast<int32_t*>(at + 2 * (size_t)kLanes * stride);
-        if (!lane_qkv_) {
-            lane_qkv_ = dalloc((size_t)kLanes * (c.q_dim() + 2 * kv));
-            lane_logits_ = dalloc((size_t)kLanes * c.vocab);
-            lane_state_ = reinterpret_cast<LlmLaneState*>(dalloc((sizeof(LlmLaneState) + 3) / 4));
-            lane_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kLanes));
-            hip_check(hipMemset(lane_best_, 0, sizeof(unsigned long long) * kLanes), "memset");
-            lane_pcounts_ = reinterpret_cast<int*>(dalloc((size_t)kLanes * c.vocab));
-            lane_pndistinct_ = reinterpret_cast<int*>(dalloc(kLanes));
-            lane_host_ = std::make_unique<LlmLaneState>();
-        }
-        lane_alloc_ = nl;
-        lane_alloc_cap_ = nc;
+        b.qkv = take(qkv);
+        b.logits = take(logits);
+        b.pcounts = reinterpret_cast<int*>(take(logits));
+        b.att = take(att);
+        b.hist_stride = (int)stride;
+        b.hist = reinterpret_cast<int32_t*>(take(hist));
+        b.ptok = reinterpret_cast<int32_t*>(take(hist));
+        b.pdistinct = reinterpret_cast<int32_t*>(take(hist));
+        b.pndistinct = reinterpret_cast<int*>(take(pad(nl)));
+        b.alloc = (int)nl;
+        b.alloc_cap = (int)nc;
         // the shared-prefix copy reads its pointers from the device: (main K, lane-0 K, main V, lane-0 V) per layer
         std::vector<LlmKvCopyPair> pairs(layers_.size());
-        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, lane_k_[i], layers_[i].v_cache, lane_v_[i]};
-        if (!lane_copy_table_) lane_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((pairs.size() * sizeof(LlmKvCopyPair) + 3) / 4));
-        hip_check(hipMemcpy(lane_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
+        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, b.k[i], layers_[i].v_cache, b.v[i]};
+        hip_check(hipMemcpy(b.copy_table, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
     }
-    if (cap != lane_cap_) {  // (the capacity is an argument of the captured launches)
-        drop_graphs(lane_graphs_);
-        drop_lane_logprob_graphs(false);
-    }
-    lanes_ = lanes;
-    lane_cap_ = cap;
-    std::memset(lane_host_.get(), 0, sizeof(LlmLaneState));
-    std::fill(lane_len_, lane_len_ + kLanes, 0);
-    lane_state_to_device();
+    if (cap != b.cap) drop_lane_graphs(b);  // (the capacity is an argument of the captured launches)
+    b.lanes = lanes;
+    b.cap = cap;
+    std::memset(b.mirror.get(), 0, b.state_bytes);
+    std::fill(b.len, b.len + kWideLanes, 0);
+    lane_state_to_device(b);
 }
 
-void LlmModel::lane_state_to_device()
+void LlmModel::lane_state_to_device(LaneBank& b)
 {
-    hip_check(hipMemcpyAsync(lane_state_, lane_host_.get(), sizeof(LlmLaneState), hipMemcpyHostToDevice, stream_), "H2D lane state");
+    hip_check(hipMemcpyAsync(b.state, b.mirror.get(), b.state_bytes, hipMemcpyHostToDevice, stream_), "H2D lane state");
     hip_check(hipStreamSynchronize(stream_), "sync");  // (the mirror is edited again right away)
 }
 
-void LlmModel::lane_state_from_device()
+void LlmModel::lane_state_from_device(LaneBank& b)
 {
-    hip_check(hipMemcpyAsync(lane_host_.get(), lane_state_, sizeof(LlmLaneState), hipMemcpyDeviceToHost, stream_), "D2H lane state");
+    hip_check(hipMemcpyAsync(b.mirror.get(), b.state, b.state_bytes, hipMemcpyDeviceToHost, stream_), "D2H lane state");
     hip_check(hipStreamSynchronize(stream_), "sync");
 }
 
-void LlmModel::lanes_begin(int lanes, int lane_context)
+void LlmModel::lanes_begin(Bank bank, int lanes, int lane_context)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lanes == 0) lanes = kLanes;
-    ensure_lanes(lanes, lane_context);
+    LaneBank& b = bank_of(bank);
+    ensure_lane_bank(b, lanes == 0 ? b.max_lanes : lanes, lane_context);
 }
 
-// A prompt into one lane, by the prompt routes of forward(): the layers' cache pointers (and the capacity) are pointed at the
-// lane for the duration of the call.  The last position's logits are kept as the lane's logits row.
-void LlmModel::lane_prefill(int lane, const uint32_t* ids, int n) { lane_prefill_at(lane, 0, ids, n); }
+void LlmModel::lane_prefill(Bank bank, int lane, const uint32_t* ids, int n) { lane_prefill_at(bank_of(bank), lane, 0, ids, n); }
 
 // Rows [0, s) of every layer's K and V, single-sequence cache -> lane, in one launch on the model's stream.
-void LlmModel::lane_copy_prefix(int lane, int s)
+void LlmModel::lane_copy_prefix(LaneBank& b, int lane, int s)
 {
-    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
-    if (s < 0 || s > cache_len_ || s > lane_cap_) throw std::runtime_error("shared prefix out of range");
+    if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
+    if (s < 0 || s > cache_len_ || s > b.cap) throw std::runtime_error("shared prefix out of range");
     const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
-    hip_check(launch_kv_prefix_copy(lane_copy_table_, (int)layers_.size(), (int64_t)lane * lane_alloc_cap_ * kv, (int64_t)s * kv, stream_),
-              "prefix copy");
+    hip_check(launch_kv_prefix_copy(b.copy_table, (int)layers_.size(), (int64_t)lane * b.alloc_cap * kv, (int64_t)s * kv, stream_), "prefix copy");
 }
 
-void LlmModel::lane_prefill_shared(int lane, int s, const uint32_t* ids, int n)
+void LlmModel::lane_prefill_shared(Bank bank, int lane, int s, const uint32_t* ids, int n) { lane_prefill_shared(bank_of(bank), lane, s, ids, n); }
+
+void LlmModel::lane_prefill_shared(LaneBank& b, int lane, int s, const uint32_t* ids, int n)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
     if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
     if (s < 0 || s > cache_len_) throw std::runtime_error("shared prefix out of range");
-    if ((int64_t)s + n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
-    lane_copy_prefix(lane, s);
-    lane_prefill_at(lane, s, ids, n);
+    if ((int64_t)s + n > b.cap) throw std::runtime_error("prompt does not fit the lane");
+    lane_copy_prefix(b, lane, s);
+    lane_prefill_at(b, lane, s, ids, n);
 }
 
-void LlmModel::lane_prefill_at(int lane, int base, const uint32_t* ids, int n)
+void LlmModel::lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* ids, int n)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
+    if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
     if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
-    if (base < 0 || (int64_t)base + n > lane_cap_) throw std::runtime_error("prompt does not fit the lane");
-    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    prefill_into(lane_k_, lane_v_, (size_t)lane * lane_alloc_cap_ * kv, lane_cap_, lane_logits_ + (size_t)lane * cfg_.vocab, base, ids, n);
-    lane_len_[lane] = base + n;
-}
-
-void LlmModel::prefill_into(const std::vector<float*>& k, const std::vector<float*>& v, size_t off, int cap, float* logits_row, int base,
-                            const uint32_t* ids, int n)
-{
+    if (base < 0 || (int64_t)base + n > b.cap) throw std::runtime_error("prompt does not fit the lane");
+    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim), off = (size_t)lane * b.alloc_cap * kv;
     std::vector<std::pair<float*, float*>> saved(layers_.size());
     const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
     const size_t saved_resident = resident_.size();
     for (size_t i = 0; i < layers_.size(); ++i) {
         saved[i] = {layers_[i].k_cache, layers_[i].v_cache};
-        layers_[i].k_cache = k[i] + off;
-        layers_[i].v_cache = v[i] + off;
+        layers_[i].k_cache = b.k[i] + off;
+        layers_[i].v_cache = b.v[i] + off;
     }
     cache_len_ = base;
-    cache_cap_ = cap;
+    cache_cap_ = b.cap;
     auto restore = [&] {
         for (size_t i = 0; i < layers_.size(); ++i) {
             layers_[i].k_cache = saved[i].first;
@@ -2267,7 +2263,8 @@ void LlmModel::prefill_into(const std::vector<float*>& k, const std::vector<floa
     };
     try {
         forward(ids, n);
-        hip_check(hipMemcpyAsync(logits_row, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice, stream_), "D2D logits");
+        hip_check(hipMemcpyAsync(b.logits + (size_t)lane * cfg_.vocab, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice, stream_),
+                  "D2D logits");
         // (forward left the lane's length in pos_: the single-sequence cache's own length goes back)
         hip_check(hipMemcpyAsync(pos_, &saved_len, sizeof(int), hipMemcpyHostToDevice, stream_), "H2D pos");
         hip_check(hipStreamSynchronize(stream_), "sync");
@@ -2278,24 +2275,41 @@ void LlmModel::prefill_into(const std::vector<float*>& k, const std::vector<floa
         throw;
     }
     restore();
+    b.len[lane] = base + n;
 }
 
-// One lock-step step: pass()'s stages with one row per lane.  Its own first half of the layer -- Q | K | V of every lane into the
-// staging rows, then one kernel rotates them and scatters K and V to row pos[lane] of each lane's cache -- and the ragged
-// attention; embedding, layer_finish, final norm and head are pass()'s.
+// The middle of either step body for one layer: the staging rows' Q rotated in place, K rotated (GPT-2: copied) and V copied to
+// row pos[lane] of each lane's cache, then the ragged attention (pos[lane] + 1 keys; frozen lanes skipped) and its merge.
+void LlmModel::lane_attention(const LaneBank& b, int n, size_t li, float* scratch, float* ctx)
+{
+    const LlmConfig& c = cfg_;
+    const Layer& L = layers_[li];
+    const int d = c.head_dim, QD = c.q_dim(), kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
+    const int64_t stride = (int64_t)b.alloc_cap * kv;
+    if (c.qwen3())
+        hip_check(launch_lane_qk_norm_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, b.k[li], b.v[li], stride,
+                                                   b.cap, b.dev, stream_), "head norm + rotate + scatter");
+    else
+        hip_check(launch_lane_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, cos_, sin_, b.k[li], b.v[li], stride, b.cap, b.dev, gpt2_ ? 0 : 1,
+                                           stream_), "rotate + scatter");
+    hip_check(launch_decode_attention(b.qkv, ldq, n, b.k[li], kv, b.v[li], kv, b.cap, nullptr, b.cap, c.heads, d, -1, splits_, scratch, ctx, QD,
+                                      stream_, c.heads / kvh, stride, stride, 1, b.dev.pos, b.dev.live), "attention");
+}
+
+// One lock-step step of the lanes bank: pass()'s stages with one row per lane.  Its own first half of the layer -- Q | K | V of
+// every lane into the staging rows -- then lane_attention(); embedding, layer_finish, final norm and head are pass()'s.
 void LlmModel::lane_step(int n)
 {
     hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
+    const LaneBank& b = lane_bank_;
     const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
     const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
-    const int64_t stride = (int64_t)lane_alloc_cap_ * kv;
-    const LlmLaneState* st = lane_state_;
-    embed_rows(reinterpret_cast<const uint32_t*>(st->token), n, h_, 0, nullptr, st->pos);
+    embed_rows(reinterpret_cast<const uint32_t*>(b.dev.token), n, h_, 0, nullptr, b.dev.pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
         if (fp8_) {
-            fp8_qkv(n, L, lane_qkv_, ldq, lane_qkv_ + QD, lane_qkv_ + QD + kv, ldq, 0, nullptr);
+            fp8_qkv(n, L, b.qkv, ldq, b.qkv + QD, b.qkv + QD + kv, ldq, 0, nullptr);
         } else if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
             QFusedArgs a;
             a.mode = QF_PLAIN;
@@ -2304,78 +2318,95 @@ void LlmModel::lane_step(int n)
             a.seg_jobs[0] = H / 2; a.seg_jobs[1] = kv / 2; a.seg_jobs[2] = kv / 2;
             a.jobs = H / 2 + kv;
             a.bias = L.bqkv; a.bias_off[1] = H; a.bias_off[2] = H + kv;
-            a.Y[0] = lane_qkv_; a.Y[1] = lane_qkv_ + H; a.Y[2] = lane_qkv_ + H + kv;
+            a.Y[0] = b.qkv; a.Y[1] = b.qkv + H; a.Y[2] = b.qkv + H + kv;
             a.ldy[0] = a.ldy[1] = a.ldy[2] = ldq;
             hip_check(launch_qfused(a, s), "norm + qkv");
         } else {
             LlmGemvArgs a;
             a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
-            a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = lane_qkv_; a.ldy0 = ldq;
+            a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = b.qkv; a.ldy0 = ldq;
             project(StepRoute::Lanes, a, "norm + qkv");
         }
-        if (c.qwen3())
-            hip_check(launch_lane_qk_norm_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, lane_k_[li],
-                                                       lane_v_[li], stride, lane_cap_, st, s), "head norm + rotate + scatter");
-        else
-        hip_check(launch_lane_rope_scatter(lane_qkv_, ldq, n, c.heads, kvh, d, cos_, sin_, lane_k_[li], lane_v_[li], stride, lane_cap_, st,
-                                           gpt2_ ? 0 : 1, s), "rotate + scatter");
-        hip_check(launch_decode_attention(lane_qkv_, ldq, n, lane_k_[li], kv, lane_v_[li], kv, lane_cap_, nullptr, lane_cap_, c.heads, d, -1,
-                                          splits_, att_scratch_, ctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
+        lane_attention(b, n, li, att_scratch_, ctx_);
         layer_finish(StepRoute::Lanes, n, L, false);
     }
     final_norm(h_, n, last_);
-    head(StepRoute::Lanes, last_, n, lane_logits_);
+    head(StepRoute::Lanes, last_, n, b.logits);
 }
 
-void LlmModel::lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
+void LlmModel::lane_step_enqueue(LaneBank& b, int n)
+{
+    if (b.wide) wide_step_enqueue(n);
+    else lane_step(n);
+}
+
+void LlmModel::lane_pick_enqueue(LaneBank& b, int lanes, int first, int advance)
+{
+    hip_check(launch_lane_pick(b.logits, cfg_.vocab, cfg_.vocab, lanes, first, b.best, b.dev, b.hist, b.hist_stride, b.cap, advance, stream_),
+              b.wide ? "wide pick" : "lane pick");
+}
+
+void LlmModel::lanes_step(Bank bank, const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lanes_ < 1) throw std::runtime_error("lanes_begin first");
-    LlmLaneState& h = *lane_host_;
-    for (int l = 0; l < lanes_; ++l) {
+    LaneBank& b = bank_of(bank);
+    if (b.lanes < 1) throw std::runtime_error(b.begin_error);
+    const LaneStateRef& h = b.host;
+    for (int l = 0; l < b.lanes; ++l) {
         const bool on = live ? live[l] != 0 : true;
-        if (on && lane_len_[l] >= lane_cap_) throw std::runtime_error("lane " + std::to_string(l) + " is full");
+        if (on && b.len[l] >= b.cap) throw std::runtime_error("lane " + std::to_string(l) + " is full");
         h.token[l] = (int32_t)ids[l];
-        h.pos[l] = lane_len_[l];
+        h.pos[l] = b.len[l];
         h.live[l] = on ? 1 : 0;
     }
-    lane_state_to_device();
-    lane_step(lanes_);
+    lane_state_to_device(b);
+    lane_step_enqueue(b, b.lanes);
     hip_check(hipStreamSynchronize(stream_), "sync");
-    for (int l = 0; l < lanes_; ++l)
-        if (h.live[l]) lane_len_[l] += 1;
-    if (hidden_out) hip_check(hipMemcpy(hidden_out, last_, (size_t)lanes_ * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
+    for (int l = 0; l < b.lanes; ++l)
+        if (h.live[l]) b.len[l] += 1;
+    const float* hidden = b.wide ? pn_ : last_;  // where the step body's final norm wrote
+    if (hidden_out) hip_check(hipMemcpy(hidden_out, hidden, (size_t)b.lanes * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
     if (logits_out)
-        hip_check(hipMemcpy(logits_out, lane_logits_, (size_t)lanes_ * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
+        hip_check(hipMemcpy(logits_out, b.logits, (size_t)b.lanes * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
 }
 
-int LlmModel::lane_cache_len(int lane) const
+int LlmModel::lane_cache_len(Bank bank, int lane) const
 {
-    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
-    return lane_len_[lane];
+    const LaneBank& b = bank_of(bank);
+    if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
+    return b.len[lane];
 }
 
-void LlmModel::lane_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const
+void LlmModel::lane_kv_rows(Bank bank, int lane, int layer, int first, int rows, float* k_out, float* v_out) const
 {
-    if (lane < 0 || lane >= lanes_) throw std::runtime_error("no such lane");
-    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > lane_len_[lane] || rows > lane_len_[lane] - first)
+    const LaneBank& b = bank_of(bank);
+    if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
+    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > b.len[lane] || rows > b.len[lane] - first)
         throw std::runtime_error("cache rows out of range");
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(stream_), "sync");
     const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    const size_t off = ((size_t)lane * lane_alloc_cap_ + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
-    hip_check(hipMemcpy(k_out, lane_k_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
-    hip_check(hipMemcpy(v_out, lane_v_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+    const size_t off = ((size_t)lane * b.alloc_cap + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
+    hip_check(hipMemcpy(k_out, b.k[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+    hip_check(hipMemcpy(v_out, b.v[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
 }
 
-hipGraphExec_t LlmModel::lane_step_graph(int n)
+hipGraphExec_t LlmModel::lane_step_graph(LaneBank& b, int n)
 {
-    if (lane_graphs_[n]) return lane_graphs_[n];
-    return lane_graphs_[n] = capture_graph(stream_, [&] {
-        lane_step(n);
-        hip_check(launch_lane_pick(lane_logits_, cfg_.vocab, cfg_.vocab, n, 0, lane_best_, lane_state_, lane_hist_, lane_hist_stride_, lane_cap_, 1,
-                                   stream_), "lane pick");
+    if (b.graphs[n]) return b.graphs[n];
+    return b.graphs[n] = capture_graph(stream_, [&] {
+        lane_step_enqueue(b, n);
+        lane_pick_enqueue(b, n, 0, 1);
     });
+}
+
+void LlmModel::lane_burst(LaneBank& b, int n, size_t times, hipGraphExec_t chain)
+{
+    hipGraphExec_t exec = chain ? chain : lane_step_graph(b, n);
+    for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
+    if (!b.wide) return;
+    for (const Layer& L : layers_)  // (a replay runs no host code: the routing record's row count of the rows route is set here)
+        if (L.moe) L.moe_rec_rows = n;
 }
 
 std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
@@ -2383,39 +2414,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_lanes(const std::vector<La
 {
     if (lanes == 0) lanes = kLanes;
     if (lanes < 1 || lanes > kLanes) throw InvalidConfig("lanes must be 1..8 (0 = 8)");
-    return generate_on_lanes(reqs, lanes, lane_context, on_token, false, false);
-}
-
-// The 8-lane set as the scheduling loop sees it: the enqueue functions are the launches generate_lanes has always made.
-LlmModel::LaneSet LlmModel::lane_set()
-{
-    LlmLaneState& h = *lane_host_;
-    LaneSet S;
-    S.token = h.token; S.pos = h.pos; S.live = h.live; S.count = h.count; S.limit = h.limit; S.n_stop = h.n_stop; S.stop = h.stop;
-    S.len = lane_len_;
-    S.hist_stride = lane_hist_stride_;
-    S.hist = lane_hist_; S.ptok = lane_ptok_; S.pdistinct = lane_pdistinct_; S.pcounts = lane_pcounts_; S.pndistinct = lane_pndistinct_;
-    S.logits = lane_logits_;
-    S.to_device = [this] { lane_state_to_device(); };
-    S.from_device = [this] { lane_state_from_device(); };
-    S.first_pick = [this](int l) {
-        hip_check(launch_lane_pick(lane_logits_, (int64_t)cfg_.vocab, cfg_.vocab, 1, l, lane_best_, lane_state_, lane_hist_, lane_hist_stride_,
-                                   lane_cap_, 0, stream_), "lane pick");
-    };
-    S.prefill = [this](int l, int shared, const uint32_t* ids, int n) {
-        if (shared >= 1) lane_prefill_shared(l, shared, ids, n);
-        else lane_prefill(l, ids, n);
-    };
-    S.step = [this](int n) { lane_step(n); };
-    S.burst = [this](int n, size_t times, hipGraphExec_t chain) {
-        hipGraphExec_t exec = chain ? chain : lane_step_graph(n);
-        for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-    };
-    return S;
+    return generate_on_lanes(reqs, lanes, lane_context, on_token, lane_bank_, false);
 }
 
 std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
-                                                               const std::function<bool(size_t, uint32_t)>& on_token, bool wide, bool strict)
+                                                               const std::function<bool(size_t, uint32_t)>& on_token, LaneBank& b, bool strict)
 {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     auto refuse = [&](const std::string& what) {  // generate_lanes' own refusals keep their types
@@ -2472,18 +2475,20 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
     }
     if (reqs.empty()) return out;
     const int n = (int)std::min<size_t>((size_t)lanes, reqs.size());
-    if (wide) ensure_wide(n, lane_context);
-    else ensure_lanes(n, lane_context);
+    ensure_lane_bank(b, n, lane_context);
     if (lp) {
         ensure_logprobs();
-        ensure_lane_logprobs(wide);
+        ensure_lane_logprobs(b);
         for (const LaneRequest& r : reqs)
             if (r.options.logprobs >= 0 && r.options.logprob_sink) r.options.logprob_sink->clear(r.options.logprobs);
     }
     if (automata) ensure_lane_automata();
-    const LaneLogs& LL = lane_logs_[wide ? 1 : 0];
-    const LaneSet S = wide ? wide_set() : lane_set();
-    const LaneSet& h = S;  // (the mirror's fields, as the loop has always named them)
+    const LaneLogs& LL = b.logs;
+    const LaneStateRef& h = b.host;  // (the mirror's fields)
+    auto prefill = [&](int l, int shared, const uint32_t* ids, int count) {  // behind `shared` copied prefix rows
+        if (shared >= 1) lane_prefill_shared(b, l, shared, ids, count);
+        else lane_prefill_at(b, l, 0, ids, count);
+    };
     const size_t vocab = (size_t)cfg_.vocab;
     // Prefix reuse: the prefix every prompt shares (one token short of the shortest prompt, whose last token must be forwarded
     // for its logits) is prefilled once into the single-sequence cache -- where it also stays for the next call -- and copied
@@ -2617,11 +2622,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             }
             if (on_token) r.on_token = [&on_token, i](uint32_t tok) { return on_token(i, tok); };
             if (shared >= 1) {
-                S.prefill(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
+                prefill(l, shared, q.prompt.data() + shared, (int)q.prompt.size() - shared);
                 prefix_reused_ += (uint64_t)shared;
                 prefix_computed_ += q.prompt.size() - (size_t)shared;
             } else {
-                S.prefill(l, 0, q.prompt.data(), (int)q.prompt.size());
+                prefill(l, 0, q.prompt.data(), (int)q.prompt.size());
                 if (prefix_reuse_) prefix_computed_ += q.prompt.size();
             }
             h.token[l] = 0;
@@ -2649,14 +2654,14 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         // the host looks every few steps (generate()'s cadence).  Tokens a lane computed past its stop are discarded.
         // a lane's first token comes from its prefill's logits row: the lane pick on that row alone
         auto first_pick = [&](int l) {
-            S.to_device();
+            lane_state_to_device(b);
             if (automata) {  // the lane's mask on the prefill's row, the pick, the automaton's first move
-                lane_automaton_pick_enqueue(wide, l, 1, 0, lp, lpk);
+                lane_automaton_pick_enqueue(b, l, 1, 0, lp, lpk);
             } else {
-                if (lp) lane_logprobs_enqueue(wide, l, 1, lpk);  // (the lane's count is 0: record 0 of its new request)
-                S.first_pick(l);
+                if (lp) lane_logprobs_enqueue(b, l, 1, lpk);  // (the lane's count is 0: record 0 of its new request)
+                lane_pick_enqueue(b, 1, l, 0);
             }
-            S.from_device();
+            lane_state_from_device(b);
         };
         auto drain = [&](size_t steps) {  // step-major, lane order within a step
             std::vector<std::vector<int32_t>> fresh((size_t)n);
@@ -2668,9 +2673,9 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                 Run& r = run[l];
                 const size_t have = (size_t)h.count[l];
                 if (r.req < 0 || have <= r.seen) continue;
-                const size_t m = have - r.seen, at = (size_t)l * S.hist_stride + r.seen;
+                const size_t m = have - r.seen, at = (size_t)l * b.hist_stride + r.seen;
                 fresh[(size_t)l].resize(m);
-                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), S.hist + at, m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
+                hip_check(hipMemcpyAsync(fresh[(size_t)l].data(), b.hist + at, m * sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "D2H tokens");
                 first_new[(size_t)l] = r.seen;
                 if (lp && r.sink) {
                     lo = std::min(lo, r.seen);
@@ -2682,7 +2687,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             std::vector<float> flp((size_t)n * win), ftlp((size_t)n * win * kSlots);
             std::vector<uint32_t> fids((size_t)n * win * kSlots);
             if (win) {
-                const size_t pitch = (size_t)S.hist_stride;
+                const size_t pitch = (size_t)b.hist_stride;
                 hip_check(hipMemcpy2DAsync(flp.data(), win * sizeof(float), LL.lp + lo, pitch * sizeof(float), win * sizeof(float), (size_t)n,
                                            hipMemcpyDeviceToHost, stream_), "D2H logprobs");
                 hip_check(hipMemcpy2DAsync(fids.data(), win * kSlots * sizeof(uint32_t), LL.ids + lo * kSlots, pitch * kSlots * sizeof(uint32_t),
@@ -2717,19 +2722,19 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
                     if (!start(l)) break;
                     first_pick(l);  // (writes the whole state, this pass's edits included)
                     dirty = false;
-                    S.len[l] = h.pos[l];
+                    b.len[l] = h.pos[l];
                     drain(1);
                     if (!h.live[l]) r.g.done = true;
                 }
             }
             if (!any_running()) break;
-            if (dirty) S.to_device();
-            // (with records: the chain that has them in it, captured per (set, lanes, width), through the set's own burst)
-            // (under automata: the chain with the lane apply and advance around the pick, one per (set, lanes, records))
-            S.burst(n, burst, automata ? lane_automaton_step_graph(wide, n, lp, lpk) : lp ? lane_logprob_step_graph(wide, n, lpk) : nullptr);
-            S.from_device();
+            if (dirty) lane_state_to_device(b);
+            // (with records: the chain that has them in it, captured per (bank, lanes, width))
+            // (under automata: the chain with the lane apply and advance around the pick, one per (bank, lanes, records))
+            lane_burst(b, n, burst, automata ? lane_automaton_step_graph(b, n, lp, lpk) : lp ? lane_logprob_step_graph(b, n, lpk) : nullptr);
+            lane_state_from_device(b);
             for (int l = 0; l < n; ++l)
-                if (run[l].req >= 0) S.len[l] = h.pos[l];
+                if (run[l].req >= 0) b.len[l] = h.pos[l];
             drain(burst);
         }
         for (int l = 0; l < n; ++l) report(l);
@@ -2744,10 +2749,10 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
     std::vector<float> probs;
     std::vector<uint32_t> ids;
     auto pstate = [&](int l, int32_t*& tok, int32_t*& distinct, int*& counts, int*& nd) {
-        tok = S.ptok + (size_t)l * S.hist_stride;
-        distinct = S.pdistinct + (size_t)l * S.hist_stride;
-        counts = S.pcounts + (size_t)l * vocab;
-        nd = S.pndistinct + l;
+        tok = b.ptok + (size_t)l * b.hist_stride;
+        distinct = b.pdistinct + (size_t)l * b.hist_stride;
+        counts = b.pcounts + (size_t)l * vocab;
+        nd = b.pndistinct + l;
     };
     auto begin_history = [&](int l) {  // the history so far = the prompt
         const Run& r = run[l];
@@ -2766,7 +2771,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
             // the round's step rewrites every row)
             while (!r.g.done) {
                 const GenerateOptions& o = reqs[(size_t)r.req].options;
-                float* row = S.logits + (size_t)l * vocab;
+                float* row = b.logits + (size_t)l * vocab;
                 int32_t *tok, *distinct;
                 int *counts, *nd;
                 pstate(l, tok, distinct, counts, nd);
@@ -2845,11 +2850,11 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
         bool step = false;
         for (int l = 0; l < n; ++l) step = step || h.live[l];
         if (step) {
-            S.to_device();
-            S.step(n);
+            lane_state_to_device(b);
+            lane_step_enqueue(b, n);
             hip_check(hipStreamSynchronize(stream_), "sync");
             for (int l = 0; l < n; ++l)
-                if (h.live[l]) S.len[l] = h.pos[l] + 1;
+                if (h.live[l]) b.len[l] = h.pos[l] + 1;
         }
     }
     for (int l = 0; l < n; ++l) report(l);
@@ -2859,145 +2864,21 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
 // ---------------------------------------------------------------------------------------------------------------------
 // Wide lanes: 9..64 sequences in lock step.  The lanes' state, staging layout, scatter, ragged attention and pick, with every
 // projection on the prompt GEMM (one 64-row M-tile: the weights are read once per step whatever the width) instead of the
-// 8-row GEMV kernels.  The scheduling loop is generate_on_lanes() above, on wide_set().
-
-void LlmModel::ensure_wide(int lanes, int lane_context)
-{
-    if (lanes <= kLanes || lanes > kWideLanes) throw InvalidConfig("wide lanes must be 9..64 (8 or fewer are the lanes route's)");
-    if (quant_ && !fp8_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_: with the switch on, the FP8 prompt GEMM reads the codes)
-        throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
-                            " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
-    const LlmConfig& c = cfg_;
-    const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
-    if (!rows_geometry(c) || !decode_attention_accepts(c.head_dim, splits_, cap, 1, true, true, false))
-        throw InvalidConfig("more than 8 lanes need hidden, heads * head_dim and intermediate_size multiples of 32 and a head_dim that is a "
-                            "multiple of 4 dividing 1024 (8 lanes or fewer run other shapes)");
-    ensure_prompt_workspace();
-    const size_t kv = (size_t)(gpt2_ ? c.hidden : c.kv_heads * c.head_dim), vocab = (size_t)c.vocab;
-    if (!wide_state_) {
-        wide_state_ = reinterpret_cast<LlmWideState*>(dalloc((sizeof(LlmWideState) + 3) / 4));
-        wide_best_ = reinterpret_cast<unsigned long long*>(dalloc(2 * kWideLanes));
-        hip_check(hipMemset(wide_best_, 0, sizeof(unsigned long long) * kWideLanes), "memset");
-        wide_copy_table_ = reinterpret_cast<LlmKvCopyPair*>(dalloc((layers_.size() * sizeof(LlmKvCopyPair) + 3) / 4));
-        wide_host_ = std::make_unique<LlmWideState>();
-    }
-    if (lanes > wide_alloc_ || cap > wide_alloc_cap_) {
-        hip_check(hipStreamSynchronize(stream_), "sync");
-        drop_graphs(wide_graphs_);
-        drop_lane_logprob_graphs(true);
-        // one allocation of its own, sized by the width and the rows asked for, replaced when either grows
-        const size_t nl = (size_t)std::max(lanes, wide_alloc_), nc = (size_t)std::max(cap, wide_alloc_cap_), stride = nc + 16;
-        auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
-        const size_t per_cache = pad(nl * nc * kv), qkv = pad(nl * ((size_t)c.q_dim() + 2 * kv)), logits = pad(nl * vocab);
-        const size_t att = pad(decode_attention_scratch_floats((int)nl, c.heads, c.head_dim, splits_)), hist = pad(nl * stride);
-        const size_t floats = 2 * layers_.size() * per_cache + qkv + 2 * logits + att + 3 * hist + pad(nl);
-        void* fresh = arena_.alloc_own(floats * sizeof(float));
-        if (wide_block_) arena_.free_own(wide_block_);
-        wide_block_ = fresh;
-        float* at = static_cast<float*>(fresh);
-        auto take = [&](size_t n) {
-            float* p = at;
-            at += n;
-            return p;
-        };
-        wide_k_.assign(layers_.size(), nullptr);
-        wide_v_.assign(layers_.size(), nullptr);
-        for (size_t i = 0; i < layers_.size(); ++i) {
-            wide_k_[i] = take(per_cache);
-            wide_v_[i] = take(per_cache);
-        }
-        wide_qkv_ = take(qkv);
-        wide_logits_ = take(logits);
-        wide_pcounts_ = reinterpret_cast<int*>(take(logits));
-        wide_att_ = take(att);
-        wide_hist_stride_ = (int)stride;
-        wide_hist_ = reinterpret_cast<int32_t*>(take(hist));
-        wide_ptok_ = reinterpret_cast<int32_t*>(take(hist));
-        wide_pdistinct_ = reinterpret_cast<int32_t*>(take(hist));
-        wide_pndistinct_ = reinterpret_cast<int*>(take(pad(nl)));
-        wide_alloc_ = (int)nl;
-        wide_alloc_cap_ = (int)nc;
-        std::vector<LlmKvCopyPair> pairs(layers_.size());
-        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, wide_k_[i], layers_[i].v_cache, wide_v_[i]};
-        hip_check(hipMemcpy(wide_copy_table_, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
-    }
-    if (cap != wide_cap_) {  // (the capacity is an argument of the captured launches)
-        drop_graphs(wide_graphs_);
-        drop_lane_logprob_graphs(true);
-    }
-    wide_lanes_ = lanes;
-    wide_cap_ = cap;
-    std::memset(wide_host_.get(), 0, sizeof(LlmWideState));
-    std::fill(wide_len_, wide_len_ + kWideLanes, 0);
-    wide_state_to_device();
-}
+// 8-row GEMV kernels.  The scheduling loop is generate_on_lanes() above, on the wide bank.
 
 void LlmModel::set_fp8_matrix_cores(bool on)
 {
     if (!fp8_ || on == fp8_mc_) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(stream_), "sync");
-    drop_graphs(wide_graphs_);  // (they hold the route's launches)
-    drop_lane_logprob_graphs(true);
-    wide_lanes_ = 0;  // a wide session ends here: wide_begin() decides again
+    drop_lane_graphs(wide_bank_);  // (they hold the route's launches)
+    wide_bank_.lanes = 0;       // a wide session ends here: lanes_begin() decides again
     fp8_mc_ = on;
-}
-
-void LlmModel::wide_state_to_device()
-{
-    hip_check(hipMemcpyAsync(wide_state_, wide_host_.get(), sizeof(LlmWideState), hipMemcpyHostToDevice, stream_), "H2D wide state");
-    hip_check(hipStreamSynchronize(stream_), "sync");  // (the mirror is edited again right away)
-}
-
-void LlmModel::wide_state_from_device()
-{
-    hip_check(hipMemcpyAsync(wide_host_.get(), wide_state_, sizeof(LlmWideState), hipMemcpyDeviceToHost, stream_), "D2H wide state");
-    hip_check(hipStreamSynchronize(stream_), "sync");
-}
-
-void LlmModel::wide_begin(int lanes, int lane_context)
-{
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lanes == 0) lanes = kWideLanes;
-    ensure_wide(lanes, lane_context);
-}
-
-void LlmModel::wide_prefill(int lane, const uint32_t* ids, int n) { wide_prefill_at(lane, 0, ids, n); }
-
-void LlmModel::wide_copy_prefix(int lane, int s)
-{
-    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
-    if (s < 0 || s > cache_len_ || s > wide_cap_) throw std::runtime_error("shared prefix out of range");
-    const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
-    hip_check(launch_kv_prefix_copy(wide_copy_table_, (int)layers_.size(), (int64_t)lane * wide_alloc_cap_ * kv, (int64_t)s * kv, stream_),
-              "prefix copy");
-}
-
-void LlmModel::wide_prefill_shared(int lane, int s, const uint32_t* ids, int n)
-{
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
-    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
-    if (s < 0 || s > cache_len_) throw std::runtime_error("shared prefix out of range");
-    if ((int64_t)s + n > wide_cap_) throw std::runtime_error("prompt does not fit the lane");
-    wide_copy_prefix(lane, s);
-    wide_prefill_at(lane, s, ids, n);
-}
-
-void LlmModel::wide_prefill_at(int lane, int base, const uint32_t* ids, int n)
-{
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
-    if (n < 1) throw std::runtime_error("cannot generate from empty prompt");
-    if (base < 0 || (int64_t)base + n > wide_cap_) throw std::runtime_error("prompt does not fit the lane");
-    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    prefill_into(wide_k_, wide_v_, (size_t)lane * wide_alloc_cap_ * kv, wide_cap_, wide_logits_ + (size_t)lane * cfg_.vocab, base, ids, n);
-    wide_len_[lane] = base + n;
 }
 
 // One wide step, a linear chain on the model's stream: the embedding at the lanes' positions, per layer norm 1 -> ONE GEMM of
 // the fused [Q;K;V] matrix into the lanes' staging rows -> rotate-and-scatter -> ragged attention -> rows_finish() (o-proj,
-// norm 2, SwiGLU / GPT-2 MLP / the MoE rows hook), then the final norm and the head as a GEMM into wide_logits_.  Frozen lanes
+// norm 2, SwiGLU / GPT-2 MLP / the MoE rows hook), then the final norm and the head as a GEMM into the bank's logits.  Frozen lanes
 // ride along as rows of the GEMMs (each output row depends on its own input row only); the scatter and the attention skip them.
 void LlmModel::wide_step_enqueue(int n)
 {
@@ -3005,116 +2886,26 @@ void LlmModel::wide_step_enqueue(int n)
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
     const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
-    const int64_t stride = (int64_t)wide_alloc_cap_ * kv;
-    const LlmWideState* st = wide_state_;
-    embed_rows(reinterpret_cast<const uint32_t*>(st->token), n, ph_, 0, nullptr, st->pos);
+    const LaneBank& b = wide_bank_;
+    embed_rows(reinterpret_cast<const uint32_t*>(b.dev.token), n, ph_, 0, nullptr, b.dev.pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
         if (gpt2_) hip_check(launch_layernorm(ph_, L.ln1, L.ln1_b, c.eps, n, H, pn_, s), "ln_1");
         else hip_check(launch_rmsnorm(ph_, L.ln1, c.eps, n, H, pn_, s), "rmsnorm 1");
-        if (fp8_) {  // three matrices of their own (ensure_wide: only with the switch on), each into its column segment of the rows
-            prompt_proj(n, pn_, H, nullptr, L.bqkv, nullptr, wide_qkv_, ldq, QD, H, nullptr, "q proj", nullptr, false, &L.fq);
-            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD : nullptr, nullptr, wide_qkv_ + QD, ldq, kv, H, nullptr, "k proj", nullptr, false,
+        if (fp8_) {  // three matrices of their own (ensure_lane_bank: only with the switch on), each into its column segment of the rows
+            prompt_proj(n, pn_, H, nullptr, L.bqkv, nullptr, b.qkv, ldq, QD, H, nullptr, "q proj", nullptr, false, &L.fq);
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD : nullptr, nullptr, b.qkv + QD, ldq, kv, H, nullptr, "k proj", nullptr, false,
                         &L.fk);
-            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, wide_qkv_ + QD + kv, ldq, kv, H, nullptr, "v proj", nullptr,
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, b.qkv + QD + kv, ldq, kv, H, nullptr, "v proj", nullptr,
                         false, &L.fv);
         } else {
-            prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, wide_qkv_, ldq, ldq, H, nullptr, "q|k|v proj");
+            prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, b.qkv, ldq, ldq, H, nullptr, "q|k|v proj");
         }
-        if (c.qwen3())
-            hip_check(launch_wide_qk_norm_rope_scatter(wide_qkv_, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, wide_k_[li],
-                                                       wide_v_[li], stride, wide_cap_, st, s), "head norm + rotate + scatter");
-        else
-            hip_check(launch_wide_rope_scatter(wide_qkv_, ldq, n, c.heads, kvh, d, cos_, sin_, wide_k_[li], wide_v_[li], stride, wide_cap_, st,
-                                               gpt2_ ? 0 : 1, s), "rotate + scatter");
-        hip_check(launch_decode_attention(wide_qkv_, ldq, n, wide_k_[li], kv, wide_v_[li], kv, wide_cap_, nullptr, wide_cap_, c.heads, d, -1,
-                                          splits_, wide_att_, pctx_, QD, s, c.heads / kvh, stride, stride, 1, st->pos, st->live), "attention");
+        lane_attention(b, n, li, b.att, pctx_);
         rows_finish(n, L);
     }
     final_norm(ph_, n, pn_);  // (the norm buffer is free behind the last layer)
-    prompt_proj(n, pn_, H, lm_head_, nullptr, nullptr, wide_logits_, c.vocab, c.vocab, H, nullptr, "lm head");
-}
-
-void LlmModel::wide_pick_enqueue(int lanes, int first, int advance)
-{
-    hip_check(launch_wide_pick(wide_logits_, cfg_.vocab, cfg_.vocab, lanes, first, wide_best_, wide_state_, wide_hist_, wide_hist_stride_,
-                               wide_cap_, advance, stream_), "wide pick");
-}
-
-hipGraphExec_t LlmModel::wide_step_graph(int n)
-{
-    if (wide_graphs_[n]) return wide_graphs_[n];
-    return wide_graphs_[n] = capture_graph(stream_, [&] {
-        wide_step_enqueue(n);
-        wide_pick_enqueue(n, 0, 1);
-    });
-}
-
-void LlmModel::wide_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out)
-{
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (wide_lanes_ < 1) throw std::runtime_error("wide_begin first");
-    LlmWideState& h = *wide_host_;
-    for (int l = 0; l < wide_lanes_; ++l) {
-        const bool on = live ? live[l] != 0 : true;
-        if (on && wide_len_[l] >= wide_cap_) throw std::runtime_error("lane " + std::to_string(l) + " is full");
-        h.token[l] = (int32_t)ids[l];
-        h.pos[l] = wide_len_[l];
-        h.live[l] = on ? 1 : 0;
-    }
-    wide_state_to_device();
-    wide_step_enqueue(wide_lanes_);
-    hip_check(hipStreamSynchronize(stream_), "sync");
-    for (int l = 0; l < wide_lanes_; ++l)
-        if (h.live[l]) wide_len_[l] += 1;
-    if (hidden_out) hip_check(hipMemcpy(hidden_out, pn_, (size_t)wide_lanes_ * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost), "D2H hidden");
-    if (logits_out)
-        hip_check(hipMemcpy(logits_out, wide_logits_, (size_t)wide_lanes_ * cfg_.vocab * sizeof(float), hipMemcpyDeviceToHost), "D2H logits");
-}
-
-int LlmModel::wide_cache_len(int lane) const
-{
-    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
-    return wide_len_[lane];
-}
-
-void LlmModel::wide_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const
-{
-    if (lane < 0 || lane >= wide_lanes_) throw std::runtime_error("no such lane");
-    if (layer < 0 || layer >= (int)layers_.size() || first < 0 || rows < 0 || first > wide_len_[lane] || rows > wide_len_[lane] - first)
-        throw std::runtime_error("cache rows out of range");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(stream_), "sync");
-    const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    const size_t off = ((size_t)lane * wide_alloc_cap_ + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
-    hip_check(hipMemcpy(k_out, wide_k_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
-    hip_check(hipMemcpy(v_out, wide_v_[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
-}
-
-LlmModel::LaneSet LlmModel::wide_set()
-{
-    LlmWideState& h = *wide_host_;
-    LaneSet S;
-    S.token = h.token; S.pos = h.pos; S.live = h.live; S.count = h.count; S.limit = h.limit; S.n_stop = h.n_stop; S.stop = h.stop;
-    S.len = wide_len_;
-    S.hist_stride = wide_hist_stride_;
-    S.hist = wide_hist_; S.ptok = wide_ptok_; S.pdistinct = wide_pdistinct_; S.pcounts = wide_pcounts_; S.pndistinct = wide_pndistinct_;
-    S.logits = wide_logits_;
-    S.to_device = [this] { wide_state_to_device(); };
-    S.from_device = [this] { wide_state_from_device(); };
-    S.first_pick = [this](int l) { wide_pick_enqueue(1, l, 0); };
-    S.prefill = [this](int l, int shared, const uint32_t* ids, int n) {
-        if (shared >= 1) wide_prefill_shared(l, shared, ids, n);
-        else wide_prefill(l, ids, n);
-    };
-    S.step = [this](int n) { wide_step_enqueue(n); };
-    S.burst = [this](int n, size_t times, hipGraphExec_t chain) {  // (no stage of the chain reads anything back, the MoE rows hook included: always captured)
-        hipGraphExec_t exec = chain ? chain : wide_step_graph(n);
-        for (size_t i = 0; i < times; ++i) hip_check(hipGraphLaunch(exec, stream_), "graph launch");
-        for (const Layer& L : layers_)  // (a replay runs no host code: the routing record's row count is set here)
-            if (L.moe) L.moe_rec_rows = n;
-    };
-    return S;
+    prompt_proj(n, pn_, H, lm_head_, nullptr, nullptr, b.logits, c.vocab, c.vocab, H, nullptr, "lm head");
 }
 
 std::vector<std::vector<uint32_t>> LlmModel::generate_wide(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,
@@ -3124,8 +2915,8 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_wide(const std::vector<Lan
     if (lanes == 0) lanes = kWideLanes;
     const size_t width = std::min<size_t>((size_t)lanes, reqs.size());
     if (width <= (size_t)kLanes)  // generate_lanes' route (its GEMV step), under this entry's refusals
-        return generate_on_lanes(reqs, (int)std::max<size_t>(width, 1), lane_context, on_token, false, true);
-    return generate_on_lanes(reqs, lanes, lane_context, on_token, true, true);
+        return generate_on_lanes(reqs, (int)std::max<size_t>(width, 1), lane_context, on_token, lane_bank_, true);
+    return generate_on_lanes(reqs, lanes, lane_context, on_token, wide_bank_, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

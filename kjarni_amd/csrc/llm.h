@@ -21,6 +21,7 @@
 #include "encoder.h"
 #include "fp8_kernels.h"
 #include "generation_run.h"
+#include "llm_kernels.h"
 #include "quant_kernels.h"
 #include "sampling.h"
 
@@ -59,8 +60,6 @@ struct LaneRequest {
     GenerateOptions options;
 };
 
-struct LlmLaneState;  // llm_kernels.h
-struct LlmWideState;
 struct ConstraintView;  // constraint_kernels.h
 struct ConstraintRow;
 struct GrammarView;  // grammar_kernels.h
@@ -152,10 +151,10 @@ public:
     bool prefix_reuse() const { return prefix_reuse_; }
     // ---- FP8 checkpoints on the matrix cores (off by default; a no-op on a checkpoint that is not FP8) --------------------------
     // On: a prompt projection on the 64 x 64 route multiplies the FP8 codes themselves (launch_prefill_gemm_fp8) instead of
-    // dequantizing the matrix into the f32 scratch first, and ensure_wide() takes the checkpoint: the wide step then writes Q, K
+    // dequantizing the matrix into the f32 scratch first, and the wide bank takes the checkpoint: the wide step then writes Q, K
     // and V from their three matrices into the staging rows' column segments and rows_finish() runs on the same GEMM.  Off:
-    // everything enqueued is what it was before the switch existed.  Flipping it drops the captured wide graphs and ends a wide
-    // session (wide_begin again).
+    // everything enqueued is what it was before the switch existed.  Flipping it drops the wide bank's captured graphs and ends
+    // its session (lanes_begin(Bank::Wide) again).
     void set_fp8_matrix_cores(bool on);
     bool fp8_matrix_cores() const { return fp8_mc_; }
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
@@ -277,8 +276,11 @@ public:
     std::vector<uint32_t> generate(const std::vector<uint32_t>& prompt, const GenerateOptions& options,
                                    const std::function<bool(uint32_t)>& on_token);
 
-    // ---- lanes: up to kLanes sequences decoded in lock step, each with its own KV cache and position -------------------------
-    static constexpr int kLanes = 8;  // the GEMV kernels are built for <= 8 rows
+    // ---- lanes: sequences decoded in lock step, each with its own KV cache and position.  Two banks of lanes share everything but
+    // the step body: Bank::Lanes runs 1..kLanes sequences on the multi-row GEMV kernels, Bank::Wide 9..kWideLanes on the prompt GEMM.
+    static constexpr int kLanes = 8;       // the GEMV kernels are built for <= 8 rows
+    static constexpr int kWideLanes = 64;  // one M-tile of launch_prefill_gemm: every width up to it reads the weights once per step
+    enum class Bank { Lanes, Wide };
     // generate() for every request, `lanes` (1..8, 0 = 8) of them at a time: the prompts are prefilled into lane caches of
     // min(context(), lane_context) rows (lane_context <= 0: context()) by the prompt routes of forward(), the live lanes then
     // step together (one captured graph per lane count for greedy requests without processors; requests with a repetition
@@ -288,27 +290,26 @@ public:
     // request only.  Throws InvalidConfig (before any GPU work) for lanes outside 0..8 or a prompt longer than a lane.
     std::vector<std::vector<uint32_t>> generate_lanes(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
                                                       const std::function<bool(size_t, uint32_t)>& on_token);
-    // Test hooks: lane caches for `lanes` lanes, all empty; a prompt into one lane; one lock-step step over ids[lanes] for the
-    // lanes with live[lane] != 0 (the others are frozen: nothing of theirs is read or written) returning the final-normed
-    // hidden rows [lanes, hidden] and logits [lanes, vocab]; a lane's cache length and rows.
-    void lanes_begin(int lanes, int lane_context);
-    void lane_prefill(int lane, const uint32_t* ids, int n);
+    // Test hooks, one set for either bank: lane caches for `lanes` lanes (Lanes: 1..8, Wide: 9..64; 0 = the bank's most), all
+    // empty; a prompt into one lane; one lock-step step over ids[lanes] for the lanes with live[lane] != 0 (the others are frozen:
+    // nothing of theirs is read or written) returning the final-normed hidden rows [lanes, hidden] and logits [lanes, vocab]; a
+    // lane's cache length and rows.
+    void lanes_begin(Bank bank, int lanes, int lane_context);
+    void lane_prefill(Bank bank, int lane, const uint32_t* ids, int n);
     // Test hook of the shared-prefix path: rows [0, s) of the single-sequence cache (s <= cache_len()) are copied into the lane
     // (one launch_kv_prefix_copy), then ids[0, n) are prefilled behind them; the lane holds s + n rows.
-    void lane_prefill_shared(int lane, int s, const uint32_t* ids, int n);
-    void lanes_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
-    int lane_cache_len(int lane) const;
-    int lane_capacity() const { return lane_cap_; }
-    void lane_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
+    void lane_prefill_shared(Bank bank, int lane, int s, const uint32_t* ids, int n);
+    void lanes_step(Bank bank, const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
+    int lane_cache_len(Bank bank, int lane) const;
+    int lane_capacity(Bank bank) const { return bank_of(bank).cap; }
+    void lane_kv_rows(Bank bank, int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
     // Projections of lane steps that took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel
     // since load (counted when enqueued: a replayed graph counts once, at capture).
     uint64_t lane_stream_calls() const { return lane_stream_calls_; }
     uint64_t lane_fallback_calls() const { return lane_fallback_calls_; }
 
-    // ---- wide lanes: 9..kWideLanes sequences in lock step, the projections on the prompt GEMM's 64-row tile ------------------
-    static constexpr int kWideLanes = 64;  // one M-tile of launch_prefill_gemm: every width up to it reads the weights once per step
     // generate_lanes() for `lanes` (1..64, 0 = 64) requests at a time.  An effective width min(lanes, requests) of 8 or less runs
-    // generate_lanes' own GEMV step; 9..64 runs wide_step(): the rows-route layer body (one Q|K|V GEMM into the lanes' staging
+    // generate_lanes' own GEMV step; 9..64 runs the wide bank's step: the rows-route layer body (one Q|K|V GEMM into the lanes' staging
     // layout, rotate-and-scatter, the ragged decode attention, rows_finish()), the head as a GEMM, the wide pick -- captured once
     // per (width, lane capacity) for greedy requests without processors.  Results, callback order, stop rules, lane turnover,
     // prefix reuse and the processors / sampling path are generate_lanes'.  The lane caches cost 2 * layers * lanes * rows * kv
@@ -319,7 +320,7 @@ public:
     // Constrained requests (options.constraint or options.grammar, per request; generate_lanes takes them too): the lane that takes
     // the request gets the request's view and a fresh row in its slot of the device's lane automaton table (lane_constraint_kernels.h)
     // before its first pick.  Greedy requests without processors replay step -> (records' slab pass) -> lane apply -> pick -> lane
-    // advance (-> records' finish) as one captured chain per (set, width, records), and the host walks its own copy of each
+    // advance (-> records' finish) as one captured chain per (bank, width, records), and the host walks its own copy of each
     // request's automaton over the drained tokens, ending the request where generate() would; requests with processors or sampling
     // are decided lane by lane through the single-row launchers on the lane's slot, the mask ahead of the processors.  The ids and
     // the outcome (options.constraint_outcome) are generate()'s for that request alone.  A call whose requests carry no automaton
@@ -327,14 +328,6 @@ public:
     // request, an automaton of another device or vocabulary, more than 16 stop ids, check_states of that request's automaton.
     std::vector<std::vector<uint32_t>> generate_wide(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
                                                      const std::function<bool(size_t, uint32_t)>& on_token = nullptr);
-    // Test hooks of the wide route, mirroring the lane hooks (wide_begin takes 9..64 lanes: fewer belong to lanes_begin).
-    void wide_begin(int lanes, int lane_context);
-    void wide_prefill(int lane, const uint32_t* ids, int n);
-    void wide_prefill_shared(int lane, int s, const uint32_t* ids, int n);
-    void wide_step(const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
-    int wide_cache_len(int lane) const;
-    int wide_capacity() const { return wide_cap_; }
-    void wide_kv_rows(int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
 
     // ---- prompt-lookup decoding: greedy generate() that emits several tokens per step ----------------------------------------
     // generate() for a greedy request without logits processors, with every step verifying a draft: the continuation of the
@@ -402,55 +395,87 @@ public:
 
 private:
     LlmModel() = default;
-    void ensure_lanes(int lanes, int lane_context);
-    void lane_prefill_at(int lane, int base, const uint32_t* ids, int n);  // lane_prefill behind `base` rows the lane already holds
-    void lane_copy_prefix(int lane, int s);                                // rows [0, s) of every layer's K and V into the lane
     // Empties the cache down to the rows it may keep for `prompt` (all of them dropped with reuse off) and forwards the rest:
     // leaves the model as reset(); forward(prompt) does.
     void begin_sequence(const std::vector<uint32_t>& prompt);
     int keep_prefix(const uint32_t* prompt, size_t n, size_t limit);  // truncates the cache, counts; returns the rows kept
     void leave_resident(const std::vector<uint32_t>& all);            // what a generate loop leaves: the fed tokens of `all`
-    void lane_step(int lanes);                 // enqueue one lock-step step over lanes [0, lanes)
-    hipGraphExec_t lane_step_graph(int lanes);  // lane_step + the lane pick, captured once per lane count
-    void lane_state_to_device();
-    void lane_state_from_device();
-    // A prompt through forward()'s routes into caches other than the single-sequence ones: the layers' cache pointers are
-    // pointed at k[layer] + off / v[layer] + off (capacity cap, `base` rows already there) for the call, the last position's
-    // logits go to logits_row.  lane_prefill_at and wide_prefill_at are this.
-    void prefill_into(const std::vector<float*>& k, const std::vector<float*>& v, size_t off, int cap, float* logits_row, int base,
-                      const uint32_t* ids, int n);
-    // What generate_lanes' scheduling loop needs of a set of lanes: the host mirror of the device state by field (the 8-lane and
-    // the wide state differ in their array lengths only), the lane buffers, and how to enqueue a prefill, a step and a pick.
-    struct LaneSet {
-        int32_t *token, *pos, *live, *count, *limit, *n_stop;
-        int32_t (*stop)[16];
-        int* len;  // the lanes' cache lengths (host)
-        int hist_stride;
-        int32_t *hist, *ptok, *pdistinct;
-        int *pcounts, *pndistinct;
-        float* logits;
-        std::function<void()> to_device, from_device;
-        std::function<void(int lane)> first_pick;  // the pick on the lane's prefill row alone (no advance)
-        std::function<void(int lane, int shared, const uint32_t* ids, int n)> prefill;  // behind `shared` copied prefix rows
-        std::function<void(int n)> step;                                                // one step, enqueued directly
-        // `times` x (step + pick), replayed from a captured graph where one exists; chain: another captured chain of the same step
-        // to replay in its place (the one with the log-probability records in it), with the burst's own host-side steps around it
-        std::function<void(int n, size_t times, hipGraphExec_t chain)> burst;
+    // The record logs of a bank whose requests set logprobs: [lanes, hist stride] and [lanes, hist stride, KJARNI_SCORE_TOPK_MAX], a
+    // slab scratch for all its rows and one raw-copy row, in one allocation of their own.
+    struct LaneLogs {
+        void* block = nullptr;
+        int stride = 0;
+        float *lp = nullptr, *tlp = nullptr, *copy = nullptr;
+        uint32_t* ids = nullptr;
+        void* scratch = nullptr;
     };
-    LaneSet lane_set();
-    LaneSet wide_set();
-    // generate_lanes / generate_wide behind their own checks of `lanes`: n = min(lanes, requests) lanes of the 8-lane set, or of
-    // the wide set when `wide`.  strict: every refusal is an InvalidConfig (generate_wide's contract).
+    // A bank of lock-step lanes: everything generate_on_lanes() and the test hooks need of one, allocated on first use.
+    struct LaneBank {
+        // the bank's constants: the step body it runs (lane_step() or wide_step_enqueue()), the widths it takes and their refusal,
+        // the lanes of its state layout (LlmLaneState: 8, LlmWideState: 64) and that layout's size, what a step without a session says
+        const bool wide;
+        const int min_lanes, max_lanes;
+        const char* const range_error;
+        const int width;
+        const size_t state_bytes;
+        const char* const begin_error;
+        LaneBank(bool wide_step, int lo, int hi, const char* range, int layout, size_t bytes, const char* begin)
+            : wide(wide_step), min_lanes(lo), max_lanes(hi), range_error(range), width(layout), state_bytes(bytes), begin_error(begin)
+        {
+        }
+        // per layer the lane-major caches [lanes][lane rows][kv] (one stride, alloc_cap * kv, addresses a lane)
+        std::vector<float*> k, v;
+        // One allocation of its own behind everything sized by lanes x rows or lanes x vocab, replaced when either grows: the
+        // caches, the Q|K|V staging rows, the logits rows, the pick history [lanes, hist_stride], the logits processors' history,
+        // distinct tokens, counts [lanes, vocab] and numbers of distinct tokens, and the wide bank's attention scratch.
+        void* block = nullptr;
+        int alloc = 0, alloc_cap = 0, lanes = 0, cap = 0, hist_stride = 0;  // allocated lanes x rows; the session's lanes x rows
+        int len[kWideLanes] = {};                                          // the lanes' cache lengths
+        float *qkv = nullptr, *logits = nullptr, *att = nullptr;
+        int32_t *hist = nullptr, *ptok = nullptr, *pdistinct = nullptr;
+        int *pcounts = nullptr, *pndistinct = nullptr;
+        // fixed: the state on the device and its host mirror, each also by field, the pick scratch, and the device table of (main K,
+        // lane-0 K, main V, lane-0 V) per layer that launch_kv_prefix_copy reads
+        void* state = nullptr;
+        std::unique_ptr<int32_t[]> mirror;
+        LaneStateRef dev, host;
+        unsigned long long* best = nullptr;
+        LlmKvCopyPair* copy_table = nullptr;
+        // captured chains by lane count: step -> pick; step -> records -> pick [k == 1 | k > 1]; step -> the automaton pick [no
+        // records | k == 1 | k > 1]
+        hipGraphExec_t graphs[kWideLanes + 1] = {}, lp_graphs[2][kWideLanes + 1] = {}, auto_graphs[3][kWideLanes + 1] = {};
+        LaneLogs logs;
+    };
+    const LaneBank& bank_of(Bank b) const { return b == Bank::Wide ? wide_bank_ : lane_bank_; }
+    LaneBank& bank_of(Bank b) { return b == Bank::Wide ? wide_bank_ : lane_bank_; }
+    // Validates the width (the wide bank: also the checkpoint and the geometry its step takes), carves the block, builds the copy
+    // table, and starts a session of `lanes` empty lanes.
+    void ensure_lane_bank(LaneBank& b, int lanes, int lane_context);
+    void drop_lane_record_graphs(LaneBank& b);  // the chains that hold the record logs or the automaton table
+    void drop_lane_graphs(LaneBank& b);         // every captured chain of the bank
+    void lane_state_to_device(LaneBank& b);
+    void lane_state_from_device(LaneBank& b);
+    void lane_copy_prefix(LaneBank& b, int lane, int s);  // rows [0, s) of every layer's K and V into the lane
+    // A prompt into one lane behind `base` rows it already holds, through forward()'s routes: the layers' cache pointers (and the
+    // capacity) are pointed at the lane for the call, the last position's logits become the lane's logits row.
+    void lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* ids, int n);
+    void lane_prefill_shared(LaneBank& b, int lane, int s, const uint32_t* ids, int n);
+    // The two step bodies, each one lock-step step over lanes [0, lanes) of its bank enqueued on the stream, logits into the
+    // bank's rows; lane_attention is the middle they share: rotate-and-scatter (Qwen3: behind the per-head norm) of the staging
+    // rows into layer li's lane caches, then the ragged attention over `scratch` into `ctx`.
+    void lane_step(int lanes);
+    void wide_step_enqueue(int lanes);
+    void lane_attention(const LaneBank& b, int lanes, size_t li, float* scratch, float* ctx);
+    void lane_step_enqueue(LaneBank& b, int lanes);  // the bank's step body
+    void lane_pick_enqueue(LaneBank& b, int lanes, int first, int advance);
+    hipGraphExec_t lane_step_graph(LaneBank& b, int lanes);  // step + pick, captured once per (lane count, lane capacity)
+    // `times` x (step + pick) replayed from the captured chain, or from `chain` in its place (the one with the records or the
+    // automata in it)
+    void lane_burst(LaneBank& b, int lanes, size_t times, hipGraphExec_t chain);
+    // generate_lanes / generate_wide behind their own checks of `lanes`: n = min(lanes, requests) lanes of the bank.  strict: every
+    // refusal is an InvalidConfig (generate_wide's contract).
     std::vector<std::vector<uint32_t>> generate_on_lanes(const std::vector<LaneRequest>& requests, int lanes, int lane_context,
-                                                         const std::function<bool(size_t, uint32_t)>& on_token, bool wide, bool strict);
-    void ensure_wide(int lanes, int lane_context);
-    void wide_prefill_at(int lane, int base, const uint32_t* ids, int n);
-    void wide_copy_prefix(int lane, int s);
-    void wide_step_enqueue(int lanes);            // one wide step over lanes [0, lanes), logits into wide_logits_
-    void wide_pick_enqueue(int lanes, int first, int advance);
-    hipGraphExec_t wide_step_graph(int lanes);    // wide step + pick, captured once per (width, lane capacity)
-    void wide_state_to_device();
-    void wide_state_from_device();
+                                                         const std::function<bool(size_t, uint32_t)>& on_token, LaneBank& b, bool strict);
     void* upload_weight(const std::vector<float>& host);  // f32 or bf16 according to bf16_
     float* upload_f32(const std::vector<float>& host);
     float* dalloc(size_t floats);
@@ -558,27 +583,18 @@ private:
     void logprob_partial_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, float* copy);
     void logprob_finish_on(const float* logits, int rows, const int32_t* live, int k, void* scratch, const float* raw, const int32_t* token,
                            const int* count, int bias, int stride, float* lp, uint32_t* ids, float* tlp);
-    // Lanes (generate_lanes / generate_wide with a request that sets logprobs): the record logs of a lane set, [lanes, hist stride]
-    // and [lanes, hist stride, KJARNI_SCORE_TOPK_MAX], a slab scratch for all its rows and one raw-copy row; the two launches over
+    // Lanes (generate_lanes / generate_wide with a request that sets logprobs): the bank's record logs; the two launches over
     // lanes [first, first + rows) ahead of the pick (frozen lanes write nothing; the record index is the lane's own device-held
     // count, so a lane that takes the next request starts at record 0); the captured chain step -> records -> pick.
-    struct LaneLogs {
-        void* block = nullptr;
-        int stride = 0;
-        float *lp = nullptr, *tlp = nullptr, *copy = nullptr;
-        uint32_t* ids = nullptr;
-        void* scratch = nullptr;
-    };
-    void ensure_lane_logprobs(bool wide);
-    void drop_lane_logprob_graphs(bool wide);
-    void lane_logprobs_enqueue(bool wide, int first, int rows, int k);
-    hipGraphExec_t lane_logprob_step_graph(bool wide, int lanes, int k);
+    void ensure_lane_logprobs(LaneBank& b);
+    void lane_logprobs_enqueue(LaneBank& b, int first, int rows, int k);
+    hipGraphExec_t lane_logprob_step_graph(LaneBank& b, int lanes, int k);
     // Constrained lanes: the device's automaton table (allocated on first use) with its host copy; the pick of lanes [first, first
     // + rows) under their automata -- (records' slab pass) -> lane apply -> pick -> lane advance (-> records' finish, on the lanes
-    // and tokens the advance reports) --; the captured chain step -> that, per (set, lanes, no records | k == 1 | k > 1).
+    // and tokens the advance reports) --; the captured chain step -> that, per (bank, lanes, no records | k == 1 | k > 1).
     void ensure_lane_automata();
-    void lane_automaton_pick_enqueue(bool wide, int first, int rows, int advance, bool records, int k);
-    hipGraphExec_t lane_automaton_step_graph(bool wide, int lanes, bool records, int k);
+    void lane_automaton_pick_enqueue(LaneBank& b, int first, int rows, int advance, bool records, int k);
+    hipGraphExec_t lane_automaton_step_graph(LaneBank& b, int lanes, bool records, int k);
     void enqueue_logprob_partial(int k, bool copy);   // the slab pass over logits_ (copy: the row also goes to lp_copy_)
     // The record of the token at *token: read from lp_copy_ (from_copy) or logits_, written at index (count ? *count : 0) + bias.
     void enqueue_logprob_finish(int k, bool from_copy, const int32_t* token, const int* count, int bias);
@@ -724,43 +740,13 @@ private:
     uint32_t* lp_ids_log_ = nullptr;
     int32_t* lp_tok_ = nullptr;
     hipGraphExec_t lp_graphs_[3][2] = {};
-    LaneLogs lane_logs_[2];  // [lanes | wide]
-    hipGraphExec_t lane_lp_graphs_[2][kLanes + 1] = {}, wide_lp_graphs_[2][kWideLanes + 1] = {};  // [k == 1 | k > 1][lanes]
     LaneAutomatonTable* lane_auto_ = nullptr;
     std::unique_ptr<LaneAutomatonTable> lane_auto_host_;
-    hipGraphExec_t lane_auto_graphs_[3][kLanes + 1] = {}, wide_auto_graphs_[3][kWideLanes + 1] = {};  // [no records | k == 1 | k > 1][lanes]
-    // lanes (allocated on first use): per layer the lane-major caches [lanes][lane rows][kv] (one stride addresses a lane), the
-    // Q|K|V staging rows, the logits rows, the lane state on the device and its host mirror, the per-lane pick history
-    std::vector<float*> lane_k_, lane_v_;
-    void* lane_block_ = nullptr;  // one allocation of its own behind everything sized by lanes x rows, replaced when they grow
-    int lane_alloc_ = 0, lane_alloc_cap_ = 0, lanes_ = 0, lane_cap_ = 0, lane_hist_stride_ = 0;
-    int lane_len_[kLanes] = {};
-    float *lane_qkv_ = nullptr, *lane_logits_ = nullptr;
-    LlmLaneState* lane_state_ = nullptr;
-    std::unique_ptr<LlmLaneState> lane_host_;
-    int32_t* lane_hist_ = nullptr;
-    unsigned long long* lane_best_ = nullptr;
-    // logits processors per lane: history, distinct tokens, counts [lanes][vocab], number of distinct tokens
-    int32_t *lane_ptok_ = nullptr, *lane_pdistinct_ = nullptr;
-    int *lane_pcounts_ = nullptr, *lane_pndistinct_ = nullptr;
-    hipGraphExec_t lane_graphs_[kLanes + 1] = {};
+    // the two banks of lanes (LaneBank above)
+    LaneBank lane_bank_{false, 1, kLanes, "lanes must be 1..8", kMaxLanes, sizeof(LlmLaneState), "lanes_begin first"};
+    LaneBank wide_bank_{true, kLanes + 1, kWideLanes, "wide lanes must be 9..64 (8 or fewer are the lanes route's)", kMaxWideLanes,
+                        sizeof(LlmWideState), "wide_begin first"};
     uint64_t lane_stream_calls_ = 0, lane_fallback_calls_ = 0;
-    // wide lanes (allocated on first use, sized by the width asked for): one allocation of its own holds the lane-major caches
-    // of every layer, the staging rows, the logits rows, the attention scratch, the pick history and the processors' per-lane
-    // history / distinct list / counts; the state (device + host mirror), the pick scratch and the prefix-copy table are fixed
-    std::vector<float*> wide_k_, wide_v_;
-    void* wide_block_ = nullptr;
-    int wide_alloc_ = 0, wide_alloc_cap_ = 0, wide_lanes_ = 0, wide_cap_ = 0, wide_hist_stride_ = 0;
-    int wide_len_[kWideLanes] = {};
-    float *wide_qkv_ = nullptr, *wide_logits_ = nullptr, *wide_att_ = nullptr;
-    LlmWideState* wide_state_ = nullptr;
-    std::unique_ptr<LlmWideState> wide_host_;
-    int32_t* wide_hist_ = nullptr;
-    unsigned long long* wide_best_ = nullptr;
-    int32_t *wide_ptok_ = nullptr, *wide_pdistinct_ = nullptr;
-    int *wide_pcounts_ = nullptr, *wide_pndistinct_ = nullptr;
-    LlmKvCopyPair* wide_copy_table_ = nullptr;
-    hipGraphExec_t wide_graphs_[kWideLanes + 1] = {};
     // prompt-lookup decoding (allocated on first use): the ids and logits rows of a verify step, the device state, the history
     // (prompt + picks), the per-step (m, a) log, and one captured chain per row count for the n-gram bounds in lookup_ngram_
     float* vlogits_ = nullptr;
@@ -802,13 +788,11 @@ private:
     size_t score_tk_scratch_bytes_ = 0;
     bool score_fused_ = true;
     uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0;
-    // prefix reuse: the tokens of the cache rows (host only), the switch, the counters, and the device table of
-    // (main K, lane K base, main V, lane V base) per layer that launch_kv_prefix_copy reads (built in ensure_lanes)
+    // prefix reuse: the tokens of the cache rows (host only), the switch, the counters
     std::vector<uint32_t> resident_;
     bool prefix_reuse_ = false;
     bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
-    LlmKvCopyPair* lane_copy_table_ = nullptr;
 };
 
 }  // namespace kjarni

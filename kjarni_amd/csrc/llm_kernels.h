@@ -128,18 +128,42 @@ hipError_t launch_gelu_tanh(float* x, size_t n, hipStream_t stream);
 hipError_t launch_argmax(const float* logits, int vocab, unsigned long long* best_scratch, int32_t* out, int32_t* history, int* count,
                          int* pos, hipStream_t stream);
 
-// ---- lanes: up to kMaxLanes independent sequences decoded in lock step (LlmModel::generate_lanes) ------------------------
-constexpr int kMaxLanes = 8, kMaxLaneStops = 16;
+// ---- lanes: sequences decoded in lock step, 1..kMaxLanes on the GEMV kernels (LlmModel::generate_lanes) and 9..kMaxWideLanes on
+// the prompt GEMM (LlmModel::generate_wide; 64 = one M-tile of it: every width up to it streams the weights once per step) ----------
+constexpr int kMaxLanes = 8, kMaxWideLanes = 64, kMaxLaneStops = 16;
 // Everything the next lock-step step needs, on the device (so the step replays as a captured graph); the host reads it back
-// and rewrites it between bursts of steps.
-struct LlmLaneState {
-    int32_t token[kMaxLanes];  // the lane's next input token
-    int32_t pos[kMaxLanes];    // its position = the lane's cache length
-    int32_t live[kMaxLanes];   // 0: frozen (finished, or no prompt) -- the step writes nothing for it
-    int32_t count[kMaxLanes];  // tokens picked for the lane's current request (history entries)
-    int32_t limit[kMaxLanes];  // picks after which the lane is done (max_new_tokens and the context limit)
-    int32_t n_stop[kMaxLanes];
-    int32_t stop[kMaxLanes][kMaxLaneStops];  // picking one of these ends the lane
+// and rewrites it between bursts of steps.  One definition, two layouts: N = 8 and N = 64.
+template <int N>
+struct LlmLaneStateT {
+    int32_t token[N];  // the lane's next input token
+    int32_t pos[N];    // its position = the lane's cache length
+    int32_t live[N];   // 0: frozen (finished, or no prompt) -- the step writes nothing for it
+    int32_t count[N];  // tokens picked for the lane's current request (history entries)
+    int32_t limit[N];  // picks after which the lane is done (max_new_tokens and the context limit)
+    int32_t n_stop[N];
+    int32_t stop[N][kMaxLaneStops];  // picking one of these ends the lane
+};
+using LlmLaneState = LlmLaneStateT<kMaxLanes>;
+using LlmWideState = LlmLaneStateT<kMaxWideLanes>;
+// Either layout by field, passed by value: what the lane launchers and the pick's finalize kernel take.  Made from a state in
+// device memory (only addresses are formed) or from its host mirror.
+struct LaneStateRef {
+    int32_t *token = nullptr, *pos = nullptr, *live = nullptr, *count = nullptr, *limit = nullptr, *n_stop = nullptr;
+    int32_t (*stop)[kMaxLaneStops] = nullptr;
+    int width = 0;  // the layout's lanes: kMaxLanes or kMaxWideLanes
+    LaneStateRef() = default;
+    template <int N>
+    LaneStateRef(LlmLaneStateT<N>* s)
+        : token(s->token), pos(s->pos), live(s->live), count(s->count), limit(s->limit), n_stop(s->n_stop), stop(s->stop), width(N)
+    {
+    }
+    // the layout of `width` lanes at `base` (null for any other width)
+    static LaneStateRef at(void* base, int width)
+    {
+        if (width == kMaxLanes) return LaneStateRef(static_cast<LlmLaneState*>(base));
+        if (width == kMaxWideLanes) return LaneStateRef(static_cast<LlmWideState*>(base));
+        return LaneStateRef();
+    }
 };
 // launch_llm_gemv for 2-8 independent rows: the multi-row weight-streaming kernel where llm_gemv_lanes_takes() (k >= 512,
 // 16-byte aligned operands), else launch_llm_gemv's one-wave-per-column kernel; *streamed (may be null) says which ran.
@@ -151,21 +175,23 @@ struct LlmGemvLanesRoute {
 };
 LlmGemvLanesRoute llm_gemv_lanes_route(const LlmGemvArgs& args);
 hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& args, hipStream_t stream, int* streamed);
-// qkv [lanes, (n_heads + 2 n_kv_heads) * head_dim]: Q rotated in place at state->pos[lane], K rotated (rotate == 0: copied) and V
-// copied to row pos[lane] of cache + lane * lane_stride; frozen lanes and positions >= capacity write nothing.
+// qkv [lanes, (n_heads + 2 n_kv_heads) * head_dim]: Q rotated in place at state.pos[lane], K rotated (rotate == 0: copied) and V
+// copied to row pos[lane] of cache + lane * lane_stride; frozen lanes and positions >= capacity write nothing.  A workgroup per
+// lane; lanes > state.width is refused (as by every launcher that takes the view).
 hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
                                     const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
-                                    const LlmLaneState* state, int rotate, hipStream_t stream);
+                                    LaneStateRef state, int rotate, hipStream_t stream);
 // The same for Qwen3: Q and K are RMS-normalised per head (gamma_q / gamma_k [head_dim], eps) before the rotation.
 hipError_t launch_lane_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
                                             const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
-                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmLaneState* state,
+                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, LaneStateRef state,
                                             hipStream_t stream);
-// Per-lane argmax over rows [first_lane, first_lane + lanes) of logits [kMaxLanes, ld] (last maximum wins) for the live lanes:
-// appended to history[lane, count], count (and pos when `advance`: after a step) + 1, live cleared on a stop id / the limit /
-// a full cache, else token = the pick.  best_scratch: kMaxLanes zero-initialised u64 (re-zeroed by the call).
+// Per-lane argmax over rows [first_lane, first_lane + lanes) of logits [state.width, ld] (argmax_partial_kernel: last maximum
+// wins) for the live lanes, then the finalize: appended to history[lane, count], count (and pos when `advance`: after a step)
+// + 1, live cleared on a stop id / the limit / a full cache, else token = the pick.  best_scratch: state.width zero-initialised
+// u64 (re-zeroed by the call).
 hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                            LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
+                            LaneStateRef state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
 // Shared prompt prefix: `count` floats from the start of every layer's single-sequence K and V cache into a lane's caches, one
 // launch for all layers.  table[layer] (device memory) = the source pointers and the lane-0 destination pointers; dst_offset =
 // the lane's offset in floats.  Bit-exact; 16-byte vector copies where source and destination are 16-byte aligned, 4-byte
@@ -177,32 +203,6 @@ struct LlmKvCopyPair {
     float* dst_v;
 };
 hipError_t launch_kv_prefix_copy(const LlmKvCopyPair* table, int layers, int64_t dst_offset, int64_t count, hipStream_t stream);
-
-// ---- wide lanes: 9..kMaxWideLanes sequences in lock step, the projections on the prompt GEMM (LlmModel::generate_wide) -------
-constexpr int kMaxWideLanes = 64;  // one M-tile of the prompt GEMM: every width up to it streams the weights once per step
-// LlmLaneState for kMaxWideLanes lanes (same fields, same meaning).
-struct LlmWideState {
-    int32_t token[kMaxWideLanes];
-    int32_t pos[kMaxWideLanes];
-    int32_t live[kMaxWideLanes];
-    int32_t count[kMaxWideLanes];
-    int32_t limit[kMaxWideLanes];
-    int32_t n_stop[kMaxWideLanes];
-    int32_t stop[kMaxWideLanes][kMaxLaneStops];
-};
-// launch_lane_rope_scatter / launch_lane_qk_norm_rope_scatter over an LlmWideState: the same two kernels (they take the position
-// and live arrays, a workgroup per lane), for up to kMaxWideLanes lanes.
-hipError_t launch_wide_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
-                                    const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
-                                    const LlmWideState* state, int rotate, hipStream_t stream);
-hipError_t launch_wide_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
-                                            const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
-                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmWideState* state,
-                                            hipStream_t stream);
-// launch_lane_pick over an LlmWideState: argmax_partial_kernel over rows [first_lane, first_lane + lanes) of logits
-// [kMaxWideLanes, ld], then the wide finalize.  best_scratch: kMaxWideLanes zero-initialised u64 (re-zeroed by the call).
-hipError_t launch_wide_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                            LlmWideState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream);
 
 // ---- prompt-lookup decoding (LlmModel::generate_lookup): draft from the sequence's own history, verify in one multi-row step
 constexpr int kLookupMaxDraft = 7, kLookupMaxNgram = 4;

@@ -2546,23 +2546,25 @@ __global__ __launch_bounds__(256) void lane_rope_scatter_kernel(float* __restric
 
 // The pick of a live lane: the token joins the lane's history, count (and, after a step, pos) advance; the lane stays live
 // -- and the token becomes its next input -- unless the token is one of its stop ids, it has its max_new_tokens, or its
-// cache is full.
-__global__ void lane_pick_finalize_kernel(unsigned long long* __restrict__ best, LlmLaneState* __restrict__ st,
-                                          int32_t* __restrict__ history, int hist_stride, int first_lane, int lanes, int capacity,
-                                          int advance)
+// cache is full.  One wave, a thread per lane of [first_lane, first_lane + lanes) of either layout; a lane past the layout, a
+// count that is no history entry and stop ids past the list are not followed.
+__global__ __launch_bounds__(kMaxWideLanes) void lane_pick_finalize_kernel(unsigned long long* __restrict__ best, LaneStateRef st,
+                                                                           int32_t* __restrict__ history, int hist_stride, int first_lane,
+                                                                           int lanes, int capacity, int advance)
 {
     const int l = first_lane + threadIdx.x;
-    if (l >= first_lane + lanes || !st->live[l]) return;
+    if (l >= first_lane + lanes || l >= st.width || !st.live[l]) return;
     const int tok = (int)(uint32_t)(best[l] & 0xFFFFFFFFull);
     best[l] = 0ull;
-    const int cnt = st->count[l];
-    if (cnt < hist_stride) history[(int64_t)l * hist_stride + cnt] = tok;
-    st->count[l] = cnt + 1;
-    if (advance) st->pos[l] += 1;
-    bool stop = cnt + 1 >= st->limit[l] || st->pos[l] >= capacity;
-    for (int e = 0; e < st->n_stop[l]; ++e) stop = stop || st->stop[l][e] == tok;
-    if (stop) st->live[l] = 0;
-    else st->token[l] = tok;
+    const int cnt = st.count[l];
+    if (cnt >= 0 && cnt < hist_stride) history[(int64_t)l * hist_stride + cnt] = tok;
+    st.count[l] = cnt + 1;
+    if (advance) st.pos[l] += 1;
+    bool stop = cnt + 1 >= st.limit[l] || st.pos[l] >= capacity;
+    const int ns = min(st.n_stop[l], kMaxLaneStops);
+    for (int e = 0; e < ns; ++e) stop = stop || st.stop[l][e] == tok;
+    if (stop) st.live[l] = 0;
+    else st.token[l] = tok;
 }
 
 }  // namespace
@@ -2655,26 +2657,26 @@ hipError_t launch_llm_gemv_lanes(const LlmGemvArgs& a, hipStream_t stream, int* 
 
 hipError_t launch_lane_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
                                     const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
-                                    const LlmLaneState* state, int rotate, hipStream_t stream)
+                                    LaneStateRef state, int rotate, hipStream_t stream)
 {
     if (lanes <= 0) return hipSuccess;
-    if (lanes > LLM_MAX_ROWS || (rotate && (head_dim & 1))) return hipErrorInvalidValue;
+    if (lanes > state.width || (rotate && (head_dim & 1))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lane_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim, cos_t,
-                       sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live, rotate);
+                       sin_t, k_cache, v_cache, lane_stride, capacity, state.pos, state.live, rotate);
     return hipGetLastError();
 }
 
 hipError_t launch_lane_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                            LlmLaneState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream)
+                            LaneStateRef state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream)
 {
     if (lanes <= 0) return hipSuccess;
-    if (first_lane < 0 || first_lane + lanes > LLM_MAX_ROWS) return hipErrorInvalidValue;
+    if (first_lane < 0 || first_lane + lanes > state.width || vocab < 1 || hist_stride < 1) return hipErrorInvalidValue;
     int blocks = (vocab + 2047) / 2048;
     if (blocks > 64) blocks = 64;
     hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)lanes), dim3(256), 0, stream, logits, ld, vocab, first_lane,
-                       static_cast<const int*>(state->live), best_scratch);
-    hipLaunchKernelGGL(lane_pick_finalize_kernel, dim3(1), dim3(64), 0, stream, best_scratch, state, history, hist_stride, first_lane, lanes,
-                       capacity, advance);
+                       static_cast<const int*>(state.live), best_scratch);
+    hipLaunchKernelGGL(lane_pick_finalize_kernel, dim3(1), dim3(kMaxWideLanes), 0, stream, best_scratch, state, history, hist_stride, first_lane,
+                       lanes, capacity, advance);
     return hipGetLastError();
 }
 
@@ -2812,79 +2814,13 @@ hipError_t launch_qk_norm_rope(float* q, int64_t ldq, float* k, int64_t ldk, int
 
 hipError_t launch_lane_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
                                             const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
-                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmLaneState* state,
+                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, LaneStateRef state,
                                             hipStream_t stream)
 {
     if (lanes <= 0) return hipSuccess;
-    if (lanes > LLM_MAX_ROWS || head_dim < 2 || head_dim > 128 || (head_dim & 1)) return hipErrorInvalidValue;
+    if (lanes > state.width || head_dim < 2 || head_dim > 128 || (head_dim & 1)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lane_qk_norm_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim,
-                       gamma_q, gamma_k, eps, cos_t, sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Wide lanes (llm.cpp: LlmModel::wide_step): the lane kernels over an LlmWideState.  The two scatter kernels take the position
-// and live arrays and run a workgroup per lane, so the wide launchers are grids of up to kMaxWideLanes workgroups over them;
-// the pick's partial stage is argmax_partial_kernel, a row per blockIdx.y, and only its finalize reads the wider state.
-namespace {
-
-// lane_pick_finalize_kernel over an LlmWideState: one thread per lane of [first_lane, first_lane + lanes).
-__global__ __launch_bounds__(kMaxWideLanes) void wide_pick_finalize_kernel(unsigned long long* __restrict__ best,
-                                                                           LlmWideState* __restrict__ st, int32_t* __restrict__ history,
-                                                                           int hist_stride, int first_lane, int lanes, int capacity,
-                                                                           int advance)
-{
-    const int l = first_lane + threadIdx.x;
-    if (l >= first_lane + lanes || l >= kMaxWideLanes || !st->live[l]) return;
-    const int tok = (int)(uint32_t)(best[l] & 0xFFFFFFFFull);
-    best[l] = 0ull;
-    const int cnt = st->count[l];
-    if (cnt >= 0 && cnt < hist_stride) history[(int64_t)l * hist_stride + cnt] = tok;
-    st->count[l] = cnt + 1;
-    if (advance) st->pos[l] += 1;
-    bool stop = cnt + 1 >= st->limit[l] || st->pos[l] >= capacity;
-    const int ns = min(st->n_stop[l], kMaxLaneStops);
-    for (int e = 0; e < ns; ++e) stop = stop || st->stop[l][e] == tok;
-    if (stop) st->live[l] = 0;
-    else st->token[l] = tok;
-}
-
-}  // namespace
-
-hipError_t launch_wide_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim, const float* cos_t,
-                                    const float* sin_t, float* k_cache, float* v_cache, int64_t lane_stride, int capacity,
-                                    const LlmWideState* state, int rotate, hipStream_t stream)
-{
-    if (lanes <= 0) return hipSuccess;
-    if (lanes > kMaxWideLanes || (rotate && (head_dim & 1))) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lane_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim, cos_t,
-                       sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live, rotate);
-    return hipGetLastError();
-}
-
-hipError_t launch_wide_qk_norm_rope_scatter(float* qkv, int64_t ld, int lanes, int n_heads, int n_kv_heads, int head_dim,
-                                            const float* gamma_q, const float* gamma_k, float eps, const float* cos_t, const float* sin_t,
-                                            float* k_cache, float* v_cache, int64_t lane_stride, int capacity, const LlmWideState* state,
-                                            hipStream_t stream)
-{
-    if (lanes <= 0) return hipSuccess;
-    if (lanes > kMaxWideLanes || head_dim < 2 || head_dim > 128 || (head_dim & 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lane_qk_norm_rope_scatter_kernel, dim3((unsigned)lanes), dim3(256), 0, stream, qkv, ld, n_heads, n_kv_heads, head_dim,
-                       gamma_q, gamma_k, eps, cos_t, sin_t, k_cache, v_cache, lane_stride, capacity, state->pos, state->live);
-    return hipGetLastError();
-}
-
-hipError_t launch_wide_pick(const float* logits, int64_t ld, int vocab, int lanes, int first_lane, unsigned long long* best_scratch,
-                            LlmWideState* state, int32_t* history, int hist_stride, int capacity, int advance, hipStream_t stream)
-{
-    if (lanes <= 0) return hipSuccess;
-    if (first_lane < 0 || first_lane + lanes > kMaxWideLanes || vocab < 1 || hist_stride < 1) return hipErrorInvalidValue;
-    int blocks = (vocab + 2047) / 2048;
-    if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(argmax_partial_kernel, dim3((unsigned)blocks, (unsigned)lanes), dim3(256), 0, stream, logits, ld, vocab, first_lane,
-                       static_cast<const int*>(state->live), best_scratch);
-    hipLaunchKernelGGL(wide_pick_finalize_kernel, dim3(1), dim3(kMaxWideLanes), 0, stream, best_scratch, state, history, hist_stride, first_lane,
-                       lanes, capacity, advance);
+                       gamma_q, gamma_k, eps, cos_t, sin_t, k_cache, v_cache, lane_stride, capacity, state.pos, state.live);
     return hipGetLastError();
 }
 

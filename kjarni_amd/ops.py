@@ -1267,7 +1267,7 @@ def score_head_topk(hidden, W, targets, top_k, bf16=False, slab_tiles=0, fused=T
 
 def wide_rope_scatter(qkv, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, sin_t, k_cache, v_cache, capacity: int, pos, live,
                       rotate: bool = True, gamma_q=None, gamma_k=None, eps: float = 0.0, device: int = 0):
-    """One launch_wide_rope_scatter (gamma_q / gamma_k given: launch_wide_qk_norm_rope_scatter, the Qwen3 form) on host arrays
+    """One launch_lane_rope_scatter (gamma_q / gamma_k given: launch_lane_qk_norm_rope_scatter, the Qwen3 form) over the 64-lane state on host arrays
     (kjarni_hip_op_wide_rope_scatter).  qkv [lanes, ld] holds Q | K | V of each lane's new token; k_cache / v_cache
     [lanes, lane rows, kv] (lane rows >= capacity).  Returns copies (qkv, k_cache, v_cache) after the call: Q rotated in place,
     K rotated (rotate False: copied) and V copied to row pos[lane] of the lane's caches, nothing for a lane with live == 0 or
@@ -1291,7 +1291,7 @@ def wide_rope_scatter(qkv, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, 
 
 def wide_pick(logits, state: "_ffi.KjarniHipWideState", history, capacity: int, lanes: Optional[int] = None, first_lane: int = 0,
               advance: bool = True, vocab: Optional[int] = None, device: int = 0):
-    """One launch_wide_pick (kjarni_hip_op_wide_pick) over lanes [first_lane, first_lane + lanes) of logits [rows, ld]: `state` is
+    """One launch_lane_pick over the 64-lane state (kjarni_hip_op_wide_pick) over lanes [first_lane, first_lane + lanes) of logits [rows, ld]: `state` is
     updated in place; returns the history [64, stride] after the call (a copy)."""
     lg = np.ascontiguousarray(logits, np.float32)
     hist = np.array(history, np.int32, order="C")

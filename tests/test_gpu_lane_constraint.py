@@ -265,6 +265,106 @@ def test_pick_and_advance_every_branch(wide):
     assert la2.states[2] == q_yes and la2.done[2] == 1 and st2.live[2] == 0 and la2.states[1] == q0 and la2.violated[1] == -7
 
 
+# ---- one finalize kernel, two state layouts -------------------------------------------------------------------------------------------
+
+_FIELDS = ("token", "pos", "live", "count", "limit", "n_stop")
+
+
+def _two_layout_contents(vocab, cap, stride, UNT):
+    """Lanes 0..7 as both layouts hold them, and a logits row per lane.  Per triple of lanes a launch touches ([0, 3) and [5, 8)):
+    0 a tie (the last maximum wins) and stays live, 1 frozen, 2 at its limit; 5 picks a stop id (the last of three, in a tied row),
+    6 has a full cache once the pick advances, 7 a tie and its limit.  Lanes 3 and 4 are live and never in a range."""
+    rng = np.random.default_rng(vocab)
+    logits = rng.standard_normal((8, vocab)).astype(np.float32)
+    a, z = (2, 6) if vocab <= 8 else (5, vocab - 1)           # 2 049 tokens: the two maxima lie in different argmax blocks
+    for l in (0, 5, 7):
+        logits[l, a] = logits[l, z] = 9.0
+    for l in (1, 2, 3, 4, 6):
+        logits[l, (3 * l) % vocab] = 9.0
+    lanes = []
+    for l in range(8):
+        s = dict(token=UNT - l, pos=10 + l, live=1, count=l % 3, limit=1 << 20, n_stop=2, stop=[vocab + 1, vocab + 2] + [UNT] * 14)
+        lanes.append(s)
+    lanes[1]["live"] = 0
+    lanes[2]["limit"] = lanes[2]["count"] + 1
+    lanes[5]["n_stop"], lanes[5]["stop"][:3] = 3, [vocab + 1, a, z]
+    lanes[6]["pos"] = cap - 1
+    lanes[7]["limit"] = lanes[7]["count"] + 1
+    return logits, lanes
+
+
+def _fill_layout(st, hist, lanes, rows, UNT):
+    for l in range(rows):                                 # behind lane 7 (the 64-lane layout): live sentinels no range reaches
+        s = lanes[l] if l < 8 else dict(token=UNT - l, pos=UNT, live=1, count=2, limit=UNT, n_stop=16, stop=[UNT] * 16)
+        for f in _FIELDS:
+            getattr(st, f)[l] = s[f]
+        for e in range(16):
+            st.stop[l][e] = s["stop"][e]
+    hist[:] = UNT
+    for l in range(8):                                    # the history rows hold earlier picks up to the lane's count
+        hist[l, :lanes[l]["count"]] = 100 + l
+
+
+def _read_layout(st, rows):
+    return {f: [getattr(st, f)[l] for l in range(rows)] for f in _FIELDS} | {"stop": [[st.stop[l][e] for e in range(16)] for l in range(rows)]}
+
+
+def _pick_rule(logits, lanes, first, n, cap, advance, stride):
+    """launch_lane_pick's rule on the host: TS.last_max, then the finalize (count, pos, history, the three ways a lane ends)."""
+    want, hist = [dict(s, stop=list(s["stop"])) for s in lanes], {}
+    for l in range(first, first + n):
+        s = want[l]
+        if not s["live"]:
+            continue
+        tok, cnt = TS.last_max(logits[l]), s["count"]
+        if 0 <= cnt < stride:
+            hist[(l, cnt)] = tok
+        s["count"], s["pos"] = cnt + 1, s["pos"] + (1 if advance else 0)
+        if cnt + 1 >= s["limit"] or s["pos"] >= cap or tok in s["stop"][:min(s["n_stop"], 16)]:
+            s["live"] = 0
+        else:
+            s["token"] = tok
+    return want, hist
+
+
+@pytest.mark.parametrize("advance", [0, 1])
+@pytest.mark.parametrize("first_lane", [0, 5])
+@pytest.mark.parametrize("vocab", [8, 2049])
+def test_the_pick_is_one_kernel_over_both_state_layouts(vocab, first_lane, advance):
+    """The same lanes 0..7 through kjarni_hip_op_lane_automaton_pick (every slot kind 0: the plain pick) in the 8-lane and in the
+    64-lane layout: the same state, history rows and scratch, the host rule's, and nothing else written.  The hook itself fails a
+    call whose scratch does not come back all zero or whose guard words around logits, state, history, scratch or table changed, so
+    the scratch and the guards are equal between the layouts wherever both calls return."""
+    from kjarni_amd import _ffi
+    K = _K()
+    n, stride, cap, UNT = 3, 6, 40, -77
+    logits, lanes = _two_layout_contents(vocab, cap, stride, UNT)
+    want, want_hist = _pick_rule(logits, lanes, first_lane, n, cap, advance, stride)
+    assert TS.last_max(logits[0]) == TS.last_max(logits[5]) == lanes[5]["stop"][2] == (vocab - 1 if vocab > 8 else 6)   # the later maximum
+    got = {}
+    for rows, st in ((8, _ffi.KjarniHipLaneState()), (64, _ffi.KjarniHipWideState())):
+        hist = np.empty((rows, stride), np.int32)
+        _fill_layout(st, hist, lanes, rows, UNT)
+        before, hist0 = _read_layout(st, rows), hist.copy()
+        la = K.LaneAutomata([None] * 8)
+        la.pick(logits[:first_lane + n], st, hist, cap, lanes=n, first_lane=first_lane, advance=advance)
+        after = _read_layout(st, rows)
+        in_range = (np.arange(64) >= first_lane) & (np.arange(64) < first_lane + n)              # kind 0: the automata saw nothing
+        assert (la.violated == np.where(in_range, 0, -7)).all() and (la.states == 0).all() and (la.done == 0).all()
+        for l in range(rows):
+            exp = {f: want[l][f] for f in _FIELDS + ("stop",)} if l < 8 else {f: before[f][l] for f in before}
+            assert {f: after[f][l] for f in after} == exp, f"{rows}-lane layout, lane {l}"
+            exp_row = hist0[l].copy()
+            for (hl, at), tok in want_hist.items():
+                if hl == l:
+                    exp_row[at] = tok
+            assert (hist[l] == exp_row).all(), f"{rows}-lane layout, history row {l}"
+        got[rows] = ({f: [after[f][l] for l in range(8)] for f in after}, hist[:8].copy())
+    assert got[8][0] == got[64][0] and (got[8][1] == got[64][1]).all()
+    live = [want[l]["live"] for l in range(first_lane, first_lane + n)]
+    assert live == ([1, 0, 0] if first_lane == 0 else [0, 0 if advance else 1, 0])               # every way a lane ends was taken
+
+
 # ---- the loops -------------------------------------------------------------------------------------------------------------------------
 
 class _Case:
