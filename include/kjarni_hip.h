@@ -903,6 +903,15 @@ void kjarni_hip_decoder_set_prefix_reuse(KjarniHipDecoder* decoder, int32_t on);
  * kjarni_hip_decoder_fp8_matrix_cores reads it back (0 for NULL). */
 void kjarni_hip_decoder_set_fp8_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
 int32_t kjarni_hip_decoder_fp8_matrix_cores(const KjarniHipDecoder* decoder);
+/* GGUF checkpoints (Q8_0 / Q4_K / Q6_K) on the matrix cores (off by default; a no-op on a checkpoint that is not GGUF-quantized; a
+ * NULL handle is ignored).  On: the prompt projections of up to a few hundred rows multiply the integer codes themselves on the bf16
+ * matrix cores (launch_prefill_gemm_ggml), the block and sub-block scales applied in f32, instead of writing every matrix as f32
+ * first, and the checkpoint is accepted on the wide lanes (9 .. 64), whose step then runs Q, K, V, the MLP and the head through the
+ * same GEMM.  Off: everything enqueued is what it was before the switch existed, the refusal above 8 lanes included.  Flipping it
+ * drops the captured wide-step graphs.  kjarni_hip_decoder_ggml_matrix_cores reads it back (0 for NULL).
+ * kjarni_hip_decoder_set_fp8_matrix_cores stays a no-op on a GGUF checkpoint, and this switch on an FP8 one. */
+void kjarni_hip_decoder_set_ggml_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
+int32_t kjarni_hip_decoder_ggml_matrix_cores(const KjarniHipDecoder* decoder);
 /* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
  * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
  * tokens as kept and the rest of the prompt as computed. */
@@ -1192,6 +1201,16 @@ KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, const float* a, i
                                                int32_t scale_rows, int32_t scale_cols, const float* bias, const float* r, int64_t ldr,
                                                int32_t r_is_y, float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
                                                int32_t* ksplit_used, int64_t* scratch_written);
+/* kjarni_hip_op_prefill_gemm_ggml: the same call through launch_prefill_gemm_ggml -- the weights as raw GGUF blocks [n, k] of
+ * ggml_type (8 Q8_0, 12 Q4_K, 14 Q6_K), repacked into the device planes as the loader does: y = a . dequantize(blocks)^T (+ bias)
+ * (+ r), the code bytes unpacked in the tile loader and multiplied on the bf16 matrix cores, the scales folded per sub-block in f32
+ * (a Q6_K matrix takes the rows as f32).  Every other argument, the split scratch, *ksplit_used and *scratch_written as in
+ * kjarni_hip_op_prefill_gemm; a guard band lies behind every device buffer, the planes included, and the outputs come back whole.
+ * INVALID_CONFIG, before any GPU work and with every output untouched: the refusals of kjarni_hip_op_prefill_gemm, a type that is
+ * not one of the three, k not a whole number of the type's blocks (32 for Q8_0, 256 for the K-quants). */
+KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks, int32_t ggml_type,
+                                                const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
+                                                int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used, int64_t* scratch_written);
 /* kjarni_hip_op_prefill_attention: causal grouped-query attention of `rows` prompt rows at positions base .. base + rows - 1 over
  * key rows 0 .. base + rows - 1 through launch_prefill_attention: query row s sees keys <= base + s.  q [rows, ldq]
  * (heads * head_dim used); k / v: k_floats / v_floats floats, key row t at k + t * ldk, KV head h / kv_group at columns
@@ -1400,6 +1419,9 @@ KjarniErrorCode kjarni_hip_generator_set_prefix_reuse(KjarniGenerator* generator
 /* kjarni_hip_decoder_set_fp8_matrix_cores on the handle's model. */
 KjarniErrorCode kjarni_hip_chat_set_fp8_matrix_cores(KjarniChat* chat, int32_t on);
 KjarniErrorCode kjarni_hip_generator_set_fp8_matrix_cores(KjarniGenerator* generator, int32_t on);
+/* kjarni_hip_decoder_set_ggml_matrix_cores on the handle's model. */
+KjarniErrorCode kjarni_hip_chat_set_ggml_matrix_cores(KjarniChat* chat, int32_t on);
+KjarniErrorCode kjarni_hip_generator_set_ggml_matrix_cores(KjarniGenerator* generator, int32_t on);
 void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
 
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */

@@ -2904,6 +2904,63 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, con
     });
 }
 
+// launch_prefill_gemm_ggml on host arrays: kjarni_hip_op_prefill_gemm's arguments with the weights as raw GGUF blocks [n, k] of one
+// type, repacked into the device planes (repack_ggml) as kjarni_hip_op_fused_proj_ggml does.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks,
+                                                              int32_t ggml_type, const float* bias, const float* r, int64_t ldr, int32_t r_is_y,
+                                                              float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
+                                                              int32_t* ksplit_used, int64_t* scratch_written)
+{
+    if (!a || !blocks || !y || !ksplit_used) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (m < 0 || m > 4096 || a_rows < std::max(m, 1) || a_rows > 8192) throw InvalidConfig("m must be 0 .. 4096 and a_rows max(m, 1) .. 8192");
+        if (n < 1 || k < 1 || n > (1 << 17) || k > (1 << 16) || (int64_t)n * k > ((int64_t)1 << 26))
+            throw InvalidConfig("n must be 1 .. 2^17, k 1 .. 2^16, n * k at most 2^26");
+        check_qmat_type(ggml_type, k);
+        if (lda % 4) throw InvalidConfig("launch_prefill_gemm_ggml refuses these arguments: lda a multiple of 4");
+        if (lda < k || ldy < n || std::max(lda, ldy) > (1 << 18)) throw InvalidConfig("lda must cover k and ldy n (at most 2^18)");
+        const bool res = r_is_y || r;
+        const int64_t ldr_ = r_is_y ? ldy : ldr;
+        if (res && (ldr_ < n || ldr_ > (1 << 18))) throw InvalidConfig("ldr must cover n (at most 2^18)");
+        if (gate && (ldy != n || (n & 3))) throw InvalidConfig("launch_prefill_gemm_ggml refuses these arguments: a gate needs ldy == n and n a multiple of 4");
+        if (split != 0 && split != 1) throw InvalidConfig("split must be 0 or 1");
+        if (scratch_written && !split) throw InvalidConfig("scratch_written without split");
+        use_device(device);
+        const QPlanes planes = repack_ggml((uint32_t)ggml_type, static_cast<const uint8_t*>(blocks), n, k);
+        const size_t ab = (size_t)a_rows * (size_t)lda * 4, yb = (size_t)m * (size_t)ldy * 4;
+        const size_t rb = r && !r_is_y ? (size_t)m * (size_t)ldr * 4 : 0, gb = gate ? (size_t)m * (size_t)n * 4 : 0;
+        const size_t sb = split ? prefill_gemm_scratch_floats(m, n) * 4 : 0;
+        std::vector<std::unique_ptr<BandBuf>> pd;  // the planes, a guard band behind each
+        const void* pp[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < 4; ++i) {
+            if (planes.plane[i].empty()) continue;
+            pd.push_back(std::make_unique<BandBuf>(planes.plane[i].data(), planes.plane[i].size(), kBandWords, "H2D weights"));
+            pp[i] = pd.back()->buf.p;
+        }
+        BandBuf ad(a, ab, kBandWords, "H2D a"), bd(bias, bias ? (size_t)n * 4 : 0, kBandWords, "H2D bias"), rd(rb ? r : nullptr, rb, kBandWords, "H2D r");
+        BandBuf yd(y, yb, kBandWords, "H2D y"), gd(gate, gb, kBandWords, "H2D gate"), sd(nullptr, sb, kBandWords, "scratch");
+        if (sb) hip_check(hipMemset(sd.buf.p, 0xFF, sb), "poison scratch");  // (all-ones words are NaN: a slab the kernels skip would show)
+        QMat W;
+        W.type = (uint32_t)ggml_type; W.n = n; W.k = k; W.q = pp[0]; W.q2 = pp[1]; W.s = pp[2]; W.s2 = pp[3];
+        const float* bp = bias ? bd.as<const float>() : nullptr;
+        const float* rp = r_is_y ? yd.as<const float>() : (r ? rd.as<const float>() : nullptr);
+        float* sp = split ? sd.as<float>() : nullptr;
+        *ksplit_used = prefill_gemm_launch_ksplit(bp, rp, ldr_, yd.as<const float>(), ldy, m, n, k, sp);
+        launcher_check(launch_prefill_gemm_ggml(ad.as<const float>(), lda, W, bp, rp, ldr_, yd.as<float>(), ldy, m, nullptr, sp,
+                                                gate ? gd.as<float>() : nullptr), "ggml prefill gemm");
+        hip_check(hipDeviceSynchronize(), "sync");
+        yd.fetch(y, yb, "D2H y");
+        gd.fetch(gate, gb, "D2H gate");
+        sd.fetch(nullptr, 0, "scratch");
+        for (const auto& p : pd) p->fetch(nullptr, 0, "weights");
+        if (scratch_written) {  // the scratch words that no longer hold the poison
+            std::vector<uint32_t> words(sb / 4);
+            hip_check(hipMemcpy(words.data(), sd.buf.p, sb, hipMemcpyDeviceToHost), "D2H scratch");
+            *scratch_written = (int64_t)(words.size() - (size_t)std::count(words.begin(), words.end(), 0xFFFFFFFFu));
+        }
+    });
+}
+
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mask_lengths(int32_t device, const uint32_t* mask, int64_t batch, int32_t seq, uint32_t* lens_out)
 {
     if (!mask || !lens_out) return KJARNI_ERROR_NULL_POINTER;

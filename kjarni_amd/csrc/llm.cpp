@@ -1034,7 +1034,7 @@ void LlmModel::ensure_prompt_workspace()
 // per projection: the 128 x 128 tiles when they number at least one per CU (m / 128 x N / 128 >= 208), from kTileRows rows
 // gelu (GPT-2's c_fc): Y = gelu_tanh(A W^T + bias), in the f32 tile GEMM's epilogue, else as a pass over Y after the GEMM
 void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                           float* gate, const char* what, const QMat* qm, bool gelu, const Fp8Mat* fm)
+                           float* gate, const char* what, const QMat* qm, bool gelu, const Fp8Mat* fm, bool q6k_q8k)
 {
     hipStream_t s = stream_;
     const int H = cfg_.hidden, kv = cfg_.kv_heads * cfg_.head_dim, I = cfg_.inter, QD = cfg_.q_dim();
@@ -1053,6 +1053,17 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
         hip_check(launch_prefill_gemm_fp8(Ain, lda, *fm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
         return;
     }
+    const bool q8k_rows = qm && qm->type == GGML_Q6_K && q6k_q8k;  // a Q6_K linear: its rows through Q8_K and back first
+    if (qm && ggml_mc_ && !tiles) {  // the switch: the code bytes themselves on the bf16 matrix cores, no f32 copy of the matrix
+        if (gelu) throw InvalidConfig(std::string(what) + ": the GGUF matrix-core GEMM has no GELU epilogue");
+        if (q8k_rows) {
+            hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
+            Ain = pact_;
+            lda = K;
+        }
+        hip_check(launch_prefill_gemm_ggml(Ain, lda, *qm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
+        return;
+    }
     if (fm) {  // an FP8 matrix: decode(code) * scale into the f32 scratch, then the f32 route
         hip_check(launch_fp8_dequant(*fm, pw32_, s), what);
         W = pw32_;
@@ -1060,7 +1071,7 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
         bf = false;
     } else if (qm) {
         hip_check(launch_qdequant(*qm, pw32_, s), what);
-        if (qm->type == GGML_Q6_K) {
+        if (q8k_rows) {
             hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
             Ain = pact_;
             lda = K;
@@ -2123,7 +2134,8 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
     const LlmConfig& c = cfg_;
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     if (b.wide) {  // what the wide step alone asks of the checkpoint
-        if (quant_ && !fp8_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_: with the switch on, the FP8 prompt GEMM reads the codes)
+        if (quant_ && !fp8_mc_ && !ggml_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_, ggml_mc_ a GGUF checkpoint: with its switch
+                                              // on, the checkpoint's prompt GEMM reads the codes)
             throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
                                 " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
         if (!rows_geometry(c) || !decode_attention_accepts(c.head_dim, splits_, cap, 1, true, true, false))
@@ -2876,6 +2888,16 @@ void LlmModel::set_fp8_matrix_cores(bool on)
     fp8_mc_ = on;
 }
 
+void LlmModel::set_ggml_matrix_cores(bool on)
+{
+    if (!quant_ || fp8_ || on == ggml_mc_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    drop_lane_graphs(wide_bank_);  // (they hold the route's launches)
+    wide_bank_.lanes = 0;       // a wide session ends here: lanes_begin() decides again
+    ggml_mc_ = on;
+}
+
 // One wide step, a linear chain on the model's stream: the embedding at the lanes' positions, per layer norm 1 -> ONE GEMM of
 // the fused [Q;K;V] matrix into the lanes' staging rows -> rotate-and-scatter -> ragged attention -> rows_finish() (o-proj,
 // norm 2, SwiGLU / GPT-2 MLP / the MoE rows hook), then the final norm and the head as a GEMM into the bank's logits.  Frozen lanes
@@ -2898,6 +2920,10 @@ void LlmModel::wide_step_enqueue(int n)
                         &L.fk);
             prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, b.qkv + QD + kv, ldq, kv, H, nullptr, "v proj", nullptr,
                         false, &L.fv);
+        } else if (quant_) {  // a GGUF checkpoint (the same: only with its switch on), each matrix of its own type
+            prompt_proj(n, pn_, H, nullptr, L.bqkv, nullptr, b.qkv, ldq, QD, H, nullptr, "q proj", &L.q);
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD : nullptr, nullptr, b.qkv + QD, ldq, kv, H, nullptr, "k proj", &L.k);
+            prompt_proj(n, pn_, H, nullptr, L.bqkv ? L.bqkv + QD + kv : nullptr, nullptr, b.qkv + QD + kv, ldq, kv, H, nullptr, "v proj", &L.v);
         } else {
             prompt_proj(n, pn_, H, L.wqkv, L.bqkv, nullptr, b.qkv, ldq, ldq, H, nullptr, "q|k|v proj");
         }
@@ -2905,7 +2931,10 @@ void LlmModel::wide_step_enqueue(int n)
         rows_finish(n, L);
     }
     final_norm(ph_, n, pn_);  // (the norm buffer is free behind the last layer)
-    prompt_proj(n, pn_, H, lm_head_, nullptr, nullptr, b.logits, c.vocab, c.vocab, H, nullptr, "lm head");
+    if (quant_ && !fp8_)  // the quantized head (maybe the tied table), its rows by head()'s rule: Q8_K first only where head_q8k_
+        prompt_proj(n, pn_, H, nullptr, nullptr, nullptr, b.logits, c.vocab, c.vocab, H, nullptr, "lm head", &qhead_, false, nullptr, head_q8k_);
+    else
+        prompt_proj(n, pn_, H, lm_head_, nullptr, nullptr, b.logits, c.vocab, c.vocab, H, nullptr, "lm head");
 }
 
 std::vector<std::vector<uint32_t>> LlmModel::generate_wide(const std::vector<LaneRequest>& reqs, int lanes, int lane_context,

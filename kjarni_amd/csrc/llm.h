@@ -157,6 +157,14 @@ public:
     // its session (lanes_begin(Bank::Wide) again).
     void set_fp8_matrix_cores(bool on);
     bool fp8_matrix_cores() const { return fp8_mc_; }
+    // ---- GGUF checkpoints on the matrix cores (off by default; a no-op on a checkpoint that is not GGUF-quantized) ---------------
+    // On: a prompt projection on the 64 x 64 route multiplies the Q8_0 / Q4_K / Q6_K codes themselves (launch_prefill_gemm_ggml)
+    // instead of dequantizing the matrix into the f32 scratch first -- a Q6_K linear's rows still go through Q8_K and back, as the
+    // decode kernels quantize them -- and ensure_lane_bank() takes the checkpoint on the wide bank: the wide step writes Q, K and V
+    // from their three matrices into the staging rows' column segments and the head is qhead_ on the same GEMM.  Off: everything
+    // enqueued is what it was before the switch existed.  Flipping it drops the captured wide graphs and ends a wide session.
+    void set_ggml_matrix_cores(bool on);
+    bool ggml_matrix_cores() const { return ggml_mc_; }
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
     uint64_t prefix_reused_tokens() const { return prefix_reused_; }
     uint64_t prefix_computed_tokens() const { return prefix_computed_; }
@@ -554,9 +562,11 @@ private:
                                   const std::vector<EmbedBlock>& mfma, const std::vector<PrefixBlock>& prefix);
     // One projection of m prompt rows: Y[m, N] = A W^T (+ bias) (+ R), or with `gate`: gate = silu(gate) * (A W^T); gelu (GPT-2's
     // c_fc): Y = gelu_tanh(A W^T + bias).  Routes: the 64 x 64 prompt kernel, or from 512 rows and 208 tiles the 128 x 128-tile
-    // GEMM (bf16 weights on the bf16 matrix cores); qm / fm: a GGUF-quantized / FP8 matrix, dequantized into the f32 scratch first.
+    // GEMM (bf16 weights on the bf16 matrix cores); qm / fm: a GGUF-quantized / FP8 matrix, dequantized into the f32 scratch first, or
+    // with its switch on and on the 64 x 64 route multiplied as codes.  q6k_q8k: a Q6_K matrix is a linear layer, whose rows go through
+    // Q8_K and back first (false: the tied head, f32 rows).
     void prompt_proj(int m, const float* Ain, int lda, const void* W, const float* bias, const float* R, float* Y, int ldy, int N, int K,
-                     float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false, const Fp8Mat* fm = nullptr);
+                     float* gate, const char* what, const QMat* qm = nullptr, bool gelu = false, const Fp8Mat* fm = nullptr, bool q6k_q8k = true);
     void forward_rows(const uint32_t* ids, int n, bool score, int score_base = 0);  // forward(), with score()'s sink
     void ensure_score();
     void ensure_score_topk();
@@ -792,6 +802,7 @@ private:
     std::vector<uint32_t> resident_;
     bool prefix_reuse_ = false;
     bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
+    bool ggml_mc_ = false;  // set_ggml_matrix_cores(): only ever true with quant_ && !fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
 };
 

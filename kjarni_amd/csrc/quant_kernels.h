@@ -86,6 +86,15 @@ hipError_t launch_qprep(const float* X, int64_t ldx, int rows, int k, const floa
 hipError_t launch_q8k_quantize(const float* X, int64_t ldx, int rows, int k, int8_t* codes, float* scales, float* deq, hipStream_t stream);
 // W dequantized into out [n, k] f32 (the prompt route's f32 scratch).
 hipError_t launch_qdequant(const QMat& W, float* out, hipStream_t stream);
+// The prompt GEMM on the codes (ggml_gemm.hip): Y[M, N] = A[M, K] . W^T (+ bias) (+ R), N = W.n, K = W.k, on the bf16 matrix cores --
+// the code bytes become exact bf16 integers in the tile loader, the f32 activations three exact bf16 pieces, the block and sub-block
+// scales are applied in f32.  launch_prefill_gemm's contract (llm_kernels.h): its tile order, its K-slice rule
+// (prefill_gemm_launch_ksplit), its scratch layout and reduce kernel, R may alias Y, silu_gate as there.  A Q6_K matrix takes the
+// rows it is given as f32 (a caller that wants the Q8_K rounding of a Q6_K linear passes launch_q8k_quantize's deq rows).  Refused
+// (hipErrorInvalidValue): a type that is not Q8_0 / Q4_K / Q6_K, K % 256 for the K-quants and K % 32 for Q8_0, lda % 4, A or a plane
+// not 16-byte aligned, a gate with ldy != N or N % 4.
+hipError_t launch_prefill_gemm_ggml(const float* A, int64_t lda, const QMat& W, const float* bias, const float* R, int64_t ldr, float* Y,
+                                    int64_t ldy, int M, hipStream_t stream, float* split_scratch = nullptr, float* silu_gate = nullptr);
 // Embedding rows ids[0..n) of the table [vocab, hidden], dequantized; an id >= vocab gives zeros.
 hipError_t launch_qembed(const uint32_t* ids, int n, const QMat& table, float* out, hipStream_t stream);
 

@@ -875,6 +875,17 @@ class HipDecoder:
     def fp8_matrix_cores(self) -> bool:
         return bool(lib().kjarni_hip_decoder_fp8_matrix_cores(self._h))
 
+    # ---- GGUF checkpoints on the matrix cores ----
+    def set_ggml_matrix_cores(self, on: bool):
+        """Off (the default): a GGUF checkpoint's prompt projections dequantize each matrix to f32 first, and more than 8 lanes
+        refuse it.  On: the prompt GEMM multiplies the Q8_0 / Q4_K / Q6_K codes themselves on the bf16 matrix cores
+        (launch_prefill_gemm_ggml) and generate_wide / the wide hooks accept the checkpoint.  A no-op on a checkpoint that is not
+        GGUF-quantized."""
+        lib().kjarni_hip_decoder_set_ggml_matrix_cores(self._h, 1 if on else 0)
+
+    def ggml_matrix_cores(self) -> bool:
+        return bool(lib().kjarni_hip_decoder_ggml_matrix_cores(self._h))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
         a, b = C.c_uint64(), C.c_uint64()

@@ -68,6 +68,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            widths, and the prompt's time at 128 / 384 tokens with the switch off, on and for bf16; Llama-3.2-1B shape (per-channel
            scales) and Qwen3-0.6B shape (block scales), every leg twice, best of two.  The lines also go to
            profiles/llm_wide_fp8_bench.jsonl.
+  llm_wide_gguf  (only on request) GGUF checkpoints on the matrix cores (HipDecoder.set_ggml_matrix_cores): Llama-3.2-1B shape, the
+           Q4_K_M mix of tests/gguf_fixture.py on random codes; forward() on 128 / 384 tokens with the switch off, on and for bf16,
+           generate_wide at 16 / 32 / 64 lanes with the switch on against GGUF generate_batch at 8 lanes and against a bf16 load at
+           the same widths; every leg twice in one process, best of two.  The lines also go to profiles/llm_wide_gguf_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1083,6 +1087,86 @@ def main():
         with open(out_path, "w") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+    if "llm_wide_gguf" in which:
+        # GGUF checkpoints on the matrix cores (HipDecoder.set_ggml_matrix_cores).  Method (as llm_wide_fp8): one process on one box,
+        # every leg warmed first, every leg twice, best of two; a decode window is a whole call minus the same call cut after its
+        # first token; a prompt's time is the median of 5 forward() calls that end in a synchronise, the switch off and on alternated
+        # twice on one decoder, the better of two.  The decode legs of one checkpoint run as a block (a load per checkpoint).
+        from tests import gguf_fixture
+        rng = np.random.default_rng(0)
+        n_new, ctx = 64, 512
+
+        def window(fn):
+            t0 = time.perf_counter()
+            fn(1)
+            t1 = time.perf_counter()
+            outs = fn(n_new)
+            t2 = time.perf_counter()
+            assert all(len(o) == n_new for o in outs)
+            return (t2 - t1) - (t1 - t0)
+
+        def wide_legs(dec, prompts, names):
+            legs = {"lanes-8": (8, lambda n: dec.generate_batch(prompts[:8], n, lanes=8, lane_context=ctx))}
+            for w in (16, 32, 64):
+                legs[f"wide-{w}"] = (w, (lambda w: lambda n: dec.generate_wide(prompts[:w], n, lanes=w, lane_context=ctx))(w))
+            legs = {k: v for k, v in legs.items() if k in names}
+            for _, fn in legs.values():
+                fn(12)
+            rows = {}
+            for rep in range(2):
+                for name, (width, fn) in legs.items():
+                    dt = window(fn)
+                    rows.setdefault(name, []).append({"tokens_per_s": round(width * (n_new - 1) / dt, 1), "ms_per_step": round(dt * 1e3 / (n_new - 1), 4)})
+            return {k: max(v, key=lambda r: r["tokens_per_s"]) for k, v in rows.items()}
+
+        def prompt_ms(dec, ids):
+            ts = []
+            for _ in range(6):
+                dec.reset()
+                t0 = time.perf_counter()
+                dec.forward(ids, fetch=False)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            return round(float(np.median(ts[1:])), 3)
+
+        gcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=synth.LLAMA_1B["vocab_size"] + 1)
+        gpath, bdir = os.path.join(tmp, "llama-1b-q4km-wide.gguf"), os.path.join(tmp, "llama-1b-bf16-gguf-wide")
+        gguf_fixture.gguf_model(gpath, gcfg, gguf_fixture.q4_k_m_types(gcfg["num_hidden_layers"]), seed=0, rope_freqs=True, keep_hf=False)
+        synth.llm_model(bdir, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        prompts = [rng.integers(1000, 100000, 128).tolist() for _ in range(64)]
+        long_ids = {n: rng.integers(1000, 100000, n).tolist() for n in (128, 384)}
+        wides = ("wide-16", "wide-32", "wide-64")
+        gdec = kjarni_amd.HipDecoder(gpath, max_context=2048)
+        off = wide_legs(gdec, prompts, ("lanes-8",))
+        gdec.set_ggml_matrix_cores(True)
+        on = wide_legs(gdec, prompts, ("lanes-8",) + wides)
+        p_off, p_on = {}, {}
+        for rep in range(2):  # the prompt legs alternated off / on, twice, the better of two
+            for flag, dst in ((False, p_off), (True, p_on)):
+                gdec.set_ggml_matrix_cores(flag)
+                for n, ids in long_ids.items():
+                    dst[n] = min(dst.get(n, float("inf")), prompt_ms(gdec, ids))
+        gbytes = gdec.weight_bytes
+        del gdec
+        bdec = kjarni_amd.HipDecoder(bdir, max_context=2048)
+        bf = wide_legs(bdec, prompts, ("lanes-8",) + wides)
+        p_bf = {n: min(prompt_ms(bdec, ids) for _ in range(2)) for n, ids in long_ids.items()}
+        line = {"metric": "aggregate tokens/sec greedy decode in wide lanes, Llama-3.2-1B shape, GGUF Q4_K_M mix on the bf16 matrix cores",
+                "unit": "tokens/s", "value": on["wide-64"]["tokens_per_s"], "n_gpus": 1, "data": "synthetic",
+                "dtype": "Q4_K / Q6_K blocks in HBM, f32 activations/accumulate/KV",
+                "config": {"workload": f"random codes, one 128-token prompt per lane, {n_new} generated tokens per lane, lane_context {ctx}; every leg "
+                                       "twice in one process, best of two"},
+                "ggml_switch_off": off, "ggml_switch_on": on, "bf16_same_shape": bf,
+                "x_gguf_lanes_8": {k: round(on[k]["tokens_per_s"] / off["lanes-8"]["tokens_per_s"], 3) for k in wides},
+                "x_bf16_same_width": {k: round(on[k]["tokens_per_s"] / bf[k]["tokens_per_s"], 3) for k in wides},
+                "prompt_ms": {"ggml_switch_off": p_off, "ggml_switch_on": p_on, "bf16": p_bf},
+                "prompt_x_switch_off": {n: round(p_on[n] / p_off[n], 3) for n in p_on},
+                "prompt_x_bf16": {n: round(p_on[n] / p_bf[n], 3) for n in p_on},
+                "weight_bytes": {"gguf": gbytes, "bf16": bdec.weight_bytes}}
+        del bdec
+        emit(line)
+        with open(os.path.join(ROOT, "profiles", "llm_wide_gguf_bench.jsonl"), "w") as f:
+            f.write(json.dumps(line) + "\n")
 
     if "llm_lookup" in which:
         # Method (measuring guide, section 5; as llm_lanes): one process on one box; the plain step graph, the verify hook at
