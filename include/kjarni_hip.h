@@ -588,6 +588,24 @@ KjarniErrorCode kjarni_hip_op_fused_proj_ggml(int32_t device, int32_t mode, cons
                                               const int64_t* ldy, int32_t row_off, int32_t offset_on_device, int32_t head_dim,
                                               const float* cos_t, const float* sin_t, int32_t positions, int32_t q8k, float* xn_out,
                                               int8_t* xq_out, float* xd_out);
+/* launch_affine_proj alone (affine_kernels.hip): the decode projection of the Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K family over rows (1 .. 8)
+   rows of x [rows_alloc, ldx].  mode 0 plain (bias, residual r or in place with r_is_y0), 1 Q | K | V (three matrices, each of its own
+   type; y[1] / y[2] rows land at row_off + r -- read from the device with offset_on_device), 2 SwiGLU (gate, up).  blocks[i]: raw GGUF
+   blocks [n[i], k] of type ggml_types[i], one of the five or Q8_0.  Every argument is checked before a device is asked for; y[i]
+   [out_rows[i], ldy[i]] is uploaded as given, guarded behind its end, and returned whole -- untouched when the call is refused. */
+KjarniErrorCode kjarni_hip_op_affine_proj(int32_t device, int32_t mode, const void* const* blocks, const int32_t* ggml_types, const int32_t* n,
+                                          int32_t k, const float* x, int32_t rows_alloc, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                          const float* bias, int32_t bias_floats, const int32_t* bias_off, const float* r, int64_t ldr,
+                                          int32_t r_is_y0, float* const* y, const int32_t* out_rows, const int64_t* ldy, int32_t row_off,
+                                          int32_t offset_on_device);
+/* The affine-32 device planes of raw blocks [n, k] of one of the five types, made on the host (no device): nibbles [n, k / 2],
+   fifth_bits [n, k / 32] (5-bit types; may be NULL otherwise), ab [n, k / 32, 2]. */
+KjarniErrorCode kjarni_hip_op_affine_repack(const void* blocks, int32_t ggml_type, int32_t n, int32_t k, uint8_t* nibbles, uint32_t* fifth_bits,
+                                            float* ab);
+/* launch_affine_dequant alone (ids NULL: out [n, k]), or launch_affine_embed (out [n_ids, k] = rows ids[i] of the table [n, k]; an id >= n
+   gives zeros).  out is uploaded as given, guarded, returned whole. */
+KjarniErrorCode kjarni_hip_op_affine_dequant(int32_t device, const void* blocks, int32_t ggml_type, int32_t n, int32_t k, const uint32_t* ids,
+                                             int32_t n_ids, float* out);
 /* launch_qembed alone: out [n_ids, k] (uploaded as given, returned whole) = the dequantized rows ids[i] of the table [vocab, k]
  * given as raw GGUF blocks; an id >= vocab gives zeros. */
 KjarniErrorCode kjarni_hip_op_qembed(int32_t device, const uint32_t* ids, int32_t n_ids, const void* blocks, int32_t ggml_type, int32_t vocab,

@@ -486,6 +486,11 @@ SIGNATURES = {
                                                 c_int64, c_int32, _f32p, c_float, _f32p, c_int32, POINTER(c_int32), _f32p, c_int64, c_int32,
                                                 POINTER(c_void_p), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32, c_int32, _f32p, _f32p,
                                                 c_int32, c_int32, _f32p, c_void_p, _f32p]),
+    "kjarni_hip_op_affine_proj": (c_int32, [c_int32, c_int32, POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, _f32p, c_int32,
+                                            c_int64, c_int32, _f32p, c_float, _f32p, c_int32, POINTER(c_int32), _f32p, c_int64, c_int32,
+                                            POINTER(c_void_p), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32]),
+    "kjarni_hip_op_affine_repack": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, _f32p]),
+    "kjarni_hip_op_affine_dequant": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, _u32p, c_int32, _f32p]),
     "kjarni_hip_op_qembed": (c_int32, [c_int32, _u32p, c_int32, c_void_p, c_int32, c_int32, c_int32, _f32p]),
     "kjarni_hip_op_q8k_quantize": (c_int32, [c_int32, _f32p, c_int32, c_int64, c_int32, c_void_p, _f32p, _f32p]),
     "kjarni_hip_decoder_set_device_sampling": (None, [c_void_p, c_int32]),

@@ -1928,6 +1928,118 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_fused_proj_ggml(int32_t device, int3
     });
 }
 
+// ---- the affine-32 family (affine_kernels.hip), alone -------------------------------------------------------------------------------
+
+namespace {
+
+// A matrix the affine projection takes: one of the five affine-32 types, or Q8_0; k a whole number of the type's blocks.
+void check_affine_type(int32_t ggml_type, int32_t k, bool q8_too)
+{
+    const bool ok = ggml_affine_type((uint32_t)ggml_type) || (q8_too && ggml_type == (int32_t)GGML_Q8_0);
+    if (!ok) throw InvalidConfig(std::string("unsupported GGML matrix type ") + ggml_type_name((uint32_t)ggml_type) +
+                                 (q8_too ? ": Q4_0, Q4_1, Q5_0, Q5_1, Q5_K or Q8_0" : ": Q4_0, Q4_1, Q5_0, Q5_1 or Q5_K"));
+    if (k < 32 || k > (1 << 20) || k % 32 || (ggml_type == (int32_t)GGML_Q5_K && k % 256)) throw InvalidConfig("k must be a whole number of the type's blocks");
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_affine_proj(int32_t device, int32_t mode, const void* const* blocks, const int32_t* ggml_types,
+                                                        const int32_t* n, int32_t k, const float* x, int32_t rows_alloc, int64_t ldx, int32_t rows,
+                                                        const float* gamma, float eps, const float* bias, int32_t bias_floats,
+                                                        const int32_t* bias_off, const float* r, int64_t ldr, int32_t r_is_y0, float* const* y,
+                                                        const int32_t* out_rows, const int64_t* ldy, int32_t row_off, int32_t offset_on_device)
+{
+    if (!blocks || !ggml_types || !n || !x || !y || !out_rows || !ldy) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const ProjShape s = check_fused_proj(mode, n, k, rows_alloc, ldx, rows, r, ldr, r_is_y0, y, out_rows, ldy, row_off);
+        if (rows < 1 || rows > 8) throw InvalidConfig("the affine projection takes 1 .. 8 rows");
+        for (int i = 0; i < s.n_mats; ++i) {
+            if (!blocks[i]) throw InvalidConfig("a matrix of this mode is NULL");
+            check_affine_type(ggml_types[i], k, true);
+        }
+        if (bias) {
+            if (mode == 2) throw InvalidConfig("no bias with SwiGLU");
+            if (!bias_off) throw InvalidConfig("a bias needs bias_off[3]");
+            for (int i = 0; i < s.n_mats; ++i)
+                if (bias_off[i] < 0 || (int64_t)bias_off[i] + n[i] > bias_floats) throw InvalidConfig("bias_off + the segment's columns exceed bias_floats");
+        }
+        if (mode == 2 && (r || r_is_y0)) throw InvalidConfig("no residual with SwiGLU");
+        use_device(device);
+        std::vector<std::unique_ptr<DeviceBuf>> keep;
+        AffineProjArgs a;
+        a.mode = mode == 1 ? AF_QKV : (mode == 2 ? AF_SWIGLU : AF_PLAIN);
+        for (int i = 0; i < s.n_mats; ++i) a.W[i] = upload_qmat(ggml_types[i], blocks[i], n[i], k, keep);
+        const auto xd = upload(x, (size_t)rows_alloc * (size_t)ldx * 4, "H2D x");
+        const auto gd = upload(gamma, (size_t)k * 4, "H2D gamma");
+        const auto bd = upload(bias, bias ? (size_t)bias_floats * 4 : 0, "H2D bias");
+        const auto rd = upload(r, (size_t)rows * (size_t)ldr * 4, "H2D r");
+        const auto od = upload(&row_off, sizeof(int), "H2D row_off");
+        const ProjOutputs out(s, y, out_rows, ldy);
+        a.X = static_cast<const float*>(xd->p); a.ldx = ldx; a.rows = rows;
+        a.gamma = gamma ? static_cast<const float*>(gd->p) : nullptr; a.eps = eps;
+        if (bias) {
+            a.bias = static_cast<const float*>(bd->p);
+            for (int i = 0; i < s.n_mats; ++i) a.bias_off[i] = bias_off[i];
+        }
+        if (r_is_y0) {
+            a.R = out.dev(0); a.ldr = ldy[0];
+        } else if (r) {
+            a.R = static_cast<const float*>(rd->p); a.ldr = ldr;
+        }
+        for (int i = 0; i < s.n_outs; ++i) {
+            a.Y[i] = out.dev(i); a.ldy[i] = ldy[i];
+        }
+        a.row_off = row_off;
+        if (offset_on_device) {
+            a.row_off_ptr = static_cast<const int*>(od->p);
+            a.row_off = decoy_offset(row_off, mode == 1 ? std::min(out_rows[1], out_rows[2]) - rows : 0);
+        }
+        launcher_check(launch_affine_proj(a, nullptr), "affine projection");
+        hip_check(hipDeviceSynchronize(), "sync");
+        out.fetch(y);
+    });
+}
+
+// repack_ggml of an affine-32 type on the host alone (no device is asked for): the three planes as the kernels read them.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_affine_repack(const void* blocks, int32_t ggml_type, int32_t n, int32_t k, uint8_t* nibbles,
+                                                          uint32_t* fifth_bits, float* ab)
+{
+    if (!blocks || !nibbles || !ab) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n < 1 || n > (1 << 20)) throw InvalidConfig("n must be 1 .. 2^20");
+        check_affine_type(ggml_type, k, false);
+        if (affine_code_bits((uint32_t)ggml_type) == 5 && !fifth_bits) throw InvalidConfig("a 5-bit type needs fifth_bits");
+        const QPlanes p = repack_ggml((uint32_t)ggml_type, static_cast<const uint8_t*>(blocks), n, k);
+        std::memcpy(nibbles, p.plane[0].data(), p.plane[0].size());
+        if (!p.plane[1].empty()) std::memcpy(fifth_bits, p.plane[1].data(), p.plane[1].size());
+        std::memcpy(ab, p.plane[2].data(), p.plane[2].size());
+    });
+}
+
+// launch_affine_dequant (ids == NULL: out [n, k]) or launch_affine_embed (out [n_ids, k], uploaded as given and returned whole) alone.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_affine_dequant(int32_t device, const void* blocks, int32_t ggml_type, int32_t n, int32_t k,
+                                                           const uint32_t* ids, int32_t n_ids, float* out)
+{
+    if (!blocks || !out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (n < 1 || n > (1 << 20) || (int64_t)n * k > ((int64_t)1 << 28)) throw InvalidConfig("n must be 1 .. 2^20, n * k at most 2^28");
+        check_affine_type(ggml_type, k, false);
+        if (ids && (n_ids < 1 || n_ids > 4096)) throw InvalidConfig("n_ids 1 .. 4096");
+        use_device(device);
+        std::vector<std::unique_ptr<DeviceBuf>> keep;
+        const QMat W = upload_qmat(ggml_type, blocks, n, k, keep);
+        const auto idd = upload(ids, ids ? (size_t)n_ids * 4 : 0, "H2D ids");
+        const size_t ob = (size_t)(ids ? n_ids : n) * (size_t)k * 4;
+        GuardedBuf od(ob);
+        hip_check(hipMemcpy(od.buf.p, out, ob, hipMemcpyHostToDevice), "H2D out");
+        if (ids) launcher_check(launch_affine_embed(static_cast<const uint32_t*>(idd->p), n_ids, W, od.as<float>(), nullptr), "affine embed");
+        else launcher_check(launch_affine_dequant(W, od.as<float>(), nullptr), "affine dequant");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.check("dequantized rows");
+        hip_check(hipMemcpy(out, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H out");
+    });
+}
+
 // ---- the dense (f32 / bf16) decode-step projections, alone ---------------------------------------------------------------------------
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_llm_gemv(int32_t device, int32_t lanes, const float* x, int32_t x_rows, int64_t ldx, int32_t rows,

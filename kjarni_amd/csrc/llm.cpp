@@ -284,7 +284,8 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     if ((d & 3) || d > 128 || 256 % (d / 4) != 0 || (H & 7) || (c.inter & 7)) throw std::runtime_error("unsupported decoder geometry");
     auto contains = [&](const std::string& name) { return is_gguf ? gf.find_hf(name) != nullptr : st.contains(name); };
     if (is_gguf) {
-        // every matrix must be Q8_0 / Q4_K / Q6_K (the reference's F16 LinearLayer is unimplemented; F32 is for norms and biases)
+        // every matrix must be one of the eight quantized types (the reference's F16 LinearLayer is unimplemented; F32 is for norms and
+        // biases)
         std::vector<std::string> mats = {"model.embed_tokens.weight"};
         if (contains("lm_head.weight")) mats.push_back("lm_head.weight");
         for (int i = 0; i < c.layers; ++i)
@@ -293,9 +294,10 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
                 mats.push_back("model.layers." + std::to_string(i) + "." + nm + ".weight");
         for (const std::string& nm : mats) {
             const GgufTensor* t = gf.find_hf(nm);
-            if (t && !ggml_matrix_type(t->type))
+            if (t && !ggml_matrix_type(t->type) && !ggml_affine_type(t->type))
                 throw std::runtime_error("GGUF: matrix " + t->name + " has unsupported type " + ggml_type_name(t->type) + " (" +
-                                         std::to_string(t->type) + "); Q8_0, Q4_K and Q6_K are supported");
+                                         std::to_string(t->type) + "); Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K and Q6_K are supported");
+            if (t && ggml_affine_type(t->type)) m->affine_ = weights == 0;
         }
         m->bf16_ = weights == 2;
         m->quant_ = weights == 0;
@@ -385,7 +387,8 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         f.kind = t.kind;
         return f;
     };
-    if (m->quant_ && !m->fp8_ && (H % 256 || c.inter % 256)) throw std::runtime_error("quantized GGUF decoder needs hidden and intermediate sizes that are multiples of 256");
+    // (a K-quant matrix has K % 256 == 0 by its block format, and only a Q6_K linear takes the Q8_K rows of qprep)
+    if (m->quant_ && !m->fp8_ && (H % 32 || c.inter % 32)) throw std::runtime_error("quantized GGUF decoder needs hidden and intermediate sizes that are multiples of 32");
     m->layers_.resize((size_t)c.layers);
     m->cache_cap_ = std::min(max_context > 0 ? max_context : c.max_pos, c.max_pos);
     for (int i = 0; i < c.layers; ++i) {
@@ -565,6 +568,10 @@ void LlmModel::finish_load()
         xn_ = dalloc(8 * wide);
         xq_ = reinterpret_cast<int8_t*>(dalloc(2 * wide));
         xd_ = dalloc(8 * wide / 256 + 4);
+        for (const Layer& L : layers_) {
+            const QMat* gu[2] = {&L.gate_q, &L.up_q};
+            if (!fp8_ && !mid2_ && quant_stage_route(gu, 2) == 2) mid2_ = dalloc(8 * (size_t)c.inter);
+        }
     }
     if (c.moe()) {
         moe_logits_ = dalloc(8 * (size_t)c.num_experts);
@@ -716,7 +723,8 @@ void LlmModel::embed_rows(const uint32_t* ids, int n, float* dst, int pos, const
 {
     const LlmConfig& c = cfg_;
     const int wb = bf16_ ? 1 : 0;
-    if (quant_ && !fp8_) hip_check(launch_qembed(ids, n, qembed_, dst, stream_), "embed");
+    if (quant_ && !fp8_ && ggml_affine_type(qembed_.type)) hip_check(launch_affine_embed(ids, n, qembed_, dst, stream_), "embed");
+    else if (quant_ && !fp8_) hip_check(launch_qembed(ids, n, qembed_, dst, stream_), "embed");
     else if (gpt2_) hip_check(launch_llm_embed_pos(ids, n, c.hidden, c.vocab, embed_, wpe_, c.max_pos, wb, pos, pos_ptr, dst, stream_, row_pos), "embed");
     else hip_check(launch_llm_embed(ids, n, c.hidden, c.vocab, embed_, wb, dst, stream_), "embed");
 }
@@ -729,6 +737,12 @@ void LlmModel::final_norm(const float* src, int rows, float* dst)
 
 void LlmModel::qlinear(const QMat& W, const float* X, int64_t ldx, int rows, bool linear, float* Y, int64_t ldy, const char* what)
 {
+    if (ggml_affine_type(W.type) || W.k % 256) {  // (Q8_0 at such a K: the affine projection reads its planes)
+        AffineProjArgs p;
+        p.W[0] = W; p.X = X; p.ldx = ldx; p.rows = rows; p.Y[0] = Y; p.ldy[0] = ldy;
+        hip_check(launch_affine_proj(p, stream_), what);
+        return;
+    }
     QGemvArgs a;
     a.W = W; a.X = X; a.ldx = ldx; a.rows = rows; a.Y = Y; a.ldy = ldy;
     if (linear && W.type == GGML_Q6_K) {  // Q6_K x Q8_K (matmul.rs:820-875): the activation rows quantized first
@@ -756,19 +770,114 @@ void LlmModel::quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k
     a.X = gamma ? xn_ : X; a.ldx = gamma ? k : ldx; a.Xq = xq_; a.Xd = xd_;
 }
 
+int LlmModel::quant_stage_route(const QMat* const* mats, int count)
+{
+    bool any_new = false, all_affine = true, odd = false;
+    for (int i = 0; i < count; ++i) {
+        any_new |= ggml_affine_type(mats[i]->type);
+        all_affine &= affine_code_bits(mats[i]->type) != 0;
+        odd |= mats[i]->k % 256 != 0;
+    }
+    if (!any_new && !odd) return 0;
+    return all_affine ? 1 : 2;
+}
+
+void LlmModel::quant_plain(const QMat& W, int n, const float* X, int ldx, const float* gamma, const float* R, float* Y, int64_t ldy, const char* what)
+{
+    if (ggml_affine_type(W.type) || W.k % 256) {
+        AffineProjArgs p;
+        p.W[0] = W; p.X = X; p.ldx = ldx; p.rows = n; p.gamma = gamma; p.eps = cfg_.eps; p.R = R; p.ldr = ldy; p.Y[0] = Y; p.ldy[0] = ldy;
+        hip_check(launch_affine_proj(p, stream_), what);
+        return;
+    }
+    QFusedArgs a;
+    quant_source(a, n, X, ldx, W.k, gamma, q6(W), what);
+    a.W[0] = W; a.seg_jobs[0] = a.jobs = (W.n + 1) / 2; a.R = R; a.ldr = ldy; a.Y[0] = Y; a.ldy[0] = ldy;
+    hip_check(launch_qfused(a, stream_), what);
+}
+
+void LlmModel::affine_qkv(int n, const Layer& L, int route, float* q, int64_t ldq, float* kdst, float* vdst, int64_t ldkv, int row_off,
+                          const int* row_off_ptr, bool rotate)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d;
+    const QMat* W[3] = {&L.q, &L.k, &L.v};
+    AffineProjArgs p;
+    p.mode = AF_QKV;
+    p.X = h_; p.ldx = H; p.rows = n; p.gamma = L.ln1; p.eps = c.eps;
+    p.bias = L.bqkv; p.bias_off[1] = H; p.bias_off[2] = H + kv;
+    p.Y[0] = q; p.ldy[0] = ldq; p.Y[1] = kdst; p.Y[2] = vdst; p.ldy[1] = p.ldy[2] = ldkv;
+    p.row_off = row_off; p.row_off_ptr = row_off_ptr;
+    bool by_affine[3] = {true, true, true};
+    if (route == 1) {
+        for (int i = 0; i < 3; ++i) p.W[i] = *W[i];
+        hip_check(launch_affine_proj(p, s), "norm + qkv");
+    } else {
+        bool any_q6 = false;
+        for (int i = 0; i < 3; ++i) {
+            by_affine[i] = ggml_affine_type(W[i]->type) || W[i]->k % 256 != 0;
+            any_q6 |= !by_affine[i] && q6(*W[i]);
+        }
+        QFusedArgs src;  // the rows as qfused_kernel reads them (one qprep launch where a Q6_K matrix does)
+        quant_source(src, n, h_, H, H, L.ln1, any_q6, "norm + q8k 1");
+        for (int i = 0; i < 3; ++i) {
+            if (by_affine[i]) {
+                AffineProjArgs one = p;
+                one.W[i] = *W[i];
+                hip_check(launch_affine_proj(one, s), "norm + q / k / v");
+                continue;
+            }
+            QFusedArgs a = src;
+            a.mode = rotate ? QF_QKV : QF_PLAIN;
+            a.W[i] = *W[i];
+            a.seg_jobs[i] = a.jobs = W[i]->n / 2;
+            a.bias = L.bqkv; a.bias_off[i] = p.bias_off[i];
+            a.Y[i] = p.Y[i]; a.ldy[i] = p.ldy[i];
+            a.row_off = row_off; a.row_off_ptr = row_off_ptr;
+            a.head_dim = d; a.cos_t = cos_; a.sin_t = sin_;
+            hip_check(launch_qfused(a, s), "norm + q / k / v + rope");
+        }
+    }
+    if (!rotate) return;
+    if (by_affine[0]) hip_check(launch_rope(q, ldq, n, c.heads, d, cos_, sin_, row_off, row_off_ptr, 0, s), "rope q");
+    if (by_affine[1]) hip_check(launch_rope(kdst, ldkv, n, c.kv_heads, d, cos_, sin_, row_off, row_off_ptr, 1, s), "rope k");
+}
+
 void LlmModel::quant_finish(int n, const Layer& L)
 {
     hipStream_t s = stream_;
     const int H = cfg_.hidden, I = cfg_.inter;
-    QFusedArgs o;
-    quant_source(o, n, ctx_, H, H, nullptr, q6(L.o), "q8k o");
-    o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
-    hip_check(launch_qfused(o, s), "o proj");
-    QFusedArgs g;
-    g.mode = QF_SWIGLU;
-    quant_source(g, n, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
-    g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
-    hip_check(launch_qfused(g, s), "norm + gate/up");
+    const QMat *po[1] = {&L.o}, *pg[2] = {&L.gate_q, &L.up_q}, *pd[1] = {&L.down_q};
+    if (quant_stage_route(po, 1) != 0) {
+        quant_plain(L.o, n, ctx_, H, nullptr, h_, h_, H, "o proj");
+    } else {
+        QFusedArgs o;
+        quant_source(o, n, ctx_, H, H, nullptr, q6(L.o), "q8k o");
+        o.W[0] = L.o; o.seg_jobs[0] = o.jobs = H / 2; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
+        hip_check(launch_qfused(o, s), "o proj");
+    }
+    const int gate_route = quant_stage_route(pg, 2);
+    if (gate_route == 1) {
+        AffineProjArgs g;
+        g.mode = AF_SWIGLU;
+        g.W[0] = L.gate_q; g.W[1] = L.up_q; g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = cfg_.eps; g.Y[0] = mid_; g.ldy[0] = I;
+        hip_check(launch_affine_proj(g, s), "norm + gate/up");
+    } else if (gate_route == 2) {
+        quant_plain(L.gate_q, n, h_, H, L.ln2, nullptr, mid_, I, "norm + gate");
+        quant_plain(L.up_q, n, h_, H, L.ln2, nullptr, mid2_, I, "norm + up");
+        hip_check(launch_swiglu_mul(mid_, mid2_, (size_t)n * I, s), "swiglu");
+    } else {
+        QFusedArgs g;
+        g.mode = QF_SWIGLU;
+        quant_source(g, n, h_, H, H, L.ln2, q6(L.gate_q) || q6(L.up_q), "norm + q8k 2");
+        g.W[0] = L.gate_q; g.W[1] = L.up_q; g.jobs = I; g.Y[0] = mid_; g.ldy[0] = I;
+        hip_check(launch_qfused(g, s), "norm + gate/up");
+    }
+    if (quant_stage_route(pd, 1) != 0) {
+        quant_plain(L.down_q, n, mid_, I, nullptr, h_, h_, H, "down proj");
+        return;
+    }
     QFusedArgs dn;
     quant_source(dn, n, mid_, I, I, nullptr, q6(L.down_q), "q8k down");
     dn.W[0] = L.down_q; dn.seg_jobs[0] = dn.jobs = H / 2; dn.R = h_; dn.ldr = H; dn.Y[0] = h_; dn.ldy[0] = H;
@@ -837,6 +946,11 @@ void LlmModel::step_qkv(StepRoute route, int n, const Layer& L, const int* pos, 
             hip_check(launch_rope(q_, QD, n, c.heads, d, cos_, sin_, cache_len_, pos, 0, s), "rope q");
             hip_check(launch_rope(L.k_cache, kv, n, c.kv_heads, d, cos_, sin_, cache_len_, pos, 1, s), "rope k");
         }
+        return;
+    }
+    const QMat* qkv_mats[3] = {&L.q, &L.k, &L.v};
+    if (const int r = quant_ ? quant_stage_route(qkv_mats, 3) : 0) {
+        affine_qkv(n, L, r, q_, H, L.k_cache, L.v_cache, kv, cache_len_, pos, true);
         return;
     }
     if (quant_) {
@@ -1070,7 +1184,8 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
         wbu = 0;
         bf = false;
     } else if (qm) {
-        hip_check(launch_qdequant(*qm, pw32_, s), what);
+        if (ggml_affine_type(qm->type)) hip_check(launch_affine_dequant(*qm, pw32_, s), what);
+        else hip_check(launch_qdequant(*qm, pw32_, s), what);
         if (q8k_rows) {
             hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
             Ain = pact_;
@@ -2320,8 +2435,11 @@ void LlmModel::lane_step(int n)
     embed_rows(reinterpret_cast<const uint32_t*>(b.dev.token), n, h_, 0, nullptr, b.dev.pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
+        const QMat* qkv_mats[3] = {&L.q, &L.k, &L.v};
         if (fp8_) {
             fp8_qkv(n, L, b.qkv, ldq, b.qkv + QD, b.qkv + QD + kv, ldq, 0, nullptr);
+        } else if (const int r = quant_ ? quant_stage_route(qkv_mats, 3) : 0) {
+            affine_qkv(n, L, r, b.qkv, ldq, b.qkv + H, b.qkv + H + kv, ldq, 0, nullptr, false);
         } else if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
             QFusedArgs a;
             a.mode = QF_PLAIN;
@@ -2890,7 +3008,9 @@ void LlmModel::set_fp8_matrix_cores(bool on)
 
 void LlmModel::set_ggml_matrix_cores(bool on)
 {
-    if (!quant_ || fp8_ || on == ggml_mc_) return;
+    // (a checkpoint that holds a Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrix stays where it is: ggml_gemm.hip has no instance for them;
+    // so does a Q8_0-only file whose hidden or intermediate size is no multiple of 256, the only widths the route has been run at)
+    if (!quant_ || fp8_ || affine_ || cfg_.hidden % 256 || cfg_.inter % 256 || on == ggml_mc_) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(stream_), "sync");
     drop_lane_graphs(wide_bank_);  // (they hold the route's launches)

@@ -22,6 +22,7 @@
 #include "fp8_kernels.h"
 #include "generation_run.h"
 #include "llm_kernels.h"
+#include "affine_kernels.h"
 #include "quant_kernels.h"
 #include "sampling.h"
 
@@ -666,6 +667,16 @@ private:
     // quant_finish (layer_finish's quantized form): o-proj + residual, RMSNorm + gate/up + SwiGLU, down + residual.
     void quant_source(QFusedArgs& a, int n, const float* X, int ldx, int k, const float* gamma, bool q8k, const char* what);
     void quant_finish(int n, const Layer& L);
+    // Stages that hold a Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrix, or a Q8_0 one whose K is no multiple of 256 (affine_kernels.hip).
+    // quant_stage_route: 0 the stage as before that family, 1 one launch of the affine projection (every matrix is one of the five
+    // types or Q8_0), 2 a plain launch per matrix, each by its own family (Q4_K / Q6_K beside a new type).  quant_plain: one matrix
+    // over n rows of X (normalised by gamma), a Q6_K linear through qprep.  affine_qkv: Q | K | V as plain segments (K / V rows at
+    // row_off / *row_off_ptr + r); rotate: the step's RoPE -- in the epilogue of the matrices qfused_kernel projects, launch_rope
+    // where the rows sit for the others.
+    static int quant_stage_route(const QMat* const* mats, int count);
+    void quant_plain(const QMat& W, int n, const float* X, int ldx, const float* gamma, const float* R, float* Y, int64_t ldy, const char* what);
+    void affine_qkv(int n, const Layer& L, int route, float* q, int64_t ldq, float* kdst, float* vdst, int64_t ldkv, int row_off,
+                    const int* row_off_ptr, bool rotate);
     // FP8 checkpoints ride the quantized control flow with kernels of their own (fp8_kernels.hip).  fp8_qkv: norm + Q | K | V
     // as plain segments in one launch, Q into `q` (rows of ldq), K / V into rows row_off / *row_off_ptr + r of `kdst` / `vdst`.
     void fp8_qkv(int n, const Layer& L, float* q, int64_t ldq, float* kdst, float* vdst, int64_t ldkv, int row_off, const int* row_off_ptr);
@@ -683,6 +694,8 @@ private:
     float* xn_ = nullptr;       // quantized decode: normalised rows [8, max(H, I)]
     int8_t* xq_ = nullptr;      // their Q8_K codes
     float* xd_ = nullptr;       // and scales
+    float* mid2_ = nullptr;     // the up rows [8, I] of a gate/up stage that runs a launch per matrix (quant_stage_route 2)
+    bool affine_ = false;       // the checkpoint holds a Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrix
     float* pact_ = nullptr;     // prompt route, Q6_K linears: the activation rows through Q8_K and back
     DeviceArena arena_;   // every device buffer of the model
     std::vector<Layer> layers_;

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "affine_kernels.h"
 #include "gguf.h"
 
 namespace kjarni {
@@ -524,6 +525,7 @@ bool ggml_matrix_type(uint32_t type) { return type == GGML_Q8_0 || type == GGML_
 
 QPlanes repack_ggml(uint32_t type, const uint8_t* blocks, int n, int k)
 {
+    if (ggml_affine_type(type)) return repack_affine32(type, blocks, n, k);  // (affine_kernels.hip: its own layout)
     QPlanes p;
     const int64_t N = n;
     auto f16 = [](const uint8_t* src) {

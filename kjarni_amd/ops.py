@@ -869,6 +869,66 @@ def fused_proj_ggml(mode: int, mats, x, rows: int, ys, gamma=None, eps: float = 
     return out, ((xn, xq, xd) if q8k else None)
 
 
+_AFFINE_BLOCK = {2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 13: (256, 176), 8: (32, 34)}
+
+
+def _affine_blocks(ggml_type, blocks, n, k):
+    """Raw blocks [n, bytes per row] of an affine-32 type or Q8_0, checked against k as _ggml_blocks does."""
+    ba = np.ascontiguousarray(blocks, np.uint8)
+    be, bb = _AFFINE_BLOCK.get(int(ggml_type), (0, 0))
+    if be and k >= be and k % be == 0 and ba.size != n * (k // be) * bb:
+        raise ValueError(f"blocks: {n} rows of {k // be} blocks of {bb} bytes, not {ba.size} bytes")
+    return ba
+
+
+def affine_proj(mode: int, mats, x, rows: int, ys, gamma=None, eps: float = 0.0, bias=None, bias_off=(0, 0, 0), r=None,
+                r_is_y0: bool = False, row_off: int = 0, offset_on_device: bool = False, k: Optional[int] = None, in_place: bool = False,
+                device: int = 0):
+    """One launch_affine_proj on host arrays (kjarni_hip_op_affine_proj).  mats: 1-3 of (ggml type -- Q4_0 / Q4_1 / Q5_0 / Q5_1 /
+    Q5_K or Q8_0 --, raw blocks uint8 [n, bytes per row]); k: the matrices' columns (default: x's); ys: the mode's outputs
+    [out_rows, ldy] as they are before the launch.  Returns the outputs after it."""
+    xa, out, yp, orows, ldy, ra = _proj_common(mats, x, ys, r, rows, in_place)
+    k = xa.shape[1] if k is None else int(k)
+    if any(np.ndim(b) != 2 for _, b in mats):
+        raise ValueError("blocks [n, bytes per row]")
+    blocks = [_affine_blocks(t, b, np.shape(b)[0], k) for t, b in mats]
+    bp = (C.c_void_p * 3)(*[b.ctypes.data for b in blocks])
+    ty = (C.c_int32 * 3)(*[int(t) for t, _ in mats])
+    n = (C.c_int32 * 3)(*[b.shape[0] for b in blocks])
+    g, b = _proj_vector(gamma, k, "gamma"), _c(bias)
+    boff = (C.c_int32 * 3)(*[int(v) for v in bias_off])
+    check_error(lib().kjarni_hip_op_affine_proj(device, int(mode), bp, ty, n, k, _f(xa), xa.shape[0], xa.shape[1], int(rows), _f(g), float(eps),
+                                                _f(b), 0 if b is None else b.size, boff, _f(ra), 0 if ra is None else ra.shape[1],
+                                                int(bool(r_is_y0)), yp, orows, ldy, int(row_off), int(bool(offset_on_device))))
+    return out
+
+
+def affine_repack(ggml_type: int, blocks, n: int, k: int):
+    """The affine-32 device planes of raw blocks [n, k] (kjarni_hip_op_affine_repack; host only): (nibbles uint8 [n, k / 2],
+    fifth bits uint32 [n, k / 32] -- None for a 4-bit type --, ab float32 [n, k / 32, 2])."""
+    ba = _affine_blocks(ggml_type, blocks, int(n), int(k))
+    runs = max(k // 32, 1)
+    nib, high, ab = np.zeros((n, runs * 16), np.uint8), np.zeros((n, runs), np.uint32), np.zeros((n, runs, 2), np.float32)
+    check_error(lib().kjarni_hip_op_affine_repack(ba.ctypes.data_as(C.c_void_p), int(ggml_type), int(n), int(k), nib.ctypes.data_as(C.c_void_p),
+                                                  high.ctypes.data_as(C.c_void_p), _f(ab)))
+    return nib, (high if int(ggml_type) in (6, 7, 13) else None), ab
+
+
+def affine_dequant(ggml_type: int, blocks, n: int, k: int, ids=None, out=None, device: int = 0):
+    """launch_affine_dequant alone (kjarni_hip_op_affine_dequant): the matrix [n, k] in f32 -- or, with ids, launch_affine_embed:
+    the rows ids[i] [len(ids), k], an id >= n giving zeros."""
+    ba = _affine_blocks(ggml_type, blocks, int(n), int(k))
+    ia = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+    m = n if ia is None else ia.size
+    oa = np.full((m, k), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+    if oa.size != m * k:
+        raise ValueError("out: [rows, k]")
+    check_error(lib().kjarni_hip_op_affine_dequant(device, ba.ctypes.data_as(C.c_void_p), int(ggml_type), int(n), int(k),
+                                                   None if ia is None else ia.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if ia is None else ia.size,
+                                                   _f(oa)))
+    return oa
+
+
 def qembed(ids, ggml_type: int, blocks, vocab: int, k: int, out=None, device: int = 0):
     """launch_qembed alone (kjarni_hip_op_qembed): the dequantized table rows ids[i] [len(ids), k]; an id >= vocab gives zeros."""
     ia = np.ascontiguousarray(ids, np.uint32)

@@ -72,6 +72,13 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            Q4_K_M mix of tests/gguf_fixture.py on random codes; forward() on 128 / 384 tokens with the switch off, on and for bf16,
            generate_wide at 16 / 32 / 64 lanes with the switch on against GGUF generate_batch at 8 lanes and against a bf16 load at
            the same widths; every leg twice in one process, best of two.  The lines also go to profiles/llm_wide_gguf_bench.jsonl.
+  llm_affine  (only on request) GGUF decoders with Q4_0 / Q5_K matrices quantized in HBM (affine_kernels.hip): Llama-3.2-1B shape on
+           random blocks as an all-Q4_0 file, a Q5_K_M-style mix (Q5_K, Q6_K token_embd and Q6_K attn_v / ffn_down in the even
+           layers: half the Q|K|V stages run one launch per matrix), the same mix with attn_v in Q5_K (no mixed Q|K|V stage: the
+           difference is the per-matrix fallback's cost), the Q4_K_M mix and bf16; single-stream tokens/s and the 128-token
+           prompt's time, the legs alternated twice in one process, best of two; set_ggml_matrix_cores(True) tried on each file.
+           The line also goes to profiles/llm_affine_bench.jsonl.  KJARNI_AFFINE_TRACE=1: only one Q8_0 and one Q4_0 matrix
+           [2 048, K] at K = 2 048 / 8 192, 1 and 8 rows, through affine_proj_kernel and (Q8_0) qfused_kernel, for a kernel trace.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1166,6 +1173,94 @@ def main():
         del bdec
         emit(line)
         with open(os.path.join(ROOT, "profiles", "llm_wide_gguf_bench.jsonl"), "w") as f:
+            f.write(json.dumps(line) + "\n")
+
+    if "llm_affine" in which:
+        # Method (as llm_wide_gguf): one process on one box, every decoder loaded and warmed first, then the legs alternated twice,
+        # best of two; a decode window is a whole generate() minus the same call cut after its first token; a prompt's time is the
+        # median of 5 forward() calls that end in a synchronise.
+        from kjarni_amd import ops
+        from tests import gguf_fixture
+        from tests import gguf_types_fixture as T
+        rng = np.random.default_rng(0)
+        if os.environ.get("KJARNI_AFFINE_TRACE"):
+            for k in (2048, 8192):
+                for t in (8, T.Q4_0):
+                    blocks = T.random_blocks(t, 2048, k, rng)
+                    for rows in (1, 8):
+                        x = rng.standard_normal((rows, k)).astype(np.float32)
+                        for _ in range(5):
+                            ops.affine_proj(0, [(t, blocks)], x, rows, [np.zeros((rows, 2048), np.float32)], k=k)
+                            if t == 8:
+                                ops.fused_proj_ggml(0, [(t, blocks)], x, rows, [np.zeros((rows, 2048), np.float32)], k=k)
+            return
+        n_new = 128
+        gcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=synth.LLAMA_1B["vocab_size"] + 1)
+        layers = gcfg["num_hidden_layers"]
+        names = ("embed", "q", "k", "v", "o", "gate", "up", "down")
+        q5km = dict({key: T.Q5_K for key in names}, **gguf_fixture.q4_k_m_types(layers))
+        files = {"q4_0": {key: T.Q4_0 for key in names}, "q5_k_m": q5km,
+                 "q5_k_m_v_q5_k": {key: v for key, v in q5km.items() if not key.startswith("v.")},
+                 "q4_k_m": gguf_fixture.q4_k_m_types(layers)}
+        decs = {}
+        for name, types in files.items():
+            path = os.path.join(tmp, f"llama-1b-{name}.gguf")
+            T.gguf_model(path, gcfg, types, seed=0, rope_freqs=True, keep_hf=False)
+            decs[name] = kjarni_amd.HipDecoder(path, max_context=2048)
+        bdir = os.path.join(tmp, "llama-1b-bf16-affine")
+        synth.llm_model(bdir, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        decs["bf16"] = kjarni_amd.HipDecoder(bdir, max_context=2048)
+        prompt = rng.integers(1000, 100000, 128).tolist()
+
+        def leg(dec):
+            t0 = time.perf_counter()
+            dec.generate(prompt, 1)
+            t1 = time.perf_counter()
+            out = dec.generate(prompt, n_new)
+            t2 = time.perf_counter()
+            assert len(out) == n_new
+            ts = []
+            for _ in range(6):
+                dec.reset()
+                t0p = time.perf_counter()
+                dec.forward(prompt, fetch=False)
+                ts.append((time.perf_counter() - t0p) * 1e3)
+            dt = (t2 - t1) - (t1 - t0)
+            return {"tokens_per_s": round((n_new - 1) / dt, 1), "ms_per_token": round(dt * 1e3 / (n_new - 1), 4),
+                    "prompt_128_ms": round(float(np.median(ts[1:])), 3)}
+
+        def better(a, b):
+            return {"tokens_per_s": max(a["tokens_per_s"], b["tokens_per_s"]), "ms_per_token": min(a["ms_per_token"], b["ms_per_token"]),
+                    "prompt_128_ms": min(a["prompt_128_ms"], b["prompt_128_ms"])}
+
+        for dec in decs.values():
+            dec.generate(prompt, 8)
+        off, on, switch = {}, {}, {}
+        for rep in range(2):
+            for name, dec in decs.items():
+                r = leg(dec)
+                off[name] = better(off[name], r) if name in off else r
+                if name == "bf16":
+                    continue
+                dec.set_ggml_matrix_cores(True)
+                switch[name] = bool(dec.ggml_matrix_cores())   # (False: no instance for the file's types, nothing is rerouted)
+                if switch[name]:
+                    r = leg(dec)
+                    on[name] = better(on[name], r) if name in on else r
+                dec.set_ggml_matrix_cores(False)
+        fallback = off["q5_k_m"]["ms_per_token"] - off["q5_k_m_v_q5_k"]["ms_per_token"]
+        line = {"metric": "tokens/sec greedy decode, Llama-3.2-1B shape, GGUF all-Q4_0 in HBM, batch 1", "value": off["q4_0"]["tokens_per_s"],
+                "unit": "tokens/s", "n_gpus": 1, "data": "synthetic", "dtype": "Q4_0 / Q5_K / Q6_K blocks in HBM, f32 activations/accumulate/KV",
+                "config": {"workload": f"random blocks, 128-token prompt, {n_new} generated tokens; legs alternated twice in one process, best of two"},
+                "ggml_switch_off": off, "ggml_switch_on": on, "ggml_switch_taken": switch,
+                "per_matrix_fallback": {"ms_per_token": round(fallback, 4), "mixed_qkv_stages": layers // 2,
+                                        "us_per_stage": round(fallback * 1e3 / (layers // 2), 2),
+                                        "share_of_q5_k_m_token": round(fallback / off["q5_k_m"]["ms_per_token"], 4)},
+                "x_bf16": {k: round(v["tokens_per_s"] / off["bf16"]["tokens_per_s"], 3) for k, v in off.items()},
+                "weight_bytes": {k: d.weight_bytes for k, d in decs.items()}}
+        decs.clear()
+        emit(line)
+        with open(os.path.join(ROOT, "profiles", "llm_affine_bench.jsonl"), "w") as f:
             f.write(json.dumps(line) + "\n")
 
     if "llm_lookup" in which:
