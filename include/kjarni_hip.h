@@ -930,6 +930,16 @@ int32_t kjarni_hip_decoder_fp8_matrix_cores(const KjarniHipDecoder* decoder);
  * kjarni_hip_decoder_set_fp8_matrix_cores stays a no-op on a GGUF checkpoint, and this switch on an FP8 one. */
 void kjarni_hip_decoder_set_ggml_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
 int32_t kjarni_hip_decoder_ggml_matrix_cores(const KjarniHipDecoder* decoder);
+/* Every GGUF checkpoint on the matrix cores (off by default; a no-op on a checkpoint that is not GGUF-quantized; a NULL handle is
+ * ignored).  kjarni_hip_decoder_set_ggml_matrix_cores leaves a checkpoint off that holds a Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrix, or
+ * whose hidden or intermediate size is no multiple of 256; this switch takes any GGUF checkpoint.  On: a prompt projection of up to a
+ * few hundred rows sends a matrix of those five types to launch_prefill_gemm_affine, which multiplies the 4- / 5-bit codes themselves
+ * on the bf16 matrix cores with (a, b) of every run of 32 applied in f32, and any other matrix to launch_prefill_gemm_ggml; the
+ * checkpoint is accepted on the wide lanes (9 .. 64).  With both switches off everything enqueued is what it was before either
+ * existed, the refusal above 8 lanes included.  Flipping it drops the captured wide-step graphs.
+ * kjarni_hip_decoder_affine_matrix_cores reads it back (0 for NULL). */
+void kjarni_hip_decoder_set_affine_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
+int32_t kjarni_hip_decoder_affine_matrix_cores(const KjarniHipDecoder* decoder);
 /* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
  * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
  * tokens as kept and the rest of the prompt as computed. */
@@ -1229,6 +1239,14 @@ KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, const float* a, i
 KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks, int32_t ggml_type,
                                                 const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
                                                 int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used, int64_t* scratch_written);
+/* kjarni_hip_op_prefill_gemm_affine: kjarni_hip_op_prefill_gemm_ggml for the types it refuses -- ggml_type 2 Q4_0, 3 Q4_1, 6 Q5_0,
+ * 7 Q5_1, 13 Q5_K -- through launch_prefill_gemm_affine: the blocks are repacked into the affine-32 planes as the loader does and
+ * y = a . dequantize(blocks)^T (+ bias) (+ r), the nibbles and fifth bits unpacked in the tile loader.  Every other argument and
+ * output as there.  INVALID_CONFIG, before any GPU work and with every output untouched: the refusals of
+ * kjarni_hip_op_prefill_gemm, a type that is not one of the five, k % 32 (k % 256 for Q5_K). */
+KjarniErrorCode kjarni_hip_op_prefill_gemm_affine(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks, int32_t ggml_type,
+                                                  const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, float* gate,
+                                                  int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used, int64_t* scratch_written);
 /* kjarni_hip_op_prefill_attention: causal grouped-query attention of `rows` prompt rows at positions base .. base + rows - 1 over
  * key rows 0 .. base + rows - 1 through launch_prefill_attention: query row s sees keys <= base + s.  q [rows, ldq]
  * (heads * head_dim used); k / v: k_floats / v_floats floats, key row t at k + t * ldk, KV head h / kv_group at columns
@@ -1440,6 +1458,9 @@ KjarniErrorCode kjarni_hip_generator_set_fp8_matrix_cores(KjarniGenerator* gener
 /* kjarni_hip_decoder_set_ggml_matrix_cores on the handle's model. */
 KjarniErrorCode kjarni_hip_chat_set_ggml_matrix_cores(KjarniChat* chat, int32_t on);
 KjarniErrorCode kjarni_hip_generator_set_ggml_matrix_cores(KjarniGenerator* generator, int32_t on);
+/* kjarni_hip_decoder_set_affine_matrix_cores on the handle's model. */
+KjarniErrorCode kjarni_hip_chat_set_affine_matrix_cores(KjarniChat* chat, int32_t on);
+KjarniErrorCode kjarni_hip_generator_set_affine_matrix_cores(KjarniGenerator* generator, int32_t on);
 void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
 
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */

@@ -258,6 +258,12 @@ class Chat:
         the checkpoint on more than 8 lanes.  Off by default; a no-op on a checkpoint that is not GGUF-quantized."""
         check_error(lib().kjarni_hip_chat_set_ggml_matrix_cores(self._handle, 1 if on else 0))
 
+    def set_affine_matrix_cores(self, on: bool):
+        """Every GGUF checkpoint, Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrices included: multiply the codes themselves on the bf16 matrix
+        cores in the prompt GEMM, and accept the checkpoint on more than 8 lanes.  Off by default; a no-op on a checkpoint that is
+        not GGUF-quantized."""
+        check_error(lib().kjarni_hip_chat_set_affine_matrix_cores(self._handle, 1 if on else 0))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose cache rows were kept / computed by the calls that ran with reuse on."""
         a, b = C.c_uint64(0), C.c_uint64(0)

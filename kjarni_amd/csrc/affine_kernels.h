@@ -43,6 +43,14 @@ struct AffineProjArgs {
 hipError_t launch_affine_proj(const AffineProjArgs& a, hipStream_t stream);
 // W (an affine type) dequantized into out [n, k] f32: fmaf(a, q, b) per weight.
 hipError_t launch_affine_dequant(const QMat& W, float* out, hipStream_t stream);
+// The prompt GEMM on the affine-32 planes (affine_gemm.hip): Y[M, N] = A[M, K] . W^T (+ bias) (+ R), N = W.n, K = W.k, on the bf16
+// matrix cores -- the codes, less 8 / 16, become exact bf16 integers in the tile loader, the f32 activations three exact bf16 pieces,
+// (a, b) of every run is applied in f32.  launch_prefill_gemm_ggml's contract (quant_kernels.h): tile order, K-slice rule
+// (prefill_gemm_launch_ksplit), scratch layout and reduce kernel, R may alias Y, silu_gate as there.  Refused (hipErrorInvalidValue):
+// a type that is not one of the five, K % 32 (K % 256 for Q5_K), lda % 4, A or a plane not 16-byte aligned, a 5-bit type without
+// q2, a gate with ldy != N or N % 4.
+hipError_t launch_prefill_gemm_affine(const float* A, int64_t lda, const QMat& W, const float* bias, const float* R, int64_t ldr, float* Y,
+                                      int64_t ldy, int M, hipStream_t stream, float* split_scratch = nullptr, float* silu_gate = nullptr);
 // Embedding rows ids[0..n) of an affine-type table [vocab, hidden], dequantized; an id >= vocab gives zeros.
 hipError_t launch_affine_embed(const uint32_t* ids, int n, const QMat& table, float* out, hipStream_t stream);
 

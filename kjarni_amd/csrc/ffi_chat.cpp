@@ -1048,6 +1048,19 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_ggml_matrix_cores(KjarniG
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->model().set_ggml_matrix_cores(on != 0); });
 }
 
+// Every GGUF checkpoint on the matrix cores (LlmModel::set_affine_matrix_cores) on the handle's model.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_affine_matrix_cores(KjarniChat* chat, int32_t on)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->model().set_affine_matrix_cores(on != 0); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_affine_matrix_cores(KjarniGenerator* gen, int32_t on)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->model().set_affine_matrix_cores(on != 0); });
+}
+
 KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
 {
     if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;

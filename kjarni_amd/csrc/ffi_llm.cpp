@@ -1084,6 +1084,17 @@ KJARNI_EXPORT void kjarni_hip_decoder_set_ggml_matrix_cores(KjarniHipDecoder* d,
 
 KJARNI_EXPORT int32_t kjarni_hip_decoder_ggml_matrix_cores(const KjarniHipDecoder* d) { return d && d->model->ggml_matrix_cores() ? 1 : 0; }
 
+// ---- every GGUF checkpoint on the matrix cores (LlmModel::set_affine_matrix_cores) -----------------------------------------------
+
+KJARNI_EXPORT void kjarni_hip_decoder_set_affine_matrix_cores(KjarniHipDecoder* d, int32_t on)
+{
+    if (!d) return;
+    std::lock_guard<std::mutex> lock(d->mu);
+    (void)guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { d->model->set_affine_matrix_cores(on != 0); });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_affine_matrix_cores(const KjarniHipDecoder* d) { return d && d->model->affine_matrix_cores() ? 1 : 0; }
+
 KJARNI_EXPORT void kjarni_hip_decoder_prefix_stats(const KjarniHipDecoder* d, uint64_t* reused, uint64_t* computed)
 {
     if (reused) *reused = d ? d->model->prefix_reused_tokens() : 0;

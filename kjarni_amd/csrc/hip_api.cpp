@@ -3016,25 +3016,29 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_fp8(int32_t device, con
     });
 }
 
-// launch_prefill_gemm_ggml on host arrays: kjarni_hip_op_prefill_gemm's arguments with the weights as raw GGUF blocks [n, k] of one
-// type, repacked into the device planes (repack_ggml) as kjarni_hip_op_fused_proj_ggml does.
-KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks,
-                                                              int32_t ggml_type, const float* bias, const float* r, int64_t ldr, int32_t r_is_y,
-                                                              float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
-                                                              int32_t* ksplit_used, int64_t* scratch_written)
+namespace {
+
+// launch_prefill_gemm_ggml (affine: launch_prefill_gemm_affine) on host arrays: kjarni_hip_op_prefill_gemm's arguments with the weights
+// as raw GGUF blocks [n, k] of one type, repacked into the device planes (repack_ggml) as kjarni_hip_op_fused_proj_ggml does.
+KjarniErrorCode prefill_gemm_blocks_op(bool affine, int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks,
+                                       int32_t ggml_type, const float* bias, const float* r, int64_t ldr, int32_t r_is_y, float* y, int64_t ldy,
+                                       float* gate, int32_t m, int32_t n, int32_t k, int32_t split, int32_t* ksplit_used,
+                                       int64_t* scratch_written)
 {
     if (!a || !blocks || !y || !ksplit_used) return KJARNI_ERROR_NULL_POINTER;
+    const std::string who = affine ? "launch_prefill_gemm_affine" : "launch_prefill_gemm_ggml";
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         if (m < 0 || m > 4096 || a_rows < std::max(m, 1) || a_rows > 8192) throw InvalidConfig("m must be 0 .. 4096 and a_rows max(m, 1) .. 8192");
         if (n < 1 || k < 1 || n > (1 << 17) || k > (1 << 16) || (int64_t)n * k > ((int64_t)1 << 26))
             throw InvalidConfig("n must be 1 .. 2^17, k 1 .. 2^16, n * k at most 2^26");
-        check_qmat_type(ggml_type, k);
-        if (lda % 4) throw InvalidConfig("launch_prefill_gemm_ggml refuses these arguments: lda a multiple of 4");
+        if (affine) check_affine_type(ggml_type, k, false);
+        else check_qmat_type(ggml_type, k);
+        if (lda % 4) throw InvalidConfig(who + " refuses these arguments: lda a multiple of 4");
         if (lda < k || ldy < n || std::max(lda, ldy) > (1 << 18)) throw InvalidConfig("lda must cover k and ldy n (at most 2^18)");
         const bool res = r_is_y || r;
         const int64_t ldr_ = r_is_y ? ldy : ldr;
         if (res && (ldr_ < n || ldr_ > (1 << 18))) throw InvalidConfig("ldr must cover n (at most 2^18)");
-        if (gate && (ldy != n || (n & 3))) throw InvalidConfig("launch_prefill_gemm_ggml refuses these arguments: a gate needs ldy == n and n a multiple of 4");
+        if (gate && (ldy != n || (n & 3))) throw InvalidConfig(who + " refuses these arguments: a gate needs ldy == n and n a multiple of 4");
         if (split != 0 && split != 1) throw InvalidConfig("split must be 0 or 1");
         if (scratch_written && !split) throw InvalidConfig("scratch_written without split");
         use_device(device);
@@ -3058,8 +3062,9 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, co
         const float* rp = r_is_y ? yd.as<const float>() : (r ? rd.as<const float>() : nullptr);
         float* sp = split ? sd.as<float>() : nullptr;
         *ksplit_used = prefill_gemm_launch_ksplit(bp, rp, ldr_, yd.as<const float>(), ldy, m, n, k, sp);
-        launcher_check(launch_prefill_gemm_ggml(ad.as<const float>(), lda, W, bp, rp, ldr_, yd.as<float>(), ldy, m, nullptr, sp,
-                                                gate ? gd.as<float>() : nullptr), "ggml prefill gemm");
+        launcher_check((affine ? launch_prefill_gemm_affine : launch_prefill_gemm_ggml)(ad.as<const float>(), lda, W, bp, rp, ldr_, yd.as<float>(), ldy,
+                                                                                        m, nullptr, sp, gate ? gd.as<float>() : nullptr),
+                       affine ? "affine prefill gemm" : "ggml prefill gemm");
         hip_check(hipDeviceSynchronize(), "sync");
         yd.fetch(y, yb, "D2H y");
         gd.fetch(gate, gb, "D2H gate");
@@ -3071,6 +3076,27 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, co
             *scratch_written = (int64_t)(words.size() - (size_t)std::count(words.begin(), words.end(), 0xFFFFFFFFu));
         }
     });
+}
+
+}  // namespace
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_ggml(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks,
+                                                              int32_t ggml_type, const float* bias, const float* r, int64_t ldr, int32_t r_is_y,
+                                                              float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
+                                                              int32_t* ksplit_used, int64_t* scratch_written)
+{
+    return prefill_gemm_blocks_op(false, device, a, lda, a_rows, blocks, ggml_type, bias, r, ldr, r_is_y, y, ldy, gate, m, n, k, split, ksplit_used,
+                                  scratch_written);
+}
+
+// The same over the affine-32 planes (affine_gemm.hip): Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_prefill_gemm_affine(int32_t device, const float* a, int64_t lda, int32_t a_rows, const void* blocks,
+                                                                int32_t ggml_type, const float* bias, const float* r, int64_t ldr, int32_t r_is_y,
+                                                                float* y, int64_t ldy, float* gate, int32_t m, int32_t n, int32_t k, int32_t split,
+                                                                int32_t* ksplit_used, int64_t* scratch_written)
+{
+    return prefill_gemm_blocks_op(true, device, a, lda, a_rows, blocks, ggml_type, bias, r, ldr, r_is_y, y, ldy, gate, m, n, k, split, ksplit_used,
+                                  scratch_written);
 }
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_mask_lengths(int32_t device, const uint32_t* mask, int64_t batch, int32_t seq, uint32_t* lens_out)

@@ -1168,14 +1168,17 @@ void LlmModel::prompt_proj(int m, const float* Ain, int lda, const void* W, cons
         return;
     }
     const bool q8k_rows = qm && qm->type == GGML_Q6_K && q6k_q8k;  // a Q6_K linear: its rows through Q8_K and back first
-    if (qm && ggml_mc_ && !tiles) {  // the switch: the code bytes themselves on the bf16 matrix cores, no f32 copy of the matrix
+    if (qm && (ggml_mc_ || affine_mc_) && !tiles) {  // a switch: the code bytes themselves on the bf16 matrix cores, no f32 copy of the matrix
         if (gelu) throw InvalidConfig(std::string(what) + ": the GGUF matrix-core GEMM has no GELU epilogue");
         if (q8k_rows) {
             hip_check(launch_q8k_quantize(Ain, lda, m, K, nullptr, nullptr, pact_, s), what);
             Ain = pact_;
             lda = K;
         }
-        hip_check(launch_prefill_gemm_ggml(Ain, lda, *qm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
+        if (ggml_affine_type(qm->type))  // (only under affine_mc_: set_ggml_matrix_cores() leaves a checkpoint with such a matrix off)
+            hip_check(launch_prefill_gemm_affine(Ain, lda, *qm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
+        else
+            hip_check(launch_prefill_gemm_ggml(Ain, lda, *qm, bias, R, ldy, Y, ldy, m, s, psplit_, gate), what);
         return;
     }
     if (fm) {  // an FP8 matrix: decode(code) * scale into the f32 scratch, then the f32 route
@@ -2249,8 +2252,8 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
     const LlmConfig& c = cfg_;
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
     if (b.wide) {  // what the wide step alone asks of the checkpoint
-        if (quant_ && !fp8_mc_ && !ggml_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_, ggml_mc_ a GGUF checkpoint: with its switch
-                                              // on, the checkpoint's prompt GEMM reads the codes)
+        if (quant_ && !fp8_mc_ && !ggml_mc_ && !affine_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_, ggml_mc_ / affine_mc_ a GGUF
+                                                             // checkpoint: with its switch on, the checkpoint's prompt GEMM reads the codes)
             throw InvalidConfig(std::string("more than 8 lanes do not take a ") + (fp8_ ? "FP8" : "quantized (GGUF)") +
                                 " checkpoint: the prompt GEMM would dequantize every matrix in every step (8 lanes or fewer run it)");
         if (!rows_geometry(c) || !decode_attention_accepts(c.head_dim, splits_, cap, 1, true, true, false))
@@ -3016,6 +3019,16 @@ void LlmModel::set_ggml_matrix_cores(bool on)
     drop_lane_graphs(wide_bank_);  // (they hold the route's launches)
     wide_bank_.lanes = 0;       // a wide session ends here: lanes_begin() decides again
     ggml_mc_ = on;
+}
+
+void LlmModel::set_affine_matrix_cores(bool on)
+{
+    if (!quant_ || fp8_ || on == affine_mc_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    drop_lane_graphs(wide_bank_);  // (they hold the route's launches)
+    wide_bank_.lanes = 0;       // a wide session ends here: lanes_begin() decides again
+    affine_mc_ = on;
 }
 
 // One wide step, a linear chain on the model's stream: the embedding at the lanes' positions, per layer norm 1 -> ONE GEMM of

@@ -166,6 +166,15 @@ public:
     // enqueued is what it was before the switch existed.  Flipping it drops the captured wide graphs and ends a wide session.
     void set_ggml_matrix_cores(bool on);
     bool ggml_matrix_cores() const { return ggml_mc_; }
+    // ---- every GGUF checkpoint on the matrix cores (off by default; a no-op on a checkpoint that is not GGUF-quantized) ------------
+    // set_ggml_matrix_cores() leaves a checkpoint off that holds a Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrix or whose hidden or
+    // intermediate size is no multiple of 256.  This switch takes any GGUF checkpoint: on, a prompt projection on the 64 x 64 route
+    // sends a matrix of those five types to launch_prefill_gemm_affine (affine_gemm.hip) and any other to launch_prefill_gemm_ggml
+    // (Q8_0 at K % 32, a Q6_K linear with its Q8_K rows), and ensure_lane_bank() takes the checkpoint on the wide bank.  With both
+    // switches off everything enqueued is what it was before either existed.  Flipping it drops the captured wide graphs and ends a
+    // wide session.
+    void set_affine_matrix_cores(bool on);
+    bool affine_matrix_cores() const { return affine_mc_; }
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
     uint64_t prefix_reused_tokens() const { return prefix_reused_; }
     uint64_t prefix_computed_tokens() const { return prefix_computed_; }
@@ -816,6 +825,7 @@ private:
     bool prefix_reuse_ = false;
     bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
     bool ggml_mc_ = false;  // set_ggml_matrix_cores(): only ever true with quant_ && !fp8_
+    bool affine_mc_ = false;  // set_affine_matrix_cores(): only ever true with quant_ && !fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
 };
 

@@ -886,6 +886,17 @@ class HipDecoder:
     def ggml_matrix_cores(self) -> bool:
         return bool(lib().kjarni_hip_decoder_ggml_matrix_cores(self._h))
 
+    # ---- every GGUF checkpoint on the matrix cores ----
+    def set_affine_matrix_cores(self, on: bool):
+        """set_ggml_matrix_cores for every GGUF checkpoint, those with Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q5_K matrices or with sizes that are
+        only multiples of 32 included: on, the prompt GEMM multiplies the 4- / 5-bit codes themselves on the bf16 matrix cores
+        (launch_prefill_gemm_affine; any other matrix through launch_prefill_gemm_ggml) and generate_wide / the wide hooks accept the
+        checkpoint.  Off by default; a no-op on a checkpoint that is not GGUF-quantized."""
+        lib().kjarni_hip_decoder_set_affine_matrix_cores(self._h, 1 if on else 0)
+
+    def affine_matrix_cores(self) -> bool:
+        return bool(lib().kjarni_hip_decoder_affine_matrix_cores(self._h))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
         a, b = C.c_uint64(), C.c_uint64()

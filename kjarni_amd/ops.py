@@ -347,7 +347,7 @@ def prefill_gemm_fp8(a, codes, scale, m: int, y, bias=None, r=None, r_is_y: bool
 
 
 def prefill_gemm_ggml(a, blocks, ggml_type: int, k: int, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=None, split: bool = True,
-                      want_scratch_written: bool = False, device: int = 0):
+                      want_scratch_written: bool = False, device: int = 0, _hook: str = "kjarni_hip_op_prefill_gemm_ggml"):
     """launch_prefill_gemm_ggml on host arrays (kjarni_hip_op_prefill_gemm_ggml): prefill_gemm's arguments with the weights as raw
     GGUF blocks [n, bytes per row] (uint8) of ggml_type (8 Q8_0, 12 Q4_K, 14 Q6_K) and k columns.
     Returns (y, gate or None, ksplit_used[, scratch words written]) -- copies; the arguments stay as they were."""
@@ -365,11 +365,18 @@ def prefill_gemm_ggml(a, blocks, ggml_type: int, k: int, m: int, y, bias=None, r
     if ga is not None and ga.shape != (int(m), n):
         raise ValueError("gate: [m, n]")
     used, written = C.c_int32(-1), C.c_int64(-1)
-    check_error(lib().kjarni_hip_op_prefill_gemm_ggml(device, _f(aa), aa.shape[1], aa.shape[0], ba_.ctypes.data_as(C.c_void_p), int(ggml_type), _f(ba),
-                                                      _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y)), _f(ya), ya.shape[1], _f(ga),
-                                                      int(m), n, int(k), int(bool(split)), C.byref(used),
-                                                      C.byref(written) if want_scratch_written else None))
+    check_error(getattr(lib(), _hook)(device, _f(aa), aa.shape[1], aa.shape[0], ba_.ctypes.data_as(C.c_void_p), int(ggml_type), _f(ba),
+                                      _f(ra), 0 if ra is None else ra.shape[1], int(bool(r_is_y)), _f(ya), ya.shape[1], _f(ga),
+                                      int(m), n, int(k), int(bool(split)), C.byref(used), C.byref(written) if want_scratch_written else None))
     return (ya, ga, used.value, written.value) if want_scratch_written else (ya, ga, used.value)
+
+
+def prefill_gemm_affine(a, blocks, ggml_type: int, k: int, m: int, y, bias=None, r=None, r_is_y: bool = False, gate=None, split: bool = True,
+                        want_scratch_written: bool = False, device: int = 0):
+    """launch_prefill_gemm_affine on host arrays (kjarni_hip_op_prefill_gemm_affine): prefill_gemm_ggml's arguments and results for
+    ggml_type 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 13 Q5_K."""
+    return prefill_gemm_ggml(a, blocks, ggml_type, k, m, y, bias, r, r_is_y, gate, split, want_scratch_written, device,
+                             _hook="kjarni_hip_op_prefill_gemm_affine")
 
 
 # ---- the dense (f32 / bf16) decode-step projections, alone ----

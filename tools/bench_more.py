@@ -79,6 +79,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            prompt's time, the legs alternated twice in one process, best of two; set_ggml_matrix_cores(True) tried on each file.
            The line also goes to profiles/llm_affine_bench.jsonl.  KJARNI_AFFINE_TRACE=1: only one Q8_0 and one Q4_0 matrix
            [2 048, K] at K = 2 048 / 8 192, 1 and 8 rows, through affine_proj_kernel and (Q8_0) qfused_kernel, for a kernel trace.
+  llm_wide_affine  (only on request) every GGUF checkpoint on the matrix cores (HipDecoder.set_affine_matrix_cores): Llama-3.2-1B shape as
+           all-Q4_0 and as the Q5_K_M-style mix of llm_affine; the prompt at 128 / 384 tokens with the switch off / on / bf16, wide
+           lanes at 16 / 32 / 64 with the switch on against the same file at 8 lanes and bf16 at the same widths; llm_wide_gguf's
+           method: one process, legs alternated twice, best of two.  The lines also go to profiles/llm_wide_affine_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1174,6 +1178,87 @@ def main():
         emit(line)
         with open(os.path.join(ROOT, "profiles", "llm_wide_gguf_bench.jsonl"), "w") as f:
             f.write(json.dumps(line) + "\n")
+
+    if "llm_wide_affine" in which:
+        # Every GGUF checkpoint on the matrix cores (HipDecoder.set_affine_matrix_cores).  Method: llm_wide_gguf's -- one process on
+        # one box, every leg warmed first, every leg twice, best of two; a decode window is a whole call minus the same call cut after
+        # its first token; a prompt's time is the median of 5 forward() calls that end in a synchronise, the switch off and on
+        # alternated twice on one decoder, the better of two.
+        from tests import gguf_fixture
+        from tests import gguf_types_fixture as T
+        rng = np.random.default_rng(0)
+        n_new, ctx, wides = 64, 512, ("wide-16", "wide-32", "wide-64")
+
+        def wide_legs(dec, prompts, names):
+            legs = {"lanes-8": (8, lambda n: dec.generate_batch(prompts[:8], n, lanes=8, lane_context=ctx))}
+            for w in (16, 32, 64):
+                legs[f"wide-{w}"] = (w, (lambda w: lambda n: dec.generate_wide(prompts[:w], n, lanes=w, lane_context=ctx))(w))
+            legs = {k: v for k, v in legs.items() if k in names}
+            for _, fn in legs.values():
+                fn(12)
+            rows = {}
+            for rep in range(2):
+                for name, (width, fn) in legs.items():
+                    t0 = time.perf_counter()
+                    fn(1)
+                    t1 = time.perf_counter()
+                    outs = fn(n_new)
+                    dt = (time.perf_counter() - t1) - (t1 - t0)
+                    assert all(len(o) == n_new for o in outs)
+                    rows.setdefault(name, []).append({"tokens_per_s": round(width * (n_new - 1) / dt, 1), "ms_per_step": round(dt * 1e3 / (n_new - 1), 4)})
+            return {k: max(v, key=lambda r: r["tokens_per_s"]) for k, v in rows.items()}
+
+        def prompt_ms(dec, ids):
+            ts = []
+            for _ in range(6):
+                dec.reset()
+                t0 = time.perf_counter()
+                dec.forward(ids, fetch=False)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            return round(float(np.median(ts[1:])), 3)
+
+        gcfg = dict(synth.LLAMA_1B, max_position_embeddings=4096, eos_token_id=synth.LLAMA_1B["vocab_size"] + 1)
+        names = ("embed", "q", "k", "v", "o", "gate", "up", "down")
+        files = {"q4_0": {key: T.Q4_0 for key in names},
+                 "q5_k_m": dict({key: T.Q5_K for key in names}, **gguf_fixture.q4_k_m_types(gcfg["num_hidden_layers"]))}
+        prompts = [rng.integers(1000, 100000, 128).tolist() for _ in range(64)]
+        long_ids = {n: rng.integers(1000, 100000, n).tolist() for n in (128, 384)}
+        bdir = os.path.join(tmp, "llama-1b-bf16-wide-affine")
+        synth.llm_model(bdir, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        bdec = kjarni_amd.HipDecoder(bdir, max_context=2048)
+        bf = wide_legs(bdec, prompts, ("lanes-8",) + wides)
+        p_bf = {n: min(prompt_ms(bdec, ids) for _ in range(2)) for n, ids in long_ids.items()}
+        del bdec
+        lines = []
+        for name, types in files.items():
+            path = os.path.join(tmp, f"llama-1b-{name}-wide.gguf")
+            T.gguf_model(path, gcfg, types, seed=0, rope_freqs=True, keep_hf=False)
+            dec = kjarni_amd.HipDecoder(path, max_context=2048)
+            off = wide_legs(dec, prompts, ("lanes-8",))
+            dec.set_affine_matrix_cores(True)
+            on = wide_legs(dec, prompts, ("lanes-8",) + wides)
+            p_off, p_on = {}, {}
+            for rep in range(2):  # the prompt legs alternated off / on, twice, the better of two
+                for flag, dst in ((False, p_off), (True, p_on)):
+                    dec.set_affine_matrix_cores(flag)
+                    for n, ids in long_ids.items():
+                        dst[n] = min(dst.get(n, float("inf")), prompt_ms(dec, ids))
+            lines.append({"metric": f"aggregate tokens/sec greedy decode in wide lanes, Llama-3.2-1B shape, GGUF {name} on the bf16 matrix cores",
+                          "unit": "tokens/s", "value": on["wide-64"]["tokens_per_s"], "n_gpus": 1, "data": "synthetic",
+                          "dtype": "Q4_0 / Q5_K / Q6_K blocks in HBM, f32 activations/accumulate/KV",
+                          "config": {"workload": f"random codes, one 128-token prompt per lane, {n_new} generated tokens per lane, lane_context {ctx}; "
+                                                 "every leg twice in one process, best of two"},
+                          "affine_switch_off": off, "affine_switch_on": on, "bf16_same_shape": bf,
+                          "x_gguf_lanes_8": {k: round(on[k]["tokens_per_s"] / off["lanes-8"]["tokens_per_s"], 3) for k in wides},
+                          "x_bf16_same_width": {k: round(on[k]["tokens_per_s"] / bf[k]["tokens_per_s"], 3) for k in wides},
+                          "prompt_ms": {"affine_switch_off": p_off, "affine_switch_on": p_on, "bf16": p_bf},
+                          "prompt_x_switch_off": {n: round(p_on[n] / p_off[n], 3) for n in p_on},
+                          "weight_bytes": dec.weight_bytes})
+            del dec
+        with open(os.path.join(ROOT, "profiles", "llm_wide_affine_bench.jsonl"), "w") as f:
+            for line in lines:
+                emit(line)
+                f.write(json.dumps(line) + "\n")
 
     if "llm_affine" in which:
         # Method (as llm_wide_gguf): one process on one box, every decoder loaded and warmed first, then the legs alternated twice,
