@@ -1317,6 +1317,19 @@ KjarniErrorCode kjarni_hip_op_moe_ffn(int32_t device, const float* x, int64_t ld
                                       int32_t E, int32_t k, int32_t Im, int32_t norm_topk, const float* r, int64_t ldr, int32_t r_is_y, float* y,
                                       int64_t ldy, int32_t route, int32_t* ids_out, float* weights_out, int32_t* route_used,
                                       int32_t* tiles_used);
+/* kjarni_hip_op_moe_ffn_fp8: kjarni_hip_op_moe_ffn over FP8 (OCP e4m3fn) expert stacks that stay codes on the device: gate / up
+ * [E, Im, hidden] and down [E, hidden, Im] as one-byte codes, each with f32 scales [E, extent] of one `kind` for the three stacks
+ * (0 per tensor: extent 1; 1 per output channel: extent n; 2 blocks of 128 x 128: extent ceil(n / 128) * (k / 128), for a matrix
+ * [n, k]); w = decode(code) * scale.  router [E, hidden] is f32.  grouped: 0 the steps kernels in blocks of 8 rows, 1 the grouped
+ * matrix-core kernels; *tiles_used as there (0 on the steps route).  x, gamma, the residual, y, ids_out and weights_out as there.
+ * Every output has a guard band behind it on the device; a kernel that writes into one fails the call.  INVALID_CONFIG, before any
+ * GPU work and with every output untouched: what kjarni_hip_op_moe_ffn refuses, kind outside 0 .. 2, block scales with hidden or
+ * Im no multiple of 128, grouped outside 0 .. 1, a NaN code (0x7F / 0xFF) in a stack. */
+KjarniErrorCode kjarni_hip_op_moe_ffn_fp8(int32_t device, const float* x, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                          const float* router, const uint8_t* gate, const float* gate_scale, const uint8_t* up,
+                                          const float* up_scale, const uint8_t* down, const float* down_scale, int32_t kind, int32_t hidden,
+                                          int32_t E, int32_t k, int32_t Im, int32_t norm_topk, const float* r, int64_t ldr, int32_t r_is_y,
+                                          float* y, int64_t ldy, int32_t grouped, int32_t* ids_out, float* weights_out, int32_t* tiles_used);
 /* kjarni_hip_decoder_moe_routing: what sparse layer `layer` of a qwen3_moe decoder chose in its last pass (a decode step: 1 row;
  * a verify block or a lane step: its rows; a prompt chunk or a packed pass: its rows, at most 2048).  *rows gets the number of
  * rows recorded; ids_out / weights_out (each may be NULL to ask for the count alone; capacity rows_capacity * k) get [rows, k].

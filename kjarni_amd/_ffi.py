@@ -635,6 +635,9 @@ SIGNATURES = {
     "kjarni_hip_op_moe_ffn": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                         c_int32, c_int32, c_int32, c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int32, POINTER(c_int32),
                                         _f32p, POINTER(c_int32), POINTER(c_int32)]),
+    "kjarni_hip_op_moe_ffn_fp8": (c_int32, [c_int32, _f32p, c_int64, c_int32, _f32p, c_float, _f32p, c_void_p, _f32p, c_void_p, _f32p, c_void_p, _f32p,
+                                            c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _f32p, c_int64, c_int32, _f32p, c_int64, c_int32,
+                                            POINTER(c_int32), _f32p, POINTER(c_int32)]),
     "kjarni_hip_decoder_moe_routing": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), _f32p]),
     "kjarni_hip_op_rope": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p, c_int32, c_int32]),
     "kjarni_hip_op_rope_rows": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, c_int32, _f32p, _f32p, c_int32,

@@ -18,6 +18,7 @@
 
 #include "bf16_split.h"
 #include "device_utils.h"
+#include "fp8_decode.h"
 #include "fp8_kernels.h"
 #include "llm_kernels.h"
 
@@ -27,21 +28,6 @@ namespace {
 
 constexpr int FG_BM = 64, FG_BN = 64, FG_BK = 32;
 constexpr int FG_PLANE = 64 * 32;  // bf16 per plane: 64 rows x 64 bytes, the four 16-byte chunks of a row swizzled by (row >> 2) & 3
-
-// Eight codes (two dwords, code j in byte j) as eight bf16 in the same order: v_cvt_scalef32_pk_bf16_fp8 with scale 1.0, one
-// instruction per pair of codes (v_cvt_pk_f32_fp8 and a byte permute to keep the high halves is the same result in twice as many).
-// Every e4m3fn value is a bf16 number, so the conversion has nothing to round; the scale operand stays 1.0 -- a matrix's real scale
-// is applied in f32 (above).
-__device__ __forceinline__ u32x4 fp8x8_to_bf16x8(u32x2 c)
-{
-    u32x4 o;
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        o[2 * d] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[d], 1.0f, false));     // codes 4d, 4d + 1
-        o[2 * d + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[d], 1.0f, true));  // codes 4d + 2, 4d + 3
-    }
-    return o;
-}
 
 // One workgroup per (64 x 64 tile, K slice): 256 threads, four waves of one 32 x 32 tile each, LDS double-buffered as
 // [stage][A1 | A2 | A3 | W].  scale: FP8_PER_TENSOR [1], FP8_PER_CHANNEL [N], FP8_BLOCK [ceil(N / 128)][scale_cols].

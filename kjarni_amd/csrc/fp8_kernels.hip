@@ -23,6 +23,7 @@
 
 #include "device_utils.h"
 #include "dynamic_lds.h"
+#include "fp8_decode.h"
 #include "fp8_kernels.h"
 
 namespace kjarni {
@@ -32,9 +33,6 @@ namespace {
 constexpr int F8_ROWS_LIMIT = 8;
 // CH 16-code pieces per lane, column and slice: a workgroup holds CH * 1024 columns of K at a time (CH * 64 pieces per row, CH
 // float4 of one row's slice per thread).
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 // One matrix as the kernels index it: scale of (row j, column i) = scale[(j >> row_shift) * scale_cols + (i >> 7) * col_mul].
 struct Fp8Seg {
@@ -74,22 +72,6 @@ Fp8Seg make_seg(const Fp8Mat& m)
     s.scale_cols = m.kind == FP8_BLOCK ? m.k / kFp8Block : 1;
     s.col_mul = m.kind == FP8_BLOCK ? 1 : 0;
     return s;
-}
-
-__device__ __forceinline__ u32x4 load_nt16(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
-// The 16 codes of a piece as floats (code 4 d + e of the piece in w[4 d + e]).
-__device__ __forceinline__ void decode16(u32x4 p, float (&w)[16])
-{
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const f32x2v lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p[d], false);
-        const f32x2v hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p[d], true);
-        w[4 * d] = lo[0];
-        w[4 * d + 1] = lo[1];
-        w[4 * d + 2] = hi[0];
-        w[4 * d + 3] = hi[1];
-    }
 }
 
 // Column n of the concatenated matrices: which segment, and its row there (NM == 2: both segments hold column n).

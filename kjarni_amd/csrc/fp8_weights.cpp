@@ -61,7 +61,7 @@ Fp8Checkpoint::Fp8Checkpoint(const SafeTensors& st, const std::string& config_js
 
 bool Fp8Checkpoint::is_fp8(const std::string& name) const { return st_.contains(name) && st_.get(name).dtype == "F8_E4M3"; }
 
-Fp8Tensor Fp8Checkpoint::read(const std::string& name) const
+Fp8Tensor Fp8Checkpoint::describe(const std::string& name, std::string* scale_name) const
 {
     const TensorView& w = st_.get(name);
     if (w.dtype != "F8_E4M3") throw std::runtime_error("tensor " + name + " is " + w.dtype + ", not F8_E4M3");
@@ -99,8 +99,16 @@ Fp8Tensor Fp8Checkpoint::read(const std::string& name) const
     if (t.kind < 0)
         throw std::runtime_error("scale " + sname + " of FP8 tensor " + name + " " + shape_text(w.shape) + " has shape " + shape_text(ss) +
                                  ": neither one element (per tensor), [n] / [n, 1] (per channel) nor [ceil(n / 128), k / 128] (block)");
+    if (scale_name) *scale_name = sname;
+    return t;
+}
+
+Fp8Tensor Fp8Checkpoint::read(const std::string& name) const
+{
+    std::string sname;
+    Fp8Tensor t = describe(name, &sname);
     st_.read_f32(sname, t.scale);
-    t.codes = w.data;
+    t.codes = st_.get(name).data;
     for (int64_t i = 0, e = t.n * t.k; i < e; ++i)
         if ((t.codes[i] & 0x7F) == 0x7F) {
             char hex[8];

@@ -32,6 +32,9 @@ public:
     // The matrix `name` (X.weight) with its scale, checked: a missing scale, both scale names, a scale shape that fits no kind,
     // k % 16, a block size other than 128, another fmt, a NaN code.
     Fp8Tensor read(const std::string& name) const;
+    // read()'s checks of the header alone: shape, scale tensor, kind -- codes null, scale empty, no NaN scan (the file's pages stay
+    // untouched: what a host-side check of a large checkpoint asks before the upload reads every matrix anyway)
+    Fp8Tensor describe(const std::string& name, std::string* scale_name = nullptr) const;
     // The same, dequantized: out[j, i] = decode(code) * scale in f32; returns the shape.
     std::vector<int64_t> read_f32(const std::string& name, std::vector<float>& out) const;
 

@@ -22,6 +22,7 @@
 #include "whisper_kernels.h"
 #include "quant_kernels.h"
 #include "moe_kernels.h"
+#include "moe_fp8_kernels.h"
 #include "logprob_kernels.h"
 
 using namespace kjarni;
@@ -1059,6 +1060,117 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_moe_ffn(int32_t device, const float*
         hip_check(hipMemcpy(ids_out, idd.p, S * 4, hipMemcpyDeviceToHost), "D2H ids");
         hip_check(hipMemcpy(weights_out, wtd.p, S * 4, hipMemcpyDeviceToHost), "D2H weights");
         if (grouped) hip_check(hipMemcpy(tiles_used, moe_plan_at((int32_t*)plan.p, (int)S, E).ntiles, 4, hipMemcpyDeviceToHost), "D2H tiles");
+    });
+}
+
+// The same call over FP8 stacks (moe_fp8_kernels.h).  Every output lives on the device with a guard band behind it, filled before
+// the launches and read back after them: a kernel that writes past an output is an error here, not a corrupted neighbour.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_moe_ffn_fp8(int32_t device, const float* x, int64_t ldx, int32_t rows, const float* gamma, float eps,
+                                                        const float* router, const uint8_t* gate, const float* gate_scale, const uint8_t* up,
+                                                        const float* up_scale, const uint8_t* down, const float* down_scale, int32_t kind,
+                                                        int32_t hidden, int32_t E, int32_t k, int32_t Im, int32_t norm_topk, const float* r,
+                                                        int64_t ldr, int32_t r_is_y, float* y, int64_t ldy, int32_t grouped, int32_t* ids_out,
+                                                        float* weights_out, int32_t* tiles_used)
+{
+    if (!x || !router || !gate || !gate_scale || !up || !up_scale || !down || !down_scale || !y || !ids_out || !weights_out || !tiles_used)
+        return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > 4096) throw InvalidConfig("rows must be 1 .. 4096");
+        if (grouped != 0 && grouped != 1) throw InvalidConfig("grouped must be 0 (the steps kernels in blocks of 8 rows) or 1 (the grouped kernels)");
+        if (!r_is_y && !r) throw InvalidConfig("a residual is needed: r, or r_is_y");
+        const int64_t ldr_ = r_is_y ? ldy : ldr;
+        MoeFp8FfnArgs f;
+        MoeFfnArgs& a = f.base;
+        a.ldx = ldx; a.rows = rows; a.eps = eps; a.bf16 = 0; a.E = E; a.k = k; a.Im = Im; a.H = hidden; a.norm_topk = norm_topk ? 1 : 0;
+        a.ldr = ldr_; a.ldy = ldy;
+        f.gate.kind = f.up.kind = f.down.kind = kind;
+        MoeFp8FfnArgs chk = f;
+        chk.base.rows = 1;  // (blocks of 8 rows on the steps route, a contiguous copy for the norm on the grouped route)
+        chk.base.ldx = std::max<int64_t>(ldx, 0);
+        if (const char* why = moe_fp8_ffn_refusal(chk, false)) throw InvalidConfig(std::string("the launchers refuse these arguments: ") + why);
+        if (grouped) {  // the grouped launcher's own rule, on what it will be given: x packed to ldx == hidden below when gamma needs it
+            chk.base.gamma = gamma;
+            if (gamma) chk.base.ldx = hidden;
+            if (const char* why = moe_fp8_ffn_refusal(chk, true)) throw InvalidConfig(std::string("the launchers refuse these arguments: ") + why);
+        }
+        if (std::max(std::max(ldx, ldy), ldr_) > (1 << 18)) throw InvalidConfig("leading dimensions above 2^18");
+        const int64_t stack = (int64_t)E * Im * hidden;
+        if (stack > ((int64_t)1 << 27)) throw InvalidConfig("an expert stack above 2^27 elements");
+        for (const uint8_t* codes : {gate, up, down})  // (a NaN code would reach every output of its expert)
+            for (int64_t i = 0; i < stack; ++i)
+                if ((codes[i] & 0x7F) == 0x7F) throw InvalidConfig("a stack holds a NaN code (0x7F / 0xFF)");
+        use_device(device);
+        constexpr size_t kGuard = 256;  // bytes behind every output
+        const size_t S = (size_t)rows * (size_t)k;
+        const size_t xb = (size_t)rows * (size_t)ldx * 4, yb = (size_t)rows * (size_t)ldy * 4, rb = r_is_y ? 0 : (size_t)rows * (size_t)ldr * 4;
+        const size_t gsb = (size_t)E * (size_t)moe_fp8_scale_extent(kind, Im, hidden) * 4, dsb = (size_t)E * (size_t)moe_fp8_scale_extent(kind, hidden, Im) * 4;
+        const size_t mb = S * (size_t)Im * 4, ysb = grouped ? S * (size_t)hidden * 4 : 0;
+        DeviceBuf xd(xb), gd((size_t)hidden * 4), rtd((size_t)E * hidden * 4), gtd((size_t)stack), upd((size_t)stack), dnd((size_t)stack), gsd(gsb),
+            usd(gsb), dsd(dsb), rd(rb), yd(yb + kGuard), lg((size_t)rows * E * 4), idd(S * 4 + kGuard), wtd(S * 4 + kGuard), mid(mb + kGuard);
+        DeviceBuf xc(grouped && gamma ? (size_t)rows * hidden * 4 : 0), xn(grouped && gamma ? (size_t)rows * hidden * 4 : 0);
+        DeviceBuf ys(ysb + kGuard), plan(grouped ? moe_plan_ints((int)S, E) * 4 : 0);
+        hip_check(hipMemcpy(xd.p, x, xb, hipMemcpyHostToDevice), "H2D x");
+        if (gamma) hip_check(hipMemcpy(gd.p, gamma, (size_t)hidden * 4, hipMemcpyHostToDevice), "H2D gamma");
+        hip_check(hipMemcpy(rtd.p, router, (size_t)E * hidden * 4, hipMemcpyHostToDevice), "H2D router");
+        hip_check(hipMemcpy(gtd.p, gate, (size_t)stack, hipMemcpyHostToDevice), "H2D gate");
+        hip_check(hipMemcpy(upd.p, up, (size_t)stack, hipMemcpyHostToDevice), "H2D up");
+        hip_check(hipMemcpy(dnd.p, down, (size_t)stack, hipMemcpyHostToDevice), "H2D down");
+        hip_check(hipMemcpy(gsd.p, gate_scale, gsb, hipMemcpyHostToDevice), "H2D gate scale");
+        hip_check(hipMemcpy(usd.p, up_scale, gsb, hipMemcpyHostToDevice), "H2D up scale");
+        hip_check(hipMemcpy(dsd.p, down_scale, dsb, hipMemcpyHostToDevice), "H2D down scale");
+        if (rb) hip_check(hipMemcpy(rd.p, r, rb, hipMemcpyHostToDevice), "H2D r");
+        hip_check(hipMemcpy(yd.p, y, yb, hipMemcpyHostToDevice), "H2D y");
+        hip_check(hipMemset(mid.p, 0xFF, mb), "poison mid");  // (all-ones words are NaN: a slot the kernels skip would show)
+        hip_check(hipMemset(idd.p, 0xFF, S * 4), "poison ids");
+        hip_check(hipMemset(wtd.p, 0xFF, S * 4), "poison weights");
+        if (ysb) hip_check(hipMemset(ys.p, 0xFF, ysb), "poison y slots");
+        struct Band { void* p; size_t at; const char* what; };
+        const Band bands[5] = {{yd.p, yb, "y"}, {idd.p, S * 4, "ids"}, {wtd.p, S * 4, "weights"}, {mid.p, mb, "mid"}, {ys.p, ysb, "y slots"}};
+        for (const Band& b : bands) hip_check(hipMemset(static_cast<char*>(b.p) + b.at, 0xA5, kGuard), "guard band");
+        a.gamma = gamma ? (const float*)gd.p : nullptr;
+        a.router = rtd.p;
+        f.gate.codes = (const uint8_t*)gtd.p; f.gate.scale = (const float*)gsd.p;
+        f.up.codes = (const uint8_t*)upd.p; f.up.scale = (const float*)usd.p;
+        f.down.codes = (const uint8_t*)dnd.p; f.down.scale = (const float*)dsd.p;
+        const float* rp = r_is_y ? (const float*)yd.p : (const float*)rd.p;
+        if (grouped) {
+            a.X = (const float*)xd.p;
+            if (gamma && ldx != hidden) {  // the norm kernel reads contiguous rows
+                hip_check(hipMemcpy2D(xc.p, (size_t)hidden * 4, xd.p, (size_t)ldx * 4, (size_t)hidden * 4, (size_t)rows, hipMemcpyDeviceToDevice), "pack x");
+                a.X = (const float*)xc.p;
+                a.ldx = hidden;
+            }
+            a.xn = (float*)xn.p;
+            a.R = rp; a.Y = (float*)yd.p;
+            a.logits = (float*)lg.p; a.ids = (int32_t*)idd.p; a.weights = (float*)wtd.p; a.mid = (float*)mid.p; a.y = (float*)ys.p;
+            a.plan = (int32_t*)plan.p;
+            launcher_check(launch_moe_fp8_ffn_grouped(f, nullptr), "moe fp8 ffn (grouped)");
+        } else {
+            for (int r0 = 0; r0 < rows; r0 += 8) {
+                MoeFp8FfnArgs g = f;
+                MoeFfnArgs& b = g.base;
+                b.rows = std::min(8, rows - r0);
+                b.X = (const float*)xd.p + (size_t)r0 * ldx;
+                b.R = rp + (size_t)r0 * ldr_;
+                b.Y = (float*)yd.p + (size_t)r0 * ldy;
+                b.logits = (float*)lg.p + (size_t)r0 * E; b.ids = (int32_t*)idd.p + (size_t)r0 * k; b.weights = (float*)wtd.p + (size_t)r0 * k;
+                b.mid = (float*)mid.p + (size_t)r0 * k * Im;
+                launcher_check(launch_moe_fp8_ffn_steps(g, nullptr), "moe fp8 ffn (steps)");
+            }
+        }
+        hip_check(hipDeviceSynchronize(), "sync");
+        std::vector<uint8_t> band(kGuard);
+        for (const Band& b : bands) {
+            hip_check(hipMemcpy(band.data(), static_cast<char*>(b.p) + b.at, kGuard, hipMemcpyDeviceToHost), "D2H guard band");
+            if (std::count(band.begin(), band.end(), (uint8_t)0xA5) != (ptrdiff_t)kGuard)
+                throw std::runtime_error(std::string("moe fp8 ffn: a kernel wrote behind ") + b.what);
+        }
+        int32_t tiles = 0;
+        if (grouped) hip_check(hipMemcpy(&tiles, moe_plan_at((int32_t*)plan.p, (int)S, E).ntiles, 4, hipMemcpyDeviceToHost), "D2H tiles");
+        hip_check(hipMemcpy(y, yd.p, yb, hipMemcpyDeviceToHost), "D2H y");
+        hip_check(hipMemcpy(ids_out, idd.p, S * 4, hipMemcpyDeviceToHost), "D2H ids");
+        hip_check(hipMemcpy(weights_out, wtd.p, S * 4, hipMemcpyDeviceToHost), "D2H weights");
+        *tiles_used = tiles;
     });
 }
 

@@ -132,9 +132,13 @@ LlmConfig LlmConfig::from_json(const std::string& text)
         if (c.moe_inter < 32 || c.moe_inter % 32)
             throw std::runtime_error("config.json: moe_intermediate_size is " + std::to_string(c.moe_inter) + "; a positive multiple of 32 is needed");
         if (c.sparse_step < 1) throw std::runtime_error("config.json: decoder_sparse_step is " + std::to_string(c.sparse_step) + "; it must be at least 1");
-        if (j.find("quantization_config"))
-            throw std::runtime_error("config.json: a qwen3_moe checkpoint with a quantization_config: quantized mixture-of-experts checkpoints "
-                                     "(FP8, GGUF) are out of scope, bf16 and f32 are supported");
+        if (const Json* q = j.find("quantization_config")) {
+            const std::string method = q->is_object() ? q->get_string("quant_method", "") : "";
+            if (method != "fp8" && method != "compressed-tensors")
+                throw std::runtime_error("config.json: a qwen3_moe checkpoint with a quantization_config: quantized mixture-of-experts checkpoints "
+                                         "(FP8, GGUF) are out of scope, bf16 and f32 are supported");
+            c.moe_fp8 = true;  // (what the tensors hold is checked by check_moe_checkpoint)
+        }
     }
     // Qwen3 sets head_dim apart from hidden / heads (0.6B: 16 heads x 128 over a hidden size of 1024); the others may not
     if (c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.head_dim <= 0 || (!c.qwen3() && c.head_dim * c.heads != c.hidden))
@@ -189,6 +193,57 @@ void LlmModel::check_moe_checkpoint(const std::string& dir)
                                      "mixture-of-experts checkpoints (FP8, GGUF) are out of scope");
         if (t.shape != want) throw std::runtime_error("tensor " + name + " has shape " + shape_text(t.shape) + ", expected " + shape_text(want));
     };
+    // An FP8 directory (quantization_config.quant_method fp8 / compressed-tensors): every attention linear, every dense-layer MLP
+    // linear and every expert matrix is F8_E4M3 with exactly one scale beside it (Fp8Checkpoint::read decides), the scales of one
+    // stack are of one kind; the router, the norms, the table and the head stay float tensors.
+    const Fp8Checkpoint f8(st, text);
+    const char* kind_names[3] = {"per tensor", "per channel", "block"};
+    auto need_f8 = [&](const std::string& name, int64_t n, int64_t k) {
+        if (!st.contains(name)) throw std::runtime_error("missing tensor " + name);
+        const TensorView& t = st.get(name);
+        if (t.dtype != "F8_E4M3")
+            throw std::runtime_error("tensor " + name + " is " + t.dtype + " in an FP8 qwen3_moe checkpoint: every attention, MLP and expert matrix "
+                                     "must be F8_E4M3 with its scale");
+        if (t.shape != std::vector<int64_t>{n, k})
+            throw std::runtime_error("tensor " + name + " has shape " + shape_text(t.shape) + ", expected " + shape_text({n, k}));
+        if (H % kFp8Block || Im % kFp8Block)  // a block scale [ceil(n / 128), > 1 columns] beside widths the block kernels do not take
+            for (const char* suffix : {"_scale_inv", "_scale"})
+                if (st.contains(name + suffix) && st.get(name + suffix).shape.size() == 2 && st.get(name + suffix).shape[1] > 1)
+                    throw std::runtime_error("FP8 tensor " + name + " carries block scales " + shape_text(st.get(name + suffix).shape) +
+                                             " with hidden_size " + std::to_string(H) + " and moe_intermediate_size " + std::to_string(Im) +
+                                             "; block scales need both to be multiples of 128");
+        return f8.describe(name).kind;  // (the header alone: the upload reads the scales and scans the codes)
+    };
+    for (int i = 0; c.moe_fp8 && i < c.layers; ++i) {
+        const std::string a = "model.layers." + std::to_string(i) + ".self_attn.", p = "model.layers." + std::to_string(i) + ".mlp.";
+        const int64_t QD = c.q_dim(), kv = (int64_t)c.kv_heads * c.head_dim;
+        need_f8(a + "q_proj.weight", QD, H);
+        need_f8(a + "k_proj.weight", kv, H);
+        need_f8(a + "v_proj.weight", kv, H);
+        need_f8(a + "o_proj.weight", H, QD);
+        if (!c.sparse_layer(i)) {
+            need_f8(p + "gate_proj.weight", c.inter, H);
+            need_f8(p + "up_proj.weight", c.inter, H);
+            need_f8(p + "down_proj.weight", H, c.inter);
+            continue;
+        }
+        if (st.contains(p + "gate_proj.weight"))
+            throw std::runtime_error("sparse layer " + std::to_string(i) + " also carries the dense tensor " + p + "gate_proj.weight");
+        need(p + "gate.weight", {E, H});
+        int first_kind[3] = {-1, -1, -1};
+        for (int e = 0; e < E; ++e) {
+            const std::string q = p + "experts." + std::to_string(e) + ".";
+            const char* names[3] = {"gate_proj.weight", "up_proj.weight", "down_proj.weight"};
+            for (int t = 0; t < 3; ++t) {
+                const int kind = t == 2 ? need_f8(q + names[t], H, Im) : need_f8(q + names[t], Im, H);
+                if (first_kind[t] < 0) first_kind[t] = kind;
+                if (kind != first_kind[t])
+                    throw std::runtime_error("FP8 tensor " + q + names[t] + " has " + kind_names[kind] + " scales while expert 0's " + names[t] +
+                                             " has " + kind_names[first_kind[t]] + " scales: the experts of one stack must share a scale kind");
+            }
+        }
+    }
+    if (c.moe_fp8) return;
     for (int i = 0; i < c.layers; ++i) {
         const std::string p = "model.layers." + std::to_string(i) + ".mlp.";
         if (!c.sparse_layer(i)) {
@@ -313,6 +368,9 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
     }
     // FP8 checkpoints (fp8_weights.h): as stored, the seven matrices of every layer stay FP8 codes in HBM -- all of them or none
     const Fp8Checkpoint f8(st, is_gguf ? std::string() : m->config_json_);
+    if (c.moe_fp8 && weights != 0)
+        throw std::runtime_error("an FP8 qwen3_moe checkpoint runs on its codes: weights_dtype 0 (as stored) is the only one, there is no f32 or "
+                                 "bf16 copy of an expert matrix");
     if (!is_gguf && weights == 0) {
         std::string first_fp8, first_other, other_dtype;
         for (int i = 0; i < c.layers; ++i)
@@ -421,9 +479,43 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
         L.bqkv = any_bias ? m->upload_f32(b) : nullptr;
         if (m->fp8_) {
             L.fo = upload_f8(p + ".self_attn.o_proj.weight", H, QD);
-            L.fgate = upload_f8(p + ".mlp.gate_proj.weight", c.inter, H);
-            L.fup = upload_f8(p + ".mlp.up_proj.weight", c.inter, H);
-            L.fdown = upload_f8(p + ".mlp.down_proj.weight", H, c.inter);
+            if (c.sparse_layer(i)) {
+                // the router in f32; the three stacks as they are in the file: each expert's codes copied into its place in a
+                // preallocated stack, its scales into the stack's f32 scale array (check_moe_checkpoint: one kind per stack)
+                const int E = c.num_experts, Im = c.moe_inter;
+                L.moe = true;
+                get(p + ".mlp.gate.weight", {E, H});
+                L.router = m->upload_f32(buf);
+                const size_t per = (size_t)Im * H;
+                MoeFp8Stack* stacks[3] = {&L.fgate_stack, &L.fup_stack, &L.fdown_stack};
+                const char* names[3] = {"gate_proj.weight", "up_proj.weight", "down_proj.weight"};
+                for (int t = 0; t < 3; ++t) {
+                    void* codes = m->dalloc(((size_t)E * per + 3) / 4);
+                    std::vector<float> scales;
+                    int kind = -1;
+                    for (int e = 0; e < E; ++e) {
+                        const std::string name = p + ".mlp.experts." + std::to_string(e) + "." + names[t];
+                        const Fp8Tensor ft = f8.read(name);
+                        if (ft.n != (t == 2 ? H : Im) || ft.k != (t == 2 ? Im : H)) throw std::runtime_error("tensor " + name + " has an unexpected shape");
+                        if (kind < 0) kind = ft.kind;
+                        if (ft.kind != kind || (int64_t)ft.scale.size() != moe_fp8_scale_extent(kind, ft.n, ft.k))
+                            throw std::runtime_error("FP8 tensor " + name + ": the experts of one stack must share a scale kind");
+                        hip_check(hipMemcpy(static_cast<char*>(codes) + (size_t)e * per, ft.codes, per, hipMemcpyHostToDevice), "hipMemcpy(expert)");
+                        scales.insert(scales.end(), ft.scale.begin(), ft.scale.end());
+                    }
+                    stacks[t]->codes = static_cast<const uint8_t*>(codes);
+                    stacks[t]->scale = m->upload_f32(scales);
+                    stacks[t]->kind = kind;
+                }
+                m->weight_bytes_ += 3 * (size_t)E * per;
+                m->bytes_by_type_[kFp8WeightType] += 3 * (uint64_t)E * per;
+                L.moe_ids = reinterpret_cast<int32_t*>(m->dalloc((size_t)kMoeRecordRows * c.experts_per_tok));
+                L.moe_weights = m->dalloc((size_t)kMoeRecordRows * c.experts_per_tok);
+            } else {
+                L.fgate = upload_f8(p + ".mlp.gate_proj.weight", c.inter, H);
+                L.fup = upload_f8(p + ".mlp.up_proj.weight", c.inter, H);
+                L.fdown = upload_f8(p + ".mlp.down_proj.weight", H, c.inter);
+            }
         } else if (m->quant_) {
             L.o = upload_q(p + ".self_attn.o_proj.weight", H, H);
             L.gate_q = upload_q(p + ".mlp.gate_proj.weight", c.inter, H);
@@ -902,6 +994,10 @@ void LlmModel::fp8_finish(int n, const Layer& L)
     Fp8ProjArgs o;
     o.W[0] = L.fo; o.X = ctx_; o.ldx = QD; o.rows = n; o.R = h_; o.ldr = H; o.Y[0] = h_; o.ldy[0] = H;
     hip_check(launch_fp8_proj(o, s), "o proj");
+    if (L.moe) {
+        moe_steps(n, L);
+        return;
+    }
     Fp8ProjArgs g;
     g.mode = F8_SWIGLU;
     g.W[0] = L.fgate; g.W[1] = L.fup; g.X = h_; g.ldx = H; g.rows = n; g.gamma = L.ln2; g.eps = cfg_.eps; g.Y[0] = mid_; g.ldy[0] = I;
@@ -1033,6 +1129,17 @@ MoeFfnArgs moe_args(const LlmConfig& c, bool bf16)
     return a;
 }
 
+// The same call over an FP8 checkpoint's stacks: the router there is f32.
+MoeFp8FfnArgs moe_fp8_args(const MoeFfnArgs& a, const MoeFp8Stack& gate, const MoeFp8Stack& up, const MoeFp8Stack& down)
+{
+    MoeFp8FfnArgs f;
+    f.base = a;
+    f.base.bf16 = 0;
+    f.base.gate = f.base.up = f.base.down = nullptr;
+    f.gate = gate; f.up = up; f.down = down;
+    return f;
+}
+
 }  // namespace
 
 void LlmModel::moe_steps(int n, const Layer& L)
@@ -1043,7 +1150,8 @@ void LlmModel::moe_steps(int n, const Layer& L)
     a.router = L.router; a.gate = L.gate_stack; a.up = L.up_stack; a.down = L.down_stack;
     a.R = h_; a.ldr = H; a.Y = h_; a.ldy = H;
     a.logits = moe_logits_; a.ids = L.moe_ids; a.weights = L.moe_weights; a.mid = moe_mid_;
-    hip_check(launch_moe_ffn_steps(a, stream_), "moe ffn (steps)");
+    if (fp8_) hip_check(launch_moe_fp8_ffn_steps(moe_fp8_args(a, L.fgate_stack, L.fup_stack, L.fdown_stack), stream_), "moe fp8 ffn (steps)");
+    else hip_check(launch_moe_ffn_steps(a, stream_), "moe ffn (steps)");
     L.moe_rec_rows = n;
 }
 
@@ -1060,7 +1168,9 @@ void LlmModel::moe_rows(int m, const Layer& L)
         a.R = h; a.ldr = H; a.Y = h; a.ldy = H;
         a.logits = pmoe_logits_; a.ids = L.moe_ids + (size_t)r0 * k; a.weights = L.moe_weights + (size_t)r0 * k;
         a.mid = pmoe_mid_; a.y = pmoe_y_; a.plan = pmoe_plan_;
-        hip_check(launch_moe_ffn_grouped(a, stream_), "moe ffn (rows)");
+        // (the expert matrices of an FP8 checkpoint have one rows route, whatever set_fp8_matrix_cores says: the grouped GEMM on the codes)
+        if (fp8_) hip_check(launch_moe_fp8_ffn_grouped(moe_fp8_args(a, L.fgate_stack, L.fup_stack, L.fdown_stack), stream_), "moe fp8 ffn (rows)");
+        else hip_check(launch_moe_ffn_grouped(a, stream_), "moe ffn (rows)");
     }
     L.moe_rec_rows = m;
 }

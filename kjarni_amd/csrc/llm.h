@@ -22,6 +22,7 @@
 #include "fp8_kernels.h"
 #include "generation_run.h"
 #include "llm_kernels.h"
+#include "moe_fp8_kernels.h"
 #include "affine_kernels.h"
 #include "quant_kernels.h"
 #include "sampling.h"
@@ -49,6 +50,7 @@ struct LlmConfig {
     // (i + 1) % sparse_step == 0, else a dense Qwen3 layer of `inter`
     int num_experts = 0, experts_per_tok = 0, moe_inter = 0, sparse_step = 1;
     bool norm_topk = false;
+    bool moe_fp8 = false;  // a quantization_config whose quant_method is "fp8" or "compressed-tensors": the matrices are FP8 codes (fp8_weights.h)
     std::vector<int> mlp_only_layers;
     bool sparse_layer(int i) const;
     int q_dim() const { return heads * head_dim; }  // the width of Q and of the attention's context rows (== hidden except for Qwen3)
@@ -635,6 +637,8 @@ private:
         // dtype (gate / up / down are then null), and the record of the last pass: ids / weights [moe_rec_rows, k]
         bool moe = false;
         void *router = nullptr, *gate_stack = nullptr, *up_stack = nullptr, *down_stack = nullptr;
+        // an FP8 checkpoint's sparse layer: the three stacks as codes with f32 scales, one kind per stack (moe_fp8_kernels.h); the router f32
+        MoeFp8Stack fgate_stack, fup_stack, fdown_stack;
         int32_t* moe_ids = nullptr;
         float* moe_weights = nullptr;
         mutable int moe_rec_rows = 0;

@@ -758,6 +758,43 @@ def moe_ffn(x, router, gate, up, down, k: int, y, r=None, r_is_y: bool = False, 
     return ya, ids, w, used.value, tiles.value
 
 
+FP8_KINDS = {"tensor": 0, "channel": 1, "block": 2}
+
+
+def moe_ffn_fp8(x, router, gate, up, down, kind, k: int, y, r=None, r_is_y: bool = False, gamma=None, eps: float = 1e-6, norm_topk: bool = False,
+                grouped: bool = False, device: int = 0):
+    """The sparse FFN over FP8 stacks on host arrays (kjarni_hip_op_moe_ffn_fp8): gate / up / down are (codes uint8, scales f32)
+    pairs, codes [E, Im, hidden] x 2 and [E, hidden, Im], scales [E, extent of `kind`] ("tensor", "channel", "block" or 0 .. 2);
+    router [E, hidden] f32; x, y, r as moe_ffn.  grouped: the matrix-core kernels, else the steps kernels in blocks of 8 rows.
+    Returns (y, ids, weights, tiles_used) -- copies."""
+    kd = FP8_KINDS.get(kind, kind)
+    xa, ra_ = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(router, np.float32)
+    (ga, gs), (ua, us), (da, ds) = ((np.ascontiguousarray(c, np.uint8), np.ascontiguousarray(s, np.float32)) for c, s in (gate, up, down))
+    ya = np.array(y, np.float32, order="C")
+    if xa.ndim != 2 or ya.ndim != 2 or ya.shape[0] != xa.shape[0] or ra_.ndim != 2 or ga.ndim != 3 or ua.shape != ga.shape or da.ndim != 3:
+        raise ValueError("x: [rows, ldx]; y: [rows, ldy]; router: [E, hidden]; gate, up: [E, Im, hidden]; down: [E, hidden, Im]")
+    e, im, h = ga.shape
+    if ra_.shape != (e, h) or da.shape != (e, h, im):
+        raise ValueError("router: [E, hidden]; down: [E, hidden, Im]")
+    extent = lambda n, kk: {0: 1, 1: n, 2: -(-n // 128) * (kk // 128)}.get(kd, -1)  # noqa: E731
+    if gs.size != e * extent(im, h) or us.size != gs.size or ds.size != e * extent(h, im):
+        raise ValueError("scales: [E, 1], [E, n] or [E, ceil(n / 128) * (k / 128)] by kind")
+    rows = xa.shape[0]
+    gm = _proj_vector(gamma, h, "gamma")
+    rr = None if r is None else np.ascontiguousarray(r, np.float32)
+    if rr is not None and (rr.ndim != 2 or rr.shape[0] != rows):
+        raise ValueError("r: [rows, ldr]")
+    kk = max(int(k), 0)
+    ids, w = np.full((rows, kk), -1, np.int32), np.full((rows, kk), np.nan, np.float32)
+    tiles = C.c_int32(-1)
+    v = lambda t: t.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check_error(lib().kjarni_hip_op_moe_ffn_fp8(device, _f(xa), xa.shape[1], rows, _f(gm), float(eps), _f(ra_), v(ga), _f(gs), v(ua), _f(us), v(da),
+                                                _f(ds), int(kd), h, e, int(k), im, int(bool(norm_topk)), _f(rr), 0 if rr is None else rr.shape[1],
+                                                int(bool(r_is_y)), _f(ya), ya.shape[1], int(bool(grouped)), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                _f(w), C.byref(tiles)))
+    return ya, ids, w, tiles.value
+
+
 def prefill_attention(q, k, v, ldk: int, ldv: int, base: int, heads: int, head_dim: int, kv_group: int = 1, ctx=None, device: int = 0):
     """launch_prefill_attention on host arrays (kjarni_hip_op_prefill_attention): q [rows, ldq]; k and v flat float buffers, key row
     t at t * ldk; row s sees keys <= base + s.  Returns (ctx [rows, ldc] -- given, or NaN [rows, heads * head_dim] -- with the context

@@ -47,6 +47,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            to 4 layers: a 5 GB fixture) against a dense Qwen3 model of the same widths with intermediate_size 6144 (the same active
            FFN bytes and FLOPs) in one process, alternated twice: greedy ms / token and the 128-token prompt time of both, their
            ratios, and the sparse step's streamed bytes against the HBM peak.
+  llm_moe_fp8  (only on request) the same qwen3_moe widths (4 layers) as an FP8 checkpoint -- every linear F8_E4M3 with 128 x 128 block
+           scales, the router, norms and table bf16 -- against a bf16 twin holding the same values, in one process, alternated
+           twice: greedy ms / token, the 128-token prompt, and ms per lock-step step at 16 and 64 wide lanes (set_fp8_matrix_cores
+           on), with the FP8 / bf16 ratios.
   llm_logprobs  (only on request) generation log-probabilities (HipDecoder.generate_logprobs / generate_wide_logprobs) against the same
            loop with them off: greedy and sampled, top_k 0 and 8, on the Llama-1B and gpt2-small shapes; 64 wide lanes off and on;
            the kernel pair alone at V = 128 256 / 151 936 for 1 and 64 rows against the one-workgroup-per-row score kernel on the same
@@ -2024,6 +2028,92 @@ def main():
               "weight_bytes": {k: d.weight_bytes for k, d in decs.items()}, "fixture_and_load_s": round(setup_s, 1),
               "note": "4 layers: the per-token streams (a few hundred MB) fit the 256 MiB Infinity Cache only in part; the fractions "
                       "may overstate what HBM delivered"})
+        del decs
+
+    if "llm_moe_fp8" in which:
+        # Method: one process on one box.  Random codes of magnitude below 2 (no NaN code) with block scales that are powers of two,
+        # so that decode(code) * scale is a bf16 number and the bf16 twin holds the very same weights.  Both warmed first, then
+        # alternated twice, medians: greedy ms / token and the prompt as in llm_moe; wide lanes as the time of a 33-token
+        # generate_wide minus the same call cut after its first token, over 32 steps.
+        from tests import fp8_fixture as _Q
+        rng = np.random.default_rng(0)
+        H, NH, NKV, D, E_, K_, IM, LAYERS, VOC = 2048, 32, 4, 128, 128, 8, 768, 4, 32000
+        n_new = int(os.environ.get("KJARNI_MOE_TOKENS", "128"))
+        base = dict(model_type="qwen3_moe", hidden_size=H, num_hidden_layers=LAYERS, num_attention_heads=NH, num_key_value_heads=NKV, head_dim=D,
+                    intermediate_size=K_ * IM, vocab_size=VOC, max_position_embeddings=4096, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                    tie_word_embeddings=True, eos_token_id=[], num_experts=E_, num_experts_per_tok=K_, moe_intermediate_size=IM,
+                    norm_topk_prob=True, decoder_sparse_step=1, mlp_only_layers=[])
+        f8, bf = {}, {}
+
+        def plain(name, a):
+            f8[name] = bf[name] = _Q.entry(a, "BF16")
+
+        def matrix(name, n, k):
+            codes = (rng.integers(0, 0x40, (n, k), dtype=np.uint8) | (rng.integers(0, 2, (n, k), dtype=np.uint8) << 7)).astype(np.uint8)
+            scale = (2.0 ** rng.integers(-7, -4, _Q.scale_shape("block", n, k))).astype(np.float32)
+            f8.update(_Q.matrix_entries(name, codes, scale, "block"))
+            bf[name] = _Q.entry(_Q.dequantize(codes, scale, "block"), "BF16")
+
+        plain("model.embed_tokens.weight", rng.standard_normal((VOC, H), dtype=np.float32) * np.float32(0.05))
+        plain("model.norm.weight", np.ones(H, np.float32))
+        for i in range(LAYERS):
+            q = f"model.layers.{i}."
+            for nm, (n, k) in (("q_proj", (NH * D, H)), ("k_proj", (NKV * D, H)), ("v_proj", (NKV * D, H)), ("o_proj", (H, NH * D))):
+                matrix(q + f"self_attn.{nm}.weight", n, k)
+            for nm, n in (("self_attn.q_norm", D), ("self_attn.k_norm", D), ("input_layernorm", H), ("post_attention_layernorm", H)):
+                plain(q + nm + ".weight", np.ones(n, np.float32))
+            plain(q + "mlp.gate.weight", rng.standard_normal((E_, H), dtype=np.float32) * np.float32(0.05))
+            for e in range(E_):
+                for nm, (n, k) in (("gate_proj", (IM, H)), ("up_proj", (IM, H)), ("down_proj", (H, IM))):
+                    matrix(f"{q}mlp.experts.{e}.{nm}.weight", n, k)
+        t0 = time.perf_counter()
+        qc = {"quant_method": "fp8", "fmt": "e4m3", "activation_scheme": "dynamic", "weight_block_size": [128, 128]}
+        decs = {"fp8": kjarni_amd.HipDecoder(_Q.write_dir(os.path.join(tmp, "moe-fp8-4l"), dict(base, quantization_config=qc), f8), max_context=1024),
+                "bf16": kjarni_amd.HipDecoder(_Q.write_dir(os.path.join(tmp, "moe-bf16-4l"), base, bf), max_context=1024)}
+        del f8, bf
+        setup_s = time.perf_counter() - t0
+        decs["fp8"].set_fp8_matrix_cores(True)
+        prompt = rng.integers(1000, VOC, 128).tolist()
+        lane_prompts = [rng.integers(1000, VOC, 16).tolist() for _ in range(64)]
+        res = {name: {"step": [], "prompt": [], "wide16": [], "wide64": []} for name in decs}
+
+        def once(dec, out):
+            dec.reset()
+            t0 = time.perf_counter()
+            dec.generate(prompt, 1)
+            t1 = time.perf_counter()
+            dec.reset()
+            got = dec.generate(prompt, n_new)
+            t2 = time.perf_counter()
+            dec.reset()
+            t3 = time.perf_counter()
+            dec.forward(prompt, fetch=False)
+            t4 = time.perf_counter()
+            out["step"].append(((t2 - t1) - (t1 - t0)) * 1e3 / max(len(got) - 1, 1))
+            out["prompt"].append((t4 - t3) * 1e3)
+            for lanes in (16, 64):
+                t5 = time.perf_counter()
+                dec.generate_wide(lane_prompts[:lanes], 1, lanes=lanes)
+                t6 = time.perf_counter()
+                dec.generate_wide(lane_prompts[:lanes], 33, lanes=lanes)
+                t7 = time.perf_counter()
+                out[f"wide{lanes}"].append(((t7 - t6) - (t6 - t5)) * 1e3 / 32)
+
+        for name in decs:
+            once(decs[name], {"step": [], "prompt": [], "wide16": [], "wide64": []})     # warm: captures, workspaces
+        for _ in range(2):
+            for name in decs:
+                for _ in range(3):
+                    once(decs[name], res[name])
+        med = {name: {k: float(np.median(v)) for k, v in r.items()} for name, r in res.items()}
+        emit({"metric": "qwen3_moe at the Qwen3-30B-A3B widths (4 layers): FP8 codes with 128 x 128 block scales against a bf16 twin of the "
+                        "same values; greedy ms/token, 128-token prompt ms, ms per step at 16 / 64 wide lanes", "section": "llm_moe_fp8",
+              "config": {"hidden": H, "experts": E_, "experts_per_tok": K_, "moe_intermediate": IM, "layers": LAYERS, "vocab": VOC, "tokens": n_new,
+                         "prompt": 128, "fp8_matrix_cores": True},
+              "fp8_ms": {k: round(v, 4) for k, v in med["fp8"].items()}, "bf16_ms": {k: round(v, 4) for k, v in med["bf16"].items()},
+              "fp8_over_bf16": {k: round(med["fp8"][k] / med["bf16"][k], 3) for k in med["fp8"]},
+              "all_ms": {name: {k: [round(x, 4) for x in v] for k, v in r.items()} for name, r in res.items()},
+              "weight_bytes": {k: d.weight_bytes for k, d in decs.items()}, "fixture_and_load_s": round(setup_s, 1)})
         del decs
 
     if "llm_constraint" in which:
