@@ -940,6 +940,23 @@ int32_t kjarni_hip_decoder_ggml_matrix_cores(const KjarniHipDecoder* decoder);
  * kjarni_hip_decoder_affine_matrix_cores reads it back (0 for NULL). */
 void kjarni_hip_decoder_set_affine_matrix_cores(KjarniHipDecoder* decoder, int32_t on);
 int32_t kjarni_hip_decoder_affine_matrix_cores(const KjarniHipDecoder* decoder);
+/* The KV cache type of the lock-step lanes (generate_batch / generate_wide and the lanes_* / wide_* hooks; the single-sequence cache,
+ * embed and score_batch stay f32).  F32 is the default: with it every launch enqueued is what it was before the setting existed.
+ * BF16: a row is the round-to-nearest-even of the f32 value an f32 lane would hold.  F8_E4M3: OCP e4m3fn codes with one f32 scale
+ * per (cache row, KV head): scale = amax / 448 over the head's head_dim values, codes = RNE(x * 448 / amax) (a head row of zeros:
+ * scale 0, codes 0); K and V have their own scales.  A decode step encodes its row and attends over the codes; a prompt is computed
+ * in f32 and then encoded, so its own attention reads unrounded K / V.  Flipping the type synchronises, drops the captured lane
+ * graphs, ends the lane and wide sessions and frees their caches.  KJARNI_ERROR_INVALID_CONFIG for a type outside 0..2; with a
+ * compact type the next session (or generate call) refuses a head_dim that is not 16 / 32 / 64 / 128 and heads that are no multiple
+ * of kv_heads.  kjarni_hip_decoder_lane_kv_type reads it back (0 for NULL); kjarni_hip_decoder_lane_cache_bytes returns the bytes of
+ * K + V + scales of the current session of the lanes (wide == 0) or wide (wide != 0) bank, 0 without one:
+ * 2 * layers * lanes * rows * (kv * element bytes [+ 4 * kv_heads]). */
+#define KJARNI_HIP_LANE_KV_F32 0
+#define KJARNI_HIP_LANE_KV_BF16 1
+#define KJARNI_HIP_LANE_KV_F8_E4M3 2
+KjarniErrorCode kjarni_hip_decoder_set_lane_kv_type(KjarniHipDecoder* decoder, int32_t type);
+int32_t kjarni_hip_decoder_lane_kv_type(const KjarniHipDecoder* decoder);
+uint64_t kjarni_hip_decoder_lane_cache_bytes(const KjarniHipDecoder* decoder, int32_t wide);
 /* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
  * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
  * tokens as kept and the rest of the prompt as computed. */
@@ -1287,6 +1304,33 @@ KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, float* qkv, int6
                                                 int32_t head_dim, const float* gamma_q, const float* gamma_k, float eps, const float* cos_t,
                                                 const float* sin_t, int32_t table_rows, float* k_cache, float* v_cache, int64_t lane_stride,
                                                 int32_t capacity, const int32_t* pos, const int32_t* live, int32_t rotate);
+/* kjarni_hip_op_lane_kv_scatter: kjarni_hip_op_wide_rope_scatter into a compact lane cache (type KJARNI_HIP_LANE_KV_BF16 or
+ * _F8_E4M3): ONE call of launch_lane_rope_scatter_kv, or of launch_lane_qk_norm_rope_scatter_kv with gamma_q / gamma_k.  k_codes /
+ * v_codes [lanes, lane_rows, kv] hold 2-byte (bf16) or 1-byte (e4m3) elements; k_scale / v_scale [lanes, lane_rows, n_kv_heads] f32
+ * are needed for FP8 and ignored for bf16 (may be NULL).  Every plane and qkv are read and written back whole, each behind a guard
+ * band.  INVALID_CONFIG, before any GPU work and with every output untouched: a type other than 1 / 2, lanes outside 1..64, a
+ * head_dim that is no multiple of 16 or outside 16..128, n_kv_heads above n_heads, ld short of Q | K | V, lane_rows below capacity,
+ * FP8 without scale planes, a negative position, a live position inside the capacity but outside the tables, one gamma without the
+ * other, the Qwen3 form with rotate == 0. */
+KjarniErrorCode kjarni_hip_op_lane_kv_scatter(int32_t device, int32_t type, float* qkv, int64_t ld, int32_t lanes, int32_t n_heads,
+                                              int32_t n_kv_heads, int32_t head_dim, const float* gamma_q, const float* gamma_k, float eps,
+                                              const float* cos_t, const float* sin_t, int32_t table_rows, void* k_codes, void* v_codes,
+                                              float* k_scale, float* v_scale, int64_t lane_rows, int32_t capacity, const int32_t* pos,
+                                              const int32_t* live, int32_t rotate);
+/* kjarni_hip_op_lane_attention_kv: ONE call of launch_lane_attention_kv (the grouped-query partial kernel over compact planes laid
+ * out as above, then the merge): lane s attends to lane_live[s] ? min(lane_pos[s] + 1, capacity) : 0 keys of its own cache; q
+ * [lanes, ldq], ctx [lanes, ldc] (written back whole; a frozen or empty lane's heads are zeros); slabs (may be NULL) receives
+ * [lanes, heads, splits, head_dim + 4].  INVALID_CONFIG, before any GPU work and with every output untouched: the refusals of the
+ * planes above, a head_dim other than 16 / 32 / 64 / 128, heads no multiple of n_kv_heads, splits outside 1..256, more than 512
+ * keys per split at the capacity, ldq / ldc short of the heads, a negative position. */
+/* Does launch_lane_attention_kv take these arguments (1) or refuse them (0)?  Pure host: type 1 / 2, lanes 1..64, capacity >= 1,
+ * head_dim 16 / 32 / 64 / 128, heads a multiple of n_kv_heads, splits >= 1 and ceil(capacity / splits) <= 512. */
+int32_t kjarni_hip_lane_attention_kv_accepts(int32_t type, int32_t lanes, int32_t capacity, int32_t heads, int32_t n_kv_heads,
+                                             int32_t head_dim, int32_t splits);
+KjarniErrorCode kjarni_hip_op_lane_attention_kv(int32_t device, int32_t type, const float* q, int64_t ldq, int32_t lanes, const void* k_codes,
+                                                const void* v_codes, const float* k_scale, const float* v_scale, int64_t lane_rows,
+                                                int32_t capacity, int32_t heads, int32_t n_kv_heads, int32_t head_dim, int32_t splits,
+                                                const int32_t* lane_pos, const int32_t* lane_live, float* ctx, int64_t ldc, float* slabs);
 /* kjarni_hip_op_wide_pick: ONE call of launch_wide_pick over lanes [first_lane, first_lane + lanes) of logits
  * [first_lane + lanes, ld]: for every live lane the argmax (the last maximum wins, +0 == -0, NaN lowest) is appended to
  * history[lane * hist_stride + count], count (and pos when advance) + 1, live cleared on a stop id, at count == limit or at
@@ -1474,6 +1518,9 @@ KjarniErrorCode kjarni_hip_generator_set_ggml_matrix_cores(KjarniGenerator* gene
 /* kjarni_hip_decoder_set_affine_matrix_cores on the handle's model. */
 KjarniErrorCode kjarni_hip_chat_set_affine_matrix_cores(KjarniChat* chat, int32_t on);
 KjarniErrorCode kjarni_hip_generator_set_affine_matrix_cores(KjarniGenerator* generator, int32_t on);
+/* kjarni_hip_decoder_set_lane_kv_type on the handle's model. */
+KjarniErrorCode kjarni_hip_chat_set_lane_kv_type(KjarniChat* chat, int32_t type);
+KjarniErrorCode kjarni_hip_generator_set_lane_kv_type(KjarniGenerator* generator, int32_t type);
 void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
 
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */

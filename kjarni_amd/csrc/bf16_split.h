@@ -1,6 +1,6 @@
 // An f32 number as three bf16 pieces, exactly (gemm_split.hip's comment has the arithmetic): shared by the kernels that stage f32
-// operands for the bf16 matrix cores (gemm_split.hip, fp8_gemm.hip).  Translation units that use it are compiled with
-// -fno-slp-vectorize (the Makefile says why).
+// operands for the bf16 matrix cores (gemm_split.hip, fp8_gemm.hip).  Translation units that split operands beside MFMAs with it are
+// compiled with -fno-slp-vectorize (the Makefile says why); lane_kv_kernels.hip only packs bf16 codes with sp_pack and is not.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

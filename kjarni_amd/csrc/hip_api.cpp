@@ -18,6 +18,7 @@
 #include "decoder_embed_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
+#include "lane_kv_kernels.h"
 #include "llm_kernels.h"
 #include "whisper_kernels.h"
 #include "quant_kernels.h"
@@ -2660,6 +2661,142 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_wide_rope_scatter(int32_t device, fl
         hip_check(hipMemcpy(qkv, qd.buf.p, qb, hipMemcpyDeviceToHost), "D2H qkv");
         hip_check(hipMemcpy(k_cache, kd.buf.p, cb, hipMemcpyDeviceToHost), "D2H k_cache");
         hip_check(hipMemcpy(v_cache, vd.buf.p, cb, hipMemcpyDeviceToHost), "D2H v_cache");
+    });
+}
+
+// ---- compact lane KV caches (lane_kv_kernels.h): the encoding scatter and the grouped-query attention alone -----------------------
+
+namespace {
+
+// The checks the two hooks share; returns the bytes of a code plane.  Everything is refused before a device is asked for.
+size_t lane_kv_plane_bytes(int32_t type, int32_t lanes, int32_t n_heads, int32_t n_kv_heads, int32_t head_dim, int64_t lane_rows, int32_t capacity,
+                           const void* k_scale, const void* v_scale)
+{
+    if (type != LANE_KV_BF16 && type != LANE_KV_F8_E4M3) throw InvalidConfig("type must be 1 (bf16) or 2 (FP8 e4m3)");
+    if (lanes < 1 || lanes > kMaxWideLanes) throw InvalidConfig("lanes must be 1..64");
+    if (head_dim < 16 || head_dim > 128 || (head_dim & 15) || n_heads < 1 || n_heads > 256 || n_kv_heads < 1 || n_kv_heads > n_heads)
+        throw InvalidConfig("invalid head geometry (head_dim a multiple of 16, 16..128; n_heads 1..256; n_kv_heads 1..n_heads)");
+    if (capacity < 1 || capacity > (1 << 16) || lane_rows < capacity || lane_rows > (1 << 16) ||
+        (int64_t)lanes * lane_rows * n_kv_heads * head_dim > ((int64_t)1 << 26))
+        throw InvalidConfig("capacity 1..2^16 rows, lane_rows capacity..2^16, at most 2^26 cached elements");
+    if (type == LANE_KV_F8_E4M3 && (!k_scale || !v_scale)) throw InvalidConfig("k_scale and v_scale are needed for FP8");
+    return (size_t)lanes * (size_t)lane_rows * (size_t)n_kv_heads * (size_t)head_dim * (size_t)lane_kv_elem_bytes(type);
+}
+
+}  // namespace
+
+// lane_attention_kv_accepts itself: pure host, no device is asked for.
+KJARNI_EXPORT int32_t kjarni_hip_lane_attention_kv_accepts(int32_t type, int32_t lanes, int32_t capacity, int32_t heads, int32_t n_kv_heads,
+                                                           int32_t head_dim, int32_t splits)
+{
+    return lane_attention_kv_accepts(type, lanes, capacity, heads, n_kv_heads, head_dim, splits) ? 1 : 0;
+}
+
+// ONE call of launch_lane_rope_scatter_kv (gamma_q / gamma_k NULL) or launch_lane_qk_norm_rope_scatter_kv (both given) over the
+// 64-lane state layout on host arrays: qkv [lanes, ld], the code planes [lanes, lane_rows, kv] (2- or 1-byte elements) and, for FP8,
+// the scale planes [lanes, lane_rows, n_kv_heads] are read, run and written back whole, each behind a guard band.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lane_kv_scatter(int32_t device, int32_t type, float* qkv, int64_t ld, int32_t lanes, int32_t n_heads,
+                                                            int32_t n_kv_heads, int32_t head_dim, const float* gamma_q, const float* gamma_k,
+                                                            float eps, const float* cos_t, const float* sin_t, int32_t table_rows, void* k_codes,
+                                                            void* v_codes, float* k_scale, float* v_scale, int64_t lane_rows, int32_t capacity,
+                                                            const int32_t* pos, const int32_t* live, int32_t rotate)
+{
+    if (!qkv || !cos_t || !sin_t || !k_codes || !v_codes || !pos || !live) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const size_t cb = lane_kv_plane_bytes(type, lanes, n_heads, n_kv_heads, head_dim, lane_rows, capacity, k_scale, v_scale);
+        if (!gamma_q != !gamma_k) throw InvalidConfig("gamma_q and gamma_k go together (both: the Qwen3 form, neither: the plain form)");
+        if (gamma_q && !rotate) throw InvalidConfig("the Qwen3 form always rotates: rotate must be 1 with gamma_q / gamma_k");
+        const int64_t kv = (int64_t)n_kv_heads * head_dim, width = (int64_t)n_heads * head_dim + 2 * kv;
+        if (ld < width || ld > ((int64_t)1 << 20)) throw InvalidConfig("ld does not cover Q | K | V (or exceeds 2^20)");
+        if (table_rows < 1 || table_rows > (1 << 20)) throw InvalidConfig("table_rows must be 1..2^20");
+        for (int32_t l = 0; l < lanes; ++l) {
+            if (pos[l] < 0) throw InvalidConfig("pos[" + std::to_string(l) + "] is negative");
+            if (live[l] && pos[l] < capacity && pos[l] >= table_rows)
+                throw InvalidConfig("pos[" + std::to_string(l) + "] = " + std::to_string(pos[l]) + " is outside the RoPE tables");
+        }
+        use_device(device);
+        const bool f8 = type == LANE_KV_F8_E4M3;
+        const size_t qb = (size_t)lanes * (size_t)ld * 4, tb = (size_t)table_rows * (head_dim / 2) * 4;
+        const size_t sb = f8 ? (size_t)lanes * (size_t)lane_rows * (size_t)n_kv_heads * 4 : 0;
+        LlmWideState st = {};
+        for (int32_t l = 0; l < lanes; ++l) {
+            st.pos[l] = pos[l];
+            st.live[l] = live[l] ? 1 : 0;
+        }
+        const auto sd = upload(&st, sizeof(st), "H2D state");
+        const auto cd = upload(cos_t, tb, "H2D cos"), snd = upload(sin_t, tb, "H2D sin");
+        const auto gq = upload(gamma_q, gamma_q ? (size_t)head_dim * 4 : 0, "H2D gamma_q"), gk = upload(gamma_k, gamma_k ? (size_t)head_dim * 4 : 0, "H2D gamma_k");
+        GuardedBuf qd(qb), kd(cb), vd(cb), ksd(sb), vsd(sb);
+        hip_check(hipMemcpy(qd.buf.p, qkv, qb, hipMemcpyHostToDevice), "H2D qkv");
+        hip_check(hipMemcpy(kd.buf.p, k_codes, cb, hipMemcpyHostToDevice), "H2D k_codes");
+        hip_check(hipMemcpy(vd.buf.p, v_codes, cb, hipMemcpyHostToDevice), "H2D v_codes");
+        if (f8) {
+            hip_check(hipMemcpy(ksd.buf.p, k_scale, sb, hipMemcpyHostToDevice), "H2D k_scale");
+            hip_check(hipMemcpy(vsd.buf.p, v_scale, sb, hipMemcpyHostToDevice), "H2D v_scale");
+        }
+        const LaneStateRef ds(static_cast<LlmWideState*>(sd->p));
+        if (gamma_q)
+            launcher_check(launch_lane_qk_norm_rope_scatter_kv(type, qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim,
+                                                               static_cast<const float*>(gq->p), static_cast<const float*>(gk->p), eps,
+                                                               static_cast<const float*>(cd->p), static_cast<const float*>(snd->p), kd.buf.p, vd.buf.p,
+                                                               f8 ? ksd.as<float>() : nullptr, f8 ? vsd.as<float>() : nullptr, lane_rows, capacity, ds,
+                                                               nullptr), "compact head norm + rotate + scatter");
+        else
+            launcher_check(launch_lane_rope_scatter_kv(type, qd.as<float>(), ld, lanes, n_heads, n_kv_heads, head_dim, static_cast<const float*>(cd->p),
+                                                       static_cast<const float*>(snd->p), kd.buf.p, vd.buf.p, f8 ? ksd.as<float>() : nullptr,
+                                                       f8 ? vsd.as<float>() : nullptr, lane_rows, capacity, ds, rotate ? 1 : 0, nullptr),
+                           "compact rotate + scatter");
+        hip_check(hipDeviceSynchronize(), "sync");
+        qd.check("qkv"); kd.check("k_codes"); vd.check("v_codes"); ksd.check("k_scale"); vsd.check("v_scale");
+        hip_check(hipMemcpy(qkv, qd.buf.p, qb, hipMemcpyDeviceToHost), "D2H qkv");
+        hip_check(hipMemcpy(k_codes, kd.buf.p, cb, hipMemcpyDeviceToHost), "D2H k_codes");
+        hip_check(hipMemcpy(v_codes, vd.buf.p, cb, hipMemcpyDeviceToHost), "D2H v_codes");
+        if (f8) {
+            hip_check(hipMemcpy(k_scale, ksd.buf.p, sb, hipMemcpyDeviceToHost), "D2H k_scale");
+            hip_check(hipMemcpy(v_scale, vsd.buf.p, sb, hipMemcpyDeviceToHost), "D2H v_scale");
+        }
+    });
+}
+
+// ONE call of launch_lane_attention_kv (partial kernel + merge) on host planes laid out as above: q [lanes, ldq], ctx [lanes, ldc]
+// (read, run, written back whole); slabs (may be NULL) receives [lanes, heads, splits, head_dim + 4].
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lane_attention_kv(int32_t device, int32_t type, const float* q, int64_t ldq, int32_t lanes,
+                                                              const void* k_codes, const void* v_codes, const float* k_scale,
+                                                              const float* v_scale, int64_t lane_rows, int32_t capacity, int32_t heads,
+                                                              int32_t n_kv_heads, int32_t head_dim, int32_t splits, const int32_t* lane_pos,
+                                                              const int32_t* lane_live, float* ctx, int64_t ldc, float* slabs)
+{
+    if (!q || !k_codes || !v_codes || !lane_pos || !lane_live || !ctx) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        const size_t cb = lane_kv_plane_bytes(type, lanes, heads, n_kv_heads, head_dim, lane_rows, capacity, k_scale, v_scale);
+        if (splits < 1 || splits > 256) throw InvalidConfig("splits must be 1..256");
+        if (!lane_attention_kv_accepts(type, lanes, capacity, heads, n_kv_heads, head_dim, splits))
+            throw InvalidConfig("launch_lane_attention_kv refuses these arguments (head_dim 16, 32, 64 or 128; heads a multiple of n_kv_heads; at "
+                                "most 512 keys per split)");
+        const int64_t qd = (int64_t)heads * head_dim;
+        if (ldq < qd || ldc < qd || (ldq & 3) || std::max(ldq, ldc) > (1 << 20))
+            throw InvalidConfig("ldq / ldc must cover the heads and be at most 2^20, ldq a multiple of 4");
+        for (int32_t l = 0; l < lanes; ++l)
+            if (lane_pos[l] < 0) throw InvalidConfig("lane_pos[" + std::to_string(l) + "] is negative");
+        use_device(device);
+        const bool f8 = type == LANE_KV_F8_E4M3;
+        const size_t qb = (size_t)lanes * (size_t)ldq * 4, ob = (size_t)lanes * (size_t)ldc * 4;
+        const size_t sb = f8 ? (size_t)lanes * (size_t)lane_rows * (size_t)n_kv_heads * 4 : 0;
+        const size_t pb = decode_attention_scratch_floats(lanes, heads, head_dim, splits) * 4;
+        const auto qdv = upload(q, qb, "H2D q"), kd = upload(k_codes, cb, "H2D k_codes"), vd = upload(v_codes, cb, "H2D v_codes");
+        const auto ksd = upload(k_scale, sb, "H2D k_scale"), vsd = upload(v_scale, sb, "H2D v_scale");
+        const auto pd = upload(lane_pos, (size_t)lanes * 4, "H2D lane_pos"), ld = upload(lane_live, (size_t)lanes * 4, "H2D lane_live");
+        GuardedBuf od(ob), sd(pb);
+        hip_check(hipMemcpy(od.buf.p, ctx, ob, hipMemcpyHostToDevice), "H2D ctx");
+        hip_check(hipMemset(sd.buf.p, 0xFF, pb), "poison scratch");  // (all-ones words are NaN: a slab the kernel skips would show)
+        launcher_check(launch_lane_attention_kv(type, static_cast<const float*>(qdv->p), ldq, lanes, kd->p, vd->p,
+                                                f8 ? static_cast<const float*>(ksd->p) : nullptr, f8 ? static_cast<const float*>(vsd->p) : nullptr,
+                                                lane_rows, capacity, heads, n_kv_heads, head_dim, splits, sd.as<float>(), od.as<float>(), ldc,
+                                                static_cast<const int*>(pd->p), static_cast<const int*>(ld->p), nullptr), "compact lane attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.check("ctx"); sd.check("slabs");
+        hip_check(hipMemcpy(ctx, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H ctx");
+        if (slabs) hip_check(hipMemcpy(slabs, sd.buf.p, pb, hipMemcpyDeviceToHost), "D2H slabs");
     });
 }
 

@@ -21,6 +21,7 @@
 #include "constraint_kernels.h"
 #include "grammar_kernels.h"
 #include "lane_constraint_kernels.h"
+#include "lane_kv_kernels.h"
 #include "logprob_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
@@ -2361,6 +2362,14 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
     if (lanes < b.min_lanes || lanes > b.max_lanes) throw InvalidConfig(b.range_error);
     const LlmConfig& c = cfg_;
     const int cap = lane_context <= 0 ? cache_cap_ : std::min(cache_cap_, lane_context);
+    const int kvt = lane_kv_type_, kvh = gpt2_ ? c.heads : c.kv_heads;
+    if (kvt != LANE_KV_F32) {  // what the compact planes and their attention ask of the geometry
+        if (c.head_dim % 16) throw InvalidConfig("lane_kv_type: a compact lane cache needs a head_dim that is a multiple of 16 (it is " + std::to_string(c.head_dim) + ")");
+        if (c.head_dim > 128) throw InvalidConfig("lane_kv_type: a compact lane cache takes a head_dim of at most 128 (it is " + std::to_string(c.head_dim) + ")");
+        if (kvh < 1 || c.heads % kvh) throw InvalidConfig("lane_kv_type: a compact lane cache needs heads / kv_heads to be a whole number");
+        if (!lane_attention_kv_accepts(kvt, lanes, cap, c.heads, kvh, c.head_dim, splits_))
+            throw InvalidConfig("lane_kv_type: the compact lanes' attention takes head_dim 16, 32, 64 or 128 and at most 512 keys per split");
+    }
     if (b.wide) {  // what the wide step alone asks of the checkpoint
         if (quant_ && !fp8_mc_ && !ggml_mc_ && !affine_mc_)  // (fp8_ implies quant_; fp8_mc_ implies fp8_, ggml_mc_ / affine_mc_ a GGUF
                                                              // checkpoint: with its switch on, the checkpoint's prompt GEMM reads the codes)
@@ -2380,6 +2389,7 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
         b.best = reinterpret_cast<unsigned long long*>(dalloc(2 * (size_t)b.width));
         hip_check(hipMemset(b.best, 0, sizeof(unsigned long long) * b.width), "memset");
         b.copy_table = reinterpret_cast<LlmKvCopyPair*>(dalloc((layers_.size() * sizeof(LlmKvCopyPair) + 3) / 4));
+        b.pack_table = reinterpret_cast<LaneKvPackEntry*>(dalloc((layers_.size() * sizeof(LaneKvPackEntry) + 3) / 4));
     }
     if (lanes > b.alloc || cap > b.alloc_cap) {
         hip_check(hipStreamSynchronize(stream_), "sync");
@@ -2389,9 +2399,12 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
         // head() are pass()'s), the wide bank's in the prompt workspace with an attention scratch of its own, carved here.
         const size_t nl = (size_t)std::max(lanes, b.alloc), nc = (size_t)std::max(cap, b.alloc_cap), stride = nc + 16;
         auto pad = [](size_t floats) { return (floats + 63) & ~(size_t)63; };
-        const size_t per_cache = pad(nl * nc * kv), qkv = pad(nl * ((size_t)c.q_dim() + 2 * kv)), logits = pad(nl * vocab);
+        // (a cache plane in floats, whatever its element: f32 as it always was; bf16 / FP8 codes in half / a quarter of the bytes, FP8
+        //  with a scale plane; compact types add one f32 staging lane per layer and per K / V)
+        const size_t per_cache = pad((nl * nc * kv * (size_t)lane_kv_elem_bytes(kvt) + 3) / 4), qkv = pad(nl * ((size_t)c.q_dim() + 2 * kv)), logits = pad(nl * vocab);
+        const size_t per_scale = kvt == LANE_KV_F8_E4M3 ? pad(nl * nc * (size_t)kvh) : 0, per_stage = kvt != LANE_KV_F32 ? pad(nc * kv) : 0;
         const size_t att = b.wide ? pad(decode_attention_scratch_floats((int)nl, c.heads, c.head_dim, splits_)) : 0, hist = pad(nl * stride);
-        const size_t floats = 2 * layers_.size() * per_cache + qkv + 2 * logits + att + 3 * hist + pad(nl);
+        const size_t floats = 2 * layers_.size() * (per_cache + per_scale + per_stage) + qkv + 2 * logits + att + 3 * hist + pad(nl);
         void* fresh = arena_.alloc_own(floats * sizeof(float));
         if (b.block) arena_.free_own(b.block);
         b.block = fresh;
@@ -2403,9 +2416,21 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
         };
         b.k.assign(layers_.size(), nullptr);
         b.v.assign(layers_.size(), nullptr);
+        b.k_scale.assign(layers_.size(), nullptr);
+        b.v_scale.assign(layers_.size(), nullptr);
+        b.stage_k.assign(layers_.size(), nullptr);
+        b.stage_v.assign(layers_.size(), nullptr);
         for (size_t i = 0; i < layers_.size(); ++i) {
-            b.k[i] = take(per_cache);
-            b.v[i] = take(per_cache);
+            b.k[i] = reinterpret_cast<uint8_t*>(take(per_cache));
+            b.v[i] = reinterpret_cast<uint8_t*>(take(per_cache));
+            if (per_scale) {
+                b.k_scale[i] = take(per_scale);
+                b.v_scale[i] = take(per_scale);
+            }
+            if (per_stage) {
+                b.stage_k[i] = take(per_stage);
+                b.stage_v[i] = take(per_stage);
+            }
         }
         b.qkv = take(qkv);
         b.logits = take(logits);
@@ -2420,8 +2445,17 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
         b.alloc_cap = (int)nc;
         // the shared-prefix copy reads its pointers from the device: (main K, lane-0 K, main V, lane-0 V) per layer
         std::vector<LlmKvCopyPair> pairs(layers_.size());
-        for (size_t i = 0; i < layers_.size(); ++i) pairs[i] = {layers_[i].k_cache, b.k[i], layers_[i].v_cache, b.v[i]};
+        // (compact types: into the staging lane, which launch_lane_kv_pack then encodes into the lane by its own table)
+        for (size_t i = 0; i < layers_.size(); ++i) {
+            if (kvt == LANE_KV_F32) pairs[i] = {layers_[i].k_cache, reinterpret_cast<float*>(b.k[i]), layers_[i].v_cache, reinterpret_cast<float*>(b.v[i])};
+            else pairs[i] = {layers_[i].k_cache, b.stage_k[i], layers_[i].v_cache, b.stage_v[i]};
+        }
         hip_check(hipMemcpy(b.copy_table, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
+        if (kvt != LANE_KV_F32) {
+            std::vector<LaneKvPackEntry> pack(layers_.size());
+            for (size_t i = 0; i < layers_.size(); ++i) pack[i] = {b.stage_k[i], b.stage_v[i], b.k[i], b.v[i], b.k_scale[i], b.v_scale[i]};
+            hip_check(hipMemcpy(b.pack_table, pack.data(), pack.size() * sizeof(LaneKvPackEntry), hipMemcpyHostToDevice), "H2D pack table");
+        }
     }
     if (cap != b.cap) drop_lane_graphs(b);  // (the capacity is an argument of the captured launches)
     b.lanes = lanes;
@@ -2458,7 +2492,9 @@ void LlmModel::lane_copy_prefix(LaneBank& b, int lane, int s)
     if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
     if (s < 0 || s > cache_len_ || s > b.cap) throw std::runtime_error("shared prefix out of range");
     const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
-    hip_check(launch_kv_prefix_copy(b.copy_table, (int)layers_.size(), (int64_t)lane * b.alloc_cap * kv, (int64_t)s * kv, stream_), "prefix copy");
+    // (a compact bank's table points at the one staging lane: lane_prefill_at() packs rows [0, s + n) from there into the lane)
+    const int64_t dst = lane_kv_type_ == LANE_KV_F32 ? (int64_t)lane * b.alloc_cap * kv : 0;
+    hip_check(launch_kv_prefix_copy(b.copy_table, (int)layers_.size(), dst, (int64_t)s * kv, stream_), "prefix copy");
 }
 
 void LlmModel::lane_prefill_shared(Bank bank, int lane, int s, const uint32_t* ids, int n) { lane_prefill_shared(bank_of(bank), lane, s, ids, n); }
@@ -2484,10 +2520,14 @@ void LlmModel::lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* 
     std::vector<std::pair<float*, float*>> saved(layers_.size());
     const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
     const size_t saved_resident = resident_.size();
+    // Compact types: the prompt is computed in the bank's f32 staging lane (rows [0, base) are there: lane_copy_prefix() put them, the
+    // only way a caller gets base > 0) and rows [0, base + n) are then encoded into the lane -- the prompt's own attention reads
+    // unrounded K / V, the decode steps the stored codes.
+    const bool compact = lane_kv_type_ != LANE_KV_F32;
     for (size_t i = 0; i < layers_.size(); ++i) {
         saved[i] = {layers_[i].k_cache, layers_[i].v_cache};
-        layers_[i].k_cache = b.k[i] + off;
-        layers_[i].v_cache = b.v[i] + off;
+        layers_[i].k_cache = compact ? b.stage_k[i] : reinterpret_cast<float*>(b.k[i]) + off;
+        layers_[i].v_cache = compact ? b.stage_v[i] : reinterpret_cast<float*>(b.v[i]) + off;
     }
     cache_len_ = base;
     cache_cap_ = b.cap;
@@ -2503,6 +2543,9 @@ void LlmModel::lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* 
     };
     try {
         forward(ids, n);
+        if (compact)
+            hip_check(launch_lane_kv_pack(lane_kv_type_, b.pack_table, (int)layers_.size(), lane, b.alloc_cap, base + n,
+                                          gpt2_ ? cfg_.heads : cfg_.kv_heads, cfg_.head_dim, stream_), "lane kv pack");
         hip_check(hipMemcpyAsync(b.logits + (size_t)lane * cfg_.vocab, logits_, (size_t)cfg_.vocab * sizeof(float), hipMemcpyDeviceToDevice, stream_),
                   "D2D logits");
         // (forward left the lane's length in pos_: the single-sequence cache's own length goes back)
@@ -2526,13 +2569,26 @@ void LlmModel::lane_attention(const LaneBank& b, int n, size_t li, float* scratc
     const Layer& L = layers_[li];
     const int d = c.head_dim, QD = c.q_dim(), kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
     const int64_t stride = (int64_t)b.alloc_cap * kv;
+    if (const int t = lane_kv_type_; t != LANE_KV_F32) {  // compact planes: the encoding scatter, the grouped-query attention over the codes
+        if (c.qwen3())
+            hip_check(launch_lane_qk_norm_rope_scatter_kv(t, b.qkv, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, b.k[li], b.v[li],
+                                                          b.k_scale[li], b.v_scale[li], b.alloc_cap, b.cap, b.dev, stream_),
+                      "head norm + rotate + scatter (compact)");
+        else
+            hip_check(launch_lane_rope_scatter_kv(t, b.qkv, ldq, n, c.heads, kvh, d, cos_, sin_, b.k[li], b.v[li], b.k_scale[li], b.v_scale[li],
+                                                  b.alloc_cap, b.cap, b.dev, gpt2_ ? 0 : 1, stream_), "rotate + scatter (compact)");
+        hip_check(launch_lane_attention_kv(t, b.qkv, ldq, n, b.k[li], b.v[li], b.k_scale[li], b.v_scale[li], b.alloc_cap, b.cap, c.heads, kvh, d,
+                                           splits_, scratch, ctx, QD, b.dev.pos, b.dev.live, stream_), "attention (compact)");
+        return;
+    }
+    float *kc = reinterpret_cast<float*>(b.k[li]), *vc = reinterpret_cast<float*>(b.v[li]);
     if (c.qwen3())
-        hip_check(launch_lane_qk_norm_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, b.k[li], b.v[li], stride,
+        hip_check(launch_lane_qk_norm_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, kc, vc, stride,
                                                    b.cap, b.dev, stream_), "head norm + rotate + scatter");
     else
-        hip_check(launch_lane_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, cos_, sin_, b.k[li], b.v[li], stride, b.cap, b.dev, gpt2_ ? 0 : 1,
+        hip_check(launch_lane_rope_scatter(b.qkv, ldq, n, c.heads, kvh, d, cos_, sin_, kc, vc, stride, b.cap, b.dev, gpt2_ ? 0 : 1,
                                            stream_), "rotate + scatter");
-    hip_check(launch_decode_attention(b.qkv, ldq, n, b.k[li], kv, b.v[li], kv, b.cap, nullptr, b.cap, c.heads, d, -1, splits_, scratch, ctx, QD,
+    hip_check(launch_decode_attention(b.qkv, ldq, n, kc, kv, vc, kv, b.cap, nullptr, b.cap, c.heads, d, -1, splits_, scratch, ctx, QD,
                                       stream_, c.heads / kvh, stride, stride, 1, b.dev.pos, b.dev.live), "attention");
 }
 
@@ -2629,9 +2685,61 @@ void LlmModel::lane_kv_rows(Bank bank, int lane, int layer, int first, int rows,
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(stream_), "sync");
     const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim);
-    const size_t off = ((size_t)lane * b.alloc_cap + (size_t)first) * kv, bytes = (size_t)rows * kv * sizeof(float);
-    hip_check(hipMemcpy(k_out, b.k[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
-    hip_check(hipMemcpy(v_out, b.v[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+    const size_t row0 = (size_t)lane * b.alloc_cap + (size_t)first, es = (size_t)lane_kv_elem_bytes(lane_kv_type_);
+    const size_t off = row0 * kv * es, bytes = (size_t)rows * kv * es;
+    if (lane_kv_type_ == LANE_KV_F32) {
+        hip_check(hipMemcpy(k_out, b.k[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+        hip_check(hipMemcpy(v_out, b.v[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+        return;
+    }
+    // compact: the codes (and scales) to the host, widened there -- bf16 by a shift, FP8 by value times the head's scale in f32
+    const size_t kvh = (size_t)(gpt2_ ? cfg_.heads : cfg_.kv_heads), d = (size_t)cfg_.head_dim;
+    std::vector<uint8_t> codes(bytes);
+    std::vector<float> scales(lane_kv_type_ == LANE_KV_F8_E4M3 ? (size_t)rows * kvh : 0);
+    for (int which = 0; which < 2; ++which) {
+        float* out = which ? v_out : k_out;
+        hip_check(hipMemcpy(codes.data(), (which ? b.v : b.k)[(size_t)layer] + off, bytes, hipMemcpyDeviceToHost), "D2H cache codes");
+        if (lane_kv_type_ == LANE_KV_BF16) {
+            for (size_t i = 0; i < (size_t)rows * kv; ++i) {
+                const uint32_t u = (uint32_t)(codes[2 * i] | (codes[2 * i + 1] << 8)) << 16;
+                std::memcpy(out + i, &u, 4);
+            }
+            continue;
+        }
+        hip_check(hipMemcpy(scales.data(), (which ? b.v_scale : b.k_scale)[(size_t)layer] + row0 * kvh, scales.size() * sizeof(float),
+                            hipMemcpyDeviceToHost), "D2H cache scales");
+        for (size_t i = 0; i < (size_t)rows * kv; ++i) out[i] = fp8_e4m3_to_f32(codes[i]) * scales[(i / kv) * kvh + (i % kv) / d];
+    }
+}
+
+size_t LlmModel::lane_cache_bytes(Bank bank) const
+{
+    const LaneBank& b = bank_of(bank);
+    const size_t kvh = (size_t)(gpt2_ ? cfg_.heads : cfg_.kv_heads), kv = kvh * (size_t)cfg_.head_dim;
+    const size_t row = kv * (size_t)lane_kv_elem_bytes(lane_kv_type_) + (lane_kv_type_ == LANE_KV_F8_E4M3 ? kvh * sizeof(float) : 0);
+    return 2 * layers_.size() * (size_t)b.lanes * (size_t)b.cap * row;
+}
+
+void LlmModel::set_lane_kv_type(int type)
+{
+    if (type < LANE_KV_F32 || type > LANE_KV_F8_E4M3)
+        throw InvalidConfig("lane_kv_type must be 0 (f32), 1 (bf16) or 2 (FP8 e4m3); it is " + std::to_string(type));
+    if (type == lane_kv_type_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    for (LaneBank* b : {&lane_bank_, &wide_bank_}) {  // (the captured chains hold the type's launches and the block's addresses)
+        drop_lane_graphs(*b);
+        b->lanes = 0;  // the session ends here: lanes_begin() carves the planes of the new type
+        b->cap = 0;
+        if (b->block) arena_.free_own(b->block);
+        b->block = nullptr;
+        b->alloc = b->alloc_cap = 0;
+        for (auto* v : {&b->k_scale, &b->v_scale, &b->stage_k, &b->stage_v}) v->clear();  // (nothing points into the freed block)
+        b->k.clear();
+        b->v.clear();
+        b->qkv = b->logits = b->att = nullptr;
+    }
+    lane_kv_type_ = type;
 }
 
 hipGraphExec_t LlmModel::lane_step_graph(LaneBank& b, int n)

@@ -71,6 +71,7 @@ struct LaneAutomatonTable;  // lane_constraint_kernels.h
 struct LlmLookupState;
 struct SampleHeader;
 struct LlmKvCopyPair;
+struct LaneKvPackEntry;
 struct EmbedBlock;   // decoder_embed_kernels.h
 struct PrefixBlock;  // score_batch_kernels.h
 
@@ -177,6 +178,17 @@ public:
     // wide session.
     void set_affine_matrix_cores(bool on);
     bool affine_matrix_cores() const { return affine_mc_; }
+    // ---- the lanes' KV cache type (lane_kv_kernels.h; 0 = f32, the default: every launch enqueued is what it was before) ---------
+    // 1: bf16 rows, 2: FP8 e4m3 rows with one f32 scale per (row, KV head).  Both banks; the single-sequence cache, embed and
+    // score_batch stay f32.  A decode step encodes its K / V row in the scatter (launch_lane_*_scatter_kv) and attends over the codes
+    // (launch_lane_attention_kv: one workgroup per KV head serves that head's query heads).  A prompt runs forward() on ONE f32 staging
+    // lane per layer and is then packed into its lane (launch_lane_kv_pack): the prompt's own attention reads unrounded K / V, the
+    // decode steps the stored codes.  Flipping the type synchronises, drops every captured chain of both banks, ends both sessions
+    // and frees the banks' blocks.  InvalidConfig, before any GPU work: a type outside 0..2 here; at lanes_begin() / a generate call
+    // with a compact type, a head_dim that is no multiple of 16 or above 128, heads no multiple of kv_heads, or a geometry
+    // lane_attention_kv_accepts() refuses.
+    void set_lane_kv_type(int type);
+    int lane_kv_type() const { return lane_kv_type_; }
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
     uint64_t prefix_reused_tokens() const { return prefix_reused_; }
     uint64_t prefix_computed_tokens() const { return prefix_computed_; }
@@ -322,7 +334,10 @@ public:
     void lanes_step(Bank bank, const uint32_t* ids, const int32_t* live, float* hidden_out, float* logits_out);
     int lane_cache_len(Bank bank, int lane) const;
     int lane_capacity(Bank bank) const { return bank_of(bank).cap; }
+    // (a compact lane's rows come back DECODED: the codes are copied to the host and widened there, FP8 times its scale in f32)
     void lane_kv_rows(Bank bank, int lane, int layer, int first, int rows, float* k_out, float* v_out) const;
+    // Bytes of K + V (+ FP8 scales) of the bank's current session: layers * 2 * lanes * rows * (kv * element + scales); 0 without one.
+    size_t lane_cache_bytes(Bank bank) const;
     // Projections of lane steps that took the multi-row weight-streaming kernel / fell back to the one-wave-per-column kernel
     // since load (counted when enqueued: a replayed graph counts once, at capture).
     uint64_t lane_stream_calls() const { return lane_stream_calls_; }
@@ -443,8 +458,11 @@ private:
             : wide(wide_step), min_lanes(lo), max_lanes(hi), range_error(range), width(layout), state_bytes(bytes), begin_error(begin)
         {
         }
-        // per layer the lane-major caches [lanes][lane rows][kv] (one stride, alloc_cap * kv, addresses a lane)
-        std::vector<float*> k, v;
+        // per layer the lane-major caches [lanes][lane rows][kv] of the model's lane_kv_type (f32, bf16 or FP8 codes; one stride,
+        // alloc_cap rows, addresses a lane), the FP8 scale planes [lanes][lane rows][kv_heads] beside them, and -- compact types -- ONE f32
+        // staging lane [lane rows][kv] per layer that prompts are computed in before launch_lane_kv_pack encodes them into their lane
+        std::vector<uint8_t*> k, v;
+        std::vector<float*> k_scale, v_scale, stage_k, stage_v;
         // One allocation of its own behind everything sized by lanes x rows or lanes x vocab, replaced when either grows: the
         // caches, the Q|K|V staging rows, the logits rows, the pick history [lanes, hist_stride], the logits processors' history,
         // distinct tokens, counts [lanes, vocab] and numbers of distinct tokens, and the wide bank's attention scratch.
@@ -461,6 +479,7 @@ private:
         LaneStateRef dev, host;
         unsigned long long* best = nullptr;
         LlmKvCopyPair* copy_table = nullptr;
+        LaneKvPackEntry* pack_table = nullptr;  // compact types: copy_table then points at the staging lane, this from it into lane 0
         // captured chains by lane count: step -> pick; step -> records -> pick [k == 1 | k > 1]; step -> the automaton pick [no
         // records | k == 1 | k > 1]
         hipGraphExec_t graphs[kWideLanes + 1] = {}, lp_graphs[2][kWideLanes + 1] = {}, auto_graphs[3][kWideLanes + 1] = {};
@@ -829,6 +848,7 @@ private:
     bool prefix_reuse_ = false;
     bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
     bool ggml_mc_ = false;  // set_ggml_matrix_cores(): only ever true with quant_ && !fp8_
+    int lane_kv_type_ = 0;    // set_lane_kv_type(): LaneKvType
     bool affine_mc_ = false;  // set_affine_matrix_cores(): only ever true with quant_ && !fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
 };

@@ -897,6 +897,24 @@ class HipDecoder:
     def affine_matrix_cores(self) -> bool:
         return bool(lib().kjarni_hip_decoder_affine_matrix_cores(self._h))
 
+    # ---- the lanes' KV cache type ----
+    LANE_KV_F32, LANE_KV_BF16, LANE_KV_F8_E4M3 = 0, 1, 2
+
+    def set_lane_kv_type(self, kv_type: int):
+        """The KV cache type of the lock-step lanes (generate_batch / generate_wide and the lane hooks): 0 f32 (the default: nothing
+        changes), 1 bf16 (half the bytes), 2 FP8 e4m3 with one f32 scale per (row, KV head) (a quarter plus the scales).  A decode step
+        encodes its K / V row and attends over the codes, one workgroup per KV head serving that head's query heads; a prompt is
+        computed in f32 and then encoded.  Flipping the type ends the lane sessions and frees their caches.  The single-sequence cache
+        stays f32."""
+        check_error(lib().kjarni_hip_decoder_set_lane_kv_type(self._h, int(kv_type)))
+
+    def lane_kv_type(self) -> int:
+        return int(lib().kjarni_hip_decoder_lane_kv_type(self._h))
+
+    def lane_cache_bytes(self, wide: bool = False) -> int:
+        """Bytes of K + V (+ FP8 scales) of the current lanes (or wide) session; 0 without one."""
+        return int(lib().kjarni_hip_decoder_lane_cache_bytes(self._h, 1 if wide else 0))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
         a, b = C.c_uint64(), C.c_uint64()

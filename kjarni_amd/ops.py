@@ -1419,6 +1419,65 @@ def wide_rope_scatter(qkv, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, 
     return q, kc, vc
 
 
+def _lane_kv_planes(kv_type, k_codes, v_codes, k_scale, v_scale):
+    """The code planes [lanes, lane rows, kv] as uint16 (bf16) / uint8 (FP8) copies and, for FP8, the scale planes [lanes, lane rows,
+    kv_heads]."""
+    if kv_type not in (1, 2):  # (the C side refuses it too; the dtype below needs it here)
+        raise ValueError("kv_type must be 1 (bf16) or 2 (FP8 e4m3)")
+    dt = np.uint16 if kv_type == 1 else np.uint8
+    kc, vc = np.array(k_codes, dt, order="C"), np.array(v_codes, dt, order="C")
+    if kc.ndim != 3 or kc.shape != vc.shape:
+        raise ValueError("k_codes and v_codes [lanes, lane rows, kv]")
+    ks = vs = None
+    if kv_type == 2:
+        ks, vs = np.array(k_scale, np.float32, order="C"), np.array(v_scale, np.float32, order="C")
+        if ks.ndim != 3 or ks.shape != vs.shape or ks.shape[:2] != kc.shape[:2]:
+            raise ValueError("k_scale and v_scale [lanes, lane rows, kv_heads]")
+    return kc, vc, ks, vs
+
+
+def lane_kv_scatter(kv_type: int, qkv, n_heads: int, n_kv_heads: int, head_dim: int, cos_t, sin_t, k_codes, v_codes, capacity: int, pos, live,
+                    k_scale=None, v_scale=None, rotate: bool = True, gamma_q=None, gamma_k=None, eps: float = 0.0, device: int = 0):
+    """wide_rope_scatter into a compact lane cache (kjarni_hip_op_lane_kv_scatter): kv_type 1 = bf16 codes (uint16), 2 = FP8 e4m3
+    codes (uint8) with scales [lanes, lane rows, kv_heads].  Returns copies (qkv, k_codes, v_codes, k_scale, v_scale) after the call."""
+    q = np.array(qkv, np.float32, order="C")
+    kc, vc, ks, vs = _lane_kv_planes(kv_type, k_codes, v_codes, k_scale, v_scale)
+    if q.ndim != 2 or kc.shape[0] != q.shape[0]:
+        raise ValueError("qkv [lanes, ld]; one plane row block per lane")
+    lanes = q.shape[0]
+    ps, lv = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(live, np.int32)
+    ct, st = _c(cos_t), _c(sin_t)
+    if ps.size != lanes or lv.size != lanes or ct.shape != st.shape or ct.ndim != 2:
+        raise ValueError("pos / live [lanes]; cos_t / sin_t [table rows, head_dim / 2]")
+    gq, gk = _c(gamma_q), _c(gamma_k)
+    check_error(lib().kjarni_hip_op_lane_kv_scatter(device, int(kv_type), _f(q), q.shape[1], lanes, int(n_heads), int(n_kv_heads), int(head_dim),
+                                                    _f(gq), _f(gk), float(eps), _f(ct), _f(st), ct.shape[0], kc.ctypes.data, vc.ctypes.data,
+                                                    _f(ks), _f(vs), kc.shape[1], int(capacity), ps.ctypes.data_as(_i32p),
+                                                    lv.ctypes.data_as(_i32p), int(bool(rotate))))
+    return q, kc, vc, ks, vs
+
+
+def lane_attention_kv(kv_type: int, q, k_codes, v_codes, heads: int, n_kv_heads: int, head_dim: int, capacity: int, splits: int, pos, live,
+                      k_scale=None, v_scale=None, want_slabs: bool = False, device: int = 0):
+    """One launch_lane_attention_kv over compact planes laid out as lane_kv_scatter's (kjarni_hip_op_lane_attention_kv): q [lanes, ldq]
+    -> ctx [lanes, heads * head_dim] (and the slabs [lanes, heads, splits, head_dim + 4] with want_slabs)."""
+    qq = np.ascontiguousarray(q, np.float32)
+    kc, vc, ks, vs = _lane_kv_planes(kv_type, k_codes, v_codes, k_scale, v_scale)
+    if qq.ndim != 2 or kc.shape[0] != qq.shape[0]:
+        raise ValueError("q [lanes, ldq]; one plane row block per lane")
+    lanes = qq.shape[0]
+    ps, lv = np.ascontiguousarray(pos, np.int32), np.ascontiguousarray(live, np.int32)
+    if ps.size != lanes or lv.size != lanes:
+        raise ValueError("pos / live [lanes]")
+    ctx = np.full((lanes, int(heads) * int(head_dim)), np.nan, np.float32)
+    slabs = np.empty((lanes, int(heads), int(splits), int(head_dim) + 4), np.float32) if want_slabs else None
+    check_error(lib().kjarni_hip_op_lane_attention_kv(device, int(kv_type), _f(qq), qq.shape[1], lanes, kc.ctypes.data, vc.ctypes.data, _f(ks),
+                                                      _f(vs), kc.shape[1], int(capacity), int(heads), int(n_kv_heads), int(head_dim),
+                                                      int(splits), ps.ctypes.data_as(_i32p), lv.ctypes.data_as(_i32p), _f(ctx), ctx.shape[1],
+                                                      _f(slabs)))
+    return (ctx, slabs) if want_slabs else ctx
+
+
 def wide_pick(logits, state: "_ffi.KjarniHipWideState", history, capacity: int, lanes: Optional[int] = None, first_lane: int = 0,
               advance: bool = True, vocab: Optional[int] = None, device: int = 0):
     """One launch_lane_pick over the 64-lane state (kjarni_hip_op_wide_pick) over lanes [first_lane, first_lane + lanes) of logits [rows, ld]: `state` is

@@ -87,6 +87,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            all-Q4_0 and as the Q5_K_M-style mix of llm_affine; the prompt at 128 / 384 tokens with the switch off / on / bf16, wide
            lanes at 16 / 32 / 64 with the switch on against the same file at 8 lanes and bf16 at the same widths; llm_wide_gguf's
            method: one process, legs alternated twice, best of two.  The lines also go to profiles/llm_wide_affine_bench.jsonl.
+  llm_wide_kv  (only on request) the lanes' KV cache types (HipDecoder.set_lane_kv_type): Llama-3.2-1B shape, bf16 weights, 64 and 16 wide
+           lanes at lane_context 512 (128-token prompts) and 4 096 (2 048-token prompts); f32 / bf16 / FP8 alternated in one process,
+           best of two; ms per step, aggregate tokens/s and lane_cache_bytes per type.  The lines also go to
+           profiles/llm_wide_kv_bench.jsonl.  KJARNI_KV_TRACE=<0|1|2>: only the 4 096 / 64-lane leg of that type, for a kernel trace.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1263,6 +1267,62 @@ def main():
             for line in lines:
                 emit(line)
                 f.write(json.dumps(line) + "\n")
+
+    if "llm_wide_kv" in which:
+        # The lanes' KV cache types (HipDecoder.set_lane_kv_type): Llama-1B shape, bf16 weights, 64 and 16 wide lanes, at lane_context
+        # 512 with 128-token prompts and 4 096 with 2 048-token prompts.  One process on one box; every (setting, width, type) leg warmed
+        # first, then the three types alternated twice, best of two; a decode window is a whole call minus the same call cut after its
+        # first token.  KJARNI_KV_TRACE=<type> runs only the 4 096 / 64-lane leg of that type, for a kernel trace of its own.
+        rng = np.random.default_rng(0)
+        n_new, kinds = 64, {0: "f32", 1: "bf16", 2: "fp8_e4m3"}
+        settings = {"ctx512_prompt128": (512, 128), "ctx4096_prompt2048": (4096, 2048)}
+        d = os.path.join(tmp, "llama-1b-bf16-wide-kv")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=4096)
+        trace = os.environ.get("KJARNI_KV_TRACE")
+
+        def window(width, ctx, prompts):
+            t0 = time.perf_counter()
+            dec.generate_wide(prompts[:width], 1, lanes=width, lane_context=ctx)
+            t1 = time.perf_counter()
+            outs = dec.generate_wide(prompts[:width], n_new, lanes=width, lane_context=ctx)
+            dt = (time.perf_counter() - t1) - (t1 - t0)
+            assert all(len(o) == n_new for o in outs)
+            dec.wide_begin(width, ctx)  # (a session of the same shape: what lane_cache_bytes counts)
+            return {"ms_per_step": round(dt * 1e3 / (n_new - 1), 4), "tokens_per_s": round(width * (n_new - 1) / dt, 1),
+                    "lane_cache_bytes": dec.lane_cache_bytes(wide=True)}
+
+        lines = []
+        for sname, (ctx, plen) in settings.items():
+            prompts = [rng.integers(1000, 100000, plen).tolist() for _ in range(64)]
+            if trace is not None:
+                if ctx == 4096:
+                    dec.set_lane_kv_type(int(trace))
+                    window(64, ctx, prompts)
+                continue
+            for width in (64, 16):
+                best = {}
+                for rep in range(3):  # (rep 0 warms every type's graphs and caches and is dropped)
+                    for t, kind in kinds.items():
+                        dec.set_lane_kv_type(t)
+                        r = window(width, ctx, prompts)
+                        if rep and (kind not in best or r["tokens_per_s"] > best[kind]["tokens_per_s"]):
+                            best[kind] = r
+                lines.append({"metric": f"aggregate tokens/sec greedy decode, {width} wide lanes, Llama-3.2-1B shape, by lane KV cache type",
+                              "unit": "tokens/s", "value": best["f32"]["tokens_per_s"], "n_gpus": 1, "data": "synthetic",
+                              "dtype": "bf16 weights, f32 activations/accumulate; lane KV f32 / bf16 / FP8 e4m3",
+                              "config": {"workload": f"random weights, one {plen}-token prompt per lane, {n_new} generated tokens per lane, "
+                                                     f"lane_context {ctx}; the three types alternated in one process, best of two", "setting": sname,
+                                         "lanes": width},
+                              "by_type": best,
+                              "x_f32": {k: round(best[k]["tokens_per_s"] / best["f32"]["tokens_per_s"], 3) for k in ("bf16", "fp8_e4m3")}})
+        dec.set_lane_kv_type(0)
+        del dec
+        if trace is None:
+            with open(os.path.join(ROOT, "profiles", "llm_wide_kv_bench.jsonl"), "w") as f:
+                for line in lines:
+                    emit(line)
+                    f.write(json.dumps(line) + "\n")
 
     if "llm_affine" in which:
         # Method (as llm_wide_gguf): one process on one box, every decoder loaded and warmed first, then the legs alternated twice,
