@@ -957,6 +957,19 @@ int32_t kjarni_hip_decoder_affine_matrix_cores(const KjarniHipDecoder* decoder);
 KjarniErrorCode kjarni_hip_decoder_set_lane_kv_type(KjarniHipDecoder* decoder, int32_t type);
 int32_t kjarni_hip_decoder_lane_kv_type(const KjarniHipDecoder* decoder);
 uint64_t kjarni_hip_decoder_lane_cache_bytes(const KjarniHipDecoder* decoder, int32_t wide);
+/* The KV cache type of the single-sequence cache (forward, generate and its captured step, prompt-lookup, draft-model verification,
+ * prefix reuse within the cache, Chat and Generator), with the lanes' numbering, codes and scale rule; embed, score_batch and
+ * rerank do not live in the cache and stay f32.  F32 is the default: every launch enqueued is what it was before the setting
+ * existed.  With a compact type a row's K / V are projected into f32 staging rows and encoded into the cache; a one-row step
+ * attends with the lanes' kernel on one lane, a block of rows (a prompt chunk, the verify rows) with launch_seq_attention_kv over
+ * the codes.  Flipping the type synchronises, drops the captured single-sequence chains, empties the cache and reallocates it.
+ * KJARNI_ERROR_INVALID_CONFIG for a type outside 0..2; with a compact type the first forward / generate refuses a head_dim that is
+ * not 16 / 32 / 64 / 128 ("kv_type: ..."), and the entries that copy rows from the single-sequence cache into a lane
+ * (kjarni_hip_decoder_lane_prefill_shared) are refused.  kjarni_hip_decoder_kv_rows returns the DECODED rows as f32 for every
+ * type.  kjarni_hip_decoder_cache_bytes: 2 * layers * rows * (kv * element bytes [+ 4 * kv_heads]) (0 for NULL). */
+KjarniErrorCode kjarni_hip_decoder_set_kv_type(KjarniHipDecoder* decoder, int32_t type);
+int32_t kjarni_hip_decoder_kv_type(const KjarniHipDecoder* decoder);
+uint64_t kjarni_hip_decoder_cache_bytes(const KjarniHipDecoder* decoder);
 /* Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load (zeros on NULL; either output
  * may be NULL).  A batched call counts its shared prefix once for the single-sequence cache and, per request, the shared
  * tokens as kept and the rest of the prompt as computed. */
@@ -1331,6 +1344,21 @@ KjarniErrorCode kjarni_hip_op_lane_attention_kv(int32_t device, int32_t type, co
                                                 const void* v_codes, const float* k_scale, const float* v_scale, int64_t lane_rows,
                                                 int32_t capacity, int32_t heads, int32_t n_kv_heads, int32_t head_dim, int32_t splits,
                                                 const int32_t* lane_pos, const int32_t* lane_live, float* ctx, int64_t ldc, float* slabs);
+/* Does launch_seq_attention_kv take these arguments (1) or refuse them (0)?  Pure host: type 1 / 2, rows >= 1, base >= 0,
+ * base + rows <= capacity, head_dim 16 / 32 / 64 / 128, heads a multiple of n_kv_heads, splits >= 1. */
+int32_t kjarni_hip_seq_attention_kv_accepts(int32_t type, int32_t rows, int32_t base, int32_t capacity, int32_t heads, int32_t n_kv_heads,
+                                            int32_t head_dim, int32_t splits);
+/* kjarni_hip_op_seq_attention_kv: ONE call of launch_seq_attention_kv (the single-sequence compact cache's rows attention on the
+ * bf16 matrix cores, then the merge): query row r of q [rows, ldq] sits at position base + r and attends, causally, to rows
+ * [0, base + r] of the code planes k_codes / v_codes [cache_rows, kv] (2-byte bf16 or 1-byte e4m3 elements; k_scale / v_scale
+ * [cache_rows, n_kv_heads] for FP8, ignored for bf16).  ctx [rows, ldc] is written back whole; slabs (may be NULL) receives
+ * [rows, heads, splits, head_dim + 4].  INVALID_CONFIG, before any GPU work and with every output untouched: a type other than
+ * 1 / 2, rows outside 1..2^16, a head_dim other than 16 / 32 / 64 / 128, heads no multiple of n_kv_heads, FP8 without scale planes,
+ * splits outside 1..256, base < 0 or base + rows > cache_rows, ldq / ldc short of the heads. */
+KjarniErrorCode kjarni_hip_op_seq_attention_kv(int32_t device, int32_t type, const float* q, int64_t ldq, int32_t rows, const void* k_codes,
+                                               const void* v_codes, const float* k_scale, const float* v_scale, int32_t cache_rows,
+                                               int32_t base, int32_t heads, int32_t n_kv_heads, int32_t head_dim, int32_t splits, float* ctx,
+                                               int64_t ldc, float* slabs);
 /* kjarni_hip_op_wide_pick: ONE call of launch_wide_pick over lanes [first_lane, first_lane + lanes) of logits
  * [first_lane + lanes, ld]: for every live lane the argmax (the last maximum wins, +0 == -0, NaN lowest) is appended to
  * history[lane * hist_stride + count], count (and pos when advance) + 1, live cleared on a stop id, at count == limit or at
@@ -1521,6 +1549,9 @@ KjarniErrorCode kjarni_hip_generator_set_affine_matrix_cores(KjarniGenerator* ge
 /* kjarni_hip_decoder_set_lane_kv_type on the handle's model. */
 KjarniErrorCode kjarni_hip_chat_set_lane_kv_type(KjarniChat* chat, int32_t type);
 KjarniErrorCode kjarni_hip_generator_set_lane_kv_type(KjarniGenerator* generator, int32_t type);
+/* kjarni_hip_decoder_set_kv_type on the handle's model. */
+KjarniErrorCode kjarni_hip_chat_set_kv_type(KjarniChat* chat, int32_t type);
+KjarniErrorCode kjarni_hip_generator_set_kv_type(KjarniGenerator* generator, int32_t type);
 void kjarni_hip_generator_prefix_stats(KjarniGenerator* generator, uint64_t* reused, uint64_t* computed);
 
 /* ---- device memory helpers for callers without a HIP runtime binding --------- */

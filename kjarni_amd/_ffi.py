@@ -526,6 +526,9 @@ SIGNATURES = {
     "kjarni_hip_lane_attention_kv_accepts": (c_int32, [c_int32] * 7),
     "kjarni_hip_op_lane_attention_kv": (c_int32, [c_int32, c_int32, _f32p, c_int64, c_int32, c_void_p, c_void_p, _f32p, _f32p, c_int64, c_int32,
                                                   c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), _f32p, c_int64, _f32p]),
+    "kjarni_hip_seq_attention_kv_accepts": (c_int32, [c_int32] * 8),
+    "kjarni_hip_op_seq_attention_kv": (c_int32, [c_int32, c_int32, _f32p, c_int64, c_int32, c_void_p, c_void_p, _f32p, _f32p, c_int32, c_int32,
+                                                 c_int32, c_int32, c_int32, c_int32, _f32p, c_int64, _f32p]),
     "kjarni_hip_op_wide_pick": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_int32, c_int32, POINTER(KjarniHipWideState), POINTER(c_int32),
                                           c_int32, c_int32, c_int32]),
     "kjarni_hip_lookup_config_default": (KjarniHipLookupConfig, []),
@@ -589,6 +592,9 @@ SIGNATURES = {
     "kjarni_hip_decoder_set_lane_kv_type": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_decoder_lane_kv_type": (c_int32, [c_void_p]),
     "kjarni_hip_decoder_lane_cache_bytes": (c_uint64, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_set_kv_type": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_decoder_kv_type": (c_int32, [c_void_p]),
+    "kjarni_hip_decoder_cache_bytes": (c_uint64, [c_void_p]),
     "kjarni_hip_decoder_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_hip_decoder_resident": (c_int32, [c_void_p, _u32p, c_size_t, POINTER(c_size_t)]),
     "kjarni_hip_decoder_last_logits": (c_int32, [c_void_p, _f32p]),
@@ -761,6 +767,8 @@ SIGNATURES = {
     "kjarni_hip_generator_set_affine_matrix_cores": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_chat_set_lane_kv_type": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_generator_set_lane_kv_type": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_chat_set_kv_type": (c_int32, [c_void_p, c_int32]),
+    "kjarni_hip_generator_set_kv_type": (c_int32, [c_void_p, c_int32]),
     "kjarni_hip_generator_prefix_stats": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "kjarni_text_split": (c_int32, [c_char_p, c_size_t, c_size_t, c_char_p, POINTER(KjarniStringArray)]),
     "kjarni_collect_files": (c_int32, [POINTER(KjarniIndexerConfig), POINTER(c_char_p), c_size_t,

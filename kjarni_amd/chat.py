@@ -269,6 +269,11 @@ class Chat:
         per (row, KV head)."""
         check_error(lib().kjarni_hip_chat_set_lane_kv_type(self._handle, int(kv_type)))
 
+    def set_kv_type(self, kv_type: int):
+        """The KV cache type of the conversation's own cache (HipDecoder.set_kv_type): 0 f32 (default), 1 bf16, 2 FP8 e4m3 with a scale
+        per (row, KV head).  Flipping it empties the cache."""
+        check_error(lib().kjarni_hip_chat_set_kv_type(self._handle, int(kv_type)))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose cache rows were kept / computed by the calls that ran with reuse on."""
         a, b = C.c_uint64(0), C.c_uint64(0)

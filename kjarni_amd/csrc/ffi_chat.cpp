@@ -1074,6 +1074,19 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_lane_kv_type(KjarniGenera
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->model().set_lane_kv_type(type); });
 }
 
+// The single-sequence cache's type (LlmModel::set_kv_type) on the handle's model.
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_chat_set_kv_type(KjarniChat* chat, int32_t type)
+{
+    if (!chat) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { chat->inner->model().set_kv_type(type); });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_generator_set_kv_type(KjarniGenerator* gen, int32_t type)
+{
+    if (!gen) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { gen->inner->model().set_kv_type(type); });
+}
+
 KJARNI_EXPORT void kjarni_hip_generator_verify_gemv_calls(KjarniGenerator* gen, uint64_t* streamed, uint64_t* fallback)
 {
     if (streamed) *streamed = gen ? gen->inner->model().verify_stream_calls() : 0;

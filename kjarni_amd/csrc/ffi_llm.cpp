@@ -1111,6 +1111,19 @@ KJARNI_EXPORT uint64_t kjarni_hip_decoder_lane_cache_bytes(const KjarniHipDecode
     return d ? (uint64_t)d->model->lane_cache_bytes(wide ? LlmModel::Bank::Wide : LlmModel::Bank::Lanes) : 0;
 }
 
+// ---- the single-sequence cache's type (LlmModel::set_kv_type) -----------------------------------------------------------------------
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_set_kv_type(KjarniHipDecoder* d, int32_t type)
+{
+    if (!d) return KJARNI_ERROR_NULL_POINTER;
+    std::lock_guard<std::mutex> lock(d->mu);
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] { d->model->set_kv_type(type); });
+}
+
+KJARNI_EXPORT int32_t kjarni_hip_decoder_kv_type(const KjarniHipDecoder* d) { return d ? d->model->kv_type() : 0; }
+
+KJARNI_EXPORT uint64_t kjarni_hip_decoder_cache_bytes(const KjarniHipDecoder* d) { return d ? (uint64_t)d->model->cache_bytes() : 0; }
+
 KJARNI_EXPORT void kjarni_hip_decoder_prefix_stats(const KjarniHipDecoder* d, uint64_t* reused, uint64_t* computed)
 {
     if (reused) *reused = d ? d->model->prefix_reused_tokens() : 0;

@@ -19,6 +19,7 @@
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
 #include "lane_kv_kernels.h"
+#include "seq_kv_kernels.h"
 #include "llm_kernels.h"
 #include "whisper_kernels.h"
 #include "quant_kernels.h"
@@ -2793,6 +2794,54 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_lane_attention_kv(int32_t device, in
                                                 f8 ? static_cast<const float*>(ksd->p) : nullptr, f8 ? static_cast<const float*>(vsd->p) : nullptr,
                                                 lane_rows, capacity, heads, n_kv_heads, head_dim, splits, sd.as<float>(), od.as<float>(), ldc,
                                                 static_cast<const int*>(pd->p), static_cast<const int*>(ld->p), nullptr), "compact lane attention");
+        hip_check(hipDeviceSynchronize(), "sync");
+        od.check("ctx"); sd.check("slabs");
+        hip_check(hipMemcpy(ctx, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H ctx");
+        if (slabs) hip_check(hipMemcpy(slabs, sd.buf.p, pb, hipMemcpyDeviceToHost), "D2H slabs");
+    });
+}
+
+// seq_attention_kv_accepts itself: pure host, no device is asked for.
+KJARNI_EXPORT int32_t kjarni_hip_seq_attention_kv_accepts(int32_t type, int32_t rows, int32_t base, int32_t capacity, int32_t heads,
+                                                          int32_t n_kv_heads, int32_t head_dim, int32_t splits)
+{
+    return seq_attention_kv_accepts(type, rows, base, capacity, heads, n_kv_heads, head_dim, splits) ? 1 : 0;
+}
+
+// ONE call of launch_seq_attention_kv (the matrix-core rows kernel + merge) on host planes: q [rows, ldq], code planes [cache_rows, kv]
+// and, for FP8, scale planes [cache_rows, n_kv_heads]; ctx [rows, ldc] (read, run, written back whole); slabs (may be NULL) receives
+// [rows, heads, splits, head_dim + 4].
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_seq_attention_kv(int32_t device, int32_t type, const float* q, int64_t ldq, int32_t rows,
+                                                             const void* k_codes, const void* v_codes, const float* k_scale,
+                                                             const float* v_scale, int32_t cache_rows, int32_t base, int32_t heads,
+                                                             int32_t n_kv_heads, int32_t head_dim, int32_t splits, float* ctx, int64_t ldc,
+                                                             float* slabs)
+{
+    if (!q || !k_codes || !v_codes || !ctx) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (rows < 1 || rows > (1 << 16)) throw InvalidConfig("rows must be 1..2^16");
+        const size_t cb = lane_kv_plane_bytes(type, 1, heads, n_kv_heads, head_dim, cache_rows, cache_rows, k_scale, v_scale);
+        if (splits < 1 || splits > 256) throw InvalidConfig("splits must be 1..256");
+        if (!seq_attention_kv_accepts(type, rows, base, cache_rows, heads, n_kv_heads, head_dim, splits))
+            throw InvalidConfig("launch_seq_attention_kv refuses these arguments (head_dim 16, 32, 64 or 128; heads a multiple of n_kv_heads; "
+                                "base >= 0 and base + rows <= cache_rows)");
+        const int64_t qd = (int64_t)heads * head_dim;
+        if (ldq < qd || ldc < qd || (ldq & 3) || std::max(ldq, ldc) > (1 << 20))
+            throw InvalidConfig("ldq / ldc must cover the heads and be at most 2^20, ldq a multiple of 4");
+        use_device(device);
+        const bool f8 = type == LANE_KV_F8_E4M3;
+        const size_t qb = (size_t)rows * (size_t)ldq * 4, ob = (size_t)rows * (size_t)ldc * 4;
+        const size_t sb = f8 ? (size_t)cache_rows * (size_t)n_kv_heads * 4 : 0;
+        const size_t pb = decode_attention_scratch_floats(rows, heads, head_dim, splits) * 4;
+        const auto qdv = upload(q, qb, "H2D q"), kd = upload(k_codes, cb, "H2D k_codes"), vd = upload(v_codes, cb, "H2D v_codes");
+        const auto ksd = upload(k_scale, sb, "H2D k_scale"), vsd = upload(v_scale, sb, "H2D v_scale");
+        GuardedBuf od(ob), sd(pb);
+        hip_check(hipMemcpy(od.buf.p, ctx, ob, hipMemcpyHostToDevice), "H2D ctx");
+        hip_check(hipMemset(sd.buf.p, 0xFF, pb), "poison scratch");  // (all-ones words are NaN: a slab the kernel skips would show)
+        launcher_check(launch_seq_attention_kv(type, static_cast<const float*>(qdv->p), ldq, rows, kd->p, vd->p,
+                                               f8 ? static_cast<const float*>(ksd->p) : nullptr, f8 ? static_cast<const float*>(vsd->p) : nullptr,
+                                               base, nullptr, cache_rows, heads, n_kv_heads, head_dim, splits, sd.as<float>(), od.as<float>(), ldc,
+                                               nullptr), "compact rows attention");
         hip_check(hipDeviceSynchronize(), "sync");
         od.check("ctx"); sd.check("slabs");
         hip_check(hipMemcpy(ctx, od.buf.p, ob, hipMemcpyDeviceToHost), "D2H ctx");

@@ -22,6 +22,7 @@
 #include "grammar_kernels.h"
 #include "lane_constraint_kernels.h"
 #include "lane_kv_kernels.h"
+#include "seq_kv_kernels.h"
 #include "logprob_kernels.h"
 #include "score_batch_kernels.h"
 #include "answer_logits_kernels.h"
@@ -314,13 +315,14 @@ LlmModel::~LlmModel()
     arena_.release();
 }
 
+static std::atomic<uint64_t> next_serial{1};  // (0 is "no drafter" in the graph keys)
+
 std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int weights, int max_context)
 {
     check_moe_checkpoint(dir);  // (returns at once for every other kind of checkpoint)
     if (visible_device_count() <= device) throw GpuUnavailable("no usable HIP device " + std::to_string(device));
     std::unique_ptr<LlmModel> m(new LlmModel());
     m->device_ = device;
-    static std::atomic<uint64_t> next_serial{1};  // (0 is "no drafter" in the graph keys)
     m->serial_ = next_serial.fetch_add(1);
     hip_check(hipSetDevice(device), "hipSetDevice");
     // a `.gguf` file, or a directory: safetensors win, else its first `*.gguf` (model_weights.rs:45-77)
@@ -581,8 +583,6 @@ std::unique_ptr<LlmModel> LlmModel::load(const std::string& dir, int device, int
                 (nm[0] == 'q' ? L.q_norm : L.k_norm) = m->upload_f32(buf);
             }
         }
-        L.k_cache = m->dalloc((size_t)m->cache_cap_ * kv);
-        L.v_cache = m->dalloc((size_t)m->cache_cap_ * kv);
     }
     const bool tied = c.tie_embeddings || !contains("lm_head.weight");
     if (m->quant_ && !m->fp8_) {
@@ -651,6 +651,7 @@ void LlmModel::finish_load()
     // that the output projection can merge the slabs itself
     splits_ = std::max(1, std::min(64, (cache_cap_ + 511) / 512));
     while ((cache_cap_ + splits_ - 1) / splits_ > 512) ++splits_;
+    alloc_cache(LANE_KV_F32);
     h_ = dalloc(8 * (size_t)H);
     q_ = dalloc(8 * (size_t)QD);
     ctx_ = dalloc(8 * (size_t)QD);
@@ -736,8 +737,6 @@ void LlmModel::load_gpt2(SafeTensors& st, int weights)
         L.bfc = vec(q + "mlp.c_fc.bias", I);
         L.down = conv1d(q + "mlp.c_proj.weight", I, H);
         L.bdown = vec(q + "mlp.c_proj.bias", H);
-        L.k_cache = dalloc((size_t)cache_cap_ * H);
-        L.v_cache = dalloc((size_t)cache_cap_ * H);
     }
     read(p + "wte.weight", {c.vocab, H});
     embed_ = lm_head_ = upload_weight(buf);
@@ -1207,6 +1206,11 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     const StepRoute route = verify ? StepRoute::Verify : StepRoute::Step;
     const int* pp = device_pos ? pos_ : nullptr;
+    if (kv_type_ != LANE_KV_F32) {  // a compact cache: its own embedding and layers, the same head
+        compact_pass_layers(ids_dev, n, pp, verify);
+        pass_head(n, verify);
+        return;
+    }
     const bool one = n == 1 && !verify, llama = !quant_ && !gpt2_;
     const bool fused_qkv = one && llama && !c.qwen3() && H <= 8192;  // (Qwen3 normalises Q and K per head between projection and rotation)
     const bool embed_in_qkv = fused_qkv && !layers_.empty() && llm_qkv_rope_embeds(H, layers_[0].ln1, layers_[0].wqkv, embed_);
@@ -1218,6 +1222,15 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
                                           splits_, att_scratch_, merge_in_proj ? nullptr : ctx_, QD, stream_, c.heads / c.kv_heads), "attention");
         layer_finish(route, n, L, merge_in_proj);
     }
+    pass_head(n, verify);
+}
+
+// pass()'s end: the final norm and the vocabulary head over the rows of h_.
+void LlmModel::pass_head(int n, bool verify)
+{
+    const int H = cfg_.hidden;
+    const StepRoute route = verify ? StepRoute::Verify : StepRoute::Step;
+    const bool one = n == 1 && !verify, llama = !quant_ && !gpt2_;
     if (one && (llama || fp8_) && llm_gemv_streams(H, lm_head_, nullptr)) {  // the head normalises the row itself (and stores it in last_)
         head(route, h_, 1, logits_, true);
         return;
@@ -1225,6 +1238,152 @@ void LlmModel::pass(const uint32_t* ids_dev, int n, bool device_pos, bool verify
     final_norm(h_, n, last_);  // every row: forward_rows() scores from them
     if (verify) head(route, last_, n, vlogits_);  // every row's logits
     else head(route, last_ + (size_t)(n - 1) * H, 1, logits_);
+}
+
+// pass()'s layers over a compact single-sequence cache (set_kv_type): per layer Q | K | V of the n rows as plain segments into the
+// staging rows (the lanes' first half), the row-indexed scatter that rotates Q in place and encodes K / V into cache rows pos + r, the
+// attention over the codes -- the lanes' one-row kernel on one lane for the step, the matrix-core rows kernel for a block -- and
+// layer_finish().
+void LlmModel::compact_pass_layers(const uint32_t* ids_dev, int n, const int* pp, bool verify)
+{
+    const LlmConfig& c = cfg_;
+    const int d = c.head_dim, QD = c.q_dim(), kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv, t = kv_type_;
+    const StepRoute route = verify ? StepRoute::Verify : StepRoute::Step;
+    const bool one = n == 1 && !verify;
+    const int* lane_pos = pp;
+    if (one && !pp) {  // (the lanes' kernel reads its position from the device)
+        hip_check(hipStreamSynchronize(stream_), "sync");  // (never captured: a pass at a host-held position is forward()'s)
+        hip_check(hipMemcpy(seq_state_, &cache_len_, sizeof(int), hipMemcpyHostToDevice), "H2D pos");
+        lane_pos = seq_state_;
+    }
+    embed_rows(ids_dev, n, h_, cache_len_, pp, nullptr);
+    for (const Layer& L : layers_) {
+        staged_qkv(route, n, L, sqkv_, ldq);
+        hip_check(launch_seq_kv_scatter(t, sqkv_, ldq, sqkv_ + QD, ldq, sqkv_ + QD + kv, ldq, n, c.heads, kvh, d, c.qwen3() ? L.q_norm : nullptr,
+                                        c.qwen3() ? L.k_norm : nullptr, c.eps, cos_, sin_, L.kc, L.vc, L.ks, L.vs, cache_len_, pp, cache_cap_,
+                                        gpt2_ ? 0 : 1, stream_), "rotate + scatter (compact)");
+        if (one)
+            hip_check(launch_lane_attention_kv(t, sqkv_, ldq, 1, L.kc, L.vc, L.ks, L.vs, cache_cap_, cache_cap_, c.heads, kvh, d, splits_,
+                                               att_scratch_, ctx_, QD, lane_pos, seq_state_ + 1, stream_), "attention (compact step)");
+        else
+            hip_check(launch_seq_attention_kv(t, sqkv_, ldq, n, L.kc, L.vc, L.ks, L.vs, cache_len_, pp, cache_cap_, c.heads, kvh, d, splits_,
+                                              att_scratch_, ctx_, QD, stream_), "attention (compact rows)");
+        layer_finish(route, n, L, false);
+    }
+}
+
+// What pass() over a compact cache needs beside it: the staging rows [8, Q | K | V] and two device ints (the step's position when
+// the host holds it; a 1 that the lanes' kernel reads as "live").  A few KiB from the arena, kept for the model's life.
+void LlmModel::ensure_seq_kv()
+{
+    if (sqkv_) return;
+    const LlmConfig& c = cfg_;
+    const size_t kv = (size_t)(gpt2_ ? c.heads : c.kv_heads) * c.head_dim;
+    sqkv_ = dalloc(8 * ((size_t)c.q_dim() + 2 * kv));
+    seq_state_ = reinterpret_cast<int*>(dalloc(2));
+    const int init[2] = {0, 1};
+    hip_check(hipMemcpy(seq_state_, init, sizeof(init), hipMemcpyHostToDevice), "H2D seq state");
+}
+
+// The prompt route's: K and V staging rows [prefill_cap_, kv] and the chunk's one-slab attention scratch, in ONE allocation of its
+// own that set_kv_type() returns to the device when the type goes back to f32.
+void LlmModel::ensure_seq_prompt()
+{
+    if (seq_prompt_block_) return;
+    const LlmConfig& c = cfg_;
+    const size_t kv = (size_t)(gpt2_ ? c.heads : c.kv_heads) * c.head_dim, P = (size_t)prefill_cap_;
+    const size_t rows = (P * kv + 63) & ~(size_t)63;  // (floats: the three pieces stay 256-byte aligned)
+    float* p = static_cast<float*>(arena_.alloc_own((2 * rows + decode_attention_scratch_floats(prefill_cap_, c.heads, c.head_dim, 1)) * sizeof(float)));
+    seq_prompt_block_ = p;
+    psk_ = p;
+    psv_ = p + rows;
+    seq_att_ = p + 2 * rows;
+}
+
+// Every layer's cache planes of `type` in ONE allocation of its own (cache_block_): f32 K and V [rows][kv], or the code planes and,
+// FP8, the scale planes [rows][kv_heads].  Nothing else lives in the block, so set_kv_type() can return it to the device whole.
+void LlmModel::alloc_cache(int type)
+{
+    const size_t kvh = (size_t)(gpt2_ ? cfg_.heads : cfg_.kv_heads), kv = kvh * (size_t)cfg_.head_dim, cap = (size_t)cache_cap_;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t plane = pad(cap * kv * (size_t)lane_kv_elem_bytes(type)), scale = type == LANE_KV_F8_E4M3 ? pad(cap * kvh * sizeof(float)) : 0;
+    char* p = static_cast<char*>(arena_.alloc_own(2 * layers_.size() * (plane + scale)));
+    cache_block_ = p;
+    auto take = [&](size_t bytes) {
+        char* r = bytes ? p : nullptr;
+        p += bytes;
+        return r;
+    };
+    for (Layer& L : layers_) {
+        L.k_cache = L.v_cache = nullptr;
+        L.kc = L.vc = nullptr;
+        L.ks = L.vs = nullptr;
+        if (type == LANE_KV_F32) {
+            L.k_cache = reinterpret_cast<float*>(take(plane));
+            L.v_cache = reinterpret_cast<float*>(take(plane));
+            continue;
+        }
+        L.kc = reinterpret_cast<uint8_t*>(take(plane));
+        L.vc = reinterpret_cast<uint8_t*>(take(plane));
+        L.ks = reinterpret_cast<float*>(take(scale));
+        L.vs = reinterpret_cast<float*>(take(scale));
+    }
+}
+
+void LlmModel::set_kv_type(int type)
+{
+    if (type < LANE_KV_F32 || type > LANE_KV_F8_E4M3)
+        throw InvalidConfig("kv_type must be 0 (f32), 1 (bf16) or 2 (FP8 e4m3); it is " + std::to_string(type));
+    if (type == kv_type_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    // the captured chains hold the type's launches and the planes' addresses
+    for (hipGraphExec_t* g : {&graph_, &cgraph_, &ggraph_}) {
+        if (*g) (void)hipGraphExecDestroy(*g);
+        *g = nullptr;
+    }
+    for (auto& kind : lp_graphs_)
+        for (hipGraphExec_t& g : kind) {
+            if (g) (void)hipGraphExecDestroy(g);
+            g = nullptr;
+        }
+    drop_graphs(lookup_graphs_);
+    drop_graphs(lookup_sampled_graphs_);
+    serial_ = next_serial.fetch_add(1);  // (a target whose chains captured this model as its drafter captures them again)
+    reset();
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    arena_.free_own(cache_block_);  // (alloc_cache()'s own allocation: only cache planes live in it)
+    cache_block_ = nullptr;
+    if (type == LANE_KV_F32 && seq_prompt_block_) {
+        arena_.free_own(seq_prompt_block_);
+        seq_prompt_block_ = nullptr;
+        psk_ = psv_ = seq_att_ = nullptr;
+    }
+    kv_type_ = type;
+    alloc_cache(type);
+    if (type != LANE_KV_F32) ensure_seq_kv();  // (here, not at first use: the first pass() may run inside a stream capture)
+    // (the lane banks' shared-prefix tables hold the f32 planes' addresses)
+    for (LaneBank* b : {&lane_bank_, &wide_bank_})
+        if (b->copy_table && b->block) upload_lane_copy_table(*b);
+}
+
+size_t LlmModel::cache_bytes() const
+{
+    const size_t kvh = (size_t)(gpt2_ ? cfg_.heads : cfg_.kv_heads), kv = kvh * (size_t)cfg_.head_dim;
+    const size_t row = kv * (size_t)lane_kv_elem_bytes(kv_type_) + (kv_type_ == LANE_KV_F8_E4M3 ? kvh * sizeof(float) : 0);
+    return 2 * layers_.size() * (size_t)cache_cap_ * row;
+}
+
+// The geometry the compact routes ask of the checkpoint, checked where a pass would first use it.
+void LlmModel::check_kv_geometry() const
+{
+    if (kv_type_ == LANE_KV_F32) return;
+    const LlmConfig& c = cfg_;
+    const int kvh = gpt2_ ? c.heads : c.kv_heads;
+    if (!seq_attention_kv_accepts(kv_type_, 1, 0, cache_cap_, c.heads, kvh, c.head_dim, splits_) ||
+        !lane_attention_kv_accepts(kv_type_, 1, cache_cap_, c.heads, kvh, c.head_dim, splits_))
+        throw InvalidConfig("kv_type: a compact single-sequence cache takes head_dim 16, 32, 64 or 128 (it is " + std::to_string(c.head_dim) +
+                            ") and heads that are a multiple of kv_heads");
 }
 
 void LlmModel::ensure_prompt_workspace()
@@ -1392,11 +1551,23 @@ void LlmModel::prefill_rows(const uint32_t* ids_host, int n, bool score, int sco
     const LlmConfig& c = cfg_;
     const int H = c.hidden, d = c.head_dim, kv = c.kv_heads * d, QD = c.q_dim();
     ensure_prompt_workspace();
+    if (kv_type_ != LANE_KV_F32) ensure_seq_prompt();
     for (int done = 0; done < n; done += prefill_cap_) {
         const int m = std::min(prefill_cap_, n - done);
         hip_check(hipMemcpyAsync(pids_, ids_host + done, (size_t)m * 4, hipMemcpyHostToDevice, s), "H2D ids");
         embed_rows(pids_, m, ph_, cache_len_, nullptr, nullptr);
         for (const Layer& L : layers_) {
+            if (kv_type_ != LANE_KV_F32) {  // compact cache: K / V into staging rows, encoded by the scatter; attention over the codes
+                const int kvh = gpt2_ ? c.heads : c.kv_heads;
+                rows_qkv(m, L, psk_, psv_);
+                hip_check(launch_seq_kv_scatter(kv_type_, pq_, QD, psk_, kv, psv_, kv, m, c.heads, kvh, d, c.qwen3() ? L.q_norm : nullptr,
+                                                c.qwen3() ? L.k_norm : nullptr, c.eps, cos_, sin_, L.kc, L.vc, L.ks, L.vs, cache_len_, nullptr,
+                                                cache_cap_, gpt2_ ? 0 : 1, s), "rotate + scatter (compact)");
+                hip_check(launch_seq_attention_kv(kv_type_, pq_, QD, m, L.kc, L.vc, L.ks, L.vs, cache_len_, nullptr, cache_cap_, c.heads, kvh, d, 1,
+                                                  seq_att_, pctx_, QD, s), "attention (compact rows)");
+                rows_finish(m, L);
+                continue;
+            }
             rows_qkv(m, L, L.k_cache + (size_t)cache_len_ * kv, L.v_cache + (size_t)cache_len_ * kv);
             if (c.qwen3()) {  // head norm + rotation over the chunk's Q rows and its K rows in the cache
                 hip_check(launch_qk_norm_rope(pq_, QD, L.k_cache, kv, m, c.heads, c.kv_heads, d, L.q_norm, L.k_norm, c.eps, cos_, sin_, cache_len_,
@@ -1466,6 +1637,7 @@ void LlmModel::forward_rows(const uint32_t* ids, int n, bool score, int score_ba
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (n < 1) throw std::runtime_error("forward needs at least one token");
     if (cache_len_ + n > cache_cap_) throw std::runtime_error("context is full");
+    check_kv_geometry();
     const bool tracked = resident_.size() == (size_t)cache_len_;  // (else: untracked rows lie between; resident_ stays a prefix)
     constexpr int kMinGemmRows = 24;  // rows from which the matrix-core route is used
     if (n >= kMinGemmRows && rows_geometry(cfg_)) {
@@ -1618,8 +1790,29 @@ void LlmModel::kv_rows(int layer, int first, int rows, float* k_out, float* v_ou
     hip_check(hipStreamSynchronize(stream_), "sync");
     const size_t kv = (size_t)cfg_.kv_heads * cfg_.head_dim, off = (size_t)first * kv, bytes = (size_t)rows * kv * sizeof(float);
     const Layer& L = layers_[(size_t)layer];
-    hip_check(hipMemcpy(k_out, L.k_cache + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
-    hip_check(hipMemcpy(v_out, L.v_cache + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+    if (kv_type_ == LANE_KV_F32) {
+        hip_check(hipMemcpy(k_out, L.k_cache + off, bytes, hipMemcpyDeviceToHost), "D2H k cache");
+        hip_check(hipMemcpy(v_out, L.v_cache + off, bytes, hipMemcpyDeviceToHost), "D2H v cache");
+        return;
+    }
+    // compact: the codes (and scales) to the host, widened there as lane_kv_rows() does
+    const size_t kvh = (size_t)(gpt2_ ? cfg_.heads : cfg_.kv_heads), d = (size_t)cfg_.head_dim, es = (size_t)lane_kv_elem_bytes(kv_type_);
+    std::vector<uint8_t> codes((size_t)rows * kv * es);
+    std::vector<float> scales(kv_type_ == LANE_KV_F8_E4M3 ? (size_t)rows * kvh : 0);
+    for (int which = 0; which < 2; ++which) {
+        float* out = which ? v_out : k_out;
+        hip_check(hipMemcpy(codes.data(), (which ? L.vc : L.kc) + off * es, codes.size(), hipMemcpyDeviceToHost), "D2H cache codes");
+        if (kv_type_ == LANE_KV_BF16) {
+            for (size_t i = 0; i < (size_t)rows * kv; ++i) {
+                const uint32_t u = (uint32_t)(codes[2 * i] | (codes[2 * i + 1] << 8)) << 16;
+                std::memcpy(out + i, &u, 4);
+            }
+            continue;
+        }
+        hip_check(hipMemcpy(scales.data(), (which ? L.vs : L.ks) + (size_t)first * kvh, scales.size() * sizeof(float), hipMemcpyDeviceToHost),
+                  "D2H cache scales");
+        for (size_t i = 0; i < (size_t)rows * kv; ++i) out[i] = fp8_e4m3_to_f32(codes[i]) * scales[(i / kv) * kvh + (i % kv) / d];
+    }
 }
 
 void LlmModel::logits_to_host(float* out) const
@@ -2443,14 +2636,7 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
         b.pndistinct = reinterpret_cast<int*>(take(pad(nl)));
         b.alloc = (int)nl;
         b.alloc_cap = (int)nc;
-        // the shared-prefix copy reads its pointers from the device: (main K, lane-0 K, main V, lane-0 V) per layer
-        std::vector<LlmKvCopyPair> pairs(layers_.size());
-        // (compact types: into the staging lane, which launch_lane_kv_pack then encodes into the lane by its own table)
-        for (size_t i = 0; i < layers_.size(); ++i) {
-            if (kvt == LANE_KV_F32) pairs[i] = {layers_[i].k_cache, reinterpret_cast<float*>(b.k[i]), layers_[i].v_cache, reinterpret_cast<float*>(b.v[i])};
-            else pairs[i] = {layers_[i].k_cache, b.stage_k[i], layers_[i].v_cache, b.stage_v[i]};
-        }
-        hip_check(hipMemcpy(b.copy_table, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
+        upload_lane_copy_table(b);
         if (kvt != LANE_KV_F32) {
             std::vector<LaneKvPackEntry> pack(layers_.size());
             for (size_t i = 0; i < layers_.size(); ++i) pack[i] = {b.stage_k[i], b.stage_v[i], b.k[i], b.v[i], b.k_scale[i], b.v_scale[i]};
@@ -2463,6 +2649,18 @@ void LlmModel::ensure_lane_bank(LaneBank& b, int lanes, int lane_context)
     std::memset(b.mirror.get(), 0, b.state_bytes);
     std::fill(b.len, b.len + kWideLanes, 0);
     lane_state_to_device(b);
+}
+
+// The shared-prefix copy reads its pointers from the device: (main K, lane-0 K, main V, lane-0 V) per layer.
+void LlmModel::upload_lane_copy_table(LaneBank& b)
+{
+    std::vector<LlmKvCopyPair> pairs(layers_.size());
+    // (compact types: into the staging lane, which launch_lane_kv_pack then encodes into the lane by its own table)
+    for (size_t i = 0; i < layers_.size(); ++i) {
+        if (lane_kv_type_ == LANE_KV_F32) pairs[i] = {layers_[i].k_cache, reinterpret_cast<float*>(b.k[i]), layers_[i].v_cache, reinterpret_cast<float*>(b.v[i])};
+        else pairs[i] = {layers_[i].k_cache, b.stage_k[i], layers_[i].v_cache, b.stage_v[i]};
+    }
+    hip_check(hipMemcpy(b.copy_table, pairs.data(), pairs.size() * sizeof(LlmKvCopyPair), hipMemcpyHostToDevice), "H2D copy table");
 }
 
 void LlmModel::lane_state_to_device(LaneBank& b)
@@ -2491,6 +2689,9 @@ void LlmModel::lane_copy_prefix(LaneBank& b, int lane, int s)
 {
     if (lane < 0 || lane >= b.lanes) throw std::runtime_error("no such lane");
     if (s < 0 || s > cache_len_ || s > b.cap) throw std::runtime_error("shared prefix out of range");
+    if (kv_type_ != LANE_KV_F32)  // (the copy reads f32 rows)
+        throw InvalidConfig("lane_prefill_shared: rows of a compact single-sequence cache (kv_type " + std::to_string(kv_type_) +
+                            ") are not copied into the lanes (lane_kv_type " + std::to_string(lane_kv_type_) + "); set kv_type 0");
     const int64_t kv = gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim;
     // (a compact bank's table points at the one staging lane: lane_prefill_at() packs rows [0, s + n) from there into the lane)
     const int64_t dst = lane_kv_type_ == LANE_KV_F32 ? (int64_t)lane * b.alloc_cap * kv : 0;
@@ -2518,8 +2719,9 @@ void LlmModel::lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* 
     if (base < 0 || (int64_t)base + n > b.cap) throw std::runtime_error("prompt does not fit the lane");
     const size_t kv = (size_t)(gpt2_ ? cfg_.hidden : cfg_.kv_heads * cfg_.head_dim), off = (size_t)lane * b.alloc_cap * kv;
     std::vector<std::pair<float*, float*>> saved(layers_.size());
-    const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_;
+    const int saved_len = cache_len_, saved_cap = cache_cap_, saved_rows = last_rows_, saved_type = kv_type_;
     const size_t saved_resident = resident_.size();
+    kv_type_ = LANE_KV_F32;  // (forward() below writes f32 rows into the lane's memory whatever the single-sequence cache's type)
     // Compact types: the prompt is computed in the bank's f32 staging lane (rows [0, base) are there: lane_copy_prefix() put them, the
     // only way a caller gets base > 0) and rows [0, base + n) are then encoded into the lane -- the prompt's own attention reads
     // unrounded K / V, the decode steps the stored codes.
@@ -2539,6 +2741,7 @@ void LlmModel::lane_prefill_at(LaneBank& b, int lane, int base, const uint32_t* 
         cache_len_ = saved_len;
         cache_cap_ = saved_cap;
         last_rows_ = saved_rows;
+        kv_type_ = saved_type;
         resident_.resize(std::min(resident_.size(), saved_resident));  // (forward() may have appended the lane's tokens)
     };
     try {
@@ -2592,40 +2795,49 @@ void LlmModel::lane_attention(const LaneBank& b, int n, size_t li, float* scratc
                                       stream_, c.heads / kvh, stride, stride, 1, b.dev.pos, b.dev.live), "attention");
 }
 
+// Norm + Q | K | V of n <= 8 rows of h_ as plain segments into staging rows dst [n, ldq] (Q | K | V side by side, nothing rotated): the
+// first half of a lane step's layer, and of a pass() over a compact single-sequence cache.
+void LlmModel::staged_qkv(StepRoute route, int n, const Layer& L, float* dst, int ldq)
+{
+    hipStream_t s = stream_;
+    const LlmConfig& c = cfg_;
+    const int H = c.hidden, QD = c.q_dim(), kv = (gpt2_ ? c.heads : c.kv_heads) * c.head_dim;
+    const QMat* qkv_mats[3] = {&L.q, &L.k, &L.v};
+    if (fp8_) {
+        fp8_qkv(n, L, dst, ldq, dst + QD, dst + QD + kv, ldq, 0, nullptr);
+    } else if (const int r = quant_ ? quant_stage_route(qkv_mats, 3) : 0) {
+        affine_qkv(n, L, r, dst, ldq, dst + H, dst + H + kv, ldq, 0, nullptr, false);
+    } else if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
+        QFusedArgs a;
+        a.mode = QF_PLAIN;
+        quant_source(a, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
+        a.W[0] = L.q; a.W[1] = L.k; a.W[2] = L.v;
+        a.seg_jobs[0] = H / 2; a.seg_jobs[1] = kv / 2; a.seg_jobs[2] = kv / 2;
+        a.jobs = H / 2 + kv;
+        a.bias = L.bqkv; a.bias_off[1] = H; a.bias_off[2] = H + kv;
+        a.Y[0] = dst; a.Y[1] = dst + H; a.Y[2] = dst + H + kv;
+        a.ldy[0] = a.ldy[1] = a.ldy[2] = ldq;
+        hip_check(launch_qfused(a, s), "norm + qkv");
+    } else {
+        LlmGemvArgs a;
+        a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
+        a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = dst; a.ldy0 = ldq;
+        project(route, a, "norm + qkv");
+    }
+}
+
 // One lock-step step of the lanes bank: pass()'s stages with one row per lane.  Its own first half of the layer -- Q | K | V of
 // every lane into the staging rows -- then lane_attention(); embedding, layer_finish, final norm and head are pass()'s.
 void LlmModel::lane_step(int n)
 {
-    hipStream_t s = stream_;
     const LlmConfig& c = cfg_;
     const LaneBank& b = lane_bank_;
-    const int H = c.hidden, d = c.head_dim, QD = c.q_dim();
+    const int d = c.head_dim, QD = c.q_dim();
     const int kvh = gpt2_ ? c.heads : c.kv_heads, kv = kvh * d, ldq = QD + 2 * kv;
     embed_rows(reinterpret_cast<const uint32_t*>(b.dev.token), n, h_, 0, nullptr, b.dev.pos);
     for (size_t li = 0; li < layers_.size(); ++li) {
         const Layer& L = layers_[li];
-        const QMat* qkv_mats[3] = {&L.q, &L.k, &L.v};
-        if (fp8_) {
-            fp8_qkv(n, L, b.qkv, ldq, b.qkv + QD, b.qkv + QD + kv, ldq, 0, nullptr);
-        } else if (const int r = quant_ ? quant_stage_route(qkv_mats, 3) : 0) {
-            affine_qkv(n, L, r, b.qkv, ldq, b.qkv + H, b.qkv + H + kv, ldq, 0, nullptr, false);
-        } else if (quant_) {  // Q | K | V as plain segments into the staging rows (launch_qfused streams the weights once for <= 8 rows)
-            QFusedArgs a;
-            a.mode = QF_PLAIN;
-            quant_source(a, n, h_, H, H, L.ln1, q6(L.q) || q6(L.k) || q6(L.v), "norm + q8k 1");
-            a.W[0] = L.q; a.W[1] = L.k; a.W[2] = L.v;
-            a.seg_jobs[0] = H / 2; a.seg_jobs[1] = kv / 2; a.seg_jobs[2] = kv / 2;
-            a.jobs = H / 2 + kv;
-            a.bias = L.bqkv; a.bias_off[1] = H; a.bias_off[2] = H + kv;
-            a.Y[0] = b.qkv; a.Y[1] = b.qkv + H; a.Y[2] = b.qkv + H + kv;
-            a.ldy[0] = a.ldy[1] = a.ldy[2] = ldq;
-            hip_check(launch_qfused(a, s), "norm + qkv");
-        } else {
-            LlmGemvArgs a;
-            a.X = h_; a.ldx = H; a.rows = n; a.gamma = L.ln1; a.beta = L.ln1_b; a.layernorm = gpt2_ ? 1 : 0; a.eps = c.eps; a.W = L.wqkv;
-            a.bf16 = bf16_; a.bias = L.bqkv; a.n_out = ldq; a.k = H; a.Y0 = b.qkv; a.ldy0 = ldq;
-            project(StepRoute::Lanes, a, "norm + qkv");
-        }
+        staged_qkv(StepRoute::Lanes, n, L, b.qkv, ldq);
         lane_attention(b, n, li, att_scratch_, ctx_);
         layer_finish(StepRoute::Lanes, n, L, false);
     }
@@ -2846,7 +3058,7 @@ std::vector<std::vector<uint32_t>> LlmModel::generate_on_lanes(const std::vector
     // into each lane that takes a request; the lane prefills the rest behind it.
     // Only the requests that will enter a lane count (generate()'s rule, as start() below applies it: something to generate).
     int shared = 0;
-    if (prefix_reuse_) {
+    if (prefix_reuse_ && kv_type_ == LANE_KV_F32) {  // (a compact single-sequence cache shares nothing with the lanes: every lane prefills alone)
         const LaneRequest* head = nullptr;
         size_t lcp = 0;
         for (size_t i = 0; i < reqs.size(); ++i) {

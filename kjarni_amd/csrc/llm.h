@@ -189,6 +189,18 @@ public:
     // lane_attention_kv_accepts() refuses.
     void set_lane_kv_type(int type);
     int lane_kv_type() const { return lane_kv_type_; }
+    // ---- the single-sequence cache's type (seq_kv_kernels.h; the lanes' numbering, codes and layout with one lane; 0 = f32, the
+    // default: every launch enqueued is what it was before) --------------------------------------------------------------------------
+    // Every route that lives in the cache runs on it: forward() (both routes), the captured step, the verify rows of prompt-lookup
+    // and of the draft model, prefix reuse within the cache.  K / V are projected into f32 staging rows and encoded by
+    // launch_seq_kv_scatter; a one-row step attends with launch_lane_attention_kv on one lane, a block of rows with
+    // launch_seq_attention_kv.  Flipping the type synchronises, drops the captured single-sequence chains, empties the cache and
+    // reallocates it.  InvalidConfig: a type outside 0..2 here; at the first forward() with a compact type a head_dim other than
+    // 16 / 32 / 64 / 128 ("kv_type: ..."); lane_prefill_shared (rows copied from this cache into a lane) while the type is compact --
+    // generate_lanes / generate_wide with prefix reuse on then prefill every lane alone.  embed, score_batch and rerank stay f32.
+    void set_kv_type(int type);
+    int kv_type() const { return kv_type_; }
+    size_t cache_bytes() const;  // 2 * layers * rows * (kv * element + FP8 scales)
     // Prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load.
     uint64_t prefix_reused_tokens() const { return prefix_reused_; }
     uint64_t prefix_computed_tokens() const { return prefix_computed_; }
@@ -649,7 +661,9 @@ private:
         float *bqkv, *ln1, *ln2;
         float *q_norm = nullptr, *k_norm = nullptr;  // Qwen3: per-head RMSNorm weights [head_dim]
         float *ln1_b = nullptr, *ln2_b = nullptr, *bo = nullptr, *bfc = nullptr, *bdown = nullptr;  // GPT-2's LayerNorm and projection biases
-        float *k_cache, *v_cache;
+        float *k_cache, *v_cache;  // the f32 planes [rows][kv] (kv_type_ 0; null while a compact type holds the cache)
+        uint8_t *kc = nullptr, *vc = nullptr;  // the compact planes' codes [rows][kv] and, FP8, scales [rows][kv_heads]
+        float *ks = nullptr, *vs = nullptr;
         QMat q, k, v, o, gate_q, up_q, down_q;  // quantized checkpoints (wqkv ... down are then null)
         Fp8Mat fq, fk, fv, fo, fgate, fup, fdown;  // FP8 checkpoints (quant_ && fp8_): the codes and scales of the seven matrices
         // a sparse layer (qwen3_moe): the router [E, hidden] and the expert stacks [E, Im, hidden] x 2, [E, hidden, Im] in the weights'
@@ -684,6 +698,16 @@ private:
     // pass()'s first half of a layer: norm + Q|K|V + rotation, Q into q_, K and V into the cache rows at cache_len_ / *pos.
     // fused: the one-token Llama launch; embed_ids (non-null only with it, in the first layer): it gathers the embedding row too.
     void step_qkv(StepRoute route, int n, const Layer& L, const int* pos, bool fused, const uint32_t* embed_ids);
+    // Q | K | V of n <= 8 rows as plain segments into staging rows (lane_step(), compact_pass_layers()); pass()'s embedding and
+    // layers over a compact cache; the compact routes' buffers; their geometry check; the lane banks' shared-prefix table.
+    void staged_qkv(StepRoute route, int n, const Layer& L, float* dst, int ldq);
+    void compact_pass_layers(const uint32_t* ids_dev, int n, const int* pp, bool verify);
+    void pass_head(int n, bool verify);  // pass()'s end: final norm + head
+    void ensure_seq_kv();
+    void ensure_seq_prompt();
+    void alloc_cache(int type);  // every layer's cache planes of `type`, one allocation of its own (cache_block_)
+    void check_kv_geometry() const;
+    void upload_lane_copy_table(LaneBank& b);
     // The second half, shared with lane_step(): o-proj + residual, norm + MLP-in (SwiGLU, or GPT-2's LayerNorm + c_fc + GELU-tanh),
     // down + residual, h_ -> h_.  slabs: the o-proj reads and merges the attention's split slabs in att_scratch_ instead of ctx_.
     // Quantized checkpoints: quant_finish().
@@ -849,6 +873,11 @@ private:
     bool fp8_mc_ = false;  // set_fp8_matrix_cores(): only ever true with fp8_
     bool ggml_mc_ = false;  // set_ggml_matrix_cores(): only ever true with quant_ && !fp8_
     int lane_kv_type_ = 0;    // set_lane_kv_type(): LaneKvType
+    int kv_type_ = 0;         // set_kv_type(): LaneKvType of the single-sequence cache
+    void* cache_block_ = nullptr;       // alloc_cache(): the one allocation behind every layer's cache planes
+    void* seq_prompt_block_ = nullptr;  // ensure_seq_prompt(): psk_ | psv_ | seq_att_, freed when the type goes back to f32
+    float *sqkv_ = nullptr, *psk_ = nullptr, *psv_ = nullptr, *seq_att_ = nullptr;  // ensure_seq_kv() / ensure_seq_prompt()
+    int* seq_state_ = nullptr;
     bool affine_mc_ = false;  // set_affine_matrix_cores(): only ever true with quant_ && !fp8_
     uint64_t prefix_reused_ = 0, prefix_computed_ = 0;
 };

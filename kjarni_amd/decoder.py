@@ -915,6 +915,23 @@ class HipDecoder:
         """Bytes of K + V (+ FP8 scales) of the current lanes (or wide) session; 0 without one."""
         return int(lib().kjarni_hip_decoder_lane_cache_bytes(self._h, 1 if wide else 0))
 
+    # ---- the single-sequence cache's type ----
+    def set_kv_type(self, kv_type: int):
+        """The KV cache type of the single-sequence cache -- forward / generate and its captured step, prompt-lookup, draft-model
+        verification, prefix reuse within the cache: 0 f32 (the default: nothing changes), 1 bf16, 2 FP8 e4m3 with one f32 scale per
+        (row, KV head); the lanes' codes and layout with one lane.  Rows are projected in f32 and encoded; a one-row step attends with
+        the lanes' kernel, blocks of rows (prompt chunks, verify rows) with the matrix-core kernel over the codes
+        (ops.seq_attention_kv).  Flipping the type empties the cache and reallocates it.  embed, score_batch and rerank stay f32;
+        lane_prefill_shared is refused while the type is compact."""
+        check_error(lib().kjarni_hip_decoder_set_kv_type(self._h, int(kv_type)))
+
+    def kv_type(self) -> int:
+        return int(lib().kjarni_hip_decoder_kv_type(self._h))
+
+    def cache_bytes(self) -> int:
+        """Bytes of K + V (+ FP8 scales) of the single-sequence cache: 2 * layers * rows * (kv * element + 4 * kv_heads for FP8)."""
+        return int(lib().kjarni_hip_decoder_cache_bytes(self._h))
+
     def prefix_stats(self):
         """(reused, computed): prompt tokens whose rows were kept / computed by the calls that ran with reuse on, since load."""
         a, b = C.c_uint64(), C.c_uint64()

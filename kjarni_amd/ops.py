@@ -1478,6 +1478,25 @@ def lane_attention_kv(kv_type: int, q, k_codes, v_codes, heads: int, n_kv_heads:
     return (ctx, slabs) if want_slabs else ctx
 
 
+def seq_attention_kv(kv_type: int, q, k_codes, v_codes, heads: int, n_kv_heads: int, head_dim: int, base: int, splits: int = 1,
+                     k_scale=None, v_scale=None, want_slabs: bool = False, device: int = 0):
+    """One launch_seq_attention_kv (kjarni_hip_op_seq_attention_kv): q [rows, ldq] at positions base .. base + rows - 1, causal, over the
+    single-sequence code planes k_codes / v_codes [cache rows, kv] (uint16 bf16 / uint8 e4m3; FP8 scales [cache rows, kv_heads]) ->
+    ctx [rows, heads * head_dim] (and the slabs [rows, heads, splits, head_dim + 4] with want_slabs)."""
+    qq = np.ascontiguousarray(q, np.float32)
+    three = lambda a: None if a is None else np.asarray(a)[None]
+    kc, vc, ks, vs = _lane_kv_planes(kv_type, three(k_codes), three(v_codes), three(k_scale), three(v_scale))
+    if qq.ndim != 2:
+        raise ValueError("q [rows, ldq]")
+    rows = qq.shape[0]
+    ctx = np.full((rows, int(heads) * int(head_dim)), np.nan, np.float32)
+    slabs = np.empty((rows, int(heads), int(splits), int(head_dim) + 4), np.float32) if want_slabs else None
+    check_error(lib().kjarni_hip_op_seq_attention_kv(device, int(kv_type), _f(qq), qq.shape[1], rows, kc.ctypes.data, vc.ctypes.data, _f(ks),
+                                                     _f(vs), kc.shape[1], int(base), int(heads), int(n_kv_heads), int(head_dim), int(splits),
+                                                     _f(ctx), ctx.shape[1], _f(slabs)))
+    return (ctx, slabs) if want_slabs else ctx
+
+
 def wide_pick(logits, state: "_ffi.KjarniHipWideState", history, capacity: int, lanes: Optional[int] = None, first_lane: int = 0,
               advance: bool = True, vocab: Optional[int] = None, device: int = 0):
     """One launch_lane_pick over the 64-lane state (kjarni_hip_op_wide_pick) over lanes [first_lane, first_lane + lanes) of logits [rows, ld]: `state` is

@@ -91,6 +91,9 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            lanes at lane_context 512 (128-token prompts) and 4 096 (2 048-token prompts); f32 / bf16 / FP8 alternated in one process,
            best of two; ms per step, aggregate tokens/s and lane_cache_bytes per type.  The lines also go to
            profiles/llm_wide_kv_bench.jsonl.  KJARNI_KV_TRACE=<0|1|2>: only the 4 096 / 64-lane leg of that type, for a kernel trace.
+  llm_seq_kv  (only on request) the single-sequence cache's types (HipDecoder.set_kv_type): Llama-3.2-1B shape, bf16 weights, contexts
+           512 / 4 096 / 32 768; f32 / bf16 / FP8 alternated in one process, best of two; prompt ms, ms per token and cache_bytes per
+           type.  The lines also go to profiles/llm_seq_kv_bench.jsonl.
   llm_score  (only on request) HipDecoder.score() against forward() of the same ids in one process, alternated twice: Llama-3.2-1B
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
@@ -1323,6 +1326,50 @@ def main():
                 for line in lines:
                     emit(line)
                     f.write(json.dumps(line) + "\n")
+
+    if "llm_seq_kv" in which:
+        # The single-sequence cache's types (HipDecoder.set_kv_type): Llama-1B shape, bf16 weights, contexts 512 / 4 096 / 32 768 (a
+        # prompt of context - 128 tokens, then 64 generated).  One process on one box; every (context, type) leg warmed first, then the
+        # three types alternated twice, best of two; the prompt's time is a forward() that ends in a synchronise, a decode window a whole
+        # generate() minus the same call cut after its first token.  Compare against type 0 of the same run only.
+        rng = np.random.default_rng(0)
+        n_new, kinds = 64, {0: "f32", 1: "bf16", 2: "fp8_e4m3"}
+        d = os.path.join(tmp, "llama-1b-bf16-seq-kv")
+        synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=32768, eos_token_id=[])
+        dec = kjarni_amd.HipDecoder(d, max_context=32768)
+        lines = []
+        for ctx in (512, 4096, 32768):
+            prompt = rng.integers(1000, 100000, ctx - 128).tolist()
+            best = {}
+            for rep in range(3):  # (rep 0 warms every type's graphs and is dropped)
+                for t, kind in kinds.items():
+                    dec.set_kv_type(t)
+                    dec.reset()
+                    t0 = time.perf_counter()
+                    dec.forward(prompt, fetch=False)
+                    dec.cache_len()
+                    t1 = time.perf_counter()
+                    dec.generate(prompt, 1)
+                    t2 = time.perf_counter()
+                    out = dec.generate(prompt, n_new)
+                    dt = (time.perf_counter() - t2) - (t2 - t1)
+                    assert len(out) == n_new
+                    r = {"prompt_ms": round((t1 - t0) * 1e3, 3), "ms_per_token": round(dt * 1e3 / (n_new - 1), 4), "cache_bytes": dec.cache_bytes()}
+                    if rep and (kind not in best or r["ms_per_token"] < best[kind]["ms_per_token"]):
+                        best[kind] = r
+            lines.append({"metric": "ms per token greedy decode, Llama-3.2-1B shape, by single-sequence KV cache type", "unit": "ms",
+                          "value": best["f32"]["ms_per_token"], "n_gpus": 1, "data": "synthetic",
+                          "dtype": "bf16 weights, f32 activations/accumulate; KV f32 / bf16 / FP8 e4m3",
+                          "config": {"workload": f"random weights, a {ctx - 128}-token prompt, {n_new} generated tokens; the three types "
+                                                 "alternated in one process, best of two", "context": ctx},
+                          "by_type": best,
+                          "x_f32": {k: round(best[k]["ms_per_token"] / best["f32"]["ms_per_token"], 3) for k in ("bf16", "fp8_e4m3")}})
+        dec.set_kv_type(0)
+        del dec
+        with open(os.path.join(ROOT, "profiles", "llm_seq_kv_bench.jsonl"), "w") as f:
+            for line in lines:
+                emit(line)
+                f.write(json.dumps(line) + "\n")
 
     if "llm_affine" in which:
         # Method (as llm_wide_gguf): one process on one box, every decoder loaded and warmed first, then the legs alternated twice,
