@@ -388,6 +388,44 @@ KjarniErrorCode kjarni_hip_cosine_search_host(int32_t device, const float* queri
                                               KjarniHipCosineMode mode, int32_t k, int64_t* idx_out,
                                               float* score_out, int64_t* n_hits_out);
 
+/* ---- cosine search over an int8 companion plane ---------------------------------
+ * Beside the f32 rows an immutable corpus may keep a PLANE: int8 codes c with scale s = max|d_i| / 127 per document
+ * (d = s c + r) and, per document, four floats {s, e >= ||r||, ||d||, 1 if the rule below covers the row else 0}.  Layout:
+ * codes [n_docs, dim] (padded to 256 bytes), then the floats.  dim: a multiple of 64, at most 1 024.
+ * A search encodes its queries the same way; |q.d - s_q s (c_q.c)| <= (||q|| + e_q) e + e_q ||d||, and c_q.c is an exact
+ * integer, so a pass over the plane (one byte per element, v_mfma_i32_16x16x64_i8) keeps every document whose cosine can
+ * reach the k-th best; the survivors' cosines are taken from the F32 rows with the arithmetic of kjarni_hip_cosine_search's
+ * filter route: the same indices and scores as that route, bit for bit (one query: scores within 2e-6 of
+ * kjarni_hip_cosine_search's one-query pass, which sums in another order).  Rows the rule does not cover (a non-finite
+ * value, a norm below 1e-4) are decided exactly.  The int8 passes serve dim 128 / 256 / 384 / 512 / 768 / 1024 from 20 000
+ * documents on, k up to an eighth of the sample's units; any other accepted shape, and a search whose lists overflow, is
+ * answered by kjarni_hip_cosine_search inside the same workspace.
+ * stats_out (host, may be NULL): [0] (query, document) pairs judged, [1] pairs that passed the filter, [2] candidates after
+ * the exact pass, [3] fallback: 0 none, 1 a list overflowed, 2 a shape the int8 passes do not serve.
+ * kjarni_hip_cosine_search_coded waits for `stream` before it returns (the overflow word is read on the host).
+ * Refused before any GPU work (KJARNI_ERROR_INVALID_CONFIG): dim not a multiple of 64 or above 1 024, more than 1 024
+ * queries, k above 1 024. */
+size_t kjarni_hip_cosine_codes_bytes(int64_t n_docs, int32_t dim);
+KjarniErrorCode kjarni_hip_cosine_encode(int32_t device, const float* corpus_dev, int64_t n_docs, int32_t dim,
+                                         void* codes_out_dev, void* stream);
+size_t kjarni_hip_cosine_search_coded_workspace_bytes(int32_t n_queries, int64_t n_docs, int32_t dim, int32_t k);
+KjarniErrorCode kjarni_hip_cosine_search_coded(int32_t device, const float* queries_dev, int32_t n_queries,
+                                               const float* corpus_dev, int64_t n_docs, int32_t dim,
+                                               KjarniHipCosineMode mode, int32_t k, const void* codes_dev,
+                                               void* workspace_dev, int64_t* idx_out_dev, float* score_out_dev,
+                                               uint64_t* stats_out, void* stream);
+KjarniErrorCode kjarni_hip_cosine_search_coded_host(int32_t device, const float* queries, int32_t n_queries,
+                                                    const float* corpus, int64_t n_docs, int32_t dim,
+                                                    KjarniHipCosineMode mode, int32_t k, int64_t* idx_out,
+                                                    float* score_out, int64_t* n_hits_out, uint64_t* stats_out);
+/* Process-wide, off by default.  On: an index image uploaded by kjarni_searcher_search* / kjarni_hip_index_search also gets
+ * its plane (counted in the image's bytes and in eviction), and the one-query scan goes through it at the shapes the int8
+ * passes serve.  An image uploaded under the other setting is replaced at the next query.  Off: nothing changes. */
+void kjarni_hip_set_index_codes(int32_t on);
+int32_t kjarni_hip_index_codes(void);
+/* Device bytes held by the index images of every live searcher (rows + planes). */
+size_t kjarni_hip_index_image_bytes(void);
+
 /* Where the calling thread's last kjarni_searcher_search* / kjarni_hip_index_search call spent its time, in microseconds:
  * out[0] re-opening the index, out[1] the scan over the index's device image (lookup, copies, two launches, wait), out[2] of it
  * between the query's H2D copy and the hits' arrival, out[3] the whole call; the rest is host work (BM25, rank fusion, reading

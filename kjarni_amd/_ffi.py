@@ -870,6 +870,16 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "kjarni_hip_cosine_search_host": (c_int32, [c_int32, _f32p, c_int32, _f32p, c_int64, c_int32, c_int32,
                                                 c_int32, _i64p, _f32p, _i64p]),
+    "kjarni_hip_cosine_codes_bytes": (c_size_t, [c_int64, c_int32]),
+    "kjarni_hip_cosine_encode": (c_int32, [c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "kjarni_hip_cosine_search_coded_workspace_bytes": (c_size_t, [c_int32, c_int64, c_int32, c_int32]),
+    "kjarni_hip_cosine_search_coded": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64), c_void_p]),
+    "kjarni_hip_cosine_search_coded_host": (c_int32, [c_int32, _f32p, c_int32, _f32p, c_int64, c_int32, c_int32,
+                                                      c_int32, _i64p, _f32p, _i64p, POINTER(c_uint64)]),
+    "kjarni_hip_set_index_codes": (None, [c_int32]),
+    "kjarni_hip_index_codes": (c_int32, []),
+    "kjarni_hip_index_image_bytes": (c_size_t, []),
     "kjarni_tokenizer_load": (c_int32, [c_char_p, c_size_t, POINTER(c_void_p)]),
     "kjarni_tokenizer_free": (None, [c_void_p]),
     "kjarni_tokenizer_encode_batch": (c_int32, [c_void_p, POINTER(c_char_p), POINTER(c_char_p), c_size_t,

@@ -2121,4 +2121,74 @@ hipError_t launch_cosine_search(const float* queries, int nq, const float* corpu
     return launch_cosine_topk(scores, nq, n_docs, k, topk_ws, out_idx, out_score, stream);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The filtered search's stages as they are, for the int8-plane search (cosine_coded.hip): one bound per query (thr_k = 1).
+// ---------------------------------------------------------------------------------------------------------------------
+bool cosine_filter_width(int dim) { return filter_width(dim); }
+int cosine_count_stride() { return kCountStride; }
+
+hipError_t cosine_query_sqnorms(const float* queries, int nq, int dim, float* qn2, hipStream_t stream)
+{
+    return query_sqnorms(queries, nq, dim, qn2, stream);
+}
+
+// thr = the k-th largest of each query's n <= 4 096 maxima (row length n); zeroes the candidate counters
+hipError_t cosine_sample_bound(const float* maxima, int n, int nq, int k, float* thr_score, int64_t* thr_idx, unsigned* counters,
+                               hipStream_t stream)
+{
+    if (n > 4096) return hipErrorInvalidValue;
+    if (n <= 1024)
+        hipLaunchKernelGGL(sample_bound_wave_kernel<16>, dim3((unsigned)(nq + 3) / 4), dim3(256), 0, stream, maxima, n, (int64_t)n, k, nq, thr_score,
+                           thr_idx, counters, 0.0f);
+    else
+        hipLaunchKernelGGL(sample_bound_kernel<16>, dim3((unsigned)nq), dim3(256), 0, stream, maxima, n, (int64_t)n, k, thr_score, thr_idx, counters,
+                           0.0f);
+    return hipGetLastError();
+}
+
+hipError_t cosine_rescore(int mode, int dim, const float* queries, const float* corpus, const float* qn2, const float* thr_score,
+                          const int64_t* thr_idx, const uint64_t* wave_list, const unsigned* wave_count, int n_lists, unsigned cap_w,
+                          unsigned* counters, unsigned cap_q, uint64_t* cand_key, hipStream_t stream)
+{
+    if (!filter_width(dim) || n_lists > (int)kFilterMaxWaves || (mode != 0 && mode != 1)) return hipErrorInvalidValue;
+#define KJ_RESCORE_X(MODE_, NK_)                                                                                                 \
+    hipLaunchKernelGGL((cosine_rescore_kernel<MODE_, NK_>), dim3(256), dim3(256), 0, stream, queries, corpus, qn2, thr_score, thr_idx, \
+                       1, wave_list, wave_count, n_lists, cap_w, counters, cap_q, cand_key)
+#define KJ_RESCORE_XM(NK_)                                                                                                       \
+    do {                                                                                                                         \
+        if (mode == 0) KJ_RESCORE_X(0, NK_);                                                                                     \
+        else KJ_RESCORE_X(1, NK_);                                                                                               \
+    } while (0)
+    switch (dim / 32) {
+    case 4: KJ_RESCORE_XM(4); break;
+    case 8: KJ_RESCORE_XM(8); break;
+    case 12: KJ_RESCORE_XM(12); break;
+    case 16: KJ_RESCORE_XM(16); break;
+    case 24: KJ_RESCORE_XM(24); break;
+    default: KJ_RESCORE_XM(32); break;
+    }
+#undef KJ_RESCORE_XM
+#undef KJ_RESCORE_X
+    return hipGetLastError();
+}
+
+hipError_t cosine_topk_candidates(int k, int nq, const uint64_t* cand_key, const unsigned* counters, unsigned cap_q, int64_t* out_idx,
+                                  float* out_score, hipStream_t stream)
+{
+#define KJ_CAND_X(KP_)                                                                                                        \
+    hipLaunchKernelGGL(topk_candidates_kernel<KP_>, dim3((unsigned)nq), dim3(256), 0, stream, cand_key, counters, cap_q, k, out_idx, \
+                       out_score)
+    switch (kpad_for(k)) {
+    case 16: KJ_CAND_X(16); break;
+    case 32: KJ_CAND_X(32); break;
+    case 64: KJ_CAND_X(64); break;
+    case 128: KJ_CAND_X(128); break;
+    case 256: KJ_CAND_X(256); break;
+    case 512: KJ_CAND_X(512); break;
+    default: KJ_CAND_X(1024); break;
+    }
+#undef KJ_CAND_X
+    return hipGetLastError();
+}
+
 }  // namespace kjarni

@@ -8,6 +8,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cmath>
@@ -66,6 +67,10 @@ std::unique_ptr<IndexReader> open_index(const std::string& path)
         throw IndexOpenFailed(std::string("Search failed: ") + e.what());
     }
 }
+
+// kjarni_hip_set_index_codes: images uploaded while it is on carry an int8 plane (cosine_coded.hip) and are scanned through it
+std::atomic<int> g_index_codes{0};
+inline bool plane_width(size_t dim) { return dim % 64 == 0 && dim <= 1024; }
 
 class SegmentScanner;
 std::mutex g_scanners_mu;
@@ -165,7 +170,10 @@ public:
         Context& c = lease.ctx();
         // (image->vectors and c.io come from hipMalloc: 256-byte aligned, so the one-query bound applies -- 4 MB per context on
         // the fused pass instead of 36 MB + 4 bytes per document)
-        const size_t need = cosine_search_one_query_workspace_bytes((int64_t)total, (int)query_dim, k);
+        // (the int8-plane route: the switch on, an image that carries the plane, a shape its passes serve)
+        const bool coded = image->codes && g_index_codes.load(std::memory_order_relaxed) && cosine_coded_serves(1, (int64_t)total, (int)query_dim, k);
+        const size_t need = coded ? cosine_search_coded_workspace_bytes(1, (int64_t)total, (int)query_dim, k, true)
+                                  : cosine_search_one_query_workspace_bytes((int64_t)total, (int)query_dim, k);
         if (need > c.work_bytes) {
             if (c.work) {
                 hip_check(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
@@ -195,10 +203,16 @@ public:
         const double t0 = now_us();
         std::memcpy(c.pin, query, query_dim * 4);
         hip_check(hipMemcpyAsync(c.io, c.pin, query_dim * 4, hipMemcpyHostToDevice, c.stream), "H2D query");
-        hip_check(launch_cosine_search(reinterpret_cast<const float*>(c.io), 1, image->vectors, (int64_t)total, (int)query_dim,
-                                       /*segment mode*/ 1, k, c.work, reinterpret_cast<int64_t*>(c.io + i_off),
-                                       reinterpret_cast<float*>(c.io + s_off), c.stream),
-                  "cosine_search");
+        if (coded)
+            hip_check(launch_cosine_search_coded(reinterpret_cast<const float*>(c.io), 1, image->vectors, (int64_t)total, (int)query_dim,
+                                                 /*segment mode*/ 1, k, image->codes, c.work, true, reinterpret_cast<int64_t*>(c.io + i_off),
+                                                 reinterpret_cast<float*>(c.io + s_off), nullptr, c.stream),
+                      "cosine_search_coded");
+        else
+            hip_check(launch_cosine_search(reinterpret_cast<const float*>(c.io), 1, image->vectors, (int64_t)total, (int)query_dim,
+                                           /*segment mode*/ 1, k, c.work, reinterpret_cast<int64_t*>(c.io + i_off),
+                                           reinterpret_cast<float*>(c.io + s_off), c.stream),
+                      "cosine_search");
         hip_check(hipMemcpyAsync(c.pin + i_off, c.io + i_off, (s_off - i_off) + (size_t)k * 4, hipMemcpyDeviceToHost, c.stream), "D2H hits");
         hip_check(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
         t_breakdown.device_us += now_us() - t0;
@@ -233,11 +247,14 @@ private:
         std::vector<std::string> dirs;
         std::vector<size_t> offsets;   // first row of segment i; back() = rows in all
         float* vectors = nullptr;
-        size_t bytes = 0, dim = 0;
+        void* codes = nullptr;         // the int8 plane of the rows (null: uploaded with the switch off, or a width without one)
+        bool coded = false;            // (set at registration: what the upload will build)
+        size_t bytes = 0, dim = 0;     // bytes: rows + plane
         uint64_t last_used = 0;
         bool ready = false, failed = false;  // (under the scanner's mu_) uploaded / its upload threw
         ~Image()
         {
+            if (codes) (void)hipFree(codes);
             if (vectors) (void)hipFree(vectors);  // (runs on a thread whose current device is the scanner's)
         }
     };
@@ -294,11 +311,13 @@ private:
                                      const std::vector<uint64_t>& uids, size_t dim)
     {
         std::shared_ptr<Image> im;
+        // (an image uploaded under the other setting of the switch is superseded like one of an older segment list)
+        const bool want_coded = g_index_codes.load(std::memory_order_relaxed) != 0 && plane_width(dim);
         {
             std::unique_lock<std::mutex> lock(mu_);
             const uint64_t tick = ++tick_;
             for (auto& x : images_)
-                if (x->dim == dim && x->uids == uids) {
+                if (x->dim == dim && x->uids == uids && x->coded == want_coded) {
                     x->last_used = tick;
                     std::shared_ptr<Image> found = x;
                     image_cv_.wait(lock, [&] { return found->ready || found->failed; });
@@ -313,7 +332,8 @@ private:
                 im->dirs.push_back(segs[u]->dir());
                 im->offsets.push_back(im->offsets.back() + segs[u]->doc_count());
             }
-            im->bytes = im->offsets.back() * dim * sizeof(float);
+            im->coded = want_coded && im->offsets.back() > 0;
+            im->bytes = im->offsets.back() * dim * sizeof(float) + (im->coded ? cosine_codes_bytes((int64_t)im->offsets.back(), (int)dim) : 0);
             // a superseded image of the same index (a segment was added: the old list is a prefix or shares directories) goes
             // first, then least-recently-used ones until the new image fits the budget (images still uploading are kept)
             for (auto it = images_.begin(); it != images_.end();) {
@@ -335,12 +355,18 @@ private:
             images_.push_back(im);
         }
         try {
-            hip_check(hipMalloc((void**)&im->vectors, im->bytes ? im->bytes : 4), "hipMalloc(index image)");
+            const size_t row_bytes = im->offsets.back() * dim * sizeof(float);
+            hip_check(hipMalloc((void**)&im->vectors, row_bytes ? row_bytes : 4), "hipMalloc(index image)");
             for (size_t i = 0; i < use.size(); ++i) {
                 const Segment& seg = *segs[use[i]];
                 hip_check(hipMemcpy(im->vectors + im->offsets[i] * dim, seg.vectors(), seg.doc_count() * dim * sizeof(float),
                                     hipMemcpyHostToDevice),
                           "H2D segment vectors");
+            }
+            if (im->coded) {
+                hip_check(hipMalloc(&im->codes, im->bytes - row_bytes), "hipMalloc(index codes)");
+                hip_check(launch_cosine_encode_plane(im->vectors, (int64_t)im->offsets.back(), (int)dim, im->codes, nullptr), "cosine_encode");
+                hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
             }
         } catch (...) {
             std::lock_guard<std::mutex> lock(mu_);
@@ -737,6 +763,18 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_index_search(const char* index_path, co
 // wait), out[2] of it between the query's H2D copy and the hits' arrival, out[3] the whole call -- the rest is host work: BM25,
 // rank fusion, reading the hits' documents and metadata back, (for a Searcher) tokenising and embedding the query.
 KJARNI_EXPORT void kjarni_hip_set_keyword_parallel_min_docs(size_t docs) { set_keyword_parallel_min_docs(docs); }
+
+KJARNI_EXPORT void kjarni_hip_set_index_codes(int32_t on) { g_index_codes.store(on ? 1 : 0, std::memory_order_relaxed); }
+KJARNI_EXPORT int32_t kjarni_hip_index_codes(void) { return g_index_codes.load(std::memory_order_relaxed); }
+
+// Device bytes held by the index images of every live searcher (rows + int8 planes).
+KJARNI_EXPORT size_t kjarni_hip_index_image_bytes(void)
+{
+    std::lock_guard<std::mutex> lock(g_scanners_mu);
+    size_t b = 0;
+    for (const SegmentScanner* s : g_scanners) b += s->cached_bytes();
+    return b;
+}
 
 KJARNI_EXPORT void kjarni_hip_search_breakdown(double* out, size_t n)
 {

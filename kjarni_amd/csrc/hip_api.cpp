@@ -3755,6 +3755,97 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_cosine_search_host(int32_t device, cons
     });
 }
 
+// ---- cosine search over an int8 plane (cosine_coded.hip) ----------------------------
+
+namespace {
+// refused before any GPU work: widths the plane does not exist for, k past the many-query search's limit
+inline bool coded_shape_ok(int32_t n_queries, int64_t n_docs, int32_t dim, int32_t k)
+{
+    return dim > 0 && dim % 64 == 0 && dim <= 1024 && n_queries >= 0 && n_queries <= 1024 && n_docs >= 0 && k >= 0 && k <= 1024;
+}
+}  // namespace
+
+KJARNI_EXPORT size_t kjarni_hip_cosine_codes_bytes(int64_t n_docs, int32_t dim)
+{
+    if (n_docs <= 0 || dim <= 0 || dim % 64 != 0 || dim > 1024) return 0;
+    return cosine_codes_bytes(n_docs, dim);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_cosine_encode(int32_t device, const float* corpus_dev, int64_t n_docs, int32_t dim,
+                                                       void* codes_out_dev, void* stream)
+{
+    if (!corpus_dev || !codes_out_dev) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (dim <= 0 || dim % 64 != 0 || dim > 1024 || n_docs < 0) throw InvalidConfig("coded search: dim must be a multiple of 64, at most 1024");
+        if ((reinterpret_cast<uintptr_t>(corpus_dev) | reinterpret_cast<uintptr_t>(codes_out_dev)) & 15)
+            throw InvalidConfig("coded search: pointers must be 16-byte aligned");
+        use_device(device);
+        hip_check(launch_cosine_encode_plane(corpus_dev, n_docs, dim, codes_out_dev, (hipStream_t)stream), "cosine_encode");
+    });
+}
+
+KJARNI_EXPORT size_t kjarni_hip_cosine_search_coded_workspace_bytes(int32_t n_queries, int64_t n_docs, int32_t dim, int32_t k)
+{
+    if (n_queries <= 0 || n_docs <= 0 || k <= 0 || !coded_shape_ok(n_queries, n_docs, dim, k)) return 256;
+    return cosine_search_coded_workspace_bytes(n_queries, n_docs, dim, k, false);
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_cosine_search_coded(int32_t device, const float* queries_dev, int32_t n_queries,
+                                                             const float* corpus_dev, int64_t n_docs, int32_t dim,
+                                                             KjarniHipCosineMode mode, int32_t k, const void* codes_dev,
+                                                             void* workspace_dev, int64_t* idx_out_dev, float* score_out_dev,
+                                                             uint64_t* stats_out, void* stream)
+{
+    if (!queries_dev || !corpus_dev || !codes_dev || !workspace_dev || !idx_out_dev || !score_out_dev) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!coded_shape_ok(n_queries, n_docs, dim, k)) throw InvalidConfig("coded search: dim a multiple of 64 up to 1024, at most 1024 queries, k <= 1024");
+        use_device(device);
+        hip_check(launch_cosine_search_coded(queries_dev, n_queries, corpus_dev, n_docs, dim, (int)mode, k, codes_dev, workspace_dev, false,
+                                             idx_out_dev, score_out_dev, stats_out, (hipStream_t)stream),
+                  "cosine_search_coded");
+    });
+}
+
+KJARNI_EXPORT KjarniErrorCode kjarni_hip_cosine_search_coded_host(int32_t device, const float* queries, int32_t n_queries,
+                                                                  const float* corpus, int64_t n_docs, int32_t dim,
+                                                                  KjarniHipCosineMode mode, int32_t k, int64_t* idx_out,
+                                                                  float* score_out, int64_t* n_hits_out, uint64_t* stats_out)
+{
+    if (!queries || !corpus || !idx_out || !score_out) return KJARNI_ERROR_NULL_POINTER;
+    return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
+        if (!coded_shape_ok(n_queries, n_docs, dim, k)) throw InvalidConfig("coded search: dim a multiple of 64 up to 1024, at most 1024 queries, k <= 1024");
+        if (n_hits_out) *n_hits_out = 0;
+        if (stats_out) stats_out[0] = stats_out[1] = stats_out[2] = stats_out[3] = 0;
+        if (n_queries == 0 || n_docs == 0 || k == 0) return;
+        use_device(device);
+        const size_t qb = (size_t)n_queries * dim * 4, cb = (size_t)n_docs * dim * 4;
+        DeviceBuf q_d(qb), c_d(cb), p_d(cosine_codes_bytes(n_docs, dim));
+        DeviceBuf ws(cosine_search_coded_workspace_bytes(n_queries, n_docs, dim, k, false));
+        DeviceBuf i_d((size_t)n_queries * k * 8), o_d((size_t)n_queries * k * 4);
+        hip_check(hipMemcpy(q_d.p, queries, qb, hipMemcpyHostToDevice), "H2D queries");
+        hip_check(hipMemcpy(c_d.p, corpus, cb, hipMemcpyHostToDevice), "H2D corpus");
+        hip_check(launch_cosine_encode_plane((const float*)c_d.p, n_docs, dim, p_d.p, nullptr), "cosine_encode");
+        hip_check(launch_cosine_search_coded((const float*)q_d.p, n_queries, (const float*)c_d.p, n_docs, dim, (int)mode, k, p_d.p, ws.p, false,
+                                             (int64_t*)i_d.p, (float*)o_d.p, stats_out, nullptr),
+                  "cosine_search_coded");
+        hip_check(hipMemcpy(idx_out, i_d.p, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost), "D2H idx");
+        hip_check(hipMemcpy(score_out, o_d.p, (size_t)n_queries * k * 4, hipMemcpyDeviceToHost), "D2H scores");
+        if (mode == KJARNI_HIP_COSINE_SEGMENT) {
+            // segment.rs:313-317: a query whose norm is < 1e-9 has no hits (as kjarni_hip_cosine_search_host)
+            for (int32_t j = 0; j < n_queries; ++j) {
+                float s2 = 0.0f;
+                for (int32_t i = 0; i < dim; ++i) s2 += queries[(size_t)j * dim + i] * queries[(size_t)j * dim + i];
+                if (std::sqrt(s2) < 1e-9f)
+                    for (int32_t i = 0; i < k; ++i) {
+                        idx_out[(size_t)j * k + i] = -1;
+                        score_out[(size_t)j * k + i] = -std::numeric_limits<float>::infinity();
+                    }
+            }
+        }
+        if (n_hits_out) *n_hits_out = (k < n_docs) ? k : n_docs;
+    });
+}
+
 // ---- device memory helpers ------------------------------------------------------
 
 KJARNI_EXPORT KjarniErrorCode kjarni_hip_malloc(int32_t device, size_t bytes, void** out_dev)

@@ -190,6 +190,32 @@ size_t cosine_search_one_query_workspace_bytes(int64_t n_docs, int dim, int k);
 hipError_t launch_cosine_search(const float* queries, int nq, const float* corpus, int64_t n_docs, int dim, int mode, int k,
                                 void* workspace, int64_t* out_idx, float* out_score, hipStream_t stream);
 
+// The stages of launch_cosine_search's filtered route, one bound per query (cosine.hip; used by cosine_coded.hip).
+bool cosine_filter_width(int dim);
+int cosine_count_stride();
+hipError_t cosine_query_sqnorms(const float* queries, int nq, int dim, float* qn2, hipStream_t stream);
+hipError_t cosine_sample_bound(const float* maxima, int n, int nq, int k, float* thr_score, int64_t* thr_idx, unsigned* counters,
+                               hipStream_t stream);
+hipError_t cosine_rescore(int mode, int dim, const float* queries, const float* corpus, const float* qn2, const float* thr_score,
+                          const int64_t* thr_idx, const uint64_t* wave_list, const unsigned* wave_count, int n_lists, unsigned cap_w,
+                          unsigned* counters, unsigned cap_q, uint64_t* cand_key, hipStream_t stream);
+hipError_t cosine_topk_candidates(int k, int nq, const uint64_t* cand_key, const unsigned* counters, unsigned cap_q, int64_t* out_idx,
+                                  float* out_score, hipStream_t stream);
+
+// Cosine search over an int8 companion plane of the corpus (cosine_coded.hip): exact results, the filter pass reads one byte per
+// element.  The plane: codes int8 [n_docs, dim] (padded to 256 bytes), then per document {scale, residual norm (rounded up),
+// ||d||, covered-by-the-rule flag} as four floats.  dim: a multiple of 64, at most 1 024.
+size_t cosine_codes_bytes(int64_t n_docs, int dim);
+hipError_t launch_cosine_encode_plane(const float* corpus, int64_t n_docs, int dim, void* plane, hipStream_t stream);
+bool cosine_coded_serves(int nq, int64_t n_docs, int dim, int k);
+// one_query_aligned: nq = 1 with 16-byte aligned pointers (cosine_search_one_query_workspace_bytes for the fallback's share)
+size_t cosine_search_coded_workspace_bytes(int nq, int64_t n_docs, int dim, int k, bool one_query_aligned);
+// Synchronises the stream.  stats (host, may be null): pairs judged, pairs passed, candidates after rescoring, fallback (0 none,
+// 1 a list overflowed, 2 a shape the int8 passes do not serve: launch_cosine_search answered).
+hipError_t launch_cosine_search_coded(const float* queries, int nq, const float* corpus, int64_t n_docs, int dim, int mode, int k,
+                                      const void* plane, void* workspace, bool one_query_aligned, int64_t* out_idx, float* out_score,
+                                      uint64_t* stats, hipStream_t stream);
+
 // Measurement aid: one wave stamps the shader-cycle counter and the 100 MHz counter around a spin of spin_ticks x 10 ns;
 // out[0] = shader cycles, out[1] = 10 ns ticks (clock in GHz = out[0] / out[1] / 10).  rowops.hip.
 hipError_t launch_clock_probe(uint64_t* out, unsigned spin_ticks, hipStream_t stream);

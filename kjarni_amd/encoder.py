@@ -229,8 +229,11 @@ class HipEncoderGroup:
             self._ptr_array(type_ptrs) if type_ptrs else None, batch_total, seq, fill, self._ptr_array(out_ptrs)))
 
 
-def cosine_search(queries, corpus, k: int, mode: int = COSINE_VECTOR_STORE, device: int = 0):
+def cosine_search(queries, corpus, k: int, mode: int = COSINE_VECTOR_STORE, device: int = 0, codes: bool = False, stats=None):
     """Brute-force cosine top-k on the GPU (VectorStore::search / Segment::search_vectors).
+
+    codes=True: through an int8 plane of the corpus built for the call (kjarni_hip_cosine_search_coded_host; dim a multiple of
+    64 up to 1024) -- the same hits; `stats`, a list, then receives [pairs judged, pairs passed, candidates, fallback].
 
     Returns (idx int64 [nq, k'], score f32 [nq, k']) with k' = min(k, n_docs)."""
     queries = np.ascontiguousarray(queries, np.float32)
@@ -244,6 +247,14 @@ def cosine_search(queries, corpus, k: int, mode: int = COSINE_VECTOR_STORE, devi
     idx = np.empty((nq, k), np.int64)
     sc = np.empty((nq, k), np.float32)
     hits = C.c_int64(0)
+    if codes:
+        st = (C.c_uint64 * 4)()
+        check_error(lib().kjarni_hip_cosine_search_coded_host(
+            device, _p(queries, _ffi._f32p), nq, _p(corpus, _ffi._f32p), n, dim, mode, k,
+            _p(idx, _ffi._i64p), _p(sc, _ffi._f32p), C.byref(hits), st))
+        if stats is not None:
+            stats[:] = [int(v) for v in st]
+        return idx[:, :hits.value], sc[:, :hits.value]
     check_error(lib().kjarni_hip_cosine_search_host(
         device, _p(queries, _ffi._f32p), nq, _p(corpus, _ffi._f32p), n, dim, mode, k,
         _p(idx, _ffi._i64p), _p(sc, _ffi._f32p), C.byref(hits)))

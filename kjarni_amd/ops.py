@@ -1349,6 +1349,58 @@ def topk(scores, k: int, device: int = 0):
             L.kjarni_hip_free(device, p)
 
 
+def _device_call(device, inputs, out_shapes, call):
+    """Host arrays in, device buffers around `call(in_ptrs, out_ptrs)`, host arrays (shape, dtype) out."""
+    import ctypes as C
+    from ._ffi import check_error
+    L = lib()
+    bufs = []
+
+    def dmalloc(nbytes):
+        p = C.c_void_p()
+        check_error(L.kjarni_hip_malloc(device, max(nbytes, 16), C.byref(p)))
+        bufs.append(p)
+        return p
+    try:
+        ins = []
+        for a in inputs:
+            ins.append(dmalloc(a.nbytes))
+            check_error(L.kjarni_hip_memcpy_h2d(device, ins[-1], a.ctypes.data_as(C.c_void_p), a.nbytes))
+        outs = [np.empty(shape, dt) for shape, dt in out_shapes]
+        d_outs = [dmalloc(o.nbytes) for o in outs]
+        call(ins, d_outs)
+        check_error(L.kjarni_hip_synchronize(device))
+        for o, d in zip(outs, d_outs):
+            check_error(L.kjarni_hip_memcpy_d2h(device, o.ctypes.data_as(C.c_void_p), d, o.nbytes))
+        return outs
+    finally:
+        for p in bufs:
+            L.kjarni_hip_free(device, p)
+
+
+def cosine_scores(queries, corpus, mode: int = 0, device: int = 0):
+    """Scores [nq, n] of every corpus row against every query (kjarni_hip_cosine_scores); mode 2: the rows' squared norms."""
+    from ._ffi import check_error
+    q = np.ascontiguousarray(queries, np.float32).reshape(-1, np.shape(corpus)[1])
+    c = np.ascontiguousarray(corpus, np.float32)
+    return _device_call(device, [q, c], [((q.shape[0], c.shape[0]), np.float32)],
+                        lambda i, o: check_error(lib().kjarni_hip_cosine_scores(device, i[0], q.shape[0], i[1], c.shape[0], c.shape[1], mode,
+                                                                               o[0], None)))[0]
+
+
+def cosine_encode(rows, device: int = 0):
+    """The int8 plane of f32 rows [n, dim] (kjarni_hip_cosine_encode; dim a multiple of 64 up to 1024): codes int8 [n, dim] and
+    per row f32 {scale, residual norm rounded up, norm, 1 if the filter's rule covers the row else 0}."""
+    from ._ffi import check_error
+    x = np.ascontiguousarray(rows, np.float32)
+    n, dim = x.shape
+    total = lib().kjarni_hip_cosine_codes_bytes(n, dim)
+    if total == 0:
+        raise ValueError("dim must be a multiple of 64, at most 1024")
+    plane = _device_call(device, [x], [((total,), np.uint8)],
+                         lambda i, o: check_error(lib().kjarni_hip_cosine_encode(device, i[0], n, dim, o[0], None)))[0]
+    return plane[:n * dim].view(np.int8).reshape(n, dim), plane[total - 16 * n:].view(np.float32).reshape(n, 4)
+
 
 def score_head(hidden, W, targets, bf16=False, slab_tiles=0, fused=True, device=0):
     """The scoring head kernels alone (kjarni_hip_op_score_head): hidden f32 [m, k] (final-normed rows), W [vocab, k] f32, or

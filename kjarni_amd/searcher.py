@@ -112,6 +112,21 @@ def rrf_fuse(keyword_ids, semantic_ids, limit: int):
     return [(int(ids[i]), float(sc[i])) for i in range(n.value)]
 
 
+def set_index_codes(on: bool) -> None:
+    """Process-wide switch (off by default): index images also get an int8 plane and one-query scans go through it
+    (kjarni_hip_set_index_codes)."""
+    lib().kjarni_hip_set_index_codes(1 if on else 0)
+
+
+def index_codes() -> bool:
+    return bool(lib().kjarni_hip_index_codes())
+
+
+def index_image_bytes() -> int:
+    """Device bytes held by the index images of every live searcher (rows + int8 planes)."""
+    return int(lib().kjarni_hip_index_image_bytes())
+
+
 def set_keyword_parallel_min_docs(docs: int) -> None:
     """Index size from which BM25 walks the segments on several host threads (kjarni_hip_set_keyword_parallel_min_docs)."""
     lib().kjarni_hip_set_keyword_parallel_min_docs(docs)

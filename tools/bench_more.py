@@ -373,6 +373,46 @@ def main():
             del corpus
             torch.cuda.empty_cache()
 
+    if "search_coded" in which:   # (on request) the int8-plane search against kjarni_hip_cosine_search of the same build, in turn;
+        # for the parent commit's library run its own bench_more.py scan leg on the same machine and compare ms_search_one_call
+        import ctypes as C
+        dim, k = 384, 10
+        for n in (1_000_000, 10_000_000):
+            g = torch.Generator(device=dev).manual_seed(2)
+            corpus = torch.randn((n, dim), generator=g, device=dev, dtype=torch.float32)
+            plane = torch.empty(L.kjarni_hip_cosine_codes_bytes(n, dim), dtype=torch.uint8, device=dev)
+
+            def encode():
+                _ffi.check_error(L.kjarni_hip_cosine_encode(0, corpus.data_ptr(), n, dim, plane.data_ptr(), stream()))
+            t_enc = timed(encode, sync, 3, 1)
+            for nq in (1, 64):
+                q = torch.randn((nq, dim), generator=g, device=dev, dtype=torch.float32)
+                idx = torch.empty((2, nq, k), dtype=torch.int64, device=dev)
+                sc = torch.empty((2, nq, k), dtype=torch.float32, device=dev)
+                ws = torch.empty(L.kjarni_hip_cosine_search_coded_workspace_bytes(nq, n, dim, k), dtype=torch.uint8, device=dev)
+                st = (C.c_uint64 * 4)()
+
+                def coded():
+                    _ffi.check_error(L.kjarni_hip_cosine_search_coded(0, q.data_ptr(), nq, corpus.data_ptr(), n, dim, 1, k, plane.data_ptr(),
+                                                                      ws.data_ptr(), idx[0].data_ptr(), sc[0].data_ptr(), st, stream()))
+
+                def plain():
+                    _ffi.check_error(L.kjarni_hip_cosine_search(0, q.data_ptr(), nq, corpus.data_ptr(), n, dim, 1, k, ws.data_ptr(),
+                                                                idx[1].data_ptr(), sc[1].data_ptr(), stream()))
+                steps = 20 if n <= 1_000_000 else 5
+                rounds = [(timed(coded, sync, steps, 2), timed(plain, sync, steps, 2)) for _ in range(3)]   # in turn, best of three
+                t_c, t_p = min(r[0] for r in rounds), min(r[1] for r in rounds)
+                emit({"metric": "ms per cosine search through the int8 plane, top-10 (dim 384)", "value": round(t_c * 1e3, 4), "unit": "ms",
+                      "n_gpus": 1, "dtype": "int8 filter + f32 rescoring", "data": "synthetic",
+                      "config": {"workload": f"corpus [{n}, 384] Gaussian rows and their plane resident in HBM, {nq} quer{'y' if nq == 1 else 'ies'}, k=10"},
+                      "ms_search_same_build": round(t_p * 1e3, 4), "speedup": round(t_p / t_c, 3), "stats": [int(v) for v in st],
+                      "same_indices": bool(torch.equal(idx[0], idx[1])), "max_score_diff": float((sc[0] - sc[1]).abs().max()),
+                      "ms_encode_per_1e6_rows": round(t_enc * 1e3 * 1e6 / n, 4),
+                      "filter_bytes": n * dim + 16 * n, "corpus_bytes": n * dim * 4})
+                del ws, idx, sc, q
+            del corpus, plane
+            torch.cuda.empty_cache()
+
     if "strings" in which:
         rng = np.random.default_rng(0)
         vocab = json.load(open(os.path.join(emb_dir, "tokenizer.json")))["model"]["vocab"]
