@@ -912,11 +912,19 @@ void kjarni_hip_chat_verify_gemv_calls(KjarniChat* chat, uint64_t* streamed, uin
  * work, the message names the argument. */
 KjarniErrorCode kjarni_hip_decoder_score(KjarniHipDecoder* decoder, const uint32_t* ids, int32_t n, int32_t first, float* logprob_out,
                                          uint32_t* top_out, float* top_logprob_out);
-void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* decoder, int32_t on);   /* default on; 0: every checkpoint takes the rows route */
-/* Head launches of kjarni_hip_decoder_score by route since load (zeros on NULL). */
+/* 1 (the default): the fused route as above.  0: every checkpoint takes the rows route.  2: a bf16 head (bf16 and FP8 checkpoints,
+ * hidden a multiple of 32) runs on the bf16 matrix cores instead -- the bf16 weights are the operands as they are, the f32 hidden
+ * states enter as three exact bf16 pieces, products exact and sums f32: the fused route's arithmetic in another summation order;
+ * every other checkpoint does exactly what 1 does.  Any other value is taken as 1. */
+void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* decoder, int32_t on);
+/* Head launches of kjarni_hip_decoder_score by route since load (zeros on NULL): the f32 matrix-core head and the rows route; the
+ * launches of the bf16 matrix-core head (set_score_fused(2)) are counted apart, by kjarni_hip_decoder_score_bf16_calls (0 on NULL). */
 void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* decoder, uint64_t* fused, uint64_t* rows);
+uint64_t kjarni_hip_decoder_score_bf16_calls(const KjarniHipDecoder* decoder);
 /* The head kernels alone, host pointers (as kjarni_hip_op_linear_ggml): hidden f32 [m, k]; W [vocab, k] f32 (bf16 = 0) or
- * bf16 bits (bf16 = 1); targets [m]; slab_tiles 0 = automatic; fused 0 = the rows route (materialised in 8-row blocks).
+ * bf16 bits (bf16 = 1); targets [m]; slab_tiles 0 = automatic; fused 0 = the rows route (materialised in 8-row blocks), 1 = the
+ * f32 matrix-core head, 2 = the bf16 matrix-core head (bf16 = 1 only); fused 1 and 2 need k % 32 == 0.  fused outside 0..2, or 2
+ * with bf16 = 0: INVALID_CONFIG naming the argument, before any GPU work.
  * Outputs [m] each, any may be NULL: log-probability of the target, arg-max, its log-probability, the row's log-sum-exp. */
 KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const float* hidden, int64_t m, int32_t k, const void* W, int32_t bf16,
                                          int32_t vocab, const uint32_t* targets, int32_t slab_tiles, int32_t fused, float* logprob_out,

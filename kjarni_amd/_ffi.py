@@ -574,6 +574,7 @@ SIGNATURES = {
     "kjarni_hip_decoder_score": (c_int32, [c_void_p, _u32p, c_int32, c_int32, _f32p, _u32p, _f32p]),
     "kjarni_hip_decoder_set_score_fused": (None, [c_void_p, c_int32]),
     "kjarni_hip_decoder_score_calls": (None, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "kjarni_hip_decoder_score_bf16_calls": (c_uint64, [c_void_p]),
     "kjarni_hip_op_score_head": (c_int32, [c_int32, _f32p, c_int64, c_int32, c_void_p, c_int32, c_int32, _u32p, c_int32, c_int32, _f32p,
                                            _u32p, _f32p, _f32p]),
     "kjarni_generator_score": (c_int32, [c_void_p, c_char_p, c_char_p, POINTER(KjarniScoreResult)]),

@@ -858,7 +858,12 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_decoder_score_topk(KjarniHipDecoder* d,
 
 KJARNI_EXPORT void kjarni_hip_decoder_set_score_fused(KjarniHipDecoder* d, int32_t on)
 {
-    if (d) d->model->set_score_fused(on != 0);
+    if (d) d->model->set_score_fused(on == 0 || on == 2 ? on : 1);
+}
+
+KJARNI_EXPORT uint64_t kjarni_hip_decoder_score_bf16_calls(const KjarniHipDecoder* d)
+{
+    return d ? d->model->score_bf16_calls() : 0;
 }
 
 KJARNI_EXPORT void kjarni_hip_decoder_score_calls(const KjarniHipDecoder* d, uint64_t* fused, uint64_t* rows)

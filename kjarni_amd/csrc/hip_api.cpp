@@ -2935,6 +2935,8 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const flo
     return guarded(KJARNI_ERROR_INFERENCE_FAILED, [&] {
         if (m < 0 || m > (1 << 20) || k <= 0 || vocab <= 0 || slab_tiles < 0 || (bf16 != 0 && bf16 != 1))
             throw InvalidConfig("invalid score head dimensions");
+        if (fused < 0 || fused > 2) throw InvalidConfig("fused (" + std::to_string(fused) + ") must be 0, 1 or 2");
+        if (fused == 2 && !bf16) throw InvalidConfig("fused = 2 (the bf16 matrix-core head) needs bf16 = 1");
         if (fused ? k % 32 != 0 : k % 8 != 0) throw InvalidConfig(fused ? "the fused score head needs k % 32 == 0" : "the rows route needs k % 8 == 0");
         for (int64_t r = 0; r < m; ++r)
             if (targets[r] >= (uint32_t)vocab) throw InvalidConfig("targets[" + std::to_string(r) + "] is not below vocab");
@@ -2951,7 +2953,10 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head(int32_t device, const flo
         uint32_t* TP = static_cast<uint32_t*>(tp.p);
         if (fused) {
             DeviceBuf scratch(score_head_scratch_bytes((int)m, vocab, slab_tiles));
-            hip_check(launch_score_head(X, k, (int)m, wd.p, bf16, vocab, k, T, slab_tiles, scratch.p, LP, TP, TL, LS, nullptr), "score head");
+            if (fused == 2)
+                hip_check(launch_score_head_bf16(X, k, (int)m, wd.p, vocab, k, T, slab_tiles, scratch.p, LP, TP, TL, LS, nullptr), "bf16 score head");
+            else
+                hip_check(launch_score_head(X, k, (int)m, wd.p, bf16, vocab, k, T, slab_tiles, scratch.p, LP, TP, TL, LS, nullptr), "score head");
             hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         } else {
             DeviceBuf logits((size_t)8 * vocab * 4);
@@ -2983,6 +2988,8 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, cons
         if (top_k < 1 || top_k > KJARNI_SCORE_TOPK_MAX || top_k > vocab)
             throw InvalidConfig("top_k (" + std::to_string(top_k) + ") must be in [1, " + std::to_string(KJARNI_SCORE_TOPK_MAX) +
                                 "] and not above vocab (" + std::to_string(vocab) + ")");
+        if (fused < 0 || fused > 2) throw InvalidConfig("fused (" + std::to_string(fused) + ") must be 0, 1 or 2");
+        if (fused == 2 && !bf16) throw InvalidConfig("fused = 2 (the bf16 matrix-core head) needs bf16 = 1");
         if (fused ? k % 32 != 0 : k % 8 != 0) throw InvalidConfig(fused ? "the fused score head needs k % 32 == 0" : "the rows route needs k % 8 == 0");
         for (int64_t r = 0; r < m; ++r)
             if (targets[r] >= (uint32_t)vocab) throw InvalidConfig("targets[" + std::to_string(r) + "] is not below vocab");
@@ -2999,8 +3006,12 @@ KJARNI_EXPORT KjarniErrorCode kjarni_hip_op_score_head_topk(int32_t device, cons
         uint32_t* TI = static_cast<uint32_t*>(ti.p);
         if (fused) {
             DeviceBuf scratch(score_head_topk_scratch_bytes((int)m, vocab, slab_tiles, top_k));
-            hip_check(launch_score_head_topk(X, k, (int)m, wd.p, bf16, vocab, k, T, slab_tiles, top_k, scratch.p, LP, TI, TL, LS, nullptr),
-                      "score head top-k");
+            if (fused == 2)
+                hip_check(launch_score_head_bf16_topk(X, k, (int)m, wd.p, vocab, k, T, slab_tiles, top_k, scratch.p, LP, TI, TL, LS, nullptr),
+                          "bf16 score head top-k");
+            else
+                hip_check(launch_score_head_topk(X, k, (int)m, wd.p, bf16, vocab, k, T, slab_tiles, top_k, scratch.p, LP, TI, TL, LS, nullptr),
+                          "score head top-k");
             hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         } else {
             DeviceBuf logits((size_t)8 * vocab * 4);

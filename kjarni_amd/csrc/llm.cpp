@@ -1698,6 +1698,20 @@ void LlmModel::score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, 
 {
     const LlmConfig& c = cfg_;
     const int H = c.hidden;
+    if (score_fused_ == 2 && (!quant_ || fp8_) && bf16_ && llm_score_head_bf16_takes(Xn, H, lm_head_, H)) {  // (the f32 head's scratch sizes)
+        if (k > 0) {
+            if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, k) > score_tk_scratch_bytes_)
+                throw std::runtime_error("score head: top-k slab scratch too small");
+            hip_check(launch_score_head_bf16_topk(Xn, H, cnt, lm_head_, c.vocab, H, tgt, 0, k, score_tk_scratch_, lp, ids, tlp, nullptr, stream_),
+                      "bf16 score head top-k");
+        } else {
+            if (score_head_scratch_bytes(cnt, c.vocab, 0) > score_scratch_bytes_) throw std::runtime_error("score head: slab scratch too small");
+            hip_check(launch_score_head_bf16(Xn, H, cnt, lm_head_, c.vocab, H, tgt, 0, score_scratch_, lp, ids, tlp, nullptr, stream_),
+                      "bf16 score head");
+        }
+        ++score_bf16_calls_;
+        return;
+    }
     if (score_fused_ && (!quant_ || fp8_) && llm_score_head_takes(Xn, H, lm_head_, bf16_ ? 1 : 0, H)) {
         if (k > 0) {
             if (score_head_topk_scratch_bytes(cnt, c.vocab, 0, k) > score_tk_scratch_bytes_)

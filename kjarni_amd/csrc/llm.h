@@ -224,10 +224,13 @@ public:
     // the larger id first), slot 0 what score() returns as top / top_logprob.  Same sink, routes, chunks, prefix reuse, counters
     // and final state as score(); logprob_out is bit-identical to score()'s.  Any output may be null.
     void score_topk(const uint32_t* ids, int n, int first, int top_k, float* logprob_out, uint32_t* topk_ids_out, float* topk_logprob_out);
-    void set_score_fused(bool on) { score_fused_ = on; }
+    // 0: the rows route; 1 (the default): the f32 matrix-core head; 2: the bf16 matrix-core head (launch_score_head_bf16) where the
+    // head is bf16 (FP8 checkpoints included) and llm_score_head_bf16_takes, else exactly what 1 does.
+    void set_score_fused(int mode) { score_fused_ = mode; }
     // Head launches of score() by route since load.
     uint64_t score_fused_calls() const { return score_fused_calls_; }
     uint64_t score_rows_calls() const { return score_rows_calls_; }
+    uint64_t score_bf16_calls() const { return score_bf16_calls_; }
     // ---- embedding: last-token pooling over a packed batch ---------------------------------------------------------------------
     // Sequence b is ids[offsets[b], offsets[b + 1]); out[b, :] = the final-normed hidden state of its last token, L2-normalised
     // when `normalize` (x / ||x|| when ||x|| > 0).  The sequences are packed, in order, into chunks of at most 2 048 rows
@@ -618,8 +621,9 @@ private:
     // score()'s result rows, then score_head()
     void score_head_rows(const float* Xn, int lo, int cnt);
     // The vocabulary head of score(), score_topk() and score_batch() over cnt final-normed rows Xn [cnt, hidden] against tgt [cnt]:
-    // the fused slab head where llm_score_head_takes (f32 / bf16 heads, unless set_score_fused(false)), else 8 rows at a time
-    // through vlogits_ (quantized heads: qlinear) and the rows kernels; counted in score_fused_calls_ / score_rows_calls_.
+    // the fused slab head where llm_score_head_takes (f32 / bf16 heads, unless set_score_fused(0); under set_score_fused(2) bf16
+    // heads take the bf16 matrix-core form of it), else 8 rows at a time through vlogits_ (quantized heads: qlinear) and the rows
+    // kernels; counted in score_fused_calls_ / score_bf16_calls_ / score_rows_calls_.
     // k == 0: the plain kernels, ids / tlp [cnt] the arg-max and its log-probability; k >= 1: the top-k kernels, ids / tlp [cnt, k].
     void score_head(const float* Xn, int cnt, const uint32_t* tgt, int k, float* lp, uint32_t* ids, float* tlp);
     void enqueue_argmax(bool record);
@@ -865,8 +869,8 @@ private:
     float* score_tk_lp_ = nullptr;
     void* score_tk_scratch_ = nullptr;
     size_t score_tk_scratch_bytes_ = 0;
-    bool score_fused_ = true;
-    uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0;
+    int score_fused_ = 1;  // set_score_fused
+    uint64_t score_fused_calls_ = 0, score_rows_calls_ = 0, score_bf16_calls_ = 0;
     // prefix reuse: the tokens of the cache rows (host only), the switch, the counters
     std::vector<uint32_t> resident_;
     bool prefix_reuse_ = false;

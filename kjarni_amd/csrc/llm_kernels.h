@@ -248,6 +248,16 @@ size_t score_head_topk_scratch_bytes(int m, int vocab, int slab_tiles, int top_k
 hipError_t launch_score_head_topk(const float* X, int64_t ldx, int m, const void* W, int bf16, int vocab, int k, const uint32_t* targets,
                                   int slab_tiles, int top_k, void* scratch, float* logprob, uint32_t* topk_ids, float* topk_logprob, float* lse,
                                   hipStream_t stream);
+// The same two launches with the head on the bf16 matrix cores (score_head_bf16.hip: llm_score_head_bf16_kernel, then the merge
+// kernels above): W [vocab, k] bf16 only, read as it is; X split into three exact bf16 planes, three bf16 MFMAs per 16 columns
+// of k, f32 sums -- the f32 head's arithmetic in another summation order.  Same slab_tiles, scratch sizes and scratch layout.
+// Needs k % 32 == 0, ldx % 4 == 0 and 16-byte aligned X and W (llm_score_head_bf16_takes).
+bool llm_score_head_bf16_takes(const float* X, int64_t ldx, const void* W, int k);
+hipError_t launch_score_head_bf16(const float* X, int64_t ldx, int m, const void* W, int vocab, int k, const uint32_t* targets, int slab_tiles,
+                                  void* scratch, float* logprob, uint32_t* top, float* top_logprob, float* lse, hipStream_t stream);
+hipError_t launch_score_head_bf16_topk(const float* X, int64_t ldx, int m, const void* W, int vocab, int k, const uint32_t* targets,
+                                       int slab_tiles, int top_k, void* scratch, float* logprob, uint32_t* topk_ids, float* topk_logprob,
+                                       float* lse, hipStream_t stream);
 // The rows route: the same outputs from up to 8 materialised logits rows [rows, ld] (llm_score_rows_kernel).
 hipError_t launch_score_rows(const float* logits, int64_t ld, int rows, int vocab, const uint32_t* targets, float* logprob, uint32_t* top,
                              float* top_logprob, float* lse, hipStream_t stream);

@@ -14,6 +14,7 @@
 #include "dynamic_lds.h"
 #include "llm_kernels.h"
 #include "kernels.h"
+#include "score_head_common.h"
 
 namespace kjarni {
 
@@ -965,13 +966,7 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const uint32_t* __restri
     }
 }
 
-__device__ __forceinline__ unsigned long long argmax_key(float v, int idx)
-{
-    uint32_t u = v == 0.0f ? 0u : __float_as_uint(v);  // -0.0 == +0.0 (partial_cmp): one key for both, the later index wins
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // larger float -> larger uint
-    if (v != v) u = 0;                               // NaN lowest
-    return ((unsigned long long)u << 32) | (uint32_t)idx;  // equal values: the LAST index wins (Iterator::max_by)
-}
+// (argmax_key: score_head_common.h)
 
 // The largest key of the wave, in every lane (butterfly).
 __device__ __forceinline__ unsigned long long wave_max_key(unsigned long long key)
@@ -2930,56 +2925,9 @@ hipError_t launch_lookup_pick(const float* logits, int64_t ld, int vocab, int ro
 
 namespace {
 
-constexpr int SC_BM = 64, SC_BN = 64, SC_BK = 32, SC_STRIDE = SC_BK + 4;
+constexpr int SC_BK = 32, SC_STRIDE = SC_BK + 4;  // (SC_BM, SC_BN: score_head_common.h)
 
-// What one slab of vocabulary tiles knows about one row.
-struct ScorePartial {
-    unsigned long long key;  // argmax_key of the slab's best logit (0: nothing seen)
-    float mx;                // the slab's maximum
-    float sm;                // sum of exp(x - mx) over the slab
-    float tgt;               // the target's logit where the target lies in the slab, else 0
-    float pad;
-};
-
-__device__ __forceinline__ float argmax_key_value(unsigned long long key)
-{
-    const uint32_t u = (uint32_t)(key >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
-
-// (mx, sm) += (omx, osm): sums of exp(x - mx) brought to the common maximum.
-__device__ __forceinline__ void score_combine(float& mx, float& sm, float omx, float osm)
-{
-    const float m = fmaxf(mx, omx);
-    if (m == -INFINITY) return;  // both empty
-    sm = sm * expf(mx - m) + osm * expf(omx - m);
-    mx = m;
-}
-
-// Top-k lists: TOPK argmax_keys in descending order, every index static so that the list lives in registers; 0 marks an empty
-// slot.  Keys of different columns differ, so "the TOPK largest keys" is one set whatever the order of the insertions.
-constexpr int SC_TOPK = KJARNI_SCORE_TOPK_MAX;
-
-template <int TOPK>
-__device__ __forceinline__ void topk_insert(unsigned long long (&lst)[TOPK], unsigned long long kk)
-{
-    if (kk > lst[TOPK - 1]) {  // the one compare of the common path
-#pragma unroll
-        for (int j = TOPK - 1; j > 0; --j) lst[j] = kk > lst[j - 1] ? lst[j - 1] : (kk > lst[j] ? kk : lst[j]);
-        lst[0] = kk > lst[0] ? kk : lst[0];
-    }
-}
-
-// lst = the TOPK largest of lst and the list lane ^ off holds; every lane of a pair ends with the same list.
-template <int TOPK>
-__device__ __forceinline__ void topk_merge_lane(unsigned long long (&lst)[TOPK], int off)
-{
-    unsigned long long o[TOPK];
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) o[j] = __shfl_xor(lst[j], off, kWave);
-#pragma unroll
-    for (int j = 0; j < TOPK; ++j) topk_insert(lst, o[j]);
-}
+// (ScorePartial, score_combine, argmax_key_value and the top-k lists: score_head_common.h)
 
 // Eight consecutive weights of a row as two f32x4 (bf16 widened).
 __device__ __forceinline__ void score_load_w(const float* p, f32x4& a, f32x4& b)
@@ -3349,6 +3297,22 @@ hipError_t launch_score_head(const float* X, int64_t ldx, int m, const void* W, 
                            k, m_tiles, st, n_tiles, slabs, P);
     hipLaunchKernelGGL(llm_score_merge_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, P, targets, m, vocab, slabs, st, logprob, top,
                        top_logprob, lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_merge(const ScorePartial* P, const uint32_t* targets, int m, int vocab, int slabs, int slab_tiles, float* logprob,
+                              uint32_t* top, float* top_logprob, float* lse, hipStream_t stream)
+{
+    hipLaunchKernelGGL(llm_score_merge_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, P, targets, m, vocab, slabs, slab_tiles,
+                       logprob, top, top_logprob, lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_topk_merge(const unsigned long long* PK, const float* lse, int m, int slabs, int top_k, uint32_t* topk_ids,
+                                   float* topk_logprob, hipStream_t stream)
+{
+    hipLaunchKernelGGL(llm_score_topk_merge_kernel<SC_TOPK>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, PK, lse, m, slabs, top_k,
+                       topk_ids, topk_logprob);
     return hipGetLastError();
 }
 

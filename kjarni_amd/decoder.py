@@ -761,16 +761,21 @@ class HipDecoder:
         check_error(lib().kjarni_hip_decoder_score_topk(self._h, u32(a), a.size, int(first), int(top_k), f(lp), u32(tid), f(tlp)))
         return lp, tid, tlp
 
-    def set_score_fused(self, on: bool):
-        """On (the default): f32 / bf16 heads are scored on the matrix cores without storing the logits; off: every checkpoint
-        takes the rows route (8 materialised logits rows at a time)."""
-        lib().kjarni_hip_decoder_set_score_fused(self._h, 1 if on else 0)
+    def set_score_fused(self, on):
+        """1 / True (the default): f32 / bf16 heads are scored on the f32 matrix cores without storing the logits; 0 / False: every
+        checkpoint takes the rows route (8 materialised logits rows at a time); 2: bf16 heads are scored on the bf16 matrix cores
+        (bf16 weights as they are, hidden states as three exact bf16 pieces), every other checkpoint as under 1."""
+        lib().kjarni_hip_decoder_set_score_fused(self._h, int(on))
 
     def score_calls(self):
         """(fused, rows): head launches of score() by route since load."""
         a, b = C.c_uint64(), C.c_uint64()
         lib().kjarni_hip_decoder_score_calls(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
+
+    def score_bf16_calls(self) -> int:
+        """Head launches of score() on the bf16 matrix cores (set_score_fused(2)) since load; not part of score_calls()."""
+        return int(lib().kjarni_hip_decoder_score_bf16_calls(self._h))
 
     # ---- scoring many sequences in one packed pass ----
     def score_batch(self, seqs: Sequence[Sequence[int]], firsts: Sequence[int], top_k: int = 1):

@@ -1405,8 +1405,9 @@ def cosine_encode(rows, device: int = 0):
 def score_head(hidden, W, targets, bf16=False, slab_tiles=0, fused=True, device=0):
     """The scoring head kernels alone (kjarni_hip_op_score_head): hidden f32 [m, k] (final-normed rows), W [vocab, k] f32, or
     with bf16=True its bf16 bits (uint16); targets [m].  Returns (logprob f32 [m], top u32 [m], top_logprob f32 [m], lse f32 [m]).
-    fused: the matrix-core kernel that never stores the logits (slab_tiles 64-wide vocabulary tiles per workgroup, 0 =
-    automatic); else the rows route over logits materialised 8 rows at a time."""
+    fused 1 / True: the f32 matrix-core kernel that never stores the logits (slab_tiles 64-wide vocabulary tiles per workgroup, 0 =
+    automatic); 2: the same on the bf16 matrix cores (bf16=True only); 0 / False: the rows route over logits materialised 8 rows
+    at a time."""
     import ctypes as C
     from ._ffi import check_error
     hidden = np.ascontiguousarray(hidden, np.float32)
@@ -1420,7 +1421,7 @@ def score_head(hidden, W, targets, bf16=False, slab_tiles=0, fused=True, device=
     f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
     check_error(lib().kjarni_hip_op_score_head(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab, u32(targets),
-                                               slab_tiles, 1 if fused else 0, f(lp), u32(top), f(tlp), f(lse)))
+                                               slab_tiles, int(fused), f(lp), u32(top), f(tlp), f(lse)))
     return lp, top, tlp, lse
 
 
@@ -1443,7 +1444,7 @@ def score_head_topk(hidden, W, targets, top_k, bf16=False, slab_tiles=0, fused=T
     f = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))  # noqa: E731
     check_error(lib().kjarni_hip_op_score_head_topk(device, f(hidden), m, k, W.ctypes.data_as(C.c_void_p), 1 if bf16 else 0, vocab,
-                                                    u32(targets), slab_tiles, 1 if fused else 0, int(top_k), f(lp), u32(tid), f(tlp), f(lse)))
+                                                    u32(targets), slab_tiles, int(fused), int(top_k), f(lp), u32(tid), f(tlp), f(lse)))
     return lp, tid, tlp, lse
 
 

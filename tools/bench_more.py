@@ -98,7 +98,10 @@ One JSON line per measurement (1 GPU; the N > 1 driver is bench.py):
            shape (bf16) and gpt2-small (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused route (the head on the
            matrix cores, no logits stored) and on the rows route (8 materialised logits rows at a time); medians of runs that
            end in a synchronise; the head's added time score - forward per route.
-           KJARNI_SCORE_TRACE=N: N fused score() calls of the 2 048-token prompt on the Llama shape only (for a kernel trace).
+           On the Llama shape score() under set_score_fused(2), the head on the bf16 matrix cores, joins the alternation: its added
+           time next to the fused route's of the same build; those lines also go to profiles/llm_score_bf16_bench.jsonl.
+           KJARNI_SCORE_TRACE=N: N score() calls of the 2 048-token prompt under set_score_fused(1) and N under (2) on the Llama
+           shape only (for a kernel trace).
   llm_score_topk  (only on request) HipDecoder.score_topk() at top_k = 1 and 8 against score() of the same ids in one process,
            alternated twice: Llama-3.2-1B shape (bf16), prompts of 128 and 2 048 tokens, first = 1, on the fused and on the rows
            route; medians of runs that end in a synchronise; the ratio score_topk / score per case.  One line per (length,
@@ -1782,8 +1785,9 @@ def main():
     if "llm_score" in which:
         # Method (measuring guide, section 5; as llm_lookup): one process on one box; forward() -- the yardstick --, score() on
         # the fused route and score() on the rows route are warmed first, then alternated twice; every run ends in a
-        # synchronise (forward() and score() return after one), medians over the runs.  KJARNI_SCORE_TRACE=N: N fused score()
-        # calls of the 2 048-token prompt on the Llama shape only (for a kernel trace of its own).
+        # synchronise (forward() and score() return after one), medians over the runs.  bf16_head: set_score_fused(2) is a
+        # fourth leg of the same alternation.  KJARNI_SCORE_TRACE=N: N score() calls of the 2 048-token prompt under setting 1 and
+        # N under setting 2, on the Llama shape only (for a kernel trace of its own).
         from tests import gpt2_fixture
         rng = np.random.default_rng(0)
         trace_calls = int(os.environ.get("KJARNI_SCORE_TRACE", "0"))
@@ -1794,11 +1798,13 @@ def main():
             fn()
             return (time.perf_counter() - t0) * 1e3
 
-        def measure(label, dec, vocab, lo, dtype):
+        def measure(label, dec, vocab, lo, dtype, bf16_head=False):
             prompts = {n: rng.integers(lo, vocab, n).tolist() for n in LENS}
             if trace_calls:
-                for _ in range(trace_calls):
-                    dec.score(prompts[2048])
+                for setting in (1, 2):
+                    dec.set_score_fused(setting)
+                    for _ in range(trace_calls):
+                        dec.score(prompts[2048])
                 return
 
             def fwd(ids):
@@ -1812,13 +1818,19 @@ def main():
                 fwd(prompts[n])
                 score(prompts[n], True)
                 score(prompts[n], False)
-            runs = {(kind, n): [] for kind in ("forward", "fused", "rows") for n in LENS}
+                if bf16_head:
+                    score(prompts[n], 2)
+            kinds = ("forward", "fused", "rows") + (("bf16",) if bf16_head else ())
+            runs = {(kind, n): [] for kind in kinds for n in LENS}
             for rep in range(2):
                 for n in LENS:
                     for _ in range(3):
                         runs[("forward", n)].append(run_ms(lambda: fwd(prompts[n])))
                         runs[("fused", n)].append(run_ms(lambda: score(prompts[n], True)))
                         runs[("rows", n)].append(run_ms(lambda: score(prompts[n], False)))
+                        if bf16_head:
+                            runs[("bf16", n)].append(run_ms(lambda: score(prompts[n], 2)))
+            assert not bf16_head or dec.score_bf16_calls() > 0
             dec.set_score_fused(True)
             med = lambda xs: float(np.median(xs))  # noqa: E731
             out = {}
@@ -1828,18 +1840,32 @@ def main():
                                "head_added_fused_ms": round(a - f, 3), "head_added_rows_ms": round(b - f, 3),
                                "rows_over_fused_added": round((b - f) / (a - f), 2) if a > f else None,
                                "head_gflop": round(2.0 * (n - 1) * vocab * dec.hidden / 1e9, 2),
-                               "runs": {k: [round(x, 3) for x in runs[(k, n)]] for k in ("forward", "fused", "rows")}}
+                               "runs": {k: [round(x, 3) for x in runs[(k, n)]] for k in kinds}}
+                if bf16_head:
+                    c = med(runs[("bf16", n)])
+                    out[str(n)].update({"score_bf16_ms": round(c, 3), "head_added_bf16_ms": round(c - f, 3),
+                                        "fused_over_bf16_added": round((a - f) / (c - f), 2) if c > f else None})
             emit({"metric": f"scoring, {label}", "unit": "ms added by the head at 2048 tokens (fused)", "value": out["2048"]["head_added_fused_ms"],
                   "n_gpus": 1, "dtype": dtype, "data": "synthetic",
                   "config": {"workload": f"{label}, random init; forward() of a 128- and a 2 048-token prompt against score() of the same ids "
                                          "(first = 1) on the fused and on the rows route, alternated twice in one process, medians of 6 runs, "
                                          "every run ends in a synchronise"},
                   "lengths": out, "weight_bytes": dec.weight_bytes})
+            if bf16_head:
+                with open(os.path.join(ROOT, "profiles", "llm_score_bf16_bench.jsonl"), "w") as fh:
+                    for n in LENS:
+                        o = out[str(n)]
+                        fh.write(json.dumps({"metric": f"scoring head, set_score_fused(2) against (1), {label}, {n} tokens",
+                                             "value": o["fused_over_bf16_added"], "unit": "ratio of the heads' added ms, setting 1 / setting 2",
+                                             "n_gpus": 1, "dtype": dtype, "data": "synthetic", "tokens": n,
+                                             "config": {"workload": "random init; forward() and score() (first = 1) under set_score_fused(1), "
+                                                                    "(0) and (2), alternated twice in one process, medians of 6 runs, every "
+                                                                    "run ends in a synchronise"}, **o}) + "\n")
 
         d = os.path.join(tmp, "llama-1b-score")
         synth.llm_model(d, synth.LLAMA_1B, seed=0, store_bf16=True, max_position_embeddings=4096, eos_token_id=[])
         dec = kjarni_amd.HipDecoder(d, max_context=2048)
-        measure("Llama-3.2-1B shape, bf16 weights", dec, 100000, 1000, "bf16 weights, f32 activations/accumulate/KV")
+        measure("Llama-3.2-1B shape, bf16 weights", dec, 100000, 1000, "bf16 weights, f32 activations/accumulate/KV", bf16_head=True)
         del dec
         if not trace_calls:  # (the trace run is the Llama shape alone)
             gcfg = gpt2_fixture.gpt2_config(n_embd=768, n_layer=12, n_head=12, n_ctx=2048, vocab_size=50257, eos_token_id=None)
